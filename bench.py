@@ -4,10 +4,11 @@ HBM roofline (BASELINE.json).  One "step" = one full Matsuno step (predictor +
 corrector, every prognostic field read once and written once) over the whole grid.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|c5_phys...] [--only]
+                  [--dump-outputs DIR]
 
-The timed region is a block of EXACTLY K steps between barrier + synchronize fences; the block is
-repeated until at least MIN_TIMED_S seconds have been timed and the MEDIAN block is reported
-(`ms_per_step`, `value`), with the fastest and slowest block beside it (`ms_per_step_min/max`).
+The timed region is EXACTLY K steps between barrier + synchronize fences (`ms_per_step`, `value`).
+The untimed steps before it leave the same state in every run, so with the same arguments the last
+timed step computes the same state; --dump-outputs DIR writes that state as DIR/<field>.npy.
 
 The headline workload is c3 (BASELINE configs[2], 4096x2048 shallow water + theta +
 viscosity + van-Leer tracer, fp64).  N > 1 is launched by torch.distributed.run, one rank
@@ -32,8 +33,8 @@ HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 L2_PEAK_GBS = 34500.0     # aggregate L2 read rate, 8 XCDs x 4 MiB (MI355X_MICROARCH.md, L2 section)
 L2_BYTES = 32 * 2 ** 20
 SETTLE_S = float(os.environ.get("GCM_BENCH_SETTLE_S", "0.15"))   # untimed pre-conditioning before warm-up (see run_workload)
-MIN_TIMED_S = float(os.environ.get("GCM_BENCH_MIN_TIMED_S", "0.5"))   # the K-step block is repeated until this much is timed
-MAX_BLOCKS = 400
+SETTLE_STEPS_PE = 64      # the GCM_PE25D workloads' pre-conditioning: a number of steps, not a time (see run_workload)
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together stay below this
 PROFILE_ROUND = "r04"     # profiles/<round>/traffic.json: PMC passes of this same command (tools/tools_prof.sh)
 
 WORKLOADS = {
@@ -150,6 +151,22 @@ def cpu_baseline(name):
                       % (nst, W, H, el, os.cpu_count())}
 
 
+def write_outputs(outdir, arrays, dtype):
+    """arrays (name -> global field) as outdir/<name>.npy in `dtype`.  When the whole set would exceed DUMP_BYTES,
+    every field is written as a 1-D sample instead: its elements at sorted flat (C-order) positions drawn with a
+    fixed seed, a share of the budget proportional to the field's size -- the same positions in every run."""
+    itemsize = np.dtype(dtype).itemsize
+    total = sum(a.size for a in arrays.values())
+    cap = (DUMP_BYTES - 4096 * len(arrays)) // itemsize          # (4 KiB per file for the .npy header)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if total > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, a.size * cap // total))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a.astype(dtype))
+
+
 class Ctx:
     """process-wide handles: torch, dist, ranks"""
 
@@ -163,8 +180,9 @@ def halo_steps_for(name, world):
     return 4 if world == 2 else 8
 
 
-def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kernel=True):
-    """-> dict(value, ms_per_step, [roofline]) measured on `world` ranks (default: all)"""
+def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kernel=True, dump=None):
+    """-> dict(value, ms_per_step, [roofline]) measured on `world` ranks (default: all); `dump`: a directory for the
+    state the last timed step computed (write_outputs, rank 0)"""
     import gcmiipy_amd as g
     from gcmiipy_amd import _lib, geometry
     from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange, split_rows
@@ -214,6 +232,7 @@ def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kern
         # non-finite after ~1100 (c3) / ~1300 (c2) steps, in the reference as here.  A run longer
         # than `life` steps goes back to the initial state (a device-side copy, gcm_restore, inside
         # the timed region: one 0.1 ms copy per `life` steps), at an exchange boundary on bands.
+        # The copy is made before the step that needs it, so the state after the last step is that step's.
         life = {"c3": 400, "c2": 800}.get(name)
         if life is not None:
             life = life // k * k
@@ -222,13 +241,13 @@ def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kern
 
         def run(n, timed=False):
             while n > 0:
+                if life is not None and since[0] == life:
+                    core.restore()
+                    since[0] = 0
                 m = n if life is None else min(n, life - since[0])
                 run_chunk(m, timed)
                 since[0] += m
                 n -= m
-                if life is not None and since[0] == life:
-                    core.restore()
-                    since[0] = 0
     else:
         def run(n, timed=False):
             pass
@@ -243,7 +262,10 @@ def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kern
     # Untimed pre-conditioning: the chip needs some tens of milliseconds of sustained load before it
     # runs at its sustained clock (the same 400 steps of c3 take 0.153 ms each from idle and 0.146
     # after 60 ms of load).  SETTLE_S seconds of the same steps, then back to the initial state
-    # (2-D workloads), then the W warm-up steps and the K timed steps of the contract.
+    # (2-D workloads), then the W warm-up steps and the K timed steps of the contract.  The warm-up
+    # must start from the same state in every run (--dump-outputs): GCM_PE25D has no device-side
+    # snapshot, and putting its inputs back from the host idles the GPU long enough to slow the timed
+    # steps (c4: 2.5 %), so its settle is SETTLE_STEPS_PE steps (~0.12 s of c4) whatever they take.
     if active:
         t0 = time.perf_counter()
         run(2 * k)
@@ -257,11 +279,8 @@ def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kern
         per = float(tt.item())
     n_settle = 0
     if active:
-        n_settle = min(20000, int(SETTLE_S / max(per, 1e-6))) // k * k
+        n_settle = SETTLE_STEPS_PE if model == "PE25D" else min(20000, int(SETTLE_S / max(per, 1e-6))) // k * k
         run(n_settle)
-        if life is not None and since[0]:
-            core.restore()
-            since[0] = 0
     # Deep-halo bands whose exchange the library posts itself: the exchange can be hidden behind the
     # interior rows of the steps around it at the price of four more launches per window
     # (gcm_set_band_overlap).  GCM_PE25D bands: the interior rows' update can be held back until the edge rows'
@@ -286,49 +305,52 @@ def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kern
             overlap_probe["overlap" if flag else "plain"] = float(tt.item()) / npr * 1e3
         overlap_probe["chosen"] = "overlap" if overlap_probe["overlap"] < overlap_probe["plain"] else "plain"
         core.set_band_overlap(overlap_probe["chosen"] == "overlap")
-        if life is not None and since[0]:
-            core.restore()
-            since[0] = 0
-    run(warmup)
-    # The timed region: a block of exactly `steps` steps between two fences (barrier + synchronize),
-    # repeated until MIN_TIMED_S seconds have been timed (every rank sees the same all-reduced block
-    # times, so all stop together); the median block is the result.
-    blocks, own_blocks, t_queued = [], [], 0.0
-    while True:
-        fence()
-        t0 = time.perf_counter()
-        run(steps, timed=True)
-        t_queued += time.perf_counter() - t0          # the host has queued all K steps
-        torch.cuda.synchronize()
-        own_blocks.append(time.perf_counter() - t0)   # this rank's own band, before it waits for the others
-        fence()
-        el = time.perf_counter() - t0
-        if dist is not None and not solo:
-            tt = torch.tensor([el], dtype=torch.float64, device="cuda" if cx.backend == "nccl" else "cpu")
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            el = float(tt.item())
-        blocks.append(el)
-        if sum(blocks) >= MIN_TIMED_S or len(blocks) >= MAX_BLOCKS:
-            break
-    el = float(np.median(blocks))
-    t_queued /= len(blocks)
-    # N > 1: every rank's own median (its band done, before the closing barrier), gathered so that the line shows the
+    if active and life is not None:
+        core.restore()
+        since[0] = 0
+    run(warmup, timed=True)        # the path the timed steps take: its first-call costs stay out of the timed region
+    if active:
+        region.clear()
+    # The timed region: exactly `steps` steps between two fences (barrier + synchronize)
+    fence()
+    t0 = time.perf_counter()
+    run(steps, timed=True)
+    t_queued = time.perf_counter() - t0          # the host has queued all K steps
+    torch.cuda.synchronize()
+    own = time.perf_counter() - t0               # this rank's own band, before it waits for the others
+    fence()
+    el = time.perf_counter() - t0
+    if dist is not None and not solo:
+        tt = torch.tensor([el], dtype=torch.float64, device="cuda" if cx.backend == "nccl" else "cpu")
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        el = float(tt.item())
+    # N > 1: every rank's own time (its band done, before the closing barrier), gathered so that the line shows the
     # slowest and the fastest band
     per_rank_ms = None
     if dist is not None and not solo and world > 1:
-        tt = torch.tensor([float(np.median(own_blocks)) / steps * 1e3], dtype=torch.float64,
-                          device="cuda" if cx.backend == "nccl" else "cpu")
+        tt = torch.tensor([own / steps * 1e3], dtype=torch.float64, device="cuda" if cx.backend == "nccl" else "cpu")
         allv = [torch.zeros_like(tt) for _ in range(world)]
         dist.all_gather(allv, tt)
         per_rank_ms = [float(x.item()) for x in allv]
+    if dump is not None and active:
+        # what the last timed step computed (the diagnostics below step the state further)
+        out = {f: a for f, a in zip("puvtq", core.get_state()) if a is not None}
+        if phys:
+            out["gt"] = core.get_ground()
+        if world > 1 and not solo:               # the bands, north to south, on rank 0
+            parts = [None] * world if cx.rank == 0 else None
+            dist.gather_object(out, parts, dst=0, group=cx.cpu_group)
+            if cx.rank == 0:
+                out = {f: np.concatenate([b[f] for b in parts], axis=-2) for f in out}
+        if cx.rank == 0:
+            write_outputs(dump, out, np.float32 if name.endswith("_f32") else np.float64)
     if active:
         assert core.diag(_lib.DIAG_ANY_NAN) == 0.0, "state went NaN during the timed run"
         cells = H * W * L
         value = cells * steps / el
         res = {"workload": desc, "grid": [W, H] + ([L] if L > 1 else []), "n_gpus": world, "steps": steps,
                "warmup": warmup, "value": value, "ms_per_step": el / steps * 1e3,
-               "ms_per_step_min": min(blocks) / steps * 1e3, "ms_per_step_max": max(blocks) / steps * 1e3,
-               "timed_blocks": len(blocks), "timed_seconds": sum(blocks), "settle_steps": 2 * k + n_settle,
+               "timed_seconds": el, "settle_steps": 2 * k + n_settle,
                "dtype": "f32" if name.endswith("_f32") else "f64",
                "bytes_per_cell_update": bpc,
                "hbm_roofline_frac_whole_job": value * bpc / (world * HBM_PEAK_GBS * 1e9),
@@ -389,13 +411,13 @@ def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kern
             # back-to-back launches leave no gap (rocprofv3 trace: next start == previous end).
             # "kernel_ms_isolated" is a second pass with an event pair around every launch
             # (idle gaps between launches let the chip clock higher, so it reads lower).
-            launches_timed = steps * len(blocks)
+            launches_timed = steps
             kiso = None
             launches = 1
             if model == "PE25D":
                 # one Euler stage = four launches (spu filter with pit in its launch, geopot, pgf filter, update) on two
                 # streams; the roofline entry is the WHOLE stage: half of the step's algorithmic bytes over
-                # half of the step's device time (HIP events around the timed blocks)
+                # half of the step's device time (HIP events around the timed steps)
                 kname, kms, launches = ("pe25d stage: pe_spu_filter_loop (+ pit) + pe_geopot + pe_pgf_filter + pe_update_rows"
                                         + (" (+ half of pe_radiation)" if phys else "")), region["ms"] / launches_timed / 2, 2
             elif variant == "fused" and model == "SW2D":
@@ -579,6 +601,11 @@ def main():
     ap.add_argument("--variant", default="fused", choices=["fused", "staged"])
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--only", action="store_true", help="skip the secondary workloads under 'also'")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the state the last one computed (p, u, v, t, q as the workload "
+                         "has them; gt, the ground temperature, with physics) as DIR/<name>.npy in the workload's "
+                         "float type; above %d MB in all, a fixed sample of every field (bench.write_outputs)"
+                         % (DUMP_BYTES // 10 ** 6))
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -627,7 +654,7 @@ def main():
             bring_up_direct_rccl(cx, torch, dist)
             agree_stuck(cx, torch, dist)
 
-    main_res = run_workload(cx, a.workload, a.steps, a.warmup, a.variant)
+    main_res = run_workload(cx, a.workload, a.steps, a.warmup, a.variant, dump=a.dump_outputs)
     also, cpu_cache = {}, {}
     if not a.only:
         for name in ALSO:
@@ -662,8 +689,7 @@ def main():
         out = {
             "metric": "cell-updates/s (C-grid Matsuno step)", "value": main_res["value"],
             "unit": "cell-updates/s", "n_gpus": cx.world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": main_res["ms_per_step"], "ms_per_step_min": main_res["ms_per_step_min"],
-            "ms_per_step_max": main_res["ms_per_step_max"], "timed_blocks": main_res["timed_blocks"],
+            "ms_per_step": main_res["ms_per_step"],
             "timed_seconds": main_res["timed_seconds"], "settle_steps": main_res["settle_steps"],
             "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": main_res["dtype"], "data": "synthetic",

@@ -34,7 +34,6 @@ def test_run_workload_band_path_and_overlap_probe(monkeypatch):
     import bench
     from gcmiipy_amd.bands import LoopbackExchange
     monkeypatch.setattr(bench, "SETTLE_S", 0.01)
-    monkeypatch.setattr(bench, "MIN_TIMED_S", 0.02)
     cx = bench.Ctx()
     cx.torch, cx.dist = torch, _OneRank()
     cx.rank, cx.world, cx.local, cx.backend = 0, 2, 0, "nccl"
@@ -61,7 +60,6 @@ def test_run_workload_pe25d_band_path(monkeypatch):
     import bench
     from gcmiipy_amd.bands import LoopbackExchange
     monkeypatch.setattr(bench, "SETTLE_S", 0.01)
-    monkeypatch.setattr(bench, "MIN_TIMED_S", 0.02)
     cx = bench.Ctx()
     cx.torch, cx.dist = torch, _OneRank()
     cx.rank, cx.world, cx.local, cx.backend = 3, 8, 0, "nccl"
@@ -82,7 +80,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(GCM_BENCH_BACKEND="gloo", GCM_BENCH_SETTLE_S="0.01", GCM_BENCH_MIN_TIMED_S="0.02")
+    env.update(GCM_BENCH_BACKEND="gloo", GCM_BENCH_SETTLE_S="0.01")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "4",
                         "--only", "--no-cpu"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]

@@ -150,3 +150,27 @@ def test_bring_up_init_never_returns(tmp_path):
     assert codes == [4, 4], codes
     assert all(x["stuck"] and not x["direct"] for x in v)
     assert "timed out" in v[1]["fallback"]
+
+
+def test_write_outputs_whole_or_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs' files: whole fields in the asked float type while the set fits DUMP_BYTES; above it, a 1-D sample
+    of every field at positions that do not change from run to run, all files together within the budget"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    fields = {"p": rng.standard_normal((30, 40)), "u": rng.standard_normal((5, 30, 40))}
+    bench.write_outputs(str(tmp_path / "whole"), fields, np.float32)
+    for f, a in fields.items():
+        got = np.load(str(tmp_path / "whole" / (f + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 4096 + 8 * 2000)
+    for d in ("s1", "s2"):
+        bench.write_outputs(str(tmp_path / d), fields, np.float64)
+    sizes = 0
+    for f, a in fields.items():
+        s1, s2 = (np.load(str(tmp_path / d / (f + ".npy"))) for d in ("s1", "s2"))
+        assert s1.dtype == np.float64 and s1.ndim == 1 and 0 < s1.size < a.size and np.array_equal(s1, s2)
+        assert np.isin(s1, a).all()
+        sizes += os.path.getsize(str(tmp_path / "s1" / (f + ".npy")))
+    assert sizes <= bench.DUMP_BYTES
