@@ -1,7 +1,8 @@
 """State I/O: the reference keeps its state in RAM only; long device-resident
 runs want a restart file.  One `.npz` per handle holds the prognostic tuple, the ground
 temperature of the column physics (when set), the model tag, every option the handle was created
-with (dx, tracer, kernel variant, filter, Coriolis, dtype, band placement) and the geometry tables:
+with (dx, tracer, kernel variant, filter, Coriolis, dtype, band placement), the passive tracers of a GCM_PE25D
+handle (key "tracers", only when it carries some) and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
 import numpy as np
@@ -24,6 +25,8 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
         out["opt_" + name] = np.asarray(val)
     if core.has_ground:
         out["ground"] = core.get_ground()
+    if core.tracer_count > 0:
+        out["tracers"] = core.get_tracers()
     for k, a in zip("puvtq", (p, u, v, t, q)):
         if a is not None:
             out["state_" + k] = a
@@ -36,7 +39,8 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 
 def load(path):
-    """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra)"""
+    """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers); ground and
+    tracers are None where the file has none"""
     d = np.load(path, allow_pickle=False)
     L, H, W = (int(x) for x in d["shape"])
     state = {k: d["state_" + k] for k in "puvtq" if "state_" + k in d.files}
@@ -56,7 +60,8 @@ def load(path):
                                                                (float(a) if a.dtype.kind == "f" else int(a)))
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
-                ground=d["ground"] if "ground" in d.files else None)
+                ground=d["ground"] if "ground" in d.files else None,
+                tracers=d["tracers"] if "tracers" in d.files else None)
 
 
 def restore(path, **core_kwargs):
@@ -72,4 +77,6 @@ def restore(path, **core_kwargs):
     core.set_state(**ck["state"])
     if ck["ground"] is not None:
         core.set_ground(ck["ground"])
+    if ck["tracers"] is not None:
+        core.set_tracers(ck["tracers"])
     return core, ck

@@ -35,6 +35,19 @@ def as_f64(x, shape=None, name="array"):
     return a
 
 
+def tracer_array(c, L, H, W):
+    """the passive tracers of a GCM_PE25D handle as gcm_set_tracers takes them: float64 C-contiguous
+    (n, L, H, W) with 0 <= n <= MAX_TRACERS (None: no tracers); ValueError otherwise"""
+    if c is None:
+        return np.empty((0, L, H, W))
+    a = as_f64(c, name="tracers")
+    if a.ndim != 4 or a.shape[1:] != (L, H, W):
+        raise ValueError("tracers have shape %s, expected (n, %d, %d, %d)" % (a.shape, L, H, W))
+    if a.shape[0] > _lib.MAX_TRACERS:
+        raise ValueError("%d tracers: at most %d" % (a.shape[0], _lib.MAX_TRACERS))
+    return a
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -140,6 +153,26 @@ class Core:
 
     def get_star(self, fields=(_lib.P, _lib.U, _lib.V, _lib.T)):
         return self._get(lib.gcm_get_star, fields)
+
+    # -- passive tracers (GCM_PE25D, single domain) -------------------------------------
+    def set_tracers(self, c):
+        """carry the tracers c (n, L, H, W) from now on (n = 0 or None: none); every stage advances them
+        with the update of q (gcm_set_tracers)"""
+        a = tracer_array(c, self.L, self.H, self.W)
+        _check(lib.gcm_set_tracers(self._h, a.shape[0], _ptr(a) if a.shape[0] else None), self._h)
+
+    def get_tracers(self, star=False):
+        """-> (n, L, H, W): the current tracers, or with star=True those of the last predictor"""
+        out = np.empty((self.tracer_count, self.L, self.H, self.W))
+        _check(lib.gcm_get_tracers(self._h, 1 if star else 0, _ptr(out) if out.size else None), self._h)
+        return out
+
+    @property
+    def tracer_count(self):
+        n = lib.gcm_tracer_count(self._h)
+        if n < 0:
+            _check(n, self._h)
+        return n
 
     # -- stepping ------------------------------------------------------------------
     def step(self, nsteps, dt):

@@ -479,6 +479,7 @@ int gcm_step(gcm_handle *h, int nsteps, double dt) {
                 h->phys.utc += dt;
             }
         }
+        pe25d_join_tracers(h->pe, h->stream);             // (the passive tracers' tail on the second stream)
         return GCM_OK;
     }
     if (!h->wrap && h->since_exchange + nsteps > h->G / kGhost)
@@ -510,6 +511,30 @@ int gcm_step(gcm_handle *h, int nsteps, double dt) {
     }
     h->star_valid = false;
     return launch_status(h);
+}
+
+static int tracer_refusal(const gcm_handle *h, const char *fn) {
+    if (!h) return GCM_ERR_ARG;
+    if (!h->pe) return fail(const_cast<gcm_handle *>(h), GCM_ERR_UNSUPPORTED, std::string(fn) + ": GCM_PE25D only");
+    if (!h->wrap) return fail(const_cast<gcm_handle *>(h), GCM_ERR_UNSUPPORTED, std::string(fn) + ": not on latitude bands");
+    return GCM_OK;
+}
+
+int gcm_set_tracers(gcm_handle *h, int n, const double *c) {
+    if (int rc = tracer_refusal(h, "gcm_set_tracers")) return rc;
+    if (h->cfg.device >= 0) HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pe25d_set_tracers(h->pe, n, c, h->stream, &h->err);
+}
+
+int gcm_get_tracers(gcm_handle *h, int which, double *c) {
+    if (int rc = tracer_refusal(h, "gcm_get_tracers")) return rc;
+    if (h->cfg.device >= 0) HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pe25d_get_tracers(h->pe, which, c, h->stream, &h->err);
+}
+
+int gcm_tracer_count(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_tracer_count(h->pe) : 0;
 }
 
 int gcm_step_interior(gcm_handle *h, double dt, void *stream) {
@@ -694,6 +719,7 @@ int gcm_restore(gcm_handle *h) {
 
 int gcm_sync(gcm_handle *h) {
     if (!h) return GCM_ERR_ARG;
+    if (h->pe) pe25d_join_tracers(h->pe, h->stream);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return GCM_OK;
 }

@@ -63,6 +63,20 @@ struct PeArgsT {
     T dt, inv_dy, ptop;
 };
 
+// passive tracers (pe25d_tracer.h)
+template <typename T>
+struct TracerArgsT {
+    // state and stage intermediates, device layout [j][k][i] (2-D: [j][i]), pointers at interior row 0
+    const T *p, *pn, *sp, *sv, *spu, *pit;
+    const T *inv_dxj, *dsig, *inv_dsig, *sigb;   // [Hg], [L] tables
+    // tracers, [n][H][L][W]: base (current), stage, out (in the corrector the current set again: in place)
+    const T *c, *sc;
+    T *oc;
+    long tstride;                                // elements per tracer
+    int W, H, L, Hg, row0, wrap;
+    T dt, inv_dy;
+};
+
 __device__ __forceinline__ int wrapi(int x, int n) {
     x %= n;
     return x < 0 ? x + n : x;
@@ -168,6 +182,10 @@ template <typename T, int R> FilterKernel<T> update_rows_kernel_rt(bool same, bo
 template <typename T> inline FilterKernel<T> update_rows_kernel_for(int rows_per_group, bool same, bool oddtop = false) {
     return rows_per_group == 7 ? update_rows_kernel_rt<T, 7>(same, oddtop) : update_rows_kernel_rt<T, 3>(same, oddtop);
 }  // pe25d_k4.h (R = 3 or 7)
+template <typename T> using TracerKernel = void (*)(TracerArgsT<T>);
+template <typename T> TracerKernel<T> tracer_kernel_for(int nc, bool same);   // pe25d_tracer.h (nc = 4, 2 or 1)
+constexpr int kTrCols = 64;       // tracer kernel: workgroup of 64 columns x kTrRows rows, one thread per (j, i) column
+constexpr int kTrRows = 4;
 constexpr int kUpdCols = 62;      // row-group update kernel: columns a wave produces (lanes 0 and 63 carry the halo columns)
 constexpr int kFftThreads = 256;  // generic filter path; the composite path sizes the workgroup from its plan
 

@@ -544,6 +544,14 @@ struct Pe25d {
     bool edges_first = false;
     hipEvent_t ev_pre_edge = nullptr;
     bool pre_edge_pending = false;
+    // passive tracers (gcm_set_tracers; single domain only): 2 x ntr fields of H x L x W in T, device layout
+    // [j][k][i] -- the current set (ntr fields), then the star set.  The tracer kernel runs on chain B (see half_t);
+    // ev_tr, recorded on `aux` behind the last tracer launch, is how the caller's stream joins that tail
+    int ntr = 0;
+    void *tr = nullptr;
+    bool tr_star = false;                       // the star set holds the tracers of a predictor
+    bool tr_pending = false;                    // a tracer launch on `aux` that the caller's stream has not joined
+    hipEvent_t ev_tr = nullptr;
 };
 
 template <typename T> static PeBufs<T> &bufs(Pe25d *m);
@@ -902,6 +910,7 @@ void pe25d_destroy(Pe25d *m) {
     if (m->ev_cs) (void)hipEventDestroy(m->ev_cs);
     if (m->ev_k4) (void)hipEventDestroy(m->ev_k4);
     if (m->ev_pre_edge) (void)hipEventDestroy(m->ev_pre_edge);
+    if (m->ev_tr) (void)hipEventDestroy(m->ev_tr);
     if (m->aux2) {
         (void)hipStreamSynchronize(m->aux2);
         (void)hipStreamDestroy(m->aux2);
@@ -911,6 +920,7 @@ void pe25d_destroy(Pe25d *m) {
         (void)hipStreamDestroy(m->aux);
     }
     for (void *p : m->allocs) (void)hipFree(p);
+    if (m->tr) (void)hipFree(m->tr);
     delete m;
 }
 
@@ -1064,6 +1074,38 @@ static void prep_rows(Pe25d *m, const PeArgsT<T> &a, int stage_set, bool p2, int
     if (!m->wrap || (fresh && c.cs_rows)) geopot(c, sb);
 }
 
+// The passive tracers of one stage (pe25d_tracer.h): base = the current tracers, stage = the star set in the corrector,
+// out = the star set in the predictor and the current set again in the corrector (each cell reads its base value
+// only at itself: in place).  Chunks of 4, then 2, then 1 tracers, one launch per chunk size (blockIdx.y = chunk).
+template <typename T>
+static void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out_set, hipStream_t st) {
+    const long stride = (long)m->H * m->L * m->W;
+    T *const cur = (T *)m->tr, *const star = cur + (long)m->ntr * stride;
+    TracerArgsT<T> t{};
+    t.p = a.p; t.pn = a.pn; t.sp = a.sp; t.sv = a.sv; t.spu = a.spu; t.pit = a.pit;
+    t.inv_dxj = a.inv_dxj; t.dsig = a.dsig; t.inv_dsig = a.inv_dsig; t.sigb = a.sigb;
+    t.c = cur;
+    t.sc = stage_set == 2 ? star : cur;
+    t.oc = out_set == 2 ? star : cur;
+    t.tstride = stride;
+    t.W = m->W; t.H = m->H; t.L = m->L; t.Hg = m->Hg; t.row0 = m->cfg.row0; t.wrap = a.wrap;
+    t.dt = a.dt; t.inv_dy = a.inv_dy;
+    const bool same = t.sc == t.c;
+    const long tiles = (long)((m->W + kTrCols - 1) / kTrCols) * ((m->H + kTrRows - 1) / kTrRows);
+    const dim3 block(kTrCols * kTrRows);
+    int done = 0;
+    for (const int nc : {4, 2, 1}) {
+        const int chunks = (m->ntr - done) / nc;
+        if (chunks == 0) continue;
+        TracerArgsT<T> c = t;
+        c.c += done * stride; c.sc += done * stride; c.oc += done * stride;
+        hipLaunchKernelGGL(tracer_kernel_for<T>(nc, same), dim3((unsigned)((tiles + 7) / 8 * 8), (unsigned)chunks), block, 0, st, c);
+        done += chunks * nc;
+    }
+    m->tr_star = out_set == 2;
+    m->tr_pending = m->aux != nullptr;
+}
+
 // one Euler stage over rows [j0, j1): state `stage_set` -> `out_set`, base = current.
 // mode 0: everything; mode 1: K1-K3 on all rows + K4 on the two edge rows of either side (the rows
 // a neighbouring band needs); mode 2: K4 on the remaining interior rows.  Modes 1 + 2 == mode 0.
@@ -1195,6 +1237,17 @@ static void half_t(Pe25d *m, int stage_set, int out_set, double dt, int j0, int 
             hipLaunchKernelGGL(pe_pit_kernel<T>, dim3((unsigned)((tiles + 7) / 8 * 8)), dim3(256), 0, sb, a);
         }
         if (m->aux && !split_k1 && !ev_a_done) (void)hipEventRecord(m->ev_a, m->aux);      // (what K4 of the interior rows takes from this chain)
+        // ---- the passive tracers (single domain): on chain B right behind K1 + pit and after ev_a, so that K4 on
+        //      chain A never waits for them and they run beside K2a, K3 and K4.  Two invariants hold them in place:
+        //      * the next stage's K1 must not overwrite spu, pit or p_n while this launch still reads them: it is
+        //        queued on this same stream behind it.  (Not on `s` behind K4: chain B forks at ev_k4 when
+        //        k4_fork_valid is set, and the next K1 would then race the tracer kernel.)  The state sets it reads
+        //        (sp, sv, p) are overwritten only by a later K4, which waits for a later ev_a: behind this launch too;
+        //      * everything that returns to the caller joins chain B's tail: gcm_step (and so gcm_time_steps'
+        //        stop event), gcm_half_step, gcm_get_tracers, gcm_set_tracers and gcm_sync make `s` wait for ev_tr,
+        //        recorded on `aux` behind the last tracer launch (pe25d_join_tracers).
+        //      Without tracers nothing is launched, recorded or waited for here.
+        if (m->ntr > 0 && mode == 0) launch_tracers<T>(m, a, stage_set, out_set, sb);
         // ---- chain A: geopotential of the own rows, then the filtered pressure-gradient force
         a.j0 = j0;
         a.j1 = j1;
@@ -1362,6 +1415,85 @@ int pe25d_prep_ghost_rows(Pe25d *m, std::string *err) {
     return GCM_OK;
 }
 
+void pe25d_join_tracers(Pe25d *m, hipStream_t s) {
+    if (!m->tr_pending) return;
+    m->tr_pending = false;
+    (void)hipEventRecord(m->ev_tr, m->aux);
+    (void)hipStreamWaitEvent(s, m->ev_tr, 0);
+}
+
+int pe25d_tracer_count(const Pe25d *m) { return m->ntr; }
+
+int pe25d_set_tracers(Pe25d *m, int n, const double *c, hipStream_t s, std::string *err) {
+    if (!m->wrap) {
+        *err = "gcm_set_tracers: tracers on latitude bands are not supported";
+        return GCM_ERR_UNSUPPORTED;
+    }
+    if (n < 0 || n > GCM_MAX_TRACERS || (n > 0 && !c)) {
+        *err = "gcm_set_tracers: n must be 0 .. GCM_MAX_TRACERS, with a host array for n > 0";
+        return GCM_ERR_ARG;
+    }
+    pe25d_join_tracers(m, s);
+    const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
+    const size_t cells = (size_t)m->H * m->L * m->W;
+    hipError_t e = hipStreamSynchronize(s);                       // (the last tracer launch has ended: buffers free to go)
+    if (e == hipSuccess && n != m->ntr) {
+        if (m->tr) e = hipFree(m->tr);
+        m->tr = nullptr;
+        m->ntr = 0;
+        if (e == hipSuccess && n > 0) e = hipMalloc(&m->tr, 2 * (size_t)n * cells * esz);
+        if (e == hipSuccess) m->ntr = n;
+    }
+    if (e == hipSuccess && n > 0 && m->aux && !m->ev_tr) e = hipEventCreateWithFlags(&m->ev_tr, hipEventDisableTiming);
+    for (int f = 0; f < n && e == hipSuccess; ++f) {
+        e = hipMemcpyAsync(m->stage3, c + (size_t)f * cells, sizeof(double) * cells, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) break;
+        if (m->f32) hipLaunchKernelGGL(pe_to_device_kernel<float>, dim3(1024), dim3(256), 0, s, (float *)m->tr + f * cells, m->stage3, m->W, m->H, m->L);
+        else hipLaunchKernelGGL(pe_to_device_kernel<double>, dim3(1024), dim3(256), 0, s, (double *)m->tr + f * cells, m->stage3, m->W, m->H, m->L);
+    }
+    // the star set starts as a copy (a corrector behind gcm_set_star, without a predictor, reads it)
+    if (e == hipSuccess && n > 0) e = hipMemcpyAsync((char *)m->tr + (size_t)n * cells * esz, m->tr, (size_t)n * cells * esz, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    m->tr_star = false;
+    m->k4_fork_valid = false;                    // (the uploads on the caller's stream: the next chain B follows them)
+    if (e != hipSuccess) {
+        *err = std::string("gcm_set_tracers: ") + hipGetErrorString(e);
+        return GCM_ERR_HIP;
+    }
+    return GCM_OK;
+}
+
+int pe25d_get_tracers(Pe25d *m, int which, double *c, hipStream_t s, std::string *err) {
+    if (which != 0 && which != 1) {
+        *err = "gcm_get_tracers: which must be 0 (current) or 1 (star)";
+        return GCM_ERR_ARG;
+    }
+    if (which == 1 && !m->tr_star) {
+        *err = "gcm_get_tracers: no predicted tracers yet";
+        return GCM_ERR_STATE;
+    }
+    if (m->ntr > 0 && !c) {
+        *err = "gcm_get_tracers: no host array";
+        return GCM_ERR_ARG;
+    }
+    pe25d_join_tracers(m, s);
+    const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
+    const size_t cells = (size_t)m->H * m->L * m->W;
+    const char *base = (const char *)m->tr + (which ? (size_t)m->ntr * cells * esz : 0);
+    hipError_t e = hipSuccess;
+    for (int f = 0; f < m->ntr && e == hipSuccess; ++f) {
+        if (m->f32) hipLaunchKernelGGL(pe_to_host_kernel<float>, dim3(1024), dim3(256), 0, s, m->stage3, (const float *)base + f * cells, m->W, m->H, m->L);
+        else hipLaunchKernelGGL(pe_to_host_kernel<double>, dim3(1024), dim3(256), 0, s, m->stage3, (const double *)base + f * cells, m->W, m->H, m->L);
+        e = hipMemcpyAsync(c + (size_t)f * cells, m->stage3, sizeof(double) * cells, hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        *err = std::string("gcm_get_tracers: ") + hipGetErrorString(e);
+        return GCM_ERR_HIP;
+    }
+    return GCM_OK;
+}
+
 int pe25d_half(Pe25d *m, int stage, double dt, hipStream_t s, std::string *err) {
     if (!m->wrap) {
         *err = "half_step on a latitude band: use step_part";
@@ -1379,6 +1511,7 @@ int pe25d_half(Pe25d *m, int stage, double dt, hipStream_t s, std::string *err) 
         m->cur_i = 1 - m->cur_i;
         m->star_valid = false;
     }
+    pe25d_join_tracers(m, s);
     if (hipGetLastError() != hipSuccess) {
         *err = "hip: pe25d kernel launch failed";
         return GCM_ERR_HIP;

@@ -49,14 +49,35 @@ def half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, geom):
     return _wrap_out(c.get_state(), units)
 
 
-def matsuno_timestep(p, u, v, t, q, dt, geom, boundary_conditions=None, coriolis=False):
+def _prep_tracers(tracers, geom):
+    from .core import tracer_array
+    vals, un = strip(tracers)
+    return tracer_array(vals, geom.layers, geom.height, geom.width), un
+
+
+def matsuno_timestep(p, u, v, t, q, dt, geom, boundary_conditions=None, coriolis=False, tracers=None):
     """dynamics.py:230-237.  `coriolis=True` switches on the Coriolis terms the reference keeps
     behind `if False` (dynamics.py:82-92).  With a Python `boundary_conditions(sp,su,sv,st,sq,dt,geom)` hook
     the predicted state makes a host round trip between the stages (documented slow path);
-    with None both stages stay on the device."""
+    with None both stages stay on the device.  `tracers` (n, L, H, W): passive tracers advanced with
+    exactly the update of q; the result is then (p, u, v, t, q, tracers)."""
     base, units = _prep(p, u, v, t, q, geom)
     c = core_for(geom, coriolis=coriolis)
     c.set_state(*base)
+    if tracers is not None:
+        tr, tr_unit = _prep_tracers(tracers, geom)
+        c.set_tracers(tr)
+    try:
+        out = _matsuno_on(c, dt, geom, units, boundary_conditions)
+        if tracers is None:
+            return out
+        return (*out, attach(c.get_tracers(), tr_unit))
+    finally:
+        if tracers is not None:
+            c.set_tracers(None)          # the cached handle goes back to carrying none
+
+
+def _matsuno_on(c, dt, geom, units, boundary_conditions):
     dts = scalar(dt)
     if boundary_conditions is None:
         c.step(1, dts)
@@ -70,13 +91,17 @@ def matsuno_timestep(p, u, v, t, q, dt, geom, boundary_conditions=None, coriolis
     return boundary_conditions(*out, dt, geom)
 
 
-def run(p, u, v, t, q, dt, geom, steps, callback=None, every=1):
+def run(p, u, v, t, q, dt, geom, steps, callback=None, every=1, tracers=None):
     """Device-resident loop: `steps` Matsuno steps with the state in HBM throughout;
-    optional callback(p,u,v,t,q) every `every` steps (no_limits_2_5d.py:230-234)."""
+    optional callback(p,u,v,t,q) every `every` steps (no_limits_2_5d.py:230-234).  `tracers`
+    (n, L, H, W): passive tracers carried along; the result is then (p, u, v, t, q, tracers)."""
     base, units = _prep(p, u, v, t, q, geom)
     c = Core(_lib.PE25D, geom.width, geom.height, geom.layers, geom=geom)
     try:
         c.set_state(*base)
+        if tracers is not None:
+            tr, tr_unit = _prep_tracers(tracers, geom)
+            c.set_tracers(tr)
         done = 0
         while done < steps:
             n = min(every, steps - done) if callback else steps - done
@@ -84,7 +109,8 @@ def run(p, u, v, t, q, dt, geom, steps, callback=None, every=1):
             done += n
             if callback:
                 callback(*_wrap_out(c.get_state(), units))
-        return _wrap_out(c.get_state(), units)
+        out = _wrap_out(c.get_state(), units)
+        return out if tracers is None else (*out, attach(c.get_tracers(), tr_unit))
     finally:
         c.close()
 

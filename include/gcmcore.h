@@ -155,6 +155,22 @@ int gcm_get_star(gcm_handle *h, double *p, double *u, double *v, double *t, doub
 int gcm_set_star(gcm_handle *h, const double *p, const double *u, const double *v,
                  const double *t, const double *q);
 
+/* Passive tracers of GCM_PE25D (single domain): n fields c[n][L][H][W] that every Matsuno stage of
+ * gcm_step / gcm_half_step / gcm_time_steps advances with exactly the update the reference applies to q
+ * (dynamics.py:219, advec_t :174-181, advec_sig :49-52) on the stage's own mass fluxes:
+ *     c_n = (c p - (advec_t(spu, spv, sc) + advec_sig(sd, sc)) dt) / p_n,   sc = the stage value,
+ * so a tracer equal to q stays equal to q (bit for bit in fp64).  No flux limiting, no positivity (the reference
+ * applies none to q).  The handle stores them in its own real type; the host API is float64.
+ * gcm_set_tracers: 0 <= n <= GCM_MAX_TRACERS (n = 0 frees them), also resets the star set to c;
+ * gcm_get_tracers: which = 0 the current tracers, 1 those of the last predictor (GCM_ERR_STATE before
+ * one); gcm_tracer_count: n.  Other models and latitude bands (nranks > 1): GCM_ERR_UNSUPPORTED.
+ * The tracer kernel runs on the handle's second stream; these calls, gcm_step, gcm_half_step and
+ * gcm_sync include it.  Without tracers the step is the same work as before.                          */
+#define GCM_MAX_TRACERS 16
+int gcm_set_tracers(gcm_handle *h, int n, const double *c);
+int gcm_get_tracers(gcm_handle *h, int which, double *c);
+int gcm_tracer_count(const gcm_handle *h);
+
 /* Diagnostics the reference's drivers evaluate on the host every step
  * (SURVEY.md 8f-1); computed by device reductions, result copied to *out. */
 typedef enum {
