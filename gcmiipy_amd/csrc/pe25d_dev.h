@@ -170,7 +170,7 @@ template <typename T> using FilterKernel = void (*)(PeArgsT<T>);
 template <typename T> using FilterLoopKernel = void (*)(PeArgsT<T>, int, int);   // (args, pairs per workgroup, y-block that forms pit or -1)
 // plans with their own instantiation (only their passes compiled in): the row lengths of the
 // BASELINE configs and the powers of 16
-constexpr unsigned kMask1440 = pass_bit(5, 2) | pass_bit(4, 3);                    // 1440, 720, 360, 120 ...
+constexpr unsigned kMask1440 = pass_bit(5, 2) | pass_bit(4, 3);                    // 1440 = 10.12.12, 120 = 10.12
 constexpr unsigned kMask2880 = pass_bit(5, 3) | pass_bit(4, 3) | pass_bit(4, 4);   // 2880
 constexpr unsigned kMask4096 = pass_bit(4, 4);                                     // 256, 4096
 template <typename T> FilterKernel<T> spu_filter_kernel_for(const SuperPlan &P);            // pe25d_k1.h

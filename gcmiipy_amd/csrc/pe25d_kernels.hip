@@ -590,6 +590,12 @@ template <typename T>
 static size_t filter_lds_bytes(const Pe25d *m) {
     return (size_t)(m->cplan.ok ? 1 : 2) * m->W * sizeof(typename Vec2<T>::type);
 }
+// pe_pit2d_kernel: the composite path keeps the filtered row after its one-row workspace, the generic path in the
+// free half of its two (pe_pit2d_row)
+template <typename T>
+static size_t pit2d_lds_bytes(const Pe25d *m) {
+    return filter_lds_bytes<T>(m) + (m->cplan.ok ? sizeof(T) * (size_t)m->W : 0);
+}
 
 template <typename T>
 static const char *alloc_all(Pe25d *m, const gcm_config &cfg) {
@@ -671,7 +677,7 @@ static const char *alloc_all(Pe25d *m, const gcm_config &cfg) {
         hipFuncSetAttribute((const void *)pgf_filter_kernel_for<T>(m->cplan), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)filter_lds_bytes<T>(m)) != hipSuccess ||
         hipFuncSetAttribute((const void *)pit2d_kernel_for<T>(m->cplan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(filter_lds_bytes<T>(m) + sizeof(T) * (size_t)W)) != hipSuccess ||
+                            (int)pit2d_lds_bytes<T>(m)) != hipSuccess ||
         hipFuncSetAttribute((const void *)pe_geopot_kernel<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(L * kColThreads * sizeof(T))) != hipSuccess ||
         hipFuncSetAttribute((const void *)pe_geopot_kernel<T, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -824,10 +830,16 @@ Pe25d *pe25d_create(const gcm_config &cfg, hipStream_t main_stream, std::string 
         pe25d_destroy(m);
         return nullptr;
     }
-    if ((size_t)L * kColThreads * sizeof(double) + kExnerTabDoubles * sizeof(double) > 160 * 1024 ||
-        sizeof(double) * (size_t)L * kRadThreads + 4096 > 160 * 1024 ||
-        upd_lds_bytes<double>(3, L) + 4096 > 160 * 1024) {
-        *err = "GCM_PE25D: too many layers for the column kernels' LDS (max 100)";
+    // the LDS-parked column kernels (L > 40: pe_geopot_kernel<T, 0>, pe_radiation_kernel<T, 0>) hold one value per level
+    // and thread; the radiation park is the largest (fp64 whatever the handle's type): L <= 156
+    const auto layers_fit = [](size_t l) {
+        return l * kColThreads * sizeof(double) + kExnerTabDoubles * sizeof(double) <= 160 * 1024 &&
+               sizeof(double) * l * kRadThreads + 4096 <= 160 * 1024 && upd_lds_bytes<double>(3, (int)l) + 4096 <= 160 * 1024;
+    };
+    if (!layers_fit((size_t)L)) {
+        int lmax = 1;
+        while (layers_fit((size_t)lmax + 1)) ++lmax;
+        *err = "GCM_PE25D: " + std::to_string(L) + " layers: the column kernels' LDS holds at most " + std::to_string(lmax);
         pe25d_destroy(m);
         return nullptr;
     }
@@ -1231,7 +1243,7 @@ static void half_t(Pe25d *m, int stage_set, int out_set, double dt, int j0, int 
             hipLaunchKernelGGL(spu_filter_kernel_for<T>(m->cplan), dim3(a.j1 - a.j0, pairs), dim3(fft_threads), lds, sb, a);
         }
         if (p2 && !pit_done) {
-            hipLaunchKernelGGL(pit2d_kernel_for<T>(m->cplan), dim3(a.j1 - a.j0), dim3(fft_threads), lds + sizeof(T) * (size_t)W, sb, a);
+            hipLaunchKernelGGL(pit2d_kernel_for<T>(m->cplan), dim3(a.j1 - a.j0), dim3(fft_threads), pit2d_lds_bytes<T>(m), sb, a);
         } else if (!p2) {
             const long tiles = (long)((W + 255) / 256) * (a.j1 - a.j0);
             hipLaunchKernelGGL(pe_pit_kernel<T>, dim3((unsigned)((tiles + 7) / 8 * 8)), dim3(256), 0, sb, a);

@@ -12,7 +12,10 @@ __device__ __forceinline__ void pe_pit2d_row(const PeArgsT<T> &a, typename Vec2<
     using V = typename Vec2<T>::type;
     const Idx ix{a.W, a.H, a.L, a.wrap};
     const int W = a.W;
-    T *fx = (T *)(x + (MAXR > 0 ? 1 : 2) * W);                  // the filtered row, after the transform's workspace
+    // the filtered row: after the composite transform's one-row workspace; the generic path leaves it in the half of
+    // its ping-pong pair that does not hold the result, so that the workgroup needs no more LDS than K1's (2 W complex
+    // values: a row of 4608 columns in fp64 would otherwise ask for 180 KB)
+    T *fx = (T *)(x + W);
     const int jg = wrapi(a.row0 + j, a.Hg);
     const T *sp = a.sp + ix.r2(j);
     const T *cu = a.scs_u + ix.r2(j);
@@ -29,7 +32,9 @@ __device__ __forceinline__ void pe_pit2d_row(const PeArgsT<T> &a, typename Vec2<
             for (int i = threadIdx.x; i < W; i += blockDim.x) x[i] = load(i);
             __syncthreads();
             const V *res = filter_rows<T>(x, x + W, a.tw, a.plan, a.smul + (long)jg * (W / 2 + 1));
-            for (int i = threadIdx.x; i < W; i += blockDim.x) store(i, res[i]);
+            T *fr = (T *)(res == x ? x + W : x);
+            for (int i = threadIdx.x; i < W; i += blockDim.x) fr[i] = res[i].x;
+            fx = fr;
         }
     } else {
         for (int i = threadIdx.x; i < W; i += blockDim.x) store(i, load(i));

@@ -116,12 +116,14 @@ def test_geography_harness_h1(g):
 
 @pytest.mark.parametrize("hwl", [(8, 16, 4), (6, 10, 3), (5, 12, 1), (12, 20, 5), (7, 30, 2),
                                  (3, 1440, 2), (4, 2880, 3), (3, 14, 2), (2, 2250, 1), (3, 400, 2), (2, 1250, 1),
-                                 (2, 4096, 2)])
+                                 (2, 4096, 2), (3, 1458, 3), (4, 120, 3), (3, 256, 2), (2, 4608, 1), (3, 202, 2)])
 def test_shapes_vs_oracle(g, hwl):
     """ragged sizes: odd L (unpaired level in the packed FFT), radix-3/5 widths, L = 1; the row
     lengths of BASELINE configs[3] / [4] (1440, 2880: in-place FFT), a radix-7 length (generic
     butterfly, generic ping-pong path), 2250 = 10.15.15, 400 = 20.20 and 1250 = 10.25.5 (the widest
-    composite radices), 4096 = 16.16.16"""
+    composite radices), 4096 = 16.16.16; 1458 = 6.9.9.3 (the only four-pass plan), 120 = 10.12 and
+    256 = 16.16 (the kMask1440 / kMask4096 kernels in two passes), 4608 (a {2,3}-smooth width the
+    generic path serves: a pass of 1152 butterflies), 202 = 2.101 (the generic radix-r butterfly)"""
     from gcmiipy_amd import geometry
     from oracle import dynamics as odyn, geometry as ogeo, temperature as otemp
     H, W, L = hwl
