@@ -19,8 +19,8 @@ from .core import Core, GcmError, device_count  # noqa: F401
 
 def clear_cache():
     """free the device state the per-call drop-ins keep between calls"""
-    from . import matsuno_c_grid, dynamics
-    for cache in (matsuno_c_grid._cache, dynamics._cache):
+    from . import matsuno_c_grid, dynamics, ensemble
+    for cache in (matsuno_c_grid._cache, dynamics._cache, ensemble._cache):
         while cache:
             cache.popitem()[1].close()
     _lib.lib.gcm_ops_release_scratch()      # the operator entry points' device scratch of this thread

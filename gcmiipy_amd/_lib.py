@@ -50,6 +50,7 @@ class Config(C.Structure):
         ("variant", C.c_int32), ("filter", C.c_int32), ("nranks", C.c_int32),
         ("rank", C.c_int32), ("global_height", C.c_int32), ("row0", C.c_int32),
         ("device", C.c_int32), ("dtype", C.c_int32), ("halo_steps", C.c_int32),
+        ("members", C.c_int32),
         ("dx", C.c_double), ("dy", C.c_double), ("ptop", C.c_double),
         ("dx_j", _dp), ("dx_h", _dp), ("sig", _dp), ("dsig", _dp), ("sigb", _dp),
         ("sigt", _dp), ("heightmap", _dp), ("cor_u", _dp), ("cor_v", _dp), ("stream", C.c_void_p),
@@ -83,6 +84,10 @@ SYMBOLS = {
     "gcm_last_error": (C.c_char_p, [_H]),
     "gcm_set_state": (C.c_int, [_H] + [C.c_void_p] * 5),
     "gcm_get_state": (C.c_int, [_H] + [C.c_void_p] * 5),
+    "gcm_members": (C.c_int, [_H]),
+    "gcm_set_member": (C.c_int, [_H, C.c_int] + [C.c_void_p] * 5),
+    "gcm_get_member": (C.c_int, [_H, C.c_int] + [C.c_void_p] * 5),
+    "gcm_diag_members": (C.c_int, [_H, C.c_int, _dp, C.c_int]),
     "gcm_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_half_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_get_star": (C.c_int, [_H] + [C.c_void_p] * 5),

@@ -1,7 +1,8 @@
 """State I/O: the reference keeps its state in RAM only; long device-resident
 runs want a restart file.  One `.npz` per handle holds the prognostic tuple, the ground
 temperature of the column physics (when set), the model tag, every option the handle was created
-with (dx, tracer, kernel variant, filter, Coriolis, dtype, band placement), the passive tracers of a GCM_PE25D
+with (dx, tracer, kernel variant, filter, Coriolis, dtype, band placement, ensemble members: an ensemble's
+state arrays are (M, H, W), and files without "opt_members" restore as one member), the passive tracers of a GCM_PE25D
 handle (key "tracers", only when it carries some) and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""

@@ -61,13 +61,16 @@ class Core:
 
     def __init__(self, model, width, height, layers=1, dx=0.0, tracer=_lib.TRACER_NONE,
                  variant=_lib.VARIANT_AUTO, geom=None, filter=True, nranks=1, rank=0,
-                 global_height=None, row0=0, device=-1, stream=None, halo_steps=1, coriolis=False, dtype="f64"):
+                 global_height=None, row0=0, device=-1, stream=None, halo_steps=1, coriolis=False, dtype="f64",
+                 members=1):
         self.model, self.W, self.H, self.L = model, int(width), int(height), int(layers)
+        # ensemble members (2-D models, single band): every field is (M, H, W) when M > 1
+        self.members = max(int(members), 1)
         self.nranks, self.rank = nranks, rank
         # what a checkpoint needs to rebuild this handle (checkpoint.save / restore)
         self.options = dict(dx=float(dx), tracer=int(tracer), variant=int(variant), filter=bool(filter),
                             nranks=int(nranks), rank=int(rank), row0=int(row0), halo_steps=int(halo_steps),
-                            coriolis=bool(coriolis), dtype=dtype,
+                            coriolis=bool(coriolis), dtype=dtype, members=int(members),
                             global_height=int(height if global_height is None else global_height))
         self.has_ground = False
         cfg = _lib.Config()
@@ -81,6 +84,7 @@ class Core:
         cfg.row0 = row0
         cfg.device = device
         cfg.halo_steps = halo_steps
+        cfg.members = int(members)
         cfg.dtype = {"f64": _lib.F64, "f32": _lib.F32}[dtype]
         self.dtype = dtype
         self.halo_steps = halo_steps
@@ -125,6 +129,8 @@ class Core:
     def shape_of(self, field):
         if self.is3d and field != _lib.P:
             return (self.L, self.H, self.W)
+        if self.members > 1:
+            return (self.members, self.H, self.W)
         return (self.H, self.W)
 
     def _prep_in(self, arrs):
@@ -153,6 +159,25 @@ class Core:
 
     def get_star(self, fields=(_lib.P, _lib.U, _lib.V, _lib.T)):
         return self._get(lib.gcm_get_star, fields)
+
+    # -- ensemble members ------------------------------------------------------------------
+    def set_member(self, m, p=None, u=None, v=None, t=None, q=None):
+        """member m's (H, W) fields alone (gcm_set_member)"""
+        a = [None if x is None else as_f64(x, (self.H, self.W), "puvtq"[f]) for f, x in enumerate((p, u, v, t, q))]
+        _check(lib.gcm_set_member(self._h, int(m), *[_ptr(x) for x in a]), self._h)
+
+    def get_member(self, m, fields=None):
+        """-> [p, u, v, t, q] of member m, each (H, W) (None for fields not requested / not in the model)"""
+        fields = self.fields if fields is None else fields
+        out = [np.empty((self.H, self.W)) if f in fields else None for f in range(5)]
+        _check(lib.gcm_get_member(self._h, int(m), *[_ptr(x) for x in out]), self._h)
+        return out
+
+    def diag_members(self, kind):
+        """-> (M,) array: diag(kind) of every member, by one launch and one synchronisation"""
+        out = np.empty(self.members)
+        _check(lib.gcm_diag_members(self._h, int(kind), _tab(out), self.members), self._h)
+        return out
 
     # -- passive tracers (GCM_PE25D, single domain) -------------------------------------
     def set_tracers(self, c):

@@ -45,6 +45,8 @@ struct gcm_handle {
     int snap_since_exchange = 0;
     int variant = GCM_VARIANT_FUSED;
     int rows_per_band = 32;
+    int M = 1;              // ensemble members (2-D models, single band)
+    long mstride = 0;       // doubles from one member's slab to the next: (H + 2G) W, rounded up to 256 B if M > 1
 
     // diagnostics scratch
     double *diag_dev = nullptr;
@@ -91,13 +93,20 @@ static int fail(gcm_handle *h, int code, const std::string &msg) {
     return code;
 }
 
+// diagnostics: workgroups per member of the reduction kernels (one member: gcm_handle::kDiagBlocks)
+static int diag_blocks_per_member(const gcm_handle *h) {
+    return std::max(8, gcm_handle::kDiagBlocks / h->M);
+}
+
 static int alloc_field(gcm_handle *h, double **p) {
     // Every array starts a different multiple of 256 B past its (2 MiB-aligned) allocation: rows of a
     // power-of-two width would otherwise put the same (row, column) of all fields on the same HBM channel and
     // bank, and a wave of the fused kernel touches that element of ten arrays per row (tools/micro/copy_width.hip:
     // the bare access pattern moves 4-6 % faster with the arrays skewed).  GCM_ALLOC_SKEW=0 switches it off.
+    // An ensemble's members follow one another at mstride doubles (a whole number of 256-B lines, so that
+    // every member's rows start as a single handle's do); the skew is per field, as for one member.
     static const long skew_unit = getenv("GCM_ALLOC_SKEW") ? atol(getenv("GCM_ALLOC_SKEW")) : 256;
-    const size_t n = (size_t)(h->H + 2 * h->G) * h->W;
+    const size_t n = (size_t)(h->M - 1) * h->mstride + (size_t)(h->H + 2 * h->G) * h->W;
     const size_t skew = (size_t)(skew_unit > 0 ? skew_unit : 0) * (h->allocs.size() % 16) / sizeof(double);
     void *d = nullptr;
     HIPCHK(h, hipMalloc(&d, (n + skew) * sizeof(double)));
@@ -163,6 +172,11 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
         return fail(nullptr, GCM_ERR_ARG, "gcm_create: a latitude band needs >= 2 * halo_steps rows");
     if (hsteps > 1 && (cfg->nranks == 1 || (cfg->model != GCM_SW2D && cfg->model != GCM_SW2D_TEMP)))
         return fail(nullptr, GCM_ERR_ARG, "gcm_create: halo_steps > 1 needs a 2-D latitude band");
+    if (cfg->members < 0) return fail(nullptr, GCM_ERR_ARG, "gcm_create: members must be >= 0");
+    if (cfg->members > 1 && cfg->model != GCM_SW2D && cfg->model != GCM_SW2D_TEMP)
+        return fail(nullptr, GCM_ERR_UNSUPPORTED, "gcm_create: members > 1 needs GCM_SW2D or GCM_SW2D_TEMP");
+    if (cfg->members > 1 && cfg->nranks > 1)
+        return fail(nullptr, GCM_ERR_UNSUPPORTED, "gcm_create: members > 1 is not available on latitude bands");
     if (gcm_device_count() < 1)
         return fail(nullptr, GCM_ERR_NODEVICE,
                     "gcm_create: no HIP device visible; libgcmcore has no CPU fallback");
@@ -173,6 +187,9 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
     h->L = cfg->layers;
     h->wrap = cfg->nranks == 1;
     h->G = kGhost * hsteps;
+    h->M = cfg->members > 1 ? cfg->members : 1;
+    h->mstride = (long)(h->H + 2 * h->G) * h->W;
+    if (h->M > 1) h->mstride = (h->mstride + 31) / 32 * 32;
     h->stream = (hipStream_t)cfg->stream;
     int rc = GCM_OK;
     auto bail = [&](int code, const std::string &m) {
@@ -220,7 +237,7 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
                 h->allocs.push_back(d);
                 h->exner_tab = (double *)d;
             }
-            h->rows_per_band = sw2d_fused_rows_per_band(h->W, h->H, temp, h->has[GCM_Q] ? cfg->tracer : 0, h->wrap);
+            h->rows_per_band = sw2d_fused_rows_per_band(h->W, h->H, temp, h->has[GCM_Q] ? cfg->tracer : 0, h->wrap, h->M);
             break;
         }
         case GCM_PE2D: {
@@ -255,7 +272,7 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
             return bail(GCM_ERR_UNSUPPORTED, "gcm_create: model not built in this round");
     }
     void *d = nullptr;
-    if (hipMalloc(&d, sizeof(double) * 4 * gcm_handle::kDiagBlocks) != hipSuccess)
+    if (hipMalloc(&d, sizeof(double) * 4 * diag_blocks_per_member(h) * h->M) != hipSuccess)
         return bail(GCM_ERR_HIP, "gcm_create: hipMalloc(diag) failed");
     h->allocs.push_back(d);
     h->diag_dev = (double *)d;
@@ -266,18 +283,27 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
 }
 
 // ------------------------------------------------------------------ state transfer
+// member < 0: all members ([M][H][W] host arrays; the device slabs are mstride doubles apart, so one 2-D copy
+// per field), else that member alone ([H][W])
 static int xfer(gcm_handle *h, double *const dev[GCM_NFIELDS], const double *const hostc[GCM_NFIELDS],
-                double *const hostm[GCM_NFIELDS], bool to_device) {
-    const size_t bytes = (size_t)h->H * h->W * sizeof(double);
+                double *const hostm[GCM_NFIELDS], bool to_device, int member = -1) {
+    const size_t bytes = (size_t)h->H * h->W * sizeof(double), pitch = (size_t)h->mstride * sizeof(double);
     for (int f = 0; f < GCM_NFIELDS; ++f) {
         const void *src = hostc ? (const void *)hostc[f] : (const void *)hostm[f];
         if (!src) continue;
         if (!h->has[f] || !dev[f])
             return fail(h, GCM_ERR_ARG, "state transfer: field not part of this model");
-        if (to_device)
-            HIPCHK(h, hipMemcpyAsync(dev[f], hostc[f], bytes, hipMemcpyHostToDevice, h->stream));
-        else
-            HIPCHK(h, hipMemcpyAsync(hostm[f], dev[f], bytes, hipMemcpyDeviceToHost, h->stream));
+        double *d = dev[f] + (size_t)(member < 0 ? 0 : member) * h->mstride;
+        if (member >= 0 || h->M == 1) {
+            if (to_device)
+                HIPCHK(h, hipMemcpyAsync(d, hostc[f], bytes, hipMemcpyHostToDevice, h->stream));
+            else
+                HIPCHK(h, hipMemcpyAsync(hostm[f], d, bytes, hipMemcpyDeviceToHost, h->stream));
+        } else if (to_device) {
+            HIPCHK(h, hipMemcpy2DAsync(d, pitch, hostc[f], bytes, bytes, h->M, hipMemcpyHostToDevice, h->stream));
+        } else {
+            HIPCHK(h, hipMemcpy2DAsync(hostm[f], bytes, d, pitch, bytes, h->M, hipMemcpyDeviceToHost, h->stream));
+        }
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return GCM_OK;
@@ -347,6 +373,8 @@ static Sw2dArgs base_args(gcm_handle *h, double dt) {
     a.j0 = 0;
     a.j1 = h->H;
     a.rows_per_band = h->rows_per_band;
+    a.members = h->M;
+    a.mstride = h->mstride;
     a.dt = dt;
     a.dx = h->cfg.dx;
     a.inv_dx = 1.0 / h->cfg.dx;
@@ -683,7 +711,7 @@ int gcm_halo_unpack2(gcm_handle *h, const void *north_buf, const void *south_buf
 int gcm_snapshot(gcm_handle *h) {
     if (!h) return GCM_ERR_ARG;
     if (h->pe) return fail(h, GCM_ERR_UNSUPPORTED, "gcm_snapshot: 2-D models only");
-    const size_t n = (size_t)(h->H + 2 * h->G) * h->W;
+    const size_t n = (size_t)(h->M - 1) * h->mstride + (size_t)(h->H + 2 * h->G) * h->W;   // all members
     for (int f = 0; f < GCM_NFIELDS; ++f) {
         if (!h->has[f]) continue;
         if (!h->snap[f]) {
@@ -703,7 +731,7 @@ int gcm_snapshot(gcm_handle *h) {
 int gcm_restore(gcm_handle *h) {
     if (!h) return GCM_ERR_ARG;
     if (h->pe) return fail(h, GCM_ERR_UNSUPPORTED, "gcm_restore: 2-D models only");
-    const size_t n = (size_t)(h->H + 2 * h->G) * h->W;
+    const size_t n = (size_t)(h->M - 1) * h->mstride + (size_t)(h->H + 2 * h->G) * h->W;
     for (int f = 0; f < GCM_NFIELDS; ++f) {
         if (!h->has[f]) continue;
         if (!h->snap[f]) return fail(h, GCM_ERR_STATE, "gcm_restore: no snapshot taken");
@@ -986,9 +1014,13 @@ int gcm_band_run(gcm_handle *h, int nsteps, double dt) {
 // ------------------------------------------------------------------ diagnostics
 }  // extern "C"
 
+// Both reductions are segmented: blockIdx.y picks a segment (an ensemble member) that starts `seg` elements
+// after the previous one, and block (x, y) writes partial 4 * (y * gridDim.x + x).
 template <typename T>
-__global__ __launch_bounds__(256) void diag_kernel(const T *x, long n, double *out) {
+__global__ __launch_bounds__(256) void diag_kernel(const T *x, long n, double *out, long seg = 0) {
     // out[4*b + {0,1,2,3}] = max, min, sum, nan-count of this block's grid-stride share
+    x += blockIdx.y * seg;
+    out += 4 * (long)blockIdx.y * gridDim.x;
     double mx = -INFINITY, mn = INFINITY, sm = 0.0, nn = 0.0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const double v = (double)x[i];
@@ -1027,7 +1059,10 @@ __global__ __launch_bounds__(256) void diag_kernel(const T *x, long n, double *o
 // [n_outer][n_axis][n_inner]; wrap == 0: the slab after the last one (a band's south ghost row) is
 // differenced instead of slab 0.  out[4*b + 2] = the block's partial sum, [3] = its NaN count.
 template <typename T>
-__global__ __launch_bounds__(256) void tv_kernel(const T *x, long n_outer, long n_axis, long n_inner, int wrap, double *out) {
+__global__ __launch_bounds__(256) void tv_kernel(const T *x, long n_outer, long n_axis, long n_inner, int wrap, double *out,
+                                                 long seg = 0) {
+    x += blockIdx.y * seg;
+    out += 4 * (long)blockIdx.y * gridDim.x;
     const long n = n_outer * n_axis * n_inner;
     double sm = 0.0, nn = 0.0;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
@@ -1057,27 +1092,83 @@ __global__ __launch_bounds__(256) void tv_kernel(const T *x, long n_outer, long 
 
 extern "C" {
 
-int gcm_diag(gcm_handle *h, int kind, double *out) {
-    if (!h || !out) return GCM_ERR_ARG;
-    const double *x = nullptr;
-    long n = (long)h->H * h->W;
-    int f;
-    const bool tv = kind >= GCM_DIAG_TV_P && kind <= GCM_DIAG_TV_Q;
+// which field a gcm_diag_kind reduces, or a negative status
+static int diag_field(gcm_handle *h, int kind) {
     switch (kind) {
         case GCM_DIAG_TV_P: case GCM_DIAG_TV_U: case GCM_DIAG_TV_V: case GCM_DIAG_TV_T: case GCM_DIAG_TV_Q:
-            f = kind - GCM_DIAG_TV_P;
-            if (!h->pe && !h->has[f]) return fail(h, GCM_ERR_ARG, "gcm_diag: the model has no such field");
-            // a 2-D band differences its last row against the south ghost row: that row must belong to
-            // the CURRENT state (bands exchange before a step, so after a step it is stale)
-            if (!h->pe && !h->wrap && !h->ghosts_current)
-                return fail(h, GCM_ERR_STATE, "gcm_diag: total variation on a latitude band needs the current state's "
-                                              "ghost rows (exchange them first: gcm_halo_pack2 / exchange / gcm_halo_unpack2)");
-            break;
-        case GCM_DIAG_ANY_NAN: case GCM_DIAG_MAX_U: case GCM_DIAG_MIN_U: f = GCM_U; break;
-        case GCM_DIAG_MEAN_P: case GCM_DIAG_SUM_P: f = GCM_P; break;
-        case GCM_DIAG_MAX_V: case GCM_DIAG_MIN_V: f = GCM_V; break;
+            if (!h->has[kind - GCM_DIAG_TV_P]) return fail(h, GCM_ERR_ARG, "gcm_diag: the model has no such field");
+            return kind - GCM_DIAG_TV_P;
+        case GCM_DIAG_ANY_NAN: case GCM_DIAG_MAX_U: case GCM_DIAG_MIN_U: return GCM_U;
+        case GCM_DIAG_MEAN_P: case GCM_DIAG_SUM_P: return GCM_P;
+        case GCM_DIAG_MAX_V: case GCM_DIAG_MIN_V: return GCM_V;
         default: return fail(h, GCM_ERR_ARG, "gcm_diag: unknown kind");
     }
+}
+
+// a diagnostic's value from the reduced max, min, sum and NaN count of n elements
+static double diag_value(int kind, double mx, double mn, double sm, double nn, double n) {
+    switch (kind) {
+        case GCM_DIAG_ANY_NAN: return nn > 0 ? 1.0 : 0.0;
+        case GCM_DIAG_MAX_U: case GCM_DIAG_MAX_V: return nn > 0 ? NAN : mx;
+        case GCM_DIAG_MIN_U: case GCM_DIAG_MIN_V: return nn > 0 ? NAN : mn;
+        case GCM_DIAG_MEAN_P: return sm / n;
+        case GCM_DIAG_SUM_P: return sm;
+        default: return nn > 0 ? NAN : sm;                 // total variation
+    }
+}
+
+// Ensemble handles (2-D, single band): every member's diagnostic by one segmented launch (nb workgroups per
+// member) and one synchronisation.  per_member[M] (may be NULL) and / or *all, the figure over all members
+// (a mean over all M H W cells; total variations add up, each member's rows wrapping inside the member).
+static int diag_members(gcm_handle *h, int kind, double *per_member, double *all) {
+    const int f = diag_field(h, kind);
+    if (f < 0) return f;
+    const bool tv = kind >= GCM_DIAG_TV_P && kind <= GCM_DIAG_TV_Q;
+    const int nb = diag_blocks_per_member(h), M = h->M;
+    const long n = (long)h->H * h->W;
+    if (tv)
+        hipLaunchKernelGGL(tv_kernel<double>, dim3(nb, M), dim3(256), 0, h->stream, h->cur[f], 1L, (long)h->H, (long)h->W,
+                           1, h->diag_dev, h->mstride);
+    else
+        hipLaunchKernelGGL(diag_kernel<double>, dim3(nb, M), dim3(256), 0, h->stream, h->cur[f], n, h->diag_dev,
+                           h->mstride);
+    HIPCHK(h, hipGetLastError());
+    std::vector<double> part(4 * (size_t)nb * M);
+    HIPCHK(h, hipMemcpyAsync(part.data(), h->diag_dev, sizeof(double) * part.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    double amx = -INFINITY, amn = INFINITY, asm_ = 0.0, ann = 0.0;
+    for (int m = 0; m < M; ++m) {
+        double mx = -INFINITY, mn = INFINITY, sm = 0.0, nn = 0.0;
+        for (int b = 0; b < nb; ++b) {
+            const double *q = &part[4 * ((size_t)m * nb + b)];
+            mx = std::fmax(mx, q[0]);
+            mn = std::fmin(mn, q[1]);
+            sm += q[2];
+            nn += q[3];
+        }
+        if (per_member) per_member[m] = diag_value(kind, mx, mn, sm, nn, (double)n);
+        amx = std::fmax(amx, mx);
+        amn = std::fmin(amn, mn);
+        asm_ += sm;
+        ann += nn;
+    }
+    if (all) *all = diag_value(kind, amx, amn, asm_, ann, (double)n * M);
+    return GCM_OK;
+}
+
+int gcm_diag(gcm_handle *h, int kind, double *out) {
+    if (!h || !out) return GCM_ERR_ARG;
+    if (h->M > 1) return diag_members(h, kind, nullptr, out);
+    const double *x = nullptr;
+    long n = (long)h->H * h->W;
+    const int f = diag_field(h, kind);
+    if (f < 0) return f;
+    const bool tv = kind >= GCM_DIAG_TV_P && kind <= GCM_DIAG_TV_Q;
+    // a 2-D band differences its last row against the south ghost row: that row must belong to
+    // the CURRENT state (bands exchange before a step, so after a step it is stale)
+    if (tv && !h->pe && !h->wrap && !h->ghosts_current)
+        return fail(h, GCM_ERR_STATE, "gcm_diag: total variation on a latitude band needs the current state's "
+                                      "ghost rows (exchange them first: gcm_halo_pack2 / exchange / gcm_halo_unpack2)");
     int f32 = 0;
     const void *xv = nullptr;
     if (h->pe) {
@@ -1112,15 +1203,37 @@ int gcm_diag(gcm_handle *h, int kind, double *out) {
         sm += part[4 * b + 2];
         nn += part[4 * b + 3];
     }
-    switch (kind) {
-        case GCM_DIAG_ANY_NAN: *out = nn > 0 ? 1.0 : 0.0; break;
-        case GCM_DIAG_MAX_U: case GCM_DIAG_MAX_V: *out = nn > 0 ? NAN : mx; break;
-        case GCM_DIAG_MIN_U: case GCM_DIAG_MIN_V: *out = nn > 0 ? NAN : mn; break;
-        case GCM_DIAG_MEAN_P: *out = sm / (double)n; break;
-        case GCM_DIAG_SUM_P: *out = sm; break;
-        default: *out = nn > 0 ? NAN : sm; break;          // total variation
-    }
+    *out = diag_value(kind, mx, mn, sm, nn, (double)n);
     return GCM_OK;
+}
+
+int gcm_diag_members(gcm_handle *h, int kind, double *out, int n) {
+    if (!h || !out) return GCM_ERR_ARG;
+    if (n < h->M) return fail(h, GCM_ERR_ARG, "gcm_diag_members: out holds fewer values than the handle has members");
+    if (h->M == 1) return gcm_diag(h, kind, out);
+    return diag_members(h, kind, out, nullptr);
+}
+
+int gcm_members(const gcm_handle *h) { return h ? h->M : GCM_ERR_ARG; }
+
+int gcm_set_member(gcm_handle *h, int m, const double *p, const double *u, const double *v, const double *t,
+                   const double *q) {
+    if (!h) return GCM_ERR_ARG;
+    if (m < 0 || m >= h->M) return fail(h, GCM_ERR_ARG, "gcm_set_member: member out of range");
+    if (h->pe) return gcm_set_state(h, p, u, v, t, q);
+    h->primed = false;
+    h->ghosts_current = false;
+    h->star_valid = false;
+    const double *src[GCM_NFIELDS] = {p, u, v, t, q};
+    return xfer(h, h->cur, src, nullptr, true, m);
+}
+
+int gcm_get_member(gcm_handle *h, int m, double *p, double *u, double *v, double *t, double *q) {
+    if (!h) return GCM_ERR_ARG;
+    if (m < 0 || m >= h->M) return fail(h, GCM_ERR_ARG, "gcm_get_member: member out of range");
+    if (h->pe) return gcm_get_state(h, p, u, v, t, q);
+    double *dst[GCM_NFIELDS] = {p, u, v, t, q};
+    return xfer(h, h->cur, nullptr, dst, false, m);
 }
 
 int gcm_energy(gcm_handle *h, const double *area, int area_len, double *out4) {

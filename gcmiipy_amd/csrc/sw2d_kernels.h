@@ -9,7 +9,8 @@ constexpr int kExnerTabDoubles = 256;  // [0,128): E_e, e = -64..63; then 64 x {
 constexpr int kGhost = 2;        // ghost rows on each side of a latitude band
 constexpr int kStripCols = 60;   // output columns per wave in the fused kernel (64 lanes - 2x2 halo)
 
-// Pointers address interior row 0; with wrap_j == 0 rows -2,-1 and H,H+1 are ghost rows.
+// Pointers address interior row 0 of member 0; with wrap_j == 0 rows -2,-1 and H,H+1 are ghost rows.
+// Member m's field starts mstride doubles after member m-1's (an ensemble handle, members > 1).
 struct Sw2dArgs {
     const double *bu, *bv, *bp, *bt, *bq;   // base (time n) state
     const double *su, *sv, *sp, *st;        // stage state the tendencies are evaluated on
@@ -21,6 +22,8 @@ struct Sw2dArgs {
     int wrap_j;                             // 1: rows wrap modulo H (single band); 0: ghost rows
     int j0, j1;                             // row range [j0, j1) to produce
     int rows_per_band;                      // fused: output rows per wave
+    int members;                            // ensemble members M (>= 1): one launch advances all of them
+    long mstride;                           // doubles from one member's slab to the next (every pointer above)
     double dt, dx, inv_dx, dx2, inv_dx2;
     double h_dx;                            // 0.5 / dx (exact halving folded in)
     double dtdx;                            // dt / dx
@@ -34,7 +37,7 @@ void launch_tracer_axis(const Sw2dArgs &a, int axis, bool limit, const double *q
                         double *q_out, hipStream_t s);
 // fused variant: predictor + corrector (+ both tracer passes) in one launch
 bool launch_sw2d_fused(const Sw2dArgs &a, bool temp, int tracer, hipStream_t s);   // false: the launch was refused
-int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap);
+int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap, int members = 1);
 // GCM_SW2D, single band, short bands (small grids): TWO steps in one launch; false if not applicable
 bool launch_sw2d_fused2(const Sw2dArgs &a, hipStream_t s);
 

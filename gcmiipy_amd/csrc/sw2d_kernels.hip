@@ -40,8 +40,24 @@ void build_exner_table(double *tab) {
     }
 }
 
+// Member m of an ensemble handle: every field pointer moved to that member's slab.  m is uniform
+// over a workgroup (a block index), so the offsets live in scalar registers.
+__device__ __forceinline__ Sw2dArgs member_args(const Sw2dArgs &a0, int m) {
+    Sw2dArgs a = a0;
+    const long o = (long)m * a0.mstride;
+    auto mv = [o](auto *p) { return p ? p + o : p; };
+    a.bu = mv(a.bu); a.bv = mv(a.bv); a.bp = mv(a.bp); a.bt = mv(a.bt); a.bq = mv(a.bq);
+    a.su = mv(a.su); a.sv = mv(a.sv); a.sp = mv(a.sp); a.st = mv(a.st);
+    a.sgeo = mv(a.sgeo); a.sirho = mv(a.sirho); a.sst = mv(a.sst);
+    a.ou = mv(a.ou); a.ov = mv(a.ov); a.op = mv(a.op); a.ot = mv(a.ot); a.oq = mv(a.oq);
+    a.dgeo = mv(a.dgeo); a.dirho = mv(a.dirho); a.dst = mv(a.dst);
+    return a;
+}
+
 // ------------------------------------------------------------------ staged
-__global__ __launch_bounds__(256) void sw2d_derive_kernel(Sw2dArgs a) {
+// (blockIdx.z = ensemble member)
+__global__ __launch_bounds__(256) void sw2d_derive_kernel(Sw2dArgs a0) {
+    const Sw2dArgs a = member_args(a0, blockIdx.z);
     __shared__ double tab[kExnerTabDoubles];
     tab[threadIdx.y * 64 + threadIdx.x] = a.exner_tab[threadIdx.y * 64 + threadIdx.x];
     __syncthreads();
@@ -56,7 +72,8 @@ __global__ __launch_bounds__(256) void sw2d_derive_kernel(Sw2dArgs a) {
 }
 
 template <bool TEMP>
-__global__ __launch_bounds__(256) void sw2d_stage_kernel(Sw2dArgs a) {
+__global__ __launch_bounds__(256) void sw2d_stage_kernel(Sw2dArgs a0) {
+    const Sw2dArgs a = member_args(a0, blockIdx.z);
     const int W = a.W, H = a.H;
     const int i = blockIdx.x * 64 + threadIdx.x;
     const int j = a.j0 + blockIdx.y * 4 + threadIdx.y;
@@ -102,8 +119,11 @@ __global__ __launch_bounds__(256) void sw2d_stage_kernel(Sw2dArgs a) {
 // one axis of the dimension-split tracer step (two_d.py:103-116), axis 0 = j with V[0] = v,
 // axis 1 = i with V[1] = u
 template <int AXIS, bool LIMIT>
-__global__ __launch_bounds__(256) void tracer_axis_kernel(Sw2dArgs a, const double *qin,
+__global__ __launch_bounds__(256) void tracer_axis_kernel(Sw2dArgs a0, const double *qin,
                                                            double *qout) {
+    const Sw2dArgs a = member_args(a0, blockIdx.z);
+    qin += blockIdx.z * a0.mstride;
+    qout += blockIdx.z * a0.mstride;
     const int W = a.W, H = a.H;
     const int i = blockIdx.x * 64 + threadIdx.x;
     const int j = a.j0 + blockIdx.y * 4 + threadIdx.y;
@@ -131,7 +151,7 @@ __global__ __launch_bounds__(256) void tracer_axis_kernel(Sw2dArgs a, const doub
 }
 
 static dim3 cell_grid(const Sw2dArgs &a) {
-    return dim3((a.W + 63) / 64, (a.j1 - a.j0 + 3) / 4);
+    return dim3((a.W + 63) / 64, (a.j1 - a.j0 + 3) / 4, a.members);
 }
 
 void launch_sw2d_derive(const Sw2dArgs &a, hipStream_t s) {
@@ -338,18 +358,27 @@ __device__ __forceinline__ void preloaded_iters(Ctx &c, const Raw (&pre)[PRE + 4
 }
 
 template <bool TEMP, int TRACER, bool WRAPJ, int PRE = 0, bool STREAM = false>
-__global__ __launch_bounds__(64) void sw2d_fused_kernel(Sw2dArgs a) {
-    const int W = a.W;
+__global__ __launch_bounds__(64) void sw2d_fused_kernel(Sw2dArgs a0) {
+    const int W = a0.W;
     const int lane = threadIdx.x;
-    // Tile = (strip, band).  Workgroups are dealt round-robin over the 8 XCDs (b % 8 names the
-    // XCD group), each with its own L2: give every XCD a contiguous run of tiles, so that
-    // neighbouring strips -- which share halo columns and the 128-B lines straddling a strip
-    // edge that both write -- meet in one L2.  Speed only: any placement is correct.
+    // Tile = (member, band, strip), strips fastest.  Workgroups are dealt round-robin over the 8
+    // XCDs (b % 8 names the XCD group), each with its own L2: give every XCD a contiguous run of
+    // tiles, so that neighbouring strips -- which share halo columns and the 128-B lines straddling
+    // a strip edge that both write -- meet in one L2.  Speed only: any placement is correct.
     const int strips = (W + kStripCols - 1) / kStripCols;
     const int per_xcd = gridDim.x / 8;
-    const int tile = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    int tile = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    int member = 0;
+    if (a0.members > 1) {   // (one member: no integer divisions beyond the strip's -- a small grid is latency-bound)
+        const int per_member = strips * ((a0.j1 - a0.j0 + a0.rows_per_band - 1) / a0.rows_per_band);
+        member = tile / per_member;
+        if (member >= a0.members) return;     // the padding tiles beyond the last member
+        tile -= member * per_member;
+    }
     const int band = tile / strips;
     const int i0 = (tile - band * strips) * kStripCols;
+    // the member's own slab: rows wrap (row_off) inside it, no lane reads a neighbouring member
+    const Sw2dArgs a = member_args(a0, member);
     __shared__ double tab[kExnerTabDoubles];
     if (TEMP) {
         for (int k = 0; k < kExnerTabDoubles / 64; ++k) tab[lane + 64 * k] = a.exner_tab[lane + 64 * k];
@@ -358,7 +387,7 @@ __global__ __launch_bounds__(64) void sw2d_fused_kernel(Sw2dArgs a) {
     FusedCtx<TEMP, TRACER, WRAPJ, STREAM> c{a, tab};
     c.ja = a.j0 + band * a.rows_per_band;
     c.jb = min(c.ja + a.rows_per_band, a.j1);
-    if (c.ja >= c.jb) return;   // also the padding tiles beyond the last band
+    if (c.ja >= c.jb) return;   // also the padding tiles beyond the last band of a single member
     c.col = i0 - 2 + lane;
     c.ci = c.col % W;
     if (c.ci < 0) c.ci += W;
@@ -479,15 +508,26 @@ __device__ __forceinline__ void fused2_iters(const Fused2Ctx &c, const Raw (&pre
     }
 }
 
-template <int RPB>
-__global__ __launch_bounds__(64) void sw2d_fused2_kernel(Sw2dArgs a) {
-    const int W = a.W, H = a.H;
+// ENS: an ensemble launch.  One member compiles to the code without a member: this kernel is bound by the
+// latency of its first loads, and the member's bookkeeping in front of them cost 1-2 % at C2.
+template <int RPB, bool ENS>
+__global__ __launch_bounds__(64) void sw2d_fused2_kernel(Sw2dArgs a0) {
+    const int W = a0.W, H = a0.H;
     const int lane = threadIdx.x;
+    // tiles (member, band, strip) as in sw2d_fused_kernel
     const int strips = (W + kStrip2Cols - 1) / kStrip2Cols;
     const int per_xcd = gridDim.x / 8;
-    const int tile = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    int tile = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    int member = 0;
+    if constexpr (ENS) {
+        const int per_member = strips * ((H + RPB - 1) / RPB);
+        member = tile / per_member;
+        if (member >= a0.members) return;
+        tile -= member * per_member;
+    }
     const int band = tile / strips;
     const int i0 = (tile - band * strips) * kStrip2Cols;
+    const Sw2dArgs a = ENS ? member_args(a0, member) : a0;
     Fused2Ctx c{a};
     c.ja = a.j0 + band * RPB;
     c.jb = min(c.ja + RPB, a.j1);
@@ -521,12 +561,13 @@ bool launch_sw2d_fused2(const Sw2dArgs &a, hipStream_t s) {
     if (!a.wrap_j || a.j0 != 0 || a.j1 != a.H || a.rows_per_band < 2 || a.rows_per_band > 4) return false;
     const int strips = (a.W + kStrip2Cols - 1) / kStrip2Cols;
     const int bands = (a.H + a.rows_per_band - 1) / a.rows_per_band;
-    dim3 g((unsigned)(((long)strips * bands + 7) / 8 * 8));
+    dim3 g((unsigned)(((long)strips * bands * a.members + 7) / 8 * 8));
     Sw2dArgs arg = a;
     void *params[] = {&arg};
-    const void *fn = a.rows_per_band == 2 ? (const void *)sw2d_fused2_kernel<2>
-                   : a.rows_per_band == 3 ? (const void *)sw2d_fused2_kernel<3>
-                                          : (const void *)sw2d_fused2_kernel<4>;
+    const bool ens = a.members > 1;
+    const void *fn = a.rows_per_band == 2 ? (ens ? (const void *)sw2d_fused2_kernel<2, true> : (const void *)sw2d_fused2_kernel<2, false>)
+                   : a.rows_per_band == 3 ? (ens ? (const void *)sw2d_fused2_kernel<3, true> : (const void *)sw2d_fused2_kernel<3, false>)
+                                          : (ens ? (const void *)sw2d_fused2_kernel<4, true> : (const void *)sw2d_fused2_kernel<4, false>);
     return hipLaunchKernel(fn, g, dim3(64), params, 0, s) == hipSuccess;
 }
 
@@ -556,8 +597,10 @@ static const void *fused_kernel_ptr(bool temp, int tracer, bool wrap, int rows_p
 
 // Rows per wave.  Large grids: one resident round -- as many waves as the chip holds at
 // this kernel's register footprint (a second, partly filled round would idle most SIMDs
-// at the tail); small grids: short bands so that every SIMD gets a wave.
-int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap) {
+// at the tail); small grids: short bands so that every SIMD gets a wave.  An ensemble counts
+// the waves of all `members` grids: short bands exist only to fill the chip, and once M
+// members fill it the 4 halo rows of a short band are pure overhead.
+int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap, int members) {
     if (const char *e = getenv("GCM_FUSED_ROWS")) {
         int v = atoi(e);
         if (v > 0) return v;
@@ -571,14 +614,19 @@ int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap) {
                                                      0) == hipSuccess && nb > 0)
         waves_per_cu = nb;
     const long slots = (long)waves_per_cu * cus;
+    const long M = members < 1 ? 1 : members;
     const long strips = (W + kStripCols - 1) / kStripCols;
-    auto waves = [&](int rpb) { return strips * ((H + rpb - 1) / rpb); };
+    auto waves = [&](int rpb) { return M * strips * ((H + rpb - 1) / rpb); };
     if (waves(8) < slots) {  // small grid: aim at one wave per SIMD at least
-        long rpb = (long)H * strips / (5L * cus);   // ~1.3 waves per SIMD (measured best on 720x360)
+        long rpb = M * H * strips / (5L * cus);   // ~1.3 waves per SIMD (measured best on 720x360)
+        // plain SW2D ensembles that do not fill the chip at 8 rows: bands short enough for two steps per launch
+        // (sw2d_fused2_kernel), which halves the launches and the state's round trips -- 0.85x the time of 8-row
+        // bands at 360x180, M = 16 (tools/tools_ensemble_time.py --only rows)
+        if (!temp && M > 1 && rpb > kPreloadRows) rpb = kPreloadRows;
         return (int)(rpb < 2 ? 2 : rpb > 8 ? 8 : rpb);
     }
     long rounds = (waves(64) + slots - 1) / slots;
-    long bands = rounds * slots / strips;  // floor: stay within `rounds` full rounds
+    long bands = rounds * slots / (strips * M);  // per member; floor: stay within `rounds` full rounds
     if (bands < 1) bands = 1;
     long rpb = (H + bands - 1) / bands;
     return (int)(rpb < 8 ? 8 : rpb);
@@ -588,12 +636,13 @@ bool launch_sw2d_fused(const Sw2dArgs &a, bool temp, int tracer, hipStream_t s) 
     if (a.j1 <= a.j0) return true;
     const int strips = (a.W + kStripCols - 1) / kStripCols;
     const int bands = (a.j1 - a.j0 + a.rows_per_band - 1) / a.rows_per_band;
-    dim3 g((unsigned)(((long)strips * bands + 7) / 8 * 8));  // 1-D, padded to 8 XCD groups
+    dim3 g((unsigned)(((long)strips * bands * a.members + 7) / 8 * 8));  // 1-D, padded to 8 XCD groups
     Sw2dArgs arg = a;
     void *params[] = {&arg};
-    // fields x 8 bytes x the rows of this launch, read once: stream it when that is beyond the 256 MB Infinity Cache
+    // fields x 8 bytes x the rows of this launch (all members), read once: stream it when that is beyond the
+    // 256 MB Infinity Cache
     const int nfields = 3 + (temp ? 1 : 0) + (tracer ? 1 : 0);
-    const bool stream = (long)a.W * (a.j1 - a.j0) * 8 * nfields > (256L << 20);
+    const bool stream = (long)a.W * (a.j1 - a.j0) * a.members * 8 * nfields > (256L << 20);
     return hipLaunchKernel(fused_kernel_ptr(temp, tracer, a.wrap_j != 0, a.rows_per_band, stream), g, dim3(64), params, 0, s) == hipSuccess;
 }
 

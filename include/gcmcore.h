@@ -93,6 +93,9 @@ typedef struct {
                               storage in fp32 for the tolerance sweep; the host API stays float64) */
     int32_t halo_steps;    /* 2-D bands: Matsuno steps per ghost-row exchange (ghost depth = 2 *
                               halo_steps rows per side, deep-halo communication avoiding); 0/1 = 1 */
+    int32_t members;       /* ensemble members M of GCM_SW2D / GCM_SW2D_TEMP (single band): M independent states
+                              on one grid with one dx, model, tracer and dt, all advanced by each launch; 0/1 = 1.
+                              Negative: GCM_ERR_ARG; > 1 with GCM_PE2D, GCM_PE25D or nranks > 1: GCM_ERR_UNSUPPORTED */
     double dx;             /* scalar grid spacing in metres (2-D models: both axes)              */
     double dy;             /* GCM_PE25D: geom.dy                            geometry.py:138      */
     double ptop;           /* GCM_PE25D: geom.ptop in Pa                    geometry.py:147      */
@@ -133,12 +136,23 @@ int gcm_destroy(gcm_handle *h);
 const char *gcm_last_error(const gcm_handle *h); /* h may be NULL: last create() failure */
 
 /* State transfer (host <-> device).  NULL pointers are skipped.  Fields a model
- * does not have must be NULL.  2-D models: all five are [H][W]; GCM_PE25D: p is
+ * does not have must be NULL.  2-D models: all five are [H][W] ([M][H][W] on an
+ * ensemble handle, members M > 1, here and in gcm_get_star / gcm_set_star); GCM_PE25D: p is
  * [H][W], the rest [L][H][W].  Reference tuple orders: (u,v,p[,t]) for the
  * shallow-water schemes, (p,u,v,t,q) for the primitive-equation ones.          */
 int gcm_set_state(gcm_handle *h, const double *p, const double *u, const double *v,
                   const double *t, const double *q);
 int gcm_get_state(gcm_handle *h, double *p, double *u, double *v, double *t, double *q);
+
+/* Ensembles (config.members > 1): gcm_members gives M (1 for any other handle).  gcm_set_member /
+ * gcm_get_member move member m's [H][W] fields alone (0 <= m < M, else GCM_ERR_ARG), so a caller can
+ * perturb or read one member without copying all M.  gcm_diag_members fills out[m] with gcm_diag's
+ * value of every member (n >= M), by one launch and one synchronisation; gcm_diag on an ensemble
+ * handle reduces over all members.  gcm_snapshot / gcm_restore cover all members.                  */
+int gcm_members(const gcm_handle *h);
+int gcm_set_member(gcm_handle *h, int m, const double *p, const double *u, const double *v,
+                   const double *t, const double *q);
+int gcm_get_member(gcm_handle *h, int m, double *p, double *u, double *v, double *t, double *q);
 
 /* One or more full Matsuno steps (predictor + corrector), state stays resident.
  * Stands behind matsumo_scheme / matsuno_timestep (files cited at gcm_model). */
@@ -189,6 +203,7 @@ typedef enum {
     GCM_DIAG_TV_P = 7, GCM_DIAG_TV_U = 8, GCM_DIAG_TV_V = 9, GCM_DIAG_TV_T = 10, GCM_DIAG_TV_Q = 11
 } gcm_diag_kind;
 int gcm_diag(gcm_handle *h, int kind, double *out);
+int gcm_diag_members(gcm_handle *h, int kind, double *out, int n);   /* one value per member, see gcm_members */
 /* The reductions of constants.py for callers that hold no handle: a host float64 array viewed as
  * [n_axis][n_inner] -> out3 = { get_total_variation (sum |x - roll(x, -1, 0)|, constants.py:105-108),
  * max x, mean x (the two reductions of courant_number, :111-112) }; a NaN anywhere in x makes all
