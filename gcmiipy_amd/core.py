@@ -48,6 +48,17 @@ def tracer_array(c, L, H, W):
     return a
 
 
+DTYPES = {"f64": _lib.F64, "f32": _lib.F32}
+
+
+def check_dtype(dtype):
+    """the real type of a handle: "f64" (default) or "f32" (GCM_SW2D, GCM_SW2D_TEMP, GCM_PE25D); ValueError
+    otherwise, before any device use"""
+    if not isinstance(dtype, str) or dtype not in DTYPES:
+        raise ValueError("dtype must be 'f64' or 'f32', got %r" % (dtype,))
+    return dtype
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -63,6 +74,7 @@ class Core:
                  variant=_lib.VARIANT_AUTO, geom=None, filter=True, nranks=1, rank=0,
                  global_height=None, row0=0, device=-1, stream=None, halo_steps=1, coriolis=False, dtype="f64",
                  members=1):
+        check_dtype(dtype)
         self.model, self.W, self.H, self.L = model, int(width), int(height), int(layers)
         # ensemble members (2-D models, single band): every field is (M, H, W) when M > 1
         self.members = max(int(members), 1)
@@ -85,7 +97,7 @@ class Core:
         cfg.device = device
         cfg.halo_steps = halo_steps
         cfg.members = int(members)
-        cfg.dtype = {"f64": _lib.F64, "f32": _lib.F32}[dtype]
+        cfg.dtype = DTYPES[dtype]
         self.dtype = dtype
         self.halo_steps = halo_steps
         cfg.dx = float(dx)

@@ -30,6 +30,8 @@ __device__ __forceinline__ double rcp(double x) {
     r = __builtin_fma(r, e, r);
     return r;
 }
+// fp32: v_rcp_f32 is 1 ulp
+__device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 // ---- (p / P0) ** kappa by table + short series --------------------------------------
 // p = 2^e m, m in [1,2); i = top 6 mantissa bits; rc_i ~ 1/c_i with c_i the midpoint of
@@ -68,6 +70,9 @@ __device__ __forceinline__ double exner(double p, const double *tab /* LDS */) {
     const bool ok = (hi >= 0) && (e >= -64) && (e <= 63);   // hi >= 0: sign bit clear
     return ok ? r : __builtin_nan("");
 }
+// fp32: the float64 table + series, rounded to float once.  (__powf expands to ~110 VALU instructions -- the fp32
+// kernels executed TWICE the vector instructions of the fp64 ones -- and is less accurate than one rounding.)
+__device__ __forceinline__ float exner(float p, const double *tab) { return (float)exner((double)p, tab); }
 
 // value of the wave's lane-1 / lane+1 (columns i-1 / i+1): wave64 DPP shifts,
 // two v_mov_b32_dpp per double, no LDS.  Lane 0 / 63 read 0 (bound_ctrl; no tied
@@ -84,49 +89,66 @@ __device__ __forceinline__ double from_east(double x) {
     hi = __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
 }
+// fp32 flavours: one DPP move per value
+__device__ __forceinline__ float from_west(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x138 /*wave_shr:1*/, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float from_east(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x130 /*wave_shl:1*/, 0xf, 0xf, true));
+}
+// fp32 with two columns per lane (the 120-column strip of sw2d_fused_kernel): lane L of a strip holds columns
+// 2L and 2L+1 as one vector, so that a row segment is one 8-byte request per lane.  Arithmetic on the vector is
+// elementwise (v_pk_* instructions); the helpers below apply the scalar ones per column.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 rcp(f32x2 x) { return f32x2{rcp(x.x), rcp(x.y)}; }
+__device__ __forceinline__ f32x2 exner(f32x2 p, const double *tab) { return f32x2{exner(p.x, tab), exner(p.y, tab)}; }
+// the column west of each: the west lane's second column, then the lane's own first; east likewise
+__device__ __forceinline__ f32x2 from_west(f32x2 x) { return f32x2{from_west(x.y), x.x}; }
+__device__ __forceinline__ f32x2 from_east(f32x2 x) { return f32x2{x.y, from_east(x.x)}; }
+// the word that holds the sign bit
+__device__ __forceinline__ int sign_word(double x) { return __double2hiint(x); }
+__device__ __forceinline__ int sign_word(float x) { return __float_as_int(x); }
 
 // ---- 2-D shallow water operators (matsuno_c_grid.py) -------------------------
 // names: c=(j,i) w=(j,i-1) e=(j,i+1) n=(j-1,i) s=(j+1,i) sw=(j+1,i-1)
 
 // advection_of_velocity_u, matsuno_c_grid.py:15-51
-__device__ __forceinline__ double adv_vel_u(double uc, double uw, double ue, double un, double us,
-                                            double vc, double vw, double vs, double vsw,
-                                            double h_dx) {
+template <typename T>
+__device__ __forceinline__ T adv_vel_u(T uc, T uw, T ue, T un, T us, T vc, T vw, T vs, T vsw, T h_dx) {
     // the reference's (a + b) / 2 factors are exact, so they are folded into h_dx = 0.5/dx
-    double u_ipj = ue + uc, u_imj = uw + uc, v_ijm = vw + vc, v_ijp = vsw + vs;
-    double du_ipj = ue - uc, du_imj = uc - uw, du_ijp = us - uc, du_ijm = uc - un;
+    T u_ipj = ue + uc, u_imj = uw + uc, v_ijm = vw + vc, v_ijp = vsw + vs;
+    T du_ipj = ue - uc, du_imj = uc - uw, du_ijp = us - uc, du_ijm = uc - un;
     return (u_ipj * du_ipj + u_imj * du_imj + v_ijp * du_ijp + v_ijm * du_ijm) * h_dx;
 }
 
 // advection_of_velocity_v, matsuno_c_grid.py:54-80
-__device__ __forceinline__ double adv_vel_v(double vc, double vw, double ve, double vn, double vs,
-                                            double uc, double un, double uw, double usw,
-                                            double h_dx) {
-    double v_ijp = vs + vc, v_ijm = vn + vc, u_ipj = uc + un, u_imj = uw + usw;
-    double dv_ipj = ve - vc, dv_imj = vc - vw, dv_ijp = vs - vc, dv_ijm = vc - vn;
+template <typename T>
+__device__ __forceinline__ T adv_vel_v(T vc, T vw, T ve, T vn, T vs, T uc, T un, T uw, T usw, T h_dx) {
+    T v_ijp = vs + vc, v_ijm = vn + vc, u_ipj = uc + un, u_imj = uw + usw;
+    T dv_ipj = ve - vc, dv_imj = vc - vw, dv_ijp = vs - vc, dv_ijm = vc - vn;
     return (u_ipj * dv_ipj + u_imj * dv_imj + v_ijp * dv_ijp + v_ijm * dv_ijm) * h_dx;
 }
 
 // geopotential_gradient_u / _v, matsuno_c_grid.py:97-106: (p[+1] - p) / dx * G
-__device__ __forceinline__ double geo_grad(double p_next, double pc, double g_dx) {
+template <typename T>
+__device__ __forceinline__ T geo_grad(T p_next, T pc, T g_dx) {
     return (p_next - pc) * g_dx;          // g_dx = G / dx folded on the host
 }
 
 // advection_of_geopotential, matsuno_c_grid.py:109-118
-__device__ __forceinline__ double adv_geo(double uc, double uw, double vc, double vn,
-                                          double pc, double pw, double pe, double pn, double ps,
-                                          double h_dx) {
-    double up_imj = (pw + pc) * uw;
-    double up_ipj = (pe + pc) * uc;
-    double vp_ijm = (pn + pc) * vn;
-    double vp_ijp = (ps + pc) * vc;
+template <typename T>
+__device__ __forceinline__ T adv_geo(T uc, T uw, T vc, T vn, T pc, T pw, T pe, T pn, T ps, T h_dx) {
+    T up_imj = (pw + pc) * uw;
+    T up_ipj = (pe + pc) * uc;
+    T vp_ijm = (pn + pc) * vn;
+    T vp_ijp = (ps + pc) * vc;
     return (up_ipj - up_imj) * h_dx + (vp_ijp - vp_ijm) * h_dx;
 }
 
 // finite_laplacian_2d * mu, viscosity.py:12-25
-__device__ __forceinline__ double visc_u(double uc, double uw, double ue, double un, double us,
-                                         double mu_dx2) {
-    double top = us + un + ue + uw - 4.0 * uc;
+template <typename T>
+__device__ __forceinline__ T visc_u(T uc, T uw, T ue, T un, T us, T mu_dx2) {
+    T top = us + un + ue + uw - T(4.0) * uc;
     return top * mu_dx2;                   // mu_dx2 = mu_air / dx^2 folded on the host
 }
 
@@ -136,39 +158,47 @@ __device__ __forceinline__ double visc_u(double uc, double uw, double ue, double
 // dx*dx (matsumo_temp.py:28-35) cancels exactly in  t* = (p t dx^2 - dt adv(p t dx^2)) /
 // (p* dx^2)  because adv() is linear, and Rd of 1/rho = Rd T / p is carried by the viscosity
 // constant (mu Rd / dx^2).  Both move results by O(1 ulp).
-struct Thermo { double t_over_p, geo, st; };
-__device__ __forceinline__ Thermo thermo(double p, double t, const double *tab, double rcp_p) {
-    double temp = t * exner(p, tab);           // t / (1e5/p)**kappa
-    Thermo r;
+// The table is float64 for either real type (exner()).
+template <typename T>
+struct Thermo { T t_over_p, geo, st; };
+template <typename T>
+__device__ __forceinline__ Thermo<T> thermo(T p, T t, const double *tab, T rcp_p) {
+    T temp = t * exner(p, tab);           // t / (1e5/p)**kappa
+    Thermo<T> r;
     r.t_over_p = temp * rcp_p;                 // 1/rho = Rd * (T / p)
-    r.geo = temp * (kRd / kG);                 // p / (G rho) = Rd T / G
+    r.geo = temp * T(kRd / kG);                // p / (G rho) = Rd T / G
     r.st = p * t;
     return r;
 }
-__device__ __forceinline__ Thermo thermo(double p, double t, const double *tab) {
+template <typename T>
+__device__ __forceinline__ Thermo<T> thermo(T p, T t, const double *tab) {
     return thermo(p, t, tab, rcp(p));
 }
 
 // ---- tracer face flux (two_d.py:103-116,135-149; flux_limiter.py:10-27) -----------
 // flux through the face between cells 0 and +1 along an axis, times dt/dx.
-template <bool LIMIT>
-__device__ __forceinline__ double face_flux(double vel, double qm1, double q0, double q1,
-                                            double q2, double dtdx) {
-    const bool pos = vel > 0.0;                       // strict >, as flux_limiter.py:24
+template <bool LIMIT, typename T>
+__device__ __forceinline__ T face_flux(T vel, T qm1, T q0, T q1, T q2, T dtdx) {
+    const bool pos = vel > T(0.0);                      // strict >, as flux_limiter.py:24
     // (q0 max(vel,0) + q1 min(vel,0)) dt/dx: one of the two products is a zero
-    const double vd = vel * dtdx;
-    const double f_low = (pos ? q0 : q1) * vd;
+    const T vd = vel * dtdx;
+    const T f_low = (pos ? q0 : q1) * vd;
     if (!LIMIT) return f_low;
-    const double f_high = vd * ((q0 + q1) * 0.5);
-    const double b = q1 - q0;
-    const double num = pos ? q0 - qm1 : q2 - q1;
+    const T f_high = vd * ((q0 + q1) * T(0.5));
+    const T b = q1 - q0;
+    const T num = pos ? q0 - qm1 : q2 - q1;
     // van_leer(r), r = num / b (0 where b == 0, flux_limiter.py:19):
     // (r + |r|) / (1 + |r|) = 2 |num| / (|b| + |num|) if num b > 0 else 0 -- one reciprocal
-    const double an = fabs(num), ab = fabs(b);
+    const T an = fabs(num), ab = fabs(b);
     // r > 0 <=> num and b are nonzero with equal signs (sign bits compared: no underflow)
-    const bool rpos = ((__double2hiint(num) ^ __double2hiint(b)) >= 0) && an > 0.0 && ab > 0.0;
-    const double phi = rpos ? (an + an) * rcp(ab + an) : 0.0;
+    const bool rpos = ((sign_word(num) ^ sign_word(b)) >= 0) && an > T(0.0) && ab > T(0.0);
+    const T phi = rpos ? (an + an) * rcp(ab + an) : T(0.0);
     return f_low + phi * (f_high - f_low);
+}
+template <bool LIMIT>
+__device__ __forceinline__ f32x2 face_flux(f32x2 vel, f32x2 qm1, f32x2 q0, f32x2 q1, f32x2 q2, f32x2 dtdx) {
+    return f32x2{face_flux<LIMIT>(vel.x, qm1.x, q0.x, q1.x, q2.x, dtdx.x),
+                 face_flux<LIMIT>(vel.y, qm1.y, q0.y, q1.y, q2.y, dtdx.y)};
 }
 
 }  // namespace gcm

@@ -30,7 +30,9 @@ struct gcm_handle {
     std::string err;
     std::vector<void *> allocs;
 
-    // 2-D models: per-field arrays of (H + 2*kGhost) rows; pointers address interior row 0
+    // 2-D models: per-field arrays of (H + 2*kGhost) rows; pointers address interior row 0.  An fp32 handle
+    // (GCM_SW2D / GCM_SW2D_TEMP with dtype GCM_F32) keeps float arrays at these addresses: esz = 4, and every
+    // offset into them goes through at() (elements of esz bytes)
     double *cur[GCM_NFIELDS] = {}, *nxt[GCM_NFIELDS] = {}, *star[GCM_NFIELDS] = {};
     double *geo = nullptr, *irho = nullptr, *sst = nullptr, *qtmp = nullptr;
     bool has[GCM_NFIELDS] = {};
@@ -46,7 +48,12 @@ struct gcm_handle {
     int variant = GCM_VARIANT_FUSED;
     int rows_per_band = 32;
     int M = 1;              // ensemble members (2-D models, single band)
-    long mstride = 0;       // doubles from one member's slab to the next: (H + 2G) W, rounded up to 256 B if M > 1
+    long mstride = 0;       // elements from one member's slab to the next: (H + 2G) W, rounded up to 256 B if M > 1
+    bool f32 = false;       // 2-D models: float storage and arithmetic (gcm_config.dtype == GCM_F32)
+    int esz = 8;            // bytes per element of the 2-D state
+    int cols = 1;           // fused kernel: columns per lane (2: fp32 with an even width, 120-column strips)
+    double *staging = nullptr;   // fp32 handles: float64 staging buffer of state transfers, staging_members members
+    int staging_members = 0;
 
     // diagnostics scratch
     double *diag_dev = nullptr;
@@ -98,21 +105,25 @@ static int diag_blocks_per_member(const gcm_handle *h) {
     return std::max(8, gcm_handle::kDiagBlocks / h->M);
 }
 
+// p + n elements of the handle's 2-D state (esz bytes each)
+static double *at(const gcm_handle *h, double *p, long n) { return (double *)((char *)p + n * h->esz); }
+
 static int alloc_field(gcm_handle *h, double **p) {
     // Every array starts a different multiple of 256 B past its (2 MiB-aligned) allocation: rows of a
     // power-of-two width would otherwise put the same (row, column) of all fields on the same HBM channel and
     // bank, and a wave of the fused kernel touches that element of ten arrays per row (tools/micro/copy_width.hip:
     // the bare access pattern moves 4-6 % faster with the arrays skewed).  GCM_ALLOC_SKEW=0 switches it off.
-    // An ensemble's members follow one another at mstride doubles (a whole number of 256-B lines, so that
-    // every member's rows start as a single handle's do); the skew is per field, as for one member.
+    // An ensemble's members follow one another at mstride elements (a whole number of 256-B lines, so that
+    // every member's rows start as a single handle's do); the skew is per field, as for one member.  Sizes
+    // in elements of esz bytes (fp32 handles: 4).
     static const long skew_unit = getenv("GCM_ALLOC_SKEW") ? atol(getenv("GCM_ALLOC_SKEW")) : 256;
     const size_t n = (size_t)(h->M - 1) * h->mstride + (size_t)(h->H + 2 * h->G) * h->W;
-    const size_t skew = (size_t)(skew_unit > 0 ? skew_unit : 0) * (h->allocs.size() % 16) / sizeof(double);
+    const size_t skew = (size_t)(skew_unit > 0 ? skew_unit : 0) * (h->allocs.size() % 16) / h->esz;
     void *d = nullptr;
-    HIPCHK(h, hipMalloc(&d, (n + skew) * sizeof(double)));
-    HIPCHK(h, hipMemsetAsync(d, 0, (n + skew) * sizeof(double), h->stream));
+    HIPCHK(h, hipMalloc(&d, (n + skew) * h->esz));
+    HIPCHK(h, hipMemsetAsync(d, 0, (n + skew) * h->esz, h->stream));
     h->allocs.push_back(d);
-    *p = (double *)d + skew + (size_t)h->G * h->W;
+    *p = at(h, (double *)d, (long)(skew + (size_t)h->G * h->W));
     return GCM_OK;
 }
 
@@ -177,6 +188,12 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
         return fail(nullptr, GCM_ERR_UNSUPPORTED, "gcm_create: members > 1 needs GCM_SW2D or GCM_SW2D_TEMP");
     if (cfg->members > 1 && cfg->nranks > 1)
         return fail(nullptr, GCM_ERR_UNSUPPORTED, "gcm_create: members > 1 is not available on latitude bands");
+    const bool sw2d = cfg->model == GCM_SW2D || cfg->model == GCM_SW2D_TEMP;
+    if (sw2d && cfg->dtype != GCM_F64 && cfg->dtype != GCM_F32)
+        return fail(nullptr, GCM_ERR_ARG, "gcm_create: bad dtype");
+    // the ghost-row exchange copies 8-byte words (launch_seg_copy): G rows x (even W) floats is a whole number of them
+    if (sw2d && cfg->dtype == GCM_F32 && cfg->nranks > 1 && cfg->width % 2)
+        return fail(nullptr, GCM_ERR_UNSUPPORTED, "gcm_create: fp32 latitude bands need an even width");
     if (gcm_device_count() < 1)
         return fail(nullptr, GCM_ERR_NODEVICE,
                     "gcm_create: no HIP device visible; libgcmcore has no CPU fallback");
@@ -188,8 +205,11 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
     h->wrap = cfg->nranks == 1;
     h->G = kGhost * hsteps;
     h->M = cfg->members > 1 ? cfg->members : 1;
+    h->f32 = sw2d && cfg->dtype == GCM_F32;
+    h->esz = h->f32 ? 4 : 8;
     h->mstride = (long)(h->H + 2 * h->G) * h->W;
-    if (h->M > 1) h->mstride = (h->mstride + 31) / 32 * 32;
+    const long line = 256 / h->esz;                      // elements per 256-B line
+    if (h->M > 1) h->mstride = (h->mstride + line - 1) / line * line;
     h->stream = (hipStream_t)cfg->stream;
     int rc = GCM_OK;
     auto bail = [&](int code, const std::string &m) {
@@ -237,7 +257,10 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
                 h->allocs.push_back(d);
                 h->exner_tab = (double *)d;
             }
-            h->rows_per_band = sw2d_fused_rows_per_band(h->W, h->H, temp, h->has[GCM_Q] ? cfg->tracer : 0, h->wrap, h->M);
+            const int tr = h->has[GCM_Q] ? cfg->tracer : 0;
+            if (h->f32) h->cols = sw2d_fused_cols<float>(h->W, h->H, temp, tr, h->wrap, h->M);   // 
+            h->rows_per_band = h->f32 ? sw2d_fused_rows_per_band<float>(h->W, h->H, temp, tr, h->wrap, h->M, h->cols)
+                                      : sw2d_fused_rows_per_band<double>(h->W, h->H, temp, tr, h->wrap, h->M);
             break;
         }
         case GCM_PE2D: {
@@ -283,18 +306,46 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
 }
 
 // ------------------------------------------------------------------ state transfer
-// member < 0: all members ([M][H][W] host arrays; the device slabs are mstride doubles apart, so one 2-D copy
-// per field), else that member alone ([H][W])
+// member < 0: all members ([M][H][W] host arrays; the device slabs are mstride elements apart, so one 2-D copy
+// per field), else that member alone ([H][W]).  fp32 handles: through a float64 staging buffer, one conversion
+// launch per field and chunk of members (rounded to nearest-even up, widened exactly down).  The buffer holds
+// as many members as fit 16 MB, at least one: it does not grow with the ensemble.
 static int xfer(gcm_handle *h, double *const dev[GCM_NFIELDS], const double *const hostc[GCM_NFIELDS],
                 double *const hostm[GCM_NFIELDS], bool to_device, int member = -1) {
     const size_t bytes = (size_t)h->H * h->W * sizeof(double), pitch = (size_t)h->mstride * sizeof(double);
+    if (h->f32 && !h->staging) {
+        const size_t fit = ((size_t)16 << 20) / bytes;
+        h->staging_members = (int)std::max<size_t>(1, std::min<size_t>(fit, (size_t)h->M));
+        void *d = nullptr;
+        HIPCHK(h, hipMalloc(&d, bytes * h->staging_members));
+        h->allocs.push_back(d);
+        h->staging = (double *)d;
+    }
     for (int f = 0; f < GCM_NFIELDS; ++f) {
         const void *src = hostc ? (const void *)hostc[f] : (const void *)hostm[f];
         if (!src) continue;
         if (!h->has[f] || !dev[f])
             return fail(h, GCM_ERR_ARG, "state transfer: field not part of this model");
-        double *d = dev[f] + (size_t)(member < 0 ? 0 : member) * h->mstride;
-        if (member >= 0 || h->M == 1) {
+        double *d = at(h, dev[f], (long)(member < 0 ? 0 : member) * h->mstride);
+        if (h->f32) {
+            const int nm = member < 0 ? h->M : 1;
+            const long n = (long)h->H * h->W;
+            // (each chunk's use of the staging buffer follows the previous one's in stream order)
+            for (int m0 = 0; m0 < nm; m0 += h->staging_members) {
+                const int k = std::min(h->staging_members, nm - m0);
+                float *dm = (float *)at(h, d, (long)m0 * h->mstride);
+                if (to_device) {
+                    HIPCHK(h, hipMemcpyAsync(h->staging, hostc[f] + (size_t)m0 * n, bytes * k, hipMemcpyHostToDevice,
+                                             h->stream));
+                    launch_narrow(dm, h->mstride, h->staging, n, k, h->stream);
+                } else {
+                    launch_widen(h->staging, dm, h->mstride, n, k, h->stream);
+                    HIPCHK(h, hipMemcpyAsync(hostm[f] + (size_t)m0 * n, h->staging, bytes * k, hipMemcpyDeviceToHost,
+                                             h->stream));
+                }
+                HIPCHK(h, hipGetLastError());
+            }
+        } else if (member >= 0 || h->M == 1) {
             if (to_device)
                 HIPCHK(h, hipMemcpyAsync(d, hostc[f], bytes, hipMemcpyHostToDevice, h->stream));
             else
@@ -388,6 +439,27 @@ static Sw2dArgs base_args(gcm_handle *h, double dt) {
     return a;
 }
 
+// The 2-D launchers on the handle's real type: an fp32 handle's argument block is the same one, narrowed.
+static void run_derive(const gcm_handle *h, const Sw2dArgs &a, hipStream_t s) {
+    if (h->f32) launch_sw2d_derive(narrow_args(a), s);
+    else launch_sw2d_derive(a, s);
+}
+static void run_stage(const gcm_handle *h, const Sw2dArgs &a, bool temp, hipStream_t s) {
+    if (h->f32) launch_sw2d_stage(narrow_args(a), temp, s);
+    else launch_sw2d_stage(a, temp, s);
+}
+static void run_tracer_axis(const gcm_handle *h, const Sw2dArgs &a, int axis, bool limit, const double *q_in,
+                            double *q_out, hipStream_t s) {
+    if (h->f32) launch_tracer_axis(narrow_args(a), axis, limit, (const float *)q_in, (float *)q_out, s);
+    else launch_tracer_axis(a, axis, limit, q_in, q_out, s);
+}
+static bool run_fused(const gcm_handle *h, const Sw2dArgs &a, bool temp, int tracer, hipStream_t s) {
+    return h->f32 ? launch_sw2d_fused(narrow_args(a), temp, tracer, s, h->cols) : launch_sw2d_fused(a, temp, tracer, s);
+}
+static bool run_fused2(const gcm_handle *h, const Sw2dArgs &a, hipStream_t s) {
+    return h->f32 ? launch_sw2d_fused2(narrow_args(a), s) : launch_sw2d_fused2(a, s);
+}
+
 // gcm_set_physics: the radiation kernel's tables in place before a run queues anything (no-op without physics)
 static int physics_tables(gcm_handle *h) {
     if (!h->phys_on) return GCM_OK;
@@ -446,12 +518,12 @@ static void staged_stage(gcm_handle *h, int stage, double dt, int j0, int j1, hi
             d.j0 = j0 - 1;
             d.j1 = j1 + 1;
         }
-        launch_sw2d_derive(d, s);
+        run_derive(h, d, s);
         a.sgeo = h->geo;
         a.sirho = h->irho;
         a.sst = h->sst;
     }
-    launch_sw2d_stage(a, temp, s);
+    run_stage(h, a, temp, s);
 }
 
 static void staged_tracer(gcm_handle *h, double dt, int j0, int j1, hipStream_t s) {
@@ -460,8 +532,8 @@ static void staged_tracer(gcm_handle *h, double dt, int j0, int j1, hipStream_t 
     Sw2dArgs a = base_args(h, dt);
     a.j0 = j0;
     a.j1 = j1;
-    launch_tracer_axis(a, 0, lim, h->cur[GCM_Q], h->qtmp, s);
-    launch_tracer_axis(a, 1, lim, h->qtmp, h->nxt[GCM_Q], s);
+    run_tracer_axis(h, a, 0, lim, h->cur[GCM_Q], h->qtmp, s);
+    run_tracer_axis(h, a, 1, lim, h->qtmp, h->nxt[GCM_Q], s);
 }
 
 // one full Matsuno step producing rows [j0, j1) of nxt from cur (ghost rows already valid)
@@ -478,7 +550,7 @@ static void step_rows(gcm_handle *h, double dt, int j0, int j1, hipStream_t s) {
         a.j0 = j0;
         a.j1 = j1;
         tick(h, s);
-        if (!launch_sw2d_fused(a, temp, h->has[GCM_Q] ? h->cfg.tracer : 0, s)) h->launch_refused = true;
+        if (!run_fused(h, a, temp, h->has[GCM_Q] ? h->cfg.tracer : 0, s)) h->launch_refused = true;
         tick(h, s);
     } else {
         // the predicted state is needed one row beyond the rows produced
@@ -524,7 +596,7 @@ int gcm_step(gcm_handle *h, int nsteps, double dt) {
             a.op = h->nxt[GCM_P];
             a.j0 = 0;
             a.j1 = h->H;
-            if (!launch_sw2d_fused2(a, h->stream)) break;
+            if (!run_fused2(h, a, h->stream)) break;
             swap_state(h);
             n0 += 2;
         }
@@ -642,7 +714,7 @@ size_t gcm_halo_bytes(const gcm_handle *h) {
     if (h->pe) return pe25d_halo_bytes(h->pe);
     int nf = 0;
     for (int f = 0; f < GCM_NFIELDS; ++f) nf += h->has[f];
-    return (size_t)nf * h->G * h->W * sizeof(double);
+    return (size_t)nf * h->G * h->W * h->esz;
 }
 
 }  // extern "C"
@@ -652,15 +724,15 @@ size_t gcm_halo_bytes(const gcm_handle *h) {
 static int halo_segments(gcm_handle *h, bool pack, int side, void *dev_buf, SegCopy *c) {
     if (h->pe) return pe25d_halo_segments(h->pe, pack, side, dev_buf, c, &h->err);
     double *b = (double *)dev_buf;
-    const size_t n = (size_t)h->G * h->W;
+    const long n = (long)h->G * h->W;                    // elements; SegCopy counts 8-byte words (fp32: even W)
     for (int f = 0; f < GCM_NFIELDS; ++f) {
         if (!h->has[f]) continue;
-        double *edge = side == 0 ? h->cur[f] : h->cur[f] + (size_t)(h->H - h->G) * h->W;
-        double *ghost = side == 0 ? h->cur[f] - n : h->cur[f] + (size_t)h->H * h->W;
+        double *edge = side == 0 ? h->cur[f] : at(h, h->cur[f], (long)(h->H - h->G) * h->W);
+        double *ghost = side == 0 ? at(h, h->cur[f], -n) : at(h, h->cur[f], (long)h->H * h->W);
         c->src[c->nseg] = pack ? edge : b;
         c->dst[c->nseg] = pack ? b : ghost;
-        c->n[c->nseg++] = (long)n;
-        b += n;
+        c->n[c->nseg++] = n * h->esz / 8;
+        b = at(h, b, n);
     }
     return GCM_OK;
 }
@@ -716,11 +788,11 @@ int gcm_snapshot(gcm_handle *h) {
         if (!h->has[f]) continue;
         if (!h->snap[f]) {
             void *d = nullptr;
-            HIPCHK(h, hipMalloc(&d, n * sizeof(double)));
+            HIPCHK(h, hipMalloc(&d, n * h->esz));
             h->allocs.push_back(d);
             h->snap[f] = (double *)d;
         }
-        HIPCHK(h, hipMemcpyAsync(h->snap[f], h->cur[f] - (size_t)h->G * h->W, n * sizeof(double),
+        HIPCHK(h, hipMemcpyAsync(h->snap[f], at(h, h->cur[f], -(long)h->G * h->W), n * h->esz,
                                  hipMemcpyDeviceToDevice, h->stream));
     }
     h->snap_since_exchange = h->since_exchange;
@@ -735,7 +807,7 @@ int gcm_restore(gcm_handle *h) {
     for (int f = 0; f < GCM_NFIELDS; ++f) {
         if (!h->has[f]) continue;
         if (!h->snap[f]) return fail(h, GCM_ERR_STATE, "gcm_restore: no snapshot taken");
-        HIPCHK(h, hipMemcpyAsync(h->cur[f] - (size_t)h->G * h->W, h->snap[f], n * sizeof(double),
+        HIPCHK(h, hipMemcpyAsync(at(h, h->cur[f], -(long)h->G * h->W), h->snap[f], n * h->esz,
                                  hipMemcpyDeviceToDevice, h->stream));
     }
     h->since_exchange = h->snap_since_exchange;
@@ -1126,9 +1198,15 @@ static int diag_members(gcm_handle *h, int kind, double *per_member, double *all
     const bool tv = kind >= GCM_DIAG_TV_P && kind <= GCM_DIAG_TV_Q;
     const int nb = diag_blocks_per_member(h), M = h->M;
     const long n = (long)h->H * h->W;
-    if (tv)
+    if (tv && h->f32)
+        hipLaunchKernelGGL(tv_kernel<float>, dim3(nb, M), dim3(256), 0, h->stream, (const float *)h->cur[f], 1L,
+                           (long)h->H, (long)h->W, 1, h->diag_dev, h->mstride);
+    else if (tv)
         hipLaunchKernelGGL(tv_kernel<double>, dim3(nb, M), dim3(256), 0, h->stream, h->cur[f], 1L, (long)h->H, (long)h->W,
                            1, h->diag_dev, h->mstride);
+    else if (h->f32)
+        hipLaunchKernelGGL(diag_kernel<float>, dim3(nb, M), dim3(256), 0, h->stream, (const float *)h->cur[f], n,
+                           h->diag_dev, h->mstride);
     else
         hipLaunchKernelGGL(diag_kernel<double>, dim3(nb, M), dim3(256), 0, h->stream, h->cur[f], n, h->diag_dev,
                            h->mstride);
@@ -1173,6 +1251,9 @@ int gcm_diag(gcm_handle *h, int kind, double *out) {
     const void *xv = nullptr;
     if (h->pe) {
         xv = pe25d_field(h->pe, f, &n, &f32);
+    } else if (h->f32) {
+        xv = h->cur[f];
+        f32 = 1;
     } else {
         x = h->cur[f];
     }

@@ -20,12 +20,10 @@ namespace gcm {
 
 constexpr int kMaxSeg = 4;      // level segments of the update kernel (short bands)
 constexpr int kMaxEdgeCols = 96; // K3: columns that are multiples of 64 (W <= 5120 + rounding)
-// real-type specific pieces: reciprocal and (p/P0)**kappa.  fp32: v_rcp_f32 is 1 ulp; the Exner function goes
-// through the float64 table + series of gcm_math.h and is rounded to float once.  (__powf, which this used
-// to be, expands to ~110 VALU instructions -- the fp32 update kernel executed TWICE the vector instructions
-// of the fp64 one, profiles/r03 -- and is less accurate than one rounding of the float64 value.)
-__device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float exner(float p, const double *tab) { return (float)exner((double)p, tab); }
+// real-type specific pieces -- reciprocal, (p/P0)**kappa, the DPP row shifts -- are overloaded in gcm_math.h.
+// fp32: v_rcp_f32 is 1 ulp; the Exner function goes through the float64 table + series and is rounded to float
+// once.  (__powf, which this used to be, expands to ~110 VALU instructions -- the fp32 update kernel executed
+// TWICE the vector instructions of the fp64 one, profiles/r03 -- and is less accurate than one rounding.)
 
 template <typename T>
 struct PeArgsT {
@@ -144,10 +142,6 @@ __device__ __forceinline__ T phi_up(T phi_lo, T t_lo, T t_hi, T ex_lo, T ex_hi) 
 #pragma clang fp contract(off)
     const T stp = stp_of(t_lo, t_hi, ex_lo, ex_hi);
     return phi_lo + stp;
-}
-// value of the wave's lane+1 (column i+1), fp32 flavour of gcm_math.h's from_east
-__device__ __forceinline__ float from_east(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x130 /*wave_shl:1*/, 0xf, 0xf, true));
 }
 
 // ---------------------------------------------------------------- K2b', the 2-D form of pit

@@ -25,9 +25,7 @@ namespace gcm {
 //   * sigma-dot at (j, i+1) is the east lane's value (DPP); at (j+1, i) it is rebuilt from the tile;
 //   * the fluxes through the upper faces are the lower-face fluxes of the level above, carried.
 // A row of the stage state leaves HBM (R+2)/R times instead of up to three times.
-__device__ __forceinline__ float from_west(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x138 /*wave_shr:1*/, 0xf, 0xf, true));
-}
+// (the fp32 DPP row shifts are gcm_math.h's, shared with the 2-D kernels)
 // slots of one level tile, in units of 64 lanes
 template <int R> struct UpdTile {
     static constexpr int kMain = 0;                      // su, sv, st, sq, spu: R+2 slots each (0 = row above the group)

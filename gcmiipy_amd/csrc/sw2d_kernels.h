@@ -10,36 +10,69 @@ constexpr int kGhost = 2;        // ghost rows on each side of a latitude band
 constexpr int kStripCols = 60;   // output columns per wave in the fused kernel (64 lanes - 2x2 halo)
 
 // Pointers address interior row 0 of member 0; with wrap_j == 0 rows -2,-1 and H,H+1 are ghost rows.
-// Member m's field starts mstride doubles after member m-1's (an ensemble handle, members > 1).
-struct Sw2dArgs {
-    const double *bu, *bv, *bp, *bt, *bq;   // base (time n) state
-    const double *su, *sv, *sp, *st;        // stage state the tendencies are evaluated on
-    const double *sgeo, *sirho, *sst;       // staged TEMP: geo, T/p, p*t of the stage state
-    double *ou, *ov, *op, *ot, *oq;         // output
-    double *dgeo, *dirho, *dst;             // derive kernel outputs
-    const double *exner_tab;                // device copy of the 256-double exner table
+// Member m's field starts mstride elements after member m-1's (an ensemble handle, members > 1).
+// T is the real type of the state and of the arithmetic: double, or float for an fp32 handle.
+template <typename T>
+struct Sw2dArgsT {
+    const T *bu, *bv, *bp, *bt, *bq;        // base (time n) state
+    const T *su, *sv, *sp, *st;             // stage state the tendencies are evaluated on
+    const T *sgeo, *sirho, *sst;            // staged TEMP: geo, T/p, p*t of the stage state
+    T *ou, *ov, *op, *ot, *oq;              // output
+    T *dgeo, *dirho, *dst;                  // derive kernel outputs
+    const double *exner_tab;                // device copy of the 256-double exner table (float64 for either T)
     int W, H;                               // columns, rows owned
     int wrap_j;                             // 1: rows wrap modulo H (single band); 0: ghost rows
     int j0, j1;                             // row range [j0, j1) to produce
     int rows_per_band;                      // fused: output rows per wave
     int members;                            // ensemble members M (>= 1): one launch advances all of them
-    long mstride;                           // doubles from one member's slab to the next (every pointer above)
-    double dt, dx, inv_dx, dx2, inv_dx2;
-    double h_dx;                            // 0.5 / dx (exact halving folded in)
-    double dtdx;                            // dt / dx
-    double g_dx, mu_dx2, inv_dx2_;          // G / dx, mu_air Rd / dx^2, 1 / dx^2
+    long mstride;                           // elements from one member's slab to the next (every pointer above)
+    T dt, dx, inv_dx, dx2, inv_dx2;
+    T h_dx;                                 // 0.5 / dx (exact halving folded in)
+    T dtdx;                                 // dt / dx
+    T g_dx, mu_dx2, inv_dx2_;               // G / dx, mu_air Rd / dx^2, 1 / dx^2
 };
+using Sw2dArgs = Sw2dArgsT<double>;
 
+// an fp32 handle's argument block: the same addresses, the scalars (formed in float64) rounded once
+inline Sw2dArgsT<float> narrow_args(const Sw2dArgs &a) {
+    Sw2dArgsT<float> f{};
+    auto cp = [](auto *p) { return (float *)p; };
+    f.bu = cp(a.bu); f.bv = cp(a.bv); f.bp = cp(a.bp); f.bt = cp(a.bt); f.bq = cp(a.bq);
+    f.su = cp(a.su); f.sv = cp(a.sv); f.sp = cp(a.sp); f.st = cp(a.st);
+    f.sgeo = cp(a.sgeo); f.sirho = cp(a.sirho); f.sst = cp(a.sst);
+    f.ou = cp(a.ou); f.ov = cp(a.ov); f.op = cp(a.op); f.ot = cp(a.ot); f.oq = cp(a.oq);
+    f.dgeo = cp(a.dgeo); f.dirho = cp(a.dirho); f.dst = cp(a.dst);
+    f.exner_tab = a.exner_tab;
+    f.W = a.W; f.H = a.H; f.wrap_j = a.wrap_j; f.j0 = a.j0; f.j1 = a.j1;
+    f.rows_per_band = a.rows_per_band; f.members = a.members; f.mstride = a.mstride;
+    f.dt = (float)a.dt; f.dx = (float)a.dx; f.inv_dx = (float)a.inv_dx; f.dx2 = (float)a.dx2;
+    f.inv_dx2 = (float)a.inv_dx2; f.h_dx = (float)a.h_dx; f.dtdx = (float)a.dtdx; f.g_dx = (float)a.g_dx;
+    f.mu_dx2 = (float)a.mu_dx2; f.inv_dx2_ = (float)a.inv_dx2_;
+    return f;
+}
+
+// Launchers, instantiated for T = double (sw2d_kernels.hip) and T = float (sw2d_kernels_f32.hip).
 // staged variant
-void launch_sw2d_stage(const Sw2dArgs &a, bool temp, hipStream_t s);
-void launch_sw2d_derive(const Sw2dArgs &a, hipStream_t s);            // p,t -> geo, 1/rho, scaled_t
-void launch_tracer_axis(const Sw2dArgs &a, int axis, bool limit, const double *q_in,
-                        double *q_out, hipStream_t s);
+template <typename T> void launch_sw2d_stage(const Sw2dArgsT<T> &a, bool temp, hipStream_t s);
+template <typename T> void launch_sw2d_derive(const Sw2dArgsT<T> &a, hipStream_t s);   // p,t -> geo, 1/rho, scaled_t
+template <typename T>
+void launch_tracer_axis(const Sw2dArgsT<T> &a, int axis, bool limit, const T *q_in, T *q_out, hipStream_t s);
 // fused variant: predictor + corrector (+ both tracer passes) in one launch
-bool launch_sw2d_fused(const Sw2dArgs &a, bool temp, int tracer, hipStream_t s);   // false: the launch was refused
-int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap, int members = 1);
+// cols: columns per lane, 1 (60-column strips) or 2 (T = float with an even width: 120-column strips of 8-byte
+// requests, so that a row segment is 480 B as at fp64)
+template <typename T>
+bool launch_sw2d_fused(const Sw2dArgsT<T> &a, bool temp, int tracer, hipStream_t s, int cols = 1);   // false: refused
+template <typename T>
+int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap, int members = 1, int cols = 1);
+// the columns per lane a handle's fused launches use: 1 for double and odd widths; float: 2 once the grid (all
+// members) fills the chip, GCM_SW2D_F32_COLS=1 / 2 overrides
+template <typename T> int sw2d_fused_cols(int W, int H, bool temp, int tracer, bool wrap, int members);
 // GCM_SW2D, single band, short bands (small grids): TWO steps in one launch; false if not applicable
-bool launch_sw2d_fused2(const Sw2dArgs &a, hipStream_t s);
+template <typename T> bool launch_sw2d_fused2(const Sw2dArgsT<T> &a, hipStream_t s);
+// fp32 handles: float64 host arrays <-> the device state through a float64 staging buffer; M slabs of n elements,
+// `pitch` elements apart on the device and n apart in the staging buffer
+void launch_narrow(float *dst, long pitch, const double *src, long n, int M, hipStream_t s);
+void launch_widen(double *dst, const float *src, long pitch, long n, int M, hipStream_t s);
 
 // GCM_PE2D: one Euler stage; base/stage/out are {p,u,v,t,q} interior pointers (wrap only)
 void launch_pe2d_stage(const double *const base[5], const double *const stage[5], double *const out[5],
@@ -49,7 +82,7 @@ void launch_pe2d_stage(const double *const base[5], const double *const stage[5]
 void build_exner_table(double *tab);
 
 // ghost rows for a single band that is stepped with wrap_j == 0 (tests) and halo pack/unpack
-void launch_copy_rows(double *dst, const double *src, int W, int nrows, hipStream_t s);
+template <typename T> void launch_copy_rows(T *dst, const T *src, int W, int nrows, hipStream_t s);
 
 // up to 5 contiguous segments copied by ONE launch (ghost-row pack / unpack of all fields)
 struct SegCopy {          // up to (5 fields + the ground temperature) x 2 sides in one launch

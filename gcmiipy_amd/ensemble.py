@@ -8,11 +8,14 @@ per step advances all of them -- M small grids fill the chip where one leaves mo
     u, v, p, t, q = ensemble.matsumo_temp_scheme(u, v, p, t, dx, dt, q=q, tracer="van_leer")
     u, v, p = ensemble.run(u, v, p, dx, dt, steps, callback=cb, every=10)
     cn = ensemble.courant_numbers(p, u, dx, dt)                      # (M,)
+
+Every function takes a keyword-only dtype="f64"; "f32" runs a float32 handle (the state rounded to
+float32 on the way in, float64 arrays of float32 values back) that holds twice the members per byte.
 """
 import numpy as np
 
 from . import _lib
-from .core import Core, as_f64
+from .core import Core, as_f64, check_dtype
 from .matsumo_temp import TRACERS
 from .units import strip, scalar, attach
 
@@ -64,24 +67,26 @@ def _tracer(q, tracer):
     return TRACERS[tracer]
 
 
-def matsumo_scheme(u, v, p, dx, dt):
+def matsumo_scheme(u, v, p, dx, dt, *, dtype="f64"):
     """matsuno_c_grid.matsumo_scheme on every member: one Matsuno step; takes and returns (u, v, p), each
     (M, H, W).  Inputs are not modified."""
+    check_dtype(dtype)
     (um, vm, pm), (uu, vu, pu) = _members((("u", u), ("v", v), ("p", p)))
-    c = _core(_lib.SW2D, um.shape, scalar(dx))
+    c = _core(_lib.SW2D, um.shape, scalar(dx), dtype=dtype)
     c.set_state(p=_in(c, pm), u=_in(c, um), v=_in(c, vm))
     c.step(1, scalar(dt))
     pn, un, vn, _, _ = (_out(c, x) for x in c.get_state((_lib.P, _lib.U, _lib.V)))
     return attach(un, uu), attach(vn, vu), attach(pn, pu)
 
 
-def matsumo_temp_scheme(u, v, p, t, dx, dt, q=None, tracer="van_leer"):
+def matsumo_temp_scheme(u, v, p, t, dx, dt, q=None, tracer="van_leer", *, dtype="f64"):
     """matsumo_temp.matsumo_scheme on every member -> (u, v, p, t); with a tracer q (M, H, W) also
     advected by the time-n winds (matsumo_temp.matsumo_scheme_with_tracer) -> (u, v, p, t, q)."""
+    check_dtype(dtype)
     named = [("u", u), ("v", v), ("p", p), ("t", t)] + ([("q", q)] if q is not None else [])
     mags, units = _members(named)
     tr = _tracer(q, tracer)
-    c = _core(_lib.SW2D_TEMP, mags[0].shape, scalar(dx), tracer=tr)
+    c = _core(_lib.SW2D_TEMP, mags[0].shape, scalar(dx), tracer=tr, dtype=dtype)
     um, vm, pm, tm = mags[:4]
     c.set_state(p=_in(c, pm), u=_in(c, um), v=_in(c, vm), t=_in(c, tm), q=_in(c, mags[4]) if q is not None else None)
     c.step(1, scalar(dt))
@@ -92,12 +97,13 @@ def matsumo_temp_scheme(u, v, p, t, dx, dt, q=None, tracer="van_leer"):
     return tuple(out)
 
 
-def run(u, v, p, dx, dt, steps, t=None, q=None, tracer="van_leer", callback=None, every=1):
+def run(u, v, p, dx, dt, steps, t=None, q=None, tracer="van_leer", callback=None, every=1, *, dtype="f64"):
     """Device-resident driver loop over all members (matsuno_c_grid.run with a member axis; with t,
     GCM_SW2D_TEMP, and with q its tracer): `steps` Matsuno steps, the state stays in HBM between them.
     callback(i, u, v, p[, t[, q]]) every `every` steps with (M, H, W) arrays.  The loop ends early once
     every member carries a NaN in u (a member that blows up does not stop the others).
     -> (u, v, p[, t[, q]])"""
+    check_dtype(dtype)
     named = [("u", u), ("v", v), ("p", p)]
     if t is not None:
         named.append(("t", t))
@@ -109,7 +115,7 @@ def run(u, v, p, dx, dt, steps, t=None, q=None, tracer="van_leer", callback=None
     tr = _tracer(q, tracer)
     M, H, W = mags[0].shape
     model = _lib.SW2D if t is None else _lib.SW2D_TEMP
-    c = Core(model, W, H, dx=scalar(dx), tracer=tr, members=M)
+    c = Core(model, W, H, dx=scalar(dx), tracer=tr, members=M, dtype=dtype)
     fields = (_lib.U, _lib.V, _lib.P, _lib.T, _lib.Q)[:len(named)]
 
     def state():
@@ -132,10 +138,11 @@ def run(u, v, p, dx, dt, steps, t=None, q=None, tracer="van_leer", callback=None
         c.close()
 
 
-def courant_numbers(p, u, dx, dt):
+def courant_numbers(p, u, dx, dt, *, dtype="f64"):
     """matsuno_c_grid.courant_number of every member, (M,): (max u + sqrt(mean p g)) dt / dx by device
     reductions (one launch and one synchronisation per reduction for all members)."""
+    check_dtype(dtype)
     (pm, um), _ = _members((("p", p), ("u", u)))
-    c = _core(_lib.SW2D, um.shape, scalar(dx))
+    c = _core(_lib.SW2D, um.shape, scalar(dx), dtype=dtype)
     c.set_state(p=_in(c, pm), u=_in(c, um), v=_in(c, np.zeros_like(um)))
     return (c.diag_members(_lib.DIAG_MAX_U) + np.sqrt(c.diag_members(_lib.DIAG_MEAN_P) * 9.8)) * scalar(dt) / scalar(dx)

@@ -89,8 +89,13 @@ typedef struct {
     int32_t global_height;
     int32_t row0;
     int32_t device;        /* HIP device ordinal; -1 = current                                   */
-    int32_t dtype;         /* gcm_dtype: GCM_F64 (default) or GCM_F32 (GCM_PE25D only: arithmetic and
-                              storage in fp32 for the tolerance sweep; the host API stays float64) */
+    int32_t dtype;         /* gcm_dtype: GCM_F64 (default) or GCM_F32: arithmetic and storage in fp32.
+                              Honoured by GCM_PE25D, GCM_SW2D and GCM_SW2D_TEMP (any tracer, variant,
+                              ensemble or band); GCM_PE2D and the stand-alone operators stay fp64.  The
+                              host API stays float64: uploads round to nearest-even, downloads widen
+                              exactly.  Other values: GCM_ERR_ARG from GCM_SW2D, GCM_SW2D_TEMP and
+                              GCM_PE25D (GCM_PE2D ignores the field).  fp32 2-D latitude bands of odd
+                              width: GCM_ERR_UNSUPPORTED                                           */
     int32_t halo_steps;    /* 2-D bands: Matsuno steps per ghost-row exchange (ghost depth = 2 *
                               halo_steps rows per side, deep-halo communication avoiding); 0/1 = 1 */
     int32_t members;       /* ensemble members M of GCM_SW2D / GCM_SW2D_TEMP (single band): M independent states
