@@ -138,6 +138,7 @@ SYMBOLS = {
     "gcm_set_tracers": (C.c_int, [_H, C.c_int, C.c_void_p]),
     "gcm_get_tracers": (C.c_int, [_H, C.c_int, C.c_void_p]),
     "gcm_tracer_count": (C.c_int, [_H]),
+    "gcm_set_band_tracers": (C.c_int, [_H, C.c_int]),
 }
 
 

@@ -73,8 +73,16 @@ class Core:
     def __init__(self, model, width, height, layers=1, dx=0.0, tracer=_lib.TRACER_NONE,
                  variant=_lib.VARIANT_AUTO, geom=None, filter=True, nranks=1, rank=0,
                  global_height=None, row0=0, device=-1, stream=None, halo_steps=1, coriolis=False, dtype="f64",
-                 members=1):
+                 members=1, band_tracers=0):
+        """band_tracers: a GCM_PE25D latitude band (nranks > 1) that carries that many passive tracers
+        (gcm_set_band_tracers, right after gcm_create: the ghost-row message and halo_bytes() include them)"""
         check_dtype(dtype)
+        band_tracers = int(band_tracers)
+        if not 0 <= band_tracers <= _lib.MAX_TRACERS:
+            raise ValueError("band_tracers=%d: 0 .. %d" % (band_tracers, _lib.MAX_TRACERS))
+        if band_tracers > 0 and (model != _lib.PE25D or nranks <= 1):
+            raise ValueError("band_tracers needs a GCM_PE25D latitude band (nranks > 1); a single domain takes "
+                             "set_tracers directly")
         self.model, self.W, self.H, self.L = model, int(width), int(height), int(layers)
         # ensemble members (2-D models, single band): every field is (M, H, W) when M > 1
         self.members = max(int(members), 1)
@@ -82,7 +90,7 @@ class Core:
         # what a checkpoint needs to rebuild this handle (checkpoint.save / restore)
         self.options = dict(dx=float(dx), tracer=int(tracer), variant=int(variant), filter=bool(filter),
                             nranks=int(nranks), rank=int(rank), row0=int(row0), halo_steps=int(halo_steps),
-                            coriolis=bool(coriolis), dtype=dtype, members=int(members),
+                            coriolis=bool(coriolis), dtype=dtype, members=int(members), band_tracers=band_tracers,
                             global_height=int(height if global_height is None else global_height))
         self.has_ground = False
         cfg = _lib.Config()
@@ -131,6 +139,8 @@ class Core:
             if rc == _lib.ERR_ARG:
                 raise ValueError(msg)
             raise GcmError("gcm_create failed (%d): %s" % (rc, msg))
+        if band_tracers > 0:
+            _check(lib.gcm_set_band_tracers(self._h, band_tracers), self._h)
         self.is3d = model == _lib.PE25D
         self.fields = {_lib.SW2D: (_lib.P, _lib.U, _lib.V),
                        _lib.SW2D_TEMP: (_lib.P, _lib.U, _lib.V, _lib.T) +
@@ -191,10 +201,10 @@ class Core:
         _check(lib.gcm_diag_members(self._h, int(kind), _tab(out), self.members), self._h)
         return out
 
-    # -- passive tracers (GCM_PE25D, single domain) -------------------------------------
+    # -- passive tracers (GCM_PE25D; a latitude band: Core(..., band_tracers=n)) ----------
     def set_tracers(self, c):
         """carry the tracers c (n, L, H, W) from now on (n = 0 or None: none); every stage advances them
-        with the update of q (gcm_set_tracers)"""
+        with the update of q (gcm_set_tracers).  A band: its own rows, n = the declared band_tracers"""
         a = tracer_array(c, self.L, self.H, self.W)
         _check(lib.gcm_set_tracers(self._h, a.shape[0], _ptr(a) if a.shape[0] else None), self._h)
 

@@ -616,14 +616,22 @@ int gcm_step(gcm_handle *h, int nsteps, double dt) {
 static int tracer_refusal(const gcm_handle *h, const char *fn) {
     if (!h) return GCM_ERR_ARG;
     if (!h->pe) return fail(const_cast<gcm_handle *>(h), GCM_ERR_UNSUPPORTED, std::string(fn) + ": GCM_PE25D only");
-    if (!h->wrap) return fail(const_cast<gcm_handle *>(h), GCM_ERR_UNSUPPORTED, std::string(fn) + ": not on latitude bands");
     return GCM_OK;
 }
 
 int gcm_set_tracers(gcm_handle *h, int n, const double *c) {
     if (int rc = tracer_refusal(h, "gcm_set_tracers")) return rc;
     if (h->cfg.device >= 0) HIPCHK(h, hipSetDevice(h->cfg.device));
-    return pe25d_set_tracers(h->pe, n, c, h->stream, &h->err);
+    const int rc = pe25d_set_tracers(h->pe, n, c, h->stream, &h->err);
+    if (rc == GCM_OK && !h->wrap) h->primed = false;     // gcm_band_run: the new tracers' ghost rows are not exchanged yet
+    return rc;
+}
+
+int gcm_set_band_tracers(gcm_handle *h, int n) {
+    if (!h) return GCM_ERR_ARG;
+    if (!h->pe) return fail(h, GCM_ERR_UNSUPPORTED, "gcm_set_band_tracers: GCM_PE25D latitude bands only");
+    if (h->cfg.device >= 0) HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pe25d_set_band_tracers(h->pe, n, h->stream, &h->err);
 }
 
 int gcm_get_tracers(gcm_handle *h, int which, double *c) {
@@ -750,6 +758,7 @@ static int halo_run(gcm_handle *h, bool pack, void *north, void *south, void *st
     // GCM_PE25D: ghost rows filled on any stream but the library's second one (a host-driven exchange, gcm_band_run's
     // first exchange of a run): the next stage's second-stream work must follow THAT, not only the last update kernel
     if (!pack && h->pe && (hipStream_t)stream != pe25d_aux_stream(h->pe)) pe25d_fork_invalidate(h->pe);
+    if (h->pe) pe25d_follow_tracers(h->pe, (hipStream_t)stream);   // (a band's tracer rows: hazard 3 of half_t)
     launch_seg_copy(c, (hipStream_t)stream);
     return launch_status(h);
 }
@@ -992,6 +1001,7 @@ int gcm_band_run(gcm_handle *h, int nsteps, double dt) {
             h->join_pending = false;
         }
         pe25d_join_third_stream(h->pe, h->stream);
+        pe25d_join_tracers(h->pe, h->stream);             // (a band's tracers: the last stage's launches)
         return GCM_OK;
     }
     const int k = h->G / kGhost;                            // steps per exchange

@@ -70,8 +70,9 @@ struct TracerArgsT {
     // tracers, [n][H][L][W]: base (current), stage, out (in the corrector the current set again: in place)
     const T *c, *sc;
     T *oc;
-    long tstride;                                // elements per tracer
+    long tstride;                                // elements per tracer (a band's ghost rows included)
     int W, H, L, Hg, row0, wrap;
+    int j0, j1, jb0, jb1;                        // the rows of the launch: [j0, j1) and [jb0, jb1)
     T dt, inv_dy;
 };
 

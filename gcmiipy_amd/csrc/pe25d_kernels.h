@@ -51,11 +51,13 @@ int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], 
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan
 void pe25d_tv_shape(const Pe25d *m, int field, long *n_outer, long *n_axis, long *n_inner, int *wrap);
 const void *pe25d_field(Pe25d *m, int field, long *n, int *f32);
-// passive tracers (single domain): c / the result [n][L][H][W] float64; which 0 = current, 1 = star
+// passive tracers: c / the result [n][L][H][W] float64 (a band: its own rows); which 0 = current, 1 = star
 int pe25d_set_tracers(Pe25d *m, int n, const double *c, hipStream_t s, std::string *err);
 int pe25d_get_tracers(Pe25d *m, int which, double *c, hipStream_t s, std::string *err);
 int pe25d_tracer_count(const Pe25d *m);
-void pe25d_join_tracers(Pe25d *m, hipStream_t s);   // `s` waits for the last tracer launch on the second stream
+void pe25d_join_tracers(Pe25d *m, hipStream_t s);   // `s` waits for the last tracer launches on the other streams
+void pe25d_follow_tracers(Pe25d *m, hipStream_t s); // a pack / unpack on `s` follows the tracer launches on the second stream
+int pe25d_set_band_tracers(Pe25d *m, int n, hipStream_t s, std::string *err);   // gcm_set_band_tracers
 void pe25d_timing(Pe25d *m, std::vector<hipEvent_t> *ev, size_t *used);
 
 }  // namespace gcm

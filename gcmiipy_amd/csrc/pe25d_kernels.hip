@@ -544,15 +544,34 @@ struct Pe25d {
     bool edges_first = false;
     hipEvent_t ev_pre_edge = nullptr;
     bool pre_edge_pending = false;
-    // passive tracers (gcm_set_tracers; single domain only): 2 x ntr fields of H x L x W in T, device layout
-    // [j][k][i] -- the current set (ntr fields), then the star set.  The tracer kernel runs on chain B (see half_t);
-    // ev_tr, recorded on `aux` behind the last tracer launch, is how the caller's stream joins that tail
+    // passive tracers (gcm_set_tracers; a band: gcm_set_band_tracers first): 2 x ntr fields of (H + 2 tr_ghost(m)) x L x W
+    // in T, device layout [j][k][i] -- the current set (ntr fields), then the star set; a band's fields carry one ghost
+    // row a side (the kernel reads rows j -+ 1 only), addressed from interior row 0.  The tracer kernel runs on chain B
+    // (see half_t); ev_tr, recorded on `aux` behind the last tracer launch, is how the caller's stream joins that tail
     int ntr = 0;
     void *tr = nullptr;
     bool tr_star = false;                       // the star set holds the tracers of a predictor
     bool tr_pending = false;                    // a tracer launch on `aux` that the caller's stream has not joined
     hipEvent_t ev_tr = nullptr;
+    // a band's split stage (modes 1 + 2) runs the tracers' interior rows on the third stream (see half_t): ev_tr_int
+    // follows that launch; the next stage's chain B waits for it (tr_int_wait), the caller's stream joins it (tr_int_join)
+    hipEvent_t ev_tr_int = nullptr;
+    hipStream_t tr_int_stream = nullptr;
+    bool tr_int_wait = false, tr_int_join = false;
+    bool halo_fixed = false;                    // send / exchange buffers were registered: the message format is fixed
 };
+
+static_assert(sizeof(SegCopy::n) / sizeof(long) >= 2 * (GCM_NFIELDS + 1 + GCM_MAX_TRACERS),
+              "SegCopy holds one message per side: 5 fields, the ground temperature and every tracer");
+
+// a band's tracer fields: one ghost row a side (pe_tracer_kernel reads rows j - 1 .. j + 1 only); a single domain: none
+static int tr_ghost(const Pe25d *m) { return m->wrap ? 0 : 1; }
+static long tr_stride(const Pe25d *m) { return (long)(m->H + 2 * tr_ghost(m)) * m->L * m->W; }
+// tracer f of set 0 (current) or 1 (star), at interior row 0
+static char *tr_field(const Pe25d *m, int set, int f) {
+    const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
+    return (char *)m->tr + esz * ((size_t)(set * m->ntr + f) * tr_stride(m) + (size_t)tr_ghost(m) * m->L * m->W);
+}
 
 template <typename T> static PeBufs<T> &bufs(Pe25d *m);
 template <> PeBufs<double> &bufs<double>(Pe25d *m) { return m->d; }
@@ -923,6 +942,7 @@ void pe25d_destroy(Pe25d *m) {
     if (m->ev_k4) (void)hipEventDestroy(m->ev_k4);
     if (m->ev_pre_edge) (void)hipEventDestroy(m->ev_pre_edge);
     if (m->ev_tr) (void)hipEventDestroy(m->ev_tr);
+    if (m->ev_tr_int) (void)hipEventDestroy(m->ev_tr_int);
     if (m->aux2) {
         (void)hipStreamSynchronize(m->aux2);
         (void)hipStreamDestroy(m->aux2);
@@ -1086,13 +1106,17 @@ static void prep_rows(Pe25d *m, const PeArgsT<T> &a, int stage_set, bool p2, int
     if (!m->wrap || (fresh && c.cs_rows)) geopot(c, sb);
 }
 
-// The passive tracers of one stage (pe25d_tracer.h): base = the current tracers, stage = the star set in the corrector,
-// out = the star set in the predictor and the current set again in the corrector (each cell reads its base value
-// only at itself: in place).  Chunks of 4, then 2, then 1 tracers, one launch per chunk size (blockIdx.y = chunk).
+// The passive tracers of one stage (pe25d_tracer.h) over rows [r0, r1) and [rb0, rb1): base = the current tracers,
+// stage = the star set in the corrector, out = the star set in the predictor and the current set again in the
+// corrector (each cell reads its base value only at itself: in place).  Chunks of 4, then 2, then 1 tracers, one
+// launch per chunk size (blockIdx.y = chunk).
 template <typename T>
-static void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out_set, hipStream_t st) {
-    const long stride = (long)m->H * m->L * m->W;
-    T *const cur = (T *)m->tr, *const star = cur + (long)m->ntr * stride;
+static void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out_set, hipStream_t st, int r0, int r1,
+                           int rb0 = 0, int rb1 = 0) {
+    const int nrows = std::max(0, r1 - r0) + std::max(0, rb1 - rb0);
+    if (nrows <= 0) return;
+    const long stride = tr_stride(m);
+    T *const cur = (T *)tr_field(m, 0, 0), *const star = (T *)tr_field(m, 1, 0);
     TracerArgsT<T> t{};
     t.p = a.p; t.pn = a.pn; t.sp = a.sp; t.sv = a.sv; t.spu = a.spu; t.pit = a.pit;
     t.inv_dxj = a.inv_dxj; t.dsig = a.dsig; t.inv_dsig = a.inv_dsig; t.sigb = a.sigb;
@@ -1101,9 +1125,10 @@ static void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out
     t.oc = out_set == 2 ? star : cur;
     t.tstride = stride;
     t.W = m->W; t.H = m->H; t.L = m->L; t.Hg = m->Hg; t.row0 = m->cfg.row0; t.wrap = a.wrap;
+    t.j0 = r0; t.j1 = std::max(r0, r1); t.jb0 = rb0; t.jb1 = std::max(rb0, rb1);
     t.dt = a.dt; t.inv_dy = a.inv_dy;
     const bool same = t.sc == t.c;
-    const long tiles = (long)((m->W + kTrCols - 1) / kTrCols) * ((m->H + kTrRows - 1) / kTrRows);
+    const long tiles = (long)((m->W + kTrCols - 1) / kTrCols) * ((nrows + kTrRows - 1) / kTrRows);
     const dim3 block(kTrCols * kTrRows);
     int done = 0;
     for (const int nc : {4, 2, 1}) {
@@ -1115,7 +1140,7 @@ static void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out
         done += chunks * nc;
     }
     m->tr_star = out_set == 2;
-    m->tr_pending = m->aux != nullptr;
+    if (m->aux && st == m->aux) m->tr_pending = true;
 }
 
 // one Euler stage over rows [j0, j1): state `stage_set` -> `out_set`, base = current.
@@ -1185,6 +1210,17 @@ static void half_t(Pe25d *m, int stage_set, int out_set, double dt, int j0, int 
             else (void)hipEventRecord(m->ev_fork, s);
             (void)hipStreamWaitEvent(m->aux, fork, 0);
         }
+        // hazard 1 of a band's tracers: this stage's K1 overwrites spu, pit and p_n -- and its K4 the state sets -- that
+        // the last stage's tracer launch on another stream may still read (ev_tr_int, see below): chain B waits for it
+        // here, and so does the caller's stream where it takes the edge rows (no send buffers: the tracers' edge rows
+        // read what that launch wrote); the third stream's K1 follows it in stream order, or waits for it further down
+        const bool tr_prev = m->tr_int_wait;
+        m->tr_int_wait = false;
+        if (tr_prev) {
+            if (sb != m->tr_int_stream) (void)hipStreamWaitEvent(sb, m->ev_tr_int, 0);
+            hipStream_t se0 = (mode == 1 && async_edges(m) && m->aux) ? m->aux : s;
+            if (mode == 1 && se0 != sb && se0 != m->tr_int_stream) (void)hipStreamWaitEvent(se0, m->ev_tr_int, 0);
+        }
         const bool ghosts_queued = m->ghost_ready == stage_set && (!p2 || m->cs_valid[stage_set]);
         if (ghosts_queued) m->ghost_ready = -1;                    // queued behind the unpack already
         else prep_rows<T>(m, a, stage_set, p2, j1, ext, sb);
@@ -1215,7 +1251,10 @@ static void half_t(Pe25d *m, int stage_set, int out_set, double dt, int j0, int 
                 if (stop && !m->stop_events) (void)hipEventRecord(stop, st);
             };
             (void)hipStreamWaitEvent(m->aux2, fork, 0);
-            if (m->edges_ev_valid) (void)hipStreamWaitEvent(m->aux2, m->ev_edges, 0);   // (the previous stage's edge rows: su, sp of rows 0, 1, H - 2, H - 1)
+            // (the previous stage's edge rows: su, sp of rows 0, 1, H - 2, H - 1 -- and its tracers' edge rows, queued
+            // ahead of the pack: they read spu, pit and p_n of those rows, which this K1 overwrites)
+            if (m->edges_ev_valid) (void)hipStreamWaitEvent(m->aux2, m->ev_edges, 0);
+            if (tr_prev && m->tr_int_stream != m->aux2) (void)hipStreamWaitEvent(m->aux2, m->ev_tr_int, 0);
             PeArgsT<T> c = a;
             c.j0 = j0; c.j1 = j1; c.jb0 = c.jb1 = 0;
             c.pit_j0 = j0 + kGhost; c.pit_j1 = j1 - kGhost + 1;
@@ -1259,7 +1298,32 @@ static void half_t(Pe25d *m, int stage_set, int out_set, double dt, int j0, int 
         //        stop event), gcm_half_step, gcm_get_tracers, gcm_set_tracers and gcm_sync make `s` wait for ev_tr,
         //        recorded on `aux` behind the last tracer launch (pe25d_join_tracers).
         //      Without tracers nothing is launched, recorded or waited for here.
-        if (m->ntr > 0 && mode == 0) launch_tracers<T>(m, a, stage_set, out_set, sb);
+        //      A band: the whole stage (mode 0) takes the same launch over its own rows, and the next stage's chain B
+        //      waits for it on the streams where it does not follow in stream order (ev_tr_int, hazard 1 above).
+        if (m->ntr > 0 && mode == 0) {
+            launch_tracers<T>(m, a, stage_set, out_set, sb, j0, j1);
+            if (!m->wrap && m->aux) {
+                (void)hipEventRecord(m->ev_tr_int, sb);
+                m->tr_int_stream = sb;
+                m->tr_int_wait = true;
+            }
+        }
+        // ---- a band's split stage (modes 1 + 2): the tracers' edge rows go ahead of the pack (see mode 1 below), the
+        //      interior rows [j0 + 2, j1 - 2) here, on the third stream right behind the own rows' K1 (ev_a): off the
+        //      exchange chain, which never waits for them within the stage, and beside K2a and K3 on the caller's
+        //      stream, whose LDS-bound passes leave memory bandwidth free.  ev_tr_int follows them: the next stage's
+        //      chain B waits for it (hazard 1), the caller's stream joins it (pe25d_join_tracers).  Without a third
+        //      stream they go to the caller's stream, where the next stage's chain B follows them through the fork.
+        if (m->ntr > 0 && mode == 1 && split) {
+            hipStream_t ti = m->aux2 ? m->aux2 : s;
+            if (m->aux && !(split_k1 && ti == m->aux2)) (void)hipStreamWaitEvent(ti, m->ev_a, 0);   // (K1 + pit of all rows)
+            launch_tracers<T>(m, a, stage_set, out_set, ti, j0 + kGhost, j1 - kGhost);
+            if (ti != s) {
+                (void)hipEventRecord(m->ev_tr_int, ti);
+                m->tr_int_stream = ti;
+                m->tr_int_wait = m->tr_int_join = true;
+            }
+        }
         // ---- chain A: geopotential of the own rows, then the filtered pressure-gradient force
         a.j0 = j0;
         a.j1 = j1;
@@ -1331,6 +1395,14 @@ static void half_t(Pe25d *m, int stage_set, int out_set, double dt, int j0, int 
             c.jb0 = j1 - kGhost; c.jb1 = j1 + 1;
             hipLaunchKernelGGL(pe_part_kernel<T>, dim3((unsigned)((W + 255) / 256) * (2 * kGhost + 2)), dim3(256), 0, se, c);
         }
+        if (m->ntr > 0) {
+            // the tracers' edge rows (the rows a neighbour takes, and the rows next to them), on the stream of the edge
+            // rows' K4, behind K1, pit and ev_a and ahead of the wait for K3: they fill chain B's wait.  Hazard 2: in
+            // the corrector they read the star tracers' ghost rows, which the post-predictor unpack filled ahead of K1
+            // on this stream (gcm_band_run), or on the caller's stream before this call (host-driven exchange).
+            if (split) launch_tracers<T>(m, a, stage_set, out_set, se, j0, j0 + kGhost, j1 - kGhost, j1);
+            else launch_tracers<T>(m, a, stage_set, out_set, se, j0, j1);
+        }
         if (as && m->aux) (void)hipStreamWaitEvent(m->aux, m->ev_join, 0);      // the edge rows' K4 takes pgfu
         if (as && m->aux && m->edges_first && split) {
             (void)hipEventRecord(m->ev_pre_edge, se);          // chain B is about to launch the edge rows' K4
@@ -1351,6 +1423,8 @@ static void half_t(Pe25d *m, int stage_set, int out_set, double dt, int j0, int 
             update_rows(j0, j1, 0, 0, se);
         }
         if (as) {
+            // (hazard 3: the pack of the new state's edge rows follows the corrector's tracer edge launch above in
+            // stream order on `se`; a pack the caller queues -- gcm_halo_pack -- follows `aux` through halo_run)
             SegCopy c{};
             std::string err;
             (void)pe25d_halo_segments(m, true, 0, m->send_buf[0], &c, &err);
@@ -1428,18 +1502,69 @@ int pe25d_prep_ghost_rows(Pe25d *m, std::string *err) {
 }
 
 void pe25d_join_tracers(Pe25d *m, hipStream_t s) {
+    if (m->tr_int_join) {                                        // (a band's interior rows on the third stream)
+        m->tr_int_join = false;
+        if (m->tr_int_stream != s) (void)hipStreamWaitEvent(s, m->ev_tr_int, 0);
+    }
     if (!m->tr_pending) return;
     m->tr_pending = false;
     (void)hipEventRecord(m->ev_tr, m->aux);
     (void)hipStreamWaitEvent(s, m->ev_tr, 0);
 }
 
+// a ghost-row pack or unpack the caller queues on `s` (gcm_halo_pack / unpack): it follows the tracer launches on
+// the second stream, which read the edge and ghost rows it moves.  (The interior rows on the third stream touch
+// neither.)  Unlike pe25d_join_tracers this leaves the caller's join to come in place.
+void pe25d_follow_tracers(Pe25d *m, hipStream_t s) {
+    if (!m->tr_pending || s == m->aux) return;
+    (void)hipEventRecord(m->ev_tr, m->aux);
+    (void)hipStreamWaitEvent(s, m->ev_tr, 0);
+}
+
+// gcm_set_band_tracers: a band's tracer count, fixed before the message size is used (zeros until gcm_set_tracers)
+int pe25d_set_band_tracers(Pe25d *m, int n, hipStream_t s, std::string *err) {
+    if (m->wrap) {
+        *err = "gcm_set_band_tracers: GCM_PE25D latitude bands only (a single domain takes gcm_set_tracers directly)";
+        return GCM_ERR_UNSUPPORTED;
+    }
+    if (n < 0 || n > GCM_MAX_TRACERS) {
+        *err = "gcm_set_band_tracers: n must be 0 .. GCM_MAX_TRACERS";
+        return GCM_ERR_ARG;
+    }
+    if (m->halo_fixed) {
+        *err = "gcm_set_band_tracers: send or exchange buffers are registered already (their size follows the count)";
+        return GCM_ERR_STATE;
+    }
+    pe25d_join_tracers(m, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess && m->tr) e = hipFree(m->tr);
+    m->tr = nullptr;
+    m->ntr = 0;
+    m->tr_star = false;
+    const size_t bytes = 2 * (size_t)n * tr_stride(m) * (m->f32 ? sizeof(float) : sizeof(double));
+    if (e == hipSuccess && n > 0) e = hipMalloc(&m->tr, bytes);
+    if (e == hipSuccess && n > 0) e = hipMemset(m->tr, 0, bytes);
+    if (e == hipSuccess && n > 0) m->ntr = n;
+    if (e == hipSuccess && n > 0 && m->aux && !m->ev_tr) e = hipEventCreateWithFlags(&m->ev_tr, hipEventDisableTiming);
+    if (e == hipSuccess && n > 0 && m->aux && !m->ev_tr_int) e = hipEventCreateWithFlags(&m->ev_tr_int, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        *err = std::string("gcm_set_band_tracers: ") + hipGetErrorString(e);
+        return GCM_ERR_HIP;
+    }
+    return GCM_OK;
+}
+
 int pe25d_tracer_count(const Pe25d *m) { return m->ntr; }
 
 int pe25d_set_tracers(Pe25d *m, int n, const double *c, hipStream_t s, std::string *err) {
-    if (!m->wrap) {
-        *err = "gcm_set_tracers: tracers on latitude bands are not supported";
+    if (!m->wrap && m->ntr == 0) {
+        *err = "gcm_set_tracers: this latitude band declared no tracers (gcm_set_band_tracers)";
         return GCM_ERR_UNSUPPORTED;
+    }
+    if (!m->wrap && n != m->ntr) {
+        *err = "gcm_set_tracers: this latitude band declared " + std::to_string(m->ntr) +
+               " tracers (gcm_set_band_tracers); n must equal that";
+        return GCM_ERR_ARG;
     }
     if (n < 0 || n > GCM_MAX_TRACERS || (n > 0 && !c)) {
         *err = "gcm_set_tracers: n must be 0 .. GCM_MAX_TRACERS, with a host array for n > 0";
@@ -1460,11 +1585,13 @@ int pe25d_set_tracers(Pe25d *m, int n, const double *c, hipStream_t s, std::stri
     for (int f = 0; f < n && e == hipSuccess; ++f) {
         e = hipMemcpyAsync(m->stage3, c + (size_t)f * cells, sizeof(double) * cells, hipMemcpyHostToDevice, s);
         if (e != hipSuccess) break;
-        if (m->f32) hipLaunchKernelGGL(pe_to_device_kernel<float>, dim3(1024), dim3(256), 0, s, (float *)m->tr + f * cells, m->stage3, m->W, m->H, m->L);
-        else hipLaunchKernelGGL(pe_to_device_kernel<double>, dim3(1024), dim3(256), 0, s, (double *)m->tr + f * cells, m->stage3, m->W, m->H, m->L);
+        if (m->f32) hipLaunchKernelGGL(pe_to_device_kernel<float>, dim3(1024), dim3(256), 0, s, (float *)tr_field(m, 0, f), m->stage3, m->W, m->H, m->L);
+        else hipLaunchKernelGGL(pe_to_device_kernel<double>, dim3(1024), dim3(256), 0, s, (double *)tr_field(m, 0, f), m->stage3, m->W, m->H, m->L);
     }
-    // the star set starts as a copy (a corrector behind gcm_set_star, without a predictor, reads it)
-    if (e == hipSuccess && n > 0) e = hipMemcpyAsync((char *)m->tr + (size_t)n * cells * esz, m->tr, (size_t)n * cells * esz, hipMemcpyDeviceToDevice, s);
+    // the star set starts as a copy (a corrector behind gcm_set_star, without a predictor, reads it); a band's ghost
+    // rows come with it, until the next exchange fills them
+    const size_t set_bytes = (size_t)n * tr_stride(m) * esz;
+    if (e == hipSuccess && n > 0) e = hipMemcpyAsync((char *)m->tr + set_bytes, m->tr, set_bytes, hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     m->tr_star = false;
     m->k4_fork_valid = false;                    // (the uploads on the caller's stream: the next chain B follows them)
@@ -1489,13 +1616,11 @@ int pe25d_get_tracers(Pe25d *m, int which, double *c, hipStream_t s, std::string
         return GCM_ERR_ARG;
     }
     pe25d_join_tracers(m, s);
-    const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
     const size_t cells = (size_t)m->H * m->L * m->W;
-    const char *base = (const char *)m->tr + (which ? (size_t)m->ntr * cells * esz : 0);
     hipError_t e = hipSuccess;
     for (int f = 0; f < m->ntr && e == hipSuccess; ++f) {
-        if (m->f32) hipLaunchKernelGGL(pe_to_host_kernel<float>, dim3(1024), dim3(256), 0, s, m->stage3, (const float *)base + f * cells, m->W, m->H, m->L);
-        else hipLaunchKernelGGL(pe_to_host_kernel<double>, dim3(1024), dim3(256), 0, s, m->stage3, (const double *)base + f * cells, m->W, m->H, m->L);
+        if (m->f32) hipLaunchKernelGGL(pe_to_host_kernel<float>, dim3(1024), dim3(256), 0, s, m->stage3, (const float *)tr_field(m, which, f), m->W, m->H, m->L);
+        else hipLaunchKernelGGL(pe_to_host_kernel<double>, dim3(1024), dim3(256), 0, s, m->stage3, (const double *)tr_field(m, which, f), m->W, m->H, m->L);
         e = hipMemcpyAsync(c + (size_t)f * cells, m->stage3, sizeof(double) * cells, hipMemcpyDeviceToHost, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -1626,6 +1751,7 @@ int pe25d_set_halo_buffers(Pe25d *m, void *north, void *south, hipStream_t s, st
     m->send_buf[0] = north;
     m->send_buf[1] = south;
     m->edges_pending = false;
+    if (north) m->halo_fixed = true;             // (gcm_set_band_tracers: the message format is in use from now on)
     return GCM_OK;
 }
 
@@ -1644,9 +1770,11 @@ int pe25d_wait_edges(Pe25d *m, hipStream_t s, std::string *err) {
 // ghost rows: [p: 2 rows][u,v,t,q: 2 rows x L levels]; contiguous in the device layout.
 // Which state is exchanged follows the step phase: the predicted state once it exists.
 size_t pe25d_halo_bytes(const Pe25d *m) {
-    // (+ the ground temperature's two rows, float64 for either storage type: gcm_set_physics)
-    return (m->f32 ? sizeof(float) : sizeof(double)) * (size_t)kGhost * m->W * (1 + 4 * (size_t)m->L) +
-           sizeof(double) * (size_t)kGhost * m->W;
+    // (+ the ground temperature's two rows, float64 for either storage type: gcm_set_physics;
+    //  + a band's tracers, one row x L levels each: gcm_set_band_tracers)
+    const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
+    return esz * (size_t)kGhost * m->W * (1 + 4 * (size_t)m->L) + sizeof(double) * (size_t)kGhost * m->W +
+           (m->wrap ? 0 : esz * (size_t)m->ntr * tr_ghost(m) * m->L * m->W);
 }
 
 template <typename T>
@@ -1682,6 +1810,21 @@ static void halo_t(Pe25d *m, bool pack, int side, void *dev_buf, SegCopy *c) {
         c->src[c->nseg] = pack ? edge : gb;
         c->dst[c->nseg] = pack ? gb : ghost;
         c->n[c->nseg++] = (long)n2;
+        b = (T *)(gb + n2);
+    }
+    // a band's tracers, one segment each: those of the state set above (star with the predicted state, else current)
+    if (!m->wrap) {
+        const int R = tr_ghost(m);
+        const size_t n = (size_t)R * m->L * m->W;             // (R rows x L x even W floats: whole 8-byte words)
+        for (int f = 0; f < m->ntr; ++f) {
+            T *base = (T *)tr_field(m, set == 2 ? 1 : 0, f);
+            T *edge = side == 0 ? base : base + (size_t)(m->H - R) * m->L * m->W;
+            T *ghost = side == 0 ? base - n : base + (size_t)m->H * m->L * m->W;
+            c->src[c->nseg] = (const double *)(pack ? edge : b);
+            c->dst[c->nseg] = (double *)(pack ? b : ghost);
+            c->n[c->nseg++] = (long)(n * sizeof(T) / 8);
+            b += n;
+        }
     }
 }
 

@@ -26,15 +26,18 @@ __global__ __launch_bounds__(kTrCols * kTrRows) void pe_tracer_kernel(TracerArgs
     // tiles (row group, column tile) in contiguous runs per XCD (workgroups b, b+8, ... share one), column tile
     // fastest: the rows j - 1 / j + 1 a tile reads belong to tiles of the same XCD, close in time (L2 hits)
     const int ncol = (W + kTrCols - 1) / kTrCols;
-    const int ntiles = ncol * ((a.H + kTrRows - 1) / kTrRows);
+    const int n0 = a.j1 - a.j0, nrows = n0 + (a.jb1 - a.jb0);
+    const int ntiles = ncol * ((nrows + kTrRows - 1) / kTrRows);
     const int per_xcd = (int)(gridDim.x / 8);
     const int tile = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
     if (tile >= ntiles) return;
     const int rg = tile / ncol, ct = tile - rg * ncol;
     const int i = ct * kTrCols + (int)(threadIdx.x % kTrCols);
     // a wave is 64 columns of ONE row: the row and every row offset below are wave-uniform (scalar registers)
-    const int j = rg * kTrRows + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kTrCols));
-    if (i >= W || j >= a.H) return;
+    // (r: the row's place in the launch, [j0, j1) then [jb0, jb1))
+    const int r = rg * kTrRows + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kTrCols));
+    if (i >= W || r >= nrows) return;
+    const int j = r < n0 ? a.j0 + r : a.jb0 + (r - n0);
     const int iw = i == 0 ? W - 1 : i - 1, ie = i + 1 == W ? 0 : i + 1;
     const long toff = (long)blockIdx.y * NC * a.tstride;
     const T *c = a.c + toff, *sc = a.sc + toff;

@@ -85,10 +85,10 @@ void build_exner_table(double *tab);
 template <typename T> void launch_copy_rows(T *dst, const T *src, int W, int nrows, hipStream_t s);
 
 // up to 5 contiguous segments copied by ONE launch (ghost-row pack / unpack of all fields)
-struct SegCopy {          // up to (5 fields + the ground temperature) x 2 sides in one launch
-    double *dst[12];
-    const double *src[12];
-    long n[12];
+struct SegCopy {          // up to (5 fields + the ground temperature + GCM_MAX_TRACERS tracers) x 2 sides in one launch
+    double *dst[44];
+    const double *src[44];
+    long n[44];
     int nseg;
 };
 // stop: an event signalled by the copy kernel's own completion (hipExtLaunchKernelGGL), or null

@@ -174,21 +174,32 @@ int gcm_get_star(gcm_handle *h, double *p, double *u, double *v, double *t, doub
 int gcm_set_star(gcm_handle *h, const double *p, const double *u, const double *v,
                  const double *t, const double *q);
 
-/* Passive tracers of GCM_PE25D (single domain): n fields c[n][L][H][W] that every Matsuno stage of
- * gcm_step / gcm_half_step / gcm_time_steps advances with exactly the update the reference applies to q
+/* Passive tracers of GCM_PE25D: n fields c[n][L][H][W] that every Matsuno stage of gcm_step /
+ * gcm_half_step / gcm_time_steps (a latitude band: gcm_band_run, gcm_step_phase, gcm_step_interior /
+ * gcm_step_boundary) advances with exactly the update the reference applies to q
  * (dynamics.py:219, advec_t :174-181, advec_sig :49-52) on the stage's own mass fluxes:
  *     c_n = (c p - (advec_t(spu, spv, sc) + advec_sig(sd, sc)) dt) / p_n,   sc = the stage value,
  * so a tracer equal to q stays equal to q (bit for bit in fp64).  No flux limiting, no positivity (the reference
  * applies none to q).  The handle stores them in its own real type; the host API is float64.
  * gcm_set_tracers: 0 <= n <= GCM_MAX_TRACERS (n = 0 frees them), also resets the star set to c;
  * gcm_get_tracers: which = 0 the current tracers, 1 those of the last predictor (GCM_ERR_STATE before
- * one); gcm_tracer_count: n.  Other models and latitude bands (nranks > 1): GCM_ERR_UNSUPPORTED.
- * The tracer kernel runs on the handle's second stream; these calls, gcm_step, gcm_half_step and
- * gcm_sync include it.  Without tracers the step is the same work as before.                          */
+ * one); gcm_tracer_count: n.  Other models: GCM_ERR_UNSUPPORTED.  On a latitude band (nranks > 1) c holds
+ * the band's own rows (H = height) and n must equal the count declared by gcm_set_band_tracers; without a
+ * declaration (or with 0) gcm_set_tracers returns GCM_ERR_UNSUPPORTED, any other n GCM_ERR_ARG.  On a band
+ * gcm_set_tracers (like gcm_set_state) makes the next gcm_band_run exchange the ghost rows first.
+ * The tracer kernel runs on the handle's second (a band's: second and third) stream; these calls,
+ * gcm_step, gcm_half_step, gcm_band_run and gcm_sync include it.  Without tracers the step is the same
+ * work as before.                                                                                      */
 #define GCM_MAX_TRACERS 16
 int gcm_set_tracers(gcm_handle *h, int n, const double *c);
 int gcm_get_tracers(gcm_handle *h, int which, double *c);
 int gcm_tracer_count(const gcm_handle *h);
+/* GCM_PE25D latitude bands (nranks > 1): the number of passive tracers the band carries, 0..GCM_MAX_TRACERS.
+ * Fixes the ghost-row message (gcm_halo_bytes) and so must come before gcm_set_halo_buffers / gcm_set_exchange.
+ * The band's tracers start as zeros (gcm_set_tracers with the same n sets them).  Errors: n out of range
+ * GCM_ERR_ARG; any handle but a GCM_PE25D band (single domains need no declaration) GCM_ERR_UNSUPPORTED;
+ * a call after send or exchange buffers were registered GCM_ERR_STATE.                                 */
+int gcm_set_band_tracers(gcm_handle *h, int n);
 
 /* Diagnostics the reference's drivers evaluate on the host every step
  * (SURVEY.md 8f-1); computed by device reductions, result copied to *out. */
@@ -281,9 +292,13 @@ int gcm_restore(gcm_handle *h);
  * needs into / unpacks them from caller-owned DEVICE buffers (e.g. torch tensors
  * handed to torch.distributed / RCCL send-recv); it never calls a collective
  * itself.  `side` 0 = towards row 0 (north), 1 = towards the last row (south).
- * gcm_halo_bytes gives the buffer size for one side (GCM_PE25D: the two rows of p and of
- * u, v, t, q on every level in the handle's storage type, then the two rows of the ground
- * temperature in float64 -- see gcm_set_physics).                                            */
+ * gcm_halo_bytes gives the buffer size for one side.  GCM_PE25D, segment by segment: the two rows of p,
+ * then of u, v, t, q (every level) in the handle's storage type, then the two rows of the ground
+ * temperature in float64 (see gcm_set_physics), then -- with n = gcm_set_band_tracers(n) > 0 -- ONE row
+ * (every level) of each tracer in order, in the storage type: the tracer kernel reads rows j -+ 1 only.
+ * Bytes per side:  esz 2 W (1 + 4 L) + 8 * 2 W + n esz L W  (esz = 8 for fp64, 4 for fp32 storage).
+ * Each message carries the tracers that belong to the state it carries (the predicted ones after a
+ * predictor, the current ones otherwise).                                                       */
 size_t gcm_halo_bytes(const gcm_handle *h);
 int gcm_halo_pack(gcm_handle *h, int side, void *dev_buf, void *stream);
 int gcm_halo_unpack(gcm_handle *h, int side, const void *dev_buf, void *stream);

@@ -9,7 +9,10 @@ of the band's own edge rows (send buffer -> receive buffer on the second stream)
 say how far the kernels alone let the step shrink when the grid is split N ways -- the exchange
 over xGMI then has to hide behind them.  The 8-GPU runs themselves are the driver's.
 
-  python tools/tools_band_time.py [--workload c4|c3] [--splits 1,2,4,8] [--steps 20]
+  python tools/tools_band_time.py [--workload c4|c3] [--splits 1,2,4,8] [--steps 20] [--tracers n]
+
+--tracers n (GCM_PE25D): the band carries n passive tracers (Core(band_tracers=n); the single domain of N = 1 the same
+n through set_tracers), each a copy of q; "exchange_bytes_per_step" counts their ghost rows in the messages.
 """
 import argparse
 import json
@@ -20,12 +23,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def halo_bytes_pe25d(W, L, esz, ntr=0):
+    """bytes of one GCM_PE25D ghost-row message (one side; gcm_halo_bytes): two rows of p, u, v, t, q in the storage
+    type (esz bytes), two float64 rows of the ground temperature, one row of every tracer"""
+    return esz * 2 * W * (1 + 4 * L) + 8 * 2 * W + ntr * esz * L * W
+
+
+def exchange_bytes_per_step(W, L, esz, ntr=0):
+    """what one GCM_PE25D band sends per step: two exchanges (predicted state, new state), one message to either side"""
+    return 2 * 2 * halo_bytes_pe25d(W, L, esz, ntr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="c4")
     ap.add_argument("--splits", default="1,2,4,8")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--tracers", type=int, default=0, help="GCM_PE25D: passive tracers carried by the band (copies of q)")
     ap.add_argument("--exchange", default="local", choices=["local", "rccl", "torch-nccl"],
                     help="local: device copy in place of the exchange; rccl: the band sends to itself through "
                          "gcmiipy_amd.rccl (RCCL called directly: the production path, no xGMI); torch-nccl: the "
@@ -60,9 +75,13 @@ def main():
                       tracer={None: _lib.TRACER_NONE, "van_leer": _lib.TRACER_VANLEER}[tracer],
                       nranks=n, rank=rank, global_height=H, row0=row0,
                       stream=torch.cuda.current_stream().cuda_stream, halo_steps=k,
-                      dtype="f32" if a.workload.endswith("_f32") else "f64")
+                      dtype="f32" if a.workload.endswith("_f32") else "f64",
+                      band_tracers=a.tracers if n > 1 else 0)
         sl = slice(row0, row0 + nrows)
         core.set_state(**{f: (x[sl] if x.ndim == 2 else x[:, sl]) for f, x in full.items()})
+        if a.tracers:
+            import numpy as np
+            core.set_tracers(np.repeat(full["q"][None, :, sl], a.tracers, axis=0))
         if model != "PE25D":
             core.snapshot()
         eng = HipBandEngine(core, torch) if n > 1 else None
@@ -124,7 +143,11 @@ def main():
         runner.run(nq, dt)
         host_idle_ms = (time.perf_counter() - t0) * 1e3 / nq
         torch.cuda.synchronize()
-        res.append({"split": n, "band_rows": nrows, "halo_steps": k, "ms_per_step": ms, "host_ms_per_step": host_ms,
+        esz = 4 if a.workload.endswith("_f32") else 8
+        res.append({"split": n, "band_rows": nrows, "halo_steps": k, "tracers": a.tracers,
+                    "exchange_bytes_per_step": (exchange_bytes_per_step(W, L, esz, a.tracers) if model == "PE25D" and n > 1
+                                                else (2 * core.halo_bytes() // k if n > 1 else 0)),
+                    "ms_per_step": ms, "host_ms_per_step": host_ms,
                     "host_queue_ms_per_step_idle_device": host_idle_ms,
                     "one_library_call_per_run": bool(getattr(runner, "native", False))})
         print("N=%d  band of %4d rows  %.4f ms/step  (host queues a step in %.4f ms behind a busy queue, %.4f ms into an idle one)"
@@ -134,7 +157,7 @@ def main():
     for r in res:
         if base:
             r["compute_bound_speedup"] = base / r["ms_per_step"]
-    doc = {"workload": desc, "exchange": a.exchange,
+    doc = {"workload": desc, "exchange": a.exchange, "tracers": a.tracers,
            "note": "one band of an N-way split stepped on one GPU, exchange replaced by a device-local copy "
                    "(local) or sent to itself through RCCL (rccl): the kernels' own strong-scaling bound", "bands": res}
     print(json.dumps(doc))
