@@ -3,8 +3,8 @@
 HBM roofline (BASELINE.json).  One "step" = one full Matsuno step (predictor +
 corrector, every prognostic field read once and written once) over the whole grid.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|c5_phys...] [--only]
-                  [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|c5_phys...]
+                  [--dump-outputs DIR] [--full [--only] [--no-cpu]]
 
 The timed region is EXACTLY K steps between barrier + synchronize fences (`ms_per_step`, `value`).
 The untimed steps before it leave the same state in every run, so with the same arguments the last
@@ -12,10 +12,14 @@ timed step computes the same state; --dump-outputs DIR writes that state as DIR/
 
 The headline workload is c3 (BASELINE configs[2], 4096x2048 shallow water + theta +
 viscosity + van-Leer tracer, fp64).  N > 1 is launched by torch.distributed.run, one rank
-per GPU; the FIXED global grid is split into latitude bands (strong scaling).  Unless --only
-is given the JSON line also carries, under "also", short runs of the other workloads -- at
-N > 1 that includes the 1440x720x24 primitive-equation workload c4 with a same-run 1-GPU
-reference on rank 0, the strong-scaling pair BASELINE.json's north_star names.
+per GPU; the FIXED global grid is split into latitude bands (strong scaling).
+
+A plain run does only what the headline needs: set-up, settle, warm-up, the K timed steps, the dump, the line.
+--full adds everything that takes runs of its own: the isolated kernel time and a device copy of the same bytes
+(1 GPU), the loopback-exchange and idle-device host figures (N > 1), the NumPy oracle's CPU baseline (unless
+--no-cpu), and, unless --only, short runs of the other workloads under "also" -- at N > 1 that includes the
+1440x720x24 primitive-equation workload c4 with a same-run 1-GPU reference on rank 0, the strong-scaling pair
+BASELINE.json's north_star names.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -180,9 +184,10 @@ def halo_steps_for(name, world):
     return 4 if world == 2 else 8
 
 
-def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kernel=True, dump=None):
+def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kernel=True, dump=None, full=True):
     """-> dict(value, ms_per_step, [roofline]) measured on `world` ranks (default: all); `dump`: a directory for the
-    state the last timed step computed (write_outputs, rank 0)"""
+    state the last timed step computed (write_outputs, rank 0); `full`: also the figures that take runs of their own
+    after the timed steps (kernel_ms_isolated, device_copy_same_bytes, the N > 1 loopback / idle-device diagnostics)"""
     import gcmiipy_amd as g
     from gcmiipy_amd import _lib, geometry
     from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange, split_rows
@@ -373,10 +378,12 @@ def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kern
                                      "sent_per_rank_per_step": 2 * hb * per_step,
                                      "whole_job_per_step": world * 2 * hb * per_step}
             res["rccl_ranks"] = cx.ring.count() if hasattr(cx.ring, "count") else None
-            # diagnostics for the multi-GPU line: how long the host needs to queue a step, and what
+            # diagnostics for the multi-GPU line: how long the host needs to queue a step, and (full) what
             # the same band costs with the exchange replaced by a device-local copy (same launches
             # and stream dependencies, no xGMI traffic) -- the difference to ms_per_step is what the
             # exchange adds.  Run AFTER the timed region; its ghost rows are not a model state.
+            res["diagnostics"] = {"host_queue_ms_per_step": t_queued / steps * 1e3, "rank": rank}
+        if world > 1 and full:
             lb = BandRunner(eng, rank, world, LoopbackExchange())
             lb.primed, lb.count = True, 0
             nlb = max(k, 8) * 4
@@ -401,19 +408,19 @@ def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kern
             except AttributeError:              # (a torch without the spin kernel: the figure is simply absent)
                 pass
             torch.cuda.synchronize()
-            res["diagnostics"] = {"host_queue_ms_per_step": t_queued / steps * 1e3,
-                                  "host_queue_ms_per_step_idle_device": host_idle,
-                                  "band_ms_per_step_local_exchange": e0.elapsed_time(e1) / nlb,
-                                  "rank": rank}
-        if world == 1 and want_kernel:
+            res["diagnostics"].update(host_queue_ms_per_step_idle_device=host_idle,
+                                      band_ms_per_step_local_exchange=e0.elapsed_time(e1) / nlb)
+        # the staged 2-D variant's kernel figure IS the isolated run: without `full` it has none
+        staged_2d = variant != "fused" and model != "PE25D"
+        if world == 1 and want_kernel and (full or not staged_2d):
             # dominant kernel.  fused 2-D: one launch per step, so its average duration over the
             # timed region is (HIP-event time of the region on the launch stream) / launches; the
             # back-to-back launches leave no gap (rocprofv3 trace: next start == previous end).
-            # "kernel_ms_isolated" is a second pass with an event pair around every launch
+            # "kernel_ms_isolated" (full) is a second pass with an event pair around every launch
             # (idle gaps between launches let the chip clock higher, so it reads lower).
             launches_timed = steps
-            kiso = None
             launches = 1
+            kiso = core.time_steps(min(steps, 50), dt)[1] if full and model != "PE25D" else None
             if model == "PE25D":
                 # one Euler stage = four launches (spu filter with pit in its launch, geopot, pgf filter, update) on two
                 # streams; the roofline entry is the WHOLE stage: half of the step's algorithmic bytes over
@@ -423,12 +430,9 @@ def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kern
             elif variant == "fused" and model == "SW2D":
                 # plain shallow water steps in pairs (one launch = two steps): per-step figures
                 kname, kms = "sw2d_fused2_kernel (two steps per launch; per step)", region["ms"] / launches_timed
-                _, kiso = core.time_steps(min(steps, 50), dt)
             elif variant == "fused":
                 kname, kms = "sw2d_fused_kernel", region["ms"] / launches_timed
-                _, kiso = core.time_steps(min(steps, 50), dt)
             else:
-                _, kiso = core.time_steps(min(steps, 50), dt)
                 kname, kms = "sw2d_stage_kernel (corrector stage)", kiso
             ach = cells * bpc / launches / (kms * 1e-3) / 1e9
             # HBM bytes per launch from the rocprofv3 PMC passes of this same command (separate
@@ -450,24 +454,25 @@ def run_workload(cx, name, steps, warmup, variant="fused", world=None, want_kern
                         traffic /= 2.0                      # per step, as kernel_ms
             except Exception:
                 pass
-            # context: what a plain device-to-device copy of the same bytes (state in, state out)
-            # reaches on this box, timed the same way
-            nb = int(cells * bpc / 2)
-            src = torch.empty(nb // 8, dtype=torch.float64, device="cuda").normal_()
-            dst = torch.empty_like(src)
-            for _ in range(3):
-                dst.copy_(src)
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(20):
-                dst.copy_(src)
-            e1.record()
-            torch.cuda.synchronize()
-            copy_gbs = 2.0 * nb / (e0.elapsed_time(e1) / 20 * 1e-3) / 1e9
-            del src, dst
-            res["device_copy_same_bytes"] = {"GB/s": copy_gbs, "kernel_traffic_over_copy_rate":
-                                             (traffic or cells * bpc / launches) / (kms * 1e-3) / 1e9 / copy_gbs}
+            if full:
+                # context: what a plain device-to-device copy of the same bytes (state in, state out)
+                # reaches on this box, timed the same way
+                nb = int(cells * bpc / 2)
+                src = torch.empty(nb // 8, dtype=torch.float64, device="cuda").normal_()
+                dst = torch.empty_like(src)
+                for _ in range(3):
+                    dst.copy_(src)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(20):
+                    dst.copy_(src)
+                e1.record()
+                torch.cuda.synchronize()
+                copy_gbs = 2.0 * nb / (e0.elapsed_time(e1) / 20 * 1e-3) / 1e9
+                del src, dst
+                res["device_copy_same_bytes"] = {"GB/s": copy_gbs, "kernel_traffic_over_copy_rate":
+                                                 (traffic or cells * bpc / launches) / (kms * 1e-3) / 1e9 / copy_gbs}
             res["roofline"] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "kernel": kname,
                                "kernel_ms": kms, "kernel_ms_isolated": kiso, "launches_timed": launches_timed * launches,
@@ -599,8 +604,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--variant", default="fused", choices=["fused", "staged"])
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--only", action="store_true", help="skip the secondary workloads under 'also'")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also what takes runs of its own: the isolated kernel time and a device "
+                         "copy of the same bytes (1 GPU), the loopback-exchange diagnostics (N > 1), the CPU baseline "
+                         "and the secondary workloads under 'also'")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--only", action="store_true", help="with --full: skip the secondary workloads under 'also'")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write the state the last one computed (p, u, v, t, q as the workload "
                          "has them; gt, the ground temperature, with physics) as DIR/<name>.npy in the workload's "
@@ -654,9 +663,9 @@ def main():
             bring_up_direct_rccl(cx, torch, dist)
             agree_stuck(cx, torch, dist)
 
-    main_res = run_workload(cx, a.workload, a.steps, a.warmup, a.variant, dump=a.dump_outputs)
+    main_res = run_workload(cx, a.workload, a.steps, a.warmup, a.variant, dump=a.dump_outputs, full=a.full)
     also, cpu_cache = {}, {}
-    if not a.only:
+    if a.full and not a.only:
         for name in ALSO:
             if name == a.workload:
                 continue
@@ -709,7 +718,7 @@ def main():
             out["diagnostics"] = main_res["diagnostics"]
         if "device_copy_same_bytes" in main_res:
             out["device_copy_same_bytes"] = main_res["device_copy_same_bytes"]
-        if cx.world == 1:
+        if cx.world == 1 and a.full:
             out["cpu_baseline"] = None if a.no_cpu else cpu_cache.get(a.workload) or cpu_baseline(a.workload)
         if also:
             out["also"] = also

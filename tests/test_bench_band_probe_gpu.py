@@ -76,13 +76,13 @@ def test_bench_starts_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` as the driver types it, with no launcher and no WORLD_SIZE in the
     environment: the parent starts the two ranks itself (a child torch.distributed.run job; gloo here, since
     RCCL refuses two ranks on one device), rank 0 prints ONE JSON line with n_gpus == 2, the exit code is the
-    job's"""
+    job's; --full adds the loopback-exchange and idle-device diagnostics"""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GCM_BENCH_BACKEND="gloo", GCM_BENCH_SETTLE_S="0.01")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "4",
-                        "--only", "--no-cpu"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--only", "--no-cpu"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]

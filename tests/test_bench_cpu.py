@@ -45,6 +45,58 @@ def test_main_self_launches_only_without_a_launcher(monkeypatch):
     assert e.value.code == 0 and called == [2]
 
 
+def _main_on_one_fake_gpu(monkeypatch, capsys, args):
+    """bench.main() with run_workload and cpu_baseline stood in for: -> (run_workload calls, cpu_baseline calls, line)"""
+    import json
+    import torch
+    import bench
+    runs, cpus = [], []
+
+    def fake_run(cx, name, steps, warmup, variant="fused", world=None, want_kernel=True, dump=None, full=True):
+        runs.append((name, steps, warmup, want_kernel, dump, full))
+        return {"value": 1.0, "ms_per_step": 2.0, "timed_seconds": 3.0, "settle_steps": 4, "dtype": "f64",
+                "workload": name, "grid": [8, 4], "decomposition": "1 latitude band(s)", "bytes_per_cell_update": 80.0,
+                "hbm_roofline_frac_whole_job": 0.5}
+
+    monkeypatch.setattr(bench, "run_workload", fake_run)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda name: cpus.append(name) or {"value": 5.0})
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 1)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GCM_BENCH_BACKEND"):
+        monkeypatch.delenv(v, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + args)
+    bench.main()
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return runs, cpus, json.loads(lines[0])
+
+
+def test_plain_run_times_the_headline_only(monkeypatch, capsys):
+    """no --full: one run_workload call, the headline's, without the extra runs; no CPU baseline, no 'also'"""
+    sys.path.insert(0, ROOT)
+    runs, cpus, d = _main_on_one_fake_gpu(monkeypatch, capsys, ["--steps", "7", "--warmup", "3", "--dump-outputs", "D"])
+    assert runs == [("c3", 7, 3, True, "D", False)] and cpus == []
+    assert "also" not in d and "cpu_baseline" not in d
+    assert (d["value"], d["ms_per_step"], d["dtype"], d["steps"], d["warmup"]) == (1.0, 2.0, "f64", 7, 3)
+    assert d["unit"] == "cell-updates/s" and d["higher_is_better"] is True
+
+
+def test_full_run_adds_the_other_legs(monkeypatch, capsys):
+    """--full: the headline with its extra runs first, then every secondary workload and the CPU baselines;
+    --only / --no-cpu trim them"""
+    sys.path.insert(0, ROOT)
+    import bench
+    runs, cpus, d = _main_on_one_fake_gpu(monkeypatch, capsys, ["--full", "--steps", "7", "--warmup", "3"])
+    assert runs[0] == ("c3", 7, 3, True, None, True)
+    assert [r[0] for r in runs[1:]] == [n for n in bench.ALSO if n != "c3"] and all(r[5] for r in runs)
+    assert sorted(d["also"]) == sorted(n for n in bench.ALSO if n != "c3")
+    assert all("cpu_baseline" in r for r in d["also"].values()) and d["cpu_baseline"] == {"value": 5.0}
+    assert sorted(cpus) == sorted({n[:-4] if n.endswith("_f32") else n for n in bench.ALSO})   # each oracle once
+    runs, cpus, d = _main_on_one_fake_gpu(monkeypatch, capsys, ["--full", "--only", "--no-cpu"])
+    assert runs == [("c3", 200, 20, True, None, True)] and cpus == []
+    assert "also" not in d and d["cpu_baseline"] is None
+
+
 def test_workload_table_matches_baseline_configs():
     sys.path.insert(0, ROOT)
     import bench
