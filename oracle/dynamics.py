@@ -9,6 +9,23 @@ from .constants import Rd, Cp, G, P0, kappa
 from .grid import (ipj, imj, ijp, ijm, kp, km, kph, kmh, iph, imh, jph, jmh,
                    gradi, gradj)
 from .temperature import to_true_temp
+from .terms import check, term
+
+# named terms of half_timestep (oracle/terms.py).  pit: the column mass flux in the p equation; dut/dvt: the
+# horizontal momentum advection; dus/dvs: its sigma advection; pgu/phiu: the two pressure-gradient pieces of the
+# u equation (summed, then filtered), pgv/phiv those of v; advec_t/advec_q and advec_sig_t/advec_sig_q: the
+# horizontal and sigma advection of theta and q; filter_spu / filter_pgfu: what the polar filter changes in spu
+# and in pgu + phiu; coriolis_u / coriolis_v: the Coriolis terms (coriolis=True only).
+TERMS = ("pit", "dut", "dus", "pgu", "phiu", "dvt", "dvs", "pgv", "phiv", "advec_t", "advec_sig_t",
+         "advec_q", "advec_sig_q", "filter_spu", "filter_pgfu", "coriolis_u", "coriolis_v")
+
+
+def _filtered(terms, name, x, geom):
+    """lowpass.arakawa_1977(x), with what it changes in x scaled by terms[name] if that is given"""
+    f = lowpass.arakawa_1977(x, geom)
+    if not terms or name not in terms:
+        return f
+    return x + term(terms, name, f - x)
 
 
 def calc_pu(p, u): return u * iph(p)        # dynamics.py:15-17
@@ -33,7 +50,7 @@ def advec_sig(sd, q, geom):
     return -dq
 
 
-def advec_m_pu(p, u, v, pu, pv, geom, coriolis=False):
+def advec_m_pu(p, u, v, pu, pv, geom, coriolis=False, _terms=None):
     """dynamics.py:55-108.  The Coriolis branch is disabled by `if False` (:82) and the
     literal 0 is added instead (:94-95,103-104); `coriolis=True` restates the disabled
     branch (:83-92) as written."""
@@ -57,8 +74,11 @@ def advec_m_pu(p, u, v, pu, pv, geom, coriolis=False):
     else:
         coriolis_u = 0.0
         coriolis_v = coriolis_u
-    dut = (puum - puup) / geom.dx_j + (puvm - puvp) / geom.dy + coriolis_u
-    dvt = (pvvm - pvvp) / geom.dy + (pvum - pvup) / geom.dx_h + coriolis_v
+    T = _terms
+    dut = (term(T, "dut", (puum - puup) / geom.dx_j + (puvm - puvp) / geom.dy)
+           + term(T, "coriolis_u", coriolis_u))
+    dvt = (term(T, "dvt", (pvvm - pvvp) / geom.dy + (pvum - pvup) / geom.dx_h)
+           + term(T, "coriolis_v", coriolis_v))
     return dut, dvt
 
 
@@ -104,34 +124,38 @@ def advec_t(pu, pv, t, geom):
     return (tpu - imj(tpu)) / geom.dx_j + (tpv - ijm(tpv)) / geom.dy
 
 
-def half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, geom, _tap=None, coriolis=False):
-    """dynamics.py:183-227.  `_tap`, if a dict, receives every intermediate
-    (test instrumentation only)."""
+def half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, geom, _tap=None, coriolis=False, _terms=None):
+    """dynamics.py:183-227.  `_tap`, if a dict, receives every intermediate; `_terms`: see
+    oracle/terms.py (test instrumentation only)."""
+    check(_terms, TERMS)
+    T = _terms
     pu = calc_pu(p, u)
     spu_orig = calc_pu(sp, su)
-    spu = lowpass.arakawa_1977(spu_orig, geom)
+    spu = _filtered(T, "filter_spu", spu_orig, geom)
     pv = calc_pv(p, v)
     spv = calc_pv(sp, sv)
 
     pit, sd = aflux(spu, spv, geom)
-    p_n = p - pit * dt
+    p_n = p - term(T, "pit", pit) * dt
 
-    dut, dvt = advec_m_pu(sp, su, sv, spu, spv, geom, coriolis)
+    dut, dvt = advec_m_pu(sp, su, sv, spu, spv, geom, coriolis, T)
     pgu, pgv, phiu, phiv = pgf(sp, st, geom)
-    dus = advec_sig(iph(sd), su, geom)
-    dvs = advec_sig(jph(sd), sv, geom)
+    dus = term(T, "dus", advec_sig(iph(sd), su, geom))
+    dvs = term(T, "dvs", advec_sig(jph(sd), sv, geom))
 
-    pgfu = lowpass.arakawa_1977(pgu + phiu, geom)
+    pgfu = _filtered(T, "filter_pgfu", term(T, "pgu", pgu) + term(T, "phiu", phiu), geom)
     assert pu.shape == pgfu.shape
 
     pu_n = pu - (dut + dus + pgfu) * dt
-    pv_n = pv - (dvt + dvs + phiv + pgv) * dt
+    pv_n = pv - (dvt + dvs + term(T, "phiv", phiv) + term(T, "pgv", pgv)) * dt
 
     u_n = un_pu(pu_n, p_n)
     v_n = un_pv(pv_n, p_n)
 
-    t_n = (t * p - (advec_t(spu, spv, st, geom) + advec_sig(sd, st, geom)) * dt) / p_n
-    q_n = (q * p - (advec_t(spu, spv, sq, geom) + advec_sig(sd, sq, geom)) * dt) / p_n
+    t_n = (t * p - (term(T, "advec_t", advec_t(spu, spv, st, geom))
+                    + term(T, "advec_sig_t", advec_sig(sd, st, geom))) * dt) / p_n
+    q_n = (q * p - (term(T, "advec_q", advec_t(spu, spv, sq, geom))
+                    + term(T, "advec_sig_q", advec_sig(sd, sq, geom))) * dt) / p_n
 
     v_n[:, -1, :] *= 0
     if _tap is not None:
@@ -141,12 +165,13 @@ def half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, geom, _tap=None, coriol
     return p_n, u_n, v_n, t_n, q_n
 
 
-def matsuno_timestep(p, u, v, t, q, dt, geom, boundary_conditions=None, coriolis=False):
+def matsuno_timestep(p, u, v, t, q, dt, geom, boundary_conditions=None, coriolis=False, _terms=None):
     """dynamics.py:230-237."""
-    sp, su, sv, st, sq = half_timestep(p, u, v, t, q, p, u, v, t, q, dt, geom, coriolis=coriolis)
+    sp, su, sv, st, sq = half_timestep(p, u, v, t, q, p, u, v, t, q, dt, geom, coriolis=coriolis, _terms=_terms)
     if boundary_conditions:
         sp, su, sv, st, sq = boundary_conditions(sp, su, sv, st, sq, dt, geom)
-    op, ou, ov, ot, oq = half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, geom, coriolis=coriolis)
+    op, ou, ov, ot, oq = half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, geom, coriolis=coriolis,
+                                       _terms=_terms)
     if boundary_conditions:
         op, ou, ov, ot, oq = boundary_conditions(op, ou, ov, ot, oq, dt, geom)
     return op, ou, ov, ot, oq

@@ -3,6 +3,10 @@
 from .constants import Rd
 from .grid import im, iph1 as iph, imh1 as imh, div, gradh
 from .temperature import to_true_temp
+from .terms import check, term
+
+# named terms of half_timestep (oracle/terms.py)
+TERMS = ("advec_q", "advec_p", "advec_pu", "pgf", "advec_t")
 
 
 def advec_q(u, q, dx):
@@ -39,19 +43,22 @@ def pgf(p, t, dx):
     return pph / rho * gradh(p, dx)
 
 
-def half_timestep(p, u, t, q, sp, su, st, sq, dt, dx):
-    """no_limits.py:115-147."""
+def half_timestep(p, u, t, q, sp, su, st, sq, dt, dx, _terms=None):
+    """no_limits.py:115-147.  `_terms`: see oracle/terms.py (test
+    instrumentation only)."""
+    check(_terms, TERMS)
+    T = _terms
     pu = calc_pu(u, p)
     spu = calc_pu(su, sp)
-    q_n = q - advec_q(su, sq, dx) * dt
-    p_n = p - advec_p(spu, dx) * dt
-    pu_n = pu - (advec_pu(sp, spu, su, dx) + pgf(sp, st, dx)) * dt
+    q_n = q - term(T, "advec_q", advec_q(su, sq, dx)) * dt
+    p_n = p - term(T, "advec_p", advec_p(spu, dx)) * dt
+    pu_n = pu - (term(T, "advec_pu", advec_pu(sp, spu, su, dx)) + term(T, "pgf", pgf(sp, st, dx))) * dt
     u_n = un_pu(pu_n, p_n)
-    t_n = t - (advec_t(spu, st, dx) / p_n) * dt
+    t_n = t - (term(T, "advec_t", advec_t(spu, st, dx)) / p_n) * dt
     return p_n, u_n, t_n, q_n
 
 
-def matsuno_timestep(p, u, t, q, dt, dx):
+def matsuno_timestep(p, u, t, q, dt, dx, _terms=None):
     """no_limits.py:150-152."""
-    sp, su, st, sq = half_timestep(p, u, t, q, p, u, t, q, dt, dx)
-    return half_timestep(p, u, t, q, sp, su, st, sq, dt, dx)
+    sp, su, st, sq = half_timestep(p, u, t, q, p, u, t, q, dt, dx, _terms)
+    return half_timestep(p, u, t, q, sp, su, st, sq, dt, dx, _terms)

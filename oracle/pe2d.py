@@ -3,6 +3,10 @@
 from .constants import Rd
 from .grid import ipj, imj, ijp, ijm, iph, imh, jph, jmh, gradi, gradj
 from .temperature import to_true_temp
+from .terms import check, term
+
+# named terms of half_timestep (oracle/terms.py)
+TERMS = ("advec_p", "dut", "pgfu", "dvt", "pgfv", "advec_t")
 
 
 def calc_pu(p, u): return u * iph(p)       # no_limits_2d.py:21-23
@@ -53,24 +57,27 @@ def advec_t(pu, pv, t, dx):
     return (tpu - imj(tpu)) / dx + (tpv - ijm(tpv)) / dx
 
 
-def half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, dx):
-    """no_limits_2d.py:104-126 (q passes through unchanged, :126)."""
+def half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, dx, _terms=None):
+    """no_limits_2d.py:104-126 (q passes through unchanged, :126).  `_terms`:
+    see oracle/terms.py (test instrumentation only)."""
+    check(_terms, TERMS)
+    T = _terms
     pu = calc_pu(p, u)
     spu = calc_pu(sp, su)
     pv = calc_pv(p, v)
     spv = calc_pv(sp, sv)
-    p_n = p - advec_p(spu, spv, dx) * dt
+    p_n = p - term(T, "advec_p", advec_p(spu, spv, dx)) * dt
     dut, dvt = advec_m(sp, su, sv, dx)
     pgu, pgv = pgf(sp, st, dx)
-    pu_n = pu - (dut + pgu) * dt
-    pv_n = pv - (dvt + pgv) * dt
+    pu_n = pu - (term(T, "dut", dut) + term(T, "pgfu", pgu)) * dt
+    pv_n = pv - (term(T, "dvt", dvt) + term(T, "pgfv", pgv)) * dt
     u_n = un_pu(pu_n, p_n)
     v_n = un_pv(pv_n, p_n)
-    t_n = t - (advec_t(spu, spv, st, dx) / p_n) * dt
+    t_n = t - (term(T, "advec_t", advec_t(spu, spv, st, dx)) / p_n) * dt
     return p_n, u_n, v_n, t_n, q
 
 
-def matsuno_timestep(p, u, v, t, q, dt, dx):
+def matsuno_timestep(p, u, v, t, q, dt, dx, _terms=None):
     """no_limits_2d.py:129-131."""
-    sp, su, sv, st, sq = half_timestep(p, u, v, t, q, p, u, v, t, q, dt, dx)
-    return half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, dx)
+    sp, su, sv, st, sq = half_timestep(p, u, v, t, q, p, u, v, t, q, dt, dx, _terms)
+    return half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, dx, _terms)

@@ -1,6 +1,10 @@
 """2-D shallow water, Matsuno on the C-grid (reference matsuno_c_grid.py)."""
 from .constants import G
 from .grid import ipj, imj, ijp, ijm, imjp
+from .terms import check, term
+
+# named terms of matsumo_scheme (oracle/terms.py), each used in both Euler stages
+TERMS = ("adv_u", "pgf_u", "adv_v", "pgf_v", "adv_p")
 
 
 def advection_of_velocity_u(u, v, dx):
@@ -52,19 +56,22 @@ def advection_of_geopotential(u, v, p, dx):
     return (up_ipj - up_imj) / dx + (vp_ijp - vp_ijm) / dx
 
 
-def matsumo_scheme(u, v, p, dx, dt):
-    """matsuno_c_grid.py:125-142.  Takes and returns (u, v, p)."""
-    u_star = u - dt * (advection_of_velocity_u(u, v, dx) +
-                       geopotential_gradient_u(p, dx))
-    v_star = v - dt * (advection_of_velocity_v(u, v, dx) +
-                       geopotential_gradient_v(p, dx))
-    p_star = p - dt * advection_of_geopotential(u, v, p, dx)
+def matsumo_scheme(u, v, p, dx, dt, _terms=None):
+    """matsuno_c_grid.py:125-142.  Takes and returns (u, v, p).  `_terms`: see
+    oracle/terms.py (test instrumentation only)."""
+    check(_terms, TERMS)
+    T = _terms
+    u_star = u - dt * (term(T, "adv_u", advection_of_velocity_u(u, v, dx)) +
+                       term(T, "pgf_u", geopotential_gradient_u(p, dx)))
+    v_star = v - dt * (term(T, "adv_v", advection_of_velocity_v(u, v, dx)) +
+                       term(T, "pgf_v", geopotential_gradient_v(p, dx)))
+    p_star = p - dt * term(T, "adv_p", advection_of_geopotential(u, v, p, dx))
 
     geo_u_star = geopotential_gradient_u(p_star, dx)
-    u_next = u - dt * (advection_of_velocity_u(u_star, v_star, dx) +
-                       geo_u_star)
-    v_next = v - dt * (advection_of_velocity_v(u_star, v_star, dx) +
-                       geopotential_gradient_v(p_star, dx))
+    u_next = u - dt * (term(T, "adv_u", advection_of_velocity_u(u_star, v_star, dx)) +
+                       term(T, "pgf_u", geo_u_star))
+    v_next = v - dt * (term(T, "adv_v", advection_of_velocity_v(u_star, v_star, dx)) +
+                       term(T, "pgf_v", geopotential_gradient_v(p_star, dx)))
     pit_star = advection_of_geopotential(u_star, v_star, p_star, dx)
-    p_next = p - dt * pit_star
+    p_next = p - dt * term(T, "adv_p", pit_star)
     return u_next, v_next, p_next

@@ -5,6 +5,11 @@ from .grid import ipj, imj, ijp, ijm
 from .sw2d import (advection_of_velocity_u, advection_of_velocity_v,
                    geopotential_gradient_u, geopotential_gradient_v,
                    advection_of_geopotential)
+from .terms import check, term
+
+# named terms of matsumo_scheme (oracle/terms.py), each used in both Euler stages.  visc_u / visc_v are
+# mu lap(u) / rho in the u / v equation; "visc_v_of_v" substitutes lap(v) in the v equation.
+TERMS = ("adv_u", "pgf_u", "visc_u", "adv_v", "pgf_v", "visc_v", "adv_p", "adv_t")
 
 
 def finite_laplacian_2d(q, dx):
@@ -40,33 +45,36 @@ def geopotential_from(rho, p):
     return p / (G * rho)
 
 
-def matsumo_scheme(u, v, p, t, dx, dt):
-    """matsumo_temp.py:66-99.  The v equation uses the viscosity of u
-    (:75,:91) -- reproduced.  Takes and returns (u, v, p, t)."""
-    density = density_from(p, t)
-    geo = geopotential_from(density, p)
-    scaled_t = scaling(p, t, dx)
-    u_star = u - dt * (advection_of_velocity_u(u, v, dx)
-                       + geopotential_gradient_u(geo, dx)
-                       - incompressible_viscosity_2d(u, mu_air, dx) / density)
-    v_star = v - dt * (advection_of_velocity_v(u, v, dx)
-                       + geopotential_gradient_v(geo, dx)
-                       - incompressible_viscosity_2d(u, mu_air, dx) / density)
-    p_star = p - dt * advection_of_geopotential(u, v, p, dx)
-    tt = scaled_t - dt * advection_of_geopotential(u, v, scaled_t, dx)
-    t_star = unscaling(p_star, tt, dx)
+def euler_stage(u, v, p, scaled_t, su, sv, sp, st, dx, dt, _terms=None):
+    """One Euler stage of matsumo_temp.py:66-99: the tendencies of the state (su, sv, sp, st) applied to the
+    base state (u, v, p) and to the base's scaled temperature.  Returns (u, v, p, t)."""
+    T = _terms
+    density = density_from(sp, st)
+    geo = geopotential_from(density, sp)
+    scaled_st = scaling(sp, st, dx)
+    u_n = u - dt * (term(T, "adv_u", advection_of_velocity_u(su, sv, dx))
+                    + term(T, "pgf_u", geopotential_gradient_u(geo, dx))
+                    - term(T, "visc_u", incompressible_viscosity_2d(su, mu_air, dx) / density))
+    v_n = v - dt * (term(T, "adv_v", advection_of_velocity_v(su, sv, dx))
+                    + term(T, "pgf_v", geopotential_gradient_v(geo, dx))
+                    - term(T, "visc_v", incompressible_viscosity_2d(su, mu_air, dx) / density,
+                           visc_v_of_v=lambda: incompressible_viscosity_2d(sv, mu_air, dx) / density))
+    p_n = p - dt * term(T, "adv_p", advection_of_geopotential(su, sv, sp, dx))
+    tt = scaled_t - dt * term(T, "adv_t", advection_of_geopotential(su, sv, scaled_st, dx))
+    return u_n, v_n, p_n, unscaling(p_n, tt, dx)
 
-    density_star = density_from(p_star, t_star)
-    geo_star = geopotential_from(density_star, p_star)
-    scaled_t_star = scaling(p_star, t_star, dx)
-    u_next = u - dt * (advection_of_velocity_u(u_star, v_star, dx)
-                       + geopotential_gradient_u(geo_star, dx)
-                       - incompressible_viscosity_2d(u_star, mu_air, dx) / density_star)
-    v_next = v - dt * (advection_of_velocity_v(u_star, v_star, dx)
-                       + geopotential_gradient_v(geo_star, dx)
-                       - incompressible_viscosity_2d(u_star, mu_air, dx) / density_star)
-    pit_star = advection_of_geopotential(u_star, v_star, p_star, dx)
-    p_next = p - dt * pit_star
-    tt_next = scaled_t - dt * advection_of_geopotential(u_star, v_star, scaled_t_star, dx)
-    t_next = unscaling(p_next, tt_next, dx)
-    return u_next, v_next, p_next, t_next
+
+def predictor(u, v, p, t, dx, dt, _terms=None):
+    """matsumo_temp.py:66-80: the predicted ("star") state (u*, v*, p*, t*)."""
+    check(_terms, TERMS)
+    return euler_stage(u, v, p, scaling(p, t, dx), u, v, p, t, dx, dt, _terms)
+
+
+def matsumo_scheme(u, v, p, t, dx, dt, _terms=None):
+    """matsumo_temp.py:66-99.  The v equation uses the viscosity of u
+    (:75,:91) -- reproduced.  Takes and returns (u, v, p, t).  `_terms`: see
+    oracle/terms.py (test instrumentation only)."""
+    check(_terms, TERMS)
+    scaled_t = scaling(p, t, dx)
+    star = euler_stage(u, v, p, scaled_t, u, v, p, t, dx, dt, _terms)
+    return euler_stage(u, v, p, scaled_t, *star, dx, dt, _terms)

@@ -12,6 +12,7 @@ from operator import mul
 import numpy as np
 
 from .constants import Rd, kappa, P0, standard_temperature
+from .terms import check, term
 
 
 def upwind_axis_finite(dt, spatial_change, V, q, axis=0):
@@ -183,7 +184,12 @@ def calc_r_axis(q, axis):
     return np.divide(a, b, out=np.zeros_like(a), where=(b != 0))
 
 
-def limited_axis(dt, spatial_change, V, q, axis=0, limiter=True):
+# named terms of limited_advection (oracle/terms.py): the whole face flux and the van Leer correction
+# phi (F_high - F_low) of each axis, j = axis 0, i = axis 1
+TERMS = ("flux_j", "vanleer_j", "flux_i", "vanleer_i")
+
+
+def limited_axis(dt, spatial_change, V, q, axis=0, limiter=True, _terms=None):
     """Flux-limited finite-volume step along one axis (NOT in the reference).
 
     Face flux F = F_low + phi(r_up) * (F_high - F_low) with
@@ -211,15 +217,18 @@ def limited_axis(dt, spatial_change, V, q, axis=0, limiter=True):
         r_pos = np.divide(a, b, out=np.zeros_like(a), where=(b != 0))
         r_neg = np.divide(c, b, out=np.zeros_like(a), where=(b != 0))
         r = np.where(V[axis] > 0, r_pos, r_neg)
-        flux = f_low + van_leer(r) * (f_high - f_low)
+        flux = f_low + term(_terms, "vanleer_" + "ji"[axis], van_leer(r) * (f_high - f_low))
     else:
         flux = f_low
+    flux = term(_terms, "flux_" + "ji"[axis], flux)
     return q - flux + np.roll(flux, 1, axis)
 
 
-def limited_advection(dt, spatial_change, V, q, limiter=True):
-    """Dimension-split (axis 0 then 1, as two_d.py:198-207) limited step."""
+def limited_advection(dt, spatial_change, V, q, limiter=True, _terms=None):
+    """Dimension-split (axis 0 then 1, as two_d.py:198-207) limited step.
+    `_terms`: see oracle/terms.py (test instrumentation only)."""
+    check(_terms, TERMS)
     q_star = q
     for axis in range(2):
-        q_star = limited_axis(dt, spatial_change, V, q_star, axis, limiter)
+        q_star = limited_axis(dt, spatial_change, V, q_star, axis, limiter, _terms)
     return q_star
