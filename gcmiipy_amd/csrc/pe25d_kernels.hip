@@ -499,7 +499,7 @@ struct Pe25d {
     int ghost_ready = -1;                       // state set whose ghost rows' column sums and anchors are queued already (pe25d_prep_ghost_rows)
     int last_unpack_set = -1;                   // state set whose ghost rows the last unpack filled (halo_t)
     bool pit2d = true;                          // pit from the column sums K4 leaves (nseg == 1, row-group K4)
-    int nseg_edge = 1;                          // bands: level segments of the EDGE rows' K4 launch (see half_t)
+    int nseg_edge = 1;                          // bands: level segments of the EDGE rows' K4 launch (see update_edges)
     bool cs_valid[3] = {false, false, false};   // the state set's column sums belong to its winds
     int pack_set = -1;                          // >= 0: state set gcm_halo_pack reads (step_phase)
     double *stage3 = nullptr;                   // float64 transpose staging, host layout
@@ -516,11 +516,14 @@ struct Pe25d {
     std::vector<double> rad_tab_host, rad_geo_host, rad_latlon;   // host copies (upload sources, change detection)
     std::vector<hipEvent_t> *ev = nullptr;
     size_t *ev_used = nullptr;
-    hipStream_t aux = nullptr;                  // second stream of a stage (K2a -> K3), see half_t
+    hipStream_t aux = nullptr;                  // second stream of a stage: chain B (K1 + pit, a band's edge rows), see half_t
     hipStream_t aux2 = nullptr;                 // bands: third stream, K1 of the band's OWN rows (no ghost data: off the exchange chain)
     hipEvent_t ev_cs = nullptr;                 // aux2: the own edge rows' column sums of the state just produced are in place
     int edge_cs_set = -1;                       // state set whose own edge rows' column sums were queued on aux2 (nseg_edge > 1)
     bool k1_split = true;                       // GCM_PE_K1_SPLIT=0: K1 of all rows behind the exchange, as in round 3
+    bool filter_no_loop = false;                // GCM_PE_FILTER_NO_LOOP (diagnostic): K1 as one workgroup per pair
+    bool k4_oddtop = true;                      // GCM_PE_K4_ODDTOP=0: K4's whole columns start on an even level
+    bool rad_generic = false;                   // GCM_PE_RAD_GENERIC (diagnostic): the LDS-parked form of the radiation kernel
     // The events a stage's chains hand each other are signalled by the producing kernel's OWN completion
     // (hipExtLaunchKernelGGL's stopEvent) where a kernel is what they follow: a hipEventRecord is a packet of
     // its own behind the kernel and costs the stream 3 us (tools/micro/sync_cost.hip: 8.9 vs 5.9 us per
@@ -547,13 +550,13 @@ struct Pe25d {
     // passive tracers (gcm_set_tracers; a band: gcm_set_band_tracers first): 2 x ntr fields of (H + 2 tr_ghost(m)) x L x W
     // in T, device layout [j][k][i] -- the current set (ntr fields), then the star set; a band's fields carry one ghost
     // row a side (the kernel reads rows j -+ 1 only), addressed from interior row 0.  The tracer kernel runs on chain B
-    // (see half_t); ev_tr, recorded on `aux` behind the last tracer launch, is how the caller's stream joins that tail
+    // (see stage_tracers); ev_tr, recorded on `aux` behind the last tracer launch, is how the caller's stream joins that tail
     int ntr = 0;
     void *tr = nullptr;
     bool tr_star = false;                       // the star set holds the tracers of a predictor
     bool tr_pending = false;                    // a tracer launch on `aux` that the caller's stream has not joined
     hipEvent_t ev_tr = nullptr;
-    // a band's split stage (modes 1 + 2) runs the tracers' interior rows on the third stream (see half_t): ev_tr_int
+    // a band's split stage (modes 1 + 2) runs the tracers' interior rows on the third stream (see stage_tracers): ev_tr_int
     // follows that launch; the next stage's chain B waits for it (tr_int_wait), the caller's stream joins it (tr_int_join)
     hipEvent_t ev_tr_int = nullptr;
     hipStream_t tr_int_stream = nullptr;
@@ -702,23 +705,12 @@ static const char *alloc_all(Pe25d *m, const gcm_config &cfg) {
         hipFuncSetAttribute((const void *)pe_geopot_kernel<T, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(L * kColThreads * sizeof(T))) != hipSuccess ||
         hipFuncSetAttribute((const void *)pe_radiation_kernel<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(sizeof(double) * (size_t)L * kRadThreads)) != hipSuccess ||
-        hipFuncSetAttribute((const void *)update_rows_kernel_for<T>(7, true), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)upd_lds_bytes<T>(7, L)) != hipSuccess ||
-        hipFuncSetAttribute((const void *)update_rows_kernel_for<T>(7, false), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)upd_lds_bytes<T>(7, L)) != hipSuccess ||
-        hipFuncSetAttribute((const void *)update_rows_kernel_for<T>(7, true, true), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)upd_lds_bytes<T>(7, L)) != hipSuccess ||
-        hipFuncSetAttribute((const void *)update_rows_kernel_for<T>(7, false, true), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)upd_lds_bytes<T>(7, L)) != hipSuccess ||
-        hipFuncSetAttribute((const void *)update_rows_kernel_for<T>(3, true, true), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)upd_lds_bytes<T>(3, L)) != hipSuccess ||
-        hipFuncSetAttribute((const void *)update_rows_kernel_for<T>(3, false, true), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)upd_lds_bytes<T>(3, L)) != hipSuccess ||
-        hipFuncSetAttribute((const void *)update_rows_kernel_for<T>(3, true), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)upd_lds_bytes<T>(3, L)) != hipSuccess ||
-        hipFuncSetAttribute((const void *)update_rows_kernel_for<T>(3, false), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)upd_lds_bytes<T>(3, L)) != hipSuccess)
+                            (int)(sizeof(double) * (size_t)L * kRadThreads)) != hipSuccess)
+        return "dynamic LDS size";
+    for (const int R : {7, 3})                   // K4: rows per workgroup x (same, oddtop)
+        for (const int v : {0, 1, 2, 3})
+            if (hipFuncSetAttribute((const void *)update_rows_kernel_for<T>(R, v & 1, v & 2), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)upd_lds_bytes<T>(R, L)) != hipSuccess)
         return "dynamic LDS size";
     return nullptr;
 }
@@ -921,6 +913,9 @@ Pe25d *pe25d_create(const gcm_config &cfg, hipStream_t main_stream, std::string 
         }
     }
     if (const char *e = getenv("GCM_PE_STOP_EVENTS")) m->stop_events = atoi(e) != 0;
+    m->filter_no_loop = getenv("GCM_PE_FILTER_NO_LOOP") != nullptr;
+    if (const char *e = getenv("GCM_PE_K4_ODDTOP")) m->k4_oddtop = e[0] != '0';
+    m->rad_generic = getenv("GCM_PE_RAD_GENERIC") != nullptr;
     if (hipEventCreateWithFlags(&m->ev_pre_edge, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&m->ev_k4, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&m->ev_cs, hipEventDisableTiming) != hipSuccess ||
@@ -1055,35 +1050,49 @@ static void tick(Pe25d *m, hipStream_t s) {
     if (m->ev && m->ev_used && *m->ev_used < m->ev->size()) (void)hipEventRecord((*m->ev)[(*m->ev_used)++], s);
 }
 
+// What follows a kernel launch: nothing, or the event `ev` (see Pe25d::stop_events).  stop_only: K4's ev_k4, signalled as
+// the kernel's stop event or not at all, never by a record
+struct Then { hipEvent_t ev = nullptr; bool stop_only = false; };
+
+// The one way a stage launches a kernel that an event follows: `kern` on `st`, and `then.ev` behind it -- the kernel's
+// own completion with stop events, else a record behind the launch (none for `stop_only`: without stop events
+// k4_fork_valid stays false and nobody waits for ev_k4).
+template <typename... P>
+static void launch(const Pe25d *m, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Then then, const P &...args) {
+    if (then.ev && m->stop_events) return hipExtLaunchKernelGGL(kern, grid, block, (unsigned)lds, st, nullptr, then.ev, 0, args...);
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    if (then.ev && !then.stop_only) (void)hipEventRecord(then.ev, st);
+}
+
+// `a` over rows [j0, j1) and [jb0, jb1)
+template <typename T>
+static PeArgsT<T> rows_of(PeArgsT<T> a, int j0, int j1, int jb0 = 0, int jb1 = 0) { a.j0 = j0; a.j1 = j1; a.jb0 = jb0; a.jb1 = jb1; return a; }
+
+// pe_geopot_kernel over the rows of `c` ([j0, j1) and [jb0, jb1)); c.geo_j0 / geo_j1: the rows it forms phi
+// for, c.cs_rows: it also forms the column sums of all its rows
+template <typename T>
+static void launch_geopot(const Pe25d *m, const PeArgsT<T> &c, hipStream_t st) {
+    const int rows = (c.j1 - c.j0) + (c.jb1 - c.jb0), L = m->L;
+    if (rows <= 0) return;
+    const long tiles = (long)((m->W + kColThreads - 1) / kColThreads) * rows;
+    const size_t park = L <= 40 ? 0 : sizeof(T) * (size_t)L * kColThreads;
+    void (*kern)(PeArgsT<T>) =
+        c.cs_rows ? (L <= 24 ? pe_geopot_kernel<T, 24, true> : L <= 40 ? pe_geopot_kernel<T, 40, true> : pe_geopot_kernel<T, 0, true>)
+                  : (L <= 24 ? pe_geopot_kernel<T, 24> : L <= 40 ? pe_geopot_kernel<T, 40> : pe_geopot_kernel<T, 0>);
+    launch(m, kern, dim3((unsigned)((tiles + 7) / 8 * 8)), dim3(kColThreads), park, st, Then{}, c);
+}
+
 // Column sums and geopotential anchors of the stage state's rows that no kernel of the previous stage left:
 // all rows' sums of a freshly set state, else a band's two ghost rows next to its own (pit of row j takes V of
 // row j - 1; the intermediates extend to row j1) -- and, in the same launch, the geopotential of a band's south
-// ghost row (K4 of row j1 - 1 takes phi of row j1).  `a`: the stage's arguments with j0 / j1 set.
+// ghost row (K4 of row j1 - 1 takes phi of row j1).  `a`: the stage's arguments.
 template <typename T>
 static void prep_rows(Pe25d *m, const PeArgsT<T> &a, int stage_set, bool p2, int j1, int ext, hipStream_t sb) {
-    const int W = m->W, L = m->L;
-    const auto geopot = [&](const PeArgsT<T> &c, hipStream_t st) {
-        const int rows = (c.j1 - c.j0) + (c.jb1 - c.jb0);
-        if (rows <= 0) return;
-        const long tiles = (long)((W + kColThreads - 1) / kColThreads) * rows;
-        const dim3 gg((unsigned)((tiles + 7) / 8 * 8));
-        const size_t park = sizeof(T) * (size_t)L * kColThreads;
-        if (c.cs_rows) {
-            if (L <= 24) hipLaunchKernelGGL((pe_geopot_kernel<T, 24, true>), gg, dim3(kColThreads), 0, st, c);
-            else if (L <= 40) hipLaunchKernelGGL((pe_geopot_kernel<T, 40, true>), gg, dim3(kColThreads), 0, st, c);
-            else hipLaunchKernelGGL((pe_geopot_kernel<T, 0, true>), gg, dim3(kColThreads), park, st, c);
-        } else {
-            if (L <= 24) hipLaunchKernelGGL((pe_geopot_kernel<T, 24>), gg, dim3(kColThreads), 0, st, c);
-            else if (L <= 40) hipLaunchKernelGGL((pe_geopot_kernel<T, 40>), gg, dim3(kColThreads), 0, st, c);
-            else hipLaunchKernelGGL((pe_geopot_kernel<T, 0>), gg, dim3(kColThreads), park, st, c);
-        }
-    };
     PeArgsT<T> c = a;
     c.jb0 = c.jb1 = 0;
     bool fresh = false;
-    if (!p2) {
-        c.j0 = j1; c.j1 = j1 + ext;
-    } else if (!m->cs_valid[stage_set]) {
+    if (!p2) { c.j0 = j1; c.j1 = j1 + ext; }
+    else if (!m->cs_valid[stage_set]) {
         c.j0 = m->wrap ? 0 : -1;
         c.j1 = m->H + ext;
         m->cs_valid[stage_set] = true;
@@ -1099,11 +1108,11 @@ static void prep_rows(Pe25d *m, const PeArgsT<T> &a, int stage_set, bool p2, int
     c.geo_j0 = j1; c.geo_j1 = j1 + ext;
     if (fresh && (c.j1 - c.j0) > 8) {
         // a whole state's sums: the plain column-sum kernel (no thermodynamics compiled in), then the ghost row
-        hipLaunchKernelGGL(pe_colsum_kernel<T>, dim3((unsigned)((W + 255) / 256) * (c.j1 - c.j0)), dim3(256), 0, sb, c);
+        hipLaunchKernelGGL(pe_colsum_kernel<T>, dim3((unsigned)((m->W + 255) / 256) * (c.j1 - c.j0)), dim3(256), 0, sb, c);
         c.cs_rows = 0;
         c.j0 = j1; c.j1 = j1 + ext;
     }
-    if (!m->wrap || (fresh && c.cs_rows)) geopot(c, sb);
+    if (!m->wrap || (fresh && c.cs_rows)) launch_geopot(m, c, sb);
 }
 
 // The passive tracers of one stage (pe25d_tracer.h) over rows [r0, r1) and [rb0, rb1): base = the current tracers,
@@ -1143,326 +1152,338 @@ static void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out
     if (m->aux && st == m->aux) m->tr_pending = true;
 }
 
-// one Euler stage over rows [j0, j1): state `stage_set` -> `out_set`, base = current.
+// ---------------------------------------------------------------- one Euler stage
+// One Euler stage over rows [j0, j1): state `stage_set` -> `out_set`, base = current.
 // mode 0: everything; mode 1: K1-K3 on all rows + K4 on the two edge rows of either side (the rows
 // a neighbouring band needs); mode 2: K4 on the remaining interior rows.  Modes 1 + 2 == mode 0.
 // chained: the call comes from gcm_band_run's own sequence (nothing but the stage's kernels between two stages on `s`)
+// Two chains on two streams (a cross-queue dependency costs ~10 us on this chip when the waiting queue
+// is already idle, ~3 us when the event completed earlier: tools/micro/sync_cost.hip):
+//   A, the caller's stream:  K2a (own rows) -> K3 -> K4 (all rows, or the interior rows of a band)
+//   B, the second stream:    column sums and anchors of the ghost rows -> K1 (+ pit) [-> a band's edge
+//                            rows: their partial sums, K4, pack; the exchange and the unpack follow]
+// A is the long chain and runs without waiting for anything that has not long finished: K4 waits for
+// B's K1 (done while K3 runs), the next stage's K2a for B's edge rows (done while the interior rows
+// run).  A never touches ghost rows, so it never waits for an exchange; B does, in stream order.
+// (Round 4, built and rejected: the edge rows' K3 as a launch of its own on chain B right behind K2a, so that their
+// K4, the pack and the exchange start before the interior rows' K4 takes the chip.  Four rows are 48 workgroups of
+// five dependent LDS passes: 30-60 us on a chain that already holds K1's ghost-row launch and the partial sums, and
+// the N = 8 band got 4 % slower with no exchange time and 10 % slower with 40 us of it
+// (profiles/r04/ab_band_edge_k3_on_chain_b.txt: `base` = with it).)
+// Stage: what a stage is, decided once from the handle's state as it begins (stage_facts); the steps read it, change only the handle.
+template <typename T>
+struct Stage {
+    int stage_set, out_set, j0, j1, mode; double dt;
+    PeArgsT<T> a;                                // the stage's arguments; every launch takes its own rows (rows_of)
+    hipStream_t s;                               // chain A: the caller's stream
+    hipStream_t sb;                              // chain B: the second stream (the caller's when the handle has one stream)
+    hipStream_t se;                              // the edge rows' stream (mode 1): chain B's with send buffers registered, else the caller's
+    hipEvent_t fork;                             // what chain B follows on the caller's stream (chain_b_head)
+    int ext;                                     // intermediates are also needed on row j1 (south)
+    bool p2;                                     // pit from the 2-D column sums (pe_pit2d_kernel) where K4 marches whole columns and can leave them
+    bool split;                                  // modes 1 + 2 of a band with interior rows between its edge rows
+    bool edge_segs;                              // the edge rows are marched in level segments (update_edges)
+    FilterLoopKernel<T> k1;                      // the looping form of K1, or null
+    bool tr_prev;                                // the last stage's tracer launch on another stream may still run (hazard 1, chain_b_head)
+    bool ghosts_queued;                          // the ghost rows' column sums and anchors are queued behind the unpack already
+    bool split_k1;                               // K1 of the own rows on the third stream, of the ghost-dependent rows on the second
+};
+
+template <typename T>
+static Stage<T> stage_facts(Pe25d *m, int stage_set, int out_set, double dt, int j0, int j1, hipStream_t s, int mode, bool chained) {
+    Stage<T> g{};
+    g.stage_set = stage_set; g.out_set = out_set; g.j0 = j0; g.j1 = j1; g.mode = mode; g.dt = dt;
+    g.a = make_args<T>(m, stage_set, out_set, dt);
+    g.ext = m->wrap ? 0 : 1;
+    g.p2 = m->pit2d && g.a.nseg == 1;
+    if (g.p2) { g.a.ocs_u = bufs<T>(m).cs[out_set][0]; g.a.ocs_v = bufs<T>(m).cs[out_set][1]; }     // (the column sums K4 leaves)
+    g.s = s; g.sb = m->aux ? m->aux : s;
+    g.se = (mode == 1 && async_edges(m) && m->aux) ? m->aux : s;
+    // the previous stage's K4 (its own completion, ev_k4, when nothing else that B reads or overwrites was queued
+    // since: k4_fork_valid, which only stop events set), else the stream's position now
+    g.fork = (m->k4_fork_valid && chained) ? m->ev_k4 : m->ev_fork;
+    g.split = mode != 0 && (j1 - j0) > 2 * kGhost;
+    g.edge_segs = g.split && g.p2 && m->nseg_edge > 1;
+    if (mode == 2) return g;                     // (K4 of the interior rows: the rest belongs to modes 0 and 1)
+    g.k1 = (m->cfg.filter && m->W > 1 && !m->filter_no_loop) ? spu_filter_loop_kernel_for<T>(m->cplan) : nullptr;
+    g.tr_prev = m->tr_int_wait;
+    g.ghosts_queued = m->ghost_ready == stage_set && (!g.p2 || m->cs_valid[stage_set]);
+    // A band inside gcm_band_run (the ghost rows' column sums and anchors are queued behind the unpack already):
+    // K1 is row-local -- spu of row j takes su and sp of row j only, pit of row j the column sums of rows j - 1, j
+    // and sp of rows j - 1 .. j + 1 -- so the band's OWN rows need nothing from the exchange.  They go to a third
+    // stream that waits for the previous stage's K4 only (spu of rows [0, H), pit of rows [2, H - 2]: what the
+    // interior rows' K4 reads), and the second stream keeps the launch for the rows that do need ghost data (spu of
+    // the south ghost row, pit of rows 0, 1, H - 1, H).  The interior rows' K4 then waits for the own-row launch
+    // alone, not for the exchange chain (round 3: 32 us per corrector stage of the N = 8 band of C4).
+    g.split_k1 = g.k1 && mode == 1 && m->aux2 && g.p2 && g.ghosts_queued && (j1 - j0) >= 2 * kGhost + 3 &&
+                 (m->nseg_edge == 1 || m->edge_cs_set == stage_set);
+    return g;
+}
+
+// ---- chain B: everything that reads the whole stage state, ghost rows included.  Its head: what it waits for, and the ghost rows
+template <typename T>
+static void chain_b_head(Pe25d *m, const Stage<T> &g) {
+    if (m->aux) {
+        if (g.fork == m->ev_fork) (void)hipEventRecord(m->ev_fork, g.s);
+        (void)hipStreamWaitEvent(m->aux, g.fork, 0);
+    }
+    // hazard 1 of a band's tracers: this stage's K1 overwrites spu, pit and p_n -- and its K4 the state sets -- that
+    // the last stage's tracer launch on another stream may still read (ev_tr_int, see stage_tracers): chain B waits for
+    // it here, and so does the caller's stream where it takes the edge rows (no send buffers: the tracers' edge rows
+    // read what that launch wrote); the third stream's K1 follows it in stream order, or waits for it in chain_b_k1_pit
+    m->tr_int_wait = false;
+    if (g.tr_prev) {
+        if (g.sb != m->tr_int_stream) (void)hipStreamWaitEvent(g.sb, m->ev_tr_int, 0);
+        if (g.mode == 1 && g.se != g.sb && g.se != m->tr_int_stream) (void)hipStreamWaitEvent(g.se, m->ev_tr_int, 0);
+    }
+    if (g.ghosts_queued) m->ghost_ready = -1;                    // queued behind the unpack already
+    else prep_rows<T>(m, g.a, g.stage_set, g.p2, g.j1, g.ext, g.sb);
+    // (the own edge rows' column sums of this state were queued on the third stream behind the edge rows' K4
+    // of the stage that produced it: everything on the second stream that reads them waits for that)
+    if (m->aux2 && m->edge_cs_set == g.stage_set) (void)hipStreamWaitEvent(g.sb, m->ev_cs, 0);
+}
+
+// The looping K1 over `rows` rows of `c`: all pairs of a row in one workgroup when there are rows enough to fill the
+// chip, else groups; with `pit` (the 2-D form of pit) one more workgroup per row forms pit and p_n (pe_pit2d_row)
+template <typename T>
+static void launch_k1(const Pe25d *m, FilterLoopKernel<T> k1, const PeArgsT<T> &c, int rows, bool pit, hipStream_t st, hipEvent_t ev) {
+    const int pairs = (m->L + 1) / 2;
+    const int groups = std::min(pairs, std::max(1, (3 * m->cus + rows - 1) / rows));
+    const int ppw = (pairs + groups - 1) / groups;
+    const int ny = (pairs + ppw - 1) / ppw;
+    launch(m, k1, dim3(rows, ny + (pit ? 1 : 0)), dim3(m->cplan.ok ? m->cplan.threads : kFftThreads), filter_loop_lds_bytes<T>(m), st,
+           Then{ev}, c, ppw, pit ? ny : -1);
+}
+
+// ---- chain B: K1 and pit of rows [j0, j1 + ext), and ev_a behind them (what K4 of the interior rows takes from this chain)
+template <typename T>
+static void chain_b_k1_pit(Pe25d *m, const Stage<T> &g) {
+    const int j0 = g.j0, j1 = g.j1, ext = g.ext;
+    const PeArgsT<T> a = rows_of(g.a, j0, j1 + ext);
+    const int fft_threads = m->cplan.ok ? m->cplan.threads : kFftThreads;
+    bool pit_done = false, ev_a_done = false;
+    if (g.split_k1) {                            // (see stage_facts)
+        (void)hipStreamWaitEvent(m->aux2, g.fork, 0);
+        // (the previous stage's edge rows: su, sp of rows 0, 1, H - 2, H - 1 -- and its tracers' edge rows, queued
+        // ahead of the pack: they read spu, pit and p_n of those rows, which this K1 overwrites)
+        if (m->edges_ev_valid) (void)hipStreamWaitEvent(m->aux2, m->ev_edges, 0);
+        if (g.tr_prev && m->tr_int_stream != m->aux2) (void)hipStreamWaitEvent(m->aux2, m->ev_tr_int, 0);
+        PeArgsT<T> c = rows_of(a, j0, j1);
+        c.pit_j0 = j0 + kGhost; c.pit_j1 = j1 - kGhost + 1;
+        launch_k1<T>(m, g.k1, c, j1 - j0, true, m->aux2, m->ev_a);             // (ev_a: what K4 of the interior rows takes)
+        c = rows_of(a, j0, j0 + kGhost, j1 - 1, j1 + ext);
+        c.spu_j0 = j1; c.spu_j1 = j1 + ext;
+        launch_k1<T>(m, g.k1, c, kGhost + 1 + ext, true, g.sb, nullptr);
+        pit_done = ev_a_done = true;             // (chain B waits for ev_a in update_edges, ahead of the edge rows' partial sums)
+    } else if (g.k1) {
+        ev_a_done = g.p2 && m->aux;              // pit rides in the launch: ev_a follows K1 itself
+        launch_k1<T>(m, g.k1, a, a.j1 - a.j0, g.p2, g.sb, ev_a_done ? m->ev_a : nullptr);
+        pit_done = g.p2;
+    } else {
+        hipLaunchKernelGGL(spu_filter_kernel_for<T>(m->cplan), dim3(a.j1 - a.j0, (m->L + 1) / 2), dim3(fft_threads), filter_lds_bytes<T>(m), g.sb, a);
+    }
+    if (g.p2 && !pit_done) {
+        hipLaunchKernelGGL(pit2d_kernel_for<T>(m->cplan), dim3(a.j1 - a.j0), dim3(fft_threads), pit2d_lds_bytes<T>(m), g.sb, a);
+    } else if (!g.p2) {
+        const long tiles = (long)((m->W + 255) / 256) * (a.j1 - a.j0);
+        hipLaunchKernelGGL(pe_pit_kernel<T>, dim3((unsigned)((tiles + 7) / 8 * 8)), dim3(256), 0, g.sb, a);
+    }
+    if (m->aux && !ev_a_done) (void)hipEventRecord(m->ev_a, m->aux);      // (behind the pit kernel)
+}
+
+// ---- the passive tracers that do not belong to a band's edge rows (those: update_edges)
+template <typename T>
+static void stage_tracers(Pe25d *m, const Stage<T> &g) {
+    if (m->ntr <= 0) return;
+    // Single domain: on chain B right behind K1 + pit and after ev_a, so that K4 on
+    //      chain A never waits for them and they run beside K2a, K3 and K4.  Two invariants hold them in place:
+    //      * the next stage's K1 must not overwrite spu, pit or p_n while this launch still reads them: it is
+    //        queued on this same stream behind it.  (Not on `s` behind K4: chain B forks at ev_k4 when
+    //        k4_fork_valid is set, and the next K1 would then race the tracer kernel.)  The state sets it reads
+    //        (sp, sv, p) are overwritten only by a later K4, which waits for a later ev_a: behind this launch too;
+    //      * everything that returns to the caller joins chain B's tail: gcm_step (and so gcm_time_steps'
+    //        stop event), gcm_half_step, gcm_get_tracers, gcm_set_tracers and gcm_sync make `s` wait for ev_tr,
+    //        recorded on `aux` behind the last tracer launch (pe25d_join_tracers).
+    //      Without tracers nothing is launched, recorded or waited for here.
+    //      A band: the whole stage (mode 0) takes the same launch over its own rows, and the next stage's chain B
+    //      waits for it on the streams where it does not follow in stream order (ev_tr_int, hazard 1 in chain_b_head).
+    if (g.mode == 0) {
+        launch_tracers<T>(m, g.a, g.stage_set, g.out_set, g.sb, g.j0, g.j1);
+        if (!m->wrap && m->aux) {
+            (void)hipEventRecord(m->ev_tr_int, g.sb);
+            m->tr_int_stream = g.sb;
+            m->tr_int_wait = true;
+        }
+    }
+    // ---- a band's split stage (modes 1 + 2): the tracers' edge rows go ahead of the pack (see update_edges), the
+    //      interior rows [j0 + 2, j1 - 2) here, on the third stream right behind the own rows' K1 (ev_a): off the
+    //      exchange chain, which never waits for them within the stage, and beside K2a and K3 on the caller's
+    //      stream, whose LDS-bound passes leave memory bandwidth free.  ev_tr_int follows them: the next stage's
+    //      chain B waits for it (hazard 1), the caller's stream joins it (pe25d_join_tracers).  Without a third
+    //      stream they go to the caller's stream, where the next stage's chain B follows them through the fork.
+    if (g.mode == 1 && g.split) {
+        hipStream_t ti = m->aux2 ? m->aux2 : g.s;
+        if (m->aux && !(g.split_k1 && ti == m->aux2)) (void)hipStreamWaitEvent(ti, m->ev_a, 0);   // (K1 + pit of all rows)
+        launch_tracers<T>(m, g.a, g.stage_set, g.out_set, ti, g.j0 + kGhost, g.j1 - kGhost);
+        if (ti != g.s) {
+            (void)hipEventRecord(m->ev_tr_int, ti);
+            m->tr_int_stream = ti;
+            m->tr_int_wait = m->tr_int_join = true;
+        }
+    }
+}
+
+// ---- chain A: geopotential of the own rows, then the filtered pressure-gradient force; then the wait for chain B's ev_a
+template <typename T>
+static void chain_a(Pe25d *m, const Stage<T> &g) {
+    const PeArgsT<T> a = rows_of(g.a, g.j0, g.j1);
+    PeArgsT<T> c = a;
+    c.cs_rows = 0;
+    c.geo_j0 = g.j0; c.geo_j1 = g.j1;
+    launch_geopot(m, c, g.s);
+    // (a looping form of this filter, as K1's, was built and is 25 % SLOWER: its requests and the
+    // per-column thermodynamics push it to 187 VGPRs, two waves per SIMD instead of four)
+    // (launched with whole waves -- 192 threads for the 144 butterflies of a 1440 row, so that the
+    // per-column thermodynamics ahead of the transform fills its lanes -- it takes the same time)
+    const bool join = m->aux && g.mode == 1 && async_edges(m);                     // the edge rows' K4 on B takes pgfu
+    launch(m, pgf_filter_kernel_for<T>(m->cplan), dim3((unsigned)(8 * ((a.j1 - a.j0 + 7) / 8) * ((m->L + 1) / 2))),
+           dim3(m->cplan.ok ? m->cplan.threads : kFftThreads), filter_lds_bytes<T>(m), g.s, Then{join ? m->ev_join : nullptr}, a);
+    if (m->aux) (void)hipStreamWaitEvent(g.s, m->ev_a, 0);                         // K4 on A takes spu, pit (and a band's ghost anchors)
+}
+
+// K4 over rows [r0, r1) and [rb0, rb1) of `a`, one launch; k4_done: ev_k4 where the launch is the caller's stream's last of the stage
+template <typename T>
+static void update_rows(const Pe25d *m, PeArgsT<T> a, int r0, int r1, int rb0, int rb1, hipStream_t st, hipEvent_t k4_done = nullptr) {
+    const int rows = std::max(0, r1 - r0) + std::max(0, rb1 - rb0);
+    if (rows <= 0) return;
+    a = rows_of(a, r0, std::max(r0, r1), rb0, std::max(rb0, rb1));
+    const int Rg = m->upd_rows, L = m->L;
+    const long groups = (std::max(0, r1 - r0) + Rg - 1) / Rg + (std::max(0, rb1 - rb0) + Rg - 1) / Rg;
+    // 8 XCDs x (row group, segment) pairs per XCD x column tiles (see the kernel's index map)
+    const long rs_per_xcd = (groups * a.nseg + 7) / 8;
+    const dim3 gg((unsigned)(8 * rs_per_xcd * ((m->W + kUpdCols - 1) / kUpdCols)));
+    const bool same = a.u == a.su;
+    // whole columns of an even number of levels start on an odd level: the geopotential anchor is requested with the
+    // even levels only (an odd level steps up from the anchor in the tile below and never reads its own): one request
+    // in eleven (seven) less every other level, C4 1.881 -> 1.857 ms per step (round 4, A/B on one box)
+    const bool oddtop = m->k4_oddtop && a.nseg == 1 && L % 2 == 0;
+    launch(m, update_rows_kernel_for<T>(Rg, same, oddtop), gg, dim3(64 * (Rg + 1)), upd_lds_bytes<T>(Rg, L), st, Then{k4_done, true}, a);
+}
+
+// mode 0 -- chain A: K4 of all rows
+template <typename T>
+static void update_whole(Pe25d *m, const Stage<T> &g) {
+    tick(m, g.s);
+    update_rows<T>(m, g.a, g.j0, g.j1, 0, 0, g.s, m->ev_k4);
+    m->k4_fork_valid = m->stop_events && !(m->ev && m->ev_used);       // (timing runs put records behind the kernel)
+    tick(m, g.s);
+}
+
+// mode 1 -- the rows the neighbours wait for (an unsplittable, tiny band: all of them).  With send
+// buffers registered they are updated and packed on the second stream (chain B), which waits
+// for K3 here; the caller's stream goes straight on to the interior rows (mode 2), so the
+// two launches share the chip.
+template <typename T>
+static void update_edges(Pe25d *m, const Stage<T> &g) {
+    const int j0 = g.j0, j1 = g.j1;
+    const bool as = async_edges(m);
+    hipStream_t se = g.se;
+    if (g.split_k1) (void)hipStreamWaitEvent(se, m->ev_a, 0);      // the edge rows' partial sums and K4 take spu of own rows
+    if (g.edge_segs) {
+        // a band's edge rows are marched in level segments (below): the partial sums of conv they start from,
+        // behind K1 on chain B and ahead of its wait for K3 (beside the interior rows' K4 this kernel took 50 us
+        // instead of 14)
+        PeArgsT<T> c = rows_of(g.a, j0, j0 + kGhost + 1, j1 - kGhost, j1 + 1);   // (K4 of row j also takes the sums of row j + 1)
+        c.nseg = m->nseg_edge;
+        hipLaunchKernelGGL(pe_part_kernel<T>, dim3((unsigned)((m->W + 255) / 256) * (2 * kGhost + 2)), dim3(256), 0, se, c);
+    }
+    if (m->ntr > 0) {
+        // the tracers' edge rows (the rows a neighbour takes, and the rows next to them), on the stream of the edge
+        // rows' K4, behind K1, pit and ev_a and ahead of the wait for K3: they fill chain B's wait.  Hazard 2: in
+        // the corrector they read the star tracers' ghost rows, which the post-predictor unpack filled ahead of K1
+        // on this stream (gcm_band_run), or on the caller's stream before this call (host-driven exchange).
+        if (g.split) launch_tracers<T>(m, g.a, g.stage_set, g.out_set, se, j0, j0 + kGhost, j1 - kGhost, j1);
+        else launch_tracers<T>(m, g.a, g.stage_set, g.out_set, se, j0, j1);
+    }
+    if (as && m->aux) (void)hipStreamWaitEvent(m->aux, m->ev_join, 0);      // the edge rows' K4 takes pgfu
+    if (as && m->aux && m->edges_first && g.split) {
+        (void)hipEventRecord(m->ev_pre_edge, se);          // chain B is about to launch the edge rows' K4
+        m->pre_edge_pending = true;
+    }
+    if (g.edge_segs) {
+        // the edge rows in level segments: a quarter of the chain of dependent levels, so the pack
+        // and the exchange start while the interior rows are still at work
+        // (the partial sums of conv they start from: pe_part_kernel, queued behind K1 above)
+        PeArgsT<T> c = g.a;
+        c.nseg = m->nseg_edge;
+        c.ocs_u = c.ocs_v = nullptr;
+        update_rows<T>(m, c, j0, j0 + kGhost, j1 - kGhost, j1, se);
+    } else if (g.split) {
+        update_rows<T>(m, g.a, j0, j0 + kGhost, j1 - kGhost, j1, se);
+    } else {
+        update_rows<T>(m, g.a, j0, j1, 0, 0, se);
+    }
+    if (!as) return;
+    // (hazard 3: the pack of the new state's edge rows follows the corrector's tracer edge launch above in
+    // stream order on `se`; a pack the caller queues -- gcm_halo_pack -- follows `aux` through halo_run)
+    SegCopy c{};
+    std::string err;
+    (void)pe25d_halo_segments(m, true, 0, m->send_buf[0], &c, &err);
+    (void)pe25d_halo_segments(m, true, 1, m->send_buf[1], &c, &err);
+    launch_seg_copy(c, se, m->stop_events ? m->ev_edges : nullptr);
+    if (!m->stop_events) (void)hipEventRecord(m->ev_edges, se);
+    m->edges_pending = true;
+    m->edges_ev_valid = true;
+    if (m->aux2 && g.edge_segs) {
+        // the edge rows were marched in level segments and left no column sums: formed here, on the third
+        // stream, as soon as the rows exist -- beside the interior rows still at work, off every chain of the
+        // next stage (which read them: pit of rows 0 .. 2 and H - 2 .. H)
+        (void)hipStreamWaitEvent(m->aux2, m->ev_edges, 0);
+        const PeArgsT<T> cc = rows_of(make_args<T>(m, g.out_set, g.out_set, g.dt), j0, j0 + kGhost, j1 - kGhost, j1);
+        launch(m, pe_colsum_kernel<T>, dim3((unsigned)((m->W + 255) / 256) * (2 * kGhost)), dim3(256), 0, m->aux2, Then{m->ev_cs}, cc);
+        m->edge_cs_set = g.out_set;
+    }
+}
+
+// mode 2 -- chain A: K4 of the interior rows
+template <typename T>
+static void update_interior(Pe25d *m, const Stage<T> &g) {
+    if (g.split) {
+        if (m->pre_edge_pending) (void)hipStreamWaitEvent(g.s, m->ev_pre_edge, 0);
+        m->pre_edge_pending = false;
+        update_rows<T>(m, g.a, g.j0 + kGhost, g.j1 - kGhost, 0, 0, g.s, m->ev_k4);
+        m->k4_fork_valid = m->stop_events;
+    }
+    // whatever follows on the caller's stream also follows the edge rows
+    if (async_edges(m) && m->edges_pending) (void)hipStreamWaitEvent(g.s, m->ev_edges, 0);
+    m->edges_pending = false;
+}
+
+// The stage, step by step (s = the caller's stream, aux / aux2 = the second / third stream; -> E: E follows the kernel):
+//   chain_b_head    aux   waits ev_k4 or ev_fork (s), ev_tr_int, ev_cs;  the ghost rows' column sums and anchors
+//   chain_b_k1_pit  aux   K1 + pit -> ev_a                  split K1: aux2 waits the fork, ev_edges, ev_tr_int; own rows' K1 -> ev_a;
+//                                                            aux keeps the ghost-dependent rows' K1
+//   stage_tracers   aux   mode 0, behind K1 -> ev_tr_int    mode 1: interior rows on aux2 (else s), waits ev_a -> ev_tr_int
+//   chain_a         s     K2a, K3 -> ev_join (mode 1 with send buffers); then s waits ev_a
+//   update_whole    s     K4 -> ev_k4
+//   update_edges    aux (s without send buffers)  waits ev_a (split K1);  partial sums, tracers' edge rows;  waits ev_join;
+//                         -> ev_pre_edge;  K4 of the edge rows;  pack -> ev_edges;  aux2 waits ev_edges: column sums -> ev_cs
+//   update_interior s     waits ev_pre_edge;  K4 -> ev_k4;  waits ev_edges
 template <typename T>
 static void half_t(Pe25d *m, int stage_set, int out_set, double dt, int j0, int j1, hipStream_t s, int mode, bool chained) {
     if (j1 <= j0) return;
-    PeArgsT<T> a = make_args<T>(m, stage_set, out_set, dt);
+    const Stage<T> g = stage_facts<T>(m, stage_set, out_set, dt, j0, j1, s, mode, chained);
     m->last_stage_set = stage_set;
-    const int W = m->W, L = m->L;
-    const int ext = m->wrap ? 0 : 1;             // intermediates are also needed on row j1 (south)
-    const size_t lds = filter_lds_bytes<T>(m);
-    const int fft_threads = m->cplan.ok ? m->cplan.threads : kFftThreads;
-    const int pairs = (L + 1) / 2;
-    // pit from the 2-D column sums (pe_pit2d_kernel) where K4 marches whole columns and can leave them
-    const bool p2 = m->pit2d && a.nseg == 1;
-    if (p2) {
-        a.ocs_u = bufs<T>(m).cs[out_set][0];
-        a.ocs_v = bufs<T>(m).cs[out_set][1];
-    }
-    // Two chains on two streams (a cross-queue dependency costs ~10 us on this chip when the waiting queue
-    // is already idle, ~3 us when the event completed earlier: tools/micro/sync_cost.hip):
-    //   A, the caller's stream:  K2a (own rows) -> K3 -> K4 (all rows, or the interior rows of a band)
-    //   B, the second stream:    column sums and anchors of the ghost rows -> K1 (+ pit) [-> a band's edge
-    //                            rows: their partial sums, K4, pack; the exchange and the unpack follow]
-    // A is the long chain and runs without waiting for anything that has not long finished: K4 waits for
-    // B's K1 (done while K3 runs), the next stage's K2a for B's edge rows (done while the interior rows
-    // run).  A never touches ghost rows, so it never waits for an exchange; B does, in stream order.
-    hipStream_t sb = m->aux ? m->aux : s;
-    // pe_geopot_kernel over the rows of `c` ([j0, j1) and [jb0, jb1)); c.geo_j0 / geo_j1: the rows it forms phi
-    // for, c.cs_rows: it also forms the column sums of all its rows
-    const auto geopot = [&](const PeArgsT<T> &c, hipStream_t st, hipEvent_t stop = nullptr) {
-        const int rows = (c.j1 - c.j0) + (c.jb1 - c.jb0);
-        if (rows <= 0) return;
-        const long tiles = (long)((W + kColThreads - 1) / kColThreads) * rows;
-        const dim3 gg((unsigned)((tiles + 7) / 8 * 8));
-        const size_t park = sizeof(T) * (size_t)L * kColThreads;
-        if (c.cs_rows) {
-            if (L <= 24) hipLaunchKernelGGL((pe_geopot_kernel<T, 24, true>), gg, dim3(kColThreads), 0, st, c);
-            else if (L <= 40) hipLaunchKernelGGL((pe_geopot_kernel<T, 40, true>), gg, dim3(kColThreads), 0, st, c);
-            else hipLaunchKernelGGL((pe_geopot_kernel<T, 0, true>), gg, dim3(kColThreads), park, st, c);
-        } else {
-            void (*kern)(PeArgsT<T>) = L <= 24 ? pe_geopot_kernel<T, 24> : L <= 40 ? pe_geopot_kernel<T, 40> : pe_geopot_kernel<T, 0>;
-            const unsigned dyn = L <= 40 ? 0u : (unsigned)park;
-            if (stop) hipExtLaunchKernelGGL(kern, gg, dim3(kColThreads), dyn, st, nullptr, stop, 0, c);
-            else hipLaunchKernelGGL(kern, gg, dim3(kColThreads), dyn, st, c);
-        }
-    };
-    const bool split = mode != 0 && (j1 - j0) > 2 * kGhost;
-    // (Round 4, built and rejected: the edge rows' K3 as a launch of its own on chain B right behind K2a, so that their
-    // K4, the pack and the exchange start before the interior rows' K4 takes the chip.  Four rows are 48 workgroups of
-    // five dependent LDS passes: 30-60 us on a chain that already holds K1's ghost-row launch and the partial sums, and
-    // the N = 8 band got 4 % slower with no exchange time and 10 % slower with 40 us of it
-    // (profiles/r04/ab_band_edge_k3_on_chain_b.txt: `base` = with it).)
-    bool split_k1 = false;
     if (mode != 2) {
-        a.j0 = j0;
-        a.j1 = j1 + ext;
-        // ---- chain B: everything that reads the whole stage state, ghost rows included
-        // what chain B follows on the caller's stream: the previous stage's K4 (its own completion, ev_k4, when
-        // nothing else that B reads or overwrites was queued since), else the stream's position now
-        hipEvent_t fork = m->ev_fork;
-        if (m->aux) {
-            if (m->stop_events && m->k4_fork_valid && chained) fork = m->ev_k4;
-            else (void)hipEventRecord(m->ev_fork, s);
-            (void)hipStreamWaitEvent(m->aux, fork, 0);
-        }
-        // hazard 1 of a band's tracers: this stage's K1 overwrites spu, pit and p_n -- and its K4 the state sets -- that
-        // the last stage's tracer launch on another stream may still read (ev_tr_int, see below): chain B waits for it
-        // here, and so does the caller's stream where it takes the edge rows (no send buffers: the tracers' edge rows
-        // read what that launch wrote); the third stream's K1 follows it in stream order, or waits for it further down
-        const bool tr_prev = m->tr_int_wait;
-        m->tr_int_wait = false;
-        if (tr_prev) {
-            if (sb != m->tr_int_stream) (void)hipStreamWaitEvent(sb, m->ev_tr_int, 0);
-            hipStream_t se0 = (mode == 1 && async_edges(m) && m->aux) ? m->aux : s;
-            if (mode == 1 && se0 != sb && se0 != m->tr_int_stream) (void)hipStreamWaitEvent(se0, m->ev_tr_int, 0);
-        }
-        const bool ghosts_queued = m->ghost_ready == stage_set && (!p2 || m->cs_valid[stage_set]);
-        if (ghosts_queued) m->ghost_ready = -1;                    // queued behind the unpack already
-        else prep_rows<T>(m, a, stage_set, p2, j1, ext, sb);
-        static const bool no_loop = getenv("GCM_PE_FILTER_NO_LOOP") != nullptr;        // diagnostic: one workgroup per pair
-        const FilterLoopKernel<T> k1 = (m->cfg.filter && W > 1 && !no_loop) ? spu_filter_loop_kernel_for<T>(m->cplan) : nullptr;
-        bool pit_done = false, ev_a_done = false;
-        // (the own edge rows' column sums of this state were queued on the third stream behind the edge rows' K4
-        // of the stage that produced it: everything on the second stream that reads them waits for that)
-        if (m->aux2 && m->edge_cs_set == stage_set) (void)hipStreamWaitEvent(sb, m->ev_cs, 0);
-        // A band inside gcm_band_run (the ghost rows' column sums and anchors are queued behind the unpack already):
-        // K1 is row-local -- spu of row j takes su and sp of row j only, pit of row j the column sums of rows j - 1, j
-        // and sp of rows j - 1 .. j + 1 -- so the band's OWN rows need nothing from the exchange.  They go to a third
-        // stream that waits for the previous stage's K4 only (spu of rows [0, H), pit of rows [2, H - 2]: what the
-        // interior rows' K4 reads), and the second stream keeps the launch for the rows that do need ghost data (spu of
-        // the south ghost row, pit of rows 0, 1, H - 1, H).  The interior rows' K4 then waits for the own-row launch
-        // alone, not for the exchange chain (round 3: 32 us per corrector stage of the N = 8 band of C4).
-        split_k1 = k1 && mode == 1 && m->aux2 && p2 && ghosts_queued && (j1 - j0) >= 2 * kGhost + 3 &&
-                              (m->nseg_edge == 1 || m->edge_cs_set == stage_set);
-        if (split_k1) {
-            const auto launch_k1 = [&](const PeArgsT<T> &c, int rows, hipStream_t st, hipEvent_t stop) {
-                const int groups = std::min(pairs, std::max(1, (3 * m->cus + rows - 1) / rows));
-                const int ppw = (pairs + groups - 1) / groups;
-                const int ny = (pairs + ppw - 1) / ppw;
-                if (stop && m->stop_events)
-                    hipExtLaunchKernelGGL(k1, dim3(rows, ny + 1), dim3(fft_threads), (unsigned)filter_loop_lds_bytes<T>(m), st, nullptr, stop, 0, c, ppw, ny);
-                else
-                    hipLaunchKernelGGL(k1, dim3(rows, ny + 1), dim3(fft_threads), filter_loop_lds_bytes<T>(m), st, c, ppw, ny);
-                if (stop && !m->stop_events) (void)hipEventRecord(stop, st);
-            };
-            (void)hipStreamWaitEvent(m->aux2, fork, 0);
-            // (the previous stage's edge rows: su, sp of rows 0, 1, H - 2, H - 1 -- and its tracers' edge rows, queued
-            // ahead of the pack: they read spu, pit and p_n of those rows, which this K1 overwrites)
-            if (m->edges_ev_valid) (void)hipStreamWaitEvent(m->aux2, m->ev_edges, 0);
-            if (tr_prev && m->tr_int_stream != m->aux2) (void)hipStreamWaitEvent(m->aux2, m->ev_tr_int, 0);
-            PeArgsT<T> c = a;
-            c.j0 = j0; c.j1 = j1; c.jb0 = c.jb1 = 0;
-            c.pit_j0 = j0 + kGhost; c.pit_j1 = j1 - kGhost + 1;
-            launch_k1(c, j1 - j0, m->aux2, m->ev_a);             // (ev_a: what K4 of the interior rows takes)
-            c = a;
-            c.j0 = j0; c.j1 = j0 + kGhost; c.jb0 = j1 - 1; c.jb1 = j1 + ext;
-            c.spu_j0 = j1; c.spu_j1 = j1 + ext;
-            launch_k1(c, kGhost + 1 + ext, sb, nullptr);
-            pit_done = true;                                     // (chain B waits for ev_a below, ahead of the edge rows' partial sums)
-        } else if (k1) {
-            // all pairs of a row in one workgroup when there are rows enough to fill the chip, else groups;
-            // with the 2-D form of pit one more workgroup per row forms pit and p_n (pe_pit2d_row)
-            const int rows = a.j1 - a.j0;
-            const int groups = std::min(pairs, std::max(1, (3 * m->cus + rows - 1) / rows));
-            const int ppw = (pairs + groups - 1) / groups;
-            const int ny = (pairs + ppw - 1) / ppw;
-            if (p2 && m->aux && m->stop_events) {
-                hipExtLaunchKernelGGL(k1, dim3(rows, ny + 1), dim3(fft_threads), (unsigned)filter_loop_lds_bytes<T>(m), sb, nullptr, m->ev_a, 0, a, ppw, ny);
-                ev_a_done = true;
-            } else {
-                hipLaunchKernelGGL(k1, dim3(rows, ny + (p2 ? 1 : 0)), dim3(fft_threads), filter_loop_lds_bytes<T>(m), sb, a, ppw, p2 ? ny : -1);
-            }
-            pit_done = p2;
-        } else {
-            hipLaunchKernelGGL(spu_filter_kernel_for<T>(m->cplan), dim3(a.j1 - a.j0, pairs), dim3(fft_threads), lds, sb, a);
-        }
-        if (p2 && !pit_done) {
-            hipLaunchKernelGGL(pit2d_kernel_for<T>(m->cplan), dim3(a.j1 - a.j0), dim3(fft_threads), pit2d_lds_bytes<T>(m), sb, a);
-        } else if (!p2) {
-            const long tiles = (long)((W + 255) / 256) * (a.j1 - a.j0);
-            hipLaunchKernelGGL(pe_pit_kernel<T>, dim3((unsigned)((tiles + 7) / 8 * 8)), dim3(256), 0, sb, a);
-        }
-        if (m->aux && !split_k1 && !ev_a_done) (void)hipEventRecord(m->ev_a, m->aux);      // (what K4 of the interior rows takes from this chain)
-        // ---- the passive tracers (single domain): on chain B right behind K1 + pit and after ev_a, so that K4 on
-        //      chain A never waits for them and they run beside K2a, K3 and K4.  Two invariants hold them in place:
-        //      * the next stage's K1 must not overwrite spu, pit or p_n while this launch still reads them: it is
-        //        queued on this same stream behind it.  (Not on `s` behind K4: chain B forks at ev_k4 when
-        //        k4_fork_valid is set, and the next K1 would then race the tracer kernel.)  The state sets it reads
-        //        (sp, sv, p) are overwritten only by a later K4, which waits for a later ev_a: behind this launch too;
-        //      * everything that returns to the caller joins chain B's tail: gcm_step (and so gcm_time_steps'
-        //        stop event), gcm_half_step, gcm_get_tracers, gcm_set_tracers and gcm_sync make `s` wait for ev_tr,
-        //        recorded on `aux` behind the last tracer launch (pe25d_join_tracers).
-        //      Without tracers nothing is launched, recorded or waited for here.
-        //      A band: the whole stage (mode 0) takes the same launch over its own rows, and the next stage's chain B
-        //      waits for it on the streams where it does not follow in stream order (ev_tr_int, hazard 1 above).
-        if (m->ntr > 0 && mode == 0) {
-            launch_tracers<T>(m, a, stage_set, out_set, sb, j0, j1);
-            if (!m->wrap && m->aux) {
-                (void)hipEventRecord(m->ev_tr_int, sb);
-                m->tr_int_stream = sb;
-                m->tr_int_wait = true;
-            }
-        }
-        // ---- a band's split stage (modes 1 + 2): the tracers' edge rows go ahead of the pack (see mode 1 below), the
-        //      interior rows [j0 + 2, j1 - 2) here, on the third stream right behind the own rows' K1 (ev_a): off the
-        //      exchange chain, which never waits for them within the stage, and beside K2a and K3 on the caller's
-        //      stream, whose LDS-bound passes leave memory bandwidth free.  ev_tr_int follows them: the next stage's
-        //      chain B waits for it (hazard 1), the caller's stream joins it (pe25d_join_tracers).  Without a third
-        //      stream they go to the caller's stream, where the next stage's chain B follows them through the fork.
-        if (m->ntr > 0 && mode == 1 && split) {
-            hipStream_t ti = m->aux2 ? m->aux2 : s;
-            if (m->aux && !(split_k1 && ti == m->aux2)) (void)hipStreamWaitEvent(ti, m->ev_a, 0);   // (K1 + pit of all rows)
-            launch_tracers<T>(m, a, stage_set, out_set, ti, j0 + kGhost, j1 - kGhost);
-            if (ti != s) {
-                (void)hipEventRecord(m->ev_tr_int, ti);
-                m->tr_int_stream = ti;
-                m->tr_int_wait = m->tr_int_join = true;
-            }
-        }
-        // ---- chain A: geopotential of the own rows, then the filtered pressure-gradient force
-        a.j0 = j0;
-        a.j1 = j1;
-        {
-            PeArgsT<T> c = a;
-            c.jb0 = c.jb1 = 0;
-            c.cs_rows = 0;
-            c.geo_j0 = j0; c.geo_j1 = j1;
-            geopot(c, s);
-        }
-        // (a looping form of this filter, as K1's, was built and is 25 % SLOWER: its requests and the
-        // per-column thermodynamics push it to 187 VGPRs, two waves per SIMD instead of four)
-        // (launched with whole waves -- 192 threads for the 144 butterflies of a 1440 row, so that the
-        // per-column thermodynamics ahead of the transform fills its lanes -- it takes the same time)
-        const bool join = m->aux && mode == 1 && async_edges(m);                     // the edge rows' K4 on B takes pgfu
-        if (join && m->stop_events)
-            hipExtLaunchKernelGGL(pgf_filter_kernel_for<T>(m->cplan), dim3((unsigned)(8 * ((a.j1 - a.j0 + 7) / 8) * pairs)), dim3(fft_threads),
-                                  (unsigned)lds, s, nullptr, m->ev_join, 0, a);
-        else
-            hipLaunchKernelGGL(pgf_filter_kernel_for<T>(m->cplan), dim3((unsigned)(8 * ((a.j1 - a.j0 + 7) / 8) * pairs)), dim3(fft_threads), lds, s, a);
-        if (m->aux) {
-            if (join && !m->stop_events) (void)hipEventRecord(m->ev_join, s);
-            (void)hipStreamWaitEvent(s, m->ev_a, 0);                                   // K4 on A takes spu, pit (and a band's ghost anchors)
-        }
+        chain_b_head(m, g);
+        chain_b_k1_pit(m, g);
+        stage_tracers(m, g);
+        chain_a(m, g);
     }
-    auto update_rows = [&](int r0, int r1, int rb0, int rb1, hipStream_t st, hipEvent_t stop = nullptr) {   // rows [r0, r1) and [rb0, rb1), one launch
-        const int rows = std::max(0, r1 - r0) + std::max(0, rb1 - rb0);
-        if (rows <= 0) return;
-        a.j0 = r0;
-        a.j1 = std::max(r0, r1);
-        a.jb0 = rb0;
-        a.jb1 = std::max(rb0, rb1);
-        const int Rg = m->upd_rows;
-        const long groups = (std::max(0, r1 - r0) + Rg - 1) / Rg + (std::max(0, rb1 - rb0) + Rg - 1) / Rg;
-        // 8 XCDs x (row group, segment) pairs per XCD x column tiles (see the kernel's index map)
-        const long rs_per_xcd = (groups * a.nseg + 7) / 8;
-        const dim3 gg((unsigned)(8 * rs_per_xcd * ((W + kUpdCols - 1) / kUpdCols)));
-        const size_t lds = upd_lds_bytes<T>(Rg, L);
-        const bool same = a.u == a.su;
-        // whole columns of an even number of levels start on an odd level: the geopotential anchor is requested with the
-        // even levels only (an odd level steps up from the anchor in the tile below and never reads its own): one request
-        // in eleven (seven) less every other level, C4 1.881 -> 1.857 ms per step (round 4, A/B on one box)
-        static const bool oddtop_env = !(getenv("GCM_PE_K4_ODDTOP") && getenv("GCM_PE_K4_ODDTOP")[0] == '0');
-        const bool oddtop = oddtop_env && a.nseg == 1 && L % 2 == 0;
-        if (stop && m->stop_events) hipExtLaunchKernelGGL(update_rows_kernel_for<T>(Rg, same, oddtop), gg, dim3(64 * (Rg + 1)), (unsigned)lds, st, nullptr, stop, 0, a);
-        else hipLaunchKernelGGL(update_rows_kernel_for<T>(Rg, same, oddtop), gg, dim3(64 * (Rg + 1)), lds, st, a);
-    };
-    m->cs_valid[out_set] = p2;                   // (modes 1 + 2 together cover the rows)
-    if (mode == 0) {
-        tick(m, s);
-        update_rows(j0, j1, 0, 0, s, m->ev_k4);
-        m->k4_fork_valid = m->stop_events && !(m->ev && m->ev_used);       // (timing runs put records behind the kernel)
-        tick(m, s);
-    } else if (mode == 1) {
-        // the rows the neighbours wait for (an unsplittable, tiny band: all of them).  With send
-        // buffers registered they are updated and packed on the second stream (chain B), which waits
-        // for K3 here; the caller's stream goes straight on to the interior rows (mode 2), so the
-        // two launches share the chip.
-        const bool as = async_edges(m);
-        hipStream_t se = as && m->aux ? m->aux : s;
-        if (split_k1) (void)hipStreamWaitEvent(se, m->ev_a, 0);      // the edge rows' partial sums and K4 take spu of own rows
-        if (split && p2 && m->nseg_edge > 1) {
-            // a band's edge rows are marched in level segments (below): the partial sums of conv they start from,
-            // behind K1 on chain B and ahead of its wait for K3 (beside the interior rows' K4 this kernel took 50 us
-            // instead of 14)
-            PeArgsT<T> c = a;
-            c.nseg = m->nseg_edge;
-            c.j0 = j0; c.j1 = j0 + kGhost + 1;            // (K4 of row j also takes the sums of row j + 1)
-            c.jb0 = j1 - kGhost; c.jb1 = j1 + 1;
-            hipLaunchKernelGGL(pe_part_kernel<T>, dim3((unsigned)((W + 255) / 256) * (2 * kGhost + 2)), dim3(256), 0, se, c);
-        }
-        if (m->ntr > 0) {
-            // the tracers' edge rows (the rows a neighbour takes, and the rows next to them), on the stream of the edge
-            // rows' K4, behind K1, pit and ev_a and ahead of the wait for K3: they fill chain B's wait.  Hazard 2: in
-            // the corrector they read the star tracers' ghost rows, which the post-predictor unpack filled ahead of K1
-            // on this stream (gcm_band_run), or on the caller's stream before this call (host-driven exchange).
-            if (split) launch_tracers<T>(m, a, stage_set, out_set, se, j0, j0 + kGhost, j1 - kGhost, j1);
-            else launch_tracers<T>(m, a, stage_set, out_set, se, j0, j1);
-        }
-        if (as && m->aux) (void)hipStreamWaitEvent(m->aux, m->ev_join, 0);      // the edge rows' K4 takes pgfu
-        if (as && m->aux && m->edges_first && split) {
-            (void)hipEventRecord(m->ev_pre_edge, se);          // chain B is about to launch the edge rows' K4
-            m->pre_edge_pending = true;
-        }
-        if (split && p2 && m->nseg_edge > 1) {
-            // the edge rows in level segments: a quarter of the chain of dependent levels, so the pack
-            // and the exchange start while the interior rows are still at work
-            PeArgsT<T> keep = a;
-            a.nseg = m->nseg_edge;
-            a.ocs_u = a.ocs_v = nullptr;
-            // (the partial sums of conv they start from: pe_part_kernel, queued behind K1 above)
-            update_rows(j0, j0 + kGhost, j1 - kGhost, j1, se);
-            a = keep;
-        } else if (split) {
-            update_rows(j0, j0 + kGhost, j1 - kGhost, j1, se);
-        } else {
-            update_rows(j0, j1, 0, 0, se);
-        }
-        if (as) {
-            // (hazard 3: the pack of the new state's edge rows follows the corrector's tracer edge launch above in
-            // stream order on `se`; a pack the caller queues -- gcm_halo_pack -- follows `aux` through halo_run)
-            SegCopy c{};
-            std::string err;
-            (void)pe25d_halo_segments(m, true, 0, m->send_buf[0], &c, &err);
-            (void)pe25d_halo_segments(m, true, 1, m->send_buf[1], &c, &err);
-            if (m->stop_events) launch_seg_copy(c, se, m->ev_edges);
-            else {
-                launch_seg_copy(c, se);
-                (void)hipEventRecord(m->ev_edges, se);
-            }
-            m->edges_pending = true;
-            m->edges_ev_valid = true;
-            if (m->aux2 && split && p2 && m->nseg_edge > 1) {
-                // the edge rows were marched in level segments and left no column sums: formed here, on the third
-                // stream, as soon as the rows exist -- beside the interior rows still at work, off every chain of the
-                // next stage (which read them: pit of rows 0 .. 2 and H - 2 .. H)
-                (void)hipStreamWaitEvent(m->aux2, m->ev_edges, 0);
-                PeArgsT<T> cc = make_args<T>(m, out_set, out_set, dt);
-                cc.j0 = j0; cc.j1 = j0 + kGhost; cc.jb0 = j1 - kGhost; cc.jb1 = j1;
-                if (m->stop_events)
-                    hipExtLaunchKernelGGL(pe_colsum_kernel<T>, dim3((unsigned)((W + 255) / 256) * (2 * kGhost)), dim3(256), 0, m->aux2, nullptr, m->ev_cs, 0, cc);
-                else {
-                    hipLaunchKernelGGL(pe_colsum_kernel<T>, dim3((unsigned)((W + 255) / 256) * (2 * kGhost)), dim3(256), 0, m->aux2, cc);
-                    (void)hipEventRecord(m->ev_cs, m->aux2);
-                }
-                m->edge_cs_set = out_set;
-            }
-        }
-    } else {
-        if (split) {
-            if (m->pre_edge_pending) (void)hipStreamWaitEvent(s, m->ev_pre_edge, 0);
-            m->pre_edge_pending = false;
-            update_rows(j0 + kGhost, j1 - kGhost, 0, 0, s, m->ev_k4);
-            m->k4_fork_valid = m->stop_events;
-        }
-        // whatever follows on the caller's stream also follows the edge rows
-        if (async_edges(m) && m->edges_pending) (void)hipStreamWaitEvent(s, m->ev_edges, 0);
-        m->edges_pending = false;
-    }
+    m->cs_valid[out_set] = g.p2;                 // (modes 1 + 2 together cover the rows)
+    if (mode == 0) update_whole(m, g);
+    else if (mode == 1) update_edges(m, g);
+    else update_interior(m, g);
 }
 
 static void half(Pe25d *m, int stage_set, int out_set, double dt, int j0, int j1, hipStream_t s, int mode = 0, bool chained = false) {
@@ -1488,15 +1509,8 @@ int pe25d_prep_ghost_rows(Pe25d *m, std::string *err) {
     }
     const bool p2 = m->pit2d && m->nseg == 1;
     if (p2 && !m->cs_valid[set]) return GCM_OK;                  // (a fresh state: the stage does all rows itself)
-    if (m->f32) {
-        PeArgsT<float> a = make_args<float>(m, set, set, 0.0);
-        a.j0 = 0; a.j1 = m->H + 1;
-        prep_rows<float>(m, a, set, p2, m->H, 1, m->aux);
-    } else {
-        PeArgsT<double> a = make_args<double>(m, set, set, 0.0);
-        a.j0 = 0; a.j1 = m->H + 1;
-        prep_rows<double>(m, a, set, p2, m->H, 1, m->aux);
-    }
+    if (m->f32) prep_rows<float>(m, make_args<float>(m, set, set, 0.0), set, p2, m->H, 1, m->aux);      // (it picks its rows itself)
+    else prep_rows<double>(m, make_args<double>(m, set, set, 0.0), set, p2, m->H, 1, m->aux);
     m->ghost_ready = set;
     return GCM_OK;
 }
@@ -1631,29 +1645,37 @@ int pe25d_get_tracers(Pe25d *m, int which, double *c, hipStream_t s, std::string
     return GCM_OK;
 }
 
+// The two stages of a Matsuno step by their state sets: the predictor (stage 0) takes the current set to set 2 (star),
+// the corrector (stage 1) set 2 to the other of sets 0 / 1, which finish_stage makes the current one.
+struct StageSets { int stage_set, out_set; };
+static StageSets stage_sets(const Pe25d *m, int stage) { return stage == 0 ? StageSets{m->cur_i, 2} : StageSets{2, 1 - m->cur_i}; }
+// phased: gcm_step_phase published the set gcm_halo_pack reads (pack_set) for the stage's duration
+static void finish_stage(Pe25d *m, int stage, bool phased = false) {
+    m->star_valid = stage == 0;
+    if (stage == 0) return;
+    m->cur_i = 1 - m->cur_i;
+    if (phased) m->pack_set = -1;
+}
+static int launch_status(std::string *err) {
+    if (hipGetLastError() == hipSuccess) return GCM_OK;
+    *err = "hip: pe25d kernel launch failed";
+    return GCM_ERR_HIP;
+}
+
 int pe25d_half(Pe25d *m, int stage, double dt, hipStream_t s, std::string *err) {
     if (!m->wrap) {
         *err = "half_step on a latitude band: use step_part";
         return GCM_ERR_UNSUPPORTED;
     }
-    if (stage == 0) {
-        half(m, m->cur_i, 2, dt, 0, m->H, s);
-        m->star_valid = true;
-    } else {
-        if (!m->star_valid) {
-            *err = "half_step(1) before half_step(0)";
-            return GCM_ERR_STATE;
-        }
-        half(m, 2, 1 - m->cur_i, dt, 0, m->H, s);
-        m->cur_i = 1 - m->cur_i;
-        m->star_valid = false;
+    if (stage != 0 && !m->star_valid) {
+        *err = "half_step(1) before half_step(0)";
+        return GCM_ERR_STATE;
     }
+    const StageSets z = stage_sets(m, stage != 0);
+    half(m, z.stage_set, z.out_set, dt, 0, m->H, s);
+    finish_stage(m, stage != 0);
     pe25d_join_tracers(m, s);
-    if (hipGetLastError() != hipSuccess) {
-        *err = "hip: pe25d kernel launch failed";
-        return GCM_ERR_HIP;
-    }
-    return GCM_OK;
+    return launch_status(err);
 }
 
 int pe25d_step(Pe25d *m, double dt, hipStream_t s, std::string *err) {
@@ -1661,15 +1683,12 @@ int pe25d_step(Pe25d *m, double dt, hipStream_t s, std::string *err) {
         *err = "gcm_step: a latitude band needs ghost-row exchanges inside the step (use step_part)";
         return GCM_ERR_STATE;
     }
-    half(m, m->cur_i, 2, dt, 0, m->H, s);
-    half(m, 2, 1 - m->cur_i, dt, 0, m->H, s);
-    m->cur_i = 1 - m->cur_i;
-    m->star_valid = false;
-    if (hipGetLastError() != hipSuccess) {
-        *err = "hip: pe25d kernel launch failed";
-        return GCM_ERR_HIP;
+    for (int stage = 0; stage < 2; ++stage) {
+        const StageSets z = stage_sets(m, stage);
+        half(m, z.stage_set, z.out_set, dt, 0, m->H, s);
+        finish_stage(m, stage);
     }
-    return GCM_OK;
+    return launch_status(err);
 }
 
 // Latitude band: part 0 = predictor (needs ghost rows of the current state),
@@ -1679,19 +1698,10 @@ int pe25d_step_part(Pe25d *m, int part, double dt, hipStream_t s, std::string *e
         *err = "step_part: handle is not a latitude band";
         return GCM_ERR_STATE;
     }
-    if (part == 0) {
-        half(m, m->cur_i, 2, dt, 0, m->H, s);
-        m->star_valid = true;
-    } else {
-        half(m, 2, 1 - m->cur_i, dt, 0, m->H, s);
-        m->cur_i = 1 - m->cur_i;
-        m->star_valid = false;
-    }
-    if (hipGetLastError() != hipSuccess) {
-        *err = "hip: pe25d kernel launch failed";
-        return GCM_ERR_HIP;
-    }
-    return GCM_OK;
+    const StageSets z = stage_sets(m, part != 0);
+    half(m, z.stage_set, z.out_set, dt, 0, m->H, s);
+    finish_stage(m, part != 0);
+    return launch_status(err);
 }
 
 // Latitude band with the exchange hidden behind the interior rows of K4 (gcm_step_phase):
@@ -1706,34 +1716,20 @@ int pe25d_step_phase(Pe25d *m, int phase, double dt, hipStream_t s, std::string 
         *err = "step_phase: handle is not a latitude band";
         return GCM_ERR_STATE;
     }
-    switch (phase) {
-        case 0:
-            m->star_valid = true;
-            m->pack_set = 2;
-            half(m, m->cur_i, 2, dt, 0, m->H, s, 1, chained);
-            break;
-        case 1:
-            half(m, m->cur_i, 2, dt, 0, m->H, s, 2, chained);
-            break;
-        case 2:
-            m->pack_set = 1 - m->cur_i;
-            half(m, 2, 1 - m->cur_i, dt, 0, m->H, s, 1, chained);
-            break;
-        case 3:
-            half(m, 2, 1 - m->cur_i, dt, 0, m->H, s, 2, chained);
-            m->cur_i = 1 - m->cur_i;
-            m->star_valid = false;
-            m->pack_set = -1;
-            break;
-        default:
-            *err = "step_phase: phase must be 0..3";
-            return GCM_ERR_ARG;
+    if (phase < 0 || phase > 3) {
+        *err = "step_phase: phase must be 0..3";
+        return GCM_ERR_ARG;
     }
-    if (hipGetLastError() != hipSuccess) {
-        *err = "hip: pe25d kernel launch failed";
-        return GCM_ERR_HIP;
+    const int stage = phase / 2;
+    const bool edges = phase % 2 == 0;
+    const StageSets z = stage_sets(m, stage);
+    if (edges) {                                 // the pack at the end of the edge rows reads the set this stage writes
+        m->pack_set = z.out_set;
+        if (stage == 0) m->star_valid = true;
     }
-    return GCM_OK;
+    half(m, z.stage_set, z.out_set, dt, 0, m->H, s, edges ? 1 : 2, chained);
+    if (!edges) finish_stage(m, stage, true);
+    return launch_status(err);
 }
 
 int pe25d_set_halo_buffers(Pe25d *m, void *north, void *south, hipStream_t s, std::string *err) {
@@ -1999,7 +1995,7 @@ static int radiation_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1,
     {
         const dim3 gg((W + kRadThreads - 1) / kRadThreads, nrows);
         T *th = B.st[set][GCM_T];
-        static const bool generic = getenv("GCM_PE_RAD_GENERIC") != nullptr;     // diagnostic: the LDS-parked form
+        const bool generic = m->rad_generic;
         const bool fact = m->cfg.ptop == 0.0 && r.sigk != nullptr;
         if (L <= 24 && !generic && fact) hipLaunchKernelGGL((pe_radiation_kernel<T, 24, true>), gg, dim3(kRadThreads), 0, s, a, r, th);
         else if (L <= 40 && !generic && fact) hipLaunchKernelGGL((pe_radiation_kernel<T, 40, true>), gg, dim3(kRadThreads), 0, s, a, r, th);

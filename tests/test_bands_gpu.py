@@ -646,6 +646,8 @@ def test_band_run_chains_at_overlapping_size(dtype, phys, monkeypatch):
     (the band is its own neighbour = the periodic single domain).  Four orchestrations -- the chains of the product, one
     stream only (GCM_PE_SINGLE_STREAM=1), the exchange on the comm stream with a join per stage
     (GCM_BAND_COMM_STREAM=1), the edge rows' update dispatched ahead of the interior rows' (GCM_BAND_OVERLAP=1) --
+    and the two fallback paths of the stage -- events recorded behind the kernels instead of signalled by them
+    (GCM_PE_STOP_EVENTS=0), K1 of all rows in one launch behind the exchange (GCM_PE_K1_SPLIT=0) --
     must all give the single domain's bits; a solar_timestep and a gcm_set_state between
     runs exercise the reset of the queued ghost-row work (ghost_ready)."""
     import torch
@@ -678,8 +680,9 @@ def test_band_run_chains_at_overlapping_size(dtype, phys, monkeypatch):
     want = drive(ref, lambda n: ref.step(n, dt))
     ref.close()
     # (GCM_BAND_OVERLAP=1 = gcm_set_band_overlap(1): the interior rows' update held back until the edge rows' is dispatched)
-    for env in ({}, {"GCM_PE_SINGLE_STREAM": "1"}, {"GCM_BAND_COMM_STREAM": "1"}, {"GCM_BAND_OVERLAP": "1"}):
-        for k in ("GCM_PE_SINGLE_STREAM", "GCM_BAND_COMM_STREAM", "GCM_BAND_OVERLAP"):
+    for env in ({}, {"GCM_PE_SINGLE_STREAM": "1"}, {"GCM_BAND_COMM_STREAM": "1"}, {"GCM_BAND_OVERLAP": "1"},
+                {"GCM_PE_STOP_EVENTS": "0"}, {"GCM_PE_K1_SPLIT": "0"}):
+        for k in ("GCM_PE_SINGLE_STREAM", "GCM_BAND_COMM_STREAM", "GCM_BAND_OVERLAP", "GCM_PE_STOP_EVENTS", "GCM_PE_K1_SPLIT"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)

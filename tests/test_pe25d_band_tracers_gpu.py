@@ -195,7 +195,9 @@ def test_band_run_tracers_at_overlapping_size(dtype, monkeypatch):
     """the 48 x 1440 x 24 band of test_band_run_chains_at_overlapping_size (kernels of tens of microseconds on every
     stream: a missing dependency between the tracer launches and the stage's chains shows here) with 4 tracers, in
     the four orchestrations: the product's chains, one stream (GCM_PE_SINGLE_STREAM=1), the exchange on the comm
-    stream with a join per stage (GCM_BAND_COMM_STREAM=1), the edge rows dispatched first (GCM_BAND_OVERLAP=1)"""
+    stream with a join per stage (GCM_BAND_COMM_STREAM=1), the edge rows dispatched first (GCM_BAND_OVERLAP=1);
+    and the stage's two fallback paths: events recorded behind the kernels (GCM_PE_STOP_EVENTS=0), K1 of all rows in
+    one launch (GCM_PE_K1_SPLIT=0)"""
     import torch
     import gcmiipy_amd as g
     from gcmiipy_amd import geometry
@@ -209,8 +211,9 @@ def test_band_run_tracers_at_overlapping_size(dtype, monkeypatch):
     ref.step(5, dt)
     want, want_tr = ref.get_state(), ref.get_tracers()
     ref.close()
-    for env in ({}, {"GCM_PE_SINGLE_STREAM": "1"}, {"GCM_BAND_COMM_STREAM": "1"}, {"GCM_BAND_OVERLAP": "1"}):
-        for k in ("GCM_PE_SINGLE_STREAM", "GCM_BAND_COMM_STREAM", "GCM_BAND_OVERLAP"):
+    for env in ({}, {"GCM_PE_SINGLE_STREAM": "1"}, {"GCM_BAND_COMM_STREAM": "1"}, {"GCM_BAND_OVERLAP": "1"},
+                {"GCM_PE_STOP_EVENTS": "0"}, {"GCM_PE_K1_SPLIT": "0"}):
+        for k in ("GCM_PE_SINGLE_STREAM", "GCM_BAND_COMM_STREAM", "GCM_BAND_OVERLAP", "GCM_PE_STOP_EVENTS", "GCM_PE_K1_SPLIT"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
