@@ -49,6 +49,25 @@ def tracer_array(c, L, H, W):
 
 
 DTYPES = {"f64": _lib.F64, "f32": _lib.F32}
+# the transport scheme of a GCM_PE25D handle's passive tracers (gcm_set_tracer_scheme)
+TRACER_SCHEMES = {"centred": _lib.TRACER_NONE, "upwind": _lib.TRACER_UPWIND, "van_leer": _lib.TRACER_VANLEER}
+
+
+def tracer_scheme_id(scheme):
+    """a tracer scheme as the C ABI takes it: one of the _lib.TRACER_* constants or "centred", "upwind", "van_leer"
+    (None: centred); ValueError otherwise, before any device use"""
+    if scheme is None:
+        return _lib.TRACER_NONE
+    if isinstance(scheme, str):
+        if scheme in TRACER_SCHEMES:
+            return TRACER_SCHEMES[scheme]
+    elif not isinstance(scheme, bool):
+        try:
+            if int(scheme) == scheme and int(scheme) in TRACER_SCHEMES.values():
+                return int(scheme)
+        except (TypeError, ValueError):
+            pass
+    raise ValueError("tracer_scheme must be 'centred', 'upwind', 'van_leer' or a TRACER_* constant, got %r" % (scheme,))
 
 
 def check_dtype(dtype):
@@ -73,10 +92,14 @@ class Core:
     def __init__(self, model, width, height, layers=1, dx=0.0, tracer=_lib.TRACER_NONE,
                  variant=_lib.VARIANT_AUTO, geom=None, filter=True, nranks=1, rank=0,
                  global_height=None, row0=0, device=-1, stream=None, halo_steps=1, coriolis=False, dtype="f64",
-                 members=1, band_tracers=0):
+                 members=1, band_tracers=0, tracer_scheme=None):
         """band_tracers: a GCM_PE25D latitude band (nranks > 1) that carries that many passive tracers
-        (gcm_set_band_tracers, right after gcm_create: the ghost-row message and halo_bytes() include them)"""
+        (gcm_set_band_tracers, right after gcm_create: the ghost-row message and halo_bytes() include them);
+        tracer_scheme: the passive tracers' transport scheme (set_tracer_scheme), GCM_PE25D only"""
         check_dtype(dtype)
+        scheme = tracer_scheme_id(tracer_scheme)
+        if scheme != _lib.TRACER_NONE and model != _lib.PE25D:
+            raise ValueError("tracer_scheme needs GCM_PE25D (the 2-D models take tracer=)")
         band_tracers = int(band_tracers)
         if not 0 <= band_tracers <= _lib.MAX_TRACERS:
             raise ValueError("band_tracers=%d: 0 .. %d" % (band_tracers, _lib.MAX_TRACERS))
@@ -91,6 +114,7 @@ class Core:
         self.options = dict(dx=float(dx), tracer=int(tracer), variant=int(variant), filter=bool(filter),
                             nranks=int(nranks), rank=int(rank), row0=int(row0), halo_steps=int(halo_steps),
                             coriolis=bool(coriolis), dtype=dtype, members=int(members), band_tracers=band_tracers,
+                            tracer_scheme=_lib.TRACER_NONE,
                             global_height=int(height if global_height is None else global_height))
         self.has_ground = False
         cfg = _lib.Config()
@@ -139,8 +163,14 @@ class Core:
             if rc == _lib.ERR_ARG:
                 raise ValueError(msg)
             raise GcmError("gcm_create failed (%d): %s" % (rc, msg))
-        if band_tracers > 0:
-            _check(lib.gcm_set_band_tracers(self._h, band_tracers), self._h)
+        try:
+            if band_tracers > 0:
+                _check(lib.gcm_set_band_tracers(self._h, band_tracers), self._h)
+            if scheme != _lib.TRACER_NONE:
+                self.set_tracer_scheme(scheme)
+        except Exception:
+            self.close()
+            raise
         self.is3d = model == _lib.PE25D
         self.fields = {_lib.SW2D: (_lib.P, _lib.U, _lib.V),
                        _lib.SW2D_TEMP: (_lib.P, _lib.U, _lib.V, _lib.T) +
@@ -213,6 +243,22 @@ class Core:
         out = np.empty((self.tracer_count, self.L, self.H, self.W))
         _check(lib.gcm_get_tracers(self._h, 1 if star else 0, _ptr(out) if out.size else None), self._h)
         return out
+
+    def set_tracer_scheme(self, scheme):
+        """the transport scheme of the passive tracers from the next stage on: "centred" (the update of q, the
+        default), "upwind" (donor-cell face values) or "van_leer" (donor-cell + the van Leer limited correction;
+        single domains only), or the _lib.TRACER_* constants (gcm_set_tracer_scheme).  q is not affected"""
+        scheme = tracer_scheme_id(scheme)
+        _check(lib.gcm_set_tracer_scheme(self._h, scheme), self._h)
+        self.options["tracer_scheme"] = scheme
+
+    @property
+    def tracer_scheme(self):
+        """the scheme in force, as a _lib.TRACER_* constant"""
+        s = lib.gcm_tracer_scheme(self._h)
+        if s < 0:
+            _check(s, self._h)
+        return s
 
     @property
     def tracer_count(self):

@@ -645,6 +645,20 @@ int gcm_tracer_count(const gcm_handle *h) {
     return h->pe ? pe25d_tracer_count(h->pe) : 0;
 }
 
+int gcm_set_tracer_scheme(gcm_handle *h, int scheme) {
+    if (!h) return GCM_ERR_ARG;
+    if (scheme < GCM_TRACER_NONE || scheme > GCM_TRACER_VANLEER)
+        return fail(h, GCM_ERR_ARG, "gcm_set_tracer_scheme: scheme must be GCM_TRACER_NONE, _UPWIND or _VANLEER");
+    if (int rc = tracer_refusal(h, "gcm_set_tracer_scheme")) return rc;
+    if (h->cfg.device >= 0) HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pe25d_set_tracer_scheme(h->pe, scheme, h->stream, &h->err);
+}
+
+int gcm_tracer_scheme(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_tracer_scheme(h->pe) : GCM_TRACER_NONE;
+}
+
 int gcm_step_interior(gcm_handle *h, double dt, void *stream) {
     if (!h) return GCM_ERR_ARG;
     if (h->pe) return pe25d_step_part(h->pe, 0, dt, (hipStream_t)stream, &h->err);

@@ -179,6 +179,8 @@ template <typename T> inline FilterKernel<T> update_rows_kernel_for(int rows_per
 }  // pe25d_k4.h (R = 3 or 7)
 template <typename T> using TracerKernel = void (*)(TracerArgsT<T>);
 template <typename T> TracerKernel<T> tracer_kernel_for(int nc, bool same);   // pe25d_tracer.h (nc = 4, 2 or 1)
+// scheme = GCM_TRACER_UPWIND / GCM_TRACER_VANLEER (gcm_set_tracer_scheme)
+template <typename T> TracerKernel<T> tracer_lim_kernel_for(int scheme, int nc, bool same);   // pe25d_tracer_lim.h
 constexpr int kTrCols = 64;       // tracer kernel: workgroup of 64 columns x kTrRows rows, one thread per (j, i) column
 constexpr int kTrRows = 4;
 constexpr int kUpdCols = 62;      // row-group update kernel: columns a wave produces (lanes 0 and 63 carry the halo columns)

@@ -55,6 +55,8 @@ const void *pe25d_field(Pe25d *m, int field, long *n, int *f32);
 int pe25d_set_tracers(Pe25d *m, int n, const double *c, hipStream_t s, std::string *err);
 int pe25d_get_tracers(Pe25d *m, int which, double *c, hipStream_t s, std::string *err);
 int pe25d_tracer_count(const Pe25d *m);
+int pe25d_set_tracer_scheme(Pe25d *m, int scheme, hipStream_t s, std::string *err);   // gcm_set_tracer_scheme
+int pe25d_tracer_scheme(const Pe25d *m);
 void pe25d_join_tracers(Pe25d *m, hipStream_t s);   // `s` waits for the last tracer launches on the other streams
 void pe25d_follow_tracers(Pe25d *m, hipStream_t s); // a pack / unpack on `s` follows the tracer launches on the second stream
 int pe25d_set_band_tracers(Pe25d *m, int n, hipStream_t s, std::string *err);   // gcm_set_band_tracers

@@ -553,6 +553,7 @@ struct Pe25d {
     // (see stage_tracers); ev_tr, recorded on `aux` behind the last tracer launch, is how the caller's stream joins that tail
     int ntr = 0;
     void *tr = nullptr;
+    int tr_scheme = GCM_TRACER_NONE;            // gcm_set_tracer_scheme: the face values of the tracers' fluxes
     bool tr_star = false;                       // the star set holds the tracers of a predictor
     bool tr_pending = false;                    // a tracer launch on `aux` that the caller's stream has not joined
     hipEvent_t ev_tr = nullptr;
@@ -567,7 +568,8 @@ struct Pe25d {
 static_assert(sizeof(SegCopy::n) / sizeof(long) >= 2 * (GCM_NFIELDS + 1 + GCM_MAX_TRACERS),
               "SegCopy holds one message per side: 5 fields, the ground temperature and every tracer");
 
-// a band's tracer fields: one ghost row a side (pe_tracer_kernel reads rows j - 1 .. j + 1 only); a single domain: none
+// a band's tracer fields: one ghost row a side (pe_tracer_kernel reads rows j - 1 .. j + 1 only, and so does the
+// donor-cell scheme; the van Leer scheme reads j -+ 2 and is refused on a band); a single domain: none
 static int tr_ghost(const Pe25d *m) { return m->wrap ? 0 : 1; }
 static long tr_stride(const Pe25d *m) { return (long)(m->H + 2 * tr_ghost(m)) * m->L * m->W; }
 // tracer f of set 0 (current) or 1 (star), at interior row 0
@@ -1118,7 +1120,8 @@ static void prep_rows(Pe25d *m, const PeArgsT<T> &a, int stage_set, bool p2, int
 // The passive tracers of one stage (pe25d_tracer.h) over rows [r0, r1) and [rb0, rb1): base = the current tracers,
 // stage = the star set in the corrector, out = the star set in the predictor and the current set again in the
 // corrector (each cell reads its base value only at itself: in place).  Chunks of 4, then 2, then 1 tracers, one
-// launch per chunk size (blockIdx.y = chunk).
+// launch per chunk size (blockIdx.y = chunk).  The handle's scheme picks the kernel: the centred one of
+// pe25d_tracer.h (GCM_TRACER_NONE: nothing about the launch differs) or the limited march of pe25d_tracer_lim.h.
 template <typename T>
 static void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out_set, hipStream_t st, int r0, int r1,
                            int rb0 = 0, int rb1 = 0) {
@@ -1145,7 +1148,9 @@ static void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out
         if (chunks == 0) continue;
         TracerArgsT<T> c = t;
         c.c += done * stride; c.sc += done * stride; c.oc += done * stride;
-        hipLaunchKernelGGL(tracer_kernel_for<T>(nc, same), dim3((unsigned)((tiles + 7) / 8 * 8), (unsigned)chunks), block, 0, st, c);
+        const TracerKernel<T> kern = m->tr_scheme == GCM_TRACER_NONE ? tracer_kernel_for<T>(nc, same)
+                                                                     : tracer_lim_kernel_for<T>(m->tr_scheme, nc, same);
+        hipLaunchKernelGGL(kern, dim3((unsigned)((tiles + 7) / 8 * 8), (unsigned)chunks), block, 0, st, c);
         done += chunks * nc;
     }
     m->tr_star = out_set == 2;
@@ -1569,6 +1574,22 @@ int pe25d_set_band_tracers(Pe25d *m, int n, hipStream_t s, std::string *err) {
 }
 
 int pe25d_tracer_count(const Pe25d *m) { return m->ntr; }
+
+int pe25d_tracer_scheme(const Pe25d *m) { return m->tr_scheme; }
+
+// gcm_set_tracer_scheme: between steps, with or without tracers.  The scheme is read where a stage launches its
+// tracer kernels; the star tracers of an earlier predictor belong to the earlier scheme and are dropped.
+int pe25d_set_tracer_scheme(Pe25d *m, int scheme, hipStream_t s, std::string *err) {
+    if (scheme == GCM_TRACER_VANLEER && !m->wrap) {
+        *err = "gcm_set_tracer_scheme: GCM_TRACER_VANLEER reads two rows either side of a cell, and a latitude band's "
+               "tracers carry one ghost row per side (the message format of gcm_set_band_tracers); single domains only";
+        return GCM_ERR_UNSUPPORTED;
+    }
+    pe25d_join_tracers(m, s);
+    m->tr_scheme = scheme;
+    m->tr_star = false;
+    return GCM_OK;
+}
 
 int pe25d_set_tracers(Pe25d *m, int n, const double *c, hipStream_t s, std::string *err) {
     if (!m->wrap && m->ntr == 0) {

@@ -3,7 +3,7 @@ equations): `matsuno_timestep` and `half_timestep`, computed by the HIP kernels.
 import numpy as np
 
 from . import _lib
-from .core import Core, as_f64
+from .core import Core, as_f64, tracer_scheme_id
 from .units import strip, scalar, attach
 
 _cache = {}
@@ -37,16 +37,34 @@ def _wrap_out(arrs, units):
     return tuple(attach(a, un) for a, un in zip(arrs, units))
 
 
-def half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, geom):
+def half_timestep(p, u, v, t, q, sp, su, sv, st, sq, dt, geom, tracers=None, tracer_scheme=None):
     """dynamics.py:183-227: one Euler stage from base (p,u,v,t,q) with tendencies evaluated
-    on the stage state; returns fresh (p_n, u_n, v_n, t_n, q_n)."""
+    on the stage state; returns fresh (p_n, u_n, v_n, t_n, q_n).  `tracers` (n, L, H, W): passive tracers
+    advanced by the stage's mass fluxes under `tracer_scheme` ("centred", "upwind", "van_leer"), with their own
+    values as both the base and the stage value; the result is then (p_n, u_n, v_n, t_n, q_n, tracers)."""
+    scheme = tracer_scheme_id(tracer_scheme)
     base, units = _prep(p, u, v, t, q, geom)
     stage, _ = _prep(sp, su, sv, st, sq, geom)
     c = core_for(geom)
     c.set_state(*base)
     c.set_star(*stage)
-    c.half_step(1, scalar(dt))          # corrector form: base + stage -> new current state
-    return _wrap_out(c.get_state(), units)
+    if tracers is None:
+        c.half_step(1, scalar(dt))          # corrector form: base + stage -> new current state
+        return _wrap_out(c.get_state(), units)
+    tr, tr_unit = _prep_tracers(tracers, geom)
+    try:
+        c.set_tracer_scheme(scheme)
+        c.set_tracers(tr)                   # (the star set starts as a copy: stage value = base value)
+        c.half_step(1, scalar(dt))
+        return (*_wrap_out(c.get_state(), units), attach(c.get_tracers(), tr_unit))
+    finally:
+        _forget_tracers(c)
+
+
+def _forget_tracers(c):
+    """the cached handle goes back to carrying no tracers, under the centred scheme"""
+    c.set_tracers(None)
+    c.set_tracer_scheme(None)
 
 
 def _prep_tracers(tracers, geom):
@@ -55,26 +73,31 @@ def _prep_tracers(tracers, geom):
     return tracer_array(vals, geom.layers, geom.height, geom.width), un
 
 
-def matsuno_timestep(p, u, v, t, q, dt, geom, boundary_conditions=None, coriolis=False, tracers=None):
+def matsuno_timestep(p, u, v, t, q, dt, geom, boundary_conditions=None, coriolis=False, tracers=None,
+                     tracer_scheme=None):
     """dynamics.py:230-237.  `coriolis=True` switches on the Coriolis terms the reference keeps
     behind `if False` (dynamics.py:82-92).  With a Python `boundary_conditions(sp,su,sv,st,sq,dt,geom)` hook
     the predicted state makes a host round trip between the stages (documented slow path);
     with None both stages stay on the device.  `tracers` (n, L, H, W): passive tracers advanced with
-    exactly the update of q; the result is then (p, u, v, t, q, tracers)."""
+    exactly the update of q, or under `tracer_scheme` ("centred", "upwind", "van_leer": Core.set_tracer_scheme)
+    with donor-cell or van Leer limited face values; the result is then (p, u, v, t, q, tracers)."""
+    scheme = tracer_scheme_id(tracer_scheme)
     base, units = _prep(p, u, v, t, q, geom)
     c = core_for(geom, coriolis=coriolis)
     c.set_state(*base)
     if tracers is not None:
         tr, tr_unit = _prep_tracers(tracers, geom)
-        c.set_tracers(tr)
     try:
+        if tracers is not None:
+            c.set_tracer_scheme(scheme)
+            c.set_tracers(tr)
         out = _matsuno_on(c, dt, geom, units, boundary_conditions)
         if tracers is None:
             return out
         return (*out, attach(c.get_tracers(), tr_unit))
     finally:
         if tracers is not None:
-            c.set_tracers(None)          # the cached handle goes back to carrying none
+            _forget_tracers(c)
 
 
 def _matsuno_on(c, dt, geom, units, boundary_conditions):
@@ -91,12 +114,13 @@ def _matsuno_on(c, dt, geom, units, boundary_conditions):
     return boundary_conditions(*out, dt, geom)
 
 
-def run(p, u, v, t, q, dt, geom, steps, callback=None, every=1, tracers=None):
+def run(p, u, v, t, q, dt, geom, steps, callback=None, every=1, tracers=None, tracer_scheme=None):
     """Device-resident loop: `steps` Matsuno steps with the state in HBM throughout;
     optional callback(p,u,v,t,q) every `every` steps (no_limits_2_5d.py:230-234).  `tracers`
-    (n, L, H, W): passive tracers carried along; the result is then (p, u, v, t, q, tracers)."""
+    (n, L, H, W): passive tracers carried along, under `tracer_scheme` ("centred", "upwind", "van_leer"); the
+    result is then (p, u, v, t, q, tracers)."""
     base, units = _prep(p, u, v, t, q, geom)
-    c = Core(_lib.PE25D, geom.width, geom.height, geom.layers, geom=geom)
+    c = Core(_lib.PE25D, geom.width, geom.height, geom.layers, geom=geom, tracer_scheme=tracer_scheme)
     try:
         c.set_state(*base)
         if tracers is not None:

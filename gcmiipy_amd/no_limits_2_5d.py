@@ -59,21 +59,23 @@ def full_timestep(p, u, v, t, q, g, dt, utc, geom, stats=STATS):
     return (*_wrap_out(c.get_state(), units), g)
 
 
-def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=None, physics=False, tracers=None):
+def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=None, physics=False, tracers=None,
+              tracer_scheme=None):
     """no_limits_2_5d.py:220-236 (and test_geography.py:6-23 with `bump=(j, i, metres)`): the
     state stays in HBM for all `timesteps`; STATS come from device reductions every step.
     physics=True: every step is followed by solar_timestep(t, p, g, dt, utc, geom) with utc = 0, dt, 2 dt, ...
     -- the lines the reference keeps below full_timestep's early return (:93-96) and run_model's clock (:222, :231);
     on the device both phases are one gcm_step (gcm_set_physics), and the returned g carries the new ground temperature.
     tracers (n, layers, height, width): passive tracers carried through every step (Core.set_tracers); their final
-    values are then appended to the result."""
+    values are then appended to the result.  tracer_scheme: their transport scheme, "centred" (default), "upwind" or
+    "van_leer" (Core.set_tracer_scheme); q keeps the reference's update."""
     geom = geometry.gen_geometry(height, width, layers, sig_func=geometry.manabe_sig)
     if bump is not None:
         geom.heightmap[bump[0], bump[1]] = bump[2]
     p, u, v, t, q, g = gen_initial_conditions(geom)
     v[0, 0, 0] = 0.1
     u *= 0
-    c = Core(_lib.PE25D, width, height, layers, geom=geom)
+    c = Core(_lib.PE25D, width, height, layers, geom=geom, tracer_scheme=tracer_scheme)
     try:
         c.set_state(p, u, v, t, q)
         if tracers is not None:

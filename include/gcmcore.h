@@ -179,8 +179,9 @@ int gcm_set_star(gcm_handle *h, const double *p, const double *u, const double *
  * gcm_step_boundary) advances with exactly the update the reference applies to q
  * (dynamics.py:219, advec_t :174-181, advec_sig :49-52) on the stage's own mass fluxes:
  *     c_n = (c p - (advec_t(spu, spv, sc) + advec_sig(sd, sc)) dt) / p_n,   sc = the stage value,
- * so a tracer equal to q stays equal to q (bit for bit in fp64).  No flux limiting, no positivity (the reference
- * applies none to q).  The handle stores them in its own real type; the host API is float64.
+ * so a tracer equal to q stays equal to q (bit for bit in fp64).  That update takes centred face values: no flux
+ * limiting, no positivity (the reference applies none to q); gcm_set_tracer_scheme below selects donor-cell or
+ * van Leer limited face values for the tracers.  The handle stores them in its own real type; the host API is float64.
  * gcm_set_tracers: 0 <= n <= GCM_MAX_TRACERS (n = 0 frees them), also resets the star set to c;
  * gcm_get_tracers: which = 0 the current tracers, 1 those of the last predictor (GCM_ERR_STATE before
  * one); gcm_tracer_count: n.  Other models: GCM_ERR_UNSUPPORTED.  On a latitude band (nranks > 1) c holds
@@ -194,6 +195,25 @@ int gcm_set_star(gcm_handle *h, const double *p, const double *u, const double *
 int gcm_set_tracers(gcm_handle *h, int n, const double *c);
 int gcm_get_tracers(gcm_handle *h, int which, double *c);
 int gcm_tracer_count(const gcm_handle *h);
+/* The transport scheme of the passive tracers of a GCM_PE25D handle (q keeps the reference's update in every case).
+ * The update keeps its flux form, its mass fluxes (spu, spv, sigma-dot) and its divisor p_n; the scheme is the value
+ * of the stage tracer sc that a mass flux F carries through the face between cells A and B (F > 0: from A to B), in
+ * all three directions from the one stage field (no dimension splitting):
+ *   GCM_TRACER_NONE (default)  (sc[A] + sc[B]) / 2, the update above;
+ *   GCM_TRACER_UPWIND          sc[U], U = A if F > 0 (strict) else B                    flux_limiter.py:23-27
+ *   GCM_TRACER_VANLEER         sc[U] + 1/2 phi(r) (sc[D] - sc[U]), phi(r) = (r + |r|) / (1 + |r|),
+ *                              r = (sc[U] - sc[UU]) / (sc[D] - sc[U]), 0 where that denominator is 0
+ *                              (D: the other cell of the face, UU: the cell behind U)    flux_limiter.py:10-20
+ * Differences are plain differences of neighbouring cells.  i is periodic, rows wrap as in the centred update; the
+ * column does not wrap: a level face whose UU lies outside the column is donor-cell.
+ * gcm_set_tracer_scheme: at any time between steps, with or without tracers set; it includes the tracer stream
+ * first, as gcm_set_tracers does, and leaves no predicted tracers (gcm_get_tracers(which = 1): GCM_ERR_STATE until the
+ * next predictor).  Errors: an unknown scheme GCM_ERR_ARG; a model other than GCM_PE25D GCM_ERR_UNSUPPORTED;
+ * GCM_TRACER_VANLEER on a latitude band (nranks > 1) GCM_ERR_UNSUPPORTED: it reads rows j -+ 2, and a band's tracers
+ * carry one ghost row per side (GCM_TRACER_UPWIND reads j -+ 1 and runs on bands; every band of a run must be given
+ * the same scheme).  gcm_tracer_scheme: the scheme in force (other models: GCM_TRACER_NONE).             */
+int gcm_set_tracer_scheme(gcm_handle *h, int scheme);
+int gcm_tracer_scheme(const gcm_handle *h);
 /* GCM_PE25D latitude bands (nranks > 1): the number of passive tracers the band carries, 0..GCM_MAX_TRACERS.
  * Fixes the ghost-row message (gcm_halo_bytes) and so must come before gcm_set_halo_buffers / gcm_set_exchange.
  * The band's tracers start as zeros (gcm_set_tracers with the same n sets them).  Errors: n out of range
