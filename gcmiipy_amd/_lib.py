@@ -139,6 +139,8 @@ SYMBOLS = {
     "gcm_get_tracers": (C.c_int, [_H, C.c_int, C.c_void_p]),
     "gcm_tracer_count": (C.c_int, [_H]),
     "gcm_set_band_tracers": (C.c_int, [_H, C.c_int]),
+    "gcm_set_band_tracer_rows": (C.c_int, [_H, C.c_int]),
+    "gcm_band_tracer_rows": (C.c_int, [_H]),
     "gcm_set_tracer_scheme": (C.c_int, [_H, C.c_int]),
     "gcm_tracer_scheme": (C.c_int, [_H]),
 }

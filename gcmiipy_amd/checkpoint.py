@@ -4,7 +4,8 @@ temperature of the column physics (when set), the model tag, every option the ha
 with (dx, tracer, kernel variant, filter, Coriolis, dtype, band placement, ensemble members: an ensemble's
 state arrays are (M, H, W), and files without "opt_members" restore as one member), the passive tracers of a GCM_PE25D
 handle (key "tracers", only when it carries some; a band also stores its declared "band_tracers", files without it
-restore with 0; the tracers' transport scheme is the option "tracer_scheme", files without it restore as centred)
+restore with 0, and its ghost-row depth "band_tracer_rows", files without it restore as 1; the tracers' transport scheme
+is the option "tracer_scheme", files without it restore as centred)
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""

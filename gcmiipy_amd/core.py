@@ -92,9 +92,12 @@ class Core:
     def __init__(self, model, width, height, layers=1, dx=0.0, tracer=_lib.TRACER_NONE,
                  variant=_lib.VARIANT_AUTO, geom=None, filter=True, nranks=1, rank=0,
                  global_height=None, row0=0, device=-1, stream=None, halo_steps=1, coriolis=False, dtype="f64",
-                 members=1, band_tracers=0, tracer_scheme=None):
+                 members=1, band_tracers=0, tracer_scheme=None, band_tracer_rows=1):
         """band_tracers: a GCM_PE25D latitude band (nranks > 1) that carries that many passive tracers
         (gcm_set_band_tracers, right after gcm_create: the ghost-row message and halo_bytes() include them);
+        band_tracer_rows: the ghost rows per side those tracers carry, 1 (default) or 2 (what "van_leer" reads on a
+        band; gcm_set_band_tracer_rows, right after gcm_create and ahead of the scheme: the message carries that
+        many rows of every tracer, and every band of a run must declare the same);
         tracer_scheme: the passive tracers' transport scheme (set_tracer_scheme), GCM_PE25D only"""
         check_dtype(dtype)
         scheme = tracer_scheme_id(tracer_scheme)
@@ -106,6 +109,14 @@ class Core:
         if band_tracers > 0 and (model != _lib.PE25D or nranks <= 1):
             raise ValueError("band_tracers needs a GCM_PE25D latitude band (nranks > 1); a single domain takes "
                              "set_tracers directly")
+        is_pe_band = model == _lib.PE25D and nranks > 1
+        # (0: what the band_tracer_rows property of anything but a GCM_PE25D band reports, and its checkpoints carry)
+        if isinstance(band_tracer_rows, bool) or band_tracer_rows not in ((1, 2) if is_pe_band else (0, 1, 2)):
+            raise ValueError("band_tracer_rows must be 1 or 2, got %r" % (band_tracer_rows,))
+        if band_tracer_rows == 2 and not is_pe_band:
+            raise ValueError("band_tracer_rows needs a GCM_PE25D latitude band (nranks > 1); a single domain's rows "
+                             "wrap and carry no ghost rows")
+        band_tracer_rows = int(band_tracer_rows) if is_pe_band else 0
         self.model, self.W, self.H, self.L = model, int(width), int(height), int(layers)
         # ensemble members (2-D models, single band): every field is (M, H, W) when M > 1
         self.members = max(int(members), 1)
@@ -114,7 +125,7 @@ class Core:
         self.options = dict(dx=float(dx), tracer=int(tracer), variant=int(variant), filter=bool(filter),
                             nranks=int(nranks), rank=int(rank), row0=int(row0), halo_steps=int(halo_steps),
                             coriolis=bool(coriolis), dtype=dtype, members=int(members), band_tracers=band_tracers,
-                            tracer_scheme=_lib.TRACER_NONE,
+                            tracer_scheme=_lib.TRACER_NONE, band_tracer_rows=band_tracer_rows,
                             global_height=int(height if global_height is None else global_height))
         self.has_ground = False
         cfg = _lib.Config()
@@ -166,6 +177,8 @@ class Core:
         try:
             if band_tracers > 0:
                 _check(lib.gcm_set_band_tracers(self._h, band_tracers), self._h)
+            if band_tracer_rows == 2:
+                _check(lib.gcm_set_band_tracer_rows(self._h, band_tracer_rows), self._h)
             if scheme != _lib.TRACER_NONE:
                 self.set_tracer_scheme(scheme)
         except Exception:
@@ -246,8 +259,9 @@ class Core:
 
     def set_tracer_scheme(self, scheme):
         """the transport scheme of the passive tracers from the next stage on: "centred" (the update of q, the
-        default), "upwind" (donor-cell face values) or "van_leer" (donor-cell + the van Leer limited correction;
-        single domains only), or the _lib.TRACER_* constants (gcm_set_tracer_scheme).  q is not affected"""
+        default), "upwind" (donor-cell face values) or "van_leer" (donor-cell + the van Leer limited correction; on a
+        latitude band only with band_tracer_rows=2: it reads rows j -+ 2), or the _lib.TRACER_* constants
+        (gcm_set_tracer_scheme).  q is not affected; a refused call changes nothing"""
         scheme = tracer_scheme_id(scheme)
         _check(lib.gcm_set_tracer_scheme(self._h, scheme), self._h)
         self.options["tracer_scheme"] = scheme
@@ -259,6 +273,14 @@ class Core:
         if s < 0:
             _check(s, self._h)
         return s
+
+    @property
+    def band_tracer_rows(self):
+        """the ghost rows per side a band's tracers carry (gcm_band_tracer_rows); 0: not a GCM_PE25D band"""
+        n = lib.gcm_band_tracer_rows(self._h)
+        if n < 0:
+            _check(n, self._h)
+        return n
 
     @property
     def tracer_count(self):

@@ -634,6 +634,18 @@ int gcm_set_band_tracers(gcm_handle *h, int n) {
     return pe25d_set_band_tracers(h->pe, n, h->stream, &h->err);
 }
 
+int gcm_set_band_tracer_rows(gcm_handle *h, int rows) {
+    if (!h) return GCM_ERR_ARG;
+    if (!h->pe) return fail(h, GCM_ERR_UNSUPPORTED, "gcm_set_band_tracer_rows: GCM_PE25D latitude bands only");
+    if (h->cfg.device >= 0) HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pe25d_set_band_tracer_rows(h->pe, rows, h->stream, &h->err);
+}
+
+int gcm_band_tracer_rows(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_band_tracer_rows(h->pe) : 0;
+}
+
 int gcm_get_tracers(gcm_handle *h, int which, double *c) {
     if (int rc = tracer_refusal(h, "gcm_get_tracers")) return rc;
     if (h->cfg.device >= 0) HIPCHK(h, hipSetDevice(h->cfg.device));

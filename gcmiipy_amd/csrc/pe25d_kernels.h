@@ -60,6 +60,8 @@ int pe25d_tracer_scheme(const Pe25d *m);
 void pe25d_join_tracers(Pe25d *m, hipStream_t s);   // `s` waits for the last tracer launches on the other streams
 void pe25d_follow_tracers(Pe25d *m, hipStream_t s); // a pack / unpack on `s` follows the tracer launches on the second stream
 int pe25d_set_band_tracers(Pe25d *m, int n, hipStream_t s, std::string *err);   // gcm_set_band_tracers
+int pe25d_set_band_tracer_rows(Pe25d *m, int rows, hipStream_t s, std::string *err);   // gcm_set_band_tracer_rows
+int pe25d_band_tracer_rows(const Pe25d *m);   // a band: the depth in force; a single domain: 0
 void pe25d_timing(Pe25d *m, std::vector<hipEvent_t> *ev, size_t *used);
 
 }  // namespace gcm

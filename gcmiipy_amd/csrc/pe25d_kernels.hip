@@ -548,11 +548,13 @@ struct Pe25d {
     hipEvent_t ev_pre_edge = nullptr;
     bool pre_edge_pending = false;
     // passive tracers (gcm_set_tracers; a band: gcm_set_band_tracers first): 2 x ntr fields of (H + 2 tr_ghost(m)) x L x W
-    // in T, device layout [j][k][i] -- the current set (ntr fields), then the star set; a band's fields carry one ghost
-    // row a side (the kernel reads rows j -+ 1 only), addressed from interior row 0.  The tracer kernel runs on chain B
+    // in T, device layout [j][k][i] -- the current set (ntr fields), then the star set; a band's fields carry tr_rows
+    // ghost rows a side (gcm_set_band_tracer_rows: 1, or the 2 the van Leer scheme reads), addressed from interior row
+    // 0.  The tracer kernel runs on chain B
     // (see stage_tracers); ev_tr, recorded on `aux` behind the last tracer launch, is how the caller's stream joins that tail
     int ntr = 0;
     void *tr = nullptr;
+    int tr_rows = 1;                            // gcm_set_band_tracer_rows: a band's tracer ghost rows per side (see tr_ghost)
     int tr_scheme = GCM_TRACER_NONE;            // gcm_set_tracer_scheme: the face values of the tracers' fluxes
     bool tr_star = false;                       // the star set holds the tracers of a predictor
     bool tr_pending = false;                    // a tracer launch on `aux` that the caller's stream has not joined
@@ -568,9 +570,16 @@ struct Pe25d {
 static_assert(sizeof(SegCopy::n) / sizeof(long) >= 2 * (GCM_NFIELDS + 1 + GCM_MAX_TRACERS),
               "SegCopy holds one message per side: 5 fields, the ground temperature and every tracer");
 
-// a band's tracer fields: one ghost row a side (pe_tracer_kernel reads rows j - 1 .. j + 1 only, and so does the
-// donor-cell scheme; the van Leer scheme reads j -+ 2 and is refused on a band); a single domain: none
-static int tr_ghost(const Pe25d *m) { return m->wrap ? 0 : 1; }
+// a band's tracer fields: the declared ghost rows a side (gcm_set_band_tracer_rows).  One by default: pe_tracer_kernel
+// reads rows j - 1 .. j + 1 only, and so does the donor-cell scheme; the van Leer scheme reads j -+ 2 and is refused
+// on a band that declared fewer than two.  A single domain: none.  The storage, the message (pe25d_halo_bytes, halo_t)
+// and set / get all take the depth from here
+static int tr_ghost(const Pe25d *m) { return m->wrap ? 0 : m->tr_rows; }
+// the deepest a band's tracers may be declared: what the van Leer scheme reads.  It may not exceed the state's ghost
+// depth: the edge launch of update_edges covers kGhost own rows a side, which are the rows a neighbour takes and the
+// only rows that may read tracer ghost rows
+constexpr int kTrGhostMax = 2;
+static_assert(kTrGhostMax <= kGhost, "the tracers' edge launch covers kGhost rows a side");
 static long tr_stride(const Pe25d *m) { return (long)(m->H + 2 * tr_ghost(m)) * m->L * m->W; }
 // tracer f of set 0 (current) or 1 (star), at interior row 0
 static char *tr_field(const Pe25d *m, int set, int f) {
@@ -1235,7 +1244,16 @@ static void chain_b_head(Pe25d *m, const Stage<T> &g) {
     // hazard 1 of a band's tracers: this stage's K1 overwrites spu, pit and p_n -- and its K4 the state sets -- that
     // the last stage's tracer launch on another stream may still read (ev_tr_int, see stage_tracers): chain B waits for
     // it here, and so does the caller's stream where it takes the edge rows (no send buffers: the tracers' edge rows
-    // read what that launch wrote); the third stream's K1 follows it in stream order, or waits for it in chain_b_k1_pit
+    // read what that launch wrote); the third stream's K1 follows it in stream order, or waits for it in chain_b_k1_pit.
+    // At the van Leer scheme's reach of two rows (gcm_set_band_tracer_rows(2)) the same wait covers what is new: the
+    // edge launch of this stage writes the out set's rows 0, 1, H - 2, H - 1, which the last stage's interior launch
+    // (rows [2, H - 2)) read as its stage set at j -+ 2 -- at reach one it read rows 1 and H - 2 of them -- and it
+    // reads rows 2, 3, H - 4, H - 3, which that launch wrote (at reach one: rows 2 and H - 3).  The other direction:
+    // this stage's interior launch reads the stage set's rows 0, 1, H - 2, H - 1, which the LAST stage's edge launch
+    // wrote on the edge rows' stream (at reach one: rows 1 and H - 2, of the same launch).  It waits for ev_a, and
+    // ev_a follows that launch on every path: K1 of all rows is queued on chain B behind it (send buffers: the same
+    // stream; none: chain B's fork follows the caller's stream, which carried it), and the split K1's own rows on the
+    // third stream wait for the fork and for ev_edges, recorded behind the pack that follows it
     m->tr_int_wait = false;
     if (g.tr_prev) {
         if (g.sb != m->tr_int_stream) (void)hipStreamWaitEvent(g.sb, m->ev_tr_int, 0);
@@ -1407,6 +1425,11 @@ static void update_edges(Pe25d *m, const Stage<T> &g) {
         // rows' K4, behind K1, pit and ev_a and ahead of the wait for K3: they fill chain B's wait.  Hazard 2: in
         // the corrector they read the star tracers' ghost rows, which the post-predictor unpack filled ahead of K1
         // on this stream (gcm_band_run), or on the caller's stream before this call (host-driven exchange).
+        // With two ghost rows a side (gcm_set_band_tracer_rows) that unpack fills both from the one segment per
+        // tracer, so its completion covers rows -2, -1, H and H + 1 alike; these rows [0, 2) and [H - 2, H) are the
+        // only ones whose j -+ 2 leaves the band (the interior launch of stage_tracers reaches own rows 0 and H - 1 at
+        // most), and they are exactly the rows the pack below takes at that depth.  A band too short to split
+        // (H <= 4) takes the one launch here, behind the same unpack.
         if (g.split) launch_tracers<T>(m, g.a, g.stage_set, g.out_set, se, j0, j0 + kGhost, j1 - kGhost, j1);
         else launch_tracers<T>(m, g.a, g.stage_set, g.out_set, se, j0, j1);
     }
@@ -1540,6 +1563,30 @@ void pe25d_follow_tracers(Pe25d *m, hipStream_t s) {
     (void)hipStreamWaitEvent(s, m->ev_tr, 0);
 }
 
+// A band's tracers anew: n fields a set with `rows` ghost rows a side, zeros (until gcm_set_tracers).  Joins the tracer
+// stream first; the count and the depth change together with the storage, or -- on a HIP error -- the band is left
+// without tracers at the depth asked for
+static int band_tracers_alloc(Pe25d *m, int n, int rows, hipStream_t s, const char *fn, std::string *err) {
+    pe25d_join_tracers(m, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess && m->tr) e = hipFree(m->tr);
+    m->tr = nullptr;
+    m->ntr = 0;
+    m->tr_star = false;
+    m->tr_rows = rows;
+    const size_t bytes = 2 * (size_t)n * tr_stride(m) * (m->f32 ? sizeof(float) : sizeof(double));
+    if (e == hipSuccess && n > 0) e = hipMalloc(&m->tr, bytes);
+    if (e == hipSuccess && n > 0) e = hipMemset(m->tr, 0, bytes);
+    if (e == hipSuccess && n > 0) m->ntr = n;
+    if (e == hipSuccess && n > 0 && m->aux && !m->ev_tr) e = hipEventCreateWithFlags(&m->ev_tr, hipEventDisableTiming);
+    if (e == hipSuccess && n > 0 && m->aux && !m->ev_tr_int) e = hipEventCreateWithFlags(&m->ev_tr_int, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        *err = std::string(fn) + ": " + hipGetErrorString(e);
+        return GCM_ERR_HIP;
+    }
+    return GCM_OK;
+}
+
 // gcm_set_band_tracers: a band's tracer count, fixed before the message size is used (zeros until gcm_set_tracers)
 int pe25d_set_band_tracers(Pe25d *m, int n, hipStream_t s, std::string *err) {
     if (m->wrap) {
@@ -1554,24 +1601,34 @@ int pe25d_set_band_tracers(Pe25d *m, int n, hipStream_t s, std::string *err) {
         *err = "gcm_set_band_tracers: send or exchange buffers are registered already (their size follows the count)";
         return GCM_ERR_STATE;
     }
-    pe25d_join_tracers(m, s);
-    hipError_t e = hipStreamSynchronize(s);
-    if (e == hipSuccess && m->tr) e = hipFree(m->tr);
-    m->tr = nullptr;
-    m->ntr = 0;
-    m->tr_star = false;
-    const size_t bytes = 2 * (size_t)n * tr_stride(m) * (m->f32 ? sizeof(float) : sizeof(double));
-    if (e == hipSuccess && n > 0) e = hipMalloc(&m->tr, bytes);
-    if (e == hipSuccess && n > 0) e = hipMemset(m->tr, 0, bytes);
-    if (e == hipSuccess && n > 0) m->ntr = n;
-    if (e == hipSuccess && n > 0 && m->aux && !m->ev_tr) e = hipEventCreateWithFlags(&m->ev_tr, hipEventDisableTiming);
-    if (e == hipSuccess && n > 0 && m->aux && !m->ev_tr_int) e = hipEventCreateWithFlags(&m->ev_tr_int, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        *err = std::string("gcm_set_band_tracers: ") + hipGetErrorString(e);
-        return GCM_ERR_HIP;
-    }
-    return GCM_OK;
+    return band_tracers_alloc(m, n, m->tr_rows, s, "gcm_set_band_tracers", err);
 }
+
+// gcm_set_band_tracer_rows: the ghost rows a side of a band's tracers, fixed before the message size is used like
+// the count.  A change of depth moves interior row 0 of every field: the tracers are allocated anew, as zeros
+int pe25d_set_band_tracer_rows(Pe25d *m, int rows, hipStream_t s, std::string *err) {
+    if (m->wrap) {
+        *err = "gcm_set_band_tracer_rows: GCM_PE25D latitude bands only (a single domain's rows wrap: no ghost rows)";
+        return GCM_ERR_UNSUPPORTED;
+    }
+    if (rows < 1 || rows > kTrGhostMax) {
+        *err = "gcm_set_band_tracer_rows: rows must be 1 .. " + std::to_string(kTrGhostMax);
+        return GCM_ERR_ARG;
+    }
+    if (m->halo_fixed) {
+        *err = "gcm_set_band_tracer_rows: send or exchange buffers are registered already (their size follows the depth)";
+        return GCM_ERR_STATE;
+    }
+    if (rows == m->tr_rows) return GCM_OK;
+    if (rows < 2 && m->tr_scheme == GCM_TRACER_VANLEER) {
+        *err = "gcm_set_band_tracer_rows: GCM_TRACER_VANLEER is in force and reads two ghost rows per side "
+               "(gcm_set_tracer_scheme first)";
+        return GCM_ERR_STATE;
+    }
+    return band_tracers_alloc(m, m->ntr, rows, s, "gcm_set_band_tracer_rows", err);
+}
+
+int pe25d_band_tracer_rows(const Pe25d *m) { return tr_ghost(m); }
 
 int pe25d_tracer_count(const Pe25d *m) { return m->ntr; }
 
@@ -1580,9 +1637,12 @@ int pe25d_tracer_scheme(const Pe25d *m) { return m->tr_scheme; }
 // gcm_set_tracer_scheme: between steps, with or without tracers.  The scheme is read where a stage launches its
 // tracer kernels; the star tracers of an earlier predictor belong to the earlier scheme and are dropped.
 int pe25d_set_tracer_scheme(Pe25d *m, int scheme, hipStream_t s, std::string *err) {
-    if (scheme == GCM_TRACER_VANLEER && !m->wrap) {
-        *err = "gcm_set_tracer_scheme: GCM_TRACER_VANLEER reads two rows either side of a cell, and a latitude band's "
-               "tracers carry one ghost row per side (the message format of gcm_set_band_tracers); single domains only";
+    // (a single domain's rows wrap through Idx; a band addresses rows j -+ 2 in its ghost rows, and the edge launch of
+    // update_edges -- own rows [0, 2) and [H - 2, H) -- is the only one that reaches them)
+    if (scheme == GCM_TRACER_VANLEER && !m->wrap && tr_ghost(m) < 2) {
+        *err = "gcm_set_tracer_scheme: GCM_TRACER_VANLEER reads two rows either side of a cell, and this latitude band's "
+               "tracers carry one ghost row per side (the message format of gcm_set_band_tracers); declare two with "
+               "gcm_set_band_tracer_rows(h, 2) before the send or exchange buffers are registered";
         return GCM_ERR_UNSUPPORTED;
     }
     pe25d_join_tracers(m, s);
@@ -1788,7 +1848,7 @@ int pe25d_wait_edges(Pe25d *m, hipStream_t s, std::string *err) {
 // Which state is exchanged follows the step phase: the predicted state once it exists.
 size_t pe25d_halo_bytes(const Pe25d *m) {
     // (+ the ground temperature's two rows, float64 for either storage type: gcm_set_physics;
-    //  + a band's tracers, one row x L levels each: gcm_set_band_tracers)
+    //  + a band's tracers, tr_ghost rows x L levels each: gcm_set_band_tracers, gcm_set_band_tracer_rows)
     const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
     return esz * (size_t)kGhost * m->W * (1 + 4 * (size_t)m->L) + sizeof(double) * (size_t)kGhost * m->W +
            (m->wrap ? 0 : esz * (size_t)m->ntr * tr_ghost(m) * m->L * m->W);

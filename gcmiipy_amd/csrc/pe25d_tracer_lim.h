@@ -92,7 +92,8 @@ __global__ __launch_bounds__(kTrCols * kTrRows) void pe_tracer_lim_kernel(Tracer
     const T inv_pn = rcp(a.pn[p_c + i]);
     const T pit_c = a.pit[p_c + i];
     const long rn = ix.r3(j - 1), rc = ix.r3(j), rs = ix.r3(j + 1);
-    // (VANLEER runs on single domains only, gcm_set_tracer_scheme: rows j -+ 2 wrap through Idx)
+    // (VANLEER: rows j -+ 2 wrap through Idx on a single domain; on a band they are plain row arithmetic into the two
+    // ghost rows a side that gcm_set_band_tracer_rows declared -- gcm_set_tracer_scheme refuses the scheme without them)
     const long rnn = VL ? ix.r3(j - 2) : rn, rss = VL ? ix.r3(j + 2) : rs;
 
     // running sum of conv from the top, per tracer the flux through the upper face of the level, and the own

@@ -209,9 +209,11 @@ int gcm_tracer_count(const gcm_handle *h);
  * gcm_set_tracer_scheme: at any time between steps, with or without tracers set; it includes the tracer stream
  * first, as gcm_set_tracers does, and leaves no predicted tracers (gcm_get_tracers(which = 1): GCM_ERR_STATE until the
  * next predictor).  Errors: an unknown scheme GCM_ERR_ARG; a model other than GCM_PE25D GCM_ERR_UNSUPPORTED;
- * GCM_TRACER_VANLEER on a latitude band (nranks > 1) GCM_ERR_UNSUPPORTED: it reads rows j -+ 2, and a band's tracers
- * carry one ghost row per side (GCM_TRACER_UPWIND reads j -+ 1 and runs on bands; every band of a run must be given
- * the same scheme).  gcm_tracer_scheme: the scheme in force (other models: GCM_TRACER_NONE).             */
+ * GCM_TRACER_VANLEER on a latitude band (nranks > 1) that has not declared two tracer ghost rows per side
+ * (gcm_set_band_tracer_rows(h, 2), below) GCM_ERR_UNSUPPORTED: it reads rows j -+ 2, and a band's tracers carry one
+ * ghost row per side unless told otherwise (GCM_TRACER_UPWIND reads j -+ 1 and runs on any band; every band of a run
+ * must be given the same scheme).  A refused call leaves the scheme in force as it was.
+ * gcm_tracer_scheme: the scheme in force (other models: GCM_TRACER_NONE).                                */
 int gcm_set_tracer_scheme(gcm_handle *h, int scheme);
 int gcm_tracer_scheme(const gcm_handle *h);
 /* GCM_PE25D latitude bands (nranks > 1): the number of passive tracers the band carries, 0..GCM_MAX_TRACERS.
@@ -220,6 +222,21 @@ int gcm_tracer_scheme(const gcm_handle *h);
  * GCM_ERR_ARG; any handle but a GCM_PE25D band (single domains need no declaration) GCM_ERR_UNSUPPORTED;
  * a call after send or exchange buffers were registered GCM_ERR_STATE.                                 */
 int gcm_set_band_tracers(gcm_handle *h, int n);
+/* GCM_PE25D latitude bands: the ghost rows per side that the band's tracers carry, rows = 1 (default: the message
+ * format of gcm_set_band_tracers, byte for byte) or 2 (what GCM_TRACER_VANLEER reads; gcm_set_tracer_scheme accepts
+ * it on a band only at this depth).  The depth is a declaration of its own, not a consequence of the scheme: the
+ * scheme may change between any two steps, the message size may not change once buffers are registered.  Same life
+ * cycle as gcm_set_band_tracers: before gcm_set_halo_buffers / gcm_set_exchange, before or after
+ * gcm_set_band_tracers, and either may be repeated until then.  A change of depth includes the tracer stream first
+ * and allocates the band's tracers anew, as zeros.  With rows = 2 the centred and the donor-cell scheme compute what
+ * they compute with rows = 1 (they read j -+ 1 only): only the message grows.  EVERY band of a run must declare the
+ * same depth, as with the scheme and the count: the neighbours' messages have one size.
+ * Errors: a null handle or rows outside {1, 2} GCM_ERR_ARG; any handle but a GCM_PE25D band GCM_ERR_UNSUPPORTED;
+ * a call after send or exchange buffers were registered GCM_ERR_STATE, and so is rows = 1 while GCM_TRACER_VANLEER
+ * is in force.  A refused call leaves depth, tracers and scheme as they were.
+ * gcm_band_tracer_rows: the depth in force (a single domain and other models: 0).                          */
+int gcm_set_band_tracer_rows(gcm_handle *h, int rows);
+int gcm_band_tracer_rows(const gcm_handle *h);
 
 /* Diagnostics the reference's drivers evaluate on the host every step
  * (SURVEY.md 8f-1); computed by device reductions, result copied to *out. */
@@ -314,9 +331,11 @@ int gcm_restore(gcm_handle *h);
  * itself.  `side` 0 = towards row 0 (north), 1 = towards the last row (south).
  * gcm_halo_bytes gives the buffer size for one side.  GCM_PE25D, segment by segment: the two rows of p,
  * then of u, v, t, q (every level) in the handle's storage type, then the two rows of the ground
- * temperature in float64 (see gcm_set_physics), then -- with n = gcm_set_band_tracers(n) > 0 -- ONE row
- * (every level) of each tracer in order, in the storage type: the tracer kernel reads rows j -+ 1 only.
- * Bytes per side:  esz 2 W (1 + 4 L) + 8 * 2 W + n esz L W  (esz = 8 for fp64, 4 for fp32 storage).
+ * temperature in float64 (see gcm_set_physics), then -- with n = gcm_set_band_tracers(n) > 0 -- the R rows
+ * (every level) next to the boundary of each tracer in order, as one contiguous segment per tracer, in the storage
+ * type; R = gcm_band_tracer_rows: 1 by default (the centred and the donor-cell scheme read rows j -+ 1 only), 2
+ * after gcm_set_band_tracer_rows(h, 2).
+ * Bytes per side:  esz 2 W (1 + 4 L) + 8 * 2 W + n esz R L W  (esz = 8 for fp64, 4 for fp32 storage).
  * Each message carries the tracers that belong to the state it carries (the predicted ones after a
  * predictor, the current ones otherwise).                                                       */
 size_t gcm_halo_bytes(const gcm_handle *h);

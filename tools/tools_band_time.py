@@ -10,9 +10,12 @@ say how far the kernels alone let the step shrink when the grid is split N ways 
 over xGMI then has to hide behind them.  The 8-GPU runs themselves are the driver's.
 
   python tools/tools_band_time.py [--workload c4|c3] [--splits 1,2,4,8] [--steps 20] [--tracers n]
+                                  [--tracer-scheme centred|upwind|van_leer] [--tracer-rows 1|2]
 
 --tracers n (GCM_PE25D): the band carries n passive tracers (Core(band_tracers=n); the single domain of N = 1 the same
 n through set_tracers), each a copy of q; "exchange_bytes_per_step" counts their ghost rows in the messages.
+--tracer-scheme: their transport scheme (Core(tracer_scheme=...)); --tracer-rows: the ghost rows per side a band's
+tracers carry (Core(band_tracer_rows=...): 2 is what van_leer needs on a band, and what the message then carries).
 """
 import argparse
 import json
@@ -23,15 +26,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def halo_bytes_pe25d(W, L, esz, ntr=0):
+def halo_bytes_pe25d(W, L, esz, ntr=0, rows=1):
     """bytes of one GCM_PE25D ghost-row message (one side; gcm_halo_bytes): two rows of p, u, v, t, q in the storage
-    type (esz bytes), two float64 rows of the ground temperature, one row of every tracer"""
-    return esz * 2 * W * (1 + 4 * L) + 8 * 2 * W + ntr * esz * L * W
+    type (esz bytes), two float64 rows of the ground temperature, `rows` rows of every tracer (gcm_set_band_tracer_rows)"""
+    return esz * 2 * W * (1 + 4 * L) + 8 * 2 * W + ntr * esz * rows * L * W
 
 
-def exchange_bytes_per_step(W, L, esz, ntr=0):
+def exchange_bytes_per_step(W, L, esz, ntr=0, rows=1):
     """what one GCM_PE25D band sends per step: two exchanges (predicted state, new state), one message to either side"""
-    return 2 * 2 * halo_bytes_pe25d(W, L, esz, ntr)
+    return 2 * 2 * halo_bytes_pe25d(W, L, esz, ntr, rows)
 
 
 def main():
@@ -41,6 +44,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--tracers", type=int, default=0, help="GCM_PE25D: passive tracers carried by the band (copies of q)")
+    ap.add_argument("--tracer-scheme", default="centred", choices=["centred", "upwind", "van_leer"],
+                    help="GCM_PE25D: the tracers' transport scheme")
+    ap.add_argument("--tracer-rows", type=int, default=1, choices=[1, 2],
+                    help="GCM_PE25D bands: ghost rows per side of the tracers (2: what van_leer reads)")
     ap.add_argument("--exchange", default="local", choices=["local", "rccl", "torch-nccl"],
                     help="local: device copy in place of the exchange; rccl: the band sends to itself through "
                          "gcmiipy_amd.rccl (RCCL called directly: the production path, no xGMI); torch-nccl: the "
@@ -76,7 +83,9 @@ def main():
                       nranks=n, rank=rank, global_height=H, row0=row0,
                       stream=torch.cuda.current_stream().cuda_stream, halo_steps=k,
                       dtype="f32" if a.workload.endswith("_f32") else "f64",
-                      band_tracers=a.tracers if n > 1 else 0)
+                      band_tracers=a.tracers if n > 1 else 0,
+                      band_tracer_rows=a.tracer_rows if n > 1 and model == "PE25D" else 1,
+                      tracer_scheme=a.tracer_scheme if model == "PE25D" else None)
         sl = slice(row0, row0 + nrows)
         core.set_state(**{f: (x[sl] if x.ndim == 2 else x[:, sl]) for f, x in full.items()})
         if a.tracers:
@@ -144,8 +153,11 @@ def main():
         host_idle_ms = (time.perf_counter() - t0) * 1e3 / nq
         torch.cuda.synchronize()
         esz = 4 if a.workload.endswith("_f32") else 8
+        if model == "PE25D" and n > 1:
+            assert core.halo_bytes() == halo_bytes_pe25d(W, L, esz, a.tracers, a.tracer_rows)
         res.append({"split": n, "band_rows": nrows, "halo_steps": k, "tracers": a.tracers,
-                    "exchange_bytes_per_step": (exchange_bytes_per_step(W, L, esz, a.tracers) if model == "PE25D" and n > 1
+                    "tracer_scheme": a.tracer_scheme, "tracer_rows": a.tracer_rows if n > 1 else 0,
+                    "exchange_bytes_per_step": (exchange_bytes_per_step(W, L, esz, a.tracers, a.tracer_rows) if model == "PE25D" and n > 1
                                                 else (2 * core.halo_bytes() // k if n > 1 else 0)),
                     "ms_per_step": ms, "host_ms_per_step": host_ms,
                     "host_queue_ms_per_step_idle_device": host_idle_ms,
@@ -157,7 +169,8 @@ def main():
     for r in res:
         if base:
             r["compute_bound_speedup"] = base / r["ms_per_step"]
-    doc = {"workload": desc, "exchange": a.exchange, "tracers": a.tracers,
+    doc = {"workload": desc, "exchange": a.exchange, "tracers": a.tracers, "tracer_scheme": a.tracer_scheme,
+           "tracer_rows": a.tracer_rows,
            "note": "one band of an N-way split stepped on one GPU, exchange replaced by a device-local copy "
                    "(local) or sent to itself through RCCL (rccl): the kernels' own strong-scaling bound", "bands": res}
     print(json.dumps(doc))
