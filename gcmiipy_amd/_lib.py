@@ -18,6 +18,7 @@ TRACER_NONE, TRACER_UPWIND, TRACER_VANLEER = 0, 1, 2
 VARIANT_AUTO, VARIANT_STAGED, VARIANT_FUSED = 0, 1, 2
 F64, F32 = 0, 1
 MAX_TRACERS = 16                     # GCM_MAX_TRACERS
+TRACER_STATS_WORDS = 6               # GCM_TRACER_STATS_WORDS
 ADV_UPWIND, ADV_FV_UPWIND, ADV_FV_PLAIN, ADV_VANLEER, ADV_MOMENTUM = range(5)
 DIAG_ANY_NAN, DIAG_MAX_U, DIAG_MEAN_P, DIAG_SUM_P, DIAG_MIN_U, DIAG_MAX_V, DIAG_MIN_V = range(7)
 DIAG_TV_P, DIAG_TV_U, DIAG_TV_V, DIAG_TV_T, DIAG_TV_Q = range(7, 12)
@@ -138,6 +139,7 @@ SYMBOLS = {
     "gcm_set_tracers": (C.c_int, [_H, C.c_int, C.c_void_p]),
     "gcm_get_tracers": (C.c_int, [_H, C.c_int, C.c_void_p]),
     "gcm_tracer_count": (C.c_int, [_H]),
+    "gcm_tracer_stats": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "gcm_set_band_tracers": (C.c_int, [_H, C.c_int]),
     "gcm_set_band_tracer_rows": (C.c_int, [_H, C.c_int]),
     "gcm_band_tracer_rows": (C.c_int, [_H]),

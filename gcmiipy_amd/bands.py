@@ -36,6 +36,35 @@ def split_rows(global_h, nranks):
     return out
 
 
+def merge_tracer_stats(stats):
+    """the global TracerStats from the bands' (Core.tracer_stats of every band, in band order): min of the mins and
+    max of the maxes, NaN where any band reports NaN, and the sums of mass, air and the counts in list order.
+    A pure host function: with torch.distributed the caller all-gathers the 6 n doubles of every band itself"""
+    import numpy as np
+
+    from .core import TracerStats
+
+    stats = list(stats)
+    if not stats:
+        raise ValueError("merge_tracer_stats: no records")
+    mn = np.array(stats[0].min, dtype=np.float64)
+    mx = np.array(stats[0].max, dtype=np.float64)
+    mass = np.array(stats[0].mass, dtype=np.float64)
+    air = np.array(stats[0].air, dtype=np.float64)
+    neg = np.array(stats[0].negative, dtype=np.int64)
+    nan = np.array(stats[0].nan, dtype=np.int64)
+    for s in stats[1:]:
+        if np.shape(s.min) != mn.shape:
+            raise ValueError("merge_tracer_stats: the records differ in length")
+        mn = np.minimum(mn, s.min)               # (np.minimum / np.maximum propagate NaN)
+        mx = np.maximum(mx, s.max)
+        mass = mass + s.mass
+        air = air + s.air
+        neg = neg + np.asarray(s.negative, dtype=np.int64)
+        nan = nan + np.asarray(s.nan, dtype=np.int64)
+    return TracerStats(mn, mx, mass, air, neg, nan)
+
+
 class BandRunner:
     """Steps one band; `dist` is torch.distributed (initialised) or None for 1 rank.
 

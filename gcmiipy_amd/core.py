@@ -5,6 +5,7 @@ steps, `get_state()` copies back once.  The reference-shaped drop-in functions
 (matsuno_c_grid.py, matsumo_temp.py, dynamics.py ... in this package) are thin
 wrappers that move arrays through a cached Core per call.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -46,6 +47,19 @@ def tracer_array(c, L, H, W):
     if a.shape[0] > _lib.MAX_TRACERS:
         raise ValueError("%d tracers: at most %d" % (a.shape[0], _lib.MAX_TRACERS))
     return a
+
+
+class TracerStats(collections.namedtuple("TracerStats", "min max mass air negative nan")):
+    """the device monitor of a GCM_PE25D handle's passive tracers (Core.tracer_stats): one entry per tracer, q last
+    where asked for.  min, max: NaN where the field holds a NaN; mass = sum c p dsig_k, the quantity every
+    transport scheme conserves; air = sum p dsig_k, the same number in every entry; negative, nan: int64 counts
+    of the cells < 0 and of the NaN cells"""
+    __slots__ = ()
+
+    @property
+    def mean(self):
+        """mass / air: the mass-weighted mean mixing ratio"""
+        return self.mass / self.air
 
 
 DTYPES = {"f64": _lib.F64, "f32": _lib.F32}
@@ -256,6 +270,19 @@ class Core:
         out = np.empty((self.tracer_count, self.L, self.H, self.W))
         _check(lib.gcm_get_tracers(self._h, 1 if star else 0, _ptr(out) if out.size else None), self._h)
         return out
+
+    def tracer_stats(self, star=False, with_q=False):
+        """-> TracerStats of the current tracers (star=True: those of the last predictor), reduced on the device
+        over the handle's own rows -- a band's ghost rows are never read, bands.merge_tracer_stats gives the global
+        figure; with_q adds q of the same state as the last entry.  48 bytes per entry come back
+        (gcm_tracer_stats)"""
+        n = self.tracer_count + (1 if with_q else 0)
+        out = np.empty((max(n, 1), _lib.TRACER_STATS_WORDS))
+        _check(lib.gcm_tracer_stats(self._h, 1 if star else 0, 1 if with_q else 0, _ptr(out), n * _lib.TRACER_STATS_WORDS),
+               self._h)
+        r = out[:n]
+        return TracerStats(r[:, 0].copy(), r[:, 1].copy(), r[:, 2].copy(), r[:, 3].copy(),
+                           r[:, 4].astype(np.int64), r[:, 5].astype(np.int64))
 
     def set_tracer_scheme(self, scheme):
         """the transport scheme of the passive tracers from the next stage on: "centred" (the update of q, the

@@ -652,6 +652,13 @@ int gcm_get_tracers(gcm_handle *h, int which, double *c) {
     return pe25d_get_tracers(h->pe, which, c, h->stream, &h->err);
 }
 
+int gcm_tracer_stats(gcm_handle *h, int which, int with_q, double *out, int cap) {
+    if (!h || !out) return GCM_ERR_ARG;
+    if (int rc = tracer_refusal(h, "gcm_tracer_stats")) return rc;
+    if (h->cfg.device >= 0) HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pe25d_tracer_stats(h->pe, which, with_q != 0, out, cap, h->stream, &h->err);
+}
+
 int gcm_tracer_count(const gcm_handle *h) {
     if (!h) return GCM_ERR_ARG;
     return h->pe ? pe25d_tracer_count(h->pe) : 0;

@@ -20,6 +20,7 @@
 #include <hip/hip_ext.h>
 
 #include "pe25d_dev.h"
+#include "pe25d_tracer_stats.h"
 
 namespace gcm {
 
@@ -510,6 +511,7 @@ struct Pe25d {
     bool gt_set = false;                        // gcm_set_ground was called
     double *stats_dev = nullptr;                // gcm_stats: block partials, then the area table
     std::vector<double> stats_host, area_host;
+    double *tstats_dev = nullptr;               // gcm_tracer_stats: float64 dsig [L], the records, then the workgroups' partials
     double *rad_tab = nullptr;                  // 5 x [L] level tables of the last radiation call
     double *rad_geo = nullptr;                  // coslat[Hg], sinlat[Hg], lon[W]
     double rad_key[2] = {-1.0, -1.0};           // (t_lw, t_sw) the level tables were built for
@@ -1723,6 +1725,64 @@ int pe25d_get_tracers(Pe25d *m, int which, double *c, hipStream_t s, std::string
         *err = std::string("gcm_get_tracers: ") + hipGetErrorString(e);
         return GCM_ERR_HIP;
     }
+    return GCM_OK;
+}
+
+// gcm_tracer_stats: the records of the tracers of set `which` (0 current, 1 star), then -- with_q -- of q of the same
+// state set, over the band's own rows; mass and air take p of that state set.  Includes the tracer stream, two
+// launches and one synchronisation of `s`; 48 bytes a field come back.  The buffers live in the handle.
+int pe25d_tracer_stats(Pe25d *m, int which, bool with_q, double *out, int cap, hipStream_t s, std::string *err) {
+    if (which != 0 && which != 1) {
+        *err = "gcm_tracer_stats: which must be 0 (current) or 1 (star)";
+        return GCM_ERR_ARG;
+    }
+    const int nf = m->ntr + (with_q ? 1 : 0);
+    if (cap < GCM_TRACER_STATS_WORDS * nf) {
+        *err = "gcm_tracer_stats: out holds " + std::to_string(cap) + " doubles, " + std::to_string(GCM_TRACER_STATS_WORDS * nf) +
+               " are needed (GCM_TRACER_STATS_WORDS per tracer, and for q)";
+        return GCM_ERR_ARG;
+    }
+    // the tracers' rule is gcm_get_tracers', q's is gcm_get_star's (without tracers and with q only the latter is left)
+    if (which == 1 && !m->tr_star && (m->ntr > 0 || !with_q)) {
+        *err = "gcm_tracer_stats: no predicted tracers yet";
+        return GCM_ERR_STATE;
+    }
+    if (which == 1 && with_q && !m->star_valid) {
+        *err = "gcm_tracer_stats: no predicted state yet";
+        return GCM_ERR_STATE;
+    }
+    if (nf == 0) return GCM_OK;
+    const int groups = tracer_stats_groups(m->H, m->W);
+    const size_t n_out = (size_t)GCM_TRACER_STATS_WORDS * (GCM_MAX_TRACERS + 1);
+    if (!m->tstats_dev) {
+        std::vector<double> init((size_t)m->L + n_out * (1 + (size_t)groups), 0.0);
+        std::copy(m->dsig_host.begin(), m->dsig_host.end(), init.begin());
+        if (!dev_upload<double>(m, &m->tstats_dev, init.data(), init.size())) {
+            *err = "hip: gcm_tracer_stats allocation failed";
+            return GCM_ERR_HIP;
+        }
+    }
+    pe25d_join_tracers(m, s);
+    const int set = which == 1 ? 2 : m->cur_i;
+    TracerStatsArgs a{};
+    a.tr = m->ntr > 0 ? tr_field(m, which, 0) : nullptr;
+    a.tstride = tr_stride(m);
+    a.q = m->f32 ? (const void *)m->f.st[set][GCM_Q] : (const void *)m->d.st[set][GCM_Q];
+    a.p = m->f32 ? (const void *)m->f.st[set][GCM_P] : (const void *)m->d.st[set][GCM_P];
+    a.dsig = m->tstats_dev;
+    a.out = m->tstats_dev + m->L;
+    a.part = a.out + n_out;
+    a.ntr = m->ntr; a.nf = nf; a.W = m->W; a.H = m->H; a.L = m->L;
+    launch_tracer_stats(a, m->f32, s);
+    double rec[GCM_TRACER_STATS_WORDS * (GCM_MAX_TRACERS + 1)];
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(rec, a.out, sizeof(double) * GCM_TRACER_STATS_WORDS * nf, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        *err = std::string("gcm_tracer_stats: ") + hipGetErrorString(e);
+        return GCM_ERR_HIP;
+    }
+    std::copy(rec, rec + GCM_TRACER_STATS_WORDS * nf, out);
     return GCM_OK;
 }
 

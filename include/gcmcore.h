@@ -237,6 +237,27 @@ int gcm_set_band_tracers(gcm_handle *h, int n);
  * gcm_band_tracer_rows: the depth in force (a single domain and other models: 0).                          */
 int gcm_set_band_tracer_rows(gcm_handle *h, int rows);
 int gcm_band_tracer_rows(const gcm_handle *h);
+/* The monitor of the passive tracers of GCM_PE25D, reduced on the device (fp64 and fp32 handles, single domains and
+ * latitude bands): one record of GCM_TRACER_STATS_WORDS doubles per tracer, in tracer order, and -- with_q != 0 -- one
+ * more for q, last (with n = 0 too):
+ *   min, max, mass = sum_{k,j,i} c p dsig_k, air = sum_{k,j,i} p dsig_k, the number of cells < 0, the number of NaN cells.
+ * which = 0: the current tracers, with p and q of the current state (gcm_get_state); 1: those of the last predictor
+ * (GCM_ERR_STATE where gcm_get_tracers(which = 1) gives it) with p and q of the predicted state (q: GCM_ERR_STATE
+ * where gcm_get_star gives it; with n = 0 and with_q that is the only rule).  mass is the quantity the flux-form
+ * update conserves under every scheme: the UNWEIGHTED sum -- the meridional flux divergence carries 1 / dy only and
+ * telescopes without a row weight, so an area-weighted sum drifts -- and mass / air is the mass-weighted mean mixing
+ * ratio; air is the same number in every record of a call.  Values are widened exactly from the storage type, dsig
+ * is the float64 table of gcm_config, products and sums are float64; partial sums combine in a fixed order (no
+ * atomics), so a call repeated on the same state returns the same bits.  min and max are NaN when the field holds a
+ * NaN (np.min / np.max), mass is then whatever the arithmetic gives; -0.0 and NaN are not counted as negative.
+ * The sums cover the handle's own rows: a band's ghost rows are never read, so the call is valid right after a
+ * step, and the bands' records merge into the global one (min of mins, max of maxes, sums).  The call includes the
+ * tracer stream first, as gcm_get_tracers does, synchronises once and changes nothing a later step reads; 48 bytes
+ * a record come back.  cap = the doubles `out` holds: fewer than GCM_TRACER_STATS_WORDS (n + (with_q ? 1 : 0))
+ * GCM_ERR_ARG (nothing written); n = 0 without q writes nothing and returns GCM_OK.  A null handle or `out`:
+ * GCM_ERR_ARG; other models: GCM_ERR_UNSUPPORTED.                                                            */
+#define GCM_TRACER_STATS_WORDS 6
+int gcm_tracer_stats(gcm_handle *h, int which, int with_q, double *out, int cap);
 
 /* Diagnostics the reference's drivers evaluate on the host every step
  * (SURVEY.md 8f-1); computed by device reductions, result copied to *out. */
