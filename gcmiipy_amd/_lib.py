@@ -72,6 +72,12 @@ class Physics(C.Structure):
                 ("lat", _dp), ("lon", _dp)]
 
 
+class TracerForcing(C.Structure):
+    """gcm_tracer_forcing of include/gcmcore.h"""
+    _fields_ = [("source", C.c_double), ("decay", C.c_double), ("pin_value", C.c_double),
+                ("emission", _dp), ("pin_mask", C.POINTER(C.c_ubyte))]
+
+
 _H = C.c_void_p
 # name -> (restype, argtypes); every symbol include/gcmcore.h declares
 SYMBOLS = {
@@ -145,6 +151,8 @@ SYMBOLS = {
     "gcm_band_tracer_rows": (C.c_int, [_H]),
     "gcm_set_tracer_scheme": (C.c_int, [_H, C.c_int]),
     "gcm_tracer_scheme": (C.c_int, [_H]),
+    "gcm_set_tracer_forcing": (C.c_int, [_H, C.c_int, C.POINTER(TracerForcing)]),
+    "gcm_tracer_forced": (C.c_int, [_H, C.c_int]),
 }
 
 

@@ -5,7 +5,9 @@ with (dx, tracer, kernel variant, filter, Coriolis, dtype, band placement, ensem
 state arrays are (M, H, W), and files without "opt_members" restore as one member), the passive tracers of a GCM_PE25D
 handle (key "tracers", only when it carries some; a band also stores its declared "band_tracers", files without it
 restore with 0, and its ghost-row depth "band_tracer_rows", files without it restore as 1; the tracers' transport scheme
-is the option "tracer_scheme", files without it restore as centred)
+is the option "tracer_scheme", files without it restore as centred; the tracers' forcing, Core.set_tracer_forcing, is
+stored per forced tracer i as "forcing_<i>_scalars" (source, decay, pin_value) with "forcing_<i>_emission" and
+"forcing_<i>_pin_mask" where registered, and files without these keys restore with none)
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
@@ -31,6 +33,12 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
         out["ground"] = core.get_ground()
     if core.tracer_count > 0:
         out["tracers"] = core.get_tracers()
+        for i, rec in core.tracer_forcings().items():
+            out["forcing_%d_scalars" % i] = np.asarray([rec["source"], rec["decay"], rec["pin_value"]])
+            if rec["emission"] is not None:
+                out["forcing_%d_emission" % i] = rec["emission"]
+            if rec["pin_mask"] is not None:
+                out["forcing_%d_pin_mask" % i] = np.asarray(rec["pin_mask"], dtype=np.uint8)
     for k, a in zip("puvtq", (p, u, v, t, q)):
         if a is not None:
             out["state_" + k] = a
@@ -43,8 +51,8 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 
 def load(path):
-    """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers); ground and
-    tracers are None where the file has none"""
+    """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing); ground
+    and tracers are None where the file has none, tracer_forcing {i: dict(...)} is then empty"""
     d = np.load(path, allow_pickle=False)
     L, H, W = (int(x) for x in d["shape"])
     state = {k: d["state_" + k] for k in "puvtq" if "state_" + k in d.files}
@@ -62,10 +70,19 @@ def load(path):
             a = d[f]
             opts[f[4:]] = str(a) if a.dtype.kind in "US" else (bool(a) if a.dtype.kind == "b" else
                                                                (float(a) if a.dtype.kind == "f" else int(a)))
+    forcing = {}
+    for f in d.files:
+        if f.startswith("forcing_") and f.endswith("_scalars"):
+            i = int(f.split("_")[1])
+            source, decay, pin_value = (float(x) for x in d[f])
+            key_e, key_m = "forcing_%d_emission" % i, "forcing_%d_pin_mask" % i
+            forcing[i] = dict(source=source, decay=decay, pin_value=pin_value,
+                              emission=d[key_e] if key_e in d.files else None,
+                              pin_mask=d[key_m] if key_m in d.files else None)
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
-                tracers=d["tracers"] if "tracers" in d.files else None)
+                tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing)
 
 
 def restore(path, **core_kwargs):
@@ -83,4 +100,6 @@ def restore(path, **core_kwargs):
         core.set_ground(ck["ground"])
     if ck["tracers"] is not None:
         core.set_tracers(ck["tracers"])
+        for i, rec in sorted(ck["tracer_forcing"].items()):
+            core.set_tracer_forcing(i, **rec)
     return core, ck

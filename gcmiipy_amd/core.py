@@ -142,6 +142,7 @@ class Core:
                             tracer_scheme=_lib.TRACER_NONE, band_tracer_rows=band_tracer_rows,
                             global_height=int(height if global_height is None else global_height))
         self.has_ground = False
+        self._forcing = {}                      # tracer -> the forcing record registered (set_tracer_forcing)
         cfg = _lib.Config()
         cfg.abi_version = _lib.ABI_VERSION
         cfg.model = model
@@ -263,7 +264,10 @@ class Core:
         """carry the tracers c (n, L, H, W) from now on (n = 0 or None: none); every stage advances them
         with the update of q (gcm_set_tracers).  A band: its own rows, n = the declared band_tracers"""
         a = tracer_array(c, self.L, self.H, self.W)
+        n_before = lib.gcm_tracer_count(self._h)
         _check(lib.gcm_set_tracers(self._h, a.shape[0], _ptr(a) if a.shape[0] else None), self._h)
+        if a.shape[0] != n_before:
+            self._forcing.clear()               # (another count drops the forcing: gcm_set_tracer_forcing)
 
     def get_tracers(self, star=False):
         """-> (n, L, H, W): the current tracers, or with star=True those of the last predictor"""
@@ -283,6 +287,60 @@ class Core:
         r = out[:n]
         return TracerStats(r[:, 0].copy(), r[:, 1].copy(), r[:, 2].copy(), r[:, 3].copy(),
                            r[:, 4].astype(np.int64), r[:, 5].astype(np.int64))
+
+    # -- forcing of the passive tracers (gcm_set_tracer_forcing) ---------------------------
+    def set_tracer_forcing(self, i, source=0.0, decay=0.0, emission=None, pin_mask=None, pin_value=0.0):
+        """force tracer i from the next step on, on the device, once per Matsuno step right behind the corrector:
+            c1 = c + dt * (source + emission);  c2 = c1 * exp(-decay * dt);  c = pin_value where pin_mask else c2
+        in the handle's real type, every operation rounded on its own.  source: c per second (an age-of-air clock:
+        1.0); decay >= 0 in 1 / s; emission (L, H, W) in c per second or None; pin_mask (L, H, W) bool or uint8 or
+        None: the cells held at pin_value.  A band: its own rows.  Replaces an earlier forcing of tracer i; it
+        survives set_tracers with the same count, set_tracer_scheme and set_state, and goes with set_tracers of
+        another count.  The predictor's tracers (get_tracers(star=True)) and q are never forced.  ValueError for a
+        wrong shape or value (a refused call changes nothing)"""
+        shape = (self.L, self.H, self.W)
+        e = None if emission is None else as_f64(emission, shape, "emission")
+        m = None
+        if pin_mask is not None:
+            m = np.asarray(pin_mask)
+            if m.dtype != np.bool_ and m.dtype != np.uint8:
+                raise ValueError("pin_mask must be bool or uint8, got %s" % (m.dtype,))
+            if m.shape != shape:
+                raise ValueError("pin_mask has shape %s, expected %s" % (m.shape, shape))
+            m = np.ascontiguousarray(m != 0, dtype=np.uint8)
+        rec = _lib.TracerForcing()
+        rec.source, rec.decay, rec.pin_value = float(source), float(decay), float(pin_value)
+        rec.emission = _tab(e)
+        rec.pin_mask = None if m is None else m.ctypes.data_as(C.POINTER(C.c_ubyte))
+        _check(lib.gcm_set_tracer_forcing(self._h, int(i), C.byref(rec)), self._h)
+        self._forcing[int(i)] = dict(source=rec.source, decay=rec.decay, emission=None if e is None else e.copy(),
+                                     pin_mask=None if m is None else m.astype(np.bool_), pin_value=rec.pin_value)
+
+    def clear_tracer_forcing(self, i=None):
+        """tracer i is no longer forced (None: no tracer is)"""
+        _check(lib.gcm_set_tracer_forcing(self._h, -1 if i is None else int(i), None), self._h)
+        if i is None:
+            self._forcing.clear()
+        else:
+            self._forcing.pop(int(i), None)
+
+    def tracer_forcing(self, i):
+        """-> the forcing this object registered for tracer i, dict(source, decay, emission, pin_mask, pin_value) (a
+        host copy), or None where the handle carries none (gcm_tracer_forced) -- and also None for a forcing that was
+        registered through the C call directly, of which this object holds no copy"""
+        on = lib.gcm_tracer_forced(self._h, int(i))
+        if on < 0:
+            _check(on, self._h)
+        return self._forcing.get(int(i)) if on else None
+
+    def tracer_forcings(self):
+        """-> {i: record} of every forced tracer (see tracer_forcing)"""
+        out = {}
+        for i in range(self.tracer_count if self.model == _lib.PE25D else 0):
+            r = self.tracer_forcing(i)
+            if r is not None:
+                out[i] = r
+        return out
 
     def set_tracer_scheme(self, scheme):
         """the transport scheme of the passive tracers from the next stage on: "centred" (the update of q, the

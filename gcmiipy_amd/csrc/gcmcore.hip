@@ -659,6 +659,17 @@ int gcm_tracer_stats(gcm_handle *h, int which, int with_q, double *out, int cap)
     return pe25d_tracer_stats(h->pe, which, with_q != 0, out, cap, h->stream, &h->err);
 }
 
+int gcm_set_tracer_forcing(gcm_handle *h, int tracer, const gcm_tracer_forcing *f) {
+    if (int rc = tracer_refusal(h, "gcm_set_tracer_forcing")) return rc;
+    if (h->cfg.device >= 0) HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pe25d_set_tracer_forcing(h->pe, tracer, f, h->stream, &h->err);
+}
+
+int gcm_tracer_forced(const gcm_handle *h, int tracer) {
+    if (int rc = tracer_refusal(h, "gcm_tracer_forced")) return rc;
+    return pe25d_tracer_forced(h->pe, tracer);
+}
+
 int gcm_tracer_count(const gcm_handle *h) {
     if (!h) return GCM_ERR_ARG;
     return h->pe ? pe25d_tracer_count(h->pe) : 0;

@@ -64,6 +64,9 @@ int pe25d_set_band_tracer_rows(Pe25d *m, int rows, hipStream_t s, std::string *e
 int pe25d_band_tracer_rows(const Pe25d *m);   // a band: the depth in force; a single domain: 0
 // gcm_tracer_stats: GCM_TRACER_STATS_WORDS doubles per tracer of set `which`, then per q (with_q), own rows only
 int pe25d_tracer_stats(Pe25d *m, int which, bool with_q, double *out, int cap, hipStream_t s, std::string *err);
+// gcm_set_tracer_forcing (f == nullptr: clear tracer, -1 = all) / gcm_tracer_forced
+int pe25d_set_tracer_forcing(Pe25d *m, int tracer, const gcm_tracer_forcing *f, hipStream_t s, std::string *err);
+int pe25d_tracer_forced(const Pe25d *m, int tracer);
 void pe25d_timing(Pe25d *m, std::vector<hipEvent_t> *ev, size_t *used);
 
 }  // namespace gcm

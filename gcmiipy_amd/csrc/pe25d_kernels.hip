@@ -20,6 +20,7 @@
 #include <hip/hip_ext.h>
 
 #include "pe25d_dev.h"
+#include "pe25d_tracer_force.h"
 #include "pe25d_tracer_stats.h"
 
 namespace gcm {
@@ -567,6 +568,18 @@ struct Pe25d {
     hipStream_t tr_int_stream = nullptr;
     bool tr_int_wait = false, tr_int_join = false;
     bool halo_fixed = false;                    // send / exchange buffers were registered: the message format is fixed
+    // forcing of the tracers (gcm_set_tracer_forcing, pe25d_tracer_force.h): per tracer the record and its fields on
+    // the device, own rows in the tracers' layout [j][k][i], placed within 16 bytes like the tracer's own row 0 (the
+    // wide path of the kernel); n_forced of them are registered.  Applied behind the corrector's launches (launch_tracers)
+    struct TrForce {
+        bool on = false;
+        double source = 0.0, decay = 0.0, pin_value = 0.0;
+        void *emis_alloc = nullptr, *mask_alloc = nullptr;     // what hipMalloc gave
+        void *emis = nullptr;                                  // own row 0, in T
+        unsigned char *mask = nullptr;                         // own row 0
+    };
+    TrForce force[GCM_MAX_TRACERS];
+    int n_forced = 0;
 };
 
 static_assert(sizeof(SegCopy::n) / sizeof(long) >= 2 * (GCM_NFIELDS + 1 + GCM_MAX_TRACERS),
@@ -587,6 +600,18 @@ static long tr_stride(const Pe25d *m) { return (long)(m->H + 2 * tr_ghost(m)) * 
 static char *tr_field(const Pe25d *m, int set, int f) {
     const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
     return (char *)m->tr + esz * ((size_t)(set * m->ntr + f) * tr_stride(m) + (size_t)tr_ghost(m) * m->L * m->W);
+}
+
+// forget the forcing of tracer f (f < 0: of every tracer) and free its fields; the caller has made sure that no launch
+// still reads them
+static void drop_tracer_forcing(Pe25d *m, int f) {
+    for (int i = f < 0 ? 0 : f; i < (f < 0 ? GCM_MAX_TRACERS : f + 1); ++i) {
+        Pe25d::TrForce &r = m->force[i];
+        if (r.emis_alloc) (void)hipFree(r.emis_alloc);
+        if (r.mask_alloc) (void)hipFree(r.mask_alloc);
+        if (r.on) --m->n_forced;
+        r = Pe25d::TrForce{};
+    }
 }
 
 template <typename T> static PeBufs<T> &bufs(Pe25d *m);
@@ -961,6 +986,7 @@ void pe25d_destroy(Pe25d *m) {
     }
     for (void *p : m->allocs) (void)hipFree(p);
     if (m->tr) (void)hipFree(m->tr);
+    drop_tracer_forcing(m, -1);
     delete m;
 }
 
@@ -1163,6 +1189,30 @@ static void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out
                                                                      : tracer_lim_kernel_for<T>(m->tr_scheme, nc, same);
         hipLaunchKernelGGL(kern, dim3((unsigned)((tiles + 7) / 8 * 8), (unsigned)chunks), block, 0, st, c);
         done += chunks * nc;
+    }
+    // the forcing of the step, right behind the corrector on the same stream and rows: whatever follows the tracer
+    // launch -- the events of its callers (ev_tr_int, ev_tr), a band's pack -- is queued behind this launch too
+    if (out_set != 2 && m->n_forced > 0) {
+        const long row = (long)m->L * m->W;
+        const int a0 = std::clamp(r0, 0, m->H), a1 = std::clamp(r1, a0, m->H);
+        const int b0 = std::clamp(rb0, 0, m->H), b1 = std::clamp(rb1, b0, m->H);
+        TracerForceArgsT<T> fa{};
+        fa.off0 = a0 * row; fa.n0 = (a1 - a0) * row;
+        fa.off1 = b0 * row; fa.n1 = (b1 - b0) * row;
+        fa.dt = a.dt;
+        int entries = 0;
+        for (int f = 0; f < m->ntr; ++f) {
+            const Pe25d::TrForce &r = m->force[f];
+            if (!r.on) continue;
+            TracerForceEntryT<T> &en = fa.e[entries++];
+            en.c = (T *)tr_field(m, 0, f);
+            en.emis = (const T *)r.emis;
+            en.mask = r.mask;
+            en.source = (T)r.source;
+            en.fac = (T)std::exp(-r.decay * (double)a.dt);
+            en.pin = (T)r.pin_value;
+        }
+        launch_tracer_force<T>(fa, entries, st);
     }
     m->tr_star = out_set == 2;
     if (m->aux && st == m->aux) m->tr_pending = true;
@@ -1576,6 +1626,7 @@ static int band_tracers_alloc(Pe25d *m, int n, int rows, hipStream_t s, const ch
     m->ntr = 0;
     m->tr_star = false;
     m->tr_rows = rows;
+    drop_tracer_forcing(m, -1);                  // (the fields' placement followed the old storage)
     const size_t bytes = 2 * (size_t)n * tr_stride(m) * (m->f32 ? sizeof(float) : sizeof(double));
     if (e == hipSuccess && n > 0) e = hipMalloc(&m->tr, bytes);
     if (e == hipSuccess && n > 0) e = hipMemset(m->tr, 0, bytes);
@@ -1675,6 +1726,7 @@ int pe25d_set_tracers(Pe25d *m, int n, const double *c, hipStream_t s, std::stri
         if (m->tr) e = hipFree(m->tr);
         m->tr = nullptr;
         m->ntr = 0;
+        drop_tracer_forcing(m, -1);              // (another count: the forcing went with the tracers it belonged to)
         if (e == hipSuccess && n > 0) e = hipMalloc(&m->tr, 2 * (size_t)n * cells * esz);
         if (e == hipSuccess) m->ntr = n;
     }
@@ -1726,6 +1778,82 @@ int pe25d_get_tracers(Pe25d *m, int which, double *c, hipStream_t s, std::string
         return GCM_ERR_HIP;
     }
     return GCM_OK;
+}
+
+// gcm_set_tracer_forcing: f == nullptr clears tracer `tracer` (-1: all).  Includes the tracer stream and synchronises
+// `s` first: no launch reads the fields that are replaced.  The new fields are allocated and filled before anything
+// of the handle changes, so a refused or failed call changes nothing.  The host arrays [L][H][W] are reordered to the
+// device layout [j][k][i] here (once per registration), the emission narrowed to the handle's real type.
+int pe25d_set_tracer_forcing(Pe25d *m, int tracer, const gcm_tracer_forcing *f, hipStream_t s, std::string *err) {
+    const bool clear_all = !f && tracer == -1;
+    if (!clear_all && (tracer < 0 || tracer >= m->ntr)) {
+        *err = "gcm_set_tracer_forcing: tracer must be 0 .. gcm_tracer_count - 1 (or -1 without a record: clear all)";
+        return GCM_ERR_ARG;
+    }
+    if (f && (!std::isfinite(f->source) || !std::isfinite(f->decay) || !std::isfinite(f->pin_value) || f->decay < 0.0)) {
+        *err = "gcm_set_tracer_forcing: source, decay and pin_value must be finite, decay >= 0";
+        return GCM_ERR_ARG;
+    }
+    pe25d_join_tracers(m, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        *err = std::string("gcm_set_tracer_forcing: ") + hipGetErrorString(e);
+        return GCM_ERR_HIP;
+    }
+    if (!f) {
+        drop_tracer_forcing(m, tracer);
+        return GCM_OK;
+    }
+    const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
+    const size_t W = m->W, H = m->H, L = m->L, cells = W * H * L;
+    const uintptr_t c0 = (uintptr_t)tr_field(m, 0, tracer);
+    Pe25d::TrForce r;
+    r.on = true;
+    r.source = f->source; r.decay = f->decay; r.pin_value = f->pin_value;
+    std::vector<unsigned char> host;
+    if (f->emission) {
+        host.resize(cells * esz);
+        for (size_t j = 0; j < H; ++j)
+            for (size_t k = 0; k < L; ++k) {
+                const double *src = f->emission + (k * H + j) * W;
+                const size_t d = (j * L + k) * W;
+                if (m->f32) for (size_t i = 0; i < W; ++i) ((float *)host.data())[d + i] = (float)src[i];
+                else std::copy(src, src + W, (double *)host.data() + d);
+            }
+        e = hipMalloc(&r.emis_alloc, cells * esz + 16);
+        if (e == hipSuccess) {
+            r.emis = (char *)r.emis_alloc + (c0 & 15);           // (hipMalloc aligns to 16 bytes and more)
+            e = hipMemcpy(r.emis, host.data(), cells * esz, hipMemcpyHostToDevice);
+        }
+    }
+    if (e == hipSuccess && f->pin_mask) {
+        host.resize(cells);
+        for (size_t j = 0; j < H; ++j)
+            for (size_t k = 0; k < L; ++k) {
+                const unsigned char *src = f->pin_mask + (k * H + j) * W;
+                std::copy(src, src + W, host.data() + (j * L + k) * W);
+            }
+        e = hipMalloc(&r.mask_alloc, cells + 16);
+        if (e == hipSuccess) {
+            r.mask = (unsigned char *)r.mask_alloc + ((c0 / esz) & (16 / esz - 1));
+            e = hipMemcpy(r.mask, host.data(), cells, hipMemcpyHostToDevice);
+        }
+    }
+    if (e != hipSuccess) {
+        if (r.emis_alloc) (void)hipFree(r.emis_alloc);
+        if (r.mask_alloc) (void)hipFree(r.mask_alloc);
+        *err = std::string("gcm_set_tracer_forcing: ") + hipGetErrorString(e);
+        return GCM_ERR_HIP;
+    }
+    drop_tracer_forcing(m, tracer);
+    m->force[tracer] = r;
+    ++m->n_forced;
+    return GCM_OK;
+}
+
+int pe25d_tracer_forced(const Pe25d *m, int tracer) {
+    if (tracer < 0 || tracer >= m->ntr) return GCM_ERR_ARG;
+    return m->force[tracer].on ? 1 : 0;
 }
 
 // gcm_tracer_stats: the records of the tracers of set `which` (0 current, 1 star), then -- with_q -- of q of the same

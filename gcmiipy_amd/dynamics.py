@@ -67,6 +67,14 @@ def _forget_tracers(c):
     c.set_tracer_scheme(None)
 
 
+def _apply_forcing(c, tracer_forcing):
+    """register tracer_forcing = {i: dict(source=, decay=, emission=, pin_mask=, pin_value=)} on the handle
+    (Core.set_tracer_forcing; magnitudes are taken where a value carries units)"""
+    for i, rec in (tracer_forcing or {}).items():
+        kw = {k: (v if v is None or k == "pin_mask" else strip(v)[0]) for k, v in rec.items()}
+        c.set_tracer_forcing(i, **kw)
+
+
 def _prep_tracers(tracers, geom):
     from .core import tracer_array
     vals, un = strip(tracers)
@@ -74,14 +82,18 @@ def _prep_tracers(tracers, geom):
 
 
 def matsuno_timestep(p, u, v, t, q, dt, geom, boundary_conditions=None, coriolis=False, tracers=None,
-                     tracer_scheme=None):
+                     tracer_scheme=None, tracer_forcing=None):
     """dynamics.py:230-237.  `coriolis=True` switches on the Coriolis terms the reference keeps
     behind `if False` (dynamics.py:82-92).  With a Python `boundary_conditions(sp,su,sv,st,sq,dt,geom)` hook
     the predicted state makes a host round trip between the stages (documented slow path);
     with None both stages stay on the device.  `tracers` (n, L, H, W): passive tracers advanced with
     exactly the update of q, or under `tracer_scheme` ("centred", "upwind", "van_leer": Core.set_tracer_scheme)
-    with donor-cell or van Leer limited face values; the result is then (p, u, v, t, q, tracers)."""
+    with donor-cell or van Leer limited face values; the result is then (p, u, v, t, q, tracers).
+    `tracer_forcing` {i: dict(source=, decay=, emission=, pin_mask=, pin_value=)}: tracer i's source, decay,
+    emission and pinned cells, applied on the device behind the corrector (Core.set_tracer_forcing)."""
     scheme = tracer_scheme_id(tracer_scheme)
+    if tracer_forcing and tracers is None:
+        raise ValueError("tracer_forcing needs tracers")
     base, units = _prep(p, u, v, t, q, geom)
     c = core_for(geom, coriolis=coriolis)
     c.set_state(*base)
@@ -91,6 +103,7 @@ def matsuno_timestep(p, u, v, t, q, dt, geom, boundary_conditions=None, coriolis
         if tracers is not None:
             c.set_tracer_scheme(scheme)
             c.set_tracers(tr)
+            _apply_forcing(c, tracer_forcing)
         out = _matsuno_on(c, dt, geom, units, boundary_conditions)
         if tracers is None:
             return out
@@ -114,11 +127,15 @@ def _matsuno_on(c, dt, geom, units, boundary_conditions):
     return boundary_conditions(*out, dt, geom)
 
 
-def run(p, u, v, t, q, dt, geom, steps, callback=None, every=1, tracers=None, tracer_scheme=None):
+def run(p, u, v, t, q, dt, geom, steps, callback=None, every=1, tracers=None, tracer_scheme=None,
+        tracer_forcing=None):
     """Device-resident loop: `steps` Matsuno steps with the state in HBM throughout;
     optional callback(p,u,v,t,q) every `every` steps (no_limits_2_5d.py:230-234).  `tracers`
     (n, L, H, W): passive tracers carried along, under `tracer_scheme` ("centred", "upwind", "van_leer"); the
-    result is then (p, u, v, t, q, tracers)."""
+    result is then (p, u, v, t, q, tracers).  `tracer_forcing` {i: dict(...)}: as matsuno_timestep's; the forced run
+    stays on the device for all `steps`."""
+    if tracer_forcing and tracers is None:
+        raise ValueError("tracer_forcing needs tracers")
     base, units = _prep(p, u, v, t, q, geom)
     c = Core(_lib.PE25D, geom.width, geom.height, geom.layers, geom=geom, tracer_scheme=tracer_scheme)
     try:
@@ -126,6 +143,7 @@ def run(p, u, v, t, q, dt, geom, steps, callback=None, every=1, tracers=None, tr
         if tracers is not None:
             tr, tr_unit = _prep_tracers(tracers, geom)
             c.set_tracers(tr)
+            _apply_forcing(c, tracer_forcing)
         done = 0
         while done < steps:
             n = min(every, steps - done) if callback else steps - done

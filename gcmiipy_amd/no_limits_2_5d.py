@@ -60,7 +60,7 @@ def full_timestep(p, u, v, t, q, g, dt, utc, geom, stats=STATS):
 
 
 def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=None, physics=False, tracers=None,
-              tracer_scheme=None):
+              tracer_scheme=None, tracer_forcing=None):
     """no_limits_2_5d.py:220-236 (and test_geography.py:6-23 with `bump=(j, i, metres)`): the
     state stays in HBM for all `timesteps`; STATS come from device reductions every step.
     physics=True: every step is followed by solar_timestep(t, p, g, dt, utc, geom) with utc = 0, dt, 2 dt, ...
@@ -68,7 +68,11 @@ def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=
     on the device both phases are one gcm_step (gcm_set_physics), and the returned g carries the new ground temperature.
     tracers (n, layers, height, width): passive tracers carried through every step (Core.set_tracers); their final
     values are then appended to the result.  tracer_scheme: their transport scheme, "centred" (default), "upwind" or
-    "van_leer" (Core.set_tracer_scheme); q keeps the reference's update."""
+    "van_leer" (Core.set_tracer_scheme); q keeps the reference's update.  tracer_forcing {i: dict(source=, decay=,
+    emission=, pin_mask=, pin_value=)}: tracer i's forcing, applied on the device once per step
+    (Core.set_tracer_forcing)."""
+    if tracer_forcing and tracers is None:
+        raise ValueError("tracer_forcing needs tracers")
     geom = geometry.gen_geometry(height, width, layers, sig_func=geometry.manabe_sig)
     if bump is not None:
         geom.heightmap[bump[0], bump[1]] = bump[2]
@@ -80,6 +84,8 @@ def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=
         c.set_state(p, u, v, t, q)
         if tracers is not None:
             c.set_tracers(tracers)
+            for i, rec in (tracer_forcing or {}).items():
+                c.set_tracer_forcing(i, **rec)
         if physics:
             c.set_ground(g.gt)
             c.set_physics(geom, 0.0)

@@ -258,6 +258,39 @@ int gcm_band_tracer_rows(const gcm_handle *h);
  * GCM_ERR_ARG; other models: GCM_ERR_UNSUPPORTED.                                                            */
 #define GCM_TRACER_STATS_WORDS 6
 int gcm_tracer_stats(gcm_handle *h, int which, int with_q, double *out, int cap);
+/* Forcing of one passive tracer of GCM_PE25D: a uniform source, a decay, an emission field and cells held at a value,
+ * applied on the device once per Matsuno step right behind the corrector (an operator split, as the solar step is for
+ * theta).  The corrector writes its new current value c into each own cell of a forced tracer; the forcing then
+ * computes, in the handle's real type T and with every operation rounded on its own (no fused multiply-add):
+ *   c1 = c + dt * (source + e)      e = emission at the cell, or T(0) without an emission field
+ *   c2 = c1 * fac                   fac = T(exp(-decay * dt)), exp evaluated on the host in double
+ *   c  = pinned ? T(pin_value) : c2 pinned: pin_mask is given and non-zero at the cell
+ * dt is the stage's dt in T, as the tracer kernel receives it (the exponent takes that value widened to double); fac
+ * follows a change of dt.  source and emission are in units of c per second, decay in 1 / s.  emission and pin_mask
+ * are host arrays [L][H][W] (a band: its own rows), copied to the device at the call: the caller's arrays are free
+ * afterwards.  Without a pin_mask pin_value is not used.
+ * The predictor's (star) tracers are never forced: gcm_get_tracers(which = 1) stays the plain predictor, and so do the
+ * predicted rows a band sends; the corrected edge rows are forced before they are packed, so a neighbour receives
+ * forced values, and no ghost row is ever forced locally.  gcm_set_tracers itself applies nothing: pins take effect
+ * from the first step on.  q is never forced.  Only forced tracers cost anything: one launch per corrector launch
+ * that reads and writes the forced tracers' own rows (and reads the fields a tracer registered); with no forcing
+ * registered nothing is launched and every result and timing is as before.
+ * gcm_set_tracer_forcing: registers (replaces) the forcing of tracer `tracer`; f == NULL clears it, tracer == -1
+ * with f == NULL clears every tracer's.  It includes the tracer stream first, as gcm_set_tracers does.  The forcing
+ * survives gcm_set_tracers with an unchanged count, gcm_set_tracer_scheme and gcm_set_state; it is dropped by
+ * gcm_set_tracers with another count (0 included) and by any reallocation of gcm_set_band_tracers or
+ * gcm_set_band_tracer_rows.  Errors: a null handle, a tracer outside [0, gcm_tracer_count) (tracer == -1 with a
+ * record too), a non-finite source, decay or pin_value, decay < 0: GCM_ERR_ARG; other models: GCM_ERR_UNSUPPORTED.
+ * A refused call changes nothing.
+ * gcm_tracer_forced: 1 where tracer `tracer` has a forcing registered, else 0; a null handle or a tracer outside
+ * [0, gcm_tracer_count): GCM_ERR_ARG; other models: GCM_ERR_UNSUPPORTED.                                      */
+typedef struct gcm_tracer_forcing {
+    double source, decay, pin_value;
+    const double *emission;          /* host [L][H][W] or NULL */
+    const unsigned char *pin_mask;   /* host [L][H][W] or NULL */
+} gcm_tracer_forcing;
+int gcm_set_tracer_forcing(gcm_handle *h, int tracer, const gcm_tracer_forcing *f);
+int gcm_tracer_forced(const gcm_handle *h, int tracer);
 
 /* Diagnostics the reference's drivers evaluate on the host every step
  * (SURVEY.md 8f-1); computed by device reductions, result copied to *out. */
