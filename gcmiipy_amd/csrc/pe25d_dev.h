@@ -1,5 +1,5 @@
 // Device-side definitions shared by the translation units of GCM_PE25D (pe25d_kernels.hip = host side
-// and column kernels; pe25d_k1_*.hip, pe25d_k3_*.hip, pe25d_k4_*.hip = the filter and update kernels, one
+// and column kernels, pe25d_tracers.hip = the tracers' host side; pe25d_k1_*.hip, pe25d_k3_*.hip, pe25d_k4_*.hip = the filter and update kernels, one
 // file per real type -- K4: per real type and group height -- so that they compile in parallel): kernel arguments, index helpers, the small
 // arithmetic helpers that several kernels must round identically, and the kernel pickers' declarations.
 #pragma once

@@ -1,0 +1,201 @@
+// Host side of GCM_PE25D, private to pe25d_kernels.hip (the handle, the stage orchestration, the column kernels) and
+// pe25d_tracers.hip (the passive tracers' host side): the handle and the few helpers both units use.  gcmcore.hip sees
+// pe25d_kernels.h only.
+#pragma once
+#include "pe25d_kernels.h"
+
+#include "pe25d_dev.h"
+
+namespace gcm {
+
+// Device buffers in the handle's real type T (fp64, or fp32 for the tolerance sweep).
+template <typename T>
+struct PeBufs {
+    using T2 = typename Vec2<T>::type;
+    // state sets: 0/1 ping-pong (cur = set[cur_i]), 2 = star.  [f] p,u,v,t,q; interior pointers
+    T *st[3][GCM_NFIELDS] = {};
+    T *spu = nullptr, *phi = nullptr, *pgfu = nullptr, *pit = nullptr, *pn = nullptr;
+    T *cs[3][2] = {};                           // per state set: sum_k dsig[k] u[k], sum_k dsig[k] v[k] (2-D)
+    T *part = nullptr;                          // (kMaxSeg - 1) slabs like pit
+    T *cor_u = nullptr, *cor_v = nullptr;
+    T *inv_dxj = nullptr, *inv_dxh = nullptr, *sig = nullptr, *dsig = nullptr, *inv_dsig = nullptr,
+      *sigb = nullptr, *sigt = nullptr, *heightmap = nullptr, *smul = nullptr;
+    T2 *tw = nullptr;
+};
+
+// What the handle holds for its passive tracers; pending, ev_tr, ev_tr_int and int_* are the stream protocol, pe25d_tracers.hip's alone
+struct PeTracers {
+    // passive tracers (gcm_set_tracers; a band: gcm_set_band_tracers first): 2 x n fields of (H + 2 tr_ghost(m)) x L x W
+    // in T, device layout [j][k][i] -- the current set (n fields), then the star set; a band's fields carry `rows`
+    // ghost rows a side (gcm_set_band_tracer_rows: 1, or the 2 the van Leer scheme reads), addressed from interior row
+    // 0.  The tracer kernel runs on chain B
+    // (see stage_tracers); ev_tr, recorded on `aux` behind the last tracer launch, is how the caller's stream joins that tail
+    int n = 0;
+    void *buf = nullptr;
+    int rows = 1;                               // gcm_set_band_tracer_rows: a band's tracer ghost rows per side (see tr_ghost)
+    int scheme = GCM_TRACER_NONE;               // gcm_set_tracer_scheme: the face values of the tracers' fluxes
+    bool star = false;                          // the star set holds the tracers of a predictor
+    bool pending = false;                       // a tracer launch on `aux` that the caller's stream has not joined
+    hipEvent_t ev_tr = nullptr;
+    // a band's split stage (modes 1 + 2) runs the tracers' interior rows on the third stream (see stage_tracers): ev_tr_int
+    // follows that launch; the next stage's chain B waits for it (int_wait), the caller's stream joins it (int_join)
+    hipEvent_t ev_tr_int = nullptr;
+    hipStream_t int_stream = nullptr;
+    bool int_wait = false, int_join = false;
+    // forcing of the tracers (gcm_set_tracer_forcing, pe25d_tracer_force.h): per tracer the record and its fields on
+    // the device, own rows in the tracers' layout [j][k][i], placed within 16 bytes like the tracer's own row 0 (the
+    // wide path of the kernel); n_forced of them are registered.  Applied behind the corrector's launches (launch_tracers)
+    struct Force {
+        bool on = false;
+        double source = 0.0, decay = 0.0, pin_value = 0.0;
+        void *emis_alloc = nullptr, *mask_alloc = nullptr;     // what hipMalloc gave
+        void *emis = nullptr;                                  // own row 0, in T
+        unsigned char *mask = nullptr;                         // own row 0
+    };
+    Force force[GCM_MAX_TRACERS];
+    int n_forced = 0;
+    double *stats_dev = nullptr;                // gcm_tracer_stats: float64 dsig [L], the records, then the workgroups' partials
+};
+
+struct Pe25d {
+    gcm_config cfg{};
+    int W = 0, H = 0, L = 0, Hg = 0;
+    bool wrap = true, f32 = false;
+    std::vector<void *> allocs;
+    std::vector<double> dsig_host;              // geometry.py dsig, float64 (radiation level tables)
+    std::vector<double> sig_host;               // geometry.py sig, float64
+    PeBufs<double> d;
+    PeBufs<float> f;
+    int cur_i = 0;
+    bool star_valid = false;
+    int nseg = 1;                               // level segments of K4, chosen from the band's size
+    int upd_rows = 7;                           // rows per workgroup of K4 (3 or 7)
+    int cus = 256;
+    int last_stage_set = -1;                    // state set the last half step took its stage state from (gcm_get_intermediate)
+    int ghost_ready = -1;                       // state set whose ghost rows' column sums and anchors are queued already (pe25d_prep_ghost_rows)
+    int last_unpack_set = -1;                   // state set whose ghost rows the last unpack filled (pe25d_halo_segments)
+    bool pit2d = true;                          // pit from the column sums K4 leaves (nseg == 1, row-group K4)
+    int nseg_edge = 1;                          // bands: level segments of the EDGE rows' K4 launch (see update_edges)
+    bool cs_valid[3] = {false, false, false};   // the state set's column sums belong to its winds
+    int pack_set = -1;                          // >= 0: state set gcm_halo_pack reads (step_phase)
+    double *stage3 = nullptr;                   // float64 transpose staging, host layout
+    double *exner_tab = nullptr;
+    FftPlan plan{};
+    SuperPlan cplan{};
+    double *gt = nullptr;                       // ground temperature [H + 2 ghost rows a side][W], interior row 0 (column physics)
+    bool gt_set = false;                        // gcm_set_ground was called
+    double *stats_dev = nullptr;                // gcm_stats: block partials, then the area table
+    std::vector<double> stats_host, area_host;
+    double *rad_tab = nullptr;                  // 5 x [L] level tables of the last radiation call
+    double *rad_geo = nullptr;                  // coslat[Hg], sinlat[Hg], lon[W]
+    double rad_key[2] = {-1.0, -1.0};           // (t_lw, t_sw) the level tables were built for
+    std::vector<double> rad_tab_host, rad_geo_host, rad_latlon;   // host copies (upload sources, change detection)
+    std::vector<hipEvent_t> *ev = nullptr;
+    size_t *ev_used = nullptr;
+    hipStream_t aux = nullptr;                  // second stream of a stage: chain B (K1 + pit, a band's edge rows), see half_t
+    hipStream_t aux2 = nullptr;                 // bands: third stream, K1 of the band's OWN rows (no ghost data: off the exchange chain)
+    hipEvent_t ev_cs = nullptr;                 // aux2: the own edge rows' column sums of the state just produced are in place
+    int edge_cs_set = -1;                       // state set whose own edge rows' column sums were queued on aux2 (nseg_edge > 1)
+    bool k1_split = true;                       // GCM_PE_K1_SPLIT=0: K1 of all rows behind the exchange, as in round 3
+    bool filter_no_loop = false;                // GCM_PE_FILTER_NO_LOOP (diagnostic): K1 as one workgroup per pair
+    bool k4_oddtop = true;                      // GCM_PE_K4_ODDTOP=0: K4's whole columns start on an even level
+    bool rad_generic = false;                   // GCM_PE_RAD_GENERIC (diagnostic): the LDS-parked form of the radiation kernel
+    // The events a stage's chains hand each other are signalled by the producing kernel's OWN completion
+    // (hipExtLaunchKernelGGL's stopEvent) where a kernel is what they follow: a hipEventRecord is a packet of
+    // its own behind the kernel and costs the stream 3 us (tools/micro/sync_cost.hip: 8.9 vs 5.9 us per
+    // kernel + record; with a stop event 5.95), four of them per stage on the band's long chain.
+    bool stop_events = true;                    // GCM_PE_STOP_EVENTS=0: records, as in round 3
+    hipEvent_t ev_k4 = nullptr;                 // completion of the last K4 launch on the caller's stream
+    bool k4_fork_valid = false;                 // nothing the second stream must follow was queued on the caller's stream since
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // latitude band with registered send buffers: the edge rows of a stage are updated and packed
+    // on `aux` while the interior rows run on the caller's stream (pe25d_step_phase)
+    void *send_buf[2] = {nullptr, nullptr};
+    hipEvent_t ev_a = nullptr, ev_edges = nullptr;
+    bool edges_pending = false;
+    bool edges_ev_valid = false;                // ev_edges has been recorded at least once (a wait for it means something)
+    // gcm_set_band_overlap(1) on a GCM_PE25D band: the interior rows' K4 is held back until chain B has reached the
+    // edge rows' K4 (an event recorded right in front of it), so that the edge rows' workgroups are dispatched
+    // first: they then take 15-20 us instead of the 60-70 they take when both launches race for the chip, and the
+    // pack and the exchange start that much earlier -- at the price of the ~8 us per stage the interior rows wait.
+    // Worth it where an exchange takes longer than the ~20 us of slack the edge chain has otherwise; bench.py --gpus N
+    // times both on the real ring and keeps the faster.
+    bool edges_first = false;
+    hipEvent_t ev_pre_edge = nullptr;
+    bool pre_edge_pending = false;
+    // send / exchange buffers were registered: the format of the ghost-row message, of which the tracers' count and
+    // depth are a part, is fixed
+    bool halo_fixed = false;
+    PeTracers tr;
+};
+
+template <typename T> inline PeBufs<T> &bufs(Pe25d *m);
+template <> inline PeBufs<double> &bufs<double>(Pe25d *m) { return m->d; }
+template <> inline PeBufs<float> &bufs<float>(Pe25d *m) { return m->f; }
+
+inline size_t elem_size(const Pe25d *m) { return m->f32 ? sizeof(float) : sizeof(double); }
+// field f of state set `set` in the handle's real type, at interior row 0
+inline void *state_field(const Pe25d *m, int set, int f) { return m->f32 ? (void *)m->f.st[set][f] : (void *)m->d.st[set][f]; }
+
+// a band's tracer fields: the declared ghost rows a side (gcm_set_band_tracer_rows).  One by default: pe_tracer_kernel
+// reads rows j - 1 .. j + 1 only, and so does the donor-cell scheme; the van Leer scheme reads j -+ 2 and is refused
+// on a band that declared fewer than two.  A single domain: none.  The storage, the message (tracer_halo_bytes,
+// tracer_halo_segments) and set / get all take the depth from here
+inline int tr_ghost(const Pe25d *m) { return m->wrap ? 0 : m->tr.rows; }
+// the deepest a band's tracers may be declared: what the van Leer scheme reads.  It may not exceed the state's ghost
+// depth: the edge launch of update_edges covers kGhost own rows a side, which are the rows a neighbour takes and the
+// only rows that may read tracer ghost rows
+constexpr int kTrGhostMax = 2;
+static_assert(kTrGhostMax <= kGhost, "the tracers' edge launch covers kGhost rows a side");
+inline long tr_stride(const Pe25d *m) { return (long)(m->H + 2 * tr_ghost(m)) * m->L * m->W; }
+// tracer f of set 0 (current) or 1 (star), at interior row 0
+inline char *tr_field(const Pe25d *m, int set, int f) {
+    return (char *)m->tr.buf + elem_size(m) * ((size_t)(set * m->tr.n + f) * tr_stride(m) + (size_t)tr_ghost(m) * m->L * m->W);
+}
+
+template <typename T>
+inline bool dev_upload(Pe25d *m, T **dst, const T *src, size_t count) {
+    void *d = nullptr;
+    if (hipMalloc(&d, count * sizeof(T)) != hipSuccess) return false;
+    m->allocs.push_back(d);
+    if (src && hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return false;
+    if (!src && hipMemset(d, 0, count * sizeof(T)) != hipSuccess) return false;
+    *dst = (T *)d;
+    return true;
+}
+
+// Host layout [levels][H][W], float64, <-> a device field [j][levels][i] of the handle's own rows in its real type: the
+// copy through the staging buffer and the transpose, queued on `s`; the caller synchronises (pe25d_kernels.hip)
+hipError_t field_to_device(Pe25d *m, void *dev_field, const double *host, int levels, hipStream_t s);
+hipError_t field_to_host(Pe25d *m, double *host, const void *dev_field, int levels, hipStream_t s);
+
+// One segment of a ghost-row message, appended to *c: the `rows` edge rows of one side (0 = north) of a field of H own
+// rows go to the message at *msg (pack), or the message's rows to the field's ghost rows (unpack); *msg moves on.  base =
+// the field's own row 0, words = 8-byte words a row (SegCopy moves those: rows x even W floats are a whole number of them)
+inline void halo_segment(SegCopy *c, bool pack, int side, void *base, int H, int rows, size_t words, double **msg) {
+    double *const b = (double *)base;
+    double *const edge = side == 0 ? b : b + (size_t)(H - rows) * words;
+    double *const ghost = side == 0 ? b - (size_t)rows * words : b + (size_t)H * words;
+    c->src[c->nseg] = pack ? edge : *msg;
+    c->dst[c->nseg] = pack ? *msg : ghost;
+    c->n[c->nseg++] = (long)(rows * words);
+    *msg += rows * words;
+}
+
+// ---------------------------------------------------------------- the tracers' host side (pe25d_tracers.hip)
+// the passive tracers of one stage over rows [r0, r1) and [rb0, rb1) on `st`; `a`: the stage's arguments
+template <typename T>
+void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out_set, hipStream_t st, int r0, int r1, int rb0 = 0, int rb1 = 0);
+// hazard 1 (with pe25d_join_tracers / pe25d_follow_tracers): the last stage's tracer launch on another stream may still
+// run (Stage::tr_prev); `st` must follow it before anything queued there overwrites what it reads or reads what it wrote
+bool last_tracers_in_flight(const Pe25d *m);
+void follow_last_tracers(Pe25d *m, hipStream_t st);
+// the tracer launch just queued on `st` is the stage's whole (mode 0) or interior (mode 1) launch: the next stage
+// follows it (follow_last_tracers); caller_joins: so does the caller's stream in pe25d_join_tracers
+void stage_tracers_launched(Pe25d *m, hipStream_t st, bool caller_joins);
+// a band's tracers in the ghost-row message: their bytes a side, and their segments of state set `set`
+size_t tracer_halo_bytes(const Pe25d *m);
+void tracer_halo_segments(Pe25d *m, bool pack, int side, int set, double **msg, SegCopy *c);
+void tracers_destroy(Pe25d *m);                  // pe25d_destroy: the tracers' storage, forcing and events
+
+}  // namespace gcm

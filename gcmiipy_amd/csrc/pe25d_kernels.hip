@@ -15,13 +15,9 @@
 // The zonal filter is a complex Stockham FFT in LDS: two levels of one row are packed as
 // real and imaginary part (the filter multiplier is real and symmetric in the wavenumber, so
 // it acts on both parts independently), multiplied by S[j][n] and transformed back.
-#include "pe25d_kernels.h"
+#include "pe25d_host.h"
 
 #include <hip/hip_ext.h>
-
-#include "pe25d_dev.h"
-#include "pe25d_tracer_force.h"
-#include "pe25d_tracer_stats.h"
 
 namespace gcm {
 
@@ -468,166 +464,10 @@ __global__ void pe_to_host_kernel(double *dst, const T *src, int W, int H, int L
 }
 
 // ================================================================== host side
-// Device buffers in the handle's real type T (fp64, or fp32 for the tolerance sweep).
-template <typename T>
-struct PeBufs {
-    using T2 = typename Vec2<T>::type;
-    // state sets: 0/1 ping-pong (cur = set[cur_i]), 2 = star.  [f] p,u,v,t,q; interior pointers
-    T *st[3][GCM_NFIELDS] = {};
-    T *spu = nullptr, *phi = nullptr, *pgfu = nullptr, *pit = nullptr, *pn = nullptr;
-    T *cs[3][2] = {};                           // per state set: sum_k dsig[k] u[k], sum_k dsig[k] v[k] (2-D)
-    T *part = nullptr;                          // (kMaxSeg - 1) slabs like pit
-    T *cor_u = nullptr, *cor_v = nullptr;
-    T *inv_dxj = nullptr, *inv_dxh = nullptr, *sig = nullptr, *dsig = nullptr, *inv_dsig = nullptr,
-      *sigb = nullptr, *sigt = nullptr, *heightmap = nullptr, *smul = nullptr;
-    T2 *tw = nullptr;
-};
-
-struct Pe25d {
-    gcm_config cfg{};
-    int W = 0, H = 0, L = 0, Hg = 0;
-    bool wrap = true, f32 = false;
-    std::vector<void *> allocs;
-    std::vector<double> dsig_host;              // geometry.py dsig, float64 (radiation level tables)
-    std::vector<double> sig_host;               // geometry.py sig, float64
-    PeBufs<double> d;
-    PeBufs<float> f;
-    int cur_i = 0;
-    bool star_valid = false;
-    int nseg = 1;                               // level segments of K4, chosen from the band's size
-    int upd_rows = 7;                           // rows per workgroup of K4 (3 or 7)
-    int cus = 256;
-    int last_stage_set = -1;                    // state set the last half step took its stage state from (gcm_get_intermediate)
-    int ghost_ready = -1;                       // state set whose ghost rows' column sums and anchors are queued already (pe25d_prep_ghost_rows)
-    int last_unpack_set = -1;                   // state set whose ghost rows the last unpack filled (halo_t)
-    bool pit2d = true;                          // pit from the column sums K4 leaves (nseg == 1, row-group K4)
-    int nseg_edge = 1;                          // bands: level segments of the EDGE rows' K4 launch (see update_edges)
-    bool cs_valid[3] = {false, false, false};   // the state set's column sums belong to its winds
-    int pack_set = -1;                          // >= 0: state set gcm_halo_pack reads (step_phase)
-    double *stage3 = nullptr;                   // float64 transpose staging, host layout
-    double *exner_tab = nullptr;
-    FftPlan plan{};
-    SuperPlan cplan{};
-    double *gt = nullptr;                       // ground temperature [H + 2 ghost rows a side][W], interior row 0 (column physics)
-    bool gt_set = false;                        // gcm_set_ground was called
-    double *stats_dev = nullptr;                // gcm_stats: block partials, then the area table
-    std::vector<double> stats_host, area_host;
-    double *tstats_dev = nullptr;               // gcm_tracer_stats: float64 dsig [L], the records, then the workgroups' partials
-    double *rad_tab = nullptr;                  // 5 x [L] level tables of the last radiation call
-    double *rad_geo = nullptr;                  // coslat[Hg], sinlat[Hg], lon[W]
-    double rad_key[2] = {-1.0, -1.0};           // (t_lw, t_sw) the level tables were built for
-    std::vector<double> rad_tab_host, rad_geo_host, rad_latlon;   // host copies (upload sources, change detection)
-    std::vector<hipEvent_t> *ev = nullptr;
-    size_t *ev_used = nullptr;
-    hipStream_t aux = nullptr;                  // second stream of a stage: chain B (K1 + pit, a band's edge rows), see half_t
-    hipStream_t aux2 = nullptr;                 // bands: third stream, K1 of the band's OWN rows (no ghost data: off the exchange chain)
-    hipEvent_t ev_cs = nullptr;                 // aux2: the own edge rows' column sums of the state just produced are in place
-    int edge_cs_set = -1;                       // state set whose own edge rows' column sums were queued on aux2 (nseg_edge > 1)
-    bool k1_split = true;                       // GCM_PE_K1_SPLIT=0: K1 of all rows behind the exchange, as in round 3
-    bool filter_no_loop = false;                // GCM_PE_FILTER_NO_LOOP (diagnostic): K1 as one workgroup per pair
-    bool k4_oddtop = true;                      // GCM_PE_K4_ODDTOP=0: K4's whole columns start on an even level
-    bool rad_generic = false;                   // GCM_PE_RAD_GENERIC (diagnostic): the LDS-parked form of the radiation kernel
-    // The events a stage's chains hand each other are signalled by the producing kernel's OWN completion
-    // (hipExtLaunchKernelGGL's stopEvent) where a kernel is what they follow: a hipEventRecord is a packet of
-    // its own behind the kernel and costs the stream 3 us (tools/micro/sync_cost.hip: 8.9 vs 5.9 us per
-    // kernel + record; with a stop event 5.95), four of them per stage on the band's long chain.
-    bool stop_events = true;                    // GCM_PE_STOP_EVENTS=0: records, as in round 3
-    hipEvent_t ev_k4 = nullptr;                 // completion of the last K4 launch on the caller's stream
-    bool k4_fork_valid = false;                 // nothing the second stream must follow was queued on the caller's stream since
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // latitude band with registered send buffers: the edge rows of a stage are updated and packed
-    // on `aux` while the interior rows run on the caller's stream (pe25d_step_phase)
-    void *send_buf[2] = {nullptr, nullptr};
-    hipEvent_t ev_a = nullptr, ev_edges = nullptr;
-    bool edges_pending = false;
-    bool edges_ev_valid = false;                // ev_edges has been recorded at least once (a wait for it means something)
-    // gcm_set_band_overlap(1) on a GCM_PE25D band: the interior rows' K4 is held back until chain B has reached the
-    // edge rows' K4 (an event recorded right in front of it), so that the edge rows' workgroups are dispatched
-    // first: they then take 15-20 us instead of the 60-70 they take when both launches race for the chip, and the
-    // pack and the exchange start that much earlier -- at the price of the ~8 us per stage the interior rows wait.
-    // Worth it where an exchange takes longer than the ~20 us of slack the edge chain has otherwise; bench.py --gpus N
-    // times both on the real ring and keeps the faster.
-    bool edges_first = false;
-    hipEvent_t ev_pre_edge = nullptr;
-    bool pre_edge_pending = false;
-    // passive tracers (gcm_set_tracers; a band: gcm_set_band_tracers first): 2 x ntr fields of (H + 2 tr_ghost(m)) x L x W
-    // in T, device layout [j][k][i] -- the current set (ntr fields), then the star set; a band's fields carry tr_rows
-    // ghost rows a side (gcm_set_band_tracer_rows: 1, or the 2 the van Leer scheme reads), addressed from interior row
-    // 0.  The tracer kernel runs on chain B
-    // (see stage_tracers); ev_tr, recorded on `aux` behind the last tracer launch, is how the caller's stream joins that tail
-    int ntr = 0;
-    void *tr = nullptr;
-    int tr_rows = 1;                            // gcm_set_band_tracer_rows: a band's tracer ghost rows per side (see tr_ghost)
-    int tr_scheme = GCM_TRACER_NONE;            // gcm_set_tracer_scheme: the face values of the tracers' fluxes
-    bool tr_star = false;                       // the star set holds the tracers of a predictor
-    bool tr_pending = false;                    // a tracer launch on `aux` that the caller's stream has not joined
-    hipEvent_t ev_tr = nullptr;
-    // a band's split stage (modes 1 + 2) runs the tracers' interior rows on the third stream (see stage_tracers): ev_tr_int
-    // follows that launch; the next stage's chain B waits for it (tr_int_wait), the caller's stream joins it (tr_int_join)
-    hipEvent_t ev_tr_int = nullptr;
-    hipStream_t tr_int_stream = nullptr;
-    bool tr_int_wait = false, tr_int_join = false;
-    bool halo_fixed = false;                    // send / exchange buffers were registered: the message format is fixed
-    // forcing of the tracers (gcm_set_tracer_forcing, pe25d_tracer_force.h): per tracer the record and its fields on
-    // the device, own rows in the tracers' layout [j][k][i], placed within 16 bytes like the tracer's own row 0 (the
-    // wide path of the kernel); n_forced of them are registered.  Applied behind the corrector's launches (launch_tracers)
-    struct TrForce {
-        bool on = false;
-        double source = 0.0, decay = 0.0, pin_value = 0.0;
-        void *emis_alloc = nullptr, *mask_alloc = nullptr;     // what hipMalloc gave
-        void *emis = nullptr;                                  // own row 0, in T
-        unsigned char *mask = nullptr;                         // own row 0
-    };
-    TrForce force[GCM_MAX_TRACERS];
-    int n_forced = 0;
-};
+// (the handle, struct Pe25d, and the helpers shared with the tracers' host side: pe25d_host.h)
 
 static_assert(sizeof(SegCopy::n) / sizeof(long) >= 2 * (GCM_NFIELDS + 1 + GCM_MAX_TRACERS),
               "SegCopy holds one message per side: 5 fields, the ground temperature and every tracer");
-
-// a band's tracer fields: the declared ghost rows a side (gcm_set_band_tracer_rows).  One by default: pe_tracer_kernel
-// reads rows j - 1 .. j + 1 only, and so does the donor-cell scheme; the van Leer scheme reads j -+ 2 and is refused
-// on a band that declared fewer than two.  A single domain: none.  The storage, the message (pe25d_halo_bytes, halo_t)
-// and set / get all take the depth from here
-static int tr_ghost(const Pe25d *m) { return m->wrap ? 0 : m->tr_rows; }
-// the deepest a band's tracers may be declared: what the van Leer scheme reads.  It may not exceed the state's ghost
-// depth: the edge launch of update_edges covers kGhost own rows a side, which are the rows a neighbour takes and the
-// only rows that may read tracer ghost rows
-constexpr int kTrGhostMax = 2;
-static_assert(kTrGhostMax <= kGhost, "the tracers' edge launch covers kGhost rows a side");
-static long tr_stride(const Pe25d *m) { return (long)(m->H + 2 * tr_ghost(m)) * m->L * m->W; }
-// tracer f of set 0 (current) or 1 (star), at interior row 0
-static char *tr_field(const Pe25d *m, int set, int f) {
-    const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
-    return (char *)m->tr + esz * ((size_t)(set * m->ntr + f) * tr_stride(m) + (size_t)tr_ghost(m) * m->L * m->W);
-}
-
-// forget the forcing of tracer f (f < 0: of every tracer) and free its fields; the caller has made sure that no launch
-// still reads them
-static void drop_tracer_forcing(Pe25d *m, int f) {
-    for (int i = f < 0 ? 0 : f; i < (f < 0 ? GCM_MAX_TRACERS : f + 1); ++i) {
-        Pe25d::TrForce &r = m->force[i];
-        if (r.emis_alloc) (void)hipFree(r.emis_alloc);
-        if (r.mask_alloc) (void)hipFree(r.mask_alloc);
-        if (r.on) --m->n_forced;
-        r = Pe25d::TrForce{};
-    }
-}
-
-template <typename T> static PeBufs<T> &bufs(Pe25d *m);
-template <> PeBufs<double> &bufs<double>(Pe25d *m) { return m->d; }
-template <> PeBufs<float> &bufs<float>(Pe25d *m) { return m->f; }
-
-template <typename T>
-static bool dev_upload(Pe25d *m, T **dst, const T *src, size_t count) {
-    void *d = nullptr;
-    if (hipMalloc(&d, count * sizeof(T)) != hipSuccess) return false;
-    m->allocs.push_back(d);
-    if (src && hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return false;
-    if (!src && hipMemset(d, 0, count * sizeof(T)) != hipSuccess) return false;
-    *dst = (T *)d;
-    return true;
-}
 
 // host float64 table -> device table in T
 template <typename T>
@@ -974,8 +814,6 @@ void pe25d_destroy(Pe25d *m) {
     if (m->ev_cs) (void)hipEventDestroy(m->ev_cs);
     if (m->ev_k4) (void)hipEventDestroy(m->ev_k4);
     if (m->ev_pre_edge) (void)hipEventDestroy(m->ev_pre_edge);
-    if (m->ev_tr) (void)hipEventDestroy(m->ev_tr);
-    if (m->ev_tr_int) (void)hipEventDestroy(m->ev_tr_int);
     if (m->aux2) {
         (void)hipStreamSynchronize(m->aux2);
         (void)hipStreamDestroy(m->aux2);
@@ -985,33 +823,33 @@ void pe25d_destroy(Pe25d *m) {
         (void)hipStreamDestroy(m->aux);
     }
     for (void *p : m->allocs) (void)hipFree(p);
-    if (m->tr) (void)hipFree(m->tr);
-    drop_tracer_forcing(m, -1);
+    tracers_destroy(m);
     delete m;
 }
 
 // State transfers run on the handle's stream `s` and synchronise only that stream: other handles
 // and streams of the process are not stalled.  The float64 staging buffer is reused field by field,
 // which the stream order makes safe.
-template <typename T>
-static int xfer_t(Pe25d *m, int set, bool to_dev, const double *const in[GCM_NFIELDS],
-                  double *const out[GCM_NFIELDS], hipStream_t s, std::string *err) {
-    PeBufs<T> &B = bufs<T>(m);
-    const int W = m->W, H = m->H;
+hipError_t field_to_device(Pe25d *m, void *dev_field, const double *host, int levels, hipStream_t s) {
+    const hipError_t e = hipMemcpyAsync(m->stage3, host, sizeof(double) * (size_t)m->H * m->W * levels, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return e;
+    if (m->f32) hipLaunchKernelGGL(pe_to_device_kernel<float>, dim3(1024), dim3(256), 0, s, (float *)dev_field, m->stage3, m->W, m->H, levels);
+    else hipLaunchKernelGGL(pe_to_device_kernel<double>, dim3(1024), dim3(256), 0, s, (double *)dev_field, m->stage3, m->W, m->H, levels);
+    return hipSuccess;
+}
+hipError_t field_to_host(Pe25d *m, double *host, const void *dev_field, int levels, hipStream_t s) {
+    if (m->f32) hipLaunchKernelGGL(pe_to_host_kernel<float>, dim3(1024), dim3(256), 0, s, m->stage3, (const float *)dev_field, m->W, m->H, levels);
+    else hipLaunchKernelGGL(pe_to_host_kernel<double>, dim3(1024), dim3(256), 0, s, m->stage3, (const double *)dev_field, m->W, m->H, levels);
+    return hipMemcpyAsync(host, m->stage3, sizeof(double) * (size_t)m->H * m->W * levels, hipMemcpyDeviceToHost, s);
+}
+
+static int xfer(Pe25d *m, int set, bool to_dev, const double *const in[GCM_NFIELDS],
+                double *const out[GCM_NFIELDS], hipStream_t s, std::string *err) {
     hipError_t e = hipSuccess;
     for (int f = 0; f < GCM_NFIELDS && e == hipSuccess; ++f) {
-        const void *hp = to_dev ? (const void *)in[f] : (const void *)out[f];
-        if (!hp) continue;
+        if (!(to_dev ? (const void *)in[f] : (const void *)out[f])) continue;
         const int L = f == GCM_P ? 1 : m->L;
-        const size_t bytes = sizeof(double) * (size_t)H * W * L;
-        if (to_dev) {
-            e = hipMemcpyAsync(m->stage3, in[f], bytes, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(pe_to_device_kernel<T>, dim3(1024), dim3(256), 0, s, B.st[set][f], m->stage3, W, H, L);
-        } else {
-            hipLaunchKernelGGL(pe_to_host_kernel<T>, dim3(1024), dim3(256), 0, s, m->stage3, B.st[set][f], W, H, L);
-            e = hipMemcpyAsync(out[f], m->stage3, bytes, hipMemcpyDeviceToHost, s);
-        }
+        e = to_dev ? field_to_device(m, state_field(m, set, f), in[f], L, s) : field_to_host(m, out[f], state_field(m, set, f), L, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {
@@ -1019,11 +857,6 @@ static int xfer_t(Pe25d *m, int set, bool to_dev, const double *const in[GCM_NFI
         return GCM_ERR_HIP;
     }
     return GCM_OK;
-}
-
-static int xfer(Pe25d *m, int set, bool to_dev, const double *const in[GCM_NFIELDS],
-                double *const out[GCM_NFIELDS], hipStream_t s, std::string *err) {
-    return m->f32 ? xfer_t<float>(m, set, to_dev, in, out, s, err) : xfer_t<double>(m, set, to_dev, in, out, s, err);
 }
 
 int pe25d_set(Pe25d *m, bool star, const double *p, const double *u, const double *v,
@@ -1154,70 +987,6 @@ static void prep_rows(Pe25d *m, const PeArgsT<T> &a, int stage_set, bool p2, int
     if (!m->wrap || (fresh && c.cs_rows)) launch_geopot(m, c, sb);
 }
 
-// The passive tracers of one stage (pe25d_tracer.h) over rows [r0, r1) and [rb0, rb1): base = the current tracers,
-// stage = the star set in the corrector, out = the star set in the predictor and the current set again in the
-// corrector (each cell reads its base value only at itself: in place).  Chunks of 4, then 2, then 1 tracers, one
-// launch per chunk size (blockIdx.y = chunk).  The handle's scheme picks the kernel: the centred one of
-// pe25d_tracer.h (GCM_TRACER_NONE: nothing about the launch differs) or the limited march of pe25d_tracer_lim.h.
-template <typename T>
-static void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out_set, hipStream_t st, int r0, int r1,
-                           int rb0 = 0, int rb1 = 0) {
-    const int nrows = std::max(0, r1 - r0) + std::max(0, rb1 - rb0);
-    if (nrows <= 0) return;
-    const long stride = tr_stride(m);
-    T *const cur = (T *)tr_field(m, 0, 0), *const star = (T *)tr_field(m, 1, 0);
-    TracerArgsT<T> t{};
-    t.p = a.p; t.pn = a.pn; t.sp = a.sp; t.sv = a.sv; t.spu = a.spu; t.pit = a.pit;
-    t.inv_dxj = a.inv_dxj; t.dsig = a.dsig; t.inv_dsig = a.inv_dsig; t.sigb = a.sigb;
-    t.c = cur;
-    t.sc = stage_set == 2 ? star : cur;
-    t.oc = out_set == 2 ? star : cur;
-    t.tstride = stride;
-    t.W = m->W; t.H = m->H; t.L = m->L; t.Hg = m->Hg; t.row0 = m->cfg.row0; t.wrap = a.wrap;
-    t.j0 = r0; t.j1 = std::max(r0, r1); t.jb0 = rb0; t.jb1 = std::max(rb0, rb1);
-    t.dt = a.dt; t.inv_dy = a.inv_dy;
-    const bool same = t.sc == t.c;
-    const long tiles = (long)((m->W + kTrCols - 1) / kTrCols) * ((nrows + kTrRows - 1) / kTrRows);
-    const dim3 block(kTrCols * kTrRows);
-    int done = 0;
-    for (const int nc : {4, 2, 1}) {
-        const int chunks = (m->ntr - done) / nc;
-        if (chunks == 0) continue;
-        TracerArgsT<T> c = t;
-        c.c += done * stride; c.sc += done * stride; c.oc += done * stride;
-        const TracerKernel<T> kern = m->tr_scheme == GCM_TRACER_NONE ? tracer_kernel_for<T>(nc, same)
-                                                                     : tracer_lim_kernel_for<T>(m->tr_scheme, nc, same);
-        hipLaunchKernelGGL(kern, dim3((unsigned)((tiles + 7) / 8 * 8), (unsigned)chunks), block, 0, st, c);
-        done += chunks * nc;
-    }
-    // the forcing of the step, right behind the corrector on the same stream and rows: whatever follows the tracer
-    // launch -- the events of its callers (ev_tr_int, ev_tr), a band's pack -- is queued behind this launch too
-    if (out_set != 2 && m->n_forced > 0) {
-        const long row = (long)m->L * m->W;
-        const int a0 = std::clamp(r0, 0, m->H), a1 = std::clamp(r1, a0, m->H);
-        const int b0 = std::clamp(rb0, 0, m->H), b1 = std::clamp(rb1, b0, m->H);
-        TracerForceArgsT<T> fa{};
-        fa.off0 = a0 * row; fa.n0 = (a1 - a0) * row;
-        fa.off1 = b0 * row; fa.n1 = (b1 - b0) * row;
-        fa.dt = a.dt;
-        int entries = 0;
-        for (int f = 0; f < m->ntr; ++f) {
-            const Pe25d::TrForce &r = m->force[f];
-            if (!r.on) continue;
-            TracerForceEntryT<T> &en = fa.e[entries++];
-            en.c = (T *)tr_field(m, 0, f);
-            en.emis = (const T *)r.emis;
-            en.mask = r.mask;
-            en.source = (T)r.source;
-            en.fac = (T)std::exp(-r.decay * (double)a.dt);
-            en.pin = (T)r.pin_value;
-        }
-        launch_tracer_force<T>(fa, entries, st);
-    }
-    m->tr_star = out_set == 2;
-    if (m->aux && st == m->aux) m->tr_pending = true;
-}
-
 // ---------------------------------------------------------------- one Euler stage
 // One Euler stage over rows [j0, j1): state `stage_set` -> `out_set`, base = current.
 // mode 0: everything; mode 1: K1-K3 on all rows + K4 on the two edge rows of either side (the rows
@@ -1272,7 +1041,7 @@ static Stage<T> stage_facts(Pe25d *m, int stage_set, int out_set, double dt, int
     g.edge_segs = g.split && g.p2 && m->nseg_edge > 1;
     if (mode == 2) return g;                     // (K4 of the interior rows: the rest belongs to modes 0 and 1)
     g.k1 = (m->cfg.filter && m->W > 1 && !m->filter_no_loop) ? spu_filter_loop_kernel_for<T>(m->cplan) : nullptr;
-    g.tr_prev = m->tr_int_wait;
+    g.tr_prev = last_tracers_in_flight(m);
     g.ghosts_queued = m->ghost_ready == stage_set && (!g.p2 || m->cs_valid[stage_set]);
     // A band inside gcm_band_run (the ghost rows' column sums and anchors are queued behind the unpack already):
     // K1 is row-local -- spu of row j takes su and sp of row j only, pit of row j the column sums of rows j - 1, j
@@ -1306,10 +1075,9 @@ static void chain_b_head(Pe25d *m, const Stage<T> &g) {
     // ev_a follows that launch on every path: K1 of all rows is queued on chain B behind it (send buffers: the same
     // stream; none: chain B's fork follows the caller's stream, which carried it), and the split K1's own rows on the
     // third stream wait for the fork and for ev_edges, recorded behind the pack that follows it
-    m->tr_int_wait = false;
     if (g.tr_prev) {
-        if (g.sb != m->tr_int_stream) (void)hipStreamWaitEvent(g.sb, m->ev_tr_int, 0);
-        if (g.mode == 1 && g.se != g.sb && g.se != m->tr_int_stream) (void)hipStreamWaitEvent(g.se, m->ev_tr_int, 0);
+        follow_last_tracers(m, g.sb);
+        if (g.mode == 1 && g.se != g.sb) follow_last_tracers(m, g.se);
     }
     if (g.ghosts_queued) m->ghost_ready = -1;                    // queued behind the unpack already
     else prep_rows<T>(m, g.a, g.stage_set, g.p2, g.j1, g.ext, g.sb);
@@ -1342,7 +1110,7 @@ static void chain_b_k1_pit(Pe25d *m, const Stage<T> &g) {
         // (the previous stage's edge rows: su, sp of rows 0, 1, H - 2, H - 1 -- and its tracers' edge rows, queued
         // ahead of the pack: they read spu, pit and p_n of those rows, which this K1 overwrites)
         if (m->edges_ev_valid) (void)hipStreamWaitEvent(m->aux2, m->ev_edges, 0);
-        if (g.tr_prev && m->tr_int_stream != m->aux2) (void)hipStreamWaitEvent(m->aux2, m->ev_tr_int, 0);
+        if (g.tr_prev) follow_last_tracers(m, m->aux2);
         PeArgsT<T> c = rows_of(a, j0, j1);
         c.pit_j0 = j0 + kGhost; c.pit_j1 = j1 - kGhost + 1;
         launch_k1<T>(m, g.k1, c, j1 - j0, true, m->aux2, m->ev_a);             // (ev_a: what K4 of the interior rows takes)
@@ -1369,7 +1137,7 @@ static void chain_b_k1_pit(Pe25d *m, const Stage<T> &g) {
 // ---- the passive tracers that do not belong to a band's edge rows (those: update_edges)
 template <typename T>
 static void stage_tracers(Pe25d *m, const Stage<T> &g) {
-    if (m->ntr <= 0) return;
+    if (m->tr.n <= 0) return;
     // Single domain: on chain B right behind K1 + pit and after ev_a, so that K4 on
     //      chain A never waits for them and they run beside K2a, K3 and K4.  Two invariants hold them in place:
     //      * the next stage's K1 must not overwrite spu, pit or p_n while this launch still reads them: it is
@@ -1384,11 +1152,7 @@ static void stage_tracers(Pe25d *m, const Stage<T> &g) {
     //      waits for it on the streams where it does not follow in stream order (ev_tr_int, hazard 1 in chain_b_head).
     if (g.mode == 0) {
         launch_tracers<T>(m, g.a, g.stage_set, g.out_set, g.sb, g.j0, g.j1);
-        if (!m->wrap && m->aux) {
-            (void)hipEventRecord(m->ev_tr_int, g.sb);
-            m->tr_int_stream = g.sb;
-            m->tr_int_wait = true;
-        }
+        if (!m->wrap && m->aux) stage_tracers_launched(m, g.sb, false);
     }
     // ---- a band's split stage (modes 1 + 2): the tracers' edge rows go ahead of the pack (see update_edges), the
     //      interior rows [j0 + 2, j1 - 2) here, on the third stream right behind the own rows' K1 (ev_a): off the
@@ -1400,11 +1164,7 @@ static void stage_tracers(Pe25d *m, const Stage<T> &g) {
         hipStream_t ti = m->aux2 ? m->aux2 : g.s;
         if (m->aux && !(g.split_k1 && ti == m->aux2)) (void)hipStreamWaitEvent(ti, m->ev_a, 0);   // (K1 + pit of all rows)
         launch_tracers<T>(m, g.a, g.stage_set, g.out_set, ti, g.j0 + kGhost, g.j1 - kGhost);
-        if (ti != g.s) {
-            (void)hipEventRecord(m->ev_tr_int, ti);
-            m->tr_int_stream = ti;
-            m->tr_int_wait = m->tr_int_join = true;
-        }
+        if (ti != g.s) stage_tracers_launched(m, ti, true);
     }
 }
 
@@ -1472,7 +1232,7 @@ static void update_edges(Pe25d *m, const Stage<T> &g) {
         c.nseg = m->nseg_edge;
         hipLaunchKernelGGL(pe_part_kernel<T>, dim3((unsigned)((m->W + 255) / 256) * (2 * kGhost + 2)), dim3(256), 0, se, c);
     }
-    if (m->ntr > 0) {
+    if (m->tr.n > 0) {
         // the tracers' edge rows (the rows a neighbour takes, and the rows next to them), on the stream of the edge
         // rows' K4, behind K1, pit and ev_a and ahead of the wait for K3: they fill chain B's wait.  Hazard 2: in
         // the corrector they read the star tracers' ghost rows, which the post-predictor unpack filled ahead of K1
@@ -1579,7 +1339,7 @@ static void half(Pe25d *m, int stage_set, int out_set, double dt, int j0, int j1
 // head of the next stage's chain B, where they were 17 us in front of K1.
 int pe25d_prep_ghost_rows(Pe25d *m, std::string *err) {
     if (m->wrap || !m->aux) return GCM_OK;
-    int set = m->star_valid ? 2 : m->cur_i;                      // the set the unpack has just filled (halo_t)
+    int set = m->star_valid ? 2 : m->cur_i;                      // the set the unpack has just filled (pe25d_halo_segments)
     if (m->pack_set >= 0 && m->pack_set != 2) set = m->pack_set;
     if (set != m->last_unpack_set) {
         // the two functions pick the set by the same rule; if they ever disagree the next stage would take its
@@ -1592,325 +1352,6 @@ int pe25d_prep_ghost_rows(Pe25d *m, std::string *err) {
     if (m->f32) prep_rows<float>(m, make_args<float>(m, set, set, 0.0), set, p2, m->H, 1, m->aux);      // (it picks its rows itself)
     else prep_rows<double>(m, make_args<double>(m, set, set, 0.0), set, p2, m->H, 1, m->aux);
     m->ghost_ready = set;
-    return GCM_OK;
-}
-
-void pe25d_join_tracers(Pe25d *m, hipStream_t s) {
-    if (m->tr_int_join) {                                        // (a band's interior rows on the third stream)
-        m->tr_int_join = false;
-        if (m->tr_int_stream != s) (void)hipStreamWaitEvent(s, m->ev_tr_int, 0);
-    }
-    if (!m->tr_pending) return;
-    m->tr_pending = false;
-    (void)hipEventRecord(m->ev_tr, m->aux);
-    (void)hipStreamWaitEvent(s, m->ev_tr, 0);
-}
-
-// a ghost-row pack or unpack the caller queues on `s` (gcm_halo_pack / unpack): it follows the tracer launches on
-// the second stream, which read the edge and ghost rows it moves.  (The interior rows on the third stream touch
-// neither.)  Unlike pe25d_join_tracers this leaves the caller's join to come in place.
-void pe25d_follow_tracers(Pe25d *m, hipStream_t s) {
-    if (!m->tr_pending || s == m->aux) return;
-    (void)hipEventRecord(m->ev_tr, m->aux);
-    (void)hipStreamWaitEvent(s, m->ev_tr, 0);
-}
-
-// A band's tracers anew: n fields a set with `rows` ghost rows a side, zeros (until gcm_set_tracers).  Joins the tracer
-// stream first; the count and the depth change together with the storage, or -- on a HIP error -- the band is left
-// without tracers at the depth asked for
-static int band_tracers_alloc(Pe25d *m, int n, int rows, hipStream_t s, const char *fn, std::string *err) {
-    pe25d_join_tracers(m, s);
-    hipError_t e = hipStreamSynchronize(s);
-    if (e == hipSuccess && m->tr) e = hipFree(m->tr);
-    m->tr = nullptr;
-    m->ntr = 0;
-    m->tr_star = false;
-    m->tr_rows = rows;
-    drop_tracer_forcing(m, -1);                  // (the fields' placement followed the old storage)
-    const size_t bytes = 2 * (size_t)n * tr_stride(m) * (m->f32 ? sizeof(float) : sizeof(double));
-    if (e == hipSuccess && n > 0) e = hipMalloc(&m->tr, bytes);
-    if (e == hipSuccess && n > 0) e = hipMemset(m->tr, 0, bytes);
-    if (e == hipSuccess && n > 0) m->ntr = n;
-    if (e == hipSuccess && n > 0 && m->aux && !m->ev_tr) e = hipEventCreateWithFlags(&m->ev_tr, hipEventDisableTiming);
-    if (e == hipSuccess && n > 0 && m->aux && !m->ev_tr_int) e = hipEventCreateWithFlags(&m->ev_tr_int, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        *err = std::string(fn) + ": " + hipGetErrorString(e);
-        return GCM_ERR_HIP;
-    }
-    return GCM_OK;
-}
-
-// gcm_set_band_tracers: a band's tracer count, fixed before the message size is used (zeros until gcm_set_tracers)
-int pe25d_set_band_tracers(Pe25d *m, int n, hipStream_t s, std::string *err) {
-    if (m->wrap) {
-        *err = "gcm_set_band_tracers: GCM_PE25D latitude bands only (a single domain takes gcm_set_tracers directly)";
-        return GCM_ERR_UNSUPPORTED;
-    }
-    if (n < 0 || n > GCM_MAX_TRACERS) {
-        *err = "gcm_set_band_tracers: n must be 0 .. GCM_MAX_TRACERS";
-        return GCM_ERR_ARG;
-    }
-    if (m->halo_fixed) {
-        *err = "gcm_set_band_tracers: send or exchange buffers are registered already (their size follows the count)";
-        return GCM_ERR_STATE;
-    }
-    return band_tracers_alloc(m, n, m->tr_rows, s, "gcm_set_band_tracers", err);
-}
-
-// gcm_set_band_tracer_rows: the ghost rows a side of a band's tracers, fixed before the message size is used like
-// the count.  A change of depth moves interior row 0 of every field: the tracers are allocated anew, as zeros
-int pe25d_set_band_tracer_rows(Pe25d *m, int rows, hipStream_t s, std::string *err) {
-    if (m->wrap) {
-        *err = "gcm_set_band_tracer_rows: GCM_PE25D latitude bands only (a single domain's rows wrap: no ghost rows)";
-        return GCM_ERR_UNSUPPORTED;
-    }
-    if (rows < 1 || rows > kTrGhostMax) {
-        *err = "gcm_set_band_tracer_rows: rows must be 1 .. " + std::to_string(kTrGhostMax);
-        return GCM_ERR_ARG;
-    }
-    if (m->halo_fixed) {
-        *err = "gcm_set_band_tracer_rows: send or exchange buffers are registered already (their size follows the depth)";
-        return GCM_ERR_STATE;
-    }
-    if (rows == m->tr_rows) return GCM_OK;
-    if (rows < 2 && m->tr_scheme == GCM_TRACER_VANLEER) {
-        *err = "gcm_set_band_tracer_rows: GCM_TRACER_VANLEER is in force and reads two ghost rows per side "
-               "(gcm_set_tracer_scheme first)";
-        return GCM_ERR_STATE;
-    }
-    return band_tracers_alloc(m, m->ntr, rows, s, "gcm_set_band_tracer_rows", err);
-}
-
-int pe25d_band_tracer_rows(const Pe25d *m) { return tr_ghost(m); }
-
-int pe25d_tracer_count(const Pe25d *m) { return m->ntr; }
-
-int pe25d_tracer_scheme(const Pe25d *m) { return m->tr_scheme; }
-
-// gcm_set_tracer_scheme: between steps, with or without tracers.  The scheme is read where a stage launches its
-// tracer kernels; the star tracers of an earlier predictor belong to the earlier scheme and are dropped.
-int pe25d_set_tracer_scheme(Pe25d *m, int scheme, hipStream_t s, std::string *err) {
-    // (a single domain's rows wrap through Idx; a band addresses rows j -+ 2 in its ghost rows, and the edge launch of
-    // update_edges -- own rows [0, 2) and [H - 2, H) -- is the only one that reaches them)
-    if (scheme == GCM_TRACER_VANLEER && !m->wrap && tr_ghost(m) < 2) {
-        *err = "gcm_set_tracer_scheme: GCM_TRACER_VANLEER reads two rows either side of a cell, and this latitude band's "
-               "tracers carry one ghost row per side (the message format of gcm_set_band_tracers); declare two with "
-               "gcm_set_band_tracer_rows(h, 2) before the send or exchange buffers are registered";
-        return GCM_ERR_UNSUPPORTED;
-    }
-    pe25d_join_tracers(m, s);
-    m->tr_scheme = scheme;
-    m->tr_star = false;
-    return GCM_OK;
-}
-
-int pe25d_set_tracers(Pe25d *m, int n, const double *c, hipStream_t s, std::string *err) {
-    if (!m->wrap && m->ntr == 0) {
-        *err = "gcm_set_tracers: this latitude band declared no tracers (gcm_set_band_tracers)";
-        return GCM_ERR_UNSUPPORTED;
-    }
-    if (!m->wrap && n != m->ntr) {
-        *err = "gcm_set_tracers: this latitude band declared " + std::to_string(m->ntr) +
-               " tracers (gcm_set_band_tracers); n must equal that";
-        return GCM_ERR_ARG;
-    }
-    if (n < 0 || n > GCM_MAX_TRACERS || (n > 0 && !c)) {
-        *err = "gcm_set_tracers: n must be 0 .. GCM_MAX_TRACERS, with a host array for n > 0";
-        return GCM_ERR_ARG;
-    }
-    pe25d_join_tracers(m, s);
-    const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
-    const size_t cells = (size_t)m->H * m->L * m->W;
-    hipError_t e = hipStreamSynchronize(s);                       // (the last tracer launch has ended: buffers free to go)
-    if (e == hipSuccess && n != m->ntr) {
-        if (m->tr) e = hipFree(m->tr);
-        m->tr = nullptr;
-        m->ntr = 0;
-        drop_tracer_forcing(m, -1);              // (another count: the forcing went with the tracers it belonged to)
-        if (e == hipSuccess && n > 0) e = hipMalloc(&m->tr, 2 * (size_t)n * cells * esz);
-        if (e == hipSuccess) m->ntr = n;
-    }
-    if (e == hipSuccess && n > 0 && m->aux && !m->ev_tr) e = hipEventCreateWithFlags(&m->ev_tr, hipEventDisableTiming);
-    for (int f = 0; f < n && e == hipSuccess; ++f) {
-        e = hipMemcpyAsync(m->stage3, c + (size_t)f * cells, sizeof(double) * cells, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) break;
-        if (m->f32) hipLaunchKernelGGL(pe_to_device_kernel<float>, dim3(1024), dim3(256), 0, s, (float *)tr_field(m, 0, f), m->stage3, m->W, m->H, m->L);
-        else hipLaunchKernelGGL(pe_to_device_kernel<double>, dim3(1024), dim3(256), 0, s, (double *)tr_field(m, 0, f), m->stage3, m->W, m->H, m->L);
-    }
-    // the star set starts as a copy (a corrector behind gcm_set_star, without a predictor, reads it); a band's ghost
-    // rows come with it, until the next exchange fills them
-    const size_t set_bytes = (size_t)n * tr_stride(m) * esz;
-    if (e == hipSuccess && n > 0) e = hipMemcpyAsync((char *)m->tr + set_bytes, m->tr, set_bytes, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    m->tr_star = false;
-    m->k4_fork_valid = false;                    // (the uploads on the caller's stream: the next chain B follows them)
-    if (e != hipSuccess) {
-        *err = std::string("gcm_set_tracers: ") + hipGetErrorString(e);
-        return GCM_ERR_HIP;
-    }
-    return GCM_OK;
-}
-
-int pe25d_get_tracers(Pe25d *m, int which, double *c, hipStream_t s, std::string *err) {
-    if (which != 0 && which != 1) {
-        *err = "gcm_get_tracers: which must be 0 (current) or 1 (star)";
-        return GCM_ERR_ARG;
-    }
-    if (which == 1 && !m->tr_star) {
-        *err = "gcm_get_tracers: no predicted tracers yet";
-        return GCM_ERR_STATE;
-    }
-    if (m->ntr > 0 && !c) {
-        *err = "gcm_get_tracers: no host array";
-        return GCM_ERR_ARG;
-    }
-    pe25d_join_tracers(m, s);
-    const size_t cells = (size_t)m->H * m->L * m->W;
-    hipError_t e = hipSuccess;
-    for (int f = 0; f < m->ntr && e == hipSuccess; ++f) {
-        if (m->f32) hipLaunchKernelGGL(pe_to_host_kernel<float>, dim3(1024), dim3(256), 0, s, m->stage3, (const float *)tr_field(m, which, f), m->W, m->H, m->L);
-        else hipLaunchKernelGGL(pe_to_host_kernel<double>, dim3(1024), dim3(256), 0, s, m->stage3, (const double *)tr_field(m, which, f), m->W, m->H, m->L);
-        e = hipMemcpyAsync(c + (size_t)f * cells, m->stage3, sizeof(double) * cells, hipMemcpyDeviceToHost, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        *err = std::string("gcm_get_tracers: ") + hipGetErrorString(e);
-        return GCM_ERR_HIP;
-    }
-    return GCM_OK;
-}
-
-// gcm_set_tracer_forcing: f == nullptr clears tracer `tracer` (-1: all).  Includes the tracer stream and synchronises
-// `s` first: no launch reads the fields that are replaced.  The new fields are allocated and filled before anything
-// of the handle changes, so a refused or failed call changes nothing.  The host arrays [L][H][W] are reordered to the
-// device layout [j][k][i] here (once per registration), the emission narrowed to the handle's real type.
-int pe25d_set_tracer_forcing(Pe25d *m, int tracer, const gcm_tracer_forcing *f, hipStream_t s, std::string *err) {
-    const bool clear_all = !f && tracer == -1;
-    if (!clear_all && (tracer < 0 || tracer >= m->ntr)) {
-        *err = "gcm_set_tracer_forcing: tracer must be 0 .. gcm_tracer_count - 1 (or -1 without a record: clear all)";
-        return GCM_ERR_ARG;
-    }
-    if (f && (!std::isfinite(f->source) || !std::isfinite(f->decay) || !std::isfinite(f->pin_value) || f->decay < 0.0)) {
-        *err = "gcm_set_tracer_forcing: source, decay and pin_value must be finite, decay >= 0";
-        return GCM_ERR_ARG;
-    }
-    pe25d_join_tracers(m, s);
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        *err = std::string("gcm_set_tracer_forcing: ") + hipGetErrorString(e);
-        return GCM_ERR_HIP;
-    }
-    if (!f) {
-        drop_tracer_forcing(m, tracer);
-        return GCM_OK;
-    }
-    const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
-    const size_t W = m->W, H = m->H, L = m->L, cells = W * H * L;
-    const uintptr_t c0 = (uintptr_t)tr_field(m, 0, tracer);
-    Pe25d::TrForce r;
-    r.on = true;
-    r.source = f->source; r.decay = f->decay; r.pin_value = f->pin_value;
-    std::vector<unsigned char> host;
-    if (f->emission) {
-        host.resize(cells * esz);
-        for (size_t j = 0; j < H; ++j)
-            for (size_t k = 0; k < L; ++k) {
-                const double *src = f->emission + (k * H + j) * W;
-                const size_t d = (j * L + k) * W;
-                if (m->f32) for (size_t i = 0; i < W; ++i) ((float *)host.data())[d + i] = (float)src[i];
-                else std::copy(src, src + W, (double *)host.data() + d);
-            }
-        e = hipMalloc(&r.emis_alloc, cells * esz + 16);
-        if (e == hipSuccess) {
-            r.emis = (char *)r.emis_alloc + (c0 & 15);           // (hipMalloc aligns to 16 bytes and more)
-            e = hipMemcpy(r.emis, host.data(), cells * esz, hipMemcpyHostToDevice);
-        }
-    }
-    if (e == hipSuccess && f->pin_mask) {
-        host.resize(cells);
-        for (size_t j = 0; j < H; ++j)
-            for (size_t k = 0; k < L; ++k) {
-                const unsigned char *src = f->pin_mask + (k * H + j) * W;
-                std::copy(src, src + W, host.data() + (j * L + k) * W);
-            }
-        e = hipMalloc(&r.mask_alloc, cells + 16);
-        if (e == hipSuccess) {
-            r.mask = (unsigned char *)r.mask_alloc + ((c0 / esz) & (16 / esz - 1));
-            e = hipMemcpy(r.mask, host.data(), cells, hipMemcpyHostToDevice);
-        }
-    }
-    if (e != hipSuccess) {
-        if (r.emis_alloc) (void)hipFree(r.emis_alloc);
-        if (r.mask_alloc) (void)hipFree(r.mask_alloc);
-        *err = std::string("gcm_set_tracer_forcing: ") + hipGetErrorString(e);
-        return GCM_ERR_HIP;
-    }
-    drop_tracer_forcing(m, tracer);
-    m->force[tracer] = r;
-    ++m->n_forced;
-    return GCM_OK;
-}
-
-int pe25d_tracer_forced(const Pe25d *m, int tracer) {
-    if (tracer < 0 || tracer >= m->ntr) return GCM_ERR_ARG;
-    return m->force[tracer].on ? 1 : 0;
-}
-
-// gcm_tracer_stats: the records of the tracers of set `which` (0 current, 1 star), then -- with_q -- of q of the same
-// state set, over the band's own rows; mass and air take p of that state set.  Includes the tracer stream, two
-// launches and one synchronisation of `s`; 48 bytes a field come back.  The buffers live in the handle.
-int pe25d_tracer_stats(Pe25d *m, int which, bool with_q, double *out, int cap, hipStream_t s, std::string *err) {
-    if (which != 0 && which != 1) {
-        *err = "gcm_tracer_stats: which must be 0 (current) or 1 (star)";
-        return GCM_ERR_ARG;
-    }
-    const int nf = m->ntr + (with_q ? 1 : 0);
-    if (cap < GCM_TRACER_STATS_WORDS * nf) {
-        *err = "gcm_tracer_stats: out holds " + std::to_string(cap) + " doubles, " + std::to_string(GCM_TRACER_STATS_WORDS * nf) +
-               " are needed (GCM_TRACER_STATS_WORDS per tracer, and for q)";
-        return GCM_ERR_ARG;
-    }
-    // the tracers' rule is gcm_get_tracers', q's is gcm_get_star's (without tracers and with q only the latter is left)
-    if (which == 1 && !m->tr_star && (m->ntr > 0 || !with_q)) {
-        *err = "gcm_tracer_stats: no predicted tracers yet";
-        return GCM_ERR_STATE;
-    }
-    if (which == 1 && with_q && !m->star_valid) {
-        *err = "gcm_tracer_stats: no predicted state yet";
-        return GCM_ERR_STATE;
-    }
-    if (nf == 0) return GCM_OK;
-    const int groups = tracer_stats_groups(m->H, m->W);
-    const size_t n_out = (size_t)GCM_TRACER_STATS_WORDS * (GCM_MAX_TRACERS + 1);
-    if (!m->tstats_dev) {
-        std::vector<double> init((size_t)m->L + n_out * (1 + (size_t)groups), 0.0);
-        std::copy(m->dsig_host.begin(), m->dsig_host.end(), init.begin());
-        if (!dev_upload<double>(m, &m->tstats_dev, init.data(), init.size())) {
-            *err = "hip: gcm_tracer_stats allocation failed";
-            return GCM_ERR_HIP;
-        }
-    }
-    pe25d_join_tracers(m, s);
-    const int set = which == 1 ? 2 : m->cur_i;
-    TracerStatsArgs a{};
-    a.tr = m->ntr > 0 ? tr_field(m, which, 0) : nullptr;
-    a.tstride = tr_stride(m);
-    a.q = m->f32 ? (const void *)m->f.st[set][GCM_Q] : (const void *)m->d.st[set][GCM_Q];
-    a.p = m->f32 ? (const void *)m->f.st[set][GCM_P] : (const void *)m->d.st[set][GCM_P];
-    a.dsig = m->tstats_dev;
-    a.out = m->tstats_dev + m->L;
-    a.part = a.out + n_out;
-    a.ntr = m->ntr; a.nf = nf; a.W = m->W; a.H = m->H; a.L = m->L;
-    launch_tracer_stats(a, m->f32, s);
-    double rec[GCM_TRACER_STATS_WORDS * (GCM_MAX_TRACERS + 1)];
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(rec, a.out, sizeof(double) * GCM_TRACER_STATS_WORDS * nf, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        *err = std::string("gcm_tracer_stats: ") + hipGetErrorString(e);
-        return GCM_ERR_HIP;
-    }
-    std::copy(rec, rec + GCM_TRACER_STATS_WORDS * nf, out);
     return GCM_OK;
 }
 
@@ -2035,62 +1476,8 @@ int pe25d_wait_edges(Pe25d *m, hipStream_t s, std::string *err) {
 // ghost rows: [p: 2 rows][u,v,t,q: 2 rows x L levels]; contiguous in the device layout.
 // Which state is exchanged follows the step phase: the predicted state once it exists.
 size_t pe25d_halo_bytes(const Pe25d *m) {
-    // (+ the ground temperature's two rows, float64 for either storage type: gcm_set_physics;
-    //  + a band's tracers, tr_ghost rows x L levels each: gcm_set_band_tracers, gcm_set_band_tracer_rows)
-    const size_t esz = m->f32 ? sizeof(float) : sizeof(double);
-    return esz * (size_t)kGhost * m->W * (1 + 4 * (size_t)m->L) + sizeof(double) * (size_t)kGhost * m->W +
-           (m->wrap ? 0 : esz * (size_t)m->ntr * tr_ghost(m) * m->L * m->W);
-}
-
-template <typename T>
-static void halo_t(Pe25d *m, bool pack, int side, void *dev_buf, SegCopy *c) {
-    PeBufs<T> &Bf = bufs<T>(m);
-    // unpack: ghosts of the predicted state once it exists, else of the current state;
-    // pack: the same, unless a step_phase call named the set whose edge rows were just produced
-    int set = m->star_valid ? 2 : m->cur_i;
-    if (pack && m->pack_set >= 0) set = m->pack_set;
-    if (!pack && m->pack_set >= 0 && m->pack_set != 2) set = m->pack_set;   // new-state ghosts arrive before the swap
-    if (!pack) m->last_unpack_set = set;
-    T *b = (T *)dev_buf;
-    for (int f = 0; f < GCM_NFIELDS; ++f) {
-        const size_t per_row = (size_t)m->W * (f == GCM_P ? 1 : m->L);
-        const long n = (long)(kGhost * per_row);
-        T *base = Bf.st[set][f];
-        T *edge = side == 0 ? base : base + (size_t)(m->H - kGhost) * per_row;
-        T *ghost = side == 0 ? base - (size_t)kGhost * per_row : base + (size_t)m->H * per_row;
-        // SegCopy moves 8-byte words: 2 rows x (even W) floats is a whole number of them
-        c->src[c->nseg] = (const double *)(pack ? edge : b);
-        c->dst[c->nseg] = (double *)(pack ? b : ghost);
-        c->n[c->nseg++] = n * (long)sizeof(T) / 8;
-        b += n;
-    }
-    // the ground temperature: one array for all state sets, advanced by the column physics only.  A band's
-    // ghost rows of it are radiated locally (pe25d_solar_rows), so what a message carries equals what the
-    // ghost rows hold already -- except in the first exchange after gcm_set_ground, which is what it is for.
-    {
-        double *gb = (double *)b;                 // (2 rows x even W floats: a whole number of 8-byte words)
-        const size_t n2 = (size_t)kGhost * m->W;
-        double *edge = side == 0 ? m->gt : m->gt + (size_t)(m->H - kGhost) * m->W;
-        double *ghost = side == 0 ? m->gt - n2 : m->gt + (size_t)m->H * m->W;
-        c->src[c->nseg] = pack ? edge : gb;
-        c->dst[c->nseg] = pack ? gb : ghost;
-        c->n[c->nseg++] = (long)n2;
-        b = (T *)(gb + n2);
-    }
-    // a band's tracers, one segment each: those of the state set above (star with the predicted state, else current)
-    if (!m->wrap) {
-        const int R = tr_ghost(m);
-        const size_t n = (size_t)R * m->L * m->W;             // (R rows x L x even W floats: whole 8-byte words)
-        for (int f = 0; f < m->ntr; ++f) {
-            T *base = (T *)tr_field(m, set == 2 ? 1 : 0, f);
-            T *edge = side == 0 ? base : base + (size_t)(m->H - R) * m->L * m->W;
-            T *ghost = side == 0 ? base - n : base + (size_t)m->H * m->L * m->W;
-            c->src[c->nseg] = (const double *)(pack ? edge : b);
-            c->dst[c->nseg] = (double *)(pack ? b : ghost);
-            c->n[c->nseg++] = (long)(n * sizeof(T) / 8);
-            b += n;
-        }
-    }
+    // (+ the ground temperature's two rows, float64 for either storage type: gcm_set_physics; + a band's tracers)
+    return elem_size(m) * (size_t)kGhost * m->W * (1 + 4 * (size_t)m->L) + sizeof(double) * (size_t)kGhost * m->W + tracer_halo_bytes(m);
 }
 
 // appends the copies of one side to *c (the caller launches them: one side or both in one launch)
@@ -2099,8 +1486,20 @@ int pe25d_halo_segments(Pe25d *m, bool pack, int side, void *dev_buf, SegCopy *c
         *err = "pe25d halo: fp32 bands need an even width";
         return GCM_ERR_UNSUPPORTED;
     }
-    if (m->f32) halo_t<float>(m, pack, side, dev_buf, c);
-    else halo_t<double>(m, pack, side, dev_buf, c);
+    // unpack: ghosts of the predicted state once it exists, else of the current state;
+    // pack: the same, unless a step_phase call named the set whose edge rows were just produced
+    int set = m->star_valid ? 2 : m->cur_i;
+    if (pack && m->pack_set >= 0) set = m->pack_set;
+    if (!pack && m->pack_set >= 0 && m->pack_set != 2) set = m->pack_set;   // new-state ghosts arrive before the swap
+    if (!pack) m->last_unpack_set = set;
+    double *msg = (double *)dev_buf;
+    for (int f = 0; f < GCM_NFIELDS; ++f)
+        halo_segment(c, pack, side, state_field(m, set, f), m->H, kGhost, (size_t)m->W * (f == GCM_P ? 1 : m->L) * elem_size(m) / 8, &msg);
+    // the ground temperature: one array for all state sets, advanced by the column physics only.  A band's
+    // ghost rows of it are radiated locally (pe25d_solar_rows), so what a message carries equals what the
+    // ghost rows hold already -- except in the first exchange after gcm_set_ground, which is what it is for.
+    halo_segment(c, pack, side, m->gt, m->H, kGhost, (size_t)m->W, &msg);
+    tracer_halo_segments(m, pack, side, set, &msg, c);
     return GCM_OK;
 }
 
@@ -2115,12 +1514,10 @@ template <typename T>
 static int filter_field_t(Pe25d *m, int nlev, const double *in, double *out, hipStream_t s, std::string *err) {
     PeBufs<T> &B = bufs<T>(m);
     const int W = m->W, H = m->H;
-    const size_t bytes = sizeof(double) * (size_t)nlev * H * W;
     m->last_stage_set = -1;                      // spu, pgfu and pit are scratch here: the parity tap has nothing to return
     m->k4_fork_valid = false;
-    hipError_t e = hipMemcpyAsync(m->stage3, in, bytes, hipMemcpyHostToDevice, s);
+    hipError_t e = field_to_device(m, B.pgfu, in, nlev, s);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pe_to_device_kernel<T>, dim3(1024), dim3(256), 0, s, B.pgfu, m->stage3, W, H, nlev);
         hipLaunchKernelGGL(pe_fill_kernel<T>, dim3(256), dim3(256), 0, s, B.pit, (long)H * W, T(1.0));
         PeArgsT<T> a = make_args<T>(m, m->cur_i, m->cur_i, 0.0);
         a.L = nlev;
@@ -2133,8 +1530,7 @@ static int filter_field_t(Pe25d *m, int nlev, const double *in, double *out, hip
         const int fft_threads = m->cplan.ok ? m->cplan.threads : kFftThreads;
         hipLaunchKernelGGL(spu_filter_kernel_for<T>(m->cplan), dim3(H, (nlev + 1) / 2), dim3(fft_threads),
                            filter_lds_bytes<T>(m), s, a);
-        hipLaunchKernelGGL(pe_to_host_kernel<T>, dim3(1024), dim3(256), 0, s, m->stage3, B.spu, W, H, nlev);
-        e = hipMemcpyAsync(out, m->stage3, bytes, hipMemcpyDeviceToHost, s);
+        e = field_to_host(m, out, B.spu, nlev, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipGetLastError();
@@ -2242,7 +1638,7 @@ static int radiation_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1,
                             double hour_angle, double albedo, double *dTdt_host, double *dtg_host, hipStream_t s,
                             std::string *err) {
     PeBufs<T> &B = bufs<T>(m);
-    const int W = m->W, H = m->H, L = m->L, Hg = m->Hg;
+    const int W = m->W, L = m->L, Hg = m->Hg;
     const int nrows = std::max(0, j1 - j0) + std::max(0, jb1 - jb0);
     if (nrows <= 0) return GCM_OK;
     PeArgsT<T> a = make_args<T>(m, set, set, dt);
@@ -2274,18 +1670,8 @@ static int radiation_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1,
     }
     if (hipGetLastError() != hipSuccess) { *err = "hip: radiation kernel launch failed"; return GCM_ERR_HIP; }
     // solar_timestep (apply) stays asynchronous on `s`; the diagnostics form copies its results back
-    if (dtg_host) {
-        hipLaunchKernelGGL(pe_to_host_kernel<T>, dim3(64), dim3(256), 0, s, m->stage3, B.pit, W, H, 1);
-        if (hipMemcpyAsync(dtg_host, m->stage3, sizeof(double) * (size_t)H * W, hipMemcpyDeviceToHost, s) != hipSuccess) {
-            *err = "hip: dt_ground copy-back failed"; return GCM_ERR_HIP;
-        }
-    }
-    if (dTdt_host) {
-        hipLaunchKernelGGL(pe_to_host_kernel<T>, dim3(1024), dim3(256), 0, s, m->stage3, B.pgfu, W, H, L);
-        if (hipMemcpyAsync(dTdt_host, m->stage3, sizeof(double) * (size_t)H * W * L, hipMemcpyDeviceToHost, s) != hipSuccess) {
-            *err = "hip: dTdt copy-back failed"; return GCM_ERR_HIP;
-        }
-    }
+    if (dtg_host && field_to_host(m, dtg_host, B.pit, 1, s) != hipSuccess) { *err = "hip: dt_ground copy-back failed"; return GCM_ERR_HIP; }
+    if (dTdt_host && field_to_host(m, dTdt_host, B.pgfu, L, s) != hipSuccess) { *err = "hip: dTdt copy-back failed"; return GCM_ERR_HIP; }
     if ((dtg_host || dTdt_host) && hipStreamSynchronize(s) != hipSuccess) {
         *err = "hip: radiation kernel failed"; return GCM_ERR_HIP;
     }
@@ -2447,7 +1833,7 @@ void pe25d_tv_shape(const Pe25d *m, int field, long *n_outer, long *n_axis, long
 const void *pe25d_field(Pe25d *m, int field, long *n, int *f32) {
     *n = (long)m->H * m->W * (field == GCM_P ? 1 : m->L);
     *f32 = m->f32 ? 1 : 0;
-    return m->f32 ? (const void *)m->f.st[m->cur_i][field] : (const void *)m->d.st[m->cur_i][field];
+    return state_field(m, m->cur_i, field);
 }
 
 void pe25d_timing(Pe25d *m, std::vector<hipEvent_t> *ev, size_t *used) {

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kTrCols * kTrRows) void pe_tracer_kernel(TracerArgs
     }
 }
 
-// chunks of nc = 4, 2 or 1 tracers (pe25d_kernels.hip, launch_tracers); instantiated in pe25d_tracer_f{64,32}.hip
+// chunks of nc = 4, 2 or 1 tracers (pe25d_tracers.hip, launch_tracers); instantiated in pe25d_tracer_f{64,32}.hip
 template <typename T>
 TracerKernel<T> tracer_kernel_for(int nc, bool same) {
     if (nc == 4) return same ? pe_tracer_kernel<T, 4, true> : pe_tracer_kernel<T, 4, false>;

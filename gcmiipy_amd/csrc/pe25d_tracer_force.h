@@ -1,5 +1,5 @@
 // Forcing of the passive tracers of GCM_PE25D (gcm_set_tracer_forcing): host-visible interface of
-// pe25d_tracer_force.hip, used by pe25d_kernels.hip (launch_tracers).
+// pe25d_tracer_force.hip, used by pe25d_tracers.hip (launch_tracers).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -174,7 +174,7 @@ static TracerKernel<T> tracer_lim_kernel_of(int nc, bool same) {
     return same ? pe_tracer_lim_kernel<T, SCHEME, 1, true> : pe_tracer_lim_kernel<T, SCHEME, 1, false>;
 }
 
-// scheme = GCM_TRACER_UPWIND or GCM_TRACER_VANLEER, chunks of nc = 4, 2 or 1 tracers (pe25d_kernels.hip,
+// scheme = GCM_TRACER_UPWIND or GCM_TRACER_VANLEER, chunks of nc = 4, 2 or 1 tracers (pe25d_tracers.hip,
 // launch_tracers); instantiated in pe25d_tracer_lim_f{64,32}.hip
 template <typename T>
 TracerKernel<T> tracer_lim_kernel_for(int scheme, int nc, bool same) {

@@ -1,5 +1,5 @@
 // Device monitor of the passive tracers (and q) of GCM_PE25D: host-visible interface of pe25d_tracer_stats.hip,
-// used by pe25d_kernels.hip (pe25d_tracer_stats).
+// used by pe25d_tracers.hip (pe25d_tracer_stats).
 #pragma once
 #include <hip/hip_runtime.h>
 

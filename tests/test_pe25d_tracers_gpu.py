@@ -284,3 +284,71 @@ def test_tracer_refusals(g):
     c.set_tracers(None)
     assert c.tracer_count == 0 and c.get_tracers().shape == (0, L, H, W)
     c.close()
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_resizing_the_tracer_set_on_one_handle(g, dtype):
+    """one single-domain handle through 2 forced tracers -> 3 -> the same 3 again -> none: another count takes new
+    storage and drops the forcing, the same count keeps both, and at every point the tracers are bit for bit those of
+    a fresh handle given the same inputs; after n = 0 the state steps as on a handle that never had tracers"""
+    lib = g._lib.lib
+    L, H, W = 3, 8, 16
+    geom = _geom(H, W, L)
+    rng = np.random.default_rng(31)
+    emis = 1e-3 * rng.random((L, H, W))
+    pin = np.zeros((L, H, W), dtype=bool)
+    pin[0, 2:4, 5:9] = True
+    force = dict(source=0.5, decay=1e-4, emission=emis, pin_mask=pin, pin_value=3.0)
+    tr2, tr3, tr3b = (1.0 + rng.random((n, L, H, W)) for n in (2, 3, 3))
+
+    def fresh(state, tracers, forced):
+        """-> (tracers as set, tracers and state after one step) of a new handle"""
+        f = g.Core(g._lib.PE25D, W, H, L, geom=geom, dtype=dtype)
+        f.set_state(*state)
+        if tracers is not None:
+            f.set_tracers(tracers)
+        if forced is not None:
+            f.set_tracer_forcing(forced, **force)
+        at_set = f.get_tracers()
+        f.step(1, 60.0)
+        out = at_set, f.get_tracers(), f.get_state()
+        f.close()
+        return out
+
+    c = g.Core(g._lib.PE25D, W, H, L, geom=geom, dtype=dtype)
+    st = _state(H, W, L, 30, geom)
+    c.set_state(*st)
+    c.set_tracers(tr2)
+    c.set_tracer_forcing(1, **force)
+    assert [lib.gcm_tracer_forced(c._h, i) for i in range(2)] == [0, 1]
+    want = fresh(st, tr2, 1)
+    assert np.array_equal(c.get_tracers(), want[0])
+    c.step(1, 60.0)
+    assert np.array_equal(c.get_tracers(), want[1])
+    # another count: new storage, and the forcing went with the old tracers
+    st = c.get_state()
+    c.set_tracers(tr3)
+    assert c.tracer_count == 3 and [lib.gcm_tracer_forced(c._h, i) for i in range(3)] == [0, 0, 0]
+    want = fresh(st, tr3, None)
+    assert np.array_equal(c.get_tracers(), want[0])
+    c.step(1, 60.0)
+    assert np.array_equal(c.get_tracers(), want[1])
+    # the same count: the storage and a forcing registered in between stay
+    st = c.get_state()
+    c.set_tracer_forcing(2, **force)
+    c.set_tracers(tr3b)
+    assert c.tracer_count == 3 and [lib.gcm_tracer_forced(c._h, i) for i in range(3)] == [0, 0, 1]
+    want = fresh(st, tr3b, 2)
+    assert np.array_equal(c.get_tracers(), want[0])
+    c.step(1, 60.0)
+    assert np.array_equal(c.get_tracers(), want[1])
+    assert not np.array_equal(want[1][2], fresh(st, tr3b, None)[1][2])     # (the forcing does act at this size)
+    # none: the state goes on as on a handle that never had tracers
+    st = c.get_state()
+    c.set_tracers(None)
+    assert c.tracer_count == 0 and c.get_tracers().shape == (0, L, H, W)
+    assert lib.gcm_tracer_forced(c._h, 0) == g._lib.ERR_ARG
+    c.step(1, 60.0)
+    for a, b in zip(c.get_state(), fresh(st, None, None)[2]):
+        assert np.array_equal(a, b)
+    c.close()

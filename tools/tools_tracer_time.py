@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 
 
 def chunks(n):
-    """launches of the tracer kernel per stage are chunks of 4, then 2, then 1 tracers (pe25d_kernels.hip,
+    """launches of the tracer kernel per stage are chunks of 4, then 2, then 1 tracers (pe25d_tracers.hip,
     launch_tracers): the number of chunks"""
     return n // 4 + (n % 4) // 2 + n % 2
 
