@@ -1,6 +1,6 @@
 // Host side of GCM_PE25D, private to pe25d_kernels.hip (the handle, the stage orchestration, the column kernels) and
-// pe25d_tracers.hip (the passive tracers' host side): the handle and the few helpers both units use.  gcmcore.hip sees
-// pe25d_kernels.h only.
+// pe25d_tracers.hip (the passive tracers' host side): the handle and the few helpers both units use.  gcmcore.hip, gcm_band.hip
+// and gcm_diag.hip see pe25d_kernels.h only.
 #pragma once
 #include "pe25d_kernels.h"
 

@@ -1,5 +1,5 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
-// pe25d_kernels.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip.
+// pe25d_kernels.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip and gcm_diag.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -702,3 +702,86 @@ def test_band_run_chains_at_overlapping_size(dtype, phys, monkeypatch):
         for part, (ga, wa) in enumerate(zip(got, want)):
             for k, a, b in zip("puvtqg", ga, wa):
                 assert np.array_equal(a, b), (env, part, k, rel_err(a, b))
+
+
+def _ic_small(model, shape, seed):
+    """a state of the 2-D model `model` ("temp": GCM_SW2D_TEMP with its tracer, "sw2d": GCM_SW2D)"""
+    rng = np.random.default_rng(seed)
+    f = dict(u=rng.standard_normal(shape), v=rng.standard_normal(shape))
+    if model == "sw2d":
+        f["p"] = 8000 + rng.standard_normal(shape)
+    else:
+        f.update(p=101325 + rng.standard_normal(shape), t=273.16 + rng.standard_normal(shape), q=rng.random(shape))
+    return f
+
+
+def _single_and_loopback_band(model, variant, halo, overlap, H, W):
+    """-> (periodic single handle, band handle that is its own neighbour, its native BandRunner)"""
+    import torch
+    import gcmiipy_amd as g
+    from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange
+    var = g._lib.VARIANT_FUSED if variant == "fused" else g._lib.VARIANT_STAGED
+    if model == "sw2d":
+        mk = lambda **kw: g.Core(g._lib.SW2D, W, H, dx=300e3, variant=var, **kw)
+    else:
+        mk = lambda **kw: g.Core(g._lib.SW2D_TEMP, W, H, dx=300e3, tracer=g._lib.TRACER_VANLEER, variant=var, **kw)
+    ref = mk()
+    c = mk(nranks=2, rank=0, global_height=H, row0=0, stream=torch.cuda.current_stream().cuda_stream, halo_steps=halo)
+    runner = BandRunner(HipBandEngine(c, torch), 0, 2, LoopbackExchange(), north=0, south=0)
+    assert runner.native
+    c.set_band_overlap(overlap)
+    return ref, c, runner
+
+
+def _assert_same_state(c, ref):
+    import torch
+    torch.cuda.synchronize()
+    for k, a, b in zip("puvtq", c.get_state(), ref.get_state()):
+        assert (a is None and b is None) or np.array_equal(a, b), k
+
+
+@pytest.mark.parametrize("halo,overlap", [(1, False), (4, False), (4, True)])
+@pytest.mark.parametrize("model,variant", [("temp", "staged"), ("sw2d", "fused")])
+def test_band_run_staged_and_sw2d_equal_single_domain(model, variant, halo, overlap):
+    """gcm_band_run (loopback exchange) on the staged variant and on the model without temperature, under each 2-D
+    orchestration: an exchange per step, the deep halo on the compute stream, the deep halo hidden behind interior
+    rows.  H = 24 is just above the overlap threshold H > 2 G + 2 kGhost = 20 of G = 8; W = 66 is even and no power
+    of two.  11 steps cut so that runs end inside a window, at its end and at its start; bit for bit the single
+    periodic handle."""
+    H, W, dt = 24, 66, 300.0
+    ref, c, runner = _single_and_loopback_band(model, variant, halo, overlap, H, W)
+    ic = _ic_small(model, (H, W), 31)
+    ref.set_state(**ic)
+    c.set_state(**ic)
+    for n in (1, 2, 3, 5):
+        runner.run(n, dt)
+        for _ in range(n):                  # one step per launch, as a band steps (GCM_SW2D pairs steps otherwise)
+            ref.step(1, dt)
+    _assert_same_state(c, ref)
+    c.close()
+    ref.close()
+
+
+@pytest.mark.parametrize("change", ["set_state", "restore"])
+def test_band_run_state_change_in_mid_window(change):
+    """halo_steps = 4 with the exchange hidden behind interior rows: a new state in the middle of a window --
+    gcm_set_state after 2 steps, or gcm_restore of the snapshot taken after 2 steps once 3 more are done -- makes
+    gcm_band_run exchange that state's ghost rows first and start a window on them (primed, inflight,
+    since_exchange).  The single periodic handle does the same sequence with gcm_step; bit for bit."""
+    H, W, dt = 24, 66, 300.0
+    ref, c, runner = _single_and_loopback_band("temp", "fused", 4, True, H, W)
+    ic = _ic_small("temp", (H, W), 32)
+    both = ((c, lambda n: runner.run(n, dt)), (ref, lambda n: ref.step(n, dt)))
+    for core, run in both:
+        core.set_state(**ic)
+        run(2)
+        if change == "set_state":
+            core.set_state(**_ic_small("temp", (H, W), 33))
+        else:
+            core.snapshot()
+            run(3)
+            core.restore()
+        run(6)
+    _assert_same_state(c, ref)
+    c.close()
+    ref.close()

@@ -162,6 +162,42 @@ def test_diag_members_match_numpy(g):
     c.close()
 
 
+def test_diag_members_match_single_handles(g):
+    """every DIAG_* kind of every member of an fp32 ensemble against gcm_diag of a one-member handle holding that
+    member's state: max, min and any-NaN are the same values (==); sums and total variations are added up by a
+    different number of workgroups per member on the two paths, so both are held to the float64 NumPy figure of the
+    fp32-rounded state within 1e-12 (the bound of test_diag_members_match_numpy)"""
+    W, H, M = 34, 16, 3
+    model, tracer, L = g._lib.SW2D_TEMP, g._lib.TRACER_UPWIND, g._lib
+    s = _states(model, tracer, M, H, W, seed=17)
+    s["u"][1, 5, 7] = np.nan                                   # one member with a NaN: any-NaN, max and min follow it
+    c = g.Core(model, W, H, dx=DX, tracer=tracer, members=M, dtype="f32")
+    c.set_state(**s)
+    r = dict(zip("puvtq", c.get_state()))                      # the fp32-rounded state, widened
+
+    def tv(x):
+        return np.abs(x - np.roll(x, -1, axis=0)).sum()
+
+    exact = (L.DIAG_ANY_NAN, L.DIAG_MAX_U, L.DIAG_MIN_U, L.DIAG_MAX_V, L.DIAG_MIN_V)
+    close = {L.DIAG_MEAN_P: lambda m: r["p"][m].mean(), L.DIAG_SUM_P: lambda m: r["p"][m].sum(),
+             L.DIAG_TV_P: lambda m: tv(r["p"][m]), L.DIAG_TV_U: lambda m: tv(r["u"][m]), L.DIAG_TV_V: lambda m: tv(r["v"][m]),
+             L.DIAG_TV_T: lambda m: tv(r["t"][m]), L.DIAG_TV_Q: lambda m: tv(r["q"][m])}
+    ens = {k: c.diag_members(k) for k in exact + tuple(close)}
+    c.close()
+    for m in range(M):
+        one = g.Core(model, W, H, dx=DX, tracer=tracer, dtype="f32")
+        one.set_state(**_member(s, m))
+        for k in exact:
+            a, b = ens[k][m], one.diag(k)
+            assert a == b or (np.isnan(a) and np.isnan(b)), (m, k, a, b)
+        for k, f in close.items():
+            want = f(m)
+            for got in (ens[k][m], one.diag(k)):
+                assert (np.isnan(want) and np.isnan(got)) or abs(got - want) <= 1e-12 * abs(want), (m, k, got, want)
+        one.close()
+    assert ens[L.DIAG_ANY_NAN].tolist() == [0.0, 1.0, 0.0]
+
+
 def test_state_entry_points(g):
     W, H, M = 97, 61, 3
     model, L = g._lib.SW2D_TEMP, g._lib
