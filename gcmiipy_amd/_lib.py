@@ -153,6 +153,9 @@ SYMBOLS = {
     "gcm_tracer_scheme": (C.c_int, [_H]),
     "gcm_set_tracer_forcing": (C.c_int, [_H, C.c_int, C.POINTER(TracerForcing)]),
     "gcm_tracer_forced": (C.c_int, [_H, C.c_int]),
+    "gcm_set_tracer_mixing": (C.c_int, [_H, C.c_int, _dp, C.c_int]),
+    "gcm_tracer_mixed": (C.c_int, [_H, C.c_int]),
+    "gcm_tracer_mixing_coeffs": (C.c_int, [C.c_int, _dp, _dp, C.c_double, _dp, _dp, _dp]),
 }
 
 

@@ -7,7 +7,9 @@ handle (key "tracers", only when it carries some; a band also stores its declare
 restore with 0, and its ghost-row depth "band_tracer_rows", files without it restore as 1; the tracers' transport scheme
 is the option "tracer_scheme", files without it restore as centred; the tracers' forcing, Core.set_tracer_forcing, is
 stored per forced tracer i as "forcing_<i>_scalars" (source, decay, pin_value) with "forcing_<i>_emission" and
-"forcing_<i>_pin_mask" where registered, and files without these keys restore with none)
+"forcing_<i>_pin_mask" where registered, and files without these keys restore with none; their vertical mixing,
+Core.set_tracer_mixing, is stored per mixed tracer i as "mixing_<i>", the float64 profile K of L - 1 values, and files
+without the key restore with none)
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
@@ -39,6 +41,8 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
                 out["forcing_%d_emission" % i] = rec["emission"]
             if rec["pin_mask"] is not None:
                 out["forcing_%d_pin_mask" % i] = np.asarray(rec["pin_mask"], dtype=np.uint8)
+        for i, k in core.tracer_mixings().items():
+            out["mixing_%d" % i] = np.asarray(k, dtype=np.float64)
     for k, a in zip("puvtq", (p, u, v, t, q)):
         if a is not None:
             out["state_" + k] = a
@@ -51,8 +55,9 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 
 def load(path):
-    """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing); ground
-    and tracers are None where the file has none, tracer_forcing {i: dict(...)} is then empty"""
+    """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
+    tracer_mixing); ground and tracers are None where the file has none, tracer_forcing {i: dict(...)} and
+    tracer_mixing {i: K} are then empty"""
     d = np.load(path, allow_pickle=False)
     L, H, W = (int(x) for x in d["shape"])
     state = {k: d["state_" + k] for k in "puvtq" if "state_" + k in d.files}
@@ -79,10 +84,12 @@ def load(path):
             forcing[i] = dict(source=source, decay=decay, pin_value=pin_value,
                               emission=d[key_e] if key_e in d.files else None,
                               pin_mask=d[key_m] if key_m in d.files else None)
+    mixing = {int(f.split("_")[1]): d[f] for f in d.files if f.startswith("mixing_")}
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
-                tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing)
+                tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
+                tracer_mixing=mixing)
 
 
 def restore(path, **core_kwargs):
@@ -102,4 +109,6 @@ def restore(path, **core_kwargs):
         core.set_tracers(ck["tracers"])
         for i, rec in sorted(ck["tracer_forcing"].items()):
             core.set_tracer_forcing(i, **rec)
+        for i, k in sorted(ck["tracer_mixing"].items()):
+            core.set_tracer_mixing(i, k)
     return core, ck

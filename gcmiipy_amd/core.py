@@ -143,6 +143,7 @@ class Core:
                             global_height=int(height if global_height is None else global_height))
         self.has_ground = False
         self._forcing = {}                      # tracer -> the forcing record registered (set_tracer_forcing)
+        self._mixing = {}                       # tracer -> the profile K registered (set_tracer_mixing)
         cfg = _lib.Config()
         cfg.abi_version = _lib.ABI_VERSION
         cfg.model = model
@@ -268,6 +269,7 @@ class Core:
         _check(lib.gcm_set_tracers(self._h, a.shape[0], _ptr(a) if a.shape[0] else None), self._h)
         if a.shape[0] != n_before:
             self._forcing.clear()               # (another count drops the forcing: gcm_set_tracer_forcing)
+            self._mixing.clear()                # (and the mixing: gcm_set_tracer_mixing)
 
     def get_tracers(self, star=False):
         """-> (n, L, H, W): the current tracers, or with star=True those of the last predictor"""
@@ -340,6 +342,44 @@ class Core:
             r = self.tracer_forcing(i)
             if r is not None:
                 out[i] = r
+        return out
+
+    # -- implicit vertical mixing of the passive tracers (gcm_set_tracer_mixing) --------------
+    def set_tracer_mixing(self, i, k):
+        """mix tracer i in the column from the next step on, on the device, once per Matsuno step behind the corrector
+        and in front of the forcing: backward-Euler diffusion of the mixing ratio in sigma with zero flux at the top
+        and the bottom.  k (L - 1,): the diffusivity at the interface between levels m and m + 1 in sigma^2 / s,
+        finite and >= 0, the same in every column (all zeros: the identity).  Replaces an earlier profile of tracer i;
+        the life cycle is the forcing's.  The predictor's tracers (get_tracers(star=True)) and q are never mixed.
+        ValueError for a wrong shape or value (a refused call changes nothing)"""
+        a = as_f64(k, (self.L - 1,), "k")
+        _check(lib.gcm_set_tracer_mixing(self._h, int(i), _tab(a), a.shape[0]), self._h)
+        self._mixing[int(i)] = a.copy()
+
+    def clear_tracer_mixing(self, i=None):
+        """tracer i is no longer mixed (None: no tracer is)"""
+        _check(lib.gcm_set_tracer_mixing(self._h, -1 if i is None else int(i), None, 0), self._h)
+        if i is None:
+            self._mixing.clear()
+        else:
+            self._mixing.pop(int(i), None)
+
+    def tracer_mixing(self, i):
+        """-> the profile K (L - 1,) this object registered for tracer i (a host copy), or None where the handle
+        carries none (gcm_tracer_mixed) -- and also None for a profile that was registered through the C call
+        directly, of which this object holds no copy"""
+        on = lib.gcm_tracer_mixed(self._h, int(i))
+        if on < 0:
+            _check(on, self._h)
+        return self._mixing.get(int(i)) if on else None
+
+    def tracer_mixings(self):
+        """-> {i: K} of every mixed tracer (see tracer_mixing)"""
+        out = {}
+        for i in range(self.tracer_count if self.model == _lib.PE25D else 0):
+            k = self.tracer_mixing(i)
+            if k is not None:
+                out[i] = k
         return out
 
     def set_tracer_scheme(self, scheme):

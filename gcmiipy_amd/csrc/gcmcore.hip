@@ -554,6 +554,21 @@ int gcm_tracer_forced(const gcm_handle *h, int tracer) {
     return pe25d_tracer_forced(h->pe, tracer);
 }
 
+int gcm_set_tracer_mixing(gcm_handle *h, int tracer, const double *k, int nk) {
+    if (int rc = pe_only(h, "gcm_set_tracer_mixing")) return rc;
+    if (int rc = select_device(h)) return rc;
+    return pe25d_set_tracer_mixing(h->pe, tracer, k, nk, h->stream, &h->err);
+}
+
+int gcm_tracer_mixed(const gcm_handle *h, int tracer) {
+    if (int rc = pe_only(h, "gcm_tracer_mixed")) return rc;
+    return pe25d_tracer_mixed(h->pe, tracer);
+}
+
+int gcm_tracer_mixing_coeffs(int L, const double *dsig, const double *k, double dtd, double *lo, double *w, double *g) {
+    return tracer_mixing_coeffs(L, dsig, k, dtd, lo, w, g, &gcm_create_error());
+}
+
 int gcm_tracer_count(const gcm_handle *h) {
     if (!h) return GCM_ERR_ARG;
     return h->pe ? pe25d_tracer_count(h->pe) : 0;

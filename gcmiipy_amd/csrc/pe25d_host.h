@@ -54,6 +54,25 @@ struct PeTracers {
     };
     Force force[GCM_MAX_TRACERS];
     int n_forced = 0;
+    // implicit vertical mixing of the tracers (gcm_set_tracer_mixing, pe25d_tracer_mix.h): per tracer the float64
+    // profile K [L - 1] (empty: not mixed); n_mixed of them are registered.  The kernel's tables -- lo, w, g [L] in the
+    // handle's real type per mixed tracer, in tracer order -- are built for one dt (dt_built, valid with `built`) and
+    // built again when a stage comes with another, into the other of the two device buffers (an earlier launch on
+    // another stream may still read the first); ev_tab follows the upload on tab_stream, and the other streams of a
+    // stage wait for it once (waited).  Applied behind the corrector's launches, ahead of the forcing (launch_tracers)
+    struct Mix {
+        std::vector<double> k[GCM_MAX_TRACERS];
+        int n_mixed = 0;
+        void *tab[2] = {nullptr, nullptr};
+        int cur = 0;
+        bool built = false;
+        double dt_built = 0.0;
+        hipEvent_t ev_tab = nullptr;
+        hipStream_t tab_stream = nullptr;
+        hipStream_t waited[4] = {};
+        int n_waited = 0;
+    };
+    Mix mix;
     double *stats_dev = nullptr;                // gcm_tracer_stats: float64 dsig [L], the records, then the workgroups' partials
 };
 
@@ -196,6 +215,6 @@ void stage_tracers_launched(Pe25d *m, hipStream_t st, bool caller_joins);
 // a band's tracers in the ghost-row message: their bytes a side, and their segments of state set `set`
 size_t tracer_halo_bytes(const Pe25d *m);
 void tracer_halo_segments(Pe25d *m, bool pack, int side, int set, double **msg, SegCopy *c);
-void tracers_destroy(Pe25d *m);                  // pe25d_destroy: the tracers' storage, forcing and events
+void tracers_destroy(Pe25d *m);                  // pe25d_destroy: the tracers' storage, forcing, mixing and events
 
 }  // namespace gcm

@@ -67,6 +67,11 @@ int pe25d_tracer_stats(Pe25d *m, int which, bool with_q, double *out, int cap, h
 // gcm_set_tracer_forcing (f == nullptr: clear tracer, -1 = all) / gcm_tracer_forced
 int pe25d_set_tracer_forcing(Pe25d *m, int tracer, const gcm_tracer_forcing *f, hipStream_t s, std::string *err);
 int pe25d_tracer_forced(const Pe25d *m, int tracer);
+// gcm_set_tracer_mixing (k == nullptr: clear tracer, -1 = all) / gcm_tracer_mixed
+int pe25d_set_tracer_mixing(Pe25d *m, int tracer, const double *k, int nk, hipStream_t s, std::string *err);
+int pe25d_tracer_mixed(const Pe25d *m, int tracer);
+// gcm_tracer_mixing_coeffs (pe25d_tracer_mix.hip; no handle, no device): the tables gcm_set_tracer_mixing's launches take too
+int tracer_mixing_coeffs(int L, const double *dsig, const double *k, double dtd, double *lo, double *w, double *g, std::string *err);
 void pe25d_timing(Pe25d *m, std::vector<hipEvent_t> *ev, size_t *used);
 
 }  // namespace gcm

@@ -3,6 +3,7 @@
 // here (the device side: pe25d_tracer*.h); where a launch sits in a stage is the orchestration's business (pe25d_kernels.hip).
 #include "pe25d_host.h"
 #include "pe25d_tracer_force.h"
+#include "pe25d_tracer_mix.h"
 #include "pe25d_tracer_stats.h"
 
 namespace gcm {
@@ -15,6 +16,51 @@ static int hip_status(hipError_t e, const char *fn, std::string *err) {
 }
 
 // ---------------------------------------------------------------- the launches of one stage
+// The vertical mixing of the step (pe25d_tracer_mix.h) on `st` over own rows [a0, a1) and [b0, b1), for the mixed
+// tracers.  The tables belong to one dt: a stage with another builds them again on the host (tracer_mixing_coeffs, the
+// routine behind gcm_tracer_mixing_coeffs), rounds them to T and sends them in the arguments of small launches on `st`,
+// into the buffer the last tables did not use.  A corrector launch on another stream of the same stage waits for
+// that upload (ev_tab); the launches of the step before ended before this stage's could start (hazard 1).
+template <typename T>
+static void launch_mixing(Pe25d *m, T dt, hipStream_t st, int a0, int a1, int b0, int b1) {
+    PeTracers::Mix &x = m->tr.mix;
+    const int L = m->L;
+    const double dtd = (double)dt;
+    if (!x.built || dtd != x.dt_built) {
+        std::vector<double> lo(L), w(L), g(L);
+        std::vector<T> tab;
+        std::string err;
+        for (int f = 0; f < m->tr.n; ++f) {
+            if (x.k[f].empty()) continue;
+            // (K was checked at the registration: the routine refuses nothing here)
+            (void)tracer_mixing_coeffs(L, m->dsig_host.data(), x.k[f].data(), dtd, lo.data(), w.data(), g.data(), &err);
+            for (const std::vector<double> *v : {&lo, &w, &g})
+                for (int k = 0; k < L; ++k) tab.push_back((T)(*v)[k]);
+        }
+        x.cur ^= 1;
+        T *const dst = (T *)x.tab[x.cur];
+        for (size_t at = 0; at < tab.size(); at += kTmFillMax)
+            launch_tracer_mix_fill<T>(dst + at, tab.data() + at, (int)std::min<size_t>(kTmFillMax, tab.size() - at), st);
+        if (x.ev_tab) (void)hipEventRecord(x.ev_tab, st);
+        x.tab_stream = st;
+        x.n_waited = 0;
+        x.built = true;
+        x.dt_built = dtd;
+    }
+    if (st != x.tab_stream && x.ev_tab && std::find(x.waited, x.waited + x.n_waited, st) == x.waited + x.n_waited) {
+        (void)hipStreamWaitEvent(st, x.ev_tab, 0);
+        if (x.n_waited < 4) x.waited[x.n_waited++] = st;
+    }
+    TracerMixArgsT<T> ma{};
+    int entries = 0;
+    for (int f = 0; f < m->tr.n; ++f)
+        if (!x.k[f].empty()) ma.c[entries++] = (T *)tr_field(m, 0, f);
+    ma.tab = (const T *)x.tab[x.cur];
+    ma.W = m->W; ma.L = L;
+    ma.j0 = a0; ma.n0 = a1 - a0; ma.jb0 = b0; ma.n1 = b1 - b0;
+    launch_tracer_mix<T>(ma, entries, st);
+}
+
 // The passive tracers of one stage (pe25d_tracer.h) over rows [r0, r1) and [rb0, rb1): base = the current tracers,
 // stage = the star set in the corrector, out = the star set in the predictor and the current set again in the
 // corrector (each cell reads its base value only at itself: in place).  Chunks of 4, then 2, then 1 tracers, one
@@ -50,12 +96,14 @@ void launch_tracers(Pe25d *m, const PeArgsT<T> &a, int stage_set, int out_set, h
         hipLaunchKernelGGL(kern, dim3((unsigned)((tiles + 7) / 8 * 8), (unsigned)chunks), block, 0, st, c);
         done += chunks * nc;
     }
-    // the forcing of the step, right behind the corrector on the same stream and rows: whatever follows the tracer
-    // launch -- the events of its callers (ev_tr_int, ev_tr), a band's pack -- is queued behind this launch too
+    // the vertical mixing and then the forcing of the step, right behind the corrector on the same stream and own
+    // rows: whatever follows the tracer launch -- the events of its callers (ev_tr_int, ev_tr), a band's pack -- is
+    // queued behind these launches too
+    const int a0 = std::clamp(r0, 0, m->H), a1 = std::clamp(r1, a0, m->H);
+    const int b0 = std::clamp(rb0, 0, m->H), b1 = std::clamp(rb1, b0, m->H);
+    if (out_set != 2 && m->tr.mix.n_mixed > 0) launch_mixing<T>(m, a.dt, st, a0, a1, b0, b1);
     if (out_set != 2 && m->tr.n_forced > 0) {
         const long row = (long)m->L * m->W;
-        const int a0 = std::clamp(r0, 0, m->H), a1 = std::clamp(r1, a0, m->H);
-        const int b0 = std::clamp(rb0, 0, m->H), b1 = std::clamp(rb1, b0, m->H);
         TracerForceArgsT<T> fa{};
         fa.off0 = a0 * row; fa.n0 = (a1 - a0) * row;
         fa.off1 = b0 * row; fa.n1 = (b1 - b0) * row;
@@ -135,11 +183,22 @@ static void drop_tracer_forcing(Pe25d *m, int f) {
     }
 }
 
-// the fields and their forcing go (no launch still reads them): the handle is without tracers
+// forget the mixing of tracer f (f < 0: of every tracer); the tables are built anew at the next launch
+static void drop_tracer_mixing(Pe25d *m, int f) {
+    PeTracers::Mix &x = m->tr.mix;
+    for (int i = f < 0 ? 0 : f; i < (f < 0 ? GCM_MAX_TRACERS : f + 1); ++i) {
+        if (!x.k[i].empty()) --x.n_mixed;
+        x.k[i].clear();
+    }
+    x.built = false;
+}
+
+// the fields, their forcing and their mixing go (no launch still reads them): the handle is without tracers
 static hipError_t tracers_free(Pe25d *m) {
     const hipError_t e = m->tr.buf ? hipFree(m->tr.buf) : hipSuccess;
     m->tr.buf = nullptr; m->tr.n = 0; m->tr.star = false;
     drop_tracer_forcing(m, -1);                  // (the fields' placement followed the tracers' storage)
+    drop_tracer_mixing(m, -1);                   // (the same life cycle)
     return e;
 }
 
@@ -169,6 +228,7 @@ static int tracers_alloc(Pe25d *m, int n, int rows, hipStream_t s, const char *f
 void tracers_destroy(Pe25d *m) {
     if (m->tr.ev_tr) (void)hipEventDestroy(m->tr.ev_tr);
     if (m->tr.ev_tr_int) (void)hipEventDestroy(m->tr.ev_tr_int);
+    if (m->tr.mix.ev_tab) (void)hipEventDestroy(m->tr.mix.ev_tab);
     (void)tracers_free(m);
 }
 
@@ -348,6 +408,58 @@ int pe25d_set_tracer_forcing(Pe25d *m, int tracer, const gcm_tracer_forcing *f, 
 int pe25d_tracer_forced(const Pe25d *m, int tracer) {
     if (tracer < 0 || tracer >= m->tr.n) return GCM_ERR_ARG;
     return m->tr.force[tracer].on ? 1 : 0;
+}
+
+// ---------------------------------------------------------------- vertical mixing
+// gcm_set_tracer_mixing: k == nullptr clears tracer `tracer` (-1: all).  Includes the tracer stream and synchronises
+// `s` first, as the forcing does: no launch reads the tables that go out of use.  Everything is checked, and the two
+// table buffers and their event exist, before anything of the handle changes: a refused or failed call changes nothing.
+// The handle keeps K in float64; the tables follow at the next corrector (launch_mixing)
+int pe25d_set_tracer_mixing(Pe25d *m, int tracer, const double *k, int nk, hipStream_t s, std::string *err) {
+    const bool clear_all = !k && tracer == -1;
+    if (!clear_all && (tracer < 0 || tracer >= m->tr.n)) {
+        *err = "gcm_set_tracer_mixing: tracer must be 0 .. gcm_tracer_count - 1 (or -1 without a profile: clear all)";
+        return GCM_ERR_ARG;
+    }
+    if (k) {
+        if (m->L < 2) { *err = "gcm_set_tracer_mixing: one level has no interface to mix across (layers must be 2 or more)"; return GCM_ERR_ARG; }
+        if (nk != m->L - 1) {
+            *err = "gcm_set_tracer_mixing: nk must be layers - 1 = " + std::to_string(m->L - 1) + " (K at the interfaces between levels)";
+            return GCM_ERR_ARG;
+        }
+        // (the routine's own checks: the same refusals, before anything changes)
+        std::vector<double> lo(m->L), w(m->L), g(m->L);
+        std::string why;
+        if (tracer_mixing_coeffs(m->L, m->dsig_host.data(), k, 0.0, lo.data(), w.data(), g.data(), &why) != GCM_OK) {
+            *err = "gcm_set_tracer_mixing: K must be finite and >= 0 at every interface";
+            return GCM_ERR_ARG;
+        }
+    }
+    pe25d_join_tracers(m, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_status(e, "gcm_set_tracer_mixing", err);
+    if (!k) {
+        drop_tracer_mixing(m, tracer);
+        return GCM_OK;
+    }
+    PeTracers::Mix &x = m->tr.mix;
+    const size_t tab_bytes = (size_t)GCM_MAX_TRACERS * 3 * m->L * elem_size(m);
+    for (void *&t : x.tab)
+        if (!t && !dev_upload<char>(m, (char **)&t, nullptr, tab_bytes)) {
+            *err = "hip: gcm_set_tracer_mixing allocation failed";
+            return GCM_ERR_HIP;
+        }
+    if (!x.ev_tab && (e = hipEventCreateWithFlags(&x.ev_tab, hipEventDisableTiming)) != hipSuccess)
+        return hip_status(e, "gcm_set_tracer_mixing", err);
+    if (x.k[tracer].empty()) ++x.n_mixed;
+    x.k[tracer].assign(k, k + nk);
+    x.built = false;
+    return GCM_OK;
+}
+
+int pe25d_tracer_mixed(const Pe25d *m, int tracer) {
+    if (tracer < 0 || tracer >= m->tr.n) return GCM_ERR_ARG;
+    return m->tr.mix.k[tracer].empty() ? 0 : 1;
 }
 
 // ---------------------------------------------------------------- monitor

@@ -291,6 +291,45 @@ typedef struct gcm_tracer_forcing {
 } gcm_tracer_forcing;
 int gcm_set_tracer_forcing(gcm_handle *h, int tracer, const gcm_tracer_forcing *f);
 int gcm_tracer_forced(const gcm_handle *h, int tracer);
+/* Implicit vertical mixing of one passive tracer of GCM_PE25D: backward-Euler diffusion of the mixing ratio in sigma,
+ * zero flux at the top and the bottom, with a horizontally uniform profile K[m], m = 0 .. L - 2: the diffusivity at the
+ * interface between levels m and m + 1 in sigma^2 / s (float64, finite, >= 0).  Applied on the device once per Matsuno
+ * step, behind the corrector and IN FRONT OF the forcing above (corrector, mixing, forcing): pinned cells hold their
+ * value at the end of a step, and what a surface emission adds in step n is mixed in step n + 1.  Pins are not
+ * boundary conditions of the solve.
+ * The coefficients are float64, computed on the host, every operation rounded on its own, in this order (dsig: the
+ * table of gcm_config; dtd: the stage's dt in the handle's real type T, widened to double, as for the forcing's fac):
+ *   a[-1] = a[L-1] = 0;   a[m] = dtd * K[m] / (0.5 * (dsig[m] + dsig[m+1]))
+ *   lo[k] = a[k-1] / dsig[k];   up[k] = a[k] / dsig[k];   d = 1.0 + lo[k] + up[k]
+ *   w[0]  = 1.0 / d;            w[k] = 1.0 / (d - lo[k] * g[k-1])   (k >= 1)
+ *   g[k]  = up[k] * w[k]
+ * lo, w and g are then rounded to T, and each own column c[0 .. L) of a mixed tracer is solved in T, again with every
+ * operation rounded on its own (no fused multiply-add):
+ *   y[0] = c[0] * w[0];       y[k] = (c[k] + lo[k] * y[k-1]) * w[k]     k = 1 .. L-1
+ *   x[L-1] = y[L-1];          x[k] = y[k] + g[k] * x[k+1]               k = L-2 .. 0;      c = x
+ * All coefficients are >= 0: a non-negative column stays non-negative.  sum_k c dsig of a column, and with it the
+ * monitor's mass, is conserved up to rounding.  Backward Euler is stable for every dt.  An all-zero K is legal and is
+ * launched: the identity on finite columns.
+ * The predictor's (star) tracers are never mixed, no ghost row is ever mixed locally (a band's corrected edge rows are
+ * mixed, then forced, before they are packed), q is never mixed.  Only mixed tracers cost anything: one launch per
+ * corrector launch that reads and writes their own rows once; with no mixing registered nothing is launched and every
+ * result and timing is as before.  The handle keeps K in float64 and builds the tables in T again when a stage comes
+ * with another dt than the one they were built for, not on every step.
+ * gcm_set_tracer_mixing: registers (replaces) the profile of tracer `tracer`, nk = L - 1 values; k == NULL clears it,
+ * tracer == -1 with k == NULL clears every tracer's.  It includes the tracer stream first, as gcm_set_tracer_forcing
+ * does, and has the forcing's life cycle: it survives gcm_set_tracers with an unchanged count, gcm_set_tracer_scheme and
+ * gcm_set_state; it is dropped by gcm_set_tracers with another count (0 included) and by any reallocation of
+ * gcm_set_band_tracers or gcm_set_band_tracer_rows.  Errors: a null handle, a tracer outside [0, gcm_tracer_count)
+ * (tracer == -1 with a k too), nk != L - 1, a non-finite or negative K, L = 1: GCM_ERR_ARG; other models:
+ * GCM_ERR_UNSUPPORTED.  A refused call changes nothing.
+ * gcm_tracer_mixed: 1 where tracer `tracer` has a profile registered, else 0; errors as gcm_tracer_forced.
+ * gcm_tracer_mixing_coeffs: the coefficient routine above on its own, without a handle or a device -- the routine
+ * gcm_set_tracer_mixing's launches take their tables from.  lo, w, g [L] are float64, not yet rounded to T.  Errors
+ * (GCM_ERR_ARG, message: gcm_last_error(NULL)): L < 2, a null pointer, a non-finite or negative K.              */
+int gcm_set_tracer_mixing(gcm_handle *h, int tracer, const double *k, int nk);
+int gcm_tracer_mixed(const gcm_handle *h, int tracer);
+int gcm_tracer_mixing_coeffs(int L, const double *dsig, const double *k, double dtd,
+                             double *lo, double *w, double *g);
 
 /* Diagnostics the reference's drivers evaluate on the host every step
  * (SURVEY.md 8f-1); computed by device reductions, result copied to *out. */
