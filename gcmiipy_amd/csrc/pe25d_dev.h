@@ -1,5 +1,6 @@
-// Device-side definitions shared by the translation units of GCM_PE25D (pe25d_kernels.hip = host side
-// and column kernels, pe25d_tracers.hip = the tracers' host side; pe25d_k1_*.hip, pe25d_k3_*.hip, pe25d_k4_*.hip = the filter and update kernels, one
+// Device-side definitions shared by the translation units of GCM_PE25D (pe25d_kernels.hip = the stage orchestration
+// and the column kernels, pe25d_state.hip = the handle's life cycle and data movement, pe25d_physics.hip = grey radiation,
+// pe25d_diag.hip = diagnostics and taps, pe25d_tracers.hip = the tracers' host side; pe25d_k1_*.hip, pe25d_k3_*.hip, pe25d_k4_*.hip = the filter and update kernels, one
 // file per real type -- K4: per real type and group height -- so that they compile in parallel): kernel arguments, index helpers, the small
 // arithmetic helpers that several kernels must round identically, and the kernel pickers' declarations.
 #pragma once
@@ -185,5 +186,7 @@ constexpr int kTrCols = 64;       // tracer kernel: workgroup of 64 columns x kT
 constexpr int kTrRows = 4;
 constexpr int kUpdCols = 62;      // row-group update kernel: columns a wave produces (lanes 0 and 63 carry the halo columns)
 constexpr int kFftThreads = 256;  // generic filter path; the composite path sizes the workgroup from its plan
+constexpr int kColThreads = 128;  // pe_geopot_kernel (pe25d_kernels.hip): one thread per (j, i) column; pe25d_create sizes its LDS park from it
+constexpr int kRadThreads = 128;  // pe_radiation_kernel (pe25d_physics.hip): the same
 
 }  // namespace gcm

@@ -1,6 +1,13 @@
-// Host side of GCM_PE25D, private to pe25d_kernels.hip (the handle, the stage orchestration, the column kernels) and
-// pe25d_tracers.hip (the passive tracers' host side): the handle and the few helpers both units use.  gcmcore.hip, gcm_band.hip
-// and gcm_diag.hip see pe25d_kernels.h only.
+// Host side of GCM_PE25D, private to its five host units: the handle and the few helpers they share.
+//   pe25d_state.hip    the handle's life cycle and data movement: create / destroy (and the one reader of the GCM_PE_*
+//                      switches), the streams, set / get and the layout transposes, halo buffers and segments
+//   pe25d_kernels.hip  the stage orchestration (half_t and its steps) and the column kernels K2 it launches
+//   pe25d_physics.hip  grey radiation and the ground temperature
+//   pe25d_diag.hip     diagnostics and taps: gcm_stats, the polar filter of a field, the stage's intermediates
+//   pe25d_tracers.hip  the passive tracers' host side
+// A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
+// of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip and gcm_diag.hip see
+// pe25d_kernels.h only.
 #pragma once
 #include "pe25d_kernels.h"
 
@@ -183,8 +190,68 @@ inline bool dev_upload(Pe25d *m, T **dst, const T *src, size_t count) {
     return true;
 }
 
+inline size_t rows_alloc(const Pe25d *m) { return (size_t)m->H + 2 * kGhost; }
+
+template <typename T>
+inline size_t upd_lds_bytes(int R, int L) { return sizeof(T) * ((size_t)3 * (11 * R + 11) * 64 + 2 + 4 * (size_t)L); }
+// looping filter kernels: the complex row + iph(sp) of the row + the row's multiplier
+template <typename T>
+inline size_t filter_loop_lds_bytes(const Pe25d *m) {
+    return (size_t)m->W * sizeof(typename Vec2<T>::type) + ((size_t)m->W + m->W / 2 + 1) * sizeof(T);
+}
+template <typename T>
+inline size_t filter_lds_bytes(const Pe25d *m) {
+    return (size_t)(m->cplan.ok ? 1 : 2) * m->W * sizeof(typename Vec2<T>::type);
+}
+// pe_pit2d_kernel: the composite path keeps the filtered row after its one-row workspace, the generic path in the
+// free half of its two (pe_pit2d_row)
+template <typename T>
+inline size_t pit2d_lds_bytes(const Pe25d *m) {
+    return filter_lds_bytes<T>(m) + (m->cplan.ok ? sizeof(T) * (size_t)m->W : 0);
+}
+
+template <typename T>
+inline PeArgsT<T> make_args(Pe25d *m, int stage_set, int out_set, double dt) {
+    PeBufs<T> &Bf = bufs<T>(m);
+    PeArgsT<T> a{};
+    T *const *B = Bf.st[m->cur_i];
+    T *const *S = Bf.st[stage_set];
+    T *const *O = Bf.st[out_set];
+    a.p = B[GCM_P]; a.u = B[GCM_U]; a.v = B[GCM_V]; a.t = B[GCM_T]; a.q = B[GCM_Q];
+    a.sp = S[GCM_P]; a.su = S[GCM_U]; a.sv = S[GCM_V]; a.st = S[GCM_T]; a.sq = S[GCM_Q];
+    a.op = O[GCM_P]; a.ou = O[GCM_U]; a.ov = O[GCM_V]; a.ot = O[GCM_T]; a.oq = O[GCM_Q];
+    a.spu = Bf.spu; a.phi = Bf.phi; a.pgfu = Bf.pgfu;
+    a.pit = Bf.pit; a.pn = Bf.pn;
+    a.scs_u = Bf.cs[stage_set][0]; a.scs_v = Bf.cs[stage_set][1];
+    a.ocs_u = a.ocs_v = nullptr;
+    a.part = Bf.part;
+    a.part_stride = (long)rows_alloc(m) * m->W;
+    a.nseg = m->nseg;
+    a.spu_j0 = a.pit_j0 = -(1 << 30);            // K1: every row of the launch
+    a.spu_j1 = a.pit_j1 = 1 << 30;
+    a.inv_dxj = Bf.inv_dxj; a.inv_dxh = Bf.inv_dxh;
+    a.sig = Bf.sig; a.dsig = Bf.dsig; a.inv_dsig = Bf.inv_dsig; a.sigb = Bf.sigb; a.sigt = Bf.sigt;
+    a.heightmap = Bf.heightmap; a.cor_u = Bf.cor_u; a.cor_v = Bf.cor_v; a.smul = Bf.smul; a.tw = Bf.tw;
+    a.exner_tab = m->exner_tab;
+    a.plan = m->plan;
+    a.cplan = m->cplan;
+    a.W = m->W; a.H = m->H; a.L = m->L; a.Hg = m->Hg; a.row0 = m->cfg.row0;
+    a.wrap = m->wrap ? 1 : 0;
+    a.filter = m->cfg.filter;
+    a.dt = (T)dt;
+    a.inv_dy = (T)(1.0 / m->cfg.dy);
+    a.ptop = (T)m->cfg.ptop;
+    return a;
+}
+
+// The dynamic LDS size of every kernel a unit launches with more than the default, set where the kernel is
+// instantiated: the filter, pit2d and K4 kernels and pe_geopot_kernel<T, 0> (pe25d_kernels.hip), pe_radiation_kernel<T, 0>
+// (pe25d_physics.hip).  pe25d_create calls both; false: hipFuncSetAttribute failed
+bool stage_lds_attributes(const Pe25d *m);
+bool radiation_lds_attribute(const Pe25d *m);
+
 // Host layout [levels][H][W], float64, <-> a device field [j][levels][i] of the handle's own rows in its real type: the
-// copy through the staging buffer and the transpose, queued on `s`; the caller synchronises (pe25d_kernels.hip)
+// copy through the staging buffer and the transpose, queued on `s`; the caller synchronises (pe25d_state.hip)
 hipError_t field_to_device(Pe25d *m, void *dev_field, const double *host, int levels, hipStream_t s);
 hipError_t field_to_host(Pe25d *m, double *host, const void *dev_field, int levels, hipStream_t s);
 

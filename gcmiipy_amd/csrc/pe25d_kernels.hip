@@ -15,6 +15,10 @@
 // The zonal filter is a complex Stockham FFT in LDS: two levels of one row are packed as
 // real and imaginary part (the filter multiplier is real and symmetric in the wavenumber, so
 // it acts on both parts independently), multiplied by S[j][n] and transformed back.
+//
+// This unit: the column kernels K2 and the stage orchestration that launches K1 .. K4 (half_t and its steps) -- whatever
+// records or waits for the stage's events, or sets a protocol flag to anything but "invalid".  The handle's life cycle
+// and data movement: pe25d_state.hip; grey radiation: pe25d_physics.hip; diagnostics and taps: pe25d_diag.hip.
 #include "pe25d_host.h"
 
 #include <hip/hip_ext.h>
@@ -26,8 +30,7 @@ namespace gcm {
 // K2b pe_pit_kernel: pit = sum_k conv and p_n from the filtered mass flux (aflux).  They are two
 // kernels because they sit on two independent chains, K1 -> K2b and K2a -> K3 (see half_t).
 // The per-level stp that phi needs after the column sum is parked in LDS, park[k][thread],
-// instead of a round trip through HBM.
-constexpr int kColThreads = 128;
+// instead of a round trip through HBM.  (kColThreads: pe25d_dev.h)
 // sum_k dsig[k] u[k] and sum_k dsig[k] v[k] of one column, k = L-1 .. 0 with cs_acc, as K4 accumulates them.  Eight levels of
 // BOTH fields are requested at a time, then added in order: one memory latency per eight levels (a load per iteration
 // waits one per level: 20 us for the two ghost rows of a band, on the edge rows' chain; round 4: the two fields together)
@@ -243,332 +246,15 @@ __global__ __launch_bounds__(256) void pe_colsum_kernel(PeArgsT<T> a) {
     a.scs_v[ix.r2(j) + i] = cs_v;
 }
 
-using PeArgs = PeArgsT<double>;   // the diagnostics and the column physics below are fp64 only
+static bool async_edges(const Pe25d *m) { return m->send_buf[0] && m->send_buf[1]; }
 
-// ---------------------------------------------------------------- calc_energy + STATS (no_limits_2_5d.py:35-60,85-91)
-// thread per (j,i) column; out[kStatsWords*block + {0,1,2}] = partial sums of ke, ate, geo,
-// {3,4,5,6} = max u, min u, max v, min v of the block's columns, {7} = NaNs seen in u and v
-constexpr int kStatsWords = 8;
-__global__ __launch_bounds__(256) void pe_energy_kernel(PeArgs a, const double *area, int area_by_i,
-                                                        double *out) {
-    __shared__ double tab[kExnerTabDoubles];
-    __shared__ double red[kStatsWords][4];
-    tab[threadIdx.x] = a.exner_tab[threadIdx.x];
-    __syncthreads();
-    const Idx ix{a.W, a.H, a.L, a.wrap};
-    const int W = a.W, L = a.L;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int j = blockIdx.y;
-    double ke = 0.0, ate = 0.0, geo = 0.0;
-    double umax = -INFINITY, umin = INFINITY, vmax = -INFINITY, vmin = INFINITY, nn = 0.0;
-    if (i < W) {
-        const int iw = i == 0 ? W - 1 : i - 1;
-        const double pc = a.p[ix.r2(j) + i];
-        const double ar = area[area_by_i ? i : 0];   // geom.area (H,) broadcasts along the LAST axis (:49)
-        const long c3 = ix.r3(j), n3 = ix.r3(j - 1);
-        double depth = 0.0;
-        for (int k = 0; k < L; ++k) {
-            const long o = c3 + (long)k * W;
-            const double u_c = a.u[o + i], v_c = a.v[o + i];
-            umax = fmax(umax, u_c); umin = fmin(umin, u_c);
-            vmax = fmax(vmax, v_c); vmin = fmin(vmin, v_c);
-            if (u_c != u_c || v_c != v_c) nn += 1.0;
-            const double uc = (u_c + a.u[o + iw]) * 0.5;                          // imh(u)
-            const double vc = (v_c + a.v[n3 + (long)k * W + i]) * 0.5;            // jmh(v)
-            const double mag = sqrt(uc * uc + vc * vc);
-            const double tp = pc * a.sig[k] + a.ptop;
-            const double tt = a.t[o + i] * exner(tp, tab);
-            const double rho = tp / (kRd * tt);
-            const double gd = (pc * a.dsig[k]) / (rho * kG);
-            const double airmass = rho * gd * ar;
-            depth += gd;                                                          // cumsum over k
-            geo += depth * airmass * kG;
-            ke += mag * mag * .5 * airmass;
-            ate += tt * kCp * airmass;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        ke += __shfl_down(ke, o);
-        ate += __shfl_down(ate, o);
-        geo += __shfl_down(geo, o);
-        umax = fmax(umax, __shfl_down(umax, o)); umin = fmin(umin, __shfl_down(umin, o));
-        vmax = fmax(vmax, __shfl_down(vmax, o)); vmin = fmin(vmin, __shfl_down(vmin, o));
-        nn += __shfl_down(nn, o);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][w] = ke; red[1][w] = ate; red[2][w] = geo;
-        red[3][w] = umax; red[4][w] = umin; red[5][w] = vmax; red[6][w] = vmin; red[7][w] = nn;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double *o = out + kStatsWords * ((long)blockIdx.y * gridDim.x + blockIdx.x);
-        for (int q = 0; q < 3; ++q) o[q] = red[q][0] + red[q][1] + red[q][2] + red[q][3];
-        o[3] = fmax(fmax(red[3][0], red[3][1]), fmax(red[3][2], red[3][3]));
-        o[4] = fmin(fmin(red[4][0], red[4][1]), fmin(red[4][2], red[4][3]));
-        o[5] = fmax(fmax(red[5][0], red[5][1]), fmax(red[5][2], red[5][3]));
-        o[6] = fmin(fmin(red[6][0], red[6][1]), fmin(red[6][2], red[6][3]));
-        o[7] = red[7][0] + red[7][1] + red[7][2] + red[7][3];
-    }
-}
+// ================================================================== host side: the stage
+// (the handle, struct Pe25d, and the helpers shared with the other host units: pe25d_host.h)
 
-// ---------------------------------------------------------------- grey radiation (column physics)
-// basic_grey_radiation (grey_solar.py:358-563) + solar_timestep (no_limits_2_5d.py:66-75):
-// one thread per (j,i) column, the upwelling scan bottom-up, the downwelling scan top-down.
+// pe25d_create: the dynamic LDS sizes of the kernels a stage launches
 template <typename T>
-struct RadArgsT {
-    const double *tlw, *tsw, *csw_top, *clw_b_div, *swfac;   // [L] level tables (host-built)
-    const double *sigk;                                      // [L] sig^kappa (FACT, see pe_radiation_kernel)
-    const double *coslat, *sinlat, *lon;                     // [Hg], [Hg], [W]
-    double *gt;                                              // ground temperature [H][W]
-    T *dTdt, *dtg;                                           // tendencies out of the diagnostic form (3-D, 2-D scratch)
-    double hour_angle, albedo, dt;
-    int apply;                                               // 1: t, gt updated in place
-    int j0, n0, jb0;                                         // rows of the launch: [j0, j0 + n0), then from jb0 on (a band's ghost
-                                                             // rows on either side in one launch: negative / >= H)
-};
-
-// The arithmetic is float64 for either storage type T: the column physics is a small share of a
-// step, and the fp32 variant then differs from fp64 only by the rounding of what it stores.
-// One thread per column.  The long-wave absorption needs the upwelling flux from BELOW a level and
-// the downwelling flux from ABOVE it, two opposite scans: the bottom-up scan parks one value per
-// level (the absorbed upwelling) and the top-down scan recomputes the level's emission from theta
-// (LMAX > 0: kept in registers from the one up-front request of the column; LMAX == 0: read again).
-// LMAX > 0: L <= LMAX and the parked column lives in registers (loops unrolled); LMAX == 0: any L,
-// parked in LDS, park[L][threads].  The kernel reads theta and writes it (apply) or dTdt (diagnostic);
-// nothing else goes through HBM.
-// FACT (ptop == 0, the reference's geometry): the Exner factor of level k is (p sig_k / P0)^kappa =
-// (p / P0)^kappa sig_k^kappa -- ONE table-and-series evaluation per column and a product per use instead of
-// three evaluations per level (emission in either scan, to_potential_temp); sig^kappa comes from the host in
-// extended precision.  The product differs from the direct evaluation by an ulp or two of a factor that enters
-// theta -> T -> theta symmetrically, far inside the 1e-10 of the parity tests (golden g13, the 2880x1440x40 strips).
-constexpr int kRadThreads = 128;
-constexpr int kRadTabs = 7;      // per level: tlw, clw_b_div, swfac, sig, dsig, sig^kappa, (free)
-template <typename T, int LMAX, bool FACT = false>
-__global__ __launch_bounds__(kRadThreads) void pe_radiation_kernel(PeArgsT<T> a, RadArgsT<T> r, T *t_inout) {
-    __shared__ double tab[kExnerTabDoubles];
-    __shared__ double lev[kRadTabs][LMAX > 0 ? LMAX : 1];
-    extern __shared__ unsigned char rad_park_raw[];
-    for (int n = threadIdx.x; n < kExnerTabDoubles; n += kRadThreads) tab[n] = a.exner_tab[n];
-    const int W = a.W, L = a.L;
-    if (LMAX > 0) {
-        // the level tables go to LDS (read from global memory inside the scans, every one of their
-        // waits would also wait for the theta column still in flight)
-        for (int k = threadIdx.x; k < LMAX; k += kRadThreads) {
-            const int kk = min(k, L - 1);
-            lev[0][k] = r.tlw[kk]; lev[1][k] = r.clw_b_div[kk]; lev[2][k] = r.swfac[kk];
-            lev[3][k] = (double)a.sig[kk]; lev[4][k] = (double)a.dsig[kk];
-            if (FACT) lev[5][k] = r.sigk[kk];
-        }
-    }
-    __syncthreads();
-    constexpr double kSolar = 1.3608 * 1000.0, kSb = 5.67e-8, kCg = 1.13e6;   // constants.py:59,71,25
-    double *p_lwb = (double *)rad_park_raw + threadIdx.x;
-    double lwb_reg[LMAX > 0 ? LMAX : 1];
-    const int i = blockIdx.x * kRadThreads + threadIdx.x;
-    const int j = (int)blockIdx.y < r.n0 ? r.j0 + (int)blockIdx.y : r.jb0 + ((int)blockIdx.y - r.n0);
-    if (i >= W) return;
-    const int jg = wrapi(a.row0 + j, a.Hg);
-    const long c3 = (long)j * L * W + i, c2 = (long)j * W + i;
-    // LMAX > 0: the whole theta column is requested before any of it is used (one memory latency per
-    // column instead of one per level and scan) and kept: the top-down scan does not read it again
-    T tcol[LMAX > 0 ? LMAX : 1];
-    if (LMAX > 0) {
-#pragma unroll
-        for (int k = 0; k < LMAX; ++k) tcol[k] = t_inout[c3 + (long)min(k, L - 1) * W];
-    }
-    const double pc = (double)a.p[c2], gt = r.gt[c2], ptop = (double)a.ptop;
-    // zenith_angle, grey_solar.py:49-65 (declination 0)
-    const double pa = r.lon[i] + r.hour_angle;
-    const double sza = fmax(r.sinlat[jg] * 0.0 + r.coslat[jg] * 1.0 * cos(pa), 0.0);
-    const double Sc = kSolar * sza;
-    const double S = (1 - r.albedo) * Sc * r.csw_top[0];
-    const double g2 = gt * gt;
-    const double U_s = 1 * kSb * (g2 * g2);
-    const auto tlw = [&](int k) { return LMAX > 0 ? lev[0][k] : r.tlw[k]; };
-    const auto clw = [&](int k) { return LMAX > 0 ? lev[1][k] : r.clw_b_div[k]; };
-    const auto swf = [&](int k) { return LMAX > 0 ? lev[2][k] : r.swfac[k]; };
-    const auto sig = [&](int k) { return LMAX > 0 ? lev[3][k] : (double)a.sig[k]; };
-    const auto dsg = [&](int k) { return LMAX > 0 ? lev[4][k] : (double)a.dsig[k]; };
-    const double ex_col = FACT ? exner(pc, tab) : 0.0;
-    const auto exk = [&](int k) { return FACT ? ex_col * lev[5][LMAX > 0 ? k : 0] : exner(pc * sig(k) + ptop, tab); };
-    // true temperature and emission of one level (to_true_temp; grey_solar.py emission)
-    const auto emission = [&](int k, double *tt_out) {
-        const double th = LMAX > 0 ? (double)tcol[LMAX > 0 ? k : 0] : (double)t_inout[c3 + (long)k * W];
-        const double tt = th * exk(k);
-        const double t2 = tt * tt;
-        *tt_out = tt;
-        return (1 - tlw(k)) * kSb * (t2 * t2);
-    };
-    double B = 0.0, up = 0.0;
-    constexpr int kUnroll = LMAX > 0 ? LMAX : 2;
-#pragma unroll kUnroll
-    for (int k = 0; k < (LMAX > 0 ? LMAX : L); ++k) {       // bottom-up: emission, B, LWA_b
-        if (LMAX > 0 && k >= L) break;
-        double tt;
-        const double em = emission(k, &tt);
-        B += em * clw(k);
-        const double lwb = up * (1 - tlw(k));
-        if (LMAX > 0) lwb_reg[k] = lwb;
-        else p_lwb[k * kRadThreads] = lwb;
-        up = up * tlw(k) + em;
-    }
-    const double dtg = (B + S - U_s) / kCg / (.1);
-    if (r.apply) r.gt[c2] = gt + dtg * r.dt;
-    else r.dtg[c2] = (T)dtg;
-    double down = 0.0;
-#pragma unroll kUnroll
-    for (int kk = 0; kk < (LMAX > 0 ? LMAX : L); ++kk) {     // top-down: LWA_a, then eq. 2.34
-        const int k = (LMAX > 0 ? LMAX : L) - 1 - kk;
-        if (LMAX > 0 && k >= L) continue;
-        const long o = c3 + (long)k * W;
-        double tt;
-        const double em = emission(k, &tt);
-        const double lwa = down * (1 - tlw(k));
-        down = down * tlw(k) + em;
-        const double U_n = clw(k) * U_s * (1 - tlw(k));
-        const double S_n = swf(k) * Sc;
-        const double lwb = LMAX > 0 ? lwb_reg[k] : p_lwb[k * kRadThreads];
-        const double dTdt = (U_n + S_n - 2 * em + lwa + lwb) * (kG / (kCp * pc * dsg(k)));
-        if (r.apply) {
-            const double tt_n = tt + dTdt * r.dt;
-            t_inout[o] = (T)(tt_n * rcp(exk(k)));                  // to_potential_temp
-        } else {
-            r.dTdt[o] = (T)dTdt;
-        }
-    }
-}
-
-// ---------------------------------------------------------------- layout transposes
-// host layout [k][j][i] (rows of THIS band only, always float64) <-> device [j][k][i] in the
-// handle's real type
-template <typename T>
-__global__ void pe_to_device_kernel(T *dst, const double *src, int W, int H, int L) {
-    const long n = (long)W * H * L;
-    for (long x = (long)blockIdx.x * blockDim.x + threadIdx.x; x < n; x += (long)gridDim.x * blockDim.x) {
-        const int i = x % W;
-        const long r = x / W;
-        const int k = r % L, j = r / L;
-        dst[x] = (T)src[((long)k * H + j) * W + i];
-    }
-}
-template <typename T>
-__global__ void pe_to_host_kernel(double *dst, const T *src, int W, int H, int L) {
-    const long n = (long)W * H * L;
-    for (long x = (long)blockIdx.x * blockDim.x + threadIdx.x; x < n; x += (long)gridDim.x * blockDim.x) {
-        const int i = x % W;
-        const long r = x / W;
-        const int k = r % L, j = r / L;
-        dst[((long)k * H + j) * W + i] = (double)src[x];
-    }
-}
-
-// ================================================================== host side
-// (the handle, struct Pe25d, and the helpers shared with the tracers' host side: pe25d_host.h)
-
-static_assert(sizeof(SegCopy::n) / sizeof(long) >= 2 * (GCM_NFIELDS + 1 + GCM_MAX_TRACERS),
-              "SegCopy holds one message per side: 5 fields, the ground temperature and every tracer");
-
-// host float64 table -> device table in T
-template <typename T>
-static bool upload_as(Pe25d *m, T **dst, const double *src, size_t count) {
-    std::vector<T> tmp(count);
-    for (size_t i = 0; i < count; ++i) tmp[i] = (T)src[i];
-    return dev_upload<T>(m, dst, tmp.data(), count);
-}
-
-static size_t rows_alloc(const Pe25d *m) { return (size_t)m->H + 2 * kGhost; }
-
-template <typename T>
-static size_t upd_lds_bytes(int R, int L) { return sizeof(T) * ((size_t)3 * (11 * R + 11) * 64 + 2 + 4 * (size_t)L); }
-// looping filter kernels: the complex row + iph(sp) of the row + the row's multiplier
-template <typename T>
-static size_t filter_loop_lds_bytes(const Pe25d *m) {
-    return (size_t)m->W * sizeof(typename Vec2<T>::type) + ((size_t)m->W + m->W / 2 + 1) * sizeof(T);
-}
-template <typename T>
-static size_t filter_lds_bytes(const Pe25d *m) {
-    return (size_t)(m->cplan.ok ? 1 : 2) * m->W * sizeof(typename Vec2<T>::type);
-}
-// pe_pit2d_kernel: the composite path keeps the filtered row after its one-row workspace, the generic path in the
-// free half of its two (pe_pit2d_row)
-template <typename T>
-static size_t pit2d_lds_bytes(const Pe25d *m) {
-    return filter_lds_bytes<T>(m) + (m->cplan.ok ? sizeof(T) * (size_t)m->W : 0);
-}
-
-template <typename T>
-static const char *alloc_all(Pe25d *m, const gcm_config &cfg) {
-    PeBufs<T> &B = bufs<T>(m);
-    const int W = m->W, L = m->L, Hg = m->Hg;
-    const size_t n2 = rows_alloc(m) * W, n3 = n2 * L;
-    for (int s = 0; s < 3; ++s)
-        for (int f = 0; f < GCM_NFIELDS; ++f) {
-            T *d = nullptr;
-            if (!dev_upload<T>(m, &d, nullptr, f == GCM_P ? n2 : n3)) return "state";
-            B.st[s][f] = d + (size_t)kGhost * W * (f == GCM_P ? 1 : L);
-        }
-    T **inter3[] = {&B.spu, &B.phi, &B.pgfu};
-    for (T **pp : inter3) {
-        T *d = nullptr;
-        if (!dev_upload<T>(m, &d, nullptr, n3)) return "intermediate";
-        *pp = d + (size_t)kGhost * W * L;
-    }
-    T **inter2[] = {&B.pit, &B.pn};
-    for (T **pp : inter2) {
-        T *d = nullptr;
-        if (!dev_upload<T>(m, &d, nullptr, n2)) return "intermediate";
-        *pp = d + (size_t)kGhost * W;
-    }
-    for (int st = 0; st < 3; ++st)
-        for (int f = 0; f < 2; ++f) {
-            T *d = nullptr;
-            if (!dev_upload<T>(m, &d, nullptr, n2)) return "intermediate";
-            B.cs[st][f] = d + (size_t)kGhost * W;
-        }
-    {
-        T *d = nullptr;
-        if (!dev_upload<T>(m, &d, nullptr, n2 * (kMaxSeg - 1))) return "intermediate";
-        B.part = d + (size_t)kGhost * W;
-    }
-    // tables
-    std::vector<double> idj(Hg), idh(Hg), ids(L);
-    for (int j = 0; j < Hg; ++j) {
-        idj[j] = 1.0 / cfg.dx_j[j];
-        idh[j] = 1.0 / cfg.dx_h[j];
-    }
-    for (int k = 0; k < L; ++k) ids[k] = 1.0 / cfg.dsig[k];
-    if (!upload_as<T>(m, &B.inv_dxj, idj.data(), Hg) || !upload_as<T>(m, &B.inv_dxh, idh.data(), Hg) ||
-        !upload_as<T>(m, &B.sig, cfg.sig, L) || !upload_as<T>(m, &B.dsig, cfg.dsig, L) ||
-        !upload_as<T>(m, &B.inv_dsig, ids.data(), L) || !upload_as<T>(m, &B.sigb, cfg.sigb, L) ||
-        !upload_as<T>(m, &B.sigt, cfg.sigt, L))
-        return "tables";
-    if (cfg.heightmap && !upload_as<T>(m, &B.heightmap, cfg.heightmap, (size_t)Hg * W)) return "heightmap";
-    if (cfg.cor_u && (!upload_as<T>(m, &B.cor_u, cfg.cor_u, Hg) || !upload_as<T>(m, &B.cor_v, cfg.cor_v, Hg)))
-        return "coriolis tables";
-    if (W > 1) {
-        // filter multiplier, low_pass.py:61-72, same expression order as the reference
-        const int nh = W / 2 + 1;
-        std::vector<double> S((size_t)Hg * nh);
-        for (int j = 0; j < Hg; ++j) {
-            const double drat = cfg.dy / cfg.dx_j[j];
-            S[(size_t)j * nh] = 1.0;
-            for (int n = 1; n < nh; ++n) {
-                const double bysn = 1.0 / std::sin(M_PI / W * (double)n);
-                const double sm = 1.0 - bysn / drat;
-                S[(size_t)j * nh + n] = 1.0 - std::fmax(sm, 0.0);
-            }
-        }
-        if (!upload_as<T>(m, &B.smul, S.data(), S.size())) return "filter multiplier";
-        using T2 = typename Vec2<T>::type;
-        std::vector<T2> tw(W);
-        for (int n = 0; n < W; ++n) {
-            const long double ang = -2.0L * 3.14159265358979323846264338327950288L * n / W;
-            tw[n].x = (T)cosl(ang);
-            tw[n].y = (T)sinl(ang);
-        }
-        if (!dev_upload<T2>(m, &B.tw, tw.data(), W)) return "twiddles";
-    }
+static bool stage_lds_attributes_t(const Pe25d *m) {
+    const int L = m->L;
     if ((spu_filter_loop_kernel_for<T>(m->cplan) &&
          hipFuncSetAttribute((const void *)spu_filter_loop_kernel_for<T>(m->cplan), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)filter_loop_lds_bytes<T>(m)) != hipSuccess) ||
@@ -581,342 +267,16 @@ static const char *alloc_all(Pe25d *m, const gcm_config &cfg) {
         hipFuncSetAttribute((const void *)pe_geopot_kernel<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(L * kColThreads * sizeof(T))) != hipSuccess ||
         hipFuncSetAttribute((const void *)pe_geopot_kernel<T, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(L * kColThreads * sizeof(T))) != hipSuccess ||
-        hipFuncSetAttribute((const void *)pe_radiation_kernel<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(sizeof(double) * (size_t)L * kRadThreads)) != hipSuccess)
-        return "dynamic LDS size";
+                            (int)(L * kColThreads * sizeof(T))) != hipSuccess)
+        return false;
     for (const int R : {7, 3})                   // K4: rows per workgroup x (same, oddtop)
         for (const int v : {0, 1, 2, 3})
             if (hipFuncSetAttribute((const void *)update_rows_kernel_for<T>(R, v & 1, v & 2), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)upd_lds_bytes<T>(R, L)) != hipSuccess)
-        return "dynamic LDS size";
-    return nullptr;
+                return false;
+    return true;
 }
-
-// A second stream that really runs beside `main`.  HIP maps streams onto a few hardware queues
-// round-robin; two streams on one queue execute in order, and which streams share depends on how
-// many were created before (with RCCL initialised in the process the library's second stream
-// landed on the compute stream's queue: every kernel of a stage serialised; the comm stream on it
-// made the exchange wait for the interior rows).  So: create a few candidates, run a 100 us spin
-// kernel on `main` (and `other`) and on the candidate at once, and keep the first candidate for
-// which they all overlapped.
-__global__ void spin_kernel(long long ticks) {
-    const long long t0 = wall_clock64();          // 100 MHz
-    while (wall_clock64() - t0 < ticks) {
-    }
-}
-
-// a kernel that does nothing for `us` microseconds (the loopback exchange's stand-in for a transfer time)
-void launch_spin(hipStream_t s, double us) {
-    if (us > 0) hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, s, (long long)(us * 100.0));
-}
-
-hipStream_t concurrent_stream(hipStream_t main, hipStream_t other) {
-    constexpr int kCandidates = 6;
-    constexpr long long kSpinTicks = 10000;       // 100 us
-    hipStream_t cand[kCandidates] = {};
-    hipEvent_t e0 = nullptr, ea = nullptr, eb = nullptr, ec = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&ea) != hipSuccess || hipEventCreate(&eb) != hipSuccess ||
-        hipEventCreate(&ec) != hipSuccess)
-        return nullptr;
-    int pick = -1, made = 0;
-    const char *vb = getenv("GCM_VERBOSE");
-    const bool verbose = vb && vb[0] == '1';
-    for (int c = 0; c < kCandidates && pick < 0; ++c) {
-        if (hipStreamCreateWithFlags(&cand[c], hipStreamNonBlocking) != hipSuccess) break;
-        ++made;
-        float best = 1e30f;
-        for (int rep = 0; rep < 3; ++rep) {
-            (void)hipStreamSynchronize(main);
-            if (other) (void)hipStreamSynchronize(other);
-            (void)hipStreamSynchronize(cand[c]);
-            (void)hipEventRecord(e0, main);
-            hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, main, kSpinTicks);
-            if (other) hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, other, kSpinTicks);
-            hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, cand[c], kSpinTicks);
-            (void)hipEventRecord(ea, main);
-            if (other) (void)hipEventRecord(ec, other);
-            (void)hipEventRecord(eb, cand[c]);
-            (void)hipStreamSynchronize(main);
-            if (other) (void)hipStreamSynchronize(other);
-            (void)hipStreamSynchronize(cand[c]);
-            float ta = 0.f, tb = 0.f, tc = 0.f;
-            (void)hipEventElapsedTime(&ta, e0, ea);
-            (void)hipEventElapsedTime(&tb, e0, eb);
-            if (other) (void)hipEventElapsedTime(&tc, e0, ec);
-            best = std::min(best, std::max(ta, std::max(tb, tc)));
-        }
-        if (verbose) fprintf(stderr, "gcmcore: stream candidate %d: the 100 us spins took %.1f us\n", c, best * 1e3f);
-        if (best < 0.16f) pick = c;               // all spins inside 160 us: they overlapped
-    }
-    if (pick < 0 && made > 0) pick = 0;           // none overlaps: still correct, only serialised
-    for (int c = 0; c < made; ++c)
-        if (c != pick) (void)hipStreamDestroy(cand[c]);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(ea);
-    (void)hipEventDestroy(eb);
-    (void)hipEventDestroy(ec);
-    if (verbose) fprintf(stderr, "gcmcore: picked stream candidate %d of %d\n", pick, made);
-    return pick >= 0 ? cand[pick] : nullptr;
-}
-
-hipStream_t pe25d_aux_stream(const Pe25d *m) { return m->aux; }
-// gcm_band_run's one join: whatever follows on `s` also follows what the third stream still holds (the own edge
-// rows' column sums of the last stage)
-void pe25d_join_third_stream(Pe25d *m, hipStream_t s) {
-    if (!m->aux2) return;
-    (void)hipEventRecord(m->ev_cs, m->aux2);
-    (void)hipStreamWaitEvent(s, m->ev_cs, 0);
-}
-// something chain B reads was queued on the caller's stream by somebody else (ghost rows unpacked there, the ground
-// temperature uploaded): the next stage's chain B follows that stream's position, not just the last K4
-void pe25d_fork_invalidate(Pe25d *m) { m->k4_fork_valid = false; }
-void pe25d_set_edges_first(Pe25d *m, bool on) { m->edges_first = on; }
-int pe25d_new_state_set(const Pe25d *m) { return (m->pack_set >= 0 && m->pack_set != 2) ? m->pack_set : m->cur_i; }
-
-Pe25d *pe25d_create(const gcm_config &cfg, hipStream_t main_stream, std::string *err) {
-    if (!cfg.dx_j || !cfg.dx_h || !cfg.sig || !cfg.dsig || !cfg.sigb || !cfg.sigt) {
-        *err = "GCM_PE25D: geometry tables (dx_j, dx_h, sig, dsig, sigb, sigt) are required";
-        return nullptr;
-    }
-    if (!(cfg.dy > 0)) { *err = "GCM_PE25D: dy must be > 0"; return nullptr; }
-    if (cfg.global_height < cfg.height || cfg.row0 < 0 || cfg.row0 + cfg.height > cfg.global_height) {
-        *err = "GCM_PE25D: band rows outside the global grid";
-        return nullptr;
-    }
-    if (cfg.nranks == 1 && cfg.global_height != cfg.height) {
-        *err = "GCM_PE25D: nranks == 1 needs height == global_height";
-        return nullptr;
-    }
-    if (cfg.filter && cfg.width > 1 && cfg.width % 2) {
-        *err = "GCM_PE25D: the zonal filter needs an even width (low_pass.py:57; numpy irfft)";
-        return nullptr;
-    }
-    if ((cfg.cor_u != nullptr) != (cfg.cor_v != nullptr)) {
-        *err = "GCM_PE25D: cor_u and cor_v must be given together";
-        return nullptr;
-    }
-    if (cfg.dtype != GCM_F64 && cfg.dtype != GCM_F32) { *err = "GCM_PE25D: bad dtype"; return nullptr; }
-    Pe25d *m = new Pe25d;
-    m->cfg = cfg;
-    m->W = cfg.width;
-    m->H = cfg.height;
-    m->L = cfg.layers;
-    m->Hg = cfg.global_height;
-    m->wrap = cfg.nranks == 1;
-    m->f32 = cfg.dtype == GCM_F32;
-    m->dsig_host.assign(cfg.dsig, cfg.dsig + cfg.layers);
-    m->sig_host.assign(cfg.sig, cfg.sig + cfg.layers);
-    const int W = m->W, L = m->L;
-    auto bad = [&](const char *what) {
-        *err = std::string("hip: GCM_PE25D allocation/upload failed: ") + what;
-        pe25d_destroy(m);
-        return (Pe25d *)nullptr;
-    };
-    if (W > 1) make_super_plan(W, &m->cplan);
-    if (W > 1 && (!make_plan(W, &m->plan) || (size_t)W * 32 + 8192 > 160 * 1024)) {
-        *err = "GCM_PE25D: width not supported by the in-LDS FFT (too many factors or > 4864)";
-        pe25d_destroy(m);
-        return nullptr;
-    }
-    // the LDS-parked column kernels (L > 40: pe_geopot_kernel<T, 0>, pe_radiation_kernel<T, 0>) hold one value per level
-    // and thread; the radiation park is the largest (fp64 whatever the handle's type): L <= 156
-    const auto layers_fit = [](size_t l) {
-        return l * kColThreads * sizeof(double) + kExnerTabDoubles * sizeof(double) <= 160 * 1024 &&
-               sizeof(double) * l * kRadThreads + 4096 <= 160 * 1024 && upd_lds_bytes<double>(3, (int)l) + 4096 <= 160 * 1024;
-    };
-    if (!layers_fit((size_t)L)) {
-        int lmax = 1;
-        while (layers_fit((size_t)lmax + 1)) ++lmax;
-        *err = "GCM_PE25D: " + std::to_string(L) + " layers: the column kernels' LDS holds at most " + std::to_string(lmax);
-        pe25d_destroy(m);
-        return nullptr;
-    }
-    {
-        // K4 keeps 8 waves per CU resident (2 per SIMD), one row x 62 columns each.  A band with less than
-        // about a round and a half of them splits the level march, so that the launch is several short
-        // rounds instead of one long one (results do not depend on the split).  Measured on 1440 columns
-        // x 24 levels: 90 rows best with 2 segments, 180 and more with 1.  Short bands also take the
-        // 3-row workgroups (two per CU, out of step with each other: 3-5 % faster up to ~200 rows; the
-        // 7-row form reads the halo rows 9/7 instead of 5/3 times and is kept where bytes matter).
-        int dev = 0, cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        m->cus = cus;
-        const double rounds = (double)((W + kUpdCols - 1) / kUpdCols) * m->H / (8.0 * cus);
-        long want = (long)std::ceil(1.5 / std::max(rounds, 1e-3));
-        // fp32: 153 VGPRs and 34 KB of tiles per 3-row workgroup let THREE of them share a CU (three waves per SIMD; the
-        // 7-row form holds one 8-wave workgroup, two waves per SIMD): c4_f32 1.214 -> 1.126 ms per step (round 4, A/B
-        // on one box; 5-row groups, 6 waves, place only one workgroup per CU and take 1.44).  fp64 (215 / 231 VGPRs)
-        // stays at two waves per SIMD either way: 3-row groups only where the band is short -- up to 360 rows they win
-        // (round 4, one box: a 360-row band of C4 1.050 -> 1.008 ms, of the 2880x1440x40 grid 3.461 -> 3.396), at 720
-        // rows the 7-row form does (C4 1.874 vs 1.907, the 2880-column grid 6.597 vs 6.627).
-        m->upd_rows = (m->H <= 400 || m->f32) ? 3 : 7;
-        bool forced = false;
-        if (const char *e = getenv("GCM_PE_LEVEL_SEGMENTS")) { want = atoi(e); forced = true; }
-        if (const char *e = getenv("GCM_PE_PIT2D")) m->pit2d = atoi(e) != 0;      // 0: pit from the 3-D fields (pe_pit_kernel)
-        if (const char *e = getenv("GCM_PE_UPDATE_ROWS")) m->upd_rows = atoi(e) == 3 ? 3 : 7;      // rows per workgroup
-        const int cap = std::min(kMaxSeg, std::max(1, L / 4));
-        m->nseg = (int)std::max(1L, std::min((long)cap, want));
-        // K4 fills the chip with whole columns (a 90-row band: 2 % slower than in two segments) and then
-        // leaves the column sums pit needs: segments only on request
-        if (!forced) m->nseg = 1;
-        if (!m->wrap && m->nseg == 1 && m->pit2d && m->H > 2 * kGhost) {
-            m->nseg_edge = std::min(kMaxSeg, std::max(1, L / 6));
-            if (const char *e = getenv("GCM_PE_EDGE_SEGMENTS")) m->nseg_edge = std::max(1, std::min(kMaxSeg, atoi(e)));
-            if (L / m->nseg_edge < 2) m->nseg_edge = 1;
-        }
-    }
-    if (const char *what = m->f32 ? alloc_all<float>(m, cfg) : alloc_all<double>(m, cfg)) return bad(what);
-    if (!dev_upload<double>(m, &m->stage3, nullptr, (size_t)m->H * W * L)) return bad("staging");
-    double tab[kExnerTabDoubles];
-    build_exner_table(tab);
-    if (!dev_upload(m, &m->exner_tab, tab, kExnerTabDoubles)) return bad("exner table");
-    {
-        // ground temperature (column physics), with a band's ghost rows: they travel with every ghost-row message
-        double *d = nullptr;
-        if (!dev_upload<double>(m, &d, nullptr, rows_alloc(m) * (size_t)W)) return bad("ground temperature");
-        m->gt = d + (size_t)kGhost * W;
-    }
-    const char *no_aux = getenv("GCM_PE_SINGLE_STREAM");      // diagnostic: one chain, one stream
-    // a plain stream: a high-priority one finished the edge rows earlier, but in some processes
-    // (depending on how many streams existed before) the whole step then ran at half speed
-    if (!(no_aux && no_aux[0] == '1')) {
-        m->aux = concurrent_stream(main_stream, nullptr);
-        if (!m->aux) return bad("second stream");
-        if (const char *e = getenv("GCM_PE_K1_SPLIT")) m->k1_split = atoi(e) != 0;
-        if (!m->wrap && m->k1_split) {
-            m->aux2 = concurrent_stream(main_stream, m->aux);
-            if (!m->aux2) return bad("third stream");
-        }
-    }
-    if (const char *e = getenv("GCM_PE_STOP_EVENTS")) m->stop_events = atoi(e) != 0;
-    m->filter_no_loop = getenv("GCM_PE_FILTER_NO_LOOP") != nullptr;
-    if (const char *e = getenv("GCM_PE_K4_ODDTOP")) m->k4_oddtop = e[0] != '0';
-    m->rad_generic = getenv("GCM_PE_RAD_GENERIC") != nullptr;
-    if (hipEventCreateWithFlags(&m->ev_pre_edge, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_k4, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_cs, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_a, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_edges, hipEventDisableTiming) != hipSuccess)
-        return bad("events");
-    return m;
-}
-
-void pe25d_destroy(Pe25d *m) {
-    if (!m) return;
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-    if (m->ev_join) (void)hipEventDestroy(m->ev_join);
-    if (m->ev_a) (void)hipEventDestroy(m->ev_a);
-    if (m->ev_edges) (void)hipEventDestroy(m->ev_edges);
-    if (m->ev_cs) (void)hipEventDestroy(m->ev_cs);
-    if (m->ev_k4) (void)hipEventDestroy(m->ev_k4);
-    if (m->ev_pre_edge) (void)hipEventDestroy(m->ev_pre_edge);
-    if (m->aux2) {
-        (void)hipStreamSynchronize(m->aux2);
-        (void)hipStreamDestroy(m->aux2);
-    }
-    if (m->aux) {
-        (void)hipStreamSynchronize(m->aux);      // (a band's last exchange may still be unpacking)
-        (void)hipStreamDestroy(m->aux);
-    }
-    for (void *p : m->allocs) (void)hipFree(p);
-    tracers_destroy(m);
-    delete m;
-}
-
-// State transfers run on the handle's stream `s` and synchronise only that stream: other handles
-// and streams of the process are not stalled.  The float64 staging buffer is reused field by field,
-// which the stream order makes safe.
-hipError_t field_to_device(Pe25d *m, void *dev_field, const double *host, int levels, hipStream_t s) {
-    const hipError_t e = hipMemcpyAsync(m->stage3, host, sizeof(double) * (size_t)m->H * m->W * levels, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return e;
-    if (m->f32) hipLaunchKernelGGL(pe_to_device_kernel<float>, dim3(1024), dim3(256), 0, s, (float *)dev_field, m->stage3, m->W, m->H, levels);
-    else hipLaunchKernelGGL(pe_to_device_kernel<double>, dim3(1024), dim3(256), 0, s, (double *)dev_field, m->stage3, m->W, m->H, levels);
-    return hipSuccess;
-}
-hipError_t field_to_host(Pe25d *m, double *host, const void *dev_field, int levels, hipStream_t s) {
-    if (m->f32) hipLaunchKernelGGL(pe_to_host_kernel<float>, dim3(1024), dim3(256), 0, s, m->stage3, (const float *)dev_field, m->W, m->H, levels);
-    else hipLaunchKernelGGL(pe_to_host_kernel<double>, dim3(1024), dim3(256), 0, s, m->stage3, (const double *)dev_field, m->W, m->H, levels);
-    return hipMemcpyAsync(host, m->stage3, sizeof(double) * (size_t)m->H * m->W * levels, hipMemcpyDeviceToHost, s);
-}
-
-static int xfer(Pe25d *m, int set, bool to_dev, const double *const in[GCM_NFIELDS],
-                double *const out[GCM_NFIELDS], hipStream_t s, std::string *err) {
-    hipError_t e = hipSuccess;
-    for (int f = 0; f < GCM_NFIELDS && e == hipSuccess; ++f) {
-        if (!(to_dev ? (const void *)in[f] : (const void *)out[f])) continue;
-        const int L = f == GCM_P ? 1 : m->L;
-        e = to_dev ? field_to_device(m, state_field(m, set, f), in[f], L, s) : field_to_host(m, out[f], state_field(m, set, f), L, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        *err = std::string("pe25d state transfer: ") + hipGetErrorString(e);
-        return GCM_ERR_HIP;
-    }
-    return GCM_OK;
-}
-
-int pe25d_set(Pe25d *m, bool star, const double *p, const double *u, const double *v,
-              const double *t, const double *q, hipStream_t s, std::string *err) {
-    const double *in[GCM_NFIELDS] = {p, u, v, t, q};
-    int rc = xfer(m, star ? 2 : m->cur_i, true, in, nullptr, s, err);
-    if (u || v) m->cs_valid[star ? 2 : m->cur_i] = false;
-    m->ghost_ready = -1;
-    if (u || v) m->edge_cs_set = -1;
-    m->k4_fork_valid = false;                    // the transposes on the caller's stream: the second stream follows them
-    m->last_stage_set = -1;                      // gcm_get_intermediate: the stage state the anchors belong to is gone
-    if (rc == GCM_OK) m->star_valid = star;
-    return rc;
-}
-
-int pe25d_get(Pe25d *m, bool star, double *p, double *u, double *v, double *t, double *q,
-              hipStream_t s, std::string *err) {
-    if (star && !m->star_valid) {
-        *err = "get_star: no predicted state yet";
-        return GCM_ERR_STATE;
-    }
-    double *out[GCM_NFIELDS] = {p, u, v, t, q};
-    return xfer(m, star ? 2 : m->cur_i, false, nullptr, out, s, err);
-}
-
-template <typename T>
-static PeArgsT<T> make_args(Pe25d *m, int stage_set, int out_set, double dt) {
-    PeBufs<T> &Bf = bufs<T>(m);
-    PeArgsT<T> a{};
-    T *const *B = Bf.st[m->cur_i];
-    T *const *S = Bf.st[stage_set];
-    T *const *O = Bf.st[out_set];
-    a.p = B[GCM_P]; a.u = B[GCM_U]; a.v = B[GCM_V]; a.t = B[GCM_T]; a.q = B[GCM_Q];
-    a.sp = S[GCM_P]; a.su = S[GCM_U]; a.sv = S[GCM_V]; a.st = S[GCM_T]; a.sq = S[GCM_Q];
-    a.op = O[GCM_P]; a.ou = O[GCM_U]; a.ov = O[GCM_V]; a.ot = O[GCM_T]; a.oq = O[GCM_Q];
-    a.spu = Bf.spu; a.phi = Bf.phi; a.pgfu = Bf.pgfu;
-    a.pit = Bf.pit; a.pn = Bf.pn;
-    a.scs_u = Bf.cs[stage_set][0]; a.scs_v = Bf.cs[stage_set][1];
-    a.ocs_u = a.ocs_v = nullptr;
-    a.part = Bf.part;
-    a.part_stride = (long)rows_alloc(m) * m->W;
-    a.nseg = m->nseg;
-    a.spu_j0 = a.pit_j0 = -(1 << 30);            // K1: every row of the launch
-    a.spu_j1 = a.pit_j1 = 1 << 30;
-    a.inv_dxj = Bf.inv_dxj; a.inv_dxh = Bf.inv_dxh;
-    a.sig = Bf.sig; a.dsig = Bf.dsig; a.inv_dsig = Bf.inv_dsig; a.sigb = Bf.sigb; a.sigt = Bf.sigt;
-    a.heightmap = Bf.heightmap; a.cor_u = Bf.cor_u; a.cor_v = Bf.cor_v; a.smul = Bf.smul; a.tw = Bf.tw;
-    a.exner_tab = m->exner_tab;
-    a.plan = m->plan;
-    a.cplan = m->cplan;
-    a.W = m->W; a.H = m->H; a.L = m->L; a.Hg = m->Hg; a.row0 = m->cfg.row0;
-    a.wrap = m->wrap ? 1 : 0;
-    a.filter = m->cfg.filter;
-    a.dt = (T)dt;
-    a.inv_dy = (T)(1.0 / m->cfg.dy);
-    a.ptop = (T)m->cfg.ptop;
-    return a;
-}
-
-static bool async_edges(const Pe25d *m) { return m->send_buf[0] && m->send_buf[1]; }
+bool stage_lds_attributes(const Pe25d *m) { return m->f32 ? stage_lds_attributes_t<float>(m) : stage_lds_attributes_t<double>(m); }
 
 static void tick(Pe25d *m, hipStream_t s) {
     if (m->ev && m->ev_used && *m->ev_used < m->ev->size()) (void)hipEventRecord((*m->ev)[(*m->ev_used)++], s);
@@ -1442,23 +802,12 @@ int pe25d_step_phase(Pe25d *m, int phase, double dt, hipStream_t s, std::string 
     return launch_status(err);
 }
 
-int pe25d_set_halo_buffers(Pe25d *m, void *north, void *south, hipStream_t s, std::string *err) {
-    if (m->wrap) {
-        *err = "set_halo_buffers: handle is not a latitude band";
-        return GCM_ERR_STATE;
-    }
-    if ((north == nullptr) != (south == nullptr)) {
-        *err = "set_halo_buffers: give both buffers, or neither to unregister";
-        return GCM_ERR_ARG;
-    }
-    (void)hipStreamSynchronize(s);
-    if (m->aux) (void)hipStreamSynchronize(m->aux);
-    if (m->aux2) (void)hipStreamSynchronize(m->aux2);
-    m->send_buf[0] = north;
-    m->send_buf[1] = south;
-    m->edges_pending = false;
-    if (north) m->halo_fixed = true;             // (gcm_set_band_tracers: the message format is in use from now on)
-    return GCM_OK;
+// gcm_band_run's one join: whatever follows on `s` also follows what the third stream still holds (the own edge
+// rows' column sums of the last stage)
+void pe25d_join_third_stream(Pe25d *m, hipStream_t s) {
+    if (!m->aux2) return;
+    (void)hipEventRecord(m->ev_cs, m->aux2);
+    (void)hipStreamWaitEvent(s, m->ev_cs, 0);
 }
 
 int pe25d_wait_edges(Pe25d *m, hipStream_t s, std::string *err) {
@@ -1473,373 +822,4 @@ int pe25d_wait_edges(Pe25d *m, hipStream_t s, std::string *err) {
     return GCM_OK;
 }
 
-// ghost rows: [p: 2 rows][u,v,t,q: 2 rows x L levels]; contiguous in the device layout.
-// Which state is exchanged follows the step phase: the predicted state once it exists.
-size_t pe25d_halo_bytes(const Pe25d *m) {
-    // (+ the ground temperature's two rows, float64 for either storage type: gcm_set_physics; + a band's tracers)
-    return elem_size(m) * (size_t)kGhost * m->W * (1 + 4 * (size_t)m->L) + sizeof(double) * (size_t)kGhost * m->W + tracer_halo_bytes(m);
-}
-
-// appends the copies of one side to *c (the caller launches them: one side or both in one launch)
-int pe25d_halo_segments(Pe25d *m, bool pack, int side, void *dev_buf, SegCopy *c, std::string *err) {
-    if (m->f32 && (m->W % 2)) {
-        *err = "pe25d halo: fp32 bands need an even width";
-        return GCM_ERR_UNSUPPORTED;
-    }
-    // unpack: ghosts of the predicted state once it exists, else of the current state;
-    // pack: the same, unless a step_phase call named the set whose edge rows were just produced
-    int set = m->star_valid ? 2 : m->cur_i;
-    if (pack && m->pack_set >= 0) set = m->pack_set;
-    if (!pack && m->pack_set >= 0 && m->pack_set != 2) set = m->pack_set;   // new-state ghosts arrive before the swap
-    if (!pack) m->last_unpack_set = set;
-    double *msg = (double *)dev_buf;
-    for (int f = 0; f < GCM_NFIELDS; ++f)
-        halo_segment(c, pack, side, state_field(m, set, f), m->H, kGhost, (size_t)m->W * (f == GCM_P ? 1 : m->L) * elem_size(m) / 8, &msg);
-    // the ground temperature: one array for all state sets, advanced by the column physics only.  A band's
-    // ghost rows of it are radiated locally (pe25d_solar_rows), so what a message carries equals what the
-    // ghost rows hold already -- except in the first exchange after gcm_set_ground, which is what it is for.
-    halo_segment(c, pack, side, m->gt, m->H, kGhost, (size_t)m->W, &msg);
-    tracer_halo_segments(m, pack, side, set, &msg, c);
-    return GCM_OK;
-}
-
-// low_pass.arakawa_1977 on a field of the handle's grid, nlev <= L levels, host [nlev][H][W] in and
-// out: the spu filter kernel with iph(sp) = 1 (su * 1 is exact).  spu, pgfu and pit serve as scratch
-// -- every stage rewrites them before it reads them.
-template <typename T>
-__global__ void pe_fill_kernel(T *dst, long n, T x) {
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) dst[e] = x;
-}
-template <typename T>
-static int filter_field_t(Pe25d *m, int nlev, const double *in, double *out, hipStream_t s, std::string *err) {
-    PeBufs<T> &B = bufs<T>(m);
-    const int W = m->W, H = m->H;
-    m->last_stage_set = -1;                      // spu, pgfu and pit are scratch here: the parity tap has nothing to return
-    m->k4_fork_valid = false;
-    hipError_t e = field_to_device(m, B.pgfu, in, nlev, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pe_fill_kernel<T>, dim3(256), dim3(256), 0, s, B.pit, (long)H * W, T(1.0));
-        PeArgsT<T> a = make_args<T>(m, m->cur_i, m->cur_i, 0.0);
-        a.L = nlev;
-        a.sp = B.pit;
-        a.su = B.pgfu;
-        a.spu = B.spu;
-        a.filter = 1;
-        a.j0 = 0;
-        a.j1 = H;
-        const int fft_threads = m->cplan.ok ? m->cplan.threads : kFftThreads;
-        hipLaunchKernelGGL(spu_filter_kernel_for<T>(m->cplan), dim3(H, (nlev + 1) / 2), dim3(fft_threads),
-                           filter_lds_bytes<T>(m), s, a);
-        e = field_to_host(m, out, B.spu, nlev, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        *err = std::string("pe25d polar filter: ") + hipGetErrorString(e);
-        return GCM_ERR_HIP;
-    }
-    return GCM_OK;
-}
-
-// ---------------------------------------------------------------- parity tap: the stage's intermediates
-// phi on every level in the host layout [k][j][i], float64: the stored anchors on the even levels, the odd
-// levels stepped up from them with phi_up -- the expression K3 and K4 evaluate
-template <typename T>
-__global__ __launch_bounds__(256) void pe_phi_full_kernel(PeArgsT<T> a, double *out) {
-    __shared__ double tab[kExnerTabDoubles];
-    for (int n = threadIdx.x; n < kExnerTabDoubles; n += 256) tab[n] = a.exner_tab[n];
-    __syncthreads();
-    const int W = a.W, H = a.H, L = a.L;
-    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
-    if (i >= W) return;
-    const long c3 = (long)j * L * W + i;
-    const T spc = a.sp[(long)j * W + i];
-    T phi_lo = T(0.0), t_lo = T(0.0), ex_lo = T(0.0);
-    for (int k = 0; k < L; ++k) {
-        const T t = a.st[c3 + (long)k * W];
-        const T ex = exner(spc * a.sig[k] + a.ptop, tab);
-        const T phi = (k & 1) ? phi_up(phi_lo, t_lo, t, ex_lo, ex) : a.phi[c3 + (long)k * W];
-        out[((long)k * H + j) * W + i] = (double)phi;
-        phi_lo = phi; t_lo = t; ex_lo = ex;
-    }
-}
-
-template <typename T>
-static int intermediate_t(Pe25d *m, int kind, double *out, hipStream_t s, std::string *err) {
-    PeBufs<T> &B = bufs<T>(m);
-    const int W = m->W, H = m->H, L = m->L;
-    const T *src = nullptr;
-    int lev = L;
-    switch (kind) {
-        case GCM_INT_SPU: src = B.spu; break;
-        case GCM_INT_PGFU: src = B.pgfu; break;
-        case GCM_INT_PIT: src = B.pit; lev = 1; break;
-        case GCM_INT_PN: src = B.pn; lev = 1; break;
-        case GCM_INT_PHI: break;
-        default: *err = "gcm_get_intermediate: unknown kind"; return GCM_ERR_ARG;
-    }
-    if (kind == GCM_INT_PHI) {
-        PeArgsT<T> a = make_args<T>(m, m->last_stage_set, m->last_stage_set, 0.0);
-        hipLaunchKernelGGL(pe_phi_full_kernel<T>, dim3((W + 255) / 256, H), dim3(256), 0, s, a, m->stage3);
-    } else {
-        hipLaunchKernelGGL(pe_to_host_kernel<T>, dim3(1024), dim3(256), 0, s, m->stage3, src, W, H, lev);
-    }
-    hipError_t e = hipMemcpyAsync(out, m->stage3, sizeof(double) * (size_t)lev * H * W, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        *err = std::string("gcm_get_intermediate: ") + hipGetErrorString(e);
-        return GCM_ERR_HIP;
-    }
-    return GCM_OK;
-}
-
-int pe25d_intermediate(Pe25d *m, int kind, double *out, hipStream_t s, std::string *err) {
-    if (!m->wrap) { *err = "gcm_get_intermediate: single band only"; return GCM_ERR_UNSUPPORTED; }
-    if (m->last_stage_set < 0) { *err = "gcm_get_intermediate: no half step taken yet"; return GCM_ERR_STATE; }
-    if (m->aux) (void)hipStreamSynchronize(m->aux);
-    return m->f32 ? intermediate_t<float>(m, kind, out, s, err) : intermediate_t<double>(m, kind, out, s, err);
-}
-
-int pe25d_filter_field(Pe25d *m, int nlev, const double *in, double *out, hipStream_t s, std::string *err) {
-    if (nlev < 1 || nlev > m->L) {
-        *err = "polar filter: 1 <= levels <= the handle's layers";
-        return GCM_ERR_ARG;
-    }
-    if (!m->cfg.filter && m->W > 1) {
-        *err = "polar filter: the handle was created with filter = 0";
-        return GCM_ERR_UNSUPPORTED;
-    }
-    if (m->W == 1) {                                    // low_pass.py:58-59: identity
-        if (out != in) memcpy(out, in, sizeof(double) * (size_t)nlev * m->H);
-        return GCM_OK;
-    }
-    return m->f32 ? filter_field_t<float>(m, nlev, in, out, s, err) : filter_field_t<double>(m, nlev, in, out, s, err);
-}
-
-int pe25d_ground(Pe25d *m, bool set, const double *in, double *out, hipStream_t s, std::string *err) {
-    const size_t bytes = sizeof(double) * (size_t)m->H * m->W;
-    hipError_t e = set ? hipMemcpyAsync(m->gt, in, bytes, hipMemcpyHostToDevice, s)
-                       : hipMemcpyAsync(out, m->gt, bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { *err = "hip: ground temperature transfer failed"; return GCM_ERR_HIP; }
-    if (set) {
-        m->gt_set = true;
-        m->k4_fork_valid = false;
-    }
-    return GCM_OK;
-}
-
-// rows [j0, j1) and [jb0, jb1) of state set `set` (a band's ghost rows: negative, or >= H); keep_ghosts: the caller
-// radiates the ghost rows itself before their column sums and anchors are queued (gcm_band_run), so what
-// pe25d_prep_ghost_rows left stays valid
-template <typename T>
-static int radiation_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool apply, double dt,
-                            double hour_angle, double albedo, double *dTdt_host, double *dtg_host, hipStream_t s,
-                            std::string *err) {
-    PeBufs<T> &B = bufs<T>(m);
-    const int W = m->W, L = m->L, Hg = m->Hg;
-    const int nrows = std::max(0, j1 - j0) + std::max(0, jb1 - jb0);
-    if (nrows <= 0) return GCM_OK;
-    PeArgsT<T> a = make_args<T>(m, set, set, dt);
-    a.p = B.st[set][GCM_P];                               // (make_args takes the base state from the current set)
-    RadArgsT<T> r{};
-    r.j0 = j0; r.n0 = std::max(0, j1 - j0); r.jb0 = jb0;
-    r.tlw = m->rad_tab; r.tsw = r.tlw + L; r.csw_top = r.tsw + L; r.clw_b_div = r.csw_top + L; r.swfac = r.clw_b_div + L;
-    r.sigk = r.swfac + L;
-    r.coslat = m->rad_geo; r.sinlat = m->rad_geo + Hg; r.lon = m->rad_geo + 2 * Hg;
-    r.gt = m->gt;
-    r.dTdt = B.pgfu; r.dtg = B.pit;
-    r.hour_angle = hour_angle;
-    r.albedo = albedo; r.dt = dt; r.apply = apply ? 1 : 0;
-    if (apply && !keep_ghosts) m->ghost_ready = -1;        // theta changes in place
-    m->last_stage_set = -1;                                // gcm_get_intermediate: theta changed, or pgfu / pit hold the tendencies
-    // the diagnostic form writes pgfu / pit on `s`, and a band's explicit solar_timestep changes the ghost rows' theta
-    // there: the next stage's chain B (K1 + pit, the ghost rows' anchors) follows the stream's position, not just the last K4
-    if (!(apply && (keep_ghosts || m->wrap))) m->k4_fork_valid = false;
-    {
-        const dim3 gg((W + kRadThreads - 1) / kRadThreads, nrows);
-        T *th = B.st[set][GCM_T];
-        const bool generic = m->rad_generic;
-        const bool fact = m->cfg.ptop == 0.0 && r.sigk != nullptr;
-        if (L <= 24 && !generic && fact) hipLaunchKernelGGL((pe_radiation_kernel<T, 24, true>), gg, dim3(kRadThreads), 0, s, a, r, th);
-        else if (L <= 40 && !generic && fact) hipLaunchKernelGGL((pe_radiation_kernel<T, 40, true>), gg, dim3(kRadThreads), 0, s, a, r, th);
-        else if (L <= 24 && !generic) hipLaunchKernelGGL((pe_radiation_kernel<T, 24>), gg, dim3(kRadThreads), 0, s, a, r, th);
-        else if (L <= 40 && !generic) hipLaunchKernelGGL((pe_radiation_kernel<T, 40>), gg, dim3(kRadThreads), 0, s, a, r, th);
-        else hipLaunchKernelGGL((pe_radiation_kernel<T, 0>), gg, dim3(kRadThreads), sizeof(double) * (size_t)L * kRadThreads, s, a, r, th);
-    }
-    if (hipGetLastError() != hipSuccess) { *err = "hip: radiation kernel launch failed"; return GCM_ERR_HIP; }
-    // solar_timestep (apply) stays asynchronous on `s`; the diagnostics form copies its results back
-    if (dtg_host && field_to_host(m, dtg_host, B.pit, 1, s) != hipSuccess) { *err = "hip: dt_ground copy-back failed"; return GCM_ERR_HIP; }
-    if (dTdt_host && field_to_host(m, dTdt_host, B.pgfu, L, s) != hipSuccess) { *err = "hip: dTdt copy-back failed"; return GCM_ERR_HIP; }
-    if ((dtg_host || dTdt_host) && hipStreamSynchronize(s) != hipSuccess) {
-        *err = "hip: radiation kernel failed"; return GCM_ERR_HIP;
-    }
-    return GCM_OK;
-}
-
-// the level tables (t_lw, t_sw) and the lat / lon tables of the radiation kernel, uploaded when they change
-int pe25d_physics_tables(Pe25d *m, double t_lw, double t_sw, const double *lat, const double *lon, hipStream_t s,
-                         std::string *err) {
-    if (!m->gt_set) { *err = "radiation: set the ground temperature first (gcm_set_ground)"; return GCM_ERR_STATE; }
-    if (!lat || !lon) { *err = "radiation: lat and lon tables are required"; return GCM_ERR_ARG; }
-    const int W = m->W, L = m->L, Hg = m->Hg;
-    bool uploaded = false;
-    if (m->rad_key[0] != t_lw || m->rad_key[1] != t_sw || !m->rad_tab) {
-        // level tables, same expression order as grey_solar.py:323-333,377-385,541
-        std::vector<double> &T = m->rad_tab_host;
-        T.assign((size_t)6 * L, 0.0);
-        const std::vector<double> &dsig = m->dsig_host;
-        double *tlw = T.data(), *tsw = tlw + L, *csw = tsw + L, *cdiv = csw + L, *swf = cdiv + L;
-        for (int k = 0; k < L; ++k) {
-            tlw[k] = 1 - (1 - std::pow(t_lw, dsig[k]));
-            tsw[k] = 1 - (1 - std::pow(t_sw, dsig[k]));
-        }
-        double c = 1.0;
-        for (int k = L - 1; k >= 0; --k) { c = k == L - 1 ? tsw[k] : c * tsw[k]; csw[k] = c; }
-        for (int k = 0; k < L; ++k) { c = k == 0 ? tlw[k] : c * tlw[k]; cdiv[k] = c / tlw[k]; }
-        for (int k = 0; k < L; ++k) swf[k] = (1 - tsw[k]) * csw[k] / tsw[k];
-        for (int k = 0; k < L; ++k) swf[L + k] = (double)powl((long double)m->sig_host[k], (long double)kKappa);   // sig^kappa (FACT)
-        if (!m->rad_tab && !dev_upload<double>(m, &m->rad_tab, nullptr, (size_t)6 * L)) {
-            *err = "hip: radiation table allocation failed"; return GCM_ERR_HIP;
-        }
-        // the host copy lives in the handle until the next change, so the asynchronous upload may
-        // read it after this call returns; a change waits for the previous upload first
-        if (hipStreamSynchronize(s) != hipSuccess ||
-            hipMemcpyAsync(m->rad_tab, T.data(), sizeof(double) * 6 * L, hipMemcpyHostToDevice, s) != hipSuccess) {
-            *err = "hip: radiation table upload failed"; return GCM_ERR_HIP;
-        }
-        m->rad_key[0] = t_lw; m->rad_key[1] = t_sw;
-        uploaded = true;
-    }
-    // lat / lon tables: uploaded when their content changes (normally once)
-    if (m->rad_latlon.size() != (size_t)Hg + W || memcmp(m->rad_latlon.data(), lat, sizeof(double) * Hg) ||
-        memcmp(m->rad_latlon.data() + Hg, lon, sizeof(double) * W)) {
-        if (hipStreamSynchronize(s) != hipSuccess) { *err = "hip: radiation geometry upload failed"; return GCM_ERR_HIP; }
-        m->rad_latlon.assign(lat, lat + Hg);
-        m->rad_latlon.insert(m->rad_latlon.end(), lon, lon + W);
-        std::vector<double> &Gt = m->rad_geo_host;
-        Gt.assign((size_t)2 * Hg + W, 0.0);
-        for (int j = 0; j < Hg; ++j) { Gt[j] = std::cos(lat[j]); Gt[Hg + j] = std::sin(lat[j]); }
-        for (int i = 0; i < W; ++i) Gt[2 * Hg + i] = lon[i];
-        if (!m->rad_geo && !dev_upload<double>(m, &m->rad_geo, nullptr, Gt.size())) {
-            *err = "hip: radiation geometry allocation failed"; return GCM_ERR_HIP;
-        }
-        if (hipMemcpyAsync(m->rad_geo, Gt.data(), sizeof(double) * Gt.size(), hipMemcpyHostToDevice, s) != hipSuccess) {
-            *err = "hip: radiation geometry upload failed"; return GCM_ERR_HIP;
-        }
-        uploaded = true;
-    }
-    // (a band radiates its ghost rows on the second stream: the tables are in place before anything is queued there)
-    if (uploaded && hipStreamSynchronize(s) != hipSuccess) { *err = "hip: radiation table upload failed"; return GCM_ERR_HIP; }
-    return GCM_OK;
-}
-
-// solar_timestep (no_limits_2_5d.py:66-75) of rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one) on stream `s`;
-// the tables must be in place (pe25d_physics_tables)
-int pe25d_solar_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, double dt, double utc, double albedo,
-                     hipStream_t s, std::string *err) {
-    if (set < 0) set = m->cur_i;
-    const double hour_angle = utc / (-24 * 3600.0) * 360 * (M_PI / 180);      // grey_solar.py:51
-    return m->f32 ? radiation_launch<float>(m, set, j0, j1, jb0, jb1, keep_ghosts, true, dt, hour_angle, albedo, nullptr, nullptr, s, err)
-                  : radiation_launch<double>(m, set, j0, j1, jb0, jb1, keep_ghosts, true, dt, hour_angle, albedo, nullptr, nullptr, s, err);
-}
-
-// basic_grey_radiation (+ optional in-place solar_timestep).  dTdt_host / dtg_host may be null.  On a latitude
-// band the in-place form advances the ghost rows too (their theta as the post-corrector exchange delivered it,
-// their ground temperature as the last message delivered it): the neighbour's own inputs, the neighbour's own bits.
-int pe25d_radiation(Pe25d *m, bool apply, double dt, double utc, double t_lw, double t_sw, double albedo,
-                    const double *lat, const double *lon, double *dTdt_host, double *dtg_host,
-                    hipStream_t s, std::string *err) {
-    int rc = pe25d_physics_tables(m, t_lw, t_sw, lat, lon, s, err);
-    if (rc) return rc;
-    const double hour_angle = utc / (-24 * 3600.0) * 360 * (M_PI / 180);      // grey_solar.py:51
-    const int g = (apply && !m->wrap) ? kGhost : 0;
-    return m->f32 ? radiation_launch<float>(m, m->cur_i, -g, m->H + g, 0, 0, false, apply, dt, hour_angle, albedo, dTdt_host, dtg_host, s, err)
-                  : radiation_launch<double>(m, m->cur_i, -g, m->H + g, 0, 0, false, apply, dt, hour_angle, albedo, dTdt_host, dtg_host, s, err);
-}
-
-// calc_energy + STATS in one launch and one synchronisation of `s`: out9 = u_max, u_min, v_max,
-// v_min, ke, ate, geo, total, NaN count.  The area table and the partials live in the handle.
-int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err) {
-    if (m->f32) { *err = "gcm_energy / gcm_stats: fp64 handles only"; return GCM_ERR_UNSUPPORTED; }
-    if (!m->wrap) { *err = "gcm_energy / gcm_stats: single band only"; return GCM_ERR_UNSUPPORTED; }
-    if (!(area_len == 1 || area_len == m->W)) {
-        *err = "gcm_energy: geom.area (H,) must broadcast against the last axis W (no_limits_2_5d.py:49): "
-               "needs H == W or H == 1";
-        return GCM_ERR_ARG;
-    }
-    const int gx = (m->W + 255) / 256, nb = gx * m->H;
-    if (!m->stats_dev) {
-        if (!dev_upload<double>(m, &m->stats_dev, nullptr, (size_t)kStatsWords * nb + m->W)) {
-            *err = "hip: gcm_stats allocation failed";
-            return GCM_ERR_HIP;
-        }
-        m->stats_host.resize((size_t)kStatsWords * nb);
-    }
-    double *d_area = m->stats_dev + (size_t)kStatsWords * nb;
-    if (m->area_host.size() != (size_t)area_len || memcmp(m->area_host.data(), area_host, sizeof(double) * area_len)) {
-        m->area_host.assign(area_host, area_host + area_len);
-        if (hipMemcpyAsync(d_area, m->area_host.data(), sizeof(double) * area_len, hipMemcpyHostToDevice, s) != hipSuccess) {
-            *err = "hip: gcm_stats area upload failed";
-            return GCM_ERR_HIP;
-        }
-    }
-    PeArgs a = make_args<double>(m, m->cur_i, m->cur_i, 0.0);
-    hipLaunchKernelGGL(pe_energy_kernel, dim3(gx, m->H), dim3(256), 0, s, a, d_area, area_len > 1 ? 1 : 0, m->stats_dev);
-    double *part = m->stats_host.data();
-    if (hipMemcpyAsync(part, m->stats_dev, sizeof(double) * kStatsWords * nb, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        *err = "hip: gcm_stats kernel failed";
-        return GCM_ERR_HIP;
-    }
-    double ke = 0, ate = 0, geo = 0, nn = 0, umax = -INFINITY, umin = INFINITY, vmax = -INFINITY, vmin = INFINITY;
-    for (int b = 0; b < nb; ++b) {
-        const double *o = part + (size_t)kStatsWords * b;
-        ke += o[0]; ate += o[1]; geo += o[2]; nn += o[7];
-        umax = std::fmax(umax, o[3]); umin = std::fmin(umin, o[4]);
-        vmax = std::fmax(vmax, o[5]); vmin = std::fmin(vmin, o[6]);
-    }
-    // np.max / np.min propagate NaN
-    out[0] = nn > 0 ? NAN : umax; out[1] = nn > 0 ? NAN : umin; out[2] = nn > 0 ? NAN : vmax; out[3] = nn > 0 ? NAN : vmin;
-    out[4] = ke; out[5] = ate; out[6] = geo; out[7] = ke + ate + geo; out[8] = nn;
-    return GCM_OK;
-}
-
-// field geometry for get_total_variation (axis 0 of the reference layout): 2-D p differences rows,
-// the 3-D fields difference levels inside a row slab
-int pe25d_filter_plan(int n, unsigned *out, int cap) {
-    if (!out || n < 2 || cap < 3 + 4 * kMaxSuper) return GCM_ERR_ARG;
-    SuperPlan P;
-    make_super_plan(n, &P);
-    out[0] = (unsigned)P.ok;
-    out[1] = (unsigned)P.npass;
-    out[2] = (unsigned)P.threads;
-    for (int p = 0; p < kMaxSuper; ++p) {
-        out[3 + 4 * p] = (unsigned)P.r1[p];
-        out[4 + 4 * p] = (unsigned)P.r2[p];
-        out[5 + 4 * p] = P.magic[p];
-        out[6 + 4 * p] = P.imagic[p];
-    }
-    return GCM_OK;
-}
-
-void pe25d_tv_shape(const Pe25d *m, int field, long *n_outer, long *n_axis, long *n_inner, int *wrap) {
-    if (field == GCM_P) { *n_outer = 1; *n_axis = m->H; *n_inner = m->W; *wrap = m->wrap ? 1 : 0; }
-    else { *n_outer = m->H; *n_axis = m->L; *n_inner = m->W; *wrap = 1; }
-}
-
-// current-state field for the diagnostics reductions; *f32 tells the element type
-const void *pe25d_field(Pe25d *m, int field, long *n, int *f32) {
-    *n = (long)m->H * m->W * (field == GCM_P ? 1 : m->L);
-    *f32 = m->f32 ? 1 : 0;
-    return state_field(m, m->cur_i, field);
-}
-
-void pe25d_timing(Pe25d *m, std::vector<hipEvent_t> *ev, size_t *used) {
-    m->ev = ev;
-    m->ev_used = used;
-}
-
 }  // namespace gcm
-
