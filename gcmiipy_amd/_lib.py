@@ -72,6 +72,13 @@ class Physics(C.Structure):
                 ("lat", _dp), ("lon", _dp)]
 
 
+class HeldSuarez(C.Structure):
+    """gcm_held_suarez of include/gcmcore.h"""
+    _fields_ = [("k_f", C.c_double), ("k_a", C.c_double), ("k_s", C.c_double), ("sigma_b", C.c_double),
+                ("dT_y", C.c_double), ("dtheta_z", C.c_double), ("T_0", C.c_double), ("T_min", C.c_double),
+                ("lat", _dp)]
+
+
 class TracerForcing(C.Structure):
     """gcm_tracer_forcing of include/gcmcore.h"""
     _fields_ = [("source", C.c_double), ("decay", C.c_double), ("pin_value", C.c_double),
@@ -111,6 +118,10 @@ SYMBOLS = {
     "gcm_solar_step": (C.c_int, [_H] + [C.c_double] * 5 + [_dp, _dp]),
     "gcm_set_physics": (C.c_int, [_H, C.c_void_p]),
     "gcm_get_utc": (C.c_int, [_H, _dp]),
+    "gcm_set_held_suarez": (C.c_int, [_H, C.POINTER(HeldSuarez)]),
+    "gcm_held_suarez_on": (C.c_int, [_H]),
+    "gcm_held_suarez_step": (C.c_int, [_H, C.c_double, C.POINTER(HeldSuarez)]),
+    "gcm_held_suarez_tables": (C.c_int, [C.c_int, _dp, C.c_int, _dp, C.POINTER(HeldSuarez), C.c_double, _dp, _dp, _dp, _dp]),
     "gcm_snapshot": (C.c_int, [_H]),
     "gcm_restore": (C.c_int, [_H]),
     "gcm_halo_bytes": (C.c_size_t, [_H]),

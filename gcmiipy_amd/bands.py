@@ -288,14 +288,23 @@ class HipBandEngine:
         self.c.set_physics(geom, utc)
         self._phys = [geom, float(utc)]
 
+    def set_held_suarez(self, geom, **params):
+        """the Held-Suarez forcing after every dynamics step, behind the solar step (Core.set_held_suarez; every band
+        of a run registers the same): inside the library's gcm_band_run, or from physics_step() when the host drives
+        the exchange.  geom=None switches it off"""
+        self.c.set_held_suarez(geom, **params)
+        self._hs = None if geom is None else (geom, dict(params))
+
     def physics_step(self, dt):
         """host-driven band step: own rows and ghost rows by one gcm_solar_step on the compute stream, behind the
-        unpack of the post-corrector exchange"""
+        unpack of the post-corrector exchange; then, likewise, the Held-Suarez forcing"""
         ph = getattr(self, "_phys", None)
-        if ph is None:
-            return
-        self.c.solar_step(ph[0], dt, ph[1])
-        ph[1] += dt
+        if ph is not None:
+            self.c.solar_step(ph[0], dt, ph[1])
+            ph[1] += dt
+        hs = getattr(self, "_hs", None)
+        if hs is not None:
+            self.c.held_suarez_step(hs[0], dt, **hs[1])
 
     def send_buffer(self, side):
         self.c.halo_pack(side, self.sbuf[side].data_ptr(), self._s(self.compute))

@@ -9,14 +9,16 @@ is the option "tracer_scheme", files without it restore as centred; the tracers'
 stored per forced tracer i as "forcing_<i>_scalars" (source, decay, pin_value) with "forcing_<i>_emission" and
 "forcing_<i>_pin_mask" where registered, and files without these keys restore with none; their vertical mixing,
 Core.set_tracer_mixing, is stored per mixed tracer i as "mixing_<i>", the float64 profile K of L - 1 values, and files
-without the key restore with none)
+without the key restore with none; the Held-Suarez forcing, Core.set_held_suarez, is stored as "held_suarez", its eight
+parameters in the order of core.HELD_SUAREZ_DEFAULTS, with "held_suarez_lat", the latitudes it was given, and
+re-registered on restore; files without the key restore with none)
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
 import numpy as np
 
 from . import _lib
-from .core import Core
+from .core import Core, HELD_SUAREZ_DEFAULTS
 from .geometry import Geom
 
 _GEOM_KEYS = ("sige", "sigt", "sigb", "dsig", "sig", "dsigv", "dx_j", "dx_h", "dy", "ptop",
@@ -43,6 +45,10 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
                 out["forcing_%d_pin_mask" % i] = np.asarray(rec["pin_mask"], dtype=np.uint8)
         for i, k in core.tracer_mixings().items():
             out["mixing_%d" % i] = np.asarray(k, dtype=np.float64)
+    hs = core.held_suarez if core.model == _lib.PE25D else None
+    if hs is not None:
+        out["held_suarez"] = np.asarray([hs[k] for k in HELD_SUAREZ_DEFAULTS], dtype=np.float64)
+        out["held_suarez_lat"] = core.held_suarez_lat
     for k, a in zip("puvtq", (p, u, v, t, q)):
         if a is not None:
             out["state_" + k] = a
@@ -56,8 +62,8 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing); ground and tracers are None where the file has none, tracer_forcing {i: dict(...)} and
-    tracer_mixing {i: K} are then empty"""
+    tracer_mixing, held_suarez); ground and tracers are None where the file has none, tracer_forcing {i: dict(...)} and
+    tracer_mixing {i: K} are then empty; held_suarez is (parameters dict, lat) or None"""
     d = np.load(path, allow_pickle=False)
     L, H, W = (int(x) for x in d["shape"])
     state = {k: d["state_" + k] for k in "puvtq" if "state_" + k in d.files}
@@ -85,7 +91,10 @@ def load(path):
                               emission=d[key_e] if key_e in d.files else None,
                               pin_mask=d[key_m] if key_m in d.files else None)
     mixing = {int(f.split("_")[1]): d[f] for f in d.files if f.startswith("mixing_")}
-    return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state,
+    hs = None
+    if "held_suarez" in d.files:
+        hs = (dict(zip(HELD_SUAREZ_DEFAULTS, (float(x) for x in d["held_suarez"]))), d["held_suarez_lat"])
+    return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
@@ -111,4 +120,6 @@ def restore(path, **core_kwargs):
             core.set_tracer_forcing(i, **rec)
         for i, k in sorted(ck["tracer_mixing"].items()):
             core.set_tracer_mixing(i, k)
+    if ck["held_suarez"] is not None:
+        core.set_held_suarez(ck["held_suarez"][1], **ck["held_suarez"][0])
     return core, ck

@@ -92,6 +92,47 @@ def check_dtype(dtype):
     return dtype
 
 
+# the parameters of the Held-Suarez forcing (gcm_held_suarez) with Held & Suarez (1994)'s values, in the struct's order
+HELD_SUAREZ_DEFAULTS = collections.OrderedDict(
+    k_f=1.0 / 86400.0, k_a=1.0 / (40.0 * 86400.0), k_s=1.0 / (4.0 * 86400.0), sigma_b=0.7, dT_y=60.0, dtheta_z=10.0,
+    T_0=315.0, T_min=200.0)
+
+
+def held_suarez_params(params):
+    """the eight parameters of the Held-Suarez forcing as a dict of floats: Held & Suarez (1994)'s values with `params`
+    laid over them; ValueError for a name that is not a parameter"""
+    unknown = sorted(set(params) - set(HELD_SUAREZ_DEFAULTS))
+    if unknown:
+        raise ValueError("held_suarez: unknown parameter(s) %s; the parameters are %s"
+                         % (", ".join(unknown), ", ".join(HELD_SUAREZ_DEFAULTS)))
+    out = collections.OrderedDict(HELD_SUAREZ_DEFAULTS)
+    out.update({k: float(v) for k, v in params.items()})
+    return out
+
+
+def _held_suarez_record(lat, params):
+    """-> (gcm_held_suarez, the arrays it points to, the parameters as a dict)"""
+    par = held_suarez_params(params)
+    rec = _lib.HeldSuarez(*par.values())
+    rec.lat = _tab(lat)
+    return rec, lat, par
+
+
+def held_suarez_tables(sig, lat, dt, **params):
+    """the host tables of the Held-Suarez forcing (gcm_held_suarez_tables; no handle, no device) for the mid-level
+    sigmas `sig` (L,), the latitudes `lat` (n,) in radians and the step dt -> dict(fu (L,), kt (L, n), s2 (n,), c2 (n,)):
+    the routine the launches of Core.set_held_suarez / Core.held_suarez_step take their tables from.  ValueError for a
+    refused parameter"""
+    sig = as_f64(np.asarray(sig, dtype=np.float64).reshape(-1), name="sig")
+    lat = as_f64(np.asarray(lat, dtype=np.float64).reshape(-1), name="lat")
+    rec, _, _ = _held_suarez_record(lat, params)
+    L, n = sig.size, lat.size
+    fu, kt, s2, c2 = np.empty(L), np.empty((L, n)), np.empty(n), np.empty(n)
+    _check(lib.gcm_held_suarez_tables(L, _tab(sig), n, _tab(lat), C.byref(rec), float(dt), _tab(fu), _tab(kt), _tab(s2),
+                                      _tab(c2)))
+    return dict(fu=fu, kt=kt, s2=s2, c2=c2)
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -144,6 +185,7 @@ class Core:
         self.has_ground = False
         self._forcing = {}                      # tracer -> the forcing record registered (set_tracer_forcing)
         self._mixing = {}                       # tracer -> the profile K registered (set_tracer_mixing)
+        self._held_suarez = None                # the parameters and latitudes registered (set_held_suarez)
         cfg = _lib.Config()
         cfg.abi_version = _lib.ABI_VERSION
         cfg.model = model
@@ -517,6 +559,47 @@ class Core:
         lat, lon = self._latlon(geom)
         ph = _lib.Physics(float(utc), t_lw, t_sw, albedo, _tab(lat), _tab(lon))
         _check(lib.gcm_set_physics(self._h, C.byref(ph)), self._h)
+
+    # -- Held-Suarez forcing (GCM_PE25D) ---------------------------------------------------
+    def _hs_lat(self, geom):
+        lat = getattr(geom, "lat", geom)        # a geometry, or the latitudes themselves
+        return as_f64(np.asarray(lat, dtype=np.float64).reshape(-1), (self.global_height,), "lat")
+
+    def set_held_suarez(self, geom, **params):
+        """every step of step() / band_run() from now on ends with the Held & Suarez (1994) forcing on the device:
+        Newtonian relaxation of theta towards the prescribed equilibrium and Rayleigh friction of the winds below
+        sigma_b, backward Euler (gcm_set_held_suarez) -- the Matsuno step, then solar_timestep where set_physics is on,
+        then this.  half_step never applies it.  geom: the geometry (its .lat, radians, over the global height) or the
+        latitudes themselves; params: k_f, k_a, k_s (1 / s), sigma_b, dT_y, dtheta_z, T_0, T_min (K), Held-Suarez's
+        values by default (HELD_SUAREZ_DEFAULTS).  geom=None switches the forcing off.  ValueError for a refused
+        parameter (the call then changes nothing)"""
+        if geom is None:
+            _check(lib.gcm_set_held_suarez(self._h, None), self._h)
+            self._held_suarez = None
+            return
+        rec, lat, par = _held_suarez_record(self._hs_lat(geom), params)
+        _check(lib.gcm_set_held_suarez(self._h, C.byref(rec)), self._h)
+        self._held_suarez = (dict(par), lat.copy())
+
+    def held_suarez_step(self, geom, dt, **params):
+        """the Held-Suarez forcing once, in place on the current state, with the step dt (gcm_held_suarez_step): what
+        solar_step is to set_physics.  A band: own rows and ghost rows, the ghost rows must be current"""
+        rec, _, _ = _held_suarez_record(self._hs_lat(geom), params)
+        _check(lib.gcm_held_suarez_step(self._h, float(dt), C.byref(rec)), self._h)
+
+    @property
+    def held_suarez(self):
+        """the parameters of the registered Held-Suarez forcing as a dict, or None where the handle carries none
+        (gcm_held_suarez_on) -- and also None for one registered through the C call directly"""
+        on = lib.gcm_held_suarez_on(self._h)
+        if on < 0:
+            _check(on, self._h)
+        return dict(self._held_suarez[0]) if on and self._held_suarez else None
+
+    @property
+    def held_suarez_lat(self):
+        """the latitudes (global_height,) the registered Held-Suarez forcing was given, or None"""
+        return self._held_suarez[1].copy() if self.held_suarez is not None else None
 
     def utc(self):
         out = C.c_double()

@@ -124,6 +124,13 @@ static int band_step_pe(gcm_handle *h, double dt) {
             if (stage == 1 && h->phys_on && (rc = pe25d_solar_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, dt,
                                                                    h->phys.utc, h->phys.albedo, ax, &h->err)))
                 return rc;
+            // gcm_set_held_suarez: the ghost rows of theta, u, v as the post-corrector exchange delivered them, forced
+            // locally (the neighbour's own inputs and tables, hence its own bits), behind the unpack and the ghost rows'
+            // solar step in stream order and AHEAD of the ghost rows' column sums and anchors, which read u, v and theta
+            // (the launch marks the state's column sums stale: pe25d_prep_ghost_rows then leaves them to the next stage)
+            if (stage == 1 && h->hs_on && (rc = pe25d_hs_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, ax,
+                                                              &h->err)))
+                return rc;
             if ((rc = pe25d_prep_ghost_rows(h->pe, &h->err))) return rc;
             h->band.join_pending = true;
         }
@@ -140,12 +147,21 @@ static int band_step_pe(gcm_handle *h, double dt) {
             return rc;
         h->phys.utc += dt;
     }
+    if (h->hs_on) {
+        // own rows (and the ghost rows with them where the exchange was joined into the compute stream), behind the corrector and the
+        // solar step: the compute stream has waited for the edge rows' pack by then (update_interior), so the rows that left are
+        // unforced and the neighbour forces them itself.  The launch invalidates the fork at the last K4 (pe25d_hs_rows): the next
+        // step's launches on the second and third stream, which read own rows' u and v, follow this stream's position
+        const int g = ax ? 0 : kGhost;
+        if ((rc = pe25d_hs_rows(h->pe, -1, -g, H + g, 0, 0, ax != nullptr, h->stream, &h->err))) return rc;
+    }
     return GCM_OK;
 }
 
 static int run_pe(gcm_handle *h, int nsteps, double dt) {
     int rc = physics_tables(h);
     if (rc) return rc;
+    if (nsteps > 0 && (rc = held_suarez_step_tables(h, dt))) return rc;
     if (!h->band.primed) {                                 // ghost rows of the initial state (and of the ground temperature), once
         if ((rc = pack_edges(h)) || (rc = band_exchange(h))) return rc;
         h->band.primed = true;

@@ -77,6 +77,11 @@ struct gcm_handle {
     bool phys_on = false;
     gcm_physics phys{};
     std::vector<double> phys_lat, phys_lon;
+
+    // gcm_set_held_suarez: the Held-Suarez forcing as the last phase of every step (hs.lat: null, hs_lat is the copy)
+    bool hs_on = false;
+    gcm_held_suarez hs{};
+    std::vector<double> hs_lat;
 };
 
 #define HIPCHK(h, call)                                                                    \
@@ -136,5 +141,6 @@ extern "C" void step_rows(gcm_handle *h, double dt, int j0, int j1, hipStream_t 
 extern "C" void swap_state(gcm_handle *h);
 extern "C" int launch_status(gcm_handle *h);
 extern "C" int physics_tables(gcm_handle *h);
+extern "C" int held_suarez_step_tables(gcm_handle *h, double dt);   // the registered forcing's device tables for dt (none: GCM_OK)
 
 #pragma GCC visibility pop

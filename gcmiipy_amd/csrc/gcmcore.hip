@@ -358,6 +358,13 @@ int physics_tables(gcm_handle *h) {
     return pe25d_physics_tables(h->pe, h->phys.t_lw, h->phys.t_sw, h->phys_lat.data(), h->phys_lon.data(), h->stream, &h->err);
 }
 
+int held_suarez_step_tables(gcm_handle *h, double dt) {
+    if (!h->hs_on) return GCM_OK;
+    gcm_held_suarez hs = h->hs;
+    hs.lat = h->hs_lat.data();
+    return pe25d_hs_tables(h->pe, &hs, dt, h->stream, &h->err);
+}
+
 // what the launches queued since the last check returned: the status hipLaunchKernel handed back for the
 // fused step (kept in the handle: step_rows has many callers) and the runtime's sticky last error
 int launch_status(gcm_handle *h) {
@@ -461,6 +468,7 @@ int gcm_step(gcm_handle *h, int nsteps, double dt) {
     if (h->pe) {
         int rc = physics_tables(h);
         if (rc) return rc;
+        if (nsteps > 0 && (rc = held_suarez_step_tables(h, dt))) return rc;
         for (int n = 0; n < nsteps; ++n) {
             if ((rc = pe25d_step(h->pe, dt, h->stream, &h->err))) return rc;
             if (h->phys_on) {
@@ -470,6 +478,9 @@ int gcm_step(gcm_handle *h, int nsteps, double dt) {
                     return rc;
                 h->phys.utc += dt;
             }
+            // gcm_set_held_suarez: the last phase of the step.  The launch writes u and v, which the next stage's chain B
+            // reads: it invalidates the fork at the last K4 (pe25d_hs_rows), so that chain B follows this stream's position
+            if (h->hs_on && (rc = pe25d_hs_rows(h->pe, -1, 0, h->H, 0, 0, false, h->stream, &h->err))) return rc;
         }
         pe25d_join_tracers(h->pe, h->stream);             // (the passive tracers' tail on the second stream)
         return GCM_OK;
@@ -811,6 +822,43 @@ int gcm_set_physics(gcm_handle *h, const gcm_physics *ph) {
     h->phys.lat = h->phys.lon = nullptr;                   // (the copies above are what is used)
     h->phys_on = true;
     return GCM_OK;
+}
+
+int gcm_set_held_suarez(gcm_handle *h, const gcm_held_suarez *hs) {
+    if (int rc = pe_only(h, "gcm_set_held_suarez")) return rc;
+    if (!hs) {
+        h->hs_on = false;
+        return GCM_OK;
+    }
+    if (int rc = held_suarez_check(hs, "gcm_set_held_suarez", &h->err)) return rc;
+    for (int j = 0; j < h->cfg.global_height; ++j)
+        if (!std::isfinite(hs->lat[j])) return fail(h, GCM_ERR_ARG, "gcm_set_held_suarez: lat must be finite");
+    h->hs = *hs;
+    h->hs_lat.assign(hs->lat, hs->lat + h->cfg.global_height);
+    h->hs.lat = nullptr;                                   // (the copy above is what is used)
+    h->hs_on = true;
+    return GCM_OK;
+}
+
+int gcm_held_suarez_on(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && h->hs_on ? 1 : 0;
+}
+
+int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs) {
+    if (int rc = pe_only(h, "gcm_held_suarez_step")) return rc;
+    if (int rc = held_suarez_check(hs, "gcm_held_suarez_step", &h->err)) return rc;
+    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_held_suarez_step: dt must be finite");
+    if (int rc = select_device(h)) return rc;
+    if (int rc = pe25d_hs_tables(h->pe, hs, dt, h->stream, &h->err)) return rc;
+    // a band: own rows and ghost rows, as gcm_solar_step (the ghost rows of the current state must be current)
+    const int g = h->wrap ? 0 : kGhost;
+    return pe25d_hs_rows(h->pe, -1, -g, h->H + g, 0, 0, false, h->stream, &h->err);
+}
+
+int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
+                           double *fu, double *kt, double *s2, double *c2) {
+    return held_suarez_tables(L, sig, nlat, lat, hs, dt, fu, kt, s2, c2, &gcm_create_error());
 }
 
 int gcm_get_utc(gcm_handle *h, double *utc) {

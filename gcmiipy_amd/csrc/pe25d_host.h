@@ -5,6 +5,7 @@
 //   pe25d_physics.hip  grey radiation and the ground temperature
 //   pe25d_diag.hip     diagnostics and taps: gcm_stats, the polar filter of a field, the stage's intermediates
 //   pe25d_tracers.hip  the passive tracers' host side
+//   pe25d_held_suarez.hip  the Held-Suarez forcing: its table routine, its kernel and its launches
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip and gcm_diag.hip see
 // pe25d_kernels.h only.
@@ -83,6 +84,14 @@ struct PeTracers {
     double *stats_dev = nullptr;                // gcm_tracer_stats: float64 dsig [L], the records, then the workgroups' partials
 };
 
+// Held-Suarez forcing (pe25d_held_suarez.hip): the device tables of the last (parameters, lat, dt) a launch was asked
+// for -- `key`, compared on every step, so that they are built and uploaded again only when one of them changes
+struct PeHeldSuarez {
+    double *tab = nullptr;                      // device: 4 x [L] level tables, 2 x [Hg], 2 x [L][Hg]
+    std::vector<double> key;                    // the eight parameters, dt, lat [Hg]
+    double par[5] = {};                         // T_min, T_0, dT_y, dtheta_z, (free): what the kernel takes by value
+};
+
 struct Pe25d {
     gcm_config cfg{};
     int W = 0, H = 0, L = 0, Hg = 0;
@@ -153,6 +162,7 @@ struct Pe25d {
     // depth are a part, is fixed
     bool halo_fixed = false;
     PeTracers tr;
+    PeHeldSuarez hs;
 };
 
 template <typename T> inline PeBufs<T> &bufs(Pe25d *m);

@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
-// pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip and pe25d_tracers.hip (the passive
-// tracers), used by gcmcore.hip, gcm_band.hip and gcm_diag.hip.
+// pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip and
+// pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip and gcm_diag.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,6 +47,15 @@ int pe25d_physics_tables(Pe25d *m, double t_lw, double t_sw, const double *lat, 
                          std::string *err);
 int pe25d_solar_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, double dt, double utc, double albedo,
                      hipStream_t s, std::string *err);
+// Held-Suarez forcing (pe25d_held_suarez.hip).  held_suarez_tables: gcm_held_suarez_tables (no handle, no device);
+// pe25d_hs_tables: the device tables for (hs, dt), built and uploaded when either changed (hs->lat: [global_height]);
+// pe25d_hs_rows: the kernel over rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one) on `s`, tables in
+// place; keep_ghosts as for pe25d_solar_rows
+int held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
+                       double *fu, double *kt, double *s2, double *c2, std::string *err);
+int held_suarez_check(const gcm_held_suarez *hs, const char *fn, std::string *err);
+int pe25d_hs_tables(Pe25d *m, const gcm_held_suarez *hs, double dt, hipStream_t s, std::string *err);
+int pe25d_hs_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, hipStream_t s, std::string *err);
 int pe25d_new_state_set(const Pe25d *m);    // the set a corrector stage in flight writes (before the swap), else the current one
 int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err);
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan

@@ -411,6 +411,58 @@ typedef struct {
 } gcm_physics;
 int gcm_set_physics(gcm_handle *h, const gcm_physics *ph);
 int gcm_get_utc(gcm_handle *h, double *utc);   /* the physics clock (GCM_ERR_STATE without gcm_set_physics) */
+/* Held & Suarez (1994) forcing of GCM_PE25D on the device: Newtonian relaxation of theta towards a prescribed
+ * equilibrium and Rayleigh friction of the low-level winds, backward Euler, one launch per step (fp64 and fp32 handles,
+ * single domains and latitude bands).  State: p [H][W] in Pa (surface pressure minus ptop), t = theta, u, v [L][H][W];
+ * tables: sig[k] (the mid-level sigma of gcm_config), ptop, lat[j] in radians over the GLOBAL height (a band uses its
+ * row offset, as gcm_set_physics does).  P0 = 1e5 Pa and kappa = Rd / Cp are the model's own (constants.py:31,28), not
+ * parameters: theta <-> T must agree with the Exner function of the dynamics.
+ * Host tables, float64, every operation rounded on its own (gcm_held_suarez_tables):
+ *   r[k]     = max(0, (sig[k] - sigma_b) / (1 - sigma_b))
+ *   fu[k]    = 1 / (1 + (dt k_f) r[k])
+ *   c2[j]    = cos(lat[j])^2;   s2[j] = sin(lat[j])^2
+ *   kt[k][j] = k_a + (((k_s - k_a) r[k]) c2[j]) c2[j]
+ * r takes the model's own sigma of the level: with ptop = 0, the reference's geometry, that is exactly Held-Suarez's
+ * p / p_s; with ptop != 0 it is this build's choice, which keeps the friction a function of the level alone, so that u
+ * and v at their C-grid half points need no pressure and no row beyond the ghost rows.
+ * Update, float64 arithmetic for either storage type (as the radiation kernel), the result rounded once to it:
+ *   levels with r[k] > 0:  u <- u fu[k],  v <- v fu[k];  levels with r[k] = 0 are neither read nor written
+ *   p_lev    = sig[k] p[j][i] + ptop
+ *   theta_eq = max(T_min (P0 / p_lev)^kappa,  T_0 - dT_y s2[j] - (dtheta_z ln(p_lev / P0)) c2[j])
+ *   theta   <- (theta + (dt kt[k][j]) theta_eq) / (1 + dt kt[k][j])
+ * Backward Euler: stable for every dt, theta moves monotonically towards theta_eq, |u| never grows.  p, q, the tracers
+ * and the ground temperature are untouched.  The device takes (P0 / p_lev)^kappa from the kernels' own Exner routine
+ * and multiplies by the host's 1 / (1 + dt kt): theta agrees with the formula within the 1e-10 of the parity tests,
+ * u and v (one float64 product with the routine's own table) bit for bit.
+ * gcm_set_held_suarez: the forcing as a phase of every step taken by gcm_step and gcm_band_run: the Matsuno step, then
+ * solar_timestep where gcm_set_physics is on, then this.  gcm_half_step never applies it (as it never applies the solar
+ * step): the predicted (star) state is never forced.  On a latitude band the ghost rows of theta, u, v that the
+ * post-corrector exchange delivers are forced LOCALLY (the kernel is column-local and takes the latitude of the global
+ * row: the neighbour's own inputs, the neighbour's own bits), the packed edge rows leave unforced: no third exchange,
+ * the message format is unchanged.  `lat` [global_height] is copied; NULL switches the forcing off.  Errors, checked in
+ * the call: a null handle GCM_ERR_ARG; other models GCM_ERR_UNSUPPORTED; a non-finite number, k_f, k_a or k_s < 0,
+ * sigma_b outside [0, 1), a null `lat`: GCM_ERR_ARG.  A refused call changes nothing.  Without a registration nothing
+ * is launched and every result and timing is as before.  The handle keeps the parameters and builds the tables again
+ * when a step comes with another dt, not on every step.
+ * gcm_held_suarez_on: 1 where a forcing is registered, else 0 (other models: 0; a null handle GCM_ERR_ARG).
+ * gcm_held_suarez_step: the same kernel once, in place on the current state (what gcm_solar_step is to
+ * gcm_set_physics).  On a band it advances own rows and ghost rows: the ghost rows of the current state must be
+ * current, as for gcm_solar_step.
+ * gcm_held_suarez_tables: the table routine above on its own, without a handle or a device -- the routine the launches
+ * take their tables from.  fu [L], kt [L][nlat], s2, c2 [nlat].  Errors (GCM_ERR_ARG, message: gcm_last_error(NULL)):
+ * L or nlat < 1, a null pointer, a non-finite dt, sig or lat, the parameter errors above.                       */
+typedef struct {
+    double k_f, k_a, k_s;        /* 1 / s: friction, relaxation aloft, relaxation at the surface of the tropics */
+    double sigma_b;              /* top of the boundary layer                                  */
+    double dT_y, dtheta_z;       /* K: equator-to-pole difference, static stability            */
+    double T_0, T_min;           /* K: surface equilibrium at the equator, stratosphere        */
+    const double *lat;           /* geom.lat [global_height], radians                          */
+} gcm_held_suarez;
+int gcm_set_held_suarez(gcm_handle *h, const gcm_held_suarez *hs);
+int gcm_held_suarez_on(const gcm_handle *h);
+int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs);
+int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
+                           double *fu, double *kt, double *s2, double *c2);
 
 /* Device-side snapshot / restore of the current state, ghost rows included (2-D models): a long
  * run can restart from a known state without a host round trip.  gcm_restore is asynchronous on
