@@ -19,6 +19,7 @@ VARIANT_AUTO, VARIANT_STAGED, VARIANT_FUSED = 0, 1, 2
 F64, F32 = 0, 1
 MAX_TRACERS = 16                     # GCM_MAX_TRACERS
 TRACER_STATS_WORDS = 6               # GCM_TRACER_STATS_WORDS
+CLIM_WORDS3, CLIM_WORDS2 = 10, 2     # GCM_CLIM_WORDS3, GCM_CLIM_WORDS2
 ADV_UPWIND, ADV_FV_UPWIND, ADV_FV_PLAIN, ADV_VANLEER, ADV_MOMENTUM = range(5)
 DIAG_ANY_NAN, DIAG_MAX_U, DIAG_MEAN_P, DIAG_SUM_P, DIAG_MIN_U, DIAG_MAX_V, DIAG_MIN_V = range(7)
 DIAG_TV_P, DIAG_TV_U, DIAG_TV_V, DIAG_TV_T, DIAG_TV_Q = range(7, 12)
@@ -122,6 +123,12 @@ SYMBOLS = {
     "gcm_held_suarez_on": (C.c_int, [_H]),
     "gcm_held_suarez_step": (C.c_int, [_H, C.c_double, C.POINTER(HeldSuarez)]),
     "gcm_held_suarez_tables": (C.c_int, [C.c_int, _dp, C.c_int, _dp, C.POINTER(HeldSuarez), C.c_double, _dp, _dp, _dp, _dp]),
+    "gcm_set_climate": (C.c_int, [_H, C.c_int]),
+    "gcm_climate_every": (C.c_int, [_H]),
+    "gcm_climate_sample": (C.c_int, [_H]),
+    "gcm_climate_reset": (C.c_int, [_H]),
+    "gcm_get_climate": (C.c_int, [_H, _dp, _dp, C.POINTER(C.c_int64)]),
+    "gcm_put_climate": (C.c_int, [_H, _dp, _dp, C.c_int64]),
     "gcm_snapshot": (C.c_int, [_H]),
     "gcm_restore": (C.c_int, [_H]),
     "gcm_halo_bytes": (C.c_size_t, [_H]),

@@ -200,6 +200,19 @@ class BandRunner:
             self.step(dt)
 
 
+def merge_climate(parts):
+    """the climatology of the whole domain from its bands': `parts` are the bands' Climate records (Core.climate) in
+    row order; the rows are concatenated.  ValueError where the sample counts differ"""
+    import numpy as np
+    from .core import Climate
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_climate: no records")
+    if any(c.n != parts[0].n for c in parts):
+        raise ValueError("merge_climate: the bands hold %s samples" % ", ".join(str(c.n) for c in parts))
+    return Climate(parts[0].n, *[np.concatenate([c[f] for c in parts], axis=-1) for f in range(1, len(Climate._fields))])
+
+
 class LoopbackExchange:
     """Diagnostic stand-in for torch.distributed inside BandRunner: every send lands in the
     matching receive buffer of the SAME rank (a device-local copy on the comm stream).  The band
@@ -295,9 +308,17 @@ class HipBandEngine:
         self.c.set_held_suarez(geom, **params)
         self._hs = None if geom is None else (geom, dict(params))
 
+    def set_climate(self, every=1):
+        """the zonal-mean climatology of the band's own rows (Core.set_climate; every band of a run registers the same
+        interval): sampled inside the library's gcm_band_run, or from physics_step() when the host drives the
+        exchange.  every=0 switches it off.  merge_climate() puts the bands' records together"""
+        self.c.set_climate(every)
+        self._clim = [int(every), 0]
+
     def physics_step(self, dt):
         """host-driven band step: own rows and ghost rows by one gcm_solar_step on the compute stream, behind the
-        unpack of the post-corrector exchange; then, likewise, the Held-Suarez forcing"""
+        unpack of the post-corrector exchange; then, likewise, the Held-Suarez forcing; then the climatology's sample
+        where this step is due one"""
         ph = getattr(self, "_phys", None)
         if ph is not None:
             self.c.solar_step(ph[0], dt, ph[1])
@@ -305,6 +326,11 @@ class HipBandEngine:
         hs = getattr(self, "_hs", None)
         if hs is not None:
             self.c.held_suarez_step(hs[0], dt, **hs[1])
+        cl = getattr(self, "_clim", None)
+        if cl is not None and cl[0] > 0:
+            cl[1] += 1
+            if cl[1] % cl[0] == 0:
+                self.c.climate_sample()
 
     def send_buffer(self, side):
         self.c.halo_pack(side, self.sbuf[side].data_ptr(), self._s(self.compute))

@@ -11,7 +11,9 @@ stored per forced tracer i as "forcing_<i>_scalars" (source, decay, pin_value) w
 Core.set_tracer_mixing, is stored per mixed tracer i as "mixing_<i>", the float64 profile K of L - 1 values, and files
 without the key restore with none; the Held-Suarez forcing, Core.set_held_suarez, is stored as "held_suarez", its eight
 parameters in the order of core.HELD_SUAREZ_DEFAULTS, with "held_suarez_lat", the latitudes it was given, and
-re-registered on restore; files without the key restore with none)
+re-registered on restore; files without the key restore with none; the zonal-mean climatology, Core.set_climate, is
+stored as "climate_every", "climate_n", "climate_m3" and "climate_m2", the interval, the sample count and the raw
+float64 sums, registered and uploaded again on restore; files without these keys restore without a climatology)
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
@@ -49,6 +51,9 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
     if hs is not None:
         out["held_suarez"] = np.asarray([hs[k] for k in HELD_SUAREZ_DEFAULTS], dtype=np.float64)
         out["held_suarez_lat"] = core.held_suarez_lat
+    if core.model == _lib.PE25D and core.climate_every > 0:
+        n, m3, m2 = core.climate_sums()
+        out.update(climate_every=np.int64(core.climate_every), climate_n=np.int64(n), climate_m3=m3, climate_m2=m2)
     for k, a in zip("puvtq", (p, u, v, t, q)):
         if a is not None:
             out["state_" + k] = a
@@ -62,8 +67,9 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, held_suarez); ground and tracers are None where the file has none, tracer_forcing {i: dict(...)} and
-    tracer_mixing {i: K} are then empty; held_suarez is (parameters dict, lat) or None"""
+    tracer_mixing, held_suarez, climate); ground and tracers are None where the file has none, tracer_forcing
+    {i: dict(...)} and tracer_mixing {i: K} are then empty; held_suarez is (parameters dict, lat) or None; climate is
+    dict(every, n, m3, m2) or None"""
     d = np.load(path, allow_pickle=False)
     L, H, W = (int(x) for x in d["shape"])
     state = {k: d["state_" + k] for k in "puvtq" if "state_" + k in d.files}
@@ -94,7 +100,10 @@ def load(path):
     hs = None
     if "held_suarez" in d.files:
         hs = (dict(zip(HELD_SUAREZ_DEFAULTS, (float(x) for x in d["held_suarez"]))), d["held_suarez_lat"])
-    return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs,
+    clim = None
+    if "climate_every" in d.files:
+        clim = dict(every=int(d["climate_every"]), n=int(d["climate_n"]), m3=d["climate_m3"], m2=d["climate_m2"])
+    return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, climate=clim,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
@@ -122,4 +131,7 @@ def restore(path, **core_kwargs):
             core.set_tracer_mixing(i, k)
     if ck["held_suarez"] is not None:
         core.set_held_suarez(ck["held_suarez"][1], **ck["held_suarez"][0])
+    if ck["climate"] is not None:
+        core.set_climate(ck["climate"]["every"])
+        core.put_climate(ck["climate"]["n"], ck["climate"]["m3"], ck["climate"]["m2"])
     return core, ck

@@ -62,6 +62,47 @@ class TracerStats(collections.namedtuple("TracerStats", "min max mass air negati
         return self.mass / self.air
 
 
+CLIMATE_WORDS3 = ("u", "v", "theta", "T", "uu", "vv", "TT", "uv", "vT", "vtheta")    # the moments of gcm_get_climate's m3
+CLIMATE_WORDS2 = ("p", "pp")                                                           # ... and of its m2
+
+
+class Climate(collections.namedtuple("Climate", ("n",) + CLIMATE_WORDS3 + CLIMATE_WORDS2)):
+    """the zonal-mean climatology of a GCM_PE25D handle (Core.climate): n, the number of samples, and the time and
+    zonal means of the moments -- the device's float64 sums divided by W n (NaN where n = 0).  (L, H) arrays: u, v (at
+    their own C-grid points), theta, T = theta Pi, uu, vv, TT, uv = uc vc, vT = vc T, vtheta = vc theta, where uc, vc
+    are the winds averaged to the cell centre; (H,) arrays: p, pp.  A band: its own rows (bands.merge_climate)"""
+    __slots__ = ()
+
+    @property
+    def eddy_momentum_flux(self):
+        """[u'v'] = uv - [u][v].  uv is the mean of the product at the cell centre, [u] and [v] are the means at the
+        winds' own staggered points: the zonal mean of uc IS that of u, the mean of vc is 0.5 ([v][j] + [v][j - 1]),
+        approximated here by [v][j] -- exact where [v] does not vary from one row to the next"""
+        return self.uv - self.u * self.v
+
+    @property
+    def eddy_heat_flux(self):
+        """[v'T'] = vT - [v][T], with [v] at its own point (see eddy_momentum_flux)"""
+        return self.vT - self.v * self.T
+
+    @property
+    def T_variance(self):
+        """[T'T'] = TT - [T]^2: the eddy temperature variance"""
+        return self.TT - self.T * self.T
+
+    @property
+    def eke(self):
+        """0.5 (uu - [u]^2 + vv - [v]^2): the eddy kinetic energy per unit mass, winds at their own points"""
+        return 0.5 * (self.uu - self.u * self.u + self.vv - self.v * self.v)
+
+    @classmethod
+    def from_sums(cls, n, m3, m2, width):
+        """the record of the raw sums m3 (10, L, H), m2 (2, H) of n samples of rows of `width` columns"""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            d = np.float64(width) * np.float64(n)
+            return cls(int(n), *[m3[w] / d for w in range(len(CLIMATE_WORDS3))], *[m2[w] / d for w in range(len(CLIMATE_WORDS2))])
+
+
 DTYPES = {"f64": _lib.F64, "f32": _lib.F32}
 # the transport scheme of a GCM_PE25D handle's passive tracers (gcm_set_tracer_scheme)
 TRACER_SCHEMES = {"centred": _lib.TRACER_NONE, "upwind": _lib.TRACER_UPWIND, "van_leer": _lib.TRACER_VANLEER}
@@ -600,6 +641,52 @@ class Core:
     def held_suarez_lat(self):
         """the latitudes (global_height,) the registered Held-Suarez forcing was given, or None"""
         return self._held_suarez[1].copy() if self.held_suarez is not None else None
+
+    # -- zonal-mean climatology (GCM_PE25D) ------------------------------------------------
+    def set_climate(self, every=1):
+        """accumulate the zonal-mean climatology on the device (gcm_set_climate): from now on every `every`-th step of
+        step() / band_run() ends with one launch that adds the zonal sums of the moments of `Climate` to float64 sums in
+        the handle, behind the solar step and the Held-Suarez forcing.  The step counter runs across calls; half_step
+        never samples.  Registering again resets the sums; every=0 unregisters.  ValueError for every < 0"""
+        _check(lib.gcm_set_climate(self._h, int(every)), self._h)
+
+    @property
+    def climate_every(self):
+        """the registered sampling interval in steps, 0 where none is registered (gcm_climate_every)"""
+        n = lib.gcm_climate_every(self._h)
+        if n < 0:
+            _check(n, self._h)
+        return n
+
+    def climate_sample(self):
+        """one sample of the current state now (gcm_climate_sample); the step counter is untouched.  A band: the ghost
+        rows of the current state must be current, as for solar_step"""
+        _check(lib.gcm_climate_sample(self._h), self._h)
+
+    def climate_reset(self):
+        """zero the sums and the sample count (gcm_climate_reset)"""
+        _check(lib.gcm_climate_reset(self._h), self._h)
+
+    def climate_sums(self):
+        """-> (n, m3 (10, L, H), m2 (2, H)): the raw float64 sums as the device holds them (gcm_get_climate); one
+        synchronisation, a few hundred KB"""
+        m3 = np.empty((_lib.CLIM_WORDS3, self.L, self.H))
+        m2 = np.empty((_lib.CLIM_WORDS2, self.H))
+        n = C.c_int64()
+        _check(lib.gcm_get_climate(self._h, _tab(m3), _tab(m2), C.byref(n)), self._h)
+        return int(n.value), m3, m2
+
+    def put_climate(self, n, m3, m2):
+        """upload sums taken by climate_sums() (gcm_put_climate): a restart goes on where the run stopped"""
+        m3 = as_f64(m3, (_lib.CLIM_WORDS3, self.L, self.H), "m3")
+        m2 = as_f64(m2, (_lib.CLIM_WORDS2, self.H), "m2")
+        _check(lib.gcm_put_climate(self._h, _tab(m3), _tab(m2), int(n)), self._h)
+
+    def climate(self):
+        """-> Climate: the sample count and the means, the sums divided by W n (gcm_get_climate).  GcmError where no
+        climatology is registered"""
+        n, m3, m2 = self.climate_sums()
+        return Climate.from_sums(n, m3, m2, self.W)
 
     def utc(self):
         out = C.c_double()

@@ -155,6 +155,18 @@ static int band_step_pe(gcm_handle *h, double dt) {
         const int g = ax ? 0 : kGhost;
         if ((rc = pe25d_hs_rows(h->pe, -1, -g, H + g, 0, 0, ax != nullptr, h->stream, &h->err))) return rc;
     }
+    if (pe25d_climate_due(h->pe)) {
+        // gcm_set_climate: the sample reads the own rows as the phases above left them on the compute stream, and row -1 of v,
+        // the first north ghost row, as the post-corrector exchange delivered it and the ghost rows' Held-Suarez launch forced
+        // it -- on the second stream where the exchange runs there.  The compute stream joins that stream's tail first (the
+        // unpack, the ghost rows' physics, their column sums), on the steps that sample only; the event is gcm_band_run's own
+        // join event, which nobody else records between a run's first exchange and its end
+        if (ax) {
+            HIPCHK(h, hipEventRecord(h->band.ev_comm, ax));
+            HIPCHK(h, hipStreamWaitEvent(h->stream, h->band.ev_comm, 0));
+        }
+        if ((rc = pe25d_climate_sample(h->pe, h->stream, &h->err))) return rc;
+    }
     return GCM_OK;
 }
 

@@ -481,6 +481,8 @@ int gcm_step(gcm_handle *h, int nsteps, double dt) {
             // gcm_set_held_suarez: the last phase of the step.  The launch writes u and v, which the next stage's chain B
             // reads: it invalidates the fork at the last K4 (pe25d_hs_rows), so that chain B follows this stream's position
             if (h->hs_on && (rc = pe25d_hs_rows(h->pe, -1, 0, h->H, 0, 0, false, h->stream, &h->err))) return rc;
+            // gcm_set_climate: a sample of the state the step leaves, behind every phase that changes it
+            if (pe25d_climate_due(h->pe) && (rc = pe25d_climate_sample(h->pe, h->stream, &h->err))) return rc;
         }
         pe25d_join_tracers(h->pe, h->stream);             // (the passive tracers' tail on the second stream)
         return GCM_OK;
@@ -859,6 +861,42 @@ int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs) {
 int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
                            double *fu, double *kt, double *s2, double *c2) {
     return held_suarez_tables(L, sig, nlat, lat, hs, dt, fu, kt, s2, c2, &gcm_create_error());
+}
+
+int gcm_set_climate(gcm_handle *h, int every) {
+    if (int rc = pe_only(h, "gcm_set_climate")) return rc;
+    if (every < 0) return fail(h, GCM_ERR_ARG, "gcm_set_climate: every must be >= 0");
+    if (int rc = select_device(h)) return rc;
+    return pe25d_set_climate(h->pe, every, h->stream, &h->err);
+}
+
+int gcm_climate_every(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_climate_every(h->pe) : 0;
+}
+
+int gcm_climate_sample(gcm_handle *h) {
+    if (int rc = pe_only(h, "gcm_climate_sample")) return rc;
+    if (int rc = select_device(h)) return rc;
+    return pe25d_climate_sample(h->pe, h->stream, &h->err);
+}
+
+int gcm_climate_reset(gcm_handle *h) {
+    if (int rc = pe_only(h, "gcm_climate_reset")) return rc;
+    if (int rc = select_device(h)) return rc;
+    return pe25d_climate_reset(h->pe, h->stream, &h->err);
+}
+
+int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples) {
+    if (int rc = pe_only(h, "gcm_get_climate")) return rc;
+    if (int rc = select_device(h)) return rc;
+    return pe25d_get_climate(h->pe, m3, m2, nsamples, h->stream, &h->err);
+}
+
+int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples) {
+    if (int rc = pe_only(h, "gcm_put_climate")) return rc;
+    if (int rc = select_device(h)) return rc;
+    return pe25d_put_climate(h->pe, m3, m2, nsamples, h->stream, &h->err);
 }
 
 int gcm_get_utc(gcm_handle *h, double *utc) {

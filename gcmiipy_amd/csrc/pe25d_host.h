@@ -6,6 +6,7 @@
 //   pe25d_diag.hip     diagnostics and taps: gcm_stats, the polar filter of a field, the stage's intermediates
 //   pe25d_tracers.hip  the passive tracers' host side
 //   pe25d_held_suarez.hip  the Held-Suarez forcing: its table routine, its kernel and its launches
+//   pe25d_climate.hip  the zonal-mean climatology: its kernel, its sums and their way to the host and back
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip and gcm_diag.hip see
 // pe25d_kernels.h only.
@@ -92,6 +93,14 @@ struct PeHeldSuarez {
     double par[5] = {};                         // T_min, T_0, dT_y, dtheta_z, (free): what the kernel takes by value
 };
 
+// Zonal-mean climatology (pe25d_climate.hip, gcm_set_climate): the float64 sums on the device and the two counters
+struct PeClimate {
+    double *buf = nullptr;                      // device: sig [L], m3 [GCM_CLIM_WORDS3][L][H], m2 [GCM_CLIM_WORDS2][H]
+    int every = 0;                              // a sample every so many steps; 0: not registered
+    long long steps = 0;                        // steps taken by gcm_step / gcm_band_run since the registration
+    long long n = 0;                            // samples in the sums
+};
+
 struct Pe25d {
     gcm_config cfg{};
     int W = 0, H = 0, L = 0, Hg = 0;
@@ -163,6 +172,7 @@ struct Pe25d {
     bool halo_fixed = false;
     PeTracers tr;
     PeHeldSuarez hs;
+    PeClimate clim;
 };
 
 template <typename T> inline PeBufs<T> &bufs(Pe25d *m);

@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
-// pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip and
-// pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip and gcm_diag.hip.
+// pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
+// pe25d_climate.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip and gcm_diag.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,6 +56,15 @@ int held_suarez_tables(int L, const double *sig, int nlat, const double *lat, co
 int held_suarez_check(const gcm_held_suarez *hs, const char *fn, std::string *err);
 int pe25d_hs_tables(Pe25d *m, const gcm_held_suarez *hs, double dt, hipStream_t s, std::string *err);
 int pe25d_hs_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, hipStream_t s, std::string *err);
+// Zonal-mean climatology (pe25d_climate.hip): gcm_set_climate and its companions on `s`, the caller's stream.
+// pe25d_climate_due: counts one step of gcm_step / gcm_band_run; true where that step ends with a sample
+int pe25d_set_climate(Pe25d *m, int every, hipStream_t s, std::string *err);
+int pe25d_climate_every(const Pe25d *m);
+bool pe25d_climate_due(Pe25d *m);
+int pe25d_climate_sample(Pe25d *m, hipStream_t s, std::string *err);
+int pe25d_climate_reset(Pe25d *m, hipStream_t s, std::string *err);
+int pe25d_get_climate(Pe25d *m, double *m3, double *m2, int64_t *nsamples, hipStream_t s, std::string *err);
+int pe25d_put_climate(Pe25d *m, const double *m3, const double *m2, int64_t nsamples, hipStream_t s, std::string *err);
 int pe25d_new_state_set(const Pe25d *m);    // the set a corrector stage in flight writes (before the swap), else the current one
 int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err);
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan

@@ -463,6 +463,48 @@ int gcm_held_suarez_on(const gcm_handle *h);
 int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs);
 int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
                            double *fu, double *kt, double *s2, double *c2);
+/* Zonal-mean climatology of GCM_PE25D accumulated on the device: what a Held-Suarez run is evaluated by -- the time and
+ * zonal means of u, v, theta and T, their variances and the eddy fluxes as functions of latitude and level -- without a
+ * host round trip per step (fp64 and fp32 handles, single domains and latitude bands).  One launch per sample reads
+ * the current state once and adds, per own row j and level k, the zonal sums over i = 0 .. W - 1 of the moments below
+ * to float64 sums that live in the handle; plain sums, not divided by W: the host divides by W nsamples.
+ * Values are widened exactly from the storage type; every product and sum is float64 and rounded on its own.
+ *   m3 [GCM_CLIM_WORDS3][L][H]:  0 u   1 v   2 theta   3 T = theta Pi   4 u u   5 v v   6 T T
+ *                                7 uc vc   8 vc T   9 vc theta          (u, v at their own C-grid points)
+ *   m2 [GCM_CLIM_WORDS2][H]:     0 p   1 p p
+ *   Pi = (p_lev / P0)^kappa, p_lev = sig[k] p + ptop, from the kernels' own Exner routine (the one the Held-Suarez
+ *   and radiation kernels use: within the 1e-10 of the parity tests of pow);
+ *   uc = 0.5 (u[i] + u[i - 1]), periodic in i;  vc = 0.5 (v[j] + v[j - 1]): the winds at the cell centre.
+ *   Row -1 of a single domain is row H - 1, the model's own pole-to-pole roll, reproduced and not fixed; on a band it
+ *   is the first north ghost row of v of the current state.
+ * Reduction order of a row's W terms -- a function of W alone, whatever H, the band, the number of CUs or the number of
+ * levels a workgroup walks: 256 partial sums, partial sum t takes i = t, t + 256, ... in that order, starting from
+ * 0.0; they are 4 groups of 64 (t / 64); within a group the 64 combine by the butterfly x[t] <- x[t] + x[t ^ d],
+ * d = 32, 16, 8, 4, 2, 1; the four groups' results are added in group order; the row's sum is then added to the
+ * accumulator word, sample after sample.  One writer per word and launch, no atomics: the same state gives the same
+ * bits, and a band's rows hold the bits of the same rows of the single domain.
+ * gcm_set_climate(every >= 1) allocates and zeroes the sums and the sample count and starts a step counter at 0; from
+ * then on every step taken by gcm_step and gcm_band_run ends -- behind the solar step and the Held-Suarez forcing --
+ * with a sample where the counter, incremented per step, is a multiple of `every`.  The counter runs across calls.
+ * gcm_half_step (and a band stepped by gcm_step_phase) never samples.  Registering again resets the sums; every = 0
+ * unregisters and frees; every < 0: GCM_ERR_ARG.  Without a registration nothing is launched and every result and
+ * timing is as before; a sample changes nothing a step reads.
+ * gcm_climate_every: the registered `every`, 0 without one (other models: 0; a null handle GCM_ERR_ARG).
+ * gcm_climate_sample: one sample now; the step counter is untouched.  On a band the ghost rows of the current state
+ * must be current, as for gcm_solar_step and gcm_held_suarez_step.
+ * gcm_climate_reset zeroes the sums and the count.  gcm_get_climate synchronises the handle's stream once and copies
+ * the sums and the count; any of the three pointers may be NULL.  gcm_put_climate uploads them (restarts); both
+ * arrays are required, nsamples >= 0.
+ * Errors: a null handle GCM_ERR_ARG; other models GCM_ERR_UNSUPPORTED (and a row too wide for the sample's LDS, more
+ * than ~7800 columns); get, put, reset or sample without a registration GCM_ERR_STATE.  A refused call changes nothing. */
+#define GCM_CLIM_WORDS3 10   /* moments per (level, row) */
+#define GCM_CLIM_WORDS2 2    /* moments per row          */
+int gcm_set_climate(gcm_handle *h, int every);
+int gcm_climate_every(const gcm_handle *h);
+int gcm_climate_sample(gcm_handle *h);
+int gcm_climate_reset(gcm_handle *h);
+int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples);
+int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples);
 
 /* Device-side snapshot / restore of the current state, ghost rows included (2-D models): a long
  * run can restart from a known state without a host round trip.  gcm_restore is asynchronous on
