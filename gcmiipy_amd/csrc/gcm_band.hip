@@ -1,5 +1,6 @@
 // gcm_band_run: the library-driven band loop and the ghost-row exchange it posts itself (gcm_set_exchange).  Host
-// code only; stepping and the ghost rows' pack / unpack are gcmcore.hip's, reached through gcm_handle.h and the C ABI.
+// code only; stepping and the ghost rows' pack / unpack are gcmcore.hip's and the phases behind a GCM_PE25D step are
+// gcm_pe.hip's, reached through gcm_handle.h and the C ABI.
 #include <cstdlib>
 
 #include "gcm_handle.h"
@@ -106,31 +107,19 @@ static int band_exchange(gcm_handle *h) {
 // reads ghost rows -- the next stage's K1, column sums, edge rows -- is queued on the second stream, behind
 // the unpack, in stream order.  gcm_band_run joins the two streams once, when it returns.
 // GCM_BAND_COMM_STREAM=1: the exchange on the comm stream and a join per stage, as in round 1.
-// With gcm_set_physics the step has a second phase, solar_timestep (no_limits_2_5d.py:66-75), which changes theta and
-// the ground temperature in place AFTER the post-corrector exchange has left: the ghost rows are radiated locally
-// (column-local kernel, the neighbour's own inputs -- theta and p as the exchange delivered them, the ground
-// temperature's ghost rows, the latitude of the global row -- hence the neighbour's own bits), on the second stream
-// right behind the unpack and ahead of the ghost rows' column sums and anchors; the band's own rows follow the
-// corrector on the compute stream, which by then has waited for the edge rows and their pack.
+// The phases registered behind the dynamics (solar step, Held-Suarez, the climatology's sample) are gcm_pe.hip's: the
+// ghost rows' on the second stream right behind the corrector's unpack and ahead of the ghost rows' column sums and
+// anchors (pe_ghost_row_phases), the own rows' at the end of the step on the compute stream (pe_own_row_phases), which
+// takes the ghost rows with it when the exchange was joined into the compute stream.
 static int band_step_pe(gcm_handle *h, double dt) {
     int rc = GCM_OK;
     hipStream_t ax = h->band.on_comm ? nullptr : pe25d_aux_stream(h->pe);
-    const int H = h->H;
     for (int stage = 0; stage < 2; ++stage) {
         if ((rc = pe25d_step_phase(h->pe, 2 * stage, dt, h->stream, &h->err, ax != nullptr))) return rc;
         if (ax) {
             if ((rc = band_post(h, ax))) return rc;
             if ((rc = gcm_halo_unpack2(h, h->band.xch.recv_north, h->band.xch.recv_south, ax))) return rc;
-            if (stage == 1 && h->phys_on && (rc = pe25d_solar_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, dt,
-                                                                   h->phys.utc, h->phys.albedo, ax, &h->err)))
-                return rc;
-            // gcm_set_held_suarez: the ghost rows of theta, u, v as the post-corrector exchange delivered them, forced
-            // locally (the neighbour's own inputs and tables, hence its own bits), behind the unpack and the ghost rows'
-            // solar step in stream order and AHEAD of the ghost rows' column sums and anchors, which read u, v and theta
-            // (the launch marks the state's column sums stale: pe25d_prep_ghost_rows then leaves them to the next stage)
-            if (stage == 1 && h->hs_on && (rc = pe25d_hs_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, ax,
-                                                              &h->err)))
-                return rc;
+            if (stage == 1 && (rc = pe_ghost_row_phases(h, dt, ax))) return rc;
             if ((rc = pe25d_prep_ghost_rows(h->pe, &h->err))) return rc;
             h->band.join_pending = true;
         }
@@ -140,40 +129,12 @@ static int band_step_pe(gcm_handle *h, double dt) {
             if ((rc = band_exchange(h))) return rc;
         }
     }
-    if (h->phys_on) {
-        // own rows (and, when the exchange was joined into the compute stream, the ghost rows with them)
-        const int g = ax ? 0 : kGhost;
-        if ((rc = pe25d_solar_rows(h->pe, -1, -g, H + g, 0, 0, ax != nullptr, dt, h->phys.utc, h->phys.albedo, h->stream, &h->err)))
-            return rc;
-        h->phys.utc += dt;
-    }
-    if (h->hs_on) {
-        // own rows (and the ghost rows with them where the exchange was joined into the compute stream), behind the corrector and the
-        // solar step: the compute stream has waited for the edge rows' pack by then (update_interior), so the rows that left are
-        // unforced and the neighbour forces them itself.  The launch invalidates the fork at the last K4 (pe25d_hs_rows): the next
-        // step's launches on the second and third stream, which read own rows' u and v, follow this stream's position
-        const int g = ax ? 0 : kGhost;
-        if ((rc = pe25d_hs_rows(h->pe, -1, -g, H + g, 0, 0, ax != nullptr, h->stream, &h->err))) return rc;
-    }
-    if (pe25d_climate_due(h->pe)) {
-        // gcm_set_climate: the sample reads the own rows as the phases above left them on the compute stream, and row -1 of v,
-        // the first north ghost row, as the post-corrector exchange delivered it and the ghost rows' Held-Suarez launch forced
-        // it -- on the second stream where the exchange runs there.  The compute stream joins that stream's tail first (the
-        // unpack, the ghost rows' physics, their column sums), on the steps that sample only; the event is gcm_band_run's own
-        // join event, which nobody else records between a run's first exchange and its end
-        if (ax) {
-            HIPCHK(h, hipEventRecord(h->band.ev_comm, ax));
-            HIPCHK(h, hipStreamWaitEvent(h->stream, h->band.ev_comm, 0));
-        }
-        if ((rc = pe25d_climate_sample(h->pe, h->stream, &h->err))) return rc;
-    }
-    return GCM_OK;
+    return pe_own_row_phases(h, dt, phase_ghosts(h, ax != nullptr), ax != nullptr, ax);
 }
 
 static int run_pe(gcm_handle *h, int nsteps, double dt) {
-    int rc = physics_tables(h);
+    int rc = pe_phase_tables(h, nsteps, dt);
     if (rc) return rc;
-    if (nsteps > 0 && (rc = held_suarez_step_tables(h, dt))) return rc;
     if (!h->band.primed) {                                 // ghost rows of the initial state (and of the ground temperature), once
         if ((rc = pack_edges(h)) || (rc = band_exchange(h))) return rc;
         h->band.primed = true;
@@ -292,6 +253,7 @@ static int run_deep_overlapped(gcm_handle *h, int nsteps, double dt) {
 //   run_pe, first exchange st                comm       st      pack -> ev_pack @ st, comm waits; group -> ev_comm @ comm, st waits
 //   run_pe, every stage    ax (pe25d: with   ax         ax      none per stage: stream order on ax.  When the run returns:
 //                          the edge rows)                       -> ev_comm @ ax, st waits
+//                                                               a step that ends with a climatology sample: -> ev_comm @ ax, st waits ahead of the sample
 //   .. GCM_BAND_COMM_STREAM=1  ax (as above) comm       st      comm waits for the edge rows' pack (pe25d_wait_edges); group -> ev_comm @ comm, st waits
 //   run_exchange_per_step  st                comm       st      pack -> ev_pack @ st, comm waits; group -> ev_comm @ comm, st waits ahead of the boundary rows
 //   run_deep               st                st         st      none: stream order

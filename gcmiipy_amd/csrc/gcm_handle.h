@@ -1,6 +1,7 @@
 // The handle behind the C ABI of include/gcmcore.h, private to gcmcore.hip (create / destroy, state transfer, the 2-D
-// step, ghost rows, timing), gcm_band.hip (gcm_band_run: the exchange the library posts itself) and gcm_diag.hip (the
-// reductions): the struct, the few helpers more than one of them uses, and what the other two reach in gcmcore.hip.
+// step, ghost rows, timing), gcm_band.hip (gcm_band_run: the exchange the library posts itself), gcm_diag.hip (the
+// reductions) and gcm_pe.hip (the GCM_PE25D-only entry points and the phases of a GCM_PE25D step): the struct, the few
+// helpers more than one of them uses, and what the others reach in gcmcore.hip and gcm_pe.hip.
 #pragma once
 #include "../../include/gcmcore.h"
 
@@ -30,6 +31,16 @@ struct GcmTiming {
     bool on = false;
     std::vector<hipEvent_t> ev, region;        // region: start / end of gcm_time_steps' timed region
     size_t used = 0;
+};
+
+// GCM_PE25D: the phases registered behind the dynamics of every step (gcm_pe.hip runs them; the climatology's
+// registration is Pe25d's own).  The records' table pointers are null: the vectors are the copies that are used
+struct GcmPhases {
+    bool solar = false;                        // gcm_set_physics: solar_timestep as the second phase of every step
+    bool held_suarez = false;                  // gcm_set_held_suarez: the forcing as the last phase that changes the state
+    gcm_physics phys{};                        // phys.utc is the clock: it advances by dt behind every solar step
+    gcm_held_suarez hs{};
+    std::vector<double> phys_lat, phys_lon, hs_lat;
 };
 
 struct gcm_handle {
@@ -72,16 +83,7 @@ struct gcm_handle {
     GcmTiming time;
     gcm::Pe25d *pe = nullptr;  // GCM_PE25D state (pe25d_kernels.h)
     GcmBandExchange band;
-
-    // gcm_set_physics: solar_timestep as the second phase of every step
-    bool phys_on = false;
-    gcm_physics phys{};
-    std::vector<double> phys_lat, phys_lon;
-
-    // gcm_set_held_suarez: the Held-Suarez forcing as the last phase of every step (hs.lat: null, hs_lat is the copy)
-    bool hs_on = false;
-    gcm_held_suarez hs{};
-    std::vector<double> hs_lat;
+    GcmPhases phases;
 };
 
 #define HIPCHK(h, call)                                                                    \
@@ -130,6 +132,11 @@ inline int pe_only(const gcm_handle *h, const char *fn, bool bands = false) {
     if (h->pe) return GCM_OK;
     return fail(const_cast<gcm_handle *>(h), GCM_ERR_UNSUPPORTED, std::string(fn) + (bands ? ": GCM_PE25D latitude bands only" : ": GCM_PE25D only"));
 }
+// ... and whose next calls go to the handle's device
+inline int pe_on_device(gcm_handle *h, const char *fn, bool bands = false) {
+    if (int rc = pe_only(h, fn, bands)) return rc;
+    return select_device(h);
+}
 inline int band_only(gcm_handle *h, const char *fn) {
     if (!h) return GCM_ERR_ARG;
     if (h->wrap) return fail(h, GCM_ERR_STATE, std::string(fn) + ": handle is not a latitude band");
@@ -140,7 +147,16 @@ inline int band_only(gcm_handle *h, const char *fn) {
 extern "C" void step_rows(gcm_handle *h, double dt, int j0, int j1, hipStream_t s);
 extern "C" void swap_state(gcm_handle *h);
 extern "C" int launch_status(gcm_handle *h);
-extern "C" int physics_tables(gcm_handle *h);
-extern "C" int held_suarez_step_tables(gcm_handle *h, double dt);   // the registered forcing's device tables for dt (none: GCM_OK)
+
+// gcm_pe.hip, for gcm_step and gcm_band_run: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, sample), each
+// launched only if it is registered -- their tables before a run, a band's ghost rows on its second stream `ax` behind a
+// corrector's unpack, and the end of every step on the handle's stream over rows [-g, H + g), which joins `tail` before a sample
+extern "C" int pe_step(gcm_handle *h, int nsteps, double dt);        // gcm_step of a GCM_PE25D handle
+extern "C" int pe_phase_tables(gcm_handle *h, int nsteps, double dt);
+extern "C" int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax);
+extern "C" int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail);
+// ghost rows a side that a phase's launch on the handle's stream takes with the own rows: a band's, unless they are
+// forced apart on the second stream (pe_ghost_row_phases)
+inline int phase_ghosts(const gcm_handle *h, bool apart = false) { return h->wrap || apart ? 0 : gcm::kGhost; }
 
 #pragma GCC visibility pop

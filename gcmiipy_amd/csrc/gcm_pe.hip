@@ -1,0 +1,325 @@
+// GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (solar step, Held-Suarez forcing,
+// climatology sample), written down once for gcm_step and gcm_band_run, and the entry points that serve GCM_PE25D handles
+// only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, climatology, the filter and the taps).
+// Host code only: a guard and one forwarding call into the pe25d_* units, through gcm_handle.h and pe25d_kernels.h.
+#include <cmath>
+
+#include "gcm_handle.h"
+
+using namespace gcm;
+
+// ------------------------------------------------------------------ the phases of a step
+// The order is the model's: the dynamics step, the solar step at the current clock, utc += dt, the Held-Suarez forcing,
+// the sample.  Each launch runs only if its phase is registered (GcmPhases; the climatology: pe25d_climate_due).
+
+// gcm_set_physics: the radiation kernel's tables in place before a run queues anything (no-op without physics); then the
+// registered forcing's device tables for dt (none: GCM_OK)
+int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
+    const GcmPhases &ph = h->phases;
+    if (ph.solar)
+        if (int rc = pe25d_physics_tables(h->pe, ph.phys.t_lw, ph.phys.t_sw, ph.phys_lat.data(), ph.phys_lon.data(), h->stream, &h->err))
+            return rc;
+    if (!ph.held_suarez || nsteps <= 0) return GCM_OK;
+    gcm_held_suarez hs = ph.hs;
+    hs.lat = ph.hs_lat.data();
+    return pe25d_hs_tables(h->pe, &hs, dt, h->stream, &h->err);
+}
+
+// gcm_band_run with the exchange on the second stream `ax`: the ghost rows' phases, behind a corrector's unpack.
+// With gcm_set_physics the step has a second phase, solar_timestep (no_limits_2_5d.py:66-75), which changes theta and
+// the ground temperature in place AFTER the post-corrector exchange has left: the ghost rows are radiated locally
+// (column-local kernel, the neighbour's own inputs -- theta and p as the exchange delivered them, the ground
+// temperature's ghost rows, the latitude of the global row -- hence the neighbour's own bits), on the second stream
+// right behind the unpack and ahead of the ghost rows' column sums and anchors; the band's own rows follow the
+// corrector on the compute stream, which by then has waited for the edge rows and their pack (pe_own_row_phases).
+int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax) {
+    const GcmPhases &ph = h->phases;
+    const int H = h->H;
+    if (ph.solar)
+        if (int rc = pe25d_solar_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, dt, ph.phys.utc, ph.phys.albedo, ax,
+                                      &h->err))
+            return rc;
+    // gcm_set_held_suarez: the ghost rows of theta, u, v as the post-corrector exchange delivered them, forced
+    // locally (the neighbour's own inputs and tables, hence its own bits), behind the unpack and the ghost rows'
+    // solar step in stream order and AHEAD of the ghost rows' column sums and anchors, which read u, v and theta
+    // (the launch marks the state's column sums stale: pe25d_prep_ghost_rows then leaves them to the next stage)
+    if (ph.held_suarez) return pe25d_hs_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, ax, &h->err);
+    return GCM_OK;
+}
+
+// The end of every step, on the handle's stream: rows [-g, H + g) (phase_ghosts).  tail: the stream whose tail the
+// handle's stream joins before a sample (gcm_band_run's second stream, where the exchange runs there), else null
+int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail) {
+    GcmPhases &ph = h->phases;
+    const int j0 = -g, j1 = h->H + g;
+    if (ph.solar) {
+        // no_limits_2_5d.py:229-234 with the physics below full_timestep's early return (:96): the dynamics
+        // step, then solar_timestep at the current utc, then utc += dt.  A band: own rows (and, when the exchange was
+        // joined into the compute stream, the ghost rows with them)
+        if (int rc = pe25d_solar_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, dt, ph.phys.utc, ph.phys.albedo, h->stream, &h->err)) return rc;
+        ph.phys.utc += dt;
+    }
+    // gcm_set_held_suarez: the last phase of the step that changes the state.  A band: own rows (and the ghost rows with
+    // them where the exchange was joined into the compute stream), behind the corrector and the solar step: the compute
+    // stream has waited for the edge rows' pack by then (update_interior), so the rows that left are unforced and the
+    // neighbour forces them itself.  The launch writes u and v, which the next stage's chain B reads: it invalidates the
+    // fork at the last K4 (pe25d_hs_rows), so that the next step's launches on the second and third stream, which read
+    // own rows' u and v, follow this stream's position
+    if (ph.held_suarez)
+        if (int rc = pe25d_hs_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, h->stream, &h->err)) return rc;
+    // gcm_set_climate: a sample of the state the step leaves, behind every phase that changes it
+    if (!pe25d_climate_due(h->pe)) return GCM_OK;
+    // a band: the sample reads the own rows as the phases above left them on the compute stream, and row -1 of v,
+    // the first north ghost row, as the post-corrector exchange delivered it and the ghost rows' Held-Suarez launch forced
+    // it -- on the second stream where the exchange runs there.  The compute stream joins that stream's tail first (the
+    // unpack, the ghost rows' physics, their column sums), on the steps that sample only; the event is gcm_band_run's own
+    // join event, which nobody else records between a run's first exchange and its end
+    if (tail) {
+        HIPCHK(h, hipEventRecord(h->band.ev_comm, tail));
+        HIPCHK(h, hipStreamWaitEvent(h->stream, h->band.ev_comm, 0));
+    }
+    return pe25d_climate_sample(h->pe, h->stream, &h->err);
+}
+
+// gcm_step of a GCM_PE25D handle (the caller has selected the device)
+int pe_step(gcm_handle *h, int nsteps, double dt) {
+    if (int rc = pe_phase_tables(h, nsteps, dt)) return rc;
+    for (int n = 0; n < nsteps; ++n) {
+        if (int rc = pe25d_step(h->pe, dt, h->stream, &h->err)) return rc;
+        if (int rc = pe_own_row_phases(h, dt, 0, false, nullptr)) return rc;
+    }
+    pe25d_join_tracers(h->pe, h->stream);             // (the passive tracers' tail on the second stream)
+    return GCM_OK;
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------ passive tracers
+int gcm_set_tracers(gcm_handle *h, int n, const double *c) {
+    if (int rc = pe_on_device(h, "gcm_set_tracers")) return rc;
+    const int rc = pe25d_set_tracers(h->pe, n, c, h->stream, &h->err);
+    if (rc == GCM_OK && !h->wrap) h->band.primed = false;   // gcm_band_run: the new tracers' ghost rows are not exchanged yet
+    return rc;
+}
+
+int gcm_set_band_tracers(gcm_handle *h, int n) {
+    if (int rc = pe_on_device(h, "gcm_set_band_tracers", true)) return rc;
+    return pe25d_set_band_tracers(h->pe, n, h->stream, &h->err);
+}
+
+int gcm_set_band_tracer_rows(gcm_handle *h, int rows) {
+    if (int rc = pe_on_device(h, "gcm_set_band_tracer_rows", true)) return rc;
+    return pe25d_set_band_tracer_rows(h->pe, rows, h->stream, &h->err);
+}
+
+int gcm_band_tracer_rows(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_band_tracer_rows(h->pe) : 0;
+}
+
+int gcm_get_tracers(gcm_handle *h, int which, double *c) {
+    if (int rc = pe_on_device(h, "gcm_get_tracers")) return rc;
+    return pe25d_get_tracers(h->pe, which, c, h->stream, &h->err);
+}
+
+int gcm_tracer_stats(gcm_handle *h, int which, int with_q, double *out, int cap) {
+    if (!h || !out) return GCM_ERR_ARG;
+    if (int rc = pe_on_device(h, "gcm_tracer_stats")) return rc;
+    return pe25d_tracer_stats(h->pe, which, with_q != 0, out, cap, h->stream, &h->err);
+}
+
+int gcm_set_tracer_forcing(gcm_handle *h, int tracer, const gcm_tracer_forcing *f) {
+    if (int rc = pe_on_device(h, "gcm_set_tracer_forcing")) return rc;
+    return pe25d_set_tracer_forcing(h->pe, tracer, f, h->stream, &h->err);
+}
+
+int gcm_tracer_forced(const gcm_handle *h, int tracer) {
+    if (int rc = pe_only(h, "gcm_tracer_forced")) return rc;
+    return pe25d_tracer_forced(h->pe, tracer);
+}
+
+int gcm_set_tracer_mixing(gcm_handle *h, int tracer, const double *k, int nk) {
+    if (int rc = pe_on_device(h, "gcm_set_tracer_mixing")) return rc;
+    return pe25d_set_tracer_mixing(h->pe, tracer, k, nk, h->stream, &h->err);
+}
+
+int gcm_tracer_mixed(const gcm_handle *h, int tracer) {
+    if (int rc = pe_only(h, "gcm_tracer_mixed")) return rc;
+    return pe25d_tracer_mixed(h->pe, tracer);
+}
+
+int gcm_tracer_mixing_coeffs(int L, const double *dsig, const double *k, double dtd, double *lo, double *w, double *g) {
+    return tracer_mixing_coeffs(L, dsig, k, dtd, lo, w, g, &gcm_create_error());
+}
+
+int gcm_tracer_count(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_tracer_count(h->pe) : 0;
+}
+
+int gcm_set_tracer_scheme(gcm_handle *h, int scheme) {
+    if (!h) return GCM_ERR_ARG;
+    if (scheme < GCM_TRACER_NONE || scheme > GCM_TRACER_VANLEER)
+        return fail(h, GCM_ERR_ARG, "gcm_set_tracer_scheme: scheme must be GCM_TRACER_NONE, _UPWIND or _VANLEER");
+    if (int rc = pe_on_device(h, "gcm_set_tracer_scheme")) return rc;
+    return pe25d_set_tracer_scheme(h->pe, scheme, h->stream, &h->err);
+}
+
+int gcm_tracer_scheme(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_tracer_scheme(h->pe) : GCM_TRACER_NONE;
+}
+
+// ------------------------------------------------------------------ a band's stages driven by the host
+int gcm_step_phase(gcm_handle *h, int phase, double dt, void *stream) {
+    if (int rc = pe_only(h, "gcm_step_phase", true)) return rc;
+    return pe25d_step_phase(h->pe, phase, dt, (hipStream_t)stream, &h->err);
+}
+
+int gcm_set_halo_buffers(gcm_handle *h, void *north_send, void *south_send) {
+    if (int rc = pe_only(h, "gcm_set_halo_buffers", true)) return rc;
+    return pe25d_set_halo_buffers(h->pe, north_send, south_send, h->stream, &h->err);
+}
+
+int gcm_wait_edges(gcm_handle *h, void *stream) {
+    if (int rc = pe_only(h, "gcm_wait_edges", true)) return rc;
+    return pe25d_wait_edges(h->pe, (hipStream_t)stream, &h->err);
+}
+
+// ------------------------------------------------------------------ ground temperature and grey physics
+int gcm_set_ground(gcm_handle *h, const double *gt) {
+    if (!h || !gt) return GCM_ERR_ARG;
+    if (int rc = pe_only(h, "gcm_set_ground")) return rc;
+    h->band.primed = false;                                // gcm_band_run: the ghost rows of the ground temperature travel again
+    return pe25d_ground(h->pe, true, gt, nullptr, h->stream, &h->err);
+}
+
+int gcm_get_ground(gcm_handle *h, double *gt) {
+    if (!h || !gt) return GCM_ERR_ARG;
+    if (int rc = pe_only(h, "gcm_get_ground")) return rc;
+    return pe25d_ground(h->pe, false, nullptr, gt, h->stream, &h->err);
+}
+
+int gcm_set_physics(gcm_handle *h, const gcm_physics *ph) {
+    if (int rc = pe_only(h, "gcm_set_physics")) return rc;
+    GcmPhases &p = h->phases;
+    if (!ph) {
+        p.solar = false;
+        return GCM_OK;
+    }
+    if (!ph->lat || !ph->lon) return fail(h, GCM_ERR_ARG, "gcm_set_physics: lat and lon tables are required");
+    p.phys = *ph;
+    p.phys_lat.assign(ph->lat, ph->lat + h->cfg.global_height);
+    p.phys_lon.assign(ph->lon, ph->lon + h->W);
+    p.phys.lat = p.phys.lon = nullptr;                     // (the copies above are what is used)
+    p.solar = true;
+    return GCM_OK;
+}
+
+int gcm_get_utc(gcm_handle *h, double *utc) {
+    if (!h || !utc) return GCM_ERR_ARG;
+    if (!h->phases.solar) return fail(h, GCM_ERR_STATE, "gcm_get_utc: no physics registered (gcm_set_physics)");
+    *utc = h->phases.phys.utc;
+    return GCM_OK;
+}
+
+int gcm_grey_radiation(gcm_handle *h, double utc, double t_lw, double t_sw, double albedo,
+                       const double *lat, const double *lon, double *dTdt, double *dt_ground) {
+    if (int rc = pe_only(h, "gcm_grey_radiation")) return rc;
+    return pe25d_radiation(h->pe, false, 0.0, utc, t_lw, t_sw, albedo, lat, lon, dTdt, dt_ground,
+                           h->stream, &h->err);
+}
+
+int gcm_solar_step(gcm_handle *h, double dt, double utc, double t_lw, double t_sw, double albedo,
+                   const double *lat, const double *lon) {
+    if (int rc = pe_only(h, "gcm_solar_step")) return rc;
+    return pe25d_radiation(h->pe, true, dt, utc, t_lw, t_sw, albedo, lat, lon, nullptr, nullptr,
+                           h->stream, &h->err);
+}
+
+// ------------------------------------------------------------------ Held-Suarez forcing
+int gcm_set_held_suarez(gcm_handle *h, const gcm_held_suarez *hs) {
+    if (int rc = pe_only(h, "gcm_set_held_suarez")) return rc;
+    GcmPhases &p = h->phases;
+    if (!hs) {
+        p.held_suarez = false;
+        return GCM_OK;
+    }
+    if (int rc = held_suarez_check(hs, "gcm_set_held_suarez", &h->err)) return rc;
+    for (int j = 0; j < h->cfg.global_height; ++j)
+        if (!std::isfinite(hs->lat[j])) return fail(h, GCM_ERR_ARG, "gcm_set_held_suarez: lat must be finite");
+    p.hs = *hs;
+    p.hs_lat.assign(hs->lat, hs->lat + h->cfg.global_height);
+    p.hs.lat = nullptr;                                    // (the copy above is what is used)
+    p.held_suarez = true;
+    return GCM_OK;
+}
+
+int gcm_held_suarez_on(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && h->phases.held_suarez ? 1 : 0;
+}
+
+int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs) {
+    if (int rc = pe_only(h, "gcm_held_suarez_step")) return rc;
+    if (int rc = held_suarez_check(hs, "gcm_held_suarez_step", &h->err)) return rc;
+    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_held_suarez_step: dt must be finite");
+    if (int rc = select_device(h)) return rc;
+    if (int rc = pe25d_hs_tables(h->pe, hs, dt, h->stream, &h->err)) return rc;
+    // a band: own rows and ghost rows, as gcm_solar_step (the ghost rows of the current state must be current)
+    const int g = phase_ghosts(h);
+    return pe25d_hs_rows(h->pe, -1, -g, h->H + g, 0, 0, false, h->stream, &h->err);
+}
+
+int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
+                           double *fu, double *kt, double *s2, double *c2) {
+    return held_suarez_tables(L, sig, nlat, lat, hs, dt, fu, kt, s2, c2, &gcm_create_error());
+}
+
+// ------------------------------------------------------------------ zonal-mean climatology
+int gcm_set_climate(gcm_handle *h, int every) {
+    if (int rc = pe_only(h, "gcm_set_climate")) return rc;
+    if (every < 0) return fail(h, GCM_ERR_ARG, "gcm_set_climate: every must be >= 0");
+    if (int rc = select_device(h)) return rc;
+    return pe25d_set_climate(h->pe, every, h->stream, &h->err);
+}
+
+int gcm_climate_every(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_climate_every(h->pe) : 0;
+}
+
+int gcm_climate_sample(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_climate_sample")) return rc;
+    return pe25d_climate_sample(h->pe, h->stream, &h->err);
+}
+
+int gcm_climate_reset(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_climate_reset")) return rc;
+    return pe25d_climate_reset(h->pe, h->stream, &h->err);
+}
+
+int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples) {
+    if (int rc = pe_on_device(h, "gcm_get_climate")) return rc;
+    return pe25d_get_climate(h->pe, m3, m2, nsamples, h->stream, &h->err);
+}
+
+int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples) {
+    if (int rc = pe_on_device(h, "gcm_put_climate")) return rc;
+    return pe25d_put_climate(h->pe, m3, m2, nsamples, h->stream, &h->err);
+}
+
+// ------------------------------------------------------------------ the filter of a field, the stage's intermediates
+int gcm_polar_filter(gcm_handle *h, int nlev, const double *in, double *out) {
+    if (!h || !in || !out) return GCM_ERR_ARG;
+    if (int rc = pe_on_device(h, "gcm_polar_filter")) return rc;
+    return pe25d_filter_field(h->pe, nlev, in, out, h->stream, &h->err);
+}
+
+int gcm_get_intermediate(gcm_handle *h, int kind, double *out) {
+    if (!h || !out) return GCM_ERR_ARG;
+    if (int rc = pe_on_device(h, "gcm_get_intermediate")) return rc;
+    return pe25d_intermediate(h->pe, kind, out, h->stream, &h->err);
+}
+
+}  // extern "C"

@@ -1,5 +1,7 @@
-// Host side of libgcmcore.so: the C ABI of include/gcmcore.h.
-// Owns device buffers, picks kernels, launches on the handle's stream.  There is
+// Host side of libgcmcore.so: the C ABI of include/gcmcore.h -- create / destroy, state transfer, the 2-D step, ghost
+// rows, snapshot / restore, members, gcm_sync, gcm_comm_stream, the band's step parts, gcm_half_step and gcm_time_steps.
+// (gcm_band_run: gcm_band.hip; the reductions: gcm_diag.hip; what serves GCM_PE25D handles only, gcm_step's GCM_PE25D
+// branch included: gcm_pe.hip.)  Owns device buffers, picks kernels, launches on the handle's stream.  There is
 // no CPU fallback anywhere in this file: without a HIP device gcm_create fails.
 #include <cmath>
 #include <cstdlib>
@@ -352,19 +354,6 @@ static bool run_fused2(const gcm_handle *h, const Sw2dArgs &a, hipStream_t s) {
     return h->f32 ? launch_sw2d_fused2(narrow_args(a), s) : launch_sw2d_fused2(a, s);
 }
 
-// gcm_set_physics: the radiation kernel's tables in place before a run queues anything (no-op without physics)
-int physics_tables(gcm_handle *h) {
-    if (!h->phys_on) return GCM_OK;
-    return pe25d_physics_tables(h->pe, h->phys.t_lw, h->phys.t_sw, h->phys_lat.data(), h->phys_lon.data(), h->stream, &h->err);
-}
-
-int held_suarez_step_tables(gcm_handle *h, double dt) {
-    if (!h->hs_on) return GCM_OK;
-    gcm_held_suarez hs = h->hs;
-    hs.lat = h->hs_lat.data();
-    return pe25d_hs_tables(h->pe, &hs, dt, h->stream, &h->err);
-}
-
 // what the launches queued since the last check returned: the status hipLaunchKernel handed back for the
 // fused step (kept in the handle: step_rows has many callers) and the runtime's sticky last error
 int launch_status(gcm_handle *h) {
@@ -465,28 +454,7 @@ void step_rows(gcm_handle *h, double dt, int j0, int j1, hipStream_t s) {
 int gcm_step(gcm_handle *h, int nsteps, double dt) {
     if (!h || nsteps < 0) return GCM_ERR_ARG;
     if (int rc = select_device(h)) return rc;
-    if (h->pe) {
-        int rc = physics_tables(h);
-        if (rc) return rc;
-        if (nsteps > 0 && (rc = held_suarez_step_tables(h, dt))) return rc;
-        for (int n = 0; n < nsteps; ++n) {
-            if ((rc = pe25d_step(h->pe, dt, h->stream, &h->err))) return rc;
-            if (h->phys_on) {
-                // no_limits_2_5d.py:229-234 with the physics below full_timestep's early return (:96): the dynamics
-                // step, then solar_timestep at the current utc, then utc += dt
-                if ((rc = pe25d_solar_rows(h->pe, -1, 0, h->H, 0, 0, false, dt, h->phys.utc, h->phys.albedo, h->stream, &h->err)))
-                    return rc;
-                h->phys.utc += dt;
-            }
-            // gcm_set_held_suarez: the last phase of the step.  The launch writes u and v, which the next stage's chain B
-            // reads: it invalidates the fork at the last K4 (pe25d_hs_rows), so that chain B follows this stream's position
-            if (h->hs_on && (rc = pe25d_hs_rows(h->pe, -1, 0, h->H, 0, 0, false, h->stream, &h->err))) return rc;
-            // gcm_set_climate: a sample of the state the step leaves, behind every phase that changes it
-            if (pe25d_climate_due(h->pe) && (rc = pe25d_climate_sample(h->pe, h->stream, &h->err))) return rc;
-        }
-        pe25d_join_tracers(h->pe, h->stream);             // (the passive tracers' tail on the second stream)
-        return GCM_OK;
-    }
+    if (h->pe) return pe_step(h, nsteps, dt);
     if (!h->wrap && h->since_exchange + nsteps > h->G / kGhost)
         return fail(h, GCM_ERR_STATE,
                     "gcm_step: a latitude band needs a ghost-row exchange every halo_steps steps");
@@ -518,89 +486,6 @@ int gcm_step(gcm_handle *h, int nsteps, double dt) {
     return launch_status(h);
 }
 
-int gcm_set_tracers(gcm_handle *h, int n, const double *c) {
-    if (int rc = pe_only(h, "gcm_set_tracers")) return rc;
-    if (int rc = select_device(h)) return rc;
-    const int rc = pe25d_set_tracers(h->pe, n, c, h->stream, &h->err);
-    if (rc == GCM_OK && !h->wrap) h->band.primed = false;   // gcm_band_run: the new tracers' ghost rows are not exchanged yet
-    return rc;
-}
-
-int gcm_set_band_tracers(gcm_handle *h, int n) {
-    if (int rc = pe_only(h, "gcm_set_band_tracers", true)) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_set_band_tracers(h->pe, n, h->stream, &h->err);
-}
-
-int gcm_set_band_tracer_rows(gcm_handle *h, int rows) {
-    if (int rc = pe_only(h, "gcm_set_band_tracer_rows", true)) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_set_band_tracer_rows(h->pe, rows, h->stream, &h->err);
-}
-
-int gcm_band_tracer_rows(const gcm_handle *h) {
-    if (!h) return GCM_ERR_ARG;
-    return h->pe ? pe25d_band_tracer_rows(h->pe) : 0;
-}
-
-int gcm_get_tracers(gcm_handle *h, int which, double *c) {
-    if (int rc = pe_only(h, "gcm_get_tracers")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_get_tracers(h->pe, which, c, h->stream, &h->err);
-}
-
-int gcm_tracer_stats(gcm_handle *h, int which, int with_q, double *out, int cap) {
-    if (!h || !out) return GCM_ERR_ARG;
-    if (int rc = pe_only(h, "gcm_tracer_stats")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_tracer_stats(h->pe, which, with_q != 0, out, cap, h->stream, &h->err);
-}
-
-int gcm_set_tracer_forcing(gcm_handle *h, int tracer, const gcm_tracer_forcing *f) {
-    if (int rc = pe_only(h, "gcm_set_tracer_forcing")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_set_tracer_forcing(h->pe, tracer, f, h->stream, &h->err);
-}
-
-int gcm_tracer_forced(const gcm_handle *h, int tracer) {
-    if (int rc = pe_only(h, "gcm_tracer_forced")) return rc;
-    return pe25d_tracer_forced(h->pe, tracer);
-}
-
-int gcm_set_tracer_mixing(gcm_handle *h, int tracer, const double *k, int nk) {
-    if (int rc = pe_only(h, "gcm_set_tracer_mixing")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_set_tracer_mixing(h->pe, tracer, k, nk, h->stream, &h->err);
-}
-
-int gcm_tracer_mixed(const gcm_handle *h, int tracer) {
-    if (int rc = pe_only(h, "gcm_tracer_mixed")) return rc;
-    return pe25d_tracer_mixed(h->pe, tracer);
-}
-
-int gcm_tracer_mixing_coeffs(int L, const double *dsig, const double *k, double dtd, double *lo, double *w, double *g) {
-    return tracer_mixing_coeffs(L, dsig, k, dtd, lo, w, g, &gcm_create_error());
-}
-
-int gcm_tracer_count(const gcm_handle *h) {
-    if (!h) return GCM_ERR_ARG;
-    return h->pe ? pe25d_tracer_count(h->pe) : 0;
-}
-
-int gcm_set_tracer_scheme(gcm_handle *h, int scheme) {
-    if (!h) return GCM_ERR_ARG;
-    if (scheme < GCM_TRACER_NONE || scheme > GCM_TRACER_VANLEER)
-        return fail(h, GCM_ERR_ARG, "gcm_set_tracer_scheme: scheme must be GCM_TRACER_NONE, _UPWIND or _VANLEER");
-    if (int rc = pe_only(h, "gcm_set_tracer_scheme")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_set_tracer_scheme(h->pe, scheme, h->stream, &h->err);
-}
-
-int gcm_tracer_scheme(const gcm_handle *h) {
-    if (!h) return GCM_ERR_ARG;
-    return h->pe ? pe25d_tracer_scheme(h->pe) : GCM_TRACER_NONE;
-}
-
 int gcm_step_interior(gcm_handle *h, double dt, void *stream) {
     if (!h) return GCM_ERR_ARG;
     if (h->pe) return pe25d_step_part(h->pe, 0, dt, (hipStream_t)stream, &h->err);
@@ -626,11 +511,6 @@ int gcm_step_boundary(gcm_handle *h, double dt, void *stream) {
     return launch_status(h);
 }
 
-int gcm_step_phase(gcm_handle *h, int phase, double dt, void *stream) {
-    if (int rc = pe_only(h, "gcm_step_phase", true)) return rc;
-    return pe25d_step_phase(h->pe, phase, dt, (hipStream_t)stream, &h->err);
-}
-
 int gcm_comm_stream(gcm_handle *h, void **stream) {
     if (!h || !stream) return GCM_ERR_ARG;
     if (!h->comm) {
@@ -640,16 +520,6 @@ int gcm_comm_stream(gcm_handle *h, void **stream) {
     }
     *stream = (void *)h->comm;
     return GCM_OK;
-}
-
-int gcm_set_halo_buffers(gcm_handle *h, void *north_send, void *south_send) {
-    if (int rc = pe_only(h, "gcm_set_halo_buffers", true)) return rc;
-    return pe25d_set_halo_buffers(h->pe, north_send, south_send, h->stream, &h->err);
-}
-
-int gcm_wait_edges(gcm_handle *h, void *stream) {
-    if (int rc = pe_only(h, "gcm_wait_edges", true)) return rc;
-    return pe25d_wait_edges(h->pe, (hipStream_t)stream, &h->err);
 }
 
 int gcm_half_step(gcm_handle *h, int stage, double dt) {
@@ -802,142 +672,6 @@ int gcm_get_member(gcm_handle *h, int m, double *p, double *u, double *v, double
     if (h->pe) return gcm_get_state(h, p, u, v, t, q);
     double *dst[GCM_NFIELDS] = {p, u, v, t, q};
     return xfer(h, h->cur, nullptr, dst, false, m);
-}
-
-int gcm_set_ground(gcm_handle *h, const double *gt) {
-    if (!h || !gt) return GCM_ERR_ARG;
-    if (int rc = pe_only(h, "gcm_set_ground")) return rc;
-    h->band.primed = false;                                // gcm_band_run: the ghost rows of the ground temperature travel again
-    return pe25d_ground(h->pe, true, gt, nullptr, h->stream, &h->err);
-}
-
-int gcm_set_physics(gcm_handle *h, const gcm_physics *ph) {
-    if (int rc = pe_only(h, "gcm_set_physics")) return rc;
-    if (!ph) {
-        h->phys_on = false;
-        return GCM_OK;
-    }
-    if (!ph->lat || !ph->lon) return fail(h, GCM_ERR_ARG, "gcm_set_physics: lat and lon tables are required");
-    h->phys = *ph;
-    h->phys_lat.assign(ph->lat, ph->lat + h->cfg.global_height);
-    h->phys_lon.assign(ph->lon, ph->lon + h->W);
-    h->phys.lat = h->phys.lon = nullptr;                   // (the copies above are what is used)
-    h->phys_on = true;
-    return GCM_OK;
-}
-
-int gcm_set_held_suarez(gcm_handle *h, const gcm_held_suarez *hs) {
-    if (int rc = pe_only(h, "gcm_set_held_suarez")) return rc;
-    if (!hs) {
-        h->hs_on = false;
-        return GCM_OK;
-    }
-    if (int rc = held_suarez_check(hs, "gcm_set_held_suarez", &h->err)) return rc;
-    for (int j = 0; j < h->cfg.global_height; ++j)
-        if (!std::isfinite(hs->lat[j])) return fail(h, GCM_ERR_ARG, "gcm_set_held_suarez: lat must be finite");
-    h->hs = *hs;
-    h->hs_lat.assign(hs->lat, hs->lat + h->cfg.global_height);
-    h->hs.lat = nullptr;                                   // (the copy above is what is used)
-    h->hs_on = true;
-    return GCM_OK;
-}
-
-int gcm_held_suarez_on(const gcm_handle *h) {
-    if (!h) return GCM_ERR_ARG;
-    return h->pe && h->hs_on ? 1 : 0;
-}
-
-int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs) {
-    if (int rc = pe_only(h, "gcm_held_suarez_step")) return rc;
-    if (int rc = held_suarez_check(hs, "gcm_held_suarez_step", &h->err)) return rc;
-    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_held_suarez_step: dt must be finite");
-    if (int rc = select_device(h)) return rc;
-    if (int rc = pe25d_hs_tables(h->pe, hs, dt, h->stream, &h->err)) return rc;
-    // a band: own rows and ghost rows, as gcm_solar_step (the ghost rows of the current state must be current)
-    const int g = h->wrap ? 0 : kGhost;
-    return pe25d_hs_rows(h->pe, -1, -g, h->H + g, 0, 0, false, h->stream, &h->err);
-}
-
-int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
-                           double *fu, double *kt, double *s2, double *c2) {
-    return held_suarez_tables(L, sig, nlat, lat, hs, dt, fu, kt, s2, c2, &gcm_create_error());
-}
-
-int gcm_set_climate(gcm_handle *h, int every) {
-    if (int rc = pe_only(h, "gcm_set_climate")) return rc;
-    if (every < 0) return fail(h, GCM_ERR_ARG, "gcm_set_climate: every must be >= 0");
-    if (int rc = select_device(h)) return rc;
-    return pe25d_set_climate(h->pe, every, h->stream, &h->err);
-}
-
-int gcm_climate_every(const gcm_handle *h) {
-    if (!h) return GCM_ERR_ARG;
-    return h->pe ? pe25d_climate_every(h->pe) : 0;
-}
-
-int gcm_climate_sample(gcm_handle *h) {
-    if (int rc = pe_only(h, "gcm_climate_sample")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_climate_sample(h->pe, h->stream, &h->err);
-}
-
-int gcm_climate_reset(gcm_handle *h) {
-    if (int rc = pe_only(h, "gcm_climate_reset")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_climate_reset(h->pe, h->stream, &h->err);
-}
-
-int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples) {
-    if (int rc = pe_only(h, "gcm_get_climate")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_get_climate(h->pe, m3, m2, nsamples, h->stream, &h->err);
-}
-
-int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples) {
-    if (int rc = pe_only(h, "gcm_put_climate")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_put_climate(h->pe, m3, m2, nsamples, h->stream, &h->err);
-}
-
-int gcm_get_utc(gcm_handle *h, double *utc) {
-    if (!h || !utc) return GCM_ERR_ARG;
-    if (!h->phys_on) return fail(h, GCM_ERR_STATE, "gcm_get_utc: no physics registered (gcm_set_physics)");
-    *utc = h->phys.utc;
-    return GCM_OK;
-}
-
-int gcm_polar_filter(gcm_handle *h, int nlev, const double *in, double *out) {
-    if (!h || !in || !out) return GCM_ERR_ARG;
-    if (int rc = pe_only(h, "gcm_polar_filter")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_filter_field(h->pe, nlev, in, out, h->stream, &h->err);
-}
-
-int gcm_get_intermediate(gcm_handle *h, int kind, double *out) {
-    if (!h || !out) return GCM_ERR_ARG;
-    if (int rc = pe_only(h, "gcm_get_intermediate")) return rc;
-    if (int rc = select_device(h)) return rc;
-    return pe25d_intermediate(h->pe, kind, out, h->stream, &h->err);
-}
-
-int gcm_get_ground(gcm_handle *h, double *gt) {
-    if (!h || !gt) return GCM_ERR_ARG;
-    if (int rc = pe_only(h, "gcm_get_ground")) return rc;
-    return pe25d_ground(h->pe, false, nullptr, gt, h->stream, &h->err);
-}
-
-int gcm_grey_radiation(gcm_handle *h, double utc, double t_lw, double t_sw, double albedo,
-                       const double *lat, const double *lon, double *dTdt, double *dt_ground) {
-    if (int rc = pe_only(h, "gcm_grey_radiation")) return rc;
-    return pe25d_radiation(h->pe, false, 0.0, utc, t_lw, t_sw, albedo, lat, lon, dTdt, dt_ground,
-                           h->stream, &h->err);
-}
-
-int gcm_solar_step(gcm_handle *h, double dt, double utc, double t_lw, double t_sw, double albedo,
-                   const double *lat, const double *lon) {
-    if (int rc = pe_only(h, "gcm_solar_step")) return rc;
-    return pe25d_radiation(h->pe, true, dt, utc, t_lw, t_sw, albedo, lat, lon, nullptr, nullptr,
-                           h->stream, &h->err);
 }
 
 int gcm_time_steps(gcm_handle *h, int nsteps, double dt, double *ms, double *kernel_ms_avg) {

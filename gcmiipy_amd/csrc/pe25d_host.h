@@ -8,8 +8,9 @@
 //   pe25d_held_suarez.hip  the Held-Suarez forcing: its table routine, its kernel and its launches
 //   pe25d_climate.hip  the zonal-mean climatology: its kernel, its sums and their way to the host and back
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
-// of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip and gcm_diag.hip see
-// pe25d_kernels.h only.
+// of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
+// gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
+// pe25d_hs_rows, pe25d_climate_due, pe25d_climate_sample).
 #pragma once
 #include "pe25d_kernels.h"
 

@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip and gcm_diag.hip.
+// pe25d_climate.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

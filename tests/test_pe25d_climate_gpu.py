@@ -337,6 +337,64 @@ def test_loopback_band_run_equals_the_single_domain(dtype):
     c.close()
 
 
+_three_phase_cache = {}
+
+
+def three_phase_reference(g, dtype):
+    """the single domain with physics, Held-Suarez and every = 2 after step(4): (sums, state, ground, utc), once per type"""
+    if dtype not in _three_phase_cache:
+        H, W, L = BAND_SHAPE
+        geom = geom_of(H, W, L)
+        c = single(g, geom, state_of(geom, dtype), dtype, gt=ground_of(H, W), phys=True, hs=True, every=2)
+        c.step(4, DT)
+        sums, state, gt, utc = c.climate_sums(), c.get_state(), c.get_ground(), c.utc()
+        c.close()
+        for a in list(sums[1:]) + state + [gt]:
+            a.setflags(write=False)
+        _three_phase_cache[dtype] = (sums, state, gt, utc)
+    return _three_phase_cache[dtype]
+
+
+@pytest.mark.parametrize("comm_stream", [False, True], ids=["second-stream", "comm-stream"])
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_loopback_band_run_with_all_three_phases(dtype, comm_stream, monkeypatch):
+    """physics, Held-Suarez and the climatology registered together on the loopback band of gcm_band_run, the exchange on
+    the library's second stream or (GCM_BAND_COMM_STREAM=1, read by gcm_set_exchange) on the comm stream; 3 + 1 steps
+    with every = 2, so the first run ends between two samples.  State, ground temperature, clock and sums are the single
+    domain's after step(4), bit for bit"""
+    import torch
+    import gcmiipy_amd as g
+    from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange
+    H, W, L = BAND_SHAPE
+    want, want_state, want_gt, want_utc = three_phase_reference(g, dtype)
+    assert want[0] == 2 and want_utc == UTC0 + 4 * DT
+    geom = geom_of(H, W, L)
+    if comm_stream:
+        monkeypatch.setenv("GCM_BAND_COMM_STREAM", "1")
+    else:
+        monkeypatch.delenv("GCM_BAND_COMM_STREAM", raising=False)
+    c = g.Core(g._lib.PE25D, W, H, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0, dtype=dtype,
+               stream=torch.cuda.current_stream().cuda_stream)
+    eng = HipBandEngine(c, torch)
+    c.set_ground(ground_of(H, W))
+    eng.set_physics(geom, UTC0)
+    eng.set_held_suarez(geom)
+    eng.set_climate(2)
+    runner = BandRunner(eng, 0, 2, LoopbackExchange(), north=0, south=0)
+    assert runner.native
+    c.set_state(*state_of(geom, dtype))
+    runner.run(3, DT)
+    runner.run(1, DT)
+    torch.cuda.synchronize()
+    merged, raw = merged_sums([c])
+    assert_sums_equal(raw, want, "loopback, three phases")
+    for k, x, y in zip("puvtq", c.get_state(), want_state):
+        assert np.array_equal(x, y), k
+    assert np.array_equal(c.get_ground(), want_gt)
+    assert c.utc() == want_utc
+    c.close()
+
+
 def test_band_run_under_every_switch_in_child_processes(tmp_path):
     """the loopback band at 48 x 1440 x 24 (kernels of tens of microseconds on either stream), Held-Suarez registered,
     every = 1, 4 steps, both real types, once per orchestration switch: each run in a fresh process under its own time
