@@ -20,6 +20,7 @@ F64, F32 = 0, 1
 MAX_TRACERS = 16                     # GCM_MAX_TRACERS
 TRACER_STATS_WORDS = 6               # GCM_TRACER_STATS_WORDS
 CLIM_WORDS3, CLIM_WORDS2 = 10, 2     # GCM_CLIM_WORDS3, GCM_CLIM_WORDS2
+SW2D_PLAN_WORDS = 9                  # GCM_SW2D_PLAN_WORDS
 ADV_UPWIND, ADV_FV_UPWIND, ADV_FV_PLAIN, ADV_VANLEER, ADV_MOMENTUM = range(5)
 DIAG_ANY_NAN, DIAG_MAX_U, DIAG_MEAN_P, DIAG_SUM_P, DIAG_MIN_U, DIAG_MAX_V, DIAG_MIN_V = range(7)
 DIAG_TV_P, DIAG_TV_U, DIAG_TV_V, DIAG_TV_T, DIAG_TV_Q = range(7, 12)
@@ -104,6 +105,7 @@ SYMBOLS = {
     "gcm_get_member": (C.c_int, [_H, C.c_int] + [C.c_void_p] * 5),
     "gcm_diag_members": (C.c_int, [_H, C.c_int, _dp, C.c_int]),
     "gcm_step": (C.c_int, [_H, C.c_int, C.c_double]),
+    "gcm_sw2d_plan": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "gcm_half_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_get_star": (C.c_int, [_H] + [C.c_void_p] * 5),
     "gcm_set_star": (C.c_int, [_H] + [C.c_void_p] * 5),

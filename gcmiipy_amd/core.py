@@ -501,6 +501,17 @@ class Core:
     def step(self, nsteps, dt):
         _check(lib.gcm_step(self._h, int(nsteps), float(dt)), self._h)
 
+    def sw2d_plan(self, nsteps):
+        """what step(nsteps, .) of a 2-D handle would launch, without launching anything (gcm_sw2d_plan): a dict of
+        variant ("fused" / "staged"), rows_per_band, cols (columns per lane), strip and strip2 (the strip width in
+        columns of the single-step and of the two-step kernel), two_step_launches, single_step_launches, preload and
+        stream (the single-step kernel's form).  GCM_SW2D_TWO_STEP is read by this call as step reads it"""
+        out = (C.c_int * _lib.SW2D_PLAN_WORDS)()
+        _check(lib.gcm_sw2d_plan(self._h, int(nsteps), out, _lib.SW2D_PLAN_WORDS), self._h)
+        return dict(variant={_lib.VARIANT_FUSED: "fused", _lib.VARIANT_STAGED: "staged"}[out[0]],
+                    rows_per_band=out[1], cols=out[2], strip=out[3], strip2=out[4], two_step_launches=out[5],
+                    single_step_launches=out[6], preload=bool(out[7]), stream=bool(out[8]))
+
     def half_step(self, stage, dt):
         _check(lib.gcm_half_step(self._h, int(stage), float(dt)), self._h)
 

@@ -451,6 +451,31 @@ void step_rows(gcm_handle *h, double dt, int j0, int j1, hipStream_t s) {
     }
 }
 
+// the argument block of a two-step launch: all rows of the (periodic) grid
+static Sw2dArgs fused2_args(gcm_handle *h, double dt) {
+    Sw2dArgs a = base_args(h, dt);
+    a.ou = h->nxt[GCM_U];
+    a.ov = h->nxt[GCM_V];
+    a.op = h->nxt[GCM_P];
+    a.j0 = 0;
+    a.j1 = h->H;
+    return a;
+}
+
+// Whether gcm_step takes its steps in pairs, two per launch (sw2d_fused2_kernel; small grids): plain shallow water,
+// periodic rows, the fused variant, no per-launch timing, GCM_SW2D_TWO_STEP not 0 (read per call), and a geometry the
+// two-step kernel serves.  Shared by gcm_step and gcm_sw2d_plan.
+static bool steps_in_pairs(gcm_handle *h) {
+    if (h->cfg.model != GCM_SW2D || !h->wrap || h->variant != GCM_VARIANT_FUSED || h->time.on) return false;
+    if (getenv("GCM_SW2D_TWO_STEP") && getenv("GCM_SW2D_TWO_STEP")[0] == '0') return false;
+    const Sw2dArgs a = fused2_args(h, 0.0);
+    return sw2d_fused2_serves(a.wrap_j, a.j0, a.j1, a.H, a.rows_per_band);
+}
+
+// the rows a band's next single step produces beyond its own, per side: each step consumes two ghost rows per side;
+// the rows still valid shrink towards the interior until the next exchange (communication-avoiding deep halo)
+static int step_extra_rows(const gcm_handle *h) { return h->wrap ? 0 : h->G - kGhost * (h->since_exchange + 1); }
+
 int gcm_step(gcm_handle *h, int nsteps, double dt) {
     if (!h || nsteps < 0) return GCM_ERR_ARG;
     if (int rc = select_device(h)) return rc;
@@ -459,31 +484,49 @@ int gcm_step(gcm_handle *h, int nsteps, double dt) {
         return fail(h, GCM_ERR_STATE,
                     "gcm_step: a latitude band needs a ghost-row exchange every halo_steps steps");
     int n0 = 0;
-    if (h->cfg.model == GCM_SW2D && h->wrap && h->variant == GCM_VARIANT_FUSED && !h->time.on &&
-        !(getenv("GCM_SW2D_TWO_STEP") && getenv("GCM_SW2D_TWO_STEP")[0] == '0')) {
-        // small grids: pairs of steps in one launch (sw2d_fused2_kernel)
+    if (steps_in_pairs(h)) {
         while (nsteps - n0 >= 2) {
-            Sw2dArgs a = base_args(h, dt);
-            a.ou = h->nxt[GCM_U];
-            a.ov = h->nxt[GCM_V];
-            a.op = h->nxt[GCM_P];
-            a.j0 = 0;
-            a.j1 = h->H;
-            if (!run_fused2(h, a, h->stream)) break;
+            // (the geometry is one the kernel serves: a refusal here is the runtime's, and an error)
+            if (!run_fused2(h, fused2_args(h, dt), h->stream)) {
+                h->launch_refused = true;
+                return launch_status(h);
+            }
             swap_state(h);
             n0 += 2;
         }
     }
     for (int n = n0; n < nsteps; ++n) {
-        // bands: each step consumes two ghost rows per side; the rows still valid shrink towards
-        // the interior until the next exchange (communication-avoiding deep halo)
-        const int e = h->wrap ? 0 : h->G - kGhost * (h->since_exchange + 1);
+        const int e = step_extra_rows(h);
         step_rows(h, dt, -e, h->H + e, h->stream);
         swap_state(h);
         if (!h->wrap) ++h->since_exchange;
     }
     h->star_valid = false;
     return launch_status(h);
+}
+
+// out: variant, rows per band, columns per lane, strip width of the single-step and of the two-step kernel, two-step
+// launches, single steps, preloading form, STREAM form (include/gcmcore.h) -- from the expressions gcm_step and the
+// launchers use themselves
+int gcm_sw2d_plan(gcm_handle *h, int nsteps, int *out, int nout) {
+    if (!h || h->pe || nsteps < 0 || !out || nout < GCM_SW2D_PLAN_WORDS) return GCM_ERR_ARG;
+    const bool fused = h->variant == GCM_VARIANT_FUSED;
+    const bool temp = h->cfg.model == GCM_SW2D_TEMP;
+    const int pairs = steps_in_pairs(h) ? nsteps / 2 : 0;
+    const int e = step_extra_rows(h);
+    Sw2dFusedForm f{false, false};
+    if (fused)
+        f = sw2d_fused_form(temp, h->has[GCM_Q] ? h->cfg.tracer : 0, h->rows_per_band, h->W, h->H + 2 * e, h->M, h->esz);
+    out[0] = h->variant;
+    out[1] = fused ? h->rows_per_band : 0;
+    out[2] = fused ? h->cols : 0;
+    out[3] = fused ? sw2d_fused_strip_cols(h->cols) : 0;
+    out[4] = fused ? kStrip2Cols : 0;
+    out[5] = pairs;
+    out[6] = nsteps - 2 * pairs;
+    out[7] = f.preload;
+    out[8] = f.stream;
+    return GCM_OK;
 }
 
 int gcm_step_interior(gcm_handle *h, double dt, void *stream) {

@@ -374,7 +374,7 @@ template <typename T, bool TEMP, int TRACER, bool WRAPJ, int PRE = 0, bool STREA
 __global__ __launch_bounds__(64) void sw2d_fused_kernel(Sw2dArgsT<T> a0) {
     using Ctx = FusedCtx<T, TEMP, TRACER, WRAPJ, STREAM, CPL>;
     using V = typename Ctx::Real;
-    constexpr int kCols = CPL * kStripCols;   // output columns per wave
+    constexpr int kCols = sw2d_fused_strip_cols(CPL);   // output columns per wave
     const int W = a0.W;
     const int lane = threadIdx.x;
     // Tile = (member, band, strip), strips fastest.  Workgroups are dealt round-robin over the 8
@@ -454,8 +454,7 @@ __global__ __launch_bounds__(64) void sw2d_fused_kernel(Sw2dArgsT<T> a0) {
 // rows behind, and only its results go to memory.  Per step the halo grows by two cells each way:
 // 56 of the 64 lanes and RPB of the RPB + 4 first-step rows are output.  Rows of the band are all
 // loaded up front (compile-time indexed), the iterations are unrolled with both windows rotated by
-// name.  Periodic rows only (a single band).
-constexpr int kStrip2Cols = 56;
+// name.  Periodic rows only (a single band).  (kStrip2Cols: sw2d_kernels.h)
 
 template <typename T>
 struct Out3 {
@@ -578,7 +577,7 @@ __global__ __launch_bounds__(64) void sw2d_fused2_kernel(Sw2dArgsT<T> a0) {
 // two Matsuno steps of GCM_SW2D in one launch; needs wrap_j, rows_per_band in 2..4
 template <typename T>
 bool launch_sw2d_fused2(const Sw2dArgsT<T> &a, hipStream_t s) {
-    if (!a.wrap_j || a.j0 != 0 || a.j1 != a.H || a.rows_per_band < 2 || a.rows_per_band > 4) return false;
+    if (!sw2d_fused2_serves(a.wrap_j, a.j0, a.j1, a.H, a.rows_per_band)) return false;
     const int strips = (a.W + kStrip2Cols - 1) / kStrip2Cols;
     const int bands = (a.H + a.rows_per_band - 1) / a.rows_per_band;
     dim3 g((unsigned)(((long)strips * bands * a.members + 7) / 8 * 8));
@@ -591,8 +590,6 @@ bool launch_sw2d_fused2(const Sw2dArgsT<T> &a, hipStream_t s) {
     return hipLaunchKernel(fn, g, dim3(64), params, 0, s) == hipSuccess;
 }
 
-constexpr int kPreloadRows = 4;     // bands of up to this many rows use the preloading variant (plain SW2D)
-
 template <typename T, bool TEMP, int TRACER, int CPL = 1>
 static const void *fused_fn(bool wrap, bool stream) {
     if (stream)
@@ -602,10 +599,11 @@ static const void *fused_fn(bool wrap, bool stream) {
                 : (const void *)sw2d_fused_kernel<T, TEMP, TRACER, false, 0, false, CPL>;
 }
 
+// (preload, stream: sw2d_fused_form; kPreloadRows: sw2d_kernels.h)
 template <typename T, int CPL>
-static const void *fused_kernel_ptr_c(bool temp, int tracer, bool wrap, int rows_per_band, bool stream) {
+static const void *fused_kernel_ptr_c(bool temp, int tracer, bool wrap, bool preload, bool stream) {
     if (!temp) {
-        if (rows_per_band <= kPreloadRows)
+        if (preload)
             return wrap ? (const void *)sw2d_fused_kernel<T, false, 0, true, kPreloadRows, false, CPL>
                         : (const void *)sw2d_fused_kernel<T, false, 0, false, kPreloadRows, false, CPL>;
         return fused_fn<T, false, 0, CPL>(wrap, stream);
@@ -618,11 +616,11 @@ static const void *fused_kernel_ptr_c(bool temp, int tracer, bool wrap, int rows
 // stream: the rows this launch reads are far more than the caches hold (see FusedCtx); cols: columns per lane
 // (2: T = float and an even width only)
 template <typename T>
-static const void *fused_kernel_ptr(bool temp, int tracer, bool wrap, int rows_per_band = 1 << 30, bool stream = false,
+static const void *fused_kernel_ptr(bool temp, int tracer, bool wrap, bool preload = false, bool stream = false,
                                     int cols = 1) {
     if constexpr (std::is_same_v<T, float>)
-        if (cols == 2) return fused_kernel_ptr_c<T, 2>(temp, tracer, wrap, rows_per_band, stream);
-    return fused_kernel_ptr_c<T, 1>(temp, tracer, wrap, rows_per_band, stream);
+        if (cols == 2) return fused_kernel_ptr_c<T, 2>(temp, tracer, wrap, preload, stream);
+    return fused_kernel_ptr_c<T, 1>(temp, tracer, wrap, preload, stream);
 }
 
 // Rows per wave.  Large grids: one resident round -- as many waves as the chip holds at
@@ -641,12 +639,12 @@ int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap, int
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
         cus = prop.multiProcessorCount;
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fused_kernel_ptr<T>(temp, tracer, wrap, 1 << 30, false, cols), 64,
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fused_kernel_ptr<T>(temp, tracer, wrap, false, false, cols), 64,
                                                      0) == hipSuccess && nb > 0)
         waves_per_cu = nb;
     const long slots = (long)waves_per_cu * cus;
     const long M = members < 1 ? 1 : members;
-    const long strips = (W + cols * kStripCols - 1) / (cols * kStripCols);
+    const long strips = (W + sw2d_fused_strip_cols(cols) - 1) / sw2d_fused_strip_cols(cols);
     auto waves = [&](int rpb) { return M * strips * ((H + rpb - 1) / rpb); };
     if (waves(8) < slots) {  // small grid: aim at one wave per SIMD at least
         long rpb = M * H * strips / (5L * cus);   // ~1.3 waves per SIMD (measured best on 720x360)
@@ -686,16 +684,15 @@ int sw2d_fused_cols(int W, int H, bool temp, int tracer, bool wrap, int members)
 template <typename T>
 bool launch_sw2d_fused(const Sw2dArgsT<T> &a, bool temp, int tracer, hipStream_t s, int cols) {
     if (a.j1 <= a.j0) return true;
-    const int strips = (a.W + cols * kStripCols - 1) / (cols * kStripCols);
+    const int strips = (a.W + sw2d_fused_strip_cols(cols) - 1) / sw2d_fused_strip_cols(cols);
     const int bands = (a.j1 - a.j0 + a.rows_per_band - 1) / a.rows_per_band;
     dim3 g((unsigned)(((long)strips * bands * a.members + 7) / 8 * 8));  // 1-D, padded to 8 XCD groups
     Sw2dArgsT<T> arg = a;
     void *params[] = {&arg};
     // fields x sizeof(T) bytes x the rows of this launch (all members), read once: stream it when that is beyond the
-    // 256 MB Infinity Cache
-    const int nfields = 3 + (temp ? 1 : 0) + (tracer ? 1 : 0);
-    const bool stream = (long)a.W * (a.j1 - a.j0) * a.members * (long)sizeof(T) * nfields > (256L << 20);
-    return hipLaunchKernel(fused_kernel_ptr<T>(temp, tracer, a.wrap_j != 0, a.rows_per_band, stream, cols), g, dim3(64), params, 0, s) == hipSuccess;
+    // 256 MB Infinity Cache (sw2d_fused_form)
+    const Sw2dFusedForm f = sw2d_fused_form(temp, tracer, a.rows_per_band, a.W, a.j1 - a.j0, a.members, (long)sizeof(T));
+    return hipLaunchKernel(fused_kernel_ptr<T>(temp, tracer, a.wrap_j != 0, f.preload, f.stream, cols), g, dim3(64), params, 0, s) == hipSuccess;
 }
 
 template <typename T>

@@ -9,6 +9,29 @@ constexpr int kExnerTabDoubles = 256;  // [0,128): E_e, e = -64..63; then 64 x {
 constexpr int kGhost = 2;        // ghost rows on each side of a latitude band
 constexpr int kStripCols = 60;   // output columns per wave in the fused kernel (64 lanes - 2x2 halo)
 
+constexpr int kStrip2Cols = 56;  // output columns per wave in the two-step kernel (64 lanes - 2x4: the halo of two steps)
+constexpr int kPreloadRows = 4;  // bands of up to this many rows use the preloading variant (plain SW2D)
+
+// The launch geometry of the fused kernels: the expressions the launchers (sw2d_impl.h) and the read-only query
+// gcm_sw2d_plan (gcmcore.hip) share, so that the query cannot drift from the launch.
+// output columns per wave of the single-step kernel with `cols` columns per lane
+constexpr int sw2d_fused_strip_cols(int cols) { return cols * kStripCols; }
+// whether the two-step kernel serves a launch: periodic rows, all of them, bands of 2..4 rows
+inline bool sw2d_fused2_serves(int wrap_j, int j0, int j1, int H, int rows_per_band) {
+    return wrap_j && j0 == 0 && j1 == H && rows_per_band >= 2 && rows_per_band <= 4;
+}
+// the form of the single-step kernel: preloading (plain SW2D, short bands) or rolling, and the rolling one's STREAM
+// instantiation where the rows of one launch (all members, `esz` bytes an element) are beyond the 256 MB Infinity Cache
+struct Sw2dFusedForm {
+    bool preload, stream;
+};
+inline Sw2dFusedForm sw2d_fused_form(bool temp, int tracer, int rows_per_band, long W, long rows, long members,
+                                     long esz) {
+    const int nfields = 3 + (temp ? 1 : 0) + (tracer ? 1 : 0);
+    const bool preload = !temp && rows_per_band <= kPreloadRows;
+    return {preload, !preload && W * rows * members * esz * nfields > (256L << 20)};
+}
+
 // Pointers address interior row 0 of member 0; with wrap_j == 0 rows -2,-1 and H,H+1 are ghost rows.
 // Member m's field starts mstride elements after member m-1's (an ensemble handle, members > 1).
 // T is the real type of the state and of the arithmetic: double, or float for an fp32 handle.

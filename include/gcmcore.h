@@ -163,6 +163,21 @@ int gcm_get_member(gcm_handle *h, int m, double *p, double *u, double *v, double
  * Stands behind matsumo_scheme / matsuno_timestep (files cited at gcm_model). */
 int gcm_step(gcm_handle *h, int nsteps, double dt);
 
+/* What gcm_step(h, nsteps, .) of a 2-D handle would launch, without launching anything: a read-only query for tests
+ * and tools, taken from the expressions gcm_step and the kernel launchers use themselves (GCM_SW2D_TWO_STEP, read per
+ * call, and the per-launch timing of gcm_time_steps included).  out (nout >= GCM_SW2D_PLAN_WORDS words):
+ *   [0] the variant, GCM_VARIANT_FUSED or GCM_VARIANT_STAGED; [1] .. [4] are 0 for the staged variant
+ *   [1] rows per band (output rows per wave)      [2] columns per lane (2: fp32 with an even width)
+ *   [3] strip width in columns of the single-step kernel (60 x columns per lane)
+ *   [4] strip width in columns of the two-step kernel (56)
+ *   [5] two-step launches (each advances two steps)  [6] steps taken one at a time: nsteps - 2 x [5]
+ *   [7] 1: the single-step kernel is the preloading form (plain GCM_SW2D, bands of up to 4 rows), 0: the rolling form
+ *   [8] 1: the rolling form's STREAM instantiation (one launch reads more than 256 MB)
+ * A latitude band: the rows of its next step.  A GCM_PE25D handle, a null pointer, nsteps < 0 or nout too small:
+ * GCM_ERR_ARG.                                                                                                 */
+#define GCM_SW2D_PLAN_WORDS 9
+int gcm_sw2d_plan(gcm_handle *h, int nsteps, int *out, int nout);
+
 /* One Euler stage, for per-stage parity tests and for the reference's
  * boundary_conditions hook (dynamics.py:232-236): stage == 0 computes the
  * predictor from the current state into the handle's "star" buffers; stage == 1

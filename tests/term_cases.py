@@ -72,6 +72,50 @@ def _temp_cases():
     return out
 
 
+def _sw2d_geometry_cases():
+    """plain SW2D on the fused kernels the handle's own choice at (33, 97) does not reach.  `plan`: what Core.sw2d_plan
+    of the case's step count must report (the runner asserts it before it steps), `min_rows`: a lower bound on its
+    rows_per_band where the heuristic picks them"""
+    out = []
+    dx, dt = 300e3, 300.0
+    # pinned rows: 3 and 4 take a two-step launch (sw2d_fused2_kernel) and a leftover step of the preloading kernel,
+    # 8 and 16 two steps of the rolling kernel
+    for rows, steps in ((3, 3), (4, 3), (8, 2), (16, 2)):
+        pairs = steps // 2 if rows <= 4 else 0
+        out.append(_case("sw2d_fused_rows%d" % rows, "sw2d", "fused_rows%d" % rows, (33, 97), 210 + rows, dx, dt, steps,
+                         rows=rows, plan=dict(variant="fused", rows_per_band=rows, cols=1, strip=60, strip2=56,
+                                              two_step_launches=pairs, single_step_launches=steps - 2 * pairs,
+                                              preload=rows <= 4, stream=False)))
+    # three latitude bands stepped by the host loop: the non-wrapping kernels, preloading (the bands' own 2 rows) and
+    # rolling (8 rows)
+    out.append(_case("sw2d_band3", "sw2d", "band", (37, 130), 230, dx, dt, 2, bands=3, max_rows=4,
+                     plan=dict(variant="fused", two_step_launches=0, single_step_launches=1, preload=True,
+                               stream=False)))
+    out.append(_case("sw2d_band3_rows8", "sw2d", "band", (37, 130), 231, dx, dt, 2, bands=3, rows=8,
+                     plan=dict(variant="fused", rows_per_band=8, two_step_launches=0, single_step_launches=1,
+                               preload=False, stream=False)))
+    # the STREAM instantiation of the rolling kernel: 48 members of 360x720 read 48 * 360 * 720 * 3 * 8 B = 299 MB per
+    # launch, and a grid that fills the chip gets bands of 8 rows at least
+    out.append(_case("sw2d_stream", "sw2d", "stream", (360, 720), 240, dx, dt, 1, members=48, picks=(0, 23, 47),
+                     min_rows=8, plan=dict(variant="fused", cols=1, strip=60, two_step_launches=0,
+                                           single_step_launches=1, preload=False, stream=True)))
+    # fp32 through the two-step kernel: the handle's own 2-row bands, one two-step launch
+    for cols in (1, 2):
+        out.append(_case("sw2d_f32_two_step_cols%d" % cols, "sw2d", "f32_two_step", (33, 96), 250, dx, dt, 2, "f32",
+                         cols=cols, max_rows=4, plan=dict(variant="fused", cols=cols, strip=60 * cols, strip2=56,
+                                                          two_step_launches=1, single_step_launches=0,
+                                                          preload=True, stream=False)))
+    return out
+
+
+def check_plan(case, plan):
+    """a case's `plan`, `min_rows` and `max_rows` against what Core.sw2d_plan reported"""
+    want = case.extra["plan"]
+    assert {k: plan[k] for k in want} == want, (case.name, plan)
+    assert case.extra.get("min_rows", 1) <= plan["rows_per_band"] <= case.extra.get("max_rows", 1 << 30), \
+        (case.name, plan)
+
+
 def _other_cases():
     out = []
     for path in ("fused", "staged"):
@@ -79,6 +123,7 @@ def _other_cases():
     for cols in (1, 2):
         out.append(_case("sw2d_f32_cols%d" % cols, "sw2d", "f32_cols%d" % cols, (33, 96), 201, 300e3, 300.0, 1,
                          "f32", cols=cols))
+    out += _sw2d_geometry_cases()
     out.append(_case("pe2d", "pe2d", "core", (33, 130), 300, 100e3, 100.0, 3))
     out.append(_case("oned", "oned", "run", (257,), 400, 5e4, 60.0, 3))
     out.append(_case("pe25d", "pe25d", "core", (5, 12, 20), 500, None, 60.0, 2))
@@ -113,6 +158,13 @@ PATHS = {
     ("sw2d", "staged"): ("f64", _SW2D),
     ("sw2d", "f32_cols1"): ("f32", _SW2D),
     ("sw2d", "f32_cols2"): ("f32", _SW2D),
+    ("sw2d", "fused_rows3"): ("f64", _SW2D),
+    ("sw2d", "fused_rows4"): ("f64", _SW2D),
+    ("sw2d", "fused_rows8"): ("f64", _SW2D),
+    ("sw2d", "fused_rows16"): ("f64", _SW2D),
+    ("sw2d", "band"): ("f64", _SW2D),
+    ("sw2d", "stream"): ("f64", _SW2D),
+    ("sw2d", "f32_two_step"): ("f32", _SW2D),
     ("pe2d", "core"): ("f64", ("advec_p", "dut", "pgfu", "dvt", "pgfv", "advec_t")),
     ("oned", "run"): ("f64", ("advec_q", "advec_p", "advec_pu", "pgf", "advec_t")),
     ("pe25d", "core"): ("f64", _PE25D),

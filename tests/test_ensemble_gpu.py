@@ -49,6 +49,20 @@ def _single(g, model, tracer, variant, W, H, state, steps):
     return out
 
 
+_ORACLE = {}
+
+
+def _sw2d_oracle(state, steps, key):
+    """{u, v, p} of the float64 oracle after `steps` steps of plain shallow water, computed once per key"""
+    if key not in _ORACLE:
+        from oracle import sw2d
+        st = (state["u"], state["v"], state["p"])
+        for _ in range(steps):
+            st = sw2d.matsumo_scheme(*st, DX, DT)
+        _ORACLE[key] = dict(zip("uvp", st))
+    return _ORACLE[key]
+
+
 # the band height matters to the fused variant only: short bands (GCM_SW2D: the preloading kernel and fused2
 # pairs) and long ones
 @pytest.mark.parametrize("variant,rows", [("fused", 3), ("fused", 16), ("staged", None)])
@@ -56,7 +70,9 @@ def _single(g, model, tracer, variant, W, H, state, steps):
 @pytest.mark.parametrize("W,H", [(720, 360), (97, 61)])
 def test_every_member_equals_a_single_handle(g, monkeypatch, W, H, name, model, tracer, variant, rows):
     """5 members, 7 steps (GCM_SW2D: three fused2 pairs and a single step when the bands are short):
-    bit for bit what a one-member handle computes on each member's state, with the band height pinned"""
+    bit for bit what a one-member handle computes on each member's state, with the band height pinned.  Plain
+    shallow water at (97, 61): the handle launches what the pinned rows mean (Core.sw2d_plan) and member 0 agrees
+    with the float64 oracle, so that a fault the ensemble and the single handle share shows too"""
     if rows is not None:
         monkeypatch.setenv("GCM_FUSED_ROWS", str(rows))
     monkeypatch.setenv("GCM_SW2D_TWO_STEP", "1")
@@ -66,6 +82,7 @@ def test_every_member_equals_a_single_handle(g, monkeypatch, W, H, name, model, 
     c = g.Core(model, W, H, dx=DX, variant=var, tracer=tracer, members=M)
     assert c.members == M and c.options["members"] == M
     c.set_state(**s)
+    plan = c.sw2d_plan(7)
     c.step(7, DT)
     ens = c.get_state()
     c.close()
@@ -74,6 +91,15 @@ def test_every_member_equals_a_single_handle(g, monkeypatch, W, H, name, model, 
         for f, (a, b) in enumerate(zip(ens, one)):
             if b is not None:
                 assert np.array_equal(a[m], b), (m, "puvtq"[f])
+    if name == "sw2d" and (W, H) == (97, 61):
+        pairs = 3 if rows == 3 else 0
+        assert (plan["variant"], plan["two_step_launches"], plan["single_step_launches"]) == (variant, pairs, 7 - 2 * pairs)
+        if rows is not None:
+            assert (plan["rows_per_band"], plan["preload"], plan["stream"]) == (rows, rows <= 4, False), plan
+        want = _sw2d_oracle(_member(s, 0), 7, (W, H))
+        for k, b in want.items():
+            e = rel_err(ens["puvtq".index(k)][0], b)
+            assert e < TOL, (k, e, plan)
 
 
 @pytest.mark.parametrize("name,model,tracer", [MODELS[0], MODELS[3]])

@@ -174,7 +174,10 @@ def test_conservation(g):
 @pytest.mark.parametrize("name,model,tracer", [MODELS[0], MODELS[3]])
 def test_ensemble_members_equal_single_handles(g, monkeypatch, name, model, tracer, variant, rows, W, cols):
     """5 members, 7 steps (GCM_SW2D with 3-row bands: three two-step launches and a single step): every member
-    bit for bit what an fp32 one-member handle computes; one and two columns per lane"""
+    bit for bit what an fp32 one-member handle computes; one and two columns per lane.  Plain shallow water: the
+    handle launches what the pinned rows and columns mean (Core.sw2d_plan) and member 0 is within 7 x F32_STEP of
+    the float64 oracle on the float32-rounded inputs, so that a fault the ensemble and the single handle share
+    shows too"""
     monkeypatch.setenv("GCM_SW2D_F32_COLS", cols)
     if rows is not None:
         monkeypatch.setenv("GCM_FUSED_ROWS", str(rows))
@@ -182,11 +185,28 @@ def test_ensemble_members_equal_single_handles(g, monkeypatch, name, model, trac
     var = {"fused": g._lib.VARIANT_FUSED, "staged": g._lib.VARIANT_STAGED}[variant]
     M, H = 5, 61
     s = _states(model, tracer, H, W, seed=21 + model + tracer, M=M)
+    plan = None
+    if name == "sw2d":
+        c = g.Core(model, W, H, dx=DX, tracer=tracer, dtype="f32", variant=var, members=M)
+        plan = c.sw2d_plan(7)
+        c.close()
     ens = _run(g, model, tracer, W, H, s, 7, variant=var, members=M)
     for m in range(M):
         one = _run(g, model, tracer, W, H, _member(s, m), 7, variant=var)
         for k, b in one.items():
             assert np.array_equal(ens[k][m], b), (m, k)
+    if name == "sw2d":
+        pairs = 3 if rows == 3 else 0
+        assert (plan["variant"], plan["two_step_launches"], plan["single_step_launches"]) == (variant, pairs, 7 - 2 * pairs)
+        if rows is not None:
+            assert (plan["rows_per_band"], plan["cols"], plan["strip"], plan["preload"], plan["stream"]) == \
+                (rows, int(cols), 60 * int(cols), rows <= 4, False), plan
+        key = ("ens", W)
+        if key not in _ORACLE:
+            _ORACLE[key] = _oracle(model, tracer, _r32(_member(s, 0)), 7)
+        for k, b in _ORACLE[key].items():
+            e = rel_err(ens[k][0], b)
+            assert e < 7 * F32_STEP[model][k], (k, e, plan)
 
 
 def test_ensemble_streams(g, monkeypatch):

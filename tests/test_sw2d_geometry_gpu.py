@@ -1,0 +1,174 @@
+"""Plain shallow water (GCM_SW2D) on the fused path, every launch geometry against the float64 oracle: the two-step
+kernel sw2d_fused2_kernel<T, 2|3|4>, the preloading single-step kernel (bands of up to 4 rows) and the rolling one
+(bands of 5 rows and more), at fp64 and at fp32 with one and two columns per lane, on the smallest shapes that reach
+each strip seam, band seam and halo edge (tests/sw2d_geometry_cases.py lists them with the reason for each).
+
+Every case first asserts through Core.sw2d_plan that the handle launches the kernel family, rows per band, strip width
+and launch counts its id names -- a case that meant to cover one kernel cannot pass on another -- then steps and
+compares with oracle.sw2d.matsumo_scheme (fp32: on the float32-rounded inputs).  GCM_FUSED_ROWS and GCM_SW2D_F32_COLS
+are read per handle and set before it is created; GCM_SW2D_TWO_STEP is read per call and set before the first step.
+GCM_ALLOC_SKEW is read once per process and is out of scope here.  A failure names the worst cell's (j, i) and its
+place in the band and in the strips."""
+import numpy as np
+import pytest
+
+import sw2d_geometry_cases as gc
+
+pytestmark = pytest.mark.gpu
+SWITCHES = ("GCM_FUSED_ROWS", "GCM_SW2D_TWO_STEP", "GCM_SW2D_F32_COLS")
+
+
+@pytest.fixture(scope="module")
+def g():
+    import gcmiipy_amd
+    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
+    return gcmiipy_amd
+
+
+def _cases():
+    """(dtype, cols, geometry, shape): fp64, and fp32 with one column per lane, on every shape; fp32 with two columns
+    per lane on the even widths (an odd width takes one column whatever GCM_SW2D_F32_COLS says)"""
+    out = []
+    for dtype, cols in (("f64", 1), ("f32", 1), ("f32", 2)):
+        for geom in gc.GEOMETRIES:
+            for shape in gc.SHAPES:
+                if cols == 1 or shape[1] % 2 == 0:
+                    out.append((dtype, cols, geom, shape))
+    return out
+
+
+def _id(case):
+    dtype, cols, geom, (H, W) = case
+    return "%s%s-%s-rows%d-%dx%d" % (dtype, "-cols%d" % cols if dtype == "f32" else "", geom.family, geom.rows, H, W)
+
+
+CASES = _cases()
+
+
+def _where(err, plan):
+    """the worst cell of an error field and its place in the launch geometry"""
+    j, i = np.unravel_index(int(np.argmax(err)), err.shape)
+    return "worst cell (j, i) = (%d, %d), j %% rows_per_band = %d, i %% %d = %d, i %% %d = %d" % (
+        j, i, j % plan["rows_per_band"], plan["strip"], i % plan["strip"], plan["strip2"], i % plan["strip2"])
+
+
+def _seam_mask(shape, plan):
+    """the cells on a seam: the last and the first column of every strip of either kernel and of the grid, the first
+    row of every band and the last and first row of the grid"""
+    H, W = shape
+    cols = {W - 1, 0}
+    for strip in (plan["strip"], plan["strip2"]):
+        for edge in range(strip, W, strip):
+            cols |= {edge - 1, edge}
+    rows = set(range(0, H, plan["rows_per_band"])) | {H - 1}
+    mask = np.zeros(shape, dtype=bool)
+    mask[sorted(rows), :] = True
+    mask[:, sorted(cols)] = True
+    return mask
+
+
+def _compare(label, nsteps, got, want, dtype, plan, seams):
+    """every field of `got` within the bound of the oracle's `want`; with `seams`, the seam cells on their own too"""
+    errs = {}
+    for k in gc.FIELDS:
+        a, b = got[k], want[k]
+        assert a.shape == b.shape, (label, k, a.shape)
+        err = np.abs(a - b) / np.max(np.abs(b))
+        assert not np.isnan(err).any(), "%s: %s after %d steps holds a NaN; %s" % (
+            label, k, nsteps, _where(np.isnan(err), plan))
+        errs[k] = float(err.max())
+        lim = gc.bound(dtype, k, nsteps)
+        assert errs[k] < lim, "%s: %s after %d steps misses the oracle by %.3e (bound %.1e); %s" % (
+            label, k, nsteps, errs[k], lim, _where(err, plan))
+        if seams:
+            on_seam = np.where(_seam_mask(a.shape, plan), err, 0.0)
+            assert on_seam.max() < lim, "%s: %s after %d steps misses the oracle by %.3e on a seam (bound %.1e); %s" % (
+                label, k, nsteps, on_seam.max(), lim, _where(on_seam, plan))
+    return errs
+
+
+def _drive(g, monkeypatch, case, seams=False):
+    dtype, cols, geom, shape = case
+    H, W = shape
+    label = _id(case)
+    for k in SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("GCM_FUSED_ROWS", str(geom.rows))
+    if dtype == "f32":
+        monkeypatch.setenv("GCM_SW2D_F32_COLS", str(cols))
+    s, want = gc.inputs(shape, dtype), gc.oracle(shape, dtype)
+    c = g.Core(g._lib.SW2D, W, H, dx=gc.DX, variant=g._lib.VARIANT_FUSED, dtype=dtype)
+    try:
+        if geom.two_step is not None:
+            monkeypatch.setenv("GCM_SW2D_TWO_STEP", geom.two_step)
+        c.set_state(**s)
+        plan, log, done = None, [], 0
+
+        def step(n, total):
+            nonlocal plan
+            plan = c.sw2d_plan(n)
+            assert plan == gc.expected_plan(geom, cols, n), (label, n, plan)
+            c.step(n, gc.DT)
+            got = dict(zip("puv", c.get_state()[:3]))
+            errs = _compare(label, total, got, want[total], dtype, plan, seams)
+            log.append("%d: %s" % (total, " ".join("%s %.2e" % kv for kv in errs.items())))
+
+        for n in gc.CALLS:
+            done += n
+            step(n, done)
+        assert done == gc.TOTALS[-1]
+        for n in gc.AGAIN:                              # n steps in one call, from the initial state
+            c.set_state(**s)
+            step(n, n)
+        print(label, "plan(5)", plan, "| errors after", " | ".join(log))
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[_id(c) for c in CASES])
+def test_geometry_vs_oracle(g, monkeypatch, case):
+    """the plan the id names, then 1, 2, 4 and 5 steps against the oracle: by calls of 1, 1, 2 and 1 steps on one
+    handle, and 4 and 5 steps in one call each"""
+    _drive(g, monkeypatch, case)
+
+
+SEAM_CASES = [(dtype, 1, geom, shape) for dtype in ("f64", "f32")
+              for geom, shape in ((gc.Geometry("fused2", 4, "1"), (13, 113)), (gc.Geometry("rolling", 8, None), (10, 61)))]
+
+
+@pytest.mark.parametrize("case", SEAM_CASES, ids=[_id(c) for c in SEAM_CASES])
+def test_seams_within_the_interior_bound(g, monkeypatch, case):
+    """the cells on a strip seam (columns 55 | 56, 59 | 60, 111 | 112, W-1 | 0) and on a band seam (the multiples of
+    rows_per_band, H-1 | 0) are within the bound that holds for the interior: implied by the L-inf comparison, stated
+    apart so that a failure names the seam"""
+    dtype, cols, geom, shape = case
+    plan = gc.expected_plan(geom, cols, 1)
+    mask = _seam_mask(shape, plan)
+    for i in (55, 56, 59, 60, 111, 112, shape[1] - 1, 0):
+        assert i >= shape[1] or mask[:, i].all(), i
+    for j in list(range(0, shape[0], geom.rows)) + [shape[0] - 1]:
+        assert mask[j].all(), j
+    assert not mask.all()
+    _drive(g, monkeypatch, case, seams=True)
+
+
+def test_plan_of_other_handles(g, monkeypatch):
+    """sw2d_plan on the handles this file does not step: the staged variant takes single steps and reports no fused
+    geometry, GCM_SW2D_TEMP never pairs, and a GCM_PE25D handle is refused"""
+    for k in SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("GCM_FUSED_ROWS", "3")
+    c = g.Core(g._lib.SW2D, 61, 10, dx=gc.DX, variant=g._lib.VARIANT_STAGED)
+    assert c.sw2d_plan(5) == dict(variant="staged", rows_per_band=0, cols=0, strip=0, strip2=0, two_step_launches=0,
+                                  single_step_launches=5, preload=False, stream=False)
+    c.close()
+    c = g.Core(g._lib.SW2D_TEMP, 61, 10, dx=gc.DX, variant=g._lib.VARIANT_FUSED)
+    plan = c.sw2d_plan(5)
+    assert (plan["rows_per_band"], plan["two_step_launches"], plan["single_step_launches"], plan["preload"]) == \
+        (3, 0, 5, False)
+    c.close()
+    from gcmiipy_amd import geometry
+    c = g.Core(g._lib.PE25D, 20, 12, 5, geom=geometry.gen_geometry(12, 20, 5, sig_func=geometry.manabe_sig))
+    with pytest.raises(ValueError):
+        c.sw2d_plan(1)
+    c.close()

@@ -43,6 +43,10 @@ def _run_2d(g, case, monkeypatch):
     s = tc.state(case)
     names = tc.fields(case)
     kw = dict(dx=case.dx, tracer=case.tracer, dtype=case.dtype)
+    planned = "plan" in case.extra           # the plain-SW2D geometry cases: the launch plan is asserted before the step
+    if planned:
+        for k in ("GCM_FUSED_ROWS", "GCM_SW2D_TWO_STEP", "GCM_SW2D_F32_COLS"):
+            monkeypatch.delenv(k, raising=False)
     if "rows" in case.extra:
         monkeypatch.setenv("GCM_FUSED_ROWS", str(case.extra["rows"]))
     if "cols" in case.extra:
@@ -63,6 +67,8 @@ def _run_2d(g, case, monkeypatch):
         for r, (row0, n) in enumerate(split_rows(H, nb)):
             c = g.Core(model, W, n, nranks=nb, rank=r, global_height=H, row0=row0, **kw)
             c.set_state(**{k: a[row0:row0 + n] for k, a in s.items()})
+            if planned:
+                tc.check_plan(case, c.sw2d_plan(1))
             cores.append(c)
         for _ in range(case.steps):
             _exchange(cores, torch)
@@ -79,6 +85,8 @@ def _run_2d(g, case, monkeypatch):
         assert H * W * 8 * len(names) * M > 256 << 20        # the launch streams
         c = g.Core(model, W, H, members=M, **kw)
         c.set_state(**s)
+        if planned:
+            tc.check_plan(case, c.sw2d_plan(case.steps))
         c.step(case.steps, case.dt)
         got = [_by_field(c.get_member(m), names) for m in case.extra["picks"]]
         assert c.diag(g._lib.DIAG_ANY_NAN) == 0.0
@@ -90,6 +98,8 @@ def _run_2d(g, case, monkeypatch):
         c.half_step(0, case.dt)
         got = _by_field(c.get_star(), names)
     else:
+        if planned:
+            tc.check_plan(case, c.sw2d_plan(case.steps))
         c.step(case.steps, case.dt)
         got = _by_field(c.get_state(), names)
     c.close()
