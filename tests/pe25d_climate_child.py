@@ -14,21 +14,16 @@ sys.path[:0] = [HERE, os.path.dirname(HERE)]
 def main(path, steps, dt):
     import torch
     import gcmiipy_amd as g
-    from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange
-    import test_pe25d_climate_gpu as t
+    import gpu_setups as su
+    import pe25d_inputs as inp
     want = np.load(path)
     H, L, W = want["u_f64"].shape[1], want["u_f64"].shape[0], want["u_f64"].shape[2]
-    geom = t.geom_of(H, W, L)
+    geom = su.geom_of(H, W, L)
     bad = 0
     for dtype in ("f64", "f32"):
-        c = g.Core(g._lib.PE25D, W, H, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0, dtype=dtype,
-                   stream=torch.cuda.current_stream().cuda_stream)
-        eng = HipBandEngine(c, torch)
-        eng.set_held_suarez(geom)
-        eng.set_climate(1)
-        runner = BandRunner(eng, 0, 2, LoopbackExchange(), north=0, south=0)
+        c, eng, runner = su.loopback_band(g, torch, geom, dtype=dtype, hs={}, every=1)
         assert runner.native
-        c.set_state(*t.state_of(geom, dtype))
+        c.set_state(*inp.state_of(geom, dtype))
         runner.run(steps, dt)
         torch.cuda.synchronize()
         n, m3, m2 = c.climate_sums()

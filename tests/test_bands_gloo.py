@@ -2,14 +2,12 @@
 world_size 2 and 3, NumPy band engines (tests/band_engines.py).  The banded result must
 equal the single-domain oracle BIT FOR BIT (same arithmetic per row)."""
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -17,13 +15,8 @@ for p in (ROOT, HERE):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+import pe25d_inputs as inp  # noqa: E402
+from gpu_setups import spawn  # noqa: E402
 
 
 def _ic2d(shape, temp):
@@ -37,7 +30,7 @@ def _ic2d(shape, temp):
     return f
 
 
-def _worker_2d(rank, world, port, shape, temp, steps, outdir, halo_steps=1):
+def _worker_2d(rank, world, shape, temp, steps, outdir, halo_steps=1):
     from band_engines import NumpyBand2D
     from gcmiipy_amd.bands import BandRunner, split_rows
     # rendezvous through a file in the test's own directory: no TCP port to collide on
@@ -59,7 +52,7 @@ def _worker_2d(rank, world, port, shape, temp, steps, outdir, halo_steps=1):
     dist.destroy_process_group()
 
 
-def _worker_pe(rank, world, port, hwl, steps, outdir, edge_first=False, phys=False):
+def _worker_pe(rank, world, hwl, steps, outdir, edge_first=False, phys=False):
     from band_engines import NumpyBandPE
     from gcmiipy_amd.bands import BandRunner, split_rows
     from oracle import geometry as ogeo
@@ -68,7 +61,7 @@ def _worker_pe(rank, world, port, hwl, steps, outdir, edge_first=False, phys=Fal
     H, W, L = hwl
     geom = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
     geom.heightmap[H // 2, 3] = 300.0
-    p, u, v, t, q = _ic_pe(geom)
+    p, u, v, t, q = inp.state(geom, 9)
     row0, n = split_rows(H, world)[rank]
     sl = slice(row0, row0 + n)
     gt = _ic_gt(geom)[sl] if phys else None
@@ -82,20 +75,7 @@ def _worker_pe(rank, world, port, hwl, steps, outdir, edge_first=False, phys=Fal
     dist.destroy_process_group()
 
 
-def _ic_pe(geom):
-    from oracle import temperature
-    rng = np.random.default_rng(9)
-    L, H, W = geom.layers, geom.height, geom.width
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u = rng.standard_normal((L, H, W))
-    v = rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    t = temperature.to_potential_temp(300 + rng.standard_normal((L, H, W)), p * geom.sig + geom.ptop)
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
-    return p, u, v, t, q
-
-
-UTC0 = 5 * 3600.0
+UTC0 = inp.UTC0
 
 
 def _ic_gt(geom):
@@ -114,8 +94,7 @@ def test_split_rows():
 def test_banded_2d_equals_single_domain(tmp_path, world, temp):
     from oracle import sw2d, sw2d_temp, tracer
     shape, steps = (14, 24), 3
-    mp.spawn(_worker_2d, args=(world, _free_port(), shape, temp, steps, str(tmp_path)), nprocs=world,
-             join=True)
+    spawn(_worker_2d, (world, shape, temp, steps, str(tmp_path)), world)
     f = _ic2d(shape, temp)
     for _ in range(steps):
         if temp:
@@ -135,8 +114,7 @@ def test_banded_2d_deep_halo(tmp_path):
     """halo_steps = 2: exchange every second step, 5 steps (last window partial)"""
     from oracle import sw2d
     shape, steps, world = (18, 24), 5, 3
-    mp.spawn(_worker_2d, args=(world, _free_port(), shape, False, steps, str(tmp_path), 2), nprocs=world,
-             join=True)
+    spawn(_worker_2d, (world, shape, False, steps, str(tmp_path), 2), world)
     f = _ic2d(shape, False)
     for _ in range(steps):
         u, v, p = sw2d.matsumo_scheme(f["u"], f["v"], f["p"], 300e3, 300.0)
@@ -151,12 +129,11 @@ def test_banded_2d_deep_halo(tmp_path):
 def test_banded_pe25d_equals_single_domain(tmp_path, world, edge_first):
     from oracle import dynamics, geometry as ogeo
     hwl, steps = (12, 16, 3), 2
-    mp.spawn(_worker_pe, args=(world, _free_port(), hwl, steps, str(tmp_path), edge_first), nprocs=world,
-             join=True)
+    spawn(_worker_pe, (world, hwl, steps, str(tmp_path), edge_first), world)
     H, W, L = hwl
     geom = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
     geom.heightmap[H // 2, 3] = 300.0
-    st = _ic_pe(geom)
+    st = inp.state(geom, 9)
     for _ in range(steps):
         st = dynamics.matsuno_timestep(*st, 120.0, geom)
     parts = [np.load(os.path.join(str(tmp_path), "r%d.npz" % r)) for r in range(world)]
@@ -174,12 +151,11 @@ def test_banded_pe25d_with_physics_equals_single_domain(tmp_path, world, edge_fi
     exchange per step.  Bit for bit the single domain (the oracle: matsuno_timestep, then solar_timestep)."""
     from oracle import dynamics, physics, geometry as ogeo
     hwl, steps = (12, 16, 3), 3
-    mp.spawn(_worker_pe, args=(world, _free_port(), hwl, steps, str(tmp_path), edge_first, True), nprocs=world,
-             join=True)
+    spawn(_worker_pe, (world, hwl, steps, str(tmp_path), edge_first, True), world)
     H, W, L = hwl
     geom = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
     geom.heightmap[H // 2, 3] = 300.0
-    st, gt, utc = _ic_pe(geom), _ic_gt(geom), UTC0
+    st, gt, utc = inp.state(geom, 9), _ic_gt(geom), UTC0
     for _ in range(steps):
         st = list(dynamics.matsuno_timestep(*st, 120.0, geom))
         st[3], gt = physics.solar_timestep(st[3], st[0], gt, 120.0, utc, geom)
@@ -189,7 +165,7 @@ def test_banded_pe25d_with_physics_equals_single_domain(tmp_path, world, edge_fi
         got = np.concatenate([pp[k] for pp in parts], axis=0 if k in "pg" else 1)
         assert np.array_equal(got, want), k
     # the physics did something, and a band that skipped its ghost rows would differ: theta moved
-    assert not np.array_equal(st[3], dynamics.matsuno_timestep(*_ic_pe(geom), 120.0, geom)[3])
+    assert not np.array_equal(st[3], dynamics.matsuno_timestep(*inp.state(geom, 9), 120.0, geom)[3])
 
 
 def test_rccl_unique_id_survives_transport():

@@ -4,17 +4,16 @@ gcm_halo_pack/unpack and gcm_step_interior/boundary against the single-band resu
 processes sharing the GPU, BandRunner + HipBandEngine over torch.distributed (gloo here: RCCL
 refuses two ranks on one device; the 8-GPU run uses the same code with backend nccl)."""
 import os
-import socket
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import rel_err
+import gpu_setups as su
+import pe25d_inputs as inp
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+UTC0 = inp.UTC0
 
 
 def _ic2d(shape):
@@ -22,42 +21,6 @@ def _ic2d(shape):
     return dict(u=rng.standard_normal(shape), v=rng.standard_normal(shape),
                 p=101325 + rng.standard_normal(shape), t=273.16 + rng.standard_normal(shape),
                 q=rng.random(shape))
-
-
-def _ic_pe(geom):
-    rng = np.random.default_rng(12)
-    L, H, W = geom.layers, geom.height, geom.width
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u = rng.standard_normal((L, H, W))
-    v = rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    sig = np.asarray(geom.sig)
-    t = (300 + rng.standard_normal((L, H, W))) * ((1e5 / (p * sig + geom.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
-    return p, u, v, t, q
-
-
-UTC0 = 5 * 3600.0
-
-
-def _ic_gt(H, W):
-    return 288.0 + np.random.default_rng(13).standard_normal((H, W))
-
-
-def _exchange(cores, torch):
-    """ring exchange by device copies: the rows a band packs on side s land in the neighbour's
-    opposite ghost"""
-    n = len(cores)
-    bufs = [[torch.empty(c.halo_bytes() // 8, dtype=torch.float64, device="cuda") for _ in (0, 1)]
-            for c in cores]
-    for r, c in enumerate(cores):
-        c.halo_pack(0, bufs[r][0].data_ptr())
-        c.halo_pack(1, bufs[r][1].data_ptr())
-    torch.cuda.synchronize()
-    for r, c in enumerate(cores):
-        c.halo_unpack(1, bufs[(r + 1) % n][0].data_ptr())   # south ghost <- southern band's north edge
-        c.halo_unpack(0, bufs[(r - 1) % n][1].data_ptr())   # north ghost <- northern band's south edge
-    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("variant", ["fused", "staged"])
@@ -81,7 +44,7 @@ def test_bands_in_process_2d(variant, nb):
         c.set_state(**{k: v[row0:row0 + n] for k, v in f.items()})
         cores.append(c)
     for _ in range(steps):
-        _exchange(cores, torch)
+        su.exchange(cores, torch)
         for c in cores:
             c.step_interior(300.0)
         for c in cores:
@@ -114,7 +77,7 @@ def test_deep_halo_in_process_2d(variant):
         c.set_state(**{kk: v[row0:row0 + n] for kk, v in f.items()})
         cores.append(c)
     for _ in range(2):
-        _exchange(cores, torch)
+        su.exchange(cores, torch)
         for c in cores:
             c.step(k, 300.0)
         with pytest.raises(g.GcmError):
@@ -131,27 +94,21 @@ def test_bands_in_process_pe25d(nb):
     import torch
     import gcmiipy_amd as g
     from gcmiipy_amd import geometry
-    from gcmiipy_amd.bands import split_rows
     H, W, L, steps = 14, 20, 5, 2
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
     geom.heightmap[H // 2, 3] = 300.0
-    ic = _ic_pe(geom)
+    ic = inp.state(geom)
     ref = g.Core(g._lib.PE25D, W, H, L, geom=geom)
     ref.set_state(*ic)
     ref.step(steps, 120.0)
     want = ref.get_state()
     ref.close()
-    cores = []
-    for r, (row0, n) in enumerate(split_rows(H, nb)):
-        c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=nb, rank=r, global_height=H, row0=row0)
-        sl = slice(row0, row0 + n)
-        c.set_state(ic[0][sl], *[a[:, sl] for a in ic[1:]])
-        cores.append(c)
+    cores = su.bands(g, geom, nb, ic)
     for _ in range(steps):
-        _exchange(cores, torch)          # current state
+        su.exchange(cores, torch)        # current state
         for c in cores:
             c.step_interior(120.0)       # predictor
-        _exchange(cores, torch)          # predicted state
+        su.exchange(cores, torch)        # predicted state
         for c in cores:
             c.step_boundary(120.0)       # corrector
     parts = [c.get_state() for c in cores]
@@ -168,38 +125,25 @@ def test_bands_in_process_pe25d_edge_first(nb):
     import torch
     import gcmiipy_amd as g
     from gcmiipy_amd import geometry
-    from gcmiipy_amd.bands import split_rows
     H, W, L, steps = 15, 20, 5, 3
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    ic = _ic_pe(geom)
+    ic = inp.state(geom)
     ref = g.Core(g._lib.PE25D, W, H, L, geom=geom)
     ref.set_state(*ic)
     ref.step(steps, 120.0)
     want = ref.get_state()
     ref.close()
-    cores = []
-    for r, (row0, n) in enumerate(split_rows(H, nb)):
-        c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=nb, rank=r, global_height=H, row0=row0)
-        sl = slice(row0, row0 + n)
-        c.set_state(ic[0][sl], *[a[:, sl] for a in ic[1:]])
-        cores.append(c)
-    _exchange(cores, torch)                  # ghosts of the initial state
+    cores = su.bands(g, geom, nb, ic)
+    su.exchange(cores, torch)                # ghosts of the initial state
     for _ in range(steps):
         for stage in (0, 1):
             for c in cores:
                 c.step_phase(2 * stage, 120.0)
-            bufs = [[torch.empty(c.halo_bytes() // 8, dtype=torch.float64, device="cuda") for _ in (0, 1)]
-                    for c in cores]
-            for r, c in enumerate(cores):        # pack BEFORE the interior phase, as the runner does
-                c.halo_pack(0, bufs[r][0].data_ptr())
-                c.halo_pack(1, bufs[r][1].data_ptr())
+            bufs = su.pack(cores, torch)         # pack BEFORE the interior phase, as the runner does
             for c in cores:
                 c.step_phase(2 * stage + 1, 120.0)
             torch.cuda.synchronize()
-            for r, c in enumerate(cores):
-                c.halo_unpack(1, bufs[(r + 1) % nb][0].data_ptr())
-                c.halo_unpack(0, bufs[(r - 1) % nb][1].data_ptr())
-            torch.cuda.synchronize()
+            su.unpack(cores, bufs, torch)
     parts = [c.get_state() for c in cores]
     for c in cores:
         c.close()
@@ -258,7 +202,7 @@ def test_band_runners_in_process_stream_ordered(nb):
     from gcmiipy_amd.bands import BandRunner, HipBandEngine, split_rows
     H, W, L, steps = 23, 36, 9, 4
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    ic = _ic_pe(geom)
+    ic = inp.state(geom)
     ref = g.Core(g._lib.PE25D, W, H, L, geom=geom)
     ref.set_state(*ic)
     ref.step(steps, 120.0)
@@ -300,18 +244,8 @@ def test_band_runners_in_process_stream_ordered(nb):
         assert np.array_equal(got, want[f]), (k, rel_err(got, want[f]))
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _worker(rank, world, port, model, outdir):
-    for p in (ROOT, HERE):
-        if p not in sys.path:
-            sys.path.insert(0, p)
+def _worker(rank, world, model, outdir):
+    su.worker_paths()
     import torch
     import torch.distributed as dist
     import gcmiipy_amd as g
@@ -331,7 +265,7 @@ def _worker(rank, world, port, model, outdir):
     else:
         H, W, L, steps, dt = 14, 20, 5, 2 if model == "pe" else 3, 120.0
         geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-        ic = _ic_pe(geom)
+        ic = inp.state(geom)
         row0, n = split_rows(H, world)[rank]
         sl = slice(row0, row0 + n)
         c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=world, rank=rank, global_height=H, row0=row0,
@@ -339,7 +273,7 @@ def _worker(rank, world, port, model, outdir):
         c.set_state(ic[0][sl], *[a[:, sl] for a in ic[1:]])
     eng = HipBandEngine(c, torch, stream_aware=False)
     if model == "pephys":             # BASELINE configs[4]'s second phase on bands that are separate processes
-        c.set_ground(_ic_gt(H, W)[sl])
+        c.set_ground(inp.ground(H, W)[sl])
         eng.set_physics(geom, UTC0)
     runner = BandRunner(eng, rank, world, dist)
     runner.run(1, dt)                 # chunked path: a partial window first, then the rest
@@ -356,10 +290,9 @@ def _worker(rank, world, port, model, outdir):
 def test_band_runner_processes_one_gpu(tmp_path, model, world):
     """world = 4: every rank has two distinct ring neighbours (the N = 2 ring talks to one peer
     twice); four processes share the GPU (the box allows six)"""
-    import torch.multiprocessing as mp
     import gcmiipy_amd as g
     from gcmiipy_amd import geometry
-    mp.spawn(_worker, args=(world, _free_port(), model, str(tmp_path)), nprocs=world, join=True)
+    su.spawn(_worker, (world, model, str(tmp_path)), world)
     parts = [np.load(os.path.join(str(tmp_path), "r%d.npz" % r)) for r in range(world)]
     if model in ("c3", "c3deep"):
         H, W = 40, 130
@@ -370,9 +303,9 @@ def test_band_runner_processes_one_gpu(tmp_path, model, world):
         H, W, L = 14, 20, 5
         geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
         ref = g.Core(g._lib.PE25D, W, H, L, geom=geom)
-        ref.set_state(*_ic_pe(geom))
+        ref.set_state(*inp.state(geom))
         if model == "pephys":
-            ref.set_ground(_ic_gt(H, W))
+            ref.set_ground(inp.ground(H, W))
             ref.set_physics(geom, UTC0)
         ref.step(2 if model == "pe" else 3, 120.0)
     want = ref.get_state() + ([ref.get_ground()] if model == "pephys" else [])
@@ -413,12 +346,10 @@ def test_halo_buffer_registration_errors():
     sw.close()
 
 
-def _rccl_self_worker(rank, port, model, outdir):
+def _rccl_self_worker(rank, model, outdir):
     """one process, one GPU, the REAL backend: an RCCL ("nccl") group of one rank whose band is its
     own north and south neighbour -- numerically the periodic single domain"""
-    for p in (ROOT, HERE):
-        if p not in sys.path:
-            sys.path.insert(0, p)
+    su.worker_paths()
     import torch
     import torch.distributed as dist
     import gcmiipy_amd as g
@@ -444,9 +375,9 @@ def _rccl_self_worker(rank, port, model, outdir):
         geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
         c = g.Core(g._lib.PE25D, W, H, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0,
                    stream=torch.cuda.current_stream().cuda_stream)
-        c.set_state(*_ic_pe(geom))
+        c.set_state(*inp.state(geom))
         if phys:
-            c.set_ground(_ic_gt(H, W))
+            c.set_ground(inp.ground(H, W))
     else:
         H, W, steps, dt = 64, 130, 11, 300.0
         c = g.Core(g._lib.SW2D_TEMP, W, H, dx=300e3, tracer=g._lib.TRACER_VANLEER, nranks=2, rank=0,
@@ -480,19 +411,18 @@ def test_band_runner_over_rccl_self_ring(tmp_path, model):
     refuses two ranks per device, but a rank may send to itself, and a band that is its own
     neighbour on both sides is the periodic single domain.  Bit-identical to it (GCM_PE25D: edge
     rows updated and packed on the library's second stream while the interior rows run)."""
-    import torch.multiprocessing as mp
     import gcmiipy_amd as g
     from gcmiipy_amd import geometry
-    mp.spawn(_rccl_self_worker, args=(_free_port(), model, str(tmp_path)), nprocs=1, join=True)
+    su.spawn(_rccl_self_worker, (model, str(tmp_path)), 1)
     got = np.load(os.path.join(str(tmp_path), "self.npz"))
     model = model.split("-")[0]
     if model in ("pe", "pephys"):
         H, W, L = 23, 36, 9
         geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
         ref = g.Core(g._lib.PE25D, W, H, L, geom=geom)
-        ref.set_state(*_ic_pe(geom))
+        ref.set_state(*inp.state(geom))
         if model == "pephys":                      # the single domain: gcm_step with the physics registered
-            ref.set_ground(_ic_gt(H, W))
+            ref.set_ground(inp.ground(H, W))
             ref.set_physics(geom, UTC0)
         ref.step(5, 120.0)
     else:
@@ -526,7 +456,7 @@ def test_band_run_native_loopback_equals_single_domain(model):
         H, W, L, steps, dt = 23, 36, 9, 5, 120.0
         geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
         mk = lambda **kw: g.Core(g._lib.PE25D, W, H, L, geom=geom, **kw)
-        ic = dict(zip(("p", "u", "v", "t", "q"), _ic_pe(geom)))
+        ic = dict(zip(("p", "u", "v", "t", "q"), inp.state(geom)))
     else:
         H, W, steps, dt = 64, 130, 11 if not overlap else 23, 300.0
         mk = lambda **kw: g.Core(g._lib.SW2D_TEMP, W, H, dx=300e3, tracer=g._lib.TRACER_VANLEER, **kw)
@@ -535,7 +465,7 @@ def test_band_run_native_loopback_equals_single_domain(model):
     ref.set_state(**ic)
     if phys:
         # explicit calls on the single domain: step, solar_step at the clock, clock += dt (no_limits_2_5d.py:229-234)
-        ref.set_ground(_ic_gt(H, W))
+        ref.set_ground(inp.ground(H, W))
         for n in range(steps):
             ref.step(1, dt)
             ref.solar_step(geom, dt, UTC0 + n * dt)
@@ -552,7 +482,7 @@ def test_band_run_native_loopback_equals_single_domain(model):
         c.band_run(1, dt)
     eng = HipBandEngine(c, torch)
     if phys:
-        c.set_ground(_ic_gt(H, W))
+        c.set_ground(inp.ground(H, W))
         eng.set_physics(geom, UTC0)
     runner = BandRunner(eng, 0, 2, LoopbackExchange(), north=0, south=0)
     assert runner.native
@@ -582,10 +512,9 @@ def test_eight_bands_with_physics_equal_single_domain(dtype):
     import torch
     import gcmiipy_amd as g
     from gcmiipy_amd import geometry
-    from gcmiipy_amd.bands import split_rows
     H, W, L, steps, nb, dt = 64, 2880, 40, 3, 8, 60.0
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    ic, gt = _ic_pe(geom), _ic_gt(H, W)
+    ic, gt = inp.state(geom), inp.ground(H, W)
     ref = g.Core(g._lib.PE25D, W, H, L, geom=geom, dtype=dtype)
     ref.set_state(*ic)
     ref.set_ground(gt)
@@ -597,34 +526,14 @@ def test_eight_bands_with_physics_equal_single_domain(dtype):
         ref.solar_step(geom, dt, UTC0 + n * dt)
     want, want_gt = ref.get_state(), ref.get_ground()
     ref.close()
-    cores = []
-    for r, (row0, n) in enumerate(split_rows(H, nb)):
-        c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=nb, rank=r, global_height=H, row0=row0, dtype=dtype)
-        sl = slice(row0, row0 + n)
-        c.set_state(ic[0][sl], *[a[:, sl] for a in ic[1:]])
-        c.set_ground(gt[sl])
-        cores.append(c)
-    bufs = [[torch.empty(c.halo_bytes(), dtype=torch.uint8, device="cuda") for _ in (0, 1)] for c in cores]
+    cores = su.bands(g, geom, nb, ic, dtype=dtype, gt=gt)
 
-    def exchange():
-        for r, c in enumerate(cores):
-            c.halo_pack(0, bufs[r][0].data_ptr())
-            c.halo_pack(1, bufs[r][1].data_ptr())
-        torch.cuda.synchronize()
-        for r, c in enumerate(cores):
-            c.halo_unpack(1, bufs[(r + 1) % nb][0].data_ptr())
-            c.halo_unpack(0, bufs[(r - 1) % nb][1].data_ptr())
-        torch.cuda.synchronize()
-    exchange()                               # once: the ghost rows of the initial state and of gt
-    for n in range(steps):                   # the order of gcm_band_run: two exchanges per step, none after the physics
-        for c in cores:
-            c.step_interior(dt)              # predictor
-        exchange()                           # predicted state
-        for c in cores:
-            c.step_boundary(dt)              # corrector
-        exchange()                           # new state, BEFORE the radiation changes theta
+    def solar(n):
         for c in cores:
             c.solar_step(geom, dt, UTC0 + n * dt)      # own rows and ghost rows
+    # one exchange first (the ghost rows of the initial state and of gt), then the order of gcm_band_run: two exchanges
+    # per step -- the predicted state, and the new state BEFORE the radiation changes theta -- and none after the physics
+    su.whole_steps(cores, torch, steps, dt, after=solar)
     parts = [c.get_state() for c in cores]
     got_gt = np.concatenate([c.get_ground() for c in cores], axis=0)
     for c in cores:
@@ -656,7 +565,7 @@ def test_band_run_chains_at_overlapping_size(dtype, phys, monkeypatch):
     from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange
     H, W, L, dt = 48, 1440, 24, 1.0
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    ic, gt = _ic_pe(geom), _ic_gt(H, W)
+    ic, gt = inp.state(geom), inp.ground(H, W)
 
     def drive(core, run):
         """2 steps, an explicit solar_timestep, 3 steps; then the initial state again and 2 steps"""

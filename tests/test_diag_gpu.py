@@ -5,16 +5,11 @@ import numpy as np
 import pytest
 
 from conftest import golden, rel_err
+import gpu_setups as su
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
 
 
 def test_flux_limiter_pieces_bit_exact_vs_golden(g):
@@ -140,7 +135,7 @@ def test_band_total_variation_sums_to_global_and_needs_current_ghosts(g):
     exchanged -- and the call refuses (GCM_ERR_STATE) while they are stale, i.e. right after a step"""
     import torch
     from gcmiipy_amd.bands import split_rows
-    from test_bands_gpu import _exchange, _ic2d
+    from test_bands_gpu import _ic2d
     H, W, nb = 37, 130, 3
     f = _ic2d((H, W))
     kw = dict(dx=300e3, tracer=g._lib.TRACER_VANLEER)
@@ -154,7 +149,7 @@ def test_band_total_variation_sums_to_global_and_needs_current_ghosts(g):
     with pytest.raises(g.GcmError):
         cores[0].total_variation(g._lib.P)            # fresh state: ghost rows never filled
     for rnd in range(2):
-        _exchange(cores, torch)
+        su.exchange(cores, torch)
         for fld in (g._lib.P, g._lib.U, g._lib.Q):
             want = ref.total_variation(fld)
             got = sum(c.total_variation(fld) for c in cores)

@@ -5,17 +5,11 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
 DX, DT = 300e3, 300.0
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
 
 
 # (name, model, tracer): SW2D and SW2D_TEMP with every tracer scheme

@@ -16,31 +16,13 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+import gpu_setups as su
+import pe25d_inputs as inp
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
 DX = 300e3
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
-
-
-def pe_state(geom, seed=0):
-    """SURVEY.md 8d recipe for the primitive-equation workloads (bench.py synth())"""
-    rng = np.random.default_rng(seed)
-    L, H, W = geom.layers, geom.height, geom.width
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u = rng.standard_normal((L, H, W))
-    v = rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    tt = 300 + rng.standard_normal((L, H, W))
-    t = tt * ((1e5 / (p * np.asarray(geom.sig) + geom.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
-    return p, u, v, t, q
 
 
 # ------------------------------------------------------------------ configs[1], configs[2]
@@ -92,7 +74,7 @@ def test_c4_whole_grid_vs_oracle(g, hwl, steps):
     H, W, L = hwl
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
     og = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
-    ic = pe_state(og)
+    ic = inp.state(og, 0)
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom)
     c.set_state(*ic)
     c.step(steps, 1.0)
@@ -112,38 +94,19 @@ def test_c4_eight_bands_equal_single_domain(g):
     """1440x720x24 split into the 8 bands of BASELINE configs[3] (90 rows each, their own number
     of level segments), ghost rows moved by device copies: bit-identical to the single domain"""
     import torch
-    from gcmiipy_amd import geometry
-    from gcmiipy_amd.bands import split_rows
     H, W, L, steps, nb = 720, 1440, 24, 2, 8
-    geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    p, u, v, t, q = pe_state(geom)
-    ref = g.Core(g._lib.PE25D, W, H, L, geom=geom)
-    ref.set_state(p, u, v, t, q)
+    geom = su.geom_of(H, W, L)
+    st = inp.state(geom, 0)
+    ref = su.single(g, geom, st)
     ref.step(steps, 1.0)
     want = ref.get_state()
     ref.close()
-    cores = []
-    for r, (row0, n) in enumerate(split_rows(H, nb)):
-        c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=nb, rank=r, global_height=H, row0=row0)
-        sl = slice(row0, row0 + n)
-        c.set_state(p[sl], u[:, sl], v[:, sl], t[:, sl], q[:, sl])
-        cores.append(c)
-    bufs = [[torch.empty(c.halo_bytes(), dtype=torch.uint8, device="cuda") for _ in (0, 1)] for c in cores]
-
-    def exchange():
-        for r, c in enumerate(cores):
-            c.halo_pack(0, bufs[r][0].data_ptr())
-            c.halo_pack(1, bufs[r][1].data_ptr())
-        torch.cuda.synchronize()
-        for r, c in enumerate(cores):
-            c.halo_unpack(1, bufs[(r + 1) % nb][0].data_ptr())
-            c.halo_unpack(0, bufs[(r - 1) % nb][1].data_ptr())
-        torch.cuda.synchronize()
+    cores = su.bands(g, geom, nb, st)
     for _ in range(steps):
-        exchange()
+        su.exchange(cores, torch)
         for c in cores:
             c.step_interior(1.0)
-        exchange()
+        su.exchange(cores, torch)
         for c in cores:
             c.step_boundary(1.0)
     parts = [c.get_state() for c in cores]
@@ -199,7 +162,7 @@ def test_c5_2880x1440x40_strips_properties_fp32_sweep(g):
     dt, utc = 1.0, 6 * 3600.0
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
     og = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
-    ic = pe_state(og)
+    ic = inp.state(og, 0)
     rng = np.random.default_rng(5)
     gt = 288.0 + rng.standard_normal((H, W))
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom)

@@ -10,7 +10,7 @@ import types
 import numpy as np
 import pytest
 
-import band_van_leer_inputs as inp
+import pe25d_inputs as inp
 import pe25d_tracer_schemes_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,7 +83,7 @@ def test_one_ghost_row_cannot_give_the_single_domains_bits(band):
     c = inp.EIGHT
     H, W, L, nb, dt = c["H"], c["W"], c["L"], c["nb"], c["dt"]
     og = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
-    st = inp.state(H, W, L, og.sig, og.ptop)
+    st = inp.state(og)
     trs = inp.tracers(H, W, L, c["ntr"])
     star, spu, spv, sd = ref.stage_fluxes(st, st, dt, og)
     p, p_n = st[0], star[0]

@@ -4,113 +4,15 @@ single-domain handle, for state and tracers: the arithmetic per cell is the same
 band path -- eight in-process bands, host-driven whole stages and edge-first phases, gcm_band_run with the loopback
 exchange under every orchestration, two gloo ranks, the RCCL self-ring, checkpoints -- gives the single domain's bits.
 tests/test_pe25d_band_van_leer_cpu.py shows on the same seeded inputs that one ghost row could not."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-import band_van_leer_inputs as inp
+import gpu_setups as su
+import pe25d_inputs as inp
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-UTC0 = 5 * 3600.0
-ORCH_ENV = ("GCM_PE_SINGLE_STREAM", "GCM_BAND_COMM_STREAM", "GCM_BAND_HOST_LOOP", "GCM_BAND_OVERLAP")
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
-
-
-def _geom(H, W, L):
-    from gcmiipy_amd import geometry
-    return geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-
-
-def _ic(geom, ntr, seed=inp.TRACER_SEED):
-    H, W, L = geom.height, geom.width, geom.layers
-    return inp.state(H, W, L, np.asarray(geom.sig), geom.ptop), inp.tracers(H, W, L, ntr, seed)
-
-
-def _gt(H, W):
-    return 288.0 + np.random.default_rng(13).standard_normal((H, W))
-
-
-def _single(g, geom, st, trs, steps, dt, scheme="van_leer", dtype="f64"):
-    one = g.Core(g._lib.PE25D, geom.width, geom.height, geom.layers, geom=geom, dtype=dtype, tracer_scheme=scheme)
-    one.set_state(*st)
-    one.set_tracers(trs)
-    one.step(steps, dt)
-    out = one.get_state(), one.get_tracers()
-    one.close()
-    return out
-
-
-def _bands(g, geom, nb, st, trs, dtype="f64", scheme="van_leer", rows=2):
-    from gcmiipy_amd.bands import split_rows
-    H, W, L = geom.height, geom.width, geom.layers
-    cores = []
-    for r, (row0, n) in enumerate(split_rows(H, nb)):
-        c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=nb, rank=r, global_height=H, row0=row0, dtype=dtype,
-                   band_tracers=trs.shape[0], band_tracer_rows=rows, tracer_scheme=scheme)
-        assert c.band_tracer_rows == rows and c.tracer_scheme == g.core.tracer_scheme_id(scheme)
-        esz = 8 if dtype == "f64" else 4
-        assert c.halo_bytes() == inp.halo_bytes(W, L, esz, trs.shape[0], rows)
-        sl = slice(row0, row0 + n)
-        c.set_state(*[inp.rows(a, sl) for a in st])
-        c.set_tracers(inp.rows(trs, sl))
-        cores.append(c)
-    return cores
-
-
-def _exchange(cores, torch):
-    """ring exchange by device copies on the default stream: side s of a band lands in the neighbour's opposite ghost"""
-    n = len(cores)
-    bufs = [[torch.empty(c.halo_bytes(), dtype=torch.uint8, device="cuda") for _ in (0, 1)] for c in cores]
-    for r, c in enumerate(cores):
-        c.halo_pack(0, bufs[r][0].data_ptr())
-        c.halo_pack(1, bufs[r][1].data_ptr())
-    torch.cuda.synchronize()
-    for r, c in enumerate(cores):
-        c.halo_unpack(1, bufs[(r + 1) % n][0].data_ptr())
-        c.halo_unpack(0, bufs[(r - 1) % n][1].data_ptr())
-    torch.cuda.synchronize()
-
-
-def _whole_steps(cores, torch, n, dt, prime=True):
-    """whole stages, two exchanges per step (the order of gcm_band_run)"""
-    if prime:
-        _exchange(cores, torch)
-    for _ in range(n):
-        for c in cores:
-            c.step_interior(dt)                      # predictor
-        _exchange(cores, torch)
-        for c in cores:
-            c.step_boundary(dt)                      # corrector
-        _exchange(cores, torch)
-
-
-def _gather(cores, close=True):
-    parts = [c.get_state() for c in cores]
-    state = [np.concatenate([x[f] for x in parts], axis=0 if f == 0 else 1) for f in range(5)]
-    tr = np.concatenate([c.get_tracers() for c in cores], axis=2)
-    if close:
-        for c in cores:
-            c.close()
-    return state, tr
-
-
-def _assert_equal(got, want, what=""):
-    (gs, gtr), (ws, wtr) = got, want
-    for f in range(5):
-        assert np.array_equal(gs[f], ws[f]), (what, "puvtq"[f])
-    assert gtr.shape == wtr.shape
-    for n in range(wtr.shape[0]):
-        assert np.array_equal(gtr[n], wtr[n]), (what, "tracer", n)
+UTC0 = inp.UTC0
 
 
 # ---------------------------------------------------------------- 1. eight in-process bands
@@ -121,14 +23,14 @@ def test_van_leer_on_eight_bands_equals_single_domain(g, dtype):
     the tracers are not those of the UPWIND run (VANLEER really ran)"""
     import torch
     c = inp.EIGHT
-    geom = _geom(c["H"], c["W"], c["L"])
-    st, trs = _ic(geom, c["ntr"])
-    want = _single(g, geom, st, trs, c["steps"], c["dt"], "van_leer", dtype)
-    upwind = _single(g, geom, st, trs, c["steps"], c["dt"], "upwind", dtype)
-    cores = _bands(g, geom, c["nb"], st, trs, dtype)
-    _whole_steps(cores, torch, c["steps"], c["dt"])
-    got = _gather(cores)
-    _assert_equal(got, want, dtype)
+    geom = su.geom_of(c["H"], c["W"], c["L"])
+    st, trs = su.initial(geom, c["ntr"])
+    want = su.single_run(g, geom, st, trs, c["steps"], c["dt"], scheme="van_leer", dtype=dtype)
+    upwind = su.single_run(g, geom, st, trs, c["steps"], c["dt"], scheme="upwind", dtype=dtype)
+    cores = su.bands(g, geom, c["nb"], st, trs, dtype=dtype, scheme="van_leer", rows=2)
+    su.whole_steps(cores, torch, c["steps"], c["dt"])
+    got = su.gather(cores)
+    su.assert_equal(got, want, dtype)
     assert not np.array_equal(got[1], upwind[1])
     assert not np.array_equal(got[1][1], upwind[1][1])            # the step function itself
     assert not np.array_equal(got[1], trs)
@@ -145,24 +47,16 @@ def test_host_driven_bands_equal_single_domain(g, mode, nb, ntr):
     2; 4 + 1); 16 rows in 3 bands: bands of 6, 5 and 5 rows (one interior row between the edge rows)"""
     import torch
     H, W, L, steps, dt = 16, 20, 5, 3, 120.0
-    geom = _geom(H, W, L)
+    geom = su.geom_of(H, W, L)
     geom.heightmap[H // 2, 3] = 300.0
-    st, trs = _ic(geom, ntr)
-    want = _single(g, geom, st, trs, steps, dt)
-    cores = _bands(g, geom, nb, st, trs)
+    st, trs = su.initial(geom, ntr)
+    want = su.single_run(g, geom, st, trs, steps, dt, scheme="van_leer")
+    cores = su.bands(g, geom, nb, st, trs, scheme="van_leer", rows=2)
     if mode == "whole":
-        _whole_steps(cores, torch, steps, dt)
+        su.whole_steps(cores, torch, steps, dt)
     else:
-        _exchange(cores, torch)                              # the initial state's ghost rows
-        for _ in range(steps):
-            for stage in (0, 1):
-                for c in cores:
-                    c.step_phase(2 * stage, dt)
-                for c in cores:
-                    c.step_phase(2 * stage + 1, dt)
-                torch.cuda.synchronize()
-                _exchange(cores, torch)
-    _assert_equal(_gather(cores), want, (mode, nb, ntr))
+        su.phase_steps(cores, torch, steps, dt)
+    su.assert_equal(su.gather(cores), want, (mode, nb, ntr))
 
 
 def test_unsplittable_short_bands_equal_single_domain(g):
@@ -170,35 +64,16 @@ def test_unsplittable_short_bands_equal_single_domain(g):
     host-driven phases"""
     import torch
     H, W, L, steps, dt = 14, 20, 5, 3, 120.0
-    geom = _geom(H, W, L)
-    st, trs = _ic(geom, 3)
-    want = _single(g, geom, st, trs, steps, dt)
-    cores = _bands(g, geom, 4, st, trs)                      # 4, 4, 3, 3 rows
+    geom = su.geom_of(H, W, L)
+    st, trs = su.initial(geom, 3)
+    want = su.single_run(g, geom, st, trs, steps, dt, scheme="van_leer")
+    cores = su.bands(g, geom, 4, st, trs, scheme="van_leer", rows=2)        # 4, 4, 3, 3 rows
     assert sorted(c.H for c in cores) == [3, 3, 4, 4]
-    _exchange(cores, torch)
-    for _ in range(steps):
-        for stage in (0, 1):
-            for c in cores:
-                c.step_phase(2 * stage, dt)
-            for c in cores:
-                c.step_phase(2 * stage + 1, dt)
-            torch.cuda.synchronize()
-            _exchange(cores, torch)
-    _assert_equal(_gather(cores), want)
+    su.phase_steps(cores, torch, steps, dt)
+    su.assert_equal(su.gather(cores), want)
 
 
 # ---------------------------------------------------------------- 3. gcm_band_run, loopback exchange
-def _loopback_band(g, torch, geom, ntr, dtype, scheme="van_leer", rows=2):
-    from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange
-    H, W, L = geom.height, geom.width, geom.layers
-    c = g.Core(g._lib.PE25D, W, H, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0, dtype=dtype,
-               stream=torch.cuda.current_stream().cuda_stream, band_tracers=ntr, band_tracer_rows=rows,
-               tracer_scheme=scheme)
-    eng = HipBandEngine(c, torch)
-    runner = BandRunner(eng, 0, 2, LoopbackExchange(), north=0, south=0)
-    return c, eng, runner
-
-
 @pytest.mark.parametrize("overlap", [False, True])
 @pytest.mark.parametrize("phys", [False, True])
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
@@ -211,8 +86,8 @@ def test_band_run_loopback_equals_single_domain(g, dtype, phys, overlap):
     boundary are checked by the eight-band, host-driven, gloo and checkpoint tests."""
     import torch
     H, W, L, dt, ntr = 23, 36, 9, 120.0, 3
-    geom = _geom(H, W, L)
-    (st, tr0), gt = _ic(geom, ntr), _gt(H, W)
+    geom = su.geom_of(H, W, L)
+    (st, tr0), gt = su.initial(geom, ntr), inp.ground(H, W)
     tr1 = inp.tracers(H, W, L, ntr, seed=16)[::-1].copy()
 
     def drive(core, run, set_physics):
@@ -231,7 +106,7 @@ def test_band_run_loopback_equals_single_domain(g, dtype, phys, overlap):
     ref = g.Core(g._lib.PE25D, W, H, L, geom=geom, dtype=dtype, tracer_scheme="van_leer")
     want = drive(ref, lambda n: ref.step(n, dt), lambda: ref.set_physics(geom, UTC0))
     ref.close()
-    c, eng, runner = _loopback_band(g, torch, geom, ntr, dtype)
+    c, eng, runner = su.loopback_band(g, torch, geom, ntr, dtype, scheme="van_leer", rows=2)
     assert runner.native
     if overlap:
         c.set_band_overlap(True)
@@ -242,7 +117,7 @@ def test_band_run_loopback_equals_single_domain(g, dtype, phys, overlap):
     got = drive(c, run, lambda: eng.set_physics(geom, UTC0))
     c.close()
     for part, (a, b) in enumerate(zip(got, want)):
-        _assert_equal(a, b, part)
+        su.assert_equal(a, b, part)
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
@@ -254,16 +129,16 @@ def test_band_run_van_leer_at_overlapping_size(g, dtype, monkeypatch):
     (GCM_BAND_OVERLAP=1).  Loopback: the pole boundary only, see test_band_run_loopback_equals_single_domain."""
     import torch
     H, W, L, dt, ntr = 48, 1440, 24, 1.0, 4
-    geom = _geom(H, W, L)
-    st, trs = _ic(geom, ntr)
-    want = _single(g, geom, st, trs, 5, dt, "van_leer", dtype)
+    geom = su.geom_of(H, W, L)
+    st, trs = su.initial(geom, ntr)
+    want = su.single_run(g, geom, st, trs, 5, dt, scheme="van_leer", dtype=dtype)
     for env in ({}, {"GCM_PE_SINGLE_STREAM": "1"}, {"GCM_BAND_COMM_STREAM": "1"}, {"GCM_BAND_HOST_LOOP": "1"},
                 {"GCM_BAND_OVERLAP": "1"}):
-        for k in ORCH_ENV:
+        for k in su.ORCH_ENV:
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        c, eng, runner = _loopback_band(g, torch, geom, ntr, dtype)
+        c, eng, runner = su.loopback_band(g, torch, geom, ntr, dtype, scheme="van_leer", rows=2)
         assert runner.native == ("GCM_BAND_HOST_LOOP" not in env)
         c.set_state(*st)
         c.set_tracers(trs)
@@ -272,124 +147,33 @@ def test_band_run_van_leer_at_overlapping_size(g, dtype, monkeypatch):
         torch.cuda.synchronize()
         got = c.get_state(), c.get_tracers()
         c.close()
-        _assert_equal(got, want, env)
+        su.assert_equal(got, want, env)
 
 
 # ---------------------------------------------------------------- 4. separate processes
 GLOO_SHAPE = (14, 20, 5)        # H, W, L
 RCCL_SHAPE = (23, 36, 9)
 NTR = 3
-WORKER_TIMEOUT = 240            # seconds, each child process
 
 
 def _reference(g, shape, steps, dt):
-    geom = _geom(*shape)
-    st, trs = _ic(geom, NTR)
-    return _single(g, geom, st, trs, steps, dt)
-
-
-def _worker_paths():
-    for p in (ROOT, HERE):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-
-
-def _gloo_worker(rank, world, overlap, outdir):
-    _worker_paths()
-    import torch
-    import torch.distributed as dist
-    import gcmiipy_amd as g
-    from gcmiipy_amd.bands import BandRunner, HipBandEngine, split_rows
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", init_method="file://" + os.path.join(outdir, "rendezvous"), rank=rank, world_size=world)
-    H, W, L = GLOO_SHAPE
-    geom = _geom(H, W, L)
-    st, trs = _ic(geom, NTR)
-    row0, n = split_rows(H, world)[rank]
-    sl = slice(row0, row0 + n)
-    c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=world, rank=rank, global_height=H, row0=row0,
-               stream=torch.cuda.current_stream().cuda_stream, band_tracers=NTR, band_tracer_rows=2,
-               tracer_scheme="van_leer")
-    c.set_state(*[inp.rows(a, sl) for a in st])
-    c.set_tracers(inp.rows(trs, sl))
-    eng = HipBandEngine(c, torch, overlap=overlap, stream_aware=False)
-    assert eng.edge_first == overlap
-    runner = BandRunner(eng, rank, world, dist)
-    runner.run(1, 120.0)
-    runner.run(2, 120.0)
-    torch.cuda.synchronize()
-    np.savez(os.path.join(outdir, "r%d.npz" % rank), tr=c.get_tracers(), **dict(zip("puvtq", c.get_state())))
-    c.close()
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-def _rccl_worker(rank, outdir):
-    _worker_paths()
-    import torch
-    import torch.distributed as dist
-    import gcmiipy_amd as g
-    from gcmiipy_amd.bands import BandRunner, HipBandEngine
-    from gcmiipy_amd.rccl import RcclP2P
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", init_method="file://" + os.path.join(outdir, "rendezvous"), rank=0, world_size=1,
-                            device_id=torch.device("cuda", 0))
-    ring = RcclP2P(None, 0, 1, uid_bytes=RcclP2P.new_unique_id())
-    H, W, L = RCCL_SHAPE
-    geom = _geom(H, W, L)
-    st, trs = _ic(geom, NTR)
-    c = g.Core(g._lib.PE25D, W, H, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0,
-               stream=torch.cuda.current_stream().cuda_stream, band_tracers=NTR, band_tracer_rows=2,
-               tracer_scheme="van_leer")
-    c.set_state(*st)
-    c.set_tracers(trs)
-    runner = BandRunner(HipBandEngine(c, torch), 0, 2, ring, north=0, south=0)
-    assert runner.native
-    runner.run(3, 120.0)
-    runner.run(2, 120.0)
-    torch.cuda.synchronize()
-    np.savez(os.path.join(outdir, "self.npz"), tr=c.get_tracers(), **dict(zip("puvtq", c.get_state())))
-    c.close()
-    ring.close()
-    dist.destroy_process_group()
-
-
-def _spawn(fn, args, nprocs):
-    """fresh child processes (spawn), each under its own time limit; no retries: a child that is late is killed and
-    the test fails"""
-    import torch.multiprocessing as mp
-    ctx = mp.spawn(fn, args=args, nprocs=nprocs, join=False)
-    try:
-        for p in ctx.processes:
-            p.join(WORKER_TIMEOUT)
-        late = [p.pid for p in ctx.processes if p.is_alive()]
-        assert not late, "worker processes still running after %d s: %s" % (WORKER_TIMEOUT, late)
-        while not ctx.join(timeout=5):
-            pass                                             # (all have exited: this collects their exit status)
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-                p.join(10)
+    geom = su.geom_of(*shape)
+    st, trs = su.initial(geom, NTR)
+    return su.single_run(g, geom, st, trs, steps, dt, scheme="van_leer")
 
 
 @pytest.mark.parametrize("overlap", [True, False])
 def test_gloo_ranks_one_gpu(g, tmp_path, overlap):
     """two ranks in two processes on the one GPU, HipBandEngine + BandRunner over gloo: the default engine (edge-first
     phases, the split stage) and overlap=False (whole stages); gathered from the ranks: the single domain's bits"""
-    _spawn(_gloo_worker, (2, overlap, str(tmp_path)), 2)
-    parts = [np.load(os.path.join(str(tmp_path), "r%d.npz" % r)) for r in range(2)]
-    want = _reference(g, GLOO_SHAPE, 3, 120.0)
-    got = [np.concatenate([x[k] for x in parts], axis=0 if k == "p" else 1) for k in "puvtq"]
-    _assert_equal((got, np.concatenate([x["tr"] for x in parts], axis=2)), want, overlap)
+    su.spawn(su.gloo_tracer_worker, (2, overlap, str(tmp_path), GLOO_SHAPE, NTR, False, 2, "van_leer"), 2)
+    su.assert_equal(su.load_ranks(str(tmp_path), 2), _reference(g, GLOO_SHAPE, 3, 120.0), overlap)
 
 
 def test_rccl_self_ring_native(g, tmp_path):
     """gcm_band_run over RCCL called directly, the band its own neighbour on both sides (the periodic single domain)"""
-    _spawn(_rccl_worker, (str(tmp_path),), 1)
-    got = np.load(os.path.join(str(tmp_path), "self.npz"))
-    want = _reference(g, RCCL_SHAPE, 5, 120.0)
-    _assert_equal(([got[k] for k in "puvtq"], got["tr"]), want)
+    su.spawn(su.rccl_tracer_worker, (str(tmp_path), RCCL_SHAPE, NTR, False, 2, "van_leer"), 1)
+    su.assert_equal(su.load_self(str(tmp_path)), _reference(g, RCCL_SHAPE, 5, 120.0))
 
 
 # ---------------------------------------------------------------- 5. depth 2 under the other schemes
@@ -401,25 +185,17 @@ def test_depth_two_under_centred_and_upwind(g, scheme, dtype):
     domain's -- host-driven phases on 3 bands and gcm_band_run with the loopback exchange"""
     import torch
     H, W, L, steps, dt, ntr = 16, 20, 5, 3, 120.0, 3
-    geom = _geom(H, W, L)
-    st, trs = _ic(geom, ntr)
-    want = _single(g, geom, st, trs, steps, dt, scheme, dtype)
-    cores = _bands(g, geom, 3, st, trs, dtype, scheme, rows=2)
-    one_row = _bands(g, geom, 3, st, trs, dtype, scheme, rows=1)
+    geom = su.geom_of(H, W, L)
+    st, trs = su.initial(geom, ntr)
+    want = su.single_run(g, geom, st, trs, steps, dt, scheme=scheme, dtype=dtype)
+    cores = su.bands(g, geom, 3, st, trs, dtype=dtype, scheme=scheme, rows=2)
+    one_row = su.bands(g, geom, 3, st, trs, dtype=dtype, scheme=scheme, rows=1)
     for a, b in zip(cores, one_row):
         assert a.halo_bytes() - b.halo_bytes() == ntr * (8 if dtype == "f64" else 4) * L * W
         b.close()
-    _exchange(cores, torch)
-    for _ in range(steps):
-        for stage in (0, 1):
-            for c in cores:
-                c.step_phase(2 * stage, dt)
-            for c in cores:
-                c.step_phase(2 * stage + 1, dt)
-            torch.cuda.synchronize()
-            _exchange(cores, torch)
-    _assert_equal(_gather(cores), want, scheme)
-    c, eng, runner = _loopback_band(g, torch, geom, ntr, dtype, scheme, rows=2)
+    su.phase_steps(cores, torch, steps, dt)
+    su.assert_equal(su.gather(cores), want, scheme)
+    c, eng, runner = su.loopback_band(g, torch, geom, ntr, dtype, scheme=scheme, rows=2)
     assert runner.native
     c.set_state(*st)
     c.set_tracers(trs)
@@ -427,15 +203,15 @@ def test_depth_two_under_centred_and_upwind(g, scheme, dtype):
     torch.cuda.synchronize()
     got = c.get_state(), c.get_tracers()
     c.close()
-    _assert_equal(got, want, (scheme, "band_run"))
+    su.assert_equal(got, want, (scheme, "band_run"))
 
 
 def test_switching_schemes_on_a_depth_two_band(g):
     """VANLEER for 2 steps, then the centred scheme for 2, on 2 depth-2 bands: the single domain doing the same"""
     import torch
     H, W, L, dt, ntr = 16, 20, 5, 120.0, 3
-    geom = _geom(H, W, L)
-    st, trs = _ic(geom, ntr)
+    geom = su.geom_of(H, W, L)
+    st, trs = su.initial(geom, ntr)
     one = g.Core(g._lib.PE25D, W, H, L, geom=geom, tracer_scheme="van_leer")
     one.set_state(*st)
     one.set_tracers(trs)
@@ -445,14 +221,14 @@ def test_switching_schemes_on_a_depth_two_band(g):
     one.step(2, dt)
     want = one.get_state(), one.get_tracers()
     one.close()
-    cores = _bands(g, geom, 2, st, trs)
-    _whole_steps(cores, torch, 2, dt)
-    assert np.array_equal(_gather(cores, close=False)[1], mid)
+    cores = su.bands(g, geom, 2, st, trs, scheme="van_leer", rows=2)
+    su.whole_steps(cores, torch, 2, dt)
+    assert np.array_equal(su.gather(cores, close=False)[1], mid)
     for c in cores:
         c.set_tracer_scheme("centred")
         assert c.band_tracer_rows == 2 and c.tracer_scheme == g._lib.TRACER_NONE
-    _whole_steps(cores, torch, 2, dt, prime=False)
-    _assert_equal(_gather(cores), want)
+    su.whole_steps(cores, torch, 2, dt, prime=False)
+    su.assert_equal(su.gather(cores), want)
 
 
 # ---------------------------------------------------------------- 6. the setter's refusals
@@ -462,7 +238,7 @@ def test_refusals_of_the_setter(g):
     from gcmiipy_amd.core import GcmError
     lib = _lib.lib
     H, W, L = 12, 20, 5
-    geom = _geom(H, W, L)
+    geom = su.geom_of(H, W, L)
     band = lambda dtype="f64", **kw: g.Core(_lib.PE25D, W, 6, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0,
                                             dtype=dtype, **kw)
     c = band()
@@ -488,7 +264,7 @@ def test_refusals_of_the_setter(g):
         c.set_tracer_scheme("van_leer")
     assert c.options["tracer_scheme"] == _lib.TRACER_UPWIND
     # a change of depth gives zeros, like a change of count
-    q = inp.state(H, W, L, np.asarray(geom.sig), geom.ptop)[4]
+    q = inp.state(geom)[4]
     three = np.ascontiguousarray(np.stack([q[:, :6]] * 3))
     c.set_tracers(three)
     assert np.array_equal(c.get_tracers(), three)
@@ -538,11 +314,11 @@ def test_checkpoint_restores_depth_and_scheme(g, tmp_path):
     import torch
     from gcmiipy_amd import checkpoint
     H, W, L, dt, ntr = 16, 20, 5, 120.0, 3
-    geom = _geom(H, W, L)
-    st, trs = _ic(geom, ntr)
-    want = _single(g, geom, st, trs, 4, dt)
-    cores = _bands(g, geom, 2, st, trs)
-    _whole_steps(cores, torch, 2, dt)
+    geom = su.geom_of(H, W, L)
+    st, trs = su.initial(geom, ntr)
+    want = su.single_run(g, geom, st, trs, 4, dt, scheme="van_leer")
+    cores = su.bands(g, geom, 2, st, trs, scheme="van_leer", rows=2)
+    su.whole_steps(cores, torch, 2, dt)
     for r, c in enumerate(cores):
         checkpoint.save(str(tmp_path / ("b%d.npz" % r)), c, step=2, geom=geom)
         c.close()
@@ -552,8 +328,8 @@ def test_checkpoint_restores_depth_and_scheme(g, tmp_path):
         assert ck["options"]["band_tracer_rows"] == 2 and c.band_tracer_rows == 2
         assert c.tracer_scheme == g._lib.TRACER_VANLEER and c.tracer_count == ntr
         cores.append(c)
-    _whole_steps(cores, torch, 2, dt)
-    _assert_equal(_gather(cores), want)
+    su.whole_steps(cores, torch, 2, dt)
+    su.assert_equal(su.gather(cores), want)
     d = dict(np.load(str(tmp_path / "b0.npz")))
     del d["opt_band_tracer_rows"]                            # a file written before the option existed ...
     d["opt_tracer_scheme"] = np.asarray(g._lib.TRACER_UPWIND)     # ... which could not hold VANLEER on a band

@@ -11,8 +11,9 @@ import sys
 import numpy as np
 import pytest
 
-import band_van_leer_inputs as inp
+import gpu_setups as su
 import pe25d_climate_ref as ref
+import pe25d_inputs as inp
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SHAPES = ((6, 10, 3), (24, 36, 9), (6, 70, 2), (6, 130, 2), (4, 300, 2))      # (H, W, L)
 BAND_SHAPE = (24, 36, 9)
 PTOP = 1000.0
-UTC0 = 5 * 3600.0
+UTC0 = inp.UTC0
 DT = 120.0
 EXACT_WORDS = tuple(w for w in range(10) if w not in ref.EXNER_WORDS)
 SWITCHES = ({"GCM_PE_SINGLE_STREAM": "1"}, {"GCM_BAND_COMM_STREAM": "1"}, {"GCM_BAND_OVERLAP": "1"},
@@ -28,45 +29,8 @@ SWITCHES = ({"GCM_PE_SINGLE_STREAM": "1"}, {"GCM_BAND_COMM_STREAM": "1"}, {"GCM_
 CHILD_TIMEOUT = 120                                       # seconds: start-up of a fresh process included
 
 
-def geom_of(H, W, L, ptop=0.0):
-    from gcmiipy_amd import geometry
-    geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    geom.ptop = ptop
-    return geom
-
-
 def sig_of(geom):
     return np.asarray(geom.sig, dtype=np.float64).reshape(-1)
-
-
-def state_of(geom, dtype="f64", wind=8.0):
-    """the band tests' seeded state with winds of several m/s; f32: rounded to float32 (what the handle holds)"""
-    H, W, L = geom.height, geom.width, geom.layers
-    p, u, v, t, q = inp.state(H, W, L, np.asarray(geom.sig), geom.ptop)
-    p = p - geom.ptop
-    t = t * (1.0 + 0.05 * np.sin(np.arange(H) * 0.7)[None, :, None])
-    st = [p, wind * u, wind * v, t, q]
-    if dtype == "f32":
-        st = [a.astype(np.float32).astype(np.float64) for a in st]
-    return st
-
-
-def ground_of(H, W):
-    return 288.0 + np.random.default_rng(13).standard_normal((H, W))
-
-
-def single(g, geom, st, dtype="f64", gt=None, phys=False, hs=False, every=None):
-    c = g.Core(g._lib.PE25D, geom.width, geom.height, geom.layers, geom=geom, dtype=dtype)
-    c.set_state(*st)
-    if gt is not None:
-        c.set_ground(gt)
-    if phys:
-        c.set_physics(geom, UTC0)
-    if hs:
-        c.set_held_suarez(geom)
-    if every is not None:
-        c.set_climate(every)
-    return c
 
 
 def assert_sums_equal(got, want, what=""):
@@ -99,10 +63,10 @@ def assert_sums_match_restatement(got, want, bnd, what=""):
 def test_one_sample_equals_the_restatement(shape, ptop, dtype):
     import gcmiipy_amd as g
     H, W, L = shape
-    geom = geom_of(H, W, L, ptop)
-    st = state_of(geom, dtype)
-    trs, gt = inp.tracers(H, W, L, 2), ground_of(H, W)
-    c = single(g, geom, st, dtype, gt=gt, every=10 ** 6)
+    geom = su.geom_of(H, W, L, ptop)
+    st = inp.state_of(geom, dtype)
+    trs, gt = inp.tracers(H, W, L, 2), inp.ground(H, W)
+    c = su.single(g, geom, st, dtype=dtype, gt=gt, every=10 ** 6)
     c.set_tracers(trs)
     trs0 = c.get_tracers()
     assert c.climate_every == 10 ** 6 and c.climate().n == 0
@@ -131,13 +95,13 @@ def test_planted_values_at_the_wraps(dtype):
     row 0 exactly that times theta"""
     import gcmiipy_amd as g
     H, W, L = 6, 10, 3
-    geom = geom_of(H, W, L)
-    st = state_of(geom, dtype)
+    geom = su.geom_of(H, W, L)
+    st = inp.state_of(geom, dtype)
     u, v = np.zeros((L, H, W)), np.zeros((L, H, W))
     u[L - 1, H - 1, W - 1] = 6.0
     v[:, H - 1, 0] = 3.0 + np.arange(L)
     st = [st[0], u, v, st[3], st[4]]
-    c = single(g, geom, st, dtype, every=1)
+    c = su.single(g, geom, st, dtype=dtype, every=1)
     c.climate_sample()
     n, m3, m2 = c.climate_sums()
     c.close()
@@ -162,14 +126,14 @@ def test_planted_values_at_the_wraps(dtype):
 def test_registered_equals_explicit_samples(dtype):
     import gcmiipy_amd as g
     H, W, L = BAND_SHAPE
-    geom = geom_of(H, W, L)
-    st = state_of(geom, dtype)
-    a = single(g, geom, st, dtype, every=2)
+    geom = su.geom_of(H, W, L)
+    st = inp.state_of(geom, dtype)
+    a = su.single(g, geom, st, dtype=dtype, every=2)
     a.step(5, DT)
     got = a.climate_sums()
     assert got[0] == 2
     state_a = a.get_state()
-    b = single(g, geom, st, dtype, every=10 ** 6)
+    b = su.single(g, geom, st, dtype=dtype, every=10 ** 6)
     for n, sample in ((2, True), (2, True), (1, False)):
         b.step(n, DT)
         if sample:
@@ -177,13 +141,13 @@ def test_registered_equals_explicit_samples(dtype):
     assert_sums_equal(got, b.climate_sums(), "explicit")
     b.close()
     # the counter runs across calls
-    c = single(g, geom, st, dtype, every=2)
+    c = su.single(g, geom, st, dtype=dtype, every=2)
     for _ in range(5):
         c.step(1, DT)
     assert_sums_equal(got, c.climate_sums(), "step(1) five times")
     c.close()
     # the state is the unregistered run's
-    u = single(g, geom, st, dtype)
+    u = su.single(g, geom, st, dtype=dtype)
     u.step(5, DT)
     for k, x, y in zip("puvtq", state_a, u.get_state()):
         assert np.array_equal(x, y), k
@@ -201,14 +165,14 @@ def test_registered_sample_sees_the_forced_state(dtype):
     taken from an identical run, go through the restatement"""
     import gcmiipy_amd as g
     H, W, L = BAND_SHAPE
-    geom = geom_of(H, W, L)
-    st, gt = state_of(geom, dtype), ground_of(H, W)
-    a = single(g, geom, st, dtype, gt=gt, phys=True, hs=True, every=2)
+    geom = su.geom_of(H, W, L)
+    st, gt = inp.state_of(geom, dtype), inp.ground(H, W)
+    a = su.single(g, geom, st, dtype=dtype, gt=gt, phys=True, hs={}, every=2)
     a.step(5, DT)
     got = a.climate_sums()
     state_a = a.get_state()
     a.close()
-    b = single(g, geom, st, dtype, gt=gt, phys=True, hs=True)
+    b = su.single(g, geom, st, dtype=dtype, gt=gt, phys=True, hs={})
     seen = []
     for n in (2, 2, 1):
         b.step(n, DT)
@@ -222,27 +186,13 @@ def test_registered_sample_sees_the_forced_state(dtype):
     worst = assert_sums_match_restatement(got, want, bnd, "forced")
     print("largest ratio of the Exner words, forced state", dtype, worst)
     # the unforced run's samples are other numbers
-    plain = single(g, geom, st, dtype, every=2)
+    plain = su.single(g, geom, st, dtype=dtype, every=2)
     plain.step(5, DT)
     assert not np.array_equal(plain.climate_sums()[1][2], got[1][2])
     plain.close()
 
 
 # ---------------------------------------------------------------- 4: bands
-def _exchange(cores, torch):
-    """ring exchange by device copies on the default stream: side s of a band lands in the neighbour's opposite ghost"""
-    n = len(cores)
-    bufs = [[torch.empty(c.halo_bytes(), dtype=torch.uint8, device="cuda") for _ in (0, 1)] for c in cores]
-    for r, c in enumerate(cores):
-        c.halo_pack(0, bufs[r][0].data_ptr())
-        c.halo_pack(1, bufs[r][1].data_ptr())
-    torch.cuda.synchronize()
-    for r, c in enumerate(cores):
-        c.halo_unpack(1, bufs[(r + 1) % n][0].data_ptr())
-        c.halo_unpack(0, bufs[(r - 1) % n][1].data_ptr())
-    torch.cuda.synchronize()
-
-
 _single_cache = {}
 
 
@@ -250,8 +200,8 @@ def single_reference(g, shape, dtype, steps, dt=DT):
     """the single domain with Held-Suarez and every = 1 after `steps` steps: (sums, state), computed once per case"""
     key = (shape, dtype, steps, dt)
     if key not in _single_cache:
-        geom = geom_of(*shape)
-        c = single(g, geom, state_of(geom, dtype), dtype, hs=True, every=1)
+        geom = su.geom_of(*shape)
+        c = su.single(g, geom, inp.state_of(geom, dtype), dtype=dtype, hs={}, every=1)
         c.step(steps, dt)
         sums, state = c.climate_sums(), c.get_state()
         c.close()
@@ -277,31 +227,21 @@ def test_three_in_process_bands_equal_the_single_domain(dtype):
     import torch
     import gcmiipy_amd as g
     from gcmiipy_amd import Climate
-    from gcmiipy_amd.bands import split_rows
     H, W, L = BAND_SHAPE
     steps = 4
     want, want_state = single_reference(g, BAND_SHAPE, dtype, steps)
-    geom = geom_of(H, W, L)
-    st = state_of(geom, dtype)
-    cores = []
-    for r, (row0, n) in enumerate(split_rows(H, 3)):
-        assert n == 8
-        c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=3, rank=r, global_height=H, row0=row0, dtype=dtype)
-        c.set_state(*[inp.rows(a, slice(row0, row0 + n)) for a in st])
+    geom = su.geom_of(H, W, L)
+    cores = su.bands(g, geom, 3, inp.state_of(geom, dtype), dtype=dtype)
+    for c in cores:
+        assert c.H == 8
         c.set_held_suarez(geom)
         c.set_climate(1)
-        cores.append(c)
-    _exchange(cores, torch)
-    for _ in range(steps):
-        for c in cores:
-            c.step_interior(DT)
-        _exchange(cores, torch)
-        for c in cores:
-            c.step_boundary(DT)
-        _exchange(cores, torch)
+
+    def forcing_and_sample(k):
         for c in cores:
             c.held_suarez_step(geom, DT)
             c.climate_sample()
+    su.whole_steps(cores, torch, steps, DT, after=forcing_and_sample)
     merged, raw = merged_sums(cores)
     assert_sums_equal(raw, want, "three bands")
     whole = Climate.from_sums(want[0], want[1], want[2], W)
@@ -315,18 +255,12 @@ def test_three_in_process_bands_equal_the_single_domain(dtype):
 def test_loopback_band_run_equals_the_single_domain(dtype):
     import torch
     import gcmiipy_amd as g
-    from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange
     H, W, L = BAND_SHAPE
     want, want_state = single_reference(g, BAND_SHAPE, dtype, 4)
-    geom = geom_of(H, W, L)
-    c = g.Core(g._lib.PE25D, W, H, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0, dtype=dtype,
-               stream=torch.cuda.current_stream().cuda_stream)
-    eng = HipBandEngine(c, torch)
-    eng.set_held_suarez(geom)
-    eng.set_climate(1)
-    runner = BandRunner(eng, 0, 2, LoopbackExchange(), north=0, south=0)
+    geom = su.geom_of(H, W, L)
+    c, eng, runner = su.loopback_band(g, torch, geom, dtype=dtype, hs={}, every=1)
     assert runner.native
-    c.set_state(*state_of(geom, dtype))
+    c.set_state(*inp.state_of(geom, dtype))
     runner.run(3, DT)
     runner.run(1, DT)
     torch.cuda.synchronize()
@@ -344,8 +278,8 @@ def three_phase_reference(g, dtype):
     """the single domain with physics, Held-Suarez and every = 2 after step(4): (sums, state, ground, utc), once per type"""
     if dtype not in _three_phase_cache:
         H, W, L = BAND_SHAPE
-        geom = geom_of(H, W, L)
-        c = single(g, geom, state_of(geom, dtype), dtype, gt=ground_of(H, W), phys=True, hs=True, every=2)
+        geom = su.geom_of(H, W, L)
+        c = su.single(g, geom, inp.state_of(geom, dtype), dtype=dtype, gt=inp.ground(H, W), phys=True, hs={}, every=2)
         c.step(4, DT)
         sums, state, gt, utc = c.climate_sums(), c.get_state(), c.get_ground(), c.utc()
         c.close()
@@ -364,25 +298,17 @@ def test_loopback_band_run_with_all_three_phases(dtype, comm_stream, monkeypatch
     domain's after step(4), bit for bit"""
     import torch
     import gcmiipy_amd as g
-    from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange
     H, W, L = BAND_SHAPE
     want, want_state, want_gt, want_utc = three_phase_reference(g, dtype)
     assert want[0] == 2 and want_utc == UTC0 + 4 * DT
-    geom = geom_of(H, W, L)
+    geom = su.geom_of(H, W, L)
     if comm_stream:
         monkeypatch.setenv("GCM_BAND_COMM_STREAM", "1")
     else:
         monkeypatch.delenv("GCM_BAND_COMM_STREAM", raising=False)
-    c = g.Core(g._lib.PE25D, W, H, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0, dtype=dtype,
-               stream=torch.cuda.current_stream().cuda_stream)
-    eng = HipBandEngine(c, torch)
-    c.set_ground(ground_of(H, W))
-    eng.set_physics(geom, UTC0)
-    eng.set_held_suarez(geom)
-    eng.set_climate(2)
-    runner = BandRunner(eng, 0, 2, LoopbackExchange(), north=0, south=0)
+    c, eng, runner = su.loopback_band(g, torch, geom, dtype=dtype, gt=inp.ground(H, W), phys=True, hs={}, every=2)
     assert runner.native
-    c.set_state(*state_of(geom, dtype))
+    c.set_state(*inp.state_of(geom, dtype))
     runner.run(3, DT)
     runner.run(1, DT)
     torch.cuda.synchronize()
@@ -429,9 +355,9 @@ def test_reset_put_get_and_checkpoint(dtype, tmp_path):
     import gcmiipy_amd as g
     from gcmiipy_amd import checkpoint
     H, W, L = BAND_SHAPE
-    geom = geom_of(H, W, L)
-    st = state_of(geom, dtype)
-    whole = single(g, geom, st, dtype, hs=True, every=1)
+    geom = su.geom_of(H, W, L)
+    st = inp.state_of(geom, dtype)
+    whole = su.single(g, geom, st, dtype=dtype, hs={}, every=1)
     whole.step(5, DT)
     want = whole.climate_sums()
     assert want[0] == 5
@@ -447,13 +373,13 @@ def test_reset_put_get_and_checkpoint(dtype, tmp_path):
     assert n == 0 and not m3.any() and whole.climate_every == 3
     whole.close()
     # put then get; put then more steps equals the uninterrupted run
-    a = single(g, geom, st, dtype, hs=True, every=1)
+    a = su.single(g, geom, st, dtype=dtype, hs={}, every=1)
     a.step(3, DT)
     mid, mid_state = a.climate_sums(), a.get_state()
     path = str(tmp_path / "clim.npz")
     checkpoint.save(path, a, step=3, geom=geom)
     a.close()
-    b = single(g, geom, mid_state, dtype, hs=True, every=1)
+    b = su.single(g, geom, mid_state, dtype=dtype, hs={}, every=1)
     b.put_climate(*mid)
     assert_sums_equal(b.climate_sums(), mid, "put then get")
     b.step(2, DT)
@@ -467,7 +393,7 @@ def test_reset_put_get_and_checkpoint(dtype, tmp_path):
     assert_sums_equal(r.climate_sums(), want, "restored then steps")
     r.close()
     # a file without the keys restores without a climatology
-    plain = single(g, geom, st, dtype)
+    plain = su.single(g, geom, st, dtype=dtype)
     checkpoint.save(path, plain, geom=geom)
     plain.close()
     r, ck = checkpoint.restore(path)
@@ -480,9 +406,9 @@ def test_refusals_change_nothing():
     import gcmiipy_amd as g
     lib, L_ = g._lib.lib, g._lib
     H, W, L = SHAPES[0]
-    geom = geom_of(H, W, L)
-    st = state_of(geom)
-    c = single(g, geom, st)
+    geom = su.geom_of(H, W, L)
+    st = inp.state_of(geom)
+    c = su.single(g, geom, st)
     m3, m2, n = np.zeros((10, L, H)), np.zeros((2, H)), C.c_int64(7)
     dp = L_._dp
     # without a registration
@@ -515,7 +441,7 @@ def test_refusals_change_nothing():
     with pytest.raises(g.GcmError):
         c.climate()
     c.step(1, DT)
-    u = single(g, geom, st)
+    u = su.single(g, geom, st)
     u.step(3, DT)
     for k, x, y in zip("puvtq", c.get_state(), u.get_state()):
         assert np.array_equal(x, y), k

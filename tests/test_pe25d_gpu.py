@@ -5,16 +5,12 @@ import numpy as np
 import pytest
 
 from conftest import golden, rel_err
+import gpu_setups as su
+import pe25d_inputs as inp
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
 
 
 def _check(got, want, what, tol=TOL):
@@ -125,19 +121,11 @@ def test_shapes_vs_oracle(g, hwl):
     256 = 16.16 (the kMask1440 / kMask4096 kernels in two passes), 4608 (a {2,3}-smooth width the
     generic path serves: a pass of 1152 butterflies), 202 = 2.101 (the generic radix-r butterfly)"""
     from gcmiipy_amd import geometry
-    from oracle import dynamics as odyn, geometry as ogeo, temperature as otemp
+    from oracle import dynamics as odyn, geometry as ogeo
     H, W, L = hwl
-    rng = np.random.default_rng(H * 100 + W)
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
     og = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u = rng.standard_normal((L, H, W))
-    v = rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    tt = 300 + rng.standard_normal((L, H, W))
-    t = otemp.to_potential_temp(tt, p * og.sig + og.ptop)
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
-    want = (p, u, v, t, q)
+    p, u, v, t, q = want = inp.state(og, H * 100 + W)
     for _ in range(2):
         want = odyn.matsuno_timestep(*want, 60.0, og)
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom)
@@ -333,13 +321,8 @@ def test_level_segments_do_not_change_results(g, hwl, monkeypatch):
     to the unsplit march on the same pit"""
     from gcmiipy_amd import geometry
     H, W, L = hwl
-    rng = np.random.default_rng(11)
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u, v = rng.standard_normal((L, H, W)), rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    t = (300 + rng.standard_normal((L, H, W))) * ((1e5 / (p * geom.sig + geom.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
+    p, u, v, t, q = inp.state(geom, 11)
     res = {}
     monkeypatch.setenv("GCM_PE_PIT2D", "0")
     for nseg in (1, 2, 3, 4):
@@ -364,13 +347,8 @@ def test_pit_from_column_sums_vs_3d_form(g, hwl, monkeypatch):
     from gcmiipy_amd import geometry
     from oracle import dynamics as od, geometry as ogeo
     H, W, L = hwl
-    rng = np.random.default_rng(12)
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u, v = rng.standard_normal((L, H, W)), rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    t = (300 + rng.standard_normal((L, H, W))) * ((1e5 / (p * geom.sig + geom.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
+    p, u, v, t, q = inp.state(geom, 12)
     res = {}
     for flag in ("1", "0"):
         monkeypatch.setenv("GCM_PE_PIT2D", flag)
@@ -399,13 +377,7 @@ def test_full_size_properties_c4(g):
     from gcmiipy_amd import geometry
     H, W, L = 720, 1440, 24
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    rng = np.random.default_rng(0)
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u = rng.standard_normal((L, H, W))
-    v = rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    t = (300 + rng.standard_normal((L, H, W))) * ((1e5 / (p * geom.sig + geom.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
+    p, u, v, t, q = inp.state(geom, 0)
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom)
     c.set_state(p, u, v, t, q)
     c.step(3, 1.0)
@@ -450,40 +422,19 @@ def test_fp32_tolerance_sweep(g):
 
 def test_fp32_bands_in_process(g):
     import torch
-    from gcmiipy_amd import geometry
-    from gcmiipy_amd.bands import split_rows
     H, W, L, steps, nb = 14, 20, 5, 2, 2
-    geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    rng = np.random.default_rng(3)
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u, v = rng.standard_normal((L, H, W)), rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    t = (300 + rng.standard_normal((L, H, W))) * ((1e5 / (p * geom.sig + geom.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
-    ref = g.Core(g._lib.PE25D, W, H, L, geom=geom, dtype="f32")
-    ref.set_state(p, u, v, t, q)
+    geom = su.geom_of(H, W, L)
+    st = inp.state(geom, 3)
+    ref = su.single(g, geom, st, dtype="f32")
     ref.step(steps, 120.0)
     want = ref.get_state()
     ref.close()
-    cores = []
-    for r, (row0, n) in enumerate(split_rows(H, nb)):
-        c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=nb, rank=r, global_height=H, row0=row0, dtype="f32")
-        sl = slice(row0, row0 + n)
-        c.set_state(p[sl], u[:, sl], v[:, sl], t[:, sl], q[:, sl])
-        cores.append(c)
-    def exchange():
-        bufs = [[torch.empty(c.halo_bytes(), dtype=torch.uint8, device="cuda") for _ in (0, 1)] for c in cores]
-        for r, c in enumerate(cores):
-            c.halo_pack(0, bufs[r][0].data_ptr()); c.halo_pack(1, bufs[r][1].data_ptr())
-        torch.cuda.synchronize()
-        for r, c in enumerate(cores):
-            c.halo_unpack(1, bufs[(r + 1) % nb][0].data_ptr()); c.halo_unpack(0, bufs[(r - 1) % nb][1].data_ptr())
-        torch.cuda.synchronize()
+    cores = su.bands(g, geom, nb, st, dtype="f32")
     for _ in range(steps):
-        exchange()
+        su.exchange(cores, torch)
         for c in cores:
             c.step_interior(120.0)
-        exchange()
+        su.exchange(cores, torch)
         for c in cores:
             c.step_boundary(120.0)
     parts = [c.get_state() for c in cores]
@@ -535,12 +486,7 @@ def test_hot_path_intermediates_vs_oracle_1440_columns(g):
     geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
     og = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
     geom.heightmap[...] = og.heightmap[...] = 30 * rng.random((H, W))
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u, v = rng.standard_normal((L, H, W)), rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    t = (300 + rng.standard_normal((L, H, W))) * ((1e5 / (p * og.sig + og.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
-    base, dt = (p, u, v, t, q), 30.0
+    base, dt = inp.state(og, rng), 30.0
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom)
     c.set_state(*base)
     stage_state = base

@@ -7,22 +7,21 @@ routine's own table, rounded once: bit for bit.  theta goes through the device's
 import numpy as np
 import pytest
 
-import band_van_leer_inputs as inp
+import gpu_setups as su
 import pe25d_held_suarez_ref as ref
+import pe25d_inputs as inp
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = ((24, 36, 9), (6, 10, 3))                       # (H, W, L) of the tracer tests
 PTOP = 1000.0
-UTC0 = 5 * 3600.0
+UTC0 = inp.UTC0
 DT = 120.0
 ORCH_ENV = ("GCM_PE_SINGLE_STREAM", "GCM_BAND_COMM_STREAM", "GCM_BAND_OVERLAP", "GCM_PE_STOP_EVENTS", "GCM_PE_K1_SPLIT")
 
 
 def geom_of(H, W, L, ptop=0.0):
-    from gcmiipy_amd import geometry
-    geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    geom.ptop = ptop
+    geom = su.geom_of(H, W, L, ptop)
     r = ref.r_of(geom.sig, ref.DEFAULTS["sigma_b"])
     assert (r > 0).any() and (r == 0).any(), "the geometry needs a friction level and a free level"
     return geom
@@ -30,34 +29,6 @@ def geom_of(H, W, L, ptop=0.0):
 
 def sig_lat(geom):
     return np.asarray(geom.sig, dtype=np.float64).reshape(-1), np.asarray(geom.lat, dtype=np.float64).reshape(-1)
-
-
-def state_of(geom, dtype="f64", wind=8.0):
-    """the band tests' seeded state with winds of several m/s; f32: rounded to float32 (what the handle holds)"""
-    H, W, L = geom.height, geom.width, geom.layers
-    p, u, v, t, q = inp.state(H, W, L, np.asarray(geom.sig), geom.ptop)
-    p = p - geom.ptop
-    t = t * (1.0 + 0.05 * np.sin(np.arange(H) * 0.7)[None, :, None])
-    st = [p, wind * u, wind * v, t, q]
-    if dtype == "f32":
-        st = [a.astype(np.float32).astype(np.float64) for a in st]
-    return st
-
-
-def ground_of(H, W):
-    return 288.0 + np.random.default_rng(13).standard_normal((H, W))
-
-
-def single(g, geom, st, dtype="f64", gt=None, phys=False, hs=None):
-    c = g.Core(g._lib.PE25D, geom.width, geom.height, geom.layers, geom=geom, dtype=dtype)
-    c.set_state(*st)
-    if gt is not None:
-        c.set_ground(gt)
-    if phys:
-        c.set_physics(geom, UTC0)
-    if hs is not None:
-        c.set_held_suarez(geom, **hs)
-    return c
 
 
 def final(c, close=True):
@@ -82,11 +53,11 @@ def test_step_equals_the_restatement(shape, ptop, dtype):
     H, W, L = shape
     geom = geom_of(H, W, L, ptop)
     sig, lat = sig_lat(geom)
-    st = state_of(geom, dtype)
+    st = inp.state_of(geom, dtype)
     trs = inp.tracers(H, W, L, 2)
-    gt = ground_of(H, W)
+    gt = inp.ground(H, W)
     for over in ({}, dict(sigma_b=0.45, k_f=4e-5, T_min=240.0)):
-        c = single(g, geom, st, dtype, gt=gt)
+        c = su.single(g, geom, st, dtype=dtype, gt=gt)
         c.set_tracers(trs)
         trs0 = c.get_tracers()
         c.held_suarez_step(geom, DT, **over)
@@ -115,24 +86,24 @@ def test_registered_equals_explicit(dtype, phys):
     import gcmiipy_amd as g
     H, W, L = SHAPES[0]
     geom = geom_of(H, W, L)
-    st, gt = state_of(geom, dtype), ground_of(H, W)
-    a = single(g, geom, st, dtype, gt=gt)
+    st, gt = inp.state_of(geom, dtype), inp.ground(H, W)
+    a = su.single(g, geom, st, dtype=dtype, gt=gt)
     for n in range(5):
         a.step(1, DT)
         if phys:
             a.solar_step(geom, DT, UTC0 + n * DT)
         a.held_suarez_step(geom, DT)
     want = final(a)
-    b = single(g, geom, st, dtype, gt=gt, phys=phys, hs={})
+    b = su.single(g, geom, st, dtype=dtype, gt=gt, phys=phys, hs={})
     assert b.held_suarez == ref.DEFAULTS
     b.step(5, DT)
     assert_same(final(b, close=False), want, "registered")
     # the forcing is not the identity, and the other order of the phases gives other bits
-    plain = single(g, geom, st, dtype, gt=gt, phys=phys)
+    plain = su.single(g, geom, st, dtype=dtype, gt=gt, phys=phys)
     plain.step(5, DT)
     assert not np.array_equal(final(plain)[1], want[1])
     if phys:
-        o = single(g, geom, st, dtype, gt=gt)
+        o = su.single(g, geom, st, dtype=dtype, gt=gt)
         for n in range(5):
             o.step(1, DT)
             o.held_suarez_step(geom, DT)
@@ -142,7 +113,7 @@ def test_registered_equals_explicit(dtype, phys):
     b.set_held_suarez(None)
     assert b.held_suarez is None
     b.step(2, DT)
-    u = single(g, geom, want[:5], dtype, gt=want[5])
+    u = su.single(g, geom, want[:5], dtype=dtype, gt=want[5])
     if phys:
         u.set_physics(geom, UTC0 + 5 * DT)
     u.step(2, DT)
@@ -154,8 +125,8 @@ def test_half_step_is_never_forced(dtype):
     import gcmiipy_amd as g
     H, W, L = SHAPES[0]
     geom = geom_of(H, W, L)
-    st = state_of(geom, dtype)
-    r, u = single(g, geom, st, dtype, hs={}), single(g, geom, st, dtype)
+    st = inp.state_of(geom, dtype)
+    r, u = su.single(g, geom, st, dtype=dtype, hs={}), su.single(g, geom, st, dtype=dtype)
     for c in (r, u):
         c.half_step(0, DT)
     star_r, star_u = r.get_star(), u.get_star()
@@ -171,12 +142,12 @@ def test_tables_follow_a_change_of_dt(dtype):
     import gcmiipy_amd as g
     H, W, L = SHAPES[1]
     geom = geom_of(H, W, L)
-    st = state_of(geom, dtype)
-    a = single(g, geom, st, dtype)
+    st = inp.state_of(geom, dtype)
+    a = su.single(g, geom, st, dtype=dtype)
     for dt in (DT, DT, 45.0, 45.0, DT):
         a.step(1, dt)
         a.held_suarez_step(geom, dt)
-    b = single(g, geom, st, dtype, hs={})
+    b = su.single(g, geom, st, dtype=dtype, hs={})
     b.step(2, DT)
     b.step(2, 45.0)
     b.step(1, DT)
@@ -187,8 +158,8 @@ def test_refused_calls_change_nothing():
     import gcmiipy_amd as g
     H, W, L = SHAPES[1]
     geom = geom_of(H, W, L)
-    st = state_of(geom)
-    c = single(g, geom, st, hs=dict(k_f=2e-5))
+    st = inp.state_of(geom)
+    c = su.single(g, geom, st, hs=dict(k_f=2e-5))
     was = c.held_suarez
     nan = float("nan")
     for over in (dict(k_f=-1.0), dict(k_a=-1.0), dict(k_s=-1.0), dict(sigma_b=1.0), dict(sigma_b=-0.1), dict(T_0=nan),
@@ -207,7 +178,7 @@ def test_refused_calls_change_nothing():
     assert g._lib.lib.gcm_set_held_suarez(c._h, rec) == g._lib.ERR_ARG and g._lib.lib.gcm_held_suarez_on(c._h) == 0
     c.set_held_suarez(geom, k_f=2e-5)
     c.step(2, DT)
-    w = single(g, geom, st, hs=dict(k_f=2e-5))
+    w = su.single(g, geom, st, hs=dict(k_f=2e-5))
     w.step(2, DT)
     assert_same(final(c), final(w), "after refused calls")
     # other models
@@ -221,20 +192,6 @@ def test_refused_calls_change_nothing():
 
 
 # ---------------------------------------------------------------- 3: bands equal the single domain
-def _exchange(cores, torch):
-    """ring exchange by device copies on the default stream: side s of a band lands in the neighbour's opposite ghost"""
-    n = len(cores)
-    bufs = [[torch.empty(c.halo_bytes(), dtype=torch.uint8, device="cuda") for _ in (0, 1)] for c in cores]
-    for r, c in enumerate(cores):
-        c.halo_pack(0, bufs[r][0].data_ptr())
-        c.halo_pack(1, bufs[r][1].data_ptr())
-    torch.cuda.synchronize()
-    for r, c in enumerate(cores):
-        c.halo_unpack(1, bufs[(r + 1) % n][0].data_ptr())
-        c.halo_unpack(0, bufs[(r - 1) % n][1].data_ptr())
-    torch.cuda.synchronize()
-
-
 _single_cache = {}
 
 
@@ -243,7 +200,8 @@ def _single_reference(g, shape, dtype, phys, steps):
     key = (shape, dtype, phys, steps)
     if key not in _single_cache:
         geom = geom_of(*shape)
-        c = single(g, geom, state_of(geom, dtype), dtype, gt=ground_of(shape[0], shape[1]), phys=phys, hs={})
+        c = su.single(g, geom, inp.state_of(geom, dtype), dtype=dtype, gt=inp.ground(shape[0], shape[1]), phys=phys,
+                      hs={})
         c.step(steps[0], DT)
         first = final(c, close=False)
         c.step(steps[1], DT)
@@ -262,33 +220,20 @@ def test_in_process_bands_equal_single_domain(shape, nb, dtype, phys):
     own rows and ghost rows: the ghost rows are forced locally, no third exchange"""
     import torch
     import gcmiipy_amd as g
-    from gcmiipy_amd.bands import split_rows
     H, W, L = shape
     steps = (3, 2)
     want = _single_reference(g, shape, dtype, phys, steps)
     geom = geom_of(H, W, L)
-    st, gt = state_of(geom, dtype), ground_of(H, W)
-    cores = []
-    for r, (row0, n) in enumerate(split_rows(H, nb)):
-        c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=nb, rank=r, global_height=H, row0=row0, dtype=dtype)
-        sl = slice(row0, row0 + n)
-        c.set_state(*[inp.rows(a, sl) for a in st])
-        c.set_ground(gt[sl])
-        cores.append(c)
-    _exchange(cores, torch)
+    cores = su.bands(g, geom, nb, inp.state_of(geom, dtype), dtype=dtype, gt=inp.ground(H, W))
     done = 0
+
+    def physics(k):
+        for c in cores:
+            if phys:
+                c.solar_step(geom, DT, UTC0 + (done + k) * DT)
+            c.held_suarez_step(geom, DT)
     for part, n in enumerate(steps):
-        for k in range(n):
-            for c in cores:
-                c.step_interior(DT)
-            _exchange(cores, torch)
-            for c in cores:
-                c.step_boundary(DT)
-            _exchange(cores, torch)
-            for c in cores:
-                if phys:
-                    c.solar_step(geom, DT, UTC0 + (done + k) * DT)
-                c.held_suarez_step(geom, DT)
+        su.whole_steps(cores, torch, n, DT, prime=part == 0, after=physics)
         done += n
         parts = [c.get_state() + [c.get_ground()] for c in cores]
         got = [np.concatenate([x[f] for x in parts], axis=0 if f in (0, 5) else 1) for f in range(6)]
@@ -304,21 +249,14 @@ def test_loopback_band_run_equals_single_domain(shape, dtype, phys):
     """gcm_band_run with the forcing registered: several steps in one run, then a second run after a get_state"""
     import torch
     import gcmiipy_amd as g
-    from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange
     H, W, L = shape
     steps = (3, 2)
     want = _single_reference(g, shape, dtype, phys, steps)
     geom = geom_of(H, W, L)
-    c = g.Core(g._lib.PE25D, W, H, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0, dtype=dtype,
-               stream=torch.cuda.current_stream().cuda_stream)
-    eng = HipBandEngine(c, torch)
-    if phys:
-        eng.set_physics(geom, UTC0)
-    eng.set_held_suarez(geom)
-    runner = BandRunner(eng, 0, 2, LoopbackExchange(), north=0, south=0)
+    c, eng, runner = su.loopback_band(g, torch, geom, dtype=dtype, phys=phys, hs={})
     assert runner.native
-    c.set_state(*state_of(geom, dtype))
-    c.set_ground(ground_of(H, W))
+    c.set_state(*inp.state_of(geom, dtype))
+    c.set_ground(inp.ground(H, W))
     for part, n in enumerate(steps):
         runner.run(n, DT)
         torch.cuda.synchronize()
@@ -336,22 +274,21 @@ def test_band_run_chains_with_the_forcing(dtype, phys, monkeypatch):
     steps, and the single domain's step(4) equals four rounds of step(1) + sync()"""
     import torch
     import gcmiipy_amd as g
-    from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange
     H, W, L, dt, steps = 48, 1440, 24, 1.0, 4
     hs = dict(k_f=0.05, k_a=0.01, k_s=0.04)                # (a forcing that moves every bit in a step of one second)
     geom = geom_of(H, W, L)
-    st, gt = state_of(geom, dtype), ground_of(H, W)
+    st, gt = inp.state_of(geom, dtype), inp.ground(H, W)
     for k in ORCH_ENV:
         monkeypatch.delenv(k, raising=False)
-    ref_c = single(g, geom, st, dtype, gt=gt, phys=phys, hs=hs)
+    ref_c = su.single(g, geom, st, dtype=dtype, gt=gt, phys=phys, hs=hs)
     ref_c.step(steps, dt)
     want = final(ref_c)
-    one = single(g, geom, st, dtype, gt=gt, phys=phys, hs=hs)
+    one = su.single(g, geom, st, dtype=dtype, gt=gt, phys=phys, hs=hs)
     for _ in range(steps):
         one.step(1, dt)
         one.sync()
     assert_same(final(one), want, "step(1) + sync")
-    plain = single(g, geom, st, dtype, gt=gt, phys=phys)
+    plain = su.single(g, geom, st, dtype=dtype, gt=gt, phys=phys)
     plain.step(steps, dt)
     assert not np.array_equal(final(plain)[1], want[1])
     for env in ({}, {"GCM_PE_SINGLE_STREAM": "1"}, {"GCM_BAND_COMM_STREAM": "1"}, {"GCM_BAND_OVERLAP": "1"},
@@ -362,13 +299,7 @@ def test_band_run_chains_with_the_forcing(dtype, phys, monkeypatch):
         for k, v in env.items():
             if k in ORCH_ENV:
                 monkeypatch.setenv(k, v)
-        c = g.Core(g._lib.PE25D, W, H, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0, dtype=dtype,
-                   stream=torch.cuda.current_stream().cuda_stream)
-        eng = HipBandEngine(c, torch)
-        if phys:
-            eng.set_physics(geom, UTC0)
-        eng.set_held_suarez(geom, **hs)
-        runner = BandRunner(eng, 0, 2, LoopbackExchange(), north=0, south=0)
+        c, eng, runner = su.loopback_band(g, torch, geom, dtype=dtype, phys=phys, hs=hs)
         assert runner.native
         if "overlap_call" in env:
             c.set_band_overlap(1)
@@ -385,8 +316,8 @@ def test_physical_properties():
     H, W, L = SHAPES[0]
     geom = geom_of(H, W, L)
     sig, lat = sig_lat(geom)
-    st = state_of(geom)
-    c = single(g, geom, st)
+    st = inp.state_of(geom)
+    c = su.single(g, geom, st)
     ke0 = c.energy(np.ones(1))[0]
     c.held_suarez_step(geom, 3600.0)
     ke1 = c.energy(np.ones(1))[0]
@@ -407,7 +338,7 @@ def test_long_run_stays_finite():
     import gcmiipy_amd as g
     H, W, L = SHAPES[0]
     geom = geom_of(H, W, L)
-    c = single(g, geom, state_of(geom, wind=1.0), hs={})
+    c = su.single(g, geom, inp.state_of(geom, wind=1.0), hs={})
     c.step(200, DT)
     s = c.stats(np.ones(1))
     c.close()
@@ -421,12 +352,12 @@ def test_checkpoint_carries_the_forcing(dtype, tmp_path):
     from gcmiipy_amd import checkpoint
     H, W, L = SHAPES[0]
     geom = geom_of(H, W, L)
-    st = state_of(geom, dtype)
+    st = inp.state_of(geom, dtype)
     hs = dict(k_f=3e-5, sigma_b=0.6)
-    whole = single(g, geom, st, dtype, hs=hs)
+    whole = su.single(g, geom, st, dtype=dtype, hs=hs)
     whole.step(5, DT)
     want = final(whole)
-    a = single(g, geom, st, dtype, hs=hs)
+    a = su.single(g, geom, st, dtype=dtype, hs=hs)
     a.step(3, DT)
     path = str(tmp_path / "hs.npz")
     checkpoint.save(path, a, step=3, geom=geom)
@@ -436,7 +367,7 @@ def test_checkpoint_carries_the_forcing(dtype, tmp_path):
     b.step(2, DT)
     assert_same(final(b), want, "restored")
     # a file without the key restores with none
-    plain = single(g, geom, st, dtype)
+    plain = su.single(g, geom, st, dtype=dtype)
     checkpoint.save(path, plain, geom=geom)
     plain.close()
     c, ck = checkpoint.restore(path)

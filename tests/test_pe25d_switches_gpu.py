@@ -7,7 +7,9 @@ per handle, when it is created: every case sets its variable before it builds it
 import numpy as np
 import pytest
 
-from test_pe25d_variants_gpu import TOL, _check, _geoms, _oracle, _run, _state
+import gpu_setups as su
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
+from test_pe25d_variants_gpu import TOL, _check, _oracle, _run, _state
 
 pytestmark = pytest.mark.gpu
 SWITCHES = ("GCM_PE_UPDATE_ROWS", "GCM_PE_K4_ODDTOP", "GCM_PE_FILTER_NO_LOOP", "GCM_PE_EDGE_SEGMENTS")
@@ -26,13 +28,6 @@ CASES = [(hwl, name) for hwl in SHAPES for name in SETTINGS] + [((9, 120, 24), "
 SAME_BITS_AS_DEFAULT = {"rows3"}
 
 
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
-
-
 _single = {}
 
 
@@ -41,7 +36,7 @@ def _single_domain(g, hwl):
     switch set"""
     if hwl not in _single:
         H, W, L = hwl
-        geom, og = _geoms(H, W, L)
+        geom, og = su.geoms_of(H, W, L)
         st = _state(H, W, L, og, 7 * W + L)
         want = _oracle(st, NSTEPS, DT, og)
         got = _run(g, geom, st, NSTEPS, DT)
@@ -85,7 +80,7 @@ def test_edge_segments_band_equals_single_domain(g, edge_segments, monkeypatch):
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
     if not _band_ref:
-        geom, og = _geoms(H, W, L)
+        geom, og = su.geoms_of(H, W, L)
         st = _state(H, W, L, og, 12)
         _band_ref["x"] = (geom, st, _run(g, geom, st, nsteps, DT))
     geom, st, want = _band_ref["x"]

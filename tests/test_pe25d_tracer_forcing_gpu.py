@@ -6,7 +6,9 @@ replaces, and -- on latitude bands, under every orchestration -- with the forced
 import numpy as np
 import pytest
 
-import pe25d_tracer_forcing_setups as su
+import gpu_setups as su
+import pe25d_inputs as inp
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 from pe25d_tracer_forcing_ref import force, records
 
 pytestmark = pytest.mark.gpu
@@ -14,21 +16,10 @@ SCHEMES = ["centred", "upwind", "van_leer"]
 NTR = 4
 
 
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
-
-
 def _setup(H, W, L):
     geom = su.geom_of(H, W, L)
     st, trs = su.initial(geom, NTR)
     return geom, st, trs, records(L, H, W, int(np.argmax(np.asarray(geom.sig))))
-
-
-def _core(g, geom, st, trs, recs=None, dtype="f64", scheme="van_leer"):
-    return su.single(g, geom, st, trs, recs, dtype, scheme)
 
 
 def _force_all(tr, dt, recs, dtype):
@@ -57,8 +48,8 @@ def test_one_step_bit_for_bit(g, shape, dtype, scheme):
     H, W, L = shape
     dt = 120.0
     geom, st, trs, recs = _setup(H, W, L)
-    a = _core(g, geom, st, trs, None, dtype, scheme)
-    b = _core(g, geom, st, trs, recs, dtype, scheme)
+    a = su.single(g, geom, st, trs, dtype=dtype, scheme=scheme)
+    b = su.single(g, geom, st, trs, recs=recs, dtype=dtype, scheme=scheme)
     assert [b.tracer_forcing(i) is not None for i in range(NTR)] == [False, True, True, True]
     assert np.array_equal(b.get_tracers(), a.get_tracers())       # registering applies nothing
     a.step(1, dt)
@@ -74,8 +65,8 @@ def test_one_step_bit_for_bit(g, shape, dtype, scheme):
     _equal_state(b.get_state(), a.get_state(), (shape, dtype, scheme))
     # the two stages by hand (the predictor's tracers can be read between them only): the predictor forces nothing
     # -- the star tracers are the unforced handle's, the current ones untouched -- and the corrector does
-    c = _core(g, geom, st, trs, recs, dtype, scheme)
-    d = _core(g, geom, st, trs, None, dtype, scheme)
+    c = su.single(g, geom, st, trs, recs=recs, dtype=dtype, scheme=scheme)
+    d = su.single(g, geom, st, trs, dtype=dtype, scheme=scheme)
     t0 = c.get_tracers()
     c.half_step(0, dt)
     d.half_step(0, dt)
@@ -95,8 +86,8 @@ def test_five_steps_in_one_call_equal_the_round_trips(g, dtype):
     replaces.  Then both go on with another dt: fac follows it"""
     H, W, L = 24, 36, 9
     geom, st, trs, recs = _setup(H, W, L)
-    a = _core(g, geom, st, trs, None, dtype)
-    b = _core(g, geom, st, trs, recs, dtype)
+    a = su.single(g, geom, st, trs, dtype=dtype, scheme="van_leer")
+    b = su.single(g, geom, st, trs, recs=recs, dtype=dtype, scheme="van_leer")
 
     def rounds(n, dt):
         for _ in range(n):
@@ -120,24 +111,12 @@ def test_five_steps_in_one_call_equal_the_round_trips(g, dtype):
 
 # ---------------------------------------------------------------- 3. bands
 def _forced_single(g, geom, st, trs, recs, steps, dt, dtype="f64", runs=None):
-    one = _core(g, geom, st, trs, recs, dtype)
+    one = su.single(g, geom, st, trs, recs=recs, dtype=dtype, scheme="van_leer")
     for n in (runs or [steps]):
         one.step(n, dt)
     out = one.get_state(), one.get_tracers()
     one.close()
     return out
-
-
-def _forced_bands(g, geom, nb, st, trs, recs, dtype="f64"):
-    cores = su.bands(g, geom, nb, st, trs, recs, dtype)
-    for c in cores:
-        esz = 8 if dtype == "f64" else 4
-        assert c.halo_bytes() == su.inp.halo_bytes(geom.width, geom.layers, esz, NTR, 2)
-    return cores
-
-
-def _phases(cores, torch, steps, dt):
-    su.phase_steps(cores, torch, steps, dt)
 
 
 @pytest.mark.parametrize("nb", [2, 3])
@@ -149,11 +128,11 @@ def test_host_driven_forced_bands_equal_single_domain(g, mode, nb):
     H, W, L, steps, dt = 16, 20, 5, 3, 120.0
     geom, st, trs, recs = _setup(H, W, L)
     want = _forced_single(g, geom, st, trs, recs, steps, dt)
-    cores = _forced_bands(g, geom, nb, st, trs, recs)
+    cores = su.bands(g, geom, nb, st, trs, recs=recs, scheme="van_leer", rows=2)
     if mode == "whole":
         su.whole_steps(cores, torch, steps, dt)
     else:
-        _phases(cores, torch, steps, dt)
+        su.phase_steps(cores, torch, steps, dt)
     su.assert_equal(su.gather(cores), want, (mode, nb))
 
 
@@ -163,9 +142,9 @@ def test_unsplittable_short_forced_bands_equal_single_domain(g):
     H, W, L, steps, dt = 14, 20, 5, 3, 120.0
     geom, st, trs, recs = _setup(H, W, L)
     want = _forced_single(g, geom, st, trs, recs, steps, dt)
-    cores = _forced_bands(g, geom, 4, st, trs, recs)
+    cores = su.bands(g, geom, 4, st, trs, recs=recs, scheme="van_leer", rows=2)
     assert sorted(c.H for c in cores) == [3, 3, 4, 4]
-    _phases(cores, torch, steps, dt)
+    su.phase_steps(cores, torch, steps, dt)
     su.assert_equal(su.gather(cores), want)
 
 
@@ -178,7 +157,7 @@ def test_forced_band_run_loopback_equals_single_domain(g, dtype, phys, overlap):
     import torch
     H, W, L, dt = 23, 36, 9, 120.0
     geom, st, trs, recs = _setup(H, W, L)
-    gt = su.ground(H, W)
+    gt = inp.ground(H, W)
 
     def drive(core, run, set_physics):
         if phys:
@@ -188,10 +167,10 @@ def test_forced_band_run_loopback_equals_single_domain(g, dtype, phys, overlap):
         run(2)
         return core.get_state(), core.get_tracers()
 
-    ref = _core(g, geom, st, trs, recs, dtype)
+    ref = su.single(g, geom, st, trs, recs=recs, dtype=dtype, scheme="van_leer")
     want = drive(ref, lambda n: ref.step(n, dt), lambda: ref.set_physics(geom, su.UTC0))
     ref.close()
-    c, eng, runner = su.loopback_band(g, torch, geom, NTR, dtype)
+    c, eng, runner = su.loopback_band(g, torch, geom, NTR, dtype, scheme="van_leer", rows=2)
     assert runner.native
     if overlap:
         c.set_band_overlap(True)
@@ -217,7 +196,7 @@ def test_forced_band_run_at_overlapping_size(g, dtype, monkeypatch):
     H, W, L, dt = 48, 1440, 24, 1.0
     geom, st, trs, recs = _setup(H, W, L)
     want = _forced_single(g, geom, st, trs, recs, 5, dt, dtype)
-    plain = _core(g, geom, st, trs, None, dtype)
+    plain = su.single(g, geom, st, trs, dtype=dtype, scheme="van_leer")
     plain.step(5, dt)
     assert not np.array_equal(want[1][1], plain.get_tracers()[1])
     plain.close()
@@ -227,7 +206,7 @@ def test_forced_band_run_at_overlapping_size(g, dtype, monkeypatch):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        c, eng, runner = su.loopback_band(g, torch, geom, NTR, dtype)
+        c, eng, runner = su.loopback_band(g, torch, geom, NTR, dtype, scheme="van_leer", rows=2)
         assert runner.native == ("GCM_BAND_HOST_LOOP" not in env)
         c.set_state(*st)
         c.set_tracers(trs)
@@ -273,8 +252,8 @@ def test_runs_off_a_16_byte_boundary(g, case):
     geom = su.geom_of(H, W, L)
     st, trs = su.initial(geom, NTR)
     recs = _full_records(L, H, W, int(np.argmax(np.asarray(geom.sig))))
-    one = su.single(g, geom, st, trs, recs, dtype, scheme, filter=filt)
-    ref = su.single(g, geom, st, trs, None, dtype, scheme, filter=filt)
+    one = su.single(g, geom, st, trs, recs=recs, dtype=dtype, scheme=scheme, filter=filt)
+    ref = su.single(g, geom, st, trs, dtype=dtype, scheme=scheme, filter=filt)
     for _ in range(steps):
         one.step(1, dt)
         ref.step(1, dt)
@@ -284,7 +263,7 @@ def test_runs_off_a_16_byte_boundary(g, case):
     one.close()
     ref.close()
     for mode in ("phase", "whole"):
-        cores = su.bands(g, geom, nb, st, trs, recs, dtype, scheme, rows=1, filter=filt)
+        cores = su.bands(g, geom, nb, st, trs, recs=recs, dtype=dtype, scheme=scheme, rows=1, filter=filt)
         if mode == "phase":
             su.phase_steps(cores, torch, steps, dt)
         else:
@@ -299,8 +278,8 @@ def test_mass_budget_of_a_uniform_source(g):
     the one rounding of the forced value per cell: 3 (N + 2) 2^-53 sum |c p dsig| over the N cells"""
     H, W, L, dt, S = 24, 36, 9, 120.0, 0.37
     geom, st, trs, _ = _setup(H, W, L)
-    a = _core(g, geom, st, trs)
-    b = _core(g, geom, st, trs, {i: dict(source=S) for i in range(NTR)})
+    a = su.single(g, geom, st, trs, scheme="van_leer")
+    b = su.single(g, geom, st, trs, recs={i: dict(source=S) for i in range(NTR)}, scheme="van_leer")
     a.step(1, dt)
     b.step(1, dt)
     sa, sb = a.tracer_stats(), b.tracer_stats()
@@ -325,7 +304,7 @@ def test_life_cycle_and_refusals(g):
     lib = _lib.lib
     H, W, L, dt = 12, 20, 5, 120.0
     geom, st, trs, recs = _setup(H, W, L)
-    c = _core(g, geom, st, trs, {1: recs[1]})
+    c = su.single(g, geom, st, trs, recs={1: recs[1]}, scheme="van_leer")
     rec = lambda **kw: C.byref(_lib.TracerForcing(kw.get("source", 0.0), kw.get("decay", 0.0), kw.get("pin_value", 0.0), None, None))
     assert [lib.gcm_tracer_forced(c._h, i) for i in range(NTR)] == [0, 1, 0, 0]
     for i in (-1, NTR, 99):
@@ -343,7 +322,7 @@ def test_life_cycle_and_refusals(g):
             c.set_tracer_forcing(1, **bad)
     assert [lib.gcm_tracer_forced(c._h, i) for i in range(NTR)] == [0, 1, 0, 0]
     assert c.tracer_forcing(1)["source"] == recs[1]["source"] and c.tracer_forcing(2) is None
-    ref = _core(g, geom, st, trs, {1: recs[1]})
+    ref = su.single(g, geom, st, trs, recs={1: recs[1]}, scheme="van_leer")
     ref.step(1, dt)
     c.step(1, dt)
     assert np.array_equal(c.get_tracers(), ref.get_tracers())     # tracer 1 is forced as registered, nothing else is
@@ -362,7 +341,7 @@ def test_life_cycle_and_refusals(g):
     c.set_tracer_forcing(2, **recs[2])
     c.clear_tracer_forcing()
     assert [lib.gcm_tracer_forced(c._h, i) for i in range(NTR)] == [0] * NTR and c.tracer_forcings() == {}
-    plain = _core(g, geom, st, trs)
+    plain = su.single(g, geom, st, trs, scheme="van_leer")
     plain.step(1, dt)
     c.set_tracers(trs)
     c.set_state(*st)
@@ -408,7 +387,7 @@ def test_checkpoint_single_domain(g, tmp_path):
     H, W, L, dt = 16, 20, 5, 120.0
     geom, st, trs, recs = _setup(H, W, L)
     want = _forced_single(g, geom, st, trs, recs, 4, dt, runs=[2, 2])
-    c = _core(g, geom, st, trs, recs)
+    c = su.single(g, geom, st, trs, recs=recs, scheme="van_leer")
     c.step(2, dt)
     path = str(tmp_path / "forced.npz")
     checkpoint.save(path, c, step=2, geom=geom)
@@ -424,7 +403,7 @@ def test_checkpoint_single_domain(g, tmp_path):
     c.step(2, dt)
     su.assert_equal((c.get_state(), c.get_tracers()), want)
     c.close()
-    plain = _core(g, geom, st, trs)
+    plain = su.single(g, geom, st, trs, scheme="van_leer")
     path = str(tmp_path / "plain.npz")
     checkpoint.save(path, plain, geom=geom)
     plain.close()
@@ -441,7 +420,7 @@ def test_checkpoint_bands(g, tmp_path):
     H, W, L, dt = 16, 20, 5, 120.0
     geom, st, trs, recs = _setup(H, W, L)
     want = _forced_single(g, geom, st, trs, recs, 4, dt)
-    cores = _forced_bands(g, geom, 2, st, trs, recs)
+    cores = su.bands(g, geom, 2, st, trs, recs=recs, scheme="van_leer", rows=2)
     su.whole_steps(cores, torch, 2, dt)
     for r, c in enumerate(cores):
         checkpoint.save(str(tmp_path / ("b%d.npz" % r)), c, step=2, geom=geom)
@@ -461,14 +440,14 @@ def test_drop_ins_equal_the_core_path(g):
     want = _forced_single(g, geom, st, trs, recs, 3, dt, runs=[3])
     got = dynamics.run(*st, dt, geom, 3, tracers=trs, tracer_scheme="van_leer", tracer_forcing=recs)
     su.assert_equal((got[:5], got[5]), want, "run")
-    one = _core(g, geom, st, trs, recs, scheme="centred")
+    one = su.single(g, geom, st, trs, recs=recs, scheme="centred")
     one.step(1, dt)
     got = dynamics.matsuno_timestep(*st, dt, geom, tracers=trs, tracer_forcing=recs)
     su.assert_equal((got[:5], got[5]), (one.get_state(), one.get_tracers()), "matsuno_timestep")
     one.close()
     # the cached handle of matsuno_timestep carries no forcing over to the next call
     plain = dynamics.matsuno_timestep(*st, dt, geom, tracers=trs)
-    again = _core(g, geom, st, trs, None, scheme="centred")
+    again = su.single(g, geom, st, trs, scheme="centred")
     again.step(1, dt)
     assert np.array_equal(plain[5], again.get_tracers())
     again.close()
@@ -484,7 +463,7 @@ def test_drop_ins_equal_the_core_path(g):
     p, u, v, t, q, _ = nl.gen_initial_conditions(geom2)
     v[0, 0, 0] = 0.1
     u *= 0
-    one = _core(g, geom2, (p, u, v, t, q), trs, recs, scheme="upwind")
+    one = su.single(g, geom2, (p, u, v, t, q), trs, recs=recs, scheme="upwind")
     for _ in range(3):
         one.step(1, dt)
     su.assert_equal((out[:5], out[7]), (one.get_state(), one.get_tracers()), "run_model")

@@ -4,13 +4,14 @@ rounds every operation on its own and takes its tables from the routine the CPU 
 np.array_equal throughout: with the NumPy restatement (tests/pe25d_tracer_mixing_ref.py, then the forcing's,
 tests/pe25d_tracer_forcing_ref.py) applied on the host to an unmixed, unforced handle's result, with the get / mix /
 force / set round trip per step, and -- on latitude bands, under every orchestration -- with the mixed single domain.
-The band set-ups are those of tests/pe25d_tracer_forcing_setups.py (in-process bands with device-copied ghost rows and
+The band set-ups are those of tests/gpu_setups.py (in-process bands with device-copied ghost rows and
 the loopback band of gcm_band_run): tests/band_engines.py holds NumPy engines of the dynamics without tracers, which
 have nothing to drive here."""
 import numpy as np
 import pytest
 
-import pe25d_tracer_forcing_setups as su
+import gpu_setups as su
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 from pe25d_tracer_forcing_ref import force
 from pe25d_tracer_mixing_ref import column_sum_drift, mix, profile
 
@@ -18,13 +19,6 @@ pytestmark = pytest.mark.gpu
 SCHEMES = ["centred", "upwind", "van_leer"]
 NTR = 3                                                           # 0 mixed, 1 mixed and forced (a pin), 2 neither
 DT = 120.0
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
 
 
 def _setup(H, W, L):
@@ -44,14 +38,14 @@ def _setup(H, W, L):
 
 
 def _core(g, geom, st, trs, mixing=None, forcing=None, dtype="f64", scheme="van_leer"):
-    c = su.single(g, geom, st, trs, forcing, dtype, scheme)
+    c = su.single(g, geom, st, trs, recs=forcing, dtype=dtype, scheme=scheme)
     for i, k in (mixing or {}).items():
         c.set_tracer_mixing(i, k)
     return c
 
 
 def _bands(g, geom, nb, st, trs, mixing, forcing, dtype="f64", scheme="van_leer", rows=2):
-    cores = su.bands(g, geom, nb, st, trs, forcing, dtype, scheme, rows=rows)
+    cores = su.bands(g, geom, nb, st, trs, recs=forcing, dtype=dtype, scheme=scheme, rows=rows)
     for c in cores:
         for i, k in mixing.items():
             c.set_tracer_mixing(i, k)
@@ -242,7 +236,7 @@ def test_mixed_band_run_loopback_equals_single_domain(g, dtype, overlap):
     ref.step(1, 45.0)
     want = ref.get_state(), ref.get_tracers()
     ref.close()
-    c, eng, runner = su.loopback_band(g, torch, geom, NTR, dtype)
+    c, eng, runner = su.loopback_band(g, torch, geom, NTR, dtype, scheme="van_leer", rows=2)
     assert runner.native
     if overlap:
         c.set_band_overlap(True)
@@ -277,8 +271,8 @@ def test_mass_budget_of_a_surface_heavy_tracer(g):
     trs = np.ascontiguousarray(np.stack([heavy, heavy]))
     k = profile(L, seed=7)
     assert np.all(k > 0)
-    a = su.single(g, geom, st, trs, None, "f64", "upwind")
-    b = su.single(g, geom, st, trs, None, "f64", "upwind")
+    a = su.single(g, geom, st, trs, scheme="upwind")
+    b = su.single(g, geom, st, trs, scheme="upwind")
     b.set_tracer_mixing(0, k)
     a.step(steps, DT)
     b.step(steps, DT)
@@ -388,7 +382,7 @@ def test_life_cycle_and_refusals(g):
     # one level: nothing to mix across
     geom1 = su.geom_of(6, 10, 1)
     st1, trs1 = su.initial(geom1, 1)
-    one = su.single(g, geom1, st1, trs1)
+    one = su.single(g, geom1, st1, trs1, scheme="van_leer")
     assert lib.gcm_set_tracer_mixing(one._h, 0, dp(np.zeros(1)), 0) == _lib.ERR_ARG
     assert lib.gcm_tracer_mixed(one._h, 0) == 0
     one.close()

@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+import pe25d_inputs as inp
 import pe25d_tracer_schemes_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,17 +17,6 @@ H, W, L = 24, 36, 9
 def _og(h=H, w=W, l=L):
     from oracle import geometry as ogeo
     return ogeo.gen_geometry(h, w, l, sig_func=ogeo.manabe_sig)
-
-
-def _random_state(og, seed):
-    rng = np.random.default_rng(seed)
-    l, h, w = og.layers, og.height, og.width
-    p = 1e5 + 10 * rng.standard_normal((h, w))
-    u, v = rng.standard_normal((l, h, w)), rng.standard_normal((l, h, w))
-    v[:, -1, :] = 0
-    t = (300 + rng.standard_normal((l, h, w))) * ((1e5 / (p * og.sig + og.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((l, h, w)))
-    return p, u, v, t, q
 
 
 def flow_state(og, U=30.0, V=15.0):
@@ -103,7 +93,7 @@ def test_centred_restatement_is_the_oracle_bit_for_bit(coriolis):
     from oracle import dynamics as od
     og = _og()
     og.heightmap[H // 2, W // 3] = 1500.0
-    st = _random_state(og, 3)
+    st = inp.state(og, 3)
     rng = np.random.default_rng(4)
     trs = np.stack([1.0 + rng.random((L, H, W)), latitude_step(), st[4]])
     state, got = st, trs

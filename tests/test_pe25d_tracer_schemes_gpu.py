@@ -7,7 +7,10 @@ import pytest
 
 from conftest import rel_err
 
+import gpu_setups as su
+import pe25d_inputs as inp
 import pe25d_tracer_schemes_ref as ref
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -19,52 +22,9 @@ F32_LIM_TOL = 3.8e-7
 SCHEMES = {"upwind": ref.UPWIND, "van_leer": ref.VANLEER}
 
 
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
-
-
-def _geoms(H, W, L, bump=False):
-    """the product's geometry and the oracle's, with the same topography"""
-    from gcmiipy_amd import geometry
-    from oracle import geometry as ogeo
-    geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    og = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
-    if bump:
-        geom.heightmap[H // 2, W // 3] = 1500.0
-        og.heightmap[H // 2, W // 3] = 1500.0
-    return geom, og
-
-
-def _state(H, W, L, seed, geom):
-    rng = np.random.default_rng(seed)
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u, v = rng.standard_normal((L, H, W)), rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    t = (300 + rng.standard_normal((L, H, W))) * ((1e5 / (p * geom.sig + geom.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
-    return p, u, v, t, q
-
-
 def _tracers(H, W, L, n, seed):
-    """random positive, a latitude step function, a constant; beyond three: random fields of other offsets, steps at
-    other latitudes"""
-    rng = np.random.default_rng(seed)
-    out = []
-    for k in range(max(n, 2)):
-        kind = k % 3
-        if kind == 0:
-            out.append(1.0 + k + rng.random((L, H, W)))
-        elif kind == 1:
-            c = np.zeros((L, H, W))
-            c[:, H // 3 + k // 3: 2 * H // 3 - k // 3, :] = 1.0
-            out.append(c)
-        else:
-            out.append(np.full((L, H, W), 2.5 + k))
-    order = [0, 1, 2, 3, 4, 5, 6][:n] if n >= 3 else [1, 0][:n]     # (one tracer: the step function)
-    return np.stack([out[k] for k in order])
+    """inp.tracers; below three, in the order step function, random positive (one tracer: the step function)"""
+    return inp.tracers(H, W, L, n, seed) if n >= 3 else inp.tracers(H, W, L, 2, seed)[[1, 0][:n]]
 
 
 # (H, W, L, filter, coriolis, topography bump, GCM_PE_LEVEL_SEGMENTS, tracer counts): odd and even L, with and without
@@ -86,8 +46,8 @@ def test_limited_tracers_vs_restatement(g, case):
     """UPWIND and VANLEER, fp64: the star set after the first predictor and the tracers after 5 full steps, every cell
     of every tracer, within the project's 1e-10 of the restatement"""
     H, W, L, filt, cor, bump, seg, counts = case
-    geom, og = _geoms(H, W, L, bump)
-    st = _state(H, W, L, 3, geom)
+    geom, og = su.geoms_of(H, W, L, bump=bump)
+    st = inp.state(geom, 3)
     dt, steps = 60.0, 5
     _, hist = ref.flux_history(st, dt, og, steps, cor)
     for ntr in counts:
@@ -120,8 +80,8 @@ def test_limited_tracers_without_filter_vs_restatement_on_handle_fluxes(g, case,
     from oracle import dynamics as od
     H, W, L, filt, cor, bump, seg, counts = case
     monkeypatch.setenv("GCM_PE_LEVEL_SEGMENTS", seg)
-    geom, og = _geoms(H, W, L, bump)
-    st = _state(H, W, L, 3, geom)
+    geom, og = su.geoms_of(H, W, L, bump=bump)
+    st = inp.state(geom, 3)
     dt = 60.0
     trs = _tracers(H, W, L, counts[-1], 4)
     for name, scheme in SCHEMES.items():
@@ -145,8 +105,8 @@ def test_scheme_none_is_untouched_and_switching_mid_run(g):
     gives; the setter drops the predicted tracers"""
     from gcmiipy_amd.core import GcmError
     H, W, L, dt = 24, 36, 9, 120.0
-    geom, og = _geoms(H, W, L)
-    st = _state(H, W, L, 5, geom)
+    geom, og = su.geoms_of(H, W, L)
+    st = inp.state(geom, 5)
     trs = _tracers(H, W, L, 7, 6)
     res = []
     for mode in ("never", "none", "detour"):
@@ -191,8 +151,8 @@ def test_scheme_none_is_untouched_and_switching_mid_run(g):
 def test_state_and_q_do_not_notice_the_tracers(g, scheme):
     """p, u, v, t, q after 5 steps with 5 limited tracers are bit-identical to a handle with no tracers"""
     H, W, L = 24, 36, 9
-    geom, _ = _geoms(H, W, L, bump=True)
-    st = _state(H, W, L, 9, geom)
+    geom = su.geom_of(H, W, L, bump=True)
+    st = inp.state(geom, 9)
     res = []
     for ntr in (5, 0):
         c = g.Core(g._lib.PE25D, W, H, L, geom=geom, tracer_scheme=scheme if ntr else None)
@@ -213,8 +173,8 @@ def test_single_stream_vs_two_streams(g, scheme, monkeypatch):
     """48 x 1440 x 24, 7 tracers, 4 steps: the limited kernels on the second stream beside K3 / K4 give the bits of a
     run with every kernel on one stream (GCM_PE_SINGLE_STREAM=1)"""
     H, W, L = 48, 1440, 24
-    geom, _ = _geoms(H, W, L)
-    st = _state(H, W, L, 13, geom)
+    geom = su.geom_of(H, W, L)
+    st = inp.state(geom, 13)
     trs = _tracers(H, W, L, 7, 14)
     res = {}
     for single in ("0", "1"):
@@ -230,67 +190,23 @@ def test_single_stream_vs_two_streams(g, scheme, monkeypatch):
     assert not np.array_equal(res["0"][0], trs)
 
 
-def _rows(a, sl):
-    return np.ascontiguousarray(a[..., sl, :])
-
-
-def _exchange(cores, torch):
-    """ring exchange by device copies on the default stream: side s of a band lands in the neighbour's opposite ghost"""
-    n = len(cores)
-    bufs = [[torch.empty(c.halo_bytes(), dtype=torch.uint8, device="cuda") for _ in (0, 1)] for c in cores]
-    for r, c in enumerate(cores):
-        c.halo_pack(0, bufs[r][0].data_ptr())
-        c.halo_pack(1, bufs[r][1].data_ptr())
-    torch.cuda.synchronize()
-    for r, c in enumerate(cores):
-        c.halo_unpack(1, bufs[(r + 1) % n][0].data_ptr())
-        c.halo_unpack(0, bufs[(r - 1) % n][1].data_ptr())
-    torch.cuda.synchronize()
-
-
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_upwind_on_eight_bands_equals_single_domain(g, dtype):
     """UPWIND reads rows j -+ 1 only: 8 in-process latitude bands of a 64 x 1440 x 24 grid with 3 tracers, the ghost
     rows moved by device copies (two exchanges per step), equal the single domain bit for bit after 3 steps -- state
     and tracers"""
     import torch
-    from gcmiipy_amd.bands import split_rows
     H, W, L, steps, nb, dt = 64, 1440, 24, 3, 8, 60.0
-    geom, _ = _geoms(H, W, L)
-    st = _state(H, W, L, 12, geom)
-    trs = _tracers(H, W, L, 3, 15)
-    one = g.Core(g._lib.PE25D, W, H, L, geom=geom, dtype=dtype, tracer_scheme="upwind")
-    one.set_state(*st)
-    one.set_tracers(trs)
-    one.step(steps, dt)
-    want, want_tr = one.get_state(), one.get_tracers()
-    one.close()
-    cores = []
-    for r, (row0, n) in enumerate(split_rows(H, nb)):
-        c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=nb, rank=r, global_height=H, row0=row0, dtype=dtype,
-                   band_tracers=3, tracer_scheme="upwind")
-        assert c.tracer_scheme == g._lib.TRACER_UPWIND
-        sl = slice(row0, row0 + n)
-        c.set_state(*[_rows(a, sl) for a in st])
-        c.set_tracers(_rows(trs, sl))
-        cores.append(c)
-    _exchange(cores, torch)
-    for _ in range(steps):
-        for c in cores:
-            c.step_interior(dt)
-        _exchange(cores, torch)
-        for c in cores:
-            c.step_boundary(dt)
-        _exchange(cores, torch)
-    parts = [c.get_state() for c in cores]
-    got = [np.concatenate([x[f] for x in parts], axis=0 if f == 0 else 1) for f in range(5)]
-    got_tr = np.concatenate([c.get_tracers() for c in cores], axis=2)
+    geom = su.geom_of(H, W, L)
+    st, trs = su.initial(geom, 3)
+    want = su.single_run(g, geom, st, trs, steps, dt, dtype=dtype, scheme="upwind")
+    cores = su.bands(g, geom, nb, st, trs, dtype=dtype, scheme="upwind")
     for c in cores:
-        c.close()
-    for f in range(5):
-        assert np.array_equal(got[f], want[f]), "puvtq"[f]
-    assert np.array_equal(got_tr, want_tr)
-    assert not np.array_equal(got_tr, trs)
+        assert c.tracer_scheme == g._lib.TRACER_UPWIND
+    su.whole_steps(cores, torch, steps, dt)
+    got = su.gather(cores)
+    su.assert_equal(got, want)
+    assert not np.array_equal(got[1], trs)
 
 
 @pytest.mark.parametrize("overlap", [False, True])
@@ -298,20 +214,11 @@ def test_upwind_band_run_loopback_equals_single_domain(g, overlap):
     """gcm_band_run with the loopback exchange (the band is its own neighbour): the split stage launches the tracers'
     edge rows and interior rows apart; UPWIND gives the single domain's bits"""
     import torch
-    from gcmiipy_amd.bands import BandRunner, HipBandEngine, LoopbackExchange
     H, W, L, dt = 23, 36, 9, 120.0
-    geom, _ = _geoms(H, W, L)
-    st = _state(H, W, L, 12, geom)
-    trs = _tracers(H, W, L, 3, 15)
-    one = g.Core(g._lib.PE25D, W, H, L, geom=geom, tracer_scheme="upwind")
-    one.set_state(*st)
-    one.set_tracers(trs)
-    one.step(5, dt)
-    want, want_tr = one.get_state(), one.get_tracers()
-    one.close()
-    c = g.Core(g._lib.PE25D, W, H, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0,
-               stream=torch.cuda.current_stream().cuda_stream, band_tracers=3, tracer_scheme="upwind")
-    runner = BandRunner(HipBandEngine(c, torch), 0, 2, LoopbackExchange(), north=0, south=0)
+    geom = su.geom_of(H, W, L)
+    st, trs = su.initial(geom, 3)
+    want = su.single_run(g, geom, st, trs, 5, dt, scheme="upwind")
+    c, eng, runner = su.loopback_band(g, torch, geom, 3, scheme="upwind")
     assert runner.native
     if overlap:
         c.set_band_overlap(True)
@@ -320,11 +227,9 @@ def test_upwind_band_run_loopback_equals_single_domain(g, overlap):
     runner.run(3, dt)
     runner.run(2, dt)
     torch.cuda.synchronize()
-    got, got_tr = c.get_state(), c.get_tracers()
+    got = c.get_state(), c.get_tracers()
     c.close()
-    for a, b in zip(got, want):
-        assert np.array_equal(a, b)
-    assert np.array_equal(got_tr, want_tr)
+    su.assert_equal(got, want)
 
 
 def test_refusals(g):
@@ -334,7 +239,7 @@ def test_refusals(g):
     from gcmiipy_amd.core import GcmError
     lib = _lib.lib
     H, W, L = 12, 20, 5
-    geom, _ = _geoms(H, W, L)
+    geom = su.geom_of(H, W, L)
     band = g.Core(_lib.PE25D, W, H // 2, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0, band_tracers=1)
     band.set_tracer_scheme("upwind")
     assert lib.gcm_set_tracer_scheme(band._h, _lib.TRACER_VANLEER) == _lib.ERR_UNSUPPORTED
@@ -367,8 +272,8 @@ def test_checkpoint_keeps_the_scheme_and_the_bits(g, scheme, tmp_path):
     handle's options, and a file without it restores as centred"""
     from gcmiipy_amd import checkpoint
     H, W, L = 24, 36, 9
-    geom, _ = _geoms(H, W, L)
-    st = _state(H, W, L, 17, geom)
+    geom = su.geom_of(H, W, L)
+    st = inp.state(geom, 17)
     trs = _tracers(H, W, L, 3, 8)
     a = g.Core(g._lib.PE25D, W, H, L, geom=geom)
     a.set_state(*st)
@@ -401,8 +306,8 @@ def test_dropins_take_a_scheme(g):
     tracers, a state that is what it is without tracers, and a cached handle that is centred again afterwards"""
     from gcmiipy_amd import dynamics, no_limits_2_5d
     H, W, L, dt = 12, 20, 5, 60.0
-    geom, og = _geoms(H, W, L)
-    st = _state(H, W, L, 21, geom)
+    geom, og = su.geoms_of(H, W, L)
+    st = inp.state(geom, 21)
     trs = np.stack([st[4], _tracers(H, W, L, 1, 3)[0]])
     plain = dynamics.matsuno_timestep(*st, dt, geom)
     _, hist = ref.flux_history(st, dt, og, 3)
@@ -442,8 +347,8 @@ def test_fp32_limited_schemes_vs_fp64(g):
     1.883e-07 / 1.601e-07 / 1.586e-07, UPWIND 1.706e-07 / 1.755e-07 / 1.881e-07, VANLEER 1.767e-07 / 1.777e-07 /
     1.392e-07: the limited schemes round like the centred one, no amplification at these cells."""
     H, W, L = 24, 36, 9
-    geom, _ = _geoms(H, W, L)
-    st = _state(H, W, L, 5, geom)
+    geom = su.geom_of(H, W, L)
+    st = inp.state(geom, 5)
     trs = _smooth_tracers(H, W, L, geom)
     worst = 0.0
     for name in ("centred", "upwind", "van_leer"):

@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import pe25d_inputs as inp
 import pe25d_tracer_schemes_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -98,11 +99,7 @@ def test_unweighted_mass_is_conserved_by_the_restatement(scheme):
     H, W, L = 12, 16, 5
     og = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
     rng = np.random.default_rng(21)
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u, v = rng.standard_normal((L, H, W)), rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    t = (300 + rng.standard_normal((L, H, W))) * ((1e5 / (p * og.sig + og.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
+    p, u, v, t, q = inp.state(og, rng)
     c0 = np.stack([1.0 + rng.random((L, H, W)), rng.standard_normal((L, H, W)), np.full((L, H, W), 2.5)])
     c0[1, :, H // 3: 2 * H // 3] += 1.0
     dsig = np.asarray(og.dsig, dtype=np.float64).reshape(L, 1, 1)

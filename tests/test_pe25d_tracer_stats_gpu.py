@@ -11,37 +11,14 @@ import math
 import numpy as np
 import pytest
 
-import band_van_leer_inputs as inp
+import gpu_setups as su
+import pe25d_inputs as inp
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -53
 BAND_SHAPE = (24, 36, 9)        # H, W, L
 DT = 120.0
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
-
-
-def _geom(H, W, L):
-    from gcmiipy_amd import geometry
-    return geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-
-
-def _state(geom):
-    return inp.state(geom.height, geom.width, geom.layers, np.asarray(geom.sig), geom.ptop)
-
-
-def _core(g, geom, dtype="f64", scheme=None, st=None, trs=None):
-    c = g.Core(g._lib.PE25D, geom.width, geom.height, geom.layers, geom=geom, dtype=dtype, tracer_scheme=scheme)
-    if st is not None:
-        c.set_state(*st)
-    if trs is not None:
-        c.set_tracers(trs)
-    return c
 
 
 def _reference(fields, p, geom):
@@ -96,9 +73,9 @@ def test_shape_sweep(g, dtype, shape, n):
     per workgroup; 1, 3 and 16 tracers of both signs; with and without q: all six words of every record.  (The paths
     beyond one chunk and one unit per workgroup: test_chunks_and_strided_units.)"""
     H, W, L = shape
-    geom = _geom(H, W, L)
-    st = _state(geom)
-    c = _core(g, geom, dtype, st=st, trs=_signed_tracers(H, W, L, n, seed=H + W + n))
+    geom = su.geom_of(H, W, L)
+    st = inp.state(geom)
+    c = su.single(g, geom, st, _signed_tracers(H, W, L, n, seed=H + W + n), dtype=dtype)
     trs, (p, _, _, _, q) = c.get_tracers(), c.get_state()
     assert (trs < 0).any() and (trs > 0).any()
     got = c.tracer_stats()
@@ -120,11 +97,11 @@ def test_chunks_and_strided_units(g, dtype, shape, n):
     (5, 540, 3): three chunks a row with a 28-column tail, 15 units and as many workgroups.  The same exact checks and
     the same derived bound as the sweep; a planted minimum and maximum sit in the last unit and in the tail"""
     H, W, L = shape
-    geom = _geom(H, W, L)
+    geom = su.geom_of(H, W, L)
     trs = _signed_tracers(H, W, L, n, seed=H + W + n)
     trs[0, L - 1, H - 1, W - 1] = -1e3                         # the last column of the last unit (its tail)
     trs[n - 1, 0, H - 1, 256] = 1e3                            # the first column of the last row's second chunk
-    c = _core(g, geom, dtype, st=_state(geom), trs=trs)
+    c = su.single(g, geom, inp.state(geom), trs, dtype=dtype)
     trs, (p, _, _, _, q) = c.get_tracers(), c.get_state()
     got = c.tracer_stats(with_q=True)
     _check(got, np.concatenate([trs, q[None]]), p, geom, (dtype, shape, n, "q"))
@@ -142,14 +119,14 @@ def test_planted_corner_values(g):
     at cell (0, 0, 0); tracer 2: exactly one negative cell and exactly one NaN, in two other corners.  Tracer 2
     reports 1 and 1, NaN for min, max and mass; the NaN leaves the records of tracers 0 and 1 alone"""
     H, W, L = BAND_SHAPE
-    geom = _geom(H, W, L)
+    geom = su.geom_of(H, W, L)
     rng = np.random.default_rng(5)
     trs = 1.0 + rng.random((3, L, H, W))
     trs[0, L - 1, H - 1, W - 1] = 0.25
     trs[1, 0, 0, 0] = 7.5
     trs[2, 0, H - 1, 0] = -1.0
     trs[2, L - 1, 0, W - 1] = np.nan
-    c = _core(g, geom, st=_state(geom), trs=trs)
+    c = su.single(g, geom, inp.state(geom), trs)
     got = c.tracer_stats()
     p = c.get_state()[0]
     _check(got, c.get_tracers(), p, geom, "planted")
@@ -175,9 +152,9 @@ def test_planted_corner_values(g):
 def test_star_set(g):
     from gcmiipy_amd import _lib
     H, W, L = BAND_SHAPE
-    geom = _geom(H, W, L)
-    st, trs = _state(geom), inp.tracers(H, W, L, 3)
-    c = _core(g, geom, scheme="upwind", st=st, trs=trs)
+    geom = su.geom_of(H, W, L)
+    st, trs = inp.state(geom), inp.tracers(H, W, L, 3)
+    c = su.single(g, geom, st, trs, scheme="upwind")
     out = np.full(4 * 6, 7.0)
     ptr = out.ctypes.data_as(C.c_void_p)
     assert _lib.lib.gcm_tracer_stats(c._h, 1, 0, ptr, out.size) == _lib.ERR_STATE       # before a predictor
@@ -203,8 +180,8 @@ def test_call_joins_the_tracer_stream(g, dtype):
     """step(3) and tracer_stats() right behind it: the last tracer launch runs on the handle's second stream, and the
     call includes it itself -- the reference is taken from get_tracers() afterwards.  A second call: the same bits"""
     H, W, L = BAND_SHAPE
-    geom = _geom(H, W, L)
-    c = _core(g, geom, dtype, "van_leer", _state(geom), inp.tracers(H, W, L, 5))
+    geom = su.geom_of(H, W, L)
+    c = su.single(g, geom, inp.state(geom), inp.tracers(H, W, L, 5), dtype=dtype, scheme="van_leer")
     c.step(3, DT)
     got = c.tracer_stats(with_q=True)
     again = c.tracer_stats(with_q=True)
@@ -214,7 +191,7 @@ def test_call_joins_the_tracer_stream(g, dtype):
         assert a.tobytes() == b.tobytes()
     # the call changes nothing a later step reads
     c.step(1, DT)
-    other = _core(g, geom, dtype, "van_leer", _state(geom), inp.tracers(H, W, L, 5))
+    other = su.single(g, geom, inp.state(geom), inp.tracers(H, W, L, 5), dtype=dtype, scheme="van_leer")
     other.step(4, DT)
     assert np.array_equal(c.get_tracers(), other.get_tracers())
     assert all(np.array_equal(a, b) for a, b in zip(c.get_state(), other.get_state()))
@@ -229,10 +206,10 @@ def test_mass_is_conserved_on_the_device(g, scheme):
     update is in flux form; tests/test_pe25d_tracer_stats_cpu.py shows the restatement conserving the same sum), and
     the donor-cell scheme leaves no negative cell"""
     H, W, L = BAND_SHAPE
-    geom = _geom(H, W, L)
+    geom = su.geom_of(H, W, L)
     step = np.zeros((1, L, H, W))
     step[0, :, H // 3: 2 * H // 3, :] = 1.0
-    c = _core(g, geom, scheme=scheme, st=_state(geom), trs=step)
+    c = su.single(g, geom, inp.state(geom), step, scheme=scheme)
     before = c.tracer_stats()
     dsig = np.asarray(geom.dsig, dtype=np.float64).reshape(-1, 1, 1)
     s_abs = math.fsum(np.abs(step[0] * c.get_state()[0] * dsig).ravel())
@@ -251,20 +228,6 @@ def test_mass_is_conserved_on_the_device(g, scheme):
 
 
 # ---------------------------------------------------------------- 6. latitude bands
-def _exchange(cores, torch):
-    """ring exchange by device copies: side s of a band lands in the neighbour's opposite ghost rows"""
-    n = len(cores)
-    bufs = [[torch.empty(c.halo_bytes(), dtype=torch.uint8, device="cuda") for _ in (0, 1)] for c in cores]
-    for r, c in enumerate(cores):
-        c.halo_pack(0, bufs[r][0].data_ptr())
-        c.halo_pack(1, bufs[r][1].data_ptr())
-    torch.cuda.synchronize()
-    for r, c in enumerate(cores):
-        c.halo_unpack(1, bufs[(r + 1) % n][0].data_ptr())
-        c.halo_unpack(0, bufs[(r - 1) % n][1].data_ptr())
-    torch.cuda.synchronize()
-
-
 @pytest.mark.parametrize("rows", [1, 2])
 def test_bands_merge_to_the_single_domain(g, rows):
     """3 bands of 8 rows stepped in one process, 2 tracers, 1 or 2 tracer ghost rows a side, 2 steps (the ghost rows
@@ -275,33 +238,19 @@ def test_bands_merge_to_the_single_domain(g, rows):
     from gcmiipy_amd.bands import merge_tracer_stats, split_rows
     H, W, L = BAND_SHAPE
     nb, ntr, steps = 3, 2, 2
-    geom = _geom(H, W, L)
-    st = _state(geom)
+    geom = su.geom_of(H, W, L)
+    st = inp.state(geom)
     trs = inp.tracers(H, W, L, ntr)
     trs[0, L // 2, H // nb, W // 2] = -40.0                      # band 1's first row
     trs[1] = np.random.default_rng(9).standard_normal((L, H, W))
-    one = _core(g, geom, scheme="upwind", st=st, trs=trs)
+    one = su.single(g, geom, st, trs, scheme="upwind")
     one.step(steps, DT)
     single = one.tracer_stats(with_q=True)
     tr1, (p1, _, _, _, q1) = one.get_tracers(), one.get_state()
     one.close()
     assert np.unravel_index(np.argmin(tr1[0]), tr1[0].shape)[1] == H // nb      # the premise: still that row
-    cores = []
-    for r, (row0, n) in enumerate(split_rows(H, nb)):
-        c = g.Core(g._lib.PE25D, W, n, L, geom=geom, nranks=nb, rank=r, global_height=H, row0=row0,
-                   band_tracers=ntr, band_tracer_rows=rows, tracer_scheme="upwind")
-        sl = slice(row0, row0 + n)
-        c.set_state(*[inp.rows(a, sl) for a in st])
-        c.set_tracers(inp.rows(trs, sl))
-        cores.append(c)
-    _exchange(cores, torch)
-    for _ in range(steps):
-        for c in cores:
-            c.step_interior(DT)                                  # predictor
-        _exchange(cores, torch)
-        for c in cores:
-            c.step_boundary(DT)                                  # corrector
-        _exchange(cores, torch)
+    cores = su.bands(g, geom, nb, st, trs, scheme="upwind", rows=rows)
+    su.whole_steps(cores, torch, steps, DT)
     parts = [c.tracer_stats(with_q=True) for c in cores]
     for r, (c, (row0, n)) in enumerate(zip(cores, split_rows(H, nb))):
         own = c.get_tracers()
@@ -325,8 +274,8 @@ def test_refusals(g):
     from gcmiipy_amd import _lib
     lib = _lib.lib
     H, W, L = 6, 36, 4
-    geom = _geom(H, W, L)
-    c = _core(g, geom, st=_state(geom), trs=_signed_tracers(H, W, L, 2, seed=1))
+    geom = su.geom_of(H, W, L)
+    c = su.single(g, geom, inp.state(geom), _signed_tracers(H, W, L, 2, seed=1))
     out = np.full(3 * 6, 7.0)
     ptr = out.ctypes.data_as(C.c_void_p)
     assert lib.gcm_tracer_stats(c._h, 0, 0, ptr, 11) == _lib.ERR_ARG              # 12 needed

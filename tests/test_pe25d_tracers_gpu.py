@@ -5,27 +5,13 @@ import numpy as np
 import pytest
 
 from conftest import golden, rel_err
+import gpu_setups as su
+import pe25d_inputs as inp
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
 F32_TOL = 2e-6          # test_fp32_tolerance_sweep: fp32 vs fp64 after one step
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
-
-
-def _state(H, W, L, seed, geom):
-    rng = np.random.default_rng(seed)
-    p = 1e5 + 10 * rng.standard_normal((H, W))
-    u, v = rng.standard_normal((L, H, W)), rng.standard_normal((L, H, W))
-    v[:, -1, :] = 0
-    t = (300 + rng.standard_normal((L, H, W))) * ((1e5 / (p * geom.sig + geom.ptop)) ** (287.0 / 1004.0))
-    q = 3e-6 * (1 + 0.1 * rng.random((L, H, W)))
-    return p, u, v, t, q
 
 
 def _tracers3(H, W, L, seed):
@@ -34,14 +20,6 @@ def _tracers3(H, W, L, seed):
     step = np.zeros((L, H, W))
     step[:, H // 3: 2 * H // 3, :] = 1.0
     return np.stack([1.0 + rng.random((L, H, W)), step, np.full((L, H, W), 2.5)])
-
-
-def _geom(H, W, L, bump=False):
-    from gcmiipy_amd import geometry
-    geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    if bump:
-        geom.heightmap[H // 2, W // 3] = 1500.0
-    return geom
 
 
 # (H, W, L, dtype, filter, coriolis, topography bump, GCM_PE_LEVEL_SEGMENTS).  fp64 only: in the fp32 update
@@ -63,8 +41,8 @@ def test_tracer_equal_to_q_stays_q_bit_for_bit(g, case, monkeypatch):
     H, W, L, dtype, filt, cor, bump, seg = case
     if seg:
         monkeypatch.setenv("GCM_PE_LEVEL_SEGMENTS", seg)
-    geom = _geom(H, W, L, bump)
-    p, u, v, t, q = _state(H, W, L, 7, geom)
+    geom = su.geom_of(H, W, L, bump=bump)
+    p, u, v, t, q = inp.state(geom, 7)
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom, filter=filt, coriolis=cor, dtype=dtype)
     c.set_state(p, u, v, t, q)
     other = 1.0 + np.random.default_rng(1).random((L, H, W))
@@ -90,9 +68,9 @@ def test_tracers_vs_oracle(g, hwl, steps):
     star set against the oracle's half_timestep (predictor)"""
     from oracle import dynamics as od, geometry as ogeo
     H, W, L = hwl
-    geom = _geom(H, W, L)
+    geom = su.geom_of(H, W, L)
     og = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
-    st = _state(H, W, L, 3, geom)
+    st = inp.state(geom, 3)
     trs = _tracers3(H, W, L, 4)
     dt = 60.0
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom)
@@ -118,9 +96,9 @@ def test_fp32_tracers_vs_oracle(g):
     """the fp32 handle's tracers after one step, within the fp32 tolerance of test_fp32_tolerance_sweep"""
     from oracle import dynamics as od, geometry as ogeo
     H, W, L = 24, 36, 9
-    geom = _geom(H, W, L)
+    geom = su.geom_of(H, W, L)
     og = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
-    st = _state(H, W, L, 5, geom)
+    st = inp.state(geom, 5)
     trs = _tracers3(H, W, L, 6)
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom, dtype="f32")
     c.set_state(*st)
@@ -138,8 +116,8 @@ def test_tracers_are_passive_and_zero_costs_nothing(g, physics):
     """p, u, v, t, q after 5 steps are bit-identical between a handle with 4 tracers, one with n = 0 set and one that
     never heard of tracers"""
     H, W, L = 24, 36, 9
-    geom = _geom(H, W, L, bump=True)
-    st = _state(H, W, L, 9, geom)
+    geom = su.geom_of(H, W, L, bump=True)
+    st = inp.state(geom, 9)
     gt = 288.0 + np.random.default_rng(3).standard_normal((H, W))
     res = []
     for mode in ("four", "zero", "never"):
@@ -168,8 +146,8 @@ def test_tracers_single_stream_vs_two_streams(g, physics, monkeypatch):
     """C4 size, 4 steps: the tracers (on the second stream beside K3 / K4 by default) are bit-identical to a run
     with every kernel on one stream (GCM_PE_SINGLE_STREAM=1)"""
     H, W, L = 720, 1440, 24
-    geom = _geom(H, W, L)
-    st = _state(H, W, L, 13, geom)
+    geom = su.geom_of(H, W, L)
+    st = inp.state(geom, 13)
     trs = _tracers3(H, W, L, 14)
     gt = 288.0 + np.random.default_rng(3).standard_normal((H, W))
     res = {}
@@ -194,7 +172,7 @@ def test_checkpoint_resume_with_tracers_bit_exact(g, tmp_path):
     from gcmiipy_amd import checkpoint
     d = golden("g8_pe25d")
     H, W, L = 24, 36, 9
-    geom = _geom(H, W, L)
+    geom = su.geom_of(H, W, L)
     ic = [d["dense_%s0" % k] for k in "puvtq"]
     trs = _tracers3(H, W, L, 8)
     a = g.Core(g._lib.PE25D, W, H, L, geom=geom)
@@ -226,8 +204,8 @@ def test_dropins_carry_tracers(g):
     them, and a tracer equal to q comes back equal to q"""
     from gcmiipy_amd import dynamics, no_limits_2_5d
     H, W, L = 12, 20, 5
-    geom = _geom(H, W, L)
-    st = _state(H, W, L, 21, geom)
+    geom = su.geom_of(H, W, L)
+    st = inp.state(geom, 21)
     trs = np.stack([st[4], np.ones((L, H, W))])
     plain = dynamics.matsuno_timestep(*st, 60.0, geom)
     out = dynamics.matsuno_timestep(*st, 60.0, geom, tracers=trs)
@@ -254,7 +232,7 @@ def test_tracer_refusals(g):
     from gcmiipy_amd.core import GcmError
     lib = g._lib.lib
     H, W, L = 12, 20, 5
-    geom = _geom(H, W, L)
+    geom = su.geom_of(H, W, L)
     band = g.Core(g._lib.PE25D, W, H // 2, L, geom=geom, nranks=2, rank=0, global_height=H, row0=0)
     x = np.ones((1, L, H // 2, W))
     assert lib.gcm_set_tracers(band._h, 1, x.ctypes.data_as(C.c_void_p)) == g._lib.ERR_UNSUPPORTED
@@ -265,7 +243,7 @@ def test_tracer_refusals(g):
     assert lib.gcm_get_tracers(sw._h, 0, None) == g._lib.ERR_UNSUPPORTED
     sw.close()
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom)
-    c.set_state(*_state(H, W, L, 1, geom))
+    c.set_state(*inp.state(geom, 1))
     big = np.ones((17, L, H, W))
     assert lib.gcm_set_tracers(c._h, 17, big.ctypes.data_as(C.c_void_p)) == g._lib.ERR_ARG
     assert lib.gcm_set_tracers(c._h, -1, None) == g._lib.ERR_ARG
@@ -293,7 +271,7 @@ def test_resizing_the_tracer_set_on_one_handle(g, dtype):
     a fresh handle given the same inputs; after n = 0 the state steps as on a handle that never had tracers"""
     lib = g._lib.lib
     L, H, W = 3, 8, 16
-    geom = _geom(H, W, L)
+    geom = su.geom_of(H, W, L)
     rng = np.random.default_rng(31)
     emis = 1e-3 * rng.random((L, H, W))
     pin = np.zeros((L, H, W), dtype=bool)
@@ -316,7 +294,7 @@ def test_resizing_the_tracer_set_on_one_handle(g, dtype):
         return out
 
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom, dtype=dtype)
-    st = _state(H, W, L, 30, geom)
+    st = inp.state(geom, 30)
     c.set_state(*st)
     c.set_tracers(tr2)
     c.set_tracer_forcing(1, **force)

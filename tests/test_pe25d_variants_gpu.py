@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, rel_err
+import gpu_setups as su
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 from test_pe25d_variants_cpu import FILTER_WIDTHS
 
 pytestmark = pytest.mark.gpu
@@ -24,22 +26,6 @@ F32_FILTER = 1e-6
 F32_RAD = (2e-5, 2e-5, 3e-7, 1e-7)
 L_MAX = 156          # pe25d_create: the radiation kernel's LDS park, 8 L 128 bytes + 4 KB <= 160 KB (both dtypes)
 PTOP = 5000.0
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
-
-
-def _geoms(H, W, L, ptop=0.0):
-    from gcmiipy_amd import geometry
-    from oracle import geometry as ogeo
-    geom = geometry.gen_geometry(H, W, L, sig_func=geometry.manabe_sig)
-    og = ogeo.gen_geometry(H, W, L, sig_func=ogeo.manabe_sig)
-    geom.ptop = og.ptop = ptop
-    return geom, og
 
 
 def _f32(x):
@@ -93,7 +79,7 @@ def test_polar_filter_vs_oracle(g, W, dtype):
     +-67.5: the multiplier is < 1 in all of them), three levels (one unpaired)"""
     from oracle import lowpass
     H, L = 4, 3
-    geom, og = _geoms(H, W, L)
+    geom, og = su.geoms_of(H, W, L)
     q = 1e3 * np.random.default_rng(W).standard_normal((L, H, W))
     tol = TOL
     if dtype == "f32":
@@ -114,7 +100,7 @@ def test_one_step_fp32_vs_oracle(g, W):
     """one step of an fp32 handle (K1 looping or not, pit, K3, K4 of the width's plan in float) against the float64
     oracle from the same float32-rounded state"""
     H, L = 4, 3
-    geom, og = _geoms(H, W, L)
+    geom, og = su.geoms_of(H, W, L)
     st = _state(H, W, L, og, 1000 + W, f32=True)
     want = _oracle(st, 1, 60.0, og)
     assert rel_err(want[1], st[1]) > 1e3 * F32_STEP         # the step moves the winds
@@ -138,7 +124,7 @@ def test_hot_path_intermediates_fp32_vs_oracle(g, W):
     kMask1440 K3) and 1458 (the four-pass plan in every filter kernel); a failure points at K1, pit or K3"""
     from oracle import dynamics as od
     H, L = 8, 24
-    geom, og = _geoms(H, W, L)
+    geom, og = su.geoms_of(H, W, L)
     rng = np.random.default_rng(W)
     geom.heightmap[...] = og.heightmap[...] = _f32(30 * rng.random((H, W)))
     base, dt = _state(H, W, L, og, W + 1, f32=True), 30.0
@@ -172,7 +158,7 @@ def test_level_counts_vs_oracle(g, L, dtype, monkeypatch):
     the LDS park above), even L (K4 starts the march on an odd level, oddtop) and odd L, up to the largest L the handle
     accepts; default, pit from the 3-D fields (the geopot launch without column sums), K4 in three level segments"""
     H, W = 5, 30
-    geom, og = _geoms(H, W, L)
+    geom, og = su.geoms_of(H, W, L)
     f32 = dtype == "f32"
     st = _state(H, W, L, og, L, f32=f32)
     nsteps = 1 if f32 else 2
@@ -218,7 +204,7 @@ def test_level_counts_radiation_vs_oracle(g, L, dtype):
     """grey_radiation and solar_step at the same level counts (pe_radiation_kernel<T, 24 / 40, FACT> and the LDS-parked
     <T, 0> above 40 levels)"""
     H, W = 5, 30
-    geom, og = _geoms(H, W, L)
+    geom, og = su.geoms_of(H, W, L)
     st = _state(H, W, L, og, 2 * L, f32=dtype == "f32")
     got, want = _radiation(g, geom, og, st, dtype, L)
     _check_rad(got, want, (L, dtype), F32_RAD if dtype == "f32" else (TOL,) * 4)
@@ -257,7 +243,7 @@ def test_radiation_generic_form_matches_default(g, tmp_path):
     cases, ins = [], {}
     for L, ptop in ((9, 0.0), (24, 0.0), (33, 0.0), (9, PTOP), (33, PTOP)):
         H, W = 4, 20
-        geom, og = _geoms(H, W, L, ptop)
+        geom, og = su.geoms_of(H, W, L, ptop)
         p, _, _, t, _ = _state(H, W, L, og, L + int(ptop))
         gt = 270 + 30 * np.random.default_rng(L).random((H, W))
         key = "%dx%dx%dx%g" % (L, H, W, ptop)
@@ -290,7 +276,7 @@ def test_radiation_generic_form_matches_default(g, tmp_path):
 def test_tracer_equal_to_q_stays_equal_at_64_levels(g):
     """a tracer that starts equal to q stays equal to q bit for bit (the tracer kernel and K4's q update, 64 levels)"""
     H, W, L = 6, 30, 64
-    geom, og = _geoms(H, W, L)
+    geom, og = su.geoms_of(H, W, L)
     st = _state(H, W, L, og, 64)
     c = g.Core(g._lib.PE25D, W, H, L, geom=geom)
     c.set_state(*st)
@@ -306,7 +292,7 @@ def test_tracer_equal_to_q_stays_equal_at_64_levels(g):
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_one_layer_too_many_is_refused(g, dtype):
     """L_MAX + 1 levels: gcm_create refuses the handle and names the limit; nothing is launched"""
-    geom, _ = _geoms(4, 20, L_MAX + 1)
+    geom, _ = su.geoms_of(4, 20, L_MAX + 1)
     with pytest.raises(ValueError, match="%d layers: the column kernels' LDS holds at most %d" % (L_MAX + 1, L_MAX)):
         g.Core(g._lib.PE25D, 20, 4, L_MAX + 1, geom=geom, dtype=dtype)
 
@@ -320,11 +306,11 @@ def test_ptop_dynamics_and_radiation_vs_oracle(g, hwl):
     """ptop = 50 hPa enters the geopotential, K3, K4 and the radiation kernels without FACT (<T, 24> for 5 and 24 levels,
     <T, 40> for 32, the LDS-parked <T, 0> for 41): two fp64 steps, grey_radiation + solar_step, one fp32 step"""
     H, W, L = hwl
-    geom, og = _geoms(H, W, L, PTOP)
+    geom, og = su.geoms_of(H, W, L, PTOP)
     st = _state(H, W, L, og, H * W + L)
     _check(_run(g, geom, st, 2, 60.0), _oracle(st, 2, 60.0, og), ("ptop", hwl))
     # the ptop terms matter: the same state with ptop = 0 in the oracle is far off
-    _, og0 = _geoms(H, W, L)
+    _, og0 = su.geoms_of(H, W, L)
     assert rel_err(_oracle(st, 1, 60.0, og0)[1], _oracle(st, 1, 60.0, og)[1]) > 1e-6
     for dtype, tols in (("f64", (TOL,) * 4), ("f32", F32_RAD)):
         got, want = _radiation(g, geom, og, _state(H, W, L, og, H * W + L, f32=dtype == "f32"), dtype, H + L)

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+import gpu_setups as su
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 DX, DT = 300e3, 300.0
@@ -22,13 +24,6 @@ MODELS = [("sw2d", 1, 0), ("temp", 2, 0), ("temp_upwind", 2, 1), ("temp_vanleer"
 # (SW2D) or 1e5 (SW2D_TEMP) that differ by O(1): in fp32 that difference keeps only 2-3 significant digits.
 F32_STEP = {1: {"u": 4e-6, "v": 4e-6, "p": 1e-7},
             2: {"u": 2e-5, "v": 2e-5, "p": 8e-7, "t": 6e-7, "q": 6e-7}}
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
 
 
 def _states(model, tracer, H, W, seed, M=None):
@@ -255,20 +250,6 @@ def test_member_entry_points_and_diag_members(g):
     assert np.all(np.abs(after - sums) < 1e-7 * np.abs(sums))
 
 
-def _ring_exchange(cores, torch):
-    """ring exchange by device copies: the rows a band packs on side s land in the neighbour's opposite ghost"""
-    n = len(cores)
-    bufs = [[torch.empty(c.halo_bytes() // 8, dtype=torch.float64, device="cuda") for _ in (0, 1)] for c in cores]
-    for r, c in enumerate(cores):
-        c.halo_pack(0, bufs[r][0].data_ptr())
-        c.halo_pack(1, bufs[r][1].data_ptr())
-    torch.cuda.synchronize()
-    for r, c in enumerate(cores):
-        c.halo_unpack(1, bufs[(r + 1) % n][0].data_ptr())
-        c.halo_unpack(0, bufs[(r - 1) % n][1].data_ptr())
-    torch.cuda.synchronize()
-
-
 @pytest.mark.parametrize("variant", ["fused1", "fused2", "staged"])
 @pytest.mark.parametrize("nb,halo", [(2, 1), (4, 1), (2, 2), (4, 2)])
 def test_bands_host_loop_equal_single_domain(g, monkeypatch, nb, halo, variant):
@@ -291,7 +272,7 @@ def test_bands_host_loop_equal_single_domain(g, monkeypatch, nb, halo, variant):
         c.set_state(**{k: a[row0:row0 + n] for k, a in s.items()})
         cores.append(c)
     for _ in range(steps // halo):
-        _ring_exchange(cores, torch)
+        su.exchange(cores, torch)
         for c in cores:
             if halo == 1:
                 c.step_interior(DT)

@@ -13,16 +13,10 @@ import numpy as np
 import pytest
 
 import sw2d_geometry_cases as gc
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 SWITCHES = ("GCM_FUSED_ROWS", "GCM_SW2D_TWO_STEP", "GCM_SW2D_F32_COLS")
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
 
 
 def _cases():

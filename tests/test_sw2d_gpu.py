@@ -5,16 +5,10 @@ import numpy as np
 import pytest
 
 from conftest import golden, rel_err
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
 
 
 def _variants(g):

@@ -5,36 +5,16 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+import gpu_setups as su
 import term_cases as tc
+from gpu_setups import g  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gcmiipy_amd
-    assert gcmiipy_amd.device_count() >= 1, "no MI355X visible"
-    return gcmiipy_amd
 
 
 def _by_field(got, names):
     """get_state's [p, u, v, t, q] as a tuple in the order `names`"""
     return tuple(got["puvtq".index(k)] for k in names)
-
-
-def _exchange(cores, torch):
-    """ring exchange by device copies: the rows a band packs on side s land in the neighbour's opposite ghost"""
-    n = len(cores)
-    bufs = [[torch.empty(c.halo_bytes() // 8, dtype=torch.float64, device="cuda") for _ in (0, 1)]
-            for c in cores]
-    for r, c in enumerate(cores):
-        c.halo_pack(0, bufs[r][0].data_ptr())
-        c.halo_pack(1, bufs[r][1].data_ptr())
-    torch.cuda.synchronize()
-    for r, c in enumerate(cores):
-        c.halo_unpack(1, bufs[(r + 1) % n][0].data_ptr())
-        c.halo_unpack(0, bufs[(r - 1) % n][1].data_ptr())
-    torch.cuda.synchronize()
 
 
 def _run_2d(g, case, monkeypatch):
@@ -71,7 +51,7 @@ def _run_2d(g, case, monkeypatch):
                 tc.check_plan(case, c.sw2d_plan(1))
             cores.append(c)
         for _ in range(case.steps):
-            _exchange(cores, torch)
+            su.exchange(cores, torch)
             for c in cores:
                 c.step_interior(case.dt)
             for c in cores:
