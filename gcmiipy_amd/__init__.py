@@ -13,7 +13,7 @@ Importing the package loads the library and raises ImportError if it is not
 built: nothing here computes on the CPU.
 """
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
-from .core import Climate, Core, GcmError, TracerStats, device_count, held_suarez_tables  # noqa: F401
+from .core import Climate, Core, GcmError, Moist, TracerStats, device_count, held_suarez_tables, moist_saturation  # noqa: F401
 
 
 
@@ -26,4 +26,5 @@ def clear_cache():
     _lib.lib.gcm_ops_release_scratch()      # the operator entry points' device scratch of this thread
 
 
-__all__ = ["Climate", "Core", "GcmError", "TracerStats", "device_count", "clear_cache", "held_suarez_tables"]
+__all__ = ["Climate", "Core", "GcmError", "Moist", "TracerStats", "device_count", "clear_cache", "held_suarez_tables",
+           "moist_saturation"]

@@ -81,6 +81,11 @@ class HeldSuarez(C.Structure):
                 ("lat", _dp)]
 
 
+class Moist(C.Structure):
+    """gcm_moist of include/gcmcore.h"""
+    _fields_ = [("Lv", C.c_double), ("tau_e", C.c_double), ("rh_s", C.c_double)]
+
+
 class TracerForcing(C.Structure):
     """gcm_tracer_forcing of include/gcmcore.h"""
     _fields_ = [("source", C.c_double), ("decay", C.c_double), ("pin_value", C.c_double),
@@ -125,6 +130,13 @@ SYMBOLS = {
     "gcm_held_suarez_on": (C.c_int, [_H]),
     "gcm_held_suarez_step": (C.c_int, [_H, C.c_double, C.POINTER(HeldSuarez)]),
     "gcm_held_suarez_tables": (C.c_int, [C.c_int, _dp, C.c_int, _dp, C.POINTER(HeldSuarez), C.c_double, _dp, _dp, _dp, _dp]),
+    "gcm_set_moist": (C.c_int, [_H, C.POINTER(Moist)]),
+    "gcm_moist_on": (C.c_int, [_H]),
+    "gcm_moist_step": (C.c_int, [_H, C.c_double, C.POINTER(Moist)]),
+    "gcm_get_moist": (C.c_int, [_H, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "gcm_put_moist": (C.c_int, [_H, _dp, _dp, C.c_double, C.c_int64]),
+    "gcm_moist_reset": (C.c_int, [_H]),
+    "gcm_moist_saturation": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     "gcm_set_climate": (C.c_int, [_H, C.c_int]),
     "gcm_climate_every": (C.c_int, [_H]),
     "gcm_climate_sample": (C.c_int, [_H]),

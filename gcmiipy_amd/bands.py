@@ -213,6 +213,21 @@ def merge_climate(parts):
     return Climate(parts[0].n, *[np.concatenate([c[f] for c in parts], axis=-1) for f in range(1, len(Climate._fields))])
 
 
+def merge_moist(parts):
+    """the moist physics' sums of the whole domain from its bands': `parts` are the bands' Moist records
+    (Core.moist_sums) in row order; the rows are concatenated.  ValueError where nsteps or seconds differ"""
+    import numpy as np
+    from .core import Moist
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_moist: no records")
+    if any(m.nsteps != parts[0].nsteps or m.seconds != parts[0].seconds for m in parts):
+        raise ValueError("merge_moist: the bands hold %s applications over %s seconds"
+                         % (", ".join(str(m.nsteps) for m in parts), ", ".join(repr(m.seconds) for m in parts)))
+    return Moist(parts[0].nsteps, parts[0].seconds, np.concatenate([m.precip for m in parts], axis=0),
+                 np.concatenate([m.evap for m in parts], axis=0))
+
+
 class LoopbackExchange:
     """Diagnostic stand-in for torch.distributed inside BandRunner: every send lands in the
     matching receive buffer of the SAME rank (a device-local copy on the comm stream).  The band
@@ -308,6 +323,13 @@ class HipBandEngine:
         self.c.set_held_suarez(geom, **params)
         self._hs = None if geom is None else (geom, dict(params))
 
+    def set_moist(self, *off, **params):
+        """the moist physics after every dynamics step, behind the Held-Suarez forcing (Core.set_moist; every band of a
+        run registers the same): inside the library's gcm_band_run, or from physics_step() when the host drives the
+        exchange.  set_moist(None) switches it off.  merge_moist() puts the bands' sums together"""
+        self.c.set_moist(*off, **params)
+        self._moist = None if off else dict(params)
+
     def set_climate(self, every=1):
         """the zonal-mean climatology of the band's own rows (Core.set_climate; every band of a run registers the same
         interval): sampled inside the library's gcm_band_run, or from physics_step() when the host drives the
@@ -317,7 +339,7 @@ class HipBandEngine:
 
     def physics_step(self, dt):
         """host-driven band step: own rows and ghost rows by one gcm_solar_step on the compute stream, behind the
-        unpack of the post-corrector exchange; then, likewise, the Held-Suarez forcing; then the climatology's sample
+        unpack of the post-corrector exchange; then, likewise, the Held-Suarez forcing and the moist physics; then the climatology's sample
         where this step is due one"""
         ph = getattr(self, "_phys", None)
         if ph is not None:
@@ -326,6 +348,9 @@ class HipBandEngine:
         hs = getattr(self, "_hs", None)
         if hs is not None:
             self.c.held_suarez_step(hs[0], dt, **hs[1])
+        mo = getattr(self, "_moist", None)
+        if mo is not None:
+            self.c.moist_step(dt, **mo)
         cl = getattr(self, "_clim", None)
         if cl is not None and cl[0] > 0:
             cl[1] += 1

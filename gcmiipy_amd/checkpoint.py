@@ -13,14 +13,17 @@ without the key restore with none; the Held-Suarez forcing, Core.set_held_suarez
 parameters in the order of core.HELD_SUAREZ_DEFAULTS, with "held_suarez_lat", the latitudes it was given, and
 re-registered on restore; files without the key restore with none; the zonal-mean climatology, Core.set_climate, is
 stored as "climate_every", "climate_n", "climate_m3" and "climate_m2", the interval, the sample count and the raw
-float64 sums, registered and uploaded again on restore; files without these keys restore without a climatology)
+float64 sums, registered and uploaded again on restore; files without these keys restore without a climatology; the
+moist physics, Core.set_moist, is stored as "moist", its three parameters in the order of core.MOIST_DEFAULTS, with
+"moist_n", "moist_seconds", "moist_precip" and "moist_evap", the count, the seconds and the raw float64 sums, registered
+and uploaded again on restore; files without these keys restore with none)
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
 import numpy as np
 
 from . import _lib
-from .core import Core, HELD_SUAREZ_DEFAULTS
+from .core import Core, GcmError, HELD_SUAREZ_DEFAULTS, MOIST_DEFAULTS
 from .geometry import Geom
 
 _GEOM_KEYS = ("sige", "sigt", "sigb", "dsig", "sig", "dsigv", "dx_j", "dx_h", "dy", "ptop",
@@ -54,6 +57,14 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
     if core.model == _lib.PE25D and core.climate_every > 0:
         n, m3, m2 = core.climate_sums()
         out.update(climate_every=np.int64(core.climate_every), climate_n=np.int64(n), climate_m3=m3, climate_m2=m2)
+    mo = getattr(core, "moist", None) if core.model == _lib.PE25D else None
+    if mo is None and core.model == _lib.PE25D and getattr(core, "moist_registered", False):
+        raise GcmError("checkpoint.save: the handle's moist physics was registered through gcm_set_moist directly; its "
+                       "parameters are unknown here and the phase and its sums would be lost (register with Core.set_moist)")
+    if mo is not None:
+        sums = core.moist_sums()
+        out.update(moist=np.asarray([mo[k] for k in MOIST_DEFAULTS], dtype=np.float64), moist_n=np.int64(sums.nsteps),
+                   moist_seconds=np.float64(sums.seconds), moist_precip=sums.precip, moist_evap=sums.evap)
     for k, a in zip("puvtq", (p, u, v, t, q)):
         if a is not None:
             out["state_" + k] = a
@@ -67,9 +78,9 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, held_suarez, climate); ground and tracers are None where the file has none, tracer_forcing
+    tracer_mixing, held_suarez, climate, moist); ground and tracers are None where the file has none, tracer_forcing
     {i: dict(...)} and tracer_mixing {i: K} are then empty; held_suarez is (parameters dict, lat) or None; climate is
-    dict(every, n, m3, m2) or None"""
+    dict(every, n, m3, m2) or None; moist is dict(params, n, seconds, precip, evap) or None"""
     d = np.load(path, allow_pickle=False)
     L, H, W = (int(x) for x in d["shape"])
     state = {k: d["state_" + k] for k in "puvtq" if "state_" + k in d.files}
@@ -103,7 +114,12 @@ def load(path):
     clim = None
     if "climate_every" in d.files:
         clim = dict(every=int(d["climate_every"]), n=int(d["climate_n"]), m3=d["climate_m3"], m2=d["climate_m2"])
+    moist = None
+    if "moist" in d.files:
+        moist = dict(params=dict(zip(MOIST_DEFAULTS, (float(x) for x in d["moist"]))), n=int(d["moist_n"]),
+                     seconds=float(d["moist_seconds"]), precip=d["moist_precip"], evap=d["moist_evap"])
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, climate=clim,
+                moist=moist,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
@@ -134,4 +150,7 @@ def restore(path, **core_kwargs):
     if ck["climate"] is not None:
         core.set_climate(ck["climate"]["every"])
         core.put_climate(ck["climate"]["n"], ck["climate"]["m3"], ck["climate"]["m2"])
+    if ck["moist"] is not None:
+        core.set_moist(**ck["moist"]["params"])
+        core.put_moist(ck["moist"]["n"], ck["moist"]["seconds"], ck["moist"]["precip"], ck["moist"]["evap"])
     return core, ck

@@ -174,6 +174,58 @@ def held_suarez_tables(sig, lat, dt, **params):
     return dict(fu=fu, kt=kt, s2=s2, c2=c2)
 
 
+# the parameters of the moist physics (gcm_moist), in the struct's order: the latent heat (J / kg), the evaporation time
+# scale (s; 0: no evaporation) and the target relative humidity of the lowest level
+MOIST_DEFAULTS = collections.OrderedDict(Lv=2.5e6, tau_e=0.0, rh_s=0.8)
+
+
+def moist_params(params):
+    """the three parameters of the moist physics as a dict of floats: MOIST_DEFAULTS with `params` laid over them;
+    ValueError for a name that is not a parameter"""
+    unknown = sorted(set(params) - set(MOIST_DEFAULTS))
+    if unknown:
+        raise ValueError("moist: unknown parameter(s) %s; the parameters are %s"
+                         % (", ".join(unknown), ", ".join(MOIST_DEFAULTS)))
+    out = collections.OrderedDict(MOIST_DEFAULTS)
+    out.update({k: float(v) for k, v in params.items()})
+    return out
+
+
+class Moist(collections.namedtuple("Moist", "nsteps seconds precip evap")):
+    """the sums of a GCM_PE25D handle's moist physics (Core.moist_sums): the applications counted, the sum of their dt
+    in seconds, and per column (H, W) the precipitation and the evaporation accumulated over them, kg / m^2, float64.
+    A band: its own rows (bands.merge_moist)"""
+    __slots__ = ()
+
+    def _rate(self, a):
+        if self.seconds == 0:
+            raise ValueError("Moist: no time accumulated (seconds == 0)")
+        return a / self.seconds
+
+    def precip_rate(self):
+        """kg / m^2 / s: precip / seconds; ValueError where seconds == 0"""
+        return self._rate(self.precip)
+
+    def evap_rate(self):
+        """kg / m^2 / s: evap / seconds; ValueError where seconds == 0"""
+        return self._rate(self.evap)
+
+
+def moist_saturation(T, p_lev):
+    """the saturation routine of the moist physics (gcm_moist_saturation; the host build of the one routine the kernel
+    calls, no handle, no device) for true temperatures T (K) and level pressures p_lev (Pa) of one shape
+    -> (q_s, dq_s, can): the saturation specific humidity, its derivative in T at constant pressure, and whether the cell
+    can saturate (e_s < p_lev; where it cannot, q_s and dq_s are 0)"""
+    T = np.asarray(T, dtype=np.float64)
+    p_lev = np.asarray(p_lev, dtype=np.float64)
+    if T.shape != p_lev.shape:
+        raise ValueError("moist_saturation: T has shape %s, p_lev %s" % (T.shape, p_lev.shape))
+    t, pl = as_f64(T.reshape(-1)), as_f64(p_lev.reshape(-1))
+    qs, dqs, can = np.empty(t.size), np.empty(t.size), np.empty(t.size, dtype=np.intc)
+    _check(lib.gcm_moist_saturation(t.size, _tab(t), _tab(pl), _tab(qs), _tab(dqs), can.ctypes.data_as(C.POINTER(C.c_int))))
+    return qs.reshape(T.shape), dqs.reshape(T.shape), can.reshape(T.shape).astype(bool)
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -227,6 +279,7 @@ class Core:
         self._forcing = {}                      # tracer -> the forcing record registered (set_tracer_forcing)
         self._mixing = {}                       # tracer -> the profile K registered (set_tracer_mixing)
         self._held_suarez = None                # the parameters and latitudes registered (set_held_suarez)
+        self._moist = None                      # the parameters registered (set_moist)
         cfg = _lib.Config()
         cfg.abi_version = _lib.ABI_VERSION
         cfg.model = model
@@ -652,6 +705,69 @@ class Core:
     def held_suarez_lat(self):
         """the latitudes (global_height,) the registered Held-Suarez forcing was given, or None"""
         return self._held_suarez[1].copy() if self.held_suarez is not None else None
+
+    # -- moist physics (GCM_PE25D) ---------------------------------------------------------
+    def set_moist(self, *off, **params):
+        """every step of step() / band_run() from now on ends with the moist physics on the device: q in excess of
+        saturation condenses, the latent heat warms theta, the condensate leaves the column as precipitation, and with
+        tau_e > 0 the lowest level is moistened towards the relative humidity rh_s (gcm_set_moist) -- the Matsuno step,
+        solar_timestep where set_physics is on, the Held-Suarez forcing where registered, then this, then the
+        climatology's sample.  half_step never applies it.  params: Lv (J / kg), tau_e (s, 0: no evaporation), rh_s
+        (MOIST_DEFAULTS).  Precipitation and evaporation are accumulated per column (moist_sums); registering again
+        resets the sums.  set_moist(None) switches the phase off.  ValueError for a refused parameter (the call then
+        changes nothing)"""
+        if off:
+            if off != (None,) or params:
+                raise ValueError("set_moist takes keyword parameters, or None alone to switch the phase off")
+            _check(lib.gcm_set_moist(self._h, None), self._h)
+            self._moist = None
+            return
+        par = moist_params(params)
+        rec = _lib.Moist(*par.values())
+        _check(lib.gcm_set_moist(self._h, C.byref(rec)), self._h)
+        self._moist = dict(par)
+
+    @property
+    def moist(self):
+        """the parameters of the registered moist physics as a dict, or None where the handle carries none
+        (gcm_moist_on) -- and also None for one registered through the C call directly"""
+        on = lib.gcm_moist_on(self._h)
+        if on < 0:
+            _check(on, self._h)
+        return dict(self._moist) if on and self._moist else None
+
+    @property
+    def moist_registered(self):
+        """whether the handle carries the phase at all (gcm_moist_on), whoever registered it"""
+        on = lib.gcm_moist_on(self._h)
+        if on < 0:
+            _check(on, self._h)
+        return bool(on)
+
+    def moist_step(self, dt, **params):
+        """the moist physics once, in place on the current state, with the step dt (gcm_moist_step): what
+        held_suarez_step is to set_held_suarez.  With a registration the call adds to its sums, without one the sums
+        of the call are dropped.  A band: own rows and ghost rows, the ghost rows must be current"""
+        rec = _lib.Moist(*moist_params(params).values())
+        _check(lib.gcm_moist_step(self._h, float(dt), C.byref(rec)), self._h)
+
+    def moist_sums(self):
+        """-> Moist(nsteps, seconds, precip (H, W), evap (H, W)): the float64 sums as the device holds them
+        (gcm_get_moist); one synchronisation.  GcmError where no moist physics is registered"""
+        precip, evap = np.empty((self.H, self.W)), np.empty((self.H, self.W))
+        sec, n = C.c_double(), C.c_int64()
+        _check(lib.gcm_get_moist(self._h, _tab(precip), _tab(evap), C.byref(sec), C.byref(n)), self._h)
+        return Moist(int(n.value), float(sec.value), precip, evap)
+
+    def put_moist(self, nsteps, seconds, precip, evap):
+        """upload sums taken by moist_sums() (gcm_put_moist): a restart goes on where the run stopped"""
+        precip = as_f64(precip, (self.H, self.W), "precip")
+        evap = as_f64(evap, (self.H, self.W), "evap")
+        _check(lib.gcm_put_moist(self._h, _tab(precip), _tab(evap), float(seconds), int(nsteps)), self._h)
+
+    def moist_reset(self):
+        """zero the sums, the seconds and the count (gcm_moist_reset)"""
+        _check(lib.gcm_moist_reset(self._h), self._h)
 
     # -- zonal-mean climatology (GCM_PE25D) ------------------------------------------------
     def set_climate(self, every=1):

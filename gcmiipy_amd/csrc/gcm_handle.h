@@ -37,9 +37,11 @@ struct GcmTiming {
 // registration is Pe25d's own).  The records' table pointers are null: the vectors are the copies that are used
 struct GcmPhases {
     bool solar = false;                        // gcm_set_physics: solar_timestep as the second phase of every step
-    bool held_suarez = false;                  // gcm_set_held_suarez: the forcing as the last phase that changes the state
+    bool held_suarez = false;                  // gcm_set_held_suarez: the forcing behind the solar step
+    bool moist = false;                        // gcm_set_moist: condensation and evaporation as the last phase that changes the state
     gcm_physics phys{};                        // phys.utc is the clock: it advances by dt behind every solar step
     gcm_held_suarez hs{};
+    gcm_moist mo{};
     std::vector<double> phys_lat, phys_lon, hs_lat;
 };
 
@@ -148,7 +150,7 @@ extern "C" void step_rows(gcm_handle *h, double dt, int j0, int j1, hipStream_t 
 extern "C" void swap_state(gcm_handle *h);
 extern "C" int launch_status(gcm_handle *h);
 
-// gcm_pe.hip, for gcm_step and gcm_band_run: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, sample), each
+// gcm_pe.hip, for gcm_step and gcm_band_run: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, moist physics, sample), each
 // launched only if it is registered -- their tables before a run, a band's ghost rows on its second stream `ax` behind a
 // corrector's unpack, and the end of every step on the handle's stream over rows [-g, H + g), which joins `tail` before a sample
 extern "C" int pe_step(gcm_handle *h, int nsteps, double dt);        // gcm_step of a GCM_PE25D handle

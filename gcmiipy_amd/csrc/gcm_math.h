@@ -15,6 +15,7 @@ namespace gcm {
 
 constexpr double kG = 9.8;                    // constants.py:45
 constexpr double kRd = 287.0;                 // constants.py:16
+constexpr double kRv = 461.0;                 // constants.py:78
 constexpr double kCp = 1004.0;                // constants.py:22
 constexpr double kKappa = 287.0 / 1004.0;     // constants.py:28
 constexpr double kP0 = 100000.0;              // constants.py:31

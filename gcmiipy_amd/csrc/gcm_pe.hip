@@ -1,6 +1,6 @@
 // GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (solar step, Held-Suarez forcing,
-// climatology sample), written down once for gcm_step and gcm_band_run, and the entry points that serve GCM_PE25D handles
-// only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, climatology, the filter and the taps).
+// moist physics, climatology sample), written down once for gcm_step and gcm_band_run, and the entry points that serve GCM_PE25D handles
+// only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, moist physics, climatology, the filter and the taps).
 // Host code only: a guard and one forwarding call into the pe25d_* units, through gcm_handle.h and pe25d_kernels.h.
 #include <cmath>
 
@@ -10,19 +10,23 @@ using namespace gcm;
 
 // ------------------------------------------------------------------ the phases of a step
 // The order is the model's: the dynamics step, the solar step at the current clock, utc += dt, the Held-Suarez forcing,
-// the sample.  Each launch runs only if its phase is registered (GcmPhases; the climatology: pe25d_climate_due).
+// the moist physics, the sample.  Each launch runs only if its phase is registered (GcmPhases; the climatology: pe25d_climate_due).
 
 // gcm_set_physics: the radiation kernel's tables in place before a run queues anything (no-op without physics); then the
-// registered forcing's device tables for dt (none: GCM_OK)
+// registered forcing's device tables for dt (none: GCM_OK), and the moist physics' level tables and parameters for dt
 int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
     const GcmPhases &ph = h->phases;
     if (ph.solar)
         if (int rc = pe25d_physics_tables(h->pe, ph.phys.t_lw, ph.phys.t_sw, ph.phys_lat.data(), ph.phys_lon.data(), h->stream, &h->err))
             return rc;
-    if (!ph.held_suarez || nsteps <= 0) return GCM_OK;
-    gcm_held_suarez hs = ph.hs;
-    hs.lat = ph.hs_lat.data();
-    return pe25d_hs_tables(h->pe, &hs, dt, h->stream, &h->err);
+    if (nsteps <= 0) return GCM_OK;
+    if (ph.held_suarez) {
+        gcm_held_suarez hs = ph.hs;
+        hs.lat = ph.hs_lat.data();
+        if (int rc = pe25d_hs_tables(h->pe, &hs, dt, h->stream, &h->err)) return rc;
+    }
+    if (ph.moist) return pe25d_moist_tables(h->pe, &ph.mo, dt, &h->err);
+    return GCM_OK;
 }
 
 // gcm_band_run with the exchange on the second stream `ax`: the ghost rows' phases, behind a corrector's unpack.
@@ -43,7 +47,12 @@ int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax) {
     // locally (the neighbour's own inputs and tables, hence its own bits), behind the unpack and the ghost rows'
     // solar step in stream order and AHEAD of the ghost rows' column sums and anchors, which read u, v and theta
     // (the launch marks the state's column sums stale: pe25d_prep_ghost_rows then leaves them to the next stage)
-    if (ph.held_suarez) return pe25d_hs_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, ax, &h->err);
+    if (ph.held_suarez)
+        if (int rc = pe25d_hs_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, ax, &h->err)) return rc;
+    // gcm_set_moist: the ghost rows of theta and q, behind their Held-Suarez launch and ahead of their anchors, which
+    // read theta; column-local with the neighbour's own inputs, hence its own bits.  The precipitation of ghost rows
+    // belongs to the neighbour's sums: this launch accumulates nothing
+    if (ph.moist) return pe25d_moist_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, false, ax, &h->err);
     return GCM_OK;
 }
 
@@ -59,7 +68,7 @@ int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStre
         if (int rc = pe25d_solar_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, dt, ph.phys.utc, ph.phys.albedo, h->stream, &h->err)) return rc;
         ph.phys.utc += dt;
     }
-    // gcm_set_held_suarez: the last phase of the step that changes the state.  A band: own rows (and the ghost rows with
+    // gcm_set_held_suarez.  A band: own rows (and the ghost rows with
     // them where the exchange was joined into the compute stream), behind the corrector and the solar step: the compute
     // stream has waited for the edge rows' pack by then (update_interior), so the rows that left are unforced and the
     // neighbour forces them itself.  The launch writes u and v, which the next stage's chain B reads: it invalidates the
@@ -67,6 +76,10 @@ int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStre
     // own rows' u and v, follow this stream's position
     if (ph.held_suarez)
         if (int rc = pe25d_hs_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, h->stream, &h->err)) return rc;
+    // gcm_set_moist: the last phase of the step that changes the state, the same rows on the same stream; the own rows'
+    // precipitation and evaporation go to the handle's sums (the kernel adds rows [0, H) only)
+    if (ph.moist)
+        if (int rc = pe25d_moist_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, true, h->stream, &h->err)) return rc;
     // gcm_set_climate: a sample of the state the step leaves, behind every phase that changes it
     if (!pe25d_climate_due(h->pe)) return GCM_OK;
     // a band: the sample reads the own rows as the phases above left them on the compute stream, and row -1 of v,
@@ -274,6 +287,54 @@ int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs) {
 int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
                            double *fu, double *kt, double *s2, double *c2) {
     return held_suarez_tables(L, sig, nlat, lat, hs, dt, fu, kt, s2, c2, &gcm_create_error());
+}
+
+// ------------------------------------------------------------------ moist physics
+int gcm_set_moist(gcm_handle *h, const gcm_moist *mo) {
+    if (int rc = pe_only(h, "gcm_set_moist")) return rc;
+    if (mo)
+        if (int rc = moist_check(mo, "gcm_set_moist", &h->err)) return rc;
+    if (int rc = select_device(h)) return rc;
+    if (int rc = pe25d_set_moist(h->pe, mo != nullptr, h->stream, &h->err)) return rc;
+    h->phases.moist = mo != nullptr;
+    if (mo) h->phases.mo = *mo;
+    return GCM_OK;
+}
+
+int gcm_moist_on(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && h->phases.moist ? 1 : 0;
+}
+
+int gcm_moist_step(gcm_handle *h, double dt, const gcm_moist *mo) {
+    if (int rc = pe_only(h, "gcm_moist_step")) return rc;
+    if (int rc = moist_check(mo, "gcm_moist_step", &h->err)) return rc;
+    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_moist_step: dt must be finite");
+    if (int rc = select_device(h)) return rc;
+    if (int rc = pe25d_moist_tables(h->pe, mo, dt, &h->err)) return rc;
+    // a band: own rows and ghost rows, as gcm_held_suarez_step (the ghost rows of the current state must be current);
+    // the sums of the call go to the registration's accumulators, or nowhere
+    const int g = phase_ghosts(h);
+    return pe25d_moist_rows(h->pe, -1, -g, h->H + g, 0, 0, false, pe25d_moist_on(h->pe), h->stream, &h->err);
+}
+
+int gcm_get_moist(gcm_handle *h, double *precip, double *evap, double *seconds, int64_t *nsteps) {
+    if (int rc = pe_on_device(h, "gcm_get_moist")) return rc;
+    return pe25d_get_moist(h->pe, precip, evap, seconds, nsteps, h->stream, &h->err);
+}
+
+int gcm_put_moist(gcm_handle *h, const double *precip, const double *evap, double seconds, int64_t nsteps) {
+    if (int rc = pe_on_device(h, "gcm_put_moist")) return rc;
+    return pe25d_put_moist(h->pe, precip, evap, seconds, nsteps, h->stream, &h->err);
+}
+
+int gcm_moist_reset(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_moist_reset")) return rc;
+    return pe25d_moist_reset(h->pe, h->stream, &h->err);
+}
+
+int gcm_moist_saturation(int n, const double *T, const double *p_lev, double *q_s, double *dq_s, int *can) {
+    return moist_saturation_table(n, T, p_lev, q_s, dq_s, can, &gcm_create_error());
 }
 
 // ------------------------------------------------------------------ zonal-mean climatology

@@ -7,10 +7,11 @@
 //   pe25d_tracers.hip  the passive tracers' host side
 //   pe25d_held_suarez.hip  the Held-Suarez forcing: its table routine, its kernel and its launches
 //   pe25d_climate.hip  the zonal-mean climatology: its kernel, its sums and their way to the host and back
+//   pe25d_moist.hip    moist physics: the saturation routine, the kernel, its launches and its sums
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
 // gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
-// pe25d_hs_rows, pe25d_climate_due, pe25d_climate_sample).
+// pe25d_hs_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample).
 #pragma once
 #include "pe25d_kernels.h"
 
@@ -102,6 +103,17 @@ struct PeClimate {
     long long n = 0;                            // samples in the sums
 };
 
+// Moist physics (pe25d_moist.hip, gcm_set_moist): the float64 sums on the device with their two counters, the level
+// tables of the launches and the parameters of the launches that follow (pe25d_moist_tables)
+struct PeMoist {
+    double *acc = nullptr;                      // device: precip [H][W], evap [H][W]; non-null: registered
+    double seconds = 0.0;                       // sum of dt over the applications in the sums
+    long long n = 0;                            // applications in the sums
+    double *tab = nullptr;                      // device: sig [L], dsig [L], float64
+    int kb = 0;                                 // the level with the largest sig: the one the surface moistens
+    double lc = 0.0, x = 0.0, rh_s = 0.0, dt = 0.0;   // Lv / Cp, dt / tau_e (0: no evaporation), rh_s, dt
+};
+
 struct Pe25d {
     gcm_config cfg{};
     int W = 0, H = 0, L = 0, Hg = 0;
@@ -174,6 +186,7 @@ struct Pe25d {
     PeTracers tr;
     PeHeldSuarez hs;
     PeClimate clim;
+    PeMoist moist;
 };
 
 template <typename T> inline PeBufs<T> &bufs(Pe25d *m);

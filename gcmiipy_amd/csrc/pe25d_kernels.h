@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
+// pe25d_climate.hip, pe25d_moist.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +65,21 @@ int pe25d_climate_sample(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_climate_reset(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_get_climate(Pe25d *m, double *m3, double *m2, int64_t *nsamples, hipStream_t s, std::string *err);
 int pe25d_put_climate(Pe25d *m, const double *m3, const double *m2, int64_t nsamples, hipStream_t s, std::string *err);
+// Moist physics (pe25d_moist.hip).  moist_check / moist_saturation_table: no handle, no device (gcm_moist_saturation).
+// pe25d_set_moist: the sums allocated and zeroed (on) or freed; pe25d_moist_tables: the level tables in place (uploaded
+// once) and (mo, dt) as the parameters of the launches that follow; pe25d_moist_rows: the kernel over rows [j0, j1) and
+// [jb0, jb1) of state set `set` (-1: the current one) on `s`; keep_ghosts as for pe25d_solar_rows; accumulate: the own
+// rows' precipitation and evaporation go to the registered sums and the call counts as one application of dt
+int moist_check(const gcm_moist *mo, const char *fn, std::string *err);
+int moist_saturation_table(int n, const double *T, const double *p_lev, double *q_s, double *dq_s, int *can, std::string *err);
+int pe25d_set_moist(Pe25d *m, bool on, hipStream_t s, std::string *err);
+bool pe25d_moist_on(const Pe25d *m);
+int pe25d_moist_tables(Pe25d *m, const gcm_moist *mo, double dt, std::string *err);
+int pe25d_moist_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool accumulate, hipStream_t s,
+                     std::string *err);
+int pe25d_moist_reset(Pe25d *m, hipStream_t s, std::string *err);
+int pe25d_get_moist(Pe25d *m, double *precip, double *evap, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err);
+int pe25d_put_moist(Pe25d *m, const double *precip, const double *evap, double seconds, int64_t nsteps, hipStream_t s, std::string *err);
 int pe25d_new_state_set(const Pe25d *m);    // the set a corrector stage in flight writes (before the swap), else the current one
 int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err);
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan

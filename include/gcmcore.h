@@ -478,6 +478,73 @@ int gcm_held_suarez_on(const gcm_handle *h);
 int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs);
 int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
                            double *fu, double *kt, double *s2, double *c2);
+/* Moist physics of GCM_PE25D on the device: large-scale condensation of the specific humidity q with latent heating of
+ * theta and immediate precipitation (the saturation adjustment of Reed & Jablonowski's simple physics and of Thatcher &
+ * Jablonowski (2016)'s moist Held-Suarez test, on the model's own saturation formula), and optionally a moisture source
+ * at the level next to the surface.  One launch per step, fp64 and fp32 handles, single domains and latitude bands.
+ * The reference has nothing of the kind (its evaporation.py is empty, humidity.py serves the initial field only): this
+ * is an addition.  State: p [H][W] in Pa (surface pressure minus ptop), t = theta, q [L][H][W]; tables: sig[k], dsig[k].
+ * Constants: Rd = 287, Rv = 461, Cp = 1004, G = 9.8, P0 = 1e5, kappa = Rd / Cp are the model's own (constants.py); eps = Rd / Rv.
+ * Arithmetic per cell (k, j, i), float64 for either storage type, every operation rounded on its own (no contraction),
+ * the result rounded once to the storage type:
+ *   p_lev = sig[k] p + ptop;   Pi = (p_lev / P0)^kappa from the kernels' own Exner routine;   T = theta Pi
+ *   tc = T - 273.15;   a = 18.678 - tc / 234.5;   b = tc / (257.14 + tc)
+ *   e_s = (0.61121 * 1000.0) exp(a b)                      humidity.saturation_vapor_pressure, the Buck equation
+ *   the cell CAN SATURATE iff e_s < p_lev; then
+ *     den  = p_lev - (1 - eps) e_s;   q_s = (eps e_s) / den                      = humidity.rh_to_mmr(1, p_lev, T)
+ *     dlne = (a * 257.14) / (257.14 + tc)^2 - tc / (234.5 (257.14 + tc))         d ln e_s / dT
+ *     dq_s = (q_s (p_lev / den)) dlne                                            d q_s / dT at constant p_lev
+ *   otherwise (warm air at low pressure: the top levels of an isothermal column) both processes leave the cell alone.
+ *   Condensation, where the cell can saturate and q > q_s:
+ *     C = (q - q_s) / (1 + (Lv / Cp) dq_s);   q <- q - C;   theta <- theta + ((Lv / Cp) C) / Pi
+ *   One linearised step.  q_s is convex in T, so the step never overshoots: the cell ends at or just below saturation at
+ *   its new temperature.  The undershoot is of second order in the excess: for a cell that started 40 % supersaturated it is 3-5 %
+ *   of q_s at 300 K, 2-3 % at 285 K and under 0.3 % at 250 K; for one that started 0.1 % over, 4e-7 or less.  A second
+ *   application condenses nothing (float64).  Cells that do not condense are not
+ *   written.  Cp T + Lv q of the cell is unchanged.
+ *   Precipitation of the column, kg / m^2 per application:  P = sum_k C_k ((dsig[k] p) / G), k = 0, 1, .., L - 1 in that
+ *   order, from 0.0.  The condensate leaves the column at once.
+ *   Evaporation, only with tau_e > 0, on the one level kb with the largest sig (k = 0 in the product's geometries),
+ *   behind that level's condensation and with its updated T = theta_new Pi (theta_new in float64):
+ *     q_eq = rh_s q_s(T, p_lev);   x = dt / tau_e
+ *     where the cell can saturate and q_eq > q:  q_new = (q + x q_eq) / (1 + x);  E = (q_new - q) ((dsig[kb] p) / G);  q <- q_new
+ *   dt is taken as given: only a non-finite dt is refused, and the properties below are those of dt >= 0.
+ *   Backward Euler and one-sided: q never exceeds q_eq and never decreases.  The heat comes from the surface: theta is
+ *   not changed.  p, u, v, the tracers and the ground temperature are untouched.
+ * Accumulators in the handle, allocated by gcm_set_moist, own rows only: precip [H][W] and evap [H][W], float64, kg / m^2;
+ * seconds (the sum of dt) and nsteps.  One writer per word and launch, no atomics: the same state gives the same bits,
+ * and a band's rows hold the bits of the same rows of the single domain.
+ * gcm_set_moist: the phase as part of every step taken by gcm_step and gcm_band_run: the Matsuno step, solar_timestep
+ * where gcm_set_physics is on, the Held-Suarez forcing where registered, then this, then the climatology's sample.
+ * gcm_half_step and gcm_step_phase never apply it.  On a latitude band the ghost rows of theta and q that the
+ * post-corrector exchange delivers are adjusted LOCALLY (column-local kernel, the neighbour's own inputs, the neighbour's
+ * own bits) and add to no sum; the packed edge rows leave unadjusted: no third exchange, the message format and
+ * gcm_halo_bytes are unchanged.  NULL switches the phase off and frees the accumulators; registering again resets them.
+ * Without a registration nothing is launched and every result and timing is as before.
+ * gcm_moist_on: 1 where the phase is registered, else 0 (other models: 0; a null handle GCM_ERR_ARG).
+ * gcm_moist_step: the same kernel once, in place on the current state (what gcm_held_suarez_step is to
+ * gcm_set_held_suarez).  With a registration it adds to the accumulators, to seconds and to nsteps; without one the sums
+ * of the call are dropped.  On a band it covers own rows and ghost rows: the ghost rows must be current.
+ * gcm_get_moist synchronises the handle's stream once; any pointer may be NULL.  gcm_put_moist uploads sums and counters
+ * (restarts): both arrays are required, seconds finite and >= 0, nsteps >= 0.  gcm_moist_reset zeroes all four.
+ * gcm_moist_saturation: the saturation routine above on its own, on the host, without a handle or a device -- the one
+ * routine the kernel calls, compiled for the host.  q_s, dq_s, can [n], any of them may be NULL; where can = 0, q_s and
+ * dq_s are 0.
+ * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, a non-finite parameter,
+ * Lv <= 0, tau_e < 0, rh_s outside (0, 1], a non-finite dt.  GCM_ERR_UNSUPPORTED: other models.  GCM_ERR_STATE: get,
+ * put or reset without a registration.                                                                           */
+typedef struct {
+    double Lv;                   /* J / kg: latent heat of vaporisation (2.5e6)                 */
+    double tau_e;                /* s: evaporation time scale; 0: no evaporation                */
+    double rh_s;                 /* target relative humidity of the lowest level, (0, 1]        */
+} gcm_moist;
+int gcm_set_moist(gcm_handle *h, const gcm_moist *mo);
+int gcm_moist_on(const gcm_handle *h);
+int gcm_moist_step(gcm_handle *h, double dt, const gcm_moist *mo);
+int gcm_get_moist(gcm_handle *h, double *precip, double *evap, double *seconds, int64_t *nsteps);
+int gcm_put_moist(gcm_handle *h, const double *precip, const double *evap, double seconds, int64_t nsteps);
+int gcm_moist_reset(gcm_handle *h);
+int gcm_moist_saturation(int n, const double *T, const double *p_lev, double *q_s, double *dq_s, int *can);
 /* Zonal-mean climatology of GCM_PE25D accumulated on the device: what a Held-Suarez run is evaluated by -- the time and
  * zonal means of u, v, theta and T, their variances and the eddy fluxes as functions of latitude and level -- without a
  * host round trip per step (fp64 and fp32 handles, single domains and latitude bands).  One launch per sample reads
