@@ -13,7 +13,8 @@ Importing the package loads the library and raises ImportError if it is not
 built: nothing here computes on the CPU.
 """
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
-from .core import Climate, Core, GcmError, Moist, TracerStats, device_count, held_suarez_tables, moist_saturation  # noqa: F401
+from .core import (Climate, Convect, Core, GcmError, Moist, TracerStats, convect_columns, device_count,  # noqa: F401
+                   held_suarez_tables, moist_saturation)
 
 
 
@@ -26,5 +27,5 @@ def clear_cache():
     _lib.lib.gcm_ops_release_scratch()      # the operator entry points' device scratch of this thread
 
 
-__all__ = ["Climate", "Core", "GcmError", "Moist", "TracerStats", "device_count", "clear_cache", "held_suarez_tables",
-           "moist_saturation"]
+__all__ = ["Climate", "Convect", "Core", "GcmError", "Moist", "TracerStats", "convect_columns", "device_count",
+           "clear_cache", "held_suarez_tables", "moist_saturation"]

@@ -86,6 +86,11 @@ class Moist(C.Structure):
     _fields_ = [("Lv", C.c_double), ("tau_e", C.c_double), ("rh_s", C.c_double)]
 
 
+class Convect(C.Structure):
+    """gcm_convect of include/gcmcore.h"""
+    _fields_ = [("kappa_c", C.c_double), ("mix_q", C.c_int32)]
+
+
 class TracerForcing(C.Structure):
     """gcm_tracer_forcing of include/gcmcore.h"""
     _fields_ = [("source", C.c_double), ("decay", C.c_double), ("pin_value", C.c_double),
@@ -137,6 +142,13 @@ SYMBOLS = {
     "gcm_put_moist": (C.c_int, [_H, _dp, _dp, C.c_double, C.c_int64]),
     "gcm_moist_reset": (C.c_int, [_H]),
     "gcm_moist_saturation": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    "gcm_set_convect": (C.c_int, [_H, C.POINTER(Convect)]),
+    "gcm_convect_on": (C.c_int, [_H]),
+    "gcm_convect_step": (C.c_int, [_H, C.POINTER(Convect)]),
+    "gcm_get_convect": (C.c_int, [_H, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "gcm_put_convect": (C.c_int, [_H, _dp, _dp, C.c_double, C.c_int64]),
+    "gcm_convect_reset": (C.c_int, [_H]),
+    "gcm_convect_columns": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, C.POINTER(C.c_int32)]),
     "gcm_set_climate": (C.c_int, [_H, C.c_int]),
     "gcm_climate_every": (C.c_int, [_H]),
     "gcm_climate_sample": (C.c_int, [_H]),

@@ -228,6 +228,21 @@ def merge_moist(parts):
                  np.concatenate([m.evap for m in parts], axis=0))
 
 
+def merge_convect(parts):
+    """the convective adjustment's sums of the whole domain from its bands': `parts` are the bands' Convect records
+    (Core.convect_sums) in row order; the rows are concatenated.  ValueError where nsteps or seconds differ"""
+    import numpy as np
+    from .core import Convect
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_convect: no records")
+    if any(m.nsteps != parts[0].nsteps or m.seconds != parts[0].seconds for m in parts):
+        raise ValueError("merge_convect: the bands hold %s applications over %s seconds"
+                         % (", ".join(str(m.nsteps) for m in parts), ", ".join(repr(m.seconds) for m in parts)))
+    return Convect(parts[0].nsteps, parts[0].seconds, np.concatenate([m.count for m in parts], axis=0),
+                   np.concatenate([m.levels for m in parts], axis=0))
+
+
 class LoopbackExchange:
     """Diagnostic stand-in for torch.distributed inside BandRunner: every send lands in the
     matching receive buffer of the SAME rank (a device-local copy on the comm stream).  The band
@@ -323,6 +338,14 @@ class HipBandEngine:
         self.c.set_held_suarez(geom, **params)
         self._hs = None if geom is None else (geom, dict(params))
 
+    def set_convect(self, *off, **params):
+        """the convective adjustment after every dynamics step, behind the Held-Suarez forcing and ahead of the moist
+        physics (Core.set_convect; every band of a run registers the same): inside the library's gcm_band_run, or from
+        physics_step() when the host drives the exchange.  set_convect(None) switches it off.  merge_convect() puts the
+        bands' sums together"""
+        self.c.set_convect(*off, **params)
+        self._convect = None if off else dict(params)
+
     def set_moist(self, *off, **params):
         """the moist physics after every dynamics step, behind the Held-Suarez forcing (Core.set_moist; every band of a
         run registers the same): inside the library's gcm_band_run, or from physics_step() when the host drives the
@@ -339,7 +362,8 @@ class HipBandEngine:
 
     def physics_step(self, dt):
         """host-driven band step: own rows and ghost rows by one gcm_solar_step on the compute stream, behind the
-        unpack of the post-corrector exchange; then, likewise, the Held-Suarez forcing and the moist physics; then the climatology's sample
+        unpack of the post-corrector exchange; then, likewise, the Held-Suarez forcing, the convective adjustment and the moist physics
+        (the explicit calls: the adjustment's counts add up, its seconds do not); then the climatology's sample
         where this step is due one"""
         ph = getattr(self, "_phys", None)
         if ph is not None:
@@ -348,6 +372,9 @@ class HipBandEngine:
         hs = getattr(self, "_hs", None)
         if hs is not None:
             self.c.held_suarez_step(hs[0], dt, **hs[1])
+        cv = getattr(self, "_convect", None)
+        if cv is not None:
+            self.c.convect_step(**cv)
         mo = getattr(self, "_moist", None)
         if mo is not None:
             self.c.moist_step(dt, **mo)

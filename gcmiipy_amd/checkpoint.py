@@ -16,14 +16,16 @@ stored as "climate_every", "climate_n", "climate_m3" and "climate_m2", the inter
 float64 sums, registered and uploaded again on restore; files without these keys restore without a climatology; the
 moist physics, Core.set_moist, is stored as "moist", its three parameters in the order of core.MOIST_DEFAULTS, with
 "moist_n", "moist_seconds", "moist_precip" and "moist_evap", the count, the seconds and the raw float64 sums, registered
-and uploaded again on restore; files without these keys restore with none)
+and uploaded again on restore; files without these keys restore with none; the convective adjustment, Core.set_convect,
+is stored as "convect", its two parameters in the order of core.CONVECT_DEFAULTS, with "convect_n", "convect_seconds",
+"convect_count" and "convect_levels", saved and restored the same way)
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
 import numpy as np
 
 from . import _lib
-from .core import Core, GcmError, HELD_SUAREZ_DEFAULTS, MOIST_DEFAULTS
+from .core import CONVECT_DEFAULTS, Core, GcmError, HELD_SUAREZ_DEFAULTS, MOIST_DEFAULTS
 from .geometry import Geom
 
 _GEOM_KEYS = ("sige", "sigt", "sigb", "dsig", "sig", "dsigv", "dx_j", "dx_h", "dy", "ptop",
@@ -65,6 +67,14 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
         sums = core.moist_sums()
         out.update(moist=np.asarray([mo[k] for k in MOIST_DEFAULTS], dtype=np.float64), moist_n=np.int64(sums.nsteps),
                    moist_seconds=np.float64(sums.seconds), moist_precip=sums.precip, moist_evap=sums.evap)
+    cv = getattr(core, "convect", None) if core.model == _lib.PE25D else None
+    if cv is None and core.model == _lib.PE25D and getattr(core, "convect_registered", False):
+        raise GcmError("checkpoint.save: the handle's convective adjustment was registered through gcm_set_convect directly; its "
+                       "parameters are unknown here and the phase and its sums would be lost (register with Core.set_convect)")
+    if cv is not None:
+        sums = core.convect_sums()
+        out.update(convect=np.asarray([cv[k] for k in CONVECT_DEFAULTS], dtype=np.float64), convect_n=np.int64(sums.nsteps),
+                   convect_seconds=np.float64(sums.seconds), convect_count=sums.count, convect_levels=sums.levels)
     for k, a in zip("puvtq", (p, u, v, t, q)):
         if a is not None:
             out["state_" + k] = a
@@ -78,9 +88,10 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, held_suarez, climate, moist); ground and tracers are None where the file has none, tracer_forcing
+    tracer_mixing, held_suarez, climate, moist, convect); ground and tracers are None where the file has none, tracer_forcing
     {i: dict(...)} and tracer_mixing {i: K} are then empty; held_suarez is (parameters dict, lat) or None; climate is
-    dict(every, n, m3, m2) or None; moist is dict(params, n, seconds, precip, evap) or None"""
+    dict(every, n, m3, m2) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
+    dict(params, n, seconds, count, levels) or None"""
     d = np.load(path, allow_pickle=False)
     L, H, W = (int(x) for x in d["shape"])
     state = {k: d["state_" + k] for k in "puvtq" if "state_" + k in d.files}
@@ -118,8 +129,13 @@ def load(path):
     if "moist" in d.files:
         moist = dict(params=dict(zip(MOIST_DEFAULTS, (float(x) for x in d["moist"]))), n=int(d["moist_n"]),
                      seconds=float(d["moist_seconds"]), precip=d["moist_precip"], evap=d["moist_evap"])
+    convect = None
+    if "convect" in d.files:
+        kc, mq = (float(x) for x in d["convect"])
+        convect = dict(params=dict(zip(CONVECT_DEFAULTS, (kc, int(mq)))), n=int(d["convect_n"]),
+                       seconds=float(d["convect_seconds"]), count=d["convect_count"], levels=d["convect_levels"])
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, climate=clim,
-                moist=moist,
+                moist=moist, convect=convect,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
@@ -150,6 +166,9 @@ def restore(path, **core_kwargs):
     if ck["climate"] is not None:
         core.set_climate(ck["climate"]["every"])
         core.put_climate(ck["climate"]["n"], ck["climate"]["m3"], ck["climate"]["m2"])
+    if ck["convect"] is not None:
+        core.set_convect(**ck["convect"]["params"])
+        core.put_convect(ck["convect"]["n"], ck["convect"]["seconds"], ck["convect"]["count"], ck["convect"]["levels"])
     if ck["moist"] is not None:
         core.set_moist(**ck["moist"]["params"])
         core.put_moist(ck["moist"]["n"], ck["moist"]["seconds"], ck["moist"]["precip"], ck["moist"]["evap"])

@@ -226,6 +226,70 @@ def moist_saturation(T, p_lev):
     return qs.reshape(T.shape), dqs.reshape(T.shape), can.reshape(T.shape).astype(bool)
 
 
+# the parameters of the convective adjustment (gcm_convect), in the struct's order: kappa_c = Rd gamma / g of the neutral
+# profile (0: dry adjustment, neutral where theta is constant) and whether q of a merged block is mixed
+CONVECT_DEFAULTS = collections.OrderedDict(kappa_c=0.0, mix_q=1)
+CONVECT_RD, CONVECT_G = 287.0, 9.8              # constants.py: what turns a lapse rate gamma (K / m) into kappa_c
+
+
+def convect_params(params):
+    """the two parameters of the convective adjustment as a dict (kappa_c float, mix_q 0 or 1): CONVECT_DEFAULTS with
+    `params` laid over them.  params: at most one of gamma (the critical lapse rate, K / m: kappa_c = Rd gamma / g) and
+    kappa_c, neither means the dry adjustment; mix_q.  ValueError for a name that is not a parameter, and for gamma
+    given together with kappa_c"""
+    unknown = sorted(set(params) - {"gamma", "kappa_c", "mix_q"})
+    if unknown:
+        raise ValueError("convect: unknown parameter(s) %s; the parameters are gamma or kappa_c, and mix_q" % ", ".join(unknown))
+    gamma, kappa_c = params.get("gamma"), params.get("kappa_c")
+    if gamma is not None and kappa_c is not None:
+        raise ValueError("convect: give gamma or kappa_c, not both")
+    out = collections.OrderedDict(CONVECT_DEFAULTS)
+    if gamma is not None:
+        out["kappa_c"] = CONVECT_RD * float(gamma) / CONVECT_G
+    elif kappa_c is not None:
+        out["kappa_c"] = float(kappa_c)
+    if "mix_q" in params:
+        if params["mix_q"] not in (0, 1, False, True):
+            raise ValueError("convect: mix_q must be 0 or 1")
+        out["mix_q"] = int(params["mix_q"])
+    return out
+
+
+class Convect(collections.namedtuple("Convect", "nsteps seconds count levels")):
+    """the sums of a GCM_PE25D handle's convective adjustment (Core.convect_sums): the applications counted, the sum of
+    the registered steps' dt in seconds, and per column (H, W), float64, in how many applications the column was adjusted
+    (count) and the levels its merged blocks held, summed over them (levels).  A band: its own rows
+    (bands.merge_convect)"""
+    __slots__ = ()
+
+    @property
+    def frequency(self):
+        """count / nsteps: the share of the applications in which a column was adjusted; ValueError where nsteps == 0"""
+        if self.nsteps == 0:
+            raise ValueError("Convect: no application counted (nsteps == 0)")
+        return self.count / self.nsteps
+
+    @property
+    def mean_depth(self):
+        """levels / max(count, 1): the mean number of levels adjusted when the column was adjusted, 0 where never"""
+        return self.levels / np.maximum(self.count, 1.0)
+
+
+def convect_columns(y, w, q, dsig, mix_q=True):
+    """the pooling of the convective adjustment (gcm_convect_columns; the host build of the one routine the kernel
+    calls, no handle, no device) over columns y, w, q of shape (..., L), level 0 the bottom, with dsig (L,)
+    -> (y_out, q_out, nblock): the adjusted y and q and, per level, the size of its block (int32)"""
+    y = np.asarray(y, dtype=np.float64)
+    L = y.shape[-1] if y.ndim else 0
+    yy = as_f64(y.reshape(-1, L) if L else y, name="y")
+    ww, qq = (as_f64(a, y.shape, n).reshape(yy.shape) for a, n in ((w, "w"), (q, "q")))
+    dd = as_f64(dsig, (L,), "dsig")
+    yo, qo, nb = np.empty_like(yy), np.empty_like(yy), np.empty(yy.shape, dtype=np.int32)
+    _check(lib.gcm_convect_columns(yy.shape[0], L, _tab(yy), _tab(ww), _tab(qq), _tab(dd), int(bool(mix_q)), _tab(yo), _tab(qo),
+                                   nb.ctypes.data_as(C.POINTER(C.c_int32))))
+    return yo.reshape(y.shape), qo.reshape(y.shape), nb.reshape(y.shape)
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -280,6 +344,7 @@ class Core:
         self._mixing = {}                       # tracer -> the profile K registered (set_tracer_mixing)
         self._held_suarez = None                # the parameters and latitudes registered (set_held_suarez)
         self._moist = None                      # the parameters registered (set_moist)
+        self._convect = None                    # the parameters registered (set_convect)
         cfg = _lib.Config()
         cfg.abi_version = _lib.ABI_VERSION
         cfg.model = model
@@ -706,13 +771,75 @@ class Core:
         """the latitudes (global_height,) the registered Held-Suarez forcing was given, or None"""
         return self._held_suarez[1].copy() if self.held_suarez is not None else None
 
+    # -- convective adjustment (GCM_PE25D) -------------------------------------------------
+    def set_convect(self, *off, **params):
+        """every step of step() / band_run() from now on adjusts statically unstable columns on the device
+        (gcm_set_convect): theta, and with mix_q also q, of every unstable stretch of a column is mixed to the neutral
+        profile at constant column enthalpy and water -- behind the Held-Suarez forcing and ahead of the moist physics.
+        half_step never applies it.  params: gamma, the critical lapse rate in K / m (6.5e-3: Manabe-Strickler), or
+        kappa_c = Rd gamma / g, at most one of the two, neither: the dry adjustment; mix_q (True).  How often and how
+        deep each column was adjusted is accumulated (convect_sums); registering again resets the sums.
+        set_convect(None) switches the phase off.  ValueError for a refused parameter (the call then changes nothing)"""
+        if off:
+            if off != (None,) or params:
+                raise ValueError("set_convect takes keyword parameters, or None alone to switch the phase off")
+            _check(lib.gcm_set_convect(self._h, None), self._h)
+            self._convect = None
+            return
+        par = convect_params(params)
+        rec = _lib.Convect(*par.values())
+        _check(lib.gcm_set_convect(self._h, C.byref(rec)), self._h)
+        self._convect = dict(par)
+
+    @property
+    def convect(self):
+        """the parameters of the registered convective adjustment as a dict (kappa_c, mix_q), or None where the handle
+        carries none (gcm_convect_on) -- and also None for one registered through the C call directly"""
+        on = lib.gcm_convect_on(self._h)
+        if on < 0:
+            _check(on, self._h)
+        return dict(self._convect) if on and self._convect else None
+
+    @property
+    def convect_registered(self):
+        """whether the handle carries the phase at all (gcm_convect_on), whoever registered it"""
+        on = lib.gcm_convect_on(self._h)
+        if on < 0:
+            _check(on, self._h)
+        return bool(on)
+
+    def convect_step(self, **params):
+        """the convective adjustment once, in place on the current state (gcm_convect_step); no dt: the adjustment is
+        instantaneous.  With a registration the call adds to its counts (and no seconds), without one the counts of the
+        call are dropped.  A band: own rows and ghost rows, the ghost rows must be current"""
+        rec = _lib.Convect(*convect_params(params).values())
+        _check(lib.gcm_convect_step(self._h, C.byref(rec)), self._h)
+
+    def convect_sums(self):
+        """-> Convect(nsteps, seconds, count (H, W), levels (H, W)): the float64 sums as the device holds them
+        (gcm_get_convect); one synchronisation.  GcmError where no convective adjustment is registered"""
+        count, levels = np.empty((self.H, self.W)), np.empty((self.H, self.W))
+        sec, n = C.c_double(), C.c_int64()
+        _check(lib.gcm_get_convect(self._h, _tab(count), _tab(levels), C.byref(sec), C.byref(n)), self._h)
+        return Convect(int(n.value), float(sec.value), count, levels)
+
+    def put_convect(self, nsteps, seconds, count, levels):
+        """upload sums taken by convect_sums() (gcm_put_convect): a restart goes on where the run stopped"""
+        count = as_f64(count, (self.H, self.W), "count")
+        levels = as_f64(levels, (self.H, self.W), "levels")
+        _check(lib.gcm_put_convect(self._h, _tab(count), _tab(levels), float(seconds), int(nsteps)), self._h)
+
+    def convect_reset(self):
+        """zero the sums, the seconds and the count (gcm_convect_reset)"""
+        _check(lib.gcm_convect_reset(self._h), self._h)
+
     # -- moist physics (GCM_PE25D) ---------------------------------------------------------
     def set_moist(self, *off, **params):
         """every step of step() / band_run() from now on ends with the moist physics on the device: q in excess of
         saturation condenses, the latent heat warms theta, the condensate leaves the column as precipitation, and with
         tau_e > 0 the lowest level is moistened towards the relative humidity rh_s (gcm_set_moist) -- the Matsuno step,
-        solar_timestep where set_physics is on, the Held-Suarez forcing where registered, then this, then the
-        climatology's sample.  half_step never applies it.  params: Lv (J / kg), tau_e (s, 0: no evaporation), rh_s
+        solar_timestep where set_physics is on, the Held-Suarez forcing and the convective adjustment where registered,
+        then this, then the climatology's sample.  half_step never applies it.  params: Lv (J / kg), tau_e (s, 0: no evaporation), rh_s
         (MOIST_DEFAULTS).  Precipitation and evaporation are accumulated per column (moist_sums); registering again
         resets the sums.  set_moist(None) switches the phase off.  ValueError for a refused parameter (the call then
         changes nothing)"""

@@ -38,10 +38,12 @@ struct GcmTiming {
 struct GcmPhases {
     bool solar = false;                        // gcm_set_physics: solar_timestep as the second phase of every step
     bool held_suarez = false;                  // gcm_set_held_suarez: the forcing behind the solar step
+    bool convect = false;                      // gcm_set_convect: convective adjustment behind the forcing, ahead of the moist physics
     bool moist = false;                        // gcm_set_moist: condensation and evaporation as the last phase that changes the state
     gcm_physics phys{};                        // phys.utc is the clock: it advances by dt behind every solar step
     gcm_held_suarez hs{};
     gcm_moist mo{};
+    gcm_convect cv{};
     std::vector<double> phys_lat, phys_lon, hs_lat;
 };
 
@@ -150,7 +152,7 @@ extern "C" void step_rows(gcm_handle *h, double dt, int j0, int j1, hipStream_t 
 extern "C" void swap_state(gcm_handle *h);
 extern "C" int launch_status(gcm_handle *h);
 
-// gcm_pe.hip, for gcm_step and gcm_band_run: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, moist physics, sample), each
+// gcm_pe.hip, for gcm_step and gcm_band_run: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, convective adjustment, moist physics, sample), each
 // launched only if it is registered -- their tables before a run, a band's ghost rows on its second stream `ax` behind a
 // corrector's unpack, and the end of every step on the handle's stream over rows [-g, H + g), which joins `tail` before a sample
 extern "C" int pe_step(gcm_handle *h, int nsteps, double dt);        // gcm_step of a GCM_PE25D handle

@@ -1,6 +1,6 @@
 // GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (solar step, Held-Suarez forcing,
-// moist physics, climatology sample), written down once for gcm_step and gcm_band_run, and the entry points that serve GCM_PE25D handles
-// only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, moist physics, climatology, the filter and the taps).
+// convective adjustment, moist physics, climatology sample), written down once for gcm_step and gcm_band_run, and the entry points that serve GCM_PE25D handles
+// only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, convective adjustment, moist physics, climatology, the filter and the taps).
 // Host code only: a guard and one forwarding call into the pe25d_* units, through gcm_handle.h and pe25d_kernels.h.
 #include <cmath>
 
@@ -10,10 +10,10 @@ using namespace gcm;
 
 // ------------------------------------------------------------------ the phases of a step
 // The order is the model's: the dynamics step, the solar step at the current clock, utc += dt, the Held-Suarez forcing,
-// the moist physics, the sample.  Each launch runs only if its phase is registered (GcmPhases; the climatology: pe25d_climate_due).
+// the convective adjustment, the moist physics, the sample.  Each launch runs only if its phase is registered (GcmPhases; the climatology: pe25d_climate_due).
 
 // gcm_set_physics: the radiation kernel's tables in place before a run queues anything (no-op without physics); then the
-// registered forcing's device tables for dt (none: GCM_OK), and the moist physics' level tables and parameters for dt
+// registered forcing's device tables for dt (none: GCM_OK), and the convective adjustment's and the moist physics' level tables and parameters for dt
 int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
     const GcmPhases &ph = h->phases;
     if (ph.solar)
@@ -25,6 +25,8 @@ int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
         hs.lat = ph.hs_lat.data();
         if (int rc = pe25d_hs_tables(h->pe, &hs, dt, h->stream, &h->err)) return rc;
     }
+    if (ph.convect)
+        if (int rc = pe25d_convect_tables(h->pe, &ph.cv, dt, &h->err)) return rc;
     if (ph.moist) return pe25d_moist_tables(h->pe, &ph.mo, dt, &h->err);
     return GCM_OK;
 }
@@ -49,6 +51,11 @@ int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax) {
     // (the launch marks the state's column sums stale: pe25d_prep_ghost_rows then leaves them to the next stage)
     if (ph.held_suarez)
         if (int rc = pe25d_hs_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, ax, &h->err)) return rc;
+    // gcm_set_convect: the ghost rows of theta and q, behind their Held-Suarez launch and ahead of their moist physics and
+    // of their anchors, which read theta; column-local with the neighbour's own inputs, hence its own bits.  The counts
+    // of ghost rows belong to the neighbour's sums: this launch accumulates nothing
+    if (ph.convect)
+        if (int rc = pe25d_convect_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, false, ax, &h->err)) return rc;
     // gcm_set_moist: the ghost rows of theta and q, behind their Held-Suarez launch and ahead of their anchors, which
     // read theta; column-local with the neighbour's own inputs, hence its own bits.  The precipitation of ghost rows
     // belongs to the neighbour's sums: this launch accumulates nothing
@@ -76,6 +83,10 @@ int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStre
     // own rows' u and v, follow this stream's position
     if (ph.held_suarez)
         if (int rc = pe25d_hs_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, h->stream, &h->err)) return rc;
+    // gcm_set_convect: the same rows on the same stream, ahead of the moist physics, which then condenses whatever the
+    // mixing left supersaturated; the own rows' counts go to the handle's sums (the kernel adds rows [0, H) only)
+    if (ph.convect)
+        if (int rc = pe25d_convect_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, true, h->stream, &h->err)) return rc;
     // gcm_set_moist: the last phase of the step that changes the state, the same rows on the same stream; the own rows'
     // precipitation and evaporation go to the handle's sums (the kernel adds rows [0, H) only)
     if (ph.moist)
@@ -287,6 +298,55 @@ int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs) {
 int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
                            double *fu, double *kt, double *s2, double *c2) {
     return held_suarez_tables(L, sig, nlat, lat, hs, dt, fu, kt, s2, c2, &gcm_create_error());
+}
+
+// ------------------------------------------------------------------ convective adjustment
+int gcm_set_convect(gcm_handle *h, const gcm_convect *cv) {
+    if (int rc = pe_only(h, "gcm_set_convect")) return rc;
+    if (cv)
+        if (int rc = convect_check(cv, "gcm_set_convect", &h->err)) return rc;
+    if (int rc = select_device(h)) return rc;
+    if (int rc = pe25d_set_convect(h->pe, cv != nullptr, h->stream, &h->err)) return rc;
+    h->phases.convect = cv != nullptr;
+    if (cv) h->phases.cv = *cv;
+    return GCM_OK;
+}
+
+int gcm_convect_on(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && h->phases.convect ? 1 : 0;
+}
+
+int gcm_convect_step(gcm_handle *h, const gcm_convect *cv) {
+    if (int rc = pe_only(h, "gcm_convect_step")) return rc;
+    if (int rc = convect_check(cv, "gcm_convect_step", &h->err)) return rc;
+    if (int rc = select_device(h)) return rc;
+    // (the adjustment is instantaneous: the call adds no seconds)
+    if (int rc = pe25d_convect_tables(h->pe, cv, 0.0, &h->err)) return rc;
+    // a band: own rows and ghost rows, as gcm_moist_step (the ghost rows of the current state must be current); the
+    // counts of the call go to the registration's accumulators, or nowhere
+    const int g = phase_ghosts(h);
+    return pe25d_convect_rows(h->pe, -1, -g, h->H + g, 0, 0, false, pe25d_convect_on(h->pe), h->stream, &h->err);
+}
+
+int gcm_get_convect(gcm_handle *h, double *count, double *levels, double *seconds, int64_t *nsteps) {
+    if (int rc = pe_on_device(h, "gcm_get_convect")) return rc;
+    return pe25d_get_convect(h->pe, count, levels, seconds, nsteps, h->stream, &h->err);
+}
+
+int gcm_put_convect(gcm_handle *h, const double *count, const double *levels, double seconds, int64_t nsteps) {
+    if (int rc = pe_on_device(h, "gcm_put_convect")) return rc;
+    return pe25d_put_convect(h->pe, count, levels, seconds, nsteps, h->stream, &h->err);
+}
+
+int gcm_convect_reset(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_convect_reset")) return rc;
+    return pe25d_convect_reset(h->pe, h->stream, &h->err);
+}
+
+int gcm_convect_columns(int ncol, int L, const double *y, const double *w, const double *q, const double *dsig, int mix_q,
+                        double *y_out, double *q_out, int32_t *nblock) {
+    return convect_columns(ncol, L, y, w, q, dsig, mix_q, y_out, q_out, nblock, &gcm_create_error());
 }
 
 // ------------------------------------------------------------------ moist physics

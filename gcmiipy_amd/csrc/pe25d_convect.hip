@@ -1,0 +1,416 @@
+// GCM_PE25D, convective adjustment (gcm_set_convect, gcm_convect_step): every column's theta, and optionally q, is mixed
+// wherever it is statically unstable against a neutral profile, conserving the column's enthalpy and water; one launch
+// per step behind the Held-Suarez forcing and ahead of the moist physics.  The contract: include/gcmcore.h.
+//
+//   per cell (device, float64 for either storage type, rounded once to it; level k = 0 is the bottom):
+//     p_lev = sig[k] p + ptop;  Pi = (p_lev / P0)^kappa (exner());  r = 1 (kappa_c = 0: dry), else
+//     r = exp((kappa_c - kappa) log(p_lev / P0));  y = theta / r (dry: theta itself);  w = (Pi r) dsig[k]
+//   per column, pool adjacent violators from the bottom up (convect_push, host and device: one routine):
+//     k = 0 .. L - 1: push the block (S = w y, Wt = w, Qs = q dsig[k], D = dsig[k], n = 1, value = y); while there is a
+//     block below and value < below.value (strict; a NaN compares false) the two become one: S = below.S + S, likewise
+//     Wt, Qs, D, n, in that operand order, then value = S / Wt
+//     every level of a block with n > 1:  theta <- value r (dry: value);  mix_q: q <- Qs / D.  n = 1: not written
+//   per own column: count += 1 where the column had a merged block, levels += sum of n over its merged blocks
+//
+// Both loops are bounded by L: a push merges at most the blocks there are.  This is the weighted isotonic regression
+// of y, the exact limit of the pairwise adjustment: no iteration count, no tolerance.  sum_k y w = sum_k T dsig and
+// sum_k q dsig are conserved to rounding.
+//
+// Every operation is rounded on its own: contraction is off for the whole file (the Makefile builds it with
+// -ffp-contract=fast-honor-pragmas), host and device, so that a column gets the same bits whichever launch -- a single
+// domain's, a band's own rows', a neighbour's ghost rows' -- produces it, and the host probe gcm_convect_columns runs
+// the very routine the kernel calls.
+//
+// The state's layout is [j][k][i]: one lane owns the column (j, i), a workgroup is one wave, 64 consecutive i of one
+// row, so the request of a level is one contiguous run.
+//   pass 1, registers only: the column is marched kCvBatch levels at a time; y and a running "some y[k] < y[k - 1]".
+//     A column has a merged block iff that holds.  Most columns are stable at most steps: a wave with no unstable lane
+//     returns here (__any), having read p and theta once, and written nothing.
+//   pass 2, waves with an unstable lane: the column is marched again (its lines are still in L2), now with q, Pi and w,
+//     and pooled with the block stack in LDS, slot-major ([slot][lane]: a wave's access to a slot is 64 consecutive
+//     words, conflict-free).  A runtime-indexed private array would go to scratch.  Stable lanes of the wave pool too
+//     (they only push) and write nothing.  The Exner table is loaded into LDS here, not before: pass 1 needs none.
+// LDS of a workgroup: the 2 KB Exner table and 44 bytes per level and lane (five doubles and a count), sized from L at
+// launch: 69.6 KB at L = 24 (two workgroups share a CU), 112 KB at L = 40, 160 KB hold L = 57.
+#pragma clang fp contract(off)
+#include "pe25d_host.h"
+
+namespace gcm {
+
+// ---------------------------------------------------------------- the pooling (host and device: one routine)
+// A stack `St` offers S, Wt, Qs, D, val (double &) and n (int &) of slot b; `top` blocks are on it.  The new level's
+// block is kept in registers while it absorbs the blocks below it and is stored once.  -> the new number of blocks
+template <class St>
+__host__ __device__ inline int convect_push(St &st, int top, double y, double w, double q, double d) {
+    double S = w * y, Wt = w, Qs = q * d, D = d, val = y;
+    int n = 1;
+    while (top > 0 && val < st.val(top - 1)) {
+        --top;
+        S = st.S(top) + S;
+        Wt = st.Wt(top) + Wt;
+        Qs = st.Qs(top) + Qs;
+        D = st.D(top) + D;
+        n = st.n(top) + n;
+        val = S / Wt;
+    }
+    st.S(top) = S; st.Wt(top) = Wt; st.Qs(top) = Qs; st.D(top) = D; st.val(top) = val; st.n(top) = n;
+    return top + 1;
+}
+
+// the neutral profile's factor r and the compared value y of a cell; dry: r = 1 and y = theta, no operation on it
+__host__ __device__ inline double convect_r(double p_lev, double kdiff) { return exp(kdiff * log(p_lev / kP0)); }
+
+struct CvHostStack {
+    std::vector<double> s, wt, qs, d, v;
+    std::vector<int> c;
+    explicit CvHostStack(int L) : s(L), wt(L), qs(L), d(L), v(L), c(L) {}
+    double &S(int b) { return s[b]; }
+    double &Wt(int b) { return wt[b]; }
+    double &Qs(int b) { return qs[b]; }
+    double &D(int b) { return d[b]; }
+    double &val(int b) { return v[b]; }
+    int &n(int b) { return c[b]; }
+};
+
+int convect_check(const gcm_convect *cv, const char *fn, std::string *err) {
+    const auto bad = [&](const char *what) { *err = std::string(fn) + ": " + what; return GCM_ERR_ARG; };
+    if (!cv) return bad("no parameters");
+    if (!std::isfinite(cv->kappa_c) || !(cv->kappa_c >= 0.0 && cv->kappa_c < 1.0)) return bad("kappa_c must be finite and lie in [0, 1)");
+    if (cv->mix_q != 0 && cv->mix_q != 1) return bad("mix_q must be 0 or 1");
+    return GCM_OK;
+}
+
+// gcm_convect_columns: [ncol][L] columns of the compared value through convect_push; no handle, no device
+int convect_columns(int ncol, int L, const double *y, const double *w, const double *q, const double *dsig, int mix_q,
+                    double *y_out, double *q_out, int32_t *nblock, std::string *err) {
+    if (ncol < 0 || L < 1 || (mix_q != 0 && mix_q != 1) || (ncol > 0 && (!y || !w || !q || !dsig))) {
+        *err = "gcm_convect_columns: ncol must be >= 0, L >= 1, mix_q 0 or 1; y, w, q and dsig are required";
+        return GCM_ERR_ARG;
+    }
+    CvHostStack st(L);
+    for (int c = 0; c < ncol; ++c) {
+        const size_t o = (size_t)c * L;
+        int top = 0;
+        for (int k = 0; k < L; ++k) top = convect_push(st, top, y[o + k], w[o + k], q[o + k], dsig[k]);
+        int k = 0;
+        for (int b = 0; b < top; ++b) {
+            const int n = st.n(b);
+            for (int e = k + n; k < e; ++k) {
+                if (y_out) y_out[o + k] = n > 1 ? st.val(b) : y[o + k];
+                if (q_out) q_out[o + k] = n > 1 && mix_q ? st.Qs(b) / st.D(b) : q[o + k];
+                if (nblock) nblock[o + k] = n;
+            }
+        }
+    }
+    return GCM_OK;
+}
+
+// ---------------------------------------------------------------- the kernel
+constexpr int kCvThreads = 64;       // one wave: the workgroup's LDS is that wave's stack
+constexpr int kCvBatch = 8;          // levels requested together in pass 1, then compared in order
+constexpr int kCvBatch2 = 4;         // levels requested together in pass 2, then pushed in order
+constexpr size_t kCvSlotBytes = 5 * sizeof(double) + sizeof(int);
+
+constexpr size_t kCvLdsCap = 160 * 1024;   // a workgroup's LDS on gfx950, the figure pe25d_create sizes its kernels by
+
+size_t convect_lds_bytes(int L) { return sizeof(double) * kExnerTabDoubles + kCvSlotBytes * (size_t)L * kCvThreads; }
+
+template <typename T>
+struct CvArgsT {
+    const T *p;                      // [j][i], interior row 0
+    T *t, *q;                        // [j][k][i], interior row 0
+    const double *sig, *dsig;        // [L]
+    const double *exner_tab;
+    double *count, *levels;          // [H][W] own rows, or null: the launch accumulates nothing
+    double ptop, kdiff;              // kappa_c - kappa
+    int dry, mix_q;
+    int W, L, H;
+    int j0, n0, jb0, nrows;          // the rows of the launch: [j0, j0 + n0), then from jb0 on (a band's ghost rows: negative / >= H)
+};
+
+// the lane's stack in LDS: slot b of array a at base[(a L + b) 64 + lane]
+struct CvLdsStack {
+    double *base;
+    int *cnt;
+    int L;
+    __host__ __device__ double &at(int a, int b) { return base[(a * L + b) * kCvThreads]; }
+    __host__ __device__ double &S(int b) { return at(0, b); }
+    __host__ __device__ double &Wt(int b) { return at(1, b); }
+    __host__ __device__ double &Qs(int b) { return at(2, b); }
+    __host__ __device__ double &D(int b) { return at(3, b); }
+    __host__ __device__ double &val(int b) { return at(4, b); }
+    __host__ __device__ int &n(int b) { return cnt[b * kCvThreads]; }
+};
+
+// grid (column blocks of 64, rows)
+template <typename T>
+__global__ __launch_bounds__(kCvThreads) void pe_convect_kernel(CvArgsT<T> a) {
+    extern __shared__ double cv_lds[];
+    const int W = a.W, L = a.L;
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x * kCvThreads + lane;
+    const int r = (int)blockIdx.y;
+    if (r >= a.nrows) return;                              // (uniform: the grid has nrows rows)
+    const int j = r < a.n0 ? a.j0 + r : a.jb0 + (r - a.n0);
+    const bool live = i < W;
+    const long c3 = (long)j * L * W + (live ? i : 0);      // (a lane past the row loads nothing, stores nothing)
+    const double pc = live ? (double)a.p[(long)j * W + i] : 0.0;
+
+    // ---- pass 1: is any y[k] < y[k - 1]
+    bool unstable = false;
+    if (live) {
+        double prev = 0.0;
+        for (int k = 0; k < L; k += kCvBatch) {
+            T th[kCvBatch];
+#pragma unroll
+            for (int n = 0; n < kCvBatch; ++n)
+                if (k + n < L) th[n] = a.t[c3 + (long)(k + n) * W];
+#pragma unroll
+            for (int n = 0; n < kCvBatch; ++n) {
+                const int kk = k + n;
+                if (kk < L) {
+                    double y = (double)th[n];
+                    if (!a.dry) y = y / convect_r(a.sig[kk] * pc + a.ptop, a.kdiff);
+                    if (kk > 0 && y < prev) unstable = true;
+                    prev = y;
+                }
+            }
+        }
+    }
+    if (!__any(unstable ? 1 : 0)) return;
+
+    // ---- pass 2: the wave has an unstable lane
+    double *tab = cv_lds;
+    for (int n = lane; n < kExnerTabDoubles; n += kCvThreads) tab[n] = a.exner_tab[n];
+    __syncthreads();
+    CvLdsStack st;
+    st.base = cv_lds + kExnerTabDoubles + lane;
+    st.cnt = (int *)(cv_lds + kExnerTabDoubles + (size_t)5 * L * kCvThreads) + lane;
+    st.L = L;
+    if (!live) return;
+    int top = 0;
+    for (int k = 0; k < L; k += kCvBatch2) {
+        T th[kCvBatch2], qq[kCvBatch2];
+#pragma unroll
+        for (int n = 0; n < kCvBatch2; ++n)
+            if (k + n < L) {
+                const long o = c3 + (long)(k + n) * W;
+                th[n] = a.t[o];
+                qq[n] = a.q[o];
+            }
+#pragma unroll
+        for (int n = 0; n < kCvBatch2; ++n) {
+            const int kk = k + n;
+            if (kk < L) {
+                const double pl = a.sig[kk] * pc + a.ptop;
+                const double pi = exner(pl, tab);
+                double y = (double)th[n], w;
+                if (a.dry) {
+                    w = pi * a.dsig[kk];
+                } else {
+                    const double rr = convect_r(pl, a.kdiff);
+                    y = y / rr;
+                    w = (pi * rr) * a.dsig[kk];
+                }
+                top = convect_push(st, top, y, w, (double)qq[n], a.dsig[kk]);
+            }
+        }
+    }
+    if (!unstable) return;                                 // a stable lane of an unstable wave: nothing to write
+    double levels = 0.0;
+    int k = 0;
+    for (int b = 0; b < top; ++b) {
+        const int n = st.n(b);
+        if (n > 1) {
+            const double val = st.val(b);
+            const double qm = a.mix_q ? st.Qs(b) / st.D(b) : 0.0;
+            for (int kk = k; kk < k + n; ++kk) {
+                const long o = c3 + (long)kk * W;
+                double theta = val;
+                if (!a.dry) theta = val * convect_r(a.sig[kk] * pc + a.ptop, a.kdiff);
+                a.t[o] = (T)theta;
+                if (a.mix_q) a.q[o] = (T)qm;
+            }
+            levels = levels + (double)n;
+        }
+        k += n;
+    }
+    if (a.count && j >= 0 && j < a.H) {
+        const long o2 = (long)j * W + i;
+        a.count[o2] = a.count[o2] + 1.0;
+        a.levels[o2] = a.levels[o2] + levels;
+    }
+}
+
+// ---------------------------------------------------------------- the handle's side
+static int cv_hip(hipError_t e, const char *fn, std::string *err) {
+    if (e == hipSuccess) return GCM_OK;
+    *err = std::string("hip: ") + fn + ": " + hipGetErrorString(e);
+    return GCM_ERR_HIP;
+}
+static int cv_registered(const Pe25d *m, const char *fn, std::string *err) {
+    if (m->convect.acc) return GCM_OK;
+    *err = std::string(fn) + ": no convective adjustment registered (gcm_set_convect)";
+    return GCM_ERR_STATE;
+}
+static size_t cv_words(const Pe25d *m) { return (size_t)m->H * m->W; }
+
+// the wave's stack at the handle's L must fit a workgroup's LDS (160 KB); the kernel's dynamic LDS size is set once, here (the
+// kernel is instantiated and launched in this unit alone)
+int pe25d_convect_fits(Pe25d *m, const char *fn, std::string *err) {
+    PeConvect &z = m->convect;
+    if (z.lds_bytes) return GCM_OK;
+    const size_t need = convect_lds_bytes(m->L), cap = kCvLdsCap;
+    if (need > cap) {
+        *err = std::string(fn) + ": the block stack of " + std::to_string(m->L) + " levels takes " + std::to_string(need) +
+               " bytes of LDS, a workgroup has " + std::to_string(cap);
+        return GCM_ERR_UNSUPPORTED;
+    }
+    const void *k = m->f32 ? (const void *)pe_convect_kernel<float> : (const void *)pe_convect_kernel<double>;
+    if (int rc = cv_hip(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need), fn, err)) return rc;
+    z.lds_bytes = need;
+    return GCM_OK;
+}
+
+// gcm_set_convect: on -- the accumulators in place and zero; off -- freed
+int pe25d_set_convect(Pe25d *m, bool on, hipStream_t s, std::string *err) {
+    PeConvect &z = m->convect;
+    if (!on) {
+        if (!z.acc) return GCM_OK;
+        // (a launch may still be adding to the sums)
+        if (int rc = cv_hip(hipStreamSynchronize(s), "gcm_set_convect", err)) return rc;
+        m->allocs.erase(std::remove(m->allocs.begin(), m->allocs.end(), (void *)z.acc), m->allocs.end());
+        (void)hipFree(z.acc);
+        z.acc = nullptr;
+        z.seconds = 0.0;
+        z.n = 0;
+        return GCM_OK;
+    }
+    if (int rc = pe25d_convect_fits(m, "gcm_set_convect", err)) return rc;
+    if (!z.acc) {
+        if (!dev_upload<double>(m, &z.acc, nullptr, 2 * cv_words(m))) { *err = "hip: gcm_set_convect allocation failed"; return GCM_ERR_HIP; }
+    } else if (int rc = cv_hip(hipMemsetAsync(z.acc, 0, sizeof(double) * 2 * cv_words(m), s), "gcm_set_convect", err)) {
+        return rc;
+    }
+    z.seconds = 0.0;
+    z.n = 0;
+    return GCM_OK;
+}
+
+bool pe25d_convect_on(const Pe25d *m) { return m->convect.acc != nullptr; }
+
+// the launches' level tables (sig, dsig in float64, uploaded once) and the parameters of the launches that follow; dt:
+// what an accumulating launch adds to the seconds (the step's dt; 0 for gcm_convect_step, which takes none)
+int pe25d_convect_tables(Pe25d *m, const gcm_convect *cv, double dt, std::string *err) {
+    if (int rc = convect_check(cv, "convect", err)) return rc;
+    if (!std::isfinite(dt)) { *err = "convect: dt must be finite"; return GCM_ERR_ARG; }
+    if (int rc = pe25d_convect_fits(m, "convect", err)) return rc;
+    PeConvect &z = m->convect;
+    if (!z.tab) {
+        std::vector<double> t(m->sig_host);
+        t.insert(t.end(), m->dsig_host.begin(), m->dsig_host.end());
+        if (!dev_upload<double>(m, &z.tab, t.data(), t.size())) { *err = "hip: convect table upload failed"; return GCM_ERR_HIP; }
+    }
+    z.kappa_c = cv->kappa_c;
+    z.mix_q = cv->mix_q;
+    z.dt = dt;
+    return GCM_OK;
+}
+
+template <typename T>
+static int cv_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool accumulate, hipStream_t s, std::string *err) {
+    PeBufs<T> &B = bufs<T>(m);
+    const PeConvect &z = m->convect;
+    CvArgsT<T> a{};
+    a.p = B.st[set][GCM_P]; a.t = B.st[set][GCM_T]; a.q = B.st[set][GCM_Q];
+    a.sig = z.tab; a.dsig = z.tab + m->L;
+    a.exner_tab = m->exner_tab;
+    a.count = accumulate ? z.acc : nullptr;
+    a.levels = accumulate ? z.acc + cv_words(m) : nullptr;
+    a.ptop = m->cfg.ptop; a.kdiff = z.kappa_c - kKappa;
+    a.dry = z.kappa_c == 0.0 ? 1 : 0; a.mix_q = z.mix_q;
+    a.W = m->W; a.L = m->L; a.H = m->H;
+    a.j0 = j0; a.n0 = std::max(0, j1 - j0); a.jb0 = jb0; a.nrows = a.n0 + std::max(0, jb1 - jb0);
+    const dim3 grid((m->W + kCvThreads - 1) / kCvThreads, a.nrows);
+    hipLaunchKernelGGL(pe_convect_kernel<T>, grid, dim3(kCvThreads), z.lds_bytes, s, a);
+    if (hipGetLastError() != hipSuccess) { *err = "hip: convect kernel launch failed"; return GCM_ERR_HIP; }
+    return GCM_OK;
+}
+
+// rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one) on `s`, pe25d_convect_tables in place.
+// accumulate: the own rows' counts are added to the registered sums, and the call counts as one application
+int pe25d_convect_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool accumulate, hipStream_t s,
+                       std::string *err) {
+    PeConvect &z = m->convect;
+    if (!z.tab || !z.lds_bytes) { *err = "convect: no tables in place"; return GCM_ERR_STATE; }
+    if (accumulate && !z.acc) { *err = "convect: no sums to accumulate into (gcm_set_convect)"; return GCM_ERR_STATE; }
+    if (set < 0) set = m->cur_i;
+    if (std::max(0, j1 - j0) + std::max(0, jb1 - jb0) <= 0) return GCM_OK;
+    // Invariants of a launch, against pe25d_hs_rows' four.  The launch writes theta and q and reads p, theta and q:
+    //  * the column sums K4 left for this state (sum_k dsig u, sum_k dsig v) stay valid: u and v are not touched.  For the
+    //    same reason the wait for the third stream's column sums of the edge rows (which read u and v) is not needed;
+    //  * the fork at the last K4 stays, as behind the in-place radiation: what the next stage queues on the second and
+    //    third stream ahead of its wait for this stream (ev_join, behind K3) -- the ghost rows' column sums and anchors,
+    //    K1 and pit, the edge rows' partial sums, the tracers -- reads u, v, p, the intermediates and ghost-row theta, never
+    //    own-row theta or q, and writes none of p, theta, q of this set; the edge rows' K4, which reads them, waits for
+    //    ev_join.  The exception is a band whose ghost rows this launch takes with the own rows on this stream
+    //    (gcm_convect_step, the host-driven exchange): the ghost rows' anchors on the second stream read their theta, so
+    //    chain B must follow this stream's position;
+    //  * the ghost rows' geopotential anchors were formed from theta as it was, unless the caller forces the ghost rows
+    //    itself ahead of them (keep_ghosts: gcm_band_run);
+    //  * the parity tap's stage state is gone: theta changed.
+    if (!keep_ghosts) m->ghost_ready = -1;
+    if (!(keep_ghosts || m->wrap)) m->k4_fork_valid = false;
+    m->last_stage_set = -1;                                // gcm_get_intermediate: theta changed
+    if (int rc = m->f32 ? cv_launch<float>(m, set, j0, j1, jb0, jb1, accumulate, s, err)
+                        : cv_launch<double>(m, set, j0, j1, jb0, jb1, accumulate, s, err))
+        return rc;
+    if (accumulate) {
+        z.seconds += z.dt;
+        ++z.n;
+    }
+    return GCM_OK;
+}
+
+int pe25d_convect_reset(Pe25d *m, hipStream_t s, std::string *err) {
+    if (int rc = cv_registered(m, "gcm_convect_reset", err)) return rc;
+    PeConvect &z = m->convect;
+    if (int rc = cv_hip(hipMemsetAsync(z.acc, 0, sizeof(double) * 2 * cv_words(m), s), "gcm_convect_reset", err)) return rc;
+    z.seconds = 0.0;
+    z.n = 0;
+    return GCM_OK;
+}
+
+int pe25d_get_convect(Pe25d *m, double *count, double *levels, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err) {
+    if (int rc = cv_registered(m, "gcm_get_convect", err)) return rc;
+    const PeConvect &z = m->convect;
+    const size_t bytes = sizeof(double) * cv_words(m);
+    hipError_t e = hipSuccess;
+    if (count) e = hipMemcpyAsync(count, z.acc, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && levels) e = hipMemcpyAsync(levels, z.acc + cv_words(m), bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (int rc = cv_hip(e, "gcm_get_convect", err)) return rc;
+    if (seconds) *seconds = z.seconds;
+    if (nsteps) *nsteps = z.n;
+    return GCM_OK;
+}
+
+int pe25d_put_convect(Pe25d *m, const double *count, const double *levels, double seconds, int64_t nsteps, hipStream_t s,
+                      std::string *err) {
+    if (int rc = cv_registered(m, "gcm_put_convect", err)) return rc;
+    if (!count || !levels || !std::isfinite(seconds) || seconds < 0.0 || nsteps < 0) {
+        *err = "gcm_put_convect: count and levels are required, seconds must be finite and >= 0, nsteps >= 0";
+        return GCM_ERR_ARG;
+    }
+    PeConvect &z = m->convect;
+    const size_t bytes = sizeof(double) * cv_words(m);
+    hipError_t e = hipMemcpyAsync(z.acc, count, bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(z.acc + cv_words(m), levels, bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);          // (the caller's arrays are free again when the call returns)
+    if (int rc = cv_hip(e, "gcm_put_convect", err)) return rc;
+    z.seconds = seconds;
+    z.n = nsteps;
+    return GCM_OK;
+}
+
+}  // namespace gcm

@@ -8,10 +8,11 @@
 //   pe25d_held_suarez.hip  the Held-Suarez forcing: its table routine, its kernel and its launches
 //   pe25d_climate.hip  the zonal-mean climatology: its kernel, its sums and their way to the host and back
 //   pe25d_moist.hip    moist physics: the saturation routine, the kernel, its launches and its sums
+//   pe25d_convect.hip  convective adjustment: the pooling routine, the kernel, its launches and its sums
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
 // gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
-// pe25d_hs_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample).
+// pe25d_hs_rows, pe25d_convect_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample).
 #pragma once
 #include "pe25d_kernels.h"
 
@@ -114,6 +115,18 @@ struct PeMoist {
     double lc = 0.0, x = 0.0, rh_s = 0.0, dt = 0.0;   // Lv / Cp, dt / tau_e (0: no evaporation), rh_s, dt
 };
 
+// Convective adjustment (pe25d_convect.hip, gcm_set_convect): the float64 sums on the device with their two counters, the
+// level tables of the launches and the parameters of the launches that follow (pe25d_convect_tables)
+struct PeConvect {
+    double *acc = nullptr;                      // device: count [H][W], levels [H][W]; non-null: registered
+    double seconds = 0.0;                       // sum of dt over the registered steps in the sums
+    long long n = 0;                            // applications in the sums
+    double *tab = nullptr;                      // device: sig [L], dsig [L], float64
+    size_t lds_bytes = 0;                       // the kernel's dynamic LDS at the handle's L; 0: not checked against the device yet
+    double kappa_c = 0.0, dt = 0.0;             // the neutral profile (0: dry); what an accumulating launch adds to seconds
+    int mix_q = 0;
+};
+
 struct Pe25d {
     gcm_config cfg{};
     int W = 0, H = 0, L = 0, Hg = 0;
@@ -187,6 +200,7 @@ struct Pe25d {
     PeHeldSuarez hs;
     PeClimate clim;
     PeMoist moist;
+    PeConvect convect;
 };
 
 template <typename T> inline PeBufs<T> &bufs(Pe25d *m);

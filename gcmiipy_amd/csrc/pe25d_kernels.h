@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip, pe25d_moist.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
+// pe25d_climate.hip, pe25d_moist.hip, pe25d_convect.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -80,6 +80,24 @@ int pe25d_moist_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool k
 int pe25d_moist_reset(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_get_moist(Pe25d *m, double *precip, double *evap, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err);
 int pe25d_put_moist(Pe25d *m, const double *precip, const double *evap, double seconds, int64_t nsteps, hipStream_t s, std::string *err);
+// Convective adjustment (pe25d_convect.hip).  convect_check / convect_columns: no handle, no device (gcm_convect_columns).
+// pe25d_set_convect: the sums allocated and zeroed (on) or freed; GCM_ERR_UNSUPPORTED where the block stack of the handle's
+// L does not fit a workgroup's LDS; pe25d_convect_tables: the level tables in place (uploaded once) and cv as the
+// parameters of the launches that follow, dt what an accumulating launch adds to the seconds; pe25d_convect_rows: the
+// kernel over rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one) on `s`; keep_ghosts as for
+// pe25d_solar_rows; accumulate: the own rows' counts go to the registered sums and the call counts as one application
+int convect_check(const gcm_convect *cv, const char *fn, std::string *err);
+int convect_columns(int ncol, int L, const double *y, const double *w, const double *q, const double *dsig, int mix_q,
+                    double *y_out, double *q_out, int32_t *nblock, std::string *err);
+int pe25d_set_convect(Pe25d *m, bool on, hipStream_t s, std::string *err);
+bool pe25d_convect_on(const Pe25d *m);
+int pe25d_convect_tables(Pe25d *m, const gcm_convect *cv, double dt, std::string *err);
+int pe25d_convect_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool accumulate, hipStream_t s,
+                       std::string *err);
+int pe25d_convect_reset(Pe25d *m, hipStream_t s, std::string *err);
+int pe25d_get_convect(Pe25d *m, double *count, double *levels, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err);
+int pe25d_put_convect(Pe25d *m, const double *count, const double *levels, double seconds, int64_t nsteps, hipStream_t s,
+                      std::string *err);
 int pe25d_new_state_set(const Pe25d *m);    // the set a corrector stage in flight writes (before the swap), else the current one
 int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err);
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan

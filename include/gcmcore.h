@@ -515,7 +515,8 @@ int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat
  * seconds (the sum of dt) and nsteps.  One writer per word and launch, no atomics: the same state gives the same bits,
  * and a band's rows hold the bits of the same rows of the single domain.
  * gcm_set_moist: the phase as part of every step taken by gcm_step and gcm_band_run: the Matsuno step, solar_timestep
- * where gcm_set_physics is on, the Held-Suarez forcing where registered, then this, then the climatology's sample.
+ * where gcm_set_physics is on, the Held-Suarez forcing where registered, the convective adjustment where registered
+ * (gcm_set_convect), then this, then the climatology's sample.
  * gcm_half_step and gcm_step_phase never apply it.  On a latitude band the ghost rows of theta and q that the
  * post-corrector exchange delivers are adjusted LOCALLY (column-local kernel, the neighbour's own inputs, the neighbour's
  * own bits) and add to no sum; the packed edge rows leave unadjusted: no third exchange, the message format and
@@ -545,6 +546,68 @@ int gcm_get_moist(gcm_handle *h, double *precip, double *evap, double *seconds, 
 int gcm_put_moist(gcm_handle *h, const double *precip, const double *evap, double seconds, int64_t nsteps);
 int gcm_moist_reset(gcm_handle *h);
 int gcm_moist_saturation(int n, const double *T, const double *p_lev, double *q_s, double *dq_s, int *can);
+/* Convective adjustment of GCM_PE25D on the device: every column's theta, and optionally q, is mixed wherever it is
+ * statically unstable against a neutral profile, at constant column enthalpy and column water (the dry adjustment, and
+ * with a critical lapse rate the adjustment of Manabe & Strickler (1964)).  One launch per step, fp64 and fp32 handles,
+ * single domains and latitude bands.  The reference has nothing of the kind: this is an addition.  State: p [H][W] in Pa
+ * (surface pressure minus ptop), t = theta, q [L][H][W]; tables: sig[k], dsig[k]; level k = 0 is the bottom.
+ * The one parameter kappa_c chooses the neutral profile: kappa_c = 0 is the dry adjustment, neutral where theta is
+ * constant; kappa_c = Rd gamma / G adjusts to the critical lapse rate gamma = -dT/dz (K / m; 6.5e-3 gives 0.19036),
+ * neutral where T is proportional to p_lev^kappa_c.
+ * Arithmetic, float64 for either storage type, every operation rounded on its own (no contraction), the result rounded
+ * once to the storage type.  Per cell (k, j, i):
+ *   p_lev = sig[k] p + ptop;   Pi = (p_lev / P0)^kappa from the kernels' own Exner routine
+ *   r = 1 where kappa_c = 0, else r = exp((kappa_c - kappa) log(p_lev / P0))
+ *   the compared value  y = theta / r  (kappa_c = 0: theta itself, no operation on it)
+ *   the weight          w = (Pi r) dsig[k],  so that sum_k y w = sum_k T dsig, the column's enthalpy up to Cp p / G
+ * Per column, pool adjacent violators from the bottom up:
+ *   for k = 0 .. L - 1: push the block (S = w y, Wt = w, Qs = q dsig[k], D = dsig[k], n = 1, value = y);
+ *     while there are two blocks and top.value < below.value (strict; a NaN compares false): pop the top into the one
+ *     below,  S = below.S + top.S, likewise Wt, Qs, D and n, in that operand order, then value = S / Wt
+ *   afterwards every level of a block with n > 1:  theta <- value r  (kappa_c = 0: value);  with mix_q: q <- Qs / D
+ *   blocks with n = 1 are NOT WRITTEN: a stable column, and the stable part of any column, keeps its bits.
+ * Both loops are bounded by L.  The result is the weighted isotonic regression of y, the exact limit of the classic
+ * pairwise adjustment sweeps: no iteration count, no tolerance.  y comes out non-decreasing in k; sum_k T dsig and
+ * sum_k q dsig of the column are conserved to rounding; a second application changes no bit where kappa_c = 0.
+ * p, u, v, the tracers and the ground temperature are untouched.
+ * Accumulators in the handle, allocated by gcm_set_convect, own rows only: count [H][W] and levels [H][W], float64;
+ * an application adds 1 to count where the column had a merged block and sum of n over its merged blocks to levels.
+ * seconds (the sum of the registered steps' dt) and nsteps (the applications).  One writer per word and launch, no atomics.
+ * gcm_set_convect: the phase as part of every step taken by gcm_step and gcm_band_run: the Matsuno step, solar_timestep
+ * where gcm_set_physics is on, the Held-Suarez forcing where registered, then this, then the moist physics where
+ * registered (which condenses what the mixing left supersaturated), then the climatology's sample.  gcm_half_step and
+ * gcm_step_phase never apply it.  On a latitude band the ghost rows of theta and q that the post-corrector exchange
+ * delivers are adjusted LOCALLY (column-local kernel, the neighbour's own inputs, the neighbour's own bits) and add to no
+ * sum; the packed edge rows leave unadjusted: no third exchange, the message format and gcm_halo_bytes are unchanged.
+ * NULL switches the phase off and frees the accumulators; registering again resets them.  Without a registration nothing
+ * is launched and every result and timing is as before.
+ * gcm_convect_on: 1 where the phase is registered, else 0 (other models: 0; a null handle GCM_ERR_ARG).
+ * gcm_convect_step: the same kernel once, in place on the current state.  It takes no dt: the adjustment is
+ * instantaneous.  With a registration it adds to count, levels and nsteps (and nothing to seconds); without one the counts
+ * of the call are dropped.  On a band it covers own rows and ghost rows: the ghost rows must be current.
+ * gcm_get_convect synchronises the handle's stream once; any pointer may be NULL.  gcm_put_convect uploads sums and
+ * counters (restarts): both arrays are required, seconds finite and >= 0, nsteps >= 0.  gcm_convect_reset zeroes all four.
+ * gcm_convect_columns: the pooling above on its own, on the host, without a handle or a device -- the one routine the
+ * kernel calls, compiled for the host -- over ncol columns y, w, q [ncol][L] with dsig [L].  y_out and q_out [ncol][L]
+ * receive the adjusted y and q (q unchanged without mix_q; levels of unmerged blocks are copied), nblock [ncol][L] the
+ * size n of each level's block; any of the three may be NULL.
+ * The kernel keeps a column's blocks in LDS, 44 bytes per level and lane of a one-wave workgroup.
+ * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, no parameters, kappa_c
+ * not finite or outside [0, 1), mix_q not 0 or 1; the probe: ncol < 0, L < 1, a missing input.  GCM_ERR_UNSUPPORTED: other
+ * models, and a handle whose L makes the blocks of a wave exceed a workgroup's LDS (L = 40 fits; 160 KB hold L = 57).
+ * GCM_ERR_STATE: get, put or reset without a registration.                                                         */
+typedef struct {
+    double kappa_c;              /* Rd gamma / G of the neutral profile, [0, 1); 0: dry adjustment */
+    int32_t mix_q;               /* 1: q of a merged block becomes its mass-weighted mean; 0: q is left alone */
+} gcm_convect;
+int gcm_set_convect(gcm_handle *h, const gcm_convect *cv);
+int gcm_convect_on(const gcm_handle *h);
+int gcm_convect_step(gcm_handle *h, const gcm_convect *cv);
+int gcm_get_convect(gcm_handle *h, double *count, double *levels, double *seconds, int64_t *nsteps);
+int gcm_put_convect(gcm_handle *h, const double *count, const double *levels, double seconds, int64_t nsteps);
+int gcm_convect_reset(gcm_handle *h);
+int gcm_convect_columns(int ncol, int L, const double *y, const double *w, const double *q, const double *dsig, int mix_q,
+                        double *y_out, double *q_out, int32_t *nblock);
 /* Zonal-mean climatology of GCM_PE25D accumulated on the device: what a Held-Suarez run is evaluated by -- the time and
  * zonal means of u, v, theta and T, their variances and the eddy fluxes as functions of latitude and level -- without a
  * host round trip per step (fp64 and fp32 handles, single domains and latitude bands).  One launch per sample reads
