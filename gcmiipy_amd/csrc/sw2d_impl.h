@@ -370,8 +370,12 @@ __device__ __forceinline__ void preloaded_iters(Ctx &c, const Raw<T> (&pre)[PRE 
     }
 }
 
+// Two columns per lane with a tracer: held to three waves per SIMD, i.e. 168 VGPRs.  Contraction within an expression
+// only -- what the fp32 unit is built with, see the Makefile -- would otherwise take 170-172 VGPRs and a third of the
+// waves (4096x2048 fp32 van Leer: 1.09x the time; held to 168 with 12-20 B of scratch per lane: 1.035x).  No other
+// instantiation is touched: the fp64 unit's code is the same instruction for instruction.
 template <typename T, bool TEMP, int TRACER, bool WRAPJ, int PRE = 0, bool STREAM = false, int CPL = 1>
-__global__ __launch_bounds__(64) void sw2d_fused_kernel(Sw2dArgsT<T> a0) {
+__global__ __launch_bounds__(64, (CPL == 2 && TRACER != 0) ? 3 : 1) void sw2d_fused_kernel(Sw2dArgsT<T> a0) {
     using Ctx = FusedCtx<T, TEMP, TRACER, WRAPJ, STREAM, CPL>;
     using V = typename Ctx::Real;
     constexpr int kCols = sw2d_fused_strip_cols(CPL);   // output columns per wave
