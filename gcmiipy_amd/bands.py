@@ -213,34 +213,30 @@ def merge_climate(parts):
     return Climate(parts[0].n, *[np.concatenate([c[f] for c in parts], axis=-1) for f in range(1, len(Climate._fields))])
 
 
+def _merge_column(ph, parts):
+    """merge_moist / merge_convect: the records of core._ColumnPhase `ph` in row order -> the whole domain's"""
+    import numpy as np
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_%s: no records" % ph.name)
+    if any(m.nsteps != parts[0].nsteps or m.seconds != parts[0].seconds for m in parts):
+        raise ValueError("merge_%s: the bands hold %s applications over %s seconds"
+                         % (ph.name, ", ".join(str(m.nsteps) for m in parts), ", ".join(repr(m.seconds) for m in parts)))
+    return ph.result(parts[0].nsteps, parts[0].seconds, *[np.concatenate([getattr(m, f) for m in parts], axis=0) for f in ph.fields])
+
+
 def merge_moist(parts):
     """the moist physics' sums of the whole domain from its bands': `parts` are the bands' Moist records
     (Core.moist_sums) in row order; the rows are concatenated.  ValueError where nsteps or seconds differ"""
-    import numpy as np
-    from .core import Moist
-    parts = list(parts)
-    if not parts:
-        raise ValueError("merge_moist: no records")
-    if any(m.nsteps != parts[0].nsteps or m.seconds != parts[0].seconds for m in parts):
-        raise ValueError("merge_moist: the bands hold %s applications over %s seconds"
-                         % (", ".join(str(m.nsteps) for m in parts), ", ".join(repr(m.seconds) for m in parts)))
-    return Moist(parts[0].nsteps, parts[0].seconds, np.concatenate([m.precip for m in parts], axis=0),
-                 np.concatenate([m.evap for m in parts], axis=0))
+    from .core import _MOIST
+    return _merge_column(_MOIST, parts)
 
 
 def merge_convect(parts):
     """the convective adjustment's sums of the whole domain from its bands': `parts` are the bands' Convect records
     (Core.convect_sums) in row order; the rows are concatenated.  ValueError where nsteps or seconds differ"""
-    import numpy as np
-    from .core import Convect
-    parts = list(parts)
-    if not parts:
-        raise ValueError("merge_convect: no records")
-    if any(m.nsteps != parts[0].nsteps or m.seconds != parts[0].seconds for m in parts):
-        raise ValueError("merge_convect: the bands hold %s applications over %s seconds"
-                         % (", ".join(str(m.nsteps) for m in parts), ", ".join(repr(m.seconds) for m in parts)))
-    return Convect(parts[0].nsteps, parts[0].seconds, np.concatenate([m.count for m in parts], axis=0),
-                   np.concatenate([m.levels for m in parts], axis=0))
+    from .core import _CONVECT
+    return _merge_column(_CONVECT, parts)
 
 
 class LoopbackExchange:
@@ -298,6 +294,8 @@ class HipBandEngine:
         # interior rows run on the compute stream (gcm_set_halo_buffers / gcm_wait_edges)
         self.async_edges = self.edge_first
         self._edges_pending = False
+        # what the set_* calls below registered, for physics_step (None: not registered)
+        self._phys = self._hs = self._convect = self._moist = self._clim = None
         if self.async_edges:
             core.set_halo_buffers(self.sbuf[0].data_ptr(), self.sbuf[1].data_ptr())
 
@@ -365,20 +363,16 @@ class HipBandEngine:
         unpack of the post-corrector exchange; then, likewise, the Held-Suarez forcing, the convective adjustment and the moist physics
         (the explicit calls: the adjustment's counts add up, its seconds do not); then the climatology's sample
         where this step is due one"""
-        ph = getattr(self, "_phys", None)
-        if ph is not None:
-            self.c.solar_step(ph[0], dt, ph[1])
-            ph[1] += dt
-        hs = getattr(self, "_hs", None)
-        if hs is not None:
-            self.c.held_suarez_step(hs[0], dt, **hs[1])
-        cv = getattr(self, "_convect", None)
-        if cv is not None:
-            self.c.convect_step(**cv)
-        mo = getattr(self, "_moist", None)
-        if mo is not None:
-            self.c.moist_step(dt, **mo)
-        cl = getattr(self, "_clim", None)
+        if self._phys is not None:
+            self.c.solar_step(self._phys[0], dt, self._phys[1])
+            self._phys[1] += dt
+        if self._hs is not None:
+            self.c.held_suarez_step(self._hs[0], dt, **self._hs[1])
+        if self._convect is not None:
+            self.c.convect_step(**self._convect)
+        if self._moist is not None:
+            self.c.moist_step(dt, **self._moist)
+        cl = self._clim
         if cl is not None and cl[0] > 0:
             cl[1] += 1
             if cl[1] % cl[0] == 0:

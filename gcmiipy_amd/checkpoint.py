@@ -25,7 +25,7 @@ ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
 import numpy as np
 
 from . import _lib
-from .core import CONVECT_DEFAULTS, Core, GcmError, HELD_SUAREZ_DEFAULTS, MOIST_DEFAULTS
+from .core import COLUMN_PHASES, Core, GcmError, HELD_SUAREZ_DEFAULTS
 from .geometry import Geom
 
 _GEOM_KEYS = ("sige", "sigt", "sigb", "dsig", "sig", "dsigv", "dx_j", "dx_h", "dy", "ptop",
@@ -59,22 +59,19 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
     if core.model == _lib.PE25D and core.climate_every > 0:
         n, m3, m2 = core.climate_sums()
         out.update(climate_every=np.int64(core.climate_every), climate_n=np.int64(n), climate_m3=m3, climate_m2=m2)
-    mo = getattr(core, "moist", None) if core.model == _lib.PE25D else None
-    if mo is None and core.model == _lib.PE25D and getattr(core, "moist_registered", False):
-        raise GcmError("checkpoint.save: the handle's moist physics was registered through gcm_set_moist directly; its "
-                       "parameters are unknown here and the phase and its sums would be lost (register with Core.set_moist)")
-    if mo is not None:
-        sums = core.moist_sums()
-        out.update(moist=np.asarray([mo[k] for k in MOIST_DEFAULTS], dtype=np.float64), moist_n=np.int64(sums.nsteps),
-                   moist_seconds=np.float64(sums.seconds), moist_precip=sums.precip, moist_evap=sums.evap)
-    cv = getattr(core, "convect", None) if core.model == _lib.PE25D else None
-    if cv is None and core.model == _lib.PE25D and getattr(core, "convect_registered", False):
-        raise GcmError("checkpoint.save: the handle's convective adjustment was registered through gcm_set_convect directly; its "
-                       "parameters are unknown here and the phase and its sums would be lost (register with Core.set_convect)")
-    if cv is not None:
-        sums = core.convect_sums()
-        out.update(convect=np.asarray([cv[k] for k in CONVECT_DEFAULTS], dtype=np.float64), convect_n=np.int64(sums.nsteps),
-                   convect_seconds=np.float64(sums.seconds), convect_count=sums.count, convect_levels=sums.levels)
+    # (a core is asked only for the phases it knows: getattr, so that a stand-in without one of them will do; reversed:
+    # the files have always held the moist physics' keys ahead of the convective adjustment's)
+    for ph in reversed(COLUMN_PHASES if core.model == _lib.PE25D else ()):
+        par = getattr(core, ph.name, None)
+        if par is None and getattr(core, ph.name + "_registered", False):
+            raise GcmError("checkpoint.save: the handle's %s was registered through gcm_set_%s directly; its parameters are "
+                           "unknown here and the phase and its sums would be lost (register with Core.set_%s)"
+                           % (ph.what, ph.name, ph.name))
+        if par is not None:
+            sums = getattr(core, ph.name + "_sums")()
+            out[ph.name] = np.asarray([par[k] for k in ph.defaults], dtype=np.float64)
+            out[ph.name + "_n"], out[ph.name + "_seconds"] = np.int64(sums.nsteps), np.float64(sums.seconds)
+            out.update({"%s_%s" % (ph.name, f): getattr(sums, f) for f in ph.fields})
     for k, a in zip("puvtq", (p, u, v, t, q)):
         if a is not None:
             out["state_" + k] = a
@@ -125,21 +122,18 @@ def load(path):
     clim = None
     if "climate_every" in d.files:
         clim = dict(every=int(d["climate_every"]), n=int(d["climate_n"]), m3=d["climate_m3"], m2=d["climate_m2"])
-    moist = None
-    if "moist" in d.files:
-        moist = dict(params=dict(zip(MOIST_DEFAULTS, (float(x) for x in d["moist"]))), n=int(d["moist_n"]),
-                     seconds=float(d["moist_seconds"]), precip=d["moist_precip"], evap=d["moist_evap"])
-    convect = None
-    if "convect" in d.files:
-        kc, mq = (float(x) for x in d["convect"])
-        convect = dict(params=dict(zip(CONVECT_DEFAULTS, (kc, int(mq)))), n=int(d["convect_n"]),
-                       seconds=float(d["convect_seconds"]), count=d["convect_count"], levels=d["convect_levels"])
+    # (the parameters in the types of the phase's defaults: mix_q is an int)
+    column = {ph.name: None for ph in COLUMN_PHASES}
+    for ph in COLUMN_PHASES:
+        if ph.name in d.files:
+            par = {k: type(v)(x) for (k, v), x in zip(ph.defaults.items(), d[ph.name])}
+            column[ph.name] = dict(params=par, n=int(d[ph.name + "_n"]), seconds=float(d[ph.name + "_seconds"]),
+                                   **{f: d["%s_%s" % (ph.name, f)] for f in ph.fields})
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, climate=clim,
-                moist=moist, convect=convect,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
-                tracer_mixing=mixing)
+                tracer_mixing=mixing, **column)
 
 
 def restore(path, **core_kwargs):
@@ -166,10 +160,9 @@ def restore(path, **core_kwargs):
     if ck["climate"] is not None:
         core.set_climate(ck["climate"]["every"])
         core.put_climate(ck["climate"]["n"], ck["climate"]["m3"], ck["climate"]["m2"])
-    if ck["convect"] is not None:
-        core.set_convect(**ck["convect"]["params"])
-        core.put_convect(ck["convect"]["n"], ck["convect"]["seconds"], ck["convect"]["count"], ck["convect"]["levels"])
-    if ck["moist"] is not None:
-        core.set_moist(**ck["moist"]["params"])
-        core.put_moist(ck["moist"]["n"], ck["moist"]["seconds"], ck["moist"]["precip"], ck["moist"]["evap"])
+    for ph in COLUMN_PHASES:                 # (the model's order: the convective adjustment, then the moist physics)
+        rec = ck[ph.name]
+        if rec is not None:
+            getattr(core, "set_" + ph.name)(**rec["params"])
+            getattr(core, "put_" + ph.name)(rec["n"], rec["seconds"], *[rec[f] for f in ph.fields])
     return core, ck

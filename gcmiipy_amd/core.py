@@ -27,6 +27,13 @@ def _check(rc, h=None):
     raise GcmError("gcmcore error %d: %s" % (rc, msg))
 
 
+def _count(n, h):
+    """a non-negative int an entry point returned (a count, a flag, a constant), or the error a negative one stands for"""
+    if n < 0:
+        _check(n, h)
+    return n
+
+
 def as_f64(x, shape=None, name="array"):
     """float64 C-contiguous ndarray of `shape`; mirrors the reference's shape asserts
     (temperature.py:9,17; dynamics.py:203) with ValueError."""
@@ -290,6 +297,24 @@ def convect_columns(y, w, q, dsig, mix_q=True):
     return yo.reshape(y.shape), qo.reshape(y.shape), nb.reshape(y.shape)
 
 
+class _ColumnPhase:
+    """what tells the two phases with per-column sums apart -- the convective adjustment and the moist physics, in the
+    model's order in COLUMN_PHASES -- for Core's seven operations on each and for checkpoint.py: the name in the entry
+    points and keys, the words of the messages, the ctypes record, the *_params function with its defaults (the record's
+    order), the result namedtuple (its last two fields name the sums) and whether *_step takes dt"""
+
+    def __init__(self, name, what, record, params, defaults, result, step_takes_dt):
+        self.name, self.what, self.record, self.params, self.defaults = name, what, record, params, defaults
+        self.result, self.fields, self.step_takes_dt = result, result._fields[2:], step_takes_dt
+        self.set, self.on, self.step, self.get, self.put, self.reset = (
+            getattr(lib, "gcm_" + f % name) for f in ("set_%s", "%s_on", "%s_step", "get_%s", "put_%s", "%s_reset"))
+
+
+_CONVECT = _ColumnPhase("convect", "convective adjustment", _lib.Convect, convect_params, CONVECT_DEFAULTS, Convect, False)
+_MOIST = _ColumnPhase("moist", "moist physics", _lib.Moist, moist_params, MOIST_DEFAULTS, Moist, True)
+COLUMN_PHASES = (_CONVECT, _MOIST)
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -343,8 +368,7 @@ class Core:
         self._forcing = {}                      # tracer -> the forcing record registered (set_tracer_forcing)
         self._mixing = {}                       # tracer -> the profile K registered (set_tracer_mixing)
         self._held_suarez = None                # the parameters and latitudes registered (set_held_suarez)
-        self._moist = None                      # the parameters registered (set_moist)
-        self._convect = None                    # the parameters registered (set_convect)
+        self._column = {}                       # the parameters registered (set_convect, set_moist), by the phase's name
         cfg = _lib.Config()
         cfg.abi_version = _lib.ABI_VERSION
         cfg.model = model
@@ -531,9 +555,7 @@ class Core:
         """-> the forcing this object registered for tracer i, dict(source, decay, emission, pin_mask, pin_value) (a
         host copy), or None where the handle carries none (gcm_tracer_forced) -- and also None for a forcing that was
         registered through the C call directly, of which this object holds no copy"""
-        on = lib.gcm_tracer_forced(self._h, int(i))
-        if on < 0:
-            _check(on, self._h)
+        on = _count(lib.gcm_tracer_forced(self._h, int(i)), self._h)
         return self._forcing.get(int(i)) if on else None
 
     def tracer_forcings(self):
@@ -569,9 +591,7 @@ class Core:
         """-> the profile K (L - 1,) this object registered for tracer i (a host copy), or None where the handle
         carries none (gcm_tracer_mixed) -- and also None for a profile that was registered through the C call
         directly, of which this object holds no copy"""
-        on = lib.gcm_tracer_mixed(self._h, int(i))
-        if on < 0:
-            _check(on, self._h)
+        on = _count(lib.gcm_tracer_mixed(self._h, int(i)), self._h)
         return self._mixing.get(int(i)) if on else None
 
     def tracer_mixings(self):
@@ -595,25 +615,16 @@ class Core:
     @property
     def tracer_scheme(self):
         """the scheme in force, as a _lib.TRACER_* constant"""
-        s = lib.gcm_tracer_scheme(self._h)
-        if s < 0:
-            _check(s, self._h)
-        return s
+        return _count(lib.gcm_tracer_scheme(self._h), self._h)
 
     @property
     def band_tracer_rows(self):
         """the ghost rows per side a band's tracers carry (gcm_band_tracer_rows); 0: not a GCM_PE25D band"""
-        n = lib.gcm_band_tracer_rows(self._h)
-        if n < 0:
-            _check(n, self._h)
-        return n
+        return _count(lib.gcm_band_tracer_rows(self._h), self._h)
 
     @property
     def tracer_count(self):
-        n = lib.gcm_tracer_count(self._h)
-        if n < 0:
-            _check(n, self._h)
-        return n
+        return _count(lib.gcm_tracer_count(self._h), self._h)
 
     # -- stepping ------------------------------------------------------------------
     def step(self, nsteps, dt):
@@ -761,15 +772,50 @@ class Core:
     def held_suarez(self):
         """the parameters of the registered Held-Suarez forcing as a dict, or None where the handle carries none
         (gcm_held_suarez_on) -- and also None for one registered through the C call directly"""
-        on = lib.gcm_held_suarez_on(self._h)
-        if on < 0:
-            _check(on, self._h)
+        on = _count(lib.gcm_held_suarez_on(self._h), self._h)
         return dict(self._held_suarez[0]) if on and self._held_suarez else None
 
     @property
     def held_suarez_lat(self):
         """the latitudes (global_height,) the registered Held-Suarez forcing was given, or None"""
         return self._held_suarez[1].copy() if self.held_suarez is not None else None
+
+    # -- the phases with per-column sums (GCM_PE25D): one implementation for both, by their _ColumnPhase --------------
+    def _set_column(self, ph, off, params):
+        if off:
+            if off != (None,) or params:
+                raise ValueError("set_%s takes keyword parameters, or None alone to switch the phase off" % ph.name)
+            _check(ph.set(self._h, None), self._h)
+            self._column.pop(ph.name, None)
+            return
+        par = ph.params(params)
+        rec = ph.record(*par.values())
+        _check(ph.set(self._h, C.byref(rec)), self._h)
+        self._column[ph.name] = dict(par)
+
+    def _column_registered(self, ph):
+        return bool(_count(ph.on(self._h), self._h))
+
+    def _column_params(self, ph):
+        par = self._column.get(ph.name)
+        return dict(par) if self._column_registered(ph) and par else None
+
+    def _column_step(self, ph, dt, params):
+        rec = ph.record(*ph.params(params).values())
+        _check(ph.step(self._h, float(dt), C.byref(rec)) if ph.step_takes_dt else ph.step(self._h, C.byref(rec)), self._h)
+
+    def _column_sums(self, ph):
+        a, b = np.empty((self.H, self.W)), np.empty((self.H, self.W))
+        sec, n = C.c_double(), C.c_int64()
+        _check(ph.get(self._h, _tab(a), _tab(b), C.byref(sec), C.byref(n)), self._h)
+        return ph.result(int(n.value), float(sec.value), a, b)
+
+    def _put_column(self, ph, nsteps, seconds, a, b):
+        a, b = (as_f64(x, (self.H, self.W), name) for x, name in zip((a, b), ph.fields))
+        _check(ph.put(self._h, _tab(a), _tab(b), float(seconds), int(nsteps)), self._h)
+
+    def _column_reset(self, ph):
+        _check(ph.reset(self._h), self._h)
 
     # -- convective adjustment (GCM_PE25D) -------------------------------------------------
     def set_convect(self, *off, **params):
@@ -780,58 +826,37 @@ class Core:
         kappa_c = Rd gamma / g, at most one of the two, neither: the dry adjustment; mix_q (True).  How often and how
         deep each column was adjusted is accumulated (convect_sums); registering again resets the sums.
         set_convect(None) switches the phase off.  ValueError for a refused parameter (the call then changes nothing)"""
-        if off:
-            if off != (None,) or params:
-                raise ValueError("set_convect takes keyword parameters, or None alone to switch the phase off")
-            _check(lib.gcm_set_convect(self._h, None), self._h)
-            self._convect = None
-            return
-        par = convect_params(params)
-        rec = _lib.Convect(*par.values())
-        _check(lib.gcm_set_convect(self._h, C.byref(rec)), self._h)
-        self._convect = dict(par)
+        self._set_column(_CONVECT, off, params)
 
     @property
     def convect(self):
         """the parameters of the registered convective adjustment as a dict (kappa_c, mix_q), or None where the handle
         carries none (gcm_convect_on) -- and also None for one registered through the C call directly"""
-        on = lib.gcm_convect_on(self._h)
-        if on < 0:
-            _check(on, self._h)
-        return dict(self._convect) if on and self._convect else None
+        return self._column_params(_CONVECT)
 
     @property
     def convect_registered(self):
         """whether the handle carries the phase at all (gcm_convect_on), whoever registered it"""
-        on = lib.gcm_convect_on(self._h)
-        if on < 0:
-            _check(on, self._h)
-        return bool(on)
+        return self._column_registered(_CONVECT)
 
     def convect_step(self, **params):
         """the convective adjustment once, in place on the current state (gcm_convect_step); no dt: the adjustment is
         instantaneous.  With a registration the call adds to its counts (and no seconds), without one the counts of the
         call are dropped.  A band: own rows and ghost rows, the ghost rows must be current"""
-        rec = _lib.Convect(*convect_params(params).values())
-        _check(lib.gcm_convect_step(self._h, C.byref(rec)), self._h)
+        self._column_step(_CONVECT, None, params)
 
     def convect_sums(self):
         """-> Convect(nsteps, seconds, count (H, W), levels (H, W)): the float64 sums as the device holds them
         (gcm_get_convect); one synchronisation.  GcmError where no convective adjustment is registered"""
-        count, levels = np.empty((self.H, self.W)), np.empty((self.H, self.W))
-        sec, n = C.c_double(), C.c_int64()
-        _check(lib.gcm_get_convect(self._h, _tab(count), _tab(levels), C.byref(sec), C.byref(n)), self._h)
-        return Convect(int(n.value), float(sec.value), count, levels)
+        return self._column_sums(_CONVECT)
 
     def put_convect(self, nsteps, seconds, count, levels):
         """upload sums taken by convect_sums() (gcm_put_convect): a restart goes on where the run stopped"""
-        count = as_f64(count, (self.H, self.W), "count")
-        levels = as_f64(levels, (self.H, self.W), "levels")
-        _check(lib.gcm_put_convect(self._h, _tab(count), _tab(levels), float(seconds), int(nsteps)), self._h)
+        self._put_column(_CONVECT, nsteps, seconds, count, levels)
 
     def convect_reset(self):
         """zero the sums, the seconds and the count (gcm_convect_reset)"""
-        _check(lib.gcm_convect_reset(self._h), self._h)
+        self._column_reset(_CONVECT)
 
     # -- moist physics (GCM_PE25D) ---------------------------------------------------------
     def set_moist(self, *off, **params):
@@ -843,58 +868,37 @@ class Core:
         (MOIST_DEFAULTS).  Precipitation and evaporation are accumulated per column (moist_sums); registering again
         resets the sums.  set_moist(None) switches the phase off.  ValueError for a refused parameter (the call then
         changes nothing)"""
-        if off:
-            if off != (None,) or params:
-                raise ValueError("set_moist takes keyword parameters, or None alone to switch the phase off")
-            _check(lib.gcm_set_moist(self._h, None), self._h)
-            self._moist = None
-            return
-        par = moist_params(params)
-        rec = _lib.Moist(*par.values())
-        _check(lib.gcm_set_moist(self._h, C.byref(rec)), self._h)
-        self._moist = dict(par)
+        self._set_column(_MOIST, off, params)
 
     @property
     def moist(self):
         """the parameters of the registered moist physics as a dict, or None where the handle carries none
         (gcm_moist_on) -- and also None for one registered through the C call directly"""
-        on = lib.gcm_moist_on(self._h)
-        if on < 0:
-            _check(on, self._h)
-        return dict(self._moist) if on and self._moist else None
+        return self._column_params(_MOIST)
 
     @property
     def moist_registered(self):
         """whether the handle carries the phase at all (gcm_moist_on), whoever registered it"""
-        on = lib.gcm_moist_on(self._h)
-        if on < 0:
-            _check(on, self._h)
-        return bool(on)
+        return self._column_registered(_MOIST)
 
     def moist_step(self, dt, **params):
         """the moist physics once, in place on the current state, with the step dt (gcm_moist_step): what
         held_suarez_step is to set_held_suarez.  With a registration the call adds to its sums, without one the sums
         of the call are dropped.  A band: own rows and ghost rows, the ghost rows must be current"""
-        rec = _lib.Moist(*moist_params(params).values())
-        _check(lib.gcm_moist_step(self._h, float(dt), C.byref(rec)), self._h)
+        self._column_step(_MOIST, dt, params)
 
     def moist_sums(self):
         """-> Moist(nsteps, seconds, precip (H, W), evap (H, W)): the float64 sums as the device holds them
         (gcm_get_moist); one synchronisation.  GcmError where no moist physics is registered"""
-        precip, evap = np.empty((self.H, self.W)), np.empty((self.H, self.W))
-        sec, n = C.c_double(), C.c_int64()
-        _check(lib.gcm_get_moist(self._h, _tab(precip), _tab(evap), C.byref(sec), C.byref(n)), self._h)
-        return Moist(int(n.value), float(sec.value), precip, evap)
+        return self._column_sums(_MOIST)
 
     def put_moist(self, nsteps, seconds, precip, evap):
         """upload sums taken by moist_sums() (gcm_put_moist): a restart goes on where the run stopped"""
-        precip = as_f64(precip, (self.H, self.W), "precip")
-        evap = as_f64(evap, (self.H, self.W), "evap")
-        _check(lib.gcm_put_moist(self._h, _tab(precip), _tab(evap), float(seconds), int(nsteps)), self._h)
+        self._put_column(_MOIST, nsteps, seconds, precip, evap)
 
     def moist_reset(self):
         """zero the sums, the seconds and the count (gcm_moist_reset)"""
-        _check(lib.gcm_moist_reset(self._h), self._h)
+        self._column_reset(_MOIST)
 
     # -- zonal-mean climatology (GCM_PE25D) ------------------------------------------------
     def set_climate(self, every=1):
@@ -907,10 +911,7 @@ class Core:
     @property
     def climate_every(self):
         """the registered sampling interval in steps, 0 where none is registered (gcm_climate_every)"""
-        n = lib.gcm_climate_every(self._h)
-        if n < 0:
-            _check(n, self._h)
-        return n
+        return _count(lib.gcm_climate_every(self._h), self._h)
 
     def climate_sample(self):
         """one sample of the current state now (gcm_climate_sample); the step counter is untouched.  A band: the ghost

@@ -34,12 +34,11 @@ struct GcmTiming {
 };
 
 // GCM_PE25D: the phases registered behind the dynamics of every step (gcm_pe.hip runs them; the climatology's
-// registration is Pe25d's own).  The records' table pointers are null: the vectors are the copies that are used
+// registration is Pe25d's own, and so are the convective adjustment's and the moist physics': pe25d_sums_on -- mo and cv
+// are the parameters their steps run with).  The records' table pointers are null: the vectors are the copies that are used
 struct GcmPhases {
     bool solar = false;                        // gcm_set_physics: solar_timestep as the second phase of every step
     bool held_suarez = false;                  // gcm_set_held_suarez: the forcing behind the solar step
-    bool convect = false;                      // gcm_set_convect: convective adjustment behind the forcing, ahead of the moist physics
-    bool moist = false;                        // gcm_set_moist: condensation and evaporation as the last phase that changes the state
     gcm_physics phys{};                        // phys.utc is the clock: it advances by dt behind every solar step
     gcm_held_suarez hs{};
     gcm_moist mo{};

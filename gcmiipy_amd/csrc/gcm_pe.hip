@@ -10,7 +10,10 @@ using namespace gcm;
 
 // ------------------------------------------------------------------ the phases of a step
 // The order is the model's: the dynamics step, the solar step at the current clock, utc += dt, the Held-Suarez forcing,
-// the convective adjustment, the moist physics, the sample.  Each launch runs only if its phase is registered (GcmPhases; the climatology: pe25d_climate_due).
+// the convective adjustment, the moist physics, the sample.  Each launch runs only if its phase is registered: the solar
+// step and the forcing in GcmPhases, the adjustment and the moist physics where their sums are in place (pe25d_sums_on),
+// the climatology in pe25d_climate_due.  The order is written down in pe_phase_rows, and in pe_phase_tables for what a
+// run prepares ahead of it.
 
 // gcm_set_physics: the radiation kernel's tables in place before a run queues anything (no-op without physics); then the
 // registered forcing's device tables for dt (none: GCM_OK), and the convective adjustment's and the moist physics' level tables and parameters for dt
@@ -25,72 +28,60 @@ int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
         hs.lat = ph.hs_lat.data();
         if (int rc = pe25d_hs_tables(h->pe, &hs, dt, h->stream, &h->err)) return rc;
     }
-    if (ph.convect)
+    if (pe25d_sums_on(h->pe, kSumsConvect))
         if (int rc = pe25d_convect_tables(h->pe, &ph.cv, dt, &h->err)) return rc;
-    if (ph.moist) return pe25d_moist_tables(h->pe, &ph.mo, dt, &h->err);
+    if (pe25d_sums_on(h->pe, kSumsMoist)) return pe25d_moist_tables(h->pe, &ph.mo, dt, &h->err);
     return GCM_OK;
 }
 
-// gcm_band_run with the exchange on the second stream `ax`: the ghost rows' phases, behind a corrector's unpack.
-// With gcm_set_physics the step has a second phase, solar_timestep (no_limits_2_5d.py:66-75), which changes theta and
-// the ground temperature in place AFTER the post-corrector exchange has left: the ghost rows are radiated locally
-// (column-local kernel, the neighbour's own inputs -- theta and p as the exchange delivered them, the ground
-// temperature's ghost rows, the latitude of the global row -- hence the neighbour's own bits), on the second stream
-// right behind the unpack and ahead of the ghost rows' column sums and anchors; the band's own rows follow the
-// corrector on the compute stream, which by then has waited for the edge rows and their pack (pe_own_row_phases).
-int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax) {
-    const GcmPhases &ph = h->phases;
-    const int H = h->H;
-    if (ph.solar)
-        if (int rc = pe25d_solar_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, dt, ph.phys.utc, ph.phys.albedo, ax,
-                                      &h->err))
-            return rc;
-    // gcm_set_held_suarez: the ghost rows of theta, u, v as the post-corrector exchange delivered them, forced
-    // locally (the neighbour's own inputs and tables, hence its own bits), behind the unpack and the ghost rows'
-    // solar step in stream order and AHEAD of the ghost rows' column sums and anchors, which read u, v and theta
-    // (the launch marks the state's column sums stale: pe25d_prep_ghost_rows then leaves them to the next stage)
-    if (ph.held_suarez)
-        if (int rc = pe25d_hs_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, ax, &h->err)) return rc;
-    // gcm_set_convect: the ghost rows of theta and q, behind their Held-Suarez launch and ahead of their moist physics and
-    // of their anchors, which read theta; column-local with the neighbour's own inputs, hence its own bits.  The counts
-    // of ghost rows belong to the neighbour's sums: this launch accumulates nothing
-    if (ph.convect)
-        if (int rc = pe25d_convect_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, false, ax, &h->err)) return rc;
-    // gcm_set_moist: the ghost rows of theta and q, behind their Held-Suarez launch and ahead of their anchors, which
-    // read theta; column-local with the neighbour's own inputs, hence its own bits.  The precipitation of ghost rows
-    // belongs to the neighbour's sums: this launch accumulates nothing
-    if (ph.moist) return pe25d_moist_rows(h->pe, pe25d_new_state_set(h->pe), -kGhost, 0, H, H + kGhost, true, false, ax, &h->err);
-    return GCM_OK;
-}
-
-// The end of every step, on the handle's stream: rows [-g, H + g) (phase_ghosts).  tail: the stream whose tail the
-// handle's stream joins before a sample (gcm_band_run's second stream, where the exchange runs there), else null
-int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail) {
+// The registered phases that change the state, over rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one)
+// on `s`, each launch behind the one before it in stream order.  Every phase is column-local, so a row gets the same bits
+// whichever launch takes it: a single domain's, a band's own rows', a neighbour's ghost rows'.  Two callers:
+//  * own: the end of every step, the rows of the handle on its stream (pe_own_row_phases).  The clock advances behind
+//    the solar step, and the convective adjustment's counts and the moist physics' precipitation and evaporation go to
+//    the handle's sums (the kernels add rows [0, H) only);
+//  * !own: a band's ghost rows as the post-corrector exchange delivered them, on the second stream behind the unpack and
+//    AHEAD of the ghost rows' column sums and anchors, which read u, v and theta (pe_ghost_row_phases).  The rows are
+//    forced locally with the neighbour's own inputs and tables -- theta, p, u, v as delivered, the ground temperature's
+//    ghost rows, the latitude of the global row -- hence to the neighbour's own bits.  Their counts and precipitation
+//    belong to the neighbour's sums: these launches accumulate nothing, and the clock stays.
+// keep_ghosts: the caller forces the ghost rows itself ahead of their column sums and anchors (gcm_band_run)
+static int pe_phase_rows(gcm_handle *h, double dt, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool own, hipStream_t s) {
     GcmPhases &ph = h->phases;
-    const int j0 = -g, j1 = h->H + g;
     if (ph.solar) {
-        // no_limits_2_5d.py:229-234 with the physics below full_timestep's early return (:96): the dynamics
-        // step, then solar_timestep at the current utc, then utc += dt.  A band: own rows (and, when the exchange was
-        // joined into the compute stream, the ghost rows with them)
-        if (int rc = pe25d_solar_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, dt, ph.phys.utc, ph.phys.albedo, h->stream, &h->err)) return rc;
-        ph.phys.utc += dt;
+        // no_limits_2_5d.py:229-234 with the physics below full_timestep's early return (:96): the dynamics step, then
+        // solar_timestep (:66-75) at the current utc, which changes theta and the ground temperature in place AFTER the
+        // post-corrector exchange has left, then utc += dt
+        if (int rc = pe25d_solar_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, dt, ph.phys.utc, ph.phys.albedo, s, &h->err)) return rc;
+        if (own) ph.phys.utc += dt;
     }
-    // gcm_set_held_suarez.  A band: own rows (and the ghost rows with
-    // them where the exchange was joined into the compute stream), behind the corrector and the solar step: the compute
-    // stream has waited for the edge rows' pack by then (update_interior), so the rows that left are unforced and the
-    // neighbour forces them itself.  The launch writes u and v, which the next stage's chain B reads: it invalidates the
-    // fork at the last K4 (pe25d_hs_rows), so that the next step's launches on the second and third stream, which read
-    // own rows' u and v, follow this stream's position
+    // gcm_set_held_suarez, behind the solar step.  The launch writes u and v, which the next stage's chain B reads: it
+    // invalidates the fork at the last K4, so that the next step's launches on the second and third stream, which read own
+    // rows' u and v, follow this stream's position; and it marks the state's column sums stale, so that behind a ghost-row
+    // launch pe25d_prep_ghost_rows leaves them to the next stage (pe25d_phase_wrote)
     if (ph.held_suarez)
-        if (int rc = pe25d_hs_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, h->stream, &h->err)) return rc;
-    // gcm_set_convect: the same rows on the same stream, ahead of the moist physics, which then condenses whatever the
-    // mixing left supersaturated; the own rows' counts go to the handle's sums (the kernel adds rows [0, H) only)
-    if (ph.convect)
-        if (int rc = pe25d_convect_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, true, h->stream, &h->err)) return rc;
-    // gcm_set_moist: the last phase of the step that changes the state, the same rows on the same stream; the own rows'
-    // precipitation and evaporation go to the handle's sums (the kernel adds rows [0, H) only)
-    if (ph.moist)
-        if (int rc = pe25d_moist_rows(h->pe, -1, j0, j1, 0, 0, keep_ghosts, true, h->stream, &h->err)) return rc;
+        if (int rc = pe25d_hs_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, s, &h->err)) return rc;
+    // gcm_set_convect: theta and q, ahead of the moist physics, which then condenses whatever the mixing left supersaturated
+    if (pe25d_sums_on(h->pe, kSumsConvect))
+        if (int rc = pe25d_convect_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, own, s, &h->err)) return rc;
+    // gcm_set_moist: theta and q, the last phase of the step that changes the state
+    if (pe25d_sums_on(h->pe, kSumsMoist)) return pe25d_moist_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, own, s, &h->err);
+    return GCM_OK;
+}
+
+// gcm_band_run with the exchange on the second stream `ax`: the ghost rows' phases, behind a corrector's unpack and ahead
+// of pe25d_prep_ghost_rows; the band's own rows follow the corrector on the compute stream (pe_own_row_phases)
+int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax) {
+    return pe_phase_rows(h, dt, pe25d_new_state_set(h->pe), -kGhost, 0, h->H, h->H + kGhost, true, false, ax);
+}
+
+// The end of every step, on the handle's stream: rows [-g, H + g) (phase_ghosts) -- a band's own rows, and the ghost rows
+// with them where the exchange was joined into the compute stream.  The compute stream has waited for the edge rows and
+// their pack by then (update_interior), so the rows that left are as the corrector made them and the neighbour forces
+// them itself.  tail: the stream whose tail the handle's stream joins before a sample (gcm_band_run's second stream,
+// where the exchange runs there), else null
+int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail) {
+    if (int rc = pe_phase_rows(h, dt, -1, -g, h->H + g, 0, 0, keep_ghosts, true, h->stream)) return rc;
     // gcm_set_climate: a sample of the state the step leaves, behind every phase that changes it
     if (!pe25d_climate_due(h->pe)) return GCM_OK;
     // a band: the sample reads the own rows as the phases above left them on the compute stream, and row -1 of v,
@@ -306,15 +297,16 @@ int gcm_set_convect(gcm_handle *h, const gcm_convect *cv) {
     if (cv)
         if (int rc = convect_check(cv, "gcm_set_convect", &h->err)) return rc;
     if (int rc = select_device(h)) return rc;
-    if (int rc = pe25d_set_convect(h->pe, cv != nullptr, h->stream, &h->err)) return rc;
-    h->phases.convect = cv != nullptr;
+    if (cv)
+        if (int rc = pe25d_convect_fits(h->pe, "gcm_set_convect", &h->err)) return rc;
+    if (int rc = pe25d_sums_set(h->pe, kSumsConvect, cv != nullptr, h->stream, &h->err)) return rc;
     if (cv) h->phases.cv = *cv;
     return GCM_OK;
 }
 
 int gcm_convect_on(const gcm_handle *h) {
     if (!h) return GCM_ERR_ARG;
-    return h->pe && h->phases.convect ? 1 : 0;
+    return h->pe && pe25d_sums_on(h->pe, kSumsConvect) ? 1 : 0;
 }
 
 int gcm_convect_step(gcm_handle *h, const gcm_convect *cv) {
@@ -326,22 +318,22 @@ int gcm_convect_step(gcm_handle *h, const gcm_convect *cv) {
     // a band: own rows and ghost rows, as gcm_moist_step (the ghost rows of the current state must be current); the
     // counts of the call go to the registration's accumulators, or nowhere
     const int g = phase_ghosts(h);
-    return pe25d_convect_rows(h->pe, -1, -g, h->H + g, 0, 0, false, pe25d_convect_on(h->pe), h->stream, &h->err);
+    return pe25d_convect_rows(h->pe, -1, -g, h->H + g, 0, 0, false, pe25d_sums_on(h->pe, kSumsConvect), h->stream, &h->err);
 }
 
 int gcm_get_convect(gcm_handle *h, double *count, double *levels, double *seconds, int64_t *nsteps) {
     if (int rc = pe_on_device(h, "gcm_get_convect")) return rc;
-    return pe25d_get_convect(h->pe, count, levels, seconds, nsteps, h->stream, &h->err);
+    return pe25d_sums_get(h->pe, kSumsConvect, count, levels, seconds, nsteps, h->stream, &h->err);
 }
 
 int gcm_put_convect(gcm_handle *h, const double *count, const double *levels, double seconds, int64_t nsteps) {
     if (int rc = pe_on_device(h, "gcm_put_convect")) return rc;
-    return pe25d_put_convect(h->pe, count, levels, seconds, nsteps, h->stream, &h->err);
+    return pe25d_sums_put(h->pe, kSumsConvect, count, levels, seconds, nsteps, h->stream, &h->err);
 }
 
 int gcm_convect_reset(gcm_handle *h) {
     if (int rc = pe_on_device(h, "gcm_convect_reset")) return rc;
-    return pe25d_convect_reset(h->pe, h->stream, &h->err);
+    return pe25d_sums_reset(h->pe, kSumsConvect, h->stream, &h->err);
 }
 
 int gcm_convect_columns(int ncol, int L, const double *y, const double *w, const double *q, const double *dsig, int mix_q,
@@ -355,15 +347,14 @@ int gcm_set_moist(gcm_handle *h, const gcm_moist *mo) {
     if (mo)
         if (int rc = moist_check(mo, "gcm_set_moist", &h->err)) return rc;
     if (int rc = select_device(h)) return rc;
-    if (int rc = pe25d_set_moist(h->pe, mo != nullptr, h->stream, &h->err)) return rc;
-    h->phases.moist = mo != nullptr;
+    if (int rc = pe25d_sums_set(h->pe, kSumsMoist, mo != nullptr, h->stream, &h->err)) return rc;
     if (mo) h->phases.mo = *mo;
     return GCM_OK;
 }
 
 int gcm_moist_on(const gcm_handle *h) {
     if (!h) return GCM_ERR_ARG;
-    return h->pe && h->phases.moist ? 1 : 0;
+    return h->pe && pe25d_sums_on(h->pe, kSumsMoist) ? 1 : 0;
 }
 
 int gcm_moist_step(gcm_handle *h, double dt, const gcm_moist *mo) {
@@ -375,22 +366,22 @@ int gcm_moist_step(gcm_handle *h, double dt, const gcm_moist *mo) {
     // a band: own rows and ghost rows, as gcm_held_suarez_step (the ghost rows of the current state must be current);
     // the sums of the call go to the registration's accumulators, or nowhere
     const int g = phase_ghosts(h);
-    return pe25d_moist_rows(h->pe, -1, -g, h->H + g, 0, 0, false, pe25d_moist_on(h->pe), h->stream, &h->err);
+    return pe25d_moist_rows(h->pe, -1, -g, h->H + g, 0, 0, false, pe25d_sums_on(h->pe, kSumsMoist), h->stream, &h->err);
 }
 
 int gcm_get_moist(gcm_handle *h, double *precip, double *evap, double *seconds, int64_t *nsteps) {
     if (int rc = pe_on_device(h, "gcm_get_moist")) return rc;
-    return pe25d_get_moist(h->pe, precip, evap, seconds, nsteps, h->stream, &h->err);
+    return pe25d_sums_get(h->pe, kSumsMoist, precip, evap, seconds, nsteps, h->stream, &h->err);
 }
 
 int gcm_put_moist(gcm_handle *h, const double *precip, const double *evap, double seconds, int64_t nsteps) {
     if (int rc = pe_on_device(h, "gcm_put_moist")) return rc;
-    return pe25d_put_moist(h->pe, precip, evap, seconds, nsteps, h->stream, &h->err);
+    return pe25d_sums_put(h->pe, kSumsMoist, precip, evap, seconds, nsteps, h->stream, &h->err);
 }
 
 int gcm_moist_reset(gcm_handle *h) {
     if (int rc = pe_on_device(h, "gcm_moist_reset")) return rc;
-    return pe25d_moist_reset(h->pe, h->stream, &h->err);
+    return pe25d_sums_reset(h->pe, kSumsMoist, h->stream, &h->err);
 }
 
 int gcm_moist_saturation(int n, const double *T, const double *p_lev, double *q_s, double *dq_s, int *can) {

@@ -243,18 +243,6 @@ __global__ __launch_bounds__(kCvThreads) void pe_convect_kernel(CvArgsT<T> a) {
 }
 
 // ---------------------------------------------------------------- the handle's side
-static int cv_hip(hipError_t e, const char *fn, std::string *err) {
-    if (e == hipSuccess) return GCM_OK;
-    *err = std::string("hip: ") + fn + ": " + hipGetErrorString(e);
-    return GCM_ERR_HIP;
-}
-static int cv_registered(const Pe25d *m, const char *fn, std::string *err) {
-    if (m->convect.acc) return GCM_OK;
-    *err = std::string(fn) + ": no convective adjustment registered (gcm_set_convect)";
-    return GCM_ERR_STATE;
-}
-static size_t cv_words(const Pe25d *m) { return (size_t)m->H * m->W; }
-
 // the wave's stack at the handle's L must fit a workgroup's LDS (160 KB); the kernel's dynamic LDS size is set once, here (the
 // kernel is instantiated and launched in this unit alone)
 int pe25d_convect_fits(Pe25d *m, const char *fn, std::string *err) {
@@ -267,50 +255,19 @@ int pe25d_convect_fits(Pe25d *m, const char *fn, std::string *err) {
         return GCM_ERR_UNSUPPORTED;
     }
     const void *k = m->f32 ? (const void *)pe_convect_kernel<float> : (const void *)pe_convect_kernel<double>;
-    if (int rc = cv_hip(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need), fn, err)) return rc;
+    if (int rc = hip_rc(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need), fn, err)) return rc;
     z.lds_bytes = need;
     return GCM_OK;
 }
 
-// gcm_set_convect: on -- the accumulators in place and zero; off -- freed
-int pe25d_set_convect(Pe25d *m, bool on, hipStream_t s, std::string *err) {
-    PeConvect &z = m->convect;
-    if (!on) {
-        if (!z.acc) return GCM_OK;
-        // (a launch may still be adding to the sums)
-        if (int rc = cv_hip(hipStreamSynchronize(s), "gcm_set_convect", err)) return rc;
-        m->allocs.erase(std::remove(m->allocs.begin(), m->allocs.end(), (void *)z.acc), m->allocs.end());
-        (void)hipFree(z.acc);
-        z.acc = nullptr;
-        z.seconds = 0.0;
-        z.n = 0;
-        return GCM_OK;
-    }
-    if (int rc = pe25d_convect_fits(m, "gcm_set_convect", err)) return rc;
-    if (!z.acc) {
-        if (!dev_upload<double>(m, &z.acc, nullptr, 2 * cv_words(m))) { *err = "hip: gcm_set_convect allocation failed"; return GCM_ERR_HIP; }
-    } else if (int rc = cv_hip(hipMemsetAsync(z.acc, 0, sizeof(double) * 2 * cv_words(m), s), "gcm_set_convect", err)) {
-        return rc;
-    }
-    z.seconds = 0.0;
-    z.n = 0;
-    return GCM_OK;
-}
-
-bool pe25d_convect_on(const Pe25d *m) { return m->convect.acc != nullptr; }
-
-// the launches' level tables (sig, dsig in float64, uploaded once) and the parameters of the launches that follow; dt:
+// the launches' level tables (pe25d_level_table) and the parameters of the launches that follow; dt:
 // what an accumulating launch adds to the seconds (the step's dt; 0 for gcm_convect_step, which takes none)
 int pe25d_convect_tables(Pe25d *m, const gcm_convect *cv, double dt, std::string *err) {
     if (int rc = convect_check(cv, "convect", err)) return rc;
     if (!std::isfinite(dt)) { *err = "convect: dt must be finite"; return GCM_ERR_ARG; }
     if (int rc = pe25d_convect_fits(m, "convect", err)) return rc;
+    if (!pe25d_level_table(m, "convect", err)) return GCM_ERR_HIP;
     PeConvect &z = m->convect;
-    if (!z.tab) {
-        std::vector<double> t(m->sig_host);
-        t.insert(t.end(), m->dsig_host.begin(), m->dsig_host.end());
-        if (!dev_upload<double>(m, &z.tab, t.data(), t.size())) { *err = "hip: convect table upload failed"; return GCM_ERR_HIP; }
-    }
     z.kappa_c = cv->kappa_c;
     z.mix_q = cv->mix_q;
     z.dt = dt;
@@ -323,10 +280,10 @@ static int cv_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool a
     const PeConvect &z = m->convect;
     CvArgsT<T> a{};
     a.p = B.st[set][GCM_P]; a.t = B.st[set][GCM_T]; a.q = B.st[set][GCM_Q];
-    a.sig = z.tab; a.dsig = z.tab + m->L;
+    a.sig = m->lev_tab; a.dsig = m->lev_tab + m->L;
     a.exner_tab = m->exner_tab;
-    a.count = accumulate ? z.acc : nullptr;
-    a.levels = accumulate ? z.acc + cv_words(m) : nullptr;
+    a.count = accumulate ? z.sums.acc : nullptr;
+    a.levels = accumulate ? z.sums.acc + (size_t)m->H * m->W : nullptr;
     a.ptop = m->cfg.ptop; a.kdiff = z.kappa_c - kKappa;
     a.dry = z.kappa_c == 0.0 ? 1 : 0; a.mix_q = z.mix_q;
     a.W = m->W; a.L = m->L; a.H = m->H;
@@ -342,74 +299,15 @@ static int cv_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool a
 int pe25d_convect_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool accumulate, hipStream_t s,
                        std::string *err) {
     PeConvect &z = m->convect;
-    if (!z.tab || !z.lds_bytes) { *err = "convect: no tables in place"; return GCM_ERR_STATE; }
-    if (accumulate && !z.acc) { *err = "convect: no sums to accumulate into (gcm_set_convect)"; return GCM_ERR_STATE; }
+    if (!m->lev_tab || !z.lds_bytes) { *err = "convect: no tables in place"; return GCM_ERR_STATE; }
+    if (accumulate && !z.sums.acc) { *err = "convect: no sums to accumulate into (gcm_set_convect)"; return GCM_ERR_STATE; }
     if (set < 0) set = m->cur_i;
     if (std::max(0, j1 - j0) + std::max(0, jb1 - jb0) <= 0) return GCM_OK;
-    // Invariants of a launch, against pe25d_hs_rows' four.  The launch writes theta and q and reads p, theta and q:
-    //  * the column sums K4 left for this state (sum_k dsig u, sum_k dsig v) stay valid: u and v are not touched.  For the
-    //    same reason the wait for the third stream's column sums of the edge rows (which read u and v) is not needed;
-    //  * the fork at the last K4 stays, as behind the in-place radiation: what the next stage queues on the second and
-    //    third stream ahead of its wait for this stream (ev_join, behind K3) -- the ghost rows' column sums and anchors,
-    //    K1 and pit, the edge rows' partial sums, the tracers -- reads u, v, p, the intermediates and ghost-row theta, never
-    //    own-row theta or q, and writes none of p, theta, q of this set; the edge rows' K4, which reads them, waits for
-    //    ev_join.  The exception is a band whose ghost rows this launch takes with the own rows on this stream
-    //    (gcm_convect_step, the host-driven exchange): the ghost rows' anchors on the second stream read their theta, so
-    //    chain B must follow this stream's position;
-    //  * the ghost rows' geopotential anchors were formed from theta as it was, unless the caller forces the ghost rows
-    //    itself ahead of them (keep_ghosts: gcm_band_run);
-    //  * the parity tap's stage state is gone: theta changed.
-    if (!keep_ghosts) m->ghost_ready = -1;
-    if (!(keep_ghosts || m->wrap)) m->k4_fork_valid = false;
-    m->last_stage_set = -1;                                // gcm_get_intermediate: theta changed
+    pe25d_phase_wrote(m, set, keep_ghosts, false);         // the launch writes theta and q and reads p, theta and q
     if (int rc = m->f32 ? cv_launch<float>(m, set, j0, j1, jb0, jb1, accumulate, s, err)
                         : cv_launch<double>(m, set, j0, j1, jb0, jb1, accumulate, s, err))
         return rc;
-    if (accumulate) {
-        z.seconds += z.dt;
-        ++z.n;
-    }
-    return GCM_OK;
-}
-
-int pe25d_convect_reset(Pe25d *m, hipStream_t s, std::string *err) {
-    if (int rc = cv_registered(m, "gcm_convect_reset", err)) return rc;
-    PeConvect &z = m->convect;
-    if (int rc = cv_hip(hipMemsetAsync(z.acc, 0, sizeof(double) * 2 * cv_words(m), s), "gcm_convect_reset", err)) return rc;
-    z.seconds = 0.0;
-    z.n = 0;
-    return GCM_OK;
-}
-
-int pe25d_get_convect(Pe25d *m, double *count, double *levels, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err) {
-    if (int rc = cv_registered(m, "gcm_get_convect", err)) return rc;
-    const PeConvect &z = m->convect;
-    const size_t bytes = sizeof(double) * cv_words(m);
-    hipError_t e = hipSuccess;
-    if (count) e = hipMemcpyAsync(count, z.acc, bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && levels) e = hipMemcpyAsync(levels, z.acc + cv_words(m), bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (int rc = cv_hip(e, "gcm_get_convect", err)) return rc;
-    if (seconds) *seconds = z.seconds;
-    if (nsteps) *nsteps = z.n;
-    return GCM_OK;
-}
-
-int pe25d_put_convect(Pe25d *m, const double *count, const double *levels, double seconds, int64_t nsteps, hipStream_t s,
-                      std::string *err) {
-    if (int rc = cv_registered(m, "gcm_put_convect", err)) return rc;
-    if (!count || !levels || !std::isfinite(seconds) || seconds < 0.0 || nsteps < 0) {
-        *err = "gcm_put_convect: count and levels are required, seconds must be finite and >= 0, nsteps >= 0";
-        return GCM_ERR_ARG;
-    }
-    PeConvect &z = m->convect;
-    const size_t bytes = sizeof(double) * cv_words(m);
-    hipError_t e = hipMemcpyAsync(z.acc, count, bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(z.acc + cv_words(m), levels, bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);          // (the caller's arrays are free again when the call returns)
-    if (int rc = cv_hip(e, "gcm_put_convect", err)) return rc;
-    z.seconds = seconds;
-    z.n = nsteps;
+    if (accumulate) sums_count(z.sums, z.dt);
     return GCM_OK;
 }
 

@@ -241,20 +241,7 @@ int pe25d_hs_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep
         (void)hipStreamWaitEvent(s, m->ev_cs, 0);
         m->edge_cs_set = -1;
     }
-    // Invariants of a launch (this is the first physics phase that writes u and v):
-    //  * the column sums K4 left for this state (sum_k dsig u, sum_k dsig v: pit of the next stage) belong to the winds as
-    //    they were: they are no longer valid, and the next stage sums every row again (prep_rows, the path of a freshly set
-    //    state) -- on a band too, where pe25d_prep_ghost_rows then leaves the ghost rows' sums to that launch.  A single
-    //    domain and a band so form them by the same kernel in the same order: the same bits;
-    //  * the next stage's chain B (K1, the column sums) reads u and v, so it may not fork at the last K4's stop event as
-    //    it does behind the in-place radiation (which changes theta alone, and chain B reads no theta): it follows this
-    //    stream's position (ev_fork, recorded behind this launch), and so does everything that waits for that fork;
-    //  * the ghost rows' geopotential anchors were formed from theta as it was, unless the caller forces the ghost rows
-    //    itself ahead of them (keep_ghosts: gcm_band_run).
-    m->cs_valid[set] = false;
-    m->k4_fork_valid = false;
-    if (!keep_ghosts) m->ghost_ready = -1;
-    m->last_stage_set = -1;                                // gcm_get_intermediate: theta changed
+    pe25d_phase_wrote(m, set, keep_ghosts, true);          // the launch writes theta, u and v and reads p with them
     return m->f32 ? hs_launch<float>(m, set, j0, j1, jb0, jb1, s, err) : hs_launch<double>(m, set, j0, j1, jb0, jb1, s, err);
 }
 

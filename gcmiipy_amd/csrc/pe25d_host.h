@@ -1,14 +1,15 @@
 // Host side of GCM_PE25D, private to its five host units: the handle and the few helpers they share.
 //   pe25d_state.hip    the handle's life cycle and data movement: create / destroy (and the one reader of the GCM_PE_*
-//                      switches), the streams, set / get and the layout transposes, halo buffers and segments
+//                      switches), the streams, set / get and the layout transposes, halo buffers and segments; what the
+//                      phases behind the dynamics share: their column sums, the level table, pe25d_phase_wrote
 //   pe25d_kernels.hip  the stage orchestration (half_t and its steps) and the column kernels K2 it launches
 //   pe25d_physics.hip  grey radiation and the ground temperature
 //   pe25d_diag.hip     diagnostics and taps: gcm_stats, the polar filter of a field, the stage's intermediates
 //   pe25d_tracers.hip  the passive tracers' host side
 //   pe25d_held_suarez.hip  the Held-Suarez forcing: its table routine, its kernel and its launches
 //   pe25d_climate.hip  the zonal-mean climatology: its kernel, its sums and their way to the host and back
-//   pe25d_moist.hip    moist physics: the saturation routine, the kernel, its launches and its sums
-//   pe25d_convect.hip  convective adjustment: the pooling routine, the kernel, its launches and its sums
+//   pe25d_moist.hip    moist physics: the saturation routine, the kernel and its launches
+//   pe25d_convect.hip  convective adjustment: the pooling routine, the kernel and its launches
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
 // gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
@@ -104,24 +105,32 @@ struct PeClimate {
     long long n = 0;                            // samples in the sums
 };
 
-// Moist physics (pe25d_moist.hip, gcm_set_moist): the float64 sums on the device with their two counters, the level
-// tables of the launches and the parameters of the launches that follow (pe25d_moist_tables)
-struct PeMoist {
-    double *acc = nullptr;                      // device: precip [H][W], evap [H][W]; non-null: registered
+// The float64 column sums of a phase that runs behind the dynamics, with their two counters: two [H][W] fields of the
+// band's own rows.  One set of routines serves every such phase (pe25d_sums_*, pe25d_state.hip); kPeSumsWords holds the
+// words in which their messages differ
+struct PeColumnSums {
+    double *acc = nullptr;                      // device: the first field [H][W], then the second; non-null: registered
     double seconds = 0.0;                       // sum of dt over the applications in the sums
     long long n = 0;                            // applications in the sums
-    double *tab = nullptr;                      // device: sig [L], dsig [L], float64
+};
+struct PeSumsWords { const char *name, *what, *a, *b; };   // gcm_set_<name>, "no <what> registered", the two fields
+constexpr PeSumsWords kPeSumsWords[] = {{"convect", "convective adjustment", "count", "levels"},     // kSumsConvect
+                                        {"moist", "moist physics", "precip", "evap"}};               // kSumsMoist
+// an accumulating launch went out: one application of dt
+inline void sums_count(PeColumnSums &z, double dt) { z.seconds += dt; ++z.n; }
+
+// Moist physics (pe25d_moist.hip, gcm_set_moist): the sums (precip, evap) and the parameters of the launches that follow
+// (pe25d_moist_tables)
+struct PeMoist {
+    PeColumnSums sums;
     int kb = 0;                                 // the level with the largest sig: the one the surface moistens
     double lc = 0.0, x = 0.0, rh_s = 0.0, dt = 0.0;   // Lv / Cp, dt / tau_e (0: no evaporation), rh_s, dt
 };
 
-// Convective adjustment (pe25d_convect.hip, gcm_set_convect): the float64 sums on the device with their two counters, the
-// level tables of the launches and the parameters of the launches that follow (pe25d_convect_tables)
+// Convective adjustment (pe25d_convect.hip, gcm_set_convect): the sums (count, levels; their seconds count the registered
+// steps' dt only) and the parameters of the launches that follow (pe25d_convect_tables)
 struct PeConvect {
-    double *acc = nullptr;                      // device: count [H][W], levels [H][W]; non-null: registered
-    double seconds = 0.0;                       // sum of dt over the registered steps in the sums
-    long long n = 0;                            // applications in the sums
-    double *tab = nullptr;                      // device: sig [L], dsig [L], float64
+    PeColumnSums sums;
     size_t lds_bytes = 0;                       // the kernel's dynamic LDS at the handle's L; 0: not checked against the device yet
     double kappa_c = 0.0, dt = 0.0;             // the neutral profile (0: dry); what an accumulating launch adds to seconds
     int mix_q = 0;
@@ -150,6 +159,7 @@ struct Pe25d {
     int pack_set = -1;                          // >= 0: state set gcm_halo_pack reads (step_phase)
     double *stage3 = nullptr;                   // float64 transpose staging, host layout
     double *exner_tab = nullptr;
+    double *lev_tab = nullptr;                  // sig [L], dsig [L] in float64, uploaded on first use (pe25d_level_table)
     FftPlan plan{};
     SuperPlan cplan{};
     double *gt = nullptr;                       // ground temperature [H + 2 ghost rows a side][W], interior row 0 (column physics)
@@ -238,6 +248,13 @@ inline bool dev_upload(Pe25d *m, T **dst, const T *src, size_t count) {
     return true;
 }
 
+// a HIP status as an entry point's return code, the message prefixed with the entry point's name
+inline int hip_rc(hipError_t e, const char *fn, std::string *err) {
+    if (e == hipSuccess) return GCM_OK;
+    *err = std::string("hip: ") + fn + ": " + hipGetErrorString(e);
+    return GCM_ERR_HIP;
+}
+
 inline size_t rows_alloc(const Pe25d *m) { return (size_t)m->H + 2 * kGhost; }
 
 template <typename T>
@@ -297,6 +314,12 @@ inline PeArgsT<T> make_args(Pe25d *m, int stage_set, int out_set, double dt) {
 // (pe25d_physics.hip).  pe25d_create calls both; false: hipFuncSetAttribute failed
 bool stage_lds_attributes(const Pe25d *m);
 bool radiation_lds_attribute(const Pe25d *m);
+
+// What the moist physics and the convective adjustment share (pe25d_state.hip).  pe25d_level_table: sig [L], then dsig
+// [L], in float64 on the device, uploaded by the first call; null with *err = "hip: <who> table upload failed".
+// pe25d_phase_wrote: the handle's bookkeeping behind a launch that changes state set `set` in place, see there
+const double *pe25d_level_table(Pe25d *m, const char *who, std::string *err);
+void pe25d_phase_wrote(Pe25d *m, int set, bool keep_ghosts, bool wrote_uv);
 
 // Host layout [levels][H][W], float64, <-> a device field [j][levels][i] of the handle's own rows in its real type: the
 // copy through the staging buffer and the transpose, queued on `s`; the caller synchronises (pe25d_state.hip)

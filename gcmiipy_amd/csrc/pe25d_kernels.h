@@ -65,39 +65,39 @@ int pe25d_climate_sample(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_climate_reset(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_get_climate(Pe25d *m, double *m3, double *m2, int64_t *nsamples, hipStream_t s, std::string *err);
 int pe25d_put_climate(Pe25d *m, const double *m3, const double *m2, int64_t nsamples, hipStream_t s, std::string *err);
+// The column sums of the convective adjustment (count, levels) and of the moist physics (precip, evap), one set of
+// routines for both (pe25d_state.hip), on `s`, the caller's stream.  pe25d_sums_set: allocated and zeroed (on) or freed;
+// a phase is registered where its sums are in place, and pe25d_sums_on is the one place that says so.  reset, get and
+// put are gcm_<phase>_reset, gcm_get_<phase> and gcm_put_<phase>: GCM_ERR_STATE where the phase is not registered
+enum PeSums { kSumsConvect, kSumsMoist };
+int pe25d_sums_set(Pe25d *m, PeSums of, bool on, hipStream_t s, std::string *err);
+bool pe25d_sums_on(const Pe25d *m, PeSums of);
+int pe25d_sums_reset(Pe25d *m, PeSums of, hipStream_t s, std::string *err);
+int pe25d_sums_get(Pe25d *m, PeSums of, double *a, double *b, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err);
+int pe25d_sums_put(Pe25d *m, PeSums of, const double *a, const double *b, double seconds, int64_t nsteps, hipStream_t s, std::string *err);
 // Moist physics (pe25d_moist.hip).  moist_check / moist_saturation_table: no handle, no device (gcm_moist_saturation).
-// pe25d_set_moist: the sums allocated and zeroed (on) or freed; pe25d_moist_tables: the level tables in place (uploaded
-// once) and (mo, dt) as the parameters of the launches that follow; pe25d_moist_rows: the kernel over rows [j0, j1) and
-// [jb0, jb1) of state set `set` (-1: the current one) on `s`; keep_ghosts as for pe25d_solar_rows; accumulate: the own
-// rows' precipitation and evaporation go to the registered sums and the call counts as one application of dt
+// pe25d_moist_tables: the level tables in place and (mo, dt) as the parameters of the launches that follow;
+// pe25d_moist_rows: the kernel over rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one) on `s`;
+// keep_ghosts as for pe25d_solar_rows; accumulate: the own rows' precipitation and evaporation go to the registered sums
+// and the call counts as one application of dt
 int moist_check(const gcm_moist *mo, const char *fn, std::string *err);
 int moist_saturation_table(int n, const double *T, const double *p_lev, double *q_s, double *dq_s, int *can, std::string *err);
-int pe25d_set_moist(Pe25d *m, bool on, hipStream_t s, std::string *err);
-bool pe25d_moist_on(const Pe25d *m);
 int pe25d_moist_tables(Pe25d *m, const gcm_moist *mo, double dt, std::string *err);
 int pe25d_moist_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool accumulate, hipStream_t s,
                      std::string *err);
-int pe25d_moist_reset(Pe25d *m, hipStream_t s, std::string *err);
-int pe25d_get_moist(Pe25d *m, double *precip, double *evap, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err);
-int pe25d_put_moist(Pe25d *m, const double *precip, const double *evap, double seconds, int64_t nsteps, hipStream_t s, std::string *err);
 // Convective adjustment (pe25d_convect.hip).  convect_check / convect_columns: no handle, no device (gcm_convect_columns).
-// pe25d_set_convect: the sums allocated and zeroed (on) or freed; GCM_ERR_UNSUPPORTED where the block stack of the handle's
-// L does not fit a workgroup's LDS; pe25d_convect_tables: the level tables in place (uploaded once) and cv as the
-// parameters of the launches that follow, dt what an accumulating launch adds to the seconds; pe25d_convect_rows: the
-// kernel over rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one) on `s`; keep_ghosts as for
-// pe25d_solar_rows; accumulate: the own rows' counts go to the registered sums and the call counts as one application
+// pe25d_convect_fits: ahead of pe25d_sums_set(kSumsConvect, on); GCM_ERR_UNSUPPORTED where the block stack of the handle's
+// L does not fit a workgroup's LDS; pe25d_convect_tables: the level tables in place and cv as the parameters of the
+// launches that follow, dt what an accumulating launch adds to the seconds; pe25d_convect_rows: the kernel over rows
+// [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one) on `s`; keep_ghosts as for pe25d_solar_rows;
+// accumulate: the own rows' counts go to the registered sums and the call counts as one application
 int convect_check(const gcm_convect *cv, const char *fn, std::string *err);
 int convect_columns(int ncol, int L, const double *y, const double *w, const double *q, const double *dsig, int mix_q,
                     double *y_out, double *q_out, int32_t *nblock, std::string *err);
-int pe25d_set_convect(Pe25d *m, bool on, hipStream_t s, std::string *err);
-bool pe25d_convect_on(const Pe25d *m);
+int pe25d_convect_fits(Pe25d *m, const char *fn, std::string *err);
 int pe25d_convect_tables(Pe25d *m, const gcm_convect *cv, double dt, std::string *err);
 int pe25d_convect_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool accumulate, hipStream_t s,
                        std::string *err);
-int pe25d_convect_reset(Pe25d *m, hipStream_t s, std::string *err);
-int pe25d_get_convect(Pe25d *m, double *count, double *levels, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err);
-int pe25d_put_convect(Pe25d *m, const double *count, const double *levels, double seconds, int64_t nsteps, hipStream_t s,
-                      std::string *err);
 int pe25d_new_state_set(const Pe25d *m);    // the set a corrector stage in flight writes (before the swap), else the current one
 int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err);
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan

@@ -154,55 +154,13 @@ __global__ __launch_bounds__(kMoThreads) void pe_moist_kernel(MoArgsT<T> a) {
 }
 
 // ---------------------------------------------------------------- the handle's side
-static int mo_hip(hipError_t e, const char *fn, std::string *err) {
-    if (e == hipSuccess) return GCM_OK;
-    *err = std::string("hip: ") + fn + ": " + hipGetErrorString(e);
-    return GCM_ERR_HIP;
-}
-static int mo_registered(const Pe25d *m, const char *fn, std::string *err) {
-    if (m->moist.acc) return GCM_OK;
-    *err = std::string(fn) + ": no moist physics registered (gcm_set_moist)";
-    return GCM_ERR_STATE;
-}
-static size_t mo_words(const Pe25d *m) { return (size_t)m->H * m->W; }
-
-// gcm_set_moist: on -- the accumulators in place and zero; off -- freed
-int pe25d_set_moist(Pe25d *m, bool on, hipStream_t s, std::string *err) {
-    PeMoist &z = m->moist;
-    if (!on) {
-        if (!z.acc) return GCM_OK;
-        // (a launch may still be adding to the sums)
-        if (int rc = mo_hip(hipStreamSynchronize(s), "gcm_set_moist", err)) return rc;
-        m->allocs.erase(std::remove(m->allocs.begin(), m->allocs.end(), (void *)z.acc), m->allocs.end());
-        (void)hipFree(z.acc);
-        z.acc = nullptr;
-        z.seconds = 0.0;
-        z.n = 0;
-        return GCM_OK;
-    }
-    if (!z.acc) {
-        if (!dev_upload<double>(m, &z.acc, nullptr, 2 * mo_words(m))) { *err = "hip: gcm_set_moist allocation failed"; return GCM_ERR_HIP; }
-    } else if (int rc = mo_hip(hipMemsetAsync(z.acc, 0, sizeof(double) * 2 * mo_words(m), s), "gcm_set_moist", err)) {
-        return rc;
-    }
-    z.seconds = 0.0;
-    z.n = 0;
-    return GCM_OK;
-}
-
-bool pe25d_moist_on(const Pe25d *m) { return m->moist.acc != nullptr; }
-
-// the launches' level tables (sig, dsig in float64, uploaded once) and the parameters of the launches that follow
+// the launches' level tables (pe25d_level_table) and the parameters of the launches that follow
 int pe25d_moist_tables(Pe25d *m, const gcm_moist *mo, double dt, std::string *err) {
     if (int rc = moist_check(mo, "moist", err)) return rc;
     if (!std::isfinite(dt)) { *err = "moist: dt must be finite"; return GCM_ERR_ARG; }
+    if (!pe25d_level_table(m, "moist", err)) return GCM_ERR_HIP;
     PeMoist &z = m->moist;
-    if (!z.tab) {
-        std::vector<double> t(m->sig_host);
-        t.insert(t.end(), m->dsig_host.begin(), m->dsig_host.end());
-        if (!dev_upload<double>(m, &z.tab, t.data(), t.size())) { *err = "hip: moist table upload failed"; return GCM_ERR_HIP; }
-        z.kb = (int)(std::max_element(m->sig_host.begin(), m->sig_host.end()) - m->sig_host.begin());
-    }
+    z.kb = (int)(std::max_element(m->sig_host.begin(), m->sig_host.end()) - m->sig_host.begin());
     z.lc = mo->Lv / kCp;
     z.x = mo->tau_e > 0.0 ? dt / mo->tau_e : 0.0;
     z.rh_s = mo->rh_s;
@@ -216,10 +174,10 @@ static int mo_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool a
     const PeMoist &z = m->moist;
     MoArgsT<T> a{};
     a.p = B.st[set][GCM_P]; a.t = B.st[set][GCM_T]; a.q = B.st[set][GCM_Q];
-    a.sig = z.tab; a.dsig = z.tab + m->L;
+    a.sig = m->lev_tab; a.dsig = m->lev_tab + m->L;
     a.exner_tab = m->exner_tab;
-    a.precip = accumulate ? z.acc : nullptr;
-    a.evap = accumulate ? z.acc + mo_words(m) : nullptr;
+    a.precip = accumulate ? z.sums.acc : nullptr;
+    a.evap = accumulate ? z.sums.acc + (size_t)m->H * m->W : nullptr;
     a.ptop = m->cfg.ptop; a.lc = z.lc; a.x = z.x; a.rh_s = z.rh_s;
     a.W = m->W; a.L = m->L; a.H = m->H; a.kb = z.kb;
     a.j0 = j0; a.n0 = std::max(0, j1 - j0); a.jb0 = jb0; a.nrows = a.n0 + std::max(0, jb1 - jb0);
@@ -240,73 +198,15 @@ static int mo_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool a
 int pe25d_moist_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool accumulate, hipStream_t s,
                      std::string *err) {
     PeMoist &z = m->moist;
-    if (!z.tab) { *err = "moist: no tables in place"; return GCM_ERR_STATE; }
-    if (accumulate && !z.acc) { *err = "moist: no sums to accumulate into (gcm_set_moist)"; return GCM_ERR_STATE; }
+    if (!m->lev_tab) { *err = "moist: no tables in place"; return GCM_ERR_STATE; }
+    if (accumulate && !z.sums.acc) { *err = "moist: no sums to accumulate into (gcm_set_moist)"; return GCM_ERR_STATE; }
     if (set < 0) set = m->cur_i;
     if (std::max(0, j1 - j0) + std::max(0, jb1 - jb0) <= 0) return GCM_OK;
-    // Invariants of a launch, against pe25d_hs_rows' four.  The launch writes theta and q and reads p, theta and q:
-    //  * the column sums K4 left for this state (sum_k dsig u, sum_k dsig v) stay valid: u and v are not touched.  For the
-    //    same reason the wait for the third stream's column sums of the edge rows (which read u and v) is not needed;
-    //  * the fork at the last K4 stays, as behind the in-place radiation: what the next stage queues on the second and
-    //    third stream ahead of its wait for this stream (ev_join, behind K3) -- the ghost rows' column sums and anchors,
-    //    K1 and pit, the edge rows' partial sums, the tracers -- reads u, v, p, the intermediates and ghost-row theta, never
-    //    own-row theta or q, and writes none of p, theta, q of this set; the edge rows' K4, which reads them, waits for
-    //    ev_join.  The exception is a band whose ghost rows this launch takes with the own rows on this stream
-    //    (gcm_moist_step, the host-driven exchange): the ghost rows' anchors on the second stream read their theta, so
-    //    chain B must follow this stream's position;
-    //  * the ghost rows' geopotential anchors were formed from theta as it was, unless the caller forces the ghost rows
-    //    itself ahead of them (keep_ghosts: gcm_band_run);
-    //  * the parity tap's stage state is gone: theta changed.
-    if (!keep_ghosts) m->ghost_ready = -1;
-    if (!(keep_ghosts || m->wrap)) m->k4_fork_valid = false;
-    m->last_stage_set = -1;                                // gcm_get_intermediate: theta changed
+    pe25d_phase_wrote(m, set, keep_ghosts, false);         // the launch writes theta and q and reads p, theta and q
     if (int rc = m->f32 ? mo_launch<float>(m, set, j0, j1, jb0, jb1, accumulate, s, err)
                         : mo_launch<double>(m, set, j0, j1, jb0, jb1, accumulate, s, err))
         return rc;
-    if (accumulate) {
-        z.seconds += z.dt;
-        ++z.n;
-    }
-    return GCM_OK;
-}
-
-int pe25d_moist_reset(Pe25d *m, hipStream_t s, std::string *err) {
-    if (int rc = mo_registered(m, "gcm_moist_reset", err)) return rc;
-    PeMoist &z = m->moist;
-    if (int rc = mo_hip(hipMemsetAsync(z.acc, 0, sizeof(double) * 2 * mo_words(m), s), "gcm_moist_reset", err)) return rc;
-    z.seconds = 0.0;
-    z.n = 0;
-    return GCM_OK;
-}
-
-int pe25d_get_moist(Pe25d *m, double *precip, double *evap, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err) {
-    if (int rc = mo_registered(m, "gcm_get_moist", err)) return rc;
-    const PeMoist &z = m->moist;
-    const size_t bytes = sizeof(double) * mo_words(m);
-    hipError_t e = hipSuccess;
-    if (precip) e = hipMemcpyAsync(precip, z.acc, bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && evap) e = hipMemcpyAsync(evap, z.acc + mo_words(m), bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (int rc = mo_hip(e, "gcm_get_moist", err)) return rc;
-    if (seconds) *seconds = z.seconds;
-    if (nsteps) *nsteps = z.n;
-    return GCM_OK;
-}
-
-int pe25d_put_moist(Pe25d *m, const double *precip, const double *evap, double seconds, int64_t nsteps, hipStream_t s, std::string *err) {
-    if (int rc = mo_registered(m, "gcm_put_moist", err)) return rc;
-    if (!precip || !evap || !std::isfinite(seconds) || seconds < 0.0 || nsteps < 0) {
-        *err = "gcm_put_moist: precip and evap are required, seconds must be finite and >= 0, nsteps >= 0";
-        return GCM_ERR_ARG;
-    }
-    PeMoist &z = m->moist;
-    const size_t bytes = sizeof(double) * mo_words(m);
-    hipError_t e = hipMemcpyAsync(z.acc, precip, bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(z.acc + mo_words(m), evap, bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);          // (the caller's arrays are free again when the call returns)
-    if (int rc = mo_hip(e, "gcm_put_moist", err)) return rc;
-    z.seconds = seconds;
-    z.n = nsteps;
+    if (accumulate) sums_count(z.sums, z.dt);
     return GCM_OK;
 }
 

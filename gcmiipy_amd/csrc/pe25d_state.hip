@@ -1,6 +1,7 @@
 // GCM_PE25D: the handle's life cycle and data movement -- pe25d_create (with the one reader of the GCM_PE_* switches)
 // and pe25d_destroy, the buffers and tables, the streams that run beside the caller's, set / get with the layout
-// transposes, a band's halo buffers and the segments of its ghost-row message.  The stage that runs on all this:
+// transposes, a band's halo buffers and the segments of its ghost-row message, and what the phases behind the dynamics
+// share (their column sums, the level table, what a launch of theirs invalidates).  The stage that runs on all this:
 // pe25d_kernels.hip; the handle itself: pe25d_host.h.
 #include "pe25d_host.h"
 
@@ -189,6 +190,122 @@ hipStream_t pe25d_aux_stream(const Pe25d *m) { return m->aux; }
 void pe25d_fork_invalidate(Pe25d *m) { m->k4_fork_valid = false; }
 void pe25d_set_edges_first(Pe25d *m, bool on) { m->edges_first = on; }
 int pe25d_new_state_set(const Pe25d *m) { return (m->pack_set >= 0 && m->pack_set != 2) ? m->pack_set : m->cur_i; }
+
+// ---------------------------------------------------------------- what the phases behind the dynamics share
+// Behind a launch that changes rows of state set `set` in place on the caller's stream: theta (and q) always, u and v
+// too where wrote_uv (the Held-Suarez forcing; the moist physics and the convective adjustment write theta and q and
+// read p, theta and q).  What the handle remembers about that state is corrected here, once for every such phase:
+//  * the column sums K4 left for this state (sum_k dsig u, sum_k dsig v: pit of the next stage) belong to the winds as
+//    they were.  They stay valid where u and v are not touched, and for the same reason the wait for the third stream's
+//    column sums of the edge rows (which read u and v) is not needed.  wrote_uv: they are no longer valid, and the next
+//    stage sums every row again (prep_rows, the path of a freshly set state) -- on a band too, where
+//    pe25d_prep_ghost_rows then leaves the ghost rows' sums to that launch.  A single domain and a band so form them by
+//    the same kernel in the same order: the same bits;
+//  * the fork at the last K4 stays behind a launch that leaves u and v alone, as behind the in-place radiation: what the
+//    next stage queues on the second and third stream ahead of its wait for this stream (ev_join, behind K3) -- the ghost
+//    rows' column sums and anchors, K1 and pit, the edge rows' partial sums, the tracers -- reads u, v, p, the
+//    intermediates and ghost-row theta, never own-row theta or q, and writes none of p, theta, q of this set; the edge
+//    rows' K4, which reads them, waits for ev_join.  The exception is a band whose ghost rows the launch takes with the
+//    own rows on this stream (gcm_moist_step, gcm_convect_step, the host-driven exchange): the ghost rows' anchors on the
+//    second stream read their theta, so chain B must follow this stream's position.  wrote_uv: chain B (K1, the column
+//    sums) reads u and v, so it may never fork at the last K4's stop event: it follows this stream's position (ev_fork,
+//    recorded behind the launch), and so does everything that waits for that fork;
+//  * the ghost rows' geopotential anchors were formed from theta as it was, unless the caller forces the ghost rows
+//    itself ahead of them (keep_ghosts: gcm_band_run);
+//  * the parity tap's stage state is gone: theta changed.
+void pe25d_phase_wrote(Pe25d *m, int set, bool keep_ghosts, bool wrote_uv) {
+    if (wrote_uv) m->cs_valid[set] = false;
+    if (wrote_uv || !(keep_ghosts || m->wrap)) m->k4_fork_valid = false;
+    if (!keep_ghosts) m->ghost_ready = -1;
+    m->last_stage_set = -1;                                // gcm_get_intermediate: theta changed
+}
+
+const double *pe25d_level_table(Pe25d *m, const char *who, std::string *err) {
+    if (m->lev_tab) return m->lev_tab;
+    std::vector<double> t(m->sig_host);
+    t.insert(t.end(), m->dsig_host.begin(), m->dsig_host.end());
+    if (!dev_upload<double>(m, &m->lev_tab, t.data(), t.size())) *err = std::string("hip: ") + who + " table upload failed";
+    return m->lev_tab;
+}
+
+static PeColumnSums &sums_of(Pe25d *m, PeSums of) { return of == kSumsMoist ? m->moist.sums : m->convect.sums; }
+static size_t sums_words(const Pe25d *m) { return (size_t)m->H * m->W; }
+static int sums_zero(Pe25d *m, PeColumnSums &z, const std::string &fn, hipStream_t s, std::string *err) {
+    if (int rc = hip_rc(hipMemsetAsync(z.acc, 0, sizeof(double) * 2 * sums_words(m), s), fn.c_str(), err)) return rc;
+    z.seconds = 0.0;
+    z.n = 0;
+    return GCM_OK;
+}
+// fn: the entry point's name, "gcm_" + pre + <name> + post
+static int sums_registered(Pe25d *m, PeSums of, const char *pre, const char *post, std::string *fn, std::string *err) {
+    const PeSumsWords &w = kPeSumsWords[of];
+    *fn = std::string("gcm_") + pre + w.name + post;
+    if (sums_of(m, of).acc) return GCM_OK;
+    *err = *fn + ": no " + w.what + " registered (gcm_set_" + w.name + ")";
+    return GCM_ERR_STATE;
+}
+
+bool pe25d_sums_on(const Pe25d *m, PeSums of) { return sums_of(const_cast<Pe25d *>(m), of).acc != nullptr; }
+
+// gcm_set_<phase>: on -- the accumulators in place and zero; off -- freed
+int pe25d_sums_set(Pe25d *m, PeSums of, bool on, hipStream_t s, std::string *err) {
+    PeColumnSums &z = sums_of(m, of);
+    const std::string fn = std::string("gcm_set_") + kPeSumsWords[of].name;
+    if (!on) {
+        if (!z.acc) return GCM_OK;
+        // (a launch may still be adding to the sums)
+        if (int rc = hip_rc(hipStreamSynchronize(s), fn.c_str(), err)) return rc;
+        m->allocs.erase(std::remove(m->allocs.begin(), m->allocs.end(), (void *)z.acc), m->allocs.end());
+        (void)hipFree(z.acc);
+        z = PeColumnSums{};
+        return GCM_OK;
+    }
+    if (z.acc) return sums_zero(m, z, fn, s, err);
+    if (!dev_upload<double>(m, &z.acc, nullptr, 2 * sums_words(m))) { *err = "hip: " + fn + " allocation failed"; return GCM_ERR_HIP; }
+    z.seconds = 0.0;
+    z.n = 0;
+    return GCM_OK;
+}
+
+int pe25d_sums_reset(Pe25d *m, PeSums of, hipStream_t s, std::string *err) {
+    std::string fn;
+    if (int rc = sums_registered(m, of, "", "_reset", &fn, err)) return rc;
+    return sums_zero(m, sums_of(m, of), fn, s, err);
+}
+
+int pe25d_sums_get(Pe25d *m, PeSums of, double *a, double *b, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err) {
+    std::string fn;
+    if (int rc = sums_registered(m, of, "get_", "", &fn, err)) return rc;
+    const PeColumnSums &z = sums_of(m, of);
+    const size_t bytes = sizeof(double) * sums_words(m);
+    hipError_t e = hipSuccess;
+    if (a) e = hipMemcpyAsync(a, z.acc, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && b) e = hipMemcpyAsync(b, z.acc + sums_words(m), bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (int rc = hip_rc(e, fn.c_str(), err)) return rc;
+    if (seconds) *seconds = z.seconds;
+    if (nsteps) *nsteps = z.n;
+    return GCM_OK;
+}
+
+int pe25d_sums_put(Pe25d *m, PeSums of, const double *a, const double *b, double seconds, int64_t nsteps, hipStream_t s, std::string *err) {
+    std::string fn;
+    if (int rc = sums_registered(m, of, "put_", "", &fn, err)) return rc;
+    if (!a || !b || !std::isfinite(seconds) || seconds < 0.0 || nsteps < 0) {
+        const PeSumsWords &w = kPeSumsWords[of];
+        *err = fn + ": " + w.a + " and " + w.b + " are required, seconds must be finite and >= 0, nsteps >= 0";
+        return GCM_ERR_ARG;
+    }
+    PeColumnSums &z = sums_of(m, of);
+    const size_t bytes = sizeof(double) * sums_words(m);
+    hipError_t e = hipMemcpyAsync(z.acc, a, bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(z.acc + sums_words(m), b, bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);          // (the caller's arrays are free again when the call returns)
+    if (int rc = hip_rc(e, fn.c_str(), err)) return rc;
+    z.seconds = seconds;
+    z.n = nsteps;
+    return GCM_OK;
+}
 
 // The GCM_PE_* switches, read once per handle at the top of pe25d_create (read_switches) and applied where the handle's
 // fields are decided.  Unset = the default.  `num` below is atoi of the value, `c0` its first character.

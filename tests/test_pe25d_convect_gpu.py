@@ -400,6 +400,72 @@ def test_band_run_chains_with_the_phase(dtype, monkeypatch):
         c.close()
 
 
+_all_phases_cache = {}
+
+
+def _register_all(c, geom):
+    """every phase behind the dynamics, on a Core or a HipBandEngine"""
+    c.set_physics(geom, UTC0)
+    c.set_held_suarez(geom)
+    c.set_convect(**PAR)
+    c.set_moist(tau_e=86400.0)
+    c.set_climate(1)
+
+
+def _all_phases_reference(g, dtype, steps):
+    """the single domain with every phase registered: state, convect sums, moist sums and climatology sums after
+    steps[0] and after steps[0] + steps[1] steps, computed once per storage type"""
+    if dtype not in _all_phases_cache:
+        geom = geom_of(BAND)
+        c = handle(g, geom, wet_state(geom, dtype), dtype, gt=inp.ground(BAND[1], BAND[2]))
+        _register_all(c, geom)
+        out = []
+        for n in steps:
+            c.step(n, DTS)
+            out.append((final(c, close=False), c.convect_sums(), c.moist_sums(), c.climate_sums()))
+        c.close()
+        for state, cv, mo, (_, m3, m2) in out:
+            for a in state + [cv.count, cv.levels, mo.precip, mo.evap, m3, m2]:
+                a.setflags(write=False)
+        _all_phases_cache[dtype] = out
+    return _all_phases_cache[dtype]
+
+
+@pytest.mark.parametrize("comm_stream", [False, True])
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_all_phases_on_a_band_equal_the_single_domain(dtype, comm_stream, monkeypatch):
+    """gcm_band_run with the solar step, the Held-Suarez forcing, the convective adjustment, the moist physics and the
+    climatology all registered: the default orchestration forces the ghost rows apart on the second stream, behind the
+    corrector's unpack (pe_ghost_row_phases); GCM_BAND_COMM_STREAM=1 takes them with the own rows on the compute stream.
+    Either way the band holds the single domain's bits: state and ground temperature, both phases' sums, the climatology"""
+    import torch
+    import gcmiipy_amd as g
+    for k in su.ORCH_ENV:
+        monkeypatch.delenv(k, raising=False)
+    if comm_stream:
+        monkeypatch.setenv("GCM_BAND_COMM_STREAM", "1")
+    steps = (2, 1)
+    want = _all_phases_reference(g, dtype, steps)
+    assert want[-1][1].count.any() and want[-1][2].precip.max() > 0
+    geom = geom_of(BAND)
+    c, eng, runner = su.loopback_band(g, torch, geom, dtype=dtype, gt=inp.ground(BAND[1], BAND[2]))
+    assert runner.native
+    _register_all(eng, geom)
+    c.set_state(*wet_state(geom, dtype))
+    for part, n in enumerate(steps):
+        state, cv, mo, (nsamples, m3, m2) = want[part]
+        runner.run(n, DTS)
+        torch.cuda.synchronize()
+        assert_same(final(c, close=False), state, part)
+        assert_same_sums(c.convect_sums(), cv, part)
+        got = c.moist_sums()
+        assert (got.nsteps, got.seconds) == (mo.nsteps, mo.seconds), (part, got[:2], mo[:2])
+        assert np.array_equal(got.precip, mo.precip) and np.array_equal(got.evap, mo.evap), part
+        gn, g3, g2 = c.climate_sums()
+        assert gn == nsamples == sum(steps[:part + 1]) and np.array_equal(g3, m3) and np.array_equal(g2, m2), part
+    c.close()
+
+
 # ---------------------------------------------------------------- 4: refused calls
 def test_refused_calls_change_nothing():
     import ctypes
