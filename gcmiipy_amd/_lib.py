@@ -117,6 +117,7 @@ SYMBOLS = {
     "gcm_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_sw2d_plan": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "gcm_half_step": (C.c_int, [_H, C.c_int, C.c_double]),
+    "gcm_end_step": (C.c_int, [_H, C.c_double]),
     "gcm_get_star": (C.c_int, [_H] + [C.c_void_p] * 5),
     "gcm_set_star": (C.c_int, [_H] + [C.c_void_p] * 5),
     "gcm_diag": (C.c_int, [_H, C.c_int, _dp]),

@@ -265,7 +265,9 @@ class LoopbackExchange:
 
 
 class HipBandEngine:
-    """A `Core` band + torch CUDA buffers/streams for the exchange."""
+    """A `Core` band + torch CUDA buffers/streams for the exchange.  It keeps no registrations: the phases behind the
+    dynamics (set_physics ... set_climate) are the handle's, and a host-driven step ends with the library's own walk
+    over them (Core.end_step), the one gcm_band_run takes."""
 
     def __init__(self, core, torch, overlap=True, stream_aware=True):
         """stream_aware: the backend orders its transfers after the current CUDA stream (nccl =
@@ -294,8 +296,6 @@ class HipBandEngine:
         # interior rows run on the compute stream (gcm_set_halo_buffers / gcm_wait_edges)
         self.async_edges = self.edge_first
         self._edges_pending = False
-        # what the set_* calls below registered, for physics_step (None: not registered)
-        self._phys = self._hs = self._convect = self._moist = self._clim = None
         if self.async_edges:
             core.set_halo_buffers(self.sbuf[0].data_ptr(), self.sbuf[1].data_ptr())
 
@@ -324,59 +324,30 @@ class HipBandEngine:
         self.c.band_run(n, dt)
 
     def set_physics(self, geom, utc=0.0):
-        """solar_timestep after every dynamics step (no_limits_2_5d.py:66-75, t_lw = 0.1, t_sw = 0.9, albedo = 0.3):
-        inside the library's gcm_band_run, or from physics_step() when the host drives the exchange"""
+        """Core.set_physics; every band of a run registers the same"""
         self.c.set_physics(geom, utc)
-        self._phys = [geom, float(utc)]
 
     def set_held_suarez(self, geom, **params):
-        """the Held-Suarez forcing after every dynamics step, behind the solar step (Core.set_held_suarez; every band
-        of a run registers the same): inside the library's gcm_band_run, or from physics_step() when the host drives
-        the exchange.  geom=None switches it off"""
+        """Core.set_held_suarez; every band of a run registers the same"""
         self.c.set_held_suarez(geom, **params)
-        self._hs = None if geom is None else (geom, dict(params))
 
     def set_convect(self, *off, **params):
-        """the convective adjustment after every dynamics step, behind the Held-Suarez forcing and ahead of the moist
-        physics (Core.set_convect; every band of a run registers the same): inside the library's gcm_band_run, or from
-        physics_step() when the host drives the exchange.  set_convect(None) switches it off.  merge_convect() puts the
-        bands' sums together"""
+        """Core.set_convect; every band of a run registers the same.  merge_convect() puts the bands' sums together"""
         self.c.set_convect(*off, **params)
-        self._convect = None if off else dict(params)
 
     def set_moist(self, *off, **params):
-        """the moist physics after every dynamics step, behind the Held-Suarez forcing (Core.set_moist; every band of a
-        run registers the same): inside the library's gcm_band_run, or from physics_step() when the host drives the
-        exchange.  set_moist(None) switches it off.  merge_moist() puts the bands' sums together"""
+        """Core.set_moist; every band of a run registers the same.  merge_moist() puts the bands' sums together"""
         self.c.set_moist(*off, **params)
-        self._moist = None if off else dict(params)
 
     def set_climate(self, every=1):
-        """the zonal-mean climatology of the band's own rows (Core.set_climate; every band of a run registers the same
-        interval): sampled inside the library's gcm_band_run, or from physics_step() when the host drives the
-        exchange.  every=0 switches it off.  merge_climate() puts the bands' records together"""
+        """Core.set_climate; every band of a run registers the same interval.  merge_climate() puts the bands' records
+        together"""
         self.c.set_climate(every)
-        self._clim = [int(every), 0]
 
     def physics_step(self, dt):
-        """host-driven band step: own rows and ghost rows by one gcm_solar_step on the compute stream, behind the
-        unpack of the post-corrector exchange; then, likewise, the Held-Suarez forcing, the convective adjustment and the moist physics
-        (the explicit calls: the adjustment's counts add up, its seconds do not); then the climatology's sample
-        where this step is due one"""
-        if self._phys is not None:
-            self.c.solar_step(self._phys[0], dt, self._phys[1])
-            self._phys[1] += dt
-        if self._hs is not None:
-            self.c.held_suarez_step(self._hs[0], dt, **self._hs[1])
-        if self._convect is not None:
-            self.c.convect_step(**self._convect)
-        if self._moist is not None:
-            self.c.moist_step(dt, **self._moist)
-        cl = self._clim
-        if cl is not None and cl[0] > 0:
-            cl[1] += 1
-            if cl[1] % cl[0] == 0:
-                self.c.climate_sample()
+        """host-driven band step: behind the unpack of the post-corrector exchange, what gcm_band_run queues there"""
+        if self.pe:
+            self.c.end_step(dt)
 
     def send_buffer(self, side):
         self.c.halo_pack(side, self.sbuf[side].data_ptr(), self._s(self.compute))

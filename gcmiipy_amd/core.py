@@ -644,6 +644,13 @@ class Core:
     def half_step(self, stage, dt):
         _check(lib.gcm_half_step(self._h, int(stage), float(dt)), self._h)
 
+    def end_step(self, dt):
+        """the end of a GCM_PE25D step whose dynamics the caller took itself (gcm_end_step): every registered phase in
+        the order of step() / band_run() -- the solar step at the handle's clock, which advances, Held-Suarez, the
+        convective adjustment, the moist physics, the climatology's sample where one is due.  half_step(0),
+        half_step(1), end_step(dt) is step(1, dt).  A band: own rows and ghost rows, the ghost rows must be current"""
+        _check(lib.gcm_end_step(self._h, float(dt)), self._h)
+
     def get_intermediate(self, kind):
         """parity tap (GCM_PE25D): spu, pit, p_n, phi or pgfu of the last half step, as the stage kernels
         left them in the handle (gcm_get_intermediate; _lib.INT_*)"""
@@ -731,9 +738,10 @@ class Core:
                                   _tab(lon)), self._h)
 
     def set_physics(self, geom, utc=0.0, t_lw=0.1, t_sw=0.9, albedo=0.3):
-        """every step of step() / band_run() from now on = the dynamics step followed by
+        """every step of step() / band_run() / end_step() from now on = the dynamics step followed by
         no_limits_2_5d.solar_timestep at the handle's clock, which then advances by dt (run_model's loop,
-        no_limits_2_5d.py:229-234); geom=None switches the physics off (gcm_set_physics)"""
+        no_limits_2_5d.py:229-234).  That clock, utc(), is the only one: whoever drives the steps, it starts at `utc`
+        and counts every one of them.  geom=None switches the physics off (gcm_set_physics)"""
         if geom is None:
             _check(lib.gcm_set_physics(self._h, None), self._h)
             return
@@ -842,7 +850,8 @@ class Core:
     def convect_step(self, **params):
         """the convective adjustment once, in place on the current state (gcm_convect_step); no dt: the adjustment is
         instantaneous.  With a registration the call adds to its counts (and no seconds), without one the counts of the
-        call are dropped.  A band: own rows and ghost rows, the ghost rows must be current"""
+        call are dropped.  A band: own rows and ghost rows, the ghost rows must be current (a host that drives the
+        exchange itself ends its steps with end_step, which applies the registered phase and counts its seconds)"""
         self._column_step(_CONVECT, None, params)
 
     def convect_sums(self):
@@ -884,7 +893,8 @@ class Core:
     def moist_step(self, dt, **params):
         """the moist physics once, in place on the current state, with the step dt (gcm_moist_step): what
         held_suarez_step is to set_held_suarez.  With a registration the call adds to its sums, without one the sums
-        of the call are dropped.  A band: own rows and ghost rows, the ghost rows must be current"""
+        of the call are dropped.  A band: own rows and ghost rows, the ghost rows must be current (a host that drives
+        the exchange itself ends its steps with end_step, which applies the registered phase)"""
         self._column_step(_MOIST, dt, params)
 
     def moist_sums(self):

@@ -1,5 +1,5 @@
 // GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (solar step, Held-Suarez forcing,
-// convective adjustment, moist physics, climatology sample), written down once for gcm_step and gcm_band_run, and the entry points that serve GCM_PE25D handles
+// convective adjustment, moist physics, climatology sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
 // only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, convective adjustment, moist physics, climatology, the filter and the taps).
 // Host code only: a guard and one forwarding call into the pe25d_* units, through gcm_handle.h and pe25d_kernels.h.
 #include <cmath>
@@ -78,7 +78,8 @@ int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax) {
 // The end of every step, on the handle's stream: rows [-g, H + g) (phase_ghosts) -- a band's own rows, and the ghost rows
 // with them where the exchange was joined into the compute stream.  The compute stream has waited for the edge rows and
 // their pack by then (update_interior), so the rows that left are as the corrector made them and the neighbour forces
-// them itself.  tail: the stream whose tail the handle's stream joins before a sample (gcm_band_run's second stream,
+// them itself.  Three callers: gcm_step (g = 0), gcm_band_run, and gcm_end_step for a caller that takes the dynamics
+// step itself.  tail: the stream whose tail the handle's stream joins before a sample (gcm_band_run's second stream,
 // where the exchange runs there), else null
 int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail) {
     if (int rc = pe_phase_rows(h, dt, -1, -g, h->H + g, 0, 0, keep_ghosts, true, h->stream)) return rc;
@@ -108,6 +109,17 @@ int pe_step(gcm_handle *h, int nsteps, double dt) {
 }
 
 extern "C" {
+
+// ------------------------------------------------------------------ the end of a step whose dynamics the caller took itself
+// What gcm_band_run queues behind a corrector where the ghost rows ride with the own rows (GCM_BAND_COMM_STREAM=1): the
+// tables for dt, then every registered phase over own rows and ghost rows on the handle's stream, the clock, the sample
+int gcm_end_step(gcm_handle *h, double dt) {
+    if (int rc = pe_only(h, "gcm_end_step")) return rc;
+    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_end_step: dt must be finite");
+    if (int rc = select_device(h)) return rc;
+    if (int rc = pe_phase_tables(h, 1, dt)) return rc;
+    return pe_own_row_phases(h, dt, phase_ghosts(h), false, nullptr);
+}
 
 // ------------------------------------------------------------------ passive tracers
 int gcm_set_tracers(gcm_handle *h, int n, const double *c) {
@@ -281,7 +293,7 @@ int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs) {
     if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_held_suarez_step: dt must be finite");
     if (int rc = select_device(h)) return rc;
     if (int rc = pe25d_hs_tables(h->pe, hs, dt, h->stream, &h->err)) return rc;
-    // a band: own rows and ghost rows, as gcm_solar_step (the ghost rows of the current state must be current)
+    // a band: own rows and ghost rows, as gcm_solar_step and gcm_end_step (the ghost rows of the current state must be current)
     const int g = phase_ghosts(h);
     return pe25d_hs_rows(h->pe, -1, -g, h->H + g, 0, 0, false, h->stream, &h->err);
 }
@@ -316,7 +328,8 @@ int gcm_convect_step(gcm_handle *h, const gcm_convect *cv) {
     // (the adjustment is instantaneous: the call adds no seconds)
     if (int rc = pe25d_convect_tables(h->pe, cv, 0.0, &h->err)) return rc;
     // a band: own rows and ghost rows, as gcm_moist_step (the ghost rows of the current state must be current); the
-    // counts of the call go to the registration's accumulators, or nowhere
+    // counts of the call go to the registration's accumulators, or nowhere.  A host that drives the exchange itself ends
+    // its steps with gcm_end_step, not with this call
     const int g = phase_ghosts(h);
     return pe25d_convect_rows(h->pe, -1, -g, h->H + g, 0, 0, false, pe25d_sums_on(h->pe, kSumsConvect), h->stream, &h->err);
 }
@@ -364,7 +377,8 @@ int gcm_moist_step(gcm_handle *h, double dt, const gcm_moist *mo) {
     if (int rc = select_device(h)) return rc;
     if (int rc = pe25d_moist_tables(h->pe, mo, dt, &h->err)) return rc;
     // a band: own rows and ghost rows, as gcm_held_suarez_step (the ghost rows of the current state must be current);
-    // the sums of the call go to the registration's accumulators, or nowhere
+    // the sums of the call go to the registration's accumulators, or nowhere.  A host that drives the exchange itself
+    // ends its steps with gcm_end_step, not with this call
     const int g = phase_ghosts(h);
     return pe25d_moist_rows(h->pe, -1, -g, h->H + g, 0, 0, false, pe25d_sums_on(h->pe, kSumsMoist), h->stream, &h->err);
 }

@@ -650,6 +650,18 @@ int gcm_climate_sample(gcm_handle *h);
 int gcm_climate_reset(gcm_handle *h);
 int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples);
 int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples);
+/* The end of a GCM_PE25D step whose dynamics the caller took itself: everything gcm_step and gcm_band_run queue behind
+ * the corrector, in their order and by their code -- the solar step at the handle's clock, utc += dt, the Held-Suarez
+ * forcing, the convective adjustment, the moist physics (their sums, seconds and nsteps advance as in gcm_step), the
+ * climatology's step counter and its sample where one is due -- each only if registered, on the handle's stream.  With
+ * nothing registered it queues nothing.  On a single domain gcm_half_step(h, 0, dt), gcm_half_step(h, 1, dt),
+ * gcm_end_step(h, dt) is gcm_step(h, 1, dt).  On a latitude band it ends a step driven through gcm_step_phase or
+ * gcm_step_interior / gcm_step_boundary and the caller's own exchange: the launches take the ghost rows with the own
+ * rows, as the explicit gcm_solar_step, gcm_held_suarez_step, gcm_convect_step and gcm_moist_step do, so the ghost rows
+ * of the current state, and of the ground temperature, must be current (the post-corrector exchange unpacked).
+ * gcm_step and gcm_band_run end their steps themselves: do not call it behind them.
+ * Errors: a null handle GCM_ERR_ARG; other models GCM_ERR_UNSUPPORTED; a non-finite dt GCM_ERR_ARG, and nothing changes. */
+int gcm_end_step(gcm_handle *h, double dt);
 
 /* Device-side snapshot / restore of the current state, ghost rows included (2-D models): a long
  * run can restart from a known state without a host round trip.  gcm_restore is asynchronous on

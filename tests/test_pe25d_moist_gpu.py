@@ -321,7 +321,7 @@ def test_in_process_bands_equal_single_domain(shape, nb, dtype):
 @pytest.mark.parametrize("shape", SHAPES[:2])
 def test_loopback_band_run_equals_single_domain(shape, dtype, host_loop, monkeypatch):
     """gcm_band_run with the phase registered (and the host-driven sequence, GCM_BAND_HOST_LOOP=1, whose physics_step
-    applies it by the explicit call): several steps in one run, then a second run after a get_state"""
+    ends the step with gcm_end_step): several steps in one run, then a second run after a get_state"""
     import torch
     import gcmiipy_amd as g
     for k in su.ORCH_ENV:
