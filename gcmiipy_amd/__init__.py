@@ -13,8 +13,9 @@ Importing the package loads the library and raises ImportError if it is not
 built: nothing here computes on the CPU.
 """
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
-from .core import (Climate, Convect, Core, GcmError, Moist, TracerStats, convect_columns, device_count,  # noqa: F401
-                   held_suarez_tables, moist_saturation)
+from .core import (BoundaryLayer, Climate, Convect, Core, GcmError, Moist, TracerStats, aquaplanet_sst,  # noqa: F401
+                   boundary_layer_column, boundary_layer_surface, convect_columns, device_count, held_suarez_tables,
+                   moist_saturation)
 
 
 
@@ -27,5 +28,6 @@ def clear_cache():
     _lib.lib.gcm_ops_release_scratch()      # the operator entry points' device scratch of this thread
 
 
-__all__ = ["Climate", "Convect", "Core", "GcmError", "Moist", "TracerStats", "convect_columns", "device_count",
+__all__ = ["BoundaryLayer", "Climate", "Convect", "Core", "GcmError", "Moist", "TracerStats", "aquaplanet_sst",
+           "boundary_layer_column", "boundary_layer_surface", "convect_columns", "device_count",
            "clear_cache", "held_suarez_tables", "moist_saturation"]

@@ -86,6 +86,12 @@ class Moist(C.Structure):
     _fields_ = [("Lv", C.c_double), ("tau_e", C.c_double), ("rh_s", C.c_double)]
 
 
+class BoundaryLayer(C.Structure):
+    """gcm_boundary_layer of include/gcmcore.h"""
+    _fields_ = [("cd0", C.c_double), ("cd1", C.c_double), ("v_cap", C.c_double), ("ch", C.c_double), ("ce", C.c_double),
+                ("p_pbl", C.c_double), ("p_strat", C.c_double)]
+
+
 class Convect(C.Structure):
     """gcm_convect of include/gcmcore.h"""
     _fields_ = [("kappa_c", C.c_double), ("mix_q", C.c_int32)]
@@ -143,6 +149,14 @@ SYMBOLS = {
     "gcm_put_moist": (C.c_int, [_H, _dp, _dp, C.c_double, C.c_int64]),
     "gcm_moist_reset": (C.c_int, [_H]),
     "gcm_moist_saturation": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    "gcm_set_boundary_layer": (C.c_int, [_H, C.POINTER(BoundaryLayer)]),
+    "gcm_boundary_layer_on": (C.c_int, [_H]),
+    "gcm_boundary_layer_step": (C.c_int, [_H, C.c_double, C.POINTER(BoundaryLayer)]),
+    "gcm_get_boundary_layer": (C.c_int, [_H, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "gcm_put_boundary_layer": (C.c_int, [_H, _dp, _dp, C.c_double, C.c_int64]),
+    "gcm_boundary_layer_reset": (C.c_int, [_H]),
+    "gcm_boundary_layer_surface": (C.c_int, [C.c_int, C.POINTER(BoundaryLayer), C.c_double, C.c_double] + [_dp] * 8),
+    "gcm_boundary_layer_column": (C.c_int, [C.c_int, C.c_int] + [_dp] * 7),
     "gcm_set_convect": (C.c_int, [_H, C.POINTER(Convect)]),
     "gcm_convect_on": (C.c_int, [_H]),
     "gcm_convect_step": (C.c_int, [_H, C.POINTER(Convect)]),

@@ -18,7 +18,10 @@ moist physics, Core.set_moist, is stored as "moist", its three parameters in the
 "moist_n", "moist_seconds", "moist_precip" and "moist_evap", the count, the seconds and the raw float64 sums, registered
 and uploaded again on restore; files without these keys restore with none; the convective adjustment, Core.set_convect,
 is stored as "convect", its two parameters in the order of core.CONVECT_DEFAULTS, with "convect_n", "convect_seconds",
-"convect_count" and "convect_levels", saved and restored the same way)
+"convect_count" and "convect_levels", saved and restored the same way; the boundary layer, Core.set_boundary_layer, is
+stored as "boundary_layer", its seven parameters in the order of core.BOUNDARY_LAYER_DEFAULTS, with "boundary_layer_n",
+"boundary_layer_seconds", "boundary_layer_shf" and "boundary_layer_evap", saved the same way and restored ahead of the
+convective adjustment, in the model's order (behind the ground temperature, which its registration needs))
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
@@ -60,7 +63,7 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
         n, m3, m2 = core.climate_sums()
         out.update(climate_every=np.int64(core.climate_every), climate_n=np.int64(n), climate_m3=m3, climate_m2=m2)
     # (a core is asked only for the phases it knows: getattr, so that a stand-in without one of them will do; reversed:
-    # the files have always held the moist physics' keys ahead of the convective adjustment's)
+    # the files have always held the moist physics' keys ahead of the convective adjustment's; the boundary layer's follow)
     for ph in reversed(COLUMN_PHASES if core.model == _lib.PE25D else ()):
         par = getattr(core, ph.name, None)
         if par is None and getattr(core, ph.name + "_registered", False):
@@ -85,10 +88,10 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, held_suarez, climate, moist, convect); ground and tracers are None where the file has none, tracer_forcing
+    tracer_mixing, held_suarez, climate, moist, convect, boundary_layer); ground and tracers are None where the file has none, tracer_forcing
     {i: dict(...)} and tracer_mixing {i: K} are then empty; held_suarez is (parameters dict, lat) or None; climate is
     dict(every, n, m3, m2) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
-    dict(params, n, seconds, count, levels) or None"""
+    dict(params, n, seconds, count, levels) or None; boundary_layer is dict(params, n, seconds, shf, evap) or None"""
     d = np.load(path, allow_pickle=False)
     L, H, W = (int(x) for x in d["shape"])
     state = {k: d["state_" + k] for k in "puvtq" if "state_" + k in d.files}
@@ -160,7 +163,7 @@ def restore(path, **core_kwargs):
     if ck["climate"] is not None:
         core.set_climate(ck["climate"]["every"])
         core.put_climate(ck["climate"]["n"], ck["climate"]["m3"], ck["climate"]["m2"])
-    for ph in COLUMN_PHASES:                 # (the model's order: the convective adjustment, then the moist physics)
+    for ph in COLUMN_PHASES:                 # (the model's order: the boundary layer, the convective adjustment, the moist physics)
         rec = ck[ph.name]
         if rec is not None:
             getattr(core, "set_" + ph.name)(**rec["params"])

@@ -233,6 +233,71 @@ def moist_saturation(T, p_lev):
     return qs.reshape(T.shape), dqs.reshape(T.shape), can.reshape(T.shape).astype(bool)
 
 
+# the parameters of the surface fluxes and the boundary-layer mixing (gcm_boundary_layer), in the struct's order: the drag
+# cd = cd0 + cd1 min(S, v_cap), the exchange coefficients of heat and moisture, the pressure at and below which the mixing
+# is full (Pa) and the e-folding scale of its decay above (Pa): Reed & Jablonowski (2012)'s values
+BOUNDARY_LAYER_DEFAULTS = collections.OrderedDict(cd0=7.0e-4, cd1=6.5e-5, v_cap=20.0, ch=0.0044, ce=0.0044, p_pbl=85000.0,
+                                                  p_strat=10000.0)
+
+
+def boundary_layer_params(params):
+    """the seven parameters of the boundary layer as a dict of floats: BOUNDARY_LAYER_DEFAULTS with `params` laid over
+    them; ValueError for a name that is not a parameter"""
+    unknown = sorted(set(params) - set(BOUNDARY_LAYER_DEFAULTS))
+    if unknown:
+        raise ValueError("boundary_layer: unknown parameter(s) %s; the parameters are %s"
+                         % (", ".join(unknown), ", ".join(BOUNDARY_LAYER_DEFAULTS)))
+    out = collections.OrderedDict(BOUNDARY_LAYER_DEFAULTS)
+    out.update({k: float(v) for k, v in params.items()})
+    return out
+
+
+class BoundaryLayer(collections.namedtuple("BoundaryLayer", "nsteps seconds shf evap")):
+    """the sums of a GCM_PE25D handle's boundary layer (Core.boundary_layer_sums): the applications counted, the sum of
+    their dt in seconds, and per column (H, W), float64, the sensible heat the surface gave the air, J / m^2, and the
+    water, kg / m^2 (negative: dew)"""
+    __slots__ = ()
+
+
+def boundary_layer_surface(uc, vc, theta0, q0, p, sig0, ptop=0.0, **params):
+    """the level-0 centre quantities of the boundary layer (gcm_boundary_layer_surface; the host build of the routine the
+    kernel calls, no handle, no device) for centre winds uc, vc (m / s), theta and q of the lowest level and p (Pa, surface
+    pressure minus ptop) of one shape, sig0 the lowest level's sigma -> (S, z_a, cd): the wind speed, the height of the
+    lowest level (m) and the drag coefficient.  ValueError for a refused parameter"""
+    uc = np.asarray(uc, dtype=np.float64)
+    arrs = [as_f64(np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), uc.shape)).reshape(-1), name=n)
+            for a, n in ((uc, "uc"), (vc, "vc"), (theta0, "theta0"), (q0, "q0"), (p, "p"))]
+    rec = _lib.BoundaryLayer(*boundary_layer_params(params).values())
+    out = [np.empty(uc.size) for _ in range(3)]
+    _check(lib.gcm_boundary_layer_surface(uc.size, C.byref(rec), float(ptop), float(sig0), *[_tab(a) for a in arrs + out]))
+    return tuple(a.reshape(uc.shape) for a in out)
+
+
+def boundary_layer_column(dsig, a, x, target, X):
+    """one column solve of the boundary layer, "surface step on level 0, then diffusion" (gcm_boundary_layer_column; the
+    host build of the routines the kernels call, no handle, no device) over columns X (..., L), level 0 the bottom, with
+    dsig (L,), the interface coefficients a (..., L - 1) and per column the surface weight x and the target (...)
+    -> (X_out (..., L), X0_surface (...))"""
+    X = np.asarray(X, dtype=np.float64)
+    L = X.shape[-1] if X.ndim else 0
+    XX = as_f64(X.reshape(-1, L) if L else X, name="X")
+    n = XX.shape[0] if L else 0
+    aa = as_f64(np.asarray(a, dtype=np.float64).reshape(n, max(L - 1, 0)), name="a")
+    xx, tt = (as_f64(np.asarray(v, dtype=np.float64).reshape(n), name=nm) for v, nm in ((x, "x"), (target, "target")))
+    dd = as_f64(dsig, (L,), "dsig")
+    out, x0 = np.empty_like(XX), np.empty(n)
+    _check(lib.gcm_boundary_layer_column(n, L, _tab(dd), _tab(aa), _tab(xx), _tab(tt), _tab(XX), _tab(out), _tab(x0)))
+    return out.reshape(X.shape), x0.reshape(X.shape[:-1])
+
+
+def aquaplanet_sst(lat, dT=29.0, T_min=271.0, width=np.deg2rad(26.0)):
+    """the prescribed sea-surface temperature of the moist Held-Suarez test (Thatcher & Jablonowski 2016) at the
+    latitudes `lat` (radians), K: dT exp(-lat^2 / (2 width^2)) + T_min, width in radians (26 degrees).  What set_ground
+    takes on an aquaplanet, broadcast over the longitudes"""
+    lat = np.asarray(lat, dtype=np.float64)
+    return dT * np.exp(-(lat * lat) / (2.0 * width * width)) + T_min
+
+
 # the parameters of the convective adjustment (gcm_convect), in the struct's order: kappa_c = Rd gamma / g of the neutral
 # profile (0: dry adjustment, neutral where theta is constant) and whether q of a merged block is mixed
 CONVECT_DEFAULTS = collections.OrderedDict(kappa_c=0.0, mix_q=1)
@@ -298,8 +363,8 @@ def convect_columns(y, w, q, dsig, mix_q=True):
 
 
 class _ColumnPhase:
-    """what tells the two phases with per-column sums apart -- the convective adjustment and the moist physics, in the
-    model's order in COLUMN_PHASES -- for Core's seven operations on each and for checkpoint.py: the name in the entry
+    """what tells the phases with per-column sums apart -- the boundary layer, the convective adjustment and the moist
+    physics, in the model's order in COLUMN_PHASES -- for Core's seven operations on each and for checkpoint.py: the name in the entry
     points and keys, the words of the messages, the ctypes record, the *_params function with its defaults (the record's
     order), the result namedtuple (its last two fields name the sums) and whether *_step takes dt"""
 
@@ -312,7 +377,9 @@ class _ColumnPhase:
 
 _CONVECT = _ColumnPhase("convect", "convective adjustment", _lib.Convect, convect_params, CONVECT_DEFAULTS, Convect, False)
 _MOIST = _ColumnPhase("moist", "moist physics", _lib.Moist, moist_params, MOIST_DEFAULTS, Moist, True)
-COLUMN_PHASES = (_CONVECT, _MOIST)
+_BOUNDARY = _ColumnPhase("boundary_layer", "boundary layer", _lib.BoundaryLayer, boundary_layer_params,
+                         BOUNDARY_LAYER_DEFAULTS, BoundaryLayer, True)
+COLUMN_PHASES = (_BOUNDARY, _CONVECT, _MOIST)
 
 
 def _ptr(a):
@@ -368,7 +435,7 @@ class Core:
         self._forcing = {}                      # tracer -> the forcing record registered (set_tracer_forcing)
         self._mixing = {}                       # tracer -> the profile K registered (set_tracer_mixing)
         self._held_suarez = None                # the parameters and latitudes registered (set_held_suarez)
-        self._column = {}                       # the parameters registered (set_convect, set_moist), by the phase's name
+        self._column = {}                       # the parameters registered (set_boundary_layer, set_convect, set_moist), by the phase's name
         cfg = _lib.Config()
         cfg.abi_version = _lib.ABI_VERSION
         cfg.model = model
@@ -647,7 +714,7 @@ class Core:
     def end_step(self, dt):
         """the end of a GCM_PE25D step whose dynamics the caller took itself (gcm_end_step): every registered phase in
         the order of step() / band_run() -- the solar step at the handle's clock, which advances, Held-Suarez, the
-        convective adjustment, the moist physics, the climatology's sample where one is due.  half_step(0),
+        boundary layer (single domains), the convective adjustment, the moist physics, the climatology's sample where one is due.  half_step(0),
         half_step(1), end_step(dt) is step(1, dt).  A band: own rows and ghost rows, the ghost rows must be current"""
         _check(lib.gcm_end_step(self._h, float(dt)), self._h)
 
@@ -825,11 +892,54 @@ class Core:
     def _column_reset(self, ph):
         _check(ph.reset(self._h), self._h)
 
+    # -- surface fluxes and boundary-layer mixing (GCM_PE25D, single domains) ---------------
+    def set_boundary_layer(self, *off, **params):
+        """every step of step() / end_step() from now on exchanges momentum, heat and moisture with the surface and mixes
+        them upwards on the device (gcm_set_boundary_layer): bulk fluxes against the ground temperature (set_ground first:
+        a prescribed sea-surface temperature, e.g. aquaplanet_sst; it is never changed) and an implicit diffusion of u, v,
+        theta and q in the column -- behind the Held-Suarez forcing and ahead of the convective adjustment and the moist
+        physics, whose tau_e should then be 0.  half_step never applies it.  params: cd0, cd1, v_cap, ch, ce, p_pbl,
+        p_strat (BOUNDARY_LAYER_DEFAULTS).  The sensible heat and the water the surface gave are accumulated per column
+        (boundary_layer_sums); registering again resets the sums.  set_boundary_layer(None) switches the phase off.
+        ValueError for a refused parameter, GcmError for a latitude band (not supported yet) and for a handle without a
+        ground temperature (the call then changes nothing)"""
+        self._set_column(_BOUNDARY, off, params)
+
+    @property
+    def boundary_layer(self):
+        """the parameters of the registered boundary layer as a dict, or None where the handle carries none
+        (gcm_boundary_layer_on) -- and also None for one registered through the C call directly"""
+        return self._column_params(_BOUNDARY)
+
+    @property
+    def boundary_layer_registered(self):
+        """whether the handle carries the phase at all (gcm_boundary_layer_on), whoever registered it"""
+        return self._column_registered(_BOUNDARY)
+
+    def boundary_layer_step(self, dt, **params):
+        """the boundary layer once, in place on the current state, with the step dt (gcm_boundary_layer_step).  With a
+        registration the call adds to its sums, without one the sums of the call are dropped"""
+        self._column_step(_BOUNDARY, dt, params)
+
+    def boundary_layer_sums(self):
+        """-> BoundaryLayer(nsteps, seconds, shf (H, W), evap (H, W)): the float64 sums as the device holds them
+        (gcm_get_boundary_layer); one synchronisation.  GcmError where no boundary layer is registered"""
+        return self._column_sums(_BOUNDARY)
+
+    def put_boundary_layer(self, nsteps, seconds, shf, evap):
+        """upload sums taken by boundary_layer_sums() (gcm_put_boundary_layer): a restart goes on where the run stopped"""
+        self._put_column(_BOUNDARY, nsteps, seconds, shf, evap)
+
+    def boundary_layer_reset(self):
+        """zero the sums, the seconds and the count (gcm_boundary_layer_reset)"""
+        self._column_reset(_BOUNDARY)
+
     # -- convective adjustment (GCM_PE25D) -------------------------------------------------
     def set_convect(self, *off, **params):
         """every step of step() / band_run() from now on adjusts statically unstable columns on the device
         (gcm_set_convect): theta, and with mix_q also q, of every unstable stretch of a column is mixed to the neutral
-        profile at constant column enthalpy and water -- behind the Held-Suarez forcing and ahead of the moist physics.
+        profile at constant column enthalpy and water -- behind the Held-Suarez forcing and the boundary layer and ahead of
+        the moist physics.
         half_step never applies it.  params: gamma, the critical lapse rate in K / m (6.5e-3: Manabe-Strickler), or
         kappa_c = Rd gamma / g, at most one of the two, neither: the dry adjustment; mix_q (True).  How often and how
         deep each column was adjusted is accumulated (convect_sums); registering again resets the sums.
@@ -872,7 +982,8 @@ class Core:
         """every step of step() / band_run() from now on ends with the moist physics on the device: q in excess of
         saturation condenses, the latent heat warms theta, the condensate leaves the column as precipitation, and with
         tau_e > 0 the lowest level is moistened towards the relative humidity rh_s (gcm_set_moist) -- the Matsuno step,
-        solar_timestep where set_physics is on, the Held-Suarez forcing and the convective adjustment where registered,
+        solar_timestep where set_physics is on, the Held-Suarez forcing, the boundary layer and the convective adjustment
+        where registered,
         then this, then the climatology's sample.  half_step never applies it.  params: Lv (J / kg), tau_e (s, 0: no evaporation), rh_s
         (MOIST_DEFAULTS).  Precipitation and evaporation are accumulated per column (moist_sums); registering again
         resets the sums.  set_moist(None) switches the phase off.  ValueError for a refused parameter (the call then

@@ -34,8 +34,8 @@ struct GcmTiming {
 };
 
 // GCM_PE25D: the phases registered behind the dynamics of every step (gcm_pe.hip runs them; the climatology's
-// registration is Pe25d's own, and so are the convective adjustment's and the moist physics': pe25d_sums_on -- mo and cv
-// are the parameters their steps run with).  The records' table pointers are null: the vectors are the copies that are used
+// registration is Pe25d's own, and so are the convective adjustment's and the moist physics': pe25d_sums_on -- mo, cv
+// and bl are the parameters their steps run with).  The records' table pointers are null: the vectors are the copies that are used
 struct GcmPhases {
     bool solar = false;                        // gcm_set_physics: solar_timestep as the second phase of every step
     bool held_suarez = false;                  // gcm_set_held_suarez: the forcing behind the solar step
@@ -43,6 +43,7 @@ struct GcmPhases {
     gcm_held_suarez hs{};
     gcm_moist mo{};
     gcm_convect cv{};
+    gcm_boundary_layer bl{};
     std::vector<double> phys_lat, phys_lon, hs_lat;
 };
 
@@ -151,7 +152,7 @@ extern "C" void step_rows(gcm_handle *h, double dt, int j0, int j1, hipStream_t 
 extern "C" void swap_state(gcm_handle *h);
 extern "C" int launch_status(gcm_handle *h);
 
-// gcm_pe.hip, for gcm_step, gcm_band_run and gcm_end_step: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, convective adjustment, moist physics, sample), each
+// gcm_pe.hip, for gcm_step, gcm_band_run and gcm_end_step: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, boundary layer, convective adjustment, moist physics, sample), each
 // launched only if it is registered -- their tables before a run, a band's ghost rows on its second stream `ax` behind a
 // corrector's unpack, and the end of every step on the handle's stream over rows [-g, H + g), which joins `tail` before a sample
 extern "C" int pe_step(gcm_handle *h, int nsteps, double dt);        // gcm_step of a GCM_PE25D handle

@@ -51,12 +51,26 @@ constexpr double kBinom5 = kBinom4 * (kKappa - 4) / 5;
 constexpr double kBinom6 = kBinom5 * (kKappa - 5) / 6;
 constexpr double kBinom7 = kBinom6 * (kKappa - 6) / 7;
 
-__device__ __forceinline__ double exner(double p, const double *tab /* LDS */) {
+// One routine for the device and the host (the host probes of the phases that call it, e.g. gcm_boundary_layer_surface):
+// only how the bits of p are taken apart and m is put together differs, every operation on them is the same.
+__host__ __device__ __forceinline__ double exner(double p, const double *tab /* device: LDS */) {
+#if defined(__HIP_DEVICE_COMPILE__)
     const int hi = __double2hiint(p);
     const int e = ((hi >> 20) & 0x7ff) - 1023;
     const int idx = (hi >> 14) & 63;
     const double m = __hiloint2double((hi & 0x000fffff) | 0x3ff00000, __double2loint(p));
     const int ec = min(max(e, -64), 63);
+#else
+    unsigned long long bits;
+    __builtin_memcpy(&bits, &p, sizeof bits);
+    const int hi = (int)(unsigned)(bits >> 32);
+    const int e = ((hi >> 20) & 0x7ff) - 1023;
+    const int idx = (hi >> 14) & 63;
+    const unsigned long long mbits = ((unsigned long long)(unsigned)((hi & 0x000fffff) | 0x3ff00000) << 32) | (bits & 0xffffffffull);
+    double m;
+    __builtin_memcpy(&m, &mbits, sizeof m);
+    const int ec = e < -64 ? -64 : (e > 63 ? 63 : e);
+#endif
     const double E = tab[ec + 64];
     const double rc = tab[128 + 2 * idx], ck = tab[129 + 2 * idx];
     const double t = __builtin_fma(m, rc, -1.0);

@@ -1,6 +1,6 @@
 // GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (solar step, Held-Suarez forcing,
-// convective adjustment, moist physics, climatology sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
-// only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, convective adjustment, moist physics, climatology, the filter and the taps).
+// boundary layer, convective adjustment, moist physics, climatology sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
+// only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, boundary layer, convective adjustment, moist physics, climatology, the filter and the taps).
 // Host code only: a guard and one forwarding call into the pe25d_* units, through gcm_handle.h and pe25d_kernels.h.
 #include <cmath>
 
@@ -10,13 +10,15 @@ using namespace gcm;
 
 // ------------------------------------------------------------------ the phases of a step
 // The order is the model's: the dynamics step, the solar step at the current clock, utc += dt, the Held-Suarez forcing,
-// the convective adjustment, the moist physics, the sample.  Each launch runs only if its phase is registered: the solar
-// step and the forcing in GcmPhases, the adjustment and the moist physics where their sums are in place (pe25d_sums_on),
+// the boundary layer, the convective adjustment, the moist physics, the sample.  Each launch runs only if its phase is
+// registered: the solar step and the forcing in GcmPhases, the boundary layer, the adjustment and the moist physics where
+// their sums are in place (pe25d_sums_on),
 // the climatology in pe25d_climate_due.  The order is written down in pe_phase_rows, and in pe_phase_tables for what a
 // run prepares ahead of it.
 
 // gcm_set_physics: the radiation kernel's tables in place before a run queues anything (no-op without physics); then the
-// registered forcing's device tables for dt (none: GCM_OK), and the convective adjustment's and the moist physics' level tables and parameters for dt
+// registered forcing's device tables for dt (none: GCM_OK), the boundary layer's level tables, scratch fields and parameters
+// for dt, and the convective adjustment's and the moist physics' level tables and parameters for dt
 int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
     const GcmPhases &ph = h->phases;
     if (ph.solar)
@@ -28,6 +30,8 @@ int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
         hs.lat = ph.hs_lat.data();
         if (int rc = pe25d_hs_tables(h->pe, &hs, dt, h->stream, &h->err)) return rc;
     }
+    if (pe25d_sums_on(h->pe, kSumsBoundary))
+        if (int rc = pe25d_boundary_layer_tables(h->pe, &ph.bl, dt, h->stream, &h->err)) return rc;
     if (pe25d_sums_on(h->pe, kSumsConvect))
         if (int rc = pe25d_convect_tables(h->pe, &ph.cv, dt, &h->err)) return rc;
     if (pe25d_sums_on(h->pe, kSumsMoist)) return pe25d_moist_tables(h->pe, &ph.mo, dt, &h->err);
@@ -35,11 +39,12 @@ int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
 }
 
 // The registered phases that change the state, over rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one)
-// on `s`, each launch behind the one before it in stream order.  Every phase is column-local, so a row gets the same bits
-// whichever launch takes it: a single domain's, a band's own rows', a neighbour's ghost rows'.  Two callers:
+// on `s`, each launch behind the one before it in stream order.  Every phase but the boundary layer is column-local, so a
+// row gets the same bits whichever launch takes it: a single domain's, a band's own rows', a neighbour's ghost rows'; the
+// boundary layer reads neighbouring columns and rows and is registered on single domains only.  Two callers:
 //  * own: the end of every step, the rows of the handle on its stream (pe_own_row_phases).  The clock advances behind
-//    the solar step, and the convective adjustment's counts and the moist physics' precipitation and evaporation go to
-//    the handle's sums (the kernels add rows [0, H) only);
+//    the solar step, and the boundary layer's shf and evap, the convective adjustment's counts and the moist physics'
+//    precipitation and evaporation go to the handle's sums (the kernels add rows [0, H) only);
 //  * !own: a band's ghost rows as the post-corrector exchange delivered them, on the second stream behind the unpack and
 //    AHEAD of the ghost rows' column sums and anchors, which read u, v and theta (pe_ghost_row_phases).  The rows are
 //    forced locally with the neighbour's own inputs and tables -- theta, p, u, v as delivered, the ground temperature's
@@ -61,6 +66,15 @@ static int pe_phase_rows(gcm_handle *h, double dt, int set, int j0, int j1, int 
     // launch pe25d_prep_ghost_rows leaves them to the next stage (pe25d_phase_wrote)
     if (ph.held_suarez)
         if (int rc = pe25d_hs_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, s, &h->err)) return rc;
+    // gcm_set_boundary_layer: u, v, theta and q of a single domain (a band refuses the registration), behind the forcing:
+    // it heats and moistens the lowest level, the adjustment then mixes what became unstable.  The launches write u and v,
+    // as the forcing's does.  They take every row of the domain whatever [j0, j1) says: a single domain's walk is its own
+    // rows, all of them, and no band gets here
+    if (pe25d_sums_on(h->pe, kSumsBoundary)) {
+        if (!own || !h->wrap || j0 != 0 || j1 != h->H || jb1 > jb0)
+            return fail(h, GCM_ERR_STATE, "boundary layer: the phase walk of a single domain's own rows only");
+        if (int rc = pe25d_boundary_layer_rows(h->pe, set, keep_ghosts, own, s, &h->err)) return rc;
+    }
     // gcm_set_convect: theta and q, ahead of the moist physics, which then condenses whatever the mixing left supersaturated
     if (pe25d_sums_on(h->pe, kSumsConvect))
         if (int rc = pe25d_convect_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, own, s, &h->err)) return rc;
@@ -301,6 +315,72 @@ int gcm_held_suarez_step(gcm_handle *h, double dt, const gcm_held_suarez *hs) {
 int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat, const gcm_held_suarez *hs, double dt,
                            double *fu, double *kt, double *s2, double *c2) {
     return held_suarez_tables(L, sig, nlat, lat, hs, dt, fu, kt, s2, c2, &gcm_create_error());
+}
+
+// ------------------------------------------------------------------ surface fluxes and boundary-layer mixing
+// a latitude band, levels that do not start at the bottom, no ground temperature: refused in the call itself
+int gcm_set_boundary_layer(gcm_handle *h, const gcm_boundary_layer *bl) {
+    if (int rc = pe_only(h, "gcm_set_boundary_layer")) return rc;
+    if (bl) {
+        if (int rc = boundary_layer_check(bl, "gcm_set_boundary_layer", &h->err)) return rc;
+        if (int rc = pe25d_boundary_layer_fits(h->pe, "gcm_set_boundary_layer", &h->err)) return rc;
+    }
+    if (int rc = select_device(h)) return rc;
+    if (int rc = pe25d_boundary_layer_scratch(h->pe, bl != nullptr, h->stream, &h->err)) return rc;
+    if (int rc = pe25d_sums_set(h->pe, kSumsBoundary, bl != nullptr, h->stream, &h->err)) {
+        // (a refused call changes nothing: a handle that is not registered keeps no scratch of this call's)
+        if (bl && !pe25d_sums_on(h->pe, kSumsBoundary)) {
+            std::string ignored;
+            (void)pe25d_boundary_layer_scratch(h->pe, false, h->stream, &ignored);
+        }
+        return rc;
+    }
+    if (bl) h->phases.bl = *bl;
+    return GCM_OK;
+}
+
+int gcm_boundary_layer_on(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && pe25d_sums_on(h->pe, kSumsBoundary) ? 1 : 0;
+}
+
+int gcm_boundary_layer_step(gcm_handle *h, double dt, const gcm_boundary_layer *bl) {
+    if (int rc = pe_only(h, "gcm_boundary_layer_step")) return rc;
+    if (int rc = boundary_layer_check(bl, "gcm_boundary_layer_step", &h->err)) return rc;
+    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_boundary_layer_step: dt must be finite");
+    if (int rc = pe25d_boundary_layer_fits(h->pe, "gcm_boundary_layer_step", &h->err)) return rc;
+    if (int rc = select_device(h)) return rc;
+    if (int rc = pe25d_boundary_layer_tables(h->pe, bl, dt, h->stream, &h->err)) return rc;
+    // the sums of the call go to the registration's accumulators, or nowhere.  Without a registration the call has
+    // allocated the scratch fields itself; the handle keeps them for the next such call, until gcm_set_boundary_layer(NULL)
+    // or gcm_destroy
+    return pe25d_boundary_layer_rows(h->pe, -1, false, pe25d_sums_on(h->pe, kSumsBoundary), h->stream, &h->err);
+}
+
+int gcm_get_boundary_layer(gcm_handle *h, double *shf, double *evap, double *seconds, int64_t *nsteps) {
+    if (int rc = pe_on_device(h, "gcm_get_boundary_layer")) return rc;
+    return pe25d_sums_get(h->pe, kSumsBoundary, shf, evap, seconds, nsteps, h->stream, &h->err);
+}
+
+int gcm_put_boundary_layer(gcm_handle *h, const double *shf, const double *evap, double seconds, int64_t nsteps) {
+    if (int rc = pe_on_device(h, "gcm_put_boundary_layer")) return rc;
+    return pe25d_sums_put(h->pe, kSumsBoundary, shf, evap, seconds, nsteps, h->stream, &h->err);
+}
+
+int gcm_boundary_layer_reset(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_boundary_layer_reset")) return rc;
+    return pe25d_sums_reset(h->pe, kSumsBoundary, h->stream, &h->err);
+}
+
+int gcm_boundary_layer_surface(int n, const gcm_boundary_layer *bl, double ptop, double sig0, const double *uc,
+                               const double *vc, const double *theta0, const double *q0, const double *p,
+                               double *S, double *z_a, double *cd) {
+    return boundary_layer_surface(n, bl, ptop, sig0, uc, vc, theta0, q0, p, S, z_a, cd, &gcm_create_error());
+}
+
+int gcm_boundary_layer_column(int ncol, int L, const double *dsig, const double *a, const double *x, const double *target,
+                              const double *X, double *X_out, double *X0_surface) {
+    return boundary_layer_column(ncol, L, dsig, a, x, target, X, X_out, X0_surface, &gcm_create_error());
 }
 
 // ------------------------------------------------------------------ convective adjustment

@@ -1,6 +1,6 @@
 // GCM_PE25D, convective adjustment (gcm_set_convect, gcm_convect_step): every column's theta, and optionally q, is mixed
 // wherever it is statically unstable against a neutral profile, conserving the column's enthalpy and water; one launch
-// per step behind the Held-Suarez forcing and ahead of the moist physics.  The contract: include/gcmcore.h.
+// per step behind the Held-Suarez forcing and the boundary layer and ahead of the moist physics.  The contract: include/gcmcore.h.
 //
 //   per cell (device, float64 for either storage type, rounded once to it; level k = 0 is the bottom):
 //     p_lev = sig[k] p + ptop;  Pi = (p_lev / P0)^kappa (exner());  r = 1 (kappa_c = 0: dry), else

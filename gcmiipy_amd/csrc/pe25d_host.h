@@ -10,10 +10,11 @@
 //   pe25d_climate.hip  the zonal-mean climatology: its kernel, its sums and their way to the host and back
 //   pe25d_moist.hip    moist physics: the saturation routine, the kernel and its launches
 //   pe25d_convect.hip  convective adjustment: the pooling routine, the kernel and its launches
+//   pe25d_boundary_layer.hip  surface fluxes and boundary-layer mixing: the routines, the two kernels and their launches
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
 // gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
-// pe25d_hs_rows, pe25d_convect_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample).
+// pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample).
 #pragma once
 #include "pe25d_kernels.h"
 
@@ -115,7 +116,8 @@ struct PeColumnSums {
 };
 struct PeSumsWords { const char *name, *what, *a, *b; };   // gcm_set_<name>, "no <what> registered", the two fields
 constexpr PeSumsWords kPeSumsWords[] = {{"convect", "convective adjustment", "count", "levels"},     // kSumsConvect
-                                        {"moist", "moist physics", "precip", "evap"}};               // kSumsMoist
+                                        {"moist", "moist physics", "precip", "evap"},                // kSumsMoist
+                                        {"boundary_layer", "boundary layer", "shf", "evap"}};        // kSumsBoundary
 // an accumulating launch went out: one application of dt
 inline void sums_count(PeColumnSums &z, double dt) { z.seconds += dt; ++z.n; }
 
@@ -134,6 +136,16 @@ struct PeConvect {
     size_t lds_bytes = 0;                       // the kernel's dynamic LDS at the handle's L; 0: not checked against the device yet
     double kappa_c = 0.0, dt = 0.0;             // the neutral profile (0: dry); what an accumulating launch adds to seconds
     int mix_q = 0;
+};
+
+// Surface fluxes and boundary-layer mixing (pe25d_boundary_layer.hip, gcm_set_boundary_layer): the sums (shf, evap), the
+// float64 scratch fields the two launches hand each other and the parameters of the launches that follow
+// (pe25d_boundary_layer_tables)
+struct PeBoundary {
+    PeColumnSums sums;
+    double *scratch = nullptr;                  // device: cd [H][W], r [H][W], e [H][L-1][W]; L > 40: four park fields [H][L][W]
+    gcm_boundary_layer par{};
+    double dt = 0.0;
 };
 
 struct Pe25d {
@@ -211,6 +223,7 @@ struct Pe25d {
     PeClimate clim;
     PeMoist moist;
     PeConvect convect;
+    PeBoundary boundary;
 };
 
 template <typename T> inline PeBufs<T> &bufs(Pe25d *m);

@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip, pe25d_moist.hip, pe25d_convect.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
+// pe25d_climate.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,11 +65,11 @@ int pe25d_climate_sample(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_climate_reset(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_get_climate(Pe25d *m, double *m3, double *m2, int64_t *nsamples, hipStream_t s, std::string *err);
 int pe25d_put_climate(Pe25d *m, const double *m3, const double *m2, int64_t nsamples, hipStream_t s, std::string *err);
-// The column sums of the convective adjustment (count, levels) and of the moist physics (precip, evap), one set of
-// routines for both (pe25d_state.hip), on `s`, the caller's stream.  pe25d_sums_set: allocated and zeroed (on) or freed;
+// The column sums of the convective adjustment (count, levels), of the moist physics (precip, evap) and of the boundary
+// layer (shf, evap), one set of routines for all (pe25d_state.hip), on `s`, the caller's stream.  pe25d_sums_set: allocated and zeroed (on) or freed;
 // a phase is registered where its sums are in place, and pe25d_sums_on is the one place that says so.  reset, get and
 // put are gcm_<phase>_reset, gcm_get_<phase> and gcm_put_<phase>: GCM_ERR_STATE where the phase is not registered
-enum PeSums { kSumsConvect, kSumsMoist };
+enum PeSums { kSumsConvect, kSumsMoist, kSumsBoundary };
 int pe25d_sums_set(Pe25d *m, PeSums of, bool on, hipStream_t s, std::string *err);
 bool pe25d_sums_on(const Pe25d *m, PeSums of);
 int pe25d_sums_reset(Pe25d *m, PeSums of, hipStream_t s, std::string *err);
@@ -98,6 +98,24 @@ int pe25d_convect_fits(Pe25d *m, const char *fn, std::string *err);
 int pe25d_convect_tables(Pe25d *m, const gcm_convect *cv, double dt, std::string *err);
 int pe25d_convect_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool accumulate, hipStream_t s,
                        std::string *err);
+// Surface fluxes and boundary-layer mixing (pe25d_boundary_layer.hip).  boundary_layer_check / _surface / _column: no
+// handle, no device (gcm_boundary_layer_surface, gcm_boundary_layer_column).  pe25d_boundary_layer_fits: what a
+// registration or a step needs of the handle -- a single domain, L >= 2, sig decreasing in k (GCM_ERR_UNSUPPORTED), a
+// ground temperature (GCM_ERR_STATE); pe25d_boundary_layer_scratch: the float64 scratch fields in place or freed;
+// pe25d_boundary_layer_tables: the checks above, the level tables and the scratch in place and (bl, dt) as the
+// parameters of the launches that follow; pe25d_boundary_layer_rows: the two launches over every row of state set `set`
+// (-1: the current one) on `s`; accumulate: the surface's heat and water go to the registered sums and the call counts
+// as one application of dt
+int boundary_layer_check(const gcm_boundary_layer *bl, const char *fn, std::string *err);
+int boundary_layer_surface(int n, const gcm_boundary_layer *bl, double ptop, double sig0, const double *uc, const double *vc,
+                           const double *theta0, const double *q0, const double *p, double *S, double *z_a, double *cd,
+                           std::string *err);
+int boundary_layer_column(int ncol, int L, const double *dsig, const double *a, const double *x, const double *target,
+                          const double *X, double *X_out, double *X0_surface, std::string *err);
+int pe25d_boundary_layer_fits(Pe25d *m, const char *fn, std::string *err);
+int pe25d_boundary_layer_scratch(Pe25d *m, bool on, hipStream_t s, std::string *err);
+int pe25d_boundary_layer_tables(Pe25d *m, const gcm_boundary_layer *bl, double dt, hipStream_t s, std::string *err);
+int pe25d_boundary_layer_rows(Pe25d *m, int set, bool keep_ghosts, bool accumulate, hipStream_t s, std::string *err);
 int pe25d_new_state_set(const Pe25d *m);    // the set a corrector stage in flight writes (before the swap), else the current one
 int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err);
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan

@@ -1,6 +1,6 @@
 // GCM_PE25D, moist physics (gcm_set_moist, gcm_moist_step): large-scale condensation of the specific humidity q with
 // latent heating of theta and immediate precipitation, and an optional moisture source at the level next to the surface,
-// one launch per step behind the Held-Suarez forcing.  The contract: include/gcmcore.h.
+// one launch per step behind the Held-Suarez forcing, the boundary layer and the convective adjustment.  The contract: include/gcmcore.h.
 //
 //   per cell (device, float64 for either storage type, rounded once to it):
 //     p_lev = sig[k] p + ptop;  Pi = (p_lev / P0)^kappa (exner());  T = theta Pi;  (q_s, dq_s, can) = moist_saturation(T, p_lev)
@@ -21,33 +21,11 @@
 // accumulator word and launch, no atomics.  No LDS but the 2 KB Exner table.
 #pragma clang fp contract(off)
 #include "pe25d_host.h"
+#include "pe25d_moist_sat.h"
 
 namespace gcm {
 
-// ---------------------------------------------------------------- saturation (host and device: one routine)
-constexpr double kMoEps = kRd / kRv;
-constexpr double kMoOneMinusEps = 1.0 - kRd / kRv;
-
-struct MoistSat { double qs, dqs; int can; };
-
-// humidity.saturation_vapor_pressure (the Buck equation) and humidity.rh_to_mmr(1, p_lev, T) in the algebraically equal
-// form q_s = eps e_s / (p_lev - (1 - eps) e_s), with dq_s / dT.  A cell can saturate iff e_s < p_lev; where it cannot
-// (warm air at low pressure) q_s and dq_s are 0 and nobody uses them
-__host__ __device__ inline MoistSat moist_saturation(double T, double p_lev) {
-    const double tc = T - 273.15;
-    const double a = 18.678 - tc / 234.5;
-    const double d = 257.14 + tc;
-    const double b = tc / d;
-    const double es = (0.61121 * 1000.0) * exp(a * b);
-    MoistSat r{0.0, 0.0, es < p_lev ? 1 : 0};
-    if (!r.can) return r;
-    const double den = p_lev - kMoOneMinusEps * es;
-    r.qs = (kMoEps * es) / den;
-    const double dlne = (a * 257.14) / (d * d) - tc / (234.5 * d);
-    r.dqs = (r.qs * (p_lev / den)) * dlne;
-    return r;
-}
-
+// ---------------------------------------------------------------- saturation (host and device: one routine, pe25d_moist_sat.h)
 int moist_check(const gcm_moist *mo, const char *fn, std::string *err) {
     const auto bad = [&](const char *what) { *err = std::string(fn) + ": " + what; return GCM_ERR_ARG; };
     if (!mo) return bad("no parameters");

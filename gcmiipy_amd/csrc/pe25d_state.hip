@@ -193,7 +193,7 @@ int pe25d_new_state_set(const Pe25d *m) { return (m->pack_set >= 0 && m->pack_se
 
 // ---------------------------------------------------------------- what the phases behind the dynamics share
 // Behind a launch that changes rows of state set `set` in place on the caller's stream: theta (and q) always, u and v
-// too where wrote_uv (the Held-Suarez forcing; the moist physics and the convective adjustment write theta and q and
+// too where wrote_uv (the Held-Suarez forcing and the boundary layer; the moist physics and the convective adjustment write theta and q and
 // read p, theta and q).  What the handle remembers about that state is corrected here, once for every such phase:
 //  * the column sums K4 left for this state (sum_k dsig u, sum_k dsig v: pit of the next stage) belong to the winds as
 //    they were.  They stay valid where u and v are not touched, and for the same reason the wait for the third stream's
@@ -228,7 +228,9 @@ const double *pe25d_level_table(Pe25d *m, const char *who, std::string *err) {
     return m->lev_tab;
 }
 
-static PeColumnSums &sums_of(Pe25d *m, PeSums of) { return of == kSumsMoist ? m->moist.sums : m->convect.sums; }
+static PeColumnSums &sums_of(Pe25d *m, PeSums of) {
+    return of == kSumsMoist ? m->moist.sums : of == kSumsBoundary ? m->boundary.sums : m->convect.sums;
+}
 static size_t sums_words(const Pe25d *m) { return (size_t)m->H * m->W; }
 static int sums_zero(Pe25d *m, PeColumnSums &z, const std::string &fn, hipStream_t s, std::string *err) {
     if (int rc = hip_rc(hipMemsetAsync(z.acc, 0, sizeof(double) * 2 * sums_words(m), s), fn.c_str(), err)) return rc;

@@ -515,8 +515,9 @@ int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat
  * seconds (the sum of dt) and nsteps.  One writer per word and launch, no atomics: the same state gives the same bits,
  * and a band's rows hold the bits of the same rows of the single domain.
  * gcm_set_moist: the phase as part of every step taken by gcm_step and gcm_band_run: the Matsuno step, solar_timestep
- * where gcm_set_physics is on, the Held-Suarez forcing where registered, the convective adjustment where registered
- * (gcm_set_convect), then this, then the climatology's sample.
+ * where gcm_set_physics is on, the Held-Suarez forcing where registered, the boundary layer where registered
+ * (gcm_set_boundary_layer), the convective adjustment where registered (gcm_set_convect), then this, then the
+ * climatology's sample.
  * gcm_half_step and gcm_step_phase never apply it.  On a latitude band the ghost rows of theta and q that the
  * post-corrector exchange delivers are adjusted LOCALLY (column-local kernel, the neighbour's own inputs, the neighbour's
  * own bits) and add to no sum; the packed edge rows leave unadjusted: no third exchange, the message format and
@@ -574,7 +575,8 @@ int gcm_moist_saturation(int n, const double *T, const double *p_lev, double *q_
  * an application adds 1 to count where the column had a merged block and sum of n over its merged blocks to levels.
  * seconds (the sum of the registered steps' dt) and nsteps (the applications).  One writer per word and launch, no atomics.
  * gcm_set_convect: the phase as part of every step taken by gcm_step and gcm_band_run: the Matsuno step, solar_timestep
- * where gcm_set_physics is on, the Held-Suarez forcing where registered, then this, then the moist physics where
+ * where gcm_set_physics is on, the Held-Suarez forcing where registered, the boundary layer where registered
+ * (gcm_set_boundary_layer), then this, then the moist physics where
  * registered (which condenses what the mixing left supersaturated), then the climatology's sample.  gcm_half_step and
  * gcm_step_phase never apply it.  On a latitude band the ghost rows of theta and q that the post-corrector exchange
  * delivers are adjusted LOCALLY (column-local kernel, the neighbour's own inputs, the neighbour's own bits) and add to no
@@ -608,6 +610,97 @@ int gcm_put_convect(gcm_handle *h, const double *count, const double *levels, do
 int gcm_convect_reset(gcm_handle *h);
 int gcm_convect_columns(int ncol, int L, const double *y, const double *w, const double *q, const double *dsig, int mix_q,
                         double *y_out, double *q_out, int32_t *nblock);
+/* Surface fluxes and boundary-layer mixing of GCM_PE25D on the device: bulk exchange of momentum, heat and moisture with a
+ * surface of prescribed temperature (the ground temperature of gcm_set_ground: an ocean, it is read and never changed) and
+ * the implicit diffusion that carries the fluxes upwards -- the two parts of Reed & Jablonowski (2012)'s simple physics,
+ * as used by Thatcher & Jablonowski (2016)'s moist Held-Suarez test, that the moist physics above leaves out.  Two
+ * launches per step, fp64 and fp32 handles, SINGLE DOMAINS ONLY.  The reference has nothing of the kind: this is an
+ * addition.  State: p [H][W] in Pa (surface pressure minus ptop), u, v, t = theta, q [L][H][W] on the C grid (u between the
+ * centres i and i + 1, v between the rows j and j + 1); tables sig[k], dsig[k]; level k = 0 is the bottom.  Constants: Rd,
+ * Rv, Cp, G, P0 as for the moist physics.  With this phase on, tau_e of gcm_set_moist should be 0: two moisture sources
+ * otherwise.
+ * Arithmetic, float64 for either storage type, every operation rounded on its own (no contraction), the result rounded
+ * once to the storage type.  Coefficients are explicit, taken from the state at phase entry; the solves are implicit, so
+ * the phase is stable for every dt.
+ * (A) Centre quantities of the column (j, i); i and j are periodic, as in the dynamics and in the climatology's uc, vc;
+ *     T_s is the ground temperature of the cell:
+ *   uc = 0.5 (u[0][j][i] + u[0][j][i-1]);   vc = 0.5 (v[0][j][i] + v[0][j-1][i]);   S = sqrt(uc uc + vc vc)
+ *   p_s = p + ptop;   p_a = sig[0] p + ptop;   Pi_a = (p_a / P0)^kappa from the kernels' own Exner routine;   T_a = theta[0] Pi_a
+ *   z_a = ((Rd / G) (T_a (1 + (Rv / Rd - 1) q[0]))) log(p_s / p_a)
+ *   cd  = cd0 + cd1 min(S, v_cap);     r = S / z_a
+ *   (q_ss, can_s) = the saturation routine of the moist physics at (T_s, p_s)
+ *   interfaces m = 0 .. L-2:   sig_e = sig[m] - 0.5 dsig[m];   p_e = sig_e p + ptop
+ *     T_e = 0.5 (theta[m] Pi_m + theta[m+1] Pi_{m+1});   rho_e = p_e / (Rd T_e);   gr = (G rho_e) / p
+ *     f = 1 where p_e >= p_pbl, else exp(-(((p_pbl - p_e) / p_strat)^2))
+ *     e[m] = (((S z_a) f) (gr gr)) / (0.5 (dsig[m] + dsig[m+1]))
+ *   This is dX/dt = (g^2 / p^2) d/dsigma (rho^2 K dX/dsigma) with K = C S z_a f; the factor C is applied per field below.
+ * (B) Four column solves, each "surface step on level 0, then diffusion":
+ *   field   surface weight x                               target        interface coefficient a[m]
+ *   theta   (dt ch) r                                      T_s / Pi_a    (dt ce) e[m]
+ *   q       (dt ce) r, 0 where can_s = 0                   q_ss          (dt ce) e[m]
+ *   u       dt (0.5 (cd_i r_i + cd_{i+1} r_{i+1}))         0             dt (0.5 (cd_i e_i[m] + cd_{i+1} e_{i+1}[m]))
+ *   v       dt (0.5 (cd_j r_j + cd_{j+1} r_{j+1}))         0             dt (0.5 (cd_j e_j[m] + cd_{j+1} e_{j+1}[m]))
+ *   X0' = (X[0] + x target) / (1 + x)                       the surface step (two-sided: dew is allowed)
+ *   lo[k] = a[k-1] / dsig[k];  up[k] = a[k] / dsig[k]  (a[-1] = a[L-1] = 0);   d = (1 + lo[k]) + up[k]
+ *   w[0] = 1 / d;  w[k] = 1 / (d - lo[k] g[k-1]);  g[k] = up[k] w[k]
+ *   y[0] = X0' w[0];  y[k] = (X[k] + lo[k] y[k-1]) w[k];     X[L-1] = y[L-1];  X[k] = y[k] + g[k] X[k+1]
+ *   The recurrence is the tracer mixing's (gcm_set_tracer_mixing), with float64 coefficients of the column's own.  All
+ *   coefficients are >= 0: max |u| and max |v| of a column do not grow, theta and q stay within the range of the column
+ *   and the target; sum_k X dsig changes by the surface step alone.  An atmosphere at rest (S = 0) and dt = 0 keep every bit.
+ *   p, the tracers and the ground temperature are untouched.
+ * Accumulators in the handle, allocated by gcm_set_boundary_layer, every row, with m = (dsig[0] p) / G:
+ *   shf [H][W], J / m^2:   shf += ((Cp Pi_a) (theta0' - theta0)) m        evap [H][W], kg / m^2:   evap += (q0' - q0) m
+ *   (theta0', q0': the surface step's results in float64); seconds (the sum of dt) and nsteps.  One writer per word and
+ *   launch, no atomics.
+ * The phase is not column-local: a u- or v-column takes cd, r and e from two neighbouring centre columns.  Every launch is
+ * race-free by construction: the first writes cd, r and e of its own column to float64 scratch fields of the handle (two
+ * [H][W], one [H][L-1][W]) and solves theta and q of that column, reading u and v, which it does not write; the second
+ * solves u and v from the scratch fields and the lane's own column.
+ * gcm_set_boundary_layer: the phase as part of every step taken by gcm_step and gcm_end_step: the Matsuno step,
+ * solar_timestep where gcm_set_physics is on, the Held-Suarez forcing where registered, then this, then the convective
+ * adjustment (which mixes what the heated lowest level made unstable), the moist physics (which condenses what became
+ * supersaturated) and the climatology's sample.  gcm_half_step and gcm_step_phase never apply it.  Registration allocates
+ * the accumulators and the scratch fields; NULL switches the phase off and frees them; registering again resets the
+ * accumulators.  Without a registration nothing is launched and every result and timing is as before.
+ * Latitude bands (nranks > 1) are refused: the centre quantities of ghost row -2 need v of row -3, and v of ghost row
+ * H + 1 needs the centre quantities of row H + 2; neither exists, so the ghost rows cannot be advanced locally to the
+ * neighbour's bits, which is how every other phase avoids a third exchange.  gcm_band_run never meets the phase.
+ * gcm_boundary_layer_on: 1 where the phase is registered, else 0 (other models: 0; a null handle GCM_ERR_ARG).
+ * gcm_boundary_layer_step: the same launches once, in place on the current state.  With a registration it adds to the
+ * accumulators, to seconds and to nsteps; without one the sums of the call are dropped, and the call allocates the scratch
+ * fields itself ((L + 1) H W float64 words; four more fields of L H W above 40 levels), which the handle then keeps for the
+ * next such call until gcm_set_boundary_layer(h, NULL) or gcm_destroy frees them.
+ * gcm_get_boundary_layer synchronises the handle's stream once; any pointer may be NULL.  gcm_put_boundary_layer uploads
+ * sums and counters (restarts): both arrays are required, seconds finite and >= 0, nsteps >= 0.
+ * gcm_boundary_layer_reset zeroes all four.
+ * Host probes, the routines the kernels call compiled for the host, no handle, no device.  gcm_boundary_layer_surface: the
+ * level-0 part of (A) for n columns given uc, vc, theta[0], q[0] and p -> S, z_a, cd [n], any of them may be NULL.
+ * gcm_boundary_layer_column: (B) for ncol columns with dsig [L], a [ncol][L-1], x and target [ncol], X [ncol][L] ->
+ * X_out [ncol][L] and, where not NULL, X0_surface [ncol] = X0'.
+ * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, no parameters, a
+ * non-finite parameter, cd0, cd1, ch or ce < 0, v_cap <= 0, p_strat <= 0, a non-finite dt; the probes: n or ncol < 0,
+ * L < 2, a missing array.  GCM_ERR_UNSUPPORTED: other models, L < 2, a sig table that is not strictly decreasing in k
+ * (level 0 must be the bottom), a handle created with nranks > 1.  GCM_ERR_STATE: no ground temperature set
+ * (gcm_set_ground) -- reported by gcm_set_boundary_layer itself, not by the next step -- and get, put or reset without a
+ * registration.                                                                                                     */
+typedef struct {
+    double cd0, cd1;             /* drag: cd = cd0 + cd1 S           (7.0e-4, 6.5e-5 s/m)          */
+    double v_cap;                /* m/s: cd is held at cd0 + cd1 v_cap for S >= v_cap (20)         */
+    double ch, ce;               /* heat and moisture exchange coefficients (0.0044 both)          */
+    double p_pbl;                /* Pa: full mixing at and below this pressure (85000)             */
+    double p_strat;              /* Pa: e-folding scale of the decay above it (10000)              */
+} gcm_boundary_layer;
+int gcm_set_boundary_layer(gcm_handle *h, const gcm_boundary_layer *bl);
+int gcm_boundary_layer_on(const gcm_handle *h);
+int gcm_boundary_layer_step(gcm_handle *h, double dt, const gcm_boundary_layer *bl);
+int gcm_get_boundary_layer(gcm_handle *h, double *shf, double *evap, double *seconds, int64_t *nsteps);
+int gcm_put_boundary_layer(gcm_handle *h, const double *shf, const double *evap, double seconds, int64_t nsteps);
+int gcm_boundary_layer_reset(gcm_handle *h);
+int gcm_boundary_layer_surface(int n, const gcm_boundary_layer *bl, double ptop, double sig0, const double *uc,
+                               const double *vc, const double *theta0, const double *q0, const double *p,
+                               double *S, double *z_a, double *cd);
+int gcm_boundary_layer_column(int ncol, int L, const double *dsig, const double *a, const double *x, const double *target,
+                              const double *X, double *X_out, double *X0_surface);
 /* Zonal-mean climatology of GCM_PE25D accumulated on the device: what a Held-Suarez run is evaluated by -- the time and
  * zonal means of u, v, theta and T, their variances and the eddy fluxes as functions of latitude and level -- without a
  * host round trip per step (fp64 and fp32 handles, single domains and latitude bands).  One launch per sample reads
@@ -652,7 +745,8 @@ int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples);
 int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples);
 /* The end of a GCM_PE25D step whose dynamics the caller took itself: everything gcm_step and gcm_band_run queue behind
  * the corrector, in their order and by their code -- the solar step at the handle's clock, utc += dt, the Held-Suarez
- * forcing, the convective adjustment, the moist physics (their sums, seconds and nsteps advance as in gcm_step), the
+ * forcing, the boundary layer (single domains), the convective adjustment, the moist physics (their sums, seconds and
+ * nsteps advance as in gcm_step), the
  * climatology's step counter and its sample where one is due -- each only if registered, on the handle's stream.  With
  * nothing registered it queues nothing.  On a single domain gcm_half_step(h, 0, dt), gcm_half_step(h, 1, dt),
  * gcm_end_step(h, dt) is gcm_step(h, 1, dt).  On a latitude band it ends a step driven through gcm_step_phase or
