@@ -124,6 +124,8 @@ SYMBOLS = {
     "gcm_sw2d_plan": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "gcm_half_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_end_step": (C.c_int, [_H, C.c_double]),
+    "gcm_end_step_begin": (C.c_int, [_H, C.c_double]),
+    "gcm_end_step_finish": (C.c_int, [_H, C.c_double]),
     "gcm_get_star": (C.c_int, [_H] + [C.c_void_p] * 5),
     "gcm_set_star": (C.c_int, [_H] + [C.c_void_p] * 5),
     "gcm_diag": (C.c_int, [_H, C.c_int, _dp]),
@@ -150,6 +152,8 @@ SYMBOLS = {
     "gcm_moist_reset": (C.c_int, [_H]),
     "gcm_moist_saturation": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     "gcm_set_boundary_layer": (C.c_int, [_H, C.POINTER(BoundaryLayer)]),
+    "gcm_set_band_boundary_layer": (C.c_int, [_H, C.c_int]),
+    "gcm_band_boundary_layer": (C.c_int, [_H]),
     "gcm_boundary_layer_on": (C.c_int, [_H]),
     "gcm_boundary_layer_step": (C.c_int, [_H, C.c_double, C.POINTER(BoundaryLayer)]),
     "gcm_get_boundary_layer": (C.c_int, [_H, _dp, _dp, _dp, C.POINTER(C.c_int64)]),

@@ -87,6 +87,11 @@ class BandRunner:
                                         rows are radiated locally from the neighbour's own inputs, so no third
                                         exchange per step is needed (gcm_set_physics); an engine whose library
                                         call does the whole run (band_run) does it inside that call
+        physics_begin(dt) -> bool, physics_end(dt)
+                                        the same in two parts, for a phase that is not column-local (the boundary
+                                        layer on a band): physics_begin returns True where the ghost rows of the
+                                        current state must be exchanged again before physics_end.  An engine that
+                                        has the pair is driven through it, one that has physics_step only through that
     """
 
     def __init__(self, engine, rank, nranks, dist=None, north=None, south=None):
@@ -175,6 +180,12 @@ class BandRunner:
         self._physics(dt)
 
     def _physics(self, dt):
+        begin, end = getattr(self.e, "physics_begin", None), getattr(self.e, "physics_end", None)
+        if begin is not None and end is not None:
+            if begin(dt):                   # a third exchange: the current state's edge rows as the first part left them
+                self._finish(self.exchange_start())
+            end(dt)
+            return
         ps = getattr(self.e, "physics_step", None)
         if ps is not None:
             ps(dt)
@@ -214,7 +225,7 @@ def merge_climate(parts):
 
 
 def _merge_column(ph, parts):
-    """merge_moist / merge_convect: the records of core._ColumnPhase `ph` in row order -> the whole domain's"""
+    """merge_moist / merge_convect / merge_boundary_layer: the records of core._ColumnPhase `ph` in row order -> the whole domain's"""
     import numpy as np
     parts = list(parts)
     if not parts:
@@ -230,6 +241,13 @@ def merge_moist(parts):
     (Core.moist_sums) in row order; the rows are concatenated.  ValueError where nsteps or seconds differ"""
     from .core import _MOIST
     return _merge_column(_MOIST, parts)
+
+
+def merge_boundary_layer(parts):
+    """the boundary layer's sums of the whole domain from its bands': `parts` are the bands' BoundaryLayer records
+    (Core.boundary_layer_sums) in row order; the rows are concatenated.  ValueError where nsteps or seconds differ"""
+    from .core import _BOUNDARY
+    return _merge_column(_BOUNDARY, parts)
 
 
 def merge_convect(parts):
@@ -331,6 +349,11 @@ class HipBandEngine:
         """Core.set_held_suarez; every band of a run registers the same"""
         self.c.set_held_suarez(geom, **params)
 
+    def set_boundary_layer(self, *off, **params):
+        """Core.set_boundary_layer (the band was created with band_boundary_layer=True); every band of a run registers the
+        same.  merge_boundary_layer() puts the bands' sums together"""
+        self.c.set_boundary_layer(*off, **params)
+
     def set_convect(self, *off, **params):
         """Core.set_convect; every band of a run registers the same.  merge_convect() puts the bands' sums together"""
         self.c.set_convect(*off, **params)
@@ -344,8 +367,21 @@ class HipBandEngine:
         together"""
         self.c.set_climate(every)
 
+    def physics_begin(self, dt):
+        """host-driven band step: behind the unpack of the post-corrector exchange, the walk up to and including the
+        boundary layer (Core.end_step_begin) -> True where the band carries it: the runner exchanges the current state"""
+        if not self.pe:
+            return False
+        self.c.end_step_begin(dt)
+        return self.c.band_boundary_layer and self.c.boundary_layer_registered
+
+    def physics_end(self, dt):
+        """... and the rest of the walk (Core.end_step_finish); the two together are what gcm_band_run queues there"""
+        if self.pe:
+            self.c.end_step_finish(dt)
+
     def physics_step(self, dt):
-        """host-driven band step: behind the unpack of the post-corrector exchange, what gcm_band_run queues there"""
+        """physics_begin + physics_end with nothing between them: Core.end_step, for a runner that does not know the pair"""
         if self.pe:
             self.c.end_step(dt)
 

@@ -4,7 +4,9 @@ temperature of the column physics (when set), the model tag, every option the ha
 with (dx, tracer, kernel variant, filter, Coriolis, dtype, band placement, ensemble members: an ensemble's
 state arrays are (M, H, W), and files without "opt_members" restore as one member), the passive tracers of a GCM_PE25D
 handle (key "tracers", only when it carries some; a band also stores its declared "band_tracers", files without it
-restore with 0, and its ghost-row depth "band_tracer_rows", files without it restore as 1; the tracers' transport scheme
+restore with 0, and its ghost-row depth "band_tracer_rows", files without it restore as 1, and whether it takes the
+boundary layer over its own rows, the option "band_boundary_layer", taken from the handle as it is when saved, files
+without it restore as off and restore() opts in ahead of the registration; the tracers' transport scheme
 is the option "tracer_scheme", files without it restore as centred; the tracers' forcing, Core.set_tracer_forcing, is
 stored per forced tracer i as "forcing_<i>_scalars" (source, decay, pin_value) with "forcing_<i>_emission" and
 "forcing_<i>_pin_mask" where registered, and files without these keys restore with none; their vertical mixing,
@@ -43,6 +45,8 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
            "shape": np.asarray([core.L, core.H, core.W])}
     for name, val in core.options.items():
         out["opt_" + name] = np.asarray(val)
+    if "band_boundary_layer" in core.options:    # (what the handle says now: the opt-in may have been changed since)
+        out["opt_band_boundary_layer"] = np.asarray(bool(core.band_boundary_layer))
     if core.has_ground:
         out["ground"] = core.get_ground()
     if core.tracer_count > 0:
@@ -88,10 +92,12 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, held_suarez, climate, moist, convect, boundary_layer); ground and tracers are None where the file has none, tracer_forcing
+    tracer_mixing, held_suarez, climate, moist, convect, boundary_layer, band_boundary_layer); ground and tracers are
+    None where the file has none, tracer_forcing
     {i: dict(...)} and tracer_mixing {i: K} are then empty; held_suarez is (parameters dict, lat) or None; climate is
     dict(every, n, m3, m2) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
-    dict(params, n, seconds, count, levels) or None; boundary_layer is dict(params, n, seconds, shf, evap) or None"""
+    dict(params, n, seconds, count, levels) or None; boundary_layer is dict(params, n, seconds, shf, evap) or None;
+    band_boundary_layer is whether a band takes that phase (False for files without the option)"""
     d = np.load(path, allow_pickle=False)
     L, H, W = (int(x) for x in d["shape"])
     state = {k: d["state_" + k] for k in "puvtq" if "state_" + k in d.files}
@@ -136,7 +142,7 @@ def load(path):
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
-                tracer_mixing=mixing, **column)
+                tracer_mixing=mixing, band_boundary_layer=bool(opts.get("band_boundary_layer", False)), **column)
 
 
 def restore(path, **core_kwargs):

@@ -396,13 +396,17 @@ class Core:
     def __init__(self, model, width, height, layers=1, dx=0.0, tracer=_lib.TRACER_NONE,
                  variant=_lib.VARIANT_AUTO, geom=None, filter=True, nranks=1, rank=0,
                  global_height=None, row0=0, device=-1, stream=None, halo_steps=1, coriolis=False, dtype="f64",
-                 members=1, band_tracers=0, tracer_scheme=None, band_tracer_rows=1):
+                 members=1, band_tracers=0, tracer_scheme=None, band_tracer_rows=1, band_boundary_layer=False):
         """band_tracers: a GCM_PE25D latitude band (nranks > 1) that carries that many passive tracers
         (gcm_set_band_tracers, right after gcm_create: the ghost-row message and halo_bytes() include them);
         band_tracer_rows: the ghost rows per side those tracers carry, 1 (default) or 2 (what "van_leer" reads on a
         band; gcm_set_band_tracer_rows, right after gcm_create and ahead of the scheme: the message carries that
         many rows of every tracer, and every band of a run must declare the same);
-        tracer_scheme: the passive tracers' transport scheme (set_tracer_scheme), GCM_PE25D only"""
+        tracer_scheme: the passive tracers' transport scheme (set_tracer_scheme), GCM_PE25D only;
+        band_boundary_layer: a GCM_PE25D latitude band that takes the boundary layer over its own rows
+        (gcm_set_band_boundary_layer, right after gcm_create): set_boundary_layer is then accepted, and every step takes
+        a third exchange of the edge rows behind the phase -- band_run does it itself, a host-driven step goes
+        end_step_begin, exchange, end_step_finish.  Every band of a run must declare the same"""
         check_dtype(dtype)
         scheme = tracer_scheme_id(tracer_scheme)
         if scheme != _lib.TRACER_NONE and model != _lib.PE25D:
@@ -421,6 +425,12 @@ class Core:
             raise ValueError("band_tracer_rows needs a GCM_PE25D latitude band (nranks > 1); a single domain's rows "
                              "wrap and carry no ghost rows")
         band_tracer_rows = int(band_tracer_rows) if is_pe_band else 0
+        if band_boundary_layer not in (0, 1, False, True):
+            raise ValueError("band_boundary_layer must be True or False, got %r" % (band_boundary_layer,))
+        band_boundary_layer = bool(band_boundary_layer)
+        if band_boundary_layer and not is_pe_band:
+            raise ValueError("band_boundary_layer needs a GCM_PE25D latitude band (nranks > 1); a single domain takes "
+                             "set_boundary_layer directly")
         self.model, self.W, self.H, self.L = model, int(width), int(height), int(layers)
         # ensemble members (2-D models, single band): every field is (M, H, W) when M > 1
         self.members = max(int(members), 1)
@@ -430,6 +440,7 @@ class Core:
                             nranks=int(nranks), rank=int(rank), row0=int(row0), halo_steps=int(halo_steps),
                             coriolis=bool(coriolis), dtype=dtype, members=int(members), band_tracers=band_tracers,
                             tracer_scheme=_lib.TRACER_NONE, band_tracer_rows=band_tracer_rows,
+                            band_boundary_layer=band_boundary_layer,
                             global_height=int(height if global_height is None else global_height))
         self.has_ground = False
         self._forcing = {}                      # tracer -> the forcing record registered (set_tracer_forcing)
@@ -489,6 +500,8 @@ class Core:
                 _check(lib.gcm_set_band_tracer_rows(self._h, band_tracer_rows), self._h)
             if scheme != _lib.TRACER_NONE:
                 self.set_tracer_scheme(scheme)
+            if band_boundary_layer:
+                _check(lib.gcm_set_band_boundary_layer(self._h, 1), self._h)
         except Exception:
             self.close()
             raise
@@ -714,9 +727,22 @@ class Core:
     def end_step(self, dt):
         """the end of a GCM_PE25D step whose dynamics the caller took itself (gcm_end_step): every registered phase in
         the order of step() / band_run() -- the solar step at the handle's clock, which advances, Held-Suarez, the
-        boundary layer (single domains), the convective adjustment, the moist physics, the climatology's sample where one is due.  half_step(0),
-        half_step(1), end_step(dt) is step(1, dt).  A band: own rows and ghost rows, the ghost rows must be current"""
+        boundary layer, the convective adjustment, the moist physics, the climatology's sample where one is due.  half_step(0),
+        half_step(1), end_step(dt) is step(1, dt).  A band: own rows and ghost rows, the ghost rows must be current; a band
+        with the boundary layer registered is refused (GcmError): end_step_begin, exchange, end_step_finish"""
         _check(lib.gcm_end_step(self._h, float(dt)), self._h)
+
+    def end_step_begin(self, dt):
+        """the first part of end_step (gcm_end_step_begin): the solar step, the clock, Held-Suarez, the boundary layer (a
+        band: over its own rows).  A band with the boundary layer registered then exchanges the ghost rows of the current
+        state (halo_pack2, the transfer, halo_unpack2) ahead of end_step_finish; on every other handle nothing needs to
+        happen between the two, and begin + finish is end_step"""
+        _check(lib.gcm_end_step_begin(self._h, float(dt)), self._h)
+
+    def end_step_finish(self, dt):
+        """the second part of end_step (gcm_end_step_finish): the convective adjustment and the moist physics over own rows
+        and ghost rows, the climatology's sample where one is due"""
+        _check(lib.gcm_end_step_finish(self._h, float(dt)), self._h)
 
     def get_intermediate(self, kind):
         """parity tap (GCM_PE25D): spu, pit, p_n, phi or pgfu of the last half step, as the stage kernels
@@ -892,7 +918,13 @@ class Core:
     def _column_reset(self, ph):
         _check(ph.reset(self._h), self._h)
 
-    # -- surface fluxes and boundary-layer mixing (GCM_PE25D, single domains) ---------------
+    # -- surface fluxes and boundary-layer mixing (GCM_PE25D; a latitude band: Core(..., band_boundary_layer=True)) ----
+    @property
+    def band_boundary_layer(self):
+        """whether this is a band that takes the boundary layer over its own rows, with a third exchange per step
+        (gcm_band_boundary_layer); False: not a GCM_PE25D band, or one that has not opted in"""
+        return bool(_count(lib.gcm_band_boundary_layer(self._h), self._h))
+
     def set_boundary_layer(self, *off, **params):
         """every step of step() / end_step() from now on exchanges momentum, heat and moisture with the surface and mixes
         them upwards on the device (gcm_set_boundary_layer): bulk fluxes against the ground temperature (set_ground first:
@@ -901,7 +933,10 @@ class Core:
         physics, whose tau_e should then be 0.  half_step never applies it.  params: cd0, cd1, v_cap, ch, ce, p_pbl,
         p_strat (BOUNDARY_LAYER_DEFAULTS).  The sensible heat and the water the surface gave are accumulated per column
         (boundary_layer_sums); registering again resets the sums.  set_boundary_layer(None) switches the phase off.
-        ValueError for a refused parameter, GcmError for a latitude band (not supported yet) and for a handle without a
+        A latitude band takes the phase over its own rows where it was created with band_boundary_layer=True: band_run
+        then exchanges the edge rows a third time per step, a host-driven step goes end_step_begin, exchange,
+        end_step_finish (bands.merge_boundary_layer puts the bands' sums together).
+        ValueError for a refused parameter, GcmError for a latitude band that has not opted in and for a handle without a
         ground temperature (the call then changes nothing)"""
         self._set_column(_BOUNDARY, off, params)
 
@@ -918,7 +953,9 @@ class Core:
 
     def boundary_layer_step(self, dt, **params):
         """the boundary layer once, in place on the current state, with the step dt (gcm_boundary_layer_step).  With a
-        registration the call adds to its sums, without one the sums of the call are dropped"""
+        registration the call adds to its sums, without one the sums of the call are dropped.  A band
+        (band_boundary_layer=True): its own rows, from current ghost rows; the ghost rows of u, v, theta and q are stale
+        behind the call until the next exchange of the current state"""
         self._column_step(_BOUNDARY, dt, params)
 
     def boundary_layer_sums(self):

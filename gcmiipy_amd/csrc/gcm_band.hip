@@ -107,20 +107,27 @@ static int band_exchange(gcm_handle *h) {
 // reads ghost rows -- the next stage's K1, column sums, edge rows -- is queued on the second stream, behind
 // the unpack, in stream order.  gcm_band_run joins the two streams once, when it returns.
 // GCM_BAND_COMM_STREAM=1: the exchange on the comm stream and a join per stage, as in round 1.
-// The phases registered behind the dynamics (solar step, Held-Suarez, the climatology's sample) are gcm_pe.hip's: the
+// The phases registered behind the dynamics (solar step, Held-Suarez ... the climatology's sample) are gcm_pe.hip's: the
 // ghost rows' on the second stream right behind the corrector's unpack and ahead of the ghost rows' column sums and
 // anchors (pe_ghost_row_phases), the own rows' at the end of the step on the compute stream (pe_own_row_phases), which
 // takes the ghost rows with it when the exchange was joined into the compute stream.
+// With the boundary layer registered (the band has opted in: gcm_set_band_boundary_layer) the walk splits at it and the
+// step takes a THIRD exchange, of the current state's edge rows as the boundary layer left them (band_step_pe_bl).
+// Without it band_step_pe queues what it always has: no event, launch or copy more.
+static int band_step_pe_bl(gcm_handle *h, double dt, hipStream_t ax);
 static int band_step_pe(gcm_handle *h, double dt) {
     int rc = GCM_OK;
     hipStream_t ax = h->band.on_comm ? nullptr : pe25d_aux_stream(h->pe);
+    const bool bl = band_boundary_layer_on(h);
     for (int stage = 0; stage < 2; ++stage) {
         if ((rc = pe25d_step_phase(h->pe, 2 * stage, dt, h->stream, &h->err, ax != nullptr))) return rc;
         if (ax) {
             if ((rc = band_post(h, ax))) return rc;
             if ((rc = gcm_halo_unpack2(h, h->band.xch.recv_north, h->band.xch.recv_south, ax))) return rc;
-            if (stage == 1 && (rc = pe_ghost_row_phases(h, dt, ax))) return rc;
-            if ((rc = pe25d_prep_ghost_rows(h->pe, &h->err))) return rc;
+            if (stage == 1 && (rc = pe_ghost_row_phases(h, dt, ax, bl ? kPhasesHead : kPhasesAll))) return rc;
+            // (the corrector's ghost rows of a band with the boundary layer: overwritten by the third exchange, behind
+            // which their column sums and anchors are queued; until then nothing on `ax` reads own rows' u and v)
+            if (!(bl && stage == 1) && (rc = pe25d_prep_ghost_rows(h->pe, &h->err))) return rc;
             h->band.join_pending = true;
         }
         if ((rc = pe25d_step_phase(h->pe, 2 * stage + 1, dt, h->stream, &h->err, ax != nullptr))) return rc;
@@ -129,7 +136,39 @@ static int band_step_pe(gcm_handle *h, double dt) {
             if ((rc = band_exchange(h))) return rc;
         }
     }
-    return pe_own_row_phases(h, dt, phase_ghosts(h, ax != nullptr), ax != nullptr, ax);
+    if (bl) return band_step_pe_bl(h, dt, ax);
+    return pe_own_row_phases(h, dt, phase_ghosts(h, ax != nullptr), ax != nullptr, ax, kPhasesAll);
+}
+
+// The end of a band step with the boundary layer registered, behind the corrector (the swap is done: the current state
+// is the new one, and packs and unpacks take it -- no phase pending, pack_set < 0, no star).
+//   compute stream: solar step + Held-Suarez of the own rows (with the exchange on the comm stream: of the ghost rows too),
+//                   [ax: -> ev_comm @ ax, waits: the corrector's unpack and the ghost rows' solar step + Held-Suarez],
+//                   the boundary layer over the own rows, which reads v of ghost row -1 and all of ghost row H,
+//                   the pack of the edge rows as it left them -> ev_pack
+//   ax / comm:      waits ev_pack; the exchange; (ax:) the unpack, the ghost rows' convective adjustment + moist physics,
+//                   their column sums and anchors (pe25d_prep_ghost_rows)
+//   compute stream: (comm: waits ev_comm, the unpack;) convective adjustment + moist physics of the own rows (comm: and of
+//                   the ghost rows), beside the exchange on `ax`; the sample joins the tail of `ax` first
+// The wait for `ax` also frees the send buffers (the corrector's exchange has read them) and keeps the third unpack,
+// which follows ev_pack, behind every read of the ghost rows by the boundary layer.  The events are the run's own
+// (ev_comm, ev_pack), each waited for in stream order before it is recorded again.
+static int band_step_pe_bl(gcm_handle *h, double dt, hipStream_t ax) {
+    int rc = GCM_OK;
+    // (the head's walk makes the compute stream wait for `ax` ahead of the boundary layer: -> ev_comm @ ax)
+    if ((rc = pe_own_row_phases(h, dt, phase_ghosts(h, ax != nullptr), ax != nullptr, ax, kPhasesHead))) return rc;
+    if (!ax) {                                             // (pack -> ev_pack @ st, comm waits; the group; st waits, the unpack)
+        if ((rc = pack_edges(h)) || (rc = band_exchange(h))) return rc;
+    } else {
+        if ((rc = gcm_halo_pack2(h, h->band.xch.send_north, h->band.xch.send_south, h->stream))) return rc;
+        HIPCHK(h, hipEventRecord(h->band.ev_pack, h->stream));
+        HIPCHK(h, hipStreamWaitEvent(ax, h->band.ev_pack, 0));
+        if ((rc = band_post(h, ax))) return rc;
+        if ((rc = gcm_halo_unpack2(h, h->band.xch.recv_north, h->band.xch.recv_south, ax))) return rc;
+        if ((rc = pe_ghost_row_phases(h, dt, ax, kPhasesTail))) return rc;
+        if ((rc = pe25d_prep_ghost_rows(h->pe, &h->err))) return rc;
+    }
+    return pe_own_row_phases(h, dt, phase_ghosts(h, ax != nullptr), ax != nullptr, ax, kPhasesTail);
 }
 
 static int run_pe(gcm_handle *h, int nsteps, double dt) {
@@ -254,7 +293,11 @@ static int run_deep_overlapped(gcm_handle *h, int nsteps, double dt) {
 //   run_pe, every stage    ax (pe25d: with   ax         ax      none per stage: stream order on ax.  When the run returns:
 //                          the edge rows)                       -> ev_comm @ ax, st waits
 //                                                               a step that ends with a climatology sample: -> ev_comm @ ax, st waits ahead of the sample
+//   .. boundary layer on   st (third exch.:  ax         ax      behind the corrector's unpack and the ghost rows' solar + Held-Suarez: -> ev_comm @ ax, st waits
+//      (third exchange)    the current                          ahead of the own rows' boundary layer; pack -> ev_pack @ st, ax waits; the ghost rows'
+//                          state's edge rows)                   convect + moist and their column sums follow the unpack on ax
 //   .. GCM_BAND_COMM_STREAM=1  ax (as above) comm       st      comm waits for the edge rows' pack (pe25d_wait_edges); group -> ev_comm @ comm, st waits
+//      .. boundary layer on  st (third exch.) comm      st      pack -> ev_pack @ st, comm waits; group -> ev_comm @ comm, st waits ahead of the unpack
 //   run_exchange_per_step  st                comm       st      pack -> ev_pack @ st, comm waits; group -> ev_comm @ comm, st waits ahead of the boundary rows
 //   run_deep               st                st         st      none: stream order
 //   run_deep_overlapped    st (window_last,  comm       st      pack -> ev_pack @ st, comm waits; group -> ev_comm @ comm; st waits in window_first behind

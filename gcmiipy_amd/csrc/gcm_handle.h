@@ -155,10 +155,16 @@ extern "C" int launch_status(gcm_handle *h);
 // gcm_pe.hip, for gcm_step, gcm_band_run and gcm_end_step: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, boundary layer, convective adjustment, moist physics, sample), each
 // launched only if it is registered -- their tables before a run, a band's ghost rows on its second stream `ax` behind a
 // corrector's unpack, and the end of every step on the handle's stream over rows [-g, H + g), which joins `tail` before a sample
+// The walk splits at the boundary layer (`which`): a band that carries it exchanges the current state's edge rows between
+// kPhasesHead (solar step, clock, Held-Suarez, boundary layer over the own rows) and kPhasesTail (convective adjustment, moist
+// physics, sample); everybody else walks kPhasesAll
+enum { kPhasesHead = 1, kPhasesTail = 2, kPhasesAll = 3 };
 extern "C" int pe_step(gcm_handle *h, int nsteps, double dt);        // gcm_step of a GCM_PE25D handle
 extern "C" int pe_phase_tables(gcm_handle *h, int nsteps, double dt);
-extern "C" int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax);
-extern "C" int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail);
+extern "C" int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax, int which);
+extern "C" int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail, int which);
+// a band with the boundary layer registered (which takes the opt-in, gcm_set_band_boundary_layer): three exchanges per step
+inline bool band_boundary_layer_on(const gcm_handle *h) { return h->pe && !h->wrap && gcm::pe25d_sums_on(h->pe, gcm::kSumsBoundary); }
 // ghost rows a side that a phase's launch on the handle's stream takes with the own rows: a band's, unless they are
 // forced apart on the second stream (pe_ghost_row_phases)
 inline int phase_ghosts(const gcm_handle *h, bool apart = false) { return h->wrap || apart ? 0 : gcm::kGhost; }

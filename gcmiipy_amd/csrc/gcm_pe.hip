@@ -10,7 +10,8 @@ using namespace gcm;
 
 // ------------------------------------------------------------------ the phases of a step
 // The order is the model's: the dynamics step, the solar step at the current clock, utc += dt, the Held-Suarez forcing,
-// the boundary layer, the convective adjustment, the moist physics, the sample.  Each launch runs only if its phase is
+// the boundary layer (on a band: then a third exchange of the edge rows), the convective adjustment, the moist physics,
+// the sample.  Each launch runs only if its phase is
 // registered: the solar step and the forcing in GcmPhases, the boundary layer, the adjustment and the moist physics where
 // their sums are in place (pe25d_sums_on),
 // the climatology in pe25d_climate_due.  The order is written down in pe_phase_rows, and in pe_phase_tables for what a
@@ -18,7 +19,8 @@ using namespace gcm;
 
 // gcm_set_physics: the radiation kernel's tables in place before a run queues anything (no-op without physics); then the
 // registered forcing's device tables for dt (none: GCM_OK), the boundary layer's level tables, scratch fields and parameters
-// for dt, and the convective adjustment's and the moist physics' level tables and parameters for dt
+// for dt, and the convective adjustment's and the moist physics' level tables and parameters for dt.  Both parts of a
+// split walk (gcm_end_step_begin, gcm_end_step_finish) call it: what is in place for dt already is not built again
 int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
     const GcmPhases &ph = h->phases;
     if (ph.solar)
@@ -40,41 +42,58 @@ int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
 
 // The registered phases that change the state, over rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one)
 // on `s`, each launch behind the one before it in stream order.  Every phase but the boundary layer is column-local, so a
-// row gets the same bits whichever launch takes it: a single domain's, a band's own rows', a neighbour's ghost rows'; the
-// boundary layer reads neighbouring columns and rows and is registered on single domains only.  Two callers:
+// row gets the same bits whichever launch takes it: a single domain's, a band's own rows', a neighbour's ghost rows'.  The
+// boundary layer reads neighbouring columns and rows: it takes every row of a single domain, and the own rows of a band
+// that has opted in (gcm_set_band_boundary_layer), whose ghost rows are NOT advanced through it -- the caller exchanges
+// the current state's edge rows again behind it.  The walk therefore splits there (`which`): kPhasesHead, up to and
+// including the boundary layer; kPhasesTail, behind it; kPhasesAll, both, which a band with the boundary layer registered
+// refuses.  Two callers:
 //  * own: the end of every step, the rows of the handle on its stream (pe_own_row_phases).  The clock advances behind
 //    the solar step, and the boundary layer's shf and evap, the convective adjustment's counts and the moist physics'
 //    precipitation and evaporation go to the handle's sums (the kernels add rows [0, H) only);
-//  * !own: a band's ghost rows as the post-corrector exchange delivered them, on the second stream behind the unpack and
+//  * !own: a band's ghost rows as the last exchange delivered them, on the second stream behind the unpack and
 //    AHEAD of the ghost rows' column sums and anchors, which read u, v and theta (pe_ghost_row_phases).  The rows are
 //    forced locally with the neighbour's own inputs and tables -- theta, p, u, v as delivered, the ground temperature's
 //    ghost rows, the latitude of the global row -- hence to the neighbour's own bits.  Their counts and precipitation
-//    belong to the neighbour's sums: these launches accumulate nothing, and the clock stays.
-// keep_ghosts: the caller forces the ghost rows itself ahead of their column sums and anchors (gcm_band_run)
-static int pe_phase_rows(gcm_handle *h, double dt, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool own, hipStream_t s) {
+//    belong to the neighbour's sums: these launches accumulate nothing, the clock stays, and the boundary layer is
+//    skipped (the head's ghost rows are overwritten by the exchange behind it, the tail's arrive with it applied).
+// keep_ghosts: the caller forces the ghost rows itself ahead of their column sums and anchors (gcm_band_run), on the
+// stream `ghosts` where that is another one than `s` (else null): the boundary layer, which reads v of ghost row -1 and
+// all of ghost row H, then waits for that stream's position (the unpack, the ghost rows' solar step and forcing)
+static int pe_phase_rows(gcm_handle *h, double dt, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool own, hipStream_t s,
+                         int which, hipStream_t ghosts = nullptr) {
     GcmPhases &ph = h->phases;
-    if (ph.solar) {
-        // no_limits_2_5d.py:229-234 with the physics below full_timestep's early return (:96): the dynamics step, then
-        // solar_timestep (:66-75) at the current utc, which changes theta and the ground temperature in place AFTER the
-        // post-corrector exchange has left, then utc += dt
-        if (int rc = pe25d_solar_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, dt, ph.phys.utc, ph.phys.albedo, s, &h->err)) return rc;
-        if (own) ph.phys.utc += dt;
+    if (which == kPhasesAll && band_boundary_layer_on(h))
+        return fail(h, GCM_ERR_STATE, "boundary layer on a latitude band: the phase walk splits at it, with an exchange of the current state between the two parts");
+    if (which & kPhasesHead) {
+        if (ph.solar) {
+            // no_limits_2_5d.py:229-234 with the physics below full_timestep's early return (:96): the dynamics step, then
+            // solar_timestep (:66-75) at the current utc, which changes theta and the ground temperature in place AFTER the
+            // post-corrector exchange has left, then utc += dt
+            if (int rc = pe25d_solar_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, dt, ph.phys.utc, ph.phys.albedo, s, &h->err)) return rc;
+            if (own) ph.phys.utc += dt;
+        }
+        // gcm_set_held_suarez, behind the solar step.  The launch writes u and v, which the next stage's chain B reads: it
+        // invalidates the fork at the last K4, so that the next step's launches on the second and third stream, which read own
+        // rows' u and v, follow this stream's position; and it marks the state's column sums stale, so that behind a ghost-row
+        // launch pe25d_prep_ghost_rows leaves them to the next stage (pe25d_phase_wrote)
+        if (ph.held_suarez)
+            if (int rc = pe25d_hs_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, s, &h->err)) return rc;
+        // gcm_set_boundary_layer: u, v, theta and q, behind the forcing: it heats and moistens the lowest level, the
+        // adjustment then mixes what became unstable.  The launches write u and v, as the forcing's does.  They take every
+        // row of a single domain, the own rows of a band, whatever [j0, j1) says: a single domain's walk is its own rows,
+        // all of them, and a band's ghost rows ride in [j0, j1) for the column-local phases only
+        if (own && pe25d_sums_on(h->pe, kSumsBoundary)) {
+            if (h->wrap && (j0 != 0 || j1 != h->H || jb1 > jb0))
+                return fail(h, GCM_ERR_STATE, "boundary layer: the phase walk of a single domain's own rows only");
+            if (ghosts && ghosts != s) {                   // (gcm_band_run's own join event: see pe_own_row_phases)
+                HIPCHK(h, hipEventRecord(h->band.ev_comm, ghosts));
+                HIPCHK(h, hipStreamWaitEvent(s, h->band.ev_comm, 0));
+            }
+            if (int rc = pe25d_boundary_layer_rows(h->pe, set, keep_ghosts, own, s, &h->err)) return rc;
+        }
     }
-    // gcm_set_held_suarez, behind the solar step.  The launch writes u and v, which the next stage's chain B reads: it
-    // invalidates the fork at the last K4, so that the next step's launches on the second and third stream, which read own
-    // rows' u and v, follow this stream's position; and it marks the state's column sums stale, so that behind a ghost-row
-    // launch pe25d_prep_ghost_rows leaves them to the next stage (pe25d_phase_wrote)
-    if (ph.held_suarez)
-        if (int rc = pe25d_hs_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, s, &h->err)) return rc;
-    // gcm_set_boundary_layer: u, v, theta and q of a single domain (a band refuses the registration), behind the forcing:
-    // it heats and moistens the lowest level, the adjustment then mixes what became unstable.  The launches write u and v,
-    // as the forcing's does.  They take every row of the domain whatever [j0, j1) says: a single domain's walk is its own
-    // rows, all of them, and no band gets here
-    if (pe25d_sums_on(h->pe, kSumsBoundary)) {
-        if (!own || !h->wrap || j0 != 0 || j1 != h->H || jb1 > jb0)
-            return fail(h, GCM_ERR_STATE, "boundary layer: the phase walk of a single domain's own rows only");
-        if (int rc = pe25d_boundary_layer_rows(h->pe, set, keep_ghosts, own, s, &h->err)) return rc;
-    }
+    if (!(which & kPhasesTail)) return GCM_OK;
     // gcm_set_convect: theta and q, ahead of the moist physics, which then condenses whatever the mixing left supersaturated
     if (pe25d_sums_on(h->pe, kSumsConvect))
         if (int rc = pe25d_convect_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, own, s, &h->err)) return rc;
@@ -83,27 +102,32 @@ static int pe_phase_rows(gcm_handle *h, double dt, int set, int j0, int j1, int 
     return GCM_OK;
 }
 
-// gcm_band_run with the exchange on the second stream `ax`: the ghost rows' phases, behind a corrector's unpack and ahead
-// of pe25d_prep_ghost_rows; the band's own rows follow the corrector on the compute stream (pe_own_row_phases)
-int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax) {
-    return pe_phase_rows(h, dt, pe25d_new_state_set(h->pe), -kGhost, 0, h->H, h->H + kGhost, true, false, ax);
+// gcm_band_run with the exchange on the second stream `ax`: the ghost rows' phases, behind an unpack and ahead of
+// pe25d_prep_ghost_rows; the band's own rows follow the corrector on the compute stream (pe_own_row_phases).  With the
+// boundary layer registered the head follows the corrector's unpack and the tail the third exchange's
+int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax, int which) {
+    return pe_phase_rows(h, dt, pe25d_new_state_set(h->pe), -kGhost, 0, h->H, h->H + kGhost, true, false, ax, which);
 }
 
 // The end of every step, on the handle's stream: rows [-g, H + g) (phase_ghosts) -- a band's own rows, and the ghost rows
 // with them where the exchange was joined into the compute stream.  The compute stream has waited for the edge rows and
 // their pack by then (update_interior), so the rows that left are as the corrector made them and the neighbour forces
-// them itself.  Three callers: gcm_step (g = 0), gcm_band_run, and gcm_end_step for a caller that takes the dynamics
-// step itself.  tail: the stream whose tail the handle's stream joins before a sample (gcm_band_run's second stream,
-// where the exchange runs there), else null
-int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail) {
-    if (int rc = pe_phase_rows(h, dt, -1, -g, h->H + g, 0, 0, keep_ghosts, true, h->stream)) return rc;
+// them itself.  Callers: gcm_step (g = 0), gcm_band_run, and gcm_end_step, gcm_end_step_begin and gcm_end_step_finish
+// for a caller that takes the dynamics step itself.  which: the whole walk, or one of the parts a band with the boundary
+// layer registered exchanges between (pe_phase_rows); the sample belongs to the tail.  tail: the stream whose tail the
+// handle's stream joins before a sample, and before a band's boundary layer (gcm_band_run's second stream, where the
+// exchange runs and the ghost rows are forced there), else null
+int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail, int which) {
+    if (int rc = pe_phase_rows(h, dt, -1, -g, h->H + g, 0, 0, keep_ghosts, true, h->stream, which, h->wrap ? nullptr : tail)) return rc;
+    if (!(which & kPhasesTail)) return GCM_OK;
     // gcm_set_climate: a sample of the state the step leaves, behind every phase that changes it
     if (!pe25d_climate_due(h->pe)) return GCM_OK;
     // a band: the sample reads the own rows as the phases above left them on the compute stream, and row -1 of v,
-    // the first north ghost row, as the post-corrector exchange delivered it and the ghost rows' Held-Suarez launch forced
-    // it -- on the second stream where the exchange runs there.  The compute stream joins that stream's tail first (the
+    // the first north ghost row, as the step's last exchange delivered it (the post-corrector exchange and the ghost
+    // rows' Held-Suarez launch; with the boundary layer registered the third exchange) -- on the second stream where the
+    // exchange runs there.  The compute stream joins that stream's tail first (the
     // unpack, the ghost rows' physics, their column sums), on the steps that sample only; the event is gcm_band_run's own
-    // join event, which nobody else records between a run's first exchange and its end
+    // join event, which nobody else records between a run's first exchange and its end but the step itself, in stream order
     if (tail) {
         HIPCHK(h, hipEventRecord(h->band.ev_comm, tail));
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->band.ev_comm, 0));
@@ -116,7 +140,7 @@ int pe_step(gcm_handle *h, int nsteps, double dt) {
     if (int rc = pe_phase_tables(h, nsteps, dt)) return rc;
     for (int n = 0; n < nsteps; ++n) {
         if (int rc = pe25d_step(h->pe, dt, h->stream, &h->err)) return rc;
-        if (int rc = pe_own_row_phases(h, dt, 0, false, nullptr)) return rc;
+        if (int rc = pe_own_row_phases(h, dt, 0, false, nullptr, kPhasesAll)) return rc;
     }
     pe25d_join_tracers(h->pe, h->stream);             // (the passive tracers' tail on the second stream)
     return GCM_OK;
@@ -126,14 +150,23 @@ extern "C" {
 
 // ------------------------------------------------------------------ the end of a step whose dynamics the caller took itself
 // What gcm_band_run queues behind a corrector where the ghost rows ride with the own rows (GCM_BAND_COMM_STREAM=1): the
-// tables for dt, then every registered phase over own rows and ghost rows on the handle's stream, the clock, the sample
-int gcm_end_step(gcm_handle *h, double dt) {
-    if (int rc = pe_only(h, "gcm_end_step")) return rc;
-    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_end_step: dt must be finite");
+// tables for dt, then every registered phase over own rows and ghost rows on the handle's stream, the clock, the sample.
+// gcm_end_step is the whole walk; gcm_end_step_begin and gcm_end_step_finish are its two parts, for a band with the
+// boundary layer registered, which exchanges the current state's edge rows between them
+static int end_step_part(gcm_handle *h, double dt, const char *fn, int which) {
+    if (int rc = pe_only(h, fn)) return rc;
+    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, std::string(fn) + ": dt must be finite");
+    if (which == kPhasesAll && band_boundary_layer_on(h))
+        return fail(h, GCM_ERR_STATE, std::string(fn) + ": the boundary layer is registered on this band, whose edge rows are exchanged again behind it: "
+                                      "call gcm_end_step_begin, exchange the current state's ghost rows, then gcm_end_step_finish");
     if (int rc = select_device(h)) return rc;
     if (int rc = pe_phase_tables(h, 1, dt)) return rc;
-    return pe_own_row_phases(h, dt, phase_ghosts(h), false, nullptr);
+    return pe_own_row_phases(h, dt, phase_ghosts(h), false, nullptr, which);
 }
+
+int gcm_end_step(gcm_handle *h, double dt) { return end_step_part(h, dt, "gcm_end_step", kPhasesAll); }
+int gcm_end_step_begin(gcm_handle *h, double dt) { return end_step_part(h, dt, "gcm_end_step_begin", kPhasesHead); }
+int gcm_end_step_finish(gcm_handle *h, double dt) { return end_step_part(h, dt, "gcm_end_step_finish", kPhasesTail); }
 
 // ------------------------------------------------------------------ passive tracers
 int gcm_set_tracers(gcm_handle *h, int n, const double *c) {
@@ -318,7 +351,18 @@ int gcm_held_suarez_tables(int L, const double *sig, int nlat, const double *lat
 }
 
 // ------------------------------------------------------------------ surface fluxes and boundary-layer mixing
-// a latitude band, levels that do not start at the bottom, no ground temperature: refused in the call itself
+// a band opts in to the phase over its own rows and to the third exchange per step that goes with it
+int gcm_set_band_boundary_layer(gcm_handle *h, int on) {
+    if (int rc = pe_only(h, "gcm_set_band_boundary_layer", true)) return rc;
+    return pe25d_set_band_boundary_layer(h->pe, on != 0, &h->err);
+}
+
+int gcm_band_boundary_layer(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && pe25d_band_boundary_layer(h->pe) ? 1 : 0;
+}
+
+// a latitude band that has not opted in, levels that do not start at the bottom, no ground temperature: refused in the call itself
 int gcm_set_boundary_layer(gcm_handle *h, const gcm_boundary_layer *bl) {
     if (int rc = pe_only(h, "gcm_set_boundary_layer")) return rc;
     if (bl) {
@@ -353,7 +397,8 @@ int gcm_boundary_layer_step(gcm_handle *h, double dt, const gcm_boundary_layer *
     if (int rc = pe25d_boundary_layer_tables(h->pe, bl, dt, h->stream, &h->err)) return rc;
     // the sums of the call go to the registration's accumulators, or nowhere.  Without a registration the call has
     // allocated the scratch fields itself; the handle keeps them for the next such call, until gcm_set_boundary_layer(NULL)
-    // or gcm_destroy
+    // or gcm_destroy.  A band that has opted in: its own rows, from current ghost rows; the ghost rows of u, v, theta and q
+    // are stale behind the call until the caller's next exchange
     return pe25d_boundary_layer_rows(h->pe, -1, false, pe25d_sums_on(h->pe, kSumsBoundary), h->stream, &h->err);
 }
 

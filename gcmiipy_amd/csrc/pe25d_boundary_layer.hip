@@ -36,6 +36,13 @@
 // (8 bytes a word: no bank conflicts), 1.5 KB a level for theta + q and 1 KB for a wind: 60 KB at L = 40.  Above
 // kBlLdsLevels they are parked in float64 scratch fields of the handle instead, with the same arithmetic.  No register
 // array is indexed by a loop counter that is not unrolled: the kernels use no scratch memory.
+//
+// A latitude band that has opted in (gcm_set_band_boundary_layer) takes the BAND form of both kernels over its own rows:
+// j does not wrap, rows j - 1 and j + 1 are the neighbouring rows of the band's allocation (ghost rows -1 and H as the
+// last exchange and the ghost rows' solar step and Held-Suarez forcing left them).  Launch 1 then runs over rows [0, H]:
+// the workgroups of ghost row H form and store cd, r and e only (what v of row H - 1 reads), launch 2 over rows [0, H).
+// The arithmetic of a row is the single domain's, in the same order: the same bits.  The ghost rows are not advanced;
+// the caller exchanges the edge rows again behind the phase.
 #pragma clang fp contract(off)
 #include "pe25d_host.h"
 #include "pe25d_moist_sat.h"
@@ -164,8 +171,8 @@ struct BlArgsT {
     const double *gt;                // [j][i]
     const double *sig, *dsig;        // [L]
     const double *exner_tab;
-    double *cd, *r, *e;              // scratch: [j][i], [j][i], [j][L-1][i]
-    double *park;                    // L > kBlLdsLevels: kBlParkFields fields [j][L][i]; else null (LDS)
+    double *cd, *r, *e;              // scratch: [j][i], [j][i], [j][L-1][i]; a band: H + 1 rows of each
+    double *park;                    // L > kBlLdsLevels: kBlParkFields fields [j][L][i] of H rows; else null (LDS)
     double *shf, *evap;              // [H][W], or null: the launch accumulates nothing
     BlPar par;
     double ptop, dt, dtch, dtce;     // dt ch, dt ce
@@ -181,8 +188,8 @@ struct BlPark {
     __device__ __forceinline__ double get(int arr, int k) const { return base[arr * field + k * level]; }
 };
 
-// grid (tiles of 64 columns, rows)
-template <typename T, bool LDS>
+// grid (tiles of 64 columns, rows); BAND: rows [0, H] of a latitude band, j not periodic, row H forms cd, r and e only
+template <typename T, bool LDS, bool BAND>
 __global__ __launch_bounds__(kBlLanes) void pe_bl_theta_q_kernel(BlArgsT<T> a) {
     __shared__ double tab[kExnerTabDoubles];
     extern __shared__ double bl_lds[];
@@ -191,11 +198,11 @@ __global__ __launch_bounds__(kBlLanes) void pe_bl_theta_q_kernel(BlArgsT<T> a) {
     __syncthreads();
     const int W = a.W, H = a.H, L = a.L;
     const int i = (int)blockIdx.x * kBlLanes + lane, j = (int)blockIdx.y;
-    if (i >= W || j >= H) return;
+    if (i >= W || j >= (BAND ? H + 1 : H)) return;
     const long c2 = (long)j * W + i, c3 = (long)j * L * W + i, e3 = (long)j * (L - 1) * W + i;
     const BlPark<LDS> park = LDS ? BlPark<LDS>{bl_lds + lane, (long)L * kBlLanes, kBlLanes}
                                  : BlPark<LDS>{a.park + c3, (long)H * L * W, W};
-    const int iw = i == 0 ? W - 1 : i - 1, jn = j == 0 ? H - 1 : j - 1;
+    const int iw = i == 0 ? W - 1 : i - 1, jn = BAND ? j - 1 : (j == 0 ? H - 1 : j - 1);
     const double pc = (double)a.p[c2], Ts = a.gt[c2];
     const double th0 = (double)a.t[c3], q0 = (double)a.q[c3];
     const double uc = 0.5 * ((double)a.u[c3] + (double)a.u[(long)j * L * W + iw]);
@@ -205,6 +212,18 @@ __global__ __launch_bounds__(kBlLanes) void pe_bl_theta_q_kernel(BlArgsT<T> a) {
     a.cd[c2] = sf.cd;
     a.r[c2] = sf.r;
     const double Sz = sf.S * sf.z_a;
+    if (BAND && j == H) {
+        // the south ghost row (uniform per workgroup): e of its interfaces from the state as it came in, in the order of
+        // the march below; no solve, no store to theta or q, no sum, nothing parked
+        double th_c = th0, pi_c = pi_a;
+        for (int kk = 0; kk + 1 < L; ++kk) {
+            const double th_n = (double)a.t[c3 + (long)(kk + 1) * W];
+            const double pi_n = exner(a.sig[kk + 1] * pc + a.ptop, tab);
+            a.e[e3 + (long)kk * W] = bl_interface(a.par, Sz, pc, a.ptop, a.sig[kk], a.dsig[kk], a.dsig[kk + 1], th_c, pi_c, th_n, pi_n);
+            th_c = th_n; pi_c = pi_n;
+        }
+        return;
+    }
     const MoistSat ss = moist_saturation(Ts, pc + a.ptop);
     const double th0n = bl_surface_step(th0, a.dtch * sf.r, Ts / pi_a);
     const double q0n = bl_surface_step(q0, ss.can ? a.dtce * sf.r : 0.0, ss.qs);
@@ -262,8 +281,9 @@ __global__ __launch_bounds__(kBlLanes) void pe_bl_theta_q_kernel(BlArgsT<T> a) {
     }
 }
 
-// grid (tiles of 64 columns, rows, 2): plane 0 solves u (between the centres i and i + 1), plane 1 v (rows j and j + 1)
-template <typename T, bool LDS>
+// grid (tiles of 64 columns, rows, 2): plane 0 solves u (between the centres i and i + 1), plane 1 v (rows j and j + 1);
+// BAND: rows [0, H) of a latitude band, row j + 1 of the scratch fields does not wrap (row H: the south ghost row's)
+template <typename T, bool LDS, bool BAND>
 __global__ __launch_bounds__(kBlLanes) void pe_bl_wind_kernel(BlArgsT<T> a) {
     extern __shared__ double bl_lds[];
     const int lane = (int)threadIdx.x;
@@ -271,7 +291,7 @@ __global__ __launch_bounds__(kBlLanes) void pe_bl_wind_kernel(BlArgsT<T> a) {
     const int i = (int)blockIdx.x * kBlLanes + lane, j = (int)blockIdx.y, f = (int)blockIdx.z;
     if (i >= W || j >= H) return;
     const long c2 = (long)j * W + i, c3 = (long)j * L * W + i;
-    const int i2 = f == 0 ? (i + 1 == W ? 0 : i + 1) : i, j2 = f == 0 ? j : (j + 1 == H ? 0 : j + 1);
+    const int i2 = f == 0 ? (i + 1 == W ? 0 : i + 1) : i, j2 = f == 0 ? j : (!BAND && j + 1 == H ? 0 : j + 1);
     const long n2 = (long)j2 * W + i2;
     const long ea = (long)j * (L - 1) * W + i, eb = (long)j2 * (L - 1) * W + i2;
     const BlPark<LDS> park = LDS ? BlPark<LDS>{bl_lds + lane, (long)L * kBlLanes, kBlLanes}
@@ -315,22 +335,43 @@ __global__ __launch_bounds__(kBlLanes) void pe_bl_wind_kernel(BlArgsT<T> a) {
 }
 
 // ---------------------------------------------------------------- the handle's side
+// rows of cd, r and e: a band's own rows and its first south ghost row (what v of row H - 1 reads)
+static size_t bl_centre_rows(const Pe25d *m) { return (size_t)m->H + (m->wrap ? 0 : 1); }
 static size_t bl_scratch_words(const Pe25d *m) {
-    const size_t cells = (size_t)m->H * m->W;
-    return cells * (2 + (size_t)(m->L - 1)) + (m->L > kBlLdsLevels ? cells * m->L * kBlParkFields : 0);
+    const size_t cells = (size_t)m->H * m->W, centres = bl_centre_rows(m) * m->W;
+    return centres * (2 + (size_t)(m->L - 1)) + (m->L > kBlLdsLevels ? cells * m->L * kBlParkFields : 0);
 }
 
-// what a registration or a step needs of the handle.  GCM_ERR_UNSUPPORTED: a latitude band (the centre quantities of the
-// outer ghost rows need rows that do not exist), L < 2, levels that do not start at the bottom; GCM_ERR_STATE: no ground
+// what a registration or a step needs of the handle.  GCM_ERR_UNSUPPORTED: a latitude band that has not opted in (the
+// centre quantities of the outer ghost rows need rows that do not exist: the phase takes the own rows and the caller
+// exchanges the edge rows again, gcm_set_band_boundary_layer), L < 2, levels that do not start at the bottom;
+// GCM_ERR_STATE: no ground
 int pe25d_boundary_layer_fits(Pe25d *m, const char *fn, std::string *err) {
     const auto no = [&](int rc, const char *what) { *err = std::string(fn) + ": " + what; return rc; };
-    if (!m->wrap) return no(GCM_ERR_UNSUPPORTED, "single domains only (a latitude band's ghost rows cannot be advanced locally)");
+    if (!m->wrap && !m->boundary.band)
+        return no(GCM_ERR_UNSUPPORTED, "single domains only (a latitude band's ghost rows cannot be advanced locally: gcm_set_band_boundary_layer)");
     if (m->L < 2) return no(GCM_ERR_UNSUPPORTED, "L must be 2 or more");
     for (int k = 1; k < m->L; ++k)
         if (!(m->sig_host[k] < m->sig_host[k - 1])) return no(GCM_ERR_UNSUPPORTED, "sig must decrease strictly with k (level 0 is the bottom)");
     if (!m->gt_set) return no(GCM_ERR_STATE, "set the ground temperature first (gcm_set_ground)");
     return GCM_OK;
 }
+
+// gcm_set_band_boundary_layer: a band takes the phase over its own rows and three exchanges per step
+int pe25d_set_band_boundary_layer(Pe25d *m, bool on, std::string *err) {
+    if (m->wrap) {
+        if (!on) return GCM_OK;
+        *err = "gcm_set_band_boundary_layer: GCM_PE25D latitude bands only (a single domain takes gcm_set_boundary_layer directly)";
+        return GCM_ERR_UNSUPPORTED;
+    }
+    if (!on && m->boundary.sums.acc) {
+        *err = "gcm_set_band_boundary_layer: the boundary layer is registered (gcm_set_boundary_layer(NULL) first)";
+        return GCM_ERR_STATE;
+    }
+    m->boundary.band = on;
+    return GCM_OK;
+}
+bool pe25d_band_boundary_layer(const Pe25d *m) { return !m->wrap && m->boundary.band; }
 
 // the scratch fields: in place (on; allocated by the first call), or freed
 int pe25d_boundary_layer_scratch(Pe25d *m, bool on, hipStream_t s, std::string *err) {
@@ -360,19 +401,19 @@ int pe25d_boundary_layer_tables(Pe25d *m, const gcm_boundary_layer *bl, double d
     return GCM_OK;
 }
 
-template <typename T>
+template <typename T, bool BAND>
 static int bl_launch(Pe25d *m, int set, bool accumulate, hipStream_t s, std::string *err) {
     PeBufs<T> &B = bufs<T>(m);
     const PeBoundary &z = m->boundary;
-    const size_t cells = (size_t)m->H * m->W;
+    const size_t cells = (size_t)m->H * m->W, centres = bl_centre_rows(m) * m->W;
     BlArgsT<T> a{};
     a.p = B.st[set][GCM_P]; a.u = B.st[set][GCM_U]; a.v = B.st[set][GCM_V]; a.t = B.st[set][GCM_T]; a.q = B.st[set][GCM_Q];
     a.gt = m->gt;
     a.sig = m->lev_tab; a.dsig = m->lev_tab + m->L;
     a.exner_tab = m->exner_tab;
-    a.cd = z.scratch; a.r = a.cd + cells; a.e = a.r + cells;
+    a.cd = z.scratch; a.r = a.cd + centres; a.e = a.r + centres;
     const bool lds = m->L <= kBlLdsLevels;
-    a.park = lds ? nullptr : a.e + cells * (size_t)(m->L - 1);
+    a.park = lds ? nullptr : a.e + centres * (size_t)(m->L - 1);
     a.shf = accumulate ? z.sums.acc : nullptr;
     a.evap = accumulate ? z.sums.acc + cells : nullptr;
     a.par = bl_par(&z.par);
@@ -380,16 +421,19 @@ static int bl_launch(Pe25d *m, int set, bool accumulate, hipStream_t s, std::str
     a.W = m->W; a.H = m->H; a.L = m->L;
     const unsigned tiles = (unsigned)((m->W + kBlLanes - 1) / kBlLanes);
     const size_t word = sizeof(double) * (size_t)m->L * kBlLanes;
-    if (lds) hipLaunchKernelGGL((pe_bl_theta_q_kernel<T, true>), dim3(tiles, m->H), dim3(kBlLanes), 3 * word, s, a);
-    else hipLaunchKernelGGL((pe_bl_theta_q_kernel<T, false>), dim3(tiles, m->H), dim3(kBlLanes), 0, s, a);
+    const unsigned rows1 = (unsigned)bl_centre_rows(m);
+    if (lds) hipLaunchKernelGGL((pe_bl_theta_q_kernel<T, true, BAND>), dim3(tiles, rows1), dim3(kBlLanes), 3 * word, s, a);
+    else hipLaunchKernelGGL((pe_bl_theta_q_kernel<T, false, BAND>), dim3(tiles, rows1), dim3(kBlLanes), 0, s, a);
     if (hipGetLastError() != hipSuccess) { *err = "hip: boundary layer theta / q kernel launch failed"; return GCM_ERR_HIP; }
-    if (lds) hipLaunchKernelGGL((pe_bl_wind_kernel<T, true>), dim3(tiles, m->H, 2), dim3(kBlLanes), 2 * word, s, a);
-    else hipLaunchKernelGGL((pe_bl_wind_kernel<T, false>), dim3(tiles, m->H, 2), dim3(kBlLanes), 0, s, a);
+    if (lds) hipLaunchKernelGGL((pe_bl_wind_kernel<T, true, BAND>), dim3(tiles, m->H, 2), dim3(kBlLanes), 2 * word, s, a);
+    else hipLaunchKernelGGL((pe_bl_wind_kernel<T, false, BAND>), dim3(tiles, m->H, 2), dim3(kBlLanes), 0, s, a);
     if (hipGetLastError() != hipSuccess) { *err = "hip: boundary layer wind kernel launch failed"; return GCM_ERR_HIP; }
     return GCM_OK;
 }
 
-// every row of state set `set` (-1: the current one) of a single domain on `s`, pe25d_boundary_layer_tables in place.
+// every row of state set `set` (-1: the current one) of a single domain, or the own rows of a band that has opted in
+// (its ghost rows -1 and H must be current, and those of u, v, theta and q are stale behind the call until the edge rows
+// are exchanged again), on `s`, pe25d_boundary_layer_tables in place.
 // accumulate: the heat and the water the surface gave go to the registered sums, and the call counts as one application
 int pe25d_boundary_layer_rows(Pe25d *m, int set, bool keep_ghosts, bool accumulate, hipStream_t s, std::string *err) {
     PeBoundary &z = m->boundary;
@@ -397,7 +441,9 @@ int pe25d_boundary_layer_rows(Pe25d *m, int set, bool keep_ghosts, bool accumula
     if (accumulate && !z.sums.acc) { *err = "boundary layer: no sums to accumulate into (gcm_set_boundary_layer)"; return GCM_ERR_STATE; }
     if (set < 0) set = m->cur_i;
     pe25d_phase_wrote(m, set, keep_ghosts, true);          // the launches write u, v, theta and q
-    if (int rc = m->f32 ? bl_launch<float>(m, set, accumulate, s, err) : bl_launch<double>(m, set, accumulate, s, err)) return rc;
+    if (int rc = m->wrap ? (m->f32 ? bl_launch<float, false>(m, set, accumulate, s, err) : bl_launch<double, false>(m, set, accumulate, s, err))
+                         : (m->f32 ? bl_launch<float, true>(m, set, accumulate, s, err) : bl_launch<double, true>(m, set, accumulate, s, err)))
+        return rc;
     if (accumulate) sums_count(z.sums, z.dt);
     return GCM_OK;
 }

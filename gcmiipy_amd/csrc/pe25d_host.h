@@ -143,7 +143,8 @@ struct PeConvect {
 // (pe25d_boundary_layer_tables)
 struct PeBoundary {
     PeColumnSums sums;
-    double *scratch = nullptr;                  // device: cd [H][W], r [H][W], e [H][L-1][W]; L > 40: four park fields [H][L][W]
+    bool band = false;                          // gcm_set_band_boundary_layer: a band takes the phase over its own rows
+    double *scratch = nullptr;                  // device: cd [R][W], r [R][W], e [R][L-1][W], R = H (a band: H + 1); L > 40: four park fields [H][L][W]
     gcm_boundary_layer par{};
     double dt = 0.0;
 };

@@ -100,11 +100,14 @@ int pe25d_convect_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool
                        std::string *err);
 // Surface fluxes and boundary-layer mixing (pe25d_boundary_layer.hip).  boundary_layer_check / _surface / _column: no
 // handle, no device (gcm_boundary_layer_surface, gcm_boundary_layer_column).  pe25d_boundary_layer_fits: what a
-// registration or a step needs of the handle -- a single domain, L >= 2, sig decreasing in k (GCM_ERR_UNSUPPORTED), a
-// ground temperature (GCM_ERR_STATE); pe25d_boundary_layer_scratch: the float64 scratch fields in place or freed;
+// registration or a step needs of the handle -- a single domain or a band that has opted in
+// (pe25d_set_band_boundary_layer: gcm_set_band_boundary_layer; GCM_ERR_STATE for on = false while the phase is
+// registered), L >= 2, sig decreasing in k (GCM_ERR_UNSUPPORTED), a ground temperature (GCM_ERR_STATE);
+// pe25d_boundary_layer_scratch: the float64 scratch fields in place or freed;
 // pe25d_boundary_layer_tables: the checks above, the level tables and the scratch in place and (bl, dt) as the
 // parameters of the launches that follow; pe25d_boundary_layer_rows: the two launches over every row of state set `set`
-// (-1: the current one) on `s`; accumulate: the surface's heat and water go to the registered sums and the call counts
+// (-1: the current one) of a single domain, over the own rows of a band (ghost rows -1 and H current), on `s`;
+// accumulate: the surface's heat and water go to the registered sums and the call counts
 // as one application of dt
 int boundary_layer_check(const gcm_boundary_layer *bl, const char *fn, std::string *err);
 int boundary_layer_surface(int n, const gcm_boundary_layer *bl, double ptop, double sig0, const double *uc, const double *vc,
@@ -112,6 +115,8 @@ int boundary_layer_surface(int n, const gcm_boundary_layer *bl, double ptop, dou
                            std::string *err);
 int boundary_layer_column(int ncol, int L, const double *dsig, const double *a, const double *x, const double *target,
                           const double *X, double *X_out, double *X0_surface, std::string *err);
+int pe25d_set_band_boundary_layer(Pe25d *m, bool on, std::string *err);
+bool pe25d_band_boundary_layer(const Pe25d *m);
 int pe25d_boundary_layer_fits(Pe25d *m, const char *fn, std::string *err);
 int pe25d_boundary_layer_scratch(Pe25d *m, bool on, hipStream_t s, std::string *err);
 int pe25d_boundary_layer_tables(Pe25d *m, const gcm_boundary_layer *bl, double dt, hipStream_t s, std::string *err);

@@ -662,14 +662,44 @@ int gcm_convect_columns(int ncol, int L, const double *y, const double *w, const
  * supersaturated) and the climatology's sample.  gcm_half_step and gcm_step_phase never apply it.  Registration allocates
  * the accumulators and the scratch fields; NULL switches the phase off and frees them; registering again resets the
  * accumulators.  Without a registration nothing is launched and every result and timing is as before.
- * Latitude bands (nranks > 1) are refused: the centre quantities of ghost row -2 need v of row -3, and v of ghost row
- * H + 1 needs the centre quantities of row H + 2; neither exists, so the ghost rows cannot be advanced locally to the
- * neighbour's bits, which is how every other phase avoids a third exchange.  gcm_band_run never meets the phase.
+ * Latitude bands (nranks > 1): the centre quantities of ghost row -2 need v of row -3, and v of ghost row H + 1 needs
+ * the centre quantities of row H + 2; neither exists, so the ghost rows cannot be advanced locally to the neighbour's
+ * bits, which is how every other phase avoids a third exchange.  A band is therefore refused by default, and takes the
+ * phase after gcm_set_band_boundary_layer(h, 1), right after gcm_create and on every band of a run.  The launches then
+ * take the band's OWN rows: the first runs over rows [0, H] and forms cd, r and e only on ghost row H (no solve, no
+ * store to theta or q, no sum), the second over rows [0, H); j is not periodic, rows j - 1 and j + 1 are the
+ * neighbouring rows of the band (scratch: cd, r and e hold H + 1 rows).  They read v of ghost row -1 and every field of
+ * ghost row H, which must be current: the post-corrector exchange unpacked, the solar step and the Held-Suarez forcing
+ * applied to them.  The ghost rows are not advanced: the edge rows of the current state are exchanged a THIRD time
+ * behind the phase, in the message of every other exchange (gcm_halo_pack2 / gcm_halo_unpack2 with no phase pending,
+ * the same buffers, gcm_halo_bytes unchanged), which overwrites the ghost rows of u, v, theta and q with the
+ * neighbour's own bits.  The convective adjustment and the moist physics then take own rows and ghost rows locally, as
+ * ever.  Own rows see the same inputs and the same arithmetic in the same order as the single domain's: the same bits;
+ * shf and evap take rows [0, H).  A step of such a band, by gcm_band_run or by the host:
+ *   1. the Matsuno step with its two exchanges;
+ *   2. solar step and Held-Suarez forcing on own rows and ghost rows;        | gcm_end_step_begin
+ *   3. the boundary layer on the own rows;                                   |
+ *   4. the third exchange: pack / send and receive / unpack of the current state;
+ *   5. convective adjustment and moist physics on own rows and ghost rows;   | gcm_end_step_finish
+ *   6. the climatology's sample, which reads v of ghost row -1.              |
+ * gcm_band_run queues all six (the exchange and the ghost rows' launches beside the own rows' convective adjustment
+ * and moist physics on its second stream).  A host that drives the exchange itself calls gcm_end_step_begin, moves the
+ * ghost rows, then gcm_end_step_finish; gcm_end_step on such a band is GCM_ERR_STATE and changes nothing.  The third
+ * exchange costs one more message of gcm_halo_bytes per neighbour and step.
+ * gcm_set_band_boundary_layer(h, on): GCM_PE25D latitude bands only -- other models, and a single domain with on != 0,
+ * GCM_ERR_UNSUPPORTED (a single domain with on = 0: GCM_OK, nothing to do); on = 0 while the phase is registered
+ * GCM_ERR_STATE (unregister first); a null handle GCM_ERR_ARG.  A refused call changes nothing.  The opt-in by itself
+ * launches nothing and changes no result or timing.  gcm_band_boundary_layer: 1 on a band that has opted in, else 0 (a
+ * null handle GCM_ERR_ARG).
  * gcm_boundary_layer_on: 1 where the phase is registered, else 0 (other models: 0; a null handle GCM_ERR_ARG).
  * gcm_boundary_layer_step: the same launches once, in place on the current state.  With a registration it adds to the
  * accumulators, to seconds and to nsteps; without one the sums of the call are dropped, and the call allocates the scratch
  * fields itself ((L + 1) H W float64 words; four more fields of L H W above 40 levels), which the handle then keeps for the
- * next such call until gcm_set_boundary_layer(h, NULL) or gcm_destroy frees them.
+ * next such call until gcm_set_boundary_layer(h, NULL) or gcm_destroy frees them.  On a band that has opted in the call
+ * applies the phase to the own rows; like the other explicit calls it requires current ghost rows, and it leaves the
+ * ghost rows of u, v, theta and q STALE until the caller's next exchange of the current state (gcm_halo_pack2, the
+ * transfer, gcm_halo_unpack2): exchange before anything reads them -- the next stage, gcm_convect_step, gcm_moist_step,
+ * gcm_climate_sample.
  * gcm_get_boundary_layer synchronises the handle's stream once; any pointer may be NULL.  gcm_put_boundary_layer uploads
  * sums and counters (restarts): both arrays are required, seconds finite and >= 0, nsteps >= 0.
  * gcm_boundary_layer_reset zeroes all four.
@@ -680,7 +710,8 @@ int gcm_convect_columns(int ncol, int L, const double *y, const double *w, const
  * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, no parameters, a
  * non-finite parameter, cd0, cd1, ch or ce < 0, v_cap <= 0, p_strat <= 0, a non-finite dt; the probes: n or ncol < 0,
  * L < 2, a missing array.  GCM_ERR_UNSUPPORTED: other models, L < 2, a sig table that is not strictly decreasing in k
- * (level 0 must be the bottom), a handle created with nranks > 1.  GCM_ERR_STATE: no ground temperature set
+ * (level 0 must be the bottom), a handle created with nranks > 1 that has not opted in
+ * (gcm_set_band_boundary_layer).  GCM_ERR_STATE: no ground temperature set
  * (gcm_set_ground) -- reported by gcm_set_boundary_layer itself, not by the next step -- and get, put or reset without a
  * registration.                                                                                                     */
 typedef struct {
@@ -691,6 +722,8 @@ typedef struct {
     double p_strat;              /* Pa: e-folding scale of the decay above it (10000)              */
 } gcm_boundary_layer;
 int gcm_set_boundary_layer(gcm_handle *h, const gcm_boundary_layer *bl);
+int gcm_set_band_boundary_layer(gcm_handle *h, int on);
+int gcm_band_boundary_layer(const gcm_handle *h);
 int gcm_boundary_layer_on(const gcm_handle *h);
 int gcm_boundary_layer_step(gcm_handle *h, double dt, const gcm_boundary_layer *bl);
 int gcm_get_boundary_layer(gcm_handle *h, double *shf, double *evap, double *seconds, int64_t *nsteps);
@@ -745,7 +778,7 @@ int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples);
 int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples);
 /* The end of a GCM_PE25D step whose dynamics the caller took itself: everything gcm_step and gcm_band_run queue behind
  * the corrector, in their order and by their code -- the solar step at the handle's clock, utc += dt, the Held-Suarez
- * forcing, the boundary layer (single domains), the convective adjustment, the moist physics (their sums, seconds and
+ * forcing, the boundary layer, the convective adjustment, the moist physics (their sums, seconds and
  * nsteps advance as in gcm_step), the
  * climatology's step counter and its sample where one is due -- each only if registered, on the handle's stream.  With
  * nothing registered it queues nothing.  On a single domain gcm_half_step(h, 0, dt), gcm_half_step(h, 1, dt),
@@ -754,8 +787,18 @@ int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t n
  * rows, as the explicit gcm_solar_step, gcm_held_suarez_step, gcm_convect_step and gcm_moist_step do, so the ghost rows
  * of the current state, and of the ground temperature, must be current (the post-corrector exchange unpacked).
  * gcm_step and gcm_band_run end their steps themselves: do not call it behind them.
+ * gcm_end_step_begin and gcm_end_step_finish are its two parts, split behind the boundary layer.  begin: the tables for
+ * dt, the solar step (the clock advances once), the Held-Suarez forcing over own rows and ghost rows, the boundary layer
+ * (a band: over its own rows).  finish: the convective adjustment and the moist physics over own rows and ghost rows,
+ * the climatology's step counter and sample.  On every handle begin followed by finish, with the same dt, is
+ * gcm_end_step.  A band with the boundary layer registered (gcm_set_band_boundary_layer) moves the ghost rows of the
+ * current state between the two -- gcm_halo_pack2, the transfer, gcm_halo_unpack2 -- and gcm_end_step itself refuses such
+ * a band (GCM_ERR_STATE, the message names the two calls); on a single domain, or a band without the phase, nothing
+ * needs to happen between them.
  * Errors: a null handle GCM_ERR_ARG; other models GCM_ERR_UNSUPPORTED; a non-finite dt GCM_ERR_ARG, and nothing changes. */
 int gcm_end_step(gcm_handle *h, double dt);
+int gcm_end_step_begin(gcm_handle *h, double dt);
+int gcm_end_step_finish(gcm_handle *h, double dt);
 
 /* Device-side snapshot / restore of the current state, ghost rows included (2-D models): a long
  * run can restart from a known state without a host round trip.  gcm_restore is asynchronous on
