@@ -21,6 +21,8 @@ MAX_TRACERS = 16                     # GCM_MAX_TRACERS
 TRACER_STATS_WORDS = 6               # GCM_TRACER_STATS_WORDS
 CLIM_WORDS3, CLIM_WORDS2 = 10, 2     # GCM_CLIM_WORDS3, GCM_CLIM_WORDS2
 SW2D_PLAN_WORDS = 9                  # GCM_SW2D_PLAN_WORDS
+PHASE_HELD_SUAREZ, PHASE_MOIST, PHASE_CLIMATE, PHASE_TRACER_FORCING = range(4)   # gcm_pe25d_phase
+PHASE_PLAN_WORDS = 5                 # GCM_PHASE_PLAN_WORDS
 ADV_UPWIND, ADV_FV_UPWIND, ADV_FV_PLAIN, ADV_VANLEER, ADV_MOMENTUM = range(5)
 DIAG_ANY_NAN, DIAG_MAX_U, DIAG_MEAN_P, DIAG_SUM_P, DIAG_MIN_U, DIAG_MAX_V, DIAG_MIN_V = range(7)
 DIAG_TV_P, DIAG_TV_U, DIAG_TV_V, DIAG_TV_T, DIAG_TV_Q = range(7, 12)
@@ -122,6 +124,8 @@ SYMBOLS = {
     "gcm_diag_members": (C.c_int, [_H, C.c_int, _dp, C.c_int]),
     "gcm_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_sw2d_plan": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "gcm_pe25d_phase_geometry": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int), C.c_int]),
+    "gcm_pe25d_phase_plan": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "gcm_half_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_end_step": (C.c_int, [_H, C.c_double]),
     "gcm_end_step_begin": (C.c_int, [_H, C.c_double]),

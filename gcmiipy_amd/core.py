@@ -115,6 +115,41 @@ DTYPES = {"f64": _lib.F64, "f32": _lib.F32}
 TRACER_SCHEMES = {"centred": _lib.TRACER_NONE, "upwind": _lib.TRACER_UPWIND, "van_leer": _lib.TRACER_VANLEER}
 
 
+PHASES = {"held_suarez": _lib.PHASE_HELD_SUAREZ, "moist": _lib.PHASE_MOIST, "climate": _lib.PHASE_CLIMATE,
+          "tracer_forcing": _lib.PHASE_TRACER_FORCING}
+
+
+def phase_id(phase):
+    """a GCM_PE25D phase as gcm_pe25d_phase_geometry takes it: a name of PHASES or a _lib.PHASE_* constant"""
+    if isinstance(phase, str) and phase in PHASES:
+        return PHASES[phase]
+    if not isinstance(phase, (str, bool)) and phase in PHASES.values():
+        return int(phase)
+    raise ValueError("phase must be one of %s or a PHASE_* constant, got %r" % (sorted(PHASES), phase))
+
+
+def _phase_dict(phase, out):
+    if phase in (_lib.PHASE_HELD_SUAREZ, _lib.PHASE_MOIST):
+        return dict(grid_x=out[0], grid_y=out[1], grid_z=out[2], levels_min=out[3], levels_max=out[4])
+    if phase == _lib.PHASE_CLIMATE:
+        return dict(grid_x=out[0], nseg=out[1], levels_min=out[2], levels_max=out[3], chunks=out[4])
+    return dict(groups=out[0], passes=out[1])
+
+
+def phase_geometry(phase, W, rows, L, cus, elem_bytes=8, accumulate=True):
+    """the launch geometry of a GCM_PE25D phase over `rows` rows of W columns and L levels on a chip of `cus` compute
+    units, from the helpers the launchers use themselves (gcm_pe25d_phase_geometry; no handle, no device):
+    held_suarez, moist -- grid_x (256-column blocks), grid_y (rows), grid_z (level segments), levels_min / levels_max
+    of a segment; climate -- grid_x (rows), nseg, levels_min / levels_max a workgroup walks, chunks (iterations of a
+    level's loop over 3 x 256 columns); tracer_forcing -- groups (workgroups per forced tracer), passes"""
+    out = (C.c_int * _lib.PHASE_PLAN_WORDS)()
+    rc = lib.gcm_pe25d_phase_geometry(phase_id(phase), int(W), int(rows), int(L), int(cus), int(elem_bytes),
+                                      int(bool(accumulate)), out, _lib.PHASE_PLAN_WORDS)
+    if rc != _lib.OK:
+        raise ValueError("phase_geometry: sizes must be 1 or more and elem_bytes 4 or 8")
+    return _phase_dict(phase_id(phase), out)
+
+
 def tracer_scheme_id(scheme):
     """a tracer scheme as the C ABI takes it: one of the _lib.TRACER_* constants or "centred", "upwind", "van_leer"
     (None: centred); ValueError otherwise, before any device use"""
@@ -720,6 +755,16 @@ class Core:
         return dict(variant={_lib.VARIANT_FUSED: "fused", _lib.VARIANT_STAGED: "staged"}[out[0]],
                     rows_per_band=out[1], cols=out[2], strip=out[3], strip2=out[4], two_step_launches=out[5],
                     single_step_launches=out[6], preload=bool(out[7]), stream=bool(out[8]))
+
+    def phase_plan(self, phase, rows=None, accumulate=True):
+        """the launch geometry of a GCM_PE25D phase over `rows` rows (None: the handle's own; the explicit phase calls
+        of a band launch its four ghost rows too), without launching anything (gcm_pe25d_phase_plan).  phase:
+        "held_suarez", "moist" (accumulate: the launch adds to the registered sums), "climate" or "tracer_forcing";
+        the dict is that of phase_geometry below, at the handle's own width, levels, element size and compute units"""
+        out = (C.c_int * _lib.PHASE_PLAN_WORDS)()
+        _check(lib.gcm_pe25d_phase_plan(self._h, phase_id(phase), -1 if rows is None else int(rows), int(bool(accumulate)),
+                                        out, _lib.PHASE_PLAN_WORDS), self._h)
+        return _phase_dict(phase_id(phase), out)
 
     def half_step(self, stage, dt):
         _check(lib.gcm_half_step(self._h, int(stage), float(dt)), self._h)

@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "gcm_handle.h"
+#include "pe25d_phase_geometry.h"
 
 using namespace gcm;
 
@@ -147,6 +148,19 @@ int pe_step(gcm_handle *h, int nsteps, double dt) {
 }
 
 extern "C" {
+
+// ------------------------------------------------------------------ the phases' launch geometry, without launching
+int gcm_pe25d_phase_geometry(int phase, int W, int rows, int L, int cus, int elem_bytes, int accumulate, int *out, int nout) {
+    return pe25d_phase_geometry(phase, W, rows, L, cus, elem_bytes, accumulate, out, nout);
+}
+
+int gcm_pe25d_phase_plan(gcm_handle *h, int phase, int rows, int accumulate, int *out, int nout) {
+    if (int rc = pe_only(h, "gcm_pe25d_phase_plan")) return rc;
+    if (rows == 0) return fail(h, GCM_ERR_ARG, "gcm_pe25d_phase_plan: rows must be 1 or more, or negative for the handle's own");
+    if (int rc = pe25d_phase_plan(h->pe, phase, rows, accumulate != 0, out, nout))
+        return fail(h, rc, "gcm_pe25d_phase_plan: an unknown phase, a null pointer or fewer than GCM_PHASE_PLAN_WORDS words");
+    return GCM_OK;
+}
 
 // ------------------------------------------------------------------ the end of a step whose dynamics the caller took itself
 // What gcm_band_run queues behind a corrector where the ghost rows ride with the own rows (GCM_BAND_COMM_STREAM=1): the

@@ -26,12 +26,12 @@
 #include "pe25d_host.h"
 
 #include "pe25d_climate.h"
+#include "pe25d_phase_geometry.h"
 
 namespace gcm {
 
-constexpr int kClThreads = 256;
+// (kClThreads, kClBatch -- 256-column chunks requested together, then added in order: pe25d_phase_geometry.h)
 constexpr int kClWaves = kClThreads / 64;
-constexpr int kClBatch = 3;          // 256-column chunks requested together, then added in order
 constexpr int kClRedDoubles = 2 * kClWaves * GCM_CLIM_WORDS3;   // two buffers of the waves' sums: one barrier per level
 
 size_t climate_lds_bytes(int W) { return sizeof(double) * ((size_t)kExnerTabDoubles + kClRedDoubles + (size_t)W); }
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kClThreads) void pe_climate_kernel(ClimateArgs a) {
 
 void launch_climate(ClimateArgs a, bool f32, int cus, hipStream_t s) {
     // the levels are split over the grid until some eight workgroups a CU are in flight; the sums do not depend on it
-    a.nseg = (int)std::min<long>(a.L, std::max<long>(1, (8L * cus + a.H - 1) / a.H));
+    a.nseg = phase_climate_nseg(a.H, a.L, cus);
     const dim3 grid((unsigned)a.H, (unsigned)a.nseg);
     const size_t lds = climate_lds_bytes(a.W);
     if (f32) hipLaunchKernelGGL(pe_climate_kernel<float>, grid, dim3(kClThreads), lds, s, a);

@@ -21,6 +21,7 @@
 // are wave-uniform.  No LDS but the 2 KB Exner table.
 #pragma clang fp contract(off)
 #include "pe25d_host.h"
+#include "pe25d_phase_geometry.h"
 
 namespace gcm {
 
@@ -81,9 +82,7 @@ int held_suarez_tables(int L, const double *sig, int nlat, const double *lat, co
 }
 
 // ---------------------------------------------------------------- the kernel
-constexpr int kHsThreads = 256;
-constexpr int kHsBatch = 4;          // levels requested together, then advanced in order
-
+// (kHsThreads, kHsBatch -- levels requested together, then advanced in order: pe25d_phase_geometry.h)
 template <typename T>
 struct HsArgsT {
     const T *p;                      // [j][i], interior row 0
@@ -220,10 +219,9 @@ static int hs_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, hipStr
     a.W = m->W; a.L = L; a.Hg = Hg; a.row0 = m->cfg.row0;
     a.j0 = j0; a.n0 = std::max(0, j1 - j0); a.jb0 = jb0; a.nrows = a.n0 + std::max(0, jb1 - jb0);
     // the levels are split over the grid where the rows alone do not fill the chip (a band's ghost rows, a small band)
-    const int xb = (m->W + kHsThreads - 1) / kHsThreads;
-    const long blocks = (long)xb * a.nrows;
-    a.nseg = (int)std::min<long>(L, std::max<long>(1, (2L * m->cus + blocks - 1) / blocks));
-    const dim3 grid(xb, a.nrows, a.nseg);
+    const PhaseColumnGrid g = phase_column_grid(m->W, a.nrows, L, m->cus, kHsThreads, true);
+    a.nseg = g.nseg;
+    const dim3 grid(g.xb, g.nrows, g.nseg);
     if (m->cfg.ptop == 0.0) hipLaunchKernelGGL((pe_held_suarez_kernel<T, true>), grid, dim3(kHsThreads), 0, s, a);
     else hipLaunchKernelGGL((pe_held_suarez_kernel<T, false>), grid, dim3(kHsThreads), 0, s, a);
     if (hipGetLastError() != hipSuccess) { *err = "hip: held_suarez kernel launch failed"; return GCM_ERR_HIP; }

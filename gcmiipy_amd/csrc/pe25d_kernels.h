@@ -124,6 +124,8 @@ int pe25d_boundary_layer_rows(Pe25d *m, int set, bool keep_ghosts, bool accumula
 int pe25d_new_state_set(const Pe25d *m);    // the set a corrector stage in flight writes (before the swap), else the current one
 int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err);
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan
+// gcm_pe25d_phase_plan: pe25d_phase_geometry.h's query at the handle's own W, L, element size and compute units
+int pe25d_phase_plan(const Pe25d *m, int phase, int rows, bool accumulate, int *out, int nout);
 void pe25d_tv_shape(const Pe25d *m, int field, long *n_outer, long *n_axis, long *n_inner, int *wrap);
 const void *pe25d_field(Pe25d *m, int field, long *n, int *f32);
 // passive tracers: c / the result [n][L][H][W] float64 (a band: its own rows); which 0 = current, 1 = star

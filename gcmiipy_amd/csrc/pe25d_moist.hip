@@ -21,6 +21,7 @@
 // accumulator word and launch, no atomics.  No LDS but the 2 KB Exner table.
 #pragma clang fp contract(off)
 #include "pe25d_host.h"
+#include "pe25d_phase_geometry.h"
 #include "pe25d_moist_sat.h"
 
 namespace gcm {
@@ -48,9 +49,7 @@ int moist_saturation_table(int n, const double *T, const double *p_lev, double *
 }
 
 // ---------------------------------------------------------------- the kernel
-constexpr int kMoThreads = 256;
-constexpr int kMoBatch = 4;          // levels requested together, then advanced in order
-
+// (kMoThreads, kMoBatch -- levels requested together, then advanced in order: pe25d_phase_geometry.h)
 template <typename T>
 struct MoArgsT {
     const T *p;                      // [j][i], interior row 0
@@ -162,10 +161,9 @@ static int mo_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool a
     // a launch that accumulates marches whole columns (the column's sum is one register sum in level order); one that
     // does not -- a band's ghost rows -- splits the levels over the grid where the rows alone do not fill the chip, as
     // hs_launch does: every cell's result is independent of the split
-    const int xb = (m->W + kMoThreads - 1) / kMoThreads;
-    const long blocks = (long)xb * a.nrows;
-    a.nseg = accumulate ? 1 : (int)std::min<long>(m->L, std::max<long>(1, (2L * m->cus + blocks - 1) / blocks));
-    const dim3 grid(xb, a.nrows, a.nseg);
+    const PhaseColumnGrid g = phase_column_grid(m->W, a.nrows, m->L, m->cus, kMoThreads, !accumulate);
+    a.nseg = g.nseg;
+    const dim3 grid(g.xb, g.nrows, g.nseg);
     hipLaunchKernelGGL(pe_moist_kernel<T>, grid, dim3(kMoThreads), 0, s, a);
     if (hipGetLastError() != hipSuccess) { *err = "hip: moist kernel launch failed"; return GCM_ERR_HIP; }
     return GCM_OK;

@@ -4,6 +4,7 @@
 // share (their column sums, the level table, what a launch of theirs invalidates).  The stage that runs on all this:
 // pe25d_kernels.hip; the handle itself: pe25d_host.h.
 #include "pe25d_host.h"
+#include "pe25d_phase_geometry.h"
 
 namespace gcm {
 
@@ -601,6 +602,11 @@ int pe25d_halo_segments(Pe25d *m, bool pack, int side, void *dev_buf, SegCopy *c
     halo_segment(c, pack, side, m->gt, m->H, kGhost, (size_t)m->W, &msg);
     tracer_halo_segments(m, pack, side, set, &msg, c);
     return GCM_OK;
+}
+
+// ---------------------------------------------------------------- the phases' launch geometry (gcm_pe25d_phase_plan)
+int pe25d_phase_plan(const Pe25d *m, int phase, int rows, bool accumulate, int *out, int nout) {
+    return pe25d_phase_geometry(phase, m->W, rows < 0 ? m->H : rows, m->L, m->cus, (int)elem_size(m), accumulate, out, nout);
 }
 
 }  // namespace gcm

@@ -18,12 +18,11 @@
 #include <cstdint>
 
 #include "pe25d_tracer_force.h"
+#include "pe25d_phase_geometry.h"
 
 namespace gcm {
 
-constexpr int kTfThreads = 256;
-// the most workgroups per entry: 8 per CU; a 1440 x 720 x 24 field in fp64 is then 12 passes of 16 MiB
-constexpr int kTfGroupsMax = 2048;
+// (kTfThreads, kTfGroupsMax -- the most workgroups per entry: pe25d_phase_geometry.h)
 
 template <typename T>
 __device__ inline T tf_cell(T c, T e, bool pinned, T source, T dt, T fac, T pin) {
@@ -118,10 +117,9 @@ __global__ __launch_bounds__(kTfThreads) void pe_tracer_force_kernel(TracerForce
 
 template <typename T>
 void launch_tracer_force(const TracerForceArgsT<T> &a, int entries, hipStream_t s) {
-    constexpr long V = 16 / (long)sizeof(T);
     const long n = std::max(a.n0, a.n1);
     if (entries <= 0 || n <= 0) return;
-    const long groups = std::min<long>(kTfGroupsMax, std::max<long>(1, (n / V + kTfThreads - 1) / kTfThreads));
+    const long groups = phase_tracer_force_groups(n, (int)sizeof(T));
     hipLaunchKernelGGL(pe_tracer_force_kernel<T>, dim3((unsigned)groups, (unsigned)entries), dim3(kTfThreads), 0, s, a);
 }
 

@@ -178,6 +178,27 @@ int gcm_step(gcm_handle *h, int nsteps, double dt);
 #define GCM_SW2D_PLAN_WORDS 9
 int gcm_sw2d_plan(gcm_handle *h, int nsteps, int *out, int nout);
 
+/* The launch geometry of the GCM_PE25D phases whose grid depends on the rows of the launch, the row length and the
+ * chip's compute units, without launching anything: a read-only query for tests and tools, taken from the helpers the
+ * launchers use themselves.  gcm_pe25d_phase_geometry needs no handle and no device: a launch over `rows` rows of W
+ * columns and L levels on a chip of `cus` compute units, elem_bytes 8 (fp64) or 4 (fp32).  accumulate: GCM_PHASE_MOIST
+ * only -- 1: the launch adds to the registered sums (own rows) and marches whole columns; 0: it does not (a band's ghost
+ * rows, an unregistered gcm_moist_step) and splits the levels.  out (nout >= GCM_PHASE_PLAN_WORDS words, unused ones 0):
+ *   GCM_PHASE_HELD_SUAREZ, GCM_PHASE_MOIST: [0] grid x (256-column blocks)  [1] grid y (rows)  [2] grid z = level
+ *     segments nseg; segment s marches levels [s L / nseg, (s + 1) L / nseg), four at a time
+ *     [3] the fewest, [4] the most levels of a segment
+ *   GCM_PHASE_CLIMATE (rows = the handle's own rows H): [0] grid x = rows  [1] level segments nseg (grid y)
+ *     [2] the fewest, [3] the most levels a workgroup walks  [4] iterations of a level's loop over 3 x 256 columns
+ *   GCM_PHASE_TRACER_FORCING (one run of rows x L x W elements that starts on 16 bytes): [0] workgroups per forced
+ *     tracer  [1] passes of the whole 16-byte vectors over that grid
+ * gcm_pe25d_phase_plan is the same for a GCM_PE25D handle's own W, L, element size and compute units; rows < 0: the
+ * handle's own rows H (the explicit phase calls of a band launch H + 4: its ghost rows too).  An unknown phase, a size
+ * < 1, a null pointer, nout too small: GCM_ERR_ARG; a handle of another model: GCM_ERR_UNSUPPORTED.                     */
+typedef enum { GCM_PHASE_HELD_SUAREZ = 0, GCM_PHASE_MOIST = 1, GCM_PHASE_CLIMATE = 2, GCM_PHASE_TRACER_FORCING = 3 } gcm_pe25d_phase;
+#define GCM_PHASE_PLAN_WORDS 5
+int gcm_pe25d_phase_geometry(int phase, int W, int rows, int L, int cus, int elem_bytes, int accumulate, int *out, int nout);
+int gcm_pe25d_phase_plan(gcm_handle *h, int phase, int rows, int accumulate, int *out, int nout);
+
 /* One Euler stage, for per-stage parity tests and for the reference's
  * boundary_conditions hook (dynamics.py:232-236): stage == 0 computes the
  * predictor from the current state into the handle's "star" buffers; stage == 1

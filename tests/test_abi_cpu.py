@@ -30,6 +30,22 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in _lib.lib.gcm_build_info()
 
 
+def test_phase_plan_constants_match_header():
+    """gcm_pe25d_phase_geometry / gcm_pe25d_phase_plan: the phase numbers and the word count of the ctypes binding are
+    the header's, and the handle-free call answers without a device"""
+    from gcmiipy_amd import _lib
+    src = open(os.path.join(ROOT, "include", "gcmcore.h")).read()
+    enum = re.search(r"typedef enum \{([^}]*)\} gcm_pe25d_phase;", src).group(1)
+    values = {k: int(v) for k, v in re.findall(r"GCM_(PHASE_[A-Z_]+) = (\d+)", enum)}
+    assert values == {k: getattr(_lib, k) for k in ("PHASE_HELD_SUAREZ", "PHASE_MOIST", "PHASE_CLIMATE", "PHASE_TRACER_FORCING")}
+    assert int(re.search(r"#define GCM_PHASE_PLAN_WORDS (\d+)", src).group(1)) == _lib.PHASE_PLAN_WORDS
+    assert {"gcm_pe25d_phase_geometry", "gcm_pe25d_phase_plan"} <= set(_declared())
+    out = (ctypes.c_int * _lib.PHASE_PLAN_WORDS)()
+    assert _lib.lib.gcm_pe25d_phase_geometry(_lib.PHASE_CLIMATE, 1440, 720, 24, 256, 8, 1, out, _lib.PHASE_PLAN_WORDS) == _lib.OK
+    assert list(out) == [720, 3, 8, 8, 2]
+    assert _lib.lib.gcm_pe25d_phase_plan(None, _lib.PHASE_CLIMATE, -1, 1, out, _lib.PHASE_PLAN_WORDS) == _lib.ERR_ARG
+
+
 def test_config_struct_layout_matches_header():
     """field order/types of the ctypes mirror follow the header's gcm_config."""
     from gcmiipy_amd import _lib
