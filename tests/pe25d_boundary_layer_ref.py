@@ -1,7 +1,8 @@
 """NumPy restatement of the surface fluxes and the boundary-layer mixing of GCM_PE25D (include/gcmcore.h,
 gcm_set_boundary_layer): exactly the arithmetic the header states, float64, every operation rounded on its own, in the
 header's order -- and the inputs the tests of the phase share.  NumPy only: no torch, no library.  TEST INFRASTRUCTURE,
-no test in here; shared by tests/test_pe25d_boundary_layer_cpu.py and tests/test_pe25d_boundary_layer_gpu.py.
+no test in here; shared by tests/test_pe25d_boundary_layer_cpu.py, tests/test_pe25d_boundary_layer_gpu.py and
+tests/column_phase_cases.py.
 
     (A)  uc = 0.5 (u[0][j][i] + u[0][j][i-1]);  vc = 0.5 (v[0][j][i] + v[0][j-1][i]);  S = sqrt(uc uc + vc vc)
          p_s = p + ptop;  p_a = sig[0] p + ptop;  Pi_a = (p_a / P0)^kappa;  T_a = theta[0] Pi_a

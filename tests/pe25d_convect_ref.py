@@ -1,7 +1,7 @@
 """NumPy restatement of the convective adjustment of GCM_PE25D (include/gcmcore.h, gcm_set_convect): exactly the
 arithmetic the header states, float64, every operation rounded on its own, in the header's order -- and the unstable
 inputs the tests of the phase share.  NumPy only: no torch, no library.  TEST INFRASTRUCTURE, no test in here; shared by
-tests/test_pe25d_convect_cpu.py and tests/test_pe25d_convect_gpu.py.
+tests/test_pe25d_convect_cpu.py, tests/test_pe25d_convect_gpu.py and tests/column_phase_cases.py.
 
     p_lev = sig[k] p + ptop;  Pi = (p_lev / P0)^kappa;  r = 1 (kappa_c = 0), else exp((kappa_c - kappa) log(p_lev / P0))
     y = theta / r (kappa_c = 0: theta);  w = (Pi r) dsig[k]

@@ -1,7 +1,7 @@
 """NumPy restatement of the moist physics of GCM_PE25D (include/gcmcore.h, gcm_set_moist): exactly the arithmetic the
 header states, float64, every operation rounded on its own, in the header's order -- and the humid inputs the tests of
 the phase share.  NumPy only: no torch, no library.  TEST INFRASTRUCTURE, no test in here; shared by
-tests/test_pe25d_moist_cpu.py and tests/test_pe25d_moist_gpu.py.
+tests/test_pe25d_moist_cpu.py, tests/test_pe25d_moist_gpu.py and tests/column_phase_cases.py.
 
     p_lev = sig[k] p + ptop;  Pi = (p_lev / P0)^kappa;  T = theta Pi;  tc = T - 273.15
     a = 18.678 - tc / 234.5;  b = tc / (257.14 + tc);  e_s = (0.61121 * 1000.0) exp(a b)

@@ -7,12 +7,16 @@ under every orchestration, once at a size where the streams really overlap, the 
 refused calls and the checkpoint; and gcm_band_run once more on a band that is its own neighbour at mid-latitude rows,
 where the third exchange moves bits that reach the own rows, against the host-ended steps.  The bands are built here (Core(..., band_boundary_layer=True)); the exchange and the
 stepping patterns are gpu_setups'."""
+import functools
+
 import numpy as np
 import pytest
 
+import column_phase_cases as cc
 import gpu_setups as su
 import pe25d_boundary_layer_ref as ref
 import pe25d_inputs as inp
+from column_phase_cases import assert_same, assert_same_sums
 
 pytestmark = pytest.mark.gpu
 
@@ -74,26 +78,12 @@ def register_all(c, geom, solar=True, bl=True):
     c.set_climate(1)
 
 
-def final(c):
-    return c.get_state() + [c.get_ground()]
+final = functools.partial(cc.final, close=False)         # (every handle here has a ground temperature; the callers close)
 
 
 def merged(cores):
     parts = [final(c) for c in cores]
     return [np.concatenate([x[f] for x in parts], axis=1 if 0 < f < 5 else 0) for f in range(6)]
-
-
-def assert_same(got, want, what=""):
-    assert len(got) == len(want)
-    for k, a, b in zip("puvtqg", got, want):
-        assert np.array_equal(a, b), (what, k, float(np.max(np.abs(a - b))))
-
-
-def assert_same_sums(got, want, what=""):
-    """two records of one column phase: nsteps, seconds and both fields"""
-    assert type(got) is type(want) and (got.nsteps, got.seconds) == (want.nsteps, want.seconds), (what, got[:2], want[:2])
-    for f, a, b in zip(got._fields[2:], got[2:], want[2:]):
-        assert np.array_equal(a, b), (what, type(got).__name__, f, float(np.max(np.abs(a - b))))
 
 
 def clock(c):

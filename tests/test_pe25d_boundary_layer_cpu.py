@@ -2,7 +2,7 @@
 (gcm_boundary_layer_surface, gcm_boundary_layer_column -- the routines the kernels call, compiled for the host) against
 the NumPy restatement tests/pe25d_boundary_layer_ref.py, the properties of the restatement that the GPU test then
 checks on the device, the probes' refused calls and the checkpoint keys.  What needs a handle:
-tests/test_pe25d_boundary_layer_gpu.py.
+tests/test_pe25d_boundary_layer_gpu.py and tests/test_pe25d_column_phases_gpu.py.
 
 Bounds.  The column probe is + - x / with contraction off: bit for bit.  The surface probe goes through sqrt, log and
 the Exner routine (5.3e-16 against pow): 1e-12 relative.  The budgets are sums of L <= 42 terms of one sign, each

@@ -1,52 +1,27 @@
 """The surface fluxes and the boundary-layer mixing of GCM_PE25D on the device (gcm_set_boundary_layer,
 gcm_boundary_layer_step) against the NumPy restatement tests/pe25d_boundary_layer_ref.py, its budgets and its maximum
-principle on the device, the registered phase against the explicit calls and gcm_end_step, registration and sums,
-refused calls and the checkpoint.  The fields go through the device's Exner routine, sqrt, log and exp: 1e-10 relative
-to the field's maximum (the project's parity bound) in fp64, one rounding of float32 (2^-23) in fp32; the float64 sums
-1e-10 for either.  The budgets and the maximum principle take the bounds of tests/test_pe25d_boundary_layer_cpu.py."""
+principle on the device, the registered phase against the explicit calls and gcm_end_step, registration and sums, and
+the refusals that are its own.  What it shares with the other column phases -- the explicit step without a registration,
+the common refusals, the checkpoint -- is tests/test_pe25d_column_phases_gpu.py's.  The fields go through the device's
+Exner routine, sqrt, log and exp: 1e-10 relative to the field's maximum (the project's parity bound) in fp64, one
+rounding of float32 (2^-23) in fp32; the float64 sums 1e-10 for either.  The budgets and the maximum principle take the bounds of tests/test_pe25d_boundary_layer_cpu.py."""
 import copy
+import functools
 
 import numpy as np
 import pytest
 
+import column_phase_cases as cc
 import gpu_setups as su
 import pe25d_boundary_layer_ref as ref
 import pe25d_inputs as inp
+from column_phase_cases import DT, DTS, GAMMA, assert_same, assert_same_sums, final, linf
 
 pytestmark = pytest.mark.gpu
 
+PH = cc.BOUNDARY_LAYER
 SHAPES = ref.SHAPES
-DT = 600.0                                               # the explicit step's dt
-DTS = 120.0                                              # the dynamics' dt
-GAMMA = 6.5e-3
-
-
-def handle(g, geom, st, dtype="f64", **kw):
-    """a single-domain handle; the 300-column shape is never stepped and takes no filter plan"""
-    return su.single(g, geom, st, dtype=dtype, filter=geom.width != 300, **kw)
-
-
-def final(c, close=True):
-    out = c.get_state() + [c.get_ground()]
-    if close:
-        c.close()
-    return out
-
-
-def assert_same(got, want, what=""):
-    assert len(got) == len(want)
-    for k, a, b in zip("puvtqg", got, want):
-        assert np.array_equal(a, b), (what, k, float(np.max(np.abs(a - b))))
-
-
-def assert_same_sums(got, want, what=""):
-    assert (got.nsteps, got.seconds) == (want.nsteps, want.seconds), what
-    assert np.array_equal(got.shf, want.shf), (what, "shf", float(np.max(np.abs(got.shf - want.shf))))
-    assert np.array_equal(got.evap, want.evap), (what, "evap")
-
-
-def linf(a, b):
-    return float(np.max(np.abs(a - b)) / np.max(np.abs(b)))
+handle = functools.partial(cc.handle, PH)                # (the 300-column shape is never stepped and takes no filter plan)
 
 
 def case(shape, ptop, dtype="f64"):
@@ -101,19 +76,6 @@ def test_the_largest_lds_request_launches():
     print("boundary layer step, L = 40", errs)
     assert max(errs.values()) <= 1e-10, errs
     assert (got[1] != st[1]).any() and (got[3] != st[3]).any()
-
-
-def test_explicit_step_without_a_registration_keeps_no_sums():
-    import gcmiipy_amd as g
-    geom, st, gt = case(SHAPES[0], 0.0)
-    a, b = handle(g, geom, st, gt=gt), handle(g, geom, st, gt=gt)
-    a.boundary_layer_step(DT)
-    assert a.boundary_layer is None and not a.boundary_layer_registered
-    with pytest.raises(g.GcmError):
-        a.boundary_layer_sums()
-    b.set_boundary_layer()
-    b.boundary_layer_step(DT)
-    assert_same(final(a), final(b), "with and without sums")
 
 
 # ---------------------------------------------------------------- 2: properties on the device
@@ -255,13 +217,13 @@ def test_registration_sums_and_unregistration():
 
 # ---------------------------------------------------------------- 5: refused calls
 def test_refused_calls_change_nothing():
+    """the boundary layer's own refusals -- a null handle, no ground temperature, its parameters, a latitude band, one
+    level, reversed levels -- around the two halves of the refusals every phase shares"""
     import gcmiipy_amd as g
     lib, L_ = g._lib.lib, g._lib
-    geom, st, gt = case(SHAPES[1], 0.0)
-    H, W, L = SHAPES[1]
+    geom, st, gt = cc.refusal_inputs(PH)
+    H, W, L = PH.refusal["shape"]
     rec = L_.BoundaryLayer(*ref.DEFAULTS.values())
-    z = np.zeros((H, W))
-    dp = lambda a: a.ctypes.data_as(L_._dp)                                        # noqa: E731
     # a null handle
     assert lib.gcm_set_boundary_layer(None, rec) == L_.ERR_ARG and lib.gcm_boundary_layer_on(None) == L_.ERR_ARG
     assert lib.gcm_boundary_layer_step(None, 60.0, rec) == L_.ERR_ARG
@@ -270,14 +232,8 @@ def test_refused_calls_change_nothing():
     assert lib.gcm_set_boundary_layer(c._h, rec) == L_.ERR_STATE and lib.gcm_boundary_layer_on(c._h) == 0
     assert lib.gcm_boundary_layer_step(c._h, 60.0, rec) == L_.ERR_STATE
     assert_same(c.get_state(), st, "no ground")
-    # get, put, reset without a registration
     c.set_ground(gt)
-    assert lib.gcm_get_boundary_layer(c._h, None, None, None, None) == L_.ERR_STATE
-    assert lib.gcm_boundary_layer_reset(c._h) == L_.ERR_STATE
-    assert lib.gcm_put_boundary_layer(c._h, dp(z), dp(z), 0.0, 0) == L_.ERR_STATE
-    c.set_boundary_layer(cd0=1e-3)
-    c.boundary_layer_step(DT, cd0=1e-3)
-    was, was_state = c.boundary_layer_sums(), c.get_state()
+    was, was_state = cc.refused_without_a_registration(PH, g, c)
     nan, inf = float("nan"), float("inf")
     for over in (dict(cd0=-1e-3), dict(cd1=-1.0), dict(ch=-1.0), dict(ce=-1.0), dict(v_cap=0.0), dict(v_cap=-1.0),
                  dict(p_strat=0.0), dict(p_strat=-5.0), dict(cd0=nan), dict(cd1=inf), dict(v_cap=nan), dict(ch=inf),
@@ -292,15 +248,7 @@ def test_refused_calls_change_nothing():
     with pytest.raises(ValueError):
         c.set_boundary_layer(drag=3.0)
     assert lib.gcm_boundary_layer_step(c._h, DT, None) == L_.ERR_ARG
-    with pytest.raises(ValueError):
-        c.put_boundary_layer(-1, 0.0, was.shf, was.evap)
-    with pytest.raises(ValueError):
-        c.put_boundary_layer(1, nan, was.shf, was.evap)
-    assert lib.gcm_put_boundary_layer(c._h, None, None, 0.0, 0) == L_.ERR_ARG
-    assert c.boundary_layer == ref.params(cd0=1e-3) and lib.gcm_boundary_layer_on(c._h) == 1
-    assert_same(c.get_state(), was_state, "state after refused calls")
-    assert_same_sums(c.boundary_layer_sums(), was, "sums after refused calls")
-    c.close()
+    cc.refused_calls_changed_nothing(PH, g, c, was, was_state)
     # a latitude band
     band, other = su.bands(g, geom, 2, st, gt=gt)
     other.close()
@@ -326,50 +274,3 @@ def test_refused_calls_change_nothing():
     assert lib.gcm_set_boundary_layer(s._h, rec) == L_.ERR_UNSUPPORTED and lib.gcm_boundary_layer_on(s._h) == 0
     assert lib.gcm_boundary_layer_step(s._h, 60.0, rec) == L_.ERR_UNSUPPORTED
     s.close()
-    # other models
-    s = g.Core(g._lib.SW2D, 32, 16, dx=1e5)
-    assert lib.gcm_set_boundary_layer(s._h, rec) == L_.ERR_UNSUPPORTED
-    assert lib.gcm_boundary_layer_step(s._h, 60.0, rec) == L_.ERR_UNSUPPORTED
-    assert lib.gcm_get_boundary_layer(s._h, None, None, None, None) == L_.ERR_UNSUPPORTED
-    assert lib.gcm_boundary_layer_reset(s._h) == L_.ERR_UNSUPPORTED
-    assert lib.gcm_boundary_layer_on(s._h) == 0
-    s.close()
-
-
-# ---------------------------------------------------------------- 6: checkpoint
-@pytest.mark.parametrize("dtype", ["f64", "f32"])
-def test_checkpoint_carries_the_phase_and_its_sums(dtype, tmp_path):
-    import gcmiipy_amd as g
-    from gcmiipy_amd import checkpoint
-    geom, st, gt = case(SHAPES[0], 0.0, dtype)
-    par = dict(cd0=1e-3, p_pbl=80000.0)
-
-    def registered():
-        c = handle(g, geom, st, dtype, gt=gt)
-        c.set_boundary_layer(**par)
-        c.set_convect(gamma=GAMMA)
-        c.set_moist()
-        return c
-    whole = registered()
-    whole.step(4, DTS)
-    want, want_sums = final(whole, close=False), whole.boundary_layer_sums()
-    whole.close()
-    a = registered()
-    a.step(2, DTS)
-    path = str(tmp_path / "bl.npz")
-    checkpoint.save(path, a, step=2, geom=geom)
-    a.close()
-    b, ck = checkpoint.restore(path)
-    assert b.boundary_layer == ref.params(**par) and ck["boundary_layer"]["params"] == ref.params(**par)
-    assert ck["boundary_layer"]["n"] == 2 and b.convect is not None and b.moist is not None
-    b.step(2, DTS)
-    assert_same(final(b, close=False), want, "restored")
-    assert_same_sums(b.boundary_layer_sums(), want_sums, "restored")
-    b.close()
-    # a file without the keys restores with none
-    plain = handle(g, geom, st, dtype, gt=gt)
-    checkpoint.save(path, plain, geom=geom)
-    plain.close()
-    c, ck = checkpoint.restore(path)
-    assert ck["boundary_layer"] is None and c.boundary_layer is None
-    c.close()

@@ -2,7 +2,7 @@
 pooling probe gcm_convect_columns against the NumPy restatement (tests/pe25d_convect_ref.py) bit for bit, every
 validation error a call can report without a device, the restatement's own properties, the conditions the unstable
 inputs of the GPU tests must meet, merge_convect and the checkpoint keys.  What needs a handle:
-tests/test_pe25d_convect_gpu.py."""
+tests/test_pe25d_convect_gpu.py and tests/test_pe25d_column_phases_gpu.py."""
 import ctypes
 import os
 import re

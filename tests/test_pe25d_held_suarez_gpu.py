@@ -10,6 +10,7 @@ import pytest
 import gpu_setups as su
 import pe25d_held_suarez_ref as ref
 import pe25d_inputs as inp
+from column_phase_cases import assert_same, final
 
 pytestmark = pytest.mark.gpu
 
@@ -29,19 +30,6 @@ def geom_of(H, W, L, ptop=0.0):
 
 def sig_lat(geom):
     return np.asarray(geom.sig, dtype=np.float64).reshape(-1), np.asarray(geom.lat, dtype=np.float64).reshape(-1)
-
-
-def final(c, close=True):
-    out = c.get_state() + ([c.get_ground()] if c.has_ground else [])
-    if close:
-        c.close()
-    return out
-
-
-def assert_same(got, want, what=""):
-    assert len(got) == len(want)
-    for k, a, b in zip("puvtqg", got, want):
-        assert np.array_equal(a, b), (what, k, float(np.max(np.abs(a - b))))
 
 
 # ---------------------------------------------------------------- 1: the kernel against the restatement

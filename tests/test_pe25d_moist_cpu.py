@@ -2,7 +2,7 @@
 saturation probe gcm_moist_saturation against the NumPy restatement (tests/pe25d_moist_ref.py) and against humidity.py,
 every validation error a call can report without a device, the restatement's own properties, the conditions the humid
 inputs of the GPU tests must meet, merge_moist and the checkpoint keys.  What needs a handle:
-tests/test_pe25d_moist_gpu.py."""
+tests/test_pe25d_moist_gpu.py and tests/test_pe25d_column_phases_gpu.py."""
 import ctypes
 import os
 import re

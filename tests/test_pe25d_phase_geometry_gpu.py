@@ -206,7 +206,7 @@ def test_moist_level_split_equals_whole_columns(g, ptop, dtype):
     """bands of 4 rows without a registration: the explicit call launches own rows and ghost rows and accumulates
     nothing, so it splits the 42 levels into 8 segments; the single domain given the same columns splits them into 6
     without a registration and marches whole columns with one.  The criterion of
-    test_pe25d_moist_gpu.test_in_process_bands_equal_single_domain: the same bits; and theta and q against the
+    test_pe25d_column_phases_gpu.test_in_process_bands_equal_single_domain: the same bits; and theta and q against the
     restatement as in test_step_equals_the_restatement"""
     import torch
     H, W, L = pc.MOIST_SHAPE
