@@ -124,6 +124,7 @@ SYMBOLS = {
     "gcm_diag_members": (C.c_int, [_H, C.c_int, _dp, C.c_int]),
     "gcm_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_sw2d_plan": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "gcm_sw2d_fused_depth": (C.c_int, [_H]),
     "gcm_pe25d_phase_geometry": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int), C.c_int]),
     "gcm_pe25d_phase_plan": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "gcm_half_step": (C.c_int, [_H, C.c_int, C.c_double]),

@@ -745,6 +745,14 @@ class Core:
     def step(self, nsteps, dt):
         _check(lib.gcm_step(self._h, int(nsteps), float(dt)), self._h)
 
+    def sw2d_fused_depth(self):
+        """rows of requests a wave of the next step's fused launch keeps in flight (gcm_sw2d_fused_depth): 1, or 3 for
+        the deep march (float64 GCM_SW2D_TEMP on a streaming grid, or GCM_SW2D_DEPTH=3 when the handle was created);
+        0 for the staged variant"""
+        d = lib.gcm_sw2d_fused_depth(self._h)
+        _check(min(d, 0), self._h)
+        return d
+
     def sw2d_plan(self, nsteps):
         """what step(nsteps, .) of a 2-D handle would launch, without launching anything (gcm_sw2d_plan): a dict of
         variant ("fused" / "staged"), rows_per_band, cols (columns per lane), strip and strip2 (the strip width in

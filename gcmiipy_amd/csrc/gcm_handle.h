@@ -77,7 +77,8 @@ struct gcm_handle {
     bool f32 = false;       // 2-D models: float storage and arithmetic (gcm_config.dtype == GCM_F32)
     int esz = 8;            // bytes per element of the 2-D state
     int cols = 1;           // fused kernel: columns per lane (2: fp32 with an even width, 120-column strips)
-    double *staging = nullptr;   // fp32 handles: float64 staging buffer of state transfers, staging_members members
+    int depth_pin = 0;      // GCM_SW2D_DEPTH at gcm_create (float64 GCM_SW2D_TEMP only): 1 or 3 pins the fused form's depth, 0: none
+    double *staging = nullptr;  // fp32 handles: float64 staging buffer of state transfers, staging_members members
     int staging_members = 0;
 
     // diagnostics scratch

@@ -169,8 +169,10 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
             if (temp && !upload_exner_table(h)) return bail(GCM_ERR_HIP, "gcm_create: exner table upload failed");
             const int tr = h->has[GCM_Q] ? cfg->tracer : 0;
             if (h->f32) h->cols = sw2d_fused_cols<float>(h->W, h->H, temp, tr, h->wrap, h->M);   // 
+            if (const char *e = getenv("GCM_SW2D_DEPTH"))   // (sw2d_fused_form; every other handle ignores it)
+                if (temp && !h->f32 && (e[0] == '1' || e[0] == '3') && !e[1]) h->depth_pin = e[0] - '0';
             h->rows_per_band = h->f32 ? sw2d_fused_rows_per_band<float>(h->W, h->H, temp, tr, h->wrap, h->M, h->cols)
-                                      : sw2d_fused_rows_per_band<double>(h->W, h->H, temp, tr, h->wrap, h->M);
+                                      : sw2d_fused_rows_per_band<double>(h->W, h->H, temp, tr, h->wrap, h->M, 1, h->depth_pin);
             break;
         }
         case GCM_PE2D: {
@@ -348,7 +350,7 @@ static void run_tracer_axis(const gcm_handle *h, const Sw2dArgs &a, int axis, bo
     else launch_tracer_axis(a, axis, limit, q_in, q_out, s);
 }
 static bool run_fused(const gcm_handle *h, const Sw2dArgs &a, bool temp, int tracer, hipStream_t s) {
-    return h->f32 ? launch_sw2d_fused(narrow_args(a), temp, tracer, s, h->cols) : launch_sw2d_fused(a, temp, tracer, s);
+    return h->f32 ? launch_sw2d_fused(narrow_args(a), temp, tracer, s, h->cols) : launch_sw2d_fused(a, temp, tracer, s, 1, h->depth_pin);
 }
 static bool run_fused2(const gcm_handle *h, const Sw2dArgs &a, hipStream_t s) {
     return h->f32 ? launch_sw2d_fused2(narrow_args(a), s) : launch_sw2d_fused2(a, s);
@@ -514,9 +516,9 @@ int gcm_sw2d_plan(gcm_handle *h, int nsteps, int *out, int nout) {
     const bool temp = h->cfg.model == GCM_SW2D_TEMP;
     const int pairs = steps_in_pairs(h) ? nsteps / 2 : 0;
     const int e = step_extra_rows(h);
-    Sw2dFusedForm f{false, false};
+    Sw2dFusedForm f{false, false, 1};
     if (fused)
-        f = sw2d_fused_form(temp, h->has[GCM_Q] ? h->cfg.tracer : 0, h->rows_per_band, h->W, h->H + 2 * e, h->M, h->esz);
+        f = sw2d_fused_form(temp, h->has[GCM_Q] ? h->cfg.tracer : 0, h->rows_per_band, h->W, h->H + 2 * e, h->M, h->esz, h->depth_pin);
     out[0] = h->variant;
     out[1] = fused ? h->rows_per_band : 0;
     out[2] = fused ? h->cols : 0;
@@ -527,6 +529,16 @@ int gcm_sw2d_plan(gcm_handle *h, int nsteps, int *out, int nout) {
     out[7] = f.preload;
     out[8] = f.stream;
     return GCM_OK;
+}
+
+// rows of requests a wave of the next step's fused launch keeps in flight (sw2d_fused_form), from the expression the
+// launcher uses; 0: the staged variant
+int gcm_sw2d_fused_depth(gcm_handle *h) {
+    if (!h || h->pe) return GCM_ERR_ARG;
+    if (h->variant != GCM_VARIANT_FUSED) return 0;
+    const int e = step_extra_rows(h);
+    return sw2d_fused_form(h->cfg.model == GCM_SW2D_TEMP, h->has[GCM_Q] ? h->cfg.tracer : 0, h->rows_per_band, h->W,
+                           h->H + 2 * e, h->M, h->esz, h->depth_pin).depth;
 }
 
 int gcm_step_interior(gcm_handle *h, double dt, void *stream) {

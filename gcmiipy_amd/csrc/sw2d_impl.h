@@ -239,6 +239,25 @@ struct Raw {
     T u, v, p, t, q;
 };
 
+// The deep march's stores: one output row as a buffer of W doubles, a lane's byte offset into it, and the hardware's
+// range check in place of a branch around the store -- a lane that stores nothing (the halo lanes, columns >= W) passes
+// kNoStore, which is beyond any row (sw2d_fused_form keeps W * 8 below it), and its store is dropped.  A branch would
+// hide the stores from the compiler's count of what is in flight: it then waits for the newest requests as well.
+constexpr unsigned kNoStore = 0x80000000u;
+__device__ __forceinline__ void store_row_lanes(double *row, int W, unsigned lane_off, double x) {
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(row, 0, W * 8, 0x00020000);   // (raw, 32-bit)
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, x), rs, (int)lane_off, 0, 0);
+}
+
+// a copy the register coalescer cannot see through (FusedCtx::iter, the deep march); "memory": the refill of the slot
+// that x came from stays behind it
+__device__ __forceinline__ double own_copy(double x) {
+    double y;
+    asm volatile("v_mov_b64 %0, %1" : "=v"(y) : "v"(x) : "memory");
+    return y;
+}
+
 // STREAM: the base state is read with nontemporal loads -- a grid far larger than the caches is read once
 // per step (plus halo columns / band-edge rows), and the streaming hint is worth 1.5-2 % there (A/B on C3,
 // two boxes); nontemporal STORES cost 2-8 % (a strip's 480-byte rows share their edge lines with the
@@ -288,7 +307,12 @@ struct FusedCtx {
     // r-2, r-1; SN is a dead slot that receives predicted row r.  On exit BM's slot holds
     // base row r+2 (from the prefetched `nxt`) and `nxt` is row r+3: the caller rotates the
     // slot names instead of moving registers.
-    template <bool FETCH = true>
+    // The deep march (sw2d_fused_kernel, DEPTH = 3) calls it with AHEAD = 5: `nxt` is then the one of three request
+    // slots that holds row r+2, and it is refilled with row min(r+5, jb+1), unconditionally, so that no branch stands
+    // around a load.  LEAD names what the caller knows of r: 0 r == ja-1 (neither flux nor corrector), 1 r == ja
+    // (no corrector), 2 r > ja (both, unconditionally); -1: decided from r here.  ROWBUF: the deep march's stores
+    // (store_row_lanes).
+    template <bool FETCH = true, int AHEAD = 3, int LEAD = -1, bool ROWBUF = false>
     __device__ __forceinline__ void iter(int r, Row<V> &BM, Row<V> &B0, Row<V> &BP, Row<V> &SN, Row<V> &SM,
                                          Row<V> &S0, Raw<V> &nxt, V &qmm, V &qm, V &q0, V &qp) {
         const V dt = V(a.dt), g_dx = V(a.g_dx), h_dx = V(a.h_dx), mu_dx2 = V(a.mu_dx2), dtdx = V(a.dtdx);
@@ -307,9 +331,9 @@ struct FusedCtx {
         }
         // ---- tracer, axis-0 flux through the face between rows r-1 and r
         V f0_cur = V(0.0);
-        if (TRACER && r >= ja) f0_cur = face_flux<TRACER == 2>(BM.v, qmm, qm, q0, qp, dtdx);
+        if (TRACER && (LEAD < 0 ? r >= ja : LEAD >= 1)) f0_cur = face_flux<TRACER == 2>(BM.v, qmm, qm, q0, qp, dtdx);
         // ---- corrector: output row r-1 from predicted rows r-2, r-1, r and base row r-1
-        if (r >= ja + 1) {
+        if (LEAD < 0 ? r >= ja + 1 : LEAD >= 2) {
             const Tend<V> t = tendencies<TEMP>(SM, S0, SN, g_dx, h_dx, mu_dx2);
             const V un = BM.u - dt * t.du;
             const V vn = BM.v - dt * t.dv;
@@ -323,7 +347,15 @@ struct FusedCtx {
                 const V f1 = face_flux<TRACER == 2>(BM.u, qs_w, qs, qs_e, qs_ee, dtdx);
                 qn = qs - f1 + from_west(f1);
             }
-            if (store_lane) {
+            if constexpr (ROWBUF) {
+                const long o = (long)(r - 1) * a.W;
+                const unsigned lane_off = store_lane ? (unsigned)col * 8u : kNoStore;
+                store_row_lanes(a.ou + o, a.W, lane_off, un);
+                store_row_lanes(a.ov + o, a.W, lane_off, vn);
+                store_row_lanes(a.op + o, a.W, lane_off, pn);
+                if (TEMP) store_row_lanes(a.ot + o, a.W, lane_off, tn);
+                if (TRACER) store_row_lanes(a.oq + o, a.W, lane_off, qn);
+            } else if (store_lane) {
                 const long o = (long)(r - 1) * a.W + col;
                 if constexpr (CPL == 2) {
                     auto st = [o](T *p, V x) { *(V *)(p + o) = x; };
@@ -343,14 +375,26 @@ struct FusedCtx {
         }
         // ---- slide south: the oldest base slot takes row r+2, prefetch row r+3
         f0_prev = f0_cur;
-        make_row<TEMP>(BM, nxt.u, nxt.v, nxt.p, nxt.t, tab);
+        if constexpr (AHEAD == 3) {
+            make_row<TEMP>(BM, nxt.u, nxt.v, nxt.p, nxt.t, tab);
+        } else {
+            // The window takes copies, so that a slot's registers are dead here and the refill below lands in them
+            // again.  Left to itself the compiler lets the window row and the slot trade registers from trip to trip,
+            // and pays for it with moves of every slot in the loop's latch -- behind a wait for all that is in flight.
+            make_row<TEMP>(BM, own_copy(nxt.u), own_copy(nxt.v), own_copy(nxt.p), TEMP ? own_copy(nxt.t) : nxt.t, tab);
+        }
         if (TRACER) {
             qmm = qm;
             qm = q0;
             q0 = qp;
-            qp = nxt.q;
+            if constexpr (AHEAD == 3) qp = nxt.q;
+            else qp = own_copy(nxt.q);
         }
-        if (FETCH && r + 3 <= jb + 1) nxt = load(r + 3);   // !FETCH: the caller has the rows already
+        if constexpr (AHEAD == 3) {
+            if (FETCH && r + 3 <= jb + 1) nxt = load(r + 3);   // !FETCH: the caller has the rows already
+        } else {
+            nxt = load(min(r + AHEAD, jb + 1));
+        }
     }
 };
 
@@ -374,8 +418,12 @@ __device__ __forceinline__ void preloaded_iters(Ctx &c, const Raw<T> (&pre)[PRE 
 // only -- what the fp32 unit is built with, see the Makefile -- would otherwise take 170-172 VGPRs and a third of the
 // waves (4096x2048 fp32 van Leer: 1.09x the time; held to 168 with 12-20 B of scratch per lane: 1.035x).  No other
 // instantiation is touched: the fp64 unit's code is the same instruction for instruction.
-template <typename T, bool TEMP, int TRACER, bool WRAPJ, int PRE = 0, bool STREAM = false, int CPL = 1>
-__global__ __launch_bounds__(64, (CPL == 2 && TRACER != 0) ? 3 : 1) void sw2d_fused_kernel(Sw2dArgsT<T> a0) {
+// DEPTH: rows of requests a wave keeps in flight in the rolling march.  1: one row, asked for a row ahead of its use.
+// 3 (T = double, TEMP, CPL = 1; sw2d_fused_form picks it): three request slots, one per call site of the three-row
+// trip, each consumed three rows after it was asked for; that takes 162-176 VGPRs, so the kernel is held to two
+// waves per SIMD (256 VGPRs) instead of the three that DEPTH = 1 reaches (profiles/deep_prefetch/).
+template <typename T, bool TEMP, int TRACER, bool WRAPJ, int PRE = 0, bool STREAM = false, int CPL = 1, int DEPTH = 1>
+__global__ __launch_bounds__(64, DEPTH == 3 ? 2 : (CPL == 2 && TRACER != 0) ? 3 : 1) void sw2d_fused_kernel(Sw2dArgsT<T> a0) {
     using Ctx = FusedCtx<T, TEMP, TRACER, WRAPJ, STREAM, CPL>;
     using V = typename Ctx::Real;
     constexpr int kCols = sw2d_fused_strip_cols(CPL);   // output columns per wave
@@ -427,6 +475,35 @@ __global__ __launch_bounds__(64, (CPL == 2 && TRACER != 0) ? 3 : 1) void sw2d_fu
         Raw<V> nxt = pre[3];
         X = Y = Z = A;
         preloaded_iters<0, PRE>(c, pre, A, B, C, X, Y, Z, nxt, qmm, qm, q0, qp);
+        return;
+    }
+    if constexpr (DEPTH == 3) {
+        // Rows ja-2 .. ja make the window; rows ja+1 .. ja+3 fill the slots n0, n1, n2.  iter at row r consumes the
+        // slot that holds row r+2 and refills it with row r+5 (clamped to jb+1, the last row a band may touch: a band
+        // may be a single row).  The two rows ahead of the first output row are peeled, so that the loop's stores
+        // are unconditional (store_row_lanes), and so are the last one or two rows behind the whole trips: a loop
+        // with an exit behind each row is turned into one whose exits meet in the latch, where the slots in flight
+        // would be moved, and so waited for, every trip.
+        static_assert(PRE == 0 && CPL == 1, "the deep march is the rolling form with one column per lane");
+        const Raw<V> w0 = c.load(ja - 2), w1 = c.load(ja - 1), w2 = c.load(ja);
+        Raw<V> n0 = c.load(ja + 1), n1 = c.load(ja + 2), n2 = c.load(min(ja + 3, jb + 1));
+        make_row<TEMP>(A, w0.u, w0.v, w0.p, w0.t, tab);
+        make_row<TEMP>(B, w1.u, w1.v, w1.p, w1.t, tab);
+        make_row<TEMP>(C, w2.u, w2.v, w2.p, w2.t, tab);
+        V qmm = V(0.0), qm = w0.q, q0 = w1.q, qp = w2.q;
+        X = Y = Z = A;  // overwritten before first use
+        c.template iter<true, 5, 0, true>(ja - 1, A, B, C, X, Y, Z, n0, qmm, qm, q0, qp);
+        c.template iter<true, 5, 1, true>(ja, B, C, A, Y, Z, X, n1, qmm, qm, q0, qp);
+        int r = ja + 1;                   // rows ja+1 .. jb, three per trip
+        for (; r + 2 <= jb; r += 3) {
+            c.template iter<true, 5, 2, true>(r, C, A, B, Z, X, Y, n2, qmm, qm, q0, qp);
+            c.template iter<true, 5, 2, true>(r + 1, A, B, C, X, Y, Z, n0, qmm, qm, q0, qp);
+            c.template iter<true, 5, 2, true>(r + 2, B, C, A, Y, Z, X, n1, qmm, qm, q0, qp);
+        }
+        if (r <= jb) {                    // (the rows these would ask for are beyond jb+1)
+            c.template iter<false, 3, 2, true>(r, C, A, B, Z, X, Y, n2, qmm, qm, q0, qp);
+            if (r + 1 <= jb) c.template iter<false, 3, 2, true>(r + 1, A, B, C, X, Y, Z, n0, qmm, qm, q0, qp);
+        }
         return;
     }
     Raw<V> x = c.load(ja - 2);
@@ -595,7 +672,16 @@ bool launch_sw2d_fused2(const Sw2dArgsT<T> &a, hipStream_t s) {
 }
 
 template <typename T, bool TEMP, int TRACER, int CPL = 1>
-static const void *fused_fn(bool wrap, bool stream) {
+static const void *fused_fn(bool wrap, bool stream, int depth = 1) {
+    if constexpr (std::is_same_v<T, double> && TEMP && CPL == 1) {   // the deep march exists for these only
+        if (depth == 3) {
+            if (stream)
+                return wrap ? (const void *)sw2d_fused_kernel<T, TEMP, TRACER, true, 0, true, CPL, 3>
+                            : (const void *)sw2d_fused_kernel<T, TEMP, TRACER, false, 0, true, CPL, 3>;
+            return wrap ? (const void *)sw2d_fused_kernel<T, TEMP, TRACER, true, 0, false, CPL, 3>
+                        : (const void *)sw2d_fused_kernel<T, TEMP, TRACER, false, 0, false, CPL, 3>;
+        }
+    }
     if (stream)
         return wrap ? (const void *)sw2d_fused_kernel<T, TEMP, TRACER, true, 0, true, CPL>
                     : (const void *)sw2d_fused_kernel<T, TEMP, TRACER, false, 0, true, CPL>;
@@ -605,26 +691,26 @@ static const void *fused_fn(bool wrap, bool stream) {
 
 // (preload, stream: sw2d_fused_form; kPreloadRows: sw2d_kernels.h)
 template <typename T, int CPL>
-static const void *fused_kernel_ptr_c(bool temp, int tracer, bool wrap, bool preload, bool stream) {
+static const void *fused_kernel_ptr_c(bool temp, int tracer, bool wrap, bool preload, bool stream, int depth) {
     if (!temp) {
         if (preload)
             return wrap ? (const void *)sw2d_fused_kernel<T, false, 0, true, kPreloadRows, false, CPL>
                         : (const void *)sw2d_fused_kernel<T, false, 0, false, kPreloadRows, false, CPL>;
         return fused_fn<T, false, 0, CPL>(wrap, stream);
     }
-    if (tracer == 0) return fused_fn<T, true, 0, CPL>(wrap, stream);
-    if (tracer == 1) return fused_fn<T, true, 1, CPL>(wrap, stream);
-    return fused_fn<T, true, 2, CPL>(wrap, stream);
+    if (tracer == 0) return fused_fn<T, true, 0, CPL>(wrap, stream, depth);
+    if (tracer == 1) return fused_fn<T, true, 1, CPL>(wrap, stream, depth);
+    return fused_fn<T, true, 2, CPL>(wrap, stream, depth);
 }
 
 // stream: the rows this launch reads are far more than the caches hold (see FusedCtx); cols: columns per lane
-// (2: T = float and an even width only)
+// (2: T = float and an even width only); depth: rows of requests in flight (3: T = double with temp only)
 template <typename T>
 static const void *fused_kernel_ptr(bool temp, int tracer, bool wrap, bool preload = false, bool stream = false,
-                                    int cols = 1) {
+                                    int cols = 1, int depth = 1) {
     if constexpr (std::is_same_v<T, float>)
-        if (cols == 2) return fused_kernel_ptr_c<T, 2>(temp, tracer, wrap, preload, stream);
-    return fused_kernel_ptr_c<T, 1>(temp, tracer, wrap, preload, stream);
+        if (cols == 2) return fused_kernel_ptr_c<T, 2>(temp, tracer, wrap, preload, stream, 1);
+    return fused_kernel_ptr_c<T, 1>(temp, tracer, wrap, preload, stream, depth);
 }
 
 // Rows per wave.  Large grids: one resident round -- as many waves as the chip holds at
@@ -632,24 +718,38 @@ static const void *fused_kernel_ptr(bool temp, int tracer, bool wrap, bool prelo
 // at the tail); small grids: short bands so that every SIMD gets a wave.  An ensemble counts
 // the waves of all `members` grids: short bands exist only to fill the chip, and once M
 // members fill it the 4 halo rows of a short band are pure overhead.
+// The deep march (sw2d_fused_form: depth 3) holds fewer waves, and its occupancy is asked of the kernel that runs; it
+// takes as many resident rounds as keep a band within kDeepMaxRows rows (C3: one round, 69 strips x 29 bands of 71).
+constexpr int kDeepMaxRows = 96;
 template <typename T>
-int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap, int members, int cols) {
+int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap, int members, int cols, int depth_pin) {
     if (const char *e = getenv("GCM_FUSED_ROWS")) {
         int v = atoi(e);
         if (v > 0) return v;
     }
-    int waves_per_cu = 12, cus = 256, dev = 0;
+    const long M = members < 1 ? 1 : members;
+    // (the band length is not known yet: it matters to the form of plain shallow water only, which has no deep march)
+    const Sw2dFusedForm form = sw2d_fused_form(temp, tracer, kPreloadRows + 1, W, H, M, (long)sizeof(T), depth_pin);
+    const bool deep = form.depth == 3;
+    int waves_per_cu = deep ? 8 : 12, cus = 256, dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
         cus = prop.multiProcessorCount;
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fused_kernel_ptr<T>(temp, tracer, wrap, false, false, cols), 64,
-                                                     0) == hipSuccess && nb > 0)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fused_kernel_ptr<T>(temp, tracer, wrap, false, deep && form.stream, cols, form.depth),
+                                                     64, 0) == hipSuccess && nb > 0)
         waves_per_cu = nb;
     const long slots = (long)waves_per_cu * cus;
-    const long M = members < 1 ? 1 : members;
     const long strips = (W + sw2d_fused_strip_cols(cols) - 1) / sw2d_fused_strip_cols(cols);
     auto waves = [&](int rpb) { return M * strips * ((H + rpb - 1) / rpb); };
+    if (deep && waves(8) >= slots) {
+        for (long rounds = 1;; ++rounds) {
+            long bands = rounds * slots / (strips * M);   // per member; floor: stay within `rounds` full rounds
+            if (bands < 1) bands = 1;
+            const long rpb = (H + bands - 1) / bands;
+            if (rpb <= kDeepMaxRows || bands >= H) return (int)(rpb < 8 ? 8 : rpb);
+        }
+    }
     if (waves(8) < slots) {  // small grid: aim at one wave per SIMD at least
         long rpb = M * H * strips / (5L * cus);   // ~1.3 waves per SIMD (measured best on 720x360)
         // plain SW2D ensembles that do not fill the chip at 8 rows: bands short enough for two steps per launch
@@ -686,7 +786,7 @@ int sw2d_fused_cols(int W, int H, bool temp, int tracer, bool wrap, int members)
 }
 
 template <typename T>
-bool launch_sw2d_fused(const Sw2dArgsT<T> &a, bool temp, int tracer, hipStream_t s, int cols) {
+bool launch_sw2d_fused(const Sw2dArgsT<T> &a, bool temp, int tracer, hipStream_t s, int cols, int depth_pin) {
     if (a.j1 <= a.j0) return true;
     const int strips = (a.W + sw2d_fused_strip_cols(cols) - 1) / sw2d_fused_strip_cols(cols);
     const int bands = (a.j1 - a.j0 + a.rows_per_band - 1) / a.rows_per_band;
@@ -695,8 +795,8 @@ bool launch_sw2d_fused(const Sw2dArgsT<T> &a, bool temp, int tracer, hipStream_t
     void *params[] = {&arg};
     // fields x sizeof(T) bytes x the rows of this launch (all members), read once: stream it when that is beyond the
     // 256 MB Infinity Cache (sw2d_fused_form)
-    const Sw2dFusedForm f = sw2d_fused_form(temp, tracer, a.rows_per_band, a.W, a.j1 - a.j0, a.members, (long)sizeof(T));
-    return hipLaunchKernel(fused_kernel_ptr<T>(temp, tracer, a.wrap_j != 0, f.preload, f.stream, cols), g, dim3(64), params, 0, s) == hipSuccess;
+    const Sw2dFusedForm f = sw2d_fused_form(temp, tracer, a.rows_per_band, a.W, a.j1 - a.j0, a.members, (long)sizeof(T), depth_pin);
+    return hipLaunchKernel(fused_kernel_ptr<T>(temp, tracer, a.wrap_j != 0, f.preload, f.stream, cols, f.depth), g, dim3(64), params, 0, s) == hipSuccess;
 }
 
 template <typename T>
@@ -720,8 +820,8 @@ void launch_copy_rows(T *dst, const T *src, int W, int nrows, hipStream_t s) {
     template void launch_sw2d_stage<T>(const Sw2dArgsT<T> &, bool, hipStream_t);                                 \
     template void launch_sw2d_derive<T>(const Sw2dArgsT<T> &, hipStream_t);                                      \
     template void launch_tracer_axis<T>(const Sw2dArgsT<T> &, int, bool, const T *, T *, hipStream_t);           \
-    template bool launch_sw2d_fused<T>(const Sw2dArgsT<T> &, bool, int, hipStream_t, int);                       \
-    template int sw2d_fused_rows_per_band<T>(int, int, bool, int, bool, int, int);                              \
+    template bool launch_sw2d_fused<T>(const Sw2dArgsT<T> &, bool, int, hipStream_t, int, int);                  \
+    template int sw2d_fused_rows_per_band<T>(int, int, bool, int, bool, int, int, int);                         \
     template int sw2d_fused_cols<T>(int, int, bool, int, bool, int);                                            \
     template bool launch_sw2d_fused2<T>(const Sw2dArgsT<T> &, hipStream_t);                                      \
     template void launch_copy_rows<T>(T *, const T *, int, int, hipStream_t);

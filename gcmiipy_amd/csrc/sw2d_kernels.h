@@ -22,14 +22,23 @@ inline bool sw2d_fused2_serves(int wrap_j, int j0, int j1, int H, int rows_per_b
 }
 // the form of the single-step kernel: preloading (plain SW2D, short bands) or rolling, and the rolling one's STREAM
 // instantiation where the rows of one launch (all members, `esz` bytes an element) are beyond the 256 MB Infinity Cache
+// depth: rows of requests a wave of the rolling form keeps in flight.  3 -- the deep march, two waves per SIMD -- where
+// the launch streams, the model is GCM_SW2D_TEMP, the state is float64 and the handle has one member: a grid that size
+// leaves HBM waiting on the one row a wave has asked for.  A property of the grid, the same on every call.  `pin` (GCM_SW2D_DEPTH = 1 | 3, kept
+// in the handle; 0: none) fixes the depth of a float64 GCM_SW2D_TEMP launch of any size; nothing else has a deep form.
 struct Sw2dFusedForm {
     bool preload, stream;
+    int depth;
 };
 inline Sw2dFusedForm sw2d_fused_form(bool temp, int tracer, int rows_per_band, long W, long rows, long members,
-                                     long esz) {
+                                     long esz, int pin = 0) {
     const int nfields = 3 + (temp ? 1 : 0) + (tracer ? 1 : 0);
     const bool preload = !temp && rows_per_band <= kPreloadRows;
-    return {preload, !preload && W * rows * members * esz * nfields > (256L << 20)};
+    const bool stream = !preload && W * rows * members * esz * nfields > (256L << 20);
+    // (W: the deep march stores through one buffer per row, whose size in bytes and whose no-store offset are 32-bit)
+    // (one member: an ensemble's members stay bit for bit what single handles of their size compute, which is depth 1)
+    const bool deep = temp && esz == 8 && !preload && W < (1L << 27) && (pin ? pin == 3 : stream && members == 1);
+    return {preload, stream, deep ? 3 : 1};
 }
 
 // Pointers address interior row 0 of member 0; with wrap_j == 0 rows -2,-1 and H,H+1 are ghost rows.
@@ -83,10 +92,13 @@ void launch_tracer_axis(const Sw2dArgsT<T> &a, int axis, bool limit, const T *q_
 // fused variant: predictor + corrector (+ both tracer passes) in one launch
 // cols: columns per lane, 1 (60-column strips) or 2 (T = float with an even width: 120-column strips of 8-byte
 // requests, so that a row segment is 480 B as at fp64)
+// depth_pin: the handle's GCM_SW2D_DEPTH (sw2d_fused_form), 0 for none
 template <typename T>
-bool launch_sw2d_fused(const Sw2dArgsT<T> &a, bool temp, int tracer, hipStream_t s, int cols = 1);   // false: refused
+bool launch_sw2d_fused(const Sw2dArgsT<T> &a, bool temp, int tracer, hipStream_t s, int cols = 1,
+                       int depth_pin = 0);   // false: refused
 template <typename T>
-int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap, int members = 1, int cols = 1);
+int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap, int members = 1, int cols = 1,
+                             int depth_pin = 0);
 // the columns per lane a handle's fused launches use: 1 for double and odd widths; float: 2 once the grid (all
 // members) fills the chip, GCM_SW2D_F32_COLS=1 / 2 overrides
 template <typename T> int sw2d_fused_cols(int W, int H, bool temp, int tracer, bool wrap, int members);

@@ -178,6 +178,12 @@ int gcm_step(gcm_handle *h, int nsteps, double dt);
 #define GCM_SW2D_PLAN_WORDS 9
 int gcm_sw2d_plan(gcm_handle *h, int nsteps, int *out, int nout);
 
+/* Rows of requests a wave of the single-step fused kernel keeps in flight on the handle's next step: 1, or 3 -- the
+ * deep march at two waves per SIMD -- where the launch is the STREAM instantiation of a float64 GCM_SW2D_TEMP handle.
+ * GCM_SW2D_DEPTH = 1 | 3, read by gcm_create, pins it for float64 GCM_SW2D_TEMP handles of any size; every other
+ * handle ignores the switch.  0: the staged variant.  A GCM_PE25D handle or a null pointer: GCM_ERR_ARG.         */
+int gcm_sw2d_fused_depth(gcm_handle *h);
+
 /* The launch geometry of the GCM_PE25D phases whose grid depends on the rows of the launch, the row length and the
  * chip's compute units, without launching anything: a read-only query for tests and tools, taken from the helpers the
  * launchers use themselves.  gcm_pe25d_phase_geometry needs no handle and no device: a launch over `rows` rows of W
