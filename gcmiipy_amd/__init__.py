@@ -14,8 +14,8 @@ built: nothing here computes on the CPU.
 """
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
 from .core import (BoundaryLayer, Climate, Convect, Core, GcmError, Moist, TracerStats, aquaplanet_sst,  # noqa: F401
-                   boundary_layer_column, boundary_layer_surface, convect_columns, device_count, held_suarez_tables,
-                   moist_saturation)
+                   boundary_layer_column, boundary_layer_surface, convect_columns, convect_tracer_columns, device_count,
+                   held_suarez_tables, moist_saturation)
 
 
 
@@ -29,5 +29,5 @@ def clear_cache():
 
 
 __all__ = ["BoundaryLayer", "Climate", "Convect", "Core", "GcmError", "Moist", "TracerStats", "aquaplanet_sst",
-           "boundary_layer_column", "boundary_layer_surface", "convect_columns", "device_count",
+           "boundary_layer_column", "boundary_layer_surface", "convect_columns", "convect_tracer_columns", "device_count",
            "clear_cache", "held_suarez_tables", "moist_saturation"]

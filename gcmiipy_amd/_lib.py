@@ -224,6 +224,9 @@ SYMBOLS = {
     "gcm_set_tracer_mixing": (C.c_int, [_H, C.c_int, _dp, C.c_int]),
     "gcm_tracer_mixed": (C.c_int, [_H, C.c_int]),
     "gcm_tracer_mixing_coeffs": (C.c_int, [C.c_int, _dp, _dp, C.c_double, _dp, _dp, _dp]),
+    "gcm_set_tracer_convect": (C.c_int, [_H, C.c_int, C.c_int]),
+    "gcm_tracer_convected": (C.c_int, [_H, C.c_int]),
+    "gcm_convect_tracer_columns": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
 }
 
 

@@ -358,6 +358,11 @@ class HipBandEngine:
         """Core.set_convect; every band of a run registers the same.  merge_convect() puts the bands' sums together"""
         self.c.set_convect(*off, **params)
 
+    def set_tracer_convection(self, i, on=True):
+        """Core.set_tracer_convection: a latitude band raises the library's refusal -- the tracers' convective mixing is
+        not carried on bands yet (a band's ghost rows are adjusted locally; their tracers would have to be mixed there too)"""
+        self.c.set_tracer_convection(i, on)
+
     def set_moist(self, *off, **params):
         """Core.set_moist; every band of a run registers the same.  merge_moist() puts the bands' sums together"""
         self.c.set_moist(*off, **params)

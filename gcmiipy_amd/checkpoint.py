@@ -11,7 +11,9 @@ is the option "tracer_scheme", files without it restore as centred; the tracers'
 stored per forced tracer i as "forcing_<i>_scalars" (source, decay, pin_value) with "forcing_<i>_emission" and
 "forcing_<i>_pin_mask" where registered, and files without these keys restore with none; their vertical mixing,
 Core.set_tracer_mixing, is stored per mixed tracer i as "mixing_<i>", the float64 profile K of L - 1 values, and files
-without the key restore with none; the Held-Suarez forcing, Core.set_held_suarez, is stored as "held_suarez", its eight
+without the key restore with none; their convective mixing, Core.set_tracer_convection, is stored as "tracer_convect",
+the indices of the tracers that have opted in, only when there are some, and files without the key restore with none
+opted in; the Held-Suarez forcing, Core.set_held_suarez, is stored as "held_suarez", its eight
 parameters in the order of core.HELD_SUAREZ_DEFAULTS, with "held_suarez_lat", the latitudes it was given, and
 re-registered on restore; files without the key restore with none; the zonal-mean climatology, Core.set_climate, is
 stored as "climate_every", "climate_n", "climate_m3" and "climate_m2", the interval, the sample count and the raw
@@ -59,6 +61,9 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
                 out["forcing_%d_pin_mask" % i] = np.asarray(rec["pin_mask"], dtype=np.uint8)
         for i, k in core.tracer_mixings().items():
             out["mixing_%d" % i] = np.asarray(k, dtype=np.float64)
+        opted = getattr(core, "tracer_convections", list)()     # (getattr: a stand-in without the convective mixing will do)
+        if opted:
+            out["tracer_convect"] = np.asarray(opted, dtype=np.int64)
     hs = core.held_suarez if core.model == _lib.PE25D else None
     if hs is not None:
         out["held_suarez"] = np.asarray([hs[k] for k in HELD_SUAREZ_DEFAULTS], dtype=np.float64)
@@ -92,9 +97,11 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, held_suarez, climate, moist, convect, boundary_layer, band_boundary_layer); ground and tracers are
+    tracer_mixing, tracer_convect, held_suarez, climate, moist, convect, boundary_layer, band_boundary_layer); ground and
+    tracers are
     None where the file has none, tracer_forcing
-    {i: dict(...)} and tracer_mixing {i: K} are then empty; held_suarez is (parameters dict, lat) or None; climate is
+    {i: dict(...)} and tracer_mixing {i: K} are then empty, and so is tracer_convect, the list of the tracers that have
+    opted in to the convective mixing (files without the key: none); held_suarez is (parameters dict, lat) or None; climate is
     dict(every, n, m3, m2) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
     dict(params, n, seconds, count, levels) or None; boundary_layer is dict(params, n, seconds, shf, evap) or None;
     band_boundary_layer is whether a band takes that phase (False for files without the option)"""
@@ -142,7 +149,9 @@ def load(path):
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
-                tracer_mixing=mixing, band_boundary_layer=bool(opts.get("band_boundary_layer", False)), **column)
+                tracer_mixing=mixing,
+                tracer_convect=[int(i) for i in d["tracer_convect"]] if "tracer_convect" in d.files else [],
+                band_boundary_layer=bool(opts.get("band_boundary_layer", False)), **column)
 
 
 def restore(path, **core_kwargs):
@@ -164,6 +173,8 @@ def restore(path, **core_kwargs):
             core.set_tracer_forcing(i, **rec)
         for i, k in sorted(ck["tracer_mixing"].items()):
             core.set_tracer_mixing(i, k)
+        for i in ck["tracer_convect"]:
+            core.set_tracer_convection(i)
     if ck["held_suarez"] is not None:
         core.set_held_suarez(ck["held_suarez"][1], **ck["held_suarez"][0])
     if ck["climate"] is not None:

@@ -397,6 +397,23 @@ def convect_columns(y, w, q, dsig, mix_q=True):
     return yo.reshape(y.shape), qo.reshape(y.shape), nb.reshape(y.shape)
 
 
+def convect_tracer_columns(y, w, dsig, c, nblock=False):
+    """the convective mixing of a tracer (gcm_convect_tracer_columns; the host build of the routines the kernel calls,
+    no handle, no device) over columns y, w, c of shape (..., L), level 0 the bottom, with dsig (L,): the blocks are
+    those convect_columns pools from y and w, and c of every merged block becomes sum c dsig / sum dsig, both sums
+    sequential from the block's lowest level -> c_out; with nblock=True -> (c_out, nblock (int32))"""
+    y = np.asarray(y, dtype=np.float64)
+    L = y.shape[-1] if y.ndim else 0
+    yy = as_f64(y.reshape(-1, L) if L else y, name="y")
+    ww, cc = (as_f64(a, y.shape, n).reshape(yy.shape) for a, n in ((w, "w"), (c, "c")))
+    dd = as_f64(dsig, (L,), "dsig")
+    co, nb = np.empty_like(yy), np.empty(yy.shape, dtype=np.intc)
+    _check(lib.gcm_convect_tracer_columns(yy.shape[0], L, _tab(yy), _tab(ww), _tab(dd), _tab(cc), _tab(co),
+                                          nb.ctypes.data_as(C.POINTER(C.c_int))))
+    co = co.reshape(y.shape)
+    return (co, nb.astype(np.int32).reshape(y.shape)) if nblock else co
+
+
 class _ColumnPhase:
     """what tells the phases with per-column sums apart -- the boundary layer, the convective adjustment and the moist
     physics, in the model's order in COLUMN_PHASES -- for Core's seven operations on each and for checkpoint.py: the name in the entry
@@ -717,6 +734,23 @@ class Core:
             if k is not None:
                 out[i] = k
         return out
+
+    # -- convective mixing of the passive tracers (gcm_set_tracer_convect) --------------------
+    def set_tracer_convection(self, i, on=True):
+        """tracer i is mixed in the blocks of the convective adjustment from its next application on (on=False: no
+        longer), on the device, by a launch immediately ahead of the adjustment's -- at the end of a step with
+        set_convect registered, and in convect_step: in every block the adjustment merges, the tracer becomes its mean
+        weighted with dsig.  mix_q plays no part.  Single domains only: a latitude band raises the library's refusal.
+        The life cycle is the forcing's.  A refused call changes nothing"""
+        _check(lib.gcm_set_tracer_convect(self._h, int(i), 1 if on else 0), self._h)
+
+    def tracer_convected(self, i):
+        """-> whether tracer i has opted in (gcm_tracer_convected)"""
+        return bool(_count(lib.gcm_tracer_convected(self._h, int(i)), self._h))
+
+    def tracer_convections(self):
+        """-> the indices of the tracers that have opted in, ascending"""
+        return [i for i in range(self.tracer_count if self.model == _lib.PE25D else 0) if self.tracer_convected(i)]
 
     def set_tracer_scheme(self, scheme):
         """the transport scheme of the passive tracers from the next stage on: "centred" (the update of q, the

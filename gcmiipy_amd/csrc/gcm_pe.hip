@@ -240,6 +240,22 @@ int gcm_tracer_mixing_coeffs(int L, const double *dsig, const double *k, double 
     return tracer_mixing_coeffs(L, dsig, k, dtd, lo, w, g, &gcm_create_error());
 }
 
+// the tracers' convective mixing: the opt-in of a single domain's tracer (a band: refused, not carried yet)
+int gcm_set_tracer_convect(gcm_handle *h, int tracer, int on) {
+    if (int rc = pe_on_device(h, "gcm_set_tracer_convect")) return rc;
+    return pe25d_set_tracer_convect(h->pe, tracer, on != 0, &h->err);
+}
+
+int gcm_tracer_convected(const gcm_handle *h, int tracer) {
+    if (int rc = pe_only(h, "gcm_tracer_convected")) return rc;
+    return pe25d_tracer_convected(h->pe, tracer);
+}
+
+int gcm_convect_tracer_columns(int ncol, int L, const double *y, const double *w, const double *dsig, const double *c,
+                               double *c_out, int *nblk) {
+    return convect_tracer_columns(ncol, L, y, w, dsig, c, c_out, nblk, &gcm_create_error());
+}
+
 int gcm_tracer_count(const gcm_handle *h) {
     if (!h) return GCM_ERR_ARG;
     return h->pe ? pe25d_tracer_count(h->pe) : 0;

@@ -33,45 +33,11 @@
 // LDS of a workgroup: the 2 KB Exner table and 44 bytes per level and lane (five doubles and a count), sized from L at
 // launch: 69.6 KB at L = 24 (two workgroups share a CU), 112 KB at L = 40, 160 KB hold L = 57.
 #pragma clang fp contract(off)
-#include "pe25d_host.h"
+#include "pe25d_convect.h"
 
 namespace gcm {
 
-// ---------------------------------------------------------------- the pooling (host and device: one routine)
-// A stack `St` offers S, Wt, Qs, D, val (double &) and n (int &) of slot b; `top` blocks are on it.  The new level's
-// block is kept in registers while it absorbs the blocks below it and is stored once.  -> the new number of blocks
-template <class St>
-__host__ __device__ inline int convect_push(St &st, int top, double y, double w, double q, double d) {
-    double S = w * y, Wt = w, Qs = q * d, D = d, val = y;
-    int n = 1;
-    while (top > 0 && val < st.val(top - 1)) {
-        --top;
-        S = st.S(top) + S;
-        Wt = st.Wt(top) + Wt;
-        Qs = st.Qs(top) + Qs;
-        D = st.D(top) + D;
-        n = st.n(top) + n;
-        val = S / Wt;
-    }
-    st.S(top) = S; st.Wt(top) = Wt; st.Qs(top) = Qs; st.D(top) = D; st.val(top) = val; st.n(top) = n;
-    return top + 1;
-}
-
-// the neutral profile's factor r and the compared value y of a cell; dry: r = 1 and y = theta, no operation on it
-__host__ __device__ inline double convect_r(double p_lev, double kdiff) { return exp(kdiff * log(p_lev / kP0)); }
-
-struct CvHostStack {
-    std::vector<double> s, wt, qs, d, v;
-    std::vector<int> c;
-    explicit CvHostStack(int L) : s(L), wt(L), qs(L), d(L), v(L), c(L) {}
-    double &S(int b) { return s[b]; }
-    double &Wt(int b) { return wt[b]; }
-    double &Qs(int b) { return qs[b]; }
-    double &D(int b) { return d[b]; }
-    double &val(int b) { return v[b]; }
-    int &n(int b) { return c[b]; }
-};
-
+// (the pooling routine convect_push, convect_r and the host's stack: pe25d_convect.h, shared with pe25d_convect_tracers.hip)
 int convect_check(const gcm_convect *cv, const char *fn, std::string *err) {
     const auto bad = [&](const char *what) { *err = std::string(fn) + ": " + what; return GCM_ERR_ARG; };
     if (!cv) return bad("no parameters");
@@ -106,13 +72,7 @@ int convect_columns(int ncol, int L, const double *y, const double *w, const dou
 }
 
 // ---------------------------------------------------------------- the kernel
-constexpr int kCvThreads = 64;       // one wave: the workgroup's LDS is that wave's stack
-constexpr int kCvBatch = 8;          // levels requested together in pass 1, then compared in order
-constexpr int kCvBatch2 = 4;         // levels requested together in pass 2, then pushed in order
-constexpr size_t kCvSlotBytes = 5 * sizeof(double) + sizeof(int);
-
-constexpr size_t kCvLdsCap = 160 * 1024;   // a workgroup's LDS on gfx950, the figure pe25d_create sizes its kernels by
-
+// (the constants of the kernel's shape and the lane's stack in LDS, CvLdsStack: pe25d_convect.h)
 size_t convect_lds_bytes(int L) { return sizeof(double) * kExnerTabDoubles + kCvSlotBytes * (size_t)L * kCvThreads; }
 
 template <typename T>
@@ -126,20 +86,6 @@ struct CvArgsT {
     int dry, mix_q;
     int W, L, H;
     int j0, n0, jb0, nrows;          // the rows of the launch: [j0, j0 + n0), then from jb0 on (a band's ghost rows: negative / >= H)
-};
-
-// the lane's stack in LDS: slot b of array a at base[(a L + b) 64 + lane]
-struct CvLdsStack {
-    double *base;
-    int *cnt;
-    int L;
-    __host__ __device__ double &at(int a, int b) { return base[(a * L + b) * kCvThreads]; }
-    __host__ __device__ double &S(int b) { return at(0, b); }
-    __host__ __device__ double &Wt(int b) { return at(1, b); }
-    __host__ __device__ double &Qs(int b) { return at(2, b); }
-    __host__ __device__ double &D(int b) { return at(3, b); }
-    __host__ __device__ double &val(int b) { return at(4, b); }
-    __host__ __device__ int &n(int b) { return cnt[b * kCvThreads]; }
 };
 
 // grid (column blocks of 64, rows)
@@ -303,6 +249,9 @@ int pe25d_convect_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool
     if (accumulate && !z.sums.acc) { *err = "convect: no sums to accumulate into (gcm_set_convect)"; return GCM_ERR_STATE; }
     if (set < 0) set = m->cur_i;
     if (std::max(0, j1 - j0) + std::max(0, jb1 - jb0) <= 0) return GCM_OK;
+    // the opted-in tracers are mixed in this application's blocks, from theta as it stands: immediately ahead, in stream
+    // order (single domains: the own rows are [j0, j1); without an opt-in nothing is queued)
+    if (int rc = pe25d_convect_tracers_rows(m, set, j0, j1, s, err)) return rc;
     pe25d_phase_wrote(m, set, keep_ghosts, false);         // the launch writes theta and q and reads p, theta and q
     if (int rc = m->f32 ? cv_launch<float>(m, set, j0, j1, jb0, jb1, accumulate, s, err)
                         : cv_launch<double>(m, set, j0, j1, jb0, jb1, accumulate, s, err))

@@ -10,6 +10,7 @@
 //   pe25d_climate.hip  the zonal-mean climatology: its kernel, its sums and their way to the host and back
 //   pe25d_moist.hip    moist physics: the saturation routine, the kernel and its launches
 //   pe25d_convect.hip  convective adjustment: the pooling routine, the kernel and its launches
+//   pe25d_convect_tracers.hip  the tracers' convective mixing in the adjustment's blocks: the kernel, its launch, the opt-ins
 //   pe25d_boundary_layer.hip  surface fluxes and boundary-layer mixing: the routines, the two kernels and their launches
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
@@ -87,7 +88,12 @@ struct PeTracers {
         int n_waited = 0;
     };
     Mix mix;
-    double *stats_dev = nullptr;                // gcm_tracer_stats: float64 dsig [L], the records, then the workgroups' partials
+    // convective mixing of the tracers (gcm_set_tracer_convect, pe25d_convect_tracers.hip): per tracer the opt-in,
+    // n_convect of them; convect_lds: the kernel's dynamic LDS at the handle's L, 0: its attribute is not set yet
+    bool convect[GCM_MAX_TRACERS] = {};
+    int n_convect = 0;
+    size_t convect_lds = 0;
+    double *stats_dev = nullptr;               // gcm_tracer_stats: float64 dsig [L], the records, then the workgroups' partials
 };
 
 // Held-Suarez forcing (pe25d_held_suarez.hip): the device tables of the last (parameters, lat, dt) a launch was asked
@@ -368,5 +374,12 @@ void stage_tracers_launched(Pe25d *m, hipStream_t st, bool caller_joins);
 size_t tracer_halo_bytes(const Pe25d *m);
 void tracer_halo_segments(Pe25d *m, bool pack, int side, int set, double **msg, SegCopy *c);
 void tracers_destroy(Pe25d *m);                  // pe25d_destroy: the tracers' storage, forcing, mixing and events
+// hazard 4 (pe25d_convect_tracers.hip): the tracers' convective mixing writes the current tracers on the caller's stream,
+// ahead of the adjustment's launch (pe25d_convect_rows calls it).  It joins the last stage's tracer launches first
+// (pe25d_join_tracers); the next stage's tracer launch on the second stream follows it because the launch invalidates the
+// fork at the last K4 (pe25d_fork_invalidate: chain B then waits for the caller's stream's position) -- the invalidation
+// was chosen, not an event of its own: nothing is recorded, and a step without opt-ins queues what it queued
+int pe25d_convect_tracers_rows(Pe25d *m, int set, int j0, int j1, hipStream_t s, std::string *err);
+void tracers_convect_forget(Pe25d *m);           // the tracers' storage went: so do the opt-ins
 
 }  // namespace gcm

@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
+// pe25d_climate.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -147,6 +147,12 @@ int pe25d_tracer_forced(const Pe25d *m, int tracer);
 // gcm_set_tracer_mixing (k == nullptr: clear tracer, -1 = all) / gcm_tracer_mixed
 int pe25d_set_tracer_mixing(Pe25d *m, int tracer, const double *k, int nk, hipStream_t s, std::string *err);
 int pe25d_tracer_mixed(const Pe25d *m, int tracer);
+// gcm_set_tracer_convect / gcm_tracer_convected (pe25d_convect_tracers.hip): the opt-in of a single domain's tracer to the
+// mixing in the convective adjustment's blocks; convect_tracer_columns: gcm_convect_tracer_columns (no handle, no device)
+int pe25d_set_tracer_convect(Pe25d *m, int tracer, bool on, std::string *err);
+int pe25d_tracer_convected(const Pe25d *m, int tracer);
+int convect_tracer_columns(int ncol, int L, const double *y, const double *w, const double *dsig, const double *c,
+                           double *c_out, int32_t *nblk, std::string *err);
 // gcm_tracer_mixing_coeffs (pe25d_tracer_mix.hip; no handle, no device): the tables gcm_set_tracer_mixing's launches take too
 int tracer_mixing_coeffs(int L, const double *dsig, const double *k, double dtd, double *lo, double *w, double *g, std::string *err);
 void pe25d_timing(Pe25d *m, std::vector<hipEvent_t> *ev, size_t *used);

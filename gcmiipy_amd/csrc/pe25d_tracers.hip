@@ -135,7 +135,11 @@ template void launch_tracers<float>(Pe25d *, const PeArgsT<float> &, int, int, h
 // another stream: ev_tr_int follows it (stage_tracers_launched), the next stage's streams wait for it where they do not
 // carry it themselves (follow_last_tracers), the caller's stream joins it (pe25d_join_tracers).  Hazards 2 and 3 (the
 // edge launch behind the unpack, the pack behind the edge launch) are stream order in update_edges; a pack or unpack the
-// caller queues takes pe25d_follow_tracers.
+// caller queues takes pe25d_follow_tracers.  Hazard 4 (single domains; pe25d_convect_tracers_rows): the tracers' convective
+// mixing writes the current tracers on the caller's stream at the end of a step.  It joins the launches above first
+// (pe25d_join_tracers), and the next stage's tracer launch on the second stream follows it because it invalidates the fork
+// at the last K4 (pe25d_fork_invalidate): chain B then waits for the caller's stream's position, not for ev_k4.  The
+// invalidation was chosen over an event of its own: no record, and nothing at all where no tracer has opted in.
 bool last_tracers_in_flight(const Pe25d *m) { return m->tr.int_wait; }
 
 void follow_last_tracers(Pe25d *m, hipStream_t st) {
@@ -199,6 +203,7 @@ static hipError_t tracers_free(Pe25d *m) {
     m->tr.buf = nullptr; m->tr.n = 0; m->tr.star = false;
     drop_tracer_forcing(m, -1);                  // (the fields' placement followed the tracers' storage)
     drop_tracer_mixing(m, -1);                   // (the same life cycle)
+    tracers_convect_forget(m);                   // (and the opt-ins of the convective mixing)
     return e;
 }
 

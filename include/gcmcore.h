@@ -372,6 +372,42 @@ int gcm_set_tracer_mixing(gcm_handle *h, int tracer, const double *k, int nk);
 int gcm_tracer_mixed(const gcm_handle *h, int tracer);
 int gcm_tracer_mixing_coeffs(int L, const double *dsig, const double *k, double dtd,
                              double *lo, double *w, double *g);
+/* Convective mixing of the passive tracers of GCM_PE25D on the device, opt-in per tracer, SINGLE DOMAINS ONLY, fp64 and
+ * fp32 handles: a tracer that has opted in is pooled in the blocks of the convective adjustment (gcm_set_convect,
+ * gcm_convect_step, below), which otherwise leaves every tracer where it was.
+ * One column, level k = 0 at the bottom.  The blocks are those the adjustment forms for that column in that application:
+ * the same p and theta as they stand just ahead of it, the same kappa_c, the same pooling routine; there is no second
+ * criterion.  For every merged block (n > 1) over levels [k0, k0 + n) and every opted-in tracer c, in float64 for
+ * either storage type, every operation rounded on its own (no contraction):
+ *   D  = dsig[k0];          D  = D  + dsig[k]          k = k0 + 1 .. k0 + n - 1, ascending
+ *   Cs = c[k0] * dsig[k0];  Cs = Cs + c[k] * dsig[k]   likewise
+ *   c[k] <- Cs / D for every level of the block, rounded once to the storage type.
+ * Levels of unmerged blocks, tracers that have not opted in and stable columns are NOT WRITTEN.  p is constant within a
+ * column, so the tracer's mass sum c p dsig (gcm_tracer_stats) is conserved up to rounding, and the output lies within
+ * the block's input range.  mix_q plays no part.  The order of the two sums is the contract; it is deliberately NOT the
+ * merge-tree order in which the adjustment forms Qs and D of a block: a tracer equal to q equals the mixed q (mix_q = 1)
+ * to rounding, not to the bit.
+ * Order within a step: ... boundary layer, the tracers' convective mixing, the convective adjustment, the moist physics,
+ * the sample.  One launch immediately ahead of every launch of the adjustment (the end of a registered step, and
+ * gcm_convect_step), on the handle's stream, which first joins the tracers' last stage launches on the other streams;
+ * the next stage's tracer launches follow it.  Nothing is launched, joined or recorded when no tracer has opted in or
+ * the adjustment is neither registered nor called: a step then queues exactly what it queued.  The predictor's (star)
+ * tracers are never mixed.
+ * gcm_set_tracer_convect: on != 0 opts tracer `tracer` in, 0 out.  The opt-in has the forcing's life cycle: it survives
+ * gcm_set_tracers with an unchanged count, gcm_set_tracer_scheme and gcm_set_state, and is dropped by gcm_set_tracers
+ * with another count (0 included).  Errors: a null handle, a tracer outside [0, gcm_tracer_count): GCM_ERR_ARG; other
+ * models, a latitude band (bands are not carried yet: gcm_last_error says so) and a handle whose L makes the blocks of a
+ * wave exceed a workgroup's LDS (as gcm_set_convect): GCM_ERR_UNSUPPORTED.  A refused call changes nothing.
+ * gcm_tracer_convected: 1 where tracer `tracer` has opted in, else 0; errors as gcm_tracer_forced.
+ * gcm_convect_tracer_columns: the pooling and the two sums above on their own, on the host, without a handle or a device
+ * -- the routines the kernel calls, compiled for the host, as gcm_convect_columns -- over ncol columns y, w, c [ncol][L]
+ * (the adjustment's compared value and weight, the tracer) with dsig [L].  c_out [ncol][L] receives the mixed tracer
+ * (levels of unmerged blocks are copied), nblk [ncol][L] the size n of each level's block and may be NULL.  Errors
+ * (GCM_ERR_ARG, message: gcm_last_error(NULL)): ncol < 0, L < 1, a missing array.                                  */
+int gcm_set_tracer_convect(gcm_handle *h, int tracer, int on);
+int gcm_tracer_convected(const gcm_handle *h, int tracer);
+int gcm_convect_tracer_columns(int ncol, int L, const double *y, const double *w, const double *dsig, const double *c,
+                               double *c_out, int *nblk);
 
 /* Diagnostics the reference's drivers evaluate on the host every step
  * (SURVEY.md 8f-1); computed by device reductions, result copied to *out. */
@@ -597,7 +633,8 @@ int gcm_moist_saturation(int n, const double *T, const double *p_lev, double *q_
  * Both loops are bounded by L.  The result is the weighted isotonic regression of y, the exact limit of the classic
  * pairwise adjustment sweeps: no iteration count, no tolerance.  y comes out non-decreasing in k; sum_k T dsig and
  * sum_k q dsig of the column are conserved to rounding; a second application changes no bit where kappa_c = 0.
- * p, u, v, the tracers and the ground temperature are untouched.
+ * p, u, v, the ground temperature and the tracers are untouched (a tracer that has opted in through
+ * gcm_set_tracer_convect is mixed in the same blocks by a launch of its own ahead of this one).
  * Accumulators in the handle, allocated by gcm_set_convect, own rows only: count [H][W] and levels [H][W], float64;
  * an application adds 1 to count where the column had a merged block and sum of n over its merged blocks to levels.
  * seconds (the sum of the registered steps' dt) and nsteps (the applications).  One writer per word and launch, no atomics.
