@@ -10,8 +10,9 @@ using PeArgs = PeArgsT<double>;   // the diagnostics and the column physics belo
 
 // ---------------------------------------------------------------- calc_energy + STATS (no_limits_2_5d.py:35-60,85-91)
 // thread per (j,i) column; out[kStatsWords*block + {0,1,2}] = partial sums of ke, ate, geo,
-// {3,4,5,6} = max u, min u, max v, min v of the block's columns, {7} = NaNs seen in u and v
-constexpr int kStatsWords = 8;
+// {3,4,5,6} = max u, min u, max v, min v of the block's columns (fmax / fmin: a NaN drops out), {7} = cells where u or
+// v is NaN, {8,9} = cells where u is, where v is: the host makes a field's extrema NaN from the field's own count
+constexpr int kStatsWords = 10;
 __global__ __launch_bounds__(256) void pe_energy_kernel(PeArgs a, const double *area, int area_by_i,
                                                         double *out) {
     __shared__ double tab[kExnerTabDoubles];
@@ -23,7 +24,7 @@ __global__ __launch_bounds__(256) void pe_energy_kernel(PeArgs a, const double *
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int j = blockIdx.y;
     double ke = 0.0, ate = 0.0, geo = 0.0;
-    double umax = -INFINITY, umin = INFINITY, vmax = -INFINITY, vmin = INFINITY, nn = 0.0;
+    double umax = -INFINITY, umin = INFINITY, vmax = -INFINITY, vmin = INFINITY, nn = 0.0, nu = 0.0, nv = 0.0;
     if (i < W) {
         const int iw = i == 0 ? W - 1 : i - 1;
         const double pc = a.p[ix.r2(j) + i];
@@ -36,6 +37,8 @@ __global__ __launch_bounds__(256) void pe_energy_kernel(PeArgs a, const double *
             umax = fmax(umax, u_c); umin = fmin(umin, u_c);
             vmax = fmax(vmax, v_c); vmin = fmin(vmin, v_c);
             if (u_c != u_c || v_c != v_c) nn += 1.0;
+            if (u_c != u_c) nu += 1.0;
+            if (v_c != v_c) nv += 1.0;
             const double uc = (u_c + a.u[o + iw]) * 0.5;                          // imh(u)
             const double vc = (v_c + a.v[n3 + (long)k * W + i]) * 0.5;            // jmh(v)
             const double mag = sqrt(uc * uc + vc * vc);
@@ -57,11 +60,14 @@ __global__ __launch_bounds__(256) void pe_energy_kernel(PeArgs a, const double *
         umax = fmax(umax, __shfl_down(umax, o)); umin = fmin(umin, __shfl_down(umin, o));
         vmax = fmax(vmax, __shfl_down(vmax, o)); vmin = fmin(vmin, __shfl_down(vmin, o));
         nn += __shfl_down(nn, o);
+        nu += __shfl_down(nu, o);
+        nv += __shfl_down(nv, o);
     }
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         red[0][w] = ke; red[1][w] = ate; red[2][w] = geo;
         red[3][w] = umax; red[4][w] = umin; red[5][w] = vmax; red[6][w] = vmin; red[7][w] = nn;
+        red[8][w] = nu; red[9][w] = nv;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -71,7 +77,7 @@ __global__ __launch_bounds__(256) void pe_energy_kernel(PeArgs a, const double *
         o[4] = fmin(fmin(red[4][0], red[4][1]), fmin(red[4][2], red[4][3]));
         o[5] = fmax(fmax(red[5][0], red[5][1]), fmax(red[5][2], red[5][3]));
         o[6] = fmin(fmin(red[6][0], red[6][1]), fmin(red[6][2], red[6][3]));
-        o[7] = red[7][0] + red[7][1] + red[7][2] + red[7][3];
+        for (int q = 7; q < kStatsWords; ++q) o[q] = red[q][0] + red[q][1] + red[q][2] + red[q][3];
     }
 }
 
@@ -190,7 +196,12 @@ int pe25d_filter_field(Pe25d *m, int nlev, const double *in, double *out, hipStr
 }
 
 // calc_energy + STATS in one launch and one synchronisation of `s`: out9 = u_max, u_min, v_max,
-// v_min, ke, ate, geo, total, NaN count.  The area table and the partials live in the handle.
+// v_min, ke, ate, geo, total, the number of cells where u or v is NaN.  The area table and the partials live in the
+// handle.  The call does not join the second stream, and need not: only single domains get here, whose state sets are
+// written by K4 (update_whole) and by the phases behind the dynamics (pe_phase_rows), all of them on the caller's stream
+// `s`; a single domain's second stream carries K1 + pit (spu, pit, p_n: scratch this kernel does not read) and the
+// tracer launches (the tracers' own fields), see half_t and stage_tracers in pe25d_kernels.hip.  The kernel below follows
+// every writer of p, u, v and theta in stream order.
 int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err) {
     if (m->f32) { *err = "gcm_energy / gcm_stats: fp64 handles only"; return GCM_ERR_UNSUPPORTED; }
     if (!m->wrap) { *err = "gcm_energy / gcm_stats: single band only"; return GCM_ERR_UNSUPPORTED; }
@@ -223,15 +234,15 @@ int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], 
         *err = "hip: gcm_stats kernel failed";
         return GCM_ERR_HIP;
     }
-    double ke = 0, ate = 0, geo = 0, nn = 0, umax = -INFINITY, umin = INFINITY, vmax = -INFINITY, vmin = INFINITY;
+    double ke = 0, ate = 0, geo = 0, nn = 0, nu = 0, nv = 0, umax = -INFINITY, umin = INFINITY, vmax = -INFINITY, vmin = INFINITY;
     for (int b = 0; b < nb; ++b) {
         const double *o = part + (size_t)kStatsWords * b;
-        ke += o[0]; ate += o[1]; geo += o[2]; nn += o[7];
+        ke += o[0]; ate += o[1]; geo += o[2]; nn += o[7]; nu += o[8]; nv += o[9];
         umax = std::fmax(umax, o[3]); umin = std::fmin(umin, o[4]);
         vmax = std::fmax(vmax, o[5]); vmin = std::fmin(vmin, o[6]);
     }
-    // np.max / np.min propagate NaN
-    out[0] = nn > 0 ? NAN : umax; out[1] = nn > 0 ? NAN : umin; out[2] = nn > 0 ? NAN : vmax; out[3] = nn > 0 ? NAN : vmin;
+    // np.max / np.min propagate NaN, each of its own field (no_limits_2_5d.py:85-88): a NaN in v leaves u_max finite
+    out[0] = nu > 0 ? NAN : umax; out[1] = nu > 0 ? NAN : umin; out[2] = nv > 0 ? NAN : vmax; out[3] = nv > 0 ? NAN : vmin;
     out[4] = ke; out[5] = ate; out[6] = geo; out[7] = ke + ate + geo; out[8] = nn;
     return GCM_OK;
 }

@@ -435,7 +435,9 @@ int gcm_diag_members(gcm_handle *h, int kind, double *out, int n);   /* one valu
 int gcm_array_stats(const double *x, long n_axis, long n_inner, double *out3);
 /* The whole STATS record of full_timestep (no_limits_2_5d.py:85-91) by ONE launch and ONE
  * synchronisation (GCM_PE25D, fp64, single band): out9 = u_max, u_min, v_max, v_min, ke, ate, geo,
- * total (calc_energy, :35-60; `area` as gcm_energy), count of NaNs in u and v.                   */
+ * total (calc_energy, :35-60; `area` as gcm_energy), the number of cells where u or v is NaN.
+ * The extrema are np.max / np.min of each field on its own (:85-88): a NaN in u makes u_max and
+ * u_min NaN and leaves v_max and v_min alone, and the other way round.                           */
 int gcm_stats(gcm_handle *h, const double *area, int area_len, double *out9);
 /* calc_energy(p,u,v,t,q,g,geom) -> out4 = (ke, ate, geo, total) in J, no_limits_2_5d.py:35-60
  * (GCM_PE25D).  `area` is geom.area; the reference broadcasts its (H,) array against the LAST
