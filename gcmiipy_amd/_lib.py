@@ -20,6 +20,8 @@ F64, F32 = 0, 1
 MAX_TRACERS = 16                     # GCM_MAX_TRACERS
 TRACER_STATS_WORDS = 6               # GCM_TRACER_STATS_WORDS
 CLIM_WORDS3, CLIM_WORDS2 = 10, 2     # GCM_CLIM_WORDS3, GCM_CLIM_WORDS2
+SPEC_WORDS = 6                       # GCM_SPEC_WORDS
+SPEC_PLAN_WORDS = 6                  # GCM_SPEC_PLAN_WORDS
 SW2D_PLAN_WORDS = 9                  # GCM_SW2D_PLAN_WORDS
 PHASE_HELD_SUAREZ, PHASE_MOIST, PHASE_CLIMATE, PHASE_TRACER_FORCING = range(4)   # gcm_pe25d_phase
 PHASE_PLAN_WORDS = 5                 # GCM_PHASE_PLAN_WORDS
@@ -179,6 +181,14 @@ SYMBOLS = {
     "gcm_climate_reset": (C.c_int, [_H]),
     "gcm_get_climate": (C.c_int, [_H, _dp, _dp, C.POINTER(C.c_int64)]),
     "gcm_put_climate": (C.c_int, [_H, _dp, _dp, C.c_int64]),
+    "gcm_set_spectra": (C.c_int, [_H, C.c_int, C.c_int]),
+    "gcm_spectra_every": (C.c_int, [_H]),
+    "gcm_spectra_mmax": (C.c_int, [_H]),
+    "gcm_spectra_plan": (C.c_int, [_H, C.POINTER(C.c_int), C.c_int]),
+    "gcm_spectra_sample": (C.c_int, [_H]),
+    "gcm_spectra_reset": (C.c_int, [_H]),
+    "gcm_get_spectra": (C.c_int, [_H, _dp, C.POINTER(C.c_int64)]),
+    "gcm_put_spectra": (C.c_int, [_H, _dp, C.c_int64]),
     "gcm_snapshot": (C.c_int, [_H]),
     "gcm_restore": (C.c_int, [_H]),
     "gcm_halo_bytes": (C.c_size_t, [_H]),

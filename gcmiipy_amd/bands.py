@@ -224,6 +224,21 @@ def merge_climate(parts):
     return Climate(parts[0].n, *[np.concatenate([c[f] for c in parts], axis=-1) for f in range(1, len(Climate._fields))])
 
 
+def merge_spectra(parts):
+    """the spectra of the whole domain from its bands': `parts` are the bands' Spectra records (Core.spectra) in row
+    order; the rows are concatenated.  ValueError where the sample counts or the numbers of wavenumbers differ"""
+    import numpy as np
+    from .core import Spectra
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_spectra: no records")
+    if any(c.n != parts[0].n for c in parts):
+        raise ValueError("merge_spectra: the bands hold %s samples" % ", ".join(str(c.n) for c in parts))
+    if any(c.uu.shape[-1] != parts[0].uu.shape[-1] for c in parts):
+        raise ValueError("merge_spectra: the bands hold %s wavenumbers" % ", ".join(str(c.uu.shape[-1]) for c in parts))
+    return Spectra(parts[0].n, *[np.concatenate([c[f] for c in parts], axis=-2) for f in range(1, len(Spectra._fields))])
+
+
 def _merge_column(ph, parts):
     """merge_moist / merge_convect / merge_boundary_layer: the records of core._ColumnPhase `ph` in row order -> the whole domain's"""
     import numpy as np
@@ -284,7 +299,7 @@ class LoopbackExchange:
 
 class HipBandEngine:
     """A `Core` band + torch CUDA buffers/streams for the exchange.  It keeps no registrations: the phases behind the
-    dynamics (set_physics ... set_climate) are the handle's, and a host-driven step ends with the library's own walk
+    dynamics (set_physics ... set_climate, set_spectra) are the handle's, and a host-driven step ends with the library's own walk
     over them (Core.end_step), the one gcm_band_run takes."""
 
     def __init__(self, core, torch, overlap=True, stream_aware=True):
@@ -371,6 +386,11 @@ class HipBandEngine:
         """Core.set_climate; every band of a run registers the same interval.  merge_climate() puts the bands' records
         together"""
         self.c.set_climate(every)
+
+    def set_spectra(self, every=1, mmax=None):
+        """Core.set_spectra; every band of a run registers the same interval and mmax.  merge_spectra() puts the bands'
+        records together"""
+        self.c.set_spectra(every, mmax)
 
     def physics_begin(self, dt):
         """host-driven band step: behind the unpack of the post-corrector exchange, the walk up to and including the

@@ -18,6 +18,8 @@ parameters in the order of core.HELD_SUAREZ_DEFAULTS, with "held_suarez_lat", th
 re-registered on restore; files without the key restore with none; the zonal-mean climatology, Core.set_climate, is
 stored as "climate_every", "climate_n", "climate_m3" and "climate_m2", the interval, the sample count and the raw
 float64 sums, registered and uploaded again on restore; files without these keys restore without a climatology; the
+zonal wavenumber spectra, Core.set_spectra, are stored as "spectra_every", "spectra_mmax", "spectra_n" and "spectra_s",
+saved and restored the same way, and files without these keys restore with none; the
 moist physics, Core.set_moist, is stored as "moist", its three parameters in the order of core.MOIST_DEFAULTS, with
 "moist_n", "moist_seconds", "moist_precip" and "moist_evap", the count, the seconds and the raw float64 sums, registered
 and uploaded again on restore; files without these keys restore with none; the convective adjustment, Core.set_convect,
@@ -71,6 +73,10 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
     if core.model == _lib.PE25D and core.climate_every > 0:
         n, m3, m2 = core.climate_sums()
         out.update(climate_every=np.int64(core.climate_every), climate_n=np.int64(n), climate_m3=m3, climate_m2=m2)
+    if core.model == _lib.PE25D and getattr(core, "spectra_every", 0) > 0:   # (getattr: a stand-in without the spectra will do)
+        n, s = core.spectra_sums()
+        out.update(spectra_every=np.int64(core.spectra_every), spectra_mmax=np.int64(core.spectra_mmax), spectra_n=np.int64(n),
+                   spectra_s=s)
     # (a core is asked only for the phases it knows: getattr, so that a stand-in without one of them will do; reversed:
     # the files have always held the moist physics' keys ahead of the convective adjustment's; the boundary layer's follow)
     for ph in reversed(COLUMN_PHASES if core.model == _lib.PE25D else ()):
@@ -97,12 +103,12 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, tracer_convect, held_suarez, climate, moist, convect, boundary_layer, band_boundary_layer); ground and
+    tracer_mixing, tracer_convect, held_suarez, climate, spectra, moist, convect, boundary_layer, band_boundary_layer); ground and
     tracers are
     None where the file has none, tracer_forcing
     {i: dict(...)} and tracer_mixing {i: K} are then empty, and so is tracer_convect, the list of the tracers that have
     opted in to the convective mixing (files without the key: none); held_suarez is (parameters dict, lat) or None; climate is
-    dict(every, n, m3, m2) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
+    dict(every, n, m3, m2) or None; spectra is dict(every, mmax, n, s) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
     dict(params, n, seconds, count, levels) or None; boundary_layer is dict(params, n, seconds, shf, evap) or None;
     band_boundary_layer is whether a band takes that phase (False for files without the option)"""
     d = np.load(path, allow_pickle=False)
@@ -138,6 +144,9 @@ def load(path):
     clim = None
     if "climate_every" in d.files:
         clim = dict(every=int(d["climate_every"]), n=int(d["climate_n"]), m3=d["climate_m3"], m2=d["climate_m2"])
+    spec = None
+    if "spectra_every" in d.files:
+        spec = dict(every=int(d["spectra_every"]), mmax=int(d["spectra_mmax"]), n=int(d["spectra_n"]), s=d["spectra_s"])
     # (the parameters in the types of the phase's defaults: mix_q is an int)
     column = {ph.name: None for ph in COLUMN_PHASES}
     for ph in COLUMN_PHASES:
@@ -146,6 +155,7 @@ def load(path):
             column[ph.name] = dict(params=par, n=int(d[ph.name + "_n"]), seconds=float(d[ph.name + "_seconds"]),
                                    **{f: d["%s_%s" % (ph.name, f)] for f in ph.fields})
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, climate=clim,
+                spectra=spec,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
@@ -180,6 +190,9 @@ def restore(path, **core_kwargs):
     if ck["climate"] is not None:
         core.set_climate(ck["climate"]["every"])
         core.put_climate(ck["climate"]["n"], ck["climate"]["m3"], ck["climate"]["m2"])
+    if ck["spectra"] is not None:
+        core.set_spectra(ck["spectra"]["every"], ck["spectra"]["mmax"])
+        core.put_spectra(ck["spectra"]["n"], ck["spectra"]["s"])
     for ph in COLUMN_PHASES:                 # (the model's order: the boundary layer, the convective adjustment, the moist physics)
         rec = ck[ph.name]
         if rec is not None:

@@ -110,6 +110,42 @@ class Climate(collections.namedtuple("Climate", ("n",) + CLIMATE_WORDS3 + CLIMAT
             return cls(int(n), *[m3[w] / d for w in range(len(CLIMATE_WORDS3))], *[m2[w] / d for w in range(len(CLIMATE_WORDS2))])
 
 
+SPECTRA_WORDS = ("uu", "vv", "TT", "uv", "vT", "vtheta")    # the products of gcm_get_spectra's s
+
+
+def spectra_weights(M, width):
+    """the one-sided weights w_m of the wavenumbers m = 0 .. M - 1 of rows of `width` columns: 1 for m = 0 and for the
+    Nyquist wavenumber m = width / 2 of an even width, 2 otherwise (the wavenumbers m and width - m together)"""
+    w = np.full(M, 2.0)
+    w[0] = 1.0
+    if width % 2 == 0 and width // 2 < M:
+        w[width // 2] = 1.0
+    return w
+
+
+class Spectra(collections.namedtuple("Spectra", ("n",) + SPECTRA_WORDS)):
+    """the zonal wavenumber spectra of a GCM_PE25D handle (Core.spectra): n, the number of samples, and per product an
+    (L, H, M) array, the one-sided spectrum by zonal wavenumber m = 0 .. M - 1 averaged over the samples -- the
+    device's float64 sums times w_m / (W^2 n) (NaN where n = 0), w_m as in spectra_weights.  uu = |Uc|^2, vv = |Vc|^2,
+    TT = |That|^2, uv = Re(Uc conj Vc), vT = Re(Vc conj That), vtheta = Re(Vc conj Thetahat) of the winds at the cell
+    centre, T = theta Pi and theta.  With M = W / 2 + 1 a row's entries sum to the zonal mean of the product: uv, vT,
+    vtheta and TT then sum to the climatology's.  A band: its own rows (bands.merge_spectra)"""
+    __slots__ = ()
+
+    @property
+    def kinetic_energy(self):
+        """0.5 (uu + vv): the kinetic-energy spectrum per unit mass of the centred winds (m = 0: the zonal mean flow)"""
+        return 0.5 * (self.uu + self.vv)
+
+    @classmethod
+    def from_sums(cls, n, s, width):
+        """the record of the raw sums s (6, L, H, M) of n samples of rows of `width` columns"""
+        s = np.asarray(s, dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            scale = spectra_weights(s.shape[-1], width) / (np.float64(width) * np.float64(width) * np.float64(n))
+            return cls(int(n), *[s[w] * scale for w in range(len(SPECTRA_WORDS))])
+
+
 DTYPES = {"f64": _lib.F64, "f32": _lib.F32}
 # the transport scheme of a GCM_PE25D handle's passive tracers (gcm_set_tracer_scheme)
 TRACER_SCHEMES = {"centred": _lib.TRACER_NONE, "upwind": _lib.TRACER_UPWIND, "van_leer": _lib.TRACER_VANLEER}
@@ -1187,6 +1223,61 @@ class Core:
         climatology is registered"""
         n, m3, m2 = self.climate_sums()
         return Climate.from_sums(n, m3, m2, self.W)
+
+    # -- zonal wavenumber spectra (GCM_PE25D) ----------------------------------------------
+    def set_spectra(self, every=1, mmax=None):
+        """accumulate the zonal wavenumber spectra on the device (gcm_set_spectra): from now on every `every`-th step of
+        step() / band_run() ends -- behind the climatology's sample -- with one launch that transforms uc, vc, T and
+        theta of every (level, row) along i in float64 and adds the six products of `Spectra` at the wavenumbers
+        0 .. mmax to float64 sums in the handle.  mmax=None: min(W / 2, 63).  The step counter is the spectra's own and
+        runs across calls; half_step never samples.  Registering again resets the sums; every=0 unregisters.
+        ValueError for every < 0 and for mmax outside 0 .. W / 2"""
+        _check(lib.gcm_set_spectra(self._h, int(every), -1 if mmax is None else int(mmax)), self._h)
+
+    @property
+    def spectra_every(self):
+        """the registered sampling interval in steps, 0 where none is registered (gcm_spectra_every)"""
+        return _count(lib.gcm_spectra_every(self._h), self._h)
+
+    @property
+    def spectra_mmax(self):
+        """the highest wavenumber in the sums (gcm_spectra_mmax); GcmError where no spectra are registered"""
+        return _count(lib.gcm_spectra_mmax(self._h), self._h)
+
+    def spectra_plan(self):
+        """the launch geometry of a sample of this handle, without launching (gcm_spectra_plan): grid_x (rows), nseg
+        (level segments), threads, lds_bytes, passes of a transform, per_thread (wavenumbers a thread holds)"""
+        out = (C.c_int * _lib.SPEC_PLAN_WORDS)()
+        _check(lib.gcm_spectra_plan(self._h, out, _lib.SPEC_PLAN_WORDS), self._h)
+        return dict(zip(("grid_x", "nseg", "threads", "lds_bytes", "passes", "per_thread"), (int(x) for x in out)))
+
+    def spectra_sample(self):
+        """one sample of the current state now (gcm_spectra_sample); the step counter is untouched.  A band: the ghost
+        rows of the current state must be current, as for climate_sample"""
+        _check(lib.gcm_spectra_sample(self._h), self._h)
+
+    def spectra_reset(self):
+        """zero the sums and the sample count (gcm_spectra_reset)"""
+        _check(lib.gcm_spectra_reset(self._h), self._h)
+
+    def spectra_sums(self):
+        """-> (n, s (6, L, H, M)): the raw float64 sums as the device holds them (gcm_get_spectra), M = spectra_mmax + 1;
+        one synchronisation"""
+        s = np.empty((_lib.SPEC_WORDS, self.L, self.H, self.spectra_mmax + 1))
+        n = C.c_int64()
+        _check(lib.gcm_get_spectra(self._h, _tab(s), C.byref(n)), self._h)
+        return int(n.value), s
+
+    def put_spectra(self, n, s):
+        """upload sums taken by spectra_sums() (gcm_put_spectra): a restart goes on where the run stopped"""
+        s = as_f64(s, (_lib.SPEC_WORDS, self.L, self.H, self.spectra_mmax + 1), "s")
+        _check(lib.gcm_put_spectra(self._h, _tab(s), int(n)), self._h)
+
+    def spectra(self):
+        """-> Spectra: the sample count and the one-sided spectra, the sums times w_m / (W^2 n) (gcm_get_spectra).
+        GcmError where no spectra are registered"""
+        n, s = self.spectra_sums()
+        return Spectra.from_sums(n, s, self.W)
 
     def utc(self):
         out = C.c_double()

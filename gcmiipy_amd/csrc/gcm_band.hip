@@ -292,7 +292,7 @@ static int run_deep_overlapped(gcm_handle *h, int nsteps, double dt) {
 //   run_pe, first exchange st                comm       st      pack -> ev_pack @ st, comm waits; group -> ev_comm @ comm, st waits
 //   run_pe, every stage    ax (pe25d: with   ax         ax      none per stage: stream order on ax.  When the run returns:
 //                          the edge rows)                       -> ev_comm @ ax, st waits
-//                                                               a step that ends with a climatology sample: -> ev_comm @ ax, st waits ahead of the sample
+//                                                               a step that ends with a climatology or spectra sample: -> ev_comm @ ax, st waits ahead of the sample
 //   .. boundary layer on   st (third exch.:  ax         ax      behind the corrector's unpack and the ghost rows' solar + Held-Suarez: -> ev_comm @ ax, st waits
 //      (third exchange)    the current                          ahead of the own rows' boundary layer; pack -> ev_pack @ st, ax waits; the ghost rows'
 //                          state's edge rows)                   convect + moist and their column sums follow the unpack on ax

@@ -1,6 +1,6 @@
 // GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (solar step, Held-Suarez forcing,
-// boundary layer, convective adjustment, moist physics, climatology sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
-// only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, boundary layer, convective adjustment, moist physics, climatology, the filter and the taps).
+// boundary layer, convective adjustment, moist physics, climatology sample, spectra sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
+// only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, boundary layer, convective adjustment, moist physics, climatology, spectra, the filter and the taps).
 // Host code only: a guard and one forwarding call into the pe25d_* units, through gcm_handle.h and pe25d_kernels.h.
 #include <cmath>
 
@@ -12,10 +12,10 @@ using namespace gcm;
 // ------------------------------------------------------------------ the phases of a step
 // The order is the model's: the dynamics step, the solar step at the current clock, utc += dt, the Held-Suarez forcing,
 // the boundary layer (on a band: then a third exchange of the edge rows), the convective adjustment, the moist physics,
-// the sample.  Each launch runs only if its phase is
+// the climatology's sample, the spectra's sample.  Each launch runs only if its phase is
 // registered: the solar step and the forcing in GcmPhases, the boundary layer, the adjustment and the moist physics where
 // their sums are in place (pe25d_sums_on),
-// the climatology in pe25d_climate_due.  The order is written down in pe_phase_rows, and in pe_phase_tables for what a
+// the climatology in pe25d_climate_due, the spectra in pe25d_spectra_due.  The order is written down in pe_phase_rows, and in pe_phase_tables for what a
 // run prepares ahead of it.
 
 // gcm_set_physics: the radiation kernel's tables in place before a run queues anything (no-op without physics); then the
@@ -115,25 +115,31 @@ int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax, int which) {
 // their pack by then (update_interior), so the rows that left are as the corrector made them and the neighbour forces
 // them itself.  Callers: gcm_step (g = 0), gcm_band_run, and gcm_end_step, gcm_end_step_begin and gcm_end_step_finish
 // for a caller that takes the dynamics step itself.  which: the whole walk, or one of the parts a band with the boundary
-// layer registered exchanges between (pe_phase_rows); the sample belongs to the tail.  tail: the stream whose tail the
+// layer registered exchanges between (pe_phase_rows); the samples (climatology, spectra) belong to the tail.  tail: the stream whose tail the
 // handle's stream joins before a sample, and before a band's boundary layer (gcm_band_run's second stream, where the
 // exchange runs and the ghost rows are forced there), else null
 int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail, int which) {
     if (int rc = pe_phase_rows(h, dt, -1, -g, h->H + g, 0, 0, keep_ghosts, true, h->stream, which, h->wrap ? nullptr : tail)) return rc;
     if (!(which & kPhasesTail)) return GCM_OK;
-    // gcm_set_climate: a sample of the state the step leaves, behind every phase that changes it
-    if (!pe25d_climate_due(h->pe)) return GCM_OK;
-    // a band: the sample reads the own rows as the phases above left them on the compute stream, and row -1 of v,
+    // gcm_set_climate, gcm_set_spectra: a sample of the state the step leaves, behind every phase that changes it.  Each
+    // diagnostic counts the step on a counter of its own
+    const bool clim = pe25d_climate_due(h->pe), spec = pe25d_spectra_due(h->pe);
+    if (!clim && !spec) return GCM_OK;
+    // a band: either sample reads the own rows as the phases above left them on the compute stream, and row -1 of v,
     // the first north ghost row, as the step's last exchange delivered it (the post-corrector exchange and the ghost
     // rows' Held-Suarez launch; with the boundary layer registered the third exchange) -- on the second stream where the
     // exchange runs there.  The compute stream joins that stream's tail first (the
-    // unpack, the ghost rows' physics, their column sums), on the steps that sample only; the event is gcm_band_run's own
-    // join event, which nobody else records between a run's first exchange and its end but the step itself, in stream order
+    // unpack, the ghost rows' physics, their column sums), on the steps that sample only, once for both samples; the event is
+    // gcm_band_run's own join event, which nobody else records between a run's first exchange and its end but the step itself,
+    // in stream order
     if (tail) {
         HIPCHK(h, hipEventRecord(h->band.ev_comm, tail));
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->band.ev_comm, 0));
     }
-    return pe25d_climate_sample(h->pe, h->stream, &h->err);
+    if (clim)
+        if (int rc = pe25d_climate_sample(h->pe, h->stream, &h->err)) return rc;
+    if (spec) return pe25d_spectra_sample(h->pe, h->stream, &h->err);
+    return GCM_OK;
 }
 
 // gcm_step of a GCM_PE25D handle (the caller has selected the device)
@@ -164,7 +170,7 @@ int gcm_pe25d_phase_plan(gcm_handle *h, int phase, int rows, int accumulate, int
 
 // ------------------------------------------------------------------ the end of a step whose dynamics the caller took itself
 // What gcm_band_run queues behind a corrector where the ghost rows ride with the own rows (GCM_BAND_COMM_STREAM=1): the
-// tables for dt, then every registered phase over own rows and ghost rows on the handle's stream, the clock, the sample.
+// tables for dt, then every registered phase over own rows and ghost rows on the handle's stream, the clock, the samples.
 // gcm_end_step is the whole walk; gcm_end_step_begin and gcm_end_step_finish are its two parts, for a band with the
 // boundary layer registered, which exchanges the current state's edge rows between them
 static int end_step_part(gcm_handle *h, double dt, const char *fn, int which) {
@@ -555,6 +561,53 @@ int gcm_moist_reset(gcm_handle *h) {
 
 int gcm_moist_saturation(int n, const double *T, const double *p_lev, double *q_s, double *dq_s, int *can) {
     return moist_saturation_table(n, T, p_lev, q_s, dq_s, can, &gcm_create_error());
+}
+
+// ------------------------------------------------------------------ zonal wavenumber spectra
+int gcm_set_spectra(gcm_handle *h, int every, int mmax) {
+    if (int rc = pe_only(h, "gcm_set_spectra")) return rc;
+    if (every < 0) return fail(h, GCM_ERR_ARG, "gcm_set_spectra: every must be >= 0");
+    if (int rc = select_device(h)) return rc;
+    return pe25d_set_spectra(h->pe, every, mmax, h->stream, &h->err);
+}
+
+int gcm_spectra_every(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_spectra_every(h->pe) : 0;
+}
+
+int gcm_spectra_mmax(const gcm_handle *h) {
+    if (int rc = pe_only(h, "gcm_spectra_mmax")) return rc;
+    const int mmax = pe25d_spectra_mmax(h->pe);
+    if (mmax < 0) return fail(const_cast<gcm_handle *>(h), GCM_ERR_STATE, "gcm_spectra_mmax: no spectra registered (gcm_set_spectra)");
+    return mmax;
+}
+
+int gcm_spectra_plan(gcm_handle *h, int *out, int nout) {
+    if (int rc = pe_only(h, "gcm_spectra_plan")) return rc;
+    if (int rc = pe25d_spectra_plan(h->pe, out, nout))
+        return fail(h, rc, "gcm_spectra_plan: a null pointer or fewer than GCM_SPEC_PLAN_WORDS words");
+    return GCM_OK;
+}
+
+int gcm_spectra_sample(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_spectra_sample")) return rc;
+    return pe25d_spectra_sample(h->pe, h->stream, &h->err);
+}
+
+int gcm_spectra_reset(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_spectra_reset")) return rc;
+    return pe25d_spectra_reset(h->pe, h->stream, &h->err);
+}
+
+int gcm_get_spectra(gcm_handle *h, double *s, int64_t *nsamples) {
+    if (int rc = pe_on_device(h, "gcm_get_spectra")) return rc;
+    return pe25d_get_spectra(h->pe, s, nsamples, h->stream, &h->err);
+}
+
+int gcm_put_spectra(gcm_handle *h, const double *s, int64_t nsamples) {
+    if (int rc = pe_on_device(h, "gcm_put_spectra")) return rc;
+    return pe25d_put_spectra(h->pe, s, nsamples, h->stream, &h->err);
 }
 
 // ------------------------------------------------------------------ zonal-mean climatology

@@ -8,6 +8,7 @@
 //   pe25d_tracers.hip  the passive tracers' host side
 //   pe25d_held_suarez.hip  the Held-Suarez forcing: its table routine, its kernel and its launches
 //   pe25d_climate.hip  the zonal-mean climatology: its kernel, its sums and their way to the host and back
+//   pe25d_spectra.hip  the zonal wavenumber spectra: their kernel, their sums and their way to the host and back
 //   pe25d_moist.hip    moist physics: the saturation routine, the kernel and its launches
 //   pe25d_convect.hip  convective adjustment: the pooling routine, the kernel and its launches
 //   pe25d_convect_tracers.hip  the tracers' convective mixing in the adjustment's blocks: the kernel, its launch, the opt-ins
@@ -15,7 +16,8 @@
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
 // gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
-// pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample).
+// pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample,
+// pe25d_spectra_due, pe25d_spectra_sample).
 #pragma once
 #include "pe25d_kernels.h"
 
@@ -108,6 +110,15 @@ struct PeHeldSuarez {
 struct PeClimate {
     double *buf = nullptr;                      // device: sig [L], m3 [GCM_CLIM_WORDS3][L][H], m2 [GCM_CLIM_WORDS2][H]
     int every = 0;                              // a sample every so many steps; 0: not registered
+    long long steps = 0;                        // steps taken by gcm_step / gcm_band_run since the registration
+    long long n = 0;                            // samples in the sums
+};
+
+// Zonal wavenumber spectra (pe25d_spectra.hip, gcm_set_spectra): the float64 twiddles and sums on the device and the counters
+struct PeSpectra {
+    double *buf = nullptr;                      // device: tw [W] double2, sig [L], s [GCM_SPEC_WORDS][L][H][mmax + 1]
+    int every = 0;                              // a sample every so many steps; 0: not registered
+    int mmax = 0;                               // the highest wavenumber in the sums
     long long steps = 0;                        // steps taken by gcm_step / gcm_band_run since the registration
     long long n = 0;                            // samples in the sums
 };
@@ -228,6 +239,7 @@ struct Pe25d {
     PeTracers tr;
     PeHeldSuarez hs;
     PeClimate clim;
+    PeSpectra spec;
     PeMoist moist;
     PeConvect convect;
     PeBoundary boundary;

@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
+// pe25d_climate.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +65,18 @@ int pe25d_climate_sample(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_climate_reset(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_get_climate(Pe25d *m, double *m3, double *m2, int64_t *nsamples, hipStream_t s, std::string *err);
 int pe25d_put_climate(Pe25d *m, const double *m3, const double *m2, int64_t nsamples, hipStream_t s, std::string *err);
+// Zonal wavenumber spectra (pe25d_spectra.hip): gcm_set_spectra and its companions on `s`, the caller's stream.
+// pe25d_spectra_due: counts one step, as pe25d_climate_due does; pe25d_spectra_mmax: -1 without a registration;
+// pe25d_spectra_plan: gcm_spectra_plan
+int pe25d_set_spectra(Pe25d *m, int every, int mmax, hipStream_t s, std::string *err);
+int pe25d_spectra_every(const Pe25d *m);
+int pe25d_spectra_mmax(const Pe25d *m);
+bool pe25d_spectra_due(Pe25d *m);
+int pe25d_spectra_plan(const Pe25d *m, int *out, int nout);
+int pe25d_spectra_sample(Pe25d *m, hipStream_t s, std::string *err);
+int pe25d_spectra_reset(Pe25d *m, hipStream_t s, std::string *err);
+int pe25d_get_spectra(Pe25d *m, double *sums, int64_t *nsamples, hipStream_t s, std::string *err);
+int pe25d_put_spectra(Pe25d *m, const double *sums, int64_t nsamples, hipStream_t s, std::string *err);
 // The column sums of the convective adjustment (count, levels), of the moist physics (precip, evap) and of the boundary
 // layer (shf, evap), one set of routines for all (pe25d_state.hip), on `s`, the caller's stream.  pe25d_sums_set: allocated and zeroed (on) or freed;
 // a phase is registered where its sums are in place, and pe25d_sums_on is the one place that says so.  reset, get and

@@ -747,7 +747,8 @@ int gcm_convect_columns(int ncol, int L, const double *y, const double *w, const
  *   3. the boundary layer on the own rows;                                   |
  *   4. the third exchange: pack / send and receive / unpack of the current state;
  *   5. convective adjustment and moist physics on own rows and ghost rows;   | gcm_end_step_finish
- *   6. the climatology's sample, which reads v of ghost row -1.              |
+ *   6. the climatology's sample, then the spectra's; both read v of ghost    |
+ *      row -1.                                                              |
  * gcm_band_run queues all six (the exchange and the ghost rows' launches beside the own rows' convective adjustment
  * and moist physics on its second stream).  A host that drives the exchange itself calls gcm_end_step_begin, moves the
  * ghost rows, then gcm_end_step_finish; gcm_end_step on such a band is GCM_ERR_STATE and changes nothing.  The third
@@ -842,11 +843,70 @@ int gcm_climate_sample(gcm_handle *h);
 int gcm_climate_reset(gcm_handle *h);
 int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples);
 int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples);
+/* Zonal wavenumber spectra of GCM_PE25D accumulated on the device: the kinetic-energy and temperature spectra by zonal
+ * wavenumber and the split of the eddy momentum and heat fluxes over the waves, which the zonal sums of the climatology
+ * cannot give, without a host round trip per step (fp64 and fp32 handles, single domains and latitude bands).  One launch
+ * per sample reads the current state once.  For every own row j and level k it forms four real rows of length W in
+ * float64 -- storage values widened exactly, every product and sum float64 and rounded on its own (no contraction):
+ *   uc = 0.5 (u[i] + u[i - 1]), periodic in i;   vc = 0.5 (v[j] + v[j - 1]);   theta;   T = theta Pi(sig[k] p + ptop)
+ *   Row -1 is the climatology's: row H - 1 on a single domain, the first north ghost row of v on a band.  Pi comes from
+ *   the kernels' own Exner routine (within the 1e-10 of the parity tests of pow).
+ * Their discrete Fourier transforms along i, X_m = sum_i x_i exp(-2 pi i m i / W) (NumPy's convention), are taken in
+ * float64 on every handle, with a float64 twiddle table of the registration's own (W entries, built on the host from
+ * angles reduced to an octant in integers).  For m = 0 .. mmax the launch adds the raw products to float64 sums
+ *   s [GCM_SPEC_WORDS][L][H][M],  M = mmax + 1, m the fastest index:
+ *   0 uu = |Uc|^2   1 vv = |Vc|^2   2 TT = |That|^2   3 uv = Re(Uc conj Vc)   4 vT = Re(Vc conj That)
+ *   5 vtheta = Re(Vc conj Thetahat)
+ * Plain sums over the samples; nothing is divided on the device.  Words 3 - 5 are the wavenumber split of the
+ * climatology's words 7 - 9, word 2 that of its word 6: with mmax = W / 2 and the one-sided weights w_m = 1 for m = 0 and
+ * m = W / 2 (even W), w_m = 2 otherwise, sum_m w_m s[word][m] / W is the corresponding zonal sum up to rounding.  The
+ * one-sided spectrum per sample is w_m s / (W W nsamples): a row's entries then sum to the zonal mean of the product.
+ * How it is computed: per level two complex transforms in LDS, z1 = uc + i vc and z2 = T + i theta (the mixed-radix
+ * Stockham passes of the polar filter's generic path, the radices of W in the order 4s, 2s, odd primes
+ * ascending); the packed rows come apart as X_m = (Z_m + conj Z_{W-m}) / 2, Y_m = (Z_m - conj Z_{W-m}) / (2i), index
+ * W - m at m = 0 taken as 0.  A product is Re(A conj B) = A.re B.re + A.im B.im.
+ * Determinism: each accumulator word has one writer per launch, no atomics.  What a row contributes depends on that
+ * row's data, W and mmax only -- not on H, the band, the CU count or how levels are split over the grid; the transform's
+ * path is chosen from W alone.  The same state gives the same bits, and a band's rows hold the bits of the same rows of
+ * the single domain.
+ * gcm_set_spectra(every >= 1, mmax) allocates and zeroes the sums and the sample count and starts a step counter of the
+ * spectra's own at 0; mmax = -1: min(W / 2, 63).  From then on every step taken by gcm_step, gcm_band_run and
+ * gcm_end_step / gcm_end_step_finish ends -- directly behind the climatology's sample where that is due -- with a
+ * sample where the counter, incremented per step, is a multiple of `every`.  The counter runs across calls.  On a band
+ * the compute stream joins the exchange stream's tail before the sample, once for both diagnostics.  gcm_half_step and
+ * gcm_step_phase never sample.  Registering again resets the sums and the counters; every = 0 unregisters and frees.
+ * Without a registration nothing is launched and every result and timing is as before; a sample changes nothing a step
+ * reads.  A registration holds 8 (2 W + L + GCM_SPEC_WORDS L H M) bytes on the device: 53.1 MB at 1440 x 720 x 24 with
+ * the default mmax.  The launch takes 32 W + 8 W + 2048 bytes of LDS (W odd: 8 more).
+ * gcm_spectra_every: the registered `every`, 0 without one (other models: 0; a null handle GCM_ERR_ARG).
+ * gcm_spectra_mmax: the registered mmax; GCM_ERR_STATE without a registration.
+ * gcm_spectra_sample: one sample now; the step counter is untouched.  On a band the ghost rows of the current state
+ * must be current.  gcm_spectra_reset zeroes the sums and the count.  gcm_get_spectra synchronises the handle's stream
+ * once and copies the sums and the count; either pointer may be NULL.  gcm_put_spectra uploads them (restarts): s is
+ * required, nsamples >= 0.
+ * gcm_spectra_plan: the launch geometry of a sample of this handle, without launching, GCM_SPEC_PLAN_WORDS words:
+ *   [0] grid x = rows  [1] level segments (grid y)  [2] threads  [3] LDS bytes  [4] passes of a transform
+ *   [5] wavenumbers a thread holds (at the registered mmax, else at the default)
+ * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, every < 0, mmax < -1 or
+ * mmax > W / 2.  GCM_ERR_UNSUPPORTED: other models, and a row whose transform buffers do not fit the 160 KB of LDS a
+ * launch may ask for (W > 4044; the message states the width).  GCM_ERR_STATE: get, put, reset, sample or mmax without
+ * a registration.  GCM_ERR_HIP: an allocation that fails; nothing stays registered then.                          */
+#define GCM_SPEC_WORDS 6        /* products per (level, row, wavenumber) */
+#define GCM_SPEC_PLAN_WORDS 6
+int gcm_set_spectra(gcm_handle *h, int every, int mmax);
+int gcm_spectra_every(const gcm_handle *h);
+int gcm_spectra_mmax(const gcm_handle *h);
+int gcm_spectra_plan(gcm_handle *h, int *out, int nout);
+int gcm_spectra_sample(gcm_handle *h);
+int gcm_spectra_reset(gcm_handle *h);
+int gcm_get_spectra(gcm_handle *h, double *s, int64_t *nsamples);
+int gcm_put_spectra(gcm_handle *h, const double *s, int64_t nsamples);
 /* The end of a GCM_PE25D step whose dynamics the caller took itself: everything gcm_step and gcm_band_run queue behind
  * the corrector, in their order and by their code -- the solar step at the handle's clock, utc += dt, the Held-Suarez
  * forcing, the boundary layer, the convective adjustment, the moist physics (their sums, seconds and
  * nsteps advance as in gcm_step), the
- * climatology's step counter and its sample where one is due -- each only if registered, on the handle's stream.  With
+ * climatology's step counter and its sample where one is due, then the spectra's step counter and sample (gcm_set_spectra)
+ * -- each only if registered, on the handle's stream.  With
  * nothing registered it queues nothing.  On a single domain gcm_half_step(h, 0, dt), gcm_half_step(h, 1, dt),
  * gcm_end_step(h, dt) is gcm_step(h, 1, dt).  On a latitude band it ends a step driven through gcm_step_phase or
  * gcm_step_interior / gcm_step_boundary and the caller's own exchange: the launches take the ghost rows with the own
@@ -856,7 +916,7 @@ int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t n
  * gcm_end_step_begin and gcm_end_step_finish are its two parts, split behind the boundary layer.  begin: the tables for
  * dt, the solar step (the clock advances once), the Held-Suarez forcing over own rows and ghost rows, the boundary layer
  * (a band: over its own rows).  finish: the convective adjustment and the moist physics over own rows and ghost rows,
- * the climatology's step counter and sample.  On every handle begin followed by finish, with the same dt, is
+ * the climatology's step counter and sample, the spectra's step counter and sample.  On every handle begin followed by finish, with the same dt, is
  * gcm_end_step.  A band with the boundary layer registered (gcm_set_band_boundary_layer) moves the ghost rows of the
  * current state between the two -- gcm_halo_pack2, the transfer, gcm_halo_unpack2 -- and gcm_end_step itself refuses such
  * a band (GCM_ERR_STATE, the message names the two calls); on a single domain, or a band without the phase, nothing
