@@ -22,6 +22,8 @@ TRACER_STATS_WORDS = 6               # GCM_TRACER_STATS_WORDS
 CLIM_WORDS3, CLIM_WORDS2 = 10, 2     # GCM_CLIM_WORDS3, GCM_CLIM_WORDS2
 SPEC_WORDS = 6                       # GCM_SPEC_WORDS
 SPEC_PLAN_WORDS = 6                  # GCM_SPEC_PLAN_WORDS
+HDIFF_U, HDIFF_V, HDIFF_T, HDIFF_Q = 1, 2, 4, 8     # GCM_HDIFF_*
+HDIFF_PLAN_WORDS = 7                 # GCM_HDIFF_PLAN_WORDS
 SW2D_PLAN_WORDS = 9                  # GCM_SW2D_PLAN_WORDS
 PHASE_HELD_SUAREZ, PHASE_MOIST, PHASE_CLIMATE, PHASE_TRACER_FORCING = range(4)   # gcm_pe25d_phase
 PHASE_PLAN_WORDS = 5                 # GCM_PHASE_PLAN_WORDS
@@ -83,6 +85,11 @@ class HeldSuarez(C.Structure):
     _fields_ = [("k_f", C.c_double), ("k_a", C.c_double), ("k_s", C.c_double), ("sigma_b", C.c_double),
                 ("dT_y", C.c_double), ("dtheta_z", C.c_double), ("T_0", C.c_double), ("T_min", C.c_double),
                 ("lat", _dp)]
+
+
+class Hdiff(C.Structure):
+    """gcm_hdiff of include/gcmcore.h"""
+    _fields_ = [("order", C.c_int32), ("fields", C.c_int32), ("nu", C.c_double), ("cmax", C.c_double)]
 
 
 class Moist(C.Structure):
@@ -151,6 +158,12 @@ SYMBOLS = {
     "gcm_held_suarez_on": (C.c_int, [_H]),
     "gcm_held_suarez_step": (C.c_int, [_H, C.c_double, C.POINTER(HeldSuarez)]),
     "gcm_held_suarez_tables": (C.c_int, [C.c_int, _dp, C.c_int, _dp, C.POINTER(HeldSuarez), C.c_double, _dp, _dp, _dp, _dp]),
+    "gcm_set_hdiff": (C.c_int, [_H, C.POINTER(Hdiff)]),
+    "gcm_hdiff_on": (C.c_int, [_H]),
+    "gcm_hdiff_step": (C.c_int, [_H, C.c_double, C.POINTER(Hdiff)]),
+    "gcm_hdiff_tables": (C.c_int, [C.c_int, _dp, _dp, C.c_double, C.POINTER(Hdiff), C.c_double, _dp]),
+    "gcm_hdiff_apply": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
+    "gcm_hdiff_plan": (C.c_int, [_H, C.POINTER(C.c_int), C.c_int]),
     "gcm_set_moist": (C.c_int, [_H, C.POINTER(Moist)]),
     "gcm_moist_on": (C.c_int, [_H]),
     "gcm_moist_step": (C.c_int, [_H, C.c_double, C.POINTER(Moist)]),

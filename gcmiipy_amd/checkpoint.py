@@ -19,7 +19,9 @@ re-registered on restore; files without the key restore with none; the zonal-mea
 stored as "climate_every", "climate_n", "climate_m3" and "climate_m2", the interval, the sample count and the raw
 float64 sums, registered and uploaded again on restore; files without these keys restore without a climatology; the
 zonal wavenumber spectra, Core.set_spectra, are stored as "spectra_every", "spectra_mmax", "spectra_n" and "spectra_s",
-saved and restored the same way, and files without these keys restore with none; the
+saved and restored the same way, and files without these keys restore with none; the horizontal diffusion,
+Core.set_horizontal_diffusion, is stored as "hdiff" = [order, fields, nu, cmax] and registered again on restore, ahead of
+the first step, and files without the key restore with none; the
 moist physics, Core.set_moist, is stored as "moist", its three parameters in the order of core.MOIST_DEFAULTS, with
 "moist_n", "moist_seconds", "moist_precip" and "moist_evap", the count, the seconds and the raw float64 sums, registered
 and uploaded again on restore; files without these keys restore with none; the convective adjustment, Core.set_convect,
@@ -34,7 +36,7 @@ ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
 import numpy as np
 
 from . import _lib
-from .core import COLUMN_PHASES, Core, GcmError, HELD_SUAREZ_DEFAULTS
+from .core import COLUMN_PHASES, Core, GcmError, HDIFF_DEFAULTS, HELD_SUAREZ_DEFAULTS
 from .geometry import Geom
 
 _GEOM_KEYS = ("sige", "sigt", "sigb", "dsig", "sig", "dsigv", "dx_j", "dx_h", "dy", "ptop",
@@ -77,6 +79,9 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
         n, s = core.spectra_sums()
         out.update(spectra_every=np.int64(core.spectra_every), spectra_mmax=np.int64(core.spectra_mmax), spectra_n=np.int64(n),
                    spectra_s=s)
+    hd = getattr(core, "horizontal_diffusion", None) if core.model == _lib.PE25D else None   # (getattr: as above)
+    if hd is not None:
+        out["hdiff"] = np.asarray([hd[k] for k in HDIFF_DEFAULTS], dtype=np.float64)
     # (a core is asked only for the phases it knows: getattr, so that a stand-in without one of them will do; reversed:
     # the files have always held the moist physics' keys ahead of the convective adjustment's; the boundary layer's follow)
     for ph in reversed(COLUMN_PHASES if core.model == _lib.PE25D else ()):
@@ -103,11 +108,12 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, tracer_convect, held_suarez, climate, spectra, moist, convect, boundary_layer, band_boundary_layer); ground and
+    tracer_mixing, tracer_convect, held_suarez, hdiff, climate, spectra, moist, convect, boundary_layer, band_boundary_layer); ground and
     tracers are
     None where the file has none, tracer_forcing
     {i: dict(...)} and tracer_mixing {i: K} are then empty, and so is tracer_convect, the list of the tracers that have
-    opted in to the convective mixing (files without the key: none); held_suarez is (parameters dict, lat) or None; climate is
+    opted in to the convective mixing (files without the key: none); held_suarez is (parameters dict, lat) or None; hdiff is
+    dict(order, fields, nu, cmax) or None (files without the key: None); climate is
     dict(every, n, m3, m2) or None; spectra is dict(every, mmax, n, s) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
     dict(params, n, seconds, count, levels) or None; boundary_layer is dict(params, n, seconds, shf, evap) or None;
     band_boundary_layer is whether a band takes that phase (False for files without the option)"""
@@ -141,6 +147,10 @@ def load(path):
     hs = None
     if "held_suarez" in d.files:
         hs = (dict(zip(HELD_SUAREZ_DEFAULTS, (float(x) for x in d["held_suarez"]))), d["held_suarez_lat"])
+    hd = None
+    if "hdiff" in d.files:
+        order, fields, nu, cmax = d["hdiff"]
+        hd = dict(order=int(order), fields=int(fields), nu=float(nu), cmax=float(cmax))
     clim = None
     if "climate_every" in d.files:
         clim = dict(every=int(d["climate_every"]), n=int(d["climate_n"]), m3=d["climate_m3"], m2=d["climate_m2"])
@@ -155,7 +165,7 @@ def load(path):
             column[ph.name] = dict(params=par, n=int(d[ph.name + "_n"]), seconds=float(d[ph.name + "_seconds"]),
                                    **{f: d["%s_%s" % (ph.name, f)] for f in ph.fields})
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, climate=clim,
-                spectra=spec,
+                spectra=spec, hdiff=hd,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
@@ -187,6 +197,8 @@ def restore(path, **core_kwargs):
             core.set_tracer_convection(i)
     if ck["held_suarez"] is not None:
         core.set_held_suarez(ck["held_suarez"][1], **ck["held_suarez"][0])
+    if ck["hdiff"] is not None:
+        core.set_horizontal_diffusion(**ck["hdiff"])
     if ck["climate"] is not None:
         core.set_climate(ck["climate"]["every"])
         core.put_climate(ck["climate"]["n"], ck["climate"]["m3"], ck["climate"]["m2"])

@@ -237,6 +237,78 @@ def _held_suarez_record(lat, params):
     return rec, lat, par
 
 
+# the parameters of the horizontal diffusion (gcm_hdiff), in the order the checkpoint stores them.  nu: m^4/s at order 2,
+# m^2/s at order 1; fields: a string of the letters u v t q, or the mask of HDIFF_FIELD_BITS
+HDIFF_DEFAULTS = collections.OrderedDict(order=2, fields="uvt", nu=1.0e15, cmax=0.125)
+HDIFF_FIELD_BITS = collections.OrderedDict(u=1, v=2, t=4, q=8)       # GCM_HDIFF_U, _V, _T, _Q
+
+
+def hdiff_params(params):
+    """the four parameters of the horizontal diffusion as a dict (order int, fields the int mask, nu, cmax floats):
+    HDIFF_DEFAULTS with `params` laid over them; ValueError for a name that is not a parameter and for a `fields` that
+    is neither a string of the letters u v t q nor an int"""
+    unknown = sorted(set(params) - set(HDIFF_DEFAULTS))
+    if unknown:
+        raise ValueError("horizontal_diffusion: unknown parameter(s) %s; the parameters are %s"
+                         % (", ".join(unknown), ", ".join(HDIFF_DEFAULTS)))
+    out = collections.OrderedDict(HDIFF_DEFAULTS)
+    out.update(params)
+    fields = out["fields"]
+    if isinstance(fields, str):
+        bad = sorted(set(fields) - set(HDIFF_FIELD_BITS))
+        if bad or not fields:
+            raise ValueError("horizontal_diffusion: fields must be a non-empty string of the letters u v t q, got %r" % (fields,))
+        mask = 0
+        for c in fields:
+            mask |= HDIFF_FIELD_BITS[c]
+        fields = mask
+    elif isinstance(fields, (bool, float)) or not isinstance(fields, (int, np.integer)):
+        raise ValueError("horizontal_diffusion: fields must be a string of the letters u v t q or the int mask, got %r" % (fields,))
+    if int(out["order"]) != out["order"]:
+        raise ValueError("horizontal_diffusion: order must be 1 or 2, got %r" % (out["order"],))
+    return collections.OrderedDict(order=int(out["order"]), fields=int(fields), nu=float(out["nu"]), cmax=float(out["cmax"]))
+
+
+def _hdiff_record(params):
+    """-> (gcm_hdiff, the parameters as a dict)"""
+    par = hdiff_params(params)
+    return _lib.Hdiff(par["order"], par["fields"], par["nu"], par["cmax"]), par
+
+
+HDIFF_TABLES = ("ax", "bn", "bs", "area", "axv", "bnv", "bsv", "areav")      # the rows of gcm_hdiff_tables' out
+
+
+def hdiff_tables(geom, dt, **params):
+    """the host tables of the horizontal diffusion (gcm_hdiff_tables; no handle, no device) for the geometry's dx_j,
+    dx_h (H,) and dy and the step dt -> dict of the (H,) arrays ax, bn, bs, area (centre rows: theta, q, u) and axv,
+    bnv, bsv, areav (v rows): the routine the launches of Core.set_horizontal_diffusion / Core.horizontal_diffusion_step
+    take their tables from.  ValueError for a refused parameter"""
+    dx_j = as_f64(np.asarray(geom.dx_j, dtype=np.float64).reshape(-1), name="dx_j")
+    dx_h = as_f64(np.asarray(geom.dx_h, dtype=np.float64).reshape(-1), (dx_j.size,), "dx_h")
+    rec, _ = _hdiff_record(params)
+    out = np.empty((len(HDIFF_TABLES), dx_j.size))
+    _check(lib.gcm_hdiff_tables(dx_j.size, _tab(dx_j), _tab(dx_h), float(geom.dy), C.byref(rec), float(dt), _tab(out)))
+    return dict(zip(HDIFF_TABLES, out))
+
+
+def hdiff_apply(X, ax, bn, bs, order):
+    """one application of the horizontal diffusion to X (nlev, H, W) or (H, W) on the host in float64, periodic both
+    ways, with the rows' coefficients ax, bn, bs (H,) (gcm_hdiff_apply: the host build of the cell routine the kernel
+    calls; no handle, no device) -> the array of X's shape.  order 1: X + D(X); order 2: X - D(D(X)).  ValueError for
+    a refused argument"""
+    X = as_f64(X, name="X")
+    if X.ndim not in (2, 3):
+        raise ValueError("X has shape %s, expected (nlev, H, W) or (H, W)" % (X.shape,))
+    H, W = X.shape[-2:]
+    nlev = X.shape[0] if X.ndim == 3 else 1
+    tab = np.zeros((4, H))
+    for n, (a, name) in enumerate(zip((ax, bn, bs), ("ax", "bn", "bs"))):
+        tab[n] = as_f64(np.asarray(a, dtype=np.float64).reshape(-1), (H,), name)
+    out = np.empty_like(X)
+    _check(lib.gcm_hdiff_apply(H, W, nlev, _tab(tab), int(order), _tab(X), _tab(out)))
+    return out
+
+
 def held_suarez_tables(sig, lat, dt, **params):
     """the host tables of the Held-Suarez forcing (gcm_held_suarez_tables; no handle, no device) for the mid-level
     sigmas `sig` (L,), the latitudes `lat` (n,) in radians and the step dt -> dict(fu (L,), kt (L, n), s2 (n,), c2 (n,)):
@@ -534,6 +606,7 @@ class Core:
         self._forcing = {}                      # tracer -> the forcing record registered (set_tracer_forcing)
         self._mixing = {}                       # tracer -> the profile K registered (set_tracer_mixing)
         self._held_suarez = None                # the parameters and latitudes registered (set_held_suarez)
+        self._hdiff = None                      # the parameters registered (set_horizontal_diffusion)
         self._column = {}                       # the parameters registered (set_boundary_layer, set_convect, set_moist), by the phase's name
         cfg = _lib.Config()
         cfg.abi_version = _lib.ABI_VERSION
@@ -1003,6 +1076,46 @@ class Core:
     def held_suarez_lat(self):
         """the latitudes (global_height,) the registered Held-Suarez forcing was given, or None"""
         return self._held_suarez[1].copy() if self.held_suarez is not None else None
+
+    # -- horizontal diffusion (GCM_PE25D, single domains) ---------------------------------
+    def set_horizontal_diffusion(self, *off, **params):
+        """every step of step() / end_step() from now on applies a del-2 (order=1) or del-4 (order=2) horizontal diffusion
+        of the selected fields on the device (gcm_set_hdiff), once per step, directly behind the Matsuno step and ahead
+        of solar_timestep, on sigma surfaces, level by level, u and v component-wise.  half_step never applies it.
+        params: order, fields (a string of the letters u v t q, or the mask), nu (m^2/s at order 1, m^4/s at order 2),
+        cmax (the cap of the diffusion numbers, in (0, 1/8]); HDIFF_DEFAULTS.  set_horizontal_diffusion(None) switches
+        the phase off.  ValueError for an unknown keyword or a refused value, GcmError for a latitude band and for a grid
+        with W or H below 4 (the call then changes nothing)"""
+        if off:
+            if off != (None,) or params:
+                raise ValueError("set_horizontal_diffusion takes keyword parameters, or None alone to switch the phase off")
+            _check(lib.gcm_set_hdiff(self._h, None), self._h)
+            self._hdiff = None
+            return
+        rec, par = _hdiff_record(params)
+        _check(lib.gcm_set_hdiff(self._h, C.byref(rec)), self._h)
+        self._hdiff = dict(par)
+
+    def horizontal_diffusion_step(self, dt, **params):
+        """the horizontal diffusion once, in place on the current state, with the step dt (gcm_hdiff_step), without a
+        registration: what held_suarez_step is to set_held_suarez"""
+        rec, _ = _hdiff_record(params)
+        _check(lib.gcm_hdiff_step(self._h, float(dt), C.byref(rec)), self._h)
+
+    @property
+    def horizontal_diffusion(self):
+        """the parameters of the registered horizontal diffusion as a dict (order, fields as the mask, nu, cmax), or
+        None where the handle carries none (gcm_hdiff_on) -- and also None for one registered through the C call directly"""
+        on = _count(lib.gcm_hdiff_on(self._h), self._h)
+        return dict(self._hdiff) if on and self._hdiff else None
+
+    def horizontal_diffusion_plan(self):
+        """the launch geometry of the horizontal diffusion of this handle, without launching (gcm_hdiff_plan), at the
+        registered order and fields, else at order 2 and "uvt": tile_rows, tile_cols, tiles_i, tiles_j, grid_z (selected
+        fields x levels), lds_bytes, launches (kernel launches per application)"""
+        out = (C.c_int * _lib.HDIFF_PLAN_WORDS)()
+        _check(lib.gcm_hdiff_plan(self._h, out, _lib.HDIFF_PLAN_WORDS), self._h)
+        return dict(zip(("tile_rows", "tile_cols", "tiles_i", "tiles_j", "grid_z", "lds_bytes", "launches"), (int(x) for x in out)))
 
     # -- the phases with per-column sums (GCM_PE25D): one implementation for both, by their _ColumnPhase --------------
     def _set_column(self, ph, off, params):

@@ -1,6 +1,6 @@
-// GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (solar step, Held-Suarez forcing,
+// GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (horizontal diffusion, solar step, Held-Suarez forcing,
 // boundary layer, convective adjustment, moist physics, climatology sample, spectra sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
-// only (tracers, step phases and halo buffers, ground and physics, Held-Suarez, boundary layer, convective adjustment, moist physics, climatology, spectra, the filter and the taps).
+// only (tracers, step phases and halo buffers, ground and physics, horizontal diffusion, Held-Suarez, boundary layer, convective adjustment, moist physics, climatology, spectra, the filter and the taps).
 // Host code only: a guard and one forwarding call into the pe25d_* units, through gcm_handle.h and pe25d_kernels.h.
 #include <cmath>
 
@@ -10,20 +10,23 @@
 using namespace gcm;
 
 // ------------------------------------------------------------------ the phases of a step
-// The order is the model's: the dynamics step, the solar step at the current clock, utc += dt, the Held-Suarez forcing,
+// The order is the model's: the dynamics step, the horizontal diffusion (a single domain's only), the solar step at the
+// current clock, utc += dt, the Held-Suarez forcing,
 // the boundary layer (on a band: then a third exchange of the edge rows), the convective adjustment, the moist physics,
 // the climatology's sample, the spectra's sample.  Each launch runs only if its phase is
-// registered: the solar step and the forcing in GcmPhases, the boundary layer, the adjustment and the moist physics where
+// registered: the diffusion in pe25d_hdiff_on, the solar step and the forcing in GcmPhases, the boundary layer, the adjustment and the moist physics where
 // their sums are in place (pe25d_sums_on),
 // the climatology in pe25d_climate_due, the spectra in pe25d_spectra_due.  The order is written down in pe_phase_rows, and in pe_phase_tables for what a
 // run prepares ahead of it.
 
-// gcm_set_physics: the radiation kernel's tables in place before a run queues anything (no-op without physics); then the
-// registered forcing's device tables for dt (none: GCM_OK), the boundary layer's level tables, scratch fields and parameters
+// The registered diffusion's device tables and landing fields for dt; gcm_set_physics: the radiation kernel's tables in
+// place before a run queues anything (no-op without physics); then the registered forcing's device tables for dt (none: GCM_OK), the boundary layer's level tables, scratch fields and parameters
 // for dt, and the convective adjustment's and the moist physics' level tables and parameters for dt.  Both parts of a
 // split walk (gcm_end_step_begin, gcm_end_step_finish) call it: what is in place for dt already is not built again
 int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
     const GcmPhases &ph = h->phases;
+    if (nsteps > 0 && pe25d_hdiff_on(h->pe))
+        if (int rc = pe25d_hdiff_tables(h->pe, pe25d_hdiff_par(h->pe), dt, h->stream, &h->err)) return rc;
     if (ph.solar)
         if (int rc = pe25d_physics_tables(h->pe, ph.phys.t_lw, ph.phys.t_sw, ph.phys_lat.data(), ph.phys_lon.data(), h->stream, &h->err))
             return rc;
@@ -67,6 +70,13 @@ static int pe_phase_rows(gcm_handle *h, double dt, int set, int j0, int j1, int 
     if (which == kPhasesAll && band_boundary_layer_on(h))
         return fail(h, GCM_ERR_STATE, "boundary layer on a latitude band: the phase walk splits at it, with an exchange of the current state between the two parts");
     if (which & kPhasesHead) {
+        // gcm_set_hdiff, directly behind the Matsuno step: every row of a single domain (a band cannot register it).  The
+        // launch writes u and v, as the forcing's does (pe25d_phase_wrote)
+        if (own && h->wrap && pe25d_hdiff_on(h->pe)) {
+            if (j0 != 0 || j1 != h->H || jb1 > jb0)
+                return fail(h, GCM_ERR_STATE, "horizontal diffusion: the phase walk of a single domain's own rows only");
+            if (int rc = pe25d_hdiff_rows(h->pe, set, keep_ghosts, s, &h->err)) return rc;
+        }
         if (ph.solar) {
             // no_limits_2_5d.py:229-234 with the physics below full_timestep's early return (:96): the dynamics step, then
             // solar_timestep (:66-75) at the current utc, which changes theta and the ground temperature in place AFTER the
@@ -345,6 +355,46 @@ int gcm_solar_step(gcm_handle *h, double dt, double utc, double t_lw, double t_s
     if (int rc = pe_only(h, "gcm_solar_step")) return rc;
     return pe25d_radiation(h->pe, true, dt, utc, t_lw, t_sw, albedo, lat, lon, nullptr, nullptr,
                            h->stream, &h->err);
+}
+
+// ------------------------------------------------------------------ horizontal diffusion
+// a latitude band, W or H below 4: refused in the call itself
+int gcm_set_hdiff(gcm_handle *h, const gcm_hdiff *d) {
+    if (int rc = pe_only(h, "gcm_set_hdiff")) return rc;
+    if (int rc = select_device(h)) return rc;
+    return pe25d_set_hdiff(h->pe, d, h->stream, &h->err);
+}
+
+int gcm_hdiff_on(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && pe25d_hdiff_on(h->pe) ? 1 : 0;
+}
+
+int gcm_hdiff_step(gcm_handle *h, double dt, const gcm_hdiff *d) {
+    if (int rc = pe_only(h, "gcm_hdiff_step")) return rc;
+    if (int rc = hdiff_check(d, "gcm_hdiff_step", &h->err)) return rc;
+    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_hdiff_step: dt must be finite");
+    if (int rc = pe25d_hdiff_fits(h->pe, "gcm_hdiff_step", &h->err)) return rc;
+    if (int rc = select_device(h)) return rc;
+    // without a registration the call allocates the landing fields itself; the handle keeps them for the next such call,
+    // until gcm_set_hdiff(NULL) or gcm_destroy
+    if (int rc = pe25d_hdiff_tables(h->pe, d, dt, h->stream, &h->err)) return rc;
+    return pe25d_hdiff_rows(h->pe, -1, false, h->stream, &h->err);
+}
+
+int gcm_hdiff_tables(int H, const double *dx_j, const double *dx_h, double dy, const gcm_hdiff *d, double dt, double *out) {
+    return hdiff_tables(H, dx_j, dx_h, dy, d, dt, out, &gcm_create_error());
+}
+
+int gcm_hdiff_apply(int H, int W, int nlev, const double *tab4, int order, const double *X, double *out) {
+    return hdiff_apply(H, W, nlev, tab4, order, X, out, &gcm_create_error());
+}
+
+int gcm_hdiff_plan(gcm_handle *h, int *out, int nout) {
+    if (int rc = pe_only(h, "gcm_hdiff_plan")) return rc;
+    if (int rc = pe25d_hdiff_plan(h->pe, out, nout))
+        return fail(h, rc, "gcm_hdiff_plan: a null pointer or fewer than GCM_HDIFF_PLAN_WORDS words");
+    return GCM_OK;
 }
 
 // ------------------------------------------------------------------ Held-Suarez forcing

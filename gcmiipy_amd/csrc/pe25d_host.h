@@ -13,10 +13,11 @@
 //   pe25d_convect.hip  convective adjustment: the pooling routine, the kernel and its launches
 //   pe25d_convect_tracers.hip  the tracers' convective mixing in the adjustment's blocks: the kernel, its launch, the opt-ins
 //   pe25d_boundary_layer.hip  surface fluxes and boundary-layer mixing: the routines, the two kernels and their launches
+//   pe25d_hdiff.hip    horizontal diffusion: the table and cell routines, the tile kernel, its launch and landing fields
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
 // gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
-// pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample,
+// pe25d_hdiff_rows, pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample,
 // pe25d_spectra_due, pe25d_spectra_sample).
 #pragma once
 #include "pe25d_kernels.h"
@@ -166,6 +167,19 @@ struct PeBoundary {
     double dt = 0.0;
 };
 
+// Horizontal diffusion (pe25d_hdiff.hip, gcm_set_hdiff): the registration, the device tables of the last (parameters,
+// dt) a launch was asked for -- `key`, compared on every step as PeHeldSuarez's -- and the landing fields the launch
+// writes, own rows [H][L][W] in the handle's real type, one per state field that was ever selected; they stay until
+// gcm_set_hdiff(NULL) or gcm_destroy
+struct PeHdiff {
+    bool on = false;                            // gcm_set_hdiff: registered
+    gcm_hdiff par{};                            // the registration's parameters
+    double *tab = nullptr;                      // device: ax bn bs area axv bnv bsv areav, [8][H]
+    std::vector<double> key;                    // order, fields, nu, cmax, dt
+    int order = 0, fields = 0;                  // what the tables in place were built for
+    void *land[GCM_NFIELDS] = {};
+};
+
 struct Pe25d {
     gcm_config cfg{};
     int W = 0, H = 0, L = 0, Hg = 0;
@@ -173,6 +187,7 @@ struct Pe25d {
     std::vector<void *> allocs;
     std::vector<double> dsig_host;              // geometry.py dsig, float64 (radiation level tables)
     std::vector<double> sig_host;               // geometry.py sig, float64
+    std::vector<double> dxj_host, dxh_host;     // geometry.py dx_j, dx_h over the global height, float64 (horizontal diffusion tables)
     PeBufs<double> d;
     PeBufs<float> f;
     int cur_i = 0;
@@ -243,6 +258,7 @@ struct Pe25d {
     PeMoist moist;
     PeConvect convect;
     PeBoundary boundary;
+    PeHdiff hdiff;
 };
 
 template <typename T> inline PeBufs<T> &bufs(Pe25d *m);

@@ -133,6 +133,23 @@ int pe25d_boundary_layer_fits(Pe25d *m, const char *fn, std::string *err);
 int pe25d_boundary_layer_scratch(Pe25d *m, bool on, hipStream_t s, std::string *err);
 int pe25d_boundary_layer_tables(Pe25d *m, const gcm_boundary_layer *bl, double dt, hipStream_t s, std::string *err);
 int pe25d_boundary_layer_rows(Pe25d *m, int set, bool keep_ghosts, bool accumulate, hipStream_t s, std::string *err);
+// Horizontal diffusion (pe25d_hdiff.hip).  hdiff_check / hdiff_tables / hdiff_apply: no handle, no device
+// (gcm_hdiff_tables, gcm_hdiff_apply).  pe25d_hdiff_fits: what a registration or a step needs of the handle -- a single
+// domain, W >= 4 and H >= 4 (GCM_ERR_UNSUPPORTED); pe25d_set_hdiff: gcm_set_hdiff (d == nullptr: off, the landing fields
+// and tables freed); pe25d_hdiff_on / pe25d_hdiff_par: the registration; pe25d_hdiff_tables: the device tables for (d, dt),
+// built and uploaded when either changed, and the landing fields of d's fields in place; pe25d_hdiff_rows: the launch
+// over every row of state set `set` (-1: the current one) into the landing fields and their way back into the state,
+// on `s`, tables in place; pe25d_hdiff_plan: gcm_hdiff_plan
+int hdiff_check(const gcm_hdiff *d, const char *fn, std::string *err);
+int hdiff_tables(int H, const double *dx_j, const double *dx_h, double dy, const gcm_hdiff *d, double dt, double *out, std::string *err);
+int hdiff_apply(int H, int W, int nlev, const double *tab4, int order, const double *X, double *out, std::string *err);
+int pe25d_hdiff_fits(const Pe25d *m, const char *fn, std::string *err);
+int pe25d_set_hdiff(Pe25d *m, const gcm_hdiff *d, hipStream_t s, std::string *err);
+bool pe25d_hdiff_on(const Pe25d *m);
+const gcm_hdiff *pe25d_hdiff_par(const Pe25d *m);
+int pe25d_hdiff_tables(Pe25d *m, const gcm_hdiff *d, double dt, hipStream_t s, std::string *err);
+int pe25d_hdiff_rows(Pe25d *m, int set, bool keep_ghosts, hipStream_t s, std::string *err);
+int pe25d_hdiff_plan(const Pe25d *m, int *out, int nout);
 int pe25d_new_state_set(const Pe25d *m);    // the set a corrector stage in flight writes (before the swap), else the current one
 int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err);
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan

@@ -901,8 +901,78 @@ int gcm_spectra_sample(gcm_handle *h);
 int gcm_spectra_reset(gcm_handle *h);
 int gcm_get_spectra(gcm_handle *h, double *s, int64_t *nsamples);
 int gcm_put_spectra(gcm_handle *h, const double *s, int64_t nsamples);
+/* Horizontal del-2 / del-4 diffusion of u, v, theta (and q) of GCM_PE25D on the device: the scale-selective dissipation a
+ * lat-lon C-grid run needs besides the polar filter, which acts along i at high latitudes only (fp64 and fp32 handles,
+ * single domains only).  gcm_set_hdiff registers it as a phase of every step taken by gcm_step, applied once per step
+ * directly behind the Matsuno step and ahead of the solar step; gcm_half_step and gcm_step_phase never apply it.
+ * Grid: centres are (j, i); u lies between centres i and i + 1 on the centre latitude of row j; v lies between rows j
+ * and j + 1, on dx_h[j]'s latitude.  i and j are periodic, as in the dynamics.  The diffusion acts on the model's sigma
+ * surfaces, level by level, and component-wise on u and v: no metric terms of the vector Laplacian.
+ * Host tables, float64, every operation rounded on its own, from the handle's own dx_j, dx_h, dy over the global height
+ * (gcm_hdiff_tables builds the same ones without a handle or a device; out is [8][H]: ax bn bs area axv bnv bsv areav):
+ *   s = nu dt (order 1, nu in m^2/s);   s = sqrt(nu dt) (order 2, nu in m^4/s);   ay = min(s / (dy dy), cmax)
+ *   centre rows (theta, q, u):
+ *     ax[j] = min(s / (dx_j[j] dx_j[j]), cmax);   area[j] = ((dx_h[j-1] + dx_h[j]) dy) 0.5
+ *     bs[j] = (ay (dx_h[j] dy)) / area[j];        bn[j] = (ay (dx_h[j-1] dy)) / area[j]
+ *   v rows:
+ *     axv[j] = min(s / (dx_h[j] dx_h[j]), cmax);  areav[j] = ((dx_j[j] + dx_j[j+1]) dy) 0.5
+ *     bsv[j] = (ay (dx_j[j+1] dy)) / areav[j];    bnv[j] = (ay (dx_j[j] dy)) / areav[j]
+ * The min is what keeps the explicit step stable where the meridians converge: rows near the poles run at the capped
+ * diffusion number, the others at the physical coefficient; a division by a tiny dx_h at the pole row gives a large or
+ * infinite quotient, which the min caps.
+ * Update, float64 arithmetic for either storage type, no contraction, the result rounded once to the storage type:
+ *   zx = (X[j][i+1] - X[j][i]) - (X[j][i] - X[j][i-1]);   gs = X[j+1][i] - X[j][i];   gn = X[j][i] - X[j-1][i]
+ *   D(X) = ax[j] zx + (bs[j] gs - bn[j] gn)                                  (v: axv, bsv, bnv)
+ *   order 1: X' = X + D(X);   order 2: Y = D(X) kept in float64, never rounded to storage; X' = X - D(Y)
+ * Every operation is an IEEE add, subtract or multiply with host-built coefficients: the device result equals a NumPy
+ * restatement bit for bit in both storage types, whichever tile computes a cell.  With 0 < cmax <= 1/8,
+ * 4 ax + 2 (bn + bs) <= 1: order 1 obeys the maximum principle per level, order 2 has an amplification factor in
+ * [0, 1] for every mode, and sum_j area[j] sum_i X per level is conserved up to rounding (the meridional fluxes telescope).
+ * fields is a mask of GCM_HDIFF_U, _V, _T, _Q.  Unselected fields, p, the passive tracers and the ground temperature are
+ * neither read nor written.  The launch is out of place: it writes landing fields of the handle's real type ([H][L][W]
+ * per selected field, allocated by the registration or by the first explicit step and kept until gcm_set_hdiff(h, NULL)
+ * or gcm_destroy), which the state then takes over by a device copy on the same stream.
+ * Limits: latitude bands (nranks > 1) are refused -- the phase is not column-local, at order 2 it reads two rows beyond
+ * the own rows, and a band's ghost rows cannot be advanced locally: a band needs an exchange of its own behind the
+ * phase, which is not built; p and the passive tracers are not diffused; theta is not pressure-weighted (the diffusion
+ * conserves sum area theta per level, not the mass-weighted sum); over topography it mixes along sigma surfaces, not
+ * pressure surfaces; no vector-Laplacian metric terms; the cap stands in for an implicit zonal solve.
+ * gcm_set_hdiff(h, d) registers (d == NULL: off, and frees the landing fields and tables); registering again replaces the
+ * parameters.  Without a registration nothing is launched and every result and timing is as before.  The device tables
+ * are rebuilt when a step comes with another dt, not on every step.
+ * gcm_hdiff_on: 1 where the phase is registered, else 0 (other models: 0; a null handle GCM_ERR_ARG).
+ * gcm_hdiff_step: the same launch once, in place on the current state, with d's parameters and no registration.
+ * gcm_hdiff_apply: the host build of the very cell routine the kernel calls, over X [nlev][H][W] float64 with tab4 [4][H]
+ * = ax bn bs area (or the v rows' four), periodic both ways, into out; no handle, no device.
+ * gcm_hdiff_plan: the launch geometry of this handle without launching, GCM_HDIFF_PLAN_WORDS words, at the registered
+ * order and fields, else at order 2 and U|V|T:
+ *   [0] tile rows  [1] tile columns  [2] tiles in i  [3] tiles in j  [4] grid z (selected fields x levels)
+ *   [5] LDS bytes  [6] kernel launches per application
+ * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, no parameters in
+ * gcm_hdiff_step, order not 1 or 2, fields 0 or with unknown bits, nu not finite or <= 0, cmax outside (0, 1/8], a
+ * non-finite dt, the probes' null pointers, H, W or nlev < 1, nout < GCM_HDIFF_PLAN_WORDS (message of the probes:
+ * gcm_last_error(NULL)).  GCM_ERR_UNSUPPORTED: other models, a handle created with nranks > 1, W < 4 or H < 4 (the
+ * radius-2 halo wraps once only).                                                                                     */
+#define GCM_HDIFF_U 1
+#define GCM_HDIFF_V 2
+#define GCM_HDIFF_T 4
+#define GCM_HDIFF_Q 8
+#define GCM_HDIFF_PLAN_WORDS 7
+typedef struct {
+    int32_t order;         /* 1: del-2, 2: del-4 */
+    int32_t fields;        /* mask of GCM_HDIFF_* */
+    double nu;             /* m^2/s (order 1), m^4/s (order 2) */
+    double cmax;           /* the cap of the diffusion numbers, (0, 1/8] */
+} gcm_hdiff;
+int gcm_set_hdiff(gcm_handle *h, const gcm_hdiff *d);
+int gcm_hdiff_on(const gcm_handle *h);
+int gcm_hdiff_step(gcm_handle *h, double dt, const gcm_hdiff *d);
+int gcm_hdiff_tables(int H, const double *dx_j, const double *dx_h, double dy, const gcm_hdiff *d, double dt, double *out);
+int gcm_hdiff_apply(int H, int W, int nlev, const double *tab4, int order, const double *X, double *out);
+int gcm_hdiff_plan(gcm_handle *h, int *out, int nout);
 /* The end of a GCM_PE25D step whose dynamics the caller took itself: everything gcm_step and gcm_band_run queue behind
- * the corrector, in their order and by their code -- the solar step at the handle's clock, utc += dt, the Held-Suarez
+ * the corrector, in their order and by their code -- the horizontal diffusion (gcm_set_hdiff: single domains only), the
+ * solar step at the handle's clock, utc += dt, the Held-Suarez
  * forcing, the boundary layer, the convective adjustment, the moist physics (their sums, seconds and
  * nsteps advance as in gcm_step), the
  * climatology's step counter and its sample where one is due, then the spectra's step counter and sample (gcm_set_spectra)
