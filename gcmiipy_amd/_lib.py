@@ -138,6 +138,7 @@ SYMBOLS = {
     "gcm_pe25d_phase_plan": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "gcm_half_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_end_step": (C.c_int, [_H, C.c_double]),
+    "gcm_end_step_diffuse": (C.c_int, [_H, C.c_double]),
     "gcm_end_step_begin": (C.c_int, [_H, C.c_double]),
     "gcm_end_step_finish": (C.c_int, [_H, C.c_double]),
     "gcm_get_star": (C.c_int, [_H] + [C.c_void_p] * 5),
@@ -163,7 +164,10 @@ SYMBOLS = {
     "gcm_hdiff_step": (C.c_int, [_H, C.c_double, C.POINTER(Hdiff)]),
     "gcm_hdiff_tables": (C.c_int, [C.c_int, _dp, _dp, C.c_double, C.POINTER(Hdiff), C.c_double, _dp]),
     "gcm_hdiff_apply": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
+    "gcm_hdiff_apply_band": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
     "gcm_hdiff_plan": (C.c_int, [_H, C.POINTER(C.c_int), C.c_int]),
+    "gcm_set_band_hdiff": (C.c_int, [_H, C.c_int]),
+    "gcm_band_hdiff": (C.c_int, [_H]),
     "gcm_set_moist": (C.c_int, [_H, C.POINTER(Moist)]),
     "gcm_moist_on": (C.c_int, [_H]),
     "gcm_moist_step": (C.c_int, [_H, C.c_double, C.POINTER(Moist)]),

@@ -180,6 +180,9 @@ class BandRunner:
         self._physics(dt)
 
     def _physics(self, dt):
+        diffuse = getattr(self.e, "physics_diffuse", None)
+        if diffuse is not None and diffuse(dt):   # one more exchange: the current state's edge rows as the diffusion left them
+            self._finish(self.exchange_start())
         begin, end = getattr(self.e, "physics_begin", None), getattr(self.e, "physics_end", None)
         if begin is not None and end is not None:
             if begin(dt):                   # a third exchange: the current state's edge rows as the first part left them
@@ -392,8 +395,22 @@ class HipBandEngine:
         records together"""
         self.c.set_spectra(every, mmax)
 
+    def set_horizontal_diffusion(self, *off, **params):
+        """Core.set_horizontal_diffusion (the band was created with band_horizontal_diffusion=True); every band of a run
+        registers the same"""
+        self.c.set_horizontal_diffusion(*off, **params)
+
+    def physics_diffuse(self, dt):
+        """host-driven band step: behind the unpack of the post-corrector exchange and ahead of physics_begin, the
+        registered horizontal diffusion over the band's own rows (Core.end_step_diffuse) -> True where the band carries
+        it: the runner exchanges the current state ahead of physics_begin"""
+        if not self.pe:
+            return False
+        self.c.end_step_diffuse(dt)
+        return self.c.band_horizontal_diffusion and self.c.horizontal_diffusion_registered
+
     def physics_begin(self, dt):
-        """host-driven band step: behind the unpack of the post-corrector exchange, the walk up to and including the
+        """host-driven band step: behind the unpack of the post-corrector exchange (and of the diffusion's), the walk up to and including the
         boundary layer (Core.end_step_begin) -> True where the band carries it: the runner exchanges the current state"""
         if not self.pe:
             return False

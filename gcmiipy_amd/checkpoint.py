@@ -21,7 +21,9 @@ float64 sums, registered and uploaded again on restore; files without these keys
 zonal wavenumber spectra, Core.set_spectra, are stored as "spectra_every", "spectra_mmax", "spectra_n" and "spectra_s",
 saved and restored the same way, and files without these keys restore with none; the horizontal diffusion,
 Core.set_horizontal_diffusion, is stored as "hdiff" = [order, fields, nu, cmax] and registered again on restore, ahead of
-the first step, and files without the key restore with none; the
+the first step, and files without the key restore with none; whether a band takes that phase over its own rows is
+the option "band_horizontal_diffusion", taken from the handle as it is when saved, files without it restore as off and
+restore() opts in ahead of the registration; the
 moist physics, Core.set_moist, is stored as "moist", its three parameters in the order of core.MOIST_DEFAULTS, with
 "moist_n", "moist_seconds", "moist_precip" and "moist_evap", the count, the seconds and the raw float64 sums, registered
 and uploaded again on restore; files without these keys restore with none; the convective adjustment, Core.set_convect,
@@ -53,6 +55,8 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
         out["opt_" + name] = np.asarray(val)
     if "band_boundary_layer" in core.options:    # (what the handle says now: the opt-in may have been changed since)
         out["opt_band_boundary_layer"] = np.asarray(bool(core.band_boundary_layer))
+    if "band_horizontal_diffusion" in core.options:    # (the same for the diffusion's opt-in, stored beside "hdiff")
+        out["opt_band_horizontal_diffusion"] = np.asarray(bool(core.band_horizontal_diffusion))
     if core.has_ground:
         out["ground"] = core.get_ground()
     if core.tracer_count > 0:
@@ -108,7 +112,8 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, tracer_convect, held_suarez, hdiff, climate, spectra, moist, convect, boundary_layer, band_boundary_layer); ground and
+    tracer_mixing, tracer_convect, held_suarez, hdiff, climate, spectra, moist, convect, boundary_layer, band_boundary_layer,
+    band_horizontal_diffusion); ground and
     tracers are
     None where the file has none, tracer_forcing
     {i: dict(...)} and tracer_mixing {i: K} are then empty, and so is tracer_convect, the list of the tracers that have
@@ -116,7 +121,8 @@ def load(path):
     dict(order, fields, nu, cmax) or None (files without the key: None); climate is
     dict(every, n, m3, m2) or None; spectra is dict(every, mmax, n, s) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
     dict(params, n, seconds, count, levels) or None; boundary_layer is dict(params, n, seconds, shf, evap) or None;
-    band_boundary_layer is whether a band takes that phase (False for files without the option)"""
+    band_boundary_layer is whether a band takes that phase (False for files without the option), and
+    band_horizontal_diffusion the same for the horizontal diffusion"""
     d = np.load(path, allow_pickle=False)
     L, H, W = (int(x) for x in d["shape"])
     state = {k: d["state_" + k] for k in "puvtq" if "state_" + k in d.files}
@@ -171,7 +177,8 @@ def load(path):
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
                 tracer_mixing=mixing,
                 tracer_convect=[int(i) for i in d["tracer_convect"]] if "tracer_convect" in d.files else [],
-                band_boundary_layer=bool(opts.get("band_boundary_layer", False)), **column)
+                band_boundary_layer=bool(opts.get("band_boundary_layer", False)),
+                band_horizontal_diffusion=bool(opts.get("band_horizontal_diffusion", False)), **column)
 
 
 def restore(path, **core_kwargs):

@@ -309,6 +309,28 @@ def hdiff_apply(X, ax, bn, bs, order):
     return out
 
 
+def hdiff_apply_band(X, ax, bn, bs, order):
+    """one application of the horizontal diffusion to the own rows of a latitude band on the host in float64
+    (gcm_hdiff_apply_band: the host build of the band walk, periodic in i only; no handle, no device).  X is
+    (nlev, Hb + 4, W) or (Hb + 4, W): the band's Hb own rows with two ghost rows a side, rows -2 .. Hb + 1; ax, bn, bs
+    (Hb + 4,) are the coefficients of those rows, taken from the tables over the global height at row (row0 + j) mod
+    global_height -> the own rows, (nlev, Hb, W) or (Hb, W).  They are rows [row0, row0 + Hb) of hdiff_apply over the
+    periodic whole, bit for bit.  ValueError for a refused argument"""
+    X = as_f64(X, name="X")
+    if X.ndim not in (2, 3):
+        raise ValueError("X has shape %s, expected (nlev, Hb + 4, W) or (Hb + 4, W)" % (X.shape,))
+    HT, W = X.shape[-2:]
+    if HT < 5:
+        raise ValueError("X has %d rows: a band is 1 own row or more and two ghost rows a side" % HT)
+    nlev = X.shape[0] if X.ndim == 3 else 1
+    tab = np.zeros((4, HT))
+    for n, (a, name) in enumerate(zip((ax, bn, bs), ("ax", "bn", "bs"))):
+        tab[n] = as_f64(np.asarray(a, dtype=np.float64).reshape(-1), (HT,), name)
+    out = np.empty(X.shape[:-2] + (HT - 4, W))
+    _check(lib.gcm_hdiff_apply_band(HT - 4, W, nlev, _tab(tab), int(order), _tab(X), _tab(out)))
+    return out
+
+
 def held_suarez_tables(sig, lat, dt, **params):
     """the host tables of the Held-Suarez forcing (gcm_held_suarez_tables; no handle, no device) for the mid-level
     sigmas `sig` (L,), the latitudes `lat` (n,) in radians and the step dt -> dict(fu (L,), kt (L, n), s2 (n,), c2 (n,)):
@@ -556,7 +578,8 @@ class Core:
     def __init__(self, model, width, height, layers=1, dx=0.0, tracer=_lib.TRACER_NONE,
                  variant=_lib.VARIANT_AUTO, geom=None, filter=True, nranks=1, rank=0,
                  global_height=None, row0=0, device=-1, stream=None, halo_steps=1, coriolis=False, dtype="f64",
-                 members=1, band_tracers=0, tracer_scheme=None, band_tracer_rows=1, band_boundary_layer=False):
+                 members=1, band_tracers=0, tracer_scheme=None, band_tracer_rows=1, band_boundary_layer=False,
+                 band_horizontal_diffusion=False):
         """band_tracers: a GCM_PE25D latitude band (nranks > 1) that carries that many passive tracers
         (gcm_set_band_tracers, right after gcm_create: the ghost-row message and halo_bytes() include them);
         band_tracer_rows: the ghost rows per side those tracers carry, 1 (default) or 2 (what "van_leer" reads on a
@@ -566,7 +589,11 @@ class Core:
         band_boundary_layer: a GCM_PE25D latitude band that takes the boundary layer over its own rows
         (gcm_set_band_boundary_layer, right after gcm_create): set_boundary_layer is then accepted, and every step takes
         a third exchange of the edge rows behind the phase -- band_run does it itself, a host-driven step goes
-        end_step_begin, exchange, end_step_finish.  Every band of a run must declare the same"""
+        end_step_begin, exchange, end_step_finish.  Every band of a run must declare the same;
+        band_horizontal_diffusion: a GCM_PE25D latitude band that takes the horizontal diffusion over its own rows
+        (gcm_set_band_hdiff, right after gcm_create): set_horizontal_diffusion is then accepted, and every step takes one
+        more exchange of the edge rows behind the phase -- band_run does it itself, a host-driven step goes
+        end_step_diffuse, exchange, end_step_begin.  Every band of a run must declare the same"""
         check_dtype(dtype)
         scheme = tracer_scheme_id(tracer_scheme)
         if scheme != _lib.TRACER_NONE and model != _lib.PE25D:
@@ -591,6 +618,12 @@ class Core:
         if band_boundary_layer and not is_pe_band:
             raise ValueError("band_boundary_layer needs a GCM_PE25D latitude band (nranks > 1); a single domain takes "
                              "set_boundary_layer directly")
+        if band_horizontal_diffusion not in (0, 1, False, True):
+            raise ValueError("band_horizontal_diffusion must be True or False, got %r" % (band_horizontal_diffusion,))
+        band_horizontal_diffusion = bool(band_horizontal_diffusion)
+        if band_horizontal_diffusion and not is_pe_band:
+            raise ValueError("band_horizontal_diffusion needs a GCM_PE25D latitude band (nranks > 1); a single domain takes "
+                             "set_horizontal_diffusion directly")
         self.model, self.W, self.H, self.L = model, int(width), int(height), int(layers)
         # ensemble members (2-D models, single band): every field is (M, H, W) when M > 1
         self.members = max(int(members), 1)
@@ -601,6 +634,7 @@ class Core:
                             coriolis=bool(coriolis), dtype=dtype, members=int(members), band_tracers=band_tracers,
                             tracer_scheme=_lib.TRACER_NONE, band_tracer_rows=band_tracer_rows,
                             band_boundary_layer=band_boundary_layer,
+                            band_horizontal_diffusion=band_horizontal_diffusion,
                             global_height=int(height if global_height is None else global_height))
         self.has_ground = False
         self._forcing = {}                      # tracer -> the forcing record registered (set_tracer_forcing)
@@ -663,6 +697,8 @@ class Core:
                 self.set_tracer_scheme(scheme)
             if band_boundary_layer:
                 _check(lib.gcm_set_band_boundary_layer(self._h, 1), self._h)
+            if band_horizontal_diffusion:
+                _check(lib.gcm_set_band_hdiff(self._h, 1), self._h)
         except Exception:
             self.close()
             raise
@@ -928,6 +964,13 @@ class Core:
         with the boundary layer registered is refused (GcmError): end_step_begin, exchange, end_step_finish"""
         _check(lib.gcm_end_step(self._h, float(dt)), self._h)
 
+    def end_step_diffuse(self, dt):
+        """the part of a host-driven step ahead of end_step_begin (gcm_end_step_diffuse): the registered horizontal
+        diffusion over the own rows of a band that carries it (band_horizontal_diffusion=True), behind the unpack of the
+        post-corrector exchange.  The caller then exchanges the current state (halo_pack2, the transfer, halo_unpack2)
+        and calls end_step_begin, which such a band refuses without this call.  Every other handle: nothing happens"""
+        _check(lib.gcm_end_step_diffuse(self._h, float(dt)), self._h)
+
     def end_step_begin(self, dt):
         """the first part of end_step (gcm_end_step_begin): the solar step, the clock, Held-Suarez, the boundary layer (a
         band: over its own rows).  A band with the boundary layer registered then exchanges the ghost rows of the current
@@ -1077,15 +1120,24 @@ class Core:
         """the latitudes (global_height,) the registered Held-Suarez forcing was given, or None"""
         return self._held_suarez[1].copy() if self.held_suarez is not None else None
 
-    # -- horizontal diffusion (GCM_PE25D, single domains) ---------------------------------
+    # -- horizontal diffusion (GCM_PE25D; a latitude band: Core(..., band_horizontal_diffusion=True)) ----
+    @property
+    def band_horizontal_diffusion(self):
+        """True: a GCM_PE25D latitude band that takes the horizontal diffusion over its own rows and one more exchange
+        per step behind it (gcm_band_hdiff); False: not a GCM_PE25D band, or one that has not opted in"""
+        return bool(_count(lib.gcm_band_hdiff(self._h), self._h))
+
     def set_horizontal_diffusion(self, *off, **params):
         """every step of step() / end_step() from now on applies a del-2 (order=1) or del-4 (order=2) horizontal diffusion
         of the selected fields on the device (gcm_set_hdiff), once per step, directly behind the Matsuno step and ahead
         of solar_timestep, on sigma surfaces, level by level, u and v component-wise.  half_step never applies it.
         params: order, fields (a string of the letters u v t q, or the mask), nu (m^2/s at order 1, m^4/s at order 2),
         cmax (the cap of the diffusion numbers, in (0, 1/8]); HDIFF_DEFAULTS.  set_horizontal_diffusion(None) switches
-        the phase off.  ValueError for an unknown keyword or a refused value, GcmError for a latitude band and for a grid
-        with W or H below 4 (the call then changes nothing)"""
+        the phase off.  ValueError for an unknown keyword or a refused value, GcmError for a latitude band that has not
+        opted in and for a grid with W or H below 4 (the call then changes nothing).
+        A latitude band takes the phase over its own rows where it was created with band_horizontal_diffusion=True:
+        band_run then exchanges the edge rows once more per step behind it (one more message of halo_bytes() per
+        neighbour), a host-driven step goes end_step_diffuse, exchange, end_step_begin"""
         if off:
             if off != (None,) or params:
                 raise ValueError("set_horizontal_diffusion takes keyword parameters, or None alone to switch the phase off")
@@ -1098,7 +1150,9 @@ class Core:
 
     def horizontal_diffusion_step(self, dt, **params):
         """the horizontal diffusion once, in place on the current state, with the step dt (gcm_hdiff_step), without a
-        registration: what held_suarez_step is to set_held_suarez"""
+        registration: what held_suarez_step is to set_held_suarez.  A band that has opted in
+        (band_horizontal_diffusion=True): its own rows, from current ghost rows; the ghost rows of the selected fields
+        are stale behind the call until the caller's next exchange"""
         rec, _ = _hdiff_record(params)
         _check(lib.gcm_hdiff_step(self._h, float(dt), C.byref(rec)), self._h)
 
@@ -1108,6 +1162,11 @@ class Core:
         None where the handle carries none (gcm_hdiff_on) -- and also None for one registered through the C call directly"""
         on = _count(lib.gcm_hdiff_on(self._h), self._h)
         return dict(self._hdiff) if on and self._hdiff else None
+
+    @property
+    def horizontal_diffusion_registered(self):
+        """whether the handle carries the phase at all (gcm_hdiff_on), whoever registered it"""
+        return bool(_count(lib.gcm_hdiff_on(self._h), self._h))
 
     def horizontal_diffusion_plan(self):
         """the launch geometry of the horizontal diffusion of this handle, without launching (gcm_hdiff_plan), at the

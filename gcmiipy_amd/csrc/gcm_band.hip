@@ -113,21 +113,28 @@ static int band_exchange(gcm_handle *h) {
 // takes the ghost rows with it when the exchange was joined into the compute stream.
 // With the boundary layer registered (the band has opted in: gcm_set_band_boundary_layer) the walk splits at it and the
 // step takes a THIRD exchange, of the current state's edge rows as the boundary layer left them (band_step_pe_bl).
-// Without it band_step_pe queues what it always has: no event, launch or copy more.
+// With the horizontal diffusion registered (the band has opted in: gcm_set_band_hdiff) the own rows are diffused right
+// behind the corrector's unpack and the current state's edge rows are exchanged once more AHEAD of the walk
+// (band_step_pe_hd); the ghost rows' phases and their column sums then follow that exchange's unpack, not the
+// corrector's.  With both registered a step takes four exchanges.
+// Without either band_step_pe queues what it always has: no event, launch or copy more.
 static int band_step_pe_bl(gcm_handle *h, double dt, hipStream_t ax);
+static int band_step_pe_hd(gcm_handle *h, double dt, hipStream_t ax, bool bl);
 static int band_step_pe(gcm_handle *h, double dt) {
     int rc = GCM_OK;
     hipStream_t ax = h->band.on_comm ? nullptr : pe25d_aux_stream(h->pe);
-    const bool bl = band_boundary_layer_on(h);
+    const bool bl = band_boundary_layer_on(h), hd = band_hdiff_on(h);
     for (int stage = 0; stage < 2; ++stage) {
         if ((rc = pe25d_step_phase(h->pe, 2 * stage, dt, h->stream, &h->err, ax != nullptr))) return rc;
         if (ax) {
             if ((rc = band_post(h, ax))) return rc;
             if ((rc = gcm_halo_unpack2(h, h->band.xch.recv_north, h->band.xch.recv_south, ax))) return rc;
-            if (stage == 1 && (rc = pe_ghost_row_phases(h, dt, ax, bl ? kPhasesHead : kPhasesAll))) return rc;
+            // (the corrector's ghost rows of a band with the diffusion: read by the own rows' launch, then overwritten by the
+            // exchange behind it, whose unpack the ghost rows' phases follow: band_step_pe_hd)
+            if (stage == 1 && !hd && (rc = pe_ghost_row_phases(h, dt, ax, bl ? kPhasesHead : kPhasesAll))) return rc;
             // (the corrector's ghost rows of a band with the boundary layer: overwritten by the third exchange, behind
             // which their column sums and anchors are queued; until then nothing on `ax` reads own rows' u and v)
-            if (!(bl && stage == 1) && (rc = pe25d_prep_ghost_rows(h->pe, &h->err))) return rc;
+            if (!((bl || hd) && stage == 1) && (rc = pe25d_prep_ghost_rows(h->pe, &h->err))) return rc;
             h->band.join_pending = true;
         }
         if ((rc = pe25d_step_phase(h->pe, 2 * stage + 1, dt, h->stream, &h->err, ax != nullptr))) return rc;
@@ -136,8 +143,45 @@ static int band_step_pe(gcm_handle *h, double dt) {
             if ((rc = band_exchange(h))) return rc;
         }
     }
+    if (hd && (rc = band_step_pe_hd(h, dt, ax, bl))) return rc;
     if (bl) return band_step_pe_bl(h, dt, ax);
     return pe_own_row_phases(h, dt, phase_ghosts(h, ax != nullptr), ax != nullptr, ax, kPhasesAll);
+}
+
+// The horizontal diffusion of a band step, behind the corrector (the swap is done: the current state is the new one, and
+// packs and unpacks take it) and ahead of the phase walk.
+//   compute stream: [ax: -> ev_comm @ ax, waits: the corrector's unpack, and every read of the send buffers by the
+//                   corrector's exchange],
+//                   the diffusion of the own rows, which reads ghost rows -2, -1, H, H + 1 of the selected fields; the copy
+//                   back; the pack of the edge rows as it left them -> ev_pack
+//   ax / comm:      waits ev_pack; the exchange, in the existing message and buffers (the tracers' edge rows ride in it as
+//                   in the boundary layer's third exchange); (ax:) the unpack, the ghost rows' solar step + Held-Suarez
+//                   (without the boundary layer: + convective adjustment + moist physics, their column sums and anchors)
+//   compute stream: (comm: waits ev_comm, the unpack;) the walk as it was, beside the exchange on `ax`
+// The corrector's unpack is behind the compute stream in the comm orchestration already (band_exchange).  The new unpack
+// follows ev_pack, hence every read of the ghost rows by the diffusion.  The events are the run's own (ev_comm, ev_pack),
+// each waited for in stream order before it is recorded again.
+// Not built: the edge rows' tiles first, with the exchange beside the interior tiles.  The launch is out of place and
+// the interior tiles read the original edge rows, so these cannot be copied back and packed while it is in flight.
+static int band_step_pe_hd(gcm_handle *h, double dt, hipStream_t ax, bool bl) {
+    int rc = GCM_OK;
+    if (ax) {
+        HIPCHK(h, hipEventRecord(h->band.ev_comm, ax));
+        HIPCHK(h, hipStreamWaitEvent(h->stream, h->band.ev_comm, 0));
+    }
+    if ((rc = pe_band_hdiff_rows(h, ax != nullptr))) return rc;
+    if (!ax) {                                             // (pack -> ev_pack @ st, comm waits; the group; st waits, the unpack)
+        if ((rc = pack_edges(h)) || (rc = band_exchange(h))) return rc;
+        return GCM_OK;
+    }
+    if ((rc = gcm_halo_pack2(h, h->band.xch.send_north, h->band.xch.send_south, h->stream))) return rc;
+    HIPCHK(h, hipEventRecord(h->band.ev_pack, h->stream));
+    HIPCHK(h, hipStreamWaitEvent(ax, h->band.ev_pack, 0));
+    if ((rc = band_post(h, ax))) return rc;
+    if ((rc = gcm_halo_unpack2(h, h->band.xch.recv_north, h->band.xch.recv_south, ax))) return rc;
+    if ((rc = pe_ghost_row_phases(h, dt, ax, bl ? kPhasesHead : kPhasesAll))) return rc;
+    if (!bl && (rc = pe25d_prep_ghost_rows(h->pe, &h->err))) return rc;
+    return GCM_OK;
 }
 
 // The end of a band step with the boundary layer registered, behind the corrector (the swap is done: the current state
@@ -296,8 +340,13 @@ static int run_deep_overlapped(gcm_handle *h, int nsteps, double dt) {
 //   .. boundary layer on   st (third exch.:  ax         ax      behind the corrector's unpack and the ghost rows' solar + Held-Suarez: -> ev_comm @ ax, st waits
 //      (third exchange)    the current                          ahead of the own rows' boundary layer; pack -> ev_pack @ st, ax waits; the ghost rows'
 //                          state's edge rows)                   convect + moist and their column sums follow the unpack on ax
+//   .. diffusion on        st (behind the    ax         ax      behind the corrector's unpack: -> ev_comm @ ax, st waits ahead of the own rows' diffusion and its
+//      (one more exchange) copy back: the                       copy back; pack -> ev_pack @ st, ax waits; the ghost rows' phases and their column sums follow the
+//                          current state's edge rows)           new unpack on ax (with the boundary layer on: its head only, the rest as in the lines above)
 //   .. GCM_BAND_COMM_STREAM=1  ax (as above) comm       st      comm waits for the edge rows' pack (pe25d_wait_edges); group -> ev_comm @ comm, st waits
 //      .. boundary layer on  st (third exch.) comm      st      pack -> ev_pack @ st, comm waits; group -> ev_comm @ comm, st waits ahead of the unpack
+//      .. diffusion on     st (one more)     comm       st      behind the corrector's unpack on st: the diffusion, the copy back; pack -> ev_pack @ st, comm waits;
+//                                                               group -> ev_comm @ comm, st waits ahead of the unpack and the walk
 //   run_exchange_per_step  st                comm       st      pack -> ev_pack @ st, comm waits; group -> ev_comm @ comm, st waits ahead of the boundary rows
 //   run_deep               st                st         st      none: stream order
 //   run_deep_overlapped    st (window_last,  comm       st      pack -> ev_pack @ st, comm waits; group -> ev_comm @ comm; st waits in window_first behind

@@ -166,6 +166,10 @@ extern "C" int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax, int
 extern "C" int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail, int which);
 // a band with the boundary layer registered (which takes the opt-in, gcm_set_band_boundary_layer): three exchanges per step
 inline bool band_boundary_layer_on(const gcm_handle *h) { return h->pe && !h->wrap && gcm::pe25d_sums_on(h->pe, gcm::kSumsBoundary); }
+// a band with the horizontal diffusion registered (which takes the opt-in, gcm_set_band_hdiff): its own rows are diffused
+// behind the corrector's unpack and the current state's edge rows exchanged once more ahead of the phase walk
+inline bool band_hdiff_on(const gcm_handle *h) { return h->pe && !h->wrap && gcm::pe25d_hdiff_on(h->pe); }
+extern "C" int pe_band_hdiff_rows(gcm_handle *h, bool keep_ghosts);
 // ghost rows a side that a phase's launch on the handle's stream takes with the own rows: a band's, unless they are
 // forced apart on the second stream (pe_ghost_row_phases)
 inline int phase_ghosts(const gcm_handle *h, bool apart = false) { return h->wrap || apart ? 0 : gcm::kGhost; }

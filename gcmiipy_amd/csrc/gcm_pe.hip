@@ -10,7 +10,9 @@
 using namespace gcm;
 
 // ------------------------------------------------------------------ the phases of a step
-// The order is the model's: the dynamics step, the horizontal diffusion (a single domain's only), the solar step at the
+// The order is the model's: the dynamics step, the horizontal diffusion (a single domain's in the walk; a band that has
+// opted in: its own rows ahead of the walk, with an exchange of the current state's edge rows between the two --
+// pe_band_hdiff_rows), the solar step at the
 // current clock, utc += dt, the Held-Suarez forcing,
 // the boundary layer (on a band: then a third exchange of the edge rows), the convective adjustment, the moist physics,
 // the climatology's sample, the spectra's sample.  Each launch runs only if its phase is
@@ -70,7 +72,8 @@ static int pe_phase_rows(gcm_handle *h, double dt, int set, int j0, int j1, int 
     if (which == kPhasesAll && band_boundary_layer_on(h))
         return fail(h, GCM_ERR_STATE, "boundary layer on a latitude band: the phase walk splits at it, with an exchange of the current state between the two parts");
     if (which & kPhasesHead) {
-        // gcm_set_hdiff, directly behind the Matsuno step: every row of a single domain (a band cannot register it).  The
+        // gcm_set_hdiff, directly behind the Matsuno step: every row of a single domain.  (A band that has opted in has
+        // diffused its own rows ahead of the walk and exchanged its edge rows again: pe_band_hdiff_rows.)  The
         // launch writes u and v, as the forcing's does (pe25d_phase_wrote)
         if (own && h->wrap && pe25d_hdiff_on(h->pe)) {
             if (j0 != 0 || j1 != h->H || jb1 > jb0)
@@ -152,6 +155,15 @@ int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStre
     return GCM_OK;
 }
 
+// The registered diffusion of an opted-in band's own rows on the handle's stream, tables in place (pe_phase_tables), from
+// the ghost rows -2, -1, H, H + 1 of the selected fields as the corrector's exchange left them.  Behind it the ghost rows
+// are stale: the caller exchanges the current state's edge rows again ahead of the phase walk (gcm_band_run:
+// band_step_pe_hd; a host-driven step: gcm_end_step_diffuse).  keep_ghosts: as pe_phase_rows
+int pe_band_hdiff_rows(gcm_handle *h, bool keep_ghosts) {
+    if (!band_hdiff_on(h)) return fail(h, GCM_ERR_STATE, "horizontal diffusion on a latitude band: not registered");
+    return pe25d_hdiff_rows(h->pe, -1, keep_ghosts, h->stream, &h->err);
+}
+
 // gcm_step of a GCM_PE25D handle (the caller has selected the device)
 int pe_step(gcm_handle *h, int nsteps, double dt) {
     if (int rc = pe_phase_tables(h, nsteps, dt)) return rc;
@@ -182,16 +194,40 @@ int gcm_pe25d_phase_plan(gcm_handle *h, int phase, int rows, int accumulate, int
 // What gcm_band_run queues behind a corrector where the ghost rows ride with the own rows (GCM_BAND_COMM_STREAM=1): the
 // tables for dt, then every registered phase over own rows and ghost rows on the handle's stream, the clock, the samples.
 // gcm_end_step is the whole walk; gcm_end_step_begin and gcm_end_step_finish are its two parts, for a band with the
-// boundary layer registered, which exchanges the current state's edge rows between them
+// boundary layer registered, which exchanges the current state's edge rows between them.  A band with the horizontal
+// diffusion registered has a part of its own ahead of them, gcm_end_step_diffuse, and an exchange behind that
 static int end_step_part(gcm_handle *h, double dt, const char *fn, int which) {
     if (int rc = pe_only(h, fn)) return rc;
     if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, std::string(fn) + ": dt must be finite");
     if (which == kPhasesAll && band_boundary_layer_on(h))
         return fail(h, GCM_ERR_STATE, std::string(fn) + ": the boundary layer is registered on this band, whose edge rows are exchanged again behind it: "
                                       "call gcm_end_step_begin, exchange the current state's ghost rows, then gcm_end_step_finish");
+    const bool hd = band_hdiff_on(h);
+    if (hd && which == kPhasesAll)
+        return fail(h, GCM_ERR_STATE, std::string(fn) + ": the horizontal diffusion is registered on this band, whose edge rows are exchanged again behind it: "
+                                      "call gcm_end_step_diffuse, exchange the current state's ghost rows, then gcm_end_step_begin and gcm_end_step_finish");
+    if (hd && (which & kPhasesHead) && !pe25d_band_hdiff_done(h->pe))
+        return fail(h, GCM_ERR_STATE, std::string(fn) + ": the horizontal diffusion is registered on this band: call gcm_end_step_diffuse and exchange the "
+                                      "current state's ghost rows ahead of gcm_end_step_begin");
     if (int rc = select_device(h)) return rc;
     if (int rc = pe_phase_tables(h, 1, dt)) return rc;
-    return pe_own_row_phases(h, dt, phase_ghosts(h), false, nullptr, which);
+    if (int rc = pe_own_row_phases(h, dt, phase_ghosts(h), false, nullptr, which)) return rc;
+    if (hd && (which & kPhasesHead)) pe25d_set_band_hdiff_done(h->pe, false);     // (the next step diffuses again)
+    return GCM_OK;
+}
+
+// The part of a host-driven step ahead of gcm_end_step_begin: the diffusion of an opted-in, registered band's own rows,
+// behind the unpack of the post-corrector exchange.  Every other GCM_PE25D handle: nothing (a single domain's diffusion
+// is the head of its walk)
+int gcm_end_step_diffuse(gcm_handle *h, double dt) {
+    if (int rc = pe_only(h, "gcm_end_step_diffuse")) return rc;
+    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_end_step_diffuse: dt must be finite");
+    if (!band_hdiff_on(h)) return GCM_OK;
+    if (int rc = select_device(h)) return rc;
+    if (int rc = pe25d_hdiff_tables(h->pe, pe25d_hdiff_par(h->pe), dt, h->stream, &h->err)) return rc;
+    if (int rc = pe_band_hdiff_rows(h, false)) return rc;
+    pe25d_set_band_hdiff_done(h->pe, true);
+    return GCM_OK;
 }
 
 int gcm_end_step(gcm_handle *h, double dt) { return end_step_part(h, dt, "gcm_end_step", kPhasesAll); }
@@ -358,7 +394,18 @@ int gcm_solar_step(gcm_handle *h, double dt, double utc, double t_lw, double t_s
 }
 
 // ------------------------------------------------------------------ horizontal diffusion
-// a latitude band, W or H below 4: refused in the call itself
+// a band opts in to the phase over its own rows and to the exchange per step that goes with it
+int gcm_set_band_hdiff(gcm_handle *h, int on) {
+    if (int rc = pe_only(h, "gcm_set_band_hdiff", true)) return rc;
+    return pe25d_set_band_hdiff(h->pe, on != 0, &h->err);
+}
+
+int gcm_band_hdiff(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && pe25d_band_hdiff(h->pe) ? 1 : 0;
+}
+
+// a latitude band that has not opted in, W or H below 4: refused in the call itself
 int gcm_set_hdiff(gcm_handle *h, const gcm_hdiff *d) {
     if (int rc = pe_only(h, "gcm_set_hdiff")) return rc;
     if (int rc = select_device(h)) return rc;
@@ -378,6 +425,8 @@ int gcm_hdiff_step(gcm_handle *h, double dt, const gcm_hdiff *d) {
     if (int rc = select_device(h)) return rc;
     // without a registration the call allocates the landing fields itself; the handle keeps them for the next such call,
     // until gcm_set_hdiff(NULL) or gcm_destroy
+    // A band that has opted in: its own rows, from current ghost rows; the ghost rows of the selected fields are stale
+    // behind the call until the caller's next exchange
     if (int rc = pe25d_hdiff_tables(h->pe, d, dt, h->stream, &h->err)) return rc;
     return pe25d_hdiff_rows(h->pe, -1, false, h->stream, &h->err);
 }
@@ -388,6 +437,10 @@ int gcm_hdiff_tables(int H, const double *dx_j, const double *dx_h, double dy, c
 
 int gcm_hdiff_apply(int H, int W, int nlev, const double *tab4, int order, const double *X, double *out) {
     return hdiff_apply(H, W, nlev, tab4, order, X, out, &gcm_create_error());
+}
+
+int gcm_hdiff_apply_band(int Hb, int W, int nlev, const double *tab4, int order, const double *X, double *out) {
+    return hdiff_apply_band(Hb, W, nlev, tab4, order, X, out, &gcm_create_error());
 }
 
 int gcm_hdiff_plan(gcm_handle *h, int *out, int nout) {

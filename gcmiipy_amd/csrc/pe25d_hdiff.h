@@ -44,6 +44,9 @@ __host__ __device__ inline double hdiff_cell(double c, double w, double e, doubl
 constexpr int kHdThreads = 256;
 constexpr int kHdRows = 16;
 constexpr int kHdCols = 128;
+// The band form of the kernel (a latitude band that has opted in, gcm_set_band_hdiff) has the same geometry over the
+// band's own rows: its halo rows beyond the own rows are the band's ghost rows, kHdGhost a side -- the radius of order 2
+constexpr int kHdGhost = 2;
 
 constexpr size_t hdiff_lds_bytes(int order) {
     return sizeof(double) * ((size_t)(kHdRows + 2 * order) * (kHdCols + 2 * order) +

@@ -16,9 +16,22 @@
 // of the vector Laplacian (as incompressible_viscosity_2d does for the 2-D model); theta is not pressure-weighted, so
 // sum area theta is conserved per level, not the mass-weighted sum; p and the passive tracers are not diffused (their
 // transport schemes are limited already); the stability of the explicit step where the meridians converge comes from
-// the cap cmax on the diffusion numbers, not from an implicit zonal solve; latitude bands are refused -- the stencil
-// reads two rows beyond the own rows at order 2, a band's ghost rows cannot be advanced locally and would need an
-// exchange of their own behind the phase.
+// the cap cmax on the diffusion numbers, not from an implicit zonal solve; latitude bands are refused by default -- the
+// stencil reads two rows beyond the own rows at order 2 and a band's ghost rows cannot be advanced locally.
+//
+// A latitude band that has opted in (gcm_set_band_hdiff) takes the BAND form of the kernel over its own rows.  The phase
+// sits directly behind the corrector, whose exchange has just filled the kGhost = 2 ghost rows a side of u, v, theta
+// and q, and the order-2 stencil has radius 2: every own cell sees the single domain's inputs and operations in the
+// same order, hence its bits.  j is not periodic there: tile and halo rows j0 - R + r are addressed directly, rows -2,
+// -1, H and H + 1 being the ghost rows of the same allocation; only i wraps.  The device tables of a band are
+// [8][H + 4], rows -2 .. H + 1, gathered on the host from the tables over the global height at row (row0 + j) mod Hg
+// (rank 0's ghost row -1 is global row Hg - 1: the ring wraps as the dynamics do).  The ghost rows themselves cannot
+// be diffused (ghost row -1 would need row -3): behind the launch and the copy back they are stale, and the current
+// state's edge rows are exchanged once more before anything reads them (gcm_band.hip, band_step_pe_hd; a host-driven
+// step: gcm_end_step_diffuse, the caller's exchange, gcm_end_step_begin).  That costs one more message of
+// gcm_halo_bytes per neighbour and step.  Deliberately not built: dispatching the edge rows' tiles first, so that the
+// exchange hides behind the interior tiles.  The launch is out of place and the interior tiles read the ORIGINAL edge
+// rows, so the edge rows cannot be copied back and packed while the interior launch is in flight.
 //
 // Every operation is rounded on its own: contraction is off for the whole file (the Makefile builds it with
 // -ffp-contract=fast-honor-pragmas), host and device, so the host tables are the NumPy restatement's bits and a cell
@@ -45,6 +58,8 @@
 #include <cstring>
 
 namespace gcm {
+
+static_assert(kHdGhost == kGhost, "a band's ghost rows a side are the diffusion's halo at order 2");
 
 // ---------------------------------------------------------------- the tables and the probe (host)
 int hdiff_check(const gcm_hdiff *d, const char *fn, std::string *err) {
@@ -134,24 +149,78 @@ int hdiff_apply(int H, int W, int nlev, const double *tab4, int order, const dou
     return GCM_OK;
 }
 
+// D of rows [r0, r1) of one band level [Hb + 4][W] (row r is band row r - 2) with the rows' coefficients, periodic in i
+// only: rows r - 1 and r + 1 are addressed directly
+static void hdiff_band_level(int r0, int r1, int W, const double *ax, const double *bn, const double *bs, const double *X, double *D) {
+    for (int r = r0; r < r1; ++r) {
+        const double *c = X + (size_t)r * W, *n = c - W, *s = c + W;
+        for (int i = 0; i < W; ++i) {
+            const int iw = i == 0 ? W - 1 : i - 1, ie = i == W - 1 ? 0 : i + 1;
+            D[(size_t)r * W + i] = hdiff_cell(c[i], c[iw], c[ie], n[i], s[i], ax[r], bn[r], bs[r]);
+        }
+    }
+}
+
+// gcm_hdiff_apply_band: the host build of the band walk.  Order 2 forms Y on rows -1 .. Hb from rows -2 .. Hb + 1
+int hdiff_apply_band(int Hb, int W, int nlev, const double *tab4, int order, const double *X, double *out, std::string *err) {
+    const char *fn = "gcm_hdiff_apply_band";
+    const auto bad = [&](const char *what) { *err = std::string(fn) + ": " + what; return GCM_ERR_ARG; };
+    if (Hb < 1 || W < 1 || nlev < 1) return bad("Hb, W and nlev must be 1 or more");
+    if (!tab4 || !X || !out) return bad("a null pointer");
+    if (order != 1 && order != 2) return bad("order must be 1 or 2");
+    const int HT = Hb + 4;
+    const double *ax = tab4, *bn = ax + HT, *bs = bn + HT;
+    const size_t n = (size_t)HT * W, own = (size_t)Hb * W;
+    std::vector<double> Y(n, 0.0), D(order == 2 ? n : 0, 0.0);
+    for (int k = 0; k < nlev; ++k) {
+        const double *x = X + k * n;
+        double *o = out + k * own;
+        if (order == 1) {
+            hdiff_band_level(2, Hb + 2, W, ax, bn, bs, x, Y.data());
+            for (size_t c = 0; c < own; ++c) o[c] = x[2 * (size_t)W + c] + Y[2 * (size_t)W + c];
+        } else {
+            hdiff_band_level(1, Hb + 3, W, ax, bn, bs, x, Y.data());
+            hdiff_band_level(2, Hb + 2, W, ax, bn, bs, Y.data(), D.data());
+            for (size_t c = 0; c < own; ++c) o[c] = x[2 * (size_t)W + c] - D[2 * (size_t)W + c];
+        }
+    }
+    return GCM_OK;
+}
+
+// the tables of a band, [8][Hb + 4]: row r of each is row (row0 - 2 + r) mod Hg of the table over the global height
+void hdiff_band_tables(int Hg, int row0, int Hb, const double *glob, double *out) {
+    const int HT = Hb + 4;
+    for (int t = 0; t < 8; ++t)
+        for (int r = 0; r < HT; ++r) {
+            int j = (row0 - 2 + r) % Hg;
+            if (j < 0) j += Hg;
+            out[(size_t)t * HT + r] = glob[(size_t)t * Hg + j];
+        }
+}
+
 // ---------------------------------------------------------------- the kernel
 template <typename T>
 struct HdArgsT {
     const T *src[GCM_NFIELDS - 1];   // the selected fields of the state, [j][k][i], interior row 0
     T *dst[GCM_NFIELDS - 1];         // their landing fields, [j][k][i], own rows only
     int isv[GCM_NFIELDS - 1];        // 1: the field lies on v rows (the second four tables)
-    const double *tab;               // [8][H]
+    const double *tab;               // [8][H]; a band: [8][H + 4], rows -2 .. H + 1
     int W, H, L;
 };
 
 __device__ inline int hd_wrap(int x, int n) { return x < 0 ? x + n : x >= n ? x - n : x; }
+// a row index: periodic on a single domain, as it is on a band (rows -2 .. H + 1 exist there)
+template <bool BAND>
+__device__ inline int hd_row(int j, int H) { return BAND ? j : hd_wrap(j, H); }
 
 // grid (strips of kHdCols columns, tiles of kHdRows rows, selected field x level).  W >= 4 and H >= 4: an index a halo
 // of two cells reaches wraps once at the most.  The work of a phase is laid out so that a row is wave-uniform and a
 // lane owns a column: row addresses and the rows' coefficients are scalar (the table is read through the scalar
 // cache, no LDS copy), no index is divided, and a thread that marches down its column keeps the two values above the
-// new row in registers -- three LDS reads a cell instead of five
-template <typename T, int ORDER>
+// new row in registers -- three LDS reads a cell instead of five.
+// BAND: a latitude band's own rows [0, H).  j is not periodic: a row index is used as it is (rows -2, -1, H, H + 1 are
+// the ghost rows of the same allocation, and the table has their coefficients); H >= 2.  Everything else is the same code
+template <typename T, int ORDER, bool BAND = false>
 __global__ __launch_bounds__(kHdThreads) void pe_hdiff_kernel(HdArgsT<T> a) {
     constexpr int R = ORDER;
     constexpr int XW = kHdCols + 2 * R, XR = kHdRows + 2 * R;
@@ -171,7 +240,8 @@ __global__ __launch_bounds__(kHdThreads) void pe_hdiff_kernel(HdArgsT<T> a) {
     const T *src = f == 0 ? a.src[0] : f == 1 ? a.src[1] : f == 2 ? a.src[2] : a.src[3];
     T *dst = f == 0 ? a.dst[0] : f == 1 ? a.dst[1] : f == 2 ? a.dst[2] : a.dst[3];
     const int isv = f == 0 ? a.isv[0] : f == 1 ? a.isv[1] : f == 2 ? a.isv[2] : a.isv[3];
-    const double *ax_t = a.tab + (long)(isv ? 4 : 0) * H, *bn_t = ax_t + H, *bs_t = bn_t + H;
+    const int TH = BAND ? H + 2 * kHdGhost : H;                     // rows of a table; a band's row j is entry j + 2
+    const double *ax_t = a.tab + (long)(isv ? 4 : 0) * TH + (BAND ? kHdGhost : 0), *bn_t = ax_t + TH, *bs_t = bn_t + TH;
     const int nr = min(kHdRows, H - j0), nc = min(kHdCols, W - i0);   // the tile's own cells (a partial last tile)
     const int lr = nr + 2 * R, lc = nc + 2 * R;
     const long rs = (long)L * W;                                   // elements from a row to the next
@@ -183,7 +253,7 @@ __global__ __launch_bounds__(kHdThreads) void pe_hdiff_kernel(HdArgsT<T> a) {
     double cax[kCoef], cbn[kCoef], cbs[kCoef];
 #pragma unroll
     for (int m = 0; m < kCoef; ++m) {
-        const int j = hd_wrap(min(j0 - 1 + (kHdRows / 2) * half + m, j0 + nr), H);
+        const int j = hd_row<BAND>(min(j0 - 1 + (kHdRows / 2) * half + m, j0 + nr), H);
         cax[m] = ax_t[j];
         cbn[m] = bn_t[j];
         cbs[m] = bs_t[j];
@@ -199,13 +269,13 @@ __global__ __launch_bounds__(kHdThreads) void pe_hdiff_kernel(HdArgsT<T> a) {
         const int r = wave + 4 * n;
         va[n] = vb[n] = (T)0;
         if (r < lr) {
-            const T *row = lev + (long)hd_wrap(j0 - R + r, H) * rs;
+            const T *row = lev + (long)hd_row<BAND>(j0 - R + r, H) * rs;
             if (lane < lc) va[n] = row[ia];
             if (lane + 64 < lc) vb[n] = row[ib];
         }
     }
     const int tr = tid / (2 * R), tc = 2 * 64 + tid % (2 * R);
-    if (tid < kTail && tr < lr && tc < lc) vt = lev[(long)hd_wrap(j0 - R + tr, H) * rs + hd_wrap(i0 - R + tc, W)];
+    if (tid < kTail && tr < lr && tc < lc) vt = lev[(long)hd_row<BAND>(j0 - R + tr, H) * rs + hd_wrap(i0 - R + tc, W)];
 #pragma unroll
     for (int n = 0; n < kRowIt; ++n) {
         const int r = wave + 4 * n;
@@ -240,7 +310,7 @@ __global__ __launch_bounds__(kHdThreads) void pe_hdiff_kernel(HdArgsT<T> a) {
         }
         const int r = tid >> 1, c = kHdCols + (tid & 1);
         if (tid < 2 * YR && r < nr + 2 && c < nc + 2) {
-            const int j = hd_wrap(j0 - 1 + r, H);
+            const int j = hd_row<BAND>(j0 - 1 + r, H);
             const double *x = xs + (r + 1) * XW + (c + 1);
             ys[r * YW + c] = hdiff_cell(x[0], x[-1], x[1], x[-XW], x[XW], ax_t[j], bn_t[j], bs_t[j]);
         }
@@ -278,10 +348,36 @@ static const int kHdBit[GCM_NFIELDS - 1] = {GCM_HDIFF_U, GCM_HDIFF_V, GCM_HDIFF_
 
 int pe25d_hdiff_fits(const Pe25d *m, const char *fn, std::string *err) {
     const auto no = [&](const char *what) { *err = std::string(fn) + ": " + what; return GCM_ERR_UNSUPPORTED; };
-    if (!m->wrap) return no("single domains only (the stencil reads two rows beyond a latitude band's own rows, and its ghost rows cannot be advanced locally)");
+    if (!m->wrap && !m->hdiff.band)
+        return no("single domains only (the stencil reads two rows beyond a latitude band's own rows, and its ghost rows cannot be advanced locally: gcm_set_band_hdiff)");
+    if (!m->wrap) {
+        // (an opted-in band: rows are addressed directly, so only i must wrap once at the most; kGhost own rows at the least,
+        // as the exchange needs anyway)
+        if (m->W < 4 || m->H < kGhost || m->Hg < 4) return no("a band needs W >= 4, 2 own rows or more and a global height of 4 or more");
+        return GCM_OK;
+    }
     if (m->W < 4 || m->H < 4) return no("W and H must be 4 or more (the halo of two cells wraps once only)");
     return GCM_OK;
 }
+
+// gcm_set_band_hdiff: a band takes the phase over its own rows and one more exchange per step behind it
+int pe25d_set_band_hdiff(Pe25d *m, bool on, std::string *err) {
+    if (m->wrap) {
+        if (!on) return GCM_OK;
+        *err = "gcm_set_band_hdiff: GCM_PE25D latitude bands only (a single domain takes gcm_set_hdiff directly)";
+        return GCM_ERR_UNSUPPORTED;
+    }
+    if (!on && m->hdiff.on) {
+        *err = "gcm_set_band_hdiff: the horizontal diffusion is registered (gcm_set_hdiff(NULL) first)";
+        return GCM_ERR_STATE;
+    }
+    m->hdiff.band = on;
+    return GCM_OK;
+}
+bool pe25d_band_hdiff(const Pe25d *m) { return !m->wrap && m->hdiff.band; }
+// a band's own rows diffused for the step gcm_end_step_begin ends (gcm_end_step_diffuse sets it, begin takes it)
+bool pe25d_band_hdiff_done(const Pe25d *m) { return m->hdiff.band_done; }
+void pe25d_set_band_hdiff_done(Pe25d *m, bool done) { m->hdiff.band_done = done; }
 
 static void hdiff_free(Pe25d *m, void *p) {
     m->allocs.erase(std::remove(m->allocs.begin(), m->allocs.end(), p), m->allocs.end());
@@ -319,6 +415,7 @@ int pe25d_set_hdiff(Pe25d *m, const gcm_hdiff *d, hipStream_t s, std::string *er
         if (z.tab) { hdiff_free(m, z.tab); z.tab = nullptr; }
         z.key.clear();
         z.on = false;
+        z.band_done = false;
         return GCM_OK;
     }
     if (int rc = hdiff_check(d, "gcm_set_hdiff", err)) return rc;
@@ -338,12 +435,17 @@ int pe25d_hdiff_tables(Pe25d *m, const gcm_hdiff *d, double dt, hipStream_t s, s
     if (int rc = pe25d_hdiff_fits(m, "horizontal diffusion", err)) return rc;
     if (int rc = hdiff_landing(m, d->fields, err)) return rc;
     PeHdiff &z = m->hdiff;
-    const int H = m->H;
+    const int Hg = m->wrap ? m->H : m->Hg;                 // (the tables span the global height; a band gathers its rows)
     z.fields = d->fields;                                  // (the mask is not part of the tables)
     std::vector<double> key = {(double)d->order, d->nu, d->cmax, dt};
     if (z.tab && z.key.size() == key.size() && !memcmp(z.key.data(), key.data(), sizeof(double) * key.size())) return GCM_OK;
-    std::vector<double> T((size_t)8 * H);
-    if (int rc = hdiff_tables(H, m->dxj_host.data(), m->dxh_host.data(), m->cfg.dy, d, dt, T.data(), err)) return rc;
+    std::vector<double> T((size_t)8 * Hg);
+    if (int rc = hdiff_tables(Hg, m->dxj_host.data(), m->dxh_host.data(), m->cfg.dy, d, dt, T.data(), err)) return rc;
+    if (!m->wrap) {
+        std::vector<double> B((size_t)8 * (m->H + 2 * kGhost));
+        hdiff_band_tables(Hg, m->cfg.row0, m->H, T.data(), B.data());
+        T.swap(B);
+    }
     // A change is rare (another dt, another registration): everything queued so far may still read the tables in place,
     // so it ends first, and the upload is synchronous (as pe25d_hs_tables)
     if (hipStreamSynchronize(s) != hipSuccess) { *err = "hip: horizontal diffusion: the launches ahead of the table upload failed"; return GCM_ERR_HIP; }
@@ -375,7 +477,10 @@ static int hd_launch(Pe25d *m, int set, hipStream_t s, std::string *err) {
     a.W = m->W; a.H = m->H; a.L = m->L;
     const HdiffGrid g = hdiff_grid(m->W, m->H, m->L, nf);
     const dim3 grid(g.tiles_i, g.tiles_j, g.z);
-    if (z.order == 2) hipLaunchKernelGGL((pe_hdiff_kernel<T, 2>), grid, dim3(kHdThreads), 0, s, a);
+    if (!m->wrap) {                                        // a band that has opted in: its own rows, rows not periodic
+        if (z.order == 2) hipLaunchKernelGGL((pe_hdiff_kernel<T, 2, true>), grid, dim3(kHdThreads), 0, s, a);
+        else hipLaunchKernelGGL((pe_hdiff_kernel<T, 1, true>), grid, dim3(kHdThreads), 0, s, a);
+    } else if (z.order == 2) hipLaunchKernelGGL((pe_hdiff_kernel<T, 2>), grid, dim3(kHdThreads), 0, s, a);
     else hipLaunchKernelGGL((pe_hdiff_kernel<T, 1>), grid, dim3(kHdThreads), 0, s, a);
     if (hipGetLastError() != hipSuccess) { *err = "hip: horizontal diffusion kernel launch failed"; return GCM_ERR_HIP; }
     // the state takes the landing fields over: the own rows of a field are one contiguous run

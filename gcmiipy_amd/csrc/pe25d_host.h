@@ -173,8 +173,10 @@ struct PeBoundary {
 // gcm_set_hdiff(NULL) or gcm_destroy
 struct PeHdiff {
     bool on = false;                            // gcm_set_hdiff: registered
+    bool band = false;                          // gcm_set_band_hdiff: a band takes the phase over its own rows
+    bool band_done = false;                     // gcm_end_step_diffuse: a band's own rows are diffused for the step gcm_end_step_begin ends
     gcm_hdiff par{};                            // the registration's parameters
-    double *tab = nullptr;                      // device: ax bn bs area axv bnv bsv areav, [8][H]
+    double *tab = nullptr;                      // device: ax bn bs area axv bnv bsv areav, [8][H] (a band: [8][H + 4], rows -2 .. H + 1)
     std::vector<double> key;                    // order, fields, nu, cmax, dt
     int order = 0, fields = 0;                  // what the tables in place were built for
     void *land[GCM_NFIELDS] = {};

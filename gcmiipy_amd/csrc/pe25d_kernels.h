@@ -135,7 +135,7 @@ int pe25d_boundary_layer_tables(Pe25d *m, const gcm_boundary_layer *bl, double d
 int pe25d_boundary_layer_rows(Pe25d *m, int set, bool keep_ghosts, bool accumulate, hipStream_t s, std::string *err);
 // Horizontal diffusion (pe25d_hdiff.hip).  hdiff_check / hdiff_tables / hdiff_apply: no handle, no device
 // (gcm_hdiff_tables, gcm_hdiff_apply).  pe25d_hdiff_fits: what a registration or a step needs of the handle -- a single
-// domain, W >= 4 and H >= 4 (GCM_ERR_UNSUPPORTED); pe25d_set_hdiff: gcm_set_hdiff (d == nullptr: off, the landing fields
+// domain, W >= 4 and H >= 4, or a band that has opted in (GCM_ERR_UNSUPPORTED); pe25d_set_hdiff: gcm_set_hdiff (d == nullptr: off, the landing fields
 // and tables freed); pe25d_hdiff_on / pe25d_hdiff_par: the registration; pe25d_hdiff_tables: the device tables for (d, dt),
 // built and uploaded when either changed, and the landing fields of d's fields in place; pe25d_hdiff_rows: the launch
 // over every row of state set `set` (-1: the current one) into the landing fields and their way back into the state,
@@ -150,6 +150,17 @@ const gcm_hdiff *pe25d_hdiff_par(const Pe25d *m);
 int pe25d_hdiff_tables(Pe25d *m, const gcm_hdiff *d, double dt, hipStream_t s, std::string *err);
 int pe25d_hdiff_rows(Pe25d *m, int set, bool keep_ghosts, hipStream_t s, std::string *err);
 int pe25d_hdiff_plan(const Pe25d *m, int *out, int nout);
+// A latitude band (pe25d_set_band_hdiff: gcm_set_band_hdiff; GCM_ERR_STATE for on = false while the phase is registered,
+// GCM_ERR_UNSUPPORTED for on = true on a single domain) takes the band form of the kernel over its own rows, from the
+// ghost rows as they are; the ghost rows of the selected fields are stale behind it.  hdiff_apply_band: the host build
+// of that walk (gcm_hdiff_apply_band); hdiff_band_tables: a band's [8][Hb + 4] tables gathered from the global ones;
+// pe25d_band_hdiff_done: gcm_end_step_diffuse was called for the step gcm_end_step_begin is about to end
+int hdiff_apply_band(int Hb, int W, int nlev, const double *tab4, int order, const double *X, double *out, std::string *err);
+void hdiff_band_tables(int Hg, int row0, int Hb, const double *glob, double *out);
+int pe25d_set_band_hdiff(Pe25d *m, bool on, std::string *err);
+bool pe25d_band_hdiff(const Pe25d *m);
+bool pe25d_band_hdiff_done(const Pe25d *m);
+void pe25d_set_band_hdiff_done(Pe25d *m, bool done);
 int pe25d_new_state_set(const Pe25d *m);    // the set a corrector stage in flight writes (before the swap), else the current one
 int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], hipStream_t s, std::string *err);
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan

@@ -902,8 +902,8 @@ int gcm_spectra_reset(gcm_handle *h);
 int gcm_get_spectra(gcm_handle *h, double *s, int64_t *nsamples);
 int gcm_put_spectra(gcm_handle *h, const double *s, int64_t nsamples);
 /* Horizontal del-2 / del-4 diffusion of u, v, theta (and q) of GCM_PE25D on the device: the scale-selective dissipation a
- * lat-lon C-grid run needs besides the polar filter, which acts along i at high latitudes only (fp64 and fp32 handles,
- * single domains only).  gcm_set_hdiff registers it as a phase of every step taken by gcm_step, applied once per step
+ * lat-lon C-grid run needs besides the polar filter, which acts along i at high latitudes only (fp64 and fp32 handles;
+ * single domains, and latitude bands that have opted in: gcm_set_band_hdiff).  gcm_set_hdiff registers it as a phase of every step taken by gcm_step, applied once per step
  * directly behind the Matsuno step and ahead of the solar step; gcm_half_step and gcm_step_phase never apply it.
  * Grid: centres are (j, i); u lies between centres i and i + 1 on the centre latitude of row j; v lies between rows j
  * and j + 1, on dx_h[j]'s latitude.  i and j are periodic, as in the dynamics.  The diffusion acts on the model's sigma
@@ -932,9 +932,9 @@ int gcm_put_spectra(gcm_handle *h, const double *s, int64_t nsamples);
  * neither read nor written.  The launch is out of place: it writes landing fields of the handle's real type ([H][L][W]
  * per selected field, allocated by the registration or by the first explicit step and kept until gcm_set_hdiff(h, NULL)
  * or gcm_destroy), which the state then takes over by a device copy on the same stream.
- * Limits: latitude bands (nranks > 1) are refused -- the phase is not column-local, at order 2 it reads two rows beyond
- * the own rows, and a band's ghost rows cannot be advanced locally: a band needs an exchange of its own behind the
- * phase, which is not built; p and the passive tracers are not diffused; theta is not pressure-weighted (the diffusion
+ * Limits: latitude bands (nranks > 1) are refused by default -- the phase is not column-local, at order 2 it reads two
+ * rows beyond the own rows, and a band's ghost rows cannot be advanced locally: a band needs an exchange of its own
+ * behind the phase, which the opt-in below buys; p and the passive tracers are not diffused; theta is not pressure-weighted (the diffusion
  * conserves sum area theta per level, not the mass-weighted sum); over topography it mixes along sigma surfaces, not
  * pressure surfaces; no vector-Laplacian metric terms; the cap stands in for an implicit zonal solve.
  * gcm_set_hdiff(h, d) registers (d == NULL: off, and frees the landing fields and tables); registering again replaces the
@@ -944,15 +944,35 @@ int gcm_put_spectra(gcm_handle *h, const double *s, int64_t nsamples);
  * gcm_hdiff_step: the same launch once, in place on the current state, with d's parameters and no registration.
  * gcm_hdiff_apply: the host build of the very cell routine the kernel calls, over X [nlev][H][W] float64 with tab4 [4][H]
  * = ax bn bs area (or the v rows' four), periodic both ways, into out; no handle, no device.
- * gcm_hdiff_plan: the launch geometry of this handle without launching, GCM_HDIFF_PLAN_WORDS words, at the registered
+ * Latitude bands.  gcm_set_band_hdiff(h, on): GCM_PE25D latitude bands only -- other models, and a single domain with
+ * on != 0, are GCM_ERR_UNSUPPORTED (on = 0 on a single domain: nothing to do); called right after gcm_create, on every
+ * band of a run; on = 0 while the phase is registered is GCM_ERR_STATE; a null handle GCM_ERR_ARG; a refused call changes
+ * nothing.  The opt-in alone launches nothing and changes no result, message size (gcm_halo_bytes) or timing; without it
+ * a band stays refused.  gcm_band_hdiff: 1 on a band that has opted in, else 0 (a null handle GCM_ERR_ARG).  After the
+ * opt-in gcm_set_hdiff and gcm_hdiff_step are accepted (W >= 4, 2 own rows or more).  A band's u, v, theta and q carry
+ * two ghost rows a side, the phase sits directly behind the corrector, whose exchange has just filled them, and the
+ * order-2 stencil has radius 2: the band's own rows are diffused from what is there, with the coefficients of the
+ * global rows (row0 + j) mod global_height, to the single domain's bits.  The ghost rows themselves cannot be (ghost
+ * row -1 would need row -3): they are stale behind the launch, and the current state's edge rows are exchanged once
+ * more before anything reads them -- one more message of gcm_halo_bytes per neighbour and step, in the existing message
+ * and buffers.  With the phase registered gcm_band_run does that itself under every orchestration: the own rows'
+ * diffusion and its copy back behind the corrector's unpack, the pack, the exchange, the unpack, then the ghost rows'
+ * phases and the walk as without it (with the boundary layer registered too: four exchanges per step).  A host that
+ * drives the exchange itself: gcm_end_step_diffuse below.  gcm_hdiff_step on a band diffuses the own rows from current
+ * ghost rows and leaves the ghost rows of the selected fields stale until the caller's next exchange.
+ * gcm_hdiff_apply_band: the host build of the band walk, periodic in i only: X [nlev][Hb + 4][W] float64 holds the
+ * band's Hb own rows with two ghost rows a side (rows -2 .. Hb + 1), tab4 [4][Hb + 4] = ax bn bs area (or the v rows'
+ * four) of those rows, out [nlev][Hb][W] the own rows -- rows [row0, row0 + Hb) of gcm_hdiff_apply over the periodic
+ * whole, bit for bit; no handle, no device.
+ * gcm_hdiff_plan: the launch geometry of this handle without launching (a band: its own rows' tiles), GCM_HDIFF_PLAN_WORDS words, at the registered
  * order and fields, else at order 2 and U|V|T:
  *   [0] tile rows  [1] tile columns  [2] tiles in i  [3] tiles in j  [4] grid z (selected fields x levels)
  *   [5] LDS bytes  [6] kernel launches per application
  * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, no parameters in
  * gcm_hdiff_step, order not 1 or 2, fields 0 or with unknown bits, nu not finite or <= 0, cmax outside (0, 1/8], a
  * non-finite dt, the probes' null pointers, H, W or nlev < 1, nout < GCM_HDIFF_PLAN_WORDS (message of the probes:
- * gcm_last_error(NULL)).  GCM_ERR_UNSUPPORTED: other models, a handle created with nranks > 1, W < 4 or H < 4 (the
- * radius-2 halo wraps once only).                                                                                     */
+ * gcm_last_error(NULL)).  GCM_ERR_UNSUPPORTED: other models, a handle created with nranks > 1 that has not opted in,
+ * W < 4 or, on a single domain, H < 4 (the radius-2 halo wraps once only).                                            */
 #define GCM_HDIFF_U 1
 #define GCM_HDIFF_V 2
 #define GCM_HDIFF_T 4
@@ -969,9 +989,13 @@ int gcm_hdiff_on(const gcm_handle *h);
 int gcm_hdiff_step(gcm_handle *h, double dt, const gcm_hdiff *d);
 int gcm_hdiff_tables(int H, const double *dx_j, const double *dx_h, double dy, const gcm_hdiff *d, double dt, double *out);
 int gcm_hdiff_apply(int H, int W, int nlev, const double *tab4, int order, const double *X, double *out);
+int gcm_hdiff_apply_band(int Hb, int W, int nlev, const double *tab4, int order, const double *X, double *out);
 int gcm_hdiff_plan(gcm_handle *h, int *out, int nout);
+int gcm_set_band_hdiff(gcm_handle *h, int on);
+int gcm_band_hdiff(const gcm_handle *h);
 /* The end of a GCM_PE25D step whose dynamics the caller took itself: everything gcm_step and gcm_band_run queue behind
- * the corrector, in their order and by their code -- the horizontal diffusion (gcm_set_hdiff: single domains only), the
+ * the corrector, in their order and by their code -- the horizontal diffusion (gcm_set_hdiff: a single domain's; a band's:
+ * gcm_end_step_diffuse), the
  * solar step at the handle's clock, utc += dt, the Held-Suarez
  * forcing, the boundary layer, the convective adjustment, the moist physics (their sums, seconds and
  * nsteps advance as in gcm_step), the
@@ -991,8 +1015,16 @@ int gcm_hdiff_plan(gcm_handle *h, int *out, int nout);
  * current state between the two -- gcm_halo_pack2, the transfer, gcm_halo_unpack2 -- and gcm_end_step itself refuses such
  * a band (GCM_ERR_STATE, the message names the two calls); on a single domain, or a band without the phase, nothing
  * needs to happen between them.
+ * gcm_end_step_diffuse is the part ahead of gcm_end_step_begin: on a band with the horizontal diffusion registered
+ * (gcm_set_band_hdiff) it queues the diffusion of the band's own rows, behind the unpack of the post-corrector exchange;
+ * the caller then exchanges the current state (gcm_halo_pack2, the transfer, gcm_halo_unpack2) and calls
+ * gcm_end_step_begin.  On every other GCM_PE25D handle it returns GCM_OK and queues nothing: a single domain keeps its
+ * diffusion at the head of gcm_end_step_begin / gcm_end_step.  On such a band gcm_end_step is GCM_ERR_STATE, and so is
+ * gcm_end_step_begin without a gcm_end_step_diffuse ahead of it for the step (the messages name the calls; a refused
+ * call changes nothing).
  * Errors: a null handle GCM_ERR_ARG; other models GCM_ERR_UNSUPPORTED; a non-finite dt GCM_ERR_ARG, and nothing changes. */
 int gcm_end_step(gcm_handle *h, double dt);
+int gcm_end_step_diffuse(gcm_handle *h, double dt);
 int gcm_end_step_begin(gcm_handle *h, double dt);
 int gcm_end_step_finish(gcm_handle *h, double dt);
 
