@@ -227,6 +227,23 @@ def merge_climate(parts):
     return Climate(parts[0].n, *[np.concatenate([c[f] for c in parts], axis=-1) for f in range(1, len(Climate._fields))])
 
 
+def merge_plev_climate(parts):
+    """the pressure-level climatology of the whole domain from its bands': `parts` are the bands' PlevClimate records
+    (Core.plev_climate) in row order; the rows of the coverage and of the means are concatenated.  ValueError where the
+    sample counts or the targets differ"""
+    import numpy as np
+    from .core import PlevClimate
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_plev_climate: no records")
+    if any(c.n != parts[0].n for c in parts):
+        raise ValueError("merge_plev_climate: the bands hold %s samples" % ", ".join(str(c.n) for c in parts))
+    if any(not np.array_equal(c.plev, parts[0].plev) for c in parts):
+        raise ValueError("merge_plev_climate: the bands hold different pressure targets")
+    return PlevClimate(parts[0].n, np.array(parts[0].plev, dtype=np.float64),
+                       *[np.concatenate([c[f] for c in parts], axis=-1) for f in range(2, len(PlevClimate._fields))])
+
+
 def merge_spectra(parts):
     """the spectra of the whole domain from its bands': `parts` are the bands' Spectra records (Core.spectra) in row
     order; the rows are concatenated.  ValueError where the sample counts or the numbers of wavenumbers differ"""
@@ -302,7 +319,7 @@ class LoopbackExchange:
 
 class HipBandEngine:
     """A `Core` band + torch CUDA buffers/streams for the exchange.  It keeps no registrations: the phases behind the
-    dynamics (set_physics ... set_climate, set_spectra) are the handle's, and a host-driven step ends with the library's own walk
+    dynamics (set_physics ... set_climate, set_plev_climate, set_spectra) are the handle's, and a host-driven step ends with the library's own walk
     over them (Core.end_step), the one gcm_band_run takes."""
 
     def __init__(self, core, torch, overlap=True, stream_aware=True):
@@ -389,6 +406,11 @@ class HipBandEngine:
         """Core.set_climate; every band of a run registers the same interval.  merge_climate() puts the bands' records
         together"""
         self.c.set_climate(every)
+
+    def set_plev_climate(self, every=1, plev=None):
+        """Core.set_plev_climate; every band of a run registers the same interval and targets.  merge_plev_climate() puts
+        the bands' records together"""
+        self.c.set_plev_climate(every, plev)
 
     def set_spectra(self, every=1, mmax=None):
         """Core.set_spectra; every band of a run registers the same interval and mmax.  merge_spectra() puts the bands'

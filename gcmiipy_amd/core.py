@@ -110,6 +110,85 @@ class Climate(collections.namedtuple("Climate", ("n",) + CLIMATE_WORDS3 + CLIMAT
             return cls(int(n), *[m3[w] / d for w in range(len(CLIMATE_WORDS3))], *[m2[w] / d for w in range(len(CLIMATE_WORDS2))])
 
 
+# the conditional means of gcm_get_plev_climate's words 1 .. 12 (word 0 is the count)
+PLEV_WORDS = ("u", "v", "theta", "T", "q", "uu", "vv", "TT", "uv", "vT", "vtheta", "vq")
+
+
+def plev_array(plev):
+    """pressure targets as the C ABI takes them: float64 (N,), 1 <= N <= PLEV_MAX, in Pa, finite, positive and strictly
+    decreasing; ValueError otherwise, before any device use"""
+    P = as_f64(np.asarray(plev, dtype=np.float64).reshape(-1), name="plev")
+    if not 1 <= P.size <= _lib.PLEV_MAX:
+        raise ValueError("%d pressure targets: 1 .. %d" % (P.size, _lib.PLEV_MAX))
+    if not (np.all(np.isfinite(P)) and np.all(P > 0.0) and np.all(np.diff(P) < 0.0)):
+        raise ValueError("pressure targets must be finite, positive and strictly decreasing (Pa)")
+    return P
+
+
+class PlevClimate(collections.namedtuple("PlevClimate", ("n", "plev", "coverage") + PLEV_WORDS)):
+    """the zonal-mean climatology of a GCM_PE25D handle on pressure levels (Core.plev_climate): n, the number of
+    samples; plev (N,), the targets in Pa; coverage (N, H) = count / (W n), the fraction of columns and samples in
+    which the target was valid; and the twelve conditional means over the valid columns, each (N, H) and NaN where the
+    count is 0 -- the device's float64 sums divided by the count: u = uc, v = vc (the winds at the cell centre), theta,
+    T = theta Pi, q, uu, vv, TT, uv, vT, vtheta, vq, products of the interpolated values.  A band: its own rows
+    (bands.merge_plev_climate)"""
+    __slots__ = ()
+
+    @property
+    def eddy_momentum_flux(self):
+        """[u'v'] = uv - [u][v]: all three are means over the same valid cell centres"""
+        return self.uv - self.u * self.v
+
+    @property
+    def eddy_heat_flux(self):
+        """[v'T'] = vT - [v][T]"""
+        return self.vT - self.v * self.T
+
+    @property
+    def eddy_theta_flux(self):
+        """[v'theta'] = vtheta - [v][theta]"""
+        return self.vtheta - self.v * self.theta
+
+    @property
+    def eddy_moisture_flux(self):
+        """[v'q'] = vq - [v][q]: the eddies' share of the meridional moisture transport vq"""
+        return self.vq - self.v * self.q
+
+    @property
+    def T_variance(self):
+        """[T'T'] = TT - [T]^2: the eddy temperature variance"""
+        return self.TT - self.T * self.T
+
+    @property
+    def eke(self):
+        """0.5 (uu - [u]^2 + vv - [v]^2): the eddy kinetic energy per unit mass of the centred winds"""
+        return 0.5 * (self.uu - self.u * self.u + self.vv - self.v * self.v)
+
+    @classmethod
+    def from_sums(cls, n, plev, s, width):
+        """the record of the raw sums s (13, N, H) of n samples of rows of `width` columns at the targets plev"""
+        s = np.asarray(s, dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            count = np.where(s[0] > 0.0, s[0], np.nan)
+            cover = s[0] / (np.float64(width) * np.float64(n))
+            return cls(int(n), np.array(plev, dtype=np.float64), cover, *[s[w + 1] / count for w in range(len(PLEV_WORDS))])
+
+
+def plev_columns(pl, x, plev):
+    """the sigma -> p column rule on the host (gcm_plev_columns; the host build of the routines the kernels call, no
+    handle, no device) over columns pl, x of shape (..., L), level 0 the bottom, at the targets plev (N,)
+    -> (out (..., N), valid (..., N) bool); out holds NaN where a target is invalid.  ValueError for a refused argument"""
+    pl = np.asarray(pl, dtype=np.float64)
+    L = pl.shape[-1] if pl.ndim else 0
+    pp = as_f64(pl.reshape(-1, L) if L else pl, name="pl")
+    xx = as_f64(x, pl.shape, "x").reshape(pp.shape)
+    P = plev_array(plev)
+    out = np.full((pp.shape[0], P.size), np.nan)
+    valid = np.zeros((pp.shape[0], P.size), dtype=np.intc)
+    _check(lib.gcm_plev_columns(pp.shape[0], L, P.size, _tab(pp), _tab(xx), _tab(P), _tab(out), valid.ctypes.data_as(C.POINTER(C.c_int))))
+    return out.reshape(pl.shape[:-1] + (P.size,)), valid.reshape(pl.shape[:-1] + (P.size,)).astype(bool)
+
+
 SPECTRA_WORDS = ("uu", "vv", "TT", "uv", "vT", "vtheta")    # the products of gcm_get_spectra's s
 
 
@@ -1395,6 +1474,82 @@ class Core:
         climatology is registered"""
         n, m3, m2 = self.climate_sums()
         return Climate.from_sums(n, m3, m2, self.W)
+
+    # -- pressure levels (GCM_PE25D) -------------------------------------------------------
+    def plev_fields(self, plev, fill=np.nan):
+        """-> (out (5, N, H, W), valid (N, H, W) bool): uc, vc, theta, T and q of the current state interpolated to the
+        pressures plev (Pa, strictly decreasing), linearly in pressure, by one launch (gcm_plev_fields); `fill` where the
+        pressure lies under the ground or above the top mid-level.  The call holds 8 * 5 * N * H * W bytes of device
+        memory (and the mask's 4 N H W) while it runs: meant for a handful of levels now and then, not for all of them
+        every step.  A band: the ghost rows of the current state must be current, as for climate_sample"""
+        P = plev_array(plev)
+        out = np.empty((5, P.size, self.H, self.W))
+        valid = np.empty((P.size, self.H, self.W), dtype=np.int32)
+        _check(lib.gcm_plev_fields(self._h, P.size, _tab(P), float(fill), _tab(out), valid.ctypes.data_as(C.POINTER(C.c_int32))),
+               self._h)
+        return out, valid.astype(bool)
+
+    def set_plev_climate(self, every=1, plev=None):
+        """accumulate the zonal-mean climatology on pressure levels on the device (gcm_set_plev_climate): from now on
+        every `every`-th step of step() / band_run() / end_step() ends with one launch that interpolates every column to
+        the pressures plev (Pa, strictly decreasing) and adds the zonal sums of the words of `PlevClimate` over the
+        valid columns to float64 sums in the handle, directly behind the sigma climatology's sample.  The step counter
+        is the registration's own.  Registering again resets; every=0 unregisters"""
+        if int(every) == 0:
+            _check(lib.gcm_set_plev_climate(self._h, 0, 0, None), self._h)
+            return
+        if int(every) < 0:
+            raise ValueError("every must be >= 0")
+        P = plev_array(plev)
+        _check(lib.gcm_set_plev_climate(self._h, int(every), P.size, _tab(P)), self._h)
+
+    @property
+    def plev_climate_every(self):
+        """the registered sampling interval in steps, 0 where none is registered (gcm_plev_climate_every)"""
+        return _count(lib.gcm_plev_climate_every(self._h), self._h)
+
+    @property
+    def plev_climate_levels(self):
+        """the registered targets (N,) in Pa (gcm_plev_climate_levels); GcmError where none are registered"""
+        P = np.empty(_lib.PLEV_MAX)
+        n = _count(lib.gcm_plev_climate_levels(self._h, _tab(P), _lib.PLEV_MAX), self._h)
+        return P[:n].copy()
+
+    def plev_climate_plan(self):
+        """the launch geometry of a sample of this handle, without launching (gcm_plev_climate_plan): grid_x (rows),
+        nseg (target segments; 0 without a registration), targets (per segment), threads, lds_bytes, chunks (256-column
+        chunks of a row)"""
+        out = (C.c_int * _lib.PLEV_PLAN_WORDS)()
+        _check(lib.gcm_plev_climate_plan(self._h, out, _lib.PLEV_PLAN_WORDS), self._h)
+        return dict(grid_x=out[0], nseg=out[1], targets=out[2], threads=out[3], lds_bytes=out[4], chunks=out[5])
+
+    def plev_climate_sample(self):
+        """one sample of the current state now (gcm_plev_climate_sample); the step counter is untouched.  A band: the
+        ghost rows of the current state must be current, as for climate_sample"""
+        _check(lib.gcm_plev_climate_sample(self._h), self._h)
+
+    def plev_climate_reset(self):
+        """zero the sums and the sample count (gcm_plev_climate_reset)"""
+        _check(lib.gcm_plev_climate_reset(self._h), self._h)
+
+    def plev_climate_sums(self):
+        """-> (n, s (13, N, H)): the raw float64 sums as the device holds them (gcm_get_plev_climate), word 0 the count
+        of valid columns; one synchronisation"""
+        s = np.empty((_lib.PLEV_WORDS, self.plev_climate_levels.size, self.H))
+        n = C.c_int64(0)
+        _check(lib.gcm_get_plev_climate(self._h, _tab(s), C.byref(n)), self._h)
+        return int(n.value), s
+
+    def put_plev_climate(self, n, s):
+        """upload sums taken by plev_climate_sums() (gcm_put_plev_climate): a restart goes on where the run stopped"""
+        s = as_f64(s, (_lib.PLEV_WORDS, self.plev_climate_levels.size, self.H), "s")
+        _check(lib.gcm_put_plev_climate(self._h, _tab(s), int(n)), self._h)
+
+    def plev_climate(self):
+        """-> PlevClimate: the sample count, the targets, the coverage and the conditional means, the sums divided by
+        the count (gcm_get_plev_climate).  GcmError where none is registered"""
+        n, s = self.plev_climate_sums()
+        return PlevClimate.from_sums(n, self.plev_climate_levels, s, self.W)
 
     # -- zonal wavenumber spectra (GCM_PE25D) ----------------------------------------------
     def set_spectra(self, every=1, mmax=None):

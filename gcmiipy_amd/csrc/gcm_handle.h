@@ -153,7 +153,7 @@ extern "C" void step_rows(gcm_handle *h, double dt, int j0, int j1, hipStream_t 
 extern "C" void swap_state(gcm_handle *h);
 extern "C" int launch_status(gcm_handle *h);
 
-// gcm_pe.hip, for gcm_step, gcm_band_run and gcm_end_step: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, boundary layer, convective adjustment, moist physics, the climatology's sample, the spectra's sample), each
+// gcm_pe.hip, for gcm_step, gcm_band_run and gcm_end_step: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, boundary layer, convective adjustment, moist physics, the climatology's sample, the pressure-level climatology's sample, the spectra's sample), each
 // launched only if it is registered -- their tables before a run, a band's ghost rows on its second stream `ax` behind a
 // corrector's unpack, and the end of every step on the handle's stream over rows [-g, H + g), which joins `tail` before a sample
 // The walk splits at the boundary layer (`which`): a band that carries it exchanges the current state's edge rows between

@@ -9,6 +9,7 @@
 //   pe25d_held_suarez.hip  the Held-Suarez forcing: its table routine, its kernel and its launches
 //   pe25d_climate.hip  the zonal-mean climatology: its kernel, its sums and their way to the host and back
 //   pe25d_spectra.hip  the zonal wavenumber spectra: their kernel, their sums and their way to the host and back
+//   pe25d_plev.hip     pressure levels: the column rule's host build, the map and sample kernels, the sample's sums
 //   pe25d_moist.hip    moist physics: the saturation routine, the kernel and its launches
 //   pe25d_convect.hip  convective adjustment: the pooling routine, the kernel and its launches
 //   pe25d_convect_tracers.hip  the tracers' convective mixing in the adjustment's blocks: the kernel, its launch, the opt-ins
@@ -18,7 +19,7 @@
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
 // gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
 // pe25d_hdiff_rows, pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample,
-// pe25d_spectra_due, pe25d_spectra_sample).
+// pe25d_plev_climate_due, pe25d_plev_climate_sample, pe25d_spectra_due, pe25d_spectra_sample).
 #pragma once
 #include "pe25d_kernels.h"
 
@@ -110,6 +111,16 @@ struct PeHeldSuarez {
 // Zonal-mean climatology (pe25d_climate.hip, gcm_set_climate): the float64 sums on the device and the two counters
 struct PeClimate {
     double *buf = nullptr;                      // device: sig [L], m3 [GCM_CLIM_WORDS3][L][H], m2 [GCM_CLIM_WORDS2][H]
+    int every = 0;                              // a sample every so many steps; 0: not registered
+    long long steps = 0;                        // steps taken by gcm_step / gcm_band_run since the registration
+    long long n = 0;                            // samples in the sums
+};
+
+// Zonal-mean climatology on pressure levels (pe25d_plev.hip, gcm_set_plev_climate): the targets and the float64 sums on
+// the device, the targets' host copy (its size is N) and the two counters
+struct PePlevClimate {
+    double *buf = nullptr;                      // device: P [N], s [GCM_PLEV_WORDS][N][H]
+    std::vector<double> P;                      // the registered targets, Pa
     int every = 0;                              // a sample every so many steps; 0: not registered
     long long steps = 0;                        // steps taken by gcm_step / gcm_band_run since the registration
     long long n = 0;                            // samples in the sums
@@ -256,6 +267,7 @@ struct Pe25d {
     PeTracers tr;
     PeHeldSuarez hs;
     PeClimate clim;
+    PePlevClimate plev;
     PeSpectra spec;
     PeMoist moist;
     PeConvect convect;

@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
+// pe25d_climate.hip, pe25d_plev.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +65,21 @@ int pe25d_climate_sample(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_climate_reset(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_get_climate(Pe25d *m, double *m3, double *m2, int64_t *nsamples, hipStream_t s, std::string *err);
 int pe25d_put_climate(Pe25d *m, const double *m3, const double *m2, int64_t nsamples, hipStream_t s, std::string *err);
+// Pressure levels (pe25d_plev.hip).  plev_columns: no handle, no device (gcm_plev_columns).  pe25d_plev_fields:
+// gcm_plev_fields on `s`, synchronised before it returns.  gcm_set_plev_climate and its companions on `s`, the caller's
+// stream: pe25d_plev_climate_due counts one step, as pe25d_climate_due does; pe25d_plev_climate_levels: -1 without a
+// registration; pe25d_plev_climate_plan: gcm_plev_climate_plan
+int plev_columns(int ncol, int L, int N, const double *pl, const double *x, const double *P, double *out, int *valid, std::string *err);
+int pe25d_plev_fields(Pe25d *m, int N, const double *P, double fill, double *out, int32_t *valid, hipStream_t s, std::string *err);
+int pe25d_set_plev_climate(Pe25d *m, int every, int N, const double *P, hipStream_t s, std::string *err);
+int pe25d_plev_climate_every(const Pe25d *m);
+int pe25d_plev_climate_levels(const Pe25d *m, double *P, int cap);
+bool pe25d_plev_climate_due(Pe25d *m);
+int pe25d_plev_climate_plan(const Pe25d *m, int *out, int nout);
+int pe25d_plev_climate_sample(Pe25d *m, hipStream_t s, std::string *err);
+int pe25d_plev_climate_reset(Pe25d *m, hipStream_t s, std::string *err);
+int pe25d_get_plev_climate(Pe25d *m, double *sums, int64_t *nsamples, hipStream_t s, std::string *err);
+int pe25d_put_plev_climate(Pe25d *m, const double *sums, int64_t nsamples, hipStream_t s, std::string *err);
 // Zonal wavenumber spectra (pe25d_spectra.hip): gcm_set_spectra and its companions on `s`, the caller's stream.
 // pe25d_spectra_due: counts one step, as pe25d_climate_due does; pe25d_spectra_mmax: -1 without a registration;
 // pe25d_spectra_plan: gcm_spectra_plan

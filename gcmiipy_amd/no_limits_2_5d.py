@@ -60,7 +60,7 @@ def full_timestep(p, u, v, t, q, g, dt, utc, geom, stats=STATS):
 
 
 def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=None, physics=False, tracers=None,
-              tracer_scheme=None, tracer_forcing=None, held_suarez=False, climate=0, spectra=0):
+              tracer_scheme=None, tracer_forcing=None, held_suarez=False, climate=0, spectra=0, plev_climate=None):
     """no_limits_2_5d.py:220-236 (and test_geography.py:6-23 with `bump=(j, i, metres)`): the
     state stays in HBM for all `timesteps`; STATS come from device reductions every step.
     physics=True: every step is followed by solar_timestep(t, p, g, dt, utc, geom) with utc = 0, dt, 2 dt, ...
@@ -76,7 +76,9 @@ def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=
     with a sample of the zonal-mean climatology on the device, and its record (Core.climate) is appended to the
     result (Core.set_climate).  spectra=every (> 0): every `every`-th step ends with a sample of the zonal wavenumber
     spectra on the device, at the default mmax, and their record (Core.spectra) is appended to the result behind the
-    climatology's (Core.set_spectra)."""
+    climatology's (Core.set_spectra).  plev_climate=(every, plev): every `every`-th step ends with a sample of the
+    zonal-mean climatology on the pressure levels plev (Pa, strictly decreasing) on the device, and its record
+    (Core.plev_climate) is appended to the result last (Core.set_plev_climate)."""
     if tracer_forcing and tracers is None:
         raise ValueError("tracer_forcing needs tracers")
     geom = geometry.gen_geometry(height, width, layers, sig_func=geometry.manabe_sig)
@@ -101,6 +103,8 @@ def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=
             c.set_climate(int(climate))
         if spectra:
             c.set_spectra(int(spectra))
+        if plev_climate:
+            c.set_plev_climate(int(plev_climate[0]), plev_climate[1])
         for _ in range(timesteps):
             c.step(1, scalar(dt))
             _record(c, geom, stats)
@@ -113,7 +117,8 @@ def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=
             tracers = c.get_tracers()
         clim = c.climate() if climate else None
         spec = c.spectra() if spectra else None
+        plev = c.plev_climate() if plev_climate else None
     finally:
         c.close()
     out = (p, u, v, t, q, g, geom) + ((tracers,) if tracers is not None else ())
-    return out + ((clim,) if climate else ()) + ((spec,) if spectra else ())
+    return out + ((clim,) if climate else ()) + ((spec,) if spectra else ()) + ((plev,) if plev_climate else ())

@@ -843,6 +843,78 @@ int gcm_climate_sample(gcm_handle *h);
 int gcm_climate_reset(gcm_handle *h);
 int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples);
 int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples);
+/* GCM_PE25D on pressure levels: the sigma -> p step on the device.  The climatology and the spectra above live on the
+ * model's sigma surfaces; figures are drawn against pressure, and over topography a zonal mean along sigma mixes air of
+ * very different pressures.  Every column of the current state is interpolated to a fixed list of pressures and masked
+ * where the pressure lies under the ground or above the top mid-level; the result comes back as maps (gcm_plev_fields)
+ * or is reduced zonally into float64 sums that live in the handle (gcm_set_plev_climate), the way the sigma climatology
+ * is.  fp64 and fp32 handles, single domains and latitude bands.
+ * The column rule -- float64, storage values widened exactly, every operation rounded on its own (no contraction):
+ *   Levels run k = 0 (bottom) .. L - 1 (top), as the geometry has them.  pl[k] = sig[k] p + ptop, p the handle's p
+ *   field (surface pressure minus ptop); pl decreases strictly with k wherever p > 0.
+ *   Targets P[n], n = 0 .. N - 1, in Pa: full pressure, finite, positive and strictly decreasing (the direction of k),
+ *   1 <= N <= GCM_PLEV_MAX.
+ *   Target n of a column is VALID iff pl[L - 1] <= P[n] <= pl[0] (and pl[L - 1] < pl[0]): no extrapolation, below the
+ *   ground or above the top mid-level.  A column with p <= 0 or a NaN p has no valid target.
+ *   For a valid target: k is the largest index in 0 .. L - 2 with pl[k] >= P[n];  w = (pl[k] - P[n]) / (pl[k] - pl[k + 1])
+ *   (the correctly rounded float64 division);  x_n = (1 - w) x[k] + w x[k + 1]: a target that sits exactly on a level
+ *   returns that level's value exactly.  NaN in a value propagates; it never decides validity.
+ *   Linear in pressure on purpose: the rule needs no transcendental, so the mask and the interpolated uc, vc, theta and q
+ *   can be restated bit for bit.  Log-pressure weights and the geopotential height on pressure levels are not offered.
+ * Five cell-centre quantities are interpolated, formed per level exactly as the climatology forms them:
+ *   uc = 0.5 (u[i] + u[i - 1]), periodic in i;  vc = 0.5 (v[j] + v[j - 1]);  theta;  T = theta Pi(pl), formed on the
+ *   sigma level with the kernels' own Exner routine and then interpolated;  q.  Row -1 is row H - 1 on a single domain
+ *   and v's first north ghost row on a band.
+ * gcm_plev_columns: the host build of the rule, from the header the kernels compile from; no handle, no device.  pl and
+ *   x are [ncol][L], out and valid [ncol][N]; out is left untouched where a target is invalid.  GCM_ERR_ARG: a null
+ *   pointer, L < 2, N out of range, targets that are not strictly decreasing, positive and finite.
+ * gcm_plev_fields: one launch interpolates the current state's five quantities to the N targets.  out [5][N][H][W]
+ *   float64 in the order uc, vc, theta, T, q; an invalid entry holds `fill`.  valid [N][H][W] may be NULL.  The call
+ *   holds 8 * 5 * N * H * W bytes of device memory for its duration (4 N H W more where valid is asked for) and releases
+ *   them: it is meant for a handful of levels now and then, not for all of them every step.  On a band the ghost rows
+ *   must be current, as for gcm_climate_sample.  A pure reader of the state; it synchronises the handle's stream.
+ * gcm_set_plev_climate(every >= 1, N, P): the accumulating sample.  Sums s [GCM_PLEV_WORDS][N][H], float64, plain sums
+ *   over i and over the samples; nothing is divided on the device:
+ *     0 count (1.0 per valid column)   1 uc   2 vc   3 theta   4 T   5 q   6 uc uc   7 vc vc   8 T T   9 uc vc
+ *     10 vc T   11 vc theta   12 vc q            (products of the interpolated values)
+ *   An invalid column contributes 0.0 to every word; the host forms the conditional means s[w] / s[0].
+ *   Reduction order of a row's W terms: the climatology's, a function of W alone -- 256 partial sums over
+ *   i = t, t + 256, ... starting from 0.0, the butterfly x[t] <- x[t] + x[t ^ d], d = 32 .. 1, within each 64, the four
+ *   groups in order; the row's sum is then added to the accumulator word, sample after sample.  One writer per word and
+ *   launch, no atomics.  A row's contribution does not depend on H, the band, the CU count or how the targets are split
+ *   over the grid: a band's rows hold the bits of the same rows of the single domain.
+ *   The registration allocates and zeroes the sums, copies the targets and starts a step counter of its own; it holds
+ *   8 (N + GCM_PLEV_WORDS N H) bytes on the device.  From then on every `every`-th step of gcm_step, gcm_band_run and
+ *   gcm_end_step / gcm_end_step_finish ends with one sample, directly behind the sigma climatology's and ahead of the
+ *   spectra's; on a band the compute stream joins the exchange stream's tail once for all the samples due on that step.
+ *   gcm_half_step and gcm_step_phase never sample.  Registering again resets sums, count and counter; every = 0
+ *   unregisters and frees.  Without a registration nothing is launched and every result and timing is as before; a
+ *   sample changes nothing a step reads.
+ * gcm_plev_climate_every: the registered `every`, 0 without one (other models: 0).  gcm_plev_climate_levels: copies up
+ *   to cap targets to P (may be NULL) and returns N.  gcm_plev_climate_sample: one sample now, the counter untouched; a
+ *   band's ghost rows must be current.  gcm_plev_climate_reset zeroes the sums and the count.  gcm_get_plev_climate
+ *   synchronises the handle's stream once and copies the sums and the count; either pointer may be NULL.
+ *   gcm_put_plev_climate uploads them (restarts): s is required, nsamples >= 0.
+ * gcm_plev_climate_plan: the launch geometry of a sample, without launching, GCM_PLEV_PLAN_WORDS words:
+ *   [0] grid x = rows  [1] target segments (grid y; 0 without a registration)  [2] targets per segment  [3] threads
+ *   [4] LDS bytes  [5] 256-column chunks per row.  A segment reads, per column, only the levels that bracket its targets.
+ * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, every < 0, bad targets.
+ * GCM_ERR_UNSUPPORTED: other models, L < 2.  (A thread keeps its column's p in a register, so no row is too wide for the
+ * launch's LDS.)  GCM_ERR_STATE: levels, get, put, reset or sample without a registration.  GCM_ERR_HIP: an allocation
+ * that fails; nothing stays registered then.                                                                          */
+#define GCM_PLEV_MAX 64         /* targets of a call or a registration */
+#define GCM_PLEV_WORDS 13       /* sums per (target, row)              */
+#define GCM_PLEV_PLAN_WORDS 6
+int gcm_plev_columns(int ncol, int L, int N, const double *pl, const double *x, const double *P, double *out, int *valid);
+int gcm_plev_fields(gcm_handle *h, int N, const double *P, double fill, double *out, int32_t *valid);
+int gcm_set_plev_climate(gcm_handle *h, int every, int N, const double *P);
+int gcm_plev_climate_every(const gcm_handle *h);
+int gcm_plev_climate_levels(const gcm_handle *h, double *P, int cap);
+int gcm_plev_climate_sample(gcm_handle *h);
+int gcm_plev_climate_reset(gcm_handle *h);
+int gcm_get_plev_climate(gcm_handle *h, double *s, int64_t *nsamples);
+int gcm_put_plev_climate(gcm_handle *h, const double *s, int64_t nsamples);
+int gcm_plev_climate_plan(gcm_handle *h, int *out, int nout);
 /* Zonal wavenumber spectra of GCM_PE25D accumulated on the device: the kinetic-energy and temperature spectra by zonal
  * wavenumber and the split of the eddy momentum and heat fluxes over the waves, which the zonal sums of the climatology
  * cannot give, without a host round trip per step (fp64 and fp32 handles, single domains and latitude bands).  One launch
