@@ -28,6 +28,14 @@ HDIFF_PLAN_WORDS = 7                 # GCM_HDIFF_PLAN_WORDS
 SW2D_PLAN_WORDS = 9                  # GCM_SW2D_PLAN_WORDS
 PHASE_HELD_SUAREZ, PHASE_MOIST, PHASE_CLIMATE, PHASE_TRACER_FORCING = range(4)   # gcm_pe25d_phase
 PHASE_PLAN_WORDS = 5                 # GCM_PHASE_PLAN_WORDS
+# GCM_STAGE_*: the words of gcm_pe25d_stage_geometry / gcm_pe25d_stage_plan in order, as Core.stage_plan() names them
+STAGE_WORDS = ("k1_loop", "k1_maxr", "k1_mask", "k1_nin", "k1_nw", "k1_passes", "k1_workgroups_per_row", "k1_pairs_per_wg",
+               "k1_pairs_last_wg", "k1_pit_rides", "k4_rows", "k4_groups", "k4_rows_last_group", "k4_col_tiles",
+               "k4_cols_last_tile", "k4_nseg", "k4_oddtop", "k4_grid", "band", "k1_split", "k1_own_workgroups_per_row",
+               "k1_own_pairs_per_wg", "k1_own_pairs_last_wg", "k4_edge_groups", "k4_edge_rows_last_group", "k4_edge_oddtop",
+               "k4_edge_grid", "nseg_edge", "k4_int_groups", "k4_int_rows_last_group", "k4_int_oddtop", "k4_int_grid")
+STAGE_PLAN_WORDS = 32                # GCM_STAGE_PLAN_WORDS
+STAGE_BAND_WORD = 18                 # GCM_STAGE_BAND: the words from here on describe a band's split stage
 ADV_UPWIND, ADV_FV_UPWIND, ADV_FV_PLAIN, ADV_VANLEER, ADV_MOMENTUM = range(5)
 DIAG_ANY_NAN, DIAG_MAX_U, DIAG_MEAN_P, DIAG_SUM_P, DIAG_MIN_U, DIAG_MAX_V, DIAG_MIN_V = range(7)
 DIAG_TV_P, DIAG_TV_U, DIAG_TV_V, DIAG_TV_T, DIAG_TV_Q = range(7, 12)
@@ -137,6 +145,8 @@ SYMBOLS = {
     "gcm_sw2d_fused_depth": (C.c_int, [_H]),
     "gcm_pe25d_phase_geometry": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int), C.c_int]),
     "gcm_pe25d_phase_plan": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "gcm_pe25d_stage_geometry": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_uint), C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "gcm_pe25d_stage_plan": (C.c_int, [_H, C.POINTER(C.c_int), C.c_int]),
     "gcm_half_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_end_step": (C.c_int, [_H, C.c_double]),
     "gcm_end_step_diffuse": (C.c_int, [_H, C.c_double]),

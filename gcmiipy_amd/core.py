@@ -265,6 +265,31 @@ def phase_geometry(phase, W, rows, L, cus, elem_bytes=8, accumulate=True):
     return _phase_dict(phase_id(phase), out)
 
 
+def _stage_dict(out, band):
+    n = _lib.STAGE_PLAN_WORDS if band else _lib.STAGE_BAND_WORD
+    return {name: int(out[i]) for i, name in enumerate(_lib.STAGE_WORDS[:n])}
+
+
+def stage_geometry(W, rows, L, cus, elem_bytes=8, plan=None):
+    """the launch geometry of a whole-domain GCM_PE25D dynamics stage over `rows` rows of W columns and L levels on a
+    chip of `cus` compute units at the default switches, from the helpers the launchers use themselves
+    (gcm_pe25d_stage_geometry; no handle, no device).  plan: the words of gcm_filter_plan for W (None: the library's
+    own plan).  K1, the looping filter kernel -- k1_loop, the instantiation k1_maxr / k1_mask (0, 1440, 2880, 4096) /
+    k1_nin / k1_nw, k1_passes of the row's plan, k1_workgroups_per_row x k1_pairs_per_wg level pairs (the last
+    workgroup k1_pairs_last_wg), k1_pit_rides; K4, the update kernel -- k4_rows per workgroup, k4_groups (the last of
+    k4_rows_last_group rows), k4_col_tiles of 62 columns (the last of k4_cols_last_tile), k4_nseg, k4_oddtop, k4_grid"""
+    out = (C.c_int * _lib.STAGE_PLAN_WORDS)()
+    words, n = None, 0
+    if plan is not None:
+        n = len(plan)
+        words = (C.c_uint * n)(*[int(x) for x in plan])
+    rc = lib.gcm_pe25d_stage_geometry(int(W), int(rows), int(L), int(cus), int(elem_bytes), words, n, out,
+                                      _lib.STAGE_PLAN_WORDS)
+    if rc != _lib.OK:
+        raise ValueError("stage_geometry: sizes must be 1 or more, elem_bytes 4 or 8, plan the words of gcm_filter_plan")
+    return _stage_dict(out, False)
+
+
 def tracer_scheme_id(scheme):
     """a tracer scheme as the C ABI takes it: one of the _lib.TRACER_* constants or "centred", "upwind", "van_leer"
     (None: centred); ValueError otherwise, before any device use"""
@@ -1031,6 +1056,17 @@ class Core:
         _check(lib.gcm_pe25d_phase_plan(self._h, phase_id(phase), -1 if rows is None else int(rows), int(bool(accumulate)),
                                         out, _lib.PHASE_PLAN_WORDS), self._h)
         return _phase_dict(phase_id(phase), out)
+
+    def stage_plan(self):
+        """what a GCM_PE25D dynamics stage of this handle launches, without launching anything (gcm_pe25d_stage_plan):
+        the dict of stage_geometry below at the handle's own sizes, compute units and GCM_PE_* switches, for a stage over
+        all its rows.  A band that splits its stage into edge and interior rows adds band = 1, k1_split and the own
+        rows' K1 launch of gcm_band_run (k1_own_workgroups_per_row, k1_own_pairs_per_wg, k1_own_pairs_last_wg), K4 of
+        the edge rows (k4_edge_groups, k4_edge_rows_last_group, k4_edge_oddtop, k4_edge_grid, in nseg_edge level
+        segments) and of the interior rows (k4_int_*)"""
+        out = (C.c_int * _lib.STAGE_PLAN_WORDS)()
+        _check(lib.gcm_pe25d_stage_plan(self._h, out, _lib.STAGE_PLAN_WORDS), self._h)
+        return _stage_dict(out, bool(out[_lib.STAGE_BAND_WORD]))
 
     def half_step(self, stage, dt):
         _check(lib.gcm_half_step(self._h, int(stage), float(dt)), self._h)

@@ -6,6 +6,7 @@
 
 #include "gcm_handle.h"
 #include "pe25d_phase_geometry.h"
+#include "pe25d_stage_geometry.h"
 
 using namespace gcm;
 
@@ -183,6 +184,17 @@ extern "C" {
 // ------------------------------------------------------------------ the phases' launch geometry, without launching
 int gcm_pe25d_phase_geometry(int phase, int W, int rows, int L, int cus, int elem_bytes, int accumulate, int *out, int nout) {
     return pe25d_phase_geometry(phase, W, rows, L, cus, elem_bytes, accumulate, out, nout);
+}
+
+int gcm_pe25d_stage_geometry(int W, int rows, int L, int cus, int elem_bytes, const unsigned *plan, int nplan, int *out, int nout) {
+    return pe25d_stage_geometry(W, rows, L, cus, elem_bytes, plan, nplan, out, nout);
+}
+
+int gcm_pe25d_stage_plan(gcm_handle *h, int *out, int nout) {
+    if (int rc = pe_only(h, "gcm_pe25d_stage_plan")) return rc;
+    if (int rc = pe25d_stage_plan(h->pe, out, nout))
+        return fail(h, rc, "gcm_pe25d_stage_plan: a null pointer or fewer than GCM_STAGE_PLAN_WORDS words");
+    return GCM_OK;
 }
 
 int gcm_pe25d_phase_plan(gcm_handle *h, int phase, int rows, int accumulate, int *out, int nout) {

@@ -15,6 +15,7 @@
 
 #include "fft_lds.h"
 #include "gcm_math.h"
+#include "pe25d_stage_geometry.h"
 #include "sw2d_kernels.h"
 
 namespace gcm {
@@ -164,11 +165,7 @@ __device__ __forceinline__ T cs_acc(T acc, T x, T dsg) { return fma(x, dsg, acc)
 // 0 = generic ping-pong passes
 template <typename T> using FilterKernel = void (*)(PeArgsT<T>);
 template <typename T> using FilterLoopKernel = void (*)(PeArgsT<T>, int, int);   // (args, pairs per workgroup, y-block that forms pit or -1)
-// plans with their own instantiation (only their passes compiled in): the row lengths of the
-// BASELINE configs and the powers of 16
-constexpr unsigned kMask1440 = pass_bit(5, 2) | pass_bit(4, 3);                    // 1440 = 10.12.12, 120 = 10.12
-constexpr unsigned kMask2880 = pass_bit(5, 3) | pass_bit(4, 3) | pass_bit(4, 4);   // 2880
-constexpr unsigned kMask4096 = pass_bit(4, 4);                                     // 256, 4096
+// (kMask1440 / kMask2880 / kMask4096, the plans with their own instantiation, and kUpdCols: pe25d_stage_geometry.h)
 template <typename T> FilterKernel<T> spu_filter_kernel_for(const SuperPlan &P);            // pe25d_k1.h
 template <typename T> FilterLoopKernel<T> spu_filter_loop_kernel_for(const SuperPlan &P);   // pe25d_k1.h (null: no looping form)
 template <typename T> FilterKernel<T> pgf_filter_kernel_for(const SuperPlan &P);            // pe25d_k3.h
@@ -184,7 +181,6 @@ template <typename T> TracerKernel<T> tracer_kernel_for(int nc, bool same);   //
 template <typename T> TracerKernel<T> tracer_lim_kernel_for(int scheme, int nc, bool same);   // pe25d_tracer_lim.h
 constexpr int kTrCols = 64;       // tracer kernel: workgroup of 64 columns x kTrRows rows, one thread per (j, i) column
 constexpr int kTrRows = 4;
-constexpr int kUpdCols = 62;      // row-group update kernel: columns a wave produces (lanes 0 and 63 carry the halo columns)
 constexpr int kFftThreads = 256;  // generic filter path; the composite path sizes the workgroup from its plan
 constexpr int kColThreads = 128;  // pe_geopot_kernel (pe25d_kernels.hip): one thread per (j, i) column; pe25d_create sizes its LDS park from it
 constexpr int kRadThreads = 128;  // pe_radiation_kernel (pe25d_physics.hip): the same

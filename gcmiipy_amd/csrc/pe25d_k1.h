@@ -160,15 +160,15 @@ FilterKernel<T> spu_filter_kernel_for(const SuperPlan &P) {
 }
 template <typename T>
 FilterLoopKernel<T> spu_filter_loop_kernel_for(const SuperPlan &P) {
-    if (!P.ok || P.npass > 4 || P.npass < 2) return nullptr;
-    // the plans these masks stand for start with a pass of radix 5.2 / 5.3 / 4.4 (make_super_plan)
-    if (P.mask == kMask1440 && P.r1[0] * P.r2[0] == 10 && P.npass <= 3) return pe_spu_filter_loop_kernel<T, 12, kMask1440, 10, 3>;
-    if (P.mask == kMask2880 && P.r1[0] * P.r2[0] == 15 && P.npass <= 3) return pe_spu_filter_loop_kernel<T, 16, kMask2880, 15, 3>;
-    if (P.mask == kMask1440) return pe_spu_filter_loop_kernel<T, 12, kMask1440>;
-    if (P.mask == kMask2880) return pe_spu_filter_loop_kernel<T, 16, kMask2880>;
-    if (P.mask == kMask4096) return pe_spu_filter_loop_kernel<T, 16, kMask4096>;
-    if (P.maxr <= 12) return pe_spu_filter_loop_kernel<T, 12>;
-    if (P.maxr <= 16) return pe_spu_filter_loop_kernel<T, 16>;
+    // the rules: spu_filter_loop_desc (pe25d_stage_geometry.h), which the query gcm_pe25d_stage_plan reports; here
+    // the descriptor (MAXR, MASK, NIN, NW) becomes the instantiation of that name
+    const LoopKernelDesc d = spu_filter_loop_desc(P);
+    if (!d.loop) return nullptr;
+    if (d.mask == kMask1440) return d.nin == 10 ? pe_spu_filter_loop_kernel<T, 12, kMask1440, 10, 3> : pe_spu_filter_loop_kernel<T, 12, kMask1440>;
+    if (d.mask == kMask2880) return d.nin == 15 ? pe_spu_filter_loop_kernel<T, 16, kMask2880, 15, 3> : pe_spu_filter_loop_kernel<T, 16, kMask2880>;
+    if (d.mask == kMask4096) return pe_spu_filter_loop_kernel<T, 16, kMask4096>;
+    if (d.maxr == 12) return pe_spu_filter_loop_kernel<T, 12>;
+    if (d.maxr == 16) return pe_spu_filter_loop_kernel<T, 16>;
     return pe_spu_filter_loop_kernel<T, 25>;
 }
 

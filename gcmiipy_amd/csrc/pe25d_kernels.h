@@ -181,6 +181,8 @@ int pe25d_stats(Pe25d *m, const double *area_host, int area_len, double out[9], 
 int pe25d_filter_plan(int n, unsigned *out, int cap);   // gcm_filter_plan
 // gcm_pe25d_phase_plan: pe25d_phase_geometry.h's query at the handle's own W, L, element size and compute units
 int pe25d_phase_plan(const Pe25d *m, int phase, int rows, bool accumulate, int *out, int nout);
+// gcm_pe25d_stage_plan: what a stage of the handle launches (pe25d_stage_geometry.h at the handle's own sizes and switches)
+int pe25d_stage_plan(const Pe25d *m, int *out, int nout);
 void pe25d_tv_shape(const Pe25d *m, int field, long *n_outer, long *n_axis, long *n_inner, int *wrap);
 const void *pe25d_field(Pe25d *m, int field, long *n, int *f32);
 // passive tracers: c / the result [n][L][H][W] float64 (a band: its own rows); which 0 = current, 1 = star

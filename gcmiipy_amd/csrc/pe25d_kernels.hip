@@ -450,12 +450,9 @@ static void chain_b_head(Pe25d *m, const Stage<T> &g) {
 // chip, else groups; with `pit` (the 2-D form of pit) one more workgroup per row forms pit and p_n (pe_pit2d_row)
 template <typename T>
 static void launch_k1(const Pe25d *m, FilterLoopKernel<T> k1, const PeArgsT<T> &c, int rows, bool pit, hipStream_t st, hipEvent_t ev) {
-    const int pairs = (m->L + 1) / 2;
-    const int groups = std::min(pairs, std::max(1, (3 * m->cus + rows - 1) / rows));
-    const int ppw = (pairs + groups - 1) / groups;
-    const int ny = (pairs + ppw - 1) / ppw;
-    launch(m, k1, dim3(rows, ny + (pit ? 1 : 0)), dim3(m->cplan.ok ? m->cplan.threads : kFftThreads), filter_loop_lds_bytes<T>(m), st,
-           Then{ev}, c, ppw, pit ? ny : -1);
+    const StageK1 k = stage_k1_launch(m->L, rows, m->cus);      // (pe25d_stage_geometry.h)
+    launch(m, k1, dim3(rows, k.ny + (pit ? 1 : 0)), dim3(m->cplan.ok ? m->cplan.threads : kFftThreads), filter_loop_lds_bytes<T>(m), st,
+           Then{ev}, c, k.ppw, pit ? k.ny : -1);
 }
 
 // ---- chain B: K1 and pit of rows [j0, j1 + ext), and ev_a behind them (what K4 of the interior rows takes from this chain)
@@ -553,15 +550,14 @@ static void update_rows(const Pe25d *m, PeArgsT<T> a, int r0, int r1, int rb0, i
     if (rows <= 0) return;
     a = rows_of(a, r0, std::max(r0, r1), rb0, std::max(rb0, rb1));
     const int Rg = m->upd_rows, L = m->L;
-    const long groups = (std::max(0, r1 - r0) + Rg - 1) / Rg + (std::max(0, rb1 - rb0) + Rg - 1) / Rg;
-    // 8 XCDs x (row group, segment) pairs per XCD x column tiles (see the kernel's index map)
-    const long rs_per_xcd = (groups * a.nseg + 7) / 8;
-    const dim3 gg((unsigned)(8 * rs_per_xcd * ((m->W + kUpdCols - 1) / kUpdCols)));
+    // 8 XCDs x (row group, segment) pairs per XCD x column tiles (see the kernel's index map; pe25d_stage_geometry.h)
+    const long groups = stage_k4_groups(r1 - r0, rb1 - rb0, Rg);
+    const dim3 gg((unsigned)stage_k4_grid(groups, a.nseg, m->W));
     const bool same = a.u == a.su;
     // whole columns of an even number of levels start on an odd level: the geopotential anchor is requested with the
     // even levels only (an odd level steps up from the anchor in the tile below and never reads its own): one request
     // in eleven (seven) less every other level, C4 1.881 -> 1.857 ms per step (round 4, A/B on one box)
-    const bool oddtop = m->k4_oddtop && a.nseg == 1 && L % 2 == 0;
+    const bool oddtop = stage_k4_oddtop(m->k4_oddtop, a.nseg, L);
     launch(m, update_rows_kernel_for<T>(Rg, same, oddtop), gg, dim3(64 * (Rg + 1)), upd_lds_bytes<T>(Rg, L), st, Then{k4_done, true}, a);
 }
 
@@ -691,6 +687,33 @@ static void half(Pe25d *m, int stage_set, int out_set, double dt, int j0, int j1
     const bool ch = chained || (mode == 0 && m->wrap);
     if (m->f32) half_t<float>(m, stage_set, out_set, dt, j0, j1, s, mode, ch);
     else half_t<double>(m, stage_set, out_set, dt, j0, j1, s, mode, ch);
+}
+
+// gcm_pe25d_stage_plan: what the steps above launch, by the rules of stage_facts, chain_b_k1_pit, update_whole, update_edges
+// and update_interior and with the numbers of pe25d_stage_geometry.h that launch_k1 and update_rows take themselves
+int pe25d_stage_plan(const Pe25d *m, int *out, int nout) {
+    if (!out || nout < GCM_STAGE_PLAN_WORDS) return GCM_ERR_ARG;
+    for (int n = 0; n < GCM_STAGE_PLAN_WORDS; ++n) out[n] = 0;
+    const int H = m->H, W = m->W, L = m->L, ext = m->wrap ? 0 : 1;
+    const bool p2 = m->pit2d && m->nseg == 1;                                    // (stage_facts)
+    const bool loop = m->cfg.filter && W > 1 && !m->filter_no_loop;
+    stage_words_k1(out, m->cplan, loop, L, H + ext, m->cus, p2);                 // mode 0: K1 of rows [0, H + ext)
+    stage_words_k4(out, W, H, L, m->upd_rows, m->nseg, m->k4_oddtop);
+    if (m->wrap || H <= 2 * kGhost) return GCM_OK;                               // (no band, or one too short to split)
+    out[GCM_STAGE_BAND] = 1;
+    // the split K1 (inside gcm_band_run, the ghost rows' sums queued behind the unpack): its own-rows launch
+    if (out[GCM_STAGE_K1_LOOP] && m->aux2 && p2 && H >= 2 * kGhost + 3) {
+        const StageK1 k = stage_k1_launch(L, H, m->cus);
+        out[GCM_STAGE_K1_SPLIT] = 1;
+        out[GCM_STAGE_K1_OWN_WGS_PER_ROW] = k.ny;
+        out[GCM_STAGE_K1_OWN_PAIRS_PER_WG] = k.ppw;
+        out[GCM_STAGE_K1_OWN_PAIRS_LAST_WG] = k.pairs - (k.ny - 1) * k.ppw;
+    }
+    const int nseg_edge = (p2 && m->nseg_edge > 1) ? m->nseg_edge : m->nseg;     // (edge_segs)
+    out[GCM_STAGE_NSEG_EDGE] = nseg_edge;
+    stage_words_k4_launch(out + GCM_STAGE_K4_EDGE_GROUPS, W, kGhost, kGhost, L, m->upd_rows, nseg_edge, m->k4_oddtop);
+    stage_words_k4_launch(out + GCM_STAGE_K4_INT_GROUPS, W, H - 2 * kGhost, 0, L, m->upd_rows, m->nseg, m->k4_oddtop);
+    return GCM_OK;
 }
 
 // gcm_band_run, right behind the unpack on the second stream: the ghost rows that have just arrived belong to

@@ -419,7 +419,7 @@ Pe25d *pe25d_create(const gcm_config &cfg, hipStream_t main_stream, std::string 
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
         m->cus = cus;
-        const double rounds = (double)((W + kUpdCols - 1) / kUpdCols) * m->H / (8.0 * cus);
+        const double rounds = (double)stage_k4_col_tiles(W) * m->H / (8.0 * cus);
         long want = (long)std::ceil(1.5 / std::max(rounds, 1e-3));
         // fp32: 153 VGPRs and 34 KB of tiles per 3-row workgroup let THREE of them share a CU (three waves per SIMD; the
         // 7-row form holds one 8-wave workgroup, two waves per SIMD): c4_f32 1.214 -> 1.126 ms per step (round 4, A/B
@@ -427,7 +427,7 @@ Pe25d *pe25d_create(const gcm_config &cfg, hipStream_t main_stream, std::string 
         // stays at two waves per SIMD either way: 3-row groups only where the band is short -- up to 360 rows they win
         // (round 4, one box: a 360-row band of C4 1.050 -> 1.008 ms, of the 2880x1440x40 grid 3.461 -> 3.396), at 720
         // rows the 7-row form does (C4 1.874 vs 1.907, the 2880-column grid 6.597 vs 6.627).
-        m->upd_rows = (m->H <= 400 || m->f32) ? 3 : 7;
+        m->upd_rows = stage_k4_rows(m->H, m->f32);            // (the rule: pe25d_stage_geometry.h)
         if (env.level_segments.set) want = env.level_segments.num;
         if (env.pit2d.set) m->pit2d = env.pit2d.num != 0;      // 0: pit from the 3-D fields (pe_pit_kernel)
         if (env.update_rows.set) m->upd_rows = env.update_rows.num == 3 ? 3 : 7;      // rows per workgroup

@@ -205,6 +205,46 @@ typedef enum { GCM_PHASE_HELD_SUAREZ = 0, GCM_PHASE_MOIST = 1, GCM_PHASE_CLIMATE
 int gcm_pe25d_phase_geometry(int phase, int W, int rows, int L, int cus, int elem_bytes, int accumulate, int *out, int nout);
 int gcm_pe25d_phase_plan(gcm_handle *h, int phase, int rows, int accumulate, int *out, int nout);
 
+/* The launch geometry of the GCM_PE25D dynamics stage where it depends on the rows, the level count, the row's filter
+ * plan and the chip's compute units, without launching anything: a read-only query for tests and tools, taken from the
+ * helpers the launchers use themselves.  K1 is the looping filter kernel (spu = filter(su iph(sp)), with pit in one more
+ * workgroup a row), K4 the row-group update kernel.  gcm_pe25d_stage_geometry needs no handle and no device: a
+ * whole-domain stage over `rows` rows of W columns and L levels on a chip of `cus` compute units at the default
+ * switches, elem_bytes 8 (fp64) or 4 (fp32); plan / nplan: the words gcm_filter_plan writes for W, or NULL for the
+ * library's own plan of W.  out (nout >= GCM_STAGE_PLAN_WORDS words, unused ones 0), by GCM_STAGE_*:
+ *   K1_LOOP 1: the looping form (0: one workgroup per level pair; the instantiation words are then 0)
+ *   K1_MAXR, K1_MASK (0, 1440, 2880 or 4096: the plan the instantiation is compiled for), K1_NIN, K1_NW: the
+ *     instantiation pe_spu_filter_loop_kernel<T, MAXR, MASK, NIN, NW>;  K1_PASSES: passes of the row's composite plan
+ *   K1_WGS_PER_ROW workgroups a row that filter, each looping over K1_PAIRS_PER_WG level pairs, the last one over
+ *     K1_PAIRS_LAST_WG (an odd L: its last pair is a single level);  K1_PIT_RIDES 1: pit and p_n in the same launch
+ *   K4_ROWS rows per workgroup (3 or 7), K4_GROUPS row groups, the last of K4_ROWS_LAST_GROUP rows; K4_COL_TILES tiles
+ *     of 62 columns, the last of K4_COLS_LAST_TILE; K4_NSEG level segments; K4_ODDTOP 1: the march starts on an odd
+ *     level; K4_GRID workgroups launched (padded to the 8 XCDs)
+ * gcm_pe25d_stage_plan is the same for what a GCM_PE25D handle launches for a stage over all its rows (mode 0), with the
+ * handle's GCM_PE_* switches.  A band (nranks > 1) that splits its stage into edge rows and interior rows also reports
+ *   BAND 1;  K1_SPLIT 1: inside gcm_band_run K1 of the own rows is a launch of its own, K1_OWN_WGS_PER_ROW workgroups
+ *     a row x K1_OWN_PAIRS_PER_WG pairs, the last K1_OWN_PAIRS_LAST_WG
+ *   K4_EDGE_GROUPS, K4_EDGE_ROWS_LAST_GROUP, K4_EDGE_ODDTOP, K4_EDGE_GRID: K4 of the two edge rows of either side, one
+ *     launch over two row ranges in NSEG_EDGE level segments;  K4_INT_*: the same words for K4 of the interior rows
+ * A size < 1, a null `out`, plan words that are no plan, nout too small: GCM_ERR_ARG; a handle of another model:
+ * GCM_ERR_UNSUPPORTED.                                                                                                 */
+enum {
+    GCM_STAGE_K1_LOOP = 0, GCM_STAGE_K1_MAXR = 1, GCM_STAGE_K1_MASK = 2, GCM_STAGE_K1_NIN = 3, GCM_STAGE_K1_NW = 4,
+    GCM_STAGE_K1_PASSES = 5, GCM_STAGE_K1_WGS_PER_ROW = 6, GCM_STAGE_K1_PAIRS_PER_WG = 7, GCM_STAGE_K1_PAIRS_LAST_WG = 8,
+    GCM_STAGE_K1_PIT_RIDES = 9,
+    GCM_STAGE_K4_ROWS = 10, GCM_STAGE_K4_GROUPS = 11, GCM_STAGE_K4_ROWS_LAST_GROUP = 12, GCM_STAGE_K4_COL_TILES = 13,
+    GCM_STAGE_K4_COLS_LAST_TILE = 14, GCM_STAGE_K4_NSEG = 15, GCM_STAGE_K4_ODDTOP = 16, GCM_STAGE_K4_GRID = 17,
+    GCM_STAGE_BAND = 18, GCM_STAGE_K1_SPLIT = 19, GCM_STAGE_K1_OWN_WGS_PER_ROW = 20, GCM_STAGE_K1_OWN_PAIRS_PER_WG = 21,
+    GCM_STAGE_K1_OWN_PAIRS_LAST_WG = 22,
+    GCM_STAGE_K4_EDGE_GROUPS = 23, GCM_STAGE_K4_EDGE_ROWS_LAST_GROUP = 24, GCM_STAGE_K4_EDGE_ODDTOP = 25,
+    GCM_STAGE_K4_EDGE_GRID = 26, GCM_STAGE_NSEG_EDGE = 27,
+    GCM_STAGE_K4_INT_GROUPS = 28, GCM_STAGE_K4_INT_ROWS_LAST_GROUP = 29, GCM_STAGE_K4_INT_ODDTOP = 30,
+    GCM_STAGE_K4_INT_GRID = 31
+};
+#define GCM_STAGE_PLAN_WORDS 32
+int gcm_pe25d_stage_geometry(int W, int rows, int L, int cus, int elem_bytes, const unsigned *plan, int nplan, int *out, int nout);
+int gcm_pe25d_stage_plan(gcm_handle *h, int *out, int nout);
+
 /* One Euler stage, for per-stage parity tests and for the reference's
  * boundary_conditions hook (dynamics.py:232-236): stage == 0 computes the
  * predictor from the current state into the handle's "star" buffers; stage == 1

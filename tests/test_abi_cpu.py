@@ -46,6 +46,22 @@ def test_phase_plan_constants_match_header():
     assert _lib.lib.gcm_pe25d_phase_plan(None, _lib.PHASE_CLIMATE, -1, 1, out, _lib.PHASE_PLAN_WORDS) == _lib.ERR_ARG
 
 
+def test_stage_plan_words_match_header():
+    """gcm_pe25d_stage_geometry / gcm_pe25d_stage_plan: the names Core.stage_plan() gives the words follow the header's
+    GCM_STAGE_* numbers, and the handle-free call answers without a device"""
+    from gcmiipy_amd import _lib
+    src = open(os.path.join(ROOT, "include", "gcmcore.h")).read()
+    values = {k.lower(): int(v) for k, v in re.findall(r"GCM_STAGE_([A-Z0-9_]+) = (\d+)", src)}
+    assert sorted(values.values()) == list(range(_lib.STAGE_PLAN_WORDS))
+    assert int(re.search(r"#define GCM_STAGE_PLAN_WORDS (\d+)", src).group(1)) == _lib.STAGE_PLAN_WORDS
+    short = {"k1_workgroups_per_row": "k1_wgs_per_row", "k1_own_workgroups_per_row": "k1_own_wgs_per_row"}
+    assert [values[short.get(n, n)] for n in _lib.STAGE_WORDS] == list(range(_lib.STAGE_PLAN_WORDS))
+    assert values["band"] == _lib.STAGE_BAND_WORD
+    out = (ctypes.c_int * _lib.STAGE_PLAN_WORDS)()
+    assert _lib.lib.gcm_pe25d_stage_geometry(1440, 720, 24, 256, 8, None, 0, out, _lib.STAGE_PLAN_WORDS) == _lib.OK
+    assert list(out)[:18] == [1, 12, 1440, 10, 3, 3, 2, 6, 6, 1, 7, 103, 6, 24, 14, 1, 1, 2496] and not any(list(out)[18:])
+
+
 def test_config_struct_layout_matches_header():
     """field order/types of the ctypes mirror follow the header's gcm_config."""
     from gcmiipy_amd import _lib

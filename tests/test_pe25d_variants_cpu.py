@@ -2,9 +2,9 @@
 
 The handle picks its K1 / K3 / pit kernels from the composite plan of the row (make_super_plan, csrc/fft_lds.h)
 by the rules of spu_filter_kernel_for / spu_filter_loop_kernel_for (pe25d_k1.h) and pgf_filter_kernel_for /
-pit2d_kernel_for (pe25d_k3.h).  Those rules are restated here and applied to the library's own plans
-(gcm_filter_plan), so that the case list of test_pe25d_variants_gpu.py cannot drift away from the paths it
-claims to reach."""
+pit2d_kernel_for (pe25d_k3.h).  The non-looping kernels' rules are restated here and applied to the library's own plans
+(gcm_filter_plan); the looping K1's instantiation is the library's own answer (gcm_pe25d_stage_geometry), so that the
+case list of test_pe25d_variants_gpu.py cannot drift away from the paths it claims to reach."""
 import ctypes as C
 
 import pytest
@@ -57,21 +57,15 @@ def filter_kernel(n):
 
 def loop_kernel(n):
     """spu_filter_loop_kernel_for -> (MAXR, mask name or None, NIN, NW), or None (no looping form: K1 one
-    workgroup per level pair, pit as pe_pit2d_kernel)"""
-    ok, npass, passes = _plan(n)
-    if not ok or npass > 4 or npass < 2:
+    workgroup per level pair, pit as pe_pit2d_kernel).  The rule is stated once, in spu_filter_loop_desc
+    (csrc/pe25d_stage_geometry.h), which the picker itself reads: this is the library's answer (gcm_pe25d_stage_geometry),
+    held to the literal PINS below"""
+    from gcmiipy_amd.core import stage_geometry
+    d = stage_geometry(n, 1, 1, 1)
+    if not d["k1_loop"]:
+        assert (d["k1_maxr"], d["k1_mask"], d["k1_nin"], d["k1_nw"]) == (0, 0, 0, 0)
         return None
-    mask, maxr = _mask_maxr(passes)
-    r0 = passes[0][0] * passes[0][1]
-    if mask == MASK1440 and r0 == 10 and npass <= 3:
-        return (12, "1440", 10, 3)
-    if mask == MASK2880 and r0 == 15 and npass <= 3:
-        return (16, "2880", 15, 3)
-    if mask in _MASK_NAME:
-        m = 12 if mask == MASK1440 else 16
-        return (m, _MASK_NAME[mask], m, 5)
-    m = 12 if maxr <= 12 else 16 if maxr <= 16 else 25
-    return (m, None, m, 5)
+    return (d["k1_maxr"], {0: None, 1440: "1440", 2880: "2880", 4096: "4096"}[d["k1_mask"]], d["k1_nin"], d["k1_nw"])
 
 
 # width -> (ok, passes as "r1.r2", filter kernel, looping K1); the widths of test_pe25d_variants_gpu.py
