@@ -21,6 +21,7 @@ MAX_TRACERS = 16                     # GCM_MAX_TRACERS
 TRACER_STATS_WORDS = 6               # GCM_TRACER_STATS_WORDS
 CLIM_WORDS3, CLIM_WORDS2 = 10, 2     # GCM_CLIM_WORDS3, GCM_CLIM_WORDS2
 PLEV_MAX, PLEV_WORDS, PLEV_PLAN_WORDS = 64, 13, 6    # GCM_PLEV_MAX, GCM_PLEV_WORDS, GCM_PLEV_PLAN_WORDS
+PLEV_MAP_WORDS, PLEV_MAP_WORDS2, PLEV_MAP_PLAN_WORDS = 13, 2, 5     # GCM_PLEV_MAP_WORDS, _WORDS2, _PLAN_WORDS
 SPEC_WORDS = 6                       # GCM_SPEC_WORDS
 SPEC_PLAN_WORDS = 6                  # GCM_SPEC_PLAN_WORDS
 HDIFF_U, HDIFF_V, HDIFF_T, HDIFF_Q = 1, 2, 4, 8     # GCM_HDIFF_*
@@ -219,6 +220,16 @@ SYMBOLS = {
     "gcm_get_plev_climate": (C.c_int, [_H, _dp, C.POINTER(C.c_int64)]),
     "gcm_put_plev_climate": (C.c_int, [_H, _dp, C.c_int64]),
     "gcm_plev_climate_plan": (C.c_int, [_H, C.POINTER(C.c_int), C.c_int]),
+    "gcm_plev_height_columns": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, C.POINTER(C.c_int)]),
+    "gcm_plev_height": (C.c_int, [_H, C.c_int, _dp, C.c_double, _dp, C.POINTER(C.c_int32)]),
+    "gcm_set_plev_maps": (C.c_int, [_H, C.c_int, C.c_int, _dp]),
+    "gcm_plev_maps_every": (C.c_int, [_H]),
+    "gcm_plev_maps_levels": (C.c_int, [_H, _dp, C.c_int]),
+    "gcm_plev_maps_sample": (C.c_int, [_H]),
+    "gcm_plev_maps_reset": (C.c_int, [_H]),
+    "gcm_get_plev_maps": (C.c_int, [_H, _dp, _dp, C.POINTER(C.c_int64)]),
+    "gcm_put_plev_maps": (C.c_int, [_H, _dp, _dp, C.c_int64]),
+    "gcm_plev_maps_plan": (C.c_int, [_H, C.POINTER(C.c_int), C.c_int]),
     "gcm_set_spectra": (C.c_int, [_H, C.c_int, C.c_int]),
     "gcm_spectra_every": (C.c_int, [_H]),
     "gcm_spectra_mmax": (C.c_int, [_H]),

@@ -244,6 +244,23 @@ def merge_plev_climate(parts):
                        *[np.concatenate([c[f] for c in parts], axis=-1) for f in range(2, len(PlevClimate._fields))])
 
 
+def merge_plev_maps(parts):
+    """the time-mean maps on pressure levels of the whole domain from its bands': `parts` are the bands' PlevMaps records
+    (Core.plev_maps) in row order; the rows of the coverage, of the means and of p and pp are concatenated.  ValueError
+    where the sample counts or the targets differ"""
+    import numpy as np
+    from .core import PlevMaps
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_plev_maps: no records")
+    if any(c.n != parts[0].n for c in parts):
+        raise ValueError("merge_plev_maps: the bands hold %s samples" % ", ".join(str(c.n) for c in parts))
+    if any(not np.array_equal(c.plev, parts[0].plev) for c in parts):
+        raise ValueError("merge_plev_maps: the bands hold different pressure targets")
+    return PlevMaps(parts[0].n, np.array(parts[0].plev, dtype=np.float64),
+                    *[np.concatenate([c[f] for c in parts], axis=-2) for f in range(2, len(PlevMaps._fields))])
+
+
 def merge_spectra(parts):
     """the spectra of the whole domain from its bands': `parts` are the bands' Spectra records (Core.spectra) in row
     order; the rows are concatenated.  ValueError where the sample counts or the numbers of wavenumbers differ"""
@@ -319,7 +336,7 @@ class LoopbackExchange:
 
 class HipBandEngine:
     """A `Core` band + torch CUDA buffers/streams for the exchange.  It keeps no registrations: the phases behind the
-    dynamics (set_physics ... set_climate, set_plev_climate, set_spectra) are the handle's, and a host-driven step ends with the library's own walk
+    dynamics (set_physics ... set_climate, set_plev_climate, set_spectra, set_plev_maps) are the handle's, and a host-driven step ends with the library's own walk
     over them (Core.end_step), the one gcm_band_run takes."""
 
     def __init__(self, core, torch, overlap=True, stream_aware=True):
@@ -411,6 +428,11 @@ class HipBandEngine:
         """Core.set_plev_climate; every band of a run registers the same interval and targets.  merge_plev_climate() puts
         the bands' records together"""
         self.c.set_plev_climate(every, plev)
+
+    def set_plev_maps(self, every=1, plev=None):
+        """Core.set_plev_maps; every band of a run registers the same interval and targets.  merge_plev_maps() puts the
+        bands' records together"""
+        self.c.set_plev_maps(every, plev)
 
     def set_spectra(self, every=1, mmax=None):
         """Core.set_spectra; every band of a run registers the same interval and mmax.  merge_spectra() puts the bands'

@@ -22,7 +22,10 @@ zonal wavenumber spectra, Core.set_spectra, are stored as "spectra_every", "spec
 saved and restored the same way, and files without these keys restore with none; the climatology on pressure levels,
 Core.set_plev_climate, is stored as "plev_climate_every", "plev_climate_plev", "plev_climate_n" and "plev_climate_sums",
 the interval, the targets in Pa, the sample count and the raw float64 sums, saved and restored the same way, and files
-without these keys restore with none; the horizontal diffusion,
+without these keys restore with none; the time-mean maps on pressure levels, Core.set_plev_maps, are stored as
+"plev_maps_every", "plev_maps_plev", "plev_maps_n", "plev_maps_sums" and "plev_maps_sums2", the interval, the targets in
+Pa, the sample count and the raw float64 sums, written only with a registration, saved and restored the same way, and
+files without these keys restore with none; the horizontal diffusion,
 Core.set_horizontal_diffusion, is stored as "hdiff" = [order, fields, nu, cmax] and registered again on restore, ahead of
 the first step, and files without the key restore with none; whether a band takes that phase over its own rows is
 the option "band_horizontal_diffusion", taken from the handle as it is when saved, files without it restore as off and
@@ -90,6 +93,10 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
         n, s = core.plev_climate_sums()
         out.update(plev_climate_every=np.int64(core.plev_climate_every), plev_climate_plev=core.plev_climate_levels,
                    plev_climate_n=np.int64(n), plev_climate_sums=s)
+    if core.model == _lib.PE25D and getattr(core, "plev_maps_every", 0) > 0:   # (getattr: as above)
+        n, s, s2 = core.plev_maps_sums()
+        out.update(plev_maps_every=np.int64(core.plev_maps_every), plev_maps_plev=core.plev_maps_levels,
+                   plev_maps_n=np.int64(n), plev_maps_sums=s, plev_maps_sums2=s2)
     hd = getattr(core, "horizontal_diffusion", None) if core.model == _lib.PE25D else None   # (getattr: as above)
     if hd is not None:
         out["hdiff"] = np.asarray([hd[k] for k in HDIFF_DEFAULTS], dtype=np.float64)
@@ -119,14 +126,14 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, tracer_convect, held_suarez, hdiff, climate, plev_climate, spectra, moist, convect, boundary_layer, band_boundary_layer,
+    tracer_mixing, tracer_convect, held_suarez, hdiff, climate, plev_climate, plev_maps, spectra, moist, convect, boundary_layer, band_boundary_layer,
     band_horizontal_diffusion); ground and
     tracers are
     None where the file has none, tracer_forcing
     {i: dict(...)} and tracer_mixing {i: K} are then empty, and so is tracer_convect, the list of the tracers that have
     opted in to the convective mixing (files without the key: none); held_suarez is (parameters dict, lat) or None; hdiff is
     dict(order, fields, nu, cmax) or None (files without the key: None); climate is
-    dict(every, n, m3, m2) or None; plev_climate is dict(every, plev, n, sums) or None (files without the keys: None); spectra is dict(every, mmax, n, s) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
+    dict(every, n, m3, m2) or None; plev_climate is dict(every, plev, n, sums) or None (files without the keys: None); plev_maps is dict(every, plev, n, sums, sums2) or None (files without the keys: None); spectra is dict(every, mmax, n, s) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
     dict(params, n, seconds, count, levels) or None; boundary_layer is dict(params, n, seconds, shf, evap) or None;
     band_boundary_layer is whether a band takes that phase (False for files without the option), and
     band_horizontal_diffusion the same for the horizontal diffusion"""
@@ -171,6 +178,10 @@ def load(path):
     if "plev_climate_every" in d.files:
         plev = dict(every=int(d["plev_climate_every"]), plev=d["plev_climate_plev"], n=int(d["plev_climate_n"]),
                     sums=d["plev_climate_sums"])
+    maps = None
+    if "plev_maps_every" in d.files:
+        maps = dict(every=int(d["plev_maps_every"]), plev=d["plev_maps_plev"], n=int(d["plev_maps_n"]),
+                    sums=d["plev_maps_sums"], sums2=d["plev_maps_sums2"])
     spec = None
     if "spectra_every" in d.files:
         spec = dict(every=int(d["spectra_every"]), mmax=int(d["spectra_mmax"]), n=int(d["spectra_n"]), s=d["spectra_s"])
@@ -182,7 +193,7 @@ def load(path):
             column[ph.name] = dict(params=par, n=int(d[ph.name + "_n"]), seconds=float(d[ph.name + "_seconds"]),
                                    **{f: d["%s_%s" % (ph.name, f)] for f in ph.fields})
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, climate=clim,
-                spectra=spec, hdiff=hd, plev_climate=plev,
+                spectra=spec, hdiff=hd, plev_climate=plev, plev_maps=maps,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
@@ -226,6 +237,9 @@ def restore(path, **core_kwargs):
     if ck["spectra"] is not None:
         core.set_spectra(ck["spectra"]["every"], ck["spectra"]["mmax"])
         core.put_spectra(ck["spectra"]["n"], ck["spectra"]["s"])
+    if ck["plev_maps"] is not None:
+        core.set_plev_maps(ck["plev_maps"]["every"], ck["plev_maps"]["plev"])
+        core.put_plev_maps(ck["plev_maps"]["n"], ck["plev_maps"]["sums"], ck["plev_maps"]["sums2"])
     for ph in COLUMN_PHASES:                 # (the model's order: the boundary layer, the convective adjustment, the moist physics)
         rec = ck[ph.name]
         if rec is not None:

@@ -189,6 +189,95 @@ def plev_columns(pl, x, plev):
     return out.reshape(pl.shape[:-1] + (P.size,)), valid.reshape(pl.shape[:-1] + (P.size,)).astype(bool)
 
 
+# the conditional means of gcm_get_plev_maps' words 1 .. 12 (word 0 is the count), then the means of its s2
+PLEV_MAP_WORDS = ("Z", "ZZ", "T", "TT", "u", "v", "uu", "vv", "uv", "vT", "q", "vq")
+PLEV_MAP_WORDS2 = ("p", "pp")
+
+
+class PlevMaps(collections.namedtuple("PlevMaps", ("n", "plev", "coverage") + PLEV_MAP_WORDS + PLEV_MAP_WORDS2)):
+    """the time-mean maps of a GCM_PE25D handle on pressure levels (Core.plev_maps): n, the number of samples; plev
+    (N,), the targets in Pa; coverage (N, H, W) = count / n, the fraction of samples in which the target was valid in
+    the column; the twelve conditional means over the valid samples, each (N, H, W) and NaN where the count is 0 -- the
+    device's float64 sums divided by the count: Z (the geopotential height in m), ZZ, T = theta Pi, TT, u = uc, v = vc
+    (the winds at the cell centre), uu, vv, uv, vT, q, vq, products of the interpolated values; and p, pp (H, W), the
+    means of the handle's p field and of its square over all n samples.  A band: its own rows (bands.merge_plev_maps).
+    The variances and eddy fluxes below are differences of large numbers -- ZZ - Z^2 at 500 hPa is a few 1e3 m^2 out of
+    3e7 m^2 --: float64 sums leave them about nine digits, and a cell in which the field hardly varied may come out
+    slightly negative."""
+    __slots__ = ()
+
+    @property
+    def Z_variance(self):
+        """<Z'Z'> = ZZ - <Z>^2: the variance of the height in time, the storm track where it is large"""
+        return self.ZZ - self.Z * self.Z
+
+    @property
+    def T_variance(self):
+        """<T'T'> = TT - <T>^2"""
+        return self.TT - self.T * self.T
+
+    @property
+    def eke(self):
+        """0.5 (uu - <u>^2 + vv - <v>^2): the transient eddy kinetic energy per unit mass of the centred winds"""
+        return 0.5 * (self.uu - self.u * self.u + self.vv - self.v * self.v)
+
+    @property
+    def eddy_heat_flux(self):
+        """<v'T'> = vT - <v><T>: the transient eddies' meridional heat flux"""
+        return self.vT - self.v * self.T
+
+    @property
+    def eddy_moisture_flux(self):
+        """<v'q'> = vq - <v><q>"""
+        return self.vq - self.v * self.q
+
+    @property
+    def p_variance(self):
+        """<p'p'> = pp - <p>^2 of the handle's p field (surface pressure minus ptop)"""
+        return self.pp - self.p * self.p
+
+    def zonal_mean(self, word):
+        """the mean along longitude of the field named `word` (one of the record's fields, or a derived one such as
+        "Z_variance") over the cells that hold a value: (N, H), or (H,) for p and pp; NaN where a row holds none"""
+        x = np.asarray(getattr(self, word), dtype=np.float64)
+        ok = np.isfinite(x)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(ok, x, 0.0).sum(axis=-1) / ok.sum(axis=-1)
+
+    def stationary(self, word):
+        """the field named `word` minus its zonal mean: the stationary waves of a time mean (Z over topography)"""
+        return np.asarray(getattr(self, word), dtype=np.float64) - self.zonal_mean(word)[..., None]
+
+    @classmethod
+    def from_sums(cls, n, plev, s, s2):
+        """the record of the raw sums s (13, N, H, W), s2 (2, H, W) of n samples at the targets plev"""
+        s, s2 = np.asarray(s, dtype=np.float64), np.asarray(s2, dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            count = np.where(s[0] > 0.0, s[0], np.nan)
+            cover = s[0] / np.float64(n)
+            return cls(int(n), np.array(plev, dtype=np.float64), cover, *[s[w + 1] / count for w in range(len(PLEV_MAP_WORDS))],
+                       *[s2[w] / np.float64(n) for w in range(len(PLEV_MAP_WORDS2))])
+
+
+def plev_height_columns(p, theta, plev, sig, dsig, sigt, ptop=0.0, hmG=None):
+    """the geopotential height of columns on the pressures plev (N,) on the host (gcm_plev_height_columns; the host
+    build of the march the kernel runs, no handle, no device): p (...), theta (..., L) with level 0 the bottom, sig, dsig,
+    sigt (L,), hmG (...) the heightmap times G per column (None: 0) -> (Z (..., N) in m, valid (..., N) bool); Z holds NaN
+    where a target is invalid.  ValueError for a refused argument"""
+    theta = np.asarray(theta, dtype=np.float64)
+    L = theta.shape[-1] if theta.ndim else 0
+    tt = as_f64(theta.reshape(-1, L) if L else theta, name="theta")
+    pp = as_f64(p, theta.shape[:-1], "p").reshape(-1)
+    hh = None if hmG is None else as_f64(hmG, theta.shape[:-1], "hmG").reshape(-1)
+    lev = [as_f64(np.asarray(x, dtype=np.float64).reshape(-1), (L,), name) for x, name in ((sig, "sig"), (dsig, "dsig"), (sigt, "sigt"))]
+    P = plev_array(plev)
+    out = np.full((pp.size, P.size), np.nan)
+    valid = np.zeros((pp.size, P.size), dtype=np.intc)
+    _check(lib.gcm_plev_height_columns(pp.size, L, P.size, _tab(pp), _tab(tt), _tab(hh), _tab(lev[0]), _tab(lev[1]), _tab(lev[2]),
+                                       float(ptop), _tab(P), _tab(out), valid.ctypes.data_as(C.POINTER(C.c_int))))
+    return out.reshape(theta.shape[:-1] + (P.size,)), valid.reshape(theta.shape[:-1] + (P.size,)).astype(bool)
+
+
 SPECTRA_WORDS = ("uu", "vv", "TT", "uv", "vT", "vtheta")    # the products of gcm_get_spectra's s
 
 
@@ -1586,6 +1675,84 @@ class Core:
         the count (gcm_get_plev_climate).  GcmError where none is registered"""
         n, s = self.plev_climate_sums()
         return PlevClimate.from_sums(n, self.plev_climate_levels, s, self.W)
+
+    # -- geopotential height on pressure levels, time-mean maps (GCM_PE25D) ----------------
+    def plev_height(self, plev, fill=np.nan):
+        """-> (Z (N, H, W) in m, valid (N, H, W) bool): the geopotential height of the current state on the pressures
+        plev (Pa, strictly decreasing) by one launch (gcm_plev_height): the model's own mid-level geopotential, continued
+        inside the bracketing layer linearly in the Exner function; `fill` where the pressure lies under the ground or
+        above the top mid-level.  The call holds 8 N H W bytes of device memory (and the mask's 4 N H W) while it runs"""
+        P = plev_array(plev)
+        out = np.empty((P.size, self.H, self.W))
+        valid = np.empty((P.size, self.H, self.W), dtype=np.int32)
+        _check(lib.gcm_plev_height(self._h, P.size, _tab(P), float(fill), _tab(out), valid.ctypes.data_as(C.POINTER(C.c_int32))),
+               self._h)
+        return out, valid.astype(bool)
+
+    def set_plev_maps(self, every=1, plev=None):
+        """accumulate time-mean maps on pressure levels on the device (gcm_set_plev_maps): from now on every `every`-th
+        step of step() / band_run() / end_step() ends -- behind the spectra's sample -- with one launch that adds Z, T,
+        uc, vc, q and the products of `PlevMaps` at the pressures plev (Pa, strictly decreasing) to float64 sums per
+        (target, cell) in the handle; longitude is kept.  The sums take 8 (13 N + 2) H W bytes of device memory: meant
+        for a handful of levels (500 hPa, 850 hPa ...), not for all of them.  The step counter is the registration's own.
+        Registering again resets; every=0 unregisters and frees"""
+        if int(every) == 0:
+            _check(lib.gcm_set_plev_maps(self._h, 0, 0, None), self._h)
+            return
+        if int(every) < 0:
+            raise ValueError("every must be >= 0")
+        P = plev_array(plev)
+        _check(lib.gcm_set_plev_maps(self._h, int(every), P.size, _tab(P)), self._h)
+
+    @property
+    def plev_maps_every(self):
+        """the registered sampling interval in steps, 0 where none is registered (gcm_plev_maps_every)"""
+        return _count(lib.gcm_plev_maps_every(self._h), self._h)
+
+    @property
+    def plev_maps_levels(self):
+        """the registered targets (N,) in Pa (gcm_plev_maps_levels); GcmError where none are registered"""
+        P = np.empty(_lib.PLEV_MAX)
+        n = _count(lib.gcm_plev_maps_levels(self._h, _tab(P), _lib.PLEV_MAX), self._h)
+        return P[:n].copy()
+
+    def plev_maps_plan(self):
+        """the launch geometry of a sample of this handle, without launching (gcm_plev_maps_plan): chunks (256-column
+        chunks of a row, grid x), rows (grid y; 0 without a registration: no work), threads, lds_bytes, targets (0
+        without a registration)"""
+        out = (C.c_int * _lib.PLEV_MAP_PLAN_WORDS)()
+        _check(lib.gcm_plev_maps_plan(self._h, out, _lib.PLEV_MAP_PLAN_WORDS), self._h)
+        return dict(chunks=out[0], rows=out[1], threads=out[2], lds_bytes=out[3], targets=out[4])
+
+    def plev_maps_sample(self):
+        """one sample of the current state now (gcm_plev_maps_sample); the step counter is untouched.  A band: the
+        ghost rows of the current state must be current, as for climate_sample"""
+        _check(lib.gcm_plev_maps_sample(self._h), self._h)
+
+    def plev_maps_reset(self):
+        """zero the sums and the sample count (gcm_plev_maps_reset)"""
+        _check(lib.gcm_plev_maps_reset(self._h), self._h)
+
+    def plev_maps_sums(self):
+        """-> (n, s (13, N, H, W), s2 (2, H, W)): the raw float64 sums as the device holds them (gcm_get_plev_maps), word
+        0 of s the count of valid samples; one synchronisation"""
+        s = np.empty((_lib.PLEV_MAP_WORDS, self.plev_maps_levels.size, self.H, self.W))
+        s2 = np.empty((_lib.PLEV_MAP_WORDS2, self.H, self.W))
+        n = C.c_int64(0)
+        _check(lib.gcm_get_plev_maps(self._h, _tab(s), _tab(s2), C.byref(n)), self._h)
+        return int(n.value), s, s2
+
+    def put_plev_maps(self, n, s, s2):
+        """upload sums taken by plev_maps_sums() (gcm_put_plev_maps): a restart goes on where the run stopped"""
+        s = as_f64(s, (_lib.PLEV_MAP_WORDS, self.plev_maps_levels.size, self.H, self.W), "s")
+        s2 = as_f64(s2, (_lib.PLEV_MAP_WORDS2, self.H, self.W), "s2")
+        _check(lib.gcm_put_plev_maps(self._h, _tab(s), _tab(s2), int(n)), self._h)
+
+    def plev_maps(self):
+        """-> PlevMaps: the sample count, the targets, the coverage, the conditional means and the means of p and p p
+        (gcm_get_plev_maps).  GcmError where none are registered"""
+        n, s, s2 = self.plev_maps_sums()
+        return PlevMaps.from_sums(n, self.plev_maps_levels, s, s2)
 
     # -- zonal wavenumber spectra (GCM_PE25D) ----------------------------------------------
     def set_spectra(self, every=1, mmax=None):

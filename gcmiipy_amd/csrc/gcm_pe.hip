@@ -1,6 +1,6 @@
 // GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (horizontal diffusion, solar step, Held-Suarez forcing,
-// boundary layer, convective adjustment, moist physics, climatology sample, pressure-level climatology sample, spectra sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
-// only (tracers, step phases and halo buffers, ground and physics, horizontal diffusion, Held-Suarez, boundary layer, convective adjustment, moist physics, climatology, pressure levels, spectra, the filter and the taps).
+// boundary layer, convective adjustment, moist physics, climatology sample, pressure-level climatology sample, spectra sample, pressure-level maps sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
+// only (tracers, step phases and halo buffers, ground and physics, horizontal diffusion, Held-Suarez, boundary layer, convective adjustment, moist physics, climatology, pressure levels and their heights and maps, spectra, the filter and the taps).
 // Host code only: a guard and one forwarding call into the pe25d_* units, through gcm_handle.h and pe25d_kernels.h.
 #include <cmath>
 
@@ -16,10 +16,10 @@ using namespace gcm;
 // pe_band_hdiff_rows), the solar step at the
 // current clock, utc += dt, the Held-Suarez forcing,
 // the boundary layer (on a band: then a third exchange of the edge rows), the convective adjustment, the moist physics,
-// the climatology's sample, the pressure-level climatology's sample, the spectra's sample.  Each launch runs only if its phase is
+// the climatology's sample, the pressure-level climatology's sample, the spectra's sample, the pressure-level maps' sample.  Each launch runs only if its phase is
 // registered: the diffusion in pe25d_hdiff_on, the solar step and the forcing in GcmPhases, the boundary layer, the adjustment and the moist physics where
 // their sums are in place (pe25d_sums_on),
-// the climatology in pe25d_climate_due, the pressure-level climatology in pe25d_plev_climate_due, the spectra in pe25d_spectra_due.  The order is written down in pe_phase_rows, and in pe_phase_tables for what a
+// the climatology in pe25d_climate_due, the pressure-level climatology in pe25d_plev_climate_due, the spectra in pe25d_spectra_due, the pressure-level maps in pe25d_plev_maps_due.  The order is written down in pe_phase_rows, and in pe_phase_tables for what a
 // run prepares ahead of it.
 
 // The registered diffusion's device tables and landing fields for dt; gcm_set_physics: the radiation kernel's tables in
@@ -135,10 +135,11 @@ int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax, int which) {
 int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail, int which) {
     if (int rc = pe_phase_rows(h, dt, -1, -g, h->H + g, 0, 0, keep_ghosts, true, h->stream, which, h->wrap ? nullptr : tail)) return rc;
     if (!(which & kPhasesTail)) return GCM_OK;
-    // gcm_set_climate, gcm_set_plev_climate, gcm_set_spectra: a sample of the state the step leaves, behind every phase
-    // that changes it.  Each diagnostic counts the step on a counter of its own
+    // gcm_set_climate, gcm_set_plev_climate, gcm_set_spectra, gcm_set_plev_maps: a sample of the state the step leaves,
+    // behind every phase that changes it.  Each diagnostic counts the step on a counter of its own
     const bool clim = pe25d_climate_due(h->pe), plev = pe25d_plev_climate_due(h->pe), spec = pe25d_spectra_due(h->pe);
-    if (!clim && !plev && !spec) return GCM_OK;
+    const bool maps = pe25d_plev_maps_due(h->pe);
+    if (!clim && !plev && !spec && !maps) return GCM_OK;
     // a band: either sample reads the own rows as the phases above left them on the compute stream, and row -1 of v,
     // the first north ghost row, as the step's last exchange delivered it (the post-corrector exchange and the ghost
     // rows' Held-Suarez launch; with the boundary layer registered the third exchange) -- on the second stream where the
@@ -155,7 +156,10 @@ int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStre
     // gcm_set_plev_climate: directly behind the climatology's sample, ahead of the spectra's
     if (plev)
         if (int rc = pe25d_plev_climate_sample(h->pe, h->stream, &h->err)) return rc;
-    if (spec) return pe25d_spectra_sample(h->pe, h->stream, &h->err);
+    if (spec)
+        if (int rc = pe25d_spectra_sample(h->pe, h->stream, &h->err)) return rc;
+    // gcm_set_plev_maps: behind the spectra's sample, the last of the step
+    if (maps) return pe25d_plev_maps_sample(h->pe, h->stream, &h->err);
     return GCM_OK;
 }
 
@@ -783,6 +787,64 @@ int gcm_get_plev_climate(gcm_handle *h, double *s, int64_t *nsamples) {
 int gcm_put_plev_climate(gcm_handle *h, const double *s, int64_t nsamples) {
     if (int rc = pe_on_device(h, "gcm_put_plev_climate")) return rc;
     return pe25d_put_plev_climate(h->pe, s, nsamples, h->stream, &h->err);
+}
+
+// ------------------------------------------------------------------ geopotential height on pressure levels, time-mean maps
+int gcm_plev_height_columns(int ncol, int L, int N, const double *p, const double *theta, const double *hmG, const double *sig,
+                            const double *dsig, const double *sigt, double ptop, const double *P, double *out, int *valid) {
+    return plev_height_columns(ncol, L, N, p, theta, hmG, sig, dsig, sigt, ptop, P, out, valid, &gcm_create_error());
+}
+
+int gcm_plev_height(gcm_handle *h, int N, const double *P, double fill, double *out, int32_t *valid) {
+    if (int rc = pe_on_device(h, "gcm_plev_height")) return rc;
+    return pe25d_plev_height(h->pe, N, P, fill, out, valid, h->stream, &h->err);
+}
+
+int gcm_set_plev_maps(gcm_handle *h, int every, int N, const double *P) {
+    if (int rc = pe_only(h, "gcm_set_plev_maps")) return rc;
+    if (every < 0) return fail(h, GCM_ERR_ARG, "gcm_set_plev_maps: every must be >= 0");
+    if (int rc = select_device(h)) return rc;
+    return pe25d_set_plev_maps(h->pe, every, N, P, h->stream, &h->err);
+}
+
+int gcm_plev_maps_every(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_plev_maps_every(h->pe) : 0;
+}
+
+int gcm_plev_maps_levels(const gcm_handle *h, double *P, int cap) {
+    if (int rc = pe_only(h, "gcm_plev_maps_levels")) return rc;
+    const int N = pe25d_plev_maps_levels(h->pe, P, cap);
+    if (N < 0)
+        return fail(const_cast<gcm_handle *>(h), GCM_ERR_STATE, "gcm_plev_maps_levels: no pressure-level maps registered (gcm_set_plev_maps)");
+    return N;
+}
+
+int gcm_plev_maps_plan(gcm_handle *h, int *out, int nout) {
+    if (int rc = pe_only(h, "gcm_plev_maps_plan")) return rc;
+    if (int rc = pe25d_plev_maps_plan(h->pe, out, nout))
+        return fail(h, rc, "gcm_plev_maps_plan: a null pointer or fewer than GCM_PLEV_MAP_PLAN_WORDS words");
+    return GCM_OK;
+}
+
+int gcm_plev_maps_sample(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_plev_maps_sample")) return rc;
+    return pe25d_plev_maps_sample(h->pe, h->stream, &h->err);
+}
+
+int gcm_plev_maps_reset(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_plev_maps_reset")) return rc;
+    return pe25d_plev_maps_reset(h->pe, h->stream, &h->err);
+}
+
+int gcm_get_plev_maps(gcm_handle *h, double *s, double *s2, int64_t *nsamples) {
+    if (int rc = pe_on_device(h, "gcm_get_plev_maps")) return rc;
+    return pe25d_get_plev_maps(h->pe, s, s2, nsamples, h->stream, &h->err);
+}
+
+int gcm_put_plev_maps(gcm_handle *h, const double *s, const double *s2, int64_t nsamples) {
+    if (int rc = pe_on_device(h, "gcm_put_plev_maps")) return rc;
+    return pe25d_put_plev_maps(h->pe, s, s2, nsamples, h->stream, &h->err);
 }
 
 // ------------------------------------------------------------------ zonal-mean climatology

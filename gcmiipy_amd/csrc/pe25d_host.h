@@ -10,6 +10,7 @@
 //   pe25d_climate.hip  the zonal-mean climatology: its kernel, its sums and their way to the host and back
 //   pe25d_spectra.hip  the zonal wavenumber spectra: their kernel, their sums and their way to the host and back
 //   pe25d_plev.hip     pressure levels: the column rule's host build, the map and sample kernels, the sample's sums
+//   pe25d_plev_height.hip  geopotential height on pressure levels: the rule's host build, the kernel, the maps' sums
 //   pe25d_moist.hip    moist physics: the saturation routine, the kernel and its launches
 //   pe25d_convect.hip  convective adjustment: the pooling routine, the kernel and its launches
 //   pe25d_convect_tracers.hip  the tracers' convective mixing in the adjustment's blocks: the kernel, its launch, the opt-ins
@@ -19,7 +20,8 @@
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
 // gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
 // pe25d_hdiff_rows, pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample,
-// pe25d_plev_climate_due, pe25d_plev_climate_sample, pe25d_spectra_due, pe25d_spectra_sample).
+// pe25d_plev_climate_due, pe25d_plev_climate_sample, pe25d_spectra_due, pe25d_spectra_sample, pe25d_plev_maps_due,
+// pe25d_plev_maps_sample).
 #pragma once
 #include "pe25d_kernels.h"
 
@@ -126,6 +128,16 @@ struct PePlevClimate {
     long long n = 0;                            // samples in the sums
 };
 
+// Time-mean maps on pressure levels (pe25d_plev_height.hip, gcm_set_plev_maps): the targets and the float64 sums on the
+// device, the targets' host copy (its size is N) and the two counters
+struct PePlevMaps {
+    double *buf = nullptr;                      // device: P [N], s [GCM_PLEV_MAP_WORDS][N][H][W], s2 [GCM_PLEV_MAP_WORDS2][H][W]
+    std::vector<double> P;                      // the registered targets, Pa
+    int every = 0;                              // a sample every so many steps; 0: not registered
+    long long steps = 0;                        // steps taken by gcm_step / gcm_band_run since the registration
+    long long n = 0;                            // samples in the sums
+};
+
 // Zonal wavenumber spectra (pe25d_spectra.hip, gcm_set_spectra): the float64 twiddles and sums on the device and the counters
 struct PeSpectra {
     double *buf = nullptr;                      // device: tw [W] double2, sig [L], s [GCM_SPEC_WORDS][L][H][mmax + 1]
@@ -200,6 +212,7 @@ struct Pe25d {
     std::vector<void *> allocs;
     std::vector<double> dsig_host;              // geometry.py dsig, float64 (radiation level tables)
     std::vector<double> sig_host;               // geometry.py sig, float64
+    std::vector<double> sigt_host;              // geometry.py sigt, float64 (the height on pressure levels)
     std::vector<double> dxj_host, dxh_host;     // geometry.py dx_j, dx_h over the global height, float64 (horizontal diffusion tables)
     PeBufs<double> d;
     PeBufs<float> f;
@@ -218,6 +231,7 @@ struct Pe25d {
     double *stage3 = nullptr;                   // float64 transpose staging, host layout
     double *exner_tab = nullptr;
     double *lev_tab = nullptr;                  // sig [L], dsig [L] in float64, uploaded on first use (pe25d_level_table)
+    double *plev_height_tab = nullptr;          // sig [L], dsig [L], sigt [L] in float64, uploaded on first use (pe25d_plev_height.hip)
     FftPlan plan{};
     SuperPlan cplan{};
     double *gt = nullptr;                       // ground temperature [H + 2 ghost rows a side][W], interior row 0 (column physics)
@@ -269,6 +283,7 @@ struct Pe25d {
     PeClimate clim;
     PePlevClimate plev;
     PeSpectra spec;
+    PePlevMaps pmaps;
     PeMoist moist;
     PeConvect convect;
     PeBoundary boundary;

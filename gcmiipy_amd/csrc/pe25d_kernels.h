@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip, pe25d_plev.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
+// pe25d_climate.hip, pe25d_plev.hip, pe25d_plev_height.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -80,6 +80,22 @@ int pe25d_plev_climate_sample(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_plev_climate_reset(Pe25d *m, hipStream_t s, std::string *err);
 int pe25d_get_plev_climate(Pe25d *m, double *sums, int64_t *nsamples, hipStream_t s, std::string *err);
 int pe25d_put_plev_climate(Pe25d *m, const double *sums, int64_t nsamples, hipStream_t s, std::string *err);
+// Geopotential height on pressure levels and time-mean maps (pe25d_plev_height.hip).  plev_height_columns: no handle, no
+// device (gcm_plev_height_columns).  pe25d_plev_height: gcm_plev_height on `s`, synchronised before it returns.
+// gcm_set_plev_maps and its companions on `s`, the caller's stream: pe25d_plev_maps_due counts one step, as
+// pe25d_climate_due does; pe25d_plev_maps_levels: -1 without a registration; pe25d_plev_maps_plan: gcm_plev_maps_plan
+int plev_height_columns(int ncol, int L, int N, const double *p, const double *theta, const double *hmG, const double *sig,
+                        const double *dsig, const double *sigt, double ptop, const double *P, double *out, int *valid, std::string *err);
+int pe25d_plev_height(Pe25d *m, int N, const double *P, double fill, double *out, int32_t *valid, hipStream_t s, std::string *err);
+int pe25d_set_plev_maps(Pe25d *m, int every, int N, const double *P, hipStream_t s, std::string *err);
+int pe25d_plev_maps_every(const Pe25d *m);
+int pe25d_plev_maps_levels(const Pe25d *m, double *P, int cap);
+bool pe25d_plev_maps_due(Pe25d *m);
+int pe25d_plev_maps_plan(const Pe25d *m, int *out, int nout);
+int pe25d_plev_maps_sample(Pe25d *m, hipStream_t s, std::string *err);
+int pe25d_plev_maps_reset(Pe25d *m, hipStream_t s, std::string *err);
+int pe25d_get_plev_maps(Pe25d *m, double *sums, double *sums2, int64_t *nsamples, hipStream_t s, std::string *err);
+int pe25d_put_plev_maps(Pe25d *m, const double *sums, const double *sums2, int64_t nsamples, hipStream_t s, std::string *err);
 // Zonal wavenumber spectra (pe25d_spectra.hip): gcm_set_spectra and its companions on `s`, the caller's stream.
 // pe25d_spectra_due: counts one step, as pe25d_climate_due does; pe25d_spectra_mmax: -1 without a registration;
 // pe25d_spectra_plan: gcm_spectra_plan

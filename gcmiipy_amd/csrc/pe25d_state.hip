@@ -381,6 +381,7 @@ Pe25d *pe25d_create(const gcm_config &cfg, hipStream_t main_stream, std::string 
     m->f32 = cfg.dtype == GCM_F32;
     m->dsig_host.assign(cfg.dsig, cfg.dsig + cfg.layers);
     m->sig_host.assign(cfg.sig, cfg.sig + cfg.layers);
+    m->sigt_host.assign(cfg.sigt, cfg.sigt + cfg.layers);
     m->dxj_host.assign(cfg.dx_j, cfg.dx_j + cfg.global_height);
     m->dxh_host.assign(cfg.dx_h, cfg.dx_h + cfg.global_height);
     const int W = m->W, L = m->L;

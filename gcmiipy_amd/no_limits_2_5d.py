@@ -60,7 +60,8 @@ def full_timestep(p, u, v, t, q, g, dt, utc, geom, stats=STATS):
 
 
 def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=None, physics=False, tracers=None,
-              tracer_scheme=None, tracer_forcing=None, held_suarez=False, climate=0, spectra=0, plev_climate=None):
+              tracer_scheme=None, tracer_forcing=None, held_suarez=False, climate=0, spectra=0, plev_climate=None,
+              plev_maps=None):
     """no_limits_2_5d.py:220-236 (and test_geography.py:6-23 with `bump=(j, i, metres)`): the
     state stays in HBM for all `timesteps`; STATS come from device reductions every step.
     physics=True: every step is followed by solar_timestep(t, p, g, dt, utc, geom) with utc = 0, dt, 2 dt, ...
@@ -78,7 +79,10 @@ def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=
     spectra on the device, at the default mmax, and their record (Core.spectra) is appended to the result behind the
     climatology's (Core.set_spectra).  plev_climate=(every, plev): every `every`-th step ends with a sample of the
     zonal-mean climatology on the pressure levels plev (Pa, strictly decreasing) on the device, and its record
-    (Core.plev_climate) is appended to the result last (Core.set_plev_climate)."""
+    (Core.plev_climate) is appended to the result behind the spectra's (Core.set_plev_climate).  plev_maps=(every, plev):
+    every `every`-th step ends with a sample of the time-mean maps -- the geopotential height Z, T, the centred winds, q
+    and their products, longitude kept -- on the pressure levels plev on the device, and their record (Core.plev_maps) is
+    appended to the result last (Core.set_plev_maps)."""
     if tracer_forcing and tracers is None:
         raise ValueError("tracer_forcing needs tracers")
     geom = geometry.gen_geometry(height, width, layers, sig_func=geometry.manabe_sig)
@@ -105,6 +109,8 @@ def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=
             c.set_spectra(int(spectra))
         if plev_climate:
             c.set_plev_climate(int(plev_climate[0]), plev_climate[1])
+        if plev_maps:
+            c.set_plev_maps(int(plev_maps[0]), plev_maps[1])
         for _ in range(timesteps):
             c.step(1, scalar(dt))
             _record(c, geom, stats)
@@ -118,7 +124,8 @@ def run_model(height, width, layers, dt, timesteps, callback, stats=STATS, bump=
         clim = c.climate() if climate else None
         spec = c.spectra() if spectra else None
         plev = c.plev_climate() if plev_climate else None
+        maps = c.plev_maps() if plev_maps else None
     finally:
         c.close()
     out = (p, u, v, t, q, g, geom) + ((tracers,) if tracers is not None else ())
-    return out + ((clim,) if climate else ()) + ((spec,) if spectra else ()) + ((plev,) if plev_climate else ())
+    return out + ((clim,) if climate else ()) + ((spec,) if spectra else ()) + ((plev,) if plev_climate else ()) + ((maps,) if plev_maps else ())

@@ -900,7 +900,8 @@ int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t n
  *   (the correctly rounded float64 division);  x_n = (1 - w) x[k] + w x[k + 1]: a target that sits exactly on a level
  *   returns that level's value exactly.  NaN in a value propagates; it never decides validity.
  *   Linear in pressure on purpose: the rule needs no transcendental, so the mask and the interpolated uc, vc, theta and q
- *   can be restated bit for bit.  Log-pressure weights and the geopotential height on pressure levels are not offered.
+ *   can be restated bit for bit.  Log-pressure weights are not offered; the geopotential height on the same targets,
+ *   which is not linear in p, has calls of its own (gcm_plev_height, gcm_set_plev_maps below).
  * Five cell-centre quantities are interpolated, formed per level exactly as the climatology forms them:
  *   uc = 0.5 (u[i] + u[i - 1]), periodic in i;  vc = 0.5 (v[j] + v[j - 1]);  theta;  T = theta Pi(pl), formed on the
  *   sigma level with the kernels' own Exner routine and then interpolated;  q.  Row -1 is row H - 1 on a single domain
@@ -955,6 +956,77 @@ int gcm_plev_climate_reset(gcm_handle *h);
 int gcm_get_plev_climate(gcm_handle *h, double *s, int64_t *nsamples);
 int gcm_put_plev_climate(gcm_handle *h, const double *s, int64_t nsamples);
 int gcm_plev_climate_plan(gcm_handle *h, int *out, int nout);
+/* GCM_PE25D: geopotential height on pressure levels, and time-mean maps that keep longitude.  Z500 is the first map
+ * drawn of such a run -- its variance is the storm track, its time mean over topography (gcm_config.heightmap) the
+ * stationary waves -- and the three accumulators above all collapse longitude.  fp64 and fp32 handles, single domains
+ * and latitude bands.
+ * The column rule -- float64, storage values widened exactly, every operation rounded on its own (no contraction), the
+ * divisions correctly rounded; levels, targets P[n], validity and bracket exactly as for the pressure levels above:
+ *   The mid-level geopotential is the model's, in its summation order, Pi = (pl / P0)^kappa by the kernels' own Exner
+ *   routine:   rho[k] = pl[k] / (Rd (theta[k] Pi[k]));   s1[k] = ((sig[k] p) / rho[k]) dsig[k];
+ *   stp[k] = (Cp (0.5 (theta[k] + theta[k + 1]))) (Pi[k] - Pi[k + 1]), k + 1 = L taken as 0, as the model has it;
+ *   s2[k] = sigt[k] stp[k];   phi[0] = (sum_k (s1[k] - s2[k]), k ascending from 0.0) + heightmap G, the heightmap's row
+ *   being the global row (row0 + j on a band);   phi[k] = phi[k - 1] + stp[k - 1].
+ *   (The model's step takes a reciprocal approximation for 1 / rho: its phi agrees with this one to rounding, not bit
+ *   for bit.)
+ *   For a valid target in bracket k the height continues the model's hydrostatic relation inside the layer, linear in Pi
+ *   and not in p:   Z[n] = (phi[k] + (Cp (0.5 (theta[k] + theta[k + 1]))) (Pi(pl[k]) - Pi(P[n]))) / G.
+ *   A target that sits exactly on a level returns that level's phi / G exactly, whichever of its two brackets it is
+ *   evaluated in.  No extrapolation under the ground or above the top mid-level.  NaN in theta propagates and never
+ *   decides validity; a column with p <= 0 or a NaN p has no valid target.
+ * gcm_plev_height_columns: the host build of the rule, from the header the kernel compiles from; no handle, no device.
+ *   p [ncol], theta [ncol][L], hmG [ncol] (heightmap G per column; NULL: 0), sig, dsig, sigt [L], out and valid
+ *   [ncol][N]; out is left untouched where a target is invalid.  GCM_ERR_ARG: a null pointer other than hmG, ncol < 0,
+ *   L < 2, a ptop that is not finite, N out of range, targets that are not strictly decreasing, positive and finite.
+ * gcm_plev_height: one launch over the current state.  out [N][H][W] float64 in metres; an invalid entry holds `fill`.
+ *   valid [N][H][W] may be NULL.  The call holds 8 N H W bytes of device memory for its duration (4 N H W more where
+ *   valid is asked for) and releases them.  On a band the ghost rows need not be current: the height reads theta and p
+ *   of own rows only.  A pure reader of the state; it synchronises the handle's stream.
+ * gcm_set_plev_maps(every >= 1, N, P): the accumulating sample.  Sums s [GCM_PLEV_MAP_WORDS][N][H][W], float64, plain sums
+ *   over the samples; nothing is divided or reduced along i on the device:
+ *     0 count (1.0 per valid sample)   1 Z   2 Z Z   3 T   4 T T   5 uc   6 vc   7 uc uc   8 vc vc   9 uc vc   10 vc T
+ *     11 q   12 vc q
+ *   T = theta Pi, uc, vc and q are the pressure-level quantities above, interpolated linearly in p by the same routines:
+ *   the bits gcm_plev_fields returns; Z the bits gcm_plev_height returns; the products are products of those.  A sample
+ *   in which the target is invalid in a column adds nothing to that column's words: the host forms the conditional
+ *   means s[w] / s[0].  And s2 [GCM_PLEV_MAP_WORDS2][H][W]: p and p p of every column and sample.
+ *   One writer per accumulator word and launch, no atomics, no reduction across columns: a cell's sums depend on that
+ *   column's data only -- not on H, W, the band or the CU count -- and a band's rows hold the bits of the same rows of
+ *   the single domain.
+ *   The registration allocates and zeroes the sums, copies the targets and starts a step counter of its own; it holds
+ *   8 (N + (GCM_PLEV_MAP_WORDS N + GCM_PLEV_MAP_WORDS2) H W) bytes on the device -- 340 MB at 1440 x 720 with three
+ *   targets: it is meant for a handful of levels, not for all of them -- besides a level table of 24 L bytes that the
+ *   handle keeps.  From then on every `every`-th step of gcm_step, gcm_band_run and gcm_end_step / gcm_end_step_finish
+ *   ends with one sample, behind the spectra's; on a band the compute stream joins the exchange stream's tail once for
+ *   all the samples due on that step.  gcm_half_step and gcm_step_phase never sample.  Registering again resets sums,
+ *   count and counter; every = 0 unregisters and frees.  Without a registration nothing is launched and every result
+ *   and timing is as before; a sample changes nothing a step reads.
+ * gcm_plev_maps_every: the registered `every`, 0 without one (other models: 0).  gcm_plev_maps_levels: copies up to cap
+ *   targets to P (may be NULL) and returns N.  gcm_plev_maps_sample: one sample now, the counter untouched; a band's
+ *   ghost rows must be current (vc reads v's first north ghost row).  gcm_plev_maps_reset zeroes the sums and the count.
+ *   gcm_get_plev_maps synchronises the handle's stream once and copies the sums and the count; any of the three pointers
+ *   may be NULL.  gcm_put_plev_maps uploads them (restarts): s and s2 are required, nsamples >= 0.
+ * gcm_plev_maps_plan: the launch geometry of a sample, without launching, GCM_PLEV_MAP_PLAN_WORDS words:
+ *   [0] grid x = 256-column chunks of a row  [1] grid y = rows (0 without a registration: no work)  [2] threads
+ *   [3] LDS bytes  [4] targets (0 without a registration).  One kernel path serves every L: a lane reads its theta
+ *   column twice, the second time from cache.
+ * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, every < 0, bad targets, a
+ * null out.  GCM_ERR_UNSUPPORTED: other models, L < 2.  GCM_ERR_STATE: levels, get, put, reset or sample without a
+ * registration.  GCM_ERR_HIP: an allocation that fails; nothing stays registered then.                              */
+#define GCM_PLEV_MAP_WORDS 13      /* sums per (target, cell) */
+#define GCM_PLEV_MAP_WORDS2 2      /* sums per cell           */
+#define GCM_PLEV_MAP_PLAN_WORDS 5
+int gcm_plev_height_columns(int ncol, int L, int N, const double *p, const double *theta, const double *hmG, const double *sig,
+                            const double *dsig, const double *sigt, double ptop, const double *P, double *out, int *valid);
+int gcm_plev_height(gcm_handle *h, int N, const double *P, double fill, double *out, int32_t *valid);
+int gcm_set_plev_maps(gcm_handle *h, int every, int N, const double *P);
+int gcm_plev_maps_every(const gcm_handle *h);
+int gcm_plev_maps_levels(const gcm_handle *h, double *P, int cap);
+int gcm_plev_maps_sample(gcm_handle *h);
+int gcm_plev_maps_reset(gcm_handle *h);
+int gcm_get_plev_maps(gcm_handle *h, double *s, double *s2, int64_t *nsamples);
+int gcm_put_plev_maps(gcm_handle *h, const double *s, const double *s2, int64_t nsamples);
+int gcm_plev_maps_plan(gcm_handle *h, int *out, int nout);
 /* Zonal wavenumber spectra of GCM_PE25D accumulated on the device: the kinetic-energy and temperature spectra by zonal
  * wavenumber and the split of the eddy momentum and heat fluxes over the waves, which the zonal sums of the climatology
  * cannot give, without a host round trip per step (fp64 and fp32 handles, single domains and latitude bands).  One launch
