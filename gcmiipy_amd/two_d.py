@@ -30,7 +30,12 @@ def _advect(scheme, axes, finite, dt, spatial_change, V, q, nsteps=1):
     qm = as_f64(qm, name="q")
     if qm.ndim == 1:                                     # 1-D stacks (test_oneD.py): one row per cell
         vm = as_f64(vm, (1,) + qm.shape, "V")
-        out = _advect(scheme, 1, finite, dt, (spatial_change[0], spatial_change[0]),
+        # the cell volume is the product of ALL entries of spatial_change (two_d.py:137-138,154-155): the second
+        # spacing carries the rest, 1 for a one-entry tuple, so that the face area of the plain flux is 1
+        rest = 1.0
+        for d in spatial_change[1:]:
+            rest *= scalar(d)
+        out = _advect(scheme, 1, finite, dt, (spatial_change[0], rest),
                       np.stack([vm[0][:, None], np.zeros((qm.size, 1))]), qm[:, None], nsteps)
         return attach(np.asarray(out)[:, 0], qu)
     vm = as_f64(vm, (2,) + qm.shape, "V")
