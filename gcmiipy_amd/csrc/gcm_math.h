@@ -21,8 +21,15 @@ constexpr double kKappa = 287.0 / 1004.0;     // constants.py:28
 constexpr double kP0 = 100000.0;              // constants.py:31
 constexpr double kMuAir = 18.5 * 1e-6;        // constants.py:51
 
-// 1/x: v_rcp_f64 seed + two Newton-Raphson steps (no denormal/inf fix-ups: the
-// operands on this path are pressures, densities and sigma thicknesses).
+// 1/x: v_rcp_f64 seed + two Newton-Raphson steps, no denormal/inf fix-ups.  Most operands on this path are
+// pressures, densities and sigma thicknesses, far from either end of the range.  Two callers are not: the limiter
+// weights of face_flux (below) and of tracer_face (pe25d_tracer_lim.h) take the reciprocal of a sum of tracer
+// differences, which on the flank of a compact tracer blob is a denormal.  Measured on an MI355X: for x <= 2^-1024,
+// where 1/x overflows, the result is NaN (the seed is an infinity, the Newton steps take it to NaN); v_rcp_f32
+// returns an infinity for EVERY denormal x (profiles/tracer_range/).  face_flux at fp64 limits a face only where both
+// differences are normal numbers, so that their sum has a finite reciprocal; face_flux at fp32 and tracer_face clamp
+// the product to the weight's range, which takes NaN and infinity to its upper end.  Below the smallest normal number
+// either choice moves the result by less than that number (tests/tracer_range_cases.py).
 __device__ __forceinline__ double rcp(double x) {
     double r = __builtin_amdgcn_rcp(x);
     double e = __builtin_fma(-x, r, 1.0);
@@ -33,6 +40,7 @@ __device__ __forceinline__ double rcp(double x) {
 }
 // fp32: v_rcp_f32 is 1 ulp
 __device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+constexpr double kTinyF64 = 2.2250738585072014e-308;    // the smallest normal number: from it on 1/x is finite
 
 // ---- (p / P0) ** kappa by table + short series --------------------------------------
 // p = 2^e m, m in [1,2); i = top 6 mantissa bits; rc_i ~ 1/c_i with c_i the midpoint of
@@ -206,8 +214,20 @@ __device__ __forceinline__ T face_flux(T vel, T qm1, T q0, T q1, T q2, T dtdx) {
     // (r + |r|) / (1 + |r|) = 2 |num| / (|b| + |num|) if num b > 0 else 0 -- one reciprocal
     const T an = fabs(num), ab = fabs(b);
     // r > 0 <=> num and b are nonzero with equal signs (sign bits compared: no underflow)
-    const bool rpos = ((sign_word(num) ^ sign_word(b)) >= 0) && an > T(0.0) && ab > T(0.0);
-    const T phi = rpos ? (an + an) * rcp(ab + an) : T(0.0);
+    const bool same = (sign_word(num) ^ sign_word(b)) >= 0;
+    // 0 < phi < 2, and a sum of denormals has no reciprocal here (rcp above).  Either guard leaves the bits of every
+    // face with normal differences as they were; each type takes the one that keeps its fused kernels' registers
+    // (profiles/tracer_range/): a clamp costs the fp64 row march 0.2-0.3 % of c3, the comparisons cost the fp32
+    // one-column kernel 5 VGPRs and a wave.
+    T phi;
+    if constexpr (sizeof(T) == 8) {
+        // "nonzero" taken as "a normal number": a face with a denormal difference is donor-cell -- what the weight
+        // would have multiplied is smaller than the smallest normal number.  The comparisons stand where `> 0` stood.
+        phi = same && an >= kTinyF64 && ab >= kTinyF64 ? (an + an) * rcp(ab + an) : T(0.0);
+    } else {
+        // the clamp of tracer_face (pe25d_tracer_lim.h): the infinity of v_rcp_f32 goes to the weight's upper end
+        phi = same && an > T(0.0) && ab > T(0.0) ? fmin((an + an) * rcp(ab + an), T(2.0)) : T(0.0);
+    }
     return f_low + phi * (f_high - f_low);
 }
 template <bool LIMIT>
