@@ -214,16 +214,26 @@ class BandRunner:
             self.step(dt)
 
 
+def _merge_checked(name, parts):
+    """what merge_climate, merge_plev_climate, merge_plev_maps and merge_spectra check first of their bands' records: that
+    there are some, that they hold the same number of samples and, where they have targets, the same ones -> list(parts)"""
+    import numpy as np
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_%s: no records" % name)
+    if any(c.n != parts[0].n for c in parts):
+        raise ValueError("merge_%s: the bands hold %s samples" % (name, ", ".join(str(c.n) for c in parts)))
+    if hasattr(parts[0], "plev") and any(not np.array_equal(c.plev, parts[0].plev) for c in parts):
+        raise ValueError("merge_%s: the bands hold different pressure targets" % name)
+    return parts
+
+
 def merge_climate(parts):
     """the climatology of the whole domain from its bands': `parts` are the bands' Climate records (Core.climate) in
     row order; the rows are concatenated.  ValueError where the sample counts differ"""
     import numpy as np
     from .core import Climate
-    parts = list(parts)
-    if not parts:
-        raise ValueError("merge_climate: no records")
-    if any(c.n != parts[0].n for c in parts):
-        raise ValueError("merge_climate: the bands hold %s samples" % ", ".join(str(c.n) for c in parts))
+    parts = _merge_checked("climate", parts)
     return Climate(parts[0].n, *[np.concatenate([c[f] for c in parts], axis=-1) for f in range(1, len(Climate._fields))])
 
 
@@ -233,13 +243,7 @@ def merge_plev_climate(parts):
     sample counts or the targets differ"""
     import numpy as np
     from .core import PlevClimate
-    parts = list(parts)
-    if not parts:
-        raise ValueError("merge_plev_climate: no records")
-    if any(c.n != parts[0].n for c in parts):
-        raise ValueError("merge_plev_climate: the bands hold %s samples" % ", ".join(str(c.n) for c in parts))
-    if any(not np.array_equal(c.plev, parts[0].plev) for c in parts):
-        raise ValueError("merge_plev_climate: the bands hold different pressure targets")
+    parts = _merge_checked("plev_climate", parts)
     return PlevClimate(parts[0].n, np.array(parts[0].plev, dtype=np.float64),
                        *[np.concatenate([c[f] for c in parts], axis=-1) for f in range(2, len(PlevClimate._fields))])
 
@@ -250,13 +254,7 @@ def merge_plev_maps(parts):
     where the sample counts or the targets differ"""
     import numpy as np
     from .core import PlevMaps
-    parts = list(parts)
-    if not parts:
-        raise ValueError("merge_plev_maps: no records")
-    if any(c.n != parts[0].n for c in parts):
-        raise ValueError("merge_plev_maps: the bands hold %s samples" % ", ".join(str(c.n) for c in parts))
-    if any(not np.array_equal(c.plev, parts[0].plev) for c in parts):
-        raise ValueError("merge_plev_maps: the bands hold different pressure targets")
+    parts = _merge_checked("plev_maps", parts)
     return PlevMaps(parts[0].n, np.array(parts[0].plev, dtype=np.float64),
                     *[np.concatenate([c[f] for c in parts], axis=-2) for f in range(2, len(PlevMaps._fields))])
 
@@ -266,11 +264,7 @@ def merge_spectra(parts):
     order; the rows are concatenated.  ValueError where the sample counts or the numbers of wavenumbers differ"""
     import numpy as np
     from .core import Spectra
-    parts = list(parts)
-    if not parts:
-        raise ValueError("merge_spectra: no records")
-    if any(c.n != parts[0].n for c in parts):
-        raise ValueError("merge_spectra: the bands hold %s samples" % ", ".join(str(c.n) for c in parts))
+    parts = _merge_checked("spectra", parts)
     if any(c.uu.shape[-1] != parts[0].uu.shape[-1] for c in parts):
         raise ValueError("merge_spectra: the bands hold %s wavenumbers" % ", ".join(str(c.uu.shape[-1]) for c in parts))
     return Spectra(parts[0].n, *[np.concatenate([c[f] for c in parts], axis=-2) for f in range(1, len(Spectra._fields))])

@@ -44,7 +44,7 @@ ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
 import numpy as np
 
 from . import _lib
-from .core import COLUMN_PHASES, Core, GcmError, HDIFF_DEFAULTS, HELD_SUAREZ_DEFAULTS
+from .core import COLUMN_PHASES, Core, GcmError, HDIFF_DEFAULTS, HELD_SUAREZ_DEFAULTS, SAMPLERS
 from .geometry import Geom
 
 _GEOM_KEYS = ("sige", "sigt", "sigb", "dsig", "sig", "dsigv", "dx_j", "dx_h", "dy", "ptop",
@@ -82,21 +82,15 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
     if hs is not None:
         out["held_suarez"] = np.asarray([hs[k] for k in HELD_SUAREZ_DEFAULTS], dtype=np.float64)
         out["held_suarez_lat"] = core.held_suarez_lat
-    if core.model == _lib.PE25D and core.climate_every > 0:
-        n, m3, m2 = core.climate_sums()
-        out.update(climate_every=np.int64(core.climate_every), climate_n=np.int64(n), climate_m3=m3, climate_m2=m2)
-    if core.model == _lib.PE25D and getattr(core, "spectra_every", 0) > 0:   # (getattr: a stand-in without the spectra will do)
-        n, s = core.spectra_sums()
-        out.update(spectra_every=np.int64(core.spectra_every), spectra_mmax=np.int64(core.spectra_mmax), spectra_n=np.int64(n),
-                   spectra_s=s)
-    if core.model == _lib.PE25D and getattr(core, "plev_climate_every", 0) > 0:   # (getattr: as above)
-        n, s = core.plev_climate_sums()
-        out.update(plev_climate_every=np.int64(core.plev_climate_every), plev_climate_plev=core.plev_climate_levels,
-                   plev_climate_n=np.int64(n), plev_climate_sums=s)
-    if core.model == _lib.PE25D and getattr(core, "plev_maps_every", 0) > 0:   # (getattr: as above)
-        n, s, s2 = core.plev_maps_sums()
-        out.update(plev_maps_every=np.int64(core.plev_maps_every), plev_maps_plev=core.plev_maps_levels,
-                   plev_maps_n=np.int64(n), plev_maps_sums=s, plev_maps_sums2=s2)
+    # (the sampled diagnostics by their core._Sampler; getattr: a stand-in without one of them will do)
+    for sm in SAMPLERS if core.model == _lib.PE25D else ():
+        every = getattr(core, sm.name + "_every", 0)
+        if every > 0:
+            n, *sums = getattr(core, sm.name + "_sums")()
+            out[sm.name + "_every"], out[sm.name + "_n"] = np.int64(every), np.int64(n)
+            if sm.extra:                         # (the targets, mmax)
+                out["%s_%s" % (sm.name, sm.extra[0])] = np.asarray(getattr(core, sm.extra[1]))
+            out.update({"%s_%s" % (sm.name, k): x for k, x in zip(sm.keys, sums)})
     hd = getattr(core, "horizontal_diffusion", None) if core.model == _lib.PE25D else None   # (getattr: as above)
     if hd is not None:
         out["hdiff"] = np.asarray([hd[k] for k in HDIFF_DEFAULTS], dtype=np.float64)
@@ -171,20 +165,14 @@ def load(path):
     if "hdiff" in d.files:
         order, fields, nu, cmax = d["hdiff"]
         hd = dict(order=int(order), fields=int(fields), nu=float(nu), cmax=float(cmax))
-    clim = None
-    if "climate_every" in d.files:
-        clim = dict(every=int(d["climate_every"]), n=int(d["climate_n"]), m3=d["climate_m3"], m2=d["climate_m2"])
-    plev = None
-    if "plev_climate_every" in d.files:
-        plev = dict(every=int(d["plev_climate_every"]), plev=d["plev_climate_plev"], n=int(d["plev_climate_n"]),
-                    sums=d["plev_climate_sums"])
-    maps = None
-    if "plev_maps_every" in d.files:
-        maps = dict(every=int(d["plev_maps_every"]), plev=d["plev_maps_plev"], n=int(d["plev_maps_n"]),
-                    sums=d["plev_maps_sums"], sums2=d["plev_maps_sums2"])
-    spec = None
-    if "spectra_every" in d.files:
-        spec = dict(every=int(d["spectra_every"]), mmax=int(d["spectra_mmax"]), n=int(d["spectra_n"]), s=d["spectra_s"])
+    sampled = {sm.name: None for sm in SAMPLERS}
+    for sm in SAMPLERS:
+        if sm.name + "_every" in d.files:
+            rec = dict(every=int(d[sm.name + "_every"]), n=int(d[sm.name + "_n"]), **{k: d["%s_%s" % (sm.name, k)] for k in sm.keys})
+            if sm.extra:                         # (the targets as they are, mmax as an int)
+                x = d["%s_%s" % (sm.name, sm.extra[0])]
+                rec[sm.extra[0]] = x if x.ndim else int(x)
+            sampled[sm.name] = rec
     # (the parameters in the types of the phase's defaults: mix_q is an int)
     column = {ph.name: None for ph in COLUMN_PHASES}
     for ph in COLUMN_PHASES:
@@ -192,8 +180,7 @@ def load(path):
             par = {k: type(v)(x) for (k, v), x in zip(ph.defaults.items(), d[ph.name])}
             column[ph.name] = dict(params=par, n=int(d[ph.name + "_n"]), seconds=float(d[ph.name + "_seconds"]),
                                    **{f: d["%s_%s" % (ph.name, f)] for f in ph.fields})
-    return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, climate=clim,
-                spectra=spec, hdiff=hd, plev_climate=plev, plev_maps=maps,
+    return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, hdiff=hd, **sampled,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
@@ -228,18 +215,11 @@ def restore(path, **core_kwargs):
         core.set_held_suarez(ck["held_suarez"][1], **ck["held_suarez"][0])
     if ck["hdiff"] is not None:
         core.set_horizontal_diffusion(**ck["hdiff"])
-    if ck["climate"] is not None:
-        core.set_climate(ck["climate"]["every"])
-        core.put_climate(ck["climate"]["n"], ck["climate"]["m3"], ck["climate"]["m2"])
-    if ck["plev_climate"] is not None:
-        core.set_plev_climate(ck["plev_climate"]["every"], ck["plev_climate"]["plev"])
-        core.put_plev_climate(ck["plev_climate"]["n"], ck["plev_climate"]["sums"])
-    if ck["spectra"] is not None:
-        core.set_spectra(ck["spectra"]["every"], ck["spectra"]["mmax"])
-        core.put_spectra(ck["spectra"]["n"], ck["spectra"]["s"])
-    if ck["plev_maps"] is not None:
-        core.set_plev_maps(ck["plev_maps"]["every"], ck["plev_maps"]["plev"])
-        core.put_plev_maps(ck["plev_maps"]["n"], ck["plev_maps"]["sums"], ck["plev_maps"]["sums2"])
+    for sm in SAMPLERS:                      # (the order a step samples)
+        rec = ck[sm.name]
+        if rec is not None:
+            getattr(core, "set_" + sm.name)(rec["every"], *([rec[sm.extra[0]]] if sm.extra else []))
+            getattr(core, "put_" + sm.name)(rec["n"], *[rec[k] for k in sm.keys])
     for ph in COLUMN_PHASES:                 # (the model's order: the boundary layer, the convective adjustment, the moist physics)
         rec = ck[ph.name]
         if rec is not None:

@@ -757,6 +757,39 @@ _BOUNDARY = _ColumnPhase("boundary_layer", "boundary layer", _lib.BoundaryLayer,
 COLUMN_PHASES = (_BOUNDARY, _CONVECT, _MOIST)
 
 
+class _Sampler:
+    """what tells the sampled diagnostics apart -- the zonal-mean climatology, the pressure-level climatology, the
+    spectra and the pressure-level maps, in the order a step samples them in SAMPLERS -- for Core's operations on each
+    and for checkpoint.py: the name in the entry points and keys; the names of gcm_put_<name>'s sum arrays, their keys in
+    a checkpoint file and their shapes as a function of the core; what the registration takes besides `every` (the file
+    key and the Core property that returns it: the targets, mmax; None: nothing); the words of gcm_<name>_plan (None: no
+    such query); and record(core, n, *sums), the result's from_sums"""
+
+    def __init__(self, name, args, keys, shapes, extra, plan, record):
+        self.name, self.args, self.keys, self.shapes, self.extra, self.plan, self.record = name, args, keys, shapes, extra, plan, record
+        self.set, self.every, self.sample, self.reset, self.get, self.put = (
+            getattr(lib, "gcm_" + f % name) for f in ("set_%s", "%s_every", "%s_sample", "%s_reset", "get_%s", "put_%s"))
+        self.plan_of = getattr(lib, "gcm_%s_plan" % name) if plan else None
+
+
+_CLIMATE = _Sampler("climate", ("m3", "m2"), ("m3", "m2"),
+                    lambda c: ((_lib.CLIM_WORDS3, c.L, c.H), (_lib.CLIM_WORDS2, c.H)), None, None,
+                    lambda c, n, m3, m2: Climate.from_sums(n, m3, m2, c.W))
+_PLEV_CLIMATE = _Sampler("plev_climate", ("s",), ("sums",),
+                         lambda c: ((_lib.PLEV_WORDS, c.plev_climate_levels.size, c.H),), ("plev", "plev_climate_levels"),
+                         ("grid_x", "nseg", "targets", "threads", "lds_bytes", "chunks"),
+                         lambda c, n, s: PlevClimate.from_sums(n, c.plev_climate_levels, s, c.W))
+_SPECTRA = _Sampler("spectra", ("s",), ("s",),
+                    lambda c: ((_lib.SPEC_WORDS, c.L, c.H, c.spectra_mmax + 1),), ("mmax", "spectra_mmax"),
+                    ("grid_x", "nseg", "threads", "lds_bytes", "passes", "per_thread"),
+                    lambda c, n, s: Spectra.from_sums(n, s, c.W))
+_PLEV_MAPS = _Sampler("plev_maps", ("s", "s2"), ("sums", "sums2"),
+                      lambda c: ((_lib.PLEV_MAP_WORDS, c.plev_maps_levels.size, c.H, c.W), (_lib.PLEV_MAP_WORDS2, c.H, c.W)),
+                      ("plev", "plev_maps_levels"), ("chunks", "rows", "threads", "lds_bytes", "targets"),
+                      lambda c, n, s, s2: PlevMaps.from_sums(n, c.plev_maps_levels, s, s2))
+SAMPLERS = (_CLIMATE, _PLEV_CLIMATE, _SPECTRA, _PLEV_MAPS)
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -1557,6 +1590,48 @@ class Core:
         """zero the sums, the seconds and the count (gcm_moist_reset)"""
         self._column_reset(_MOIST)
 
+    # -- the sampled diagnostics (GCM_PE25D): one implementation for the four, by their _Sampler ----------------------
+    def _sampler_every(self, sm):
+        return _count(sm.every(self._h), self._h)
+
+    def _sampler_sample(self, sm):
+        _check(sm.sample(self._h), self._h)
+
+    def _sampler_reset(self, sm):
+        _check(sm.reset(self._h), self._h)
+
+    def _sampler_sums(self, sm):
+        sums = [np.empty(shape) for shape in sm.shapes(self)]
+        n = C.c_int64(0)
+        _check(sm.get(self._h, *[_tab(a) for a in sums], C.byref(n)), self._h)
+        return (int(n.value), *sums)
+
+    def _sampler_put(self, sm, n, *sums):
+        sums = [as_f64(a, shape, name) for a, shape, name in zip(sums, sm.shapes(self), sm.args)]
+        _check(sm.put(self._h, *[_tab(a) for a in sums], int(n)), self._h)
+
+    def _sampler_record(self, sm):
+        return sm.record(self, *self._sampler_sums(sm))
+
+    def _sampler_plan(self, sm):
+        out = (C.c_int * len(sm.plan))()
+        _check(sm.plan_of(self._h, out, len(sm.plan)), self._h)
+        return dict(zip(sm.plan, (int(x) for x in out)))
+
+    def _set_plev(self, sm, every, plev):
+        if int(every) == 0:
+            _check(sm.set(self._h, 0, 0, None), self._h)
+            return
+        if int(every) < 0:
+            raise ValueError("every must be >= 0")
+        P = plev_array(plev)
+        _check(sm.set(self._h, int(every), P.size, _tab(P)), self._h)
+
+    def _levels(self, sm):
+        P = np.empty(_lib.PLEV_MAX)
+        n = _count(getattr(lib, "gcm_%s_levels" % sm.name)(self._h, _tab(P), _lib.PLEV_MAX), self._h)
+        return P[:n].copy()
+
     # -- zonal-mean climatology (GCM_PE25D) ------------------------------------------------
     def set_climate(self, every=1):
         """accumulate the zonal-mean climatology on the device (gcm_set_climate): from now on every `every`-th step of
@@ -1568,37 +1643,30 @@ class Core:
     @property
     def climate_every(self):
         """the registered sampling interval in steps, 0 where none is registered (gcm_climate_every)"""
-        return _count(lib.gcm_climate_every(self._h), self._h)
+        return self._sampler_every(_CLIMATE)
 
     def climate_sample(self):
         """one sample of the current state now (gcm_climate_sample); the step counter is untouched.  A band: the ghost
         rows of the current state must be current, as for solar_step"""
-        _check(lib.gcm_climate_sample(self._h), self._h)
+        self._sampler_sample(_CLIMATE)
 
     def climate_reset(self):
         """zero the sums and the sample count (gcm_climate_reset)"""
-        _check(lib.gcm_climate_reset(self._h), self._h)
+        self._sampler_reset(_CLIMATE)
 
     def climate_sums(self):
         """-> (n, m3 (10, L, H), m2 (2, H)): the raw float64 sums as the device holds them (gcm_get_climate); one
         synchronisation, a few hundred KB"""
-        m3 = np.empty((_lib.CLIM_WORDS3, self.L, self.H))
-        m2 = np.empty((_lib.CLIM_WORDS2, self.H))
-        n = C.c_int64()
-        _check(lib.gcm_get_climate(self._h, _tab(m3), _tab(m2), C.byref(n)), self._h)
-        return int(n.value), m3, m2
+        return self._sampler_sums(_CLIMATE)
 
     def put_climate(self, n, m3, m2):
         """upload sums taken by climate_sums() (gcm_put_climate): a restart goes on where the run stopped"""
-        m3 = as_f64(m3, (_lib.CLIM_WORDS3, self.L, self.H), "m3")
-        m2 = as_f64(m2, (_lib.CLIM_WORDS2, self.H), "m2")
-        _check(lib.gcm_put_climate(self._h, _tab(m3), _tab(m2), int(n)), self._h)
+        self._sampler_put(_CLIMATE, n, m3, m2)
 
     def climate(self):
         """-> Climate: the sample count and the means, the sums divided by W n (gcm_get_climate).  GcmError where no
         climatology is registered"""
-        n, m3, m2 = self.climate_sums()
-        return Climate.from_sums(n, m3, m2, self.W)
+        return self._sampler_record(_CLIMATE)
 
     # -- pressure levels (GCM_PE25D) -------------------------------------------------------
     def plev_fields(self, plev, fill=np.nan):
@@ -1620,61 +1688,46 @@ class Core:
         the pressures plev (Pa, strictly decreasing) and adds the zonal sums of the words of `PlevClimate` over the
         valid columns to float64 sums in the handle, directly behind the sigma climatology's sample.  The step counter
         is the registration's own.  Registering again resets; every=0 unregisters"""
-        if int(every) == 0:
-            _check(lib.gcm_set_plev_climate(self._h, 0, 0, None), self._h)
-            return
-        if int(every) < 0:
-            raise ValueError("every must be >= 0")
-        P = plev_array(plev)
-        _check(lib.gcm_set_plev_climate(self._h, int(every), P.size, _tab(P)), self._h)
+        self._set_plev(_PLEV_CLIMATE, every, plev)
 
     @property
     def plev_climate_every(self):
         """the registered sampling interval in steps, 0 where none is registered (gcm_plev_climate_every)"""
-        return _count(lib.gcm_plev_climate_every(self._h), self._h)
+        return self._sampler_every(_PLEV_CLIMATE)
 
     @property
     def plev_climate_levels(self):
         """the registered targets (N,) in Pa (gcm_plev_climate_levels); GcmError where none are registered"""
-        P = np.empty(_lib.PLEV_MAX)
-        n = _count(lib.gcm_plev_climate_levels(self._h, _tab(P), _lib.PLEV_MAX), self._h)
-        return P[:n].copy()
+        return self._levels(_PLEV_CLIMATE)
 
     def plev_climate_plan(self):
         """the launch geometry of a sample of this handle, without launching (gcm_plev_climate_plan): grid_x (rows),
         nseg (target segments; 0 without a registration), targets (per segment), threads, lds_bytes, chunks (256-column
         chunks of a row)"""
-        out = (C.c_int * _lib.PLEV_PLAN_WORDS)()
-        _check(lib.gcm_plev_climate_plan(self._h, out, _lib.PLEV_PLAN_WORDS), self._h)
-        return dict(grid_x=out[0], nseg=out[1], targets=out[2], threads=out[3], lds_bytes=out[4], chunks=out[5])
+        return self._sampler_plan(_PLEV_CLIMATE)
 
     def plev_climate_sample(self):
         """one sample of the current state now (gcm_plev_climate_sample); the step counter is untouched.  A band: the
         ghost rows of the current state must be current, as for climate_sample"""
-        _check(lib.gcm_plev_climate_sample(self._h), self._h)
+        self._sampler_sample(_PLEV_CLIMATE)
 
     def plev_climate_reset(self):
         """zero the sums and the sample count (gcm_plev_climate_reset)"""
-        _check(lib.gcm_plev_climate_reset(self._h), self._h)
+        self._sampler_reset(_PLEV_CLIMATE)
 
     def plev_climate_sums(self):
         """-> (n, s (13, N, H)): the raw float64 sums as the device holds them (gcm_get_plev_climate), word 0 the count
         of valid columns; one synchronisation"""
-        s = np.empty((_lib.PLEV_WORDS, self.plev_climate_levels.size, self.H))
-        n = C.c_int64(0)
-        _check(lib.gcm_get_plev_climate(self._h, _tab(s), C.byref(n)), self._h)
-        return int(n.value), s
+        return self._sampler_sums(_PLEV_CLIMATE)
 
     def put_plev_climate(self, n, s):
         """upload sums taken by plev_climate_sums() (gcm_put_plev_climate): a restart goes on where the run stopped"""
-        s = as_f64(s, (_lib.PLEV_WORDS, self.plev_climate_levels.size, self.H), "s")
-        _check(lib.gcm_put_plev_climate(self._h, _tab(s), int(n)), self._h)
+        self._sampler_put(_PLEV_CLIMATE, n, s)
 
     def plev_climate(self):
         """-> PlevClimate: the sample count, the targets, the coverage and the conditional means, the sums divided by
         the count (gcm_get_plev_climate).  GcmError where none is registered"""
-        n, s = self.plev_climate_sums()
-        return PlevClimate.from_sums(n, self.plev_climate_levels, s, self.W)
+        return self._sampler_record(_PLEV_CLIMATE)
 
     # -- geopotential height on pressure levels, time-mean maps (GCM_PE25D) ----------------
     def plev_height(self, plev, fill=np.nan):
@@ -1696,63 +1749,46 @@ class Core:
         (target, cell) in the handle; longitude is kept.  The sums take 8 (13 N + 2) H W bytes of device memory: meant
         for a handful of levels (500 hPa, 850 hPa ...), not for all of them.  The step counter is the registration's own.
         Registering again resets; every=0 unregisters and frees"""
-        if int(every) == 0:
-            _check(lib.gcm_set_plev_maps(self._h, 0, 0, None), self._h)
-            return
-        if int(every) < 0:
-            raise ValueError("every must be >= 0")
-        P = plev_array(plev)
-        _check(lib.gcm_set_plev_maps(self._h, int(every), P.size, _tab(P)), self._h)
+        self._set_plev(_PLEV_MAPS, every, plev)
 
     @property
     def plev_maps_every(self):
         """the registered sampling interval in steps, 0 where none is registered (gcm_plev_maps_every)"""
-        return _count(lib.gcm_plev_maps_every(self._h), self._h)
+        return self._sampler_every(_PLEV_MAPS)
 
     @property
     def plev_maps_levels(self):
         """the registered targets (N,) in Pa (gcm_plev_maps_levels); GcmError where none are registered"""
-        P = np.empty(_lib.PLEV_MAX)
-        n = _count(lib.gcm_plev_maps_levels(self._h, _tab(P), _lib.PLEV_MAX), self._h)
-        return P[:n].copy()
+        return self._levels(_PLEV_MAPS)
 
     def plev_maps_plan(self):
         """the launch geometry of a sample of this handle, without launching (gcm_plev_maps_plan): chunks (256-column
         chunks of a row, grid x), rows (grid y; 0 without a registration: no work), threads, lds_bytes, targets (0
         without a registration)"""
-        out = (C.c_int * _lib.PLEV_MAP_PLAN_WORDS)()
-        _check(lib.gcm_plev_maps_plan(self._h, out, _lib.PLEV_MAP_PLAN_WORDS), self._h)
-        return dict(chunks=out[0], rows=out[1], threads=out[2], lds_bytes=out[3], targets=out[4])
+        return self._sampler_plan(_PLEV_MAPS)
 
     def plev_maps_sample(self):
         """one sample of the current state now (gcm_plev_maps_sample); the step counter is untouched.  A band: the
         ghost rows of the current state must be current, as for climate_sample"""
-        _check(lib.gcm_plev_maps_sample(self._h), self._h)
+        self._sampler_sample(_PLEV_MAPS)
 
     def plev_maps_reset(self):
         """zero the sums and the sample count (gcm_plev_maps_reset)"""
-        _check(lib.gcm_plev_maps_reset(self._h), self._h)
+        self._sampler_reset(_PLEV_MAPS)
 
     def plev_maps_sums(self):
         """-> (n, s (13, N, H, W), s2 (2, H, W)): the raw float64 sums as the device holds them (gcm_get_plev_maps), word
         0 of s the count of valid samples; one synchronisation"""
-        s = np.empty((_lib.PLEV_MAP_WORDS, self.plev_maps_levels.size, self.H, self.W))
-        s2 = np.empty((_lib.PLEV_MAP_WORDS2, self.H, self.W))
-        n = C.c_int64(0)
-        _check(lib.gcm_get_plev_maps(self._h, _tab(s), _tab(s2), C.byref(n)), self._h)
-        return int(n.value), s, s2
+        return self._sampler_sums(_PLEV_MAPS)
 
     def put_plev_maps(self, n, s, s2):
         """upload sums taken by plev_maps_sums() (gcm_put_plev_maps): a restart goes on where the run stopped"""
-        s = as_f64(s, (_lib.PLEV_MAP_WORDS, self.plev_maps_levels.size, self.H, self.W), "s")
-        s2 = as_f64(s2, (_lib.PLEV_MAP_WORDS2, self.H, self.W), "s2")
-        _check(lib.gcm_put_plev_maps(self._h, _tab(s), _tab(s2), int(n)), self._h)
+        self._sampler_put(_PLEV_MAPS, n, s, s2)
 
     def plev_maps(self):
         """-> PlevMaps: the sample count, the targets, the coverage, the conditional means and the means of p and p p
         (gcm_get_plev_maps).  GcmError where none are registered"""
-        n, s, s2 = self.plev_maps_sums()
-        return PlevMaps.from_sums(n, self.plev_maps_levels, s, s2)
+        return self._sampler_record(_PLEV_MAPS)
 
     # -- zonal wavenumber spectra (GCM_PE25D) ----------------------------------------------
     def set_spectra(self, every=1, mmax=None):
@@ -1767,7 +1803,7 @@ class Core:
     @property
     def spectra_every(self):
         """the registered sampling interval in steps, 0 where none is registered (gcm_spectra_every)"""
-        return _count(lib.gcm_spectra_every(self._h), self._h)
+        return self._sampler_every(_SPECTRA)
 
     @property
     def spectra_mmax(self):
@@ -1777,37 +1813,30 @@ class Core:
     def spectra_plan(self):
         """the launch geometry of a sample of this handle, without launching (gcm_spectra_plan): grid_x (rows), nseg
         (level segments), threads, lds_bytes, passes of a transform, per_thread (wavenumbers a thread holds)"""
-        out = (C.c_int * _lib.SPEC_PLAN_WORDS)()
-        _check(lib.gcm_spectra_plan(self._h, out, _lib.SPEC_PLAN_WORDS), self._h)
-        return dict(zip(("grid_x", "nseg", "threads", "lds_bytes", "passes", "per_thread"), (int(x) for x in out)))
+        return self._sampler_plan(_SPECTRA)
 
     def spectra_sample(self):
         """one sample of the current state now (gcm_spectra_sample); the step counter is untouched.  A band: the ghost
         rows of the current state must be current, as for climate_sample"""
-        _check(lib.gcm_spectra_sample(self._h), self._h)
+        self._sampler_sample(_SPECTRA)
 
     def spectra_reset(self):
         """zero the sums and the sample count (gcm_spectra_reset)"""
-        _check(lib.gcm_spectra_reset(self._h), self._h)
+        self._sampler_reset(_SPECTRA)
 
     def spectra_sums(self):
         """-> (n, s (6, L, H, M)): the raw float64 sums as the device holds them (gcm_get_spectra), M = spectra_mmax + 1;
         one synchronisation"""
-        s = np.empty((_lib.SPEC_WORDS, self.L, self.H, self.spectra_mmax + 1))
-        n = C.c_int64()
-        _check(lib.gcm_get_spectra(self._h, _tab(s), C.byref(n)), self._h)
-        return int(n.value), s
+        return self._sampler_sums(_SPECTRA)
 
     def put_spectra(self, n, s):
         """upload sums taken by spectra_sums() (gcm_put_spectra): a restart goes on where the run stopped"""
-        s = as_f64(s, (_lib.SPEC_WORDS, self.L, self.H, self.spectra_mmax + 1), "s")
-        _check(lib.gcm_put_spectra(self._h, _tab(s), int(n)), self._h)
+        self._sampler_put(_SPECTRA, n, s)
 
     def spectra(self):
         """-> Spectra: the sample count and the one-sided spectra, the sums times w_m / (W^2 n) (gcm_get_spectra).
         GcmError where no spectra are registered"""
-        n, s = self.spectra_sums()
-        return Spectra.from_sums(n, s, self.W)
+        return self._sampler_record(_SPECTRA)
 
     def utc(self):
         out = C.c_double()

@@ -19,7 +19,7 @@ using namespace gcm;
 // the climatology's sample, the pressure-level climatology's sample, the spectra's sample, the pressure-level maps' sample.  Each launch runs only if its phase is
 // registered: the diffusion in pe25d_hdiff_on, the solar step and the forcing in GcmPhases, the boundary layer, the adjustment and the moist physics where
 // their sums are in place (pe25d_sums_on),
-// the climatology in pe25d_climate_due, the pressure-level climatology in pe25d_plev_climate_due, the spectra in pe25d_spectra_due, the pressure-level maps in pe25d_plev_maps_due.  The order is written down in pe_phase_rows, and in pe_phase_tables for what a
+// the four samples in pe25d_sampler_due.  The order is written down in pe_phase_rows and kPeSamples, and in pe_phase_tables for what a
 // run prepares ahead of it.
 
 // The registered diffusion's device tables and landing fields for dt; gcm_set_physics: the radiation kernel's tables in
@@ -124,12 +124,20 @@ int pe_ghost_row_phases(gcm_handle *h, double dt, hipStream_t ax, int which) {
     return pe_phase_rows(h, dt, pe25d_new_state_set(h->pe), -kGhost, 0, h->H, h->H + kGhost, true, false, ax, which);
 }
 
+// The samples at the end of a step, in the order they are launched: the climatology's, directly behind it the
+// pressure-level climatology's, the spectra's, and the pressure-level maps', the last of the step
+struct PeSampleFn { PeSample of; int (*sample)(Pe25d *, hipStream_t, std::string *); };
+static constexpr PeSampleFn kPeSamples[] = {{kSampleClimate, pe25d_climate_sample}, {kSamplePlevClimate, pe25d_plev_climate_sample},
+                                            {kSampleSpectra, pe25d_spectra_sample}, {kSamplePlevMaps, pe25d_plev_maps_sample}};
+static_assert(kPeSamples[kSamplePlevClimate].of == kSamplePlevClimate && kPeSamples[kSampleSpectra].of == kSampleSpectra &&
+              kPeSamples[kSamplePlevMaps].of == kSamplePlevMaps, "row i is PeSample i: the entry points index the table by it");
+
 // The end of every step, on the handle's stream: rows [-g, H + g) (phase_ghosts) -- a band's own rows, and the ghost rows
 // with them where the exchange was joined into the compute stream.  The compute stream has waited for the edge rows and
 // their pack by then (update_interior), so the rows that left are as the corrector made them and the neighbour forces
 // them itself.  Callers: gcm_step (g = 0), gcm_band_run, and gcm_end_step, gcm_end_step_begin and gcm_end_step_finish
 // for a caller that takes the dynamics step itself.  which: the whole walk, or one of the parts a band with the boundary
-// layer registered exchanges between (pe_phase_rows); the samples (climatology, spectra) belong to the tail.  tail: the stream whose tail the
+// layer registered exchanges between (pe_phase_rows); the samples (kPeSamples) belong to the tail.  tail: the stream whose tail the
 // handle's stream joins before a sample, and before a band's boundary layer (gcm_band_run's second stream, where the
 // exchange runs and the ghost rows are forced there), else null
 int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStream_t tail, int which) {
@@ -137,9 +145,13 @@ int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStre
     if (!(which & kPhasesTail)) return GCM_OK;
     // gcm_set_climate, gcm_set_plev_climate, gcm_set_spectra, gcm_set_plev_maps: a sample of the state the step leaves,
     // behind every phase that changes it.  Each diagnostic counts the step on a counter of its own
-    const bool clim = pe25d_climate_due(h->pe), plev = pe25d_plev_climate_due(h->pe), spec = pe25d_spectra_due(h->pe);
-    const bool maps = pe25d_plev_maps_due(h->pe);
-    if (!clim && !plev && !spec && !maps) return GCM_OK;
+    constexpr int N = (int)(sizeof(kPeSamples) / sizeof(kPeSamples[0]));
+    bool due[N], any = false;
+    for (int i = 0; i < N; ++i) {                          // (every counter counts the step, whatever the others say)
+        due[i] = pe25d_sampler_due(h->pe, kPeSamples[i].of);
+        any = any || due[i];
+    }
+    if (!any) return GCM_OK;
     // a band: either sample reads the own rows as the phases above left them on the compute stream, and row -1 of v,
     // the first north ghost row, as the step's last exchange delivered it (the post-corrector exchange and the ghost
     // rows' Held-Suarez launch; with the boundary layer registered the third exchange) -- on the second stream where the
@@ -151,15 +163,9 @@ int pe_own_row_phases(gcm_handle *h, double dt, int g, bool keep_ghosts, hipStre
         HIPCHK(h, hipEventRecord(h->band.ev_comm, tail));
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->band.ev_comm, 0));
     }
-    if (clim)
-        if (int rc = pe25d_climate_sample(h->pe, h->stream, &h->err)) return rc;
-    // gcm_set_plev_climate: directly behind the climatology's sample, ahead of the spectra's
-    if (plev)
-        if (int rc = pe25d_plev_climate_sample(h->pe, h->stream, &h->err)) return rc;
-    if (spec)
-        if (int rc = pe25d_spectra_sample(h->pe, h->stream, &h->err)) return rc;
-    // gcm_set_plev_maps: behind the spectra's sample, the last of the step
-    if (maps) return pe25d_plev_maps_sample(h->pe, h->stream, &h->err);
+    for (int i = 0; i < N; ++i)
+        if (due[i])
+            if (int rc = kPeSamples[i].sample(h->pe, h->stream, &h->err)) return rc;
     return GCM_OK;
 }
 
@@ -685,24 +691,53 @@ int gcm_moist_saturation(int n, const double *T, const double *p_lev, double *q_
     return moist_saturation_table(n, T, p_lev, q_s, dq_s, can, &gcm_create_error());
 }
 
+// ------------------------------------------------------------------ the four sampled diagnostics
+// What the entry points of the climatology, the pressure-level climatology, the spectra and the pressure-level maps
+// share: the guard and one call into the samplers' routines (pe25d_sampler_*); fn: the entry point's name
+static int sampler_set_guard(gcm_handle *h, const char *fn, int every) {
+    if (int rc = pe_only(h, fn)) return rc;
+    if (every < 0) return fail(h, GCM_ERR_ARG, std::string(fn) + ": every must be >= 0");
+    return select_device(h);
+}
+static int sampler_every(const gcm_handle *h, PeSample of) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe ? pe25d_sampler_every(h->pe, of) : 0;
+}
+// a query that needs the registration (gcm_*_levels, gcm_spectra_mmax)
+static int sampler_registered(const gcm_handle *h, PeSample of, const char *fn) {
+    if (int rc = pe_only(h, fn)) return rc;
+    return pe25d_sampler_registered(h->pe, of, fn, &const_cast<gcm_handle *>(h)->err);
+}
+static int sampler_sample(gcm_handle *h, PeSample of, const char *fn) {
+    if (int rc = pe_on_device(h, fn)) return rc;
+    return kPeSamples[of].sample(h->pe, h->stream, &h->err);
+}
+static int sampler_reset(gcm_handle *h, PeSample of, const char *fn) {
+    if (int rc = pe_on_device(h, fn)) return rc;
+    return pe25d_sampler_reset(h->pe, of, h->stream, &h->err);
+}
+static int sampler_get(gcm_handle *h, PeSample of, const char *fn, double *a, double *b, int64_t *nsamples) {
+    if (int rc = pe_on_device(h, fn)) return rc;
+    return pe25d_sampler_get(h->pe, of, a, b, nsamples, h->stream, &h->err);
+}
+static int sampler_put(gcm_handle *h, PeSample of, const char *fn, const double *a, const double *b, int64_t nsamples) {
+    if (int rc = pe_on_device(h, fn)) return rc;
+    return pe25d_sampler_put(h->pe, of, a, b, nsamples, h->stream, &h->err);
+}
+static int plev_levels(const gcm_handle *h, PeSample of, const char *fn, double *P, int cap) {
+    if (int rc = sampler_registered(h, of, fn)) return rc;
+    return pe25d_plev_levels(h->pe, of, P, cap);
+}
+
 // ------------------------------------------------------------------ zonal wavenumber spectra
 int gcm_set_spectra(gcm_handle *h, int every, int mmax) {
-    if (int rc = pe_only(h, "gcm_set_spectra")) return rc;
-    if (every < 0) return fail(h, GCM_ERR_ARG, "gcm_set_spectra: every must be >= 0");
-    if (int rc = select_device(h)) return rc;
+    if (int rc = sampler_set_guard(h, "gcm_set_spectra", every)) return rc;
     return pe25d_set_spectra(h->pe, every, mmax, h->stream, &h->err);
 }
 
-int gcm_spectra_every(const gcm_handle *h) {
-    if (!h) return GCM_ERR_ARG;
-    return h->pe ? pe25d_spectra_every(h->pe) : 0;
-}
-
 int gcm_spectra_mmax(const gcm_handle *h) {
-    if (int rc = pe_only(h, "gcm_spectra_mmax")) return rc;
-    const int mmax = pe25d_spectra_mmax(h->pe);
-    if (mmax < 0) return fail(const_cast<gcm_handle *>(h), GCM_ERR_STATE, "gcm_spectra_mmax: no spectra registered (gcm_set_spectra)");
-    return mmax;
+    if (int rc = sampler_registered(h, kSampleSpectra, "gcm_spectra_mmax")) return rc;
+    return pe25d_spectra_mmax(h->pe);
 }
 
 int gcm_spectra_plan(gcm_handle *h, int *out, int nout) {
@@ -712,25 +747,11 @@ int gcm_spectra_plan(gcm_handle *h, int *out, int nout) {
     return GCM_OK;
 }
 
-int gcm_spectra_sample(gcm_handle *h) {
-    if (int rc = pe_on_device(h, "gcm_spectra_sample")) return rc;
-    return pe25d_spectra_sample(h->pe, h->stream, &h->err);
-}
-
-int gcm_spectra_reset(gcm_handle *h) {
-    if (int rc = pe_on_device(h, "gcm_spectra_reset")) return rc;
-    return pe25d_spectra_reset(h->pe, h->stream, &h->err);
-}
-
-int gcm_get_spectra(gcm_handle *h, double *s, int64_t *nsamples) {
-    if (int rc = pe_on_device(h, "gcm_get_spectra")) return rc;
-    return pe25d_get_spectra(h->pe, s, nsamples, h->stream, &h->err);
-}
-
-int gcm_put_spectra(gcm_handle *h, const double *s, int64_t nsamples) {
-    if (int rc = pe_on_device(h, "gcm_put_spectra")) return rc;
-    return pe25d_put_spectra(h->pe, s, nsamples, h->stream, &h->err);
-}
+int gcm_spectra_every(const gcm_handle *h) { return sampler_every(h, kSampleSpectra); }
+int gcm_spectra_sample(gcm_handle *h) { return sampler_sample(h, kSampleSpectra, "gcm_spectra_sample"); }
+int gcm_spectra_reset(gcm_handle *h) { return sampler_reset(h, kSampleSpectra, "gcm_spectra_reset"); }
+int gcm_get_spectra(gcm_handle *h, double *s, int64_t *nsamples) { return sampler_get(h, kSampleSpectra, "gcm_get_spectra", s, nullptr, nsamples); }
+int gcm_put_spectra(gcm_handle *h, const double *s, int64_t nsamples) { return sampler_put(h, kSampleSpectra, "gcm_put_spectra", s, nullptr, nsamples); }
 
 // ------------------------------------------------------------------ pressure levels
 int gcm_plev_columns(int ncol, int L, int N, const double *pl, const double *x, const double *P, double *out, int *valid) {
@@ -743,23 +764,8 @@ int gcm_plev_fields(gcm_handle *h, int N, const double *P, double fill, double *
 }
 
 int gcm_set_plev_climate(gcm_handle *h, int every, int N, const double *P) {
-    if (int rc = pe_only(h, "gcm_set_plev_climate")) return rc;
-    if (every < 0) return fail(h, GCM_ERR_ARG, "gcm_set_plev_climate: every must be >= 0");
-    if (int rc = select_device(h)) return rc;
+    if (int rc = sampler_set_guard(h, "gcm_set_plev_climate", every)) return rc;
     return pe25d_set_plev_climate(h->pe, every, N, P, h->stream, &h->err);
-}
-
-int gcm_plev_climate_every(const gcm_handle *h) {
-    if (!h) return GCM_ERR_ARG;
-    return h->pe ? pe25d_plev_climate_every(h->pe) : 0;
-}
-
-int gcm_plev_climate_levels(const gcm_handle *h, double *P, int cap) {
-    if (int rc = pe_only(h, "gcm_plev_climate_levels")) return rc;
-    const int N = pe25d_plev_climate_levels(h->pe, P, cap);
-    if (N < 0)
-        return fail(const_cast<gcm_handle *>(h), GCM_ERR_STATE, "gcm_plev_climate_levels: no pressure-level climatology registered (gcm_set_plev_climate)");
-    return N;
 }
 
 int gcm_plev_climate_plan(gcm_handle *h, int *out, int nout) {
@@ -769,25 +775,12 @@ int gcm_plev_climate_plan(gcm_handle *h, int *out, int nout) {
     return GCM_OK;
 }
 
-int gcm_plev_climate_sample(gcm_handle *h) {
-    if (int rc = pe_on_device(h, "gcm_plev_climate_sample")) return rc;
-    return pe25d_plev_climate_sample(h->pe, h->stream, &h->err);
-}
-
-int gcm_plev_climate_reset(gcm_handle *h) {
-    if (int rc = pe_on_device(h, "gcm_plev_climate_reset")) return rc;
-    return pe25d_plev_climate_reset(h->pe, h->stream, &h->err);
-}
-
-int gcm_get_plev_climate(gcm_handle *h, double *s, int64_t *nsamples) {
-    if (int rc = pe_on_device(h, "gcm_get_plev_climate")) return rc;
-    return pe25d_get_plev_climate(h->pe, s, nsamples, h->stream, &h->err);
-}
-
-int gcm_put_plev_climate(gcm_handle *h, const double *s, int64_t nsamples) {
-    if (int rc = pe_on_device(h, "gcm_put_plev_climate")) return rc;
-    return pe25d_put_plev_climate(h->pe, s, nsamples, h->stream, &h->err);
-}
+int gcm_plev_climate_every(const gcm_handle *h) { return sampler_every(h, kSamplePlevClimate); }
+int gcm_plev_climate_levels(const gcm_handle *h, double *P, int cap) { return plev_levels(h, kSamplePlevClimate, "gcm_plev_climate_levels", P, cap); }
+int gcm_plev_climate_sample(gcm_handle *h) { return sampler_sample(h, kSamplePlevClimate, "gcm_plev_climate_sample"); }
+int gcm_plev_climate_reset(gcm_handle *h) { return sampler_reset(h, kSamplePlevClimate, "gcm_plev_climate_reset"); }
+int gcm_get_plev_climate(gcm_handle *h, double *s, int64_t *nsamples) { return sampler_get(h, kSamplePlevClimate, "gcm_get_plev_climate", s, nullptr, nsamples); }
+int gcm_put_plev_climate(gcm_handle *h, const double *s, int64_t nsamples) { return sampler_put(h, kSamplePlevClimate, "gcm_put_plev_climate", s, nullptr, nsamples); }
 
 // ------------------------------------------------------------------ geopotential height on pressure levels, time-mean maps
 int gcm_plev_height_columns(int ncol, int L, int N, const double *p, const double *theta, const double *hmG, const double *sig,
@@ -801,23 +794,8 @@ int gcm_plev_height(gcm_handle *h, int N, const double *P, double fill, double *
 }
 
 int gcm_set_plev_maps(gcm_handle *h, int every, int N, const double *P) {
-    if (int rc = pe_only(h, "gcm_set_plev_maps")) return rc;
-    if (every < 0) return fail(h, GCM_ERR_ARG, "gcm_set_plev_maps: every must be >= 0");
-    if (int rc = select_device(h)) return rc;
+    if (int rc = sampler_set_guard(h, "gcm_set_plev_maps", every)) return rc;
     return pe25d_set_plev_maps(h->pe, every, N, P, h->stream, &h->err);
-}
-
-int gcm_plev_maps_every(const gcm_handle *h) {
-    if (!h) return GCM_ERR_ARG;
-    return h->pe ? pe25d_plev_maps_every(h->pe) : 0;
-}
-
-int gcm_plev_maps_levels(const gcm_handle *h, double *P, int cap) {
-    if (int rc = pe_only(h, "gcm_plev_maps_levels")) return rc;
-    const int N = pe25d_plev_maps_levels(h->pe, P, cap);
-    if (N < 0)
-        return fail(const_cast<gcm_handle *>(h), GCM_ERR_STATE, "gcm_plev_maps_levels: no pressure-level maps registered (gcm_set_plev_maps)");
-    return N;
 }
 
 int gcm_plev_maps_plan(gcm_handle *h, int *out, int nout) {
@@ -827,58 +805,24 @@ int gcm_plev_maps_plan(gcm_handle *h, int *out, int nout) {
     return GCM_OK;
 }
 
-int gcm_plev_maps_sample(gcm_handle *h) {
-    if (int rc = pe_on_device(h, "gcm_plev_maps_sample")) return rc;
-    return pe25d_plev_maps_sample(h->pe, h->stream, &h->err);
-}
-
-int gcm_plev_maps_reset(gcm_handle *h) {
-    if (int rc = pe_on_device(h, "gcm_plev_maps_reset")) return rc;
-    return pe25d_plev_maps_reset(h->pe, h->stream, &h->err);
-}
-
-int gcm_get_plev_maps(gcm_handle *h, double *s, double *s2, int64_t *nsamples) {
-    if (int rc = pe_on_device(h, "gcm_get_plev_maps")) return rc;
-    return pe25d_get_plev_maps(h->pe, s, s2, nsamples, h->stream, &h->err);
-}
-
-int gcm_put_plev_maps(gcm_handle *h, const double *s, const double *s2, int64_t nsamples) {
-    if (int rc = pe_on_device(h, "gcm_put_plev_maps")) return rc;
-    return pe25d_put_plev_maps(h->pe, s, s2, nsamples, h->stream, &h->err);
-}
+int gcm_plev_maps_every(const gcm_handle *h) { return sampler_every(h, kSamplePlevMaps); }
+int gcm_plev_maps_levels(const gcm_handle *h, double *P, int cap) { return plev_levels(h, kSamplePlevMaps, "gcm_plev_maps_levels", P, cap); }
+int gcm_plev_maps_sample(gcm_handle *h) { return sampler_sample(h, kSamplePlevMaps, "gcm_plev_maps_sample"); }
+int gcm_plev_maps_reset(gcm_handle *h) { return sampler_reset(h, kSamplePlevMaps, "gcm_plev_maps_reset"); }
+int gcm_get_plev_maps(gcm_handle *h, double *s, double *s2, int64_t *nsamples) { return sampler_get(h, kSamplePlevMaps, "gcm_get_plev_maps", s, s2, nsamples); }
+int gcm_put_plev_maps(gcm_handle *h, const double *s, const double *s2, int64_t nsamples) { return sampler_put(h, kSamplePlevMaps, "gcm_put_plev_maps", s, s2, nsamples); }
 
 // ------------------------------------------------------------------ zonal-mean climatology
 int gcm_set_climate(gcm_handle *h, int every) {
-    if (int rc = pe_only(h, "gcm_set_climate")) return rc;
-    if (every < 0) return fail(h, GCM_ERR_ARG, "gcm_set_climate: every must be >= 0");
-    if (int rc = select_device(h)) return rc;
+    if (int rc = sampler_set_guard(h, "gcm_set_climate", every)) return rc;
     return pe25d_set_climate(h->pe, every, h->stream, &h->err);
 }
 
-int gcm_climate_every(const gcm_handle *h) {
-    if (!h) return GCM_ERR_ARG;
-    return h->pe ? pe25d_climate_every(h->pe) : 0;
-}
-
-int gcm_climate_sample(gcm_handle *h) {
-    if (int rc = pe_on_device(h, "gcm_climate_sample")) return rc;
-    return pe25d_climate_sample(h->pe, h->stream, &h->err);
-}
-
-int gcm_climate_reset(gcm_handle *h) {
-    if (int rc = pe_on_device(h, "gcm_climate_reset")) return rc;
-    return pe25d_climate_reset(h->pe, h->stream, &h->err);
-}
-
-int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples) {
-    if (int rc = pe_on_device(h, "gcm_get_climate")) return rc;
-    return pe25d_get_climate(h->pe, m3, m2, nsamples, h->stream, &h->err);
-}
-
-int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples) {
-    if (int rc = pe_on_device(h, "gcm_put_climate")) return rc;
-    return pe25d_put_climate(h->pe, m3, m2, nsamples, h->stream, &h->err);
-}
+int gcm_climate_every(const gcm_handle *h) { return sampler_every(h, kSampleClimate); }
+int gcm_climate_sample(gcm_handle *h) { return sampler_sample(h, kSampleClimate, "gcm_climate_sample"); }
+int gcm_climate_reset(gcm_handle *h) { return sampler_reset(h, kSampleClimate, "gcm_climate_reset"); }
+int gcm_get_climate(gcm_handle *h, double *m3, double *m2, int64_t *nsamples) { return sampler_get(h, kSampleClimate, "gcm_get_climate", m3, m2, nsamples); }
+int gcm_put_climate(gcm_handle *h, const double *m3, const double *m2, int64_t nsamples) { return sampler_put(h, kSampleClimate, "gcm_put_climate", m3, m2, nsamples); }
 
 // ------------------------------------------------------------------ the filter of a field, the stage's intermediates
 int gcm_polar_filter(gcm_handle *h, int nlev, const double *in, double *out) {

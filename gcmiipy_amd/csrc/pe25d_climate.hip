@@ -144,117 +144,57 @@ void launch_climate(ClimateArgs a, bool f32, int cus, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- the handle's side
-// layout of PeClimate::buf (doubles): sig [L] | m3 [GCM_CLIM_WORDS3][L][H] | m2 [GCM_CLIM_WORDS2][H]
-static size_t clim_m3(const Pe25d *m) { return (size_t)GCM_CLIM_WORDS3 * m->L * m->H; }
-static size_t clim_m2(const Pe25d *m) { return (size_t)GCM_CLIM_WORDS2 * m->H; }
+// layout of the sampler's buf (doubles): sig [L] | m3 [GCM_CLIM_WORDS3][L][H] | m2 [GCM_CLIM_WORDS2][H].  every, due, reset,
+// get, put and free are the samplers' shared routines (pe25d_sampler_*, pe25d_state.hip)
 
-static int clim_hip(hipError_t e, const char *fn, std::string *err) {
-    if (e == hipSuccess) return GCM_OK;
-    *err = std::string("hip: ") + fn + ": " + hipGetErrorString(e);
-    return GCM_ERR_HIP;
-}
-static int clim_registered(const Pe25d *m, const char *fn, std::string *err) {
-    if (m->clim.every > 0) return GCM_OK;
-    *err = std::string(fn) + ": no climatology registered (gcm_set_climate)";
-    return GCM_ERR_STATE;
-}
-
+// A second registration zeroes the sums in place: the buffer's size is the handle's own
 int pe25d_set_climate(Pe25d *m, int every, hipStream_t s, std::string *err) {
-    PeClimate &z = m->clim;
+    PeSampler &z = m->clim;
     if (every < 0) { *err = "gcm_set_climate: every must be >= 0"; return GCM_ERR_ARG; }
     if (every == 0) {
         if (!z.buf) return GCM_OK;
         // (a sample may still be adding to the sums)
-        if (int rc = clim_hip(hipStreamSynchronize(s), "gcm_set_climate", err)) return rc;
-        m->allocs.erase(std::remove(m->allocs.begin(), m->allocs.end(), (void *)z.buf), m->allocs.end());
-        (void)hipFree(z.buf);
-        z = PeClimate{};
+        if (int rc = hip_rc(hipStreamSynchronize(s), "gcm_set_climate", err)) return rc;
+        pe25d_sampler_free(m, kSampleClimate);
         return GCM_OK;
     }
     if (climate_lds_bytes(m->W) > 64 * 1024) {
         *err = "gcm_set_climate: a row of " + std::to_string(m->W) + " columns does not fit the sample's LDS";
         return GCM_ERR_UNSUPPORTED;
     }
-    const size_t sums = clim_m3(m) + clim_m2(m);
+    const size_t m3 = (size_t)GCM_CLIM_WORDS3 * m->L * m->H, m2 = (size_t)GCM_CLIM_WORDS2 * m->H;
     if (!z.buf) {
-        std::vector<double> init((size_t)m->L + sums, 0.0);
+        std::vector<double> init((size_t)m->L + m3 + m2, 0.0);
         std::copy(m->sig_host.begin(), m->sig_host.end(), init.begin());
         if (!dev_upload<double>(m, &z.buf, init.data(), init.size())) { *err = "hip: gcm_set_climate allocation failed"; return GCM_ERR_HIP; }
-    } else if (int rc = clim_hip(hipMemsetAsync(z.buf + m->L, 0, sizeof(double) * sums, s), "gcm_set_climate", err)) {
+    } else if (int rc = hip_rc(hipMemsetAsync(z.buf + m->L, 0, sizeof(double) * (m3 + m2), s), "gcm_set_climate", err)) {
         return rc;
     }
+    z.head = (size_t)m->L;
+    z.words[0] = m3;
+    z.words[1] = m2;
     z.every = every;
     z.steps = 0;
     z.n = 0;
     return GCM_OK;
 }
 
-int pe25d_climate_every(const Pe25d *m) { return m->clim.every; }
-
-bool pe25d_climate_due(Pe25d *m) {
-    PeClimate &z = m->clim;
-    if (z.every <= 0) return false;
-    return ++z.steps % z.every == 0;
-}
-
-// The sample is a pure reader of the current state set on `s` and writes its own sums only: it leaves the column sums,
-// the fork at the last K4 and the ghost-row bookkeeping as they are (unlike pe25d_hs_rows, which writes u and v).
-// What must still hold is that whatever overwrites this state set later is ordered behind this launch.  The set is
-// written again by the corrector's K4 two steps on, by the physics phases behind it, and -- a band -- by the unpack
-// of the exchange that follows that K4 (its ghost rows, of which this launch reads v's row -1).  K4 of the rows the
-// caller's stream keeps (all rows; a band: the interior rows) follows this launch in stream order on `s`.  A band's
-// edge rows' K4 runs on the second stream, which every stage makes wait for its fork: the completion of the previous
-// stage's K4 on `s` (ev_k4) or a record on `s` at the head of the stage (ev_fork) -- an event behind this launch on `s`
-// in either case, from the very next stage on; the pack, the exchange and the unpack follow that K4 in stream order
-// (or on streams that wait for the pack).  The third stream writes no state set.  The launches of the next stage that
-// may run beside this one (chain B forked at ev_k4: K1, pit, column sums, anchors, the tracers) write intermediates
-// and tracers only, none of which is read here.
+// The launch reads p, u, v and theta of the current state set, and on a band v's first north ghost row; how it is
+// ordered against the stages that follow: pe25d_kernels.h, at the samplers' declarations
 int pe25d_climate_sample(Pe25d *m, hipStream_t s, std::string *err) {
-    if (int rc = clim_registered(m, "gcm_climate_sample", err)) return rc;
-    PeClimate &z = m->clim;
+    if (int rc = pe25d_sampler_registered(m, kSampleClimate, "gcm_climate_sample", err)) return rc;
+    PeSampler &z = m->clim;
     const int set = m->cur_i;
     ClimateArgs a{};
     a.p = state_field(m, set, GCM_P); a.u = state_field(m, set, GCM_U);
     a.v = state_field(m, set, GCM_V); a.t = state_field(m, set, GCM_T);
     a.sig = z.buf; a.exner_tab = m->exner_tab;
-    a.m3 = z.buf + m->L; a.m2 = a.m3 + clim_m3(m);
+    a.m3 = z.buf + z.head; a.m2 = a.m3 + z.words[0];
     a.ptop = m->cfg.ptop;
     a.W = m->W; a.H = m->H; a.L = m->L; a.wrap = m->wrap ? 1 : 0;
     launch_climate(a, m->f32, m->cus, s);
-    if (int rc = clim_hip(hipGetLastError(), "gcm_climate_sample", err)) return rc;
+    if (int rc = hip_rc(hipGetLastError(), "gcm_climate_sample", err)) return rc;
     ++z.n;
-    return GCM_OK;
-}
-
-int pe25d_climate_reset(Pe25d *m, hipStream_t s, std::string *err) {
-    if (int rc = clim_registered(m, "gcm_climate_reset", err)) return rc;
-    PeClimate &z = m->clim;
-    if (int rc = clim_hip(hipMemsetAsync(z.buf + m->L, 0, sizeof(double) * (clim_m3(m) + clim_m2(m)), s), "gcm_climate_reset", err)) return rc;
-    z.n = 0;
-    return GCM_OK;
-}
-
-int pe25d_get_climate(Pe25d *m, double *m3, double *m2, int64_t *nsamples, hipStream_t s, std::string *err) {
-    if (int rc = clim_registered(m, "gcm_get_climate", err)) return rc;
-    const PeClimate &z = m->clim;
-    hipError_t e = hipSuccess;
-    if (m3) e = hipMemcpyAsync(m3, z.buf + m->L, sizeof(double) * clim_m3(m), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && m2) e = hipMemcpyAsync(m2, z.buf + m->L + clim_m3(m), sizeof(double) * clim_m2(m), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (int rc = clim_hip(e, "gcm_get_climate", err)) return rc;
-    if (nsamples) *nsamples = z.n;
-    return GCM_OK;
-}
-
-int pe25d_put_climate(Pe25d *m, const double *m3, const double *m2, int64_t nsamples, hipStream_t s, std::string *err) {
-    if (int rc = clim_registered(m, "gcm_put_climate", err)) return rc;
-    if (!m3 || !m2 || nsamples < 0) { *err = "gcm_put_climate: m3 and m2 are required, nsamples must be >= 0"; return GCM_ERR_ARG; }
-    PeClimate &z = m->clim;
-    hipError_t e = hipMemcpyAsync(z.buf + m->L, m3, sizeof(double) * clim_m3(m), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(z.buf + m->L + clim_m3(m), m2, sizeof(double) * clim_m2(m), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);          // (the caller's arrays are free again when the call returns)
-    if (int rc = clim_hip(e, "gcm_put_climate", err)) return rc;
-    z.n = nsamples;
     return GCM_OK;
 }
 

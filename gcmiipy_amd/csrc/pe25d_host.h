@@ -1,7 +1,8 @@
 // Host side of GCM_PE25D, private to its five host units: the handle and the few helpers they share.
 //   pe25d_state.hip    the handle's life cycle and data movement: create / destroy (and the one reader of the GCM_PE_*
 //                      switches), the streams, set / get and the layout transposes, halo buffers and segments; what the
-//                      phases behind the dynamics share: their column sums, the level table, pe25d_phase_wrote
+//                      phases behind the dynamics share: their column sums, the level table, pe25d_phase_wrote; what the
+//                      four sampled diagnostics share: every / due / reset / get / put / free of a PeSampler
 //   pe25d_kernels.hip  the stage orchestration (half_t and its steps) and the column kernels K2 it launches
 //   pe25d_physics.hip  grey radiation and the ground temperature
 //   pe25d_diag.hip     diagnostics and taps: gcm_stats, the polar filter of a field, the stage's intermediates
@@ -19,8 +20,8 @@
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
 // gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
-// pe25d_hdiff_rows, pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_moist_rows, pe25d_climate_due, pe25d_climate_sample,
-// pe25d_plev_climate_due, pe25d_plev_climate_sample, pe25d_spectra_due, pe25d_spectra_sample, pe25d_plev_maps_due,
+// pe25d_hdiff_rows, pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_moist_rows, and behind
+// pe25d_sampler_due the four samples: pe25d_climate_sample, pe25d_plev_climate_sample, pe25d_spectra_sample,
 // pe25d_plev_maps_sample).
 #pragma once
 #include "pe25d_kernels.h"
@@ -110,41 +111,34 @@ struct PeHeldSuarez {
     double par[5] = {};                         // T_min, T_0, dT_y, dtheta_z, (free): what the kernel takes by value
 };
 
-// Zonal-mean climatology (pe25d_climate.hip, gcm_set_climate): the float64 sums on the device and the two counters
-struct PeClimate {
-    double *buf = nullptr;                      // device: sig [L], m3 [GCM_CLIM_WORDS3][L][H], m2 [GCM_CLIM_WORDS2][H]
+// A sampled diagnostic (gcm_set_climate, gcm_set_plev_climate, gcm_set_spectra, gcm_set_plev_maps): float64 sums on the
+// device behind `head` words of tables, one or two blocks of them, and the two counters.  One set of routines serves the
+// four (pe25d_sampler_*, pe25d_state.hip); kPeSamplerWords, in the order of PeSample, holds the words in which their
+// messages differ.  A unit's own part is its pe25d_set_* (which fills head and words), its *_sample and its *_plan
+struct PeSampler {
+    double *buf = nullptr;                      // device: head words, then the sums: words[0] of them, then words[1]
     int every = 0;                              // a sample every so many steps; 0: not registered
     long long steps = 0;                        // steps taken by gcm_step / gcm_band_run since the registration
     long long n = 0;                            // samples in the sums
+    size_t head = 0;                            // float64 words ahead of the sums
+    size_t words[2] = {0, 0};                   // the sizes of the sum blocks; words[1] = 0: one block
 };
-
-// Zonal-mean climatology on pressure levels (pe25d_plev.hip, gcm_set_plev_climate): the targets and the float64 sums on
-// the device, the targets' host copy (its size is N) and the two counters
-struct PePlevClimate {
-    double *buf = nullptr;                      // device: P [N], s [GCM_PLEV_WORDS][N][H]
-    std::vector<double> P;                      // the registered targets, Pa
-    int every = 0;                              // a sample every so many steps; 0: not registered
-    long long steps = 0;                        // steps taken by gcm_step / gcm_band_run since the registration
-    long long n = 0;                            // samples in the sums
+struct PeSamplerWords { const char *name, *what, *a, *b; };   // gcm_set_<name>, "no <what> registered", the sum arguments (b null: one)
+constexpr PeSamplerWords kPeSamplerWords[] = {{"climate", "climatology", "m3", "m2"},                      // kSampleClimate
+                                              {"plev_climate", "pressure-level climatology", "s", nullptr},  // kSamplePlevClimate
+                                              {"spectra", "spectra", "s", nullptr},                          // kSampleSpectra
+                                              {"plev_maps", "pressure-level maps", "s", "s2"}};              // kSamplePlevMaps
+// buf of the zonal-mean climatology (pe25d_climate.hip; a PeSampler and nothing else):
+//   sig [L], m3 [GCM_CLIM_WORDS3][L][H], m2 [GCM_CLIM_WORDS2][H]
+// The two on pressure levels: the registered targets' host copy (its size is N) beside the sampler.  buf of the zonal-mean
+// climatology (pe25d_plev.hip): P [N], s [GCM_PLEV_WORDS][N][H]; of the time-mean maps (pe25d_plev_height.hip): P [N],
+// s [GCM_PLEV_MAP_WORDS][N][H][W], s2 [GCM_PLEV_MAP_WORDS2][H][W]
+struct PePlev : PeSampler {
+    std::vector<double> P;                      // the registered targets, Pa; meaningful while every > 0
 };
-
-// Time-mean maps on pressure levels (pe25d_plev_height.hip, gcm_set_plev_maps): the targets and the float64 sums on the
-// device, the targets' host copy (its size is N) and the two counters
-struct PePlevMaps {
-    double *buf = nullptr;                      // device: P [N], s [GCM_PLEV_MAP_WORDS][N][H][W], s2 [GCM_PLEV_MAP_WORDS2][H][W]
-    std::vector<double> P;                      // the registered targets, Pa
-    int every = 0;                              // a sample every so many steps; 0: not registered
-    long long steps = 0;                        // steps taken by gcm_step / gcm_band_run since the registration
-    long long n = 0;                            // samples in the sums
-};
-
-// Zonal wavenumber spectra (pe25d_spectra.hip, gcm_set_spectra): the float64 twiddles and sums on the device and the counters
-struct PeSpectra {
-    double *buf = nullptr;                      // device: tw [W] double2, sig [L], s [GCM_SPEC_WORDS][L][H][mmax + 1]
-    int every = 0;                              // a sample every so many steps; 0: not registered
-    int mmax = 0;                               // the highest wavenumber in the sums
-    long long steps = 0;                        // steps taken by gcm_step / gcm_band_run since the registration
-    long long n = 0;                            // samples in the sums
+// Zonal wavenumber spectra (pe25d_spectra.hip): buf holds tw [W] double2, sig [L], s [GCM_SPEC_WORDS][L][H][mmax + 1]
+struct PeSpectra : PeSampler {
+    int mmax = 0;                               // the highest wavenumber in the sums; meaningful while every > 0
 };
 
 // The float64 column sums of a phase that runs behind the dynamics, with their two counters: two [H][W] fields of the
@@ -280,10 +274,10 @@ struct Pe25d {
     bool halo_fixed = false;
     PeTracers tr;
     PeHeldSuarez hs;
-    PeClimate clim;
-    PePlevClimate plev;
+    PeSampler clim;                             // the four sampled diagnostics, in the order a step samples (PeSample)
+    PePlev plev;
     PeSpectra spec;
-    PePlevMaps pmaps;
+    PePlev pmaps;
     PeMoist moist;
     PeConvect convect;
     PeBoundary boundary;

@@ -56,58 +56,65 @@ int held_suarez_tables(int L, const double *sig, int nlat, const double *lat, co
 int held_suarez_check(const gcm_held_suarez *hs, const char *fn, std::string *err);
 int pe25d_hs_tables(Pe25d *m, const gcm_held_suarez *hs, double dt, hipStream_t s, std::string *err);
 int pe25d_hs_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, hipStream_t s, std::string *err);
-// Zonal-mean climatology (pe25d_climate.hip): gcm_set_climate and its companions on `s`, the caller's stream.
-// pe25d_climate_due: counts one step of gcm_step / gcm_band_run; true where that step ends with a sample
+// The four sampled diagnostics, in the order a step samples.  What they share is one set of routines over a PeSampler
+// (pe25d_state.hip), on `s`, the caller's stream.  pe25d_sampler_registered: GCM_ERR_STATE and "<fn>: no <what> registered
+// (gcm_set_<name>)" without a registration, the one place that forms that message; every: the interval, 0 without one;
+// due: counts one step of gcm_step / gcm_band_run, true where that step ends with a sample; reset, get and put are
+// gcm_<name>_reset, gcm_get_<name> and gcm_put_<name> -- get takes null pointers, put needs every array the diagnostic
+// has (b: the second block of the climatology and the maps, else null) and nsamples >= 0, and synchronises `s` behind its
+// copies whether or not one failed: the caller's arrays are free when it returns; free: the buffer off the handle's list
+// and freed, the sampler cleared (a unit's pe25d_set_* calls it).  What stays with each unit: pe25d_set_* (the rules of
+// a second registration differ), *_sample (arguments and launch) and *_plan.
+//
+// A sample and the stages that follow it.  Every sample is a pure reader of the current state set on `s` and writes its
+// own sums only: it leaves the column sums, the fork at the last K4 and the ghost-row bookkeeping as they are (unlike
+// pe25d_hs_rows, which writes u and v).  What must still hold is that whatever overwrites this state set later is
+// ordered behind the launch.  The set is written again by the corrector's K4 two steps on, by the physics phases behind
+// it, and -- a band -- by the unpack of the exchange that follows that K4 (its ghost rows, of which a sample reads v's
+// row -1, the first north ghost row).  K4 of the rows the caller's stream keeps (all rows; a band: the interior rows)
+// follows the launch in stream order on `s`.  A band's edge rows' K4 runs on the second stream, which every stage makes
+// wait for its fork: the completion of the previous stage's K4 on `s` (ev_k4) or a record on `s` at the head of the
+// stage (ev_fork) -- an event behind the launch on `s` in either case, from the very next stage on; the pack, the
+// exchange and the unpack follow that K4 in stream order (or on streams that wait for the pack).  The third stream
+// writes no state set.  The launches of the next stage that may run beside a sample (chain B forked at ev_k4: K1, pit,
+// column sums, anchors, the tracers) write intermediates and tracers only, none of which a sample reads; q is a state
+// field, not a tracer.  The samples of one step follow each other on `s` and write their own sums only.
+enum PeSample { kSampleClimate, kSamplePlevClimate, kSampleSpectra, kSamplePlevMaps };
+int pe25d_sampler_registered(const Pe25d *m, PeSample of, const char *fn, std::string *err);
+int pe25d_sampler_every(const Pe25d *m, PeSample of);
+bool pe25d_sampler_due(Pe25d *m, PeSample of);
+int pe25d_sampler_reset(Pe25d *m, PeSample of, hipStream_t s, std::string *err);
+int pe25d_sampler_get(Pe25d *m, PeSample of, double *a, double *b, int64_t *nsamples, hipStream_t s, std::string *err);
+int pe25d_sampler_put(Pe25d *m, PeSample of, const double *a, const double *b, int64_t nsamples, hipStream_t s, std::string *err);
+void pe25d_sampler_free(Pe25d *m, PeSample of);
+// Zonal-mean climatology (pe25d_climate.hip): gcm_set_climate and gcm_climate_sample
 int pe25d_set_climate(Pe25d *m, int every, hipStream_t s, std::string *err);
-int pe25d_climate_every(const Pe25d *m);
-bool pe25d_climate_due(Pe25d *m);
 int pe25d_climate_sample(Pe25d *m, hipStream_t s, std::string *err);
-int pe25d_climate_reset(Pe25d *m, hipStream_t s, std::string *err);
-int pe25d_get_climate(Pe25d *m, double *m3, double *m2, int64_t *nsamples, hipStream_t s, std::string *err);
-int pe25d_put_climate(Pe25d *m, const double *m3, const double *m2, int64_t nsamples, hipStream_t s, std::string *err);
 // Pressure levels (pe25d_plev.hip).  plev_columns: no handle, no device (gcm_plev_columns).  pe25d_plev_fields:
-// gcm_plev_fields on `s`, synchronised before it returns.  gcm_set_plev_climate and its companions on `s`, the caller's
-// stream: pe25d_plev_climate_due counts one step, as pe25d_climate_due does; pe25d_plev_climate_levels: -1 without a
-// registration; pe25d_plev_climate_plan: gcm_plev_climate_plan
+// gcm_plev_fields on `s`, synchronised before it returns.  gcm_set_plev_climate, gcm_plev_climate_sample and
+// gcm_plev_climate_plan.  pe25d_plev_levels: the registered targets of the climatology or of the maps
+// (gcm_plev_climate_levels, gcm_plev_maps_levels), at most cap of them into P (may be null) -> their number
 int plev_columns(int ncol, int L, int N, const double *pl, const double *x, const double *P, double *out, int *valid, std::string *err);
 int pe25d_plev_fields(Pe25d *m, int N, const double *P, double fill, double *out, int32_t *valid, hipStream_t s, std::string *err);
 int pe25d_set_plev_climate(Pe25d *m, int every, int N, const double *P, hipStream_t s, std::string *err);
-int pe25d_plev_climate_every(const Pe25d *m);
-int pe25d_plev_climate_levels(const Pe25d *m, double *P, int cap);
-bool pe25d_plev_climate_due(Pe25d *m);
+int pe25d_plev_levels(const Pe25d *m, PeSample of, double *P, int cap);
 int pe25d_plev_climate_plan(const Pe25d *m, int *out, int nout);
 int pe25d_plev_climate_sample(Pe25d *m, hipStream_t s, std::string *err);
-int pe25d_plev_climate_reset(Pe25d *m, hipStream_t s, std::string *err);
-int pe25d_get_plev_climate(Pe25d *m, double *sums, int64_t *nsamples, hipStream_t s, std::string *err);
-int pe25d_put_plev_climate(Pe25d *m, const double *sums, int64_t nsamples, hipStream_t s, std::string *err);
 // Geopotential height on pressure levels and time-mean maps (pe25d_plev_height.hip).  plev_height_columns: no handle, no
 // device (gcm_plev_height_columns).  pe25d_plev_height: gcm_plev_height on `s`, synchronised before it returns.
-// gcm_set_plev_maps and its companions on `s`, the caller's stream: pe25d_plev_maps_due counts one step, as
-// pe25d_climate_due does; pe25d_plev_maps_levels: -1 without a registration; pe25d_plev_maps_plan: gcm_plev_maps_plan
+// gcm_set_plev_maps, gcm_plev_maps_sample and gcm_plev_maps_plan
 int plev_height_columns(int ncol, int L, int N, const double *p, const double *theta, const double *hmG, const double *sig,
                         const double *dsig, const double *sigt, double ptop, const double *P, double *out, int *valid, std::string *err);
 int pe25d_plev_height(Pe25d *m, int N, const double *P, double fill, double *out, int32_t *valid, hipStream_t s, std::string *err);
 int pe25d_set_plev_maps(Pe25d *m, int every, int N, const double *P, hipStream_t s, std::string *err);
-int pe25d_plev_maps_every(const Pe25d *m);
-int pe25d_plev_maps_levels(const Pe25d *m, double *P, int cap);
-bool pe25d_plev_maps_due(Pe25d *m);
 int pe25d_plev_maps_plan(const Pe25d *m, int *out, int nout);
 int pe25d_plev_maps_sample(Pe25d *m, hipStream_t s, std::string *err);
-int pe25d_plev_maps_reset(Pe25d *m, hipStream_t s, std::string *err);
-int pe25d_get_plev_maps(Pe25d *m, double *sums, double *sums2, int64_t *nsamples, hipStream_t s, std::string *err);
-int pe25d_put_plev_maps(Pe25d *m, const double *sums, const double *sums2, int64_t nsamples, hipStream_t s, std::string *err);
-// Zonal wavenumber spectra (pe25d_spectra.hip): gcm_set_spectra and its companions on `s`, the caller's stream.
-// pe25d_spectra_due: counts one step, as pe25d_climate_due does; pe25d_spectra_mmax: -1 without a registration;
-// pe25d_spectra_plan: gcm_spectra_plan
+// Zonal wavenumber spectra (pe25d_spectra.hip): gcm_set_spectra, gcm_spectra_sample and gcm_spectra_plan;
+// pe25d_spectra_mmax: the registered mmax (gcm_spectra_mmax)
 int pe25d_set_spectra(Pe25d *m, int every, int mmax, hipStream_t s, std::string *err);
-int pe25d_spectra_every(const Pe25d *m);
 int pe25d_spectra_mmax(const Pe25d *m);
-bool pe25d_spectra_due(Pe25d *m);
 int pe25d_spectra_plan(const Pe25d *m, int *out, int nout);
 int pe25d_spectra_sample(Pe25d *m, hipStream_t s, std::string *err);
-int pe25d_spectra_reset(Pe25d *m, hipStream_t s, std::string *err);
-int pe25d_get_spectra(Pe25d *m, double *sums, int64_t *nsamples, hipStream_t s, std::string *err);
-int pe25d_put_spectra(Pe25d *m, const double *sums, int64_t nsamples, hipStream_t s, std::string *err);
 // The column sums of the convective adjustment (count, levels), of the moist physics (precip, evap) and of the boundary
 // layer (shf, evap), one set of routines for all (pe25d_state.hip), on `s`, the caller's stream.  pe25d_sums_set: allocated and zeroed (on) or freed;
 // a phase is registered where its sums are in place, and pe25d_sums_on is the one place that says so.  reset, get and

@@ -220,23 +220,8 @@ int plev_columns(int ncol, int L, int N, const double *pl, const double *x, cons
 }
 
 // ---------------------------------------------------------------- the handle's side
-// layout of PePlevClimate::buf (doubles): P [N] | s [GCM_PLEV_WORDS][N][H]
-static size_t plev_sums(const Pe25d *m, int N) { return (size_t)GCM_PLEV_WORDS * N * m->H; }
-
-static int plev_registered(const Pe25d *m, const char *fn, std::string *err) {
-    if (m->plev.every > 0) return GCM_OK;
-    *err = std::string(fn) + ": no pressure-level climatology registered (gcm_set_plev_climate)";
-    return GCM_ERR_STATE;
-}
-
-static void plev_free(Pe25d *m) {
-    PePlevClimate &z = m->plev;
-    if (z.buf) {
-        m->allocs.erase(std::remove(m->allocs.begin(), m->allocs.end(), (void *)z.buf), m->allocs.end());
-        (void)hipFree(z.buf);
-    }
-    z = PePlevClimate{};
-}
+// layout of the sampler's buf (doubles): P [N] | s [GCM_PLEV_WORDS][N][H].  every, due, reset, get, put and free are the
+// samplers' shared routines (pe25d_sampler_*, pe25d_state.hip)
 
 // what both kernels read of the handle's current state
 static PlevArgs plev_args(Pe25d *m, const double *sig) {
@@ -250,14 +235,15 @@ static PlevArgs plev_args(Pe25d *m, const double *sig) {
     return a;
 }
 
+// A second registration always takes a new buffer: the targets change with it
 int pe25d_set_plev_climate(Pe25d *m, int every, int N, const double *P, hipStream_t s, std::string *err) {
-    PePlevClimate &z = m->plev;
+    PePlev &z = m->plev;
     if (every < 0) { *err = "gcm_set_plev_climate: every must be >= 0"; return GCM_ERR_ARG; }
     if (every == 0) {
         if (!z.buf) return GCM_OK;
         // (a sample may still be adding to the sums)
         if (int rc = hip_rc(hipStreamSynchronize(s), "gcm_set_plev_climate", err)) return rc;
-        plev_free(m);
+        pe25d_sampler_free(m, kSamplePlevClimate);
         return GCM_OK;
     }
     if (!plev_targets_ok(N, P)) {
@@ -269,36 +255,32 @@ int pe25d_set_plev_climate(Pe25d *m, int every, int N, const double *P, hipStrea
     // (the targets change with the registration, and a sample in flight reads the ones in place: a new buffer)
     if (z.buf) {
         if (int rc = hip_rc(hipStreamSynchronize(s), "gcm_set_plev_climate", err)) return rc;
-        plev_free(m);
+        pe25d_sampler_free(m, kSamplePlevClimate);
     }
-    std::vector<double> init((size_t)N + plev_sums(m, N), 0.0);
+    const size_t sums = (size_t)GCM_PLEV_WORDS * N * m->H;
+    std::vector<double> init((size_t)N + sums, 0.0);
     std::copy(P, P + N, init.begin());
     if (!dev_upload<double>(m, &z.buf, init.data(), init.size())) {
         // (dev_upload keeps what it allocated in the handle's list: gcm_destroy frees it)
-        z = PePlevClimate{};
+        z = PePlev{};
         *err = "hip: gcm_set_plev_climate allocation failed";
         return GCM_ERR_HIP;
     }
     z.P.assign(P, P + N);
+    z.head = (size_t)N;
+    z.words[0] = sums;
+    z.words[1] = 0;
     z.every = every;
     z.steps = 0;
     z.n = 0;
     return GCM_OK;
 }
 
-int pe25d_plev_climate_every(const Pe25d *m) { return m->plev.every; }
-
-int pe25d_plev_climate_levels(const Pe25d *m, double *P, int cap) {
-    const PePlevClimate &z = m->plev;
-    if (z.every <= 0) return -1;
+// gcm_plev_climate_levels, gcm_plev_maps_levels: the targets of a registration that is in place
+int pe25d_plev_levels(const Pe25d *m, PeSample of, double *P, int cap) {
+    const PePlev &z = of == kSamplePlevMaps ? m->pmaps : m->plev;
     if (P) std::copy(z.P.begin(), z.P.begin() + std::min<size_t>(z.P.size(), (size_t)std::max(cap, 0)), P);
     return (int)z.P.size();
-}
-
-bool pe25d_plev_climate_due(Pe25d *m) {
-    PePlevClimate &z = m->plev;
-    if (z.every <= 0) return false;
-    return ++z.steps % z.every == 0;
 }
 
 int pe25d_plev_climate_plan(const Pe25d *m, int *out, int nout) {
@@ -312,62 +294,19 @@ int pe25d_plev_climate_plan(const Pe25d *m, int *out, int nout) {
     return GCM_OK;
 }
 
-// The ordering argument is the climatology's (pe25d_climate_sample), restated.  The launch is a pure reader of the
-// current state set on `s` -- p, u, v, theta and q, and on a band v's first north ghost row -- and writes its own sums
-// only: it leaves the column sums, the fork at the last K4 and the ghost-row bookkeeping as they are.  What must hold is
-// that whatever overwrites this state set later is ordered behind this launch.  The set is written again by the
-// corrector's K4 two steps on, by the physics phases behind it, and -- a band -- by the unpack of the exchange that
-// follows that K4.  K4 of the rows the caller's stream keeps follows this launch in stream order on `s`.  A band's edge
-// rows' K4 runs on the second stream, which every stage makes wait for its fork: the completion of the previous stage's
-// K4 on `s` (ev_k4) or a record on `s` at the head of the stage (ev_fork) -- an event behind this launch on `s` in either
-// case, from the very next stage on; the pack, the exchange and the unpack follow that K4.  The third stream writes no
-// state set.  The launches of the next stage that may run beside this one (chain B forked at ev_k4: K1, pit, column
-// sums, anchors, the tracers) write intermediates and tracers only, none of which is read here; q is a state field, not
-// a tracer.
+// The launch reads p, u, v, theta and q of the current state set, and on a band v's first north ghost row; q is a state
+// field, not a tracer.  How it is ordered against the stages that follow: pe25d_kernels.h, at the samplers' declarations
 int pe25d_plev_climate_sample(Pe25d *m, hipStream_t s, std::string *err) {
-    if (int rc = plev_registered(m, "gcm_plev_climate_sample", err)) return rc;
-    PePlevClimate &z = m->plev;
+    if (int rc = pe25d_sampler_registered(m, kSamplePlevClimate, "gcm_plev_climate_sample", err)) return rc;
+    PePlev &z = m->plev;
     const int N = (int)z.P.size();
     PlevArgs a = plev_args(m, m->lev_tab);
-    a.P = z.buf; a.s = z.buf + N; a.N = N;
+    a.P = z.buf; a.s = z.buf + z.head; a.N = N;
     const dim3 grid((unsigned)a.H, (unsigned)plev_nseg(N));
     if (m->f32) hipLaunchKernelGGL(pe_plev_climate_kernel<float>, grid, dim3(kPlThreads), plev_lds_bytes(), s, a);
     else hipLaunchKernelGGL(pe_plev_climate_kernel<double>, grid, dim3(kPlThreads), plev_lds_bytes(), s, a);
     if (int rc = hip_rc(hipGetLastError(), "gcm_plev_climate_sample", err)) return rc;
     ++z.n;
-    return GCM_OK;
-}
-
-int pe25d_plev_climate_reset(Pe25d *m, hipStream_t s, std::string *err) {
-    if (int rc = plev_registered(m, "gcm_plev_climate_reset", err)) return rc;
-    PePlevClimate &z = m->plev;
-    const size_t N = z.P.size();
-    if (int rc = hip_rc(hipMemsetAsync(z.buf + N, 0, sizeof(double) * plev_sums(m, (int)N), s), "gcm_plev_climate_reset", err)) return rc;
-    z.n = 0;
-    return GCM_OK;
-}
-
-int pe25d_get_plev_climate(Pe25d *m, double *sums, int64_t *nsamples, hipStream_t s, std::string *err) {
-    if (int rc = plev_registered(m, "gcm_get_plev_climate", err)) return rc;
-    const PePlevClimate &z = m->plev;
-    const size_t N = z.P.size();
-    hipError_t e = hipSuccess;
-    if (sums) e = hipMemcpyAsync(sums, z.buf + N, sizeof(double) * plev_sums(m, (int)N), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (int rc = hip_rc(e, "gcm_get_plev_climate", err)) return rc;
-    if (nsamples) *nsamples = z.n;
-    return GCM_OK;
-}
-
-int pe25d_put_plev_climate(Pe25d *m, const double *sums, int64_t nsamples, hipStream_t s, std::string *err) {
-    if (int rc = plev_registered(m, "gcm_put_plev_climate", err)) return rc;
-    if (!sums || nsamples < 0) { *err = "gcm_put_plev_climate: s is required, nsamples must be >= 0"; return GCM_ERR_ARG; }
-    PePlevClimate &z = m->plev;
-    const size_t N = z.P.size();
-    hipError_t e = hipMemcpyAsync(z.buf + N, sums, sizeof(double) * plev_sums(m, (int)N), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);          // (the caller's array is free again when the call returns)
-    if (int rc = hip_rc(e, "gcm_put_plev_climate", err)) return rc;
-    z.n = nsamples;
     return GCM_OK;
 }
 

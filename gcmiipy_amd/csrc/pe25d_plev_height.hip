@@ -135,24 +135,9 @@ int plev_height_columns(int ncol, int L, int N, const double *p, const double *t
 }
 
 // ---------------------------------------------------------------- the handle's side
-// layout of PePlevMaps::buf (doubles): P [N] | s [GCM_PLEV_MAP_WORDS][N][H][W] | s2 [GCM_PLEV_MAP_WORDS2][H][W]
-static size_t maps_sums(const Pe25d *m, size_t N) { return ((size_t)GCM_PLEV_MAP_WORDS * N + GCM_PLEV_MAP_WORDS2) * m->H * m->W; }
-static size_t maps_sums3(const Pe25d *m, size_t N) { return (size_t)GCM_PLEV_MAP_WORDS * N * m->H * m->W; }
-
-static int maps_registered(const Pe25d *m, const char *fn, std::string *err) {
-    if (m->pmaps.every > 0) return GCM_OK;
-    *err = std::string(fn) + ": no pressure-level maps registered (gcm_set_plev_maps)";
-    return GCM_ERR_STATE;
-}
-
-static void maps_free(Pe25d *m) {
-    PePlevMaps &z = m->pmaps;
-    if (z.buf) {
-        m->allocs.erase(std::remove(m->allocs.begin(), m->allocs.end(), (void *)z.buf), m->allocs.end());
-        (void)hipFree(z.buf);
-    }
-    z = PePlevMaps{};
-}
+// layout of the sampler's buf (doubles): P [N] | s [GCM_PLEV_MAP_WORDS][N][H][W] | s2 [GCM_PLEV_MAP_WORDS2][H][W].  every,
+// due, reset, get, put and free are the samplers' shared routines (pe25d_sampler_*, pe25d_state.hip), the targets' query
+// pe25d_plev_levels (pe25d_plev.hip)
 
 // sig [L], dsig [L], sigt [L] in float64 on the device, uploaded by the first call and kept until the handle goes
 static const double *height_table(Pe25d *m, const char *who, std::string *err) {
@@ -195,33 +180,34 @@ static int height_checks(Pe25d *m, const char *fn, int N, const double *P, std::
     return GCM_OK;
 }
 
+// A second registration always takes a new buffer, as the pressure-level climatology's; the sums are zeroed on the device
 int pe25d_set_plev_maps(Pe25d *m, int every, int N, const double *P, hipStream_t s, std::string *err) {
-    PePlevMaps &z = m->pmaps;
+    PePlev &z = m->pmaps;
     if (every < 0) { *err = "gcm_set_plev_maps: every must be >= 0"; return GCM_ERR_ARG; }
     if (every == 0) {
         if (!z.buf) return GCM_OK;
         // (a sample may still be adding to the sums)
         if (int rc = hip_rc(hipStreamSynchronize(s), "gcm_set_plev_maps", err)) return rc;
-        maps_free(m);
+        pe25d_sampler_free(m, kSamplePlevMaps);
         return GCM_OK;
     }
     if (int rc = height_checks(m, "gcm_set_plev_maps", N, P, err)) return rc;
     // (the targets change with the registration, and a sample in flight reads the ones in place: a new buffer)
     if (z.buf) {
         if (int rc = hip_rc(hipStreamSynchronize(s), "gcm_set_plev_maps", err)) return rc;
-        maps_free(m);
+        pe25d_sampler_free(m, kSamplePlevMaps);
     }
     // (the sums are (13 N + 2) H W doubles, hundreds of MB on a product grid: zeroed on the device, not uploaded)
     void *d = nullptr;
-    const size_t words = (size_t)N + maps_sums(m, N);
-    hipError_t e = hipMalloc(&d, sizeof(double) * words);
+    const size_t cells = (size_t)m->H * m->W, sums = (size_t)GCM_PLEV_MAP_WORDS * N * cells, sums2 = (size_t)GCM_PLEV_MAP_WORDS2 * cells;
+    hipError_t e = hipMalloc(&d, sizeof(double) * ((size_t)N + sums + sums2));
     if (e != hipSuccess) {
         (void)hipGetLastError();
         *err = "hip: gcm_set_plev_maps allocation failed";
         return GCM_ERR_HIP;
     }
     e = hipMemcpyAsync(d, P, sizeof(double) * N, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync((double *)d + N, 0, sizeof(double) * (words - N), s);
+    if (e == hipSuccess) e = hipMemsetAsync((double *)d + N, 0, sizeof(double) * (sums + sums2), s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);          // (the caller's targets are free again when the call returns)
     if (e != hipSuccess) {
         (void)hipFree(d);
@@ -230,25 +216,13 @@ int pe25d_set_plev_maps(Pe25d *m, int every, int N, const double *P, hipStream_t
     m->allocs.push_back(d);
     z.buf = (double *)d;
     z.P.assign(P, P + N);
+    z.head = (size_t)N;
+    z.words[0] = sums;
+    z.words[1] = sums2;
     z.every = every;
     z.steps = 0;
     z.n = 0;
     return GCM_OK;
-}
-
-int pe25d_plev_maps_every(const Pe25d *m) { return m->pmaps.every; }
-
-int pe25d_plev_maps_levels(const Pe25d *m, double *P, int cap) {
-    const PePlevMaps &z = m->pmaps;
-    if (z.every <= 0) return -1;
-    if (P) std::copy(z.P.begin(), z.P.begin() + std::min<size_t>(z.P.size(), (size_t)std::max(cap, 0)), P);
-    return (int)z.P.size();
-}
-
-bool pe25d_plev_maps_due(Pe25d *m) {
-    PePlevMaps &z = m->pmaps;
-    if (z.every <= 0) return false;
-    return ++z.steps % z.every == 0;
 }
 
 int pe25d_plev_maps_plan(const Pe25d *m, int *out, int nout) {
@@ -262,64 +236,18 @@ int pe25d_plev_maps_plan(const Pe25d *m, int *out, int nout) {
     return GCM_OK;
 }
 
-// The ordering argument is the pressure-level climatology's (pe25d_plev_climate_sample), restated.  The launch is a pure
-// reader of the current state set on `s` -- p, u, v, theta and q, and on a band v's first north ghost row -- and of
-// tables nobody writes (the heightmap, the levels, the targets); it writes its own sums only: it leaves the column sums,
-// the fork at the last K4 and the ghost-row bookkeeping as they are.  What must hold is that whatever overwrites this
-// state set later is ordered behind this launch.  The set is written again by the corrector's K4 two steps on, by the
-// physics phases behind it, and -- a band -- by the unpack of the exchange that follows that K4.  K4 of the rows the
-// caller's stream keeps follows this launch in stream order on `s`.  A band's edge rows' K4 runs on the second stream,
-// which every stage makes wait for its fork: the completion of the previous stage's K4 on `s` (ev_k4) or a record on `s`
-// at the head of the stage (ev_fork) -- an event behind this launch on `s` in either case, from the very next stage on;
-// the pack, the exchange and the unpack follow that K4.  The third stream writes no state set.  The launches of the next
-// stage that may run beside this one (chain B forked at ev_k4: K1, pit, column sums, anchors, the tracers) write
-// intermediates and tracers only, none of which is read here; q is a state field, not a tracer.  The other samples of
-// the step (climatology, pressure-level climatology, spectra) precede this one on `s` and write their own sums only.
+// The launch reads p, u, v, theta and q of the current state set, on a band v's first north ghost row, and tables nobody
+// writes (the heightmap, the levels, the targets); the last sample of a step, behind the climatology's, the pressure-level
+// climatology's and the spectra's on `s`.  How it is ordered against the stages that follow: pe25d_kernels.h, at the
+// samplers' declarations
 int pe25d_plev_maps_sample(Pe25d *m, hipStream_t s, std::string *err) {
-    if (int rc = maps_registered(m, "gcm_plev_maps_sample", err)) return rc;
-    PePlevMaps &z = m->pmaps;
+    if (int rc = pe25d_sampler_registered(m, kSamplePlevMaps, "gcm_plev_maps_sample", err)) return rc;
+    PePlev &z = m->pmaps;
     const int N = (int)z.P.size();
     PlevHeightArgs a = height_args(m);
-    a.P = z.buf; a.s = z.buf + N; a.s2 = a.s + maps_sums3(m, N); a.N = N;
+    a.P = z.buf; a.s = z.buf + z.head; a.s2 = a.s + z.words[0]; a.N = N;
     if (int rc = hip_rc(height_launch<true>(m, a, s), "gcm_plev_maps_sample", err)) return rc;
     ++z.n;
-    return GCM_OK;
-}
-
-int pe25d_plev_maps_reset(Pe25d *m, hipStream_t s, std::string *err) {
-    if (int rc = maps_registered(m, "gcm_plev_maps_reset", err)) return rc;
-    PePlevMaps &z = m->pmaps;
-    const size_t N = z.P.size();
-    if (int rc = hip_rc(hipMemsetAsync(z.buf + N, 0, sizeof(double) * maps_sums(m, N), s), "gcm_plev_maps_reset", err)) return rc;
-    z.n = 0;
-    return GCM_OK;
-}
-
-int pe25d_get_plev_maps(Pe25d *m, double *sums, double *sums2, int64_t *nsamples, hipStream_t s, std::string *err) {
-    if (int rc = maps_registered(m, "gcm_get_plev_maps", err)) return rc;
-    const PePlevMaps &z = m->pmaps;
-    const size_t N = z.P.size(), n3 = maps_sums3(m, N);
-    hipError_t e = hipSuccess;
-    if (sums) e = hipMemcpyAsync(sums, z.buf + N, sizeof(double) * n3, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && sums2)
-        e = hipMemcpyAsync(sums2, z.buf + N + n3, sizeof(double) * (maps_sums(m, N) - n3), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (int rc = hip_rc(e, "gcm_get_plev_maps", err)) return rc;
-    if (nsamples) *nsamples = z.n;
-    return GCM_OK;
-}
-
-int pe25d_put_plev_maps(Pe25d *m, const double *sums, const double *sums2, int64_t nsamples, hipStream_t s, std::string *err) {
-    if (int rc = maps_registered(m, "gcm_put_plev_maps", err)) return rc;
-    if (!sums || !sums2 || nsamples < 0) { *err = "gcm_put_plev_maps: s and s2 are required, nsamples must be >= 0"; return GCM_ERR_ARG; }
-    PePlevMaps &z = m->pmaps;
-    const size_t N = z.P.size(), n3 = maps_sums3(m, N);
-    hipError_t e = hipMemcpyAsync(z.buf + N, sums, sizeof(double) * n3, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(z.buf + N + n3, sums2, sizeof(double) * (maps_sums(m, N) - n3), hipMemcpyHostToDevice, s);
-    const hipError_t es = hipStreamSynchronize(s);             // (the caller's arrays are free again when the call returns)
-    if (e == hipSuccess) e = es;
-    if (int rc = hip_rc(e, "gcm_put_plev_maps", err)) return rc;
-    z.n = nsamples;
     return GCM_OK;
 }
 

@@ -195,26 +195,10 @@ static const void *sp_kernel_for(int M) {
 static const void *sp_kernel(const Pe25d *m, int M) { return m->f32 ? sp_kernel_for<float>(M) : sp_kernel_for<double>(M); }
 
 // ---------------------------------------------------------------- the handle's side
-// layout of PeSpectra::buf: tw [W] double2 | sig [L] | s [GCM_SPEC_WORDS][L][H][M]
-static size_t spec_words(const Pe25d *m, int M) { return (size_t)GCM_SPEC_WORDS * m->L * m->H * M; }
-static double *spec_sig(const Pe25d *m) { return m->spec.buf + 2 * (size_t)m->W; }
-static double *spec_sums(const Pe25d *m) { return spec_sig(m) + m->L; }
+// layout of the sampler's buf: tw [W] double2 | sig [L] | s [GCM_SPEC_WORDS][L][H][M].  every, due, reset, get, put and
+// free are the samplers' shared routines (pe25d_sampler_*, pe25d_state.hip)
 
-static int spec_registered(const Pe25d *m, const char *fn, std::string *err) {
-    if (m->spec.every > 0) return GCM_OK;
-    *err = std::string(fn) + ": no spectra registered (gcm_set_spectra)";
-    return GCM_ERR_STATE;
-}
-
-static void spec_free(Pe25d *m) {
-    PeSpectra &z = m->spec;
-    if (z.buf) {
-        m->allocs.erase(std::remove(m->allocs.begin(), m->allocs.end(), (void *)z.buf), m->allocs.end());
-        (void)hipFree(z.buf);
-    }
-    z = PeSpectra{};
-}
-
+// A second registration with the same mmax zeroes the sums in place, with another it takes a new buffer
 int pe25d_set_spectra(Pe25d *m, int every, int mmax, hipStream_t s, std::string *err) {
     PeSpectra &z = m->spec;
     if (every < 0) { *err = "gcm_set_spectra: every must be >= 0"; return GCM_ERR_ARG; }
@@ -222,7 +206,7 @@ int pe25d_set_spectra(Pe25d *m, int every, int mmax, hipStream_t s, std::string 
         if (!z.buf) return GCM_OK;
         // (a sample may still be adding to the sums)
         if (int rc = hip_rc(hipStreamSynchronize(s), "gcm_set_spectra", err)) return rc;
-        spec_free(m);
+        pe25d_sampler_free(m, kSampleSpectra);
         return GCM_OK;
     }
     if (mmax < -1 || mmax > m->W / 2) {
@@ -239,15 +223,15 @@ int pe25d_set_spectra(Pe25d *m, int every, int mmax, hipStream_t s, std::string 
         return GCM_ERR_UNSUPPORTED;
     }
     if (int rc = hip_rc(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "gcm_set_spectra", err)) return rc;
-    const size_t sums = spec_words(m, M);
+    const size_t head = 2 * (size_t)m->W + m->L, sums = (size_t)GCM_SPEC_WORDS * m->L * m->H * M;
     if (z.buf && z.mmax == mmax) {
-        if (int rc = hip_rc(hipMemsetAsync(spec_sums(m), 0, sizeof(double) * sums, s), "gcm_set_spectra", err)) return rc;
+        if (int rc = hip_rc(hipMemsetAsync(z.buf + head, 0, sizeof(double) * sums, s), "gcm_set_spectra", err)) return rc;
     } else {
         if (z.buf) {
             if (int rc = hip_rc(hipStreamSynchronize(s), "gcm_set_spectra", err)) return rc;
-            spec_free(m);
+            pe25d_sampler_free(m, kSampleSpectra);
         }
-        std::vector<double> init(2 * (size_t)m->W + m->L + sums, 0.0);
+        std::vector<double> init(head + sums, 0.0);
         spectra_twiddles(m->W, (double2 *)init.data());
         std::copy(m->sig_host.begin(), m->sig_host.end(), init.begin() + 2 * (size_t)m->W);
         if (!dev_upload<double>(m, &z.buf, init.data(), init.size())) {
@@ -257,6 +241,9 @@ int pe25d_set_spectra(Pe25d *m, int every, int mmax, hipStream_t s, std::string 
             return GCM_ERR_HIP;
         }
     }
+    z.head = head;
+    z.words[0] = sums;
+    z.words[1] = 0;
     z.every = every;
     z.mmax = mmax;
     z.steps = 0;
@@ -264,26 +251,19 @@ int pe25d_set_spectra(Pe25d *m, int every, int mmax, hipStream_t s, std::string 
     return GCM_OK;
 }
 
-int pe25d_spectra_every(const Pe25d *m) { return m->spec.every; }
-int pe25d_spectra_mmax(const Pe25d *m) { return m->spec.every > 0 ? m->spec.mmax : -1; }
+int pe25d_spectra_mmax(const Pe25d *m) { return m->spec.mmax; }
 
-bool pe25d_spectra_due(Pe25d *m) {
-    PeSpectra &z = m->spec;
-    if (z.every <= 0) return false;
-    return ++z.steps % z.every == 0;
-}
-
-// A pure reader of the current state set on `s` that writes its own sums only, like the climatology's sample, and
-// ordered against the stages that follow by the same argument (pe25d_climate_sample)
+// The launch reads p, u, v and theta of the current state set, and on a band v's first north ghost row, like the
+// climatology's; how it is ordered against the stages that follow: pe25d_kernels.h, at the samplers' declarations
 int pe25d_spectra_sample(Pe25d *m, hipStream_t s, std::string *err) {
-    if (int rc = spec_registered(m, "gcm_spectra_sample", err)) return rc;
+    if (int rc = pe25d_sampler_registered(m, kSampleSpectra, "gcm_spectra_sample", err)) return rc;
     PeSpectra &z = m->spec;
     const int set = m->cur_i;
     SpectraArgs a{};
     a.p = state_field(m, set, GCM_P); a.u = state_field(m, set, GCM_U);
     a.v = state_field(m, set, GCM_V); a.t = state_field(m, set, GCM_T);
-    a.tw = (const double2 *)z.buf; a.sig = spec_sig(m); a.exner_tab = m->exner_tab;
-    a.s = spec_sums(m);
+    a.tw = (const double2 *)z.buf; a.sig = z.buf + 2 * (size_t)m->W; a.exner_tab = m->exner_tab;
+    a.s = z.buf + z.head;
     a.ptop = m->cfg.ptop;
     a.plan = m->plan;
     a.W = m->W; a.H = m->H; a.L = m->L; a.M = z.mmax + 1; a.wrap = m->wrap ? 1 : 0;
@@ -305,36 +285,6 @@ int pe25d_spectra_plan(const Pe25d *m, int *out, int nout) {
     out[3] = (int)spectra_lds_bytes(m->W);
     out[4] = m->plan.nrad;
     out[5] = (M + kSpThreads - 1) / kSpThreads;
-    return GCM_OK;
-}
-
-int pe25d_spectra_reset(Pe25d *m, hipStream_t s, std::string *err) {
-    if (int rc = spec_registered(m, "gcm_spectra_reset", err)) return rc;
-    PeSpectra &z = m->spec;
-    if (int rc = hip_rc(hipMemsetAsync(spec_sums(m), 0, sizeof(double) * spec_words(m, z.mmax + 1), s), "gcm_spectra_reset", err)) return rc;
-    z.n = 0;
-    return GCM_OK;
-}
-
-int pe25d_get_spectra(Pe25d *m, double *sums, int64_t *nsamples, hipStream_t s, std::string *err) {
-    if (int rc = spec_registered(m, "gcm_get_spectra", err)) return rc;
-    const PeSpectra &z = m->spec;
-    hipError_t e = hipSuccess;
-    if (sums) e = hipMemcpyAsync(sums, spec_sums(m), sizeof(double) * spec_words(m, z.mmax + 1), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (int rc = hip_rc(e, "gcm_get_spectra", err)) return rc;
-    if (nsamples) *nsamples = z.n;
-    return GCM_OK;
-}
-
-int pe25d_put_spectra(Pe25d *m, const double *sums, int64_t nsamples, hipStream_t s, std::string *err) {
-    if (int rc = spec_registered(m, "gcm_put_spectra", err)) return rc;
-    if (!sums || nsamples < 0) { *err = "gcm_put_spectra: s is required, nsamples must be >= 0"; return GCM_ERR_ARG; }
-    PeSpectra &z = m->spec;
-    hipError_t e = hipMemcpyAsync(spec_sums(m), sums, sizeof(double) * spec_words(m, z.mmax + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);          // (the caller's array is free again when the call returns)
-    if (int rc = hip_rc(e, "gcm_put_spectra", err)) return rc;
-    z.n = nsamples;
     return GCM_OK;
 }
 

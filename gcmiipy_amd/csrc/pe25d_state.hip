@@ -310,6 +310,86 @@ int pe25d_sums_put(Pe25d *m, PeSums of, const double *a, const double *b, double
     return GCM_OK;
 }
 
+// ---------------------------------------------------------------- what the four sampled diagnostics share
+static PeSampler &sampler_of(Pe25d *m, PeSample of) {
+    switch (of) {
+    case kSamplePlevClimate: return m->plev;
+    case kSampleSpectra: return m->spec;
+    case kSamplePlevMaps: return m->pmaps;
+    default: return m->clim;
+    }
+}
+// the entry point's name, "gcm_" + pre + <name> + post
+static std::string sampler_fn(PeSample of, const char *pre, const char *post) {
+    return std::string("gcm_") + pre + kPeSamplerWords[of].name + post;
+}
+
+int pe25d_sampler_registered(const Pe25d *m, PeSample of, const char *fn, std::string *err) {
+    if (sampler_of(const_cast<Pe25d *>(m), of).every > 0) return GCM_OK;
+    const PeSamplerWords &w = kPeSamplerWords[of];
+    *err = std::string(fn) + ": no " + w.what + " registered (gcm_set_" + w.name + ")";
+    return GCM_ERR_STATE;
+}
+
+int pe25d_sampler_every(const Pe25d *m, PeSample of) { return sampler_of(const_cast<Pe25d *>(m), of).every; }
+
+bool pe25d_sampler_due(Pe25d *m, PeSample of) {
+    PeSampler &z = sampler_of(m, of);
+    if (z.every <= 0) return false;
+    return ++z.steps % z.every == 0;
+}
+
+int pe25d_sampler_reset(Pe25d *m, PeSample of, hipStream_t s, std::string *err) {
+    const std::string fn = sampler_fn(of, "", "_reset");
+    if (int rc = pe25d_sampler_registered(m, of, fn.c_str(), err)) return rc;
+    PeSampler &z = sampler_of(m, of);
+    if (int rc = hip_rc(hipMemsetAsync(z.buf + z.head, 0, sizeof(double) * (z.words[0] + z.words[1]), s), fn.c_str(), err)) return rc;
+    z.n = 0;
+    return GCM_OK;
+}
+
+int pe25d_sampler_get(Pe25d *m, PeSample of, double *a, double *b, int64_t *nsamples, hipStream_t s, std::string *err) {
+    const std::string fn = sampler_fn(of, "get_", "");
+    if (int rc = pe25d_sampler_registered(m, of, fn.c_str(), err)) return rc;
+    const PeSampler &z = sampler_of(m, of);
+    const double *sums = z.buf + z.head;
+    hipError_t e = hipSuccess;
+    if (a) e = hipMemcpyAsync(a, sums, sizeof(double) * z.words[0], hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && b) e = hipMemcpyAsync(b, sums + z.words[0], sizeof(double) * z.words[1], hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (int rc = hip_rc(e, fn.c_str(), err)) return rc;
+    if (nsamples) *nsamples = z.n;
+    return GCM_OK;
+}
+
+int pe25d_sampler_put(Pe25d *m, PeSample of, const double *a, const double *b, int64_t nsamples, hipStream_t s, std::string *err) {
+    const std::string fn = sampler_fn(of, "put_", "");
+    if (int rc = pe25d_sampler_registered(m, of, fn.c_str(), err)) return rc;
+    const PeSamplerWords &w = kPeSamplerWords[of];
+    if (!a || (w.b && !b) || nsamples < 0) {
+        *err = fn + ": " + w.a + (w.b ? std::string(" and ") + w.b + " are" : std::string(" is")) + " required, nsamples must be >= 0";
+        return GCM_ERR_ARG;
+    }
+    PeSampler &z = sampler_of(m, of);
+    double *sums = z.buf + z.head;
+    hipError_t e = hipMemcpyAsync(sums, a, sizeof(double) * z.words[0], hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && w.b) e = hipMemcpyAsync(sums + z.words[0], b, sizeof(double) * z.words[1], hipMemcpyHostToDevice, s);
+    const hipError_t es = hipStreamSynchronize(s);             // (also where a copy failed: the caller's arrays are free again when the call returns)
+    if (e == hipSuccess) e = es;
+    if (int rc = hip_rc(e, fn.c_str(), err)) return rc;
+    z.n = nsamples;
+    return GCM_OK;
+}
+
+void pe25d_sampler_free(Pe25d *m, PeSample of) {
+    PeSampler &z = sampler_of(m, of);
+    if (z.buf) {
+        m->allocs.erase(std::remove(m->allocs.begin(), m->allocs.end(), (void *)z.buf), m->allocs.end());
+        (void)hipFree(z.buf);
+    }
+    z = PeSampler{};
+}
+
 // The GCM_PE_* switches, read once per handle at the top of pe25d_create (read_switches) and applied where the handle's
 // fields are decided.  Unset = the default.  `num` below is atoi of the value, `c0` its first character.
 //   switch                    default                          meaning
