@@ -28,6 +28,16 @@ struct Ix3 {
     __device__ __forceinline__ long s(int j, int i) const { return (long)w(j, H) * W + w(i, W); }
 };
 
+// A product rounded on its own, as NumPy rounds it.  This unit is built with -ffp-contract=fast, under which the
+// compiler turns a*b - c*d into fma(a, b, -(c*d)) and ignores a contract(off) pragma.  Where the two products are the
+// same numbers -- every neighbour is the cell itself, or i+1 and i-1 are one cell -- the reference is exactly zero,
+// and the fused form leaves the rounding error of c*d behind instead: 1e-16 of a flux, over dx_h = 2e-9 m in the
+// pole row.  The empty asm hides the multiply from the subtraction; it emits no instruction.
+__device__ __forceinline__ double rounded(double x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
 __global__ __launch_bounds__(256) void pe_op_cell_kernel(PeOpArgs a) {
     __shared__ double tab[kExnerTabDoubles];
     tab[threadIdx.x] = a.etab[threadIdx.x];
@@ -45,25 +55,25 @@ __global__ __launch_bounds__(256) void pe_op_cell_kernel(PeOpArgs a) {
         case GCM_PEOP_UN_PU: a.o[0][e] = x0[e] / iph2(x1, j, i); break;                       // :25-27
         case GCM_PEOP_UN_PV: a.o[0][e] = x0[e] / jph2(x1, j, i); break;                       // :30-32
         case GCM_PEOP_ADVEC_SIG: {                                                            // :49-52 (sd, q)
-            const auto flux = [&](int kk) { return ((x1[ix.c(kk, j, i)] + x1[ix.c(kk - 1, j, i)]) / 2) * x0[ix.c(kk, j, i)]; };
+            const auto flux = [&](int kk) { return rounded(((x1[ix.c(kk, j, i)] + x1[ix.c(kk - 1, j, i)]) / 2) * x0[ix.c(kk, j, i)]); };
             a.o[0][e] = -((flux(k) - flux(k + 1)) / a.dsig[k]);
             break;
         }
         case GCM_PEOP_ADVEC_M_PU: {                                                           // :55-108 (p, u, v, pu, pv)
             const double *u = x1, *v = x2, *pu = x3, *pv = x4;
             const auto U = [&](const double *f, int jj, int ii) { return f[ix.c(k, jj, ii)]; };
-            const auto puum = [&](int jj, int ii) { return ((U(u, jj, ii) + U(u, jj, ii - 1)) / 2) * ((U(pu, jj, ii) + U(pu, jj, ii - 1)) / 2); };
-            const auto puvp = [&](int jj, int ii) { return ((U(pv, jj, ii) + U(pv, jj, ii + 1)) / 2) * ((U(u, jj, ii) + U(u, jj + 1, ii)) / 2); };
-            const auto pvvm = [&](int jj, int ii) { return ((U(v, jj, ii) + U(v, jj - 1, ii)) / 2) * ((U(pv, jj, ii) + U(pv, jj - 1, ii)) / 2); };
-            const auto pvup = [&](int jj, int ii) { return ((U(v, jj, ii) + U(v, jj, ii + 1)) / 2) * ((U(pu, jj, ii) + U(pu, jj + 1, ii)) / 2); };
+            const auto puum = [&](int jj, int ii) { return rounded(((U(u, jj, ii) + U(u, jj, ii - 1)) / 2) * ((U(pu, jj, ii) + U(pu, jj, ii - 1)) / 2)); };
+            const auto puvp = [&](int jj, int ii) { return rounded(((U(pv, jj, ii) + U(pv, jj, ii + 1)) / 2) * ((U(u, jj, ii) + U(u, jj + 1, ii)) / 2)); };
+            const auto pvvm = [&](int jj, int ii) { return rounded(((U(v, jj, ii) + U(v, jj - 1, ii)) / 2) * ((U(pv, jj, ii) + U(pv, jj - 1, ii)) / 2)); };
+            const auto pvup = [&](int jj, int ii) { return rounded(((U(v, jj, ii) + U(v, jj, ii + 1)) / 2) * ((U(pu, jj, ii) + U(pu, jj + 1, ii)) / 2)); };
             a.o[0][e] = (puum(j, i) - puum(j, i + 1)) / a.dx_j[j] + (puvp(j - 1, i) - puvp(j, i)) / a.dy + 0.0;
             a.o[1][e] = (pvvm(j, i) - pvvm(j + 1, i)) / a.dy + (pvup(j, i - 1) - pvup(j, i)) / a.dx_h[j] + 0.0;
             break;
         }
         case GCM_PEOP_ADVEC_T: {                                                              // :174-181 (pu, pv, t)
             const auto U = [&](const double *f, int jj, int ii) { return f[ix.c(k, jj, ii)]; };
-            const auto tpu = [&](int jj, int ii) { return U(x0, jj, ii) * ((U(x2, jj, ii) + U(x2, jj, ii + 1)) / 2); };
-            const auto tpv = [&](int jj, int ii) { return U(x1, jj, ii) * ((U(x2, jj, ii) + U(x2, jj + 1, ii)) / 2); };
+            const auto tpu = [&](int jj, int ii) { return rounded(U(x0, jj, ii) * ((U(x2, jj, ii) + U(x2, jj, ii + 1)) / 2)); };
+            const auto tpv = [&](int jj, int ii) { return rounded(U(x1, jj, ii) * ((U(x2, jj, ii) + U(x2, jj + 1, ii)) / 2)); };
             a.o[0][e] = (tpu(j, i) - tpu(j, i - 1)) / a.dx_j[j] + (tpv(j, i) - tpv(j - 1, i)) / a.dy;
             break;
         }
