@@ -13,8 +13,8 @@ Importing the package loads the library and raises ImportError if it is not
 built: nothing here computes on the CPU.
 """
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
-from .core import (BoundaryLayer, Climate, Convect, Core, GcmError, Moist, PlevClimate, PlevMaps, Spectra, TracerStats, aquaplanet_sst,  # noqa: F401
-                   boundary_layer_column, boundary_layer_surface, convect_columns, convect_tracer_columns, device_count,
+from .core import (BettsMiller, BoundaryLayer, Climate, Convect, Core, GcmError, Moist, PlevClimate, PlevMaps, Spectra, TracerStats, aquaplanet_sst,  # noqa: F401
+                   betts_miller_columns, boundary_layer_column, boundary_layer_surface, convect_columns, convect_tracer_columns, device_count,
                    hdiff_apply, hdiff_apply_band, hdiff_tables, held_suarez_tables, moist_saturation, plev_columns, plev_height_columns)
 
 
@@ -28,6 +28,6 @@ def clear_cache():
     _lib.lib.gcm_ops_release_scratch()      # the operator entry points' device scratch of this thread
 
 
-__all__ = ["BoundaryLayer", "Climate", "Convect", "Core", "GcmError", "Moist", "PlevClimate", "PlevMaps", "Spectra", "TracerStats", "aquaplanet_sst",
+__all__ = ["BettsMiller", "BoundaryLayer", "Climate", "Convect", "Core", "GcmError", "Moist", "PlevClimate", "PlevMaps", "Spectra", "TracerStats", "aquaplanet_sst",
            "boundary_layer_column", "boundary_layer_surface", "convect_columns", "convect_tracer_columns", "device_count",
-           "clear_cache", "hdiff_apply", "hdiff_apply_band", "hdiff_tables", "held_suarez_tables", "moist_saturation", "plev_columns", "plev_height_columns"]
+           "betts_miller_columns", "clear_cache", "hdiff_apply", "hdiff_apply_band", "hdiff_tables", "held_suarez_tables", "moist_saturation", "plev_columns", "plev_height_columns"]

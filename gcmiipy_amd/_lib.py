@@ -118,6 +118,14 @@ class Convect(C.Structure):
     _fields_ = [("kappa_c", C.c_double), ("mix_q", C.c_int32)]
 
 
+class BettsMiller(C.Structure):
+    """gcm_betts_miller of include/gcmcore.h"""
+    _fields_ = [("Lv", C.c_double), ("tau", C.c_double), ("rh_bm", C.c_double), ("nsub", C.c_int)]
+
+
+BETTS_MILLER_MAX_LEVELS = 158                # GCM_BETTS_MILLER_MAX_LEVELS
+
+
 class TracerForcing(C.Structure):
     """gcm_tracer_forcing of include/gcmcore.h"""
     _fields_ = [("source", C.c_double), ("decay", C.c_double), ("pin_value", C.c_double),
@@ -204,6 +212,14 @@ SYMBOLS = {
     "gcm_put_convect": (C.c_int, [_H, _dp, _dp, C.c_double, C.c_int64]),
     "gcm_convect_reset": (C.c_int, [_H]),
     "gcm_convect_columns": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gcm_set_betts_miller": (C.c_int, [_H, C.POINTER(BettsMiller)]),
+    "gcm_betts_miller_on": (C.c_int, [_H]),
+    "gcm_betts_miller_step": (C.c_int, [_H, C.c_double, C.POINTER(BettsMiller)]),
+    "gcm_get_betts_miller": (C.c_int, [_H, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "gcm_put_betts_miller": (C.c_int, [_H, _dp, _dp, C.c_double, C.c_int64]),
+    "gcm_betts_miller_reset": (C.c_int, [_H]),
+    "gcm_betts_miller_columns": (C.c_int, [C.c_int, C.c_int] + [_dp] * 5 + [C.c_double, C.c_double, C.POINTER(BettsMiller), _dp, _dp, _dp,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]),
     "gcm_set_climate": (C.c_int, [_H, C.c_int]),
     "gcm_climate_every": (C.c_int, [_H]),
     "gcm_climate_sample": (C.c_int, [_H]),

@@ -289,6 +289,13 @@ def merge_moist(parts):
     return _merge_column(_MOIST, parts)
 
 
+def merge_betts_miller(parts):
+    """the Betts-Miller convection's sums of the whole domain from its bands': `parts` are the bands' BettsMiller records
+    (Core.betts_miller_sums) in row order; the rows are concatenated.  ValueError where nsteps or seconds differ"""
+    from .core import _BETTS_MILLER
+    return _merge_column(_BETTS_MILLER, parts)
+
+
 def merge_boundary_layer(parts):
     """the boundary layer's sums of the whole domain from its bands': `parts` are the bands' BoundaryLayer records
     (Core.boundary_layer_sums) in row order; the rows are concatenated.  ValueError where nsteps or seconds differ"""
@@ -408,6 +415,11 @@ class HipBandEngine:
         """Core.set_tracer_convection: a latitude band raises the library's refusal -- the tracers' convective mixing is
         not carried on bands yet (a band's ghost rows are adjusted locally; their tracers would have to be mixed there too)"""
         self.c.set_tracer_convection(i, on)
+
+    def set_betts_miller(self, *off, **params):
+        """Core.set_betts_miller; every band of a run registers the same.  merge_betts_miller() puts the bands' sums
+        together"""
+        self.c.set_betts_miller(*off, **params)
 
     def set_moist(self, *off, **params):
         """Core.set_moist; every band of a run registers the same.  merge_moist() puts the bands' sums together"""

@@ -37,14 +37,18 @@ is stored as "convect", its two parameters in the order of core.CONVECT_DEFAULTS
 "convect_count" and "convect_levels", saved and restored the same way; the boundary layer, Core.set_boundary_layer, is
 stored as "boundary_layer", its seven parameters in the order of core.BOUNDARY_LAYER_DEFAULTS, with "boundary_layer_n",
 "boundary_layer_seconds", "boundary_layer_shf" and "boundary_layer_evap", saved the same way and restored ahead of the
-convective adjustment, in the model's order (behind the ground temperature, which its registration needs))
+convective adjustment, in the model's order (behind the ground temperature, which its registration needs); the
+Betts-Miller convection, Core.set_betts_miller, is stored as "betts_miller", its four parameters in the order of
+core.BETTS_MILLER_DEFAULTS, with "betts_miller_n", "betts_miller_seconds", "betts_miller_precip" and "betts_miller_count",
+saved the same way and restored between the convective adjustment and the moist physics; files without these keys
+restore with none)
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
 import numpy as np
 
 from . import _lib
-from .core import COLUMN_PHASES, Core, GcmError, HDIFF_DEFAULTS, HELD_SUAREZ_DEFAULTS, SAMPLERS
+from .core import Core, GcmError, HDIFF_DEFAULTS, HELD_SUAREZ_DEFAULTS, SAMPLERS, STEP_COLUMN_PHASES
 from .geometry import Geom
 
 _GEOM_KEYS = ("sige", "sigt", "sigb", "dsig", "sig", "dsigv", "dx_j", "dx_h", "dy", "ptop",
@@ -96,7 +100,7 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
         out["hdiff"] = np.asarray([hd[k] for k in HDIFF_DEFAULTS], dtype=np.float64)
     # (a core is asked only for the phases it knows: getattr, so that a stand-in without one of them will do; reversed:
     # the files have always held the moist physics' keys ahead of the convective adjustment's; the boundary layer's follow)
-    for ph in reversed(COLUMN_PHASES if core.model == _lib.PE25D else ()):
+    for ph in reversed(STEP_COLUMN_PHASES if core.model == _lib.PE25D else ()):
         par = getattr(core, ph.name, None)
         if par is None and getattr(core, ph.name + "_registered", False):
             raise GcmError("checkpoint.save: the handle's %s was registered through gcm_set_%s directly; its parameters are "
@@ -120,7 +124,7 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
 
 def load(path):
     """-> dict(model, step, time, state={p,u,v,t,q}, geom or None, extra, ground, tracers, tracer_forcing,
-    tracer_mixing, tracer_convect, held_suarez, hdiff, climate, plev_climate, plev_maps, spectra, moist, convect, boundary_layer, band_boundary_layer,
+    tracer_mixing, tracer_convect, held_suarez, hdiff, climate, plev_climate, plev_maps, spectra, moist, convect, betts_miller, boundary_layer, band_boundary_layer,
     band_horizontal_diffusion); ground and
     tracers are
     None where the file has none, tracer_forcing
@@ -128,7 +132,8 @@ def load(path):
     opted in to the convective mixing (files without the key: none); held_suarez is (parameters dict, lat) or None; hdiff is
     dict(order, fields, nu, cmax) or None (files without the key: None); climate is
     dict(every, n, m3, m2) or None; plev_climate is dict(every, plev, n, sums) or None (files without the keys: None); plev_maps is dict(every, plev, n, sums, sums2) or None (files without the keys: None); spectra is dict(every, mmax, n, s) or None; moist is dict(params, n, seconds, precip, evap) or None; convect is
-    dict(params, n, seconds, count, levels) or None; boundary_layer is dict(params, n, seconds, shf, evap) or None;
+    dict(params, n, seconds, count, levels) or None; betts_miller is dict(params, n, seconds, precip, count) or None (files
+    without the keys: None); boundary_layer is dict(params, n, seconds, shf, evap) or None;
     band_boundary_layer is whether a band takes that phase (False for files without the option), and
     band_horizontal_diffusion the same for the horizontal diffusion"""
     d = np.load(path, allow_pickle=False)
@@ -173,9 +178,9 @@ def load(path):
                 x = d["%s_%s" % (sm.name, sm.extra[0])]
                 rec[sm.extra[0]] = x if x.ndim else int(x)
             sampled[sm.name] = rec
-    # (the parameters in the types of the phase's defaults: mix_q is an int)
-    column = {ph.name: None for ph in COLUMN_PHASES}
-    for ph in COLUMN_PHASES:
+    # (the parameters in the types of the phase's defaults: mix_q and nsub are ints)
+    column = {ph.name: None for ph in STEP_COLUMN_PHASES}
+    for ph in STEP_COLUMN_PHASES:
         if ph.name in d.files:
             par = {k: type(v)(x) for (k, v), x in zip(ph.defaults.items(), d[ph.name])}
             column[ph.name] = dict(params=par, n=int(d[ph.name + "_n"]), seconds=float(d[ph.name + "_seconds"]),
@@ -220,7 +225,7 @@ def restore(path, **core_kwargs):
         if rec is not None:
             getattr(core, "set_" + sm.name)(rec["every"], *([rec[sm.extra[0]]] if sm.extra else []))
             getattr(core, "put_" + sm.name)(rec["n"], *[rec[k] for k in sm.keys])
-    for ph in COLUMN_PHASES:                 # (the model's order: the boundary layer, the convective adjustment, the moist physics)
+    for ph in STEP_COLUMN_PHASES:            # (the model's order: the boundary layer, the convective adjustment, the Betts-Miller convection, the moist physics)
         rec = ck[ph.name]
         if rec is not None:
             getattr(core, "set_" + ph.name)(**rec["params"])

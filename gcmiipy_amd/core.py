@@ -737,9 +737,79 @@ def convect_tracer_columns(y, w, dsig, c, nblock=False):
     return (co, nb.astype(np.int32).reshape(y.shape)) if nblock else co
 
 
+# the parameters of the Betts-Miller convection (gcm_betts_miller), in the struct's order: the latent heat (J / kg), the
+# relaxation time (s), the relative humidity of the reference profile and the midpoint steps per level of the parcel's
+# pseudoadiabat
+BETTS_MILLER_DEFAULTS = collections.OrderedDict(Lv=2.5e6, tau=7200.0, rh_bm=0.7, nsub=2)
+
+
+def betts_miller_params(params):
+    """the four parameters of the Betts-Miller convection as a dict (Lv, tau, rh_bm floats, nsub an int):
+    BETTS_MILLER_DEFAULTS with `params` laid over them; ValueError for a name that is not a parameter and for an nsub
+    that is no whole number"""
+    unknown = sorted(set(params) - set(BETTS_MILLER_DEFAULTS))
+    if unknown:
+        raise ValueError("betts_miller: unknown parameter(s) %s; the parameters are %s"
+                         % (", ".join(unknown), ", ".join(BETTS_MILLER_DEFAULTS)))
+    out = collections.OrderedDict(BETTS_MILLER_DEFAULTS)
+    for k, v in params.items():
+        if k == "nsub":
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError("betts_miller: nsub must be a whole number")
+            out[k] = int(v)
+        else:
+            out[k] = float(v)
+    return out
+
+
+class BettsMiller(collections.namedtuple("BettsMiller", "nsteps seconds precip count")):
+    """the sums of a GCM_PE25D handle's Betts-Miller convection (Core.betts_miller_sums): the applications counted, the
+    sum of their dt in seconds, and per column (H, W), float64, the convective precipitation accumulated over them,
+    kg / m^2, and in how many applications the column convected.  A band: its own rows (bands.merge_betts_miller)"""
+    __slots__ = ()
+
+    def precip_rate(self):
+        """kg / m^2 / s: precip / seconds; ValueError where seconds == 0"""
+        if self.seconds == 0:
+            raise ValueError("BettsMiller: no time accumulated (seconds == 0)")
+        return self.precip / self.seconds
+
+    def frequency(self):
+        """count / nsteps: the share of the applications in which a column convected; ValueError where nsteps == 0"""
+        if self.nsteps == 0:
+            raise ValueError("BettsMiller: no application counted (nsteps == 0)")
+        return self.count / self.nsteps
+
+
+def betts_miller_columns(p, theta, q, sig, dsig, ptop=0.0, dt=0.0, **params):
+    """the column rule of the Betts-Miller convection (gcm_betts_miller_columns; the host build of the routines the
+    kernel calls, no handle, no device) over columns theta, q of shape (..., L), level 0 the bottom, with p (...) (Pa,
+    surface pressure minus ptop), sig and dsig (L,) and the step dt -> dict(theta, q (..., L): the columns as the phase
+    leaves them; precip (...): P_q, 0 where the column did not convect; kt (...): the cloud top, -1 where it did not;
+    k_lcl (...): the LCL's level, -1 where there is none; margin (...): the smallest relative distance of a comparison
+    the column consulted).  ValueError for a refused parameter"""
+    theta = np.asarray(theta, dtype=np.float64)
+    L = theta.shape[-1] if theta.ndim else 0
+    tt = as_f64(theta.reshape(-1, L) if L else theta, name="theta")
+    qq = as_f64(q, theta.shape, "q").reshape(tt.shape)
+    n = tt.shape[0] if L else 0
+    pp = as_f64(np.asarray(p, dtype=np.float64).reshape(n), name="p")
+    ss, dd = as_f64(np.asarray(sig, dtype=np.float64).reshape(-1), (L,), "sig"), as_f64(np.asarray(dsig, dtype=np.float64).reshape(-1), (L,), "dsig")
+    rec = _lib.BettsMiller(*betts_miller_params(params).values())
+    to, qo, pr, mg = np.empty_like(tt), np.empty_like(tt), np.empty(n), np.empty(n)
+    kt, kl = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+    i32 = C.POINTER(C.c_int32)
+    _check(lib.gcm_betts_miller_columns(n, L, _tab(pp), _tab(tt), _tab(qq), _tab(ss), _tab(dd), float(ptop), float(dt), C.byref(rec),
+                                        _tab(to), _tab(qo), _tab(pr), kt.ctypes.data_as(i32), kl.ctypes.data_as(i32), _tab(mg)))
+    lead = theta.shape[:-1]
+    return dict(theta=to.reshape(theta.shape), q=qo.reshape(theta.shape), precip=pr.reshape(lead), kt=kt.reshape(lead),
+                k_lcl=kl.reshape(lead), margin=mg.reshape(lead))
+
+
 class _ColumnPhase:
-    """what tells the phases with per-column sums apart -- the boundary layer, the convective adjustment and the moist
-    physics, in the model's order in COLUMN_PHASES -- for Core's seven operations on each and for checkpoint.py: the name in the entry
+    """what tells the phases with per-column sums apart -- the boundary layer, the convective adjustment, the Betts-Miller
+    convection and the moist physics, in the model's order in STEP_COLUMN_PHASES (COLUMN_PHASES: the three of them that
+    came first) -- for Core's seven operations on each and for checkpoint.py: the name in the entry
     points and keys, the words of the messages, the ctypes record, the *_params function with its defaults (the record's
     order), the result namedtuple (its last two fields name the sums) and whether *_step takes dt"""
 
@@ -754,7 +824,11 @@ _CONVECT = _ColumnPhase("convect", "convective adjustment", _lib.Convect, convec
 _MOIST = _ColumnPhase("moist", "moist physics", _lib.Moist, moist_params, MOIST_DEFAULTS, Moist, True)
 _BOUNDARY = _ColumnPhase("boundary_layer", "boundary layer", _lib.BoundaryLayer, boundary_layer_params,
                          BOUNDARY_LAYER_DEFAULTS, BoundaryLayer, True)
+_BETTS_MILLER = _ColumnPhase("betts_miller", "Betts-Miller convection", _lib.BettsMiller, betts_miller_params,
+                             BETTS_MILLER_DEFAULTS, BettsMiller, True)
 COLUMN_PHASES = (_BOUNDARY, _CONVECT, _MOIST)
+# every column phase in the order a step applies them: what checkpoint.py walks
+STEP_COLUMN_PHASES = (_BOUNDARY, _CONVECT, _BETTS_MILLER, _MOIST)
 
 
 class _Sampler:
@@ -1196,7 +1270,7 @@ class Core:
     def end_step(self, dt):
         """the end of a GCM_PE25D step whose dynamics the caller took itself (gcm_end_step): every registered phase in
         the order of step() / band_run() -- the solar step at the handle's clock, which advances, Held-Suarez, the
-        boundary layer, the convective adjustment, the moist physics, the climatology's sample where one is due.  half_step(0),
+        boundary layer, the convective adjustment, the Betts-Miller convection, the moist physics, the climatology's sample where one is due.  half_step(0),
         half_step(1), end_step(dt) is step(1, dt).  A band: own rows and ghost rows, the ghost rows must be current; a band
         with the boundary layer registered is refused (GcmError): end_step_begin, exchange, end_step_finish"""
         _check(lib.gcm_end_step(self._h, float(dt)), self._h)
@@ -1589,6 +1663,48 @@ class Core:
     def moist_reset(self):
         """zero the sums, the seconds and the count (gcm_moist_reset)"""
         self._column_reset(_MOIST)
+
+    # -- Betts-Miller convection (GCM_PE25D) ---------------------------------------------------
+    def set_betts_miller(self, *off, **params):
+        """every step of step() / band_run() from now on relaxes every deep-convecting column towards the moist adiabat
+        of a parcel lifted from its lowest level and towards the relative humidity rh_bm on it, over the time tau, with
+        the column's enthalpy conserved and the water taken out falling as convective precipitation
+        (gcm_set_betts_miller: the simplified Betts-Miller scheme) -- behind the convective adjustment and ahead of the
+        moist physics.  params: any of Lv, tau, rh_bm, nsub (BETTS_MILLER_DEFAULTS).  Precipitation and the count of
+        convecting applications are accumulated per column (betts_miller_sums); registering again resets the sums.
+        set_betts_miller(None) switches the phase off.  ValueError for a refused parameter (the call then changes
+        nothing); GcmError where the handle's levels are not supported (L < 2, sig not decreasing, L beyond the
+        kernel's LDS: _lib.BETTS_MILLER_MAX_LEVELS)"""
+        self._set_column(_BETTS_MILLER, off, params)
+
+    @property
+    def betts_miller(self):
+        """the parameters of the registered Betts-Miller convection as a dict, or None where the handle carries none
+        (gcm_betts_miller_on) -- and also None for one registered through the C call directly"""
+        return self._column_params(_BETTS_MILLER)
+
+    @property
+    def betts_miller_registered(self):
+        """whether the handle carries the phase at all (gcm_betts_miller_on), whoever registered it"""
+        return self._column_registered(_BETTS_MILLER)
+
+    def betts_miller_step(self, dt, **params):
+        """the Betts-Miller convection once, in place on the current state, with the step dt (gcm_betts_miller_step).
+        With a registration the call adds to its sums; without one they are dropped.  A band: own rows and ghost rows"""
+        self._column_step(_BETTS_MILLER, dt, params)
+
+    def betts_miller_sums(self):
+        """-> BettsMiller(nsteps, seconds, precip (H, W), count (H, W)): the float64 sums as the device holds them
+        (gcm_get_betts_miller); one synchronisation.  GcmError where no Betts-Miller convection is registered"""
+        return self._column_sums(_BETTS_MILLER)
+
+    def put_betts_miller(self, nsteps, seconds, precip, count):
+        """upload sums taken by betts_miller_sums() (gcm_put_betts_miller): a restart goes on where the run stopped"""
+        self._put_column(_BETTS_MILLER, nsteps, seconds, precip, count)
+
+    def betts_miller_reset(self):
+        """zero the sums, the seconds and the count (gcm_betts_miller_reset)"""
+        self._column_reset(_BETTS_MILLER)
 
     # -- the sampled diagnostics (GCM_PE25D): one implementation for the four, by their _Sampler ----------------------
     def _sampler_every(self, sm):

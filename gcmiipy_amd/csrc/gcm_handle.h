@@ -34,7 +34,7 @@ struct GcmTiming {
 };
 
 // GCM_PE25D: the phases registered behind the dynamics of every step (gcm_pe.hip runs them; the climatology's
-// registration is Pe25d's own, and so are the convective adjustment's and the moist physics': pe25d_sums_on -- mo, cv
+// registration is Pe25d's own, and so are the convective adjustment's, the Betts-Miller convection's and the moist physics': pe25d_sums_on -- mo, cv, bm
 // and bl are the parameters their steps run with).  The records' table pointers are null: the vectors are the copies that are used
 struct GcmPhases {
     bool solar = false;                        // gcm_set_physics: solar_timestep as the second phase of every step
@@ -43,6 +43,7 @@ struct GcmPhases {
     gcm_held_suarez hs{};
     gcm_moist mo{};
     gcm_convect cv{};
+    gcm_betts_miller bm{};
     gcm_boundary_layer bl{};
     std::vector<double> phys_lat, phys_lon, hs_lat;
 };
@@ -153,12 +154,12 @@ extern "C" void step_rows(gcm_handle *h, double dt, int j0, int j1, hipStream_t 
 extern "C" void swap_state(gcm_handle *h);
 extern "C" int launch_status(gcm_handle *h);
 
-// gcm_pe.hip, for gcm_step, gcm_band_run and gcm_end_step: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, boundary layer, convective adjustment, moist physics, the climatology's sample, the pressure-level climatology's sample, the spectra's sample), each
+// gcm_pe.hip, for gcm_step, gcm_band_run and gcm_end_step: the phases of a GCM_PE25D step (solar step, utc += dt, Held-Suarez, boundary layer, convective adjustment, Betts-Miller convection, moist physics, the climatology's sample, the pressure-level climatology's sample, the spectra's sample), each
 // launched only if it is registered -- their tables before a run, a band's ghost rows on its second stream `ax` behind a
 // corrector's unpack, and the end of every step on the handle's stream over rows [-g, H + g), which joins `tail` before a sample
 // The walk splits at the boundary layer (`which`): a band that carries it exchanges the current state's edge rows between
-// kPhasesHead (solar step, clock, Held-Suarez, boundary layer over the own rows) and kPhasesTail (convective adjustment, moist
-// physics, sample); everybody else walks kPhasesAll
+// kPhasesHead (solar step, clock, Held-Suarez, boundary layer over the own rows) and kPhasesTail (convective adjustment,
+// Betts-Miller convection, moist physics, sample); everybody else walks kPhasesAll
 enum { kPhasesHead = 1, kPhasesTail = 2, kPhasesAll = 3 };
 extern "C" int pe_step(gcm_handle *h, int nsteps, double dt);        // gcm_step of a GCM_PE25D handle
 extern "C" int pe_phase_tables(gcm_handle *h, int nsteps, double dt);

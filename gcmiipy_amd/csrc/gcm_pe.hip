@@ -1,6 +1,6 @@
 // GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (horizontal diffusion, solar step, Held-Suarez forcing,
-// boundary layer, convective adjustment, moist physics, climatology sample, pressure-level climatology sample, spectra sample, pressure-level maps sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
-// only (tracers, step phases and halo buffers, ground and physics, horizontal diffusion, Held-Suarez, boundary layer, convective adjustment, moist physics, climatology, pressure levels and their heights and maps, spectra, the filter and the taps).
+// boundary layer, convective adjustment, Betts-Miller convection, moist physics, climatology sample, pressure-level climatology sample, spectra sample, pressure-level maps sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
+// only (tracers, step phases and halo buffers, ground and physics, horizontal diffusion, Held-Suarez, boundary layer, convective adjustment, Betts-Miller convection, moist physics, climatology, pressure levels and their heights and maps, spectra, the filter and the taps).
 // Host code only: a guard and one forwarding call into the pe25d_* units, through gcm_handle.h and pe25d_kernels.h.
 #include <cmath>
 
@@ -15,16 +15,17 @@ using namespace gcm;
 // opted in: its own rows ahead of the walk, with an exchange of the current state's edge rows between the two --
 // pe_band_hdiff_rows), the solar step at the
 // current clock, utc += dt, the Held-Suarez forcing,
-// the boundary layer (on a band: then a third exchange of the edge rows), the convective adjustment, the moist physics,
+// the boundary layer (on a band: then a third exchange of the edge rows), the convective adjustment, the Betts-Miller
+// convection, the moist physics,
 // the climatology's sample, the pressure-level climatology's sample, the spectra's sample, the pressure-level maps' sample.  Each launch runs only if its phase is
-// registered: the diffusion in pe25d_hdiff_on, the solar step and the forcing in GcmPhases, the boundary layer, the adjustment and the moist physics where
+// registered: the diffusion in pe25d_hdiff_on, the solar step and the forcing in GcmPhases, the boundary layer, the adjustment, the Betts-Miller convection and the moist physics where
 // their sums are in place (pe25d_sums_on),
 // the four samples in pe25d_sampler_due.  The order is written down in pe_phase_rows and kPeSamples, and in pe_phase_tables for what a
 // run prepares ahead of it.
 
 // The registered diffusion's device tables and landing fields for dt; gcm_set_physics: the radiation kernel's tables in
 // place before a run queues anything (no-op without physics); then the registered forcing's device tables for dt (none: GCM_OK), the boundary layer's level tables, scratch fields and parameters
-// for dt, and the convective adjustment's and the moist physics' level tables and parameters for dt.  Both parts of a
+// for dt, and the convective adjustment's, the Betts-Miller convection's and the moist physics' level tables and parameters for dt.  Both parts of a
 // split walk (gcm_end_step_begin, gcm_end_step_finish) call it: what is in place for dt already is not built again
 int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
     const GcmPhases &ph = h->phases;
@@ -43,6 +44,8 @@ int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
         if (int rc = pe25d_boundary_layer_tables(h->pe, &ph.bl, dt, h->stream, &h->err)) return rc;
     if (pe25d_sums_on(h->pe, kSumsConvect))
         if (int rc = pe25d_convect_tables(h->pe, &ph.cv, dt, &h->err)) return rc;
+    if (pe25d_sums_on(h->pe, kSumsBettsMiller))
+        if (int rc = pe25d_betts_miller_tables(h->pe, &ph.bm, dt, &h->err)) return rc;
     if (pe25d_sums_on(h->pe, kSumsMoist)) return pe25d_moist_tables(h->pe, &ph.mo, dt, &h->err);
     return GCM_OK;
 }
@@ -112,6 +115,10 @@ static int pe_phase_rows(gcm_handle *h, double dt, int set, int j0, int j1, int 
     // gcm_set_convect: theta and q, ahead of the moist physics, which then condenses whatever the mixing left supersaturated
     if (pe25d_sums_on(h->pe, kSumsConvect))
         if (int rc = pe25d_convect_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, own, s, &h->err)) return rc;
+    // gcm_set_betts_miller: theta and q, behind the adjustment (which has removed what was unstable against its neutral
+    // profile) and ahead of the moist physics, which condenses what the relaxation left supersaturated
+    if (pe25d_sums_on(h->pe, kSumsBettsMiller))
+        if (int rc = pe25d_betts_miller_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, own, s, &h->err)) return rc;
     // gcm_set_moist: theta and q, the last phase of the step that changes the state
     if (pe25d_sums_on(h->pe, kSumsMoist)) return pe25d_moist_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, own, s, &h->err);
     return GCM_OK;
@@ -641,6 +648,59 @@ int gcm_convect_reset(gcm_handle *h) {
 int gcm_convect_columns(int ncol, int L, const double *y, const double *w, const double *q, const double *dsig, int mix_q,
                         double *y_out, double *q_out, int32_t *nblock) {
     return convect_columns(ncol, L, y, w, q, dsig, mix_q, y_out, q_out, nblock, &gcm_create_error());
+}
+
+// ------------------------------------------------------------------ Betts-Miller convection
+int gcm_set_betts_miller(gcm_handle *h, const gcm_betts_miller *bm) {
+    if (int rc = pe_only(h, "gcm_set_betts_miller")) return rc;
+    if (bm)
+        if (int rc = betts_miller_check(bm, "gcm_set_betts_miller", &h->err)) return rc;
+    if (int rc = select_device(h)) return rc;
+    if (bm)
+        if (int rc = pe25d_betts_miller_fits(h->pe, "gcm_set_betts_miller", &h->err)) return rc;
+    if (int rc = pe25d_sums_set(h->pe, kSumsBettsMiller, bm != nullptr, h->stream, &h->err)) return rc;
+    if (bm) h->phases.bm = *bm;
+    return GCM_OK;
+}
+
+int gcm_betts_miller_on(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && pe25d_sums_on(h->pe, kSumsBettsMiller) ? 1 : 0;
+}
+
+int gcm_betts_miller_step(gcm_handle *h, double dt, const gcm_betts_miller *bm) {
+    if (int rc = pe_only(h, "gcm_betts_miller_step")) return rc;
+    if (int rc = betts_miller_check(bm, "gcm_betts_miller_step", &h->err)) return rc;
+    if (!std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_betts_miller_step: dt must be finite");
+    if (int rc = select_device(h)) return rc;
+    if (int rc = pe25d_betts_miller_tables(h->pe, bm, dt, &h->err)) return rc;
+    // a band: own rows and ghost rows, as gcm_moist_step (the ghost rows of the current state must be current); the sums
+    // of the call go to the registration's accumulators, or nowhere.  A host that drives the exchange itself ends its
+    // steps with gcm_end_step, not with this call
+    const int g = phase_ghosts(h);
+    return pe25d_betts_miller_rows(h->pe, -1, -g, h->H + g, 0, 0, false, pe25d_sums_on(h->pe, kSumsBettsMiller), h->stream, &h->err);
+}
+
+int gcm_get_betts_miller(gcm_handle *h, double *precip, double *count, double *seconds, int64_t *nsteps) {
+    if (int rc = pe_on_device(h, "gcm_get_betts_miller")) return rc;
+    return pe25d_sums_get(h->pe, kSumsBettsMiller, precip, count, seconds, nsteps, h->stream, &h->err);
+}
+
+int gcm_put_betts_miller(gcm_handle *h, const double *precip, const double *count, double seconds, int64_t nsteps) {
+    if (int rc = pe_on_device(h, "gcm_put_betts_miller")) return rc;
+    return pe25d_sums_put(h->pe, kSumsBettsMiller, precip, count, seconds, nsteps, h->stream, &h->err);
+}
+
+int gcm_betts_miller_reset(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_betts_miller_reset")) return rc;
+    return pe25d_sums_reset(h->pe, kSumsBettsMiller, h->stream, &h->err);
+}
+
+int gcm_betts_miller_columns(int ncol, int L, const double *p, const double *theta, const double *q, const double *sig,
+                             const double *dsig, double ptop, double dt, const gcm_betts_miller *bm, double *theta_out,
+                             double *q_out, double *precip, int32_t *kt, int32_t *k_lcl, double *margin) {
+    return betts_miller_columns(ncol, L, p, theta, q, sig, dsig, ptop, dt, bm, theta_out, q_out, precip, kt, k_lcl, margin,
+                                &gcm_create_error());
 }
 
 // ------------------------------------------------------------------ moist physics

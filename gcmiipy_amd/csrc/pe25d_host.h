@@ -14,13 +14,14 @@
 //   pe25d_plev_height.hip  geopotential height on pressure levels: the rule's host build, the kernel, the maps' sums
 //   pe25d_moist.hip    moist physics: the saturation routine, the kernel and its launches
 //   pe25d_convect.hip  convective adjustment: the pooling routine, the kernel and its launches
+//   pe25d_betts_miller.hip  Betts-Miller convection: the column routines, the kernel and its launches
 //   pe25d_convect_tracers.hip  the tracers' convective mixing in the adjustment's blocks: the kernel, its launch, the opt-ins
 //   pe25d_boundary_layer.hip  surface fluxes and boundary-layer mixing: the routines, the two kernels and their launches
 //   pe25d_hdiff.hip    horizontal diffusion: the table and cell routines, the tile kernel, its launch and landing fields
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
 // gcm_pe.hip see pe25d_kernels.h only; of these, gcm_pe.hip alone launches the phases behind a step (pe25d_solar_rows,
-// pe25d_hdiff_rows, pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_moist_rows, and behind
+// pe25d_hdiff_rows, pe25d_hs_rows, pe25d_boundary_layer_rows, pe25d_convect_rows, pe25d_betts_miller_rows, pe25d_moist_rows, and behind
 // pe25d_sampler_due the four samples: pe25d_climate_sample, pe25d_plev_climate_sample, pe25d_spectra_sample,
 // pe25d_plev_maps_sample).
 #pragma once
@@ -152,7 +153,8 @@ struct PeColumnSums {
 struct PeSumsWords { const char *name, *what, *a, *b; };   // gcm_set_<name>, "no <what> registered", the two fields
 constexpr PeSumsWords kPeSumsWords[] = {{"convect", "convective adjustment", "count", "levels"},     // kSumsConvect
                                         {"moist", "moist physics", "precip", "evap"},                // kSumsMoist
-                                        {"boundary_layer", "boundary layer", "shf", "evap"}};        // kSumsBoundary
+                                        {"boundary_layer", "boundary layer", "shf", "evap"},         // kSumsBoundary
+                                        {"betts_miller", "Betts-Miller convection", "precip", "count"}};   // kSumsBettsMiller
 // an accumulating launch went out: one application of dt
 inline void sums_count(PeColumnSums &z, double dt) { z.seconds += dt; ++z.n; }
 
@@ -171,6 +173,15 @@ struct PeConvect {
     size_t lds_bytes = 0;                       // the kernel's dynamic LDS at the handle's L; 0: not checked against the device yet
     double kappa_c = 0.0, dt = 0.0;             // the neutral profile (0: dry); what an accumulating launch adds to seconds
     int mix_q = 0;
+};
+
+// Betts-Miller convection (pe25d_betts_miller.hip, gcm_set_betts_miller): the sums (precip, count) and the parameters of
+// the launches that follow (pe25d_betts_miller_tables)
+struct PeBettsMiller {
+    PeColumnSums sums;
+    size_t lds_bytes = 0;                       // the kernel's dynamic LDS at the handle's L; 0: not checked against the handle and the device yet
+    double lc = 0.0, r = 0.0, rh_bm = 0.0, dt = 0.0;   // Lv / Cp, x / (1 + x) with x = dt / tau, rh_bm, dt
+    int nsub = 0;
 };
 
 // Surface fluxes and boundary-layer mixing (pe25d_boundary_layer.hip, gcm_set_boundary_layer): the sums (shf, evap), the
@@ -280,6 +291,7 @@ struct Pe25d {
     PePlev pmaps;
     PeMoist moist;
     PeConvect convect;
+    PeBettsMiller betts_miller;
     PeBoundary boundary;
     PeHdiff hdiff;
 };

@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip, pe25d_plev.hip, pe25d_plev_height.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
+// pe25d_climate.hip, pe25d_plev.hip, pe25d_plev_height.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_betts_miller.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -115,11 +115,11 @@ int pe25d_set_spectra(Pe25d *m, int every, int mmax, hipStream_t s, std::string 
 int pe25d_spectra_mmax(const Pe25d *m);
 int pe25d_spectra_plan(const Pe25d *m, int *out, int nout);
 int pe25d_spectra_sample(Pe25d *m, hipStream_t s, std::string *err);
-// The column sums of the convective adjustment (count, levels), of the moist physics (precip, evap) and of the boundary
-// layer (shf, evap), one set of routines for all (pe25d_state.hip), on `s`, the caller's stream.  pe25d_sums_set: allocated and zeroed (on) or freed;
+// The column sums of the convective adjustment (count, levels), of the moist physics (precip, evap), of the boundary
+// layer (shf, evap) and of the Betts-Miller convection (precip, count), one set of routines for all (pe25d_state.hip), on `s`, the caller's stream.  pe25d_sums_set: allocated and zeroed (on) or freed;
 // a phase is registered where its sums are in place, and pe25d_sums_on is the one place that says so.  reset, get and
 // put are gcm_<phase>_reset, gcm_get_<phase> and gcm_put_<phase>: GCM_ERR_STATE where the phase is not registered
-enum PeSums { kSumsConvect, kSumsMoist, kSumsBoundary };
+enum PeSums { kSumsConvect, kSumsMoist, kSumsBoundary, kSumsBettsMiller };
 int pe25d_sums_set(Pe25d *m, PeSums of, bool on, hipStream_t s, std::string *err);
 bool pe25d_sums_on(const Pe25d *m, PeSums of);
 int pe25d_sums_reset(Pe25d *m, PeSums of, hipStream_t s, std::string *err);
@@ -148,6 +148,21 @@ int pe25d_convect_fits(Pe25d *m, const char *fn, std::string *err);
 int pe25d_convect_tables(Pe25d *m, const gcm_convect *cv, double dt, std::string *err);
 int pe25d_convect_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool accumulate, hipStream_t s,
                        std::string *err);
+// Betts-Miller convection (pe25d_betts_miller.hip).  betts_miller_check / betts_miller_columns: no handle, no device
+// (gcm_betts_miller_columns).  pe25d_betts_miller_fits: ahead of pe25d_sums_set(kSumsBettsMiller, on); GCM_ERR_UNSUPPORTED
+// for L < 2, a sig table that does not strictly decrease and an L whose parked changes do not fit a workgroup's LDS;
+// pe25d_betts_miller_tables: the level tables in place and (bm, dt) as the parameters of the launches that follow;
+// pe25d_betts_miller_rows: the kernel over rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the current one) on `s`;
+// keep_ghosts as for pe25d_solar_rows; accumulate: the own rows' precipitation and counts go to the registered sums and
+// the call counts as one application of dt
+int betts_miller_check(const gcm_betts_miller *bm, const char *fn, std::string *err);
+int betts_miller_columns(int ncol, int L, const double *p, const double *theta, const double *q, const double *sig,
+                         const double *dsig, double ptop, double dt, const gcm_betts_miller *bm, double *theta_out,
+                         double *q_out, double *precip, int32_t *kt, int32_t *k_lcl, double *margin, std::string *err);
+int pe25d_betts_miller_fits(Pe25d *m, const char *fn, std::string *err);
+int pe25d_betts_miller_tables(Pe25d *m, const gcm_betts_miller *bm, double dt, std::string *err);
+int pe25d_betts_miller_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool accumulate,
+                            hipStream_t s, std::string *err);
 // Surface fluxes and boundary-layer mixing (pe25d_boundary_layer.hip).  boundary_layer_check / _surface / _column: no
 // handle, no device (gcm_boundary_layer_surface, gcm_boundary_layer_column).  pe25d_boundary_layer_fits: what a
 // registration or a step needs of the handle -- a single domain or a band that has opted in

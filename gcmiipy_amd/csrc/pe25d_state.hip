@@ -230,7 +230,7 @@ const double *pe25d_level_table(Pe25d *m, const char *who, std::string *err) {
 }
 
 static PeColumnSums &sums_of(Pe25d *m, PeSums of) {
-    return of == kSumsMoist ? m->moist.sums : of == kSumsBoundary ? m->boundary.sums : m->convect.sums;
+    return of == kSumsMoist ? m->moist.sums : of == kSumsBoundary ? m->boundary.sums : of == kSumsBettsMiller ? m->betts_miller.sums : m->convect.sums;
 }
 static size_t sums_words(const Pe25d *m) { return (size_t)m->H * m->W; }
 static int sums_zero(Pe25d *m, PeColumnSums &z, const std::string &fn, hipStream_t s, std::string *err) {

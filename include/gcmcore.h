@@ -716,6 +716,92 @@ int gcm_put_convect(gcm_handle *h, const double *count, const double *levels, do
 int gcm_convect_reset(gcm_handle *h);
 int gcm_convect_columns(int ncol, int L, const double *y, const double *w, const double *q, const double *dsig, int mix_q,
                         double *y_out, double *q_out, int32_t *nblock);
+/* Betts-Miller convection of GCM_PE25D on the device: the simplified Betts-Miller scheme of Frierson (2007).  Every column
+ * relaxes, over the time tau, towards the moist adiabat of a parcel lifted from its lowest level and towards the relative
+ * humidity rh_bm on that adiabat; what the relaxation takes out of q is the convective precipitation, and the reference
+ * temperature is shifted uniformly so that the column's enthalpy is conserved.  One launch per step, fp64 and fp32
+ * handles, single domains and latitude bands.  The reference has nothing of the kind: this is an addition.  Only the
+ * deep-convection case is built: the paper's shallow-convection closures (for columns whose relaxation would make
+ * negative precipitation) and any convective momentum transport are out of scope; such columns are left to the
+ * convective adjustment.  State: p [H][W] in Pa (surface pressure minus ptop), t = theta, q [L][H][W]; tables: sig[k],
+ * dsig[k]; level k = 0 is the bottom and sig must strictly decrease in k.  Constants as for gcm_moist; lc = Lv / Cp;
+ * (q_s, dq_s, can) = the saturation routine of gcm_moist at (T, p), with pd = p / den of that routine.
+ * Arithmetic per column, float64 for either storage type, every operation rounded on its own (no contraction), the
+ * results rounded once to the storage type.  Per level:  p_lev = sig[k] p + ptop;  Pi = (p_lev / P0)^kappa from the
+ * kernels' own Exner routine;  T = theta Pi;  w = (dsig[k] p) / G.
+ * 1. The parcel's ascent, k = 0, 1, ..:
+ *   k = 0:  T_p = T;  the parcel keeps theta_0 = theta[0] and q_0 = q[0];  s = saturation(T_p, p_lev)
+ *   k >= 1, no LCL yet:  T_d = theta_0 Pi;  s = saturation(T_d, p_lev);  T_p = T_d;  where s.q_s <= q_0 (a NaN compares
+ *     false) this level is k_lcl and the parcel takes the moist physics' one linearised condensation step:
+ *       C = (q_0 - s.q_s) / (1 + lc s.dq_s);  T_p = T_d + lc C;  s = saturation(T_p, p_lev)
+ *     (the search starts at level 1: level 0 is where the parcel comes from)
+ *   k > k_lcl: the pseudoadiabat of that q_s, dT/dp = slope(T, p) = (kappa T + (lc q_s) pd) / ((1 + lc dq_s) p) -- which is
+ *     Cp dT - (Rd T / p) dp + Lv dq_s = 0 -- from (T_p[k-1], p_lev[k-1]) to p_lev by nsub explicit midpoint steps of
+ *     h = (p_lev - p_lev[k-1]) / nsub:  T_c = T_p[k-1];  for n = 0 .. nsub - 1:  p_a = p_lev[k-1] + n h;
+ *       f_1 = slope(T_c, p_a);  T_m = T_c + (0.5 h) f_1;  p_m = p_a + 0.5 h;  f_2 = slope(T_m, p_m);  T_c = T_c + h f_2
+ *     then T_p = T_c;  s = saturation(T_p, p_lev).  The count is fixed: no tolerance, no iteration that depends on data.
+ *   Any of these evaluations that cannot saturate ends the ascent below level k.
+ * 2. Cloud top.  At every level k >= k_lcl: buoyant = T_p > T (strict; a NaN compares false).  A buoyant level becomes kt;
+ *   a level that is not buoyant while there is a kt ends the ascent below it: kt is the top of the first contiguous run of
+ *   buoyant levels at or above k_lcl.  A column with no k_lcl or no such run does not convect.
+ * 3, 4. Every level the ascent takes (0 .. kt, and the levels it looked at above in vain):  T_ref = T_p;
+ *   q_ref = rh_bm s.q_s;  x = dt / tau;  r = x / (1 + x) (backward Euler: stable for every dt >= 0; dt is taken as given,
+ *   only a non-finite one is refused);  dq = -r (q - q_ref);  dT = -r (T - T_ref);  running sums from 0.0, in level order:
+ *   P = P - dq w;  S = S + dT w;  M = M + w.  P_q, S_T and M_t are P, S and M as they stand behind level kt.
+ * 5. Deep convection iff there is a kt and P_q > 0 and S_T > 0.  Then  D = (lc P_q - S_T) / (r M_t)  and for k = 0 .. kt:
+ *   theta <- theta + (dT + r D) / Pi;   q <- q + dq.   Every other column is NOT WRITTEN.
+ * Properties: sum_k (Cp dT + Lv dq) w = 0 and sum_k dq w = -P_q over the levels written, to rounding; q stays >= 0 (it
+ * becomes (1 - r) q + r q_ref); p, u, v, the tracers and the ground temperature are untouched.
+ * Accumulators in the handle, allocated by gcm_set_betts_miller, own rows only: precip [H][W], float64, kg / m^2, += P_q,
+ * and count [H][W], float64, += 1, for a column that convected; seconds (the sum of dt) and nsteps.  One writer per word
+ * and launch, no atomics: the same state gives the same bits, and a band's rows hold the bits of the same rows of the
+ * single domain.
+ * gcm_set_betts_miller: the phase as part of every step taken by gcm_step and gcm_band_run: the Matsuno step, the
+ * horizontal diffusion, solar_timestep, the Held-Suarez forcing, the boundary layer, the convective adjustment, each where
+ * registered, then this, then the moist physics where registered (which condenses what the relaxation left
+ * supersaturated), then the samples.  gcm_half_step and gcm_step_phase never apply it.  On a latitude band the ghost rows
+ * that the step's last exchange delivers are relaxed LOCALLY (column-local kernel, the neighbour's own inputs, the
+ * neighbour's own bits) and add to no sum: no further exchange, no opt-in, the message format and gcm_halo_bytes are
+ * unchanged; a band with the boundary layer registered takes the phase in the part of the walk behind its third
+ * exchange.  NULL switches the phase off and frees the accumulators; registering again resets them.  Without a
+ * registration nothing is launched and every result and timing is as before.
+ * gcm_betts_miller_on: 1 where the phase is registered, else 0 (other models: 0; a null handle GCM_ERR_ARG).
+ * gcm_betts_miller_step: the same kernel once, in place on the current state, with the step dt.  With a registration it
+ * adds to the accumulators, to seconds and to nsteps; without one the sums of the call are dropped.  On a band it covers
+ * own rows and ghost rows: the ghost rows must be current.
+ * gcm_get_betts_miller synchronises the handle's stream once; any pointer may be NULL.  gcm_put_betts_miller uploads sums
+ * and counters (restarts): both arrays are required, seconds finite and >= 0, nsteps >= 0.  gcm_betts_miller_reset zeroes
+ * all four.
+ * gcm_betts_miller_columns: the rule above on its own, on the host, without a handle or a device -- the very routines the
+ * kernel calls, compiled for the host -- over ncol columns: p [ncol], theta and q [ncol][L], sig and dsig [L].  theta_out
+ * and q_out [ncol][L] receive the columns as the phase leaves them (unchanged where the column did not convect), precip
+ * [ncol] P_q or 0, kt [ncol] the cloud top or -1 where the column did not convect, k_lcl [ncol] the LCL's level or -1;
+ * any of them may be NULL.  margin [ncol] (may be NULL) is the smallest relative distance of any comparison the column
+ * consulted -- |a - b| / max(|a|, |b|) for q_s <= q_0 at every level searched and for T_p > T at every level tested;
+ * |P_q| / sum |dq w| and |S_T| / sum |dT w| over levels 0 .. kt for the two signs, where there is a kt -- and +infinity
+ * where it consulted none: a column whose margin is far above the rounding of exp keeps its outcome on any device.
+ * The kernel parks dT and dq of a column in LDS, 16 bytes per level and lane of a one-wave workgroup, beside the 2 KB
+ * Exner table: GCM_BETTS_MILLER_MAX_LEVELS levels fill a workgroup's 160 KB.
+ * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, no parameters, a
+ * non-finite parameter or dt, Lv <= 0, tau <= 0, rh_bm outside (0, 1], nsub outside [1, 8]; the probe: ncol < 0, L < 1, a
+ * non-finite ptop, a missing input.  GCM_ERR_UNSUPPORTED: other models, L < 2, a sig table that does not strictly
+ * decrease, L > GCM_BETTS_MILLER_MAX_LEVELS.  GCM_ERR_STATE: get, put or reset without a registration.              */
+#define GCM_BETTS_MILLER_MAX_LEVELS 158
+typedef struct {
+    double Lv;                   /* J / kg: latent heat of vaporisation (2.5e6)                 */
+    double tau;                  /* s: relaxation time, > 0 (7200)                              */
+    double rh_bm;                /* relative humidity of the reference profile, (0, 1] (0.7)    */
+    int nsub;                    /* midpoint steps per level of the pseudoadiabat, [1, 8] (2)   */
+} gcm_betts_miller;
+int gcm_set_betts_miller(gcm_handle *h, const gcm_betts_miller *bm);
+int gcm_betts_miller_on(const gcm_handle *h);
+int gcm_betts_miller_step(gcm_handle *h, double dt, const gcm_betts_miller *bm);
+int gcm_get_betts_miller(gcm_handle *h, double *precip, double *count, double *seconds, int64_t *nsteps);
+int gcm_put_betts_miller(gcm_handle *h, const double *precip, const double *count, double seconds, int64_t nsteps);
+int gcm_betts_miller_reset(gcm_handle *h);
+int gcm_betts_miller_columns(int ncol, int L, const double *p, const double *theta, const double *q, const double *sig,
+                             const double *dsig, double ptop, double dt, const gcm_betts_miller *bm, double *theta_out,
+                             double *q_out, double *precip, int32_t *kt, int32_t *k_lcl, double *margin);
 /* Surface fluxes and boundary-layer mixing of GCM_PE25D on the device: bulk exchange of momentum, heat and moisture with a
  * surface of prescribed temperature (the ground temperature of gcm_set_ground: an ocean, it is read and never changed) and
  * the implicit diffusion that carries the fluxes upwards -- the two parts of Reed & Jablonowski (2012)'s simple physics,
