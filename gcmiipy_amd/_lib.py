@@ -173,6 +173,7 @@ SYMBOLS = {
     "gcm_get_ground": (C.c_int, [_H, C.c_void_p]),
     "gcm_grey_radiation": (C.c_int, [_H] + [C.c_double] * 4 + [_dp, _dp, C.c_void_p, C.c_void_p]),
     "gcm_solar_step": (C.c_int, [_H] + [C.c_double] * 5 + [_dp, _dp]),
+    "gcm_grey_radiation_tables": (C.c_int, [C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int]),
     "gcm_set_physics": (C.c_int, [_H, C.c_void_p]),
     "gcm_get_utc": (C.c_int, [_H, _dp]),
     "gcm_set_held_suarez": (C.c_int, [_H, C.POINTER(HeldSuarez)]),

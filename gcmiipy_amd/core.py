@@ -539,6 +539,34 @@ def held_suarez_tables(sig, lat, dt, **params):
     return dict(fu=fu, kt=kt, s2=s2, c2=c2)
 
 
+def grey_params(t_lw=0.1, t_sw=0.9, albedo=0.3, **clock):
+    """the three parameters of the grey radiation as floats, and the clock values `clock` (utc, dt) checked with them:
+    t_lw and t_sw in (0, 1], albedo in [0, 1], the clock finite -- what gcm_grey_radiation, gcm_solar_step and
+    gcm_set_physics accept, said without a handle.  ValueError otherwise (NaN included).  What depends on the levels
+    (a transmissivity so small that a level's share rounds to 0) is left to the library"""
+    t_lw, t_sw, albedo = float(t_lw), float(t_sw), float(albedo)
+    for name, x in (("t_lw", t_lw), ("t_sw", t_sw)):
+        if not (0.0 < x <= 1.0):
+            raise ValueError("grey radiation: %s must lie in (0, 1], got %r" % (name, x))
+    if not (0.0 <= albedo <= 1.0):
+        raise ValueError("grey radiation: albedo must lie in [0, 1], got %r" % albedo)
+    for name, x in clock.items():
+        if not np.isfinite(float(x)):
+            raise ValueError("grey radiation: %s must be finite, got %r" % (name, x))
+    return t_lw, t_sw, albedo
+
+
+def grey_radiation_tables(dsig, sig, t_lw=0.1, t_sw=0.9):
+    """the level tables of the radiation kernel (gcm_grey_radiation_tables; no handle, no device) for the levels dsig, sig
+    (L,) -> dict(tlw, tsw, csw_top, clw_b_div, swfac, sigk), each (L,): the routine the launches of Core.grey_radiation,
+    Core.solar_step and Core.set_physics take their tables from.  ValueError for a refused parameter"""
+    dsig = as_f64(np.asarray(dsig, dtype=np.float64).reshape(-1), name="dsig")
+    sig = as_f64(np.asarray(sig, dtype=np.float64).reshape(-1), (dsig.size,), "sig")
+    out = np.empty((6, dsig.size))
+    _check(lib.gcm_grey_radiation_tables(dsig.size, _tab(dsig), _tab(sig), float(t_lw), float(t_sw), _tab(out), out.size))
+    return dict(zip(("tlw", "tsw", "csw_top", "clw_b_div", "swfac", "sigk"), out))
+
+
 # the parameters of the moist physics (gcm_moist), in the struct's order: the latent heat (J / kg), the evaporation time
 # scale (s; 0: no evaporation) and the target relative humidity of the lowest level
 MOIST_DEFAULTS = collections.OrderedDict(Lv=2.5e6, tau_e=0.0, rh_s=0.8)
@@ -1368,7 +1396,9 @@ class Core:
         return lat, lon
 
     def grey_radiation(self, geom, utc, t_lw=0.1, t_sw=0.9, albedo=0.3):
-        """-> (dTdt [L,H,W], dt_ground [H,W]), grey_solar.basic_grey_radiation"""
+        """-> (dTdt [L,H,W], dt_ground [H,W]), grey_solar.basic_grey_radiation.  ValueError for a refused parameter
+        (grey_params; the call then changes nothing)"""
+        t_lw, t_sw, albedo = grey_params(t_lw, t_sw, albedo, utc=utc)
         lat, lon = self._latlon(geom)
         dT, dg = np.empty((self.L, self.H, self.W)), np.empty((self.H, self.W))
         _check(lib.gcm_grey_radiation(self._h, float(utc), t_lw, t_sw, albedo, _tab(lat), _tab(lon),
@@ -1376,6 +1406,9 @@ class Core:
         return dT, dg
 
     def solar_step(self, geom, dt, utc, t_lw=0.1, t_sw=0.9, albedo=0.3):
+        """no_limits_2_5d.solar_timestep in place.  ValueError for a refused parameter (grey_params; the call then
+        changes nothing)"""
+        t_lw, t_sw, albedo = grey_params(t_lw, t_sw, albedo, utc=utc, dt=dt)
         lat, lon = self._latlon(geom)
         _check(lib.gcm_solar_step(self._h, float(dt), float(utc), t_lw, t_sw, albedo, _tab(lat),
                                   _tab(lon)), self._h)
@@ -1384,10 +1417,12 @@ class Core:
         """every step of step() / band_run() / end_step() from now on = the dynamics step followed by
         no_limits_2_5d.solar_timestep at the handle's clock, which then advances by dt (run_model's loop,
         no_limits_2_5d.py:229-234).  That clock, utc(), is the only one: whoever drives the steps, it starts at `utc`
-        and counts every one of them.  geom=None switches the physics off (gcm_set_physics)"""
+        and counts every one of them.  geom=None switches the physics off (gcm_set_physics).  ValueError for a refused
+        parameter (grey_params; the registration in place, if any, then stays as it is)"""
         if geom is None:
             _check(lib.gcm_set_physics(self._h, None), self._h)
             return
+        t_lw, t_sw, albedo = grey_params(t_lw, t_sw, albedo, utc=utc)
         lat, lon = self._latlon(geom)
         ph = _lib.Physics(float(utc), t_lw, t_sw, albedo, _tab(lat), _tab(lon))
         _check(lib.gcm_set_physics(self._h, C.byref(ph)), self._h)

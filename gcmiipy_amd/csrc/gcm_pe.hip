@@ -396,6 +396,9 @@ int gcm_set_physics(gcm_handle *h, const gcm_physics *ph) {
         return GCM_OK;
     }
     if (!ph->lat || !ph->lon) return fail(h, GCM_ERR_ARG, "gcm_set_physics: lat and lon tables are required");
+    // a refused registration changes nothing: the one in place, its clock and its parameters stay
+    if (int rc = pe25d_grey_check(h->pe, ph->t_lw, ph->t_sw, ph->albedo, "gcm_set_physics", &h->err)) return rc;
+    if (!std::isfinite(ph->utc)) return fail(h, GCM_ERR_ARG, "gcm_set_physics: utc must be finite");
     p.phys = *ph;
     p.phys_lat.assign(ph->lat, ph->lat + h->cfg.global_height);
     p.phys_lon.assign(ph->lon, ph->lon + h->W);
@@ -414,6 +417,8 @@ int gcm_get_utc(gcm_handle *h, double *utc) {
 int gcm_grey_radiation(gcm_handle *h, double utc, double t_lw, double t_sw, double albedo,
                        const double *lat, const double *lon, double *dTdt, double *dt_ground) {
     if (int rc = pe_only(h, "gcm_grey_radiation")) return rc;
+    if (int rc = pe25d_grey_check(h->pe, t_lw, t_sw, albedo, "gcm_grey_radiation", &h->err)) return rc;
+    if (!std::isfinite(utc)) return fail(h, GCM_ERR_ARG, "gcm_grey_radiation: utc must be finite");
     return pe25d_radiation(h->pe, false, 0.0, utc, t_lw, t_sw, albedo, lat, lon, dTdt, dt_ground,
                            h->stream, &h->err);
 }
@@ -421,8 +426,15 @@ int gcm_grey_radiation(gcm_handle *h, double utc, double t_lw, double t_sw, doub
 int gcm_solar_step(gcm_handle *h, double dt, double utc, double t_lw, double t_sw, double albedo,
                    const double *lat, const double *lon) {
     if (int rc = pe_only(h, "gcm_solar_step")) return rc;
+    if (int rc = pe25d_grey_check(h->pe, t_lw, t_sw, albedo, "gcm_solar_step", &h->err)) return rc;
+    if (!std::isfinite(utc) || !std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_solar_step: dt and utc must be finite");
     return pe25d_radiation(h->pe, true, dt, utc, t_lw, t_sw, albedo, lat, lon, nullptr, nullptr,
                            h->stream, &h->err);
+}
+
+int gcm_grey_radiation_tables(int L, const double *dsig, const double *sig, double t_lw, double t_sw, double *out, int nout) {
+    if (L >= 1 && nout < 6 * L) return fail(nullptr, GCM_ERR_ARG, "gcm_grey_radiation_tables: out holds fewer than 6 L doubles");
+    return grey_radiation_tables(L, dsig, sig, t_lw, t_sw, out, &gcm_create_error());
 }
 
 // ------------------------------------------------------------------ horizontal diffusion

@@ -43,6 +43,12 @@ int pe25d_filter_field(Pe25d *m, int nlev, const double *in, double *out, hipStr
 int pe25d_radiation(Pe25d *m, bool apply, double dt, double utc, double t_lw, double t_sw, double albedo,
                     const double *lat, const double *lon, double *dTdt_host, double *dtg_host,
                     hipStream_t s, std::string *err);
+// grey_check: the accepted parameters (GCM_ERR_ARG and "<fn>: <what>" otherwise; dsig may be null: the levels'
+// transmissivities are then not checked); grey_radiation_tables: gcm_grey_radiation_tables (no handle, no device), the
+// builder pe25d_physics_tables uploads from
+int grey_check(int L, const double *dsig, double t_lw, double t_sw, double albedo, const char *fn, std::string *err);
+int grey_radiation_tables(int L, const double *dsig, const double *sig, double t_lw, double t_sw, double *out, std::string *err);
+int pe25d_grey_check(const Pe25d *m, double t_lw, double t_sw, double albedo, const char *fn, std::string *err);
 int pe25d_physics_tables(Pe25d *m, double t_lw, double t_sw, const double *lat, const double *lon, hipStream_t s,
                          std::string *err);
 int pe25d_solar_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, double dt, double utc, double albedo,

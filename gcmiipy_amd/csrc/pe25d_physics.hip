@@ -12,6 +12,7 @@ template <typename T>
 struct RadArgsT {
     const double *tlw, *tsw, *csw_top, *clw_b_div, *swfac;   // [L] level tables (host-built)
     const double *sigk;                                      // [L] sig^kappa (FACT, see pe_radiation_kernel)
+    const double *sig, *dsig;                                // [L] the handle's float64 level table (pe25d_level_table)
     const double *coslat, *sinlat, *lon;                     // [Hg], [Hg], [W]
     double *gt;                                              // ground temperature [H][W]
     T *dTdt, *dtg;                                           // tendencies out of the diagnostic form (3-D, 2-D scratch)
@@ -21,8 +22,10 @@ struct RadArgsT {
                                                              // rows on either side in one launch: negative / >= H)
 };
 
-// The arithmetic is float64 for either storage type T: the column physics is a small share of a
-// step, and the fp32 variant then differs from fp64 only by the rounding of what it stores.
+// The arithmetic is float64 for either storage type T, and so is every table the kernel reads -- the level tables
+// below and sig / dsig, which come from the handle's float64 level table, not from the T copies the dynamics use: the
+// column physics is a small share of a step, and the fp32 variant then differs from fp64 only by the rounding of what
+// it stores (p, theta, and the diagnostic form's dTdt and dt_ground; the ground temperature is float64 on either).
 // One thread per column.  The long-wave absorption needs the upwelling flux from BELOW a level and
 // the downwelling flux from ABOVE it, two opposite scans: the bottom-up scan parks one value per
 // level (the absorbed upwelling) and the top-down scan recomputes the level's emission from theta
@@ -49,7 +52,7 @@ __global__ __launch_bounds__(kRadThreads) void pe_radiation_kernel(PeArgsT<T> a,
         for (int k = threadIdx.x; k < LMAX; k += kRadThreads) {
             const int kk = min(k, L - 1);
             lev[0][k] = r.tlw[kk]; lev[1][k] = r.clw_b_div[kk]; lev[2][k] = r.swfac[kk];
-            lev[3][k] = (double)a.sig[kk]; lev[4][k] = (double)a.dsig[kk];
+            lev[3][k] = r.sig[kk]; lev[4][k] = r.dsig[kk];
             if (FACT) lev[5][k] = r.sigk[kk];
         }
     }
@@ -80,8 +83,8 @@ __global__ __launch_bounds__(kRadThreads) void pe_radiation_kernel(PeArgsT<T> a,
     const auto tlw = [&](int k) { return LMAX > 0 ? lev[0][k] : r.tlw[k]; };
     const auto clw = [&](int k) { return LMAX > 0 ? lev[1][k] : r.clw_b_div[k]; };
     const auto swf = [&](int k) { return LMAX > 0 ? lev[2][k] : r.swfac[k]; };
-    const auto sig = [&](int k) { return LMAX > 0 ? lev[3][k] : (double)a.sig[k]; };
-    const auto dsg = [&](int k) { return LMAX > 0 ? lev[4][k] : (double)a.dsig[k]; };
+    const auto sig = [&](int k) { return LMAX > 0 ? lev[3][k] : r.sig[k]; };
+    const auto dsg = [&](int k) { return LMAX > 0 ? lev[4][k] : r.dsig[k]; };
     const double ex_col = FACT ? exner(pc, tab) : 0.0;
     const auto exk = [&](int k) { return FACT ? ex_col * lev[5][LMAX > 0 ? k : 0] : exner(pc * sig(k) + ptop, tab); };
     // true temperature and emission of one level (to_true_temp; grey_solar.py emission)
@@ -168,6 +171,7 @@ static int radiation_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1,
     r.j0 = j0; r.n0 = std::max(0, j1 - j0); r.jb0 = jb0;
     r.tlw = m->rad_tab; r.tsw = r.tlw + L; r.csw_top = r.tsw + L; r.clw_b_div = r.csw_top + L; r.swfac = r.clw_b_div + L;
     r.sigk = r.swfac + L;
+    r.sig = m->lev_tab; r.dsig = m->lev_tab + L;
     r.coslat = m->rad_geo; r.sinlat = m->rad_geo + Hg; r.lon = m->rad_geo + 2 * Hg;
     r.gt = m->gt;
     r.dTdt = B.pgfu; r.dtg = B.pit;
@@ -199,35 +203,72 @@ static int radiation_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1,
     return GCM_OK;
 }
 
+// gcm_grey_radiation, gcm_solar_step, gcm_set_physics and gcm_grey_radiation_tables: the parameters the radiation
+// accepts.  t_lw and t_sw, the transmissivities of the whole column, lie in (0, 1]; albedo in [0, 1].  dsig (may be
+// null: not checked): no level's transmissivity t^dsig[k] may round to 0 -- the level tables divide by it (t_lw = 0:
+// clw_b_div = 0 / 0, as in the reference's own formula; t_lw = 1e-300: 1 - (1 - t^dsig) = 0 in every level)
+int grey_check(int L, const double *dsig, double t_lw, double t_sw, double albedo, const char *fn, std::string *err) {
+    const auto bad = [&](const char *what) { *err = std::string(fn) + ": " + what; return GCM_ERR_ARG; };
+    if (!(t_lw > 0.0 && t_lw <= 1.0)) return bad("t_lw must lie in (0, 1]");
+    if (!(t_sw > 0.0 && t_sw <= 1.0)) return bad("t_sw must lie in (0, 1]");
+    if (!(albedo >= 0.0 && albedo <= 1.0)) return bad("albedo must lie in [0, 1]");
+    for (int k = 0; dsig && k < L; ++k) {
+        if (!(dsig[k] > 0.0) || !std::isfinite(dsig[k])) return bad("dsig must be positive and finite");
+        if (!(1 - (1 - std::pow(t_lw, dsig[k])) > 0.0)) return bad("t_lw is too small: a level's long-wave transmissivity rounds to 0");
+        if (!(1 - (1 - std::pow(t_sw, dsig[k])) > 0.0)) return bad("t_sw is too small: a level's short-wave transmissivity rounds to 0");
+    }
+    return GCM_OK;
+}
+
+// grey_check on the handle's own levels
+int pe25d_grey_check(const Pe25d *m, double t_lw, double t_sw, double albedo, const char *fn, std::string *err) {
+    return grey_check(m->L, m->dsig_host.data(), t_lw, t_sw, albedo, fn, err);
+}
+
+// The level tables of the radiation kernel for (t_lw, t_sw), out[6][L]: tlw, tsw, csw_top, clw_b_div, swfac, sig^kappa --
+// what pe25d_physics_tables uploads and what gcm_grey_radiation_tables returns (no handle, no device).  Same expression
+// order as grey_solar.py:323-333,377-385,541; sig^kappa in extended precision (FACT)
+int grey_radiation_tables(int L, const double *dsig, const double *sig, double t_lw, double t_sw, double *out, std::string *err) {
+    const char *fn = "gcm_grey_radiation_tables";
+    const auto bad = [&](const char *what) { *err = std::string(fn) + ": " + what; return GCM_ERR_ARG; };
+    if (L < 1) return bad("L must be 1 or more");
+    if (!dsig || !sig || !out) return bad("a null pointer");
+    if (int rc = grey_check(L, dsig, t_lw, t_sw, 0.0, fn, err)) return rc;
+    for (int k = 0; k < L; ++k)
+        if (!(sig[k] > 0.0) || !std::isfinite(sig[k])) return bad("sig must be positive and finite");
+    double *tlw = out, *tsw = tlw + L, *csw = tsw + L, *cdiv = csw + L, *swf = cdiv + L;
+    for (int k = 0; k < L; ++k) {
+        tlw[k] = 1 - (1 - std::pow(t_lw, dsig[k]));
+        tsw[k] = 1 - (1 - std::pow(t_sw, dsig[k]));
+    }
+    double c = 1.0;
+    for (int k = L - 1; k >= 0; --k) { c = k == L - 1 ? tsw[k] : c * tsw[k]; csw[k] = c; }
+    for (int k = 0; k < L; ++k) { c = k == 0 ? tlw[k] : c * tlw[k]; cdiv[k] = c / tlw[k]; }
+    for (int k = 0; k < L; ++k) swf[k] = (1 - tsw[k]) * csw[k] / tsw[k];
+    for (int k = 0; k < L; ++k) swf[L + k] = (double)powl((long double)sig[k], (long double)kKappa);   // sig^kappa (FACT)
+    return GCM_OK;
+}
+
 // the level tables (t_lw, t_sw) and the lat / lon tables of the radiation kernel, uploaded when they change
 int pe25d_physics_tables(Pe25d *m, double t_lw, double t_sw, const double *lat, const double *lon, hipStream_t s,
                          std::string *err) {
     if (!m->gt_set) { *err = "radiation: set the ground temperature first (gcm_set_ground)"; return GCM_ERR_STATE; }
     if (!lat || !lon) { *err = "radiation: lat and lon tables are required"; return GCM_ERR_ARG; }
     const int W = m->W, L = m->L, Hg = m->Hg;
+    if (!pe25d_level_table(m, "radiation", err)) return GCM_ERR_HIP;      // sig and dsig in float64, for either storage type
     bool uploaded = false;
     if (m->rad_key[0] != t_lw || m->rad_key[1] != t_sw || !m->rad_tab) {
-        // level tables, same expression order as grey_solar.py:323-333,377-385,541
-        std::vector<double> &T = m->rad_tab_host;
-        T.assign((size_t)6 * L, 0.0);
-        const std::vector<double> &dsig = m->dsig_host;
-        double *tlw = T.data(), *tsw = tlw + L, *csw = tsw + L, *cdiv = csw + L, *swf = cdiv + L;
-        for (int k = 0; k < L; ++k) {
-            tlw[k] = 1 - (1 - std::pow(t_lw, dsig[k]));
-            tsw[k] = 1 - (1 - std::pow(t_sw, dsig[k]));
-        }
-        double c = 1.0;
-        for (int k = L - 1; k >= 0; --k) { c = k == L - 1 ? tsw[k] : c * tsw[k]; csw[k] = c; }
-        for (int k = 0; k < L; ++k) { c = k == 0 ? tlw[k] : c * tlw[k]; cdiv[k] = c / tlw[k]; }
-        for (int k = 0; k < L; ++k) swf[k] = (1 - tsw[k]) * csw[k] / tsw[k];
-        for (int k = 0; k < L; ++k) swf[L + k] = (double)powl((long double)m->sig_host[k], (long double)kKappa);   // sig^kappa (FACT)
+        // the tables are built aside: a refused pair leaves the ones in place, and their key, as they were
+        std::vector<double> fresh((size_t)6 * L, 0.0);
+        if (int rc = grey_radiation_tables(L, m->dsig_host.data(), m->sig_host.data(), t_lw, t_sw, fresh.data(), err)) return rc;
         if (!m->rad_tab && !dev_upload<double>(m, &m->rad_tab, nullptr, (size_t)6 * L)) {
             *err = "hip: radiation table allocation failed"; return GCM_ERR_HIP;
         }
         // the host copy lives in the handle until the next change, so the asynchronous upload may
         // read it after this call returns; a change waits for the previous upload first
-        if (hipStreamSynchronize(s) != hipSuccess ||
-            hipMemcpyAsync(m->rad_tab, T.data(), sizeof(double) * 6 * L, hipMemcpyHostToDevice, s) != hipSuccess) {
+        if (hipStreamSynchronize(s) != hipSuccess) { *err = "hip: radiation table upload failed"; return GCM_ERR_HIP; }
+        m->rad_tab_host.swap(fresh);
+        if (hipMemcpyAsync(m->rad_tab, m->rad_tab_host.data(), sizeof(double) * 6 * L, hipMemcpyHostToDevice, s) != hipSuccess) {
             *err = "hip: radiation table upload failed"; return GCM_ERR_HIP;
         }
         m->rad_key[0] = t_lw; m->rad_key[1] = t_sw;

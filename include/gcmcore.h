@@ -490,7 +490,18 @@ int gcm_energy(gcm_handle *h, const double *area, int area_len, double *out4);
  *   gcm_grey_radiation  grey_solar.basic_grey_radiation(p,tp,tt,g,t_lw,t_sw,albedo,utc,geom)
  *                       -> dTdt [L][H][W], dt_ground [H][W] (either may be NULL)  grey_solar.py:358-563
  *   gcm_solar_step      no_limits_2_5d.solar_timestep: theta and gt advanced in place by dt
- *                       (the reference passes t_lw = 0.1, t_sw = 0.9, albedo = 0.3)  no_limits_2_5d.py:66-75 */
+ *                       (the reference passes t_lw = 0.1, t_sw = 0.9, albedo = 0.3)  no_limits_2_5d.py:66-75
+ * Accepted by these two, by gcm_set_physics and by gcm_grey_radiation_tables: t_lw and t_sw, the transmissivities of the
+ * whole column, in (0, 1] and large enough that no level's share t^dsig[k] rounds to 0 (the level tables divide by it:
+ * t_lw = 0 gives 0 / 0 in the reference's own formula); albedo in [0, 1]; utc and dt finite.  Anything else, NaN
+ * included, is GCM_ERR_ARG, and the refused call changes nothing: state, ground temperature, registration, clock and the
+ * level tables in place stay.  The kernel's arithmetic and every table it reads are float64 on either handle: an fp32
+ * handle differs from an fp64 one by the rounding of what it stores (p, theta, dTdt, dt_ground), not by its levels.
+ *   gcm_grey_radiation_tables  (no handle, no device) the level tables the kernel reads for (t_lw, t_sw) on the levels
+ *                       dsig[L], sig[L], exactly as they are uploaded: out[6][L] = the levels' long-wave and short-wave
+ *                       transmissivities t^dsig, the short-wave product from the top down to the level, the long-wave
+ *                       product from the bottom up to the level over the level's own, (1 - tsw) csw / tsw, and
+ *                       sig^kappa (formed in extended precision); nout >= 6 L doubles in out       grey_solar.py:323-333 */
 /* low_pass.arakawa_1977(q, geom) (low_pass.py:41-78) on its own, GCM_PE25D handles: the zonal Fourier
  * damping of nlev <= layers levels of a field on the handle's grid, host [nlev][H][W] float64 in and
  * out (may alias).  Rows are filtered with the multiplier of their global latitude.              */
@@ -512,6 +523,7 @@ int gcm_grey_radiation(gcm_handle *h, double utc, double t_lw, double t_sw, doub
                        const double *lat, const double *lon, double *dTdt, double *dt_ground);
 int gcm_solar_step(gcm_handle *h, double dt, double utc, double t_lw, double t_sw, double albedo,
                    const double *lat, const double *lon);
+int gcm_grey_radiation_tables(int L, const double *dsig, const double *sig, double t_lw, double t_sw, double *out, int nout);
 /* The column physics as the second phase of every step (BASELINE configs[4]: dynamics + solar_timestep;
  * the loop of no_limits_2_5d.run_model, :229-234, with the physics the reference keeps below
  * full_timestep's early return, :94-96).  After gcm_set_physics every step taken by gcm_step and
