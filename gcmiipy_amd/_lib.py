@@ -113,6 +113,14 @@ class BoundaryLayer(C.Structure):
                 ("p_pbl", C.c_double), ("p_strat", C.c_double)]
 
 
+class SlabOcean(C.Structure):
+    """gcm_slab_ocean of include/gcmcore.h"""
+    _fields_ = [("heat_capacity", C.c_double), ("Lv", C.c_double)]
+
+
+SLAB_WORDS, SLAB_SUMS = 7, 10                # GCM_SLAB_WORDS, GCM_SLAB_SUMS
+
+
 class Convect(C.Structure):
     """gcm_convect of include/gcmcore.h"""
     _fields_ = [("kappa_c", C.c_double), ("mix_q", C.c_int32)]
@@ -206,6 +214,14 @@ SYMBOLS = {
     "gcm_boundary_layer_reset": (C.c_int, [_H]),
     "gcm_boundary_layer_surface": (C.c_int, [C.c_int, C.POINTER(BoundaryLayer), C.c_double, C.c_double] + [_dp] * 8),
     "gcm_boundary_layer_column": (C.c_int, [C.c_int, C.c_int] + [_dp] * 7),
+    "gcm_set_slab_ocean": (C.c_int, [_H, C.POINTER(SlabOcean), _dp, _dp]),
+    "gcm_slab_ocean_on": (C.c_int, [_H]),
+    "gcm_slab_ocean_apply": (C.c_int, [_H, C.c_double, C.POINTER(SlabOcean), _dp]),
+    "gcm_get_slab_ocean_fluxes": (C.c_int, [_H, _dp]),
+    "gcm_get_slab_ocean": (C.c_int, [_H, _dp, _dp, C.POINTER(C.c_int64)]),
+    "gcm_put_slab_ocean": (C.c_int, [_H, _dp, C.c_double, C.c_int64]),
+    "gcm_slab_ocean_reset": (C.c_int, [_H]),
+    "gcm_slab_ocean_cells": (C.c_int, [C.c_int, C.POINTER(SlabOcean), C.c_double] + [_dp] * 6),
     "gcm_set_convect": (C.c_int, [_H, C.POINTER(Convect)]),
     "gcm_convect_on": (C.c_int, [_H]),
     "gcm_convect_step": (C.c_int, [_H, C.POINTER(Convect)]),

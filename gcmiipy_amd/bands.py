@@ -303,6 +303,22 @@ def merge_boundary_layer(parts):
     return _merge_column(_BOUNDARY, parts)
 
 
+def merge_slab_ocean(parts):
+    """the slab ocean's sums of the whole domain from its bands': `parts` are the bands' SlabOcean records
+    (Core.slab_ocean_sums) in row order; the rows are concatenated.  ValueError where nsteps, seconds or the reflected
+    share differ"""
+    import numpy as np
+    from .core import SlabOcean
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_slab_ocean: no records")
+    if any(m.nsteps != parts[0].nsteps or m.seconds != parts[0].seconds or m.reflect != parts[0].reflect for m in parts):
+        raise ValueError("merge_slab_ocean: the bands hold %s applications over %s seconds (reflected share %s)"
+                         % (", ".join(str(m.nsteps) for m in parts), ", ".join(repr(m.seconds) for m in parts),
+                            ", ".join(repr(m.reflect) for m in parts)))
+    return SlabOcean(parts[0].nsteps, parts[0].seconds, np.concatenate([m.sums for m in parts], axis=1), parts[0].reflect)
+
+
 def merge_convect(parts):
     """the convective adjustment's sums of the whole domain from its bands': `parts` are the bands' Convect records
     (Core.convect_sums) in row order; the rows are concatenated.  ValueError where nsteps or seconds differ"""
@@ -406,6 +422,11 @@ class HipBandEngine:
         """Core.set_boundary_layer (the band was created with band_boundary_layer=True); every band of a run registers the
         same.  merge_boundary_layer() puts the bands' sums together"""
         self.c.set_boundary_layer(*off, **params)
+
+    def set_slab_ocean(self, *off, **params):
+        """Core.set_slab_ocean (capacity and qflux: the band's own rows); every band of a run registers the same
+        parameters.  merge_slab_ocean() puts the bands' sums together"""
+        self.c.set_slab_ocean(*off, **params)
 
     def set_convect(self, *off, **params):
         """Core.set_convect; every band of a run registers the same.  merge_convect() puts the bands' sums together"""

@@ -41,14 +41,17 @@ convective adjustment, in the model's order (behind the ground temperature, whic
 Betts-Miller convection, Core.set_betts_miller, is stored as "betts_miller", its four parameters in the order of
 core.BETTS_MILLER_DEFAULTS, with "betts_miller_n", "betts_miller_seconds", "betts_miller_precip" and "betts_miller_count",
 saved the same way and restored between the convective adjustment and the moist physics; files without these keys
-restore with none)
+restore with none; the slab ocean, Core.set_slab_ocean, is stored as "slab_ocean", its two parameters in the order of
+core.SLAB_OCEAN_DEFAULTS, with "slab_ocean_n", "slab_ocean_seconds", "slab_ocean_sums", the raw float64 sums, and, where
+registered, the fields "slab_ocean_capacity" and "slab_ocean_qflux", registered and uploaded again directly behind the
+boundary layer; files without the key restore with none)
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
 import numpy as np
 
 from . import _lib
-from .core import Core, GcmError, HDIFF_DEFAULTS, HELD_SUAREZ_DEFAULTS, SAMPLERS, STEP_COLUMN_PHASES
+from .core import Core, GcmError, HDIFF_DEFAULTS, HELD_SUAREZ_DEFAULTS, SAMPLERS, SLAB_OCEAN_DEFAULTS, STEP_COLUMN_PHASES
 from .geometry import Geom
 
 _GEOM_KEYS = ("sige", "sigt", "sigb", "dsig", "sig", "dsigv", "dx_j", "dx_h", "dy", "ptop",
@@ -111,6 +114,19 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
             out[ph.name] = np.asarray([par[k] for k in ph.defaults], dtype=np.float64)
             out[ph.name + "_n"], out[ph.name + "_seconds"] = np.int64(sums.nsteps), np.float64(sums.seconds)
             out.update({"%s_%s" % (ph.name, f): getattr(sums, f) for f in ph.fields})
+    # (getattr: a stand-in without the slab ocean will do)
+    slab = getattr(core, "slab_ocean", None) if core.model == _lib.PE25D else None
+    if slab is None and getattr(core, "slab_ocean_registered", False):
+        raise GcmError("checkpoint.save: the handle's slab ocean was registered through gcm_set_slab_ocean directly; its "
+                       "parameters are unknown here and the phase and its sums would be lost (register with Core.set_slab_ocean)")
+    if slab is not None:
+        sums = core.slab_ocean_sums()
+        out["slab_ocean"] = np.asarray([slab[k] for k in SLAB_OCEAN_DEFAULTS], dtype=np.float64)
+        out["slab_ocean_n"], out["slab_ocean_seconds"] = np.int64(sums.nsteps), np.float64(sums.seconds)
+        out["slab_ocean_sums"] = sums.sums
+        for k in ("capacity", "qflux"):
+            if slab[k] is not None:
+                out["slab_ocean_" + k] = slab[k]
     for k, a in zip("puvtq", (p, u, v, t, q)):
         if a is not None:
             out["state_" + k] = a
@@ -185,7 +201,14 @@ def load(path):
             par = {k: type(v)(x) for (k, v), x in zip(ph.defaults.items(), d[ph.name])}
             column[ph.name] = dict(params=par, n=int(d[ph.name + "_n"]), seconds=float(d[ph.name + "_seconds"]),
                                    **{f: d["%s_%s" % (ph.name, f)] for f in ph.fields})
+    slab = None
+    if "slab_ocean" in d.files:
+        slab = dict(params=dict(zip(SLAB_OCEAN_DEFAULTS, (float(x) for x in d["slab_ocean"]))), n=int(d["slab_ocean_n"]),
+                    seconds=float(d["slab_ocean_seconds"]), sums=d["slab_ocean_sums"],
+                    capacity=d["slab_ocean_capacity"] if "slab_ocean_capacity" in d.files else None,
+                    qflux=d["slab_ocean_qflux"] if "slab_ocean_qflux" in d.files else None)
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, hdiff=hd, **sampled,
+                slab_ocean=slab,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
@@ -230,4 +253,8 @@ def restore(path, **core_kwargs):
         if rec is not None:
             getattr(core, "set_" + ph.name)(**rec["params"])
             getattr(core, "put_" + ph.name)(rec["n"], rec["seconds"], *[rec[f] for f in ph.fields])
+        if ph.name == "boundary_layer" and ck["slab_ocean"] is not None:      # (the model's order: behind the boundary layer)
+            rec = ck["slab_ocean"]
+            core.set_slab_ocean(capacity=rec["capacity"], qflux=rec["qflux"], **rec["params"])
+            core.put_slab_ocean(rec["n"], rec["seconds"], rec["sums"])
     return core, ck

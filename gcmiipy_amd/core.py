@@ -676,6 +676,93 @@ def boundary_layer_column(dsig, a, x, target, X):
     return out.reshape(X.shape), x0.reshape(X.shape[:-1])
 
 
+# the parameters of the slab mixed-layer ocean (gcm_slab_ocean), in the struct's order: the heat capacity of the slab,
+# J m^-2 K^-1 (1.0e7: Frierson's 2.4 m of water; inf: a prescribed temperature), and the latent heat, J / kg
+SLAB_OCEAN_DEFAULTS = collections.OrderedDict(heat_capacity=1.0e7, Lv=2.5e6)
+# the flux words of a cell (GCM_SLAB_*) and the sums (the order of gcm_get_slab_ocean)
+SLAB_OCEAN_WORDS = ("SC", "SW_SFC", "LW_DOWN", "LW_UP", "OLR", "SH_J", "EVAP_KG")
+SLAB_OCEAN_SUMS = ("dt_SC", "dt_S", "dt_B", "dt_Us", "dt_OLR", "SH_J", "Lv_EVAP_KG", "dt_Q", "dt_gt", "dt_gt2")
+
+
+def slab_ocean_params(params):
+    """the two parameters of the slab ocean as a dict of floats: SLAB_OCEAN_DEFAULTS with `params` laid over them;
+    ValueError for a name that is not a parameter"""
+    unknown = sorted(set(params) - set(SLAB_OCEAN_DEFAULTS))
+    if unknown:
+        raise ValueError("slab_ocean: unknown parameter(s) %s; the parameters are %s"
+                         % (", ".join(unknown), ", ".join(SLAB_OCEAN_DEFAULTS)))
+    out = collections.OrderedDict(SLAB_OCEAN_DEFAULTS)
+    out.update({k: float(v) for k, v in params.items()})
+    return out
+
+
+class SlabOcean(collections.namedtuple("SlabOcean", "nsteps seconds sums reflect")):
+    """the sums of a GCM_PE25D handle's slab ocean (Core.slab_ocean_sums): the applications counted, the sum of their dt
+    in seconds, the raw float64 sums (10, H, W) in the order of SLAB_OCEAN_SUMS, and `reflect` = albedo csw_top[0] of the
+    registered physics, the share of the insolation the surface sends back to space (0 without physics).  The properties
+    are time means over `seconds`, W / m^2 and positive in the direction their name says; ValueError where seconds == 0.
+    A band: its own rows (bands.merge_slab_ocean)"""
+    __slots__ = ()
+
+    def _mean(self, n):
+        if self.seconds == 0:
+            raise ValueError("SlabOcean: no time accumulated (seconds == 0)")
+        return self.sums[n] / self.seconds
+
+    insolation = property(lambda self: self._mean(0), doc="the sun at the top of the atmosphere, SC")
+    sw_surface = property(lambda self: self._mean(1), doc="short wave absorbed by the surface, S")
+    lw_down = property(lambda self: self._mean(2), doc="long wave reaching the surface, B")
+    lw_up = property(lambda self: self._mean(3), doc="long wave leaving the surface, U_s")
+    olr = property(lambda self: self._mean(4), doc="outgoing long wave at the top")
+    shf = property(lambda self: self._mean(5), doc="sensible heat the surface gave the air")
+    lhf = property(lambda self: self._mean(6), doc="latent heat the surface gave the air, Lv times the evaporation")
+    qflux = property(lambda self: self._mean(7), doc="the prescribed ocean heat flux into the slab")
+
+    @property
+    def asr(self):
+        """short wave absorbed by the column: SC - albedo SC csw_top[0]"""
+        return self.insolation - self.reflect * self.insolation
+
+    @property
+    def surface_net(self):
+        """what the slab gains: ((S + B) - U_s) - shf - lhf + qflux"""
+        return ((self.sw_surface + self.lw_down) - self.lw_up) - self.shf - self.lhf + self.qflux
+
+    @property
+    def toa_net(self):
+        """what the column gains at the top: asr - olr"""
+        return self.asr - self.olr
+
+    @property
+    def sst_mean(self):
+        """the time mean of the slab's temperature, K"""
+        return self._mean(8)
+
+    @property
+    def sst_variance(self):
+        """the time variance of the slab's temperature, K^2: mean(gt^2) - mean(gt)^2"""
+        m = self._mean(8)
+        return self._mean(9) - m * m
+
+
+def slab_ocean_cells(gt, words, dt, capacity=None, qflux=None, **params):
+    """the cell rule of the slab ocean (gcm_slab_ocean_cells; the host build of the routine the kernel calls, no handle,
+    no device) for cells gt of any shape with the flux words `words` (7, ...) in the order of SLAB_OCEAN_WORDS, the step
+    dt, and per cell the heat capacity (None: the scalar heat_capacity) and the ocean heat flux (None: 0)
+    -> (gt_out, E4): the new temperature and the energy the step gave the cell, J / m^2.  ValueError for a refused
+    parameter"""
+    gt = np.asarray(gt, dtype=np.float64)
+    g = as_f64(gt.reshape(-1), name="gt")
+    w = as_f64(np.asarray(words, dtype=np.float64).reshape(_lib.SLAB_WORDS, -1), (_lib.SLAB_WORDS, g.size), "words")
+    opt = [None if a is None else as_f64(np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), gt.shape)).reshape(-1), name=n)
+           for a, n in ((capacity, "capacity"), (qflux, "qflux"))]
+    rec = _lib.SlabOcean(*slab_ocean_params(params).values())
+    out, e4 = np.empty(g.size), np.empty(g.size)
+    _check(lib.gcm_slab_ocean_cells(g.size, C.byref(rec), float(dt), _tab(g), None if opt[0] is None else _tab(opt[0]), _tab(w),
+                                    None if opt[1] is None else _tab(opt[1]), _tab(out), _tab(e4)))
+    return out.reshape(gt.shape), e4.reshape(gt.shape)
+
+
 def aquaplanet_sst(lat, dT=29.0, T_min=271.0, width=np.deg2rad(26.0)):
     """the prescribed sea-surface temperature of the moist Held-Suarez test (Thatcher & Jablonowski 2016) at the
     latitudes `lat` (radians), K: dT exp(-lat^2 / (2 width^2)) + T_min, width in radians (26 degrees).  What set_ground
@@ -970,6 +1057,9 @@ class Core:
         self._held_suarez = None                # the parameters and latitudes registered (set_held_suarez)
         self._hdiff = None                      # the parameters registered (set_horizontal_diffusion)
         self._column = {}                       # the parameters registered (set_boundary_layer, set_convect, set_moist), by the phase's name
+        self._slab = None                       # the parameters and fields registered (set_slab_ocean)
+        self._phys = None                       # t_lw, t_sw, albedo registered (set_physics): the slab ocean's ASR
+        self._sigma_levels = None                     # GCM_PE25D: (sig, dsig) of the geometry
         cfg = _lib.Config()
         cfg.abi_version = _lib.ABI_VERSION
         cfg.model = model
@@ -1003,6 +1093,7 @@ class Core:
             cfg.dx_j, cfg.dx_h = tab(geom.dx_j, gh), tab(geom.dx_h, gh)
             cfg.sig, cfg.dsig = tab(geom.sig, self.L), tab(geom.dsig, self.L)
             cfg.sigb, cfg.sigt = tab(geom.sigb, self.L), tab(geom.sigt, self.L)
+            self._sigma_levels = (self._keep[-4], self._keep[-3])
             cfg.heightmap = tab(geom.heightmap, gh * self.W)
             if coriolis:
                 from .geometry import coriolis_tables
@@ -1421,11 +1512,13 @@ class Core:
         parameter (grey_params; the registration in place, if any, then stays as it is)"""
         if geom is None:
             _check(lib.gcm_set_physics(self._h, None), self._h)
+            self._phys = None
             return
         t_lw, t_sw, albedo = grey_params(t_lw, t_sw, albedo, utc=utc)
         lat, lon = self._latlon(geom)
         ph = _lib.Physics(float(utc), t_lw, t_sw, albedo, _tab(lat), _tab(lon))
         _check(lib.gcm_set_physics(self._h, C.byref(ph)), self._h)
+        self._phys = dict(t_lw=t_lw, t_sw=t_sw, albedo=albedo)
 
     # -- Held-Suarez forcing (GCM_PE25D) ---------------------------------------------------
     def _hs_lat(self, geom):
@@ -1611,6 +1704,87 @@ class Core:
     def boundary_layer_reset(self):
         """zero the sums, the seconds and the count (gcm_boundary_layer_reset)"""
         self._column_reset(_BOUNDARY)
+
+    # -- slab mixed-layer ocean (GCM_PE25D) --------------------------------------------------
+    def _slab_field(self, a, name):
+        return None if a is None else as_f64(np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (self.H, self.W))),
+                                             (self.H, self.W), name)
+
+    def set_slab_ocean(self, *off, heat_capacity=1.0e7, Lv=2.5e6, capacity=None, qflux=None):
+        """every step of step() / band_run() / end_step() from now on advances the ground temperature as a slab mixed-layer
+        ocean on the device (gcm_set_slab_ocean; set_ground first), directly behind the boundary layer: the slab of heat
+        capacity heat_capacity (J m^-2 K^-1; inf: a prescribed temperature) gains the net radiation at the surface, pays
+        for the sensible heat and the evaporation the boundary layer takes from it (Lv, J / kg) and receives the ocean heat
+        flux qflux (W / m^2).  capacity, qflux: fields (H, W) or None.  While it is registered the solar step leaves the
+        ground temperature to it and records the surface and top-of-atmosphere fluxes (slab_ocean_fluxes, slab_ocean_sums);
+        registering again resets the sums.  set_slab_ocean(None) switches the phase off, and the solar step advances the
+        ground temperature by the reference's rule again.  The scheme is explicit: keep dt (4 sigma T^3 + bulk
+        coefficients) / heat_capacity << 1.  ValueError for a refused parameter, GcmError for a handle without a ground
+        temperature (the call then changes nothing)"""
+        if off:
+            if off != (None,):
+                raise ValueError("set_slab_ocean takes keyword parameters, or None alone to switch the phase off")
+            _check(lib.gcm_set_slab_ocean(self._h, None, None, None), self._h)
+            self._slab = None
+            return
+        par = slab_ocean_params(dict(heat_capacity=heat_capacity, Lv=Lv))
+        cap, qf = self._slab_field(capacity, "capacity"), self._slab_field(qflux, "qflux")
+        rec = _lib.SlabOcean(*par.values())
+        _check(lib.gcm_set_slab_ocean(self._h, C.byref(rec), None if cap is None else _tab(cap), None if qf is None else _tab(qf)),
+               self._h)
+        self._slab = dict(par, capacity=None if cap is None else cap.copy(), qflux=None if qf is None else qf.copy())
+
+    @property
+    def slab_ocean(self):
+        """the registered slab ocean as a dict (heat_capacity, Lv, capacity, qflux: the fields or None), or None where the
+        handle carries none (gcm_slab_ocean_on) -- and also None for one registered through the C call directly"""
+        slab = getattr(self, "_slab", None)
+        return dict(slab) if self.slab_ocean_registered and slab else None
+
+    @property
+    def slab_ocean_registered(self):
+        """whether the handle carries the phase at all (gcm_slab_ocean_on), whoever registered it"""
+        return bool(_count(lib.gcm_slab_ocean_on(self._h), self._h))
+
+    def slab_ocean_apply(self, dt, words, heat_capacity=1.0e7, Lv=2.5e6):
+        """the slab's cell rule once on the own rows, in place on the ground temperature, with the step dt and the flux
+        words `words` (7, H, W) in the order of SLAB_OCEAN_WORDS (gcm_slab_ocean_apply); the registered capacity and
+        heat-flux fields apply.  With a registration the call adds to its sums, without one nothing is summed"""
+        w = as_f64(words, (_lib.SLAB_WORDS, self.H, self.W), "words")
+        rec = _lib.SlabOcean(*slab_ocean_params(dict(heat_capacity=heat_capacity, Lv=Lv)).values())
+        _check(lib.gcm_slab_ocean_apply(self._h, float(dt), C.byref(rec), _tab(w)), self._h)
+
+    def slab_ocean_fluxes(self):
+        """-> the flux words of the last step (or slab_ocean_apply), (7, H, W) float64 in the order of SLAB_OCEAN_WORDS:
+        W / m^2, SH_J in J / m^2 and EVAP_KG in kg / m^2 over the step (gcm_get_slab_ocean_fluxes); one synchronisation"""
+        out = np.empty((_lib.SLAB_WORDS, self.H, self.W))
+        _check(lib.gcm_get_slab_ocean_fluxes(self._h, _tab(out)), self._h)
+        return out
+
+    def _slab_reflect(self):
+        """albedo csw_top[0] of the physics registered through set_physics, 0 without"""
+        phys = getattr(self, "_phys", None)
+        if not phys or getattr(self, "_sigma_levels", None) is None:
+            return 0.0
+        sig, dsig = self._sigma_levels
+        return phys["albedo"] * float(grey_radiation_tables(dsig, sig, phys["t_lw"], phys["t_sw"])["csw_top"][0])
+
+    def slab_ocean_sums(self):
+        """-> SlabOcean(nsteps, seconds, sums (10, H, W), reflect): the float64 sums as the device holds them
+        (gcm_get_slab_ocean) and the time means they give; one synchronisation.  GcmError where no slab ocean is registered"""
+        sums = np.empty((_lib.SLAB_SUMS, self.H, self.W))
+        sec, n = C.c_double(), C.c_int64()
+        _check(lib.gcm_get_slab_ocean(self._h, _tab(sums), C.byref(sec), C.byref(n)), self._h)
+        return SlabOcean(int(n.value), float(sec.value), sums, self._slab_reflect())
+
+    def put_slab_ocean(self, nsteps, seconds, sums):
+        """upload sums taken by slab_ocean_sums() (gcm_put_slab_ocean): a restart goes on where the run stopped"""
+        s = as_f64(sums, (_lib.SLAB_SUMS, self.H, self.W), "sums")
+        _check(lib.gcm_put_slab_ocean(self._h, _tab(s), float(seconds), int(nsteps)), self._h)
+
+    def slab_ocean_reset(self):
+        """zero the sums, the seconds and the count (gcm_slab_ocean_reset)"""
+        _check(lib.gcm_slab_ocean_reset(self._h), self._h)
 
     # -- convective adjustment (GCM_PE25D) -------------------------------------------------
     def set_convect(self, *off, **params):

@@ -1,5 +1,5 @@
 // GCM_PE25D behind the C ABI: the phases registered behind the dynamics of every step (horizontal diffusion, solar step, Held-Suarez forcing,
-// boundary layer, convective adjustment, Betts-Miller convection, moist physics, climatology sample, pressure-level climatology sample, spectra sample, pressure-level maps sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
+// boundary layer, slab ocean, convective adjustment, Betts-Miller convection, moist physics, climatology sample, pressure-level climatology sample, spectra sample, pressure-level maps sample), written down once for gcm_step, gcm_band_run and gcm_end_step, and the entry points that serve GCM_PE25D handles
 // only (tracers, step phases and halo buffers, ground and physics, horizontal diffusion, Held-Suarez, boundary layer, convective adjustment, Betts-Miller convection, moist physics, climatology, pressure levels and their heights and maps, spectra, the filter and the taps).
 // Host code only: a guard and one forwarding call into the pe25d_* units, through gcm_handle.h and pe25d_kernels.h.
 #include <cmath>
@@ -15,7 +15,8 @@ using namespace gcm;
 // opted in: its own rows ahead of the walk, with an exchange of the current state's edge rows between the two --
 // pe_band_hdiff_rows), the solar step at the
 // current clock, utc += dt, the Held-Suarez forcing,
-// the boundary layer (on a band: then a third exchange of the edge rows), the convective adjustment, the Betts-Miller
+// the boundary layer, the slab ocean (gcm_set_slab_ocean: pe25d_slab_ocean_on) (on a band with the boundary layer: then
+// a third exchange of the edge rows), the convective adjustment, the Betts-Miller
 // convection, the moist physics,
 // the climatology's sample, the pressure-level climatology's sample, the spectra's sample, the pressure-level maps' sample.  Each launch runs only if its phase is
 // registered: the diffusion in pe25d_hdiff_on, the solar step and the forcing in GcmPhases, the boundary layer, the adjustment, the Betts-Miller convection and the moist physics where
@@ -109,6 +110,22 @@ static int pe_phase_rows(gcm_handle *h, double dt, int set, int j0, int j1, int 
                 HIPCHK(h, hipStreamWaitEvent(s, h->band.ev_comm, 0));
             }
             if (int rc = pe25d_boundary_layer_rows(h->pe, set, keep_ghosts, own, s, &h->err)) return rc;
+        }
+        // gcm_set_slab_ocean, the end of the head, directly behind the boundary layer: the ground temperature from the
+        // flux words the solar step's BUDGET launch and the boundary layer have just stored over the same rows (a phase
+        // that is not registered: its words count as zero).  Column-local: the rows as they come, own rows and a band's
+        // ghost rows alike, the latter to the neighbour's bits and without sums -- but the own rows only on a band with
+        // the boundary layer registered, whose ghost rows have no SH_J and EVAP_KG: their ground temperature arrives
+        // with the third exchange, whose message carries it.  The launch writes the ground temperature, the words and
+        // the sums, no state field: nothing of the stage's bookkeeping changes
+        if (pe25d_slab_ocean_on(h->pe)) {
+            const bool bl = pe25d_sums_on(h->pe, kSumsBoundary);
+            const bool band_bl = bl && !h->wrap;
+            if (own || !band_bl) {
+                const int r0 = band_bl ? std::max(j0, 0) : j0, r1 = band_bl ? std::min(j1, h->H) : j1;
+                if (int rc = pe25d_slab_ocean_rows(h->pe, r0, r1, band_bl ? 0 : jb0, band_bl ? 0 : jb1, dt, ph.solar, bl, own, s, &h->err))
+                    return rc;
+            }
         }
     }
     if (!(which & kPhasesTail)) return GCM_OK;
@@ -609,6 +626,48 @@ int gcm_boundary_layer_surface(int n, const gcm_boundary_layer *bl, double ptop,
 int gcm_boundary_layer_column(int ncol, int L, const double *dsig, const double *a, const double *x, const double *target,
                               const double *X, double *X_out, double *X0_surface) {
     return boundary_layer_column(ncol, L, dsig, a, x, target, X, X_out, X0_surface, &gcm_create_error());
+}
+
+// ------------------------------------------------------------------ slab mixed-layer ocean
+// no ground temperature set: refused in the call itself
+int gcm_set_slab_ocean(gcm_handle *h, const gcm_slab_ocean *so, const double *capacity, const double *qflux) {
+    if (int rc = pe_on_device(h, "gcm_set_slab_ocean")) return rc;
+    return pe25d_set_slab_ocean(h->pe, so, capacity, qflux, h->stream, &h->err);
+}
+
+int gcm_slab_ocean_on(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && pe25d_slab_ocean_on(h->pe) ? 1 : 0;
+}
+
+int gcm_slab_ocean_apply(gcm_handle *h, double dt, const gcm_slab_ocean *so, const double *words) {
+    if (int rc = pe_on_device(h, "gcm_slab_ocean_apply")) return rc;
+    return pe25d_slab_ocean_apply(h->pe, dt, so, words, h->stream, &h->err);
+}
+
+int gcm_get_slab_ocean_fluxes(gcm_handle *h, double *words) {
+    if (int rc = pe_on_device(h, "gcm_get_slab_ocean_fluxes")) return rc;
+    return pe25d_slab_ocean_fluxes(h->pe, words, h->stream, &h->err);
+}
+
+int gcm_get_slab_ocean(gcm_handle *h, double *sums, double *seconds, int64_t *nsteps) {
+    if (int rc = pe_on_device(h, "gcm_get_slab_ocean")) return rc;
+    return pe25d_slab_ocean_get(h->pe, sums, seconds, nsteps, h->stream, &h->err);
+}
+
+int gcm_put_slab_ocean(gcm_handle *h, const double *sums, double seconds, int64_t nsteps) {
+    if (int rc = pe_on_device(h, "gcm_put_slab_ocean")) return rc;
+    return pe25d_slab_ocean_put(h->pe, sums, seconds, nsteps, h->stream, &h->err);
+}
+
+int gcm_slab_ocean_reset(gcm_handle *h) {
+    if (int rc = pe_on_device(h, "gcm_slab_ocean_reset")) return rc;
+    return pe25d_slab_ocean_reset(h->pe, h->stream, &h->err);
+}
+
+int gcm_slab_ocean_cells(int n, const gcm_slab_ocean *so, double dt, const double *gt, const double *C, const double *words,
+                         const double *Q, double *gt_out, double *E4_out) {
+    return slab_ocean_cells(n, so, dt, gt, C, words, Q, gt_out, E4_out, &gcm_create_error());
 }
 
 // ------------------------------------------------------------------ convective adjustment

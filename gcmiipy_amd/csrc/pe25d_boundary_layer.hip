@@ -174,6 +174,7 @@ struct BlArgsT {
     double *cd, *r, *e;              // scratch: [j][i], [j][i], [j][L-1][i]; a band: H + 1 rows of each
     double *park;                    // L > kBlLdsLevels: kBlParkFields fields [j][L][i] of H rows; else null (LDS)
     double *shf, *evap;              // [H][W], or null: the launch accumulates nothing
+    double *sh_j, *evap_kg;          // [j][i], or null: the slab ocean's flux words SH_J and EVAP_KG (pe25d_slab_ocean.hip)
     BlPar par;
     double ptop, dt, dtch, dtce;     // dt ch, dt ce
     int W, H, L;
@@ -231,6 +232,12 @@ __global__ __launch_bounds__(kBlLanes) void pe_bl_theta_q_kernel(BlArgsT<T> a) {
         const double mass = (a.dsig[0] * pc) / kG;
         a.shf[c2] = a.shf[c2] + ((kCp * pi_a) * (th0n - th0)) * mass;
         a.evap[c2] = a.evap[c2] + (q0n - q0) * mass;
+    }
+    if (a.sh_j) {
+        // the slab ocean is registered: the step's own increments of shf and evap, the same expressions, J / m^2 and kg / m^2
+        const double mass = (a.dsig[0] * pc) / kG;
+        a.sh_j[c2] = ((kCp * pi_a) * (th0n - th0)) * mass;
+        a.evap_kg[c2] = (q0n - q0) * mass;
     }
     // the march up: level kk with theta of level kk + 1 in hand (e of the interface above it, from the state at entry)
     double th_c = th0, pi_c = pi_a;                      // level kk as it came in
@@ -416,6 +423,8 @@ static int bl_launch(Pe25d *m, int set, bool accumulate, hipStream_t s, std::str
     a.park = lds ? nullptr : a.e + centres * (size_t)(m->L - 1);
     a.shf = accumulate ? z.sums.acc : nullptr;
     a.evap = accumulate ? z.sums.acc + cells : nullptr;
+    a.sh_j = pe25d_slab_ocean_word(m, GCM_SLAB_SH_J);     // (null without the slab ocean)
+    a.evap_kg = pe25d_slab_ocean_word(m, GCM_SLAB_EVAP_KG);
     a.par = bl_par(&z.par);
     a.ptop = m->cfg.ptop; a.dt = z.dt; a.dtch = z.dt * z.par.ch; a.dtce = z.dt * z.par.ce;
     a.W = m->W; a.H = m->H; a.L = m->L;

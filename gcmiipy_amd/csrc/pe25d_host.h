@@ -17,6 +17,7 @@
 //   pe25d_betts_miller.hip  Betts-Miller convection: the column routines, the kernel and its launches
 //   pe25d_convect_tracers.hip  the tracers' convective mixing in the adjustment's blocks: the kernel, its launch, the opt-ins
 //   pe25d_boundary_layer.hip  surface fluxes and boundary-layer mixing: the routines, the two kernels and their launches
+//   pe25d_slab_ocean.hip  the slab mixed-layer ocean: the cell routine's probe, the kernel, its launches, words and sums
 //   pe25d_hdiff.hip    horizontal diffusion: the table and cell routines, the tile kernel, its launch and landing fields
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
@@ -195,6 +196,19 @@ struct PeBoundary {
     double dt = 0.0;
 };
 
+// Slab mixed-layer ocean (pe25d_slab_ocean.hip, gcm_set_slab_ocean): the registration and its parameters, the float64
+// flux words the radiation's BUDGET launch and the boundary layer store while it is registered, the optional fields and
+// the sums with their two counters.  Everything is allocated by the registration (the words also by gcm_slab_ocean_apply)
+struct PeSlab {
+    bool on = false;                            // gcm_set_slab_ocean: registered
+    gcm_slab_ocean par{};
+    double *words = nullptr;                    // device: GCM_SLAB_WORDS fields [H + 2 kGhost][W], from ghost row -kGhost
+    double *sums = nullptr;                     // device: GCM_SLAB_SUMS fields [H][W]
+    double *cap = nullptr, *qflux = nullptr;    // device: [H][W], or null (the scalar heat capacity; no heat flux)
+    double seconds = 0.0;                       // sum of dt over the applications in the sums
+    long long n = 0;                            // applications in the sums
+};
+
 // Horizontal diffusion (pe25d_hdiff.hip, gcm_set_hdiff): the registration, the device tables of the last (parameters,
 // dt) a launch was asked for -- `key`, compared on every step as PeHeldSuarez's -- and the landing fields the launch
 // writes, own rows [H][L][W] in the handle's real type, one per state field that was ever selected; they stay until
@@ -293,6 +307,7 @@ struct Pe25d {
     PeConvect convect;
     PeBettsMiller betts_miller;
     PeBoundary boundary;
+    PeSlab slab;
     PeHdiff hdiff;
 };
 

@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip, pe25d_plev.hip, pe25d_plev_height.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_betts_miller.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
+// pe25d_climate.hip, pe25d_plev.hip, pe25d_plev_height.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_betts_miller.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip, pe25d_slab_ocean.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -192,6 +192,28 @@ int pe25d_boundary_layer_fits(Pe25d *m, const char *fn, std::string *err);
 int pe25d_boundary_layer_scratch(Pe25d *m, bool on, hipStream_t s, std::string *err);
 int pe25d_boundary_layer_tables(Pe25d *m, const gcm_boundary_layer *bl, double dt, hipStream_t s, std::string *err);
 int pe25d_boundary_layer_rows(Pe25d *m, int set, bool keep_ghosts, bool accumulate, hipStream_t s, std::string *err);
+// Slab mixed-layer ocean (pe25d_slab_ocean.hip).  slab_ocean_check / slab_ocean_cells: no handle, no device
+// (gcm_slab_ocean_cells).  pe25d_set_slab_ocean: gcm_set_slab_ocean (so == nullptr: off, words, sums and fields freed;
+// GCM_ERR_STATE without a ground temperature); pe25d_slab_ocean_on: the registration, the one place that says so;
+// pe25d_slab_ocean_word: flux word n (GCM_SLAB_*) at interior row 0, null without a registration -- what the radiation's
+// launch and the boundary layer's store into; pe25d_slab_ocean_rows: the registered slab over rows [j0, j1) and
+// [jb0, jb1) on `s` with the step dt, `radiation` / `boundary`: whether that phase stored its words in this step (else
+// they count, and are stored, as zero), accumulate: the own rows' terms go to the sums and the call counts as one
+// application of dt; apply, fluxes, get, put and reset are gcm_slab_ocean_apply, gcm_get_slab_ocean_fluxes,
+// gcm_get_slab_ocean, gcm_put_slab_ocean and gcm_slab_ocean_reset
+int slab_ocean_check(const gcm_slab_ocean *so, const char *fn, std::string *err);
+int slab_ocean_cells(int n, const gcm_slab_ocean *so, double dt, const double *gt, const double *C, const double *words,
+                     const double *Q, double *gt_out, double *E4_out, std::string *err);
+int pe25d_set_slab_ocean(Pe25d *m, const gcm_slab_ocean *so, const double *cap, const double *qflux, hipStream_t s, std::string *err);
+bool pe25d_slab_ocean_on(const Pe25d *m);
+double *pe25d_slab_ocean_word(const Pe25d *m, int n);
+int pe25d_slab_ocean_rows(Pe25d *m, int j0, int j1, int jb0, int jb1, double dt, bool radiation, bool boundary, bool accumulate,
+                          hipStream_t s, std::string *err);
+int pe25d_slab_ocean_apply(Pe25d *m, double dt, const gcm_slab_ocean *so, const double *words, hipStream_t s, std::string *err);
+int pe25d_slab_ocean_fluxes(Pe25d *m, double *words, hipStream_t s, std::string *err);
+int pe25d_slab_ocean_get(Pe25d *m, double *sums, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err);
+int pe25d_slab_ocean_put(Pe25d *m, const double *sums, double seconds, int64_t nsteps, hipStream_t s, std::string *err);
+int pe25d_slab_ocean_reset(Pe25d *m, hipStream_t s, std::string *err);
 // Horizontal diffusion (pe25d_hdiff.hip).  hdiff_check / hdiff_tables / hdiff_apply: no handle, no device
 // (gcm_hdiff_tables, gcm_hdiff_apply).  pe25d_hdiff_fits: what a registration or a step needs of the handle -- a single
 // domain, W >= 4 and H >= 4, or a band that has opted in (GCM_ERR_UNSUPPORTED); pe25d_set_hdiff: gcm_set_hdiff (d == nullptr: off, the landing fields

@@ -20,6 +20,11 @@ struct RadArgsT {
     int apply;                                               // 1: t, gt updated in place
     int j0, n0, jb0;                                         // rows of the launch: [j0, j0 + n0), then from jb0 on (a band's ghost
                                                              // rows on either side in one launch: negative / >= H)
+    // BUDGET only (the slab ocean is registered, pe25d_slab_ocean.hip): the flux words SC, SW_SFC, LW_DOWN, LW_UP, OLR,
+    // `bud_stride` words apart, at interior row 0; tcol: the long-wave transmissivity of the whole column
+    double *bud;
+    long bud_stride;
+    double tcol;
 };
 
 // The arithmetic is float64 for either storage type T, and so is every table the kernel reads -- the level tables
@@ -38,8 +43,13 @@ struct RadArgsT {
 // three evaluations per level (emission in either scan, to_potential_temp); sig^kappa comes from the host in
 // extended precision.  The product differs from the direct evaluation by an ulp or two of a factor that enters
 // theta -> T -> theta symmetrically, far inside the 1e-10 of the parity tests (golden g13, the 2880x1440x40 strips).
+// BUDGET (launched only while the slab ocean is registered, always in place): the ground temperature is left to the slab
+// (pe_slab_ocean_kernel); in place of its update the lane stores the column's five flux words in W / m^2 -- SC = Sc,
+// SW_SFC = S, LW_DOWN = B, LW_UP = U_s and OLR = up + U_s tcol, `up` the bottom-up scan's value above the last level.
+// theta takes the very statements of the other instantiations, which the flag does not touch: they compile to the code
+// they compiled to without it.
 constexpr int kRadTabs = 7;      // per level: tlw, clw_b_div, swfac, sig, dsig, sig^kappa, (free)
-template <typename T, int LMAX, bool FACT = false>
+template <typename T, int LMAX, bool FACT = false, bool BUDGET = false>
 __global__ __launch_bounds__(kRadThreads) void pe_radiation_kernel(PeArgsT<T> a, RadArgsT<T> r, T *t_inout) {
     __shared__ double tab[kExnerTabDoubles];
     __shared__ double lev[kRadTabs][LMAX > 0 ? LMAX : 1];
@@ -109,7 +119,13 @@ __global__ __launch_bounds__(kRadThreads) void pe_radiation_kernel(PeArgsT<T> a,
         up = up * tlw(k) + em;
     }
     const double dtg = (B + S - U_s) / kCg / (.1);
-    if (r.apply) r.gt[c2] = gt + dtg * r.dt;
+    if (BUDGET) {
+        r.bud[c2] = Sc;
+        r.bud[c2 + r.bud_stride] = S;
+        r.bud[c2 + 2 * r.bud_stride] = B;
+        r.bud[c2 + 3 * r.bud_stride] = U_s;
+        r.bud[c2 + 4 * r.bud_stride] = up + U_s * r.tcol;
+    } else if (r.apply) r.gt[c2] = gt + dtg * r.dt;
     else r.dtg[c2] = (T)dtg;
     double down = 0.0;
 #pragma unroll kUnroll
@@ -137,7 +153,9 @@ __global__ __launch_bounds__(kRadThreads) void pe_radiation_kernel(PeArgsT<T> a,
 // pe25d_create: the dynamic LDS size of the LDS-parked form
 bool radiation_lds_attribute(const Pe25d *m) {
     const int bytes = (int)(sizeof(double) * (size_t)m->L * kRadThreads);
-    return hipFuncSetAttribute(m->f32 ? (const void *)pe_radiation_kernel<float, 0> : (const void *)pe_radiation_kernel<double, 0>,
+    if (hipFuncSetAttribute(m->f32 ? (const void *)pe_radiation_kernel<float, 0> : (const void *)pe_radiation_kernel<double, 0>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+    return hipFuncSetAttribute(m->f32 ? (const void *)pe_radiation_kernel<float, 0, false, true> : (const void *)pe_radiation_kernel<double, 0, false, true>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
 }
 
@@ -154,13 +172,27 @@ int pe25d_ground(Pe25d *m, bool set, const double *in, double *out, hipStream_t 
     return GCM_OK;
 }
 
+// the one place that picks the instantiation: by L, the GENERIC switch and ptop, with or without BUDGET
+template <typename T, bool BUDGET>
+static void radiation_dispatch(const Pe25d *m, const dim3 &gg, const PeArgsT<T> &a, const RadArgsT<T> &r, T *th, hipStream_t s) {
+    const int L = m->L;
+    const bool generic = m->rad_generic;
+    const bool fact = m->cfg.ptop == 0.0 && r.sigk != nullptr;
+    if (L <= 24 && !generic && fact) hipLaunchKernelGGL((pe_radiation_kernel<T, 24, true, BUDGET>), gg, dim3(kRadThreads), 0, s, a, r, th);
+    else if (L <= 40 && !generic && fact) hipLaunchKernelGGL((pe_radiation_kernel<T, 40, true, BUDGET>), gg, dim3(kRadThreads), 0, s, a, r, th);
+    else if (L <= 24 && !generic) hipLaunchKernelGGL((pe_radiation_kernel<T, 24, false, BUDGET>), gg, dim3(kRadThreads), 0, s, a, r, th);
+    else if (L <= 40 && !generic) hipLaunchKernelGGL((pe_radiation_kernel<T, 40, false, BUDGET>), gg, dim3(kRadThreads), 0, s, a, r, th);
+    else hipLaunchKernelGGL((pe_radiation_kernel<T, 0, false, BUDGET>), gg, dim3(kRadThreads), sizeof(double) * (size_t)L * kRadThreads, s, a, r, th);
+}
+
 // rows [j0, j1) and [jb0, jb1) of state set `set` (a band's ghost rows: negative, or >= H); keep_ghosts: the caller
 // radiates the ghost rows itself before their column sums and anchors are queued (gcm_band_run), so what
 // pe25d_prep_ghost_rows left stays valid
+// budget: the in-place launch of a step while the slab ocean is registered (pe25d_solar_rows): the BUDGET instantiation
 template <typename T>
 static int radiation_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, bool apply, double dt,
                             double hour_angle, double albedo, double *dTdt_host, double *dtg_host, hipStream_t s,
-                            std::string *err) {
+                            std::string *err, bool budget = false) {
     PeBufs<T> &B = bufs<T>(m);
     const int W = m->W, L = m->L, Hg = m->Hg;
     const int nrows = std::max(0, j1 - j0) + std::max(0, jb1 - jb0);
@@ -185,13 +217,17 @@ static int radiation_launch(Pe25d *m, int set, int j0, int j1, int jb0, int jb1,
     {
         const dim3 gg((W + kRadThreads - 1) / kRadThreads, nrows);
         T *th = B.st[set][GCM_T];
-        const bool generic = m->rad_generic;
-        const bool fact = m->cfg.ptop == 0.0 && r.sigk != nullptr;
-        if (L <= 24 && !generic && fact) hipLaunchKernelGGL((pe_radiation_kernel<T, 24, true>), gg, dim3(kRadThreads), 0, s, a, r, th);
-        else if (L <= 40 && !generic && fact) hipLaunchKernelGGL((pe_radiation_kernel<T, 40, true>), gg, dim3(kRadThreads), 0, s, a, r, th);
-        else if (L <= 24 && !generic) hipLaunchKernelGGL((pe_radiation_kernel<T, 24>), gg, dim3(kRadThreads), 0, s, a, r, th);
-        else if (L <= 40 && !generic) hipLaunchKernelGGL((pe_radiation_kernel<T, 40>), gg, dim3(kRadThreads), 0, s, a, r, th);
-        else hipLaunchKernelGGL((pe_radiation_kernel<T, 0>), gg, dim3(kRadThreads), sizeof(double) * (size_t)L * kRadThreads, s, a, r, th);
+        if (budget && apply) {
+            // the column's transmissivity: tcol = clw_b_div[L-1] * tlw[L-1], formed here, once a launch, from the host copy
+            // of the tables in place (clw_b_div[L-1] is the product of tlw[0 .. L-2] in the order of grey_radiation_tables)
+            r.bud = pe25d_slab_ocean_word(m, GCM_SLAB_SC);
+            r.bud_stride = (long)rows_alloc(m) * W;
+            r.tcol = m->rad_tab_host[(size_t)3 * L + L - 1] * m->rad_tab_host[(size_t)L - 1];
+            if (!r.bud) { *err = "radiation: no slab ocean registered for the budget launch"; return GCM_ERR_STATE; }
+            radiation_dispatch<T, true>(m, gg, a, r, th, s);
+        } else {
+            radiation_dispatch<T, false>(m, gg, a, r, th, s);
+        }
     }
     if (hipGetLastError() != hipSuccess) { *err = "hip: radiation kernel launch failed"; return GCM_ERR_HIP; }
     // solar_timestep (apply) stays asynchronous on `s`; the diagnostics form copies its results back
@@ -303,8 +339,9 @@ int pe25d_solar_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool k
                      hipStream_t s, std::string *err) {
     if (set < 0) set = m->cur_i;
     const double hour_angle = utc / (-24 * 3600.0) * 360 * (M_PI / 180);      // grey_solar.py:51
-    return m->f32 ? radiation_launch<float>(m, set, j0, j1, jb0, jb1, keep_ghosts, true, dt, hour_angle, albedo, nullptr, nullptr, s, err)
-                  : radiation_launch<double>(m, set, j0, j1, jb0, jb1, keep_ghosts, true, dt, hour_angle, albedo, nullptr, nullptr, s, err);
+    const bool budget = m->slab.on;                        // the slab ocean advances the ground temperature
+    return m->f32 ? radiation_launch<float>(m, set, j0, j1, jb0, jb1, keep_ghosts, true, dt, hour_angle, albedo, nullptr, nullptr, s, err, budget)
+                  : radiation_launch<double>(m, set, j0, j1, jb0, jb1, keep_ghosts, true, dt, hour_angle, albedo, nullptr, nullptr, s, err, budget);
 }
 
 // basic_grey_radiation (+ optional in-place solar_timestep).  dTdt_host / dtg_host may be null.  On a latitude

@@ -939,6 +939,80 @@ int gcm_boundary_layer_surface(int n, const gcm_boundary_layer *bl, double ptop,
                                double *S, double *z_a, double *cd);
 int gcm_boundary_layer_column(int ncol, int L, const double *dsig, const double *a, const double *x, const double *target,
                               const double *X, double *X_out, double *X0_surface);
+/* Slab mixed-layer ocean of GCM_PE25D with a recorded surface and top-of-atmosphere budget, on the device (fp64 and fp32
+ * handles; single domains and latitude bands).  Without it the ground temperature is the reference's: a 10 cm slab that
+ * the radiation alone heats (gt += dt (B + S - U_s) / Cg / 0.1, in the radiation kernel), and the boundary layer takes
+ * sensible heat and water vapour from it for nothing.  With it the ground temperature is the temperature of a slab of heat
+ * capacity C (J m^-2 K^-1) that receives the net radiation at the surface, pays for what the boundary layer takes and
+ * may receive a prescribed ocean heat flux Q (W / m^2).  Per cell, float64 on either storage type, every operation
+ * rounded on its own, in this order (dt the step; S, B, U_s, SH_J, EVAP_KG the flux words below):
+ *   R  = (S + B) - U_s       E1 = dt R       E2 = E1 - SH_J       E3 = E2 - Lv EVAP_KG       E4 = E3 + dt Q
+ *   gt' = gt + E4 / C
+ * C is the scalar heat_capacity (1.0e7: Frierson's 2.4 m of water) or, where given, a field [H][W]; C = +inf holds a cell
+ * at its prescribed temperature (E4 / C = 0, and gt + 0 keeps gt's bits).  Q is an optional field [H][W]; none: 0.  The
+ * scheme is explicit: it is stable where dt lambda / C << 1, lambda ~ 4 sigma T^3 plus the bulk coefficients' share.
+ * Flux words, float64, GCM_SLAB_WORDS fields of [H + 2 ghost rows][W] allocated by the registration and stored by the
+ * phases that know them, while the slab is registered and at no other time:
+ *   GCM_SLAB_SC       W / m^2   insolation at the top, Sc                       | the radiation kernel's BUDGET
+ *   GCM_SLAB_SW_SFC   W / m^2   short wave absorbed by the surface, S           | instantiations, launched in place of the
+ *   GCM_SLAB_LW_DOWN  W / m^2   long wave reaching the surface, B               | others by the steps of a registered
+ *   GCM_SLAB_LW_UP    W / m^2   long wave leaving the surface, U_s              | handle; they leave gt alone and compute
+ *   GCM_SLAB_OLR      W / m^2   up + U_s tcol: up the bottom-up scan's value    | theta exactly as the others do (the
+ *                               above the last level, tcol = clw_b_div[L-1] *   | same bits)
+ *                               tlw[L-1] formed on the host from the level tables
+ *   GCM_SLAB_SH_J     J / m^2   the step's own increment of the boundary layer's shf   | pe_bl_theta_q_kernel, the
+ *   GCM_SLAB_EVAP_KG  kg / m^2  the step's own increment of the boundary layer's evap  | same expressions
+ * The words of a phase that is not registered count as zero and read as zero.
+ * Sums, float64, GCM_SLAB_SUMS fields [H][W] of the own rows, one writer per word and launch, no atomics; the same launch
+ * adds  0 dt SC   1 dt S   2 dt B   3 dt U_s   4 dt OLR   5 SH_J   6 Lv EVAP_KG   7 dt Q   8 dt gt'   9 dt gt'^2;
+ * seconds (the sum of dt) and nsteps live in the handle.  Time means in W / m^2 are sum / seconds; the surface's net gain
+ * is (1 + 2 - 3 - 5 - 6 + 7) / seconds.  The absorbed short wave of the column, ASR = SC - albedo SC csw_top[0], is not
+ * summed: albedo and csw_top[0] are constants of the registered physics, so a host forms its sum as
+ * sum 0 - albedo / (1 - albedo) sum 1 (albedo < 1), and the top's net gain as ASR - sum 4.
+ * gcm_set_slab_ocean(h, so, capacity, qflux): the phase as part of every step taken by gcm_step, gcm_band_run and
+ * gcm_end_step: Matsuno step, horizontal diffusion, solar step, Held-Suarez forcing, boundary layer, THIS, convective
+ * adjustment, Betts-Miller convection, moist physics, samples.  capacity and qflux are [H][W] or NULL.  It needs
+ * gcm_set_ground.  Registering again replaces parameters and fields and resets the sums; so = NULL unregisters and frees
+ * everything.  Without a registration nothing is launched or allocated and every result and timing is as before; after
+ * an unregistration the radiation advances the ground temperature by the reference's rule again.
+ * Latitude bands: the phase is column-local.  A band without the boundary layer advances its ghost rows locally from the
+ * neighbour's inputs (their words come from the ghost rows' radiation launch) and adds nothing for them; where a
+ * capacity or heat-flux field is registered, which holds own rows only, the ghost rows are left to the next message.  A
+ * band with the boundary layer (gcm_set_band_boundary_layer) takes its own rows, in gcm_end_step_begin, ahead of the
+ * third exchange, whose message carries the ground temperature's edge rows as every message does: gcm_halo_bytes and the
+ * message are unchanged.  Own rows see the single domain's inputs and arithmetic: the same bits, sums included.
+ * gcm_slab_ocean_on: 1 where registered, else 0 (other models: 0; a null handle GCM_ERR_ARG).
+ * gcm_slab_ocean_apply(h, dt, so, words): uploads words [GCM_SLAB_WORDS][H][W] and applies the cell rule once to the own
+ * rows with the parameters so and the registered fields; it adds to the sums, seconds and nsteps only where the slab is
+ * registered.  Without a registration the call allocates the words itself, which the handle keeps until
+ * gcm_set_slab_ocean(h, NULL, ...) or gcm_destroy.
+ * gcm_get_slab_ocean_fluxes(h, words): the words of the last step or apply, own rows, [GCM_SLAB_WORDS][H][W]; one
+ * synchronisation.  gcm_get_slab_ocean: sums [GCM_SLAB_SUMS][H][W], seconds, nsteps, any pointer may be NULL;
+ * gcm_put_slab_ocean uploads them (restarts): sums required, seconds finite and >= 0, nsteps >= 0; gcm_slab_ocean_reset
+ * zeroes all three.
+ * gcm_slab_ocean_cells: the cell rule on its own, on the host, the very routine the kernel calls, no handle, no device: n
+ * cells with gt [n], words [GCM_SLAB_WORDS][n], C [n] or NULL (the scalar), Q [n] or NULL (0) -> gt_out [n] and, where
+ * not NULL, E4_out [n].
+ * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, heat_capacity or a cell of
+ * the capacity field NaN or <= 0, Lv not finite or <= 0, a non-finite cell of the heat-flux field, a non-finite dt, a
+ * missing array; the probe: n < 0.  GCM_ERR_UNSUPPORTED: other models.  GCM_ERR_STATE: no ground temperature set
+ * (gcm_set_ground); fluxes without words in place; get, put or reset without a registration.                        */
+enum { GCM_SLAB_SC = 0, GCM_SLAB_SW_SFC = 1, GCM_SLAB_LW_DOWN = 2, GCM_SLAB_LW_UP = 3, GCM_SLAB_OLR = 4, GCM_SLAB_SH_J = 5,
+       GCM_SLAB_EVAP_KG = 6, GCM_SLAB_WORDS = 7 };
+enum { GCM_SLAB_SUMS = 10 };
+typedef struct {
+    double heat_capacity;        /* J m^-2 K^-1, > 0; +inf: prescribed temperature (1.0e7)          */
+    double Lv;                   /* J / kg: latent heat of vaporisation (2.5e6)                     */
+} gcm_slab_ocean;
+int gcm_set_slab_ocean(gcm_handle *h, const gcm_slab_ocean *so, const double *capacity, const double *qflux);
+int gcm_slab_ocean_on(const gcm_handle *h);
+int gcm_slab_ocean_apply(gcm_handle *h, double dt, const gcm_slab_ocean *so, const double *words);
+int gcm_get_slab_ocean_fluxes(gcm_handle *h, double *words);
+int gcm_get_slab_ocean(gcm_handle *h, double *sums, double *seconds, int64_t *nsteps);
+int gcm_put_slab_ocean(gcm_handle *h, const double *sums, double seconds, int64_t nsteps);
+int gcm_slab_ocean_reset(gcm_handle *h);
+int gcm_slab_ocean_cells(int n, const gcm_slab_ocean *so, double dt, const double *gt, const double *C, const double *words,
+                         const double *Q, double *gt_out, double *E4_out);
 /* Zonal-mean climatology of GCM_PE25D accumulated on the device: what a Held-Suarez run is evaluated by -- the time and
  * zonal means of u, v, theta and T, their variances and the eddy fluxes as functions of latitude and level -- without a
  * host round trip per step (fp64 and fp32 handles, single domains and latitude bands).  One launch per sample reads
