@@ -16,7 +16,7 @@ from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
 from .core import (BettsMiller, BoundaryLayer, Climate, Convect, Core, GcmError, Moist, PlevClimate, PlevMaps, Spectra, TracerStats, aquaplanet_sst,  # noqa: F401
                    betts_miller_columns, boundary_layer_column, boundary_layer_surface, convect_columns, convect_tracer_columns, device_count,
                    hdiff_apply, hdiff_apply_band, hdiff_tables, held_suarez_tables, moist_saturation, plev_columns, plev_height_columns,
-                   SlabOcean, slab_ocean_cells)
+                   SlabOcean, slab_ocean_cells, GAS_RADIATION_DEFAULTS, gas_insolation, gas_radiation_columns)
 
 
 
@@ -32,4 +32,4 @@ def clear_cache():
 __all__ = ["BettsMiller", "BoundaryLayer", "Climate", "Convect", "Core", "GcmError", "Moist", "PlevClimate", "PlevMaps", "Spectra", "TracerStats", "aquaplanet_sst",
            "boundary_layer_column", "boundary_layer_surface", "convect_columns", "convect_tracer_columns", "device_count",
            "betts_miller_columns", "clear_cache", "hdiff_apply", "hdiff_apply_band", "hdiff_tables", "held_suarez_tables", "moist_saturation", "plev_columns", "plev_height_columns",
-           "SlabOcean", "slab_ocean_cells"]
+           "SlabOcean", "slab_ocean_cells", "GAS_RADIATION_DEFAULTS", "gas_insolation", "gas_radiation_columns"]

@@ -121,6 +121,16 @@ class SlabOcean(C.Structure):
 SLAB_WORDS, SLAB_SUMS = 7, 10                # GCM_SLAB_WORDS, GCM_SLAB_SUMS
 
 
+class GasRadiation(C.Structure):
+    """gcm_gas_radiation_par of include/gcmcore.h"""
+    _fields_ = [("k_h2o_lw", C.c_double), ("k_co2_lw", C.c_double), ("k_h2o_sw", C.c_double), ("k_co2_sw", C.c_double),
+                ("co2_vmr", C.c_double), ("ground_albedo", C.c_double), ("solar_constant", C.c_double),
+                ("declination", C.c_double), ("insolation", C.c_int32)]
+
+
+INSOLATION = {"uniform": 0, "zenith": 1, "daily": 2}      # GCM_INSOLATION_*
+
+
 class Convect(C.Structure):
     """gcm_convect of include/gcmcore.h"""
     _fields_ = [("kappa_c", C.c_double), ("mix_q", C.c_int32)]
@@ -222,6 +232,12 @@ SYMBOLS = {
     "gcm_put_slab_ocean": (C.c_int, [_H, _dp, C.c_double, C.c_int64]),
     "gcm_slab_ocean_reset": (C.c_int, [_H]),
     "gcm_slab_ocean_cells": (C.c_int, [C.c_int, C.POINTER(SlabOcean), C.c_double] + [_dp] * 6),
+    "gcm_set_gas_radiation": (C.c_int, [_H, C.POINTER(GasRadiation)]),
+    "gcm_gas_radiation_on": (C.c_int, [_H]),
+    "gcm_gas_radiation": (C.c_int, [_H, C.c_double, C.POINTER(GasRadiation), _dp, _dp, _dp, _dp, _dp]),
+    "gcm_gas_radiation_step": (C.c_int, [_H, C.c_double, C.c_double, C.POINTER(GasRadiation), _dp, _dp]),
+    "gcm_gas_radiation_columns": (C.c_int, [C.c_int, C.c_int, C.POINTER(GasRadiation), _dp, _dp, C.c_double] + [_dp] * 9),
+    "gcm_gas_insolation": (C.c_int, [C.c_int, C.c_int, _dp, C.c_double, C.c_double, _dp]),
     "gcm_set_convect": (C.c_int, [_H, C.POINTER(Convect)]),
     "gcm_convect_on": (C.c_int, [_H]),
     "gcm_convect_step": (C.c_int, [_H, C.POINTER(Convect)]),

@@ -312,7 +312,15 @@ def merge_slab_ocean(parts):
     parts = list(parts)
     if not parts:
         raise ValueError("merge_slab_ocean: no records")
-    if any(m.nsteps != parts[0].nsteps or m.seconds != parts[0].seconds or m.reflect != parts[0].reflect for m in parts):
+    # (the reflected share is a field of the band's own rows while the gas radiation is registered: its rows are concatenated too)
+    fields = [np.ndim(m.reflect) > 0 for m in parts]
+    if all(fields):
+        if any(m.nsteps != parts[0].nsteps or m.seconds != parts[0].seconds for m in parts):
+            raise ValueError("merge_slab_ocean: the bands hold %s applications over %s seconds"
+                             % (", ".join(str(m.nsteps) for m in parts), ", ".join(repr(m.seconds) for m in parts)))
+        return SlabOcean(parts[0].nsteps, parts[0].seconds, np.concatenate([m.sums for m in parts], axis=1),
+                         np.concatenate([m.reflect for m in parts], axis=0))
+    if any(fields) or any(m.nsteps != parts[0].nsteps or m.seconds != parts[0].seconds or m.reflect != parts[0].reflect for m in parts):
         raise ValueError("merge_slab_ocean: the bands hold %s applications over %s seconds (reflected share %s)"
                          % (", ".join(str(m.nsteps) for m in parts), ", ".join(repr(m.seconds) for m in parts),
                             ", ".join(repr(m.reflect) for m in parts)))
@@ -427,6 +435,11 @@ class HipBandEngine:
         """Core.set_slab_ocean (capacity and qflux: the band's own rows); every band of a run registers the same
         parameters.  merge_slab_ocean() puts the bands' sums together"""
         self.c.set_slab_ocean(*off, **params)
+
+    def set_gas_radiation(self, *off, **params):
+        """Core.set_gas_radiation; every band of a run registers the same parameters (the phase is column-local and q
+        travels in the message already: nothing else changes on a band)"""
+        self.c.set_gas_radiation(*off, **params)
 
     def set_convect(self, *off, **params):
         """Core.set_convect; every band of a run registers the same.  merge_convect() puts the bands' sums together"""

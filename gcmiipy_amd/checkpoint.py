@@ -44,14 +44,17 @@ saved the same way and restored between the convective adjustment and the moist 
 restore with none; the slab ocean, Core.set_slab_ocean, is stored as "slab_ocean", its two parameters in the order of
 core.SLAB_OCEAN_DEFAULTS, with "slab_ocean_n", "slab_ocean_seconds", "slab_ocean_sums", the raw float64 sums, and, where
 registered, the fields "slab_ocean_capacity" and "slab_ocean_qflux", registered and uploaded again directly behind the
-boundary layer; files without the key restore with none)
+boundary layer; files without the key restore with none; the gas radiation, Core.set_gas_radiation, is stored as
+"gas_radiation", its parameters in the order of core.GAS_RADIATION_DEFAULTS with the insolation as its GCM_INSOLATION_*
+code, and registered again behind the ground temperature -- as the other column physics it acts while set_physics is
+on, which the caller registers again with the saved clock; files without the key restore with none)
 and the geometry tables:
 `restore()` rebuilds an equivalent handle and the run resumes bit for bit.  A latitude band writes
 ITS rows (one file per rank; `row0` / `global_height` are in the file)."""
 import numpy as np
 
 from . import _lib
-from .core import Core, GcmError, HDIFF_DEFAULTS, HELD_SUAREZ_DEFAULTS, SAMPLERS, SLAB_OCEAN_DEFAULTS, STEP_COLUMN_PHASES
+from .core import Core, GAS_RADIATION_DEFAULTS, GcmError, HDIFF_DEFAULTS, HELD_SUAREZ_DEFAULTS, SAMPLERS, SLAB_OCEAN_DEFAULTS, STEP_COLUMN_PHASES
 from .geometry import Geom
 
 _GEOM_KEYS = ("sige", "sigt", "sigb", "dsig", "sig", "dsigv", "dx_j", "dx_h", "dy", "ptop",
@@ -127,6 +130,13 @@ def save(path, core, step=0, time=0.0, geom=None, **extra):
         for k in ("capacity", "qflux"):
             if slab[k] is not None:
                 out["slab_ocean_" + k] = slab[k]
+    gas = getattr(core, "gas_radiation_params", None) if core.model == _lib.PE25D else None
+    if gas is None and getattr(core, "gas_radiation_registered", False):
+        raise GcmError("checkpoint.save: the handle's gas radiation was registered through gcm_set_gas_radiation directly; its "
+                       "parameters are unknown here and the phase would be lost (register with Core.set_gas_radiation)")
+    if gas is not None:
+        out["gas_radiation"] = np.asarray([_lib.INSOLATION[gas[k]] if k == "insolation" else gas[k] for k in GAS_RADIATION_DEFAULTS],
+                                          dtype=np.float64)
     for k, a in zip("puvtq", (p, u, v, t, q)):
         if a is not None:
             out["state_" + k] = a
@@ -207,8 +217,12 @@ def load(path):
                     seconds=float(d["slab_ocean_seconds"]), sums=d["slab_ocean_sums"],
                     capacity=d["slab_ocean_capacity"] if "slab_ocean_capacity" in d.files else None,
                     qflux=d["slab_ocean_qflux"] if "slab_ocean_qflux" in d.files else None)
+    gas = None
+    if "gas_radiation" in d.files:
+        names = {v: k for k, v in _lib.INSOLATION.items()}
+        gas = {k: names[int(x)] if k == "insolation" else float(x) for k, x in zip(GAS_RADIATION_DEFAULTS, d["gas_radiation"])}
     return dict(model=str(d["model"]), step=int(d["step"]), time=float(d["time"]), state=state, held_suarez=hs, hdiff=hd, **sampled,
-                slab_ocean=slab,
+                slab_ocean=slab, gas_radiation=gas,
                 geom=geom, extra=extra, shape=(L, H, W), options=opts,
                 ground=d["ground"] if "ground" in d.files else None,
                 tracers=d["tracers"] if "tracers" in d.files else None, tracer_forcing=forcing,
@@ -231,6 +245,8 @@ def restore(path, **core_kwargs):
     core.set_state(**ck["state"])
     if ck["ground"] is not None:
         core.set_ground(ck["ground"])
+    if ck["gas_radiation"] is not None:
+        core.set_gas_radiation(**ck["gas_radiation"])
     if ck["tracers"] is not None:
         core.set_tracers(ck["tracers"])
         for i, rec in sorted(ck["tracer_forcing"].items()):

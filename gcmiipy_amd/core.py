@@ -763,6 +763,80 @@ def slab_ocean_cells(gt, words, dt, capacity=None, qflux=None, **params):
     return out.reshape(gt.shape), e4.reshape(gt.shape)
 
 
+# the parameters of the grey radiation by water vapour and CO2 (gcm_gas_radiation_par), in the struct's order: the long-
+# and short-wave weights of water vapour and CO2, m^2 / kg, the CO2 volume mixing ratio, the ground's albedo, the solar
+# constant, W / m^2, the declination, radians, and the insolation ("uniform" | "zenith" | "daily").  The values are the
+# reference's (grey_solar.py:29,76-80,208,290), as its unit bookkeeping evaluates them
+GAS_RADIATION_DEFAULTS = collections.OrderedDict(k_h2o_lw=0.125, k_co2_lw=1.0, k_h2o_sw=0.125, k_co2_sw=1.0, co2_vmr=300 / 1e6,
+                                                 ground_albedo=0.1, solar_constant=2 * 41840 * 60.0 ** -1, declination=0.0,
+                                                 insolation="uniform")
+
+
+def gas_radiation_params(params, **clock):
+    """the parameters of the gas radiation as a dict: GAS_RADIATION_DEFAULTS with `params` laid over them, floats but for
+    the insolation's name, and the clock values `clock` (utc, dt) checked with them -- what the library accepts, said
+    without a handle.  ValueError for a name that is not a parameter and for a refused value (NaN included)"""
+    unknown = sorted(set(params) - set(GAS_RADIATION_DEFAULTS))
+    if unknown:
+        raise ValueError("gas_radiation: unknown parameter(s) %s; the parameters are %s"
+                         % (", ".join(unknown), ", ".join(GAS_RADIATION_DEFAULTS)))
+    out = collections.OrderedDict(GAS_RADIATION_DEFAULTS)
+    out.update({k: (v if k == "insolation" else float(v)) for k, v in params.items()})
+    for k in ("k_h2o_lw", "k_co2_lw", "k_h2o_sw", "k_co2_sw", "co2_vmr", "solar_constant"):
+        if not (np.isfinite(out[k]) and out[k] >= 0.0):
+            raise ValueError("gas_radiation: %s must be finite and >= 0, got %r" % (k, out[k]))
+    if not (0.0 <= out["ground_albedo"] < 1.0):
+        raise ValueError("gas_radiation: ground_albedo must lie in [0, 1), got %r" % out["ground_albedo"])
+    if not (abs(out["declination"]) <= np.pi / 2):
+        raise ValueError("gas_radiation: declination must lie in [-pi/2, pi/2], got %r" % out["declination"])
+    if out["insolation"] not in _lib.INSOLATION:
+        raise ValueError("gas_radiation: unknown insolation %r; one of %s" % (out["insolation"], ", ".join(_lib.INSOLATION)))
+    for name, x in clock.items():
+        if not np.isfinite(float(x)):
+            raise ValueError("gas_radiation: %s must be finite, got %r" % (name, x))
+    return out
+
+
+def _gas_record(par):
+    return _lib.GasRadiation(*[_lib.INSOLATION[v] if k == "insolation" else v for k, v in par.items()])
+
+
+def gas_insolation(lat, insolation="uniform", declination=0.0, solar_constant=GAS_RADIATION_DEFAULTS["solar_constant"]):
+    """the insolation of the rows at the latitudes `lat` (radians), W / m^2 (gcm_gas_insolation; no handle, no device):
+    "uniform", the reference's solar_constant 0.5 0.5, or "daily", its daily_average_irradiance(lat, declination) with the
+    arccos argument kept inside [-1, 1] (finite in polar night and polar day).  ValueError for "zenith", which has no row
+    table, and for a refused parameter"""
+    par = gas_radiation_params(dict(insolation=insolation, declination=declination, solar_constant=solar_constant))
+    lat = np.asarray(lat, dtype=np.float64)
+    la = as_f64(lat.reshape(-1), name="lat")
+    out = np.empty(la.size)
+    _check(lib.gcm_gas_insolation(_lib.INSOLATION[par["insolation"]], la.size, _tab(la), par["declination"], par["solar_constant"], _tab(out)))
+    return out.reshape(lat.shape)
+
+
+def gas_radiation_columns(SC, p, tt, q, gt, sig, dsig, ptop=0.0, words=False, **params):
+    """the column routine of the gas radiation (gcm_gas_radiation_columns; the host build of the routine the kernel calls,
+    no handle, no device): the insolation SC, the surface pressure p and the ground temperature gt of any one shape S, the
+    true temperature tt and q of shape (L,) + S, the levels sig and dsig (L,) -> (dt_ground S, dt_air (L,) + S, olr S),
+    and with words=True a fourth, (5,) + S: SC, SW_SFC, LW_DOWN, LW_UP, OLR.  ValueError for a refused parameter"""
+    par = gas_radiation_params(params)
+    p = np.asarray(p, dtype=np.float64)
+    pf = as_f64(p.reshape(-1), name="p")
+    n = pf.size
+    flat = [as_f64(np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), p.shape)).reshape(-1), (n,), nm)
+            for a, nm in ((SC, "SC"), (gt, "gt"))]
+    sig = as_f64(np.asarray(sig, dtype=np.float64).reshape(-1), name="sig")
+    L = sig.size
+    dsig = as_f64(np.asarray(dsig, dtype=np.float64).reshape(-1), (L,), "dsig")
+    lev = [as_f64(np.asarray(a, dtype=np.float64).reshape(L, -1), (L, n), nm) for a, nm in ((tt, "tt"), (q, "q"))]
+    dg, da, olr, w = np.empty(n), np.empty((L, n)), np.empty(n), np.empty((5, n))
+    rec = _gas_record(par)
+    _check(lib.gcm_gas_radiation_columns(n, L, C.byref(rec), _tab(flat[0]), _tab(pf), float(ptop), _tab(sig), _tab(dsig),
+                                         _tab(lev[0]), _tab(lev[1]), _tab(flat[1]), _tab(dg), _tab(da), _tab(olr), _tab(w)))
+    out = (dg.reshape(p.shape), da.reshape((L,) + p.shape), olr.reshape(p.shape))
+    return out + (w.reshape((5,) + p.shape),) if words else out
+
+
 def aquaplanet_sst(lat, dT=29.0, T_min=271.0, width=np.deg2rad(26.0)):
     """the prescribed sea-surface temperature of the moist Held-Suarez test (Thatcher & Jablonowski 2016) at the
     latitudes `lat` (radians), K: dT exp(-lat^2 / (2 width^2)) + T_min, width in radians (26 degrees).  What set_ground
@@ -1058,6 +1132,7 @@ class Core:
         self._hdiff = None                      # the parameters registered (set_horizontal_diffusion)
         self._column = {}                       # the parameters registered (set_boundary_layer, set_convect, set_moist), by the phase's name
         self._slab = None                       # the parameters and fields registered (set_slab_ocean)
+        self._gas = None                        # the parameters registered (set_gas_radiation)
         self._phys = None                       # t_lw, t_sw, albedo registered (set_physics): the slab ocean's ASR
         self._sigma_levels = None                     # GCM_PE25D: (sig, dsig) of the geometry
         cfg = _lib.Config()
@@ -1520,6 +1595,56 @@ class Core:
         _check(lib.gcm_set_physics(self._h, C.byref(ph)), self._h)
         self._phys = dict(t_lw=t_lw, t_sw=t_sw, albedo=albedo)
 
+    # -- grey radiation by water vapour and CO2 (GCM_PE25D) ----------------------------------
+    def set_gas_radiation(self, *off, **params):
+        """while set_physics is on, every step of step() / band_run() / end_step() from now on takes its solar step from
+        the grey radiation that absorbs by water vapour and CO2 (gcm_set_gas_radiation; set_ground first) instead of the
+        grey scheme: a level's optical depth comes from its own q and the CO2 mixing ratio.  The clock, lat and lon are the
+        physics registration's; its t_lw, t_sw and albedo are then unused.  Registering without physics is allowed and
+        takes effect when physics comes on.  params: GAS_RADIATION_DEFAULTS.  set_gas_radiation(None) switches it off:
+        the grey scheme again.  ValueError for a refused parameter, GcmError for a handle without a ground temperature
+        (the call then changes nothing)"""
+        if off:
+            if off != (None,) or params:
+                raise ValueError("set_gas_radiation takes keyword parameters, or None alone to switch the phase off")
+            _check(lib.gcm_set_gas_radiation(self._h, None), self._h)
+            self._gas = None
+            return
+        par = gas_radiation_params(params)
+        rec = _gas_record(par)
+        _check(lib.gcm_set_gas_radiation(self._h, C.byref(rec)), self._h)
+        self._gas = par
+
+    @property
+    def gas_radiation_params(self):
+        """the registered gas radiation's parameters as a dict in the order of GAS_RADIATION_DEFAULTS, or None where the
+        handle carries none -- and also None for one registered through the C call directly"""
+        gas = getattr(self, "_gas", None)
+        return dict(gas) if self.gas_radiation_registered and gas else None
+
+    @property
+    def gas_radiation_registered(self):
+        """whether the handle carries the phase at all (gcm_gas_radiation_on), whoever registered it"""
+        return bool(_count(lib.gcm_gas_radiation_on(self._h), self._h))
+
+    def gas_radiation(self, geom, utc, **params):
+        """-> (dt_ground [H,W], dt_air [L,H,W], olr [H,W]), grey_solar.grey_radiation with clouds off on the current state
+        (gcm_gas_radiation).  ValueError for a refused parameter (the call then changes nothing)"""
+        par = gas_radiation_params(params, utc=utc)
+        lat, lon = self._latlon(geom)
+        dg, da, olr = np.empty((self.H, self.W)), np.empty((self.L, self.H, self.W)), np.empty((self.H, self.W))
+        rec = _gas_record(par)
+        _check(lib.gcm_gas_radiation(self._h, float(utc), C.byref(rec), _tab(lat), _tab(lon), _tab(dg), _tab(da), _tab(olr)), self._h)
+        return dg, da, olr
+
+    def gas_radiation_step(self, geom, dt, utc, **params):
+        """no_limits_2_5d.solar_timestep's statements with grey_radiation's tendencies, once in place
+        (gcm_gas_radiation_step); a band: own rows and ghost rows.  ValueError for a refused parameter"""
+        par = gas_radiation_params(params, utc=utc, dt=dt)
+        lat, lon = self._latlon(geom)
+        rec = _gas_record(par)
+        _check(lib.gcm_gas_radiation_step(self._h, float(dt), float(utc), C.byref(rec), _tab(lat), _tab(lon)), self._h)
+
     # -- Held-Suarez forcing (GCM_PE25D) ---------------------------------------------------
     def _hs_lat(self, geom):
         lat = getattr(geom, "lat", geom)        # a geometry, or the latitudes themselves
@@ -1761,9 +1886,16 @@ class Core:
         _check(lib.gcm_get_slab_ocean_fluxes(self._h, _tab(out)), self._h)
         return out
 
-    def _slab_reflect(self):
-        """albedo csw_top[0] of the physics registered through set_physics, 0 without"""
+    def _slab_reflect(self, sums=None):
+        """albedo csw_top[0] of the physics registered through set_physics, 0 without.  While the gas radiation is
+        registered (with physics): the field a_g (sums[SW_SFC] / (1 - a_g)) / sums[SC], the share of the insolation the
+        ground sent back, and 0 where sums[SC] == 0"""
         phys = getattr(self, "_phys", None)
+        gas = self.gas_radiation_params if phys else None
+        if gas is not None and sums is not None:
+            a_g, sc = gas["ground_albedo"], sums[0]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return np.where(sc == 0, 0.0, a_g * (sums[1] / (1 - a_g)) / sc)
         if not phys or getattr(self, "_sigma_levels", None) is None:
             return 0.0
         sig, dsig = self._sigma_levels
@@ -1775,7 +1907,7 @@ class Core:
         sums = np.empty((_lib.SLAB_SUMS, self.H, self.W))
         sec, n = C.c_double(), C.c_int64()
         _check(lib.gcm_get_slab_ocean(self._h, _tab(sums), C.byref(sec), C.byref(n)), self._h)
-        return SlabOcean(int(n.value), float(sec.value), sums, self._slab_reflect())
+        return SlabOcean(int(n.value), float(sec.value), sums, self._slab_reflect(sums))
 
     def put_slab_ocean(self, nsteps, seconds, sums):
         """upload sums taken by slab_ocean_sums() (gcm_put_slab_ocean): a restart goes on where the run stopped"""

@@ -35,6 +35,10 @@ int pe_phase_tables(gcm_handle *h, int nsteps, double dt) {
     if (ph.solar)
         if (int rc = pe25d_physics_tables(h->pe, ph.phys.t_lw, ph.phys.t_sw, ph.phys_lat.data(), ph.phys_lon.data(), h->stream, &h->err))
             return rc;
+    // gcm_set_gas_radiation: the kernel that takes the solar step's place reads the physics registration's lat and lon
+    if (ph.solar && pe25d_gas_radiation_on(h->pe))
+        if (int rc = pe25d_gas_radiation_tables(h->pe, pe25d_gas_radiation_par(h->pe), ph.phys_lat.data(), ph.phys_lon.data(), h->stream, &h->err))
+            return rc;
     if (nsteps <= 0) return GCM_OK;
     if (ph.held_suarez) {
         gcm_held_suarez hs = ph.hs;
@@ -88,7 +92,8 @@ static int pe_phase_rows(gcm_handle *h, double dt, int set, int j0, int j1, int 
         if (ph.solar) {
             // no_limits_2_5d.py:229-234 with the physics below full_timestep's early return (:96): the dynamics step, then
             // solar_timestep (:66-75) at the current utc, which changes theta and the ground temperature in place AFTER the
-            // post-corrector exchange has left, then utc += dt
+            // post-corrector exchange has left, then utc += dt.  While a gas radiation is registered (gcm_set_gas_radiation)
+            // pe25d_solar_rows launches its kernel in place of the grey one, at the same clock and over the same rows
             if (int rc = pe25d_solar_rows(h->pe, set, j0, j1, jb0, jb1, keep_ghosts, dt, ph.phys.utc, ph.phys.albedo, s, &h->err)) return rc;
             if (own) ph.phys.utc += dt;
         }
@@ -452,6 +457,43 @@ int gcm_solar_step(gcm_handle *h, double dt, double utc, double t_lw, double t_s
 int gcm_grey_radiation_tables(int L, const double *dsig, const double *sig, double t_lw, double t_sw, double *out, int nout) {
     if (L >= 1 && nout < 6 * L) return fail(nullptr, GCM_ERR_ARG, "gcm_grey_radiation_tables: out holds fewer than 6 L doubles");
     return grey_radiation_tables(L, dsig, sig, t_lw, t_sw, out, &gcm_create_error());
+}
+
+// ------------------------------------------------------------------ grey radiation by water vapour and CO2
+// no ground temperature set: refused in the call itself
+int gcm_set_gas_radiation(gcm_handle *h, const gcm_gas_radiation_par *par) {
+    if (int rc = pe_on_device(h, "gcm_set_gas_radiation")) return rc;
+    return pe25d_set_gas_radiation(h->pe, par, h->stream, &h->err);
+}
+
+int gcm_gas_radiation_on(const gcm_handle *h) {
+    if (!h) return GCM_ERR_ARG;
+    return h->pe && pe25d_gas_radiation_on(h->pe) ? 1 : 0;
+}
+
+int gcm_gas_radiation(gcm_handle *h, double utc, const gcm_gas_radiation_par *par, const double *lat, const double *lon,
+                      double *dt_ground, double *dt_air, double *olr) {
+    if (int rc = pe_on_device(h, "gcm_gas_radiation")) return rc;
+    if (int rc = gas_radiation_check(par, "gcm_gas_radiation", &h->err)) return rc;
+    if (!std::isfinite(utc)) return fail(h, GCM_ERR_ARG, "gcm_gas_radiation: utc must be finite");
+    return pe25d_gas_radiation(h->pe, false, 0.0, utc, par, lat, lon, dt_ground, dt_air, olr, h->stream, &h->err);
+}
+
+int gcm_gas_radiation_step(gcm_handle *h, double dt, double utc, const gcm_gas_radiation_par *par, const double *lat, const double *lon) {
+    if (int rc = pe_on_device(h, "gcm_gas_radiation_step")) return rc;
+    if (int rc = gas_radiation_check(par, "gcm_gas_radiation_step", &h->err)) return rc;
+    if (!std::isfinite(utc) || !std::isfinite(dt)) return fail(h, GCM_ERR_ARG, "gcm_gas_radiation_step: dt and utc must be finite");
+    return pe25d_gas_radiation(h->pe, true, dt, utc, par, lat, lon, nullptr, nullptr, nullptr, h->stream, &h->err);
+}
+
+int gcm_gas_radiation_columns(int ncol, int L, const gcm_gas_radiation_par *par, const double *SC, const double *p, double ptop,
+                              const double *sig, const double *dsig, const double *tt, const double *q, const double *gt,
+                              double *dt_ground, double *dt_air, double *olr, double *words) {
+    return gas_radiation_columns(ncol, L, par, SC, p, ptop, sig, dsig, tt, q, gt, dt_ground, dt_air, olr, words, &gcm_create_error());
+}
+
+int gcm_gas_insolation(int kind, int nlat, const double *lat, double declination, double solar_constant, double *out) {
+    return gas_insolation(kind, nlat, lat, declination, solar_constant, out, &gcm_create_error());
 }
 
 // ------------------------------------------------------------------ horizontal diffusion

@@ -18,6 +18,7 @@
 //   pe25d_convect_tracers.hip  the tracers' convective mixing in the adjustment's blocks: the kernel, its launch, the opt-ins
 //   pe25d_boundary_layer.hip  surface fluxes and boundary-layer mixing: the routines, the two kernels and their launches
 //   pe25d_slab_ocean.hip  the slab mixed-layer ocean: the cell routine's probe, the kernel, its launches, words and sums
+//   pe25d_gas_radiation.hip  grey radiation by water vapour and CO2: the column routine's probe, the kernel, its tables and launches
 //   pe25d_hdiff.hip    horizontal diffusion: the table and cell routines, the tile kernel, its launch and landing fields
 // A kernel is instantiated, launched and given its LDS attribute in one unit only (a second unit would get a host stub
 // of its own, which an attribute set through the first does not reach).  gcmcore.hip, gcm_band.hip, gcm_diag.hip and
@@ -209,6 +210,20 @@ struct PeSlab {
     long long n = 0;                            // applications in the sums
 };
 
+// Grey radiation by water vapour and CO2 (pe25d_gas_radiation.hip, gcm_set_gas_radiation): the registration and its
+// parameters, the insolation of every global row for the last ("uniform" | "daily", declination, solar_constant) a launch
+// was asked for -- `key`, compared on every step -- and the diagnostic form's float64 dt_ground and olr.  Nothing is
+// allocated before a launch needs it
+struct PeGasRad {
+    bool on = false;                            // gcm_set_gas_radiation: registered
+    gcm_gas_radiation_par par{};
+    double *sc_row = nullptr;                   // device: [Hg]
+    int key_kind = -1;
+    double key[2] = {0.0, 0.0};
+    double *diag = nullptr;                     // device: dt_ground [H][W], olr [H][W]
+    int lds_set[2] = {0, 0};                    // the dynamic LDS size the kernel's two forms were last given
+};
+
 // Horizontal diffusion (pe25d_hdiff.hip, gcm_set_hdiff): the registration, the device tables of the last (parameters,
 // dt) a launch was asked for -- `key`, compared on every step as PeHeldSuarez's -- and the landing fields the launch
 // writes, own rows [H][L][W] in the handle's real type, one per state field that was ever selected; they stay until
@@ -308,6 +323,7 @@ struct Pe25d {
     PeBettsMiller betts_miller;
     PeBoundary boundary;
     PeSlab slab;
+    PeGasRad gas;
     PeHdiff hdiff;
 };
 

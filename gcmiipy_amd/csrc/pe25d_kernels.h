@@ -1,6 +1,6 @@
 // 2.5-D sigma-level primitive equations (GCM_PE25D): host-visible interface of
 // pe25d_kernels.hip (the stage), pe25d_state.hip, pe25d_physics.hip, pe25d_diag.hip, pe25d_held_suarez.hip,
-// pe25d_climate.hip, pe25d_plev.hip, pe25d_plev_height.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_betts_miller.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip, pe25d_slab_ocean.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
+// pe25d_climate.hip, pe25d_plev.hip, pe25d_plev_height.hip, pe25d_spectra.hip, pe25d_moist.hip, pe25d_convect.hip, pe25d_betts_miller.hip, pe25d_convect_tracers.hip, pe25d_boundary_layer.hip, pe25d_slab_ocean.hip, pe25d_gas_radiation.hip and pe25d_tracers.hip (the passive tracers), used by gcmcore.hip, gcm_band.hip, gcm_diag.hip and gcm_pe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -214,6 +214,27 @@ int pe25d_slab_ocean_fluxes(Pe25d *m, double *words, hipStream_t s, std::string 
 int pe25d_slab_ocean_get(Pe25d *m, double *sums, double *seconds, int64_t *nsteps, hipStream_t s, std::string *err);
 int pe25d_slab_ocean_put(Pe25d *m, const double *sums, double seconds, int64_t nsteps, hipStream_t s, std::string *err);
 int pe25d_slab_ocean_reset(Pe25d *m, hipStream_t s, std::string *err);
+// Grey radiation by water vapour and CO2 (pe25d_gas_radiation.hip).  gas_radiation_check / gas_insolation /
+// gas_radiation_columns: no handle, no device (gcm_gas_insolation, gcm_gas_radiation_columns).  pe25d_set_gas_radiation:
+// gcm_set_gas_radiation (g == nullptr: off; GCM_ERR_STATE without a ground temperature); pe25d_gas_radiation_on /
+// pe25d_gas_radiation_par: the registration (null: none); pe25d_gas_radiation_tables: what a launch with g reads, in place;
+// pe25d_gas_radiation_rows: the registered phase in place over rows [j0, j1) and [jb0, jb1) of state set `set` (-1: the
+// current one) on `s` at the clock utc, keep_ghosts as for pe25d_solar_rows, which forwards to it while a registration
+// stands; pe25d_gas_radiation: gcm_gas_radiation (apply false; any output may be null) and gcm_gas_radiation_step
+int gas_radiation_check(const gcm_gas_radiation_par *g, const char *fn, std::string *err);
+int gas_insolation(int kind, int nlat, const double *lat, double declination, double solar_constant, double *out, std::string *err);
+int gas_radiation_columns(int ncol, int L, const gcm_gas_radiation_par *g, const double *SC, const double *p, double ptop,
+                          const double *sig, const double *dsig, const double *tt, const double *q, const double *gt,
+                          double *dt_ground, double *dt_air, double *olr, double *words, std::string *err);
+int pe25d_set_gas_radiation(Pe25d *m, const gcm_gas_radiation_par *g, hipStream_t s, std::string *err);
+bool pe25d_gas_radiation_on(const Pe25d *m);
+const gcm_gas_radiation_par *pe25d_gas_radiation_par(const Pe25d *m);
+int pe25d_gas_radiation_tables(Pe25d *m, const gcm_gas_radiation_par *g, const double *lat, const double *lon, hipStream_t s,
+                               std::string *err);
+int pe25d_gas_radiation_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, double dt, double utc, hipStream_t s,
+                             std::string *err);
+int pe25d_gas_radiation(Pe25d *m, bool apply, double dt, double utc, const gcm_gas_radiation_par *g, const double *lat, const double *lon,
+                        double *dtg_host, double *dt_air_host, double *olr_host, hipStream_t s, std::string *err);
 // Horizontal diffusion (pe25d_hdiff.hip).  hdiff_check / hdiff_tables / hdiff_apply: no handle, no device
 // (gcm_hdiff_tables, gcm_hdiff_apply).  pe25d_hdiff_fits: what a registration or a step needs of the handle -- a single
 // domain, W >= 4 and H >= 4, or a band that has opted in (GCM_ERR_UNSUPPORTED); pe25d_set_hdiff: gcm_set_hdiff (d == nullptr: off, the landing fields

@@ -337,6 +337,8 @@ int pe25d_physics_tables(Pe25d *m, double t_lw, double t_sw, const double *lat, 
 // the tables must be in place (pe25d_physics_tables)
 int pe25d_solar_rows(Pe25d *m, int set, int j0, int j1, int jb0, int jb1, bool keep_ghosts, double dt, double utc, double albedo,
                      hipStream_t s, std::string *err) {
+    // gcm_set_gas_radiation: the registered gas radiation takes the solar step's place (pe25d_gas_radiation.hip)
+    if (pe25d_gas_radiation_on(m)) return pe25d_gas_radiation_rows(m, set, j0, j1, jb0, jb1, keep_ghosts, dt, utc, s, err);
     if (set < 0) set = m->cur_i;
     const double hour_angle = utc / (-24 * 3600.0) * 360 * (M_PI / 180);      // grey_solar.py:51
     const bool budget = m->slab.on;                        // the slab ocean advances the ground temperature

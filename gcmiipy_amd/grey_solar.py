@@ -44,6 +44,25 @@ def basic_grey_radiation(p, tp, tt, g, t_lw, t_sw, albedo, utc, geom):
     return c.grey_radiation(geom, scalar(utc), t_lw, t_sw, albedo)
 
 
+def grey_radiation(p, q, tt, c, g, utc, dt, geom):
+    """grey_solar.py:192-320 -> (dt_ground, dt_air, thermal_upwelling[-1]): the grey radiation that absorbs by water
+    vapour and CO2, with the reference's weights and its uniform insolation.  `tt` is the true temperature (converted
+    back to theta for the resident state); `dt` is not read, as in the reference.  Clouds are not modelled: ValueError
+    for a cloud fraction c != 0 (the reference's only call passes 0.0)."""
+    if np.any(np.asarray(strip(c)[0]) != 0):
+        raise ValueError("grey_radiation: clouds are not modelled, c must be 0")
+    shp3, shp2 = (geom.layers, geom.height, geom.width), (geom.height, geom.width)
+    pm = as_f64(strip(p)[0], shp2, "p")
+    ttm = as_f64(strip(tt)[0], shp3, "tt")
+    qm = as_f64(strip(q)[0], shp3, "q")
+    theta = ttm * ((100000.0 / (pm * geom.sig + geom.ptop)) ** (287.0 / 1004.0))   # temperature.py:15-19
+    core = core_for(geom)
+    z = as_f64(theta * 0.0, shp3)
+    core.set_state(pm, z, z, theta, qm)
+    core.set_ground(as_f64(_gt(g), shp2, "gt"))
+    return core.gas_radiation(geom, scalar(utc))
+
+
 def solar_timestep(t, p, g, dt, utc, geom):
     """no_limits_2_5d.py:66-75 -> (t_n, g_n) with t_lw = 0.1, t_sw = 0.9, albedo = 0.3."""
     shp3, shp2 = (geom.layers, geom.height, geom.width), (geom.height, geom.width)

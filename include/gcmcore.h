@@ -1013,6 +1013,72 @@ int gcm_put_slab_ocean(gcm_handle *h, const double *sums, double seconds, int64_
 int gcm_slab_ocean_reset(gcm_handle *h);
 int gcm_slab_ocean_cells(int n, const gcm_slab_ocean *so, double dt, const double *gt, const double *C, const double *words,
                          const double *Q, double *gt_out, double *E4_out);
+/* Grey radiation of GCM_PE25D that absorbs by water vapour and CO2, on the device (fp64 and fp32 handles; single domains
+ * and latitude bands): the reference's grey_radiation (grey_solar.py:192-320) with clouds off (c = 0), as a phase that
+ * takes the solar step's place.  The grey scheme of gcm_set_physics spreads two numbers for the whole planet over the
+ * levels; here a level's optical depth comes from its own q and a CO2 mixing ratio, so a moist column and a dry one
+ * radiate differently.  Float64 arithmetic on either storage type, every operation rounded on its own, one lane per
+ * column.  Per level k (sig, dsig the level table, Rd = 287, G = 9.8, Cp = 1004, sb = 5.67e-8, Cg = 1.13e6):
+ *   tp = p sig + ptop     tt = theta exner(tp)     rho = tp / (Rd tt)     depth = (p dsig) / (rho G)
+ *   a_sw = 0 + qc rho depth k_h2o_sw + co2 rho depth k_co2_sw      a_lw likewise with the long-wave weights
+ *   T_sw = 10^-a_sw       e_lw = 1 - 10^-a_lw      E = sb tt^4 e_lw
+ * qc = max(q, 0): a negative q left by the transport cannot give a transmittance above 1; co2 = co2_vmr M_CO2 / Md
+ * (44.010 and 28.97 g / mol).  Top-down scan (SWd[L] = SC, LWd[L] = 0): abs_k = SWd (1 - T_sw), SWd -= that;
+ * abs_k += LWd e_lw, LWd = LWd - that + E.  Ground (black, albedo a_g): U_s = sb gt^4, gain = (1 - a_g) SWd[0] + LWd[0],
+ * dt_ground = (gain - U_s) / Cg / 0.1.  Bottom-up scan (LWu[0] = U_s): abs_k += LWu e_lw, LWu = LWu - that + E.
+ * dt_air_k = (abs_k - 2 E) / (Cp rho depth); OLR = LWu[L].  The in-place form is solar_timestep's statements:
+ * gt += dt_ground dt, tt += dt_air dt, theta = tt / exner.  The column closes: sum_k Cp rho depth dt_air +
+ * (gain - U_s) + a_g SWd[0] + OLR = SC, to rounding.  When both weight pairs are equal (the defaults) the level's power
+ * is evaluated once for both bands.
+ * Insolation SC: GCM_INSOLATION_UNIFORM, the reference's solar_constant 0.5 0.5; GCM_INSOLATION_ZENITH, solar_constant
+ * max(sin lat sin d + cos lat cos d cos(lon + hour_angle), 0) with the hour angle of the grey kernel
+ * (utc / (-24 h) 360 degrees) and the fixed declination d; GCM_INSOLATION_DAILY, the reference's
+ * daily_average_irradiance(lat, d) with solar_constant, a host-built table per global row, the arccos argument kept
+ * inside [-1, 1] (the reference gives NaN in polar night and polar day: the one departure from it).
+ * gcm_set_gas_radiation(h, par): while gcm_set_physics is on AND this is registered, the solar step of every step taken
+ * by gcm_step, gcm_band_run and gcm_end_step launches this kernel instead of the grey one, at the physics registration's
+ * clock, lat and lon; its t_lw, t_sw and albedo are then unused.  Registering without physics is allowed and takes
+ * effect when physics comes on.  It needs gcm_set_ground.  par = NULL unregisters: the grey scheme again.  Without a
+ * registration nothing is launched, allocated or changed on any path.  While the slab ocean is registered the launch
+ * leaves the ground temperature to it and stores the flux words GCM_SLAB_SC = SC, GCM_SLAB_SW_SFC = (1 - a_g) SWd[0],
+ * GCM_SLAB_LW_DOWN = LWd[0], GCM_SLAB_LW_UP = U_s and GCM_SLAB_OLR = LWu[L]; the short wave the surface sends back to
+ * space is then a_g SW_SFC / (1 - a_g).  Latitude bands: the phase is column-local, q travels in the message already;
+ * ghost rows are advanced locally with the latitude of their global row, to the neighbour's bits.
+ * gcm_gas_radiation_on: 1 where registered, else 0 (a null handle GCM_ERR_ARG).
+ * gcm_gas_radiation(h, utc, par, lat, lon, dt_ground, dt_air, olr): the diagnostic form on the current state: lat
+ * [global_height], lon [W]; dt_ground [H][W], dt_air [L][H][W], olr [H][W], any of them may be NULL; dt_air passes
+ * through the handle's storage type, dt_ground and olr are float64.  gcm_gas_radiation_step(h, dt, utc, par, lat, lon):
+ * once in place; on a band own rows and ghost rows, as gcm_solar_step.
+ * gcm_gas_radiation_columns: the column routine on its own, on the host, the very routine the kernel calls, no handle, no
+ * device: ncol columns with SC, p, gt [ncol], the true temperature tt and q [L][ncol], sig and dsig [L] -> dt_ground
+ * [ncol], dt_air [L][ncol], olr [ncol] and words [5][ncol] in the order GCM_SLAB_SC .. GCM_SLAB_OLR; any output may be NULL.
+ * gcm_gas_insolation(kind, nlat, lat, declination, solar_constant, out): the row table out [nlat] of "uniform" and
+ * "daily"; "zenith" has none (GCM_ERR_ARG).
+ * Errors, all checked in the call; a refused call changes nothing.  GCM_ERR_ARG: a null handle, a weight, co2_vmr or
+ * solar_constant that is not finite or negative, ground_albedo outside [0, 1), |declination| > pi / 2, an unknown
+ * insolation, a non-finite utc or dt, missing lat or lon.  GCM_ERR_UNSUPPORTED: other models, more than 120 levels.
+ * GCM_ERR_STATE: no ground temperature set (gcm_set_ground).                                                             */
+enum { GCM_INSOLATION_UNIFORM = 0, GCM_INSOLATION_ZENITH = 1, GCM_INSOLATION_DAILY = 2 };
+typedef struct {
+    double k_h2o_lw;             /* m^2 / kg: long-wave weight of water vapour (0.125)                */
+    double k_co2_lw;             /* m^2 / kg: long-wave weight of CO2 (1)                             */
+    double k_h2o_sw;             /* m^2 / kg: short-wave weight of water vapour (0.125)               */
+    double k_co2_sw;             /* m^2 / kg: short-wave weight of CO2 (1: the reference's placeholder) */
+    double co2_vmr;              /* volume mixing ratio of CO2 (300e-6)                               */
+    double ground_albedo;        /* [0, 1) (0.1)                                                      */
+    double solar_constant;       /* W / m^2 (2 * 41840 / 60)                                          */
+    double declination;          /* radians, |d| <= pi / 2 (0)                                        */
+    int32_t insolation;          /* GCM_INSOLATION_* (GCM_INSOLATION_UNIFORM)                         */
+} gcm_gas_radiation_par;
+int gcm_set_gas_radiation(gcm_handle *h, const gcm_gas_radiation_par *par);
+int gcm_gas_radiation_on(const gcm_handle *h);
+int gcm_gas_radiation(gcm_handle *h, double utc, const gcm_gas_radiation_par *par, const double *lat, const double *lon,
+                      double *dt_ground, double *dt_air, double *olr);
+int gcm_gas_radiation_step(gcm_handle *h, double dt, double utc, const gcm_gas_radiation_par *par, const double *lat, const double *lon);
+int gcm_gas_radiation_columns(int ncol, int L, const gcm_gas_radiation_par *par, const double *SC, const double *p, double ptop,
+                              const double *sig, const double *dsig, const double *tt, const double *q, const double *gt,
+                              double *dt_ground, double *dt_air, double *olr, double *words);
+int gcm_gas_insolation(int kind, int nlat, const double *lat, double declination, double solar_constant, double *out);
 /* Zonal-mean climatology of GCM_PE25D accumulated on the device: what a Held-Suarez run is evaluated by -- the time and
  * zonal means of u, v, theta and T, their variances and the eddy fluxes as functions of latitude and level -- without a
  * host round trip per step (fp64 and fp32 handles, single domains and latitude bands).  One launch per sample reads
