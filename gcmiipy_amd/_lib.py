@@ -27,6 +27,7 @@ SPEC_PLAN_WORDS = 6                  # GCM_SPEC_PLAN_WORDS
 HDIFF_U, HDIFF_V, HDIFF_T, HDIFF_Q = 1, 2, 4, 8     # GCM_HDIFF_*
 HDIFF_PLAN_WORDS = 7                 # GCM_HDIFF_PLAN_WORDS
 SW2D_PLAN_WORDS = 9                  # GCM_SW2D_PLAN_WORDS
+SW2D_PAIR_WORDS = 2                  # GCM_SW2D_PAIR_WORDS
 PHASE_HELD_SUAREZ, PHASE_MOIST, PHASE_CLIMATE, PHASE_TRACER_FORCING = range(4)   # gcm_pe25d_phase
 PHASE_PLAN_WORDS = 5                 # GCM_PHASE_PLAN_WORDS
 # GCM_STAGE_*: the words of gcm_pe25d_stage_geometry / gcm_pe25d_stage_plan in order, as Core.stage_plan() names them
@@ -170,6 +171,7 @@ SYMBOLS = {
     "gcm_step": (C.c_int, [_H, C.c_int, C.c_double]),
     "gcm_sw2d_plan": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "gcm_sw2d_fused_depth": (C.c_int, [_H]),
+    "gcm_sw2d_pair_info": (C.c_int, [_H, C.POINTER(C.c_int), C.c_int]),
     "gcm_pe25d_phase_geometry": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int), C.c_int]),
     "gcm_pe25d_phase_plan": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "gcm_pe25d_stage_geometry": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_uint), C.c_int, C.POINTER(C.c_int), C.c_int]),

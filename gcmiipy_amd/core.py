@@ -1437,6 +1437,14 @@ class Core:
                     rows_per_band=out[1], cols=out[2], strip=out[3], strip2=out[4], two_step_launches=out[5],
                     single_step_launches=out[6], preload=bool(out[7]), stream=bool(out[8]))
 
+    def sw2d_pair(self):
+        """the wave pair of float64 GCM_SW2D_TEMP, two steps per launch (gcm_sw2d_pair_info): a dict of active (a
+        step(n >= 2, .) goes through it: GCM_SW2D_PAIR=0|1 when the handle was created, else the library's default)
+        and rows_per_band (its own band length, GCM_SW2D_PAIR_ROWS pins it; 0: a handle the pair never serves)"""
+        out = (C.c_int * _lib.SW2D_PAIR_WORDS)()
+        _check(lib.gcm_sw2d_pair_info(self._h, out, _lib.SW2D_PAIR_WORDS), self._h)
+        return dict(active=bool(out[0]), rows_per_band=out[1])
+
     def phase_plan(self, phase, rows=None, accumulate=True):
         """the launch geometry of a GCM_PE25D phase over `rows` rows (None: the handle's own; the explicit phase calls
         of a band launch its four ghost rows too), without launching anything (gcm_pe25d_phase_plan).  phase:

@@ -79,6 +79,8 @@ struct gcm_handle {
     int esz = 8;            // bytes per element of the 2-D state
     int cols = 1;           // fused kernel: columns per lane (2: fp32 with an even width, 120-column strips)
     int depth_pin = 0;      // GCM_SW2D_DEPTH at gcm_create (float64 GCM_SW2D_TEMP only): 1 or 3 pins the fused form's depth, 0: none
+    int pair_pin = -1;      // GCM_SW2D_PAIR at gcm_create (float64 GCM_SW2D_TEMP only): 0 or 1 pins the wave pair off or on, -1: none
+    int pair_rows = 0;      // the wave pair's own band length (sw2d_pair_rows_per_band); 0: a handle the pair never serves
     double *staging = nullptr;  // fp32 handles: float64 staging buffer of state transfers, staging_members members
     int staging_members = 0;
 

@@ -173,6 +173,14 @@ int gcm_create(const gcm_config *cfg, gcm_handle **out) {
                 if (temp && !h->f32 && (e[0] == '1' || e[0] == '3') && !e[1]) h->depth_pin = e[0] - '0';
             h->rows_per_band = h->f32 ? sw2d_fused_rows_per_band<float>(h->W, h->H, temp, tr, h->wrap, h->M, h->cols)
                                       : sw2d_fused_rows_per_band<double>(h->W, h->H, temp, tr, h->wrap, h->M, 1, h->depth_pin);
+            // the wave pair (two steps per launch, sw2d_pair_kernel): its band length and its switch, for the handles
+            // it can serve at all -- float64 GCM_SW2D_TEMP, fused, one member, a periodic single domain
+            if (temp && !h->f32 && h->variant == GCM_VARIANT_FUSED && h->M == 1 && h->wrap) {
+                if (const char *e = getenv("GCM_SW2D_PAIR"))
+                    if ((e[0] == '0' || e[0] == '1') && !e[1]) h->pair_pin = e[0] - '0';
+                const Sw2dFusedForm f = sw2d_fused_form(temp, tr, h->rows_per_band, h->W, h->H, h->M, h->esz, h->depth_pin);
+                h->pair_rows = sw2d_pair_rows_per_band<double>(h->W, h->H, tr, f.stream);
+            }
             break;
         }
         case GCM_PE2D: {
@@ -474,6 +482,28 @@ static bool steps_in_pairs(gcm_handle *h) {
     return sw2d_fused2_serves(a.wrap_j, a.j0, a.j1, a.H, a.rows_per_band);
 }
 
+// Whether gcm_step takes its steps in pairs through the wave pair (sw2d_pair_kernel): a handle it can serve
+// (pair_rows: float64 GCM_SW2D_TEMP, fused, one member, periodic), no per-launch timing, and either GCM_SW2D_PAIR=1 or,
+// with the switch unset, the default below.  Shared by gcm_step, gcm_sw2d_plan and gcm_sw2d_pair_info.
+static bool steps_in_wave_pairs(gcm_handle *h) {
+    if (h->pair_rows <= 0 || h->time.on) return false;
+    if (!sw2d_pair_serves(h->wrap ? 1 : 0, 0, h->H, h->H, h->W, h->M, h->pair_rows)) return false;
+    if (h->pair_pin >= 0) return h->pair_pin == 1;
+    // the grids the deep march streams, the rule that picks depth 3: 0.77 of the single steps' time on C3
+    const Sw2dFusedForm f = sw2d_fused_form(true, h->has[GCM_Q] ? h->cfg.tracer : 0, h->rows_per_band, h->W, h->H, h->M, h->esz, h->depth_pin);
+    return f.stream && f.depth == 3;
+}
+
+static bool run_pair(gcm_handle *h, double dt) {
+    const int tracer = h->has[GCM_Q] ? h->cfg.tracer : 0;
+    Sw2dArgs a = fused2_args(h, dt);
+    a.ot = h->nxt[GCM_T];
+    a.oq = h->nxt[GCM_Q];
+    a.rows_per_band = h->pair_rows;
+    const Sw2dFusedForm f = sw2d_fused_form(true, tracer, h->rows_per_band, h->W, h->H, h->M, h->esz, h->depth_pin);
+    return launch_sw2d_pair(a, tracer, f.stream, h->stream);
+}
+
 // the rows a band's next single step produces beyond its own, per side: each step consumes two ghost rows per side;
 // the rows still valid shrink towards the interior until the next exchange (communication-avoiding deep halo)
 static int step_extra_rows(const gcm_handle *h) { return h->wrap ? 0 : h->G - kGhost * (h->since_exchange + 1); }
@@ -496,6 +526,14 @@ int gcm_step(gcm_handle *h, int nsteps, double dt) {
             swap_state(h);
             n0 += 2;
         }
+    } else if (steps_in_wave_pairs(h)) {
+        for (; nsteps - n0 >= 2; n0 += 2) {
+            if (!run_pair(h, dt)) {
+                h->launch_refused = true;
+                return launch_status(h);
+            }
+            swap_state(h);
+        }
     }
     for (int n = n0; n < nsteps; ++n) {
         const int e = step_extra_rows(h);
@@ -514,7 +552,7 @@ int gcm_sw2d_plan(gcm_handle *h, int nsteps, int *out, int nout) {
     if (!h || h->pe || nsteps < 0 || !out || nout < GCM_SW2D_PLAN_WORDS) return GCM_ERR_ARG;
     const bool fused = h->variant == GCM_VARIANT_FUSED;
     const bool temp = h->cfg.model == GCM_SW2D_TEMP;
-    const int pairs = steps_in_pairs(h) ? nsteps / 2 : 0;
+    const int pairs = steps_in_pairs(h) || steps_in_wave_pairs(h) ? nsteps / 2 : 0;
     const int e = step_extra_rows(h);
     Sw2dFusedForm f{false, false, 1};
     if (fused)
@@ -539,6 +577,15 @@ int gcm_sw2d_fused_depth(gcm_handle *h) {
     const int e = step_extra_rows(h);
     return sw2d_fused_form(h->cfg.model == GCM_SW2D_TEMP, h->has[GCM_Q] ? h->cfg.tracer : 0, h->rows_per_band, h->W,
                            h->H + 2 * e, h->M, h->esz, h->depth_pin).depth;
+}
+
+// the wave pair of a 2-D handle: whether gcm_step's next call of two or more steps goes through it, and its own band
+// length (0: a handle it never serves)
+int gcm_sw2d_pair_info(gcm_handle *h, int *out, int nout) {
+    if (!h || h->pe || !out || nout < GCM_SW2D_PAIR_WORDS) return GCM_ERR_ARG;
+    out[0] = steps_in_wave_pairs(h) ? 1 : 0;
+    out[1] = h->pair_rows;
+    return GCM_OK;
 }
 
 int gcm_step_interior(gcm_handle *h, double dt, void *stream) {

@@ -178,6 +178,22 @@ struct Row {
     T u, uw, v, vw, p, st, g, irho;   // uw, vw: west neighbours, shifted once per row
 };
 
+// Where FusedCtx::iter puts an output row.  NoSink: the field arrays of the argument block, as every single-step kernel
+// does.  RingSink: one row slot [field][lane] in LDS, all 64 lanes (sw2d_pair_kernel: the first step's rows, which the
+// second step's wave reads back).
+struct NoSink {};
+template <bool TRACER>
+struct RingSink {
+    double *row;   // the slot, at this lane
+    __device__ __forceinline__ void put(double u, double v, double p, double t, double q) const {
+        row[0] = u;
+        row[64] = v;
+        row[128] = p;
+        row[192] = t;
+        if (TRACER) row[256] = q;
+    }
+};
+
 template <bool TEMP, typename T>
 __device__ __forceinline__ void make_row_r(Row<T> &r, T u, T v, T p, T t, const double *tab, T rcp_p) {
     r.u = u;
@@ -311,10 +327,10 @@ struct FusedCtx {
     // slots that holds row r+2, and it is refilled with row min(r+5, jb+1), unconditionally, so that no branch stands
     // around a load.  LEAD names what the caller knows of r: 0 r == ja-1 (neither flux nor corrector), 1 r == ja
     // (no corrector), 2 r > ja (both, unconditionally); -1: decided from r here.  ROWBUF: the deep march's stores
-    // (store_row_lanes).
-    template <bool FETCH = true, int AHEAD = 3, int LEAD = -1, bool ROWBUF = false>
+    // (store_row_lanes).  Sink: where the output row goes instead of the field arrays (RingSink); NoSink: the arrays.
+    template <bool FETCH = true, int AHEAD = 3, int LEAD = -1, bool ROWBUF = false, class Sink = NoSink>
     __device__ __forceinline__ void iter(int r, Row<V> &BM, Row<V> &B0, Row<V> &BP, Row<V> &SN, Row<V> &SM,
-                                         Row<V> &S0, Raw<V> &nxt, V &qmm, V &qm, V &q0, V &qp) {
+                                         Row<V> &S0, Raw<V> &nxt, V &qmm, V &qm, V &q0, V &qp, Sink sink = Sink()) {
         const V dt = V(a.dt), g_dx = V(a.g_dx), h_dx = V(a.h_dx), mu_dx2 = V(a.mu_dx2), dtdx = V(a.dtdx);
         // ---- predictor: predicted row r from base rows r-1, r, r+1
         {
@@ -347,7 +363,9 @@ struct FusedCtx {
                 const V f1 = face_flux<TRACER == 2>(BM.u, qs_w, qs, qs_e, qs_ee, dtdx);
                 qn = qs - f1 + from_west(f1);
             }
-            if constexpr (ROWBUF) {
+            if constexpr (!std::is_same_v<Sink, NoSink>) {
+                sink.put(un, vn, pn, tn, qn);
+            } else if constexpr (ROWBUF) {
                 const long o = (long)(r - 1) * a.W;
                 const unsigned lane_off = store_lane ? (unsigned)col * 8u : kNoStore;
                 store_row_lanes(a.ou + o, a.W, lane_off, un);
@@ -669,6 +687,190 @@ bool launch_sw2d_fused2(const Sw2dArgsT<T> &a, hipStream_t s) {
                    : a.rows_per_band == 3 ? (ens ? (const void *)sw2d_fused2_kernel<T, 3, true> : (const void *)sw2d_fused2_kernel<T, 3, false>)
                                           : (ens ? (const void *)sw2d_fused2_kernel<T, 4, true> : (const void *)sw2d_fused2_kernel<T, 4, false>);
     return hipLaunchKernel(fn, g, dim3(64), params, 0, s) == hipSuccess;
+}
+
+// ------------------------------------------------------------------ two steps per launch, streaming grids
+// GCM_SW2D_TEMP at float64 on a grid far beyond the caches: the deep march is on the memory ceiling of its access
+// pattern, and every step sends the whole state to HBM and fetches it back.  Here a workgroup of TWO waves owns a tile
+// (band, 56-column strip) and does two Matsuno steps: wave 0 is the deep march (three request slots, clamped refill,
+// peeled rows, own_copy) over the band extended by two rows each way, [ja - 2, jb + 2), and its output rows go to a
+// ring of row slots in LDS; wave 1 runs the second step on those rows -- FusedCtx::iter in the form that takes rows
+// the caller already has -- and stores rows [ja, jb).  Lane <-> column is the same in both waves, col = i0 - 4 + lane;
+// the first step is valid on lanes 2 .. 61, the second on lanes 4 .. 59, so a ring row is [field][lane].  A second
+// pipeline inside ONE wave (sw2d_fused2_kernel) needs about 250-260 VGPRs with theta and a tracer; here each wave keeps
+// the footprint of the single-step march.
+//
+// Trips and barriers.  A trip is three rows.  The first step's output rows are numbered k = 0 .. rows + 3 (row
+// ja - 2 + k); wave 0 writes rows 3t .. 3t + 2 in trip t, into ring rows k % 6, i.e. the ring is two groups of three
+// rows and trip t writes group t & 1.  Wave 1 reads, in trip t >= 1, the group trip t - 1 wrote: rows 0 .. 2 make its
+// window in trip 1, and from trip 2 on row k = n + 3 is the row r + 2 that its n-th iter (r = ja - 1 + n) slides in.
+// ONE __syncthreads() ends every trip of either wave, nothing else synchronises them: the group a wave touches in trip
+// t is the one the other wave touched in trip t - 1 and will touch in trip t + 1.  Both waves take 3 + (rows + 1) / 3
+// trips -- wave 1 has the rows + 2 iters of a band behind two trips of waiting; wave 0 needs ceil((rows + 4) / 3) and
+// takes the barriers of the trips it has nothing to do in -- which depends on the band's row count alone, and no barrier
+// stands under a lane mask: the role is wave-uniform.  The last rows wave 1 slides in (beyond k = rows + 3) are whatever
+// the ring holds; they enter window rows no output row reads.
+constexpr int kPairRowDoubles = 5 * 64;                 // a ring row: [field][lane]
+constexpr int kPairGroupDoubles = 3 * kPairRowDoubles;  // the ring: two groups of three rows (15 KB)
+
+template <int TRACER, bool STREAM>
+__global__ __launch_bounds__(128, 2) void sw2d_pair_kernel(Sw2dArgsT<double> a) {
+    using Ctx = FusedCtx<double, true, TRACER, true, STREAM, 1>;
+    using Sink = RingSink<TRACER != 0>;
+    const int W = a.W;
+    const int lane = threadIdx.x & 63;
+    const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    // tiles (band, strip) as in sw2d_fused_kernel, one member
+    const int strips = (W + kStrip2Cols - 1) / kStrip2Cols;
+    const int per_xcd = gridDim.x / 8;
+    const int tile = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    const int band = tile / strips;
+    const int i0 = (tile - band * strips) * kStrip2Cols;
+    __shared__ double tab[kExnerTabDoubles];
+    __shared__ double ring[2 * kPairGroupDoubles];
+    for (int k = 0; k < kExnerTabDoubles / 128; ++k) tab[threadIdx.x + 128 * k] = a.exner_tab[threadIdx.x + 128 * k];
+    __syncthreads();
+    const int ja = band * a.rows_per_band;          // (all rows of a periodic grid: sw2d_pair_serves)
+    const int jb = min(ja + a.rows_per_band, a.H);
+    if (ja >= jb) return;                           // the padding tiles: both waves leave
+    const int col = i0 - 4 + lane;
+    Ctx c{a, tab};
+    c.col = col;
+    c.ci = col % W;
+    if (c.ci < 0) c.ci += W;
+    c.f0_prev = 0.0;
+    Row<double> A, B, C, X, Y, Z;
+    int g = 0;                                      // the group of this trip, as an offset into the ring
+    if (role == 0) {
+        // ---- the first step: the deep march of sw2d_fused_kernel over [ja - 2, jb + 2), rows to the ring
+        c.ja = ja - 2;
+        c.jb = jb + 2;
+        c.store_lane = false;
+        const int j0 = c.ja, j1 = c.jb;
+        int left = 3 + (jb - ja + 1) / 3;           // barriers still to take
+        double *const slot = ring + lane;
+        const Raw<double> w0 = c.load(j0 - 2), w1 = c.load(j0 - 1), w2 = c.load(j0);
+        Raw<double> n0 = c.load(j0 + 1), n1 = c.load(j0 + 2), n2 = c.load(j0 + 3);   // (j0 + 3 < j1 + 1)
+        make_row<true>(A, w0.u, w0.v, w0.p, w0.t, tab);
+        make_row<true>(B, w1.u, w1.v, w1.p, w1.t, tab);
+        make_row<true>(C, w2.u, w2.v, w2.p, w2.t, tab);
+        double qmm = 0.0, qm = w0.q, q0 = w1.q, qp = w2.q;
+        X = Y = Z = A;  // overwritten before first use
+        c.template iter<true, 5, 0, true>(j0 - 1, A, B, C, X, Y, Z, n0, qmm, qm, q0, qp);
+        c.template iter<true, 5, 1, true>(j0, B, C, A, Y, Z, X, n1, qmm, qm, q0, qp);
+        int r = j0 + 1;                   // rows j0+1 .. j1, three per trip
+        for (; r + 2 <= j1; r += 3) {
+            c.template iter<true, 5, 2, true>(r, C, A, B, Z, X, Y, n2, qmm, qm, q0, qp, Sink{slot + g});
+            c.template iter<true, 5, 2, true>(r + 1, A, B, C, X, Y, Z, n0, qmm, qm, q0, qp, Sink{slot + g + kPairRowDoubles});
+            c.template iter<true, 5, 2, true>(r + 2, B, C, A, Y, Z, X, n1, qmm, qm, q0, qp, Sink{slot + g + 2 * kPairRowDoubles});
+            g ^= kPairGroupDoubles;
+            __syncthreads();
+            --left;
+        }
+        if (r <= j1) {                    // (the rows these would ask for are beyond j1+1)
+            c.template iter<false, 3, 2, true>(r, C, A, B, Z, X, Y, n2, qmm, qm, q0, qp, Sink{slot + g});
+            if (r + 1 <= j1) c.template iter<false, 3, 2, true>(r + 1, A, B, C, X, Y, Z, n0, qmm, qm, q0, qp, Sink{slot + g + kPairRowDoubles});
+            __syncthreads();
+            --left;
+        }
+        for (; left > 0; --left) __syncthreads();   // the trips in which only the second step has rows
+    } else {
+        // ---- the second step on the ring's rows: rows [ja, jb) to memory
+        c.ja = ja;
+        c.jb = jb;
+        c.store_lane = lane >= 4 && lane < 60 && col < W;
+        const double *const slot = ring + lane;
+        auto rd = [slot](int off) {
+            const double *p = slot + off;
+            Raw<double> x;
+            x.u = p[0];
+            x.v = p[64];
+            x.p = p[128];
+            x.t = p[192];
+            x.q = TRACER ? p[256] : 0.0;
+            return x;
+        };
+        __syncthreads();                  // trip 0: nothing to read yet
+        const Raw<double> w0 = rd(0), w1 = rd(kPairRowDoubles), w2 = rd(2 * kPairRowDoubles);   // rows ja-2 .. ja
+        make_row<true>(A, w0.u, w0.v, w0.p, w0.t, tab);
+        make_row<true>(B, w1.u, w1.v, w1.p, w1.t, tab);
+        make_row<true>(C, w2.u, w2.v, w2.p, w2.t, tab);
+        double qmm = 0.0, qm = w0.q, q0 = w1.q, qp = w2.q;
+        X = Y = Z = A;  // overwritten before first use
+        __syncthreads();                  // trip 1: the window
+        g = kPairGroupDoubles;
+        // trip 2: the two rows ahead of the first output row and that row, as the deep march peels them (a band has
+        // rows + 2 >= 3 iters)
+        Raw<double> nxt = rd(g);
+        c.template iter<false, 3, 0, true>(ja - 1, A, B, C, X, Y, Z, nxt, qmm, qm, q0, qp);
+        nxt = rd(g + kPairRowDoubles);
+        c.template iter<false, 3, 1, true>(ja, B, C, A, Y, Z, X, nxt, qmm, qm, q0, qp);
+        nxt = rd(g + 2 * kPairRowDoubles);
+        c.template iter<false, 3, 2, true>(ja + 1, C, A, B, Z, X, Y, nxt, qmm, qm, q0, qp);
+        g ^= kPairGroupDoubles;
+        __syncthreads();
+        int r = ja + 2;                   // rows ja+2 .. jb, three per trip
+        for (; r + 2 <= jb; r += 3) {
+            nxt = rd(g);
+            c.template iter<false, 3, 2, true>(r, A, B, C, X, Y, Z, nxt, qmm, qm, q0, qp);
+            nxt = rd(g + kPairRowDoubles);
+            c.template iter<false, 3, 2, true>(r + 1, B, C, A, Y, Z, X, nxt, qmm, qm, q0, qp);
+            nxt = rd(g + 2 * kPairRowDoubles);
+            c.template iter<false, 3, 2, true>(r + 2, C, A, B, Z, X, Y, nxt, qmm, qm, q0, qp);
+            g ^= kPairGroupDoubles;
+            __syncthreads();
+        }
+        if (r <= jb) {
+            nxt = rd(g);
+            c.template iter<false, 3, 2, true>(r, A, B, C, X, Y, Z, nxt, qmm, qm, q0, qp);
+            if (r + 1 <= jb) {
+                nxt = rd(g + kPairRowDoubles);
+                c.template iter<false, 3, 2, true>(r + 1, B, C, A, Y, Z, X, nxt, qmm, qm, q0, qp);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+template <typename T>
+static const void *pair_kernel_ptr(int tracer, bool stream) {
+    static_assert(std::is_same_v<T, double>, "the wave pair exists at float64 only");
+    if (tracer == 0) return stream ? (const void *)sw2d_pair_kernel<0, true> : (const void *)sw2d_pair_kernel<0, false>;
+    if (tracer == 1) return stream ? (const void *)sw2d_pair_kernel<1, true> : (const void *)sw2d_pair_kernel<1, false>;
+    return stream ? (const void *)sw2d_pair_kernel<2, true> : (const void *)sw2d_pair_kernel<2, false>;
+}
+
+// Rows per workgroup of the wave pair: one resident round -- as many workgroups as the chip holds at the kernel's
+// footprint (C3: 4 per CU, 1024; 74 strips x 13 bands of 158 rows).  GCM_SW2D_PAIR_ROWS pins it.
+template <typename T>
+int sw2d_pair_rows_per_band(int W, int H, int tracer, bool stream) {
+    if (const char *e = getenv("GCM_SW2D_PAIR_ROWS")) {
+        int v = atoi(e);
+        if (v > 0) return v;
+    }
+    int wgs_per_cu = 4, cus = 256, dev = 0, nb = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+        cus = prop.multiProcessorCount;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pair_kernel_ptr<T>(tracer, stream), 128, 0) == hipSuccess && nb > 0)
+        wgs_per_cu = nb;
+    const long strips = (W + kStrip2Cols - 1) / kStrip2Cols;
+    long bands = (long)wgs_per_cu * cus / strips;   // floor: stay within the round
+    if (bands < 1) bands = 1;
+    const long rpb = (H + bands - 1) / bands;
+    return (int)(rpb < 8 ? 8 : rpb);
+}
+
+// two Matsuno steps of float64 GCM_SW2D_TEMP in one launch (sw2d_pair_serves); false: refused
+template <typename T>
+bool launch_sw2d_pair(const Sw2dArgsT<T> &a, int tracer, bool stream, hipStream_t s) {
+    if (!sw2d_pair_serves(a.wrap_j, a.j0, a.j1, a.H, a.W, a.members, a.rows_per_band)) return false;
+    const int strips = (a.W + kStrip2Cols - 1) / kStrip2Cols;
+    const int bands = (a.H + a.rows_per_band - 1) / a.rows_per_band;
+    dim3 g((unsigned)(((long)strips * bands + 7) / 8 * 8));
+    Sw2dArgsT<T> arg = a;
+    void *params[] = {&arg};
+    return hipLaunchKernel(pair_kernel_ptr<T>(tracer, stream), g, dim3(128), params, 0, s) == hipSuccess;
 }
 
 template <typename T, bool TEMP, int TRACER, int CPL = 1>

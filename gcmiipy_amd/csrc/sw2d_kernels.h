@@ -20,6 +20,11 @@ constexpr int sw2d_fused_strip_cols(int cols) { return cols * kStripCols; }
 inline bool sw2d_fused2_serves(int wrap_j, int j0, int j1, int H, int rows_per_band) {
     return wrap_j && j0 == 0 && j1 == H && rows_per_band >= 2 && rows_per_band <= 4;
 }
+// whether the wave pair (sw2d_pair_kernel: two steps of float64 GCM_SW2D_TEMP per launch) serves a launch: periodic
+// rows, all of them, one member, a width whose rows the second step's buffer stores address (as the deep march's)
+inline bool sw2d_pair_serves(int wrap_j, int j0, int j1, int H, long W, int members, int rows_per_band) {
+    return wrap_j && j0 == 0 && j1 == H && members == 1 && rows_per_band >= 1 && W < (1L << 27);
+}
 // the form of the single-step kernel: preloading (plain SW2D, short bands) or rolling, and the rolling one's STREAM
 // instantiation where the rows of one launch (all members, `esz` bytes an element) are beyond the 256 MB Infinity Cache
 // depth: rows of requests a wave of the rolling form keeps in flight.  3 -- the deep march, two waves per SIMD -- where
@@ -104,6 +109,11 @@ int sw2d_fused_rows_per_band(int W, int H, bool temp, int tracer, bool wrap, int
 template <typename T> int sw2d_fused_cols(int W, int H, bool temp, int tracer, bool wrap, int members);
 // GCM_SW2D, single band, short bands (small grids): TWO steps in one launch; false if not applicable
 template <typename T> bool launch_sw2d_fused2(const Sw2dArgsT<T> &a, hipStream_t s);
+// float64 GCM_SW2D_TEMP, periodic single domain, one member: TWO steps in one launch by a pair of waves per tile, the
+// first step's rows handed over in LDS (T = double only); a.rows_per_band is the pair's own band length, which
+// sw2d_pair_rows_per_band chooses: one resident round of workgroups, or GCM_SW2D_PAIR_ROWS.  false: refused
+template <typename T> bool launch_sw2d_pair(const Sw2dArgsT<T> &a, int tracer, bool stream, hipStream_t s);
+template <typename T> int sw2d_pair_rows_per_band(int W, int H, int tracer, bool stream);
 // fp32 handles: float64 host arrays <-> the device state through a float64 staging buffer; M slabs of n elements,
 // `pitch` elements apart on the device and n apart in the staging buffer
 void launch_narrow(float *dst, long pitch, const double *src, long n, int M, hipStream_t s);

@@ -29,6 +29,9 @@ void build_exner_table(double *tab) {
 }
 
 GCM_SW2D_INSTANTIATE(double)
+// the wave pair: float64 only
+template bool launch_sw2d_pair<double>(const Sw2dArgsT<double> &, int, bool, hipStream_t);
+template int sw2d_pair_rows_per_band<double>(int, int, int, bool);
 
 __global__ void seg_copy_kernel(SegCopy c) {
     const int seg = blockIdx.y;

@@ -184,6 +184,16 @@ int gcm_sw2d_plan(gcm_handle *h, int nsteps, int *out, int nout);
  * handle ignores the switch.  0: the staged variant.  A GCM_PE25D handle or a null pointer: GCM_ERR_ARG.         */
 int gcm_sw2d_fused_depth(gcm_handle *h);
 
+/* The wave pair of float64 GCM_SW2D_TEMP (fused, one member, a periodic single domain): two steps per launch, which
+ * gcm_sw2d_plan reports through its words [5] and [6].  out (nout >= GCM_SW2D_PAIR_WORDS words):
+ *   [0] 1: a gcm_step call of two or more steps goes through it (GCM_SW2D_PAIR = 0 | 1, read by gcm_create, pins it
+ *       at any size; unset: the library's default for grids whose launches stream), 0: it does not
+ *   [1] its own band length in rows (one resident round of workgroups, or GCM_SW2D_PAIR_ROWS, read by gcm_create);
+ *       0: a handle the pair never serves
+ * A GCM_PE25D handle, a null pointer or nout too small: GCM_ERR_ARG.                                            */
+#define GCM_SW2D_PAIR_WORDS 2
+int gcm_sw2d_pair_info(gcm_handle *h, int *out, int nout);
+
 /* The launch geometry of the GCM_PE25D phases whose grid depends on the rows of the launch, the row length and the
  * chip's compute units, without launching anything: a read-only query for tests and tools, taken from the helpers the
  * launchers use themselves.  gcm_pe25d_phase_geometry needs no handle and no device: a launch over `rows` rows of W
